@@ -7,7 +7,7 @@ Workload at every N: each rank holds its own 4-column x 2^22-row synthetic trace
 998244353 has no 2^25 domain -- SURVEY F2/H1).  One step = the batched low-degree extension of
 that trace: 4 inverse NTTs of 2^22 points + 4 coset NTTs of 2^25 points.  Columns are independent
 units, so ranks share no data-path collective (weak scaling); value = NTT points transformed by
-all ranks per second.  Reported beside it in the same JSON line:
+all ranks per second.  A plain run measures only that; with --full the same JSON line also reports:
   * roofline    -- the dominant kernel's achieved HBM GB/s from HIP events around every launch
                    in the timed region (algorithmic bytes: 8 B per point per pass), and
                    the same launch as a pure copy with the pass's access pattern (pattern_copy);
@@ -18,6 +18,7 @@ all ranks per second.  Reported beside it in the same JSON line:
   * ntt_2p20    -- BASELINE configs[1]: 2^20-point forward+inverse on the reference prime;
                    cfg3_2p20x4_blowup8: configs[2], LDE + Merkle commit of a 2^20 x 4 trace on it;
   * four_step   -- (N > 1) one 2^26-point NTT sharded over the N GPUs with the RCCL all-to-all.
+--dump-outputs DIR writes a seeded sample of the last timed step's extension (float64 .npy) for comparing builds.
 """
 import argparse
 import json
@@ -205,20 +206,55 @@ def hash_roofline(kernels, ceiling_mix_per_s, stage_ms, n_leaves, n_trees, pmc_n
     return out
 
 
+DUMP_ROWS, DUMP_SEED = 1 << 20, 0x5354524B   # --dump-outputs: 2^20 of the 2^25 extended rows, 40 MB in all
+
+
+def dump_outputs(dirname, lde, rank=0):
+    """What the timed step hands its caller -- the extended trace, (N_COLS, N) u32 residues on the device -- as float64
+    .npy files (exact: every residue is below 2^29): the same seeded sample of rows of every column (the first and last
+    row always among them), the row indices, and per column the sums of the low and high 16 bits of every residue
+    (exact in float64, they cover the rows outside the sample).  Rank r > 0 adds the suffix _rank<r>."""
+    import torch
+    n_rows = lde.shape[1]
+    rows = np.random.default_rng(DUMP_SEED).choice(n_rows - 2, DUMP_ROWS - 2, replace=False) + 1
+    rows = np.sort(np.concatenate([[0, n_rows - 1], rows]))
+    sample = lde[:, torch.from_numpy(rows).to(lde.device)].cpu().numpy().view(np.uint32).astype(np.float64)
+    sums = np.zeros((lde.shape[0], 2), dtype=np.float64)
+    for c in range(lde.shape[0]):
+        col = lde[c].to(torch.int64)
+        sums[c] = [float((col & 0xFFFF).sum().item()), float((col >> 16).sum().item())]
+    sfx = f"_rank{rank}" if rank else ""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"lde_sample{sfx}.npy"), sample)
+    np.save(os.path.join(dirname, f"lde_sample_rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, f"lde_column_sums{sfx}.npy"), sums)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # Defaults: a timed region of more than a second.  A 20-step region (15 ms) from an idle GPU is over before the chip has
     # settled -- measured r03: 0.783 ms per step over 20 steps after 3 warm-ups, 0.697 ms over 1 500 back-to-back steps -- so
     # the headline is the sustained figure (whatever --steps / --warmup are: see `preconditioning` below) and the cold
-    # burst is reported beside it (`burst`); with a short --steps the line also carries `sustained` (>= 1 s of steps).
+    # burst is reported beside it with --full (`burst`), as is `sustained` (>= 1 s of steps) after a short --steps.
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--no-extras", action="store_true", help="skip prove / 2^20 / four-step / cpu legs")
+    # A plain run measures the headline only: set-up, pre-conditioning, W warm-up steps, K timed steps, the result line.
+    # Every other leg (burst, sustained, roofline and copy-only twins, prove, 2^20 configs, multi-GPU legs, CPU baseline)
+    # runs with --full.
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: burst, sustained, roofline, prove, 2^20 configs, "
+                         "multi-GPU legs and the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip prove / 2^20 / four-step / cpu legs")
     ap.add_argument("--in-loop-only", action="store_true",
-                    help="roofline leg: skip the pass that brackets every launch and the copy-only twins, so that a profiler "
-                         "attached to this run sees the kernels only as they run in the loop (tools/profile.sh)")
+                    help="skip the pre-conditioning, and with --full the burst, the sustained figure, the pass that brackets "
+                         "every launch and the copy-only twins, so that a profiler attached to this run sees the kernels "
+                         "only as they run in the loop (tools/profile.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the last step's extension as DIR/*.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` (N > 1) outside a launcher: start one rank per GPU ourselves, as a
     # child process, BEFORE anything in this process touches the GPU (no exec after HIP init), and
@@ -234,10 +270,14 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
                "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        if args.full:
+            cmd.append("--full")
         if args.no_extras:
             cmd.append("--no-extras")
         if args.in_loop_only:
             cmd.append("--in-loop-only")
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         sys.exit(subprocess.call(cmd, env=env))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
@@ -290,7 +330,7 @@ def main():
     # burst: what rounds 1 and 2 reported as the headline -- 20 steps after 3 warm-up steps on a GPU that was idle until
     # then (clocks still ramping); kept for continuity, never the headline
     burst = None
-    if not args.in_loop_only:
+    if args.full and not args.in_loop_only:
         for _ in range(3):
             step()
         torch.cuda.synchronize()
@@ -303,7 +343,7 @@ def main():
     # holds its clocks (profiles/r03_b_lde_warmup_trend.txt: the first 50 steps average 737 us, every later bucket 680-688),
     # and the driver calls this script with --steps 20 --warmup 5, i.e. a 15 ms region inside that transient.  So the same
     # step runs untimed for a quarter of a second BEFORE the contract's W warm-up steps: the K timed steps then measure the
-    # state a prover that is busy actually runs in, whatever W and K are.  The cold figure stays in the line (`burst`).
+    # state a prover that is busy actually runs in, whatever W and K are.  The cold figure is `burst` (with --full).
     precond = None
     if not args.in_loop_only:
         tpc = time.perf_counter()
@@ -314,7 +354,7 @@ def main():
             torch.cuda.synchronize()
             n_pc += 50
         precond = {"steps": n_pc, "seconds": time.perf_counter() - tpc,
-                   "note": "untimed, before the W warm-up steps: brings the GPU from idle to its sustained clocks; `burst` is the cold figure"}
+                   "note": "untimed, before the W warm-up steps: brings the GPU from idle to its sustained clocks; `burst` (--full) is the cold figure"}
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -331,6 +371,28 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out.view(N_COLS, N), rank)
+
+    points_per_step = N_COLS * (n + N)                      # transform sizes summed over the batch
+    value = world * points_per_step * args.steps / elapsed
+    result = {
+        "metric": "ntt_field_elements_per_sec", "value": value, "unit": "field-elements/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": "lde_2^22rows_x4cols_blowup8 (4 iNTT 2^22 + 4 coset NTT 2^25 per GPU per step)",
+                   "prime": p, "points_per_step_per_gpu": points_per_step, "parallelism": f"columns x{world} (no collective)"},
+    }
+    if not args.full:
+        if precond is not None:
+            result["preconditioning"] = precond
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        eng.close()
+        if distributed:
+            dist.destroy_process_group()
+        return
+
     # sustained: when the caller asked for a short region (--steps below ~1 s of work), also time at least a second of
     # back-to-back steps, the same way, and report it beside the headline
     sustained = None
@@ -364,9 +426,6 @@ def main():
     torch.cuda.synchronize()
     kernels = eng.profile_read()
     eng.profile(False)
-
-    points_per_step = N_COLS * (n + N)                      # transform sizes summed over the batch
-    value = world * points_per_step * args.steps / elapsed
 
     # roofline of the dominant kernel (largest total time in the timed region).  An event pair around a launch perturbs
     # what it measures: the kernel no longer runs back to back with its neighbours and the chip clocks higher (DESIGN.md
@@ -475,14 +534,7 @@ def main():
                                 "GBps": v["alg_bytes"] / (v["total_ms"] * 1e-3) / 1e9,
                                 "copy_only_ms": probe_ms.get(k)} for k, v in kernels.items()}}
 
-    result = {
-        "metric": "ntt_field_elements_per_sec", "value": value, "unit": "field-elements/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": "lde_2^22rows_x4cols_blowup8 (4 iNTT 2^22 + 4 coset NTT 2^25 per GPU per step)",
-                   "prime": p, "points_per_step_per_gpu": points_per_step, "parallelism": f"columns x{world} (no collective)"},
-        "roofline": roofline,
-    }
+    result["roofline"] = roofline
     if sustained is not None:
         result["sustained"] = sustained
     if burst is not None:

@@ -1,5 +1,6 @@
 """CPU: the host-side arithmetic of bench.py that needs no GPU -- the prove's roofline block from per-kernel records,
-the launcher's refusal to mislabel a run, and the synthetic-input generator against the oracle's."""
+the launcher's refusal to mislabel a run, its options, --dump-outputs on a host tensor, and the synthetic-input
+generator against the oracle's.  One GPU test: a plain run's line and dump against the oracle."""
 import importlib.util
 import json
 import os
@@ -7,6 +8,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -56,3 +58,64 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"],
                          env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "refusing to mislabel" in out.stderr
+
+
+def test_bench_rejects_a_step_count_below_one():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+def test_bench_offers_full_and_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_writes_a_fixed_exact_sample(tmp_path, monkeypatch):
+    """--dump-outputs on a host tensor: the same seeded rows every time (first and last included), float64 values equal to
+    the u32 residues, exact per-column bit sums, rank suffixes, well under the 64 MB budget at the real size."""
+    import torch
+    b = _bench()
+    assert (b.N_COLS + 1) * b.DUMP_ROWS * 8 + b.N_COLS * 2 * 8 <= 64 << 20       # sample + rows + sums, float64
+    monkeypatch.setattr(b, "DUMP_ROWS", 64)
+    n = 1 << 12
+    host = (b.splitmix64(7, 4 * n) % np.uint64(469762049)).astype(np.uint32).reshape(4, n)
+    lde = torch.from_numpy(host.view(np.int32))
+    b.dump_outputs(str(tmp_path / "a"), lde)
+    b.dump_outputs(str(tmp_path / "b"), lde, rank=1)
+    rows = np.load(tmp_path / "a" / "lde_sample_rows.npy")
+    sample = np.load(tmp_path / "a" / "lde_sample.npy")
+    sums = np.load(tmp_path / "a" / "lde_column_sums.npy")
+    assert rows.dtype == sample.dtype == sums.dtype == np.float64
+    r = rows.astype(np.int64)
+    assert len(r) == 64 and len(np.unique(r)) == 64 and r[0] == 0 and r[-1] == n - 1 and np.all(np.diff(r) > 0)
+    assert np.array_equal(sample, host[:, r].astype(np.float64))
+    h = host.astype(np.int64)
+    assert np.array_equal(sums, np.stack([(h & 0xFFFF).sum(1), (h >> 16).sum(1)], 1).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "lde_sample_rows_rank1.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "b" / "lde_sample_rank1.npy"), sample)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_and_dumps_the_extension(oracle, tmp_path):
+    """A plain run: the headline keys, K timed steps, none of the --full legs; its dump is the oracle's extension of the
+    synthetic trace (column 0 at the sampled rows) and its column sums."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads(out.stdout.strip().splitlines()[-1])
+    assert r["metric"] == "ntt_field_elements_per_sec" and r["unit"] == "field-elements/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "u32" and r["steps"] == 7 and r["warmup"] == 2 and r["ms_per_step"] > 0
+    assert abs(r["value"] - r["config"]["points_per_step_per_gpu"] / (r["ms_per_step"] * 1e-3)) <= 1e-9 * r["value"]
+    assert not {"roofline", "burst", "sustained", "prove_ms", "cpu_baseline"} & set(r)
+    o = oracle
+    P2, G2, logn, lb = 469762049, 3, 22, 3
+    n, N = 1 << logn, 1 << (logn + lb)
+    col0 = o.splitmix64(0x5354524B00, n) % np.uint64(P2)
+    lde0 = o.fast_coset_ntt(o.fast_intt(col0, o.ff_prim_nth_root_g(n, P2, G2), 1, P2), N, o.ff_prim_nth_root_g(N, P2, G2), G2, P2)
+    rows = np.load(tmp_path / "lde_sample_rows.npy").astype(np.int64)
+    sample = np.load(tmp_path / "lde_sample.npy")
+    assert sample.shape == (4, len(rows)) and np.array_equal(sample[0], lde0[rows].astype(np.float64))
+    sums = np.load(tmp_path / "lde_column_sums.npy")
+    l0 = lde0.astype(np.int64)
+    assert sums[0, 0] == float((l0 & 0xFFFF).sum()) and sums[0, 1] == float((l0 >> 16).sum())

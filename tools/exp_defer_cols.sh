@@ -4,7 +4,7 @@
 # per-thread input multipliers derived once for the columns of a tile (SMI_NTT_TWIN_REGS=1) or re-derived as running
 # products per column.   bash tools/exp_defer_cols.sh
 set -e
-B="python3 bench.py --no-extras --steps 20 --warmup 3"
+B="python3 bench.py --full --no-extras --steps 20 --warmup 3"
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

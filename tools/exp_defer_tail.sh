@@ -1,4 +1,4 @@
-run() { python bench.py --steps 10 2>/dev/null | python -c "
+run() { python bench.py --full --steps 10 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('   ms_per_step %.4f'%r['ms_per_step'], 'prove', round(r.get('prove_ms',0),3), r.get('prove_stage_ms'))

@@ -2,7 +2,7 @@
 # Development tool (GPU box): the last pass's first radix-16 step on its load registers (SMI_NTT_LAST_DIRECT=1,
 # NTT_LAST_DIRECT) against the transposition through LDS; kernel times with their copy-only twins.
 set -e
-B="python3 bench.py --no-extras --steps 20 --warmup 3"
+B="python3 bench.py --full --no-extras --steps 20 --warmup 3"
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Development tool (GPU box): the middle pass with the next column's loads issued under the current column's stores
 # (tuning builds -DSMI_COLS_PREFETCH=1 kept as stark_rs_amd/build/libstarkmi_pf.so / _pfmq0.so) against the default.
-B="python3 bench.py --no-extras --steps 1000 --warmup 200"
+B="python3 bench.py --full --no-extras --steps 1000 --warmup 200"
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

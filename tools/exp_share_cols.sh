@@ -3,7 +3,7 @@
 # (tile, column), and register-bounded tuning builds (stark_rs_amd/build/libstarkmi_<tag>.so, SMI_LIB).
 #   bash tools/exp_share_cols.sh [tags...]
 set -e
-B="python3 bench.py --no-extras --steps 20 --warmup 3"
+B="python3 bench.py --full --no-extras --steps 20 --warmup 3"
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

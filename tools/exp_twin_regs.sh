@@ -1,4 +1,4 @@
-B="python3 bench.py --no-extras --steps 1000 --warmup 200"
+B="python3 bench.py --full --no-extras --steps 1000 --warmup 200"
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

@@ -3,7 +3,7 @@
 # copy-only twins (in parentheses), with the generic path of the same box first.
 #   bash tools/lde_layout_sweep.sh "2 3" "3 2" ...      (pairs "geo_rq lay_kq"; default: all valid pairs)
 run() {
-  python bench.py --no-extras --steps 10 --warmup 2 2>/dev/null | python -c "
+  python bench.py --full --no-extras --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=r['roofline']['kernels']

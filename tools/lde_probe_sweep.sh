@@ -3,7 +3,7 @@
 # variants (SMI_LDE_DBG knobs of csrc/lde_core.h), with the generic three-pass kernels of the same box
 # first for reference.
 run() {
-  python bench.py --no-extras --steps 5 --warmup 2 2>/dev/null | python -c "
+  python bench.py --full --no-extras --steps 5 --warmup 2 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('   ms_per_step %.4f'%r['ms_per_step'])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Development tool (GPU box): plan shapes of the extension's transforms on the headline step (bench.py --no-extras),
 # with the column-sharing / deferred-twiddle pass kernels.   bash tools/plans_sweep2.sh
-B="python3 bench.py --no-extras --steps 800 --warmup 200"   # sustained regime (r03): the 20-step burst mostly measures the clock ramp
+B="python3 bench.py --full --no-extras --steps 800 --warmup 200"   # sustained regime (r03): the 20-step burst mostly measures the clock ramp
 show() { python3 -c "
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=r['roofline']['kernels']

@@ -144,8 +144,11 @@ extern "C" {
     pub fn smi_fri_num_rounds(cfg: *const smi_fri_cfg, rounds: *mut u64) -> c_int;
     pub fn smi_fri_fold(ctx: *mut smi_ctx, codeword: *const u64, len: usize, alpha: u64, offset: u64, omega: u64, out: *mut u64) -> c_int;
     pub fn smi_fri_commit(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, codeword: *const u64, len: usize, roots: *mut u8, alphas: *mut u64, last_codeword: *mut u64, last_len: *mut usize, run: *mut *mut smi_fri_run) -> c_int;
+    pub fn smi_fri_commit_fs(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, codeword: *const u64, len: usize, roots: *mut u8, alphas: *mut u64, last_codeword: *mut u64, last_len: *mut usize, run: *mut *mut smi_fri_run) -> c_int;
     pub fn smi_fri_prove(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, codeword: *const u64, len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64) -> c_int;
+    pub fn smi_fri_prove_fs(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, codeword: *const u64, len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64) -> c_int;
     pub fn smi_fri_verify(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize) -> c_int;
+    pub fn smi_fri_verify_fs(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize) -> c_int;
     pub fn smi_fri_run_num_codewords(run: *const smi_fri_run, n: *mut usize) -> c_int;
     pub fn smi_fri_run_codeword(run: *mut smi_fri_run, round: usize, out: *mut u64, len: *mut usize) -> c_int;
     pub fn smi_fri_run_open(run: *mut smi_fri_run, round: usize, index: usize, path: *mut u8, depth: *mut usize) -> c_int;
@@ -165,6 +168,7 @@ extern "C" {
     pub fn smi_dev_fri_fold(ctx: *mut smi_ctx, d_in: *const u32, len: usize, d_alpha: *const u64, offset: u64, omega: u64, d_out: *mut u32) -> c_int;
     pub fn smi_dev_fri_fold_shard(ctx: *mut smi_ctx, d_lo: *const u32, d_hi: *const u32, count: usize, index0: usize, full_len: usize, d_alpha: *const u64, offset: u64, omega: u64, d_out: *mut u32) -> c_int;
     pub fn smi_dev_fri_prove(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, d_codeword: *const u32, len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, run: *mut *mut smi_fri_run) -> c_int;
+    pub fn smi_dev_fri_prove_fs(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_codeword: *const u32, len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, run: *mut *mut smi_fri_run) -> c_int;
     pub fn smi_dev_combine_columns(ctx: *mut smi_ctx, d_cols: *const u32, n_cols: u32, len: usize, stride: usize, d_weights: *const u64, d_out: *mut u32) -> c_int;
     pub fn smi_dev_stark_prove(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, d_trace_cols: *const u32, column_roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
     pub fn smi_stark_verify(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, column_roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
@@ -175,6 +179,8 @@ extern "C" {
     pub fn smi_mgpu_set_min_block(m: *mut smi_mgpu, min_block: usize) -> c_int;
     pub fn smi_mgpu_fri_commit(m: *mut smi_mgpu, cfg: *const smi_fri_cfg, d_block: *const u32, block_len: usize, roots: *mut u8, alphas: *mut u64, last_codeword: *mut u64, last_len: *mut usize) -> c_int;
     pub fn smi_mgpu_fri_prove(m: *mut smi_mgpu, cfg: *const smi_fri_cfg, d_block: *const u32, block_len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64) -> c_int;
+    pub fn smi_mgpu_fri_commit_fs(m: *mut smi_mgpu, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_block: *const u32, block_len: usize, roots: *mut u8, alphas: *mut u64, last_codeword: *mut u64, last_len: *mut usize) -> c_int;
+    pub fn smi_mgpu_fri_prove_fs(m: *mut smi_mgpu, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_block: *const u32, block_len: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64) -> c_int;
     pub fn smi_mgpu_lde(m: *mut smi_mgpu, d_trace_cols: *const u32, n_cols: u32, log_n: u32, log_blowup: u32, trace_offset: u64, lde_offset: u64, d_out_blocks: *mut u32) -> c_int;
     pub fn smi_mgpu_ntt(m: *mut smi_mgpu, d_strip: *mut u32, d_out: *mut u32, log_n: u32, inverse: c_int, offset: u64) -> c_int;
     pub fn smi_mgpu_ntt_natural(m: *mut smi_mgpu, d_strip: *mut u32, d_out: *mut u32, log_n: u32, inverse: c_int, offset: u64) -> c_int;
@@ -434,6 +440,92 @@ pub fn fri_verify(ctx: &Context, cfg: &smi_fri_cfg, proof: &[u8]) -> Result<(boo
     }
     ctx.check(st);
     Ok((accept != 0, (0..n).map(|i| (idx[i] as usize, val[i])).collect()))
+}
+
+/// The roots at the head of `objs` (serialized MerkleRoot objects, at most the cfg's round count) appended to the
+/// caller's transcript: what `fiat_shamir.absorb(&root.0)` leaves behind in `Fri::commit` / `Fri::verify`
+/// (src/fri.rs:131, :328), in both cases for every root it got to.
+fn absorb_roots(cfg: &smi_fri_cfg, objs: &[u8], transcript: &mut Vec<u8>) {
+    let mut rounds = 0u64;
+    check(unsafe { smi_fri_num_rounds(cfg, &mut rounds) });
+    for k in 0..rounds as usize {
+        let at = 33 * k;
+        if objs.len() < at + 33 || objs[at] != 0 {
+            break;
+        }
+        transcript.extend_from_slice(&objs[at + 1..at + 33]);
+    }
+}
+
+/// `Fri::commit(codeword, proof_stream, fiat_shamir)` (src/fri.rs:105-156) continuing the caller's objects:
+/// `transcript` is `fiat_shamir.transcript`, `stream` the caller's `ProofStream::serialize()` bytes so far.  Appends
+/// the roots and the last codeword to `stream`, absorbs the roots into `transcript`, and returns (roots, the R-1
+/// unreduced challenges, the last codeword).
+pub fn fri_commit_with(ctx: &Context, cfg: &smi_fri_cfg, codeword: &[u64], transcript: &mut Vec<u8>, stream: &mut Vec<u8>)
+                       -> (Vec<[u8; 32]>, Vec<u64>, Vec<u64>) {
+    let mut rounds = 0u64;
+    check(unsafe { smi_fri_num_rounds(cfg, &mut rounds) });
+    let r = (rounds as usize).max(1);
+    let (mut roots, mut alphas, mut last) = (vec![0u8; 32 * r], vec![0u64; r], vec![0u64; codeword.len()]);
+    let mut last_len = 0usize;
+    ctx.check(unsafe {
+        smi_fri_commit_fs(ctx.raw, cfg, transcript.as_ptr(), transcript.len(), codeword.as_ptr(), codeword.len(), roots.as_mut_ptr(),
+                          alphas.as_mut_ptr(), last.as_mut_ptr(), &mut last_len, std::ptr::null_mut())
+    });
+    let roots: Vec<[u8; 32]> = (0..rounds as usize).map(|k| roots[32 * k..32 * k + 32].try_into().unwrap()).collect();
+    last.truncate(last_len);
+    for root in &roots {                                                    // src/fri.rs:129-131, src/stream.rs:39-42
+        stream.push(0);
+        stream.extend_from_slice(root);
+        transcript.extend_from_slice(root);
+    }
+    stream.push(2);                                                         // src/fri.rs:151, src/stream.rs:48-53
+    stream.extend_from_slice(&(last.len() as u64).to_le_bytes());
+    for v in &last {
+        stream.extend_from_slice(&v.to_le_bytes());
+    }
+    alphas.truncate((rounds as usize).saturating_sub(1));
+    (roots, alphas, last)
+}
+
+/// `Fri::prove(codeword, fiat_shamir, proof_stream)` (src/fri.rs:250-311) continuing the caller's objects: `transcript`
+/// and `stream` as in `fri_commit_with`.  Appends the objects Fri::prove pushes to `stream`, absorbs the roots into
+/// `transcript` and returns the top-level indices.
+pub fn fri_prove_with(ctx: &Context, cfg: &smi_fri_cfg, codeword: &[u64], transcript: &mut Vec<u8>, stream: &mut Vec<u8>) -> Vec<usize> {
+    let mut proof: *mut u8 = std::ptr::null_mut();
+    let mut len = 0usize;
+    let mut top = vec![0u64; (cfg.num_colinearity_tests as usize).max(1)];
+    ctx.check(unsafe {
+        smi_fri_prove_fs(ctx.raw, cfg, transcript.as_ptr(), transcript.len(), codeword.as_ptr(), codeword.len(), &mut proof, &mut len,
+                         top.as_mut_ptr())
+    });
+    let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+    unsafe { smi_free(proof as *mut c_void) };
+    absorb_roots(cfg, &bytes, transcript);
+    stream.extend_from_slice(&bytes);
+    top.truncate(cfg.num_colinearity_tests as usize);
+    top.into_iter().map(|v| v as usize).collect()
+}
+
+/// `Fri::verify(proof_stream, fiat_shamir, polynomial_values)` (src/fri.rs:313-504) continuing the caller's objects:
+/// `transcript` is `fiat_shamir.transcript`, `stream` the serialized objects still to be popped.  Absorbs the roots it
+/// pops into `transcript` and returns (verdict, the (index, value) pairs, the bytes of the objects it popped -- on
+/// acceptance; the caller goes on from there).  `Err(())` as in `fri_verify`.
+pub fn fri_verify_with(ctx: &Context, cfg: &smi_fri_cfg, transcript: &mut Vec<u8>, stream: &[u8])
+                       -> Result<(bool, Vec<(usize, u64)>, usize), ()> {
+    let t = cfg.num_colinearity_tests as usize;
+    let (mut idx, mut val) = (vec![0u64; 2 * t + 2], vec![0u64; 2 * t + 2]);
+    let (mut accept, mut n, mut consumed) = (0 as c_int, 0usize, 0usize);
+    let st = unsafe {
+        smi_fri_verify_fs(ctx.raw, cfg, transcript.as_ptr(), transcript.len(), stream.as_ptr(), stream.len(), &mut accept, idx.as_mut_ptr(),
+                          val.as_mut_ptr(), &mut n, &mut consumed)
+    };
+    if st == SMI_ERR_NOT_GEOMETRIC {
+        return Err(());
+    }
+    ctx.check(st);
+    absorb_roots(cfg, stream, transcript);
+    Ok((accept != 0, (0..n).map(|i| (idx[i] as usize, val[i])).collect(), consumed))
 }
 
 /// `Trace::to_field_elements` for all columns at once: row-major i128 rows (`Vec<Vec<i128>>` flattened) to

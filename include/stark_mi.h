@@ -213,11 +213,24 @@ int smi_fri_fold(smi_ctx *ctx, const uint64_t *codeword, size_t len, uint64_t al
  * keeps every round's codeword and tree on the device (smi_fri_run_* accessors below). */
 int smi_fri_commit(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t *roots,
                    uint64_t *alphas, uint64_t *last_codeword, size_t *last_len, smi_fri_run **run);
+/* Fri::commit (src/fri.rs:105-156) with the caller's `&mut FiatShamir`: transcript / transcript_len are the bytes its
+ * `transcript` holds before the call (host memory; NULL with 0 is a fresh FiatShamir, NULL with a length is
+ * SMI_ERR_BAD_ARG).  Each root is absorbed after them (src/fri.rs:131) and every challenge hashes the whole transcript
+ * (src/fiat_shamir.rs:19-25).  The roots are what Fri::commit pushes after the caller's objects; the transcript itself
+ * is not written: the caller appends the R roots to it, as the reference leaves it.  Outputs as smi_fri_commit. */
+int smi_fri_commit_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint64_t *codeword,
+                      size_t len, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len, smi_fri_run **run);
 /* Fri::prove (src/fri.rs:250-311) with a fresh FiatShamir and ProofStream, returning
  * ProofStream::serialize (src/stream.rs:35-64).  *proof is malloc'd: release with smi_free.
  * top_indices gets num_colinearity_tests entries (the method's return value). */
 int smi_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t **proof,
                   size_t *proof_len, uint64_t *top_indices);
+/* Fri::prove (src/fri.rs:250-311) with the caller's `&mut FiatShamir` and `&mut ProofStream`: transcript as in
+ * smi_fri_commit_fs (host memory).  *proof is the serialization of the objects Fri::prove pushes AFTER the caller's
+ * own (the caller's stream is unchanged by them); the caller then absorbs the R roots, as the reference leaves its
+ * transcript.  Outputs as smi_fri_prove. */
+int smi_fri_prove_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint64_t *codeword,
+                     size_t len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices);
 /* The `codewords` Fri::commit returns (src/fri.rs:153-155): their count, one of them (out may be
  * NULL to query *len), and MerkleTree::open on a round's retained tree. */
 /* Fri::verify (src/fri.rs:313-504) of a serialized ProofStream against a fresh FiatShamir: *accept = 1 where the
@@ -236,6 +249,13 @@ int smi_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword
  *     there), and the leaf is hashed from the raw u64, as in the reference. */
 int smi_fri_verify(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *proof, size_t proof_len, int *accept, uint64_t *pv_indices,
                    uint64_t *pv_values, size_t *n_pv);
+/* Fri::verify (src/fri.rs:313-504) with the caller's `&mut FiatShamir` (transcript as in smi_fri_commit_fs, host memory)
+ * and `&mut ProofStream`: proof holds the objects still to be popped, starting with the ones Fri::prove pushed after
+ * the caller's objects.  *accept, pv_indices / pv_values / n_pv as in smi_fri_verify.  *consumed (optional): on
+ * acceptance the bytes of the objects Fri::verify popped, so a caller whose stream carries more objects goes on from
+ * proof + *consumed; 0 on rejection.  The caller absorbs the R roots, as the reference leaves its transcript. */
+int smi_fri_verify_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                      size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed);
 int smi_fri_run_num_codewords(const smi_fri_run *run, size_t *n);
 int smi_fri_run_codeword(smi_fri_run *run, size_t round, uint64_t *out, size_t *len);
 int smi_fri_run_open(smi_fri_run *run, size_t round, size_t index, uint8_t *path, size_t *depth);
@@ -289,6 +309,11 @@ int smi_dev_fri_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d
  * index sampling run in single-lane device kernels. */
 int smi_dev_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, uint8_t **proof,
                       size_t *proof_len, uint64_t *top_indices, smi_fri_run **run);
+/* smi_dev_fri_prove continuing the caller's FiatShamir (Fri::prove, src/fri.rs:250-311, as smi_fri_prove_fs): the
+ * transcript is a HOST pointer (the reference's transcript is a host Vec<u8>; its state is computed on the host and
+ * passed to the first launch by value).  The proof is what Fri::prove pushes after the caller's objects. */
+int smi_dev_fri_prove_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                         size_t len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, smi_fri_run **run);
 
 /* out[i] = sum_c (weights[c] mod p) * cols[c*stride + i]; d_weights holds n_cols unreduced u64
  * challenges on the device (random linear combination of committed columns; build-defined,
@@ -368,6 +393,13 @@ int smi_mgpu_fri_commit(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_b
 /* Fri::prove: the serialized ProofStream (smi_free) and the top-level indices on every rank. */
 int smi_mgpu_fri_prove(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t **proof, size_t *proof_len,
                        uint64_t *top_indices);
+/* The same two continuing the caller's FiatShamir (Fri::commit / Fri::prove, src/fri.rs:105-156, 250-311, as
+ * smi_fri_commit_fs / smi_fri_prove_fs): transcript = host bytes, the same on every rank; the proof is what the
+ * method pushes after the caller's objects. */
+int smi_mgpu_fri_commit_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_block,
+                           size_t block_len, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len);
+int smi_mgpu_fri_prove_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_block,
+                          size_t block_len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices);
 /* The extension of smi_dev_lde sharded by (column, coset) units (n_cols << log_blowup and 2^log_n
  * multiples of the world size, log_blowup <= 4): d_trace_cols = the whole trace on every rank;
  * d_out_blocks gets this rank's natural-order block of every column (n_cols x N/G, stride N/G). */

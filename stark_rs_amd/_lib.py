@@ -132,6 +132,10 @@ def lib():
         "smi_fri_commit": (i32, [vp, C.POINTER(FriCfg), vp, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(vp)]),
         "smi_fri_prove": (i32, [vp, C.POINTER(FriCfg), vp, sz, C.POINTER(vp), C.POINTER(sz), vp]),
         "smi_fri_verify": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, C.POINTER(i32), vp, vp, C.POINTER(sz)]),
+        "smi_fri_commit_fs": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(vp)]),
+        "smi_fri_prove_fs": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), vp]),
+        "smi_fri_verify_fs": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32), vp, vp, C.POINTER(sz),
+                                    C.POINTER(sz)]),
         "smi_stark_verify": (i32, [vp, C.POINTER(StarkCfg), vp, C.c_char_p, sz, C.POINTER(i32)]),
         "smi_fri_run_num_codewords": (i32, [vp, C.POINTER(sz)]),
         "smi_fri_run_codeword": (i32, [vp, sz, vp, C.POINTER(sz)]),
@@ -151,6 +155,7 @@ def lib():
         "smi_dev_fri_fold": (i32, [vp, vp, sz, vp, C.c_uint64, C.c_uint64, vp]),
         "smi_dev_fri_fold_shard": (i32, [vp, vp, vp, sz, sz, sz, vp, C.c_uint64, C.c_uint64, vp]),
         "smi_dev_fri_prove": (i32, [vp, C.POINTER(FriCfg), vp, sz, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(vp)]),
+        "smi_dev_fri_prove_fs": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(vp)]),
         "smi_dev_combine_columns": (i32, [vp, vp, C.c_uint32, sz, sz, vp, vp]),
         "smi_dev_stark_prove": (i32, [vp, C.POINTER(StarkCfg), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
     }

@@ -506,6 +506,18 @@ extern "C" void emu_fs_round(uint32_t *fs_words, const uint8_t *root, uint64_t *
     memcpy(m, root, 32);
     hashc::fs_absorb_root(fs_words, m, nullptr, alpha);
 }
+// a caller's transcript as the prover continues it (hashc::fs_seed): 16 state words and the phase P mod 32
+extern "C" void emu_fs_seed(const uint8_t *transcript, size_t len, uint32_t *fs_words, uint32_t *phase) {
+    hashc::fs_seed(transcript, len, fs_words, phase);
+}
+// one root absorbed at that phase (hashc::fs_absorb_root_phase), the challenge after it to *alpha
+extern "C" void emu_fs_absorb_root_phase(uint32_t *fs_words, uint32_t phase, const uint8_t *root, uint64_t *alpha) {
+    uint32_t m[8];
+    memcpy(m, root, 32);
+    hashc::fs_absorb_root_phase(fs_words, m, phase, nullptr, alpha);
+}
+// FiatShamir::challenge at that phase (hashc::fs_challenge_phase)
+extern "C" uint64_t emu_fs_challenge_phase(const uint32_t *fs_words, uint32_t phase) { return hashc::fs_challenge_phase(fs_words, phase); }
 
 // rows of W residues, row-major in `v`: pairs through row_hash2 when W <= 4, the rest through row_hash
 extern "C" void emu_row_hash(const uint32_t *v, size_t n_rows, int W, uint8_t *out) {

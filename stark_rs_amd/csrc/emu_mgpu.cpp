@@ -90,17 +90,16 @@ struct EmuDev : MgDev {
     }
     int merkle_from_digests(size_t n, uint8_t *nodes) override { return upper_levels(n, nodes); }
 
-    size_t fs_bytes() const override { return 64; }
-    int fs_init(void *fsw) override {
-        hashc::State st;
-        hashc::init(st);
-        memcpy(fsw, st.s, 64);
+    size_t fs_bytes() const override { return 68; }   // 16 state words, then the phase
+    int fs_init(void *fsw, const uint32_t seed[16], uint32_t phase) override {
+        memcpy(fsw, seed, 64);
+        ((uint32_t *)fsw)[16] = phase;
         return SMI_OK;
     }
     int fs_round(void *fsw, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out) override {
         uint32_t m[8];
         memcpy(m, root, 32);
-        hashc::fs_absorb_root((uint32_t *)fsw, m, proof_slot, alpha_out);
+        hashc::fs_absorb_root_phase((uint32_t *)fsw, m, ((const uint32_t *)fsw)[16], proof_slot, alpha_out);
         return SMI_OK;
     }
     static uint64_t challenge_of(const hashc::State &at) {   // FiatShamir::challenge, src/fiat_shamir.rs:19-25
@@ -111,9 +110,7 @@ struct EmuDev : MgDev {
         return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
     }
     int fs_challenge(const void *fsw, uint64_t *out) override {
-        hashc::State st;
-        memcpy(st.s, fsw, 64);
-        *out = challenge_of(st);
+        *out = hashc::fs_challenge_phase((const uint32_t *)fsw, ((const uint32_t *)fsw)[16]);
         return SMI_OK;
     }
     int fs_weights(const uint8_t *const *root_ptrs, uint32_t n, uint64_t *weights, uint8_t *roots_out) override {
@@ -257,6 +254,33 @@ extern "C" int emu_mgpu_fri_prove(uint64_t p, uint64_t g, const smi_mgpu_coll *o
     if (top && !o.top.empty()) memcpy(top, o.top.data(), 8 * o.top.size());
     if (alphas && !o.alphas.empty()) memcpy(alphas, o.alphas.data(), 8 * o.alphas.size());
     return put_proof(o.proof, proof, cap, proof_len);
+}
+
+// the same loop continuing a caller's transcript (smi_mgpu_fri_prove_fs / smi_mgpu_fri_commit_fs)
+extern "C" int emu_mgpu_fri_prove_fs(uint64_t p, uint64_t g, const smi_mgpu_coll *ops, int rank, int world, const smi_fri_cfg *cfg,
+                                     const uint8_t *transcript, size_t transcript_len, const uint32_t *block, size_t block_len,
+                                     size_t min_block, uint8_t *proof, size_t cap, size_t *proof_len, uint64_t *top) {
+    EmuDev d(p, g);
+    EmuColl c(*ops);
+    MgFriOut o;
+    const int rc = mg_fri_run(d, c, rank, world, *cfg, block, block_len, min_block, true, o, transcript, transcript_len);
+    if (rc != SMI_OK) return rc;
+    if (top && !o.top.empty()) memcpy(top, o.top.data(), 8 * o.top.size());
+    return put_proof(o.proof, proof, cap, proof_len);
+}
+extern "C" int emu_mgpu_fri_commit_fs(uint64_t p, uint64_t g, const smi_mgpu_coll *ops, int rank, int world, const smi_fri_cfg *cfg,
+                                      const uint8_t *transcript, size_t transcript_len, const uint32_t *block, size_t block_len,
+                                      size_t min_block, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len) {
+    EmuDev d(p, g);
+    EmuColl c(*ops);
+    MgFriOut o;
+    const int rc = mg_fri_run(d, c, rank, world, *cfg, block, block_len, min_block, false, o, transcript, transcript_len);
+    if (rc != SMI_OK) return rc;
+    for (uint64_t r = 0; r < o.rounds; r++) memcpy(roots + 32 * r, o.proof.data() + 33 * r + 1, 32);
+    if (!o.alphas.empty()) memcpy(alphas, o.alphas.data(), 8 * o.alphas.size());
+    memcpy(last_codeword, o.proof.data() + 33 * o.rounds + 9, 8 * o.last_len);   // LE u64s, as the proof holds them
+    *last_len = o.last_len;
+    return SMI_OK;
 }
 
 extern "C" int emu_mgpu_stark_prove(uint64_t p, uint64_t g, const smi_mgpu_coll *ops, int rank, int world, const smi_stark_cfg *cfg,

@@ -36,18 +36,26 @@ __global__ __launch_bounds__(256) void fri_fold_kernel(const uint32_t *__restric
 // ever absorbed (src/fri.rs:131), so the sponge state after k roots is carried in
 // fs_state (16 words) and `challenge` = 8 more mixes on a copy: the same function of the
 // whole transcript as re-hashing it, evaluated incrementally.
+// A caller's transcript that is not whole 32-byte chunks leaves `phase` bytes pending (hash_core.h fs_seed); the phase
+// rides in the state so that the phase-aware kernels below read it with the words.
 struct FsState {
     uint32_t s[16];
+    uint32_t phase;
 };
 
+// the seed (the initial constants for a fresh transcript) arrives by value: it is computed on the host
 // (ride_*: a few bytes of the caller's -- the column roots of a prove -- placed behind the proof, to come back with its copy)
-__global__ void fs_init_kernel(FsState *fs, const uint8_t *ride_src = nullptr, uint8_t *ride_dst = nullptr, size_t ride_n = 0) {
+__global__ void fs_init_kernel(FsState *fs, FsSeed seed, const uint8_t *ride_src = nullptr, uint8_t *ride_dst = nullptr, size_t ride_n = 0) {
     if (blockIdx.x) return;
     for (size_t i = threadIdx.x; i < ride_n; i += blockDim.x) ride_dst[i] = ride_src[i];
     if (threadIdx.x) return;
-    hashc::State st;
-    hashc::init(st);
-    for (int i = 0; i < 16; i++) fs->s[i] = st.s[i];
+    for (int i = 0; i < 16; i++) fs->s[i] = seed.s[i];
+    fs->phase = seed.phase;
+}
+static FsSeed fresh_seed() {
+    FsSeed z;
+    hashc::fs_seed(nullptr, 0, z.s, &z.phase);
+    return z;
 }
 
 // absorb the root at `root`, append it (tag 0 + 32 bytes, src/stream.rs:39-42) to the proof
@@ -66,6 +74,19 @@ __global__ void fs_challenge_kernel(const FsState *fs, uint64_t *alpha_out) {
     const hashx::Lane row = hashx::make_lane(threadIdx.x);
     const uint64_t a = hashx::low_bytes_u64(hashx::fs_challenge(fs->s[threadIdx.x], row));
     if (threadIdx.x == 0) *alpha_out = a;
+}
+
+// The same two at a phase != 0 (hash_core.h fs_absorb_root_phase / fs_challenge_phase), one lane: the root straddles
+// two chunks there, which the sixteen-lane form does not cover.  Run once per round on a few hundred bytes of state.
+__global__ void fs_round_phase_kernel(FsState *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
+    if (threadIdx.x || blockIdx.x) return;
+    uint32_t m[8];
+    for (int j = 0; j < 8; j++) m[j] = root[j];
+    hashc::fs_absorb_root_phase(fs->s, m, fs->phase, proof_slot, alpha_out);
+}
+__global__ void fs_challenge_phase_kernel(const FsState *fs, uint64_t *alpha_out) {
+    if (threadIdx.x || blockIdx.x) return;
+    *alpha_out = hashc::fs_challenge_phase(fs->s, fs->phase);
 }
 
 // Fri::sample_indices (src/fri.rs:176-213) with seed = Hash::from_u64(challenge).0
@@ -233,18 +254,21 @@ __global__ void emit_codeword_kernel(const uint32_t *cw, uint64_t len, uint8_t *
 
 // launchers for the multi-GPU round loop (mgpu.hip), which sequences the same kernels
 size_t fri_fs_bytes() { return sizeof(FsState); }
-int launch_fs_init(smi_ctx *ctx, void *fs) {
-    fs_init_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs);
+// (seed == nullptr: a fresh transcript; phase: the seed's, which the caller keeps on the host to pick the kernels)
+int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed) {
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, seed ? *seed : fresh_seed());
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
-int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
-    fs_round_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, (const uint32_t *)root, proof_slot, alpha_out);
+int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase) {
+    if (phase) fs_round_phase_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, (const uint32_t *)root, proof_slot, alpha_out);
+    else fs_round_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, (const uint32_t *)root, proof_slot, alpha_out);
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
-int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out) {
-    fs_challenge_kernel<<<1, 64, 0, ctx->stream>>>((const FsState *)fs, out);
+int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out, uint32_t phase) {
+    if (phase) fs_challenge_phase_kernel<<<1, 64, 0, ctx->stream>>>((const FsState *)fs, out);
+    else fs_challenge_kernel<<<1, 64, 0, ctx->stream>>>((const FsState *)fs, out);
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
@@ -389,7 +413,7 @@ uint64_t fri_tail_len() {
 }
 int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
                    smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
-                   uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src) {
+                   uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src, const FsSeed *seed) {
     SMI_TRY(smi_fri_check(ctx, cfg));
     if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     const uint32_t p = ctx->fs.F.p;
@@ -457,7 +481,9 @@ int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, si
     uint64_t *d_reduced = (uint64_t *)(misc + ml.reduced);
     LayerInfo *d_layers = (LayerInfo *)(misc + ml.layers);
 
-    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, (const uint8_t *)ride_src, run->d_proof + off_ride, ride_bytes);
+    const FsSeed fs0 = seed ? *seed : fresh_seed();
+    const uint32_t phase = fs0.phase;
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, fs0, (const uint8_t *)ride_src, run->d_proof + off_ride, ride_bytes);
 
     uint32_t omega = (uint32_t)cfg->omega, offset = (uint32_t)cfg->offset;
     const uint32_t *cur = d_codeword;
@@ -470,6 +496,11 @@ int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, si
     // the per-round path spreads a tree's 64-leaf chunks over several CUs).  SMI_FRI_TAIL=<len> overrides
     // (0: never).
     const uint64_t tail_len = fri_tail_len();
+    // The fused tail runs the sixteen-lane Fiat-Shamir round, which knows phase 0 only.  Decided here once, for the loop
+    // head and for the fold-elision lookahead alike: a fold elided into a tail that then does not run would be lost.
+    auto tail_from = [&](uint64_t n, uint64_t round) { return phase == 0 && n <= tail_len && R - round <= SMI_FRI_TAIL_MAX_ROUNDS; };
+    // phase != 0: the merkle launches get no Fiat-Shamir hook (fs_words == nullptr), a phase-aware kernel follows each tree
+    uint32_t *const hook_fs = phase == 0 ? d_fs->s : nullptr;
     static const bool fold_in_tail = !(getenv("SMI_MERKLE_FUSE") && atoi(getenv("SMI_MERKLE_FUSE")) == 0);
     // The leaves of a round's tree can be computed by the launch that hashes them (LeafSrc, internal.h): the initial
     // codeword as the caller's weighted column sum (round0_src), every later one as the fold of the round before --
@@ -484,7 +515,7 @@ int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, si
         have_pending = true;
     }
     for (uint64_t r = 0; r < R; r++) {
-        if (cur_len <= tail_len && R - r <= SMI_FRI_TAIL_MAX_ROUNDS) {
+        if (tail_from(cur_len, r)) {
             // every remaining round in one workgroup launch (hash.hip, fri_tail_kernel)
             // the tail holds one x^-1 table per fold until its launch: none of them may be evicted in between
             if ((rc = ctx_scale_reserve(ctx, (size_t)(R - r))) != SMI_OK) return bail(rc);
@@ -539,19 +570,20 @@ int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, si
         // when that is the chunk kernel (one launch fewer per round), by a kernel of its own otherwise
         bool fs_done = false;
         if (have_pending) {
-            rc = launch_merkle_src_fs(ctx, pending, cur_len, nodes, d_fs->s, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
+            rc = launch_merkle_src_fs(ctx, pending, cur_len, nodes, hook_fs, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
             have_pending = false;
         } else {
-            rc = launch_merkle_fs(ctx, cur, cur_len, nodes, d_fs->s, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
+            rc = launch_merkle_fs(ctx, cur, cur_len, nodes, hook_fs, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
         }
         if (rc != SMI_OK) return bail(rc);
-        if (!fs_done)
-            fs_round_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, root, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r);
+        if (!fs_done && (rc = launch_fs_round(ctx, d_fs, (const uint8_t *)root, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r,
+                                              phase)) != SMI_OK)
+            return bail(rc);
         if (last) break;
         uint32_t *next = (uint32_t *)run_alloc(run, (cur_len / 2) * 4);
         if (!next) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc codeword"));
         const uint64_t next_len = cur_len / 2;
-        const bool next_is_tail = next_len <= tail_len && R - (r + 1) <= SMI_FRI_TAIL_MAX_ROUNDS;
+        const bool next_is_tail = tail_from(next_len, r + 1);
         // (the computed-leaf kernel reads and writes four elements at a time: 16-byte aligned buffers only -- the library's own
         // are, a caller's initial codeword need not be)
         const bool aligned16 = (((uintptr_t)cur | (uintptr_t)next) & 15u) == 0;
@@ -589,7 +621,7 @@ int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, si
     emit_codeword_kernel<<<(uint32_t)((cur_len + 255) / 256), 256, 0, ctx->stream>>>(cur, cur_len, run->d_proof + off_last);
 
     if (do_query) {
-        fs_challenge_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, d_seed_ch);
+        if ((rc = launch_fs_challenge(ctx, d_fs, d_seed_ch, phase)) != SMI_OK) return bail(rc);
         const uint64_t sample_size = R > 1 ? len / 2 : len;  // src/fri.rs:266-270
         sample_indices_kernel<<<1, 64, 0, ctx->stream>>>(d_seed_ch, sample_size, last_n, (uint32_t)t, d_top, d_reduced);
         if (R > 1 && t > 0) {
@@ -667,12 +699,21 @@ int smi_dev_fri_fold(smi_ctx *ctx, const uint32_t *d_in, size_t len, const uint6
     return launch_fold(ctx, d_in, len, d_alpha, offset, omega, d_out);
 }
 
-int smi_dev_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, uint8_t **proof,
-                      size_t *proof_len, uint64_t *top_indices, smi_fri_run **run) {
+// the caller's transcript (host bytes) as the device starts from it; (NULL, 0) is a fresh FiatShamir
+static int transcript_seed(const uint8_t *transcript, size_t transcript_len, FsSeed *seed) {
+    if (!transcript && transcript_len) return SMI_ERR_BAD_ARG;
+    hashc::fs_seed(transcript, transcript_len, seed->s, &seed->phase);
+    return SMI_OK;
+}
+
+int smi_dev_fri_prove_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                         size_t len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, smi_fri_run **run) {
     if (!ctx || !cfg || !d_codeword || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    FsSeed seed;
+    SMI_TRY(transcript_seed(transcript, transcript_len, &seed));
     DeviceGuard dg__(ctx);
     std::vector<uint8_t> bytes;
-    SMI_TRY(fri_run(ctx, cfg, d_codeword, len, true, true, run, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr, nullptr));
+    SMI_TRY(fri_run(ctx, cfg, d_codeword, len, true, true, run, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr, nullptr, &seed));
     *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
     if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
     memcpy(*proof, bytes.data(), bytes.size());
@@ -680,35 +721,47 @@ int smi_dev_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_co
     return SMI_OK;
 }
 
+int smi_dev_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, uint8_t **proof,
+                      size_t *proof_len, uint64_t *top_indices, smi_fri_run **run) {
+    return smi_dev_fri_prove_fs(ctx, cfg, nullptr, 0, d_codeword, len, proof, proof_len, top_indices, run);
+}
+
 static int upload_codeword(smi_ctx *ctx, const uint64_t *codeword, size_t len, uint32_t **d_cw) {
     if (hipMalloc((void **)d_cw, len * 4 ? len * 4 : 4) != hipSuccess) return smi_fail(ctx, SMI_ERR_OOM, "hipMalloc codeword");
     return host_to_dev_u32(ctx, codeword, len, *d_cw, 0);
 }
 
-int smi_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t **proof,
-                  size_t *proof_len, uint64_t *top_indices) {
-    if (!ctx || !cfg || !codeword || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+int smi_fri_prove_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint64_t *codeword,
+                     size_t len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices) {
+    if (!ctx || !cfg || !codeword || !proof || !proof_len || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     SMI_TRY(smi_fri_check(ctx, cfg));
     if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     uint32_t *d_cw = nullptr;
     int rc = upload_codeword(ctx, codeword, len, &d_cw);
-    if (rc == SMI_OK) rc = smi_dev_fri_prove(ctx, cfg, d_cw, len, proof, proof_len, top_indices, nullptr);
+    if (rc == SMI_OK) rc = smi_dev_fri_prove_fs(ctx, cfg, transcript, transcript_len, d_cw, len, proof, proof_len, top_indices, nullptr);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_cw);
     return rc;
 }
+int smi_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t **proof,
+                  size_t *proof_len, uint64_t *top_indices) {
+    return smi_fri_prove_fs(ctx, cfg, nullptr, 0, codeword, len, proof, proof_len, top_indices);
+}
 
-int smi_fri_commit(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t *roots,
-                   uint64_t *alphas, uint64_t *last_codeword, size_t *last_len, smi_fri_run **run) {
+int smi_fri_commit_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint64_t *codeword,
+                      size_t len, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len, smi_fri_run **run) {
     if (!ctx || !cfg || !codeword) return SMI_ERR_BAD_ARG;
+    FsSeed seed;
+    SMI_TRY(transcript_seed(transcript, transcript_len, &seed));
     DeviceGuard dg__(ctx);
     SMI_TRY(smi_fri_check(ctx, cfg));
     if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     uint32_t *d_cw = nullptr;
     int rc = upload_codeword(ctx, codeword, len, &d_cw);
     smi_fri_run *r = nullptr;
-    if (rc == SMI_OK) rc = fri_run(ctx, cfg, d_cw, len, false, true, run ? &r : nullptr, nullptr, nullptr, roots, alphas, last_codeword, last_len, nullptr);
+    if (rc == SMI_OK) rc = fri_run(ctx, cfg, d_cw, len, false, true, run ? &r : nullptr, nullptr, nullptr, roots, alphas, last_codeword, last_len, nullptr,
+                                   &seed);
     (void)hipStreamSynchronize(ctx->stream);
     if (rc == SMI_OK && run) {
         r->owns_first = true;  // the run keeps the uploaded codeword
@@ -717,6 +770,10 @@ int smi_fri_commit(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codewor
         (void)hipFree(d_cw);
     }
     return rc;
+}
+int smi_fri_commit(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint64_t *codeword, size_t len, uint8_t *roots,
+                   uint64_t *alphas, uint64_t *last_codeword, size_t *last_len, smi_fri_run **run) {
+    return smi_fri_commit_fs(ctx, cfg, nullptr, 0, codeword, len, roots, alphas, last_codeword, last_len, run);
 }
 
 int smi_fri_fold(smi_ctx *ctx, const uint64_t *codeword, size_t len, uint64_t alpha, uint64_t offset, uint64_t omega,

@@ -568,8 +568,8 @@ int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_no
 int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
                      uint64_t *alpha_out, bool *done) {
     const TopHook hook{fs_words, proof_slot, alpha_out};
-    *done = false;
-    return launch_merkle_impl(ctx, d_elems, n, d_nodes, 1, 0, 0, 0, 0, &hook, done);
+    *done = false;   // fs_words == nullptr: no epilogue, the caller runs the round itself
+    return launch_merkle_impl(ctx, d_elems, n, d_nodes, 1, 0, 0, 0, 0, fs_words ? &hook : nullptr, done);
 }
 // The planner's rule, restated: with more than 2048 * TOP_BLOCKS leaves the first launch of a single tree is the
 // four-leaves-per-lane kernel (the chunk kernel takes over below that), and that kernel can compute its leaves (LeafSrc).
@@ -604,7 +604,7 @@ int launch_merkle_src_fs(smi_ctx *ctx, const LeafSrc &src, size_t n, uint8_t *d_
         return smi_fail(ctx, SMI_ERR_BAD_ARG, "merkle: this tree cannot take a computed leaf source");
     const TopHook hook{fs_words, proof_slot, alpha_out};
     *done = false;
-    return launch_merkle_impl(ctx, src.cw_out, n, d_nodes, 1, 0, 0, 0, 0, &hook, done, &src);
+    return launch_merkle_impl(ctx, src.cw_out, n, d_nodes, 1, 0, 0, 0, 0, fs_words ? &hook : nullptr, done, &src);
 }
 // one tree whose leaf i hashes row i of n_cols columns (column c at d_cols + c*col_stride)
 int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes) {

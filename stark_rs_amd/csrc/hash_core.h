@@ -372,6 +372,70 @@ SMI_HD void fs_absorb_root(uint32_t *fs_words, const uint32_t m[8], uint8_t *pro
     }
 }
 
+// ---- a caller's transcript (src/fiat_shamir.rs:15-25: every challenge hashes the WHOLE transcript).  A transcript of
+// P bytes is the state S after its P/32 whole chunks (each followed by its mix) and its k = P mod 32 trailing bytes
+// absorbed at positions 0..k-1 but NOT yet mixed, plus the phase k.  Its challenge is mix^9(S) for k != 0 (the mix of
+// the short last chunk, then the 8 closing ones) and mix^8(S) for k == 0; an empty transcript is k == 0 with S = the
+// initial constants.  Roots are 32 bytes, so absorbing one leaves k unchanged.  Single lane, fully applied states.
+
+// bytes msg[0..n) at chunk positions pos0 .. pos0+n-1 (pos0 + n <= 32), src/hash.rs:15-20 byte by byte: the XOR of a
+// byte at position 25..31 wraps onto positions 0..6, which the bytes before it in the same chunk have already passed
+SMI_HD void absorb_bytes_at(State &st, int pos0, const uint8_t *msg, int n) {
+    for (int i = 0; i < n; i++) absorb_byte(st, pos0 + i, msg[i]);
+}
+
+// S and k of a transcript of P bytes, S in the representation fs_words holds (paired lanes, nothing pending)
+SMI_HD void fs_seed(const uint8_t *t, size_t P, uint32_t words[16], uint32_t *phase) {
+    State st;
+    init(st);
+    size_t off = 0;
+    for (; off + 32 <= P; off += 32) {
+        uint32_t m[8];
+        for (int j = 0; j < 8; j++)
+            m[j] = (uint32_t)t[off + 4 * j] | ((uint32_t)t[off + 4 * j + 1] << 8) | ((uint32_t)t[off + 4 * j + 2] << 16) |
+                   ((uint32_t)t[off + 4 * j + 3] << 24);
+        absorb_chunk32(st, m);
+    }
+    const int k = (int)(P - off);
+    absorb_bytes_at(st, 0, t + off, k);
+    for (int i = 0; i < 16; i++) words[i] = st.s[i];
+    *phase = (uint32_t)k;
+}
+
+// FiatShamir::challenge at phase k: the first 8 digest bytes, unreduced
+SMI_HD uint64_t fs_challenge_phase(const uint32_t *fs_words, uint32_t phase) {
+    State st;
+    for (int i = 0; i < 16; i++) st.s[i] = fs_words[i];
+    const int mixes = phase ? 9 : 8;
+    for (int k = 0; k < mixes; k++) mix(st);
+    uint32_t d[8];
+    to_words(st, d);
+    return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
+}
+
+// fs_absorb_root at phase k: root bytes 0..31-k complete the pending chunk at positions k..31 and it is mixed, root
+// bytes 32-k..31 start the next one at positions 0..k-1 and stay unmixed.  At k == 0 this is fs_absorb_root.
+SMI_HD void fs_absorb_root_phase(uint32_t *fs_words, const uint32_t m[8], uint32_t phase, uint8_t *proof_slot, uint64_t *alpha_out) {
+    if (phase == 0) {
+        fs_absorb_root(fs_words, m, proof_slot, alpha_out);
+        return;
+    }
+    const int k = (int)phase;
+    uint8_t r[32];
+    for (int i = 0; i < 32; i++) r[i] = (uint8_t)(m[i >> 2] >> (8 * (i & 3)));
+    State st;
+    for (int i = 0; i < 16; i++) st.s[i] = fs_words[i];
+    absorb_bytes_at(st, k, r, 32 - k);
+    mix(st);
+    absorb_bytes_at(st, 0, r + 32 - k, k);
+    for (int i = 0; i < 16; i++) fs_words[i] = st.s[i];
+    if (proof_slot) {
+        proof_slot[0] = 0;
+        for (int i = 0; i < 32; i++) proof_slot[1 + i] = r[i];
+    }
+    if (alpha_out) *alpha_out = fs_challenge_phase(fs_words, phase);
+}
+
 // Hash::from_field_elements(&[v as u64]) (src/hash.rs:32-35 as used by src/fri.rs:118-121):
 // 8 message bytes (LE u64 of a u32 residue: the upper four are zero), 1 + 8 mixes.
 // the 8-byte chunk of a leaf in natural layout: it touches bytes 0..14 -- v_0..v_7 as in

@@ -191,6 +191,14 @@ struct FriTailArgs {
 };
 int launch_fri_tail(smi_ctx *ctx, const FriTailArgs &a);
 uint64_t fri_tail_len();   // codewords of at most this many elements finish in the fused tail (SMI_FRI_TAIL, default 512; fri.hip)
+// A caller's Fiat-Shamir transcript as the prover continues it (hash_core.h fs_seed): the sponge state after its whole
+// 32-byte chunks and its trailing bytes, and the count of those trailing bytes.  Computed on the host: the reference's
+// transcript is a host Vec<u8>.  phase == 0 (every transcript of whole roots, the empty one included) runs the fused
+// Fiat-Shamir sites; phase != 0 takes the single-lane phase-aware kernels after each tree and no fused tail.
+struct FsSeed {
+    uint32_t s[16];
+    uint32_t phase;
+};
 
 // Where the leaves of a tree come from when they are not simply read (hash.hip, merkle_sub_kernel's LEAF_* kinds): the
 // kernel computes the codeword element, stores it to cw_out (the query phase and the next fold read it) and hashes it.

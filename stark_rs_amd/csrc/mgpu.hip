@@ -29,9 +29,9 @@ int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t
 int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, size_t full_len,
                       const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out);
 size_t fri_fs_bytes();
-int launch_fs_init(smi_ctx *ctx, void *fs);
-int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out);
-int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out);
+int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed);
+int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase);
+int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out, uint32_t phase);
 int launch_sample_indices(smi_ctx *ctx, const uint64_t *challenge, uint64_t size, uint64_t reduced_size, uint32_t number,
                           uint64_t *indices, uint64_t *reduced);
 int launch_emit_codeword(smi_ctx *ctx, const uint32_t *cw, uint64_t len, uint8_t *dst);
@@ -68,6 +68,7 @@ __global__ __launch_bounds__(256) void mg_interleave_kernel(const uint32_t *__re
 namespace {
 struct HipDev : MgDev {
     smi_ctx *ctx;
+    uint32_t fs_phase = 0;   // the phase fs_init put in the state, kept here too: it picks the kernels
     explicit HipDev(smi_ctx *c) : ctx(c) {}
     uint32_t prime() const override { return ctx->fs.F.p; }
     uint32_t root_of_unity(uint32_t log_n) const override { return h_root(ctx, log_n); }
@@ -102,9 +103,9 @@ struct HipDev : MgDev {
     }
     int merkle(const uint32_t *elems, size_t n, uint8_t *nodes) override { return launch_merkle(ctx, elems, n, nodes); }
     int merkle_fs(const uint32_t *elems, size_t n, uint8_t *nodes, void *fs, uint8_t *proof_slot, uint64_t *alpha_out) override {
-        bool done = false;   // the launch that finishes the tree runs the Fiat-Shamir round when it can (hash.hip)
-        SMI_TRY(launch_merkle_fs(ctx, elems, n, nodes, (uint32_t *)fs, proof_slot, alpha_out, &done));
-        if (!done) SMI_TRY(launch_fs_round(ctx, fs, nodes + (2 * n - 2) * 32, proof_slot, alpha_out));
+        bool done = false;   // the launch that finishes the tree runs the Fiat-Shamir round when it can (hash.hip), at phase 0
+        SMI_TRY(launch_merkle_fs(ctx, elems, n, nodes, fs_phase == 0 ? (uint32_t *)fs : nullptr, proof_slot, alpha_out, &done));
+        if (!done) SMI_TRY(launch_fs_round(ctx, fs, nodes + (2 * n - 2) * 32, proof_slot, alpha_out, fs_phase));
         return SMI_OK;
     }
     int merkle_batch(const uint32_t *elems, size_t n, uint8_t *nodes, uint32_t n_trees, size_t elem_stride, size_t node_stride_bytes) override {
@@ -112,11 +113,17 @@ struct HipDev : MgDev {
     }
     int merkle_from_digests(size_t n, uint8_t *nodes) override { return launch_merkle(ctx, nullptr, n, nodes); }
     size_t fs_bytes() const override { return fri_fs_bytes(); }
-    int fs_init(void *fs) override { return launch_fs_init(ctx, fs); }
-    int fs_round(void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out) override {
-        return launch_fs_round(ctx, fs, root, proof_slot, alpha_out);
+    int fs_init(void *fs, const uint32_t seed[16], uint32_t phase) override {
+        FsSeed s;
+        memcpy(s.s, seed, sizeof s.s);
+        s.phase = phase;
+        fs_phase = phase;
+        return launch_fs_init(ctx, fs, &s);
     }
-    int fs_challenge(const void *fs, uint64_t *out) override { return launch_fs_challenge(ctx, fs, out); }
+    int fs_round(void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out) override {
+        return launch_fs_round(ctx, fs, root, proof_slot, alpha_out, fs_phase);
+    }
+    int fs_challenge(const void *fs, uint64_t *out) override { return launch_fs_challenge(ctx, fs, out, fs_phase); }
     int fs_weights(const uint8_t *const *d_root_ptrs, uint32_t n, uint64_t *weights, uint8_t *roots_out) override {
         return launch_fs_weights(ctx, d_root_ptrs, n, weights, roots_out);
     }
@@ -367,13 +374,13 @@ static int give_proof(smi_ctx *ctx, const std::vector<uint8_t> &bytes, uint8_t *
     return SMI_OK;
 }
 
-int smi_mgpu_fri_commit(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t *roots, uint64_t *alphas,
-                        uint64_t *last_codeword, size_t *last_len) {
-    if (!m || !cfg || !d_block) return SMI_ERR_BAD_ARG;
+int smi_mgpu_fri_commit_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_block,
+                           size_t block_len, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len) {
+    if (!m || !cfg || !d_block || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(m->ctx);
     SMI_TRY(m->dev.reset());
     MgFriOut o;
-    SMI_TRY(mg_fri_run(m->dev, *m->coll, m->rank, m->world, *cfg, d_block, block_len, m->min_block, false, o));
+    SMI_TRY(mg_fri_run(m->dev, *m->coll, m->rank, m->world, *cfg, d_block, block_len, m->min_block, false, o, transcript, transcript_len));
     if (roots)
         for (uint64_t r = 0; r < o.rounds; r++) memcpy(roots + 32 * r, o.proof.data() + 33 * r + 1, 32);
     if (alphas && !o.alphas.empty()) memcpy(alphas, o.alphas.data(), 8 * o.alphas.size());
@@ -382,15 +389,24 @@ int smi_mgpu_fri_commit(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_b
     return SMI_OK;
 }
 
-int smi_mgpu_fri_prove(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t **proof, size_t *proof_len,
-                       uint64_t *top_indices) {
-    if (!m || !cfg || !d_block || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+int smi_mgpu_fri_commit(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t *roots, uint64_t *alphas,
+                        uint64_t *last_codeword, size_t *last_len) {
+    return smi_mgpu_fri_commit_fs(m, cfg, nullptr, 0, d_block, block_len, roots, alphas, last_codeword, last_len);
+}
+
+int smi_mgpu_fri_prove_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_block,
+                          size_t block_len, uint8_t **proof, size_t *proof_len, uint64_t *top_indices) {
+    if (!m || !cfg || !d_block || !proof || !proof_len || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(m->ctx);
     SMI_TRY(m->dev.reset());
     MgFriOut o;
-    SMI_TRY(mg_fri_run(m->dev, *m->coll, m->rank, m->world, *cfg, d_block, block_len, m->min_block, true, o));
+    SMI_TRY(mg_fri_run(m->dev, *m->coll, m->rank, m->world, *cfg, d_block, block_len, m->min_block, true, o, transcript, transcript_len));
     if (top_indices && !o.top.empty()) memcpy(top_indices, o.top.data(), 8 * o.top.size());
     return give_proof(m->ctx, o.proof, proof, proof_len);
+}
+int smi_mgpu_fri_prove(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t **proof, size_t *proof_len,
+                       uint64_t *top_indices) {
+    return smi_mgpu_fri_prove_fs(m, cfg, nullptr, 0, d_block, block_len, proof, proof_len, top_indices);
 }
 
 int smi_mgpu_lde(smi_mgpu *m, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n, uint32_t log_blowup, uint64_t trace_offset,

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/stark_mi.h"
+#include "hash_core.h"
 #include "mgpu_core.h"
 #include "ntt_host.h"
 
@@ -81,9 +82,11 @@ struct MgDev {
     virtual int merkle_batch(const uint32_t *elems, size_t n, uint8_t *nodes, uint32_t n_trees, size_t elem_stride,
                              size_t node_stride_bytes) = 0;
     virtual int merkle_from_digests(size_t n, uint8_t *nodes) = 0;
-    // FiatShamir (src/fiat_shamir.rs:15-25), state on the device
+    // FiatShamir (src/fiat_shamir.rs:15-25), state on the device.  fs_init starts it from a caller's transcript (hash_core.h
+    // fs_seed: 16 state words and the phase, which travels with the state); fs_round / fs_challenge continue it at that
+    // phase, merkle_fs too -- where the phase is not 0 it runs the round after the tree instead of fusing it.
     virtual size_t fs_bytes() const = 0;
-    virtual int fs_init(void *fs) = 0;
+    virtual int fs_init(void *fs, const uint32_t seed[16], uint32_t phase) = 0;
     virtual int fs_round(void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out) = 0;
     virtual int fs_challenge(const void *fs, uint64_t *out) = 0;
     virtual int fs_weights(const uint8_t *const *d_root_ptrs, uint32_t n, uint64_t *weights, uint8_t *roots_out) = 0;
@@ -147,10 +150,12 @@ inline bool pow2(uint64_t n) { return n && !(n & (n - 1)); }
 inline int pre(MgDev &d, MgColl &c) { return c.stream_ordered() ? SMI_OK : d.sync(); }
 }  // namespace mg
 
-// Fri::commit (+ the query phase of Fri::prove when do_query) over the block this rank holds.
+// Fri::commit (+ the query phase of Fri::prove when do_query) over the block this rank holds, continuing the caller's
+// transcript (host bytes, the same on every rank; empty: a fresh FiatShamir).
 inline int mg_fri_run(MgDev &d, MgColl &coll, int rank, int G, const smi_fri_cfg &cfg, const uint32_t *block, size_t block_len,
-                      size_t min_block, bool do_query, MgFriOut &out) {
+                      size_t min_block, bool do_query, MgFriOut &out, const uint8_t *transcript = nullptr, size_t transcript_len = 0) {
     using namespace mg;
+    if (!transcript && transcript_len) return d.fail(SMI_ERR_BAD_ARG, "transcript == NULL with a length");
     // asserts of Fri::new / Fri::prove (src/fri.rs:37-45, 256-260)
     if (!pow2(cfg.domain_length)) return d.fail(SMI_ERR_DOMAIN_NOT_POW2, nullptr);
     if (!pow2(cfg.expansion_factor)) return d.fail(SMI_ERR_EXPANSION_NOT_POW2, nullptr);
@@ -192,7 +197,9 @@ inline int mg_fri_run(MgDev &d, MgColl &coll, int rank, int G, const smi_fri_cfg
     uint8_t *d_proof = (uint8_t *)d.alloc(proof_len);
     if (!fs || !d_alphas || !d_seed || !d_top || !d_red || !d_dummy || !d_proof) return d.fail(SMI_ERR_OOM, "mgpu: device memory");
     MG_TRY(d.zero(d_proof, proof_len));
-    MG_TRY(d.fs_init(fs));
+    uint32_t seed[16], phase = 0;
+    hashc::fs_seed(transcript, transcript_len, seed, &phase);
+    MG_TRY(d.fs_init(fs, seed, phase));
 
     std::vector<MgSide> sides;
     const uint32_t *cur = block;
@@ -210,7 +217,7 @@ inline int mg_fri_run(MgDev &d, MgColl &coll, int rank, int G, const smi_fri_cfg
             cur_local = length;
             sharded = false;
         }
-        if (!sharded && length <= d.tail_max_len() && R - r <= d.tail_max_rounds()) {
+        if (!sharded && phase == 0 && length <= d.tail_max_len() && R - r <= d.tail_max_rounds()) {   // (the tail's rounds run at phase 0)
             // replicated and small: every remaining round in one call (SURVEY 8e "gather to one GPU and run the fused
             // tail"; here every rank runs it, so nothing has to be broadcast afterwards)
             std::vector<MgTailRound> tr((size_t)(R - r));

@@ -24,7 +24,8 @@ int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t
 int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
 int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
             smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
-            uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src);
+            uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src,
+            const FsSeed *seed = nullptr);
 
 // weights[c] = FiatShamir::challenge after absorbing roots[0..c] (unreduced u64)
 // weights_m (optional): the same weights reduced mod p in Montgomery form, what the fused combination multiplies by

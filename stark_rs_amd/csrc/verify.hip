@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "hash_core.h"
 #include "internal.h"
 #include "proof_parse.h"
 
@@ -62,24 +63,28 @@ int challenge_of(smi_ctx *ctx, const std::vector<uint8_t> &transcript, uint64_t 
     return SMI_OK;
 }
 
-// Fri::verify on objs[0..]; *used = objects consumed on acceptance
-int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const std::vector<Obj> &objs, int *accept, std::vector<uint64_t> *top_out,
-                    std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val, std::vector<uint64_t> *layer0_ab, size_t *used) {
+// Fri::verify on objs[0..] with the transcript the caller's FiatShamir holds (seed, hash_core.h fs_seed); *used = objects
+// consumed on acceptance.  The challenges continue the seed one root at a time instead of re-hashing the transcript.
+int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, const std::vector<Obj> &objs, int *accept,
+                    std::vector<uint64_t> *top_out, std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val,
+                    std::vector<uint64_t> *layer0_ab, size_t *used) {
     const uint64_t p = ctx->fs.F.p, t = cfg.num_colinearity_tests, N = cfg.domain_length;
     uint64_t R = 0;
     smi_fri_num_rounds(&cfg, &R);
     size_t at = 0;
     auto pop = [&]() -> const Obj * { return at < objs.size() ? &objs[at++] : nullptr; };
-    std::vector<uint8_t> transcript;
+    uint32_t fs[16];
+    memcpy(fs, fs0.s, sizeof fs);
     std::vector<const uint8_t *> roots;
     std::vector<uint64_t> alphas;
     for (uint64_t r = 0; r < R; r++) {                                             // src/fri.rs:325-334
         const Obj *o = pop();
         if (!o || o->tag != 0) return reject(ctx, accept, "Failed to extract Merkle root");
         roots.push_back(o->p);
-        transcript.insert(transcript.end(), o->p, o->p + 32);
+        uint32_t m[8];
+        memcpy(m, o->p, 32);   // little-endian words (proof bytes in order)
         uint64_t a = 0;
-        SMI_TRY(challenge_of(ctx, transcript, &a));
+        hashc::fs_absorb_root_phase(fs, m, fs0.phase, nullptr, &a);
         alphas.push_back(a);
     }
     const Obj *lo = pop();                                                          // :337-342
@@ -123,8 +128,7 @@ int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const std::vector<Obj>
     const uint64_t size = N >> 1, reduced_size = N >> (R - 1);
     if (t > 2 * reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, nullptr);
     if (t > reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, nullptr);
-    uint64_t seed_ch = 0;
-    SMI_TRY(challenge_of(ctx, transcript, &seed_ch));
+    const uint64_t seed_ch = hashc::fs_challenge_phase(fs, fs0.phase);
     uint8_t seed[32], seed_msg[8];
     for (int k = 0; k < 8; k++) seed_msg[k] = (uint8_t)(seed_ch >> (8 * k));
     SMI_TRY(smi_hash_bytes(ctx, seed_msg, 8, seed));                                // Hash::from_u64
@@ -231,23 +235,37 @@ size_t fri_object_count(const smi_fri_cfg &cfg) {
     smi_fri_num_rounds(&cfg, &R);
     return (size_t)(R + 1 + (R ? R - 1 : 0) * 4 * cfg.num_colinearity_tests);
 }
+FsSeed fresh_seed() {
+    FsSeed z;
+    hashc::fs_seed(nullptr, 0, z.s, &z.phase);
+    return z;
+}
 }  // namespace
 
-int smi_fri_verify(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *proof, size_t proof_len, int *accept, uint64_t *pv_indices,
-                   uint64_t *pv_values, size_t *n_pv) {
-    if (!ctx || !cfg || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+int smi_fri_verify_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                      size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed) {
+    if (!ctx || !cfg || (!proof && proof_len) || !accept || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     *accept = 0;
     if (n_pv) *n_pv = 0;
+    if (consumed) *consumed = 0;
     SMI_TRY(smi_fri_check(ctx, cfg));
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
     size_t end = 0;
     const std::vector<Obj> objs = parse(proof, proof_len, (size_t)-1, &end);
     std::vector<uint64_t> pi, pv;
-    const int rc = fri_verify_objs(ctx, *cfg, objs, accept, nullptr, &pi, &pv, nullptr, nullptr);
+    size_t used = 0;
+    const int rc = fri_verify_objs(ctx, *cfg, seed, objs, accept, nullptr, &pi, &pv, nullptr, &used);
     if (n_pv) *n_pv = pi.size();       // like the reference's &mut Vec: what was pushed before a rejection stays
     if (pv_indices && !pi.empty()) memcpy(pv_indices, pi.data(), 8 * pi.size());
     if (pv_values && !pv.empty()) memcpy(pv_values, pv.data(), 8 * pv.size());
+    if (rc == SMI_OK && *accept && consumed) (void)parse(proof, proof_len, used, consumed);   // the bytes of the popped objects
     return rc;
+}
+int smi_fri_verify(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *proof, size_t proof_len, int *accept, uint64_t *pv_indices,
+                   uint64_t *pv_values, size_t *n_pv) {
+    return smi_fri_verify_fs(ctx, cfg, nullptr, 0, proof, proof_len, accept, pv_indices, pv_values, n_pv, nullptr);
 }
 
 int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *column_roots, const uint8_t *proof, size_t proof_len,
@@ -274,7 +292,7 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
     const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc), &end);
     std::vector<uint64_t> top, ab;
     size_t used = 0;
-    SMI_TRY(fri_verify_objs(ctx, fc, objs, accept, &top, nullptr, nullptr, &ab, &used));
+    SMI_TRY(fri_verify_objs(ctx, fc, fresh_seed(), objs, accept, &top, nullptr, nullptr, &ab, &used));
     if (!*accept) return SMI_OK;
     // ---- the column openings (mgpu_core.h layout): rows, then paths
     *accept = 0;

@@ -251,49 +251,67 @@ class Engine:
         self._ck(self.L.smi_fri_fold(self.h, c.ctypes.data, len(c), alpha, offset, omega, out.ctypes.data))
         return out
 
-    def fri_commit(self, cfg, codeword):
+    # `transcript`: the bytes the caller's FiatShamir holds before the call (src/fri.rs:105-110, 250-255, 313-318); the
+    # empty default is a fresh FiatShamir and calls the entry points without a transcript.  The roots are not absorbed
+    # here: the caller appends them to its transcript, as the reference leaves it.
+    def _commit(self, cfg, codeword, transcript, run):
         c = _u64(codeword)
         R = max(self.fri_num_rounds(cfg), 1)
         roots = np.zeros((R, 32), dtype=np.uint8)
         alphas = np.zeros(R, dtype=np.uint64)
         last = np.zeros(len(c), dtype=np.uint64)
         ll = C.c_size_t()
-        self._ck(self.L.smi_fri_commit(self.h, C.byref(cfg), c.ctypes.data, len(c), roots.ctypes.data, alphas.ctypes.data,
-                                       last.ctypes.data, C.byref(ll), None))
+        tail = (roots.ctypes.data, alphas.ctypes.data, last.ctypes.data, C.byref(ll), run)
+        if transcript:
+            t = bytes(transcript)
+            self._ck(self.L.smi_fri_commit_fs(self.h, C.byref(cfg), t, len(t), c.ctypes.data, len(c), *tail))
+        else:
+            self._ck(self.L.smi_fri_commit(self.h, C.byref(cfg), c.ctypes.data, len(c), *tail))
         return roots, [int(a) for a in alphas[:R - 1]], last[:ll.value].copy()
 
-    def fri_commit_run(self, cfg, codeword):
-        """Fri::commit keeping every round's codeword and tree on the device -> (roots, alphas, FriRun)."""
-        c = _u64(codeword)
-        R = max(self.fri_num_rounds(cfg), 1)
-        roots = np.zeros((R, 32), dtype=np.uint8)
-        alphas = np.zeros(R, dtype=np.uint64)
-        last = np.zeros(len(c), dtype=np.uint64)
-        ll, run = C.c_size_t(), vp()
-        self._ck(self.L.smi_fri_commit(self.h, C.byref(cfg), c.ctypes.data, len(c), roots.ctypes.data, alphas.ctypes.data,
-                                       last.ctypes.data, C.byref(ll), C.byref(run)))
-        return roots, [int(a) for a in alphas[:R - 1]], FriRun(self, run)
+    def fri_commit(self, cfg, codeword, transcript=b""):
+        return self._commit(cfg, codeword, transcript, None)
 
-    def fri_prove(self, cfg, codeword):
-        """-> (ProofStream::serialize bytes, top-level indices) -- Fri::prove, src/fri.rs:250-311."""
+    def fri_commit_run(self, cfg, codeword, transcript=b""):
+        """Fri::commit keeping every round's codeword and tree on the device -> (roots, alphas, FriRun)."""
+        run = vp()
+        roots, alphas, _ = self._commit(cfg, codeword, transcript, C.byref(run))
+        return roots, alphas, FriRun(self, run)
+
+    def fri_prove(self, cfg, codeword, transcript=b""):
+        """-> (ProofStream::serialize bytes, top-level indices) -- Fri::prove, src/fri.rs:250-311; with a transcript,
+        the objects it pushes after the caller's."""
         c = _u64(codeword)
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(cfg.num_colinearity_tests, 1), dtype=np.uint64)
-        self._ck(self.L.smi_fri_prove(self.h, C.byref(cfg), c.ctypes.data, len(c), C.byref(proof), C.byref(plen),
-                                      top.ctypes.data))
+        if transcript:
+            t = bytes(transcript)
+            self._ck(self.L.smi_fri_prove_fs(self.h, C.byref(cfg), t, len(t), c.ctypes.data, len(c), C.byref(proof), C.byref(plen),
+                                             top.ctypes.data))
+        else:
+            self._ck(self.L.smi_fri_prove(self.h, C.byref(cfg), c.ctypes.data, len(c), C.byref(proof), C.byref(plen),
+                                          top.ctypes.data))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         return b, [int(v) for v in top[:cfg.num_colinearity_tests]]
 
     # ---- device-resident calls (pointers are ints)
-    def fri_verify(self, cfg, proof: bytes):
-        """Fri::verify (src/fri.rs:313-504) -> (accept, [(index, value)], reason); a reference panic raises."""
+    def fri_verify(self, cfg, proof: bytes, transcript=b"", want_consumed=False):
+        """Fri::verify (src/fri.rs:313-504) -> (accept, [(index, value)], reason); a reference panic raises.
+        want_consumed: a fourth item, the bytes of the objects it popped (0 on rejection)."""
         t = int(cfg.num_colinearity_tests)
         pi, pv = np.zeros(2 * t + 2, dtype=np.uint64), np.zeros(2 * t + 2, dtype=np.uint64)
-        acc, n = C.c_int(), C.c_size_t()
-        self._ck(self.L.smi_fri_verify(self.h, C.byref(cfg), proof, len(proof), C.byref(acc), pi.ctypes.data, pv.ctypes.data, C.byref(n)))
+        acc, n, used = C.c_int(), C.c_size_t(), C.c_size_t()
+        if transcript or want_consumed:
+            tr = bytes(transcript)
+            self._ck(self.L.smi_fri_verify_fs(self.h, C.byref(cfg), tr, len(tr), proof, len(proof), C.byref(acc), pi.ctypes.data,
+                                              pv.ctypes.data, C.byref(n), C.byref(used)))
+        else:
+            self._ck(self.L.smi_fri_verify(self.h, C.byref(cfg), proof, len(proof), C.byref(acc), pi.ctypes.data, pv.ctypes.data,
+                                           C.byref(n)))
         why = "" if acc.value else self.L.smi_last_error(self.h).decode()
-        return bool(acc.value), [(int(pi[i]), int(pv[i])) for i in range(n.value)], why
+        out = (bool(acc.value), [(int(pi[i]), int(pv[i])) for i in range(n.value)], why)
+        return out + (used.value,) if want_consumed else out
 
     def stark_verify(self, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
                      lde_offset=None, open_columns=False):
@@ -356,11 +374,16 @@ class Engine:
         self._ck(self.L.smi_dev_fri_fold_shard(self.h, vp(d_lo), vp(d_hi), count, index0, full_len, vp(d_alpha), offset, omega,
                                                vp(d_out)))
 
-    def dev_fri_prove(self, cfg, d_codeword, length):
+    def dev_fri_prove(self, cfg, d_codeword, length, transcript=b""):
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(cfg.num_colinearity_tests, 1), dtype=np.uint64)
-        self._ck(self.L.smi_dev_fri_prove(self.h, C.byref(cfg), vp(d_codeword), length, C.byref(proof), C.byref(plen),
-                                          top.ctypes.data, None))
+        if transcript:   # host bytes (the transcript is never on the device)
+            t = bytes(transcript)
+            self._ck(self.L.smi_dev_fri_prove_fs(self.h, C.byref(cfg), t, len(t), vp(d_codeword), length, C.byref(proof),
+                                                 C.byref(plen), top.ctypes.data, None))
+        else:
+            self._ck(self.L.smi_dev_fri_prove(self.h, C.byref(cfg), vp(d_codeword), length, C.byref(proof), C.byref(plen),
+                                              top.ctypes.data, None))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         return b, [int(v) for v in top[:cfg.num_colinearity_tests]]

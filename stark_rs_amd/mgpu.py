@@ -126,6 +126,8 @@ def _sig(L):
     L.smi_mgpu_set_min_block.argtypes = [vp, sz]
     L.smi_mgpu_fri_commit.argtypes = [vp, C.POINTER(FriCfg), vp, sz, vp, vp, vp, C.POINTER(sz)]
     L.smi_mgpu_fri_prove.argtypes = [vp, C.POINTER(FriCfg), vp, sz, C.POINTER(vp), C.POINTER(sz), vp]
+    L.smi_mgpu_fri_commit_fs.argtypes = [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, vp, vp, vp, C.POINTER(sz)]
+    L.smi_mgpu_fri_prove_fs.argtypes = [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), vp]
     L.smi_mgpu_lde.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.smi_mgpu_stark_prove.argtypes = [vp, C.POINTER(StarkCfg), vp, vp, C.POINTER(vp), C.POINTER(sz), vp]
     L.smi_mgpu_ntt.argtypes = [vp, vp, vp, C.c_uint32, i32, C.c_uint64]
@@ -181,8 +183,9 @@ class MultiGpu:
         self.L.smi_free(proof)
         return out
 
-    def fri_commit(self, cfg, d_block, block_len):
-        """-> (roots [R x bytes], alphas [R-1 ints], last codeword np.uint64) on every rank"""
+    def fri_commit(self, cfg, d_block, block_len, transcript=b""):
+        """-> (roots [R x bytes], alphas [R-1 ints], last codeword np.uint64) on every rank.  transcript: what the
+        caller's FiatShamir holds (the same bytes on every rank; empty: a fresh one)."""
         rounds = C.c_uint64()
         check(self.L.smi_fri_num_rounds(C.byref(cfg), C.byref(rounds)))
         R = max(rounds.value, 1)
@@ -190,15 +193,25 @@ class MultiGpu:
         alphas = (C.c_uint64 * R)()
         last = np.zeros(cfg.domain_length, dtype=np.uint64)
         n = sz()
-        self._ck(self.L.smi_mgpu_fri_commit(self.h, C.byref(cfg), d_block, block_len, roots, alphas, last.ctypes.data, C.byref(n)))
+        if transcript:
+            t = bytes(transcript)
+            self._ck(self.L.smi_mgpu_fri_commit_fs(self.h, C.byref(cfg), t, len(t), d_block, block_len, roots, alphas, last.ctypes.data,
+                                                   C.byref(n)))
+        else:
+            self._ck(self.L.smi_mgpu_fri_commit(self.h, C.byref(cfg), d_block, block_len, roots, alphas, last.ctypes.data, C.byref(n)))
         raw = bytes(roots)
         return [raw[32 * i:32 * i + 32] for i in range(rounds.value)], list(alphas)[:rounds.value - 1], last[:n.value]
 
-    def fri_prove(self, cfg, d_block, block_len):
-        """-> (serialized ProofStream, top-level indices) on every rank"""
+    def fri_prove(self, cfg, d_block, block_len, transcript=b""):
+        """-> (serialized ProofStream, top-level indices) on every rank; with a transcript as in fri_commit, the objects
+        Fri::prove pushes after the caller's"""
         proof, plen = vp(), sz()
         top = (C.c_uint64 * max(int(cfg.num_colinearity_tests), 1))()
-        self._ck(self.L.smi_mgpu_fri_prove(self.h, C.byref(cfg), d_block, block_len, C.byref(proof), C.byref(plen), top))
+        if transcript:
+            t = bytes(transcript)
+            self._ck(self.L.smi_mgpu_fri_prove_fs(self.h, C.byref(cfg), t, len(t), d_block, block_len, C.byref(proof), C.byref(plen), top))
+        else:
+            self._ck(self.L.smi_mgpu_fri_prove(self.h, C.byref(cfg), d_block, block_len, C.byref(proof), C.byref(plen), top))
         return self._take(proof, plen), list(top)[:int(cfg.num_colinearity_tests)]
 
     def lde(self, d_trace_cols, n_cols, log_n, log_blowup, d_out_blocks, trace_offset=1, lde_offset=None):

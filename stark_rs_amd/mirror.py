@@ -478,10 +478,9 @@ class Fri:
 
     def commit(self, initial_codeword, proof_stream, fiat_shamir):
         """fri.rs:105-156: pushes the roots and the last codeword, absorbs the roots, and returns
-        the codewords of every round (`Vec<Vec<FieldElement>>`), read back from the device."""
-        if fiat_shamir.transcript:
-            raise StarkMiError(-50, "bad argument: the device transcript starts empty (fresh FiatShamir)")
-        roots, alphas, run = self._eng.fri_commit_run(self._cfg, _vals(initial_codeword))
+        the codewords of every round (`Vec<Vec<FieldElement>>`), read back from the device.  The device continues
+        whatever fiat_shamir already holds."""
+        roots, alphas, run = self._eng.fri_commit_run(self._cfg, _vals(initial_codeword), bytes(fiat_shamir.transcript))
         for r in roots:
             proof_stream.push(ProofObject(0, Hash(bytes(r))))
             fiat_shamir.absorb(bytes(r))
@@ -492,10 +491,8 @@ class Fri:
 
     def prove(self, initial_codeword, fiat_shamir, proof_stream):
         """fri.rs:250-311: fills proof_stream, absorbs the roots into fiat_shamir, returns the
-        top-level indices."""
-        if fiat_shamir.transcript:
-            raise StarkMiError(-50, "bad argument: the device transcript starts empty (fresh FiatShamir)")
-        proof, top = self._eng.fri_prove(self._cfg, _vals(initial_codeword))
+        top-level indices.  The device continues whatever fiat_shamir already holds."""
+        proof, top = self._eng.fri_prove(self._cfg, _vals(initial_codeword), bytes(fiat_shamir.transcript))
         for obj in ProofStream.deserialize(proof, self.field).objects:
             proof_stream.push(obj)
             if obj.tag == 0:

@@ -125,6 +125,9 @@ extern "C" {
     pub fn smi_poly_mul(ctx: *mut smi_ctx, a: *const u64, na: usize, b: *const u64, nb: usize, out: *mut u64, n_out: *mut usize) -> c_int;
     pub fn smi_poly_div(ctx: *mut smi_ctx, a: *const u64, na: usize, b: *const u64, nb: usize, q: *mut u64, nq: *mut usize, r: *mut u64, nr: *mut usize) -> c_int;
     pub fn smi_domain_is_geometric(ctx: *const smi_ctx, domain: *const u64, n: usize, offset: *mut u64) -> c_int;
+    pub fn smi_poly_zerofier(ctx: *mut smi_ctx, domain: *const u64, n: usize, coeffs: *mut u64) -> c_int;
+    pub fn smi_poly_eval_points(ctx: *mut smi_ctx, coeffs: *const u64, n_coeffs: usize, points: *const u64, n_points: usize, values: *mut u64) -> c_int;
+    pub fn smi_poly_interpolate_points(ctx: *mut smi_ctx, domain: *const u64, values: *const u64, n: usize, coeffs: *mut u64) -> c_int;
     pub fn smi_lde(ctx: *mut smi_ctx, cols: *const u64, n_cols: u32, log_n: u32, log_blowup: u32, trace_offset: u64, lde_offset: u64, out: *mut u64) -> c_int;
     pub fn smi_trace_pack(ctx: *const smi_ctx, rows_i128: *const c_void, n_rows: usize, n_cols: usize, cols_out: *mut u64) -> c_int;
     pub fn smi_hash_leaves(ctx: *mut smi_ctx, elems: *const u64, n: usize, digests: *mut u8) -> c_int;
@@ -264,7 +267,8 @@ fn log2_exact(n: usize) -> u32 {
 }
 
 /// `Some(offset)` when `domain` is `offset * omega^k` for the primitive `domain.len()`-th root the reference's
-/// `prim_nth_root` returns -- the only domains the transforms serve; `None` means "keep the CPU body".
+/// `prim_nth_root` returns -- the domains the transforms serve; `None` means "take `interpolate_points` /
+/// `eval_points`".
 pub fn geometric_offset(ctx: &Context, domain: &[u64]) -> Option<u64> {
     let mut offset = 0u64;
     match unsafe { smi_domain_is_geometric(ctx.raw, domain.as_ptr(), domain.len(), &mut offset) } {
@@ -320,6 +324,31 @@ pub fn div(ctx: &Context, a: &[u64], b: &[u64]) -> (Vec<u64>, Vec<u64>) {
     q.truncate(nq);
     r.truncate(nr);
     (q, r)
+}
+
+/// `Polynomial::zerofier` on any points (duplicates and 0 allowed): the n + 1 coefficients of prod (x - d), monic.
+/// An empty domain panics as the reference does when it indexes `domain[0]`.
+pub fn zerofier(ctx: &Context, domain: &[u64]) -> Vec<u64> {
+    let mut out = vec![0u64; domain.len() + 1];
+    ctx.check(unsafe { smi_poly_zerofier(ctx.raw, domain.as_ptr(), domain.len(), out.as_mut_ptr()) });
+    out
+}
+
+/// `Polynomial::eval_domain` on any point list: `f(points[k])` in order (`coeffs` may be longer than `points`).
+pub fn eval_points(ctx: &Context, coeffs: &[u64], points: &[u64]) -> Vec<u64> {
+    let mut out = vec![0u64; points.len()];
+    ctx.check(unsafe { smi_poly_eval_points(ctx.raw, coeffs.as_ptr(), coeffs.len(), points.as_ptr(), points.len(), out.as_mut_ptr()) });
+    out
+}
+
+/// `Polynomial::interpolate_domain` on any domain of distinct points: `domain.len()` coefficients (trailing zeros
+/// included).  A repeated point panics "no inverse" like the reference's `field.inv`; the caller keeps the
+/// reference's two asserts and its H8 shape rule, as for `interpolate_domain`.
+pub fn interpolate_points(ctx: &Context, domain: &[u64], values: &[u64]) -> Vec<u64> {
+    assert!(domain.len() == values.len(), "assertion failed: domain.len() == values.len()");
+    let mut out = vec![0u64; domain.len()];
+    ctx.check(unsafe { smi_poly_interpolate_points(ctx.raw, domain.as_ptr(), values.as_ptr(), domain.len(), out.as_mut_ptr()) });
+    out
 }
 
 /// `codeword.iter().map(|e| Hash::from_field_elements(&[e.value]))` in one call (src/fri.rs:118-121).

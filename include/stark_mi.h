@@ -154,6 +154,27 @@ int smi_poly_div(smi_ctx *ctx, const uint64_t *a, size_t na, const uint64_t *b, 
  * SMI_ERR_NOT_GEOMETRIC. */
 int smi_domain_is_geometric(const smi_ctx *ctx, const uint64_t *domain, size_t n, uint64_t *offset);
 
+/* ---- univariate on arbitrary points: subproduct trees on the device (batched NTT products, LDS blocks of 256 points
+ * at the bottom; the number of launches grows with log n).  Points need not be geometric -- callers with a domain
+ * offset*omega^k keep smi_intt / smi_coset_ntt.  A value >= p gives SMI_ERR_NON_CANONICAL.  K is the modulus'
+ * usable two-adicity (smi_ctx_two_adicity: 23 for 998244353, 26 for 469762049); larger calls give
+ * SMI_ERR_ROOT_TOO_LARGE. */
+/* Polynomial::zerofier (src/univariate/mod.rs:77-96): prod_i (x - domain[i]); writes n+1 coefficients, monic.
+ * Duplicates and 0 are allowed.  n == 0 -> SMI_ERR_EMPTY_DOMAIN (the reference indexes domain[0]).
+ * n <= 2^K: 2^23 points on 998244353, 2^26 on 469762049. */
+int smi_poly_zerofier(smi_ctx *ctx, const uint64_t *domain, size_t n, uint64_t *coeffs);
+/* Polynomial::eval_domain (src/univariate/eval.rs:16-21) on ANY point list: values[k] = f(points[k]), in order.
+ * n_coeffs and n_points are independent (either may be 0; n_coeffs > n_points is allowed); duplicates allowed.
+ * max(n_coeffs, n_points) <= 2^(K-1): the root's power-series products take one doubling more than the tree
+ * (2^22 on 998244353, 2^25 on 469762049). */
+int smi_poly_eval_points(smi_ctx *ctx, const uint64_t *coeffs, size_t n_coeffs, const uint64_t *points, size_t n_points,
+                         uint64_t *values);
+/* Polynomial::interpolate_domain (src/univariate/interpolate.rs:6-44) on ANY domain of distinct points: writes n
+ * coefficients (trailing zeros included, same contract as smi_intt).  A repeated point -> SMI_ERR_NO_INVERSE
+ * "no inverse" (the reference's field.inv panic, interpolate.rs:34); n == 0 -> SMI_ERR_EMPTY_DOMAIN.
+ * n <= 2^(K-1), as smi_poly_eval_points (2^22 on 998244353, 2^25 on 469762049). */
+int smi_poly_interpolate_points(smi_ctx *ctx, const uint64_t *domain, const uint64_t *values, size_t n, uint64_t *coeffs);
+
 /* ---- trace: Trace::get_col / to_field_elements (src/trace.rs:21-34) --------------- */
 /* Low-degree extension of a column-major trace: for each of n_cols columns (n = 2^log_n
  * values on the subgroup domain trace_offset*omega_n^k) interpolate, then evaluate on

@@ -110,6 +110,9 @@ def lib():
         "smi_poly_mul": (i32, [vp, vp, sz, vp, sz, vp, C.POINTER(sz)]),
         "smi_poly_div": (i32, [vp, vp, sz, vp, sz, vp, C.POINTER(sz), vp, C.POINTER(sz)]),
         "smi_domain_is_geometric": (i32, [vp, vp, sz, u64p]),
+        "smi_poly_zerofier": (i32, [vp, vp, sz, vp]),
+        "smi_poly_eval_points": (i32, [vp, vp, sz, vp, sz, vp]),
+        "smi_poly_interpolate_points": (i32, [vp, vp, vp, sz, vp]),
         "smi_lde": (i32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]),
         "smi_trace_pack": (i32, [vp, vp, sz, sz, vp]),
         "smi_hash_leaves": (i32, [vp, vp, sz, vp]),

@@ -740,11 +740,6 @@ __global__ void reverse_kernel(const uint32_t *src, size_t deg, uint32_t *dst, s
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (; i < k; i += step) dst[i] = i <= deg ? src[deg - i] : 0u;   // dst[i] = coefficient deg-i, zero beyond
 }
-__global__ void two_minus_kernel(uint32_t *e, size_t n, uint32_t p) {   // e <- 2 - e as a power series
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t step = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += step) e[i] = fp_sub(i == 0 ? 2u % p : 0u, e[i], p);
-}
 __global__ void sub_kernel(const uint32_t *a, const uint32_t *b, uint32_t *out, size_t n, uint32_t p) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t step = (size_t)gridDim.x * blockDim.x;
@@ -807,17 +802,8 @@ int smi_poly_div(smi_ctx *ctx, const uint64_t *a, size_t na, const uint64_t *b, 
         SMI_TRY(launch_narrow(ctx, stage, B, m, 0));
         reverse_kernel<<<ew_grid(k), 256, 0, ctx->stream>>>(A, (size_t)da, rA, k);
         reverse_kernel<<<ew_grid(k), 256, 0, ctx->stream>>>(B, (size_t)db, rB, k);
-        // g = rB^-1 mod x^k: g_1 = 1 / lead(b), g_2t = g_t * (2 - rB * g_t) mod x^2t
-        const uint32_t g0 = h_inv(ctx, (uint32_t)b[db]);
-        HIP_TRY(ctx, hipMemsetAsync(g, 0, k * 4, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(g, &g0, 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // g0 lives on this frame
-        for (size_t t = 1; t < k; t <<= 1) {
-            const size_t t2 = 2 * t < k ? 2 * t : k;
-            SMI_TRY(dev_mul_trunc(ctx, rB, t2, g, t, e, t2, f1, f2));
-            two_minus_kernel<<<ew_grid(t2), 256, 0, ctx->stream>>>(e, t2, p);
-            SMI_TRY(dev_mul_trunc(ctx, g, t, e, t2, g, t2, f1, f2));
-        }
+        // g = rB^-1 mod x^k: g_1 = 1 / lead(b), g_2t = g_t * (2 - rB * g_t) mod x^2t (poly_tree.h poly_series_inv)
+        SMI_TRY(dev_series_inv(ctx, rB, k, h_inv(ctx, (uint32_t)b[db]), g, e, f1, f2));
         SMI_TRY(dev_mul_trunc(ctx, rA, k, g, k, e, k, f1, f2));            // rev(q)
         reverse_kernel<<<ew_grid(k), 256, 0, ctx->stream>>>(e, k - 1, rA, k);   // q, in rA
         SMI_TRY(launch_widen(ctx, rA, stage, k));

@@ -242,6 +242,8 @@ int dev_lde2(smi_ctx *ctx, const uint32_t *d_coef, uint32_t *d_out, uint32_t log
              size_t coef_stride, size_t out_stride);
 int dev_ntt_shard_first(smi_ctx *ctx, uint32_t *d_strip, uint32_t log_n, uint32_t log_g, uint32_t rank, int inverse, uint64_t offset);
 int dev_ntt_shard_rest(smi_ctx *ctx, uint32_t *d_rows, uint32_t *d_out, uint32_t log_n, uint32_t log_g, int inverse);
+// g = rb^-1 mod x^k by Newton iteration, rb[0] = 1 / g0 (poly.hip): e k words, f1 and f2 2^L >= 2k - 1 words each
+int dev_series_inv(smi_ctx *ctx, const uint32_t *rb, size_t k, uint32_t g0, uint32_t *g, uint32_t *e, uint32_t *f1, uint32_t *f2);
 int check_flag(smi_ctx *ctx);  // syncs; SMI_ERR_NON_CANONICAL if a narrow kernel saw a value >= p
 // caller's (pageable) u64 buffers <-> device u32 residues; synchronous on return
 int host_to_dev_u32(smi_ctx *ctx, const uint64_t *host, size_t n, uint32_t *d_out, int reduce);

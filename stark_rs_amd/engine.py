@@ -152,6 +152,29 @@ class Engine:
                                      r.ctypes.data, C.byref(nr)))
         return q[:nq.value].copy(), r[:nr.value].copy()
 
+    def poly_zerofier(self, domain):
+        """Polynomial::zerofier (mod.rs:77-96): prod (x - d) over any points, n + 1 coefficients (subproduct tree)."""
+        d = _u64(domain)
+        out = np.empty(len(d) + 1, dtype=np.uint64)
+        self._ck(self.L.smi_poly_zerofier(self.h, d.ctypes.data, len(d), out.ctypes.data))
+        return out
+
+    def poly_eval_points(self, coeffs, points):
+        """Polynomial::eval_domain (eval.rs:16-21) at any points, in order (subproduct tree)."""
+        c, x = _u64(coeffs), _u64(points)
+        out = np.empty(len(x), dtype=np.uint64)
+        self._ck(self.L.smi_poly_eval_points(self.h, c.ctypes.data, len(c), x.ctypes.data, len(x), out.ctypes.data))
+        return out
+
+    def poly_interpolate_points(self, domain, values):
+        """Polynomial::interpolate_domain (interpolate.rs:6-44) on any distinct points: n coefficients."""
+        d, v = _u64(domain), _u64(values)
+        if len(d) != len(v):
+            raise StarkMiError(-14, "assertion failed: domain.len() == values.len()")
+        out = np.empty(len(d), dtype=np.uint64)
+        self._ck(self.L.smi_poly_interpolate_points(self.h, d.ctypes.data, v.ctypes.data, len(d), out.ctypes.data))
+        return out
+
     def domain_is_geometric(self, domain):
         d = _u64(domain)
         off = C.c_uint64()

@@ -9,14 +9,18 @@ the reference (src/ff.rs:138-233) -- they are the glue between kernel calls, not
 Anything that touches a whole codeword, polynomial or tree goes to the device:
 
     Polynomial.interpolate_domain / eval_domain / scale   -> smi_intt / smi_coset_ntt / smi_poly_scale
+    Polynomial.zerofier                                    -> smi_poly_zerofier (subproduct tree, any points)
     Hash.from_field_elements / combine / from_bytes       -> smi_hash_* (device kernels, even for one digest)
     MerkleTree.new / commit / open                        -> smi_merkle_*
     FiatShamir.challenge                                   -> smi_hash_bytes
     Fri.fold_codeword / commit / prove                     -> smi_fri_fold / smi_fri_commit / smi_fri_prove
 
-Domains that are not geometric (offset * omega^k) have no fast path: the mirror raises
-StarkMiError("domain is not offset*omega^k") -- the Rust shim falls back to the original CPU
-code there; this package has no CPU compute path by design.
+Polynomial.interpolate_domain / eval_domain keep the fast-path contract: on a domain that is not
+geometric (offset * omega^k) the mirror raises StarkMiError("domain is not offset*omega^k").  Such
+domains have a general GPU path of their own, which the Rust shim takes there:
+smi_poly_interpolate_points / smi_poly_eval_points, i.e. Engine.poly_interpolate_points /
+Engine.poly_eval_points (subproduct trees on the device).  This package has no CPU compute path by
+design.
 """
 import numpy as np
 
@@ -222,16 +226,12 @@ class Polynomial:
 
     @staticmethod
     def zerofier(domain):
-        """mod.rs:77-96: prod (x - d).  The reference multiplies the factors in one by one; here a
-        balanced product tree of device NTT products gives the same polynomial."""
+        """mod.rs:77-96: prod (x - d).  The reference multiplies the factors in one by one; here one
+        subproduct tree on the device (smi_poly_zerofier) gives the same polynomial."""
         field = domain[0].field
-        polys = [Polynomial([FieldElement((-d.value) % field.p, field), field.one()], field) for d in domain]
-        while len(polys) > 1:
-            nxt = [polys[i] * polys[i + 1] for i in range(0, len(polys) - 1, 2)]
-            if len(polys) % 2:
-                nxt.append(polys[-1])
-            polys = nxt
-        return polys[0]
+        d = np.fromiter((e.value % field.p for e in domain), dtype=np.uint64, count=len(domain))
+        z = field.engine().poly_zerofier(d)
+        return Polynomial([FieldElement(int(c), field) for c in z], field)
 
     @staticmethod
     def interpolate_domain(domain, values):

@@ -98,6 +98,28 @@ pub struct smi_mgpu_coll {
     pub all_reduce_sum_u8: Option<unsafe extern "C" fn(user: *mut c_void, d_buf: *mut c_void, bytes: usize) -> c_int>,
 }
 
+/// smi_air: the flat tables of an AIR (host pointers; the entry points take it as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air {
+    pub n_constraints: u32,
+    pub n_terms: u32,
+    pub n_factors: u32,
+    pub n_boundary: u32,
+    pub constraint_first_term: *const u32,
+    pub term_coeff: *const u64,
+    pub term_first_factor: *const u32,
+    pub factor_var: *const u32,
+    pub factor_exp: *const u32,
+    pub boundary_col: *const u32,
+    pub boundary_row: *const u64,
+    pub boundary_value: *const u64,
+}
+pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
+pub const SMI_AIR_MAX_TERMS: u32 = 1024;
+pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
+pub const SMI_AIR_MAX_EXP: u32 = 255;
+pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
+
 #[link(name = "starkmi")]
 extern "C" {
     pub fn smi_status_string(status: c_int) -> *const c_char;
@@ -175,6 +197,12 @@ extern "C" {
     pub fn smi_dev_combine_columns(ctx: *mut smi_ctx, d_cols: *const u32, n_cols: u32, len: usize, stride: usize, d_weights: *const u64, d_out: *mut u32) -> c_int;
     pub fn smi_dev_stark_prove(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, d_trace_cols: *const u32, column_roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
     pub fn smi_stark_verify(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, column_roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
+    pub fn smi_air_plan(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
+    pub fn smi_air_last_error() -> *const c_char;
+    pub fn smi_dev_air_compose(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_lde: *const u32, stride: usize, d_weights: *const u64, d_out: *mut u32) -> c_int;
+    pub fn smi_dev_air_check(ctx: *mut smi_ctx, air: *const c_void, n_cols: u32, log_n: u32, d_trace_cols: *const u32, ok: *mut c_int, constraint: *mut u32, row: *mut u64) -> c_int;
+    pub fn smi_dev_air_prove(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, column_roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
+    pub fn smi_air_verify(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, column_roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -573,4 +601,122 @@ pub fn lde(ctx: &Context, cols: &[u64], n_cols: u32, log_n: u32, log_blowup: u32
     let mut out = vec![0u64; (n_cols as usize) << (log_n + log_blowup)];
     ctx.check(unsafe { smi_lde(ctx.raw, cols.as_ptr(), n_cols, log_n, log_blowup, trace_offset, lde_offset, out.as_mut_ptr()) });
     out
+}
+
+/// An AIR over `n_cols` trace columns (include/stark_mi.h, "AIR"): boundary points and transition constraints,
+/// flattened to `smi_air` for the duration of a call.  The reference has no counterpart (its `Trace` has no
+/// consumer); this is where a `Stark::prove` would call.
+#[derive(Clone, Debug, Default)]
+pub struct Air {
+    pub n_cols: u32,
+    constraint_first_term: Vec<u32>,
+    term_coeff: Vec<u64>,
+    term_first_factor: Vec<u32>,
+    factor_var: Vec<u32>,
+    factor_exp: Vec<u32>,
+    boundary_col: Vec<u32>,
+    boundary_row: Vec<u64>,
+    boundary_value: Vec<u64>,
+}
+
+/// One factor of a monomial: column, row shift (0 = this row, 1 = next row), exponent.
+#[derive(Clone, Copy, Debug)]
+pub struct AirFactor {
+    pub col: u32,
+    pub next: bool,
+    pub exp: u32,
+}
+
+impl Air {
+    pub fn new(n_cols: u32) -> Air {
+        Air { n_cols, constraint_first_term: vec![0], term_first_factor: vec![0], ..Default::default() }
+    }
+    /// Column `col` holds `value` (canonical) in row `row`.
+    pub fn boundary(&mut self, col: u32, row: u64, value: u64) -> &mut Air {
+        self.boundary_col.push(col);
+        self.boundary_row.push(row);
+        self.boundary_value.push(value);
+        self
+    }
+    /// One transition constraint: a sum of `(coefficient, factors)` terms that vanishes on every pair of consecutive rows.
+    pub fn transition(&mut self, terms: &[(u64, Vec<AirFactor>)]) -> &mut Air {
+        for (coeff, factors) in terms {
+            self.term_coeff.push(*coeff);
+            for f in factors {
+                self.factor_var.push(f.col + if f.next { self.n_cols } else { 0 });
+                self.factor_exp.push(f.exp);
+            }
+            self.term_first_factor.push(self.factor_var.len() as u32);
+        }
+        self.constraint_first_term.push(self.term_coeff.len() as u32);
+        self
+    }
+    fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        let raw = smi_air {
+            n_constraints: (self.constraint_first_term.len() - 1) as u32,
+            n_terms: self.term_coeff.len() as u32,
+            n_factors: self.factor_var.len() as u32,
+            n_boundary: self.boundary_col.len() as u32,
+            constraint_first_term: self.constraint_first_term.as_ptr(),
+            term_coeff: self.term_coeff.as_ptr(),
+            term_first_factor: self.term_first_factor.as_ptr(),
+            factor_var: self.factor_var.as_ptr(),
+            factor_exp: self.factor_exp.as_ptr(),
+            boundary_col: self.boundary_col.as_ptr(),
+            boundary_row: self.boundary_row.as_ptr(),
+            boundary_value: self.boundary_value.as_ptr(),
+        };
+        f(&raw as *const smi_air as *const c_void)
+    }
+    /// `smi_air_plan` (host only): `(degree, FRI expansion factor)`; panics naming the limit that was broken.
+    pub fn plan(&self, p: u64, cfg: &smi_stark_cfg) -> (u32, u64) {
+        let (mut d, mut e) = (0u32, 0u64);
+        let st = self.with_raw(|a| unsafe { smi_air_plan(p, cfg, a, &mut d, &mut e) });
+        if st != 0 {
+            let why = unsafe { CStr::from_ptr(smi_air_last_error()) }.to_string_lossy().into_owned();
+            panic!("{}: {}", status_text(st), why);
+        }
+        (d, e)
+    }
+    /// `smi_dev_air_check`: `None` when the device trace satisfies the AIR, else `(constraint, row)` of the first
+    /// violation (boundary points first; a transition constraint k is reported as `n_boundary + k`).
+    pub fn check_trace(&self, ctx: &Context, log_n: u32, d_trace_cols: *const u32) -> Option<(u32, u64)> {
+        let (mut ok, mut con, mut row) = (0 as c_int, 0u32, 0u64);
+        ctx.check(self.with_raw(|a| unsafe { smi_dev_air_check(ctx.raw, a, self.n_cols, log_n, d_trace_cols, &mut ok, &mut con, &mut row) }));
+        if ok != 0 { None } else { Some((con, row)) }
+    }
+    /// `smi_dev_air_compose`: the composition codeword of the extended device columns under `n_cols + K` device weights.
+    pub fn compose(&self, ctx: &Context, cfg: &smi_stark_cfg, d_lde: *const u32, stride: usize, d_weights: *const u64, d_out: *mut u32) {
+        ctx.check(self.with_raw(|a| unsafe { smi_dev_air_compose(ctx.raw, cfg, a, d_lde, stride, d_weights, d_out) }));
+    }
+    /// `smi_dev_air_prove` -> (column roots, proof bytes).  `check_trace` (the default a caller should pass: true)
+    /// runs `smi_dev_air_check` first and panics naming the first violated constraint and row.
+    pub fn prove(&self, ctx: &Context, cfg: &smi_stark_cfg, d_trace_cols: *const u32, check_trace: bool) -> (Vec<[u8; 32]>, Vec<u8>) {
+        if check_trace {
+            if let Some((con, row)) = self.check_trace(ctx, cfg.log_n, d_trace_cols) {
+                let why = unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned();
+                panic!("the trace violates constraint {} at row {}: {}", con, row, why);
+            }
+        }
+        let mut roots = vec![[0u8; 32]; cfg.n_cols as usize];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_dev_air_prove(ctx.raw, cfg, a, d_trace_cols, roots.as_mut_ptr() as *mut u8, &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut())
+        }));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (roots, bytes)
+    }
+    /// `smi_air_verify` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify(&self, ctx: &Context, cfg: &smi_stark_cfg, column_roots: &[[u8; 32]], proof: &[u8]) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_air_verify(ctx.raw, cfg, a, column_roots.as_ptr() as *const u8, proof.as_ptr(), proof.len(), &mut accept)
+        }));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
 }

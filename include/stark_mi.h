@@ -374,6 +374,98 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
 int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *column_roots, const uint8_t *proof, size_t proof_len,
                      int *accept);
 
+/* ---- AIR: boundary and transition constraints over the committed columns --------------------
+ * The reference stops at Fri (its Trace has a constructor and no consumer); its naming follows the
+ * "Anatomy of a STARK" construction, whose next step this is: a proof that the W committed columns satisfy
+ * boundary constraints (column c holds value v in row r) and transition constraints (polynomials in the cells of
+ * two consecutive rows that vanish on every row pair (r, r+1), r = 0 .. n-2, no wrap-around).
+ *
+ * Flat, pointer-plus-count, host memory.  Transition constraint k is
+ *   C_k(X_0 .. X_{2W-1}) = sum_{terms of k} coeff * prod_{factors} X_var^exp,   var = col + n_cols * shift,
+ * shift 0 = this row, 1 = next row.  Its degree d_k is the largest sum of exponents over its terms,
+ * d = max(1, max_k d_k), D = the smallest power of two >= max(1, d-1), E = 2^log_blowup / D: the expansion factor
+ * FRI runs at (the quotients have degree < D * n).
+ *
+ * The composition codeword.  p the modulus, n = 2^log_n, B = 2^log_blowup, N = nB, w = omega_n, tau = trace_offset,
+ * h = lde_offset, x_i = h * omega_N^i, lde[c][i] = f_c(x_i) (smi_dev_lde, natural order; the next row is the index
+ * shift f_c(w x_i) = lde[c][(i + B) mod N]).
+ *   column c with boundary points {(r_j, v_j)}: I_c the interpolant through (tau w^r_j, v_j), Z_c(x) = prod_j (x - tau w^r_j),
+ *       term_c(x_i) = (lde[c][i] - I_c(x_i)) / Z_c(x_i);   without boundary points term_c(x_i) = lde[c][i];
+ *   tq_k(x_i) = C_k(lde[.][i], lde[.][(i+B) mod N]) * (x_i - tau w^(n-1)) / (x_i^n - tau^n);
+ *   cw[i] = sum_{c<W} (weight_c mod p) * term_c(x_i) + sum_{k<K} (weight_{W+k} mod p) * tq_k(x_i)   (mod p).
+ * With K = 0 and no boundary point this is smi_dev_combine_columns.
+ *
+ * Limits (SMI_ERR_BAD_ARG, the text of smi_air_last_error / smi_last_error names the one that was broken):
+ *   n_cols <= 64; n_constraints <= SMI_AIR_MAX_CONSTRAINTS; n_terms <= SMI_AIR_MAX_TERMS; at most
+ *   SMI_AIR_MAX_TERM_FACTORS factors in a term; 1 <= factor_exp <= SMI_AIR_MAX_EXP; factor_var < 2 * n_cols; at most
+ *   SMI_AIR_MAX_BOUNDARY_PER_COL boundary points in a column, a (col, row) pair at most once, row < n;
+ *   offsets in 1 .. p-1.  Refused as well (SMI_ERR_BAD_ARG): lde_offset^N == 1, and (lde_offset / trace_offset)^N == 1 --
+ *   the evaluation coset then meets the trace domain and a zerofier vanishes on it (the second is the exact condition
+ *   when trace_offset != 1; the first is kept for every trace_offset).  A coefficient or boundary value >= p gives
+ *   SMI_ERR_NON_CANONICAL; E < 4 gives SMI_ERR_EXPANSION_TOO_SMALL (Fri::new's assert, src/fri.rs:45: the quotients
+ *   would not fit under the degree bound).
+ *
+ * Out of scope: row shifts other than 0 and 1; periodic or public-input columns; zero-knowledge randomisers;
+ * degree-adjusted terms (alpha + beta * x^shift); binding a digest of the AIR into the transcript; an extension
+ * field (with a 30-bit modulus the soundness of any proof from this library is bounded by the field, the reference's
+ * choice); a multi-GPU twin.
+ *
+ * The entry points take the description as `const void *air` (a pointer to an smi_air): every parameter type of this
+ * header is a scalar, a pointer to one, or one of the handle / configuration types the bindings already know. */
+#define SMI_AIR_MAX_CONSTRAINTS 64
+#define SMI_AIR_MAX_TERMS 1024
+#define SMI_AIR_MAX_TERM_FACTORS 8
+#define SMI_AIR_MAX_EXP 255
+#define SMI_AIR_MAX_BOUNDARY_PER_COL 16
+typedef struct smi_air {
+    uint32_t n_constraints, n_terms, n_factors, n_boundary;
+    const uint32_t *constraint_first_term;  /* n_constraints + 1, ascending, [0] = 0, last = n_terms          */
+    const uint64_t *term_coeff;             /* n_terms, canonical (< p)                                        */
+    const uint32_t *term_first_factor;      /* n_terms + 1; a term with no factor is a constant                */
+    const uint32_t *factor_var;             /* n_factors; var = col + n_cols * shift, shift 0 = this row, 1 = next row */
+    const uint32_t *factor_exp;             /* n_factors; >= 1                                                 */
+    const uint32_t *boundary_col;           /* n_boundary                                                      */
+    const uint64_t *boundary_row;           /* n_boundary; < n, a (col, row) pair at most once                 */
+    const uint64_t *boundary_value;         /* n_boundary; canonical                                           */
+} smi_air;
+/* Host only, no context (callable without a GPU, like smi_fri_num_rounds): validates air against cfg (log_n,
+ * log_blowup, n_cols and the two offsets are read) for the modulus p and returns d and E.  Every AIR entry point
+ * below runs it first. */
+int smi_air_plan(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint64_t *fri_expansion);
+/* The text of the calling thread's last failed smi_air_plan ("" after a success). */
+const char *smi_air_last_error(void);
+/* The composition codeword on its own: d_lde = n_cols extended columns (stride elements apart, stride >= N), d_weights
+ * = n_cols + n_constraints unreduced u64 challenges on the device, d_out = N elements.  The tables of the AIR are
+ * copied to the device from pageable memory before the launch; nothing else synchronises.  The tiled kernel needs
+ * d_lde 16-byte aligned, stride a multiple of 4 and a tile of all columns within 64 KB of LDS (n_cols * (64 + 2^log_blowup)
+ * * 4 bytes at the least); otherwise a slower kernel without tiles computes the same codeword (one power per point). */
+int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_lde, size_t stride,
+                        const uint64_t *d_weights, uint32_t *d_out);
+/* The boundary points and every C_k on the n-1 row pairs of the trace itself (column-major, n apart; no extension, no
+ * division).  *ok = 1, or 0 with the first violation in (kind, index, row) order -- boundary points (index = position
+ * in the boundary lists) before transition constraints, lowest index, lowest row -- in *constraint and *row, and a
+ * sentence naming it in smi_last_error.  *constraint is the boundary point's position or n_boundary + k.
+ * Synchronises (the verdict comes back to the host). */
+int smi_dev_air_check(smi_ctx *ctx, const void *air, uint32_t n_cols, uint32_t log_n, const uint32_t *d_trace_cols, int *ok,
+                      uint32_t *constraint, uint64_t *row);
+/* trace -> LDE -> one tree per column -> weights -> composition codeword -> Fri::prove at expansion factor E ->
+ * openings.  cfg->row_leaves must be 0 (SMI_ERR_BAD_ARG); open_columns is taken as set.
+ * Transcript: empty; for c < W absorb column root c, weight_c = challenge(); for k < K absorb k as 8 little-endian
+ * bytes, weight_{W+k} = challenge(); FRI continues this transcript of 32W + 8K bytes (as smi_dev_fri_prove_fs would).
+ * Proof bytes: the FRI objects, then per colinearity test s, with a = top[s] mod N/2 and b = a + N/2, the rows
+ * FieldElements(col_0 .. col_{W-1}) at a, b and -- only when K > 0 -- at (a+B) mod N, (b+B) mod N; then for every s
+ * and inside it every c the MerklePaths in the same position order.
+ * stage_ms (optional) gets five values {lde, commit, compose, fri, open}.  Does not run smi_dev_air_check: a proof
+ * made from a trace that violates the AIR is rejected by the verifier. */
+int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
+                      uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms);
+/* Verifier of smi_dev_air_prove: Fri::verify of the leading objects with the transcript above and expansion factor E,
+ * the length of the opening section, every authentication path against its column root, and the composition codeword
+ * recomputed at x_a and x_b from the opened rows against the layer-0 triple.  *accept and smi_last_error as in
+ * smi_stark_verify. */
+int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *column_roots, const uint8_t *proof,
+                   size_t proof_len, int *accept);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous
  * blocks (rank g holds [g*N/G, (g+1)*N/G)), and the build-defined trace -> proof composition of

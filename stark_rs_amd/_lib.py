@@ -46,6 +46,13 @@ class FriCfg(C.Structure):
                 ("expansion_factor", C.c_uint64), ("num_colinearity_tests", C.c_uint64)]
 
 
+class Air(C.Structure):
+    """smi_air (include/stark_mi.h): flat host tables; mirror.Air.flatten fills one and keeps the arrays alive"""
+    _fields_ = [("n_constraints", C.c_uint32), ("n_terms", C.c_uint32), ("n_factors", C.c_uint32), ("n_boundary", C.c_uint32),
+                ("constraint_first_term", u32p), ("term_coeff", u64p), ("term_first_factor", u32p), ("factor_var", u32p),
+                ("factor_exp", u32p), ("boundary_col", u32p), ("boundary_row", u64p), ("boundary_value", u64p)]
+
+
 def build(force=False):
     """Compile libstarkmi.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
@@ -161,6 +168,12 @@ def lib():
         "smi_dev_fri_prove_fs": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(vp)]),
         "smi_dev_combine_columns": (i32, [vp, vp, C.c_uint32, sz, sz, vp, vp]),
         "smi_dev_stark_prove": (i32, [vp, C.POINTER(StarkCfg), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
+        "smi_air_plan": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), u32p, u64p]),
+        "smi_air_last_error": (C.c_char_p, []),
+        "smi_dev_air_compose": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, sz, vp, vp]),
+        "smi_dev_air_check": (i32, [vp, C.POINTER(Air), C.c_uint32, C.c_uint32, vp, C.POINTER(i32), u32p, u64p]),
+        "smi_dev_air_prove": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
+        "smi_air_verify": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

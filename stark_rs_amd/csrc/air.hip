@@ -1,0 +1,309 @@
+// air.hip -- AIR constraints over the committed columns: the composition codeword (boundary quotients, transition
+// quotients and unconstrained columns under Fiat-Shamir weights), the trace checker and the prover that feeds the
+// codeword to Fri::prove.  The definition, the limits and the proof layout are in include/stark_mi.h ("AIR"); the
+// per-point evaluator is air_core.h, shared with the CPU emulator (emu_air.cpp).  The verifier is in verify.hip.
+//
+// air_compose_kernel.  The floor is one read of the W extended columns and one write of the codeword, 4 (W + 1) N
+// bytes.  A workgroup walks tiles of T points (grid-stride over the tiles, combine_columns_kernel's shape: the tile
+// order does not matter to HBM and a fixed grid keeps the per-workgroup set-up -- the weights, one power -- off the
+// per-tile path).  Per tile it stages T + B elements of every column into LDS with 16-byte loads, the halo of B
+// wrapping at N, so the next-row operand of point i (index i + B) is read from HBM once, as somebody's this-row
+// operand; the evaluator then walks the AIR's terms and fetches operands from LDS (lane j reads address j: no bank
+// conflict).  The AIR tables are indexed with wave-uniform values only, so they are scalar loads; x_i is one table
+// entry times one per-tile power, then a multiplication per further point; 1 / (x^n - tau^n) is a B-entry table and
+// the 1 / Z_c(x_i) share one Fermat inversion per AIR_INV_BATCH values.
+#include <string>
+#include <vector>
+
+#include "air_core.h"
+#include "hash_core.h"
+#include "internal.h"
+#include "mgpu_core.h"
+
+int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
+                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
+int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
+            smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
+            uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src,
+            const FsSeed *seed = nullptr);
+
+template <int P>
+__global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
+                                                                 const uint64_t *__restrict__ weights, uint32_t T,
+                                                                 uint32_t *__restrict__ out) {
+    extern __shared__ __align__(16) uint32_t air_lds[];
+    uint32_t *w_m = air_lds, *tile = air_lds + AIR_MAX_WEIGHTS;
+    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (1u << A.log_B);
+    for (uint32_t i = tid; i < A.W + A.K; i += threads) w_m[i] = to_mont_u64(weights[i], F);
+    const uint32_t step_m = mont_pow(A.omega_m, threads, F);
+    const uint64_t tiles = A.N / T;
+    // x of the tile's first point: one power per workgroup, then one product per tile (grid-stride: gridDim.x * T further)
+    uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, (uint64_t)blockIdx.x * T, F), F);
+    const uint32_t xstride_m = mont_pow(A.omega_m, (uint64_t)gridDim.x * T, F);
+    for (uint64_t tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const uint64_t base = tl * T;
+        __syncthreads();   // the tile of the round before is consumed
+        for (uint32_t c = 0; c < A.W; c++)
+            for (uint32_t e = tid * 4; e < pitch; e += threads * 4)   // pitch, base and N are multiples of 4: no access straddles the wrap
+                *(uint4 *)(tile + c * pitch + e) = *(const uint4 *)(cols + c * stride + ((base + e) & (A.N - 1)));
+        __syncthreads();   // tile (and, the first time, the weights) visible
+        air_tile_thread<P>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out);
+        xbase_m = mont_mul(xbase_m, xstride_m, F);   // wave-uniform
+    }
+}
+
+__global__ __launch_bounds__(AIR_BLOCK) void air_direct_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
+                                                                const uint64_t *__restrict__ weights, uint32_t *__restrict__ out) {
+    __shared__ uint32_t w_m[AIR_MAX_WEIGHTS];
+    for (uint32_t i = threadIdx.x; i < A.W + A.K; i += blockDim.x) w_m[i] = to_mont_u64(weights[i], F);
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point(A, F, w_m, cols, stride, i, out);
+}
+
+// the trace itself: thread i checks boundary point i (i < nb) and the row pair (i, i + 1) (i < n - 1); the first
+// violation in (kind, index, row) order wins an atomic minimum over the key kind << 63 | index << 32 | row
+__global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t nb,
+                                                         const uint32_t *__restrict__ bnd, unsigned long long *first) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nb) {
+        const uint32_t col = bnd[3 * i], row = bnd[3 * i + 1], val = bnd[3 * i + 2];
+        if (trace[col * n + row] != val) atomicMin(first, ((unsigned long long)i << 32) | row);
+    }
+    if (i + 1 < n)
+        for (uint32_t k = 0; k < A.K; k++) {
+            const uint32_t v = air_constraint(A, F, k, [&](uint32_t var) { return var < A.W ? trace[var * n + i] : trace[(var - A.W) * n + i + 1]; });
+            if (v) {
+                atomicMin(first, (1ull << 63) | ((unsigned long long)k << 32) | i);
+                break;   // a higher k of the same row cannot come first
+            }
+        }
+}
+
+// openings of the W column trees at a, b and -- R == 4 -- (a + B) mod N, (b + B) mod N (mgpu_core.h): one workgroup per
+// (test, column)
+__global__ __launch_bounds__(64) void air_open_kernel(const MgSide *cols, uint32_t W, const uint64_t *top, uint32_t t, uint32_t R, uint64_t B,
+                                                       uint8_t *out) {
+    mg_column_open_write_n(cols, W, blockIdx.y, top[blockIdx.x], blockIdx.x, t, 0, out, threadIdx.x, 64, R, B);
+}
+
+namespace {
+thread_local std::string g_air_err;
+
+// validated tables of (cfg, air) on the host, bound to host memory
+int air_host(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) {
+    std::string why;
+    const int rc = air_validate(ctx->fs.F.p, cfg, air, nullptr, E, &why);
+    if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    const uint32_t log_N = cfg->log_n + cfg->log_blowup;
+    if (log_N > ctx->fs.K)
+        return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, H);
+    return SMI_OK;
+}
+
+// the blob to d_blob (room for H.blob.size() words), the launch of the codeword kernel
+int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights,
+                       uint32_t *d_out) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_blob, H.blob.data(), H.blob.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    air_bind(H, d_blob);
+    const AirDev &A = H.dev;
+    const Fp F = ctx->fs.F;
+    const uint64_t B = 1ull << A.log_B;
+    AirTile tl = air_tile(A.W, B, A.N);
+    if (B < 4 || (stride & 3) || (((uintptr_t)d_lde) & 15u)) tl.T = 0;   // 16-byte loads need aligned columns
+    ProfScope ps(ctx, "air_compose_kernel", 4.0 * (A.W + 1.0) * (double)A.N);
+    if (!tl.T) {
+        size_t grid = (size_t)((A.N + AIR_BLOCK - 1) / AIR_BLOCK);
+        if (grid > 4096) grid = 4096;
+        air_direct_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out);
+    } else {
+        const uint64_t tiles = A.N / tl.T;
+        const size_t lds = (size_t)AIR_MAX_WEIGHTS * 4 + (size_t)A.W * (tl.T + B) * 4;
+        const uint64_t cap = (uint64_t)ctx->num_cus * 8;
+        const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
+        if (tl.P == 4) air_compose_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+        else if (tl.P == 2) air_compose_kernel<2><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+        else air_compose_kernel<1><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+}  // namespace
+
+int smi_air_plan(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint64_t *fri_expansion) {
+    g_air_err.clear();
+    return air_validate(p, cfg, (const smi_air *)air, degree, fri_expansion, &g_air_err);
+}
+const char *smi_air_last_error(void) { return g_air_err.c_str(); }
+
+int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_lde, size_t stride,
+                        const uint64_t *d_weights, uint32_t *d_out) {
+    if (!ctx || !cfg || !air || !d_lde || !d_weights || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    AirHost H;
+    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr));
+    if (stride < H.dev.N) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose: stride < N");
+    void *d_blob = nullptr;
+    SMI_TRY(ctx_tmp(ctx, 3, H.blob.size() * 4, &d_blob));
+    return air_launch_compose(ctx, H, (uint32_t *)d_blob, d_lde, stride, d_weights, d_out);
+}
+
+int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t log_n, const uint32_t *d_trace_cols, int *ok,
+                      uint32_t *constraint, uint64_t *row) {
+    const smi_air *air = (const smi_air *)air_;
+    if (!ctx || !air || !d_trace_cols || !ok) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *ok = 0;
+    smi_stark_cfg cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.n_cols = n_cols;
+    cfg.log_n = log_n;
+    std::string why;
+    const int rc = air_validate(ctx->fs.F.p, &cfg, air, nullptr, nullptr, &why, true);
+    if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    AirHost H;
+    air_build(ctx->fs.F, 1, &cfg, air, &H, true);
+    const uint32_t nb = air->n_boundary;
+    const size_t words = H.blob.size(), total = words + 3 * (size_t)nb + 2;
+    std::vector<uint32_t> up(H.blob);
+    for (uint32_t j = 0; j < nb; j++) {
+        up.push_back(air->boundary_col[j]);
+        up.push_back((uint32_t)air->boundary_row[j]);
+        up.push_back((uint32_t)air->boundary_value[j]);
+    }
+    void *d_blob = nullptr;
+    SMI_TRY(ctx_tmp(ctx, 3, total * 4 + 16, &d_blob));
+    unsigned long long *d_first = (unsigned long long *)((uint8_t *)d_blob + ((total * 4 + 7) & ~(size_t)7));
+    HIP_TRY(ctx, hipMemcpyAsync(d_blob, up.data(), up.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_first, 0xff, 8, ctx->stream));
+    air_bind(H, (const uint32_t *)d_blob);
+    const uint64_t n = 1ull << log_n, work = n > nb ? n : nb;
+    air_check_kernel<<<(uint32_t)((work + 255) / 256), 256, 0, ctx->stream>>>(H.dev, ctx->fs.F, d_trace_cols, n, nb, (const uint32_t *)d_blob + words,
+                                                                             d_first);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long first = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&first, d_first, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (first == ~0ull) {
+        *ok = 1;
+        return SMI_OK;
+    }
+    const bool transition = first >> 63;
+    const uint32_t idx = (uint32_t)((first >> 32) & 0x7fffffffu);
+    const uint64_t r = first & 0xffffffffull;
+    if (constraint) *constraint = transition ? nb + idx : idx;
+    if (row) *row = r;
+    ctx->err = transition ? "air_check: transition constraint " + std::to_string(idx) + " is violated on rows " + std::to_string(r) + " and " + std::to_string(r + 1)
+                          : "air_check: boundary point " + std::to_string(idx) + " (column " + std::to_string(air->boundary_col[idx]) + ", row " + std::to_string(r) +
+                                ") does not hold value " + std::to_string(air->boundary_value[idx]);
+    return SMI_OK;
+}
+
+int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const uint32_t *d_trace_cols, uint8_t *column_roots,
+                      uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms) {
+    const smi_air *air = (const smi_air *)air_;
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_prove: column trees only (row_leaves must be 0)");
+    AirHost H;
+    uint64_t E = 0;
+    SMI_TRY(air_host(ctx, cfg, air, &H, &E));
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_N = cfg->log_n + cfg->log_blowup;
+    const size_t N = (size_t)1 << log_N;
+    SMI_TRY(arena_reset(ctx));
+    struct Events {   // destroyed on every return path
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs;
+    const bool timed = stage_ms != nullptr;
+    if (timed)
+        for (int i = 0; i < 6; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+
+    const size_t tree_stride = 2 * N * 32;
+    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, N * 4);
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * (size_t)(W + K));
+    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
+    uint8_t *tree_base = (uint8_t *)arena_alloc(ctx, tree_stride * W);
+    if (!d_lde || !d_cw || !d_weights || !d_blob || !tree_base) return smi_fail(ctx, SMI_ERR_OOM, "air_prove: device memory");
+    mark(0);
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, cfg->log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
+    mark(1);
+    SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
+    mark(2);
+    // The W roots make one small round trip: the transcript (roots, then the constraint indices) and its weights
+    // are computed on the host, where fri_run's seed is computed anyway (FsSeed, internal.h).
+    std::vector<uint8_t> roots(32 * (size_t)W), tr;
+    HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, W, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> weights(W + K);
+    auto challenge = [&]() {
+        uint32_t d[8];
+        hashc::hash_bytes(tr.data(), tr.size(), d);
+        return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
+    };
+    for (uint32_t c = 0; c < W; c++) {
+        tr.insert(tr.end(), roots.begin() + 32 * c, roots.begin() + 32 * c + 32);
+        weights[c] = challenge();
+    }
+    for (uint32_t k = 0; k < K; k++) {
+        for (int i = 0; i < 8; i++) tr.push_back((uint8_t)((uint64_t)k >> (8 * i)));
+        weights[W + k] = challenge();
+    }
+    FsSeed seed;
+    hashc::fs_seed(tr.data(), tr.size(), seed.s, &seed.phase);
+    if (column_roots) memcpy(column_roots, roots.data(), roots.size());
+    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_launch_compose(ctx, H, d_blob, d_lde, N, d_weights, d_cw));
+    mark(3);
+    smi_fri_cfg fc;
+    fc.omega = h_root(ctx, log_N);
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = N;
+    fc.expansion_factor = E;
+    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> top_tmp(top_indices ? 0 : (size_t)cfg->num_colinearity_tests);
+    if (!top_indices && !top_tmp.empty()) top_indices = top_tmp.data();
+    SMI_TRY(fri_run(ctx, &fc, d_cw, N, true, false, nullptr, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr, nullptr, &seed));
+    mark(4);
+    if (cfg->num_colinearity_tests) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
+        std::vector<MgSide> sides(W);
+        for (uint32_t c = 0; c < W; c++) {
+            MgSide &sd = sides[c];
+            sd.cw = d_lde + (size_t)c * N; sd.nodes = tree_base + c * tree_stride; sd.top = nullptr; sd.len = N; sd.blk = N; sd.depth_local = log_N; sd.depth_top = 0;
+        }
+        const size_t ob = (size_t)mg_column_open_bytes(W, t, log_N, R);
+        MgSide *d_sides = (MgSide *)arena_alloc(ctx, sizeof(MgSide) * W);
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob);
+        if (!d_sides || !d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove: column openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_sides, sides.data(), sizeof(MgSide) * W, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, top_indices, 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(d_open, 0, ob, ctx->stream));
+        air_open_kernel<<<dim3(t, W), 64, 0, ctx->stream>>>(d_sides, W, d_top, t, R, 1ull << cfg->log_blowup, d_open);
+        HIP_TRY(ctx, hipGetLastError());
+        const size_t at = bytes.size();
+        bytes.resize(at + ob);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    mark(5);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed)
+        for (int i = 0; i < 5; i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
+    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
+    memcpy(*proof, bytes.data(), bytes.size());
+    *proof_len = bytes.size();
+    return SMI_OK;
+}

@@ -1,0 +1,90 @@
+// emu_air.cpp -- CPU emulator of the AIR entry points (TEST INFRASTRUCTURE).
+//
+// emu_air_compose runs air_compose_kernel's own structure in host memory: the tile choice of air_tile, the staging of
+// T + B elements per column with the wrap at N, and the per-thread body air_tile_thread (air_core.h) one "thread" at a
+// time; where the kernel takes air_direct_kernel the emulator runs air_direct_point.  emu_air_check evaluates the
+// boundary points and the constraints with the kernels' air_constraint and keeps the first violation in the order the
+// device's atomic minimum does.  Same arguments and statuses as the C ABI, with (p, g) in place of a context.
+// There is no emu_air_prove / emu_air_verify: the emulator has no single-device Fri::prove loop to continue a
+// transcript with (emu_mgpu.cpp emulates the multi-GPU round loop only), and the verifier is host code already.
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "air_core.h"
+#include "tables.h"
+
+namespace {
+template <int P>
+void emu_tiles(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, const AirTile &tl, uint32_t *out) {
+    const uint32_t B = 1u << A.log_B, pitch = tl.T + B;
+    std::vector<uint32_t> tile((size_t)A.W * pitch);
+    const uint32_t step_m = mont_pow(A.omega_m, tl.threads, F);
+    for (uint64_t base = 0; base < A.N; base += tl.T) {
+        for (uint32_t c = 0; c < A.W; c++)
+            for (uint32_t e = 0; e < pitch; e++) tile[(size_t)c * pitch + e] = cols[c * stride + ((base + e) & (A.N - 1))];
+        const uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, base, F), F);
+        for (uint32_t tid = 0; tid < tl.threads; tid++) air_tile_thread<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out);
+    }
+}
+}  // namespace
+
+extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *lde, uint64_t stride,
+                               const uint64_t *weights, uint32_t *out, int force_direct) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
+    std::string why;
+    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why);
+    if (rc != SMI_OK) return rc;
+    const uint32_t log_N = cfg->log_n + cfg->log_blowup;
+    if (log_N > fs.K) return SMI_ERR_UNSUPPORTED_PRIME;
+    AirHost H;
+    air_build(fs.F, host_powmod(fs.wmax[0], 1ull << (fs.K - log_N), fs.F.p), cfg, air, &H);
+    const AirDev &A = H.dev;
+    if (stride < A.N) return SMI_ERR_BAD_ARG;
+    std::vector<uint32_t> w_m(A.W + A.K);
+    for (uint32_t i = 0; i < A.W + A.K; i++) w_m[i] = to_mont_u64(weights[i], fs.F);
+    AirTile tl = air_tile(A.W, 1ull << A.log_B, A.N);
+    if (force_direct || (stride & 3)) tl.T = 0;
+    if (!tl.T)
+        for (uint64_t i = 0; i < A.N; i++) air_direct_point(A, fs.F, w_m.data(), lde, stride, i, out);
+    else if (tl.P == 4) emu_tiles<4>(A, fs.F, w_m.data(), lde, stride, tl, out);
+    else if (tl.P == 2) emu_tiles<2>(A, fs.F, w_m.data(), lde, stride, tl, out);
+    else emu_tiles<1>(A, fs.F, w_m.data(), lde, stride, tl, out);
+    return SMI_OK;
+}
+
+extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, uint32_t log_n, const uint32_t *trace, int *ok,
+                             uint32_t *constraint, uint64_t *row) {
+    smi_stark_cfg cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.n_cols = n_cols;
+    cfg.log_n = log_n;
+    std::string why;
+    const int rc = air_validate(p, &cfg, air, nullptr, nullptr, &why, true);
+    if (rc != SMI_OK) return rc;
+    const Fp F = fp_make((uint32_t)p);
+    AirHost H;
+    air_build(F, 1, &cfg, air, &H, true);
+    const uint64_t n = 1ull << log_n;
+    uint64_t first = ~0ull;
+    auto take = [&](uint64_t key) { if (key < first) first = key; };
+    for (uint64_t i = 0; i < n || i < air->n_boundary; i++) {
+        if (i < air->n_boundary && trace[air->boundary_col[i] * n + air->boundary_row[i]] != air->boundary_value[i])
+            take((i << 32) | air->boundary_row[i]);
+        if (i + 1 < n)
+            for (uint32_t k = 0; k < H.dev.K; k++)
+                if (air_constraint(H.dev, F, k, [&](uint32_t var) { return var < n_cols ? trace[var * n + i] : trace[(var - n_cols) * n + i + 1]; })) {
+                    take((1ull << 63) | ((uint64_t)k << 32) | i);
+                    break;
+                }
+    }
+    *ok = first == ~0ull;
+    if (!*ok) {
+        const uint32_t idx = (uint32_t)((first >> 32) & 0x7fffffffu);
+        if (constraint) *constraint = (first >> 63) ? air->n_boundary + idx : idx;
+        if (row) *row = first & 0xffffffffull;
+    }
+    return SMI_OK;
+}

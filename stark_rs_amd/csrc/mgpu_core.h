@@ -90,21 +90,27 @@ SMI_HD void mg_query_write(const MgLayer &L, uint64_t top_index, uint32_t s, int
 //   rows : t x 2 records  tag 2 | u64 W | W x u64            (row a, then row b)
 //   paths: t x W x 2 records  tag 3 | u64 depth | depth x 32  (column c at a, then at b)
 // written like the FRI openings: values and digests by the rank that owns the leaf, tags by rank 0.
-SMI_HD uint64_t mg_column_open_bytes(uint32_t W, uint32_t t, uint32_t depth) {
-    return (uint64_t)t * 2 * (9 + 8ull * W) + (uint64_t)t * W * 2 * (9 + 32ull * depth);
+SMI_HD uint64_t mg_column_open_bytes(uint32_t W, uint32_t t, uint32_t depth, uint32_t R = 2) {
+    return (uint64_t)t * R * (9 + 8ull * W) + (uint64_t)t * W * R * (9 + 32ull * depth);
 }
-SMI_HD void mg_column_open_write(const MgSide *cols, uint32_t W, uint32_t c, uint64_t top_index, uint32_t s, uint32_t t, int rank,
-                                 uint8_t *out, uint32_t lane, uint32_t n_lanes) {
+// The same records at R positions per test.  R == 2: a, b (open_columns).  R == 4: a, b, (a + shift) mod N, (b + shift) mod N
+// -- the AIR prover's next-row openings (smi_dev_air_prove, shift = the blowup): rows t x R, paths t x W x R, same order.
+SMI_HD void mg_column_open_write_n(const MgSide *cols, uint32_t W, uint32_t c, uint64_t top_index, uint32_t s, uint32_t t, int rank,
+                                   uint8_t *out, uint32_t lane, uint32_t n_lanes, uint32_t R, uint64_t shift) {
     const MgSide &side = cols[c];
     const uint32_t depth = side.depth_local + side.depth_top;
     const uint64_t half = side.len / 2, a = top_index % half, rec = 9 + 8ull * W, prec = 9 + 32ull * depth;
-    uint8_t *rows = out + (uint64_t)s * 2 * rec;
-    uint8_t *paths = out + (uint64_t)t * 2 * rec + ((uint64_t)s * W + c) * 2 * prec;
+    const uint64_t pos[4] = {a, a + half, (a + shift) & (side.len - 1), (a + half + shift) & (side.len - 1)};
+    uint8_t *rows = out + (uint64_t)s * R * rec;
+    uint8_t *paths = out + (uint64_t)t * R * rec + ((uint64_t)s * W + c) * R * prec;
     if (rank == 0 && c == 0 && lane == 0)
-        for (int k = 0; k < 2; k++) {
+        for (uint32_t k = 0; k < R; k++) {
             rows[k * rec] = 2;
             mg_put_u64(rows + k * rec + 1, W);
         }
-    mg_open_write(side, a, rank, rows + 9 + 8ull * c, paths, lane, n_lanes);
-    mg_open_write(side, a + half, rank, rows + rec + 9 + 8ull * c, paths + prec, lane, n_lanes);
+    for (uint32_t k = 0; k < R; k++) mg_open_write(side, pos[k], rank, rows + k * rec + 9 + 8ull * c, paths + k * prec, lane, n_lanes);
+}
+SMI_HD void mg_column_open_write(const MgSide *cols, uint32_t W, uint32_t c, uint64_t top_index, uint32_t s, uint32_t t, int rank,
+                                 uint8_t *out, uint32_t lane, uint32_t n_lanes) {
+    mg_column_open_write_n(cols, W, c, top_index, s, t, rank, out, lane, n_lanes, 2, 0);
 }

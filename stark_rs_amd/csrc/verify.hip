@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "air_core.h"
 #include "hash_core.h"
 #include "internal.h"
 #include "proof_parse.h"
@@ -336,6 +337,103 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
         for (uint64_t s = 0; s < 2 * t; s++)
             if (!ok[s]) return reject(ctx, accept, "column openings: authentication path does not verify");
     }
+    *accept = 1;
+    return SMI_OK;
+}
+
+// Verifier of smi_dev_air_prove (include/stark_mi.h, "AIR"): the weights and FRI's seed from the transcript of the
+// column roots and the constraint indices, Fri::verify at expansion factor E, then the openings -- length, rows,
+// every path against its column root, and the composition codeword recomputed at x_a and x_b with the evaluator
+// the prover's kernel runs (air_core.h) over the opened rows.
+int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const uint8_t *column_roots, const uint8_t *proof,
+                   size_t proof_len, int *accept) {
+    const smi_air *air = (const smi_air *)air_;
+    if (!ctx || !cfg || !air || !column_roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_verify: column trees only (row_leaves must be 0)");
+    std::string why;
+    uint64_t E = 0;
+    const int vrc = air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
+    if (logN > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    const uint64_t p = ctx->fs.F.p, N = 1ull << logN, B = 1ull << cfg->log_blowup, t = cfg->num_colinearity_tests;
+    smi_fri_cfg fc;
+    fc.omega = h_root(ctx, logN);
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = N;
+    fc.expansion_factor = E;
+    fc.num_colinearity_tests = t;
+    // transcript: root c, weight c; then k as 8 LE bytes, weight W + k
+    std::vector<uint64_t> weights(W + K);
+    std::vector<uint8_t> transcript;
+    for (uint32_t c = 0; c < W; c++) {
+        transcript.insert(transcript.end(), column_roots + 32 * c, column_roots + 32 * c + 32);
+        SMI_TRY(challenge_of(ctx, transcript, &weights[c]));
+    }
+    for (uint32_t k = 0; k < K; k++) {
+        for (int i = 0; i < 8; i++) transcript.push_back((uint8_t)((uint64_t)k >> (8 * i)));
+        SMI_TRY(challenge_of(ctx, transcript, &weights[W + k]));
+    }
+    FsSeed seed;
+    hashc::fs_seed(transcript.data(), transcript.size(), seed.s, &seed.phase);
+    size_t end = 0;
+    const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc), &end);
+    std::vector<uint64_t> top, ab;
+    size_t used = 0;
+    SMI_TRY(fri_verify_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
+    if (!*accept) return SMI_OK;
+    *accept = 0;
+    const size_t R = K ? 4 : 2, rec = 9 + 8 * (size_t)W, prec = 9 + 32 * (size_t)logN, need = t * R * rec + t * W * R * prec;
+    if (proof_len - end != need) return reject(ctx, accept, "air openings: wrong length");
+    const uint8_t *ext = proof + end, *pathsb = ext + t * R * rec;
+    const uint64_t half = N / 2;
+    std::vector<uint64_t> rows(t * R * W), pos(t * R);
+    for (uint64_t s = 0; s < t; s++) {
+        const uint64_t a = top[s] % half;
+        const uint64_t ps[4] = {a, a + half, (a + B) & (N - 1), (a + half + B) & (N - 1)};
+        for (size_t k = 0; k < R; k++) {
+            const uint8_t *r = ext + (R * s + k) * rec;
+            if (r[0] != 2 || get_u64(r + 1) != W) return reject(ctx, accept, "air openings: malformed row");
+            pos[R * s + k] = ps[k];
+            for (uint32_t c = 0; c < W; c++) rows[(R * s + k) * W + c] = get_u64(r + 9 + 8 * c);
+        }
+    }
+    for (uint32_t c = 0; c < W; c++) {
+        const size_t m = R * t;
+        std::vector<uint64_t> vals(m);
+        std::vector<uint8_t> paths(m * 32 * (size_t)logN), leaf, ok(m ? m : 1);
+        for (size_t q = 0; q < m; q++) {
+            const uint8_t *pr = pathsb + (((q / R) * W + c) * R + q % R) * prec;
+            if (pr[0] != 3 || get_u64(pr + 1) != logN) return reject(ctx, accept, "air openings: malformed path");
+            vals[q] = rows[q * W + c];
+            memcpy(&paths[q * 32 * (size_t)logN], pr + 9, 32 * (size_t)logN);
+        }
+        SMI_TRY(leaf_digests(ctx, vals.data(), m, leaf));
+        if (m) SMI_TRY(smi_merkle_verify_batch(ctx, leaf.data(), pos.data(), paths.data(), m, logN, column_roots + 32 * c, ok.data()));
+        for (size_t q = 0; q < m; q++)
+            if (!ok[q]) return reject(ctx, accept, "air openings: authentication path does not verify");
+    }
+    // the composition codeword at x_a and x_b from the opened rows
+    AirHost H;
+    air_build(ctx->fs.F, (uint32_t)fc.omega, cfg, air, &H);
+    const Fp F = ctx->fs.F;
+    std::vector<uint32_t> w_m(W + K);
+    for (uint32_t i = 0; i < W + K; i++) w_m[i] = to_mont_u64(weights[i], F);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < 2; k++) {
+            const uint64_t i = pos[R * s + k];
+            for (size_t r = k; r < R; r += 2)
+                for (uint32_t c = 0; c < W; c++)
+                    if (rows[(R * s + r) * W + c] >= p) return reject(ctx, accept, "air openings: an opened value is not canonical");
+            const uint64_t *cur = &rows[(R * s + k) * W], *nxt = K ? &rows[(R * s + k + 2) * W] : nullptr;
+            const uint32_t x_m = air_to_m((uint32_t)mulm(cfg->lde_offset, powm(fc.omega, i, p), p), (uint32_t)p), ib = (uint32_t)(i & (B - 1));
+            uint32_t got = 0;
+            air_compose_points<1>(
+                H.dev, F, w_m.data(), &x_m, &ib, [&](int, uint32_t var) { return (uint32_t)(var < W ? cur[var] : nxt[var - W]); }, &got);
+            if (got != ab[2 * s + k] % p) return reject(ctx, accept, "air openings: the composition of the opened rows is not the codeword value");
+        }
     *accept = 1;
     return SMI_OK;
 }

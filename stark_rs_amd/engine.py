@@ -433,6 +433,68 @@ class Engine:
             out["stage_ms"] = dict(zip(("lde", "commit", "combine", "fri"), [float(x) for x in stage]))
         return out
 
+    # ---- AIR constraints (include/stark_mi.h, "AIR"); `air` is a mirror.Air or a flattened _lib.Air
+    def _air(self, air):
+        return air if isinstance(air, _lib.Air) else air.flatten(self.p)
+
+    def _stark_cfg(self, n_cols, log_n, log_blowup, num_colinearity_tests=0, trace_offset=1, lde_offset=None):
+        return _lib.StarkCfg(log_n, log_blowup, n_cols, 0, trace_offset, self.g if lde_offset is None else lde_offset,
+                             num_colinearity_tests, 1)
+
+    def air_plan(self, air, n_cols, log_n, log_blowup, trace_offset=1, lde_offset=None):
+        """smi_air_plan -> (degree d, FRI expansion factor E); raises with the limit that was broken"""
+        return air_plan(self.p, self._air(air), self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset))
+
+    def dev_air_compose(self, air, d_lde, n_cols, log_n, log_blowup, d_weights, d_out, stride=None, trace_offset=1, lde_offset=None):
+        """the composition codeword of n_cols extended device columns under n_cols + K unreduced device weights"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        a = self._air(air)
+        stride = (1 << (log_n + log_blowup)) if stride is None else stride
+        self._ck(self.L.smi_dev_air_compose(self.h, C.byref(cfg), C.byref(a), vp(d_lde), stride, vp(d_weights), vp(d_out)))
+
+    def dev_air_check(self, air, d_trace_cols, n_cols, log_n):
+        """-> (ok, constraint, row, sentence): the first violation of the AIR on the trace itself; constraint is the
+        boundary point's position, or n_boundary + k for transition constraint k"""
+        a = self._air(air)
+        ok, con, row = C.c_int(), C.c_uint32(), C.c_uint64()
+        self._ck(self.L.smi_dev_air_check(self.h, C.byref(a), n_cols, log_n, vp(d_trace_cols), C.byref(ok), C.byref(con), C.byref(row)))
+        if ok.value:
+            return True, None, None, ""
+        return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
+
+    def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
+                      timed=False, check=True):
+        """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
+        dev_air_check first and raises StarkMiError naming the first violated constraint and row."""
+        a = self._air(air)
+        if check:
+            ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+            if not ok:
+                raise StarkMiError(-50, why)   # SMI_ERR_BAD_ARG: the trace handed in does not satisfy the AIR
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset)
+        roots = np.zeros((n_cols, 32), dtype=np.uint8)
+        proof, plen = vp(), C.c_size_t()
+        top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
+        stage = (C.c_double * 5)()
+        self._ck(self.L.smi_dev_air_prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof),
+                                          C.byref(plen), top.ctypes.data, stage if timed else None))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]]}
+        if timed:
+            out["stage_ms"] = dict(zip(("lde", "commit", "compose", "fri", "open"), [float(x) for x in stage]))
+        return out
+
+    def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
+                   lde_offset=None):
+        """verifier of dev_air_prove -> (accept, reason)"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset)
+        a = self._air(air)
+        roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+        acc = C.c_int()
+        self._ck(self.L.smi_air_verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc)))
+        return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
+
 
 class DeviceTree:
     """MerkleTree kept on the device (all levels, src/merkle.rs:4-8)."""
@@ -504,6 +566,16 @@ class FriRun:
             self.free()
         except Exception:
             pass
+
+
+def air_plan(p, air, cfg):
+    """smi_air_plan (host only: no context, no GPU) -> (d, E).  air: a flattened _lib.Air; cfg: a _lib.StarkCfg."""
+    d, e = C.c_uint32(), C.c_uint64()
+    L = _lib.lib()
+    st = L.smi_air_plan(p, C.byref(cfg), C.byref(air), C.byref(d), C.byref(e))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, e.value
 
 
 def default_engine(p=P_REF, g=G_REF, device=0):

@@ -697,3 +697,123 @@ def verify_column_openings(eng, proof: bytes, n_cols, log_n, log_blowup, num_col
             if acc != triples[s].payload[k].value % p:
                 return False
     return rounds > 0
+
+
+class Air:
+    """An AIR over n_cols trace columns (include/stark_mi.h, "AIR"): boundary points and transition constraints
+    written readably, flattened to the C ABI's smi_air, with a pure-Python pointwise evaluator of the composition
+    codeword (what a verifier recomputes from opened rows; plain integer arithmetic, the glue side of this mirror).
+    The reference has no counterpart: its Trace has no consumer (src/trace.rs).
+
+        air = Air(2)
+        air.boundary(0, 0, 1)                                   # column 0 holds 1 in row 0
+        air.transition({("next", 0): 1, ("cur", 1): -1})        # a' = b
+        air.transition({("next", 1): 1, ("cur", 0): -1, ("cur", 1): -1})
+
+    A monomial is () (a constant), one factor, or a tuple of factors; a factor is ("cur" | "next", column) or
+    ("cur" | "next", column, exponent).  Coefficients are integers, reduced mod p when flattened."""
+
+    def __init__(self, n_cols):
+        self.n_cols = n_cols
+        self.constraints = []   # [[(coeff, [(var, exp), ...]), ...], ...]
+        self.boundaries = []    # [(col, row, value), ...]
+
+    def _factor(self, f):
+        shift = {"cur": 0, "next": 1}[f[0]]
+        return f[1] + self.n_cols * shift, (f[2] if len(f) > 2 else 1)
+
+    def transition(self, poly):
+        terms = []
+        for mono, coeff in poly.items():
+            if mono == ():
+                factors = []
+            elif isinstance(mono[0], str):
+                factors = [self._factor(mono)]
+            else:
+                factors = [self._factor(f) for f in mono]
+            terms.append((int(coeff), factors))
+        self.constraints.append(terms)
+        return self
+
+    def boundary(self, col, row, value):
+        self.boundaries.append((int(col), int(row), int(value)))
+        return self
+
+    @property
+    def degree(self):
+        return max([1] + [sum(e for _, e in f) for con in self.constraints for _, f in con])
+
+    def flatten(self, p):
+        """-> _lib.Air (smi_air); the arrays it points to stay alive as long as the returned object"""
+        import ctypes as C
+        from . import _lib
+        cft, coeff, tff, var, exp = [0], [], [0], [], []
+        for con in self.constraints:
+            for cf, factors in con:
+                coeff.append(cf % p)
+                var += [v for v, _ in factors]
+                exp += [e for _, e in factors]
+                tff.append(len(var))
+            cft.append(len(coeff))
+        arrs = [np.array(cft, dtype=np.uint32), np.array(coeff, dtype=np.uint64), np.array(tff, dtype=np.uint32),
+                np.array(var, dtype=np.uint32), np.array(exp, dtype=np.uint32),
+                np.array([b[0] for b in self.boundaries], dtype=np.uint32), np.array([b[1] for b in self.boundaries], dtype=np.uint64),
+                np.array([b[2] for b in self.boundaries], dtype=np.uint64)]
+        ptr = lambda a, t: a.ctypes.data_as(t)
+        out = _lib.Air(len(self.constraints), len(coeff), len(var), len(self.boundaries), ptr(arrs[0], _lib.u32p), ptr(arrs[1], _lib.u64p),
+                       ptr(arrs[2], _lib.u32p), ptr(arrs[3], _lib.u32p), ptr(arrs[4], _lib.u32p), ptr(arrs[5], _lib.u32p),
+                       ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p))
+        out._keep = arrs
+        return out
+
+    def constraint_value(self, k, p, cur, nxt):
+        """C_k on one row pair"""
+        vals = [int(v) for v in cur] + [int(v) for v in nxt]
+        acc = 0
+        for cf, factors in self.constraints[k]:
+            m = cf % p
+            for v, e in factors:
+                m = m * pow(vals[v], e, p) % p
+            acc += m
+        return acc % p
+
+    def first_violation(self, p, cols):
+        """(constraint, row) of the first violation on a trace in smi_dev_air_check's order, or None"""
+        n = len(cols[0])
+        for j, (c, r, v) in enumerate(self.boundaries):
+            if int(cols[c][r]) != v % p:
+                return j, r
+        for k in range(len(self.constraints)):
+            for r in range(n - 1):
+                if self.constraint_value(k, p, [col[r] for col in cols], [col[r + 1] for col in cols]):
+                    return len(self.boundaries) + k, r
+        return None
+
+    def compose_at(self, p, log_n, log_blowup, trace_offset, lde_offset, omega_N, i, cur, nxt, weights):
+        """cw[i] from the extended columns' values at index i (cur) and (i + B) mod N (nxt; unused when there is no
+        transition constraint) under the W + K unreduced weights -- the definition of include/stark_mi.h, term by term"""
+        n, B = 1 << log_n, 1 << log_blowup
+        inv = lambda v: pow(v, p - 2, p)
+        w = pow(omega_N, B, p)
+        x = lde_offset * pow(omega_N, i, p) % p
+        acc = 0
+        for c in range(self.n_cols):
+            pts = [(trace_offset * pow(w, r, p) % p, v % p) for (cc, r, v) in self.boundaries if cc == c]
+            term = int(cur[c])
+            if pts:
+                ix, z = 0, 1
+                for j, (rj, vj) in enumerate(pts):     # Lagrange form of the interpolant at x
+                    num, den = 1, 1
+                    for k, (rk, _) in enumerate(pts):
+                        if k != j:
+                            num, den = num * (x - rk) % p, den * (rj - rk) % p
+                    ix += vj * num * inv(den)
+                    z = z * (x - rj) % p
+                term = (term - ix) * inv(z) % p
+            acc += weights[c] % p * term
+        if self.constraints:
+            last = trace_offset * pow(w, n - 1, p) % p
+            zt_inv = (x - last) * inv(pow(x, n, p) - pow(trace_offset, n, p)) % p
+            for k in range(len(self.constraints)):
+                acc += weights[self.n_cols + k] % p * (self.constraint_value(k, p, cur, nxt) * zt_inv % p)
+        return acc % p

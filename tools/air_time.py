@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""Development tool (GPU box): the numbers of DESIGN.md's AIR section.
+
+    python3 tools/air_time.py                 # compose kernel times + prove medians on this build
+    python3 tools/air_time.py --stark-only    # only smi_dev_stark_prove(open_columns = 1): what a build without the
+                                              # AIR entry points can run (set --root to that build's tree)
+    rocprofv3 --kernel-trace --output-format csv --pmc SQ_INSTS_VALU SQ_WAVES -d OUT -o air -- python3 tools/air_time.py --single
+                                              # VALU instructions per wave of each AIR's launch, in a run of its own
+
+compose: HIP-event time of air_compose_kernel (smi_ctx_profile) at (W = 4, n = 2^22, B = 8) for the empty, fib-like,
+mixer AIRs and at (W = 64, n = 2^18) for a 32-constraint AIR; median of REPS launches after 3 warm-up launches;
+achieved bytes/s of 4 (W + 1) N against an in-run device-to-device copy moving the same bytes.
+prove: median wall time of nine smi_dev_air_prove(empty) / smi_dev_stark_prove(open_columns = 1) calls on one trace."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--stark-only", action="store_true")
+ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--single", action="store_true", help="one launch per AIR at (W = 4, n = 2^22) and nothing else: the run to put under "
+                "`rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES` (the k-th air_compose_kernel dispatch is the k-th AIR printed)")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
+import torch  # noqa: E402
+import stark_rs_amd as s  # noqa: E402
+
+p, g = s.P2, s.G2
+eng = s.Engine(p, g, 0)
+dev = torch.device("cuda:0")
+rng = np.random.default_rng(1)
+
+
+def rand_cols(W, n):
+    return torch.from_numpy(rng.integers(0, p, (W, n), dtype=np.int64).astype(np.int32)).to(dev)
+
+
+def median_kernel_ms(fn, name):
+    for _ in range(3):
+        fn()
+    eng.sync()
+    eng.profile(True)
+    eng.profile_read()
+    out = []
+    for _ in range(args.reps):
+        fn()
+        out.append(eng.profile_read()[name]["total_ms"])
+    eng.profile(False)
+    return statistics.median(out), min(out), max(out)
+
+
+def copy_ms(nbytes):
+    a = torch.empty(nbytes // 8, dtype=torch.int32, device=dev)   # nbytes / 2 read + nbytes / 2 written
+    b = torch.empty_like(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for i in range(3 + args.reps):
+        e0.record()
+        b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            out.append(e0.elapsed_time(e1))
+    return statistics.median(out)
+
+
+def airs(W, n):
+    from stark_rs_amd.mirror import Air
+    empty = Air(W)
+    fib = Air(W)
+    fib.transition({("next", 0): 1, ("cur", 1): -1}).transition({("next", 1): 1, ("cur", 0): -1, ("cur", 1): -1})
+    fib.boundary(0, 0, 1).boundary(1, 0, 1).boundary(0, n - 1, 5)
+    mixer = Air(W)
+    mixer.transition({("next", 0): 1, (("cur", 0), ("cur", 1)): -1, ("cur", 2): -1})
+    mixer.transition({("next", 1): 1, (("cur", 0, 2), ("cur", 2)): -1, ("cur", 1): -3})
+    mixer.transition({("next", 2): 1, ("cur", 2): -1, (): -1})
+    mixer.boundary(0, 0, 5).boundary(1, 0, 11).boundary(2, 0, 0).boundary(2, n - 1, n - 1).boundary(0, n - 1, 9)
+    only_t = Air(W)
+    only_t.constraints = list(mixer.constraints)
+    only_b = Air(W)
+    only_b.boundaries = list(mixer.boundaries)
+    return [("empty", empty), ("fib", fib), ("mixer", mixer), ("mixer, transitions only", only_t), ("mixer, boundaries only", only_b)]
+
+
+def wide(W, K, n):
+    from stark_rs_amd.mirror import Air
+    air = Air(W)
+    for k in range(K):
+        air.transition({("next", k % W): 1, (("cur", (k + 1) % W), ("cur", (3 * k + 2) % W)): -(k + 1), ("cur", (5 * k) % W, 2): 7, (): k})
+    for c in range(0, W, 4):
+        air.boundary(c, 0, 1).boundary(c, n - 1 - c, 2)
+    return air
+
+
+if args.single:
+    W, log_n, lb = 4, 22, 3
+    N = 1 << (log_n + lb)
+    lde, out = rand_cols(W, N), torch.empty(N, dtype=torch.int32, device=dev)
+    for k, (name, air) in enumerate(airs(W, 1 << log_n)):
+        wts = torch.from_numpy(rng.integers(0, 1 << 62, W + len(air.constraints), dtype=np.int64)).to(dev)
+        torch.cuda.synchronize()
+        eng.dev_air_compose(air.flatten(p), lde.data_ptr(), W, log_n, lb, wts.data_ptr(), out.data_ptr())
+        eng.sync()
+        print(f"dispatch {k}: {name}  ({N} points)", flush=True)
+    eng.close()
+    sys.exit(0)
+
+if not args.stark_only:
+    for W, log_n, lb, cases in [(4, 22, 3, None), (64, 18, 3, "wide")]:
+        n, N = 1 << log_n, 1 << (log_n + lb)
+        lde, out = rand_cols(W, N), torch.empty(N, dtype=torch.int32, device=dev)
+        nbytes = 4 * (W + 1) * N
+        cms = copy_ms(nbytes)
+        print(f"W={W} n=2^{log_n} B={1 << lb}: 4(W+1)N = {nbytes / 1e9:.3f} GB; device copy of the same bytes {cms:.3f} ms = {nbytes / cms / 1e9:.2f} TB/s", flush=True)
+        for name, air in (airs(W, n) if cases is None else [("empty", airs(W, n)[0][1]), ("32 constraints", wide(W, 32, n))]):
+            K = len(air.constraints)
+            wts = torch.from_numpy(rng.integers(0, 1 << 62, W + K, dtype=np.int64)).to(dev)
+            flat = air.flatten(p)
+            torch.cuda.synchronize()
+            med, lo, hi = median_kernel_ms(lambda: eng.dev_air_compose(flat, lde.data_ptr(), W, log_n, lb, wts.data_ptr(), out.data_ptr()),
+                                           "air_compose_kernel")
+            print(f"  compose {name:26s}: median {med:7.3f} ms (min {lo:.3f}, max {hi:.3f}; {args.reps} launches)  {nbytes / med / 1e9:5.2f} TB/s"
+                  f" = {100 * cms / med:5.1f} % of the copy", flush=True)
+        del lde, out
+
+W, log_n, lb, t = 4, 22, 3, 32
+trace = rand_cols(W, 1 << log_n)
+torch.cuda.synchronize()
+
+
+def wall(fn):
+    for _ in range(2):
+        fn()
+    runs = []
+    for _ in range(9):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        runs.append((1e3 * (time.perf_counter() - t0), res))
+    runs.sort(key=lambda x: x[0])
+    return runs
+
+
+runs = wall(lambda: eng.dev_stark_prove(trace.data_ptr(), W, log_n, lb, t, timed=True, open_columns=True))
+print(f"stark_prove(open_columns=1) W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+if not args.stark_only:
+    from stark_rs_amd.mirror import Air
+    flat = Air(W).flatten(p)
+    runs = wall(lambda: eng.dev_air_prove(flat, trace.data_ptr(), W, log_n, lb, t, timed=True, check=False))
+    print(f"air_prove(empty)            W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+    name, mixer = airs(W, 1 << log_n)[2]
+    flat = mixer.flatten(p)
+    runs = wall(lambda: eng.dev_air_prove(flat, trace.data_ptr(), W, log_n, lb, t, timed=True, check=False))
+    print(f"air_prove(mixer, any trace) W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+eng.close()

@@ -133,6 +133,22 @@ def generate():
     lines.append("    pub all_reduce_sum_u8: Option<unsafe extern \"C\" fn(user: *mut c_void, d_buf: *mut c_void, bytes: usize) -> c_int>,")
     lines.append("}")
     lines.append("")
+    lines.append("/// smi_air: the flat tables of an AIR (host pointers; the entry points take it as `*const c_void`)")
+    lines.append("#[repr(C)] #[derive(Clone, Copy)]")
+    lines.append("pub struct smi_air {")
+    air = re.search(r"typedef struct smi_air\s*\{(.*?)\}\s*smi_air\s*;", text, flags=re.S).group(1)
+    for decl in [" ".join(d.split()) for d in air.split(";") if d.strip()]:
+        pm = re.fullmatch(r"const (\w+) \*(\w+)", decl)
+        if pm:
+            lines.append(f"    pub {pm.group(2)}: *const {SCALAR[pm.group(1)]},")
+            continue
+        ty, names = decl.split(" ", 1)
+        for nm in names.split(","):
+            lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
+    lines.append("}")
+    for m in re.finditer(r"#define (SMI_AIR_MAX_\w+) (\d+)", text):
+        lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
+    lines.append("")
     lines.append('#[link(name = "starkmi")]')
     lines.append('extern "C" {')
     for name, ps, ret in functions(text):

@@ -20,13 +20,6 @@
 #include "internal.h"
 #include "mgpu_core.h"
 
-int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
-                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
-int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
-            smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
-            uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src,
-            const FsSeed *seed = nullptr);
-
 template <int P>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
                                                                  const uint64_t *__restrict__ weights, uint32_t T,
@@ -267,10 +260,14 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     fc.domain_length = N;
     fc.expansion_factor = E;
     fc.num_colinearity_tests = cfg->num_colinearity_tests;
-    std::vector<uint8_t> bytes;
-    std::vector<uint64_t> top_tmp(top_indices ? 0 : (size_t)cfg->num_colinearity_tests);
-    if (!top_indices && !top_tmp.empty()) top_indices = top_tmp.data();
-    SMI_TRY(fri_run(ctx, &fc, d_cw, N, true, false, nullptr, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr, nullptr, &seed));
+    FriRequest rq(&fc, d_cw, N, true);
+    rq.reset_arena = false;
+    rq.seed = &seed;
+    FriResult res;
+    SMI_TRY(fri_run(ctx, rq, &res));
+    std::vector<uint8_t> &bytes = res.proof;
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    else top_indices = res.top.data();   // the column openings need the top-level indices either way
     mark(4);
     if (cfg->num_colinearity_tests) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
@@ -301,9 +298,5 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
             (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
             stage_ms[i] = ms;
         }
-    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
-    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
-    memcpy(*proof, bytes.data(), bytes.size());
-    *proof_len = bytes.size();
-    return SMI_OK;
+    return smi_proof_out(ctx, bytes, proof, proof_len);
 }

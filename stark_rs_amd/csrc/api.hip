@@ -8,13 +8,6 @@
 #include "internal.h"
 #include "lde_core.h"
 
-int launch_leaf_hash(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_digests);
-int launch_combine(smi_ctx *ctx, const uint8_t *d_in, size_t n_pairs, uint8_t *d_out);
-int launch_hash_bytes(smi_ctx *ctx, const uint8_t *d_msg, size_t len, uint32_t *d_out);
-int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes);
-int launch_verify_paths(smi_ctx *ctx, const uint8_t *d_leaves, const uint64_t *d_idx, const uint8_t *d_paths, size_t k, uint32_t depth,
-                        const uint8_t *d_root, uint8_t *d_ok);
-
 // ------------------------------------------------------------------------- errors
 const char *smi_status_string(int status) {
     switch (status) {
@@ -525,12 +518,6 @@ int host_to_dev_u32(smi_ctx *ctx, const uint64_t *host, size_t n, uint32_t *d_ou
 }
 
 // ------------------------------------------------------------------------- field scalars
-static bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
-static uint32_t ilog2(uint64_t n) {
-    uint32_t l = 0;
-    while ((n >> l) > 1) l++;
-    return l;
-}
 
 int smi_prim_nth_root(const smi_ctx *ctx, uint64_t n, uint64_t *out) {
     if (!ctx || !out) return SMI_ERR_BAD_ARG;
@@ -867,7 +854,6 @@ int smi_dev_merkle_build(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_
     if (!is_pow2(n)) return smi_fail(ctx, SMI_ERR_LEAVES_NOT_POW2, nullptr);
     return launch_merkle(ctx, d_elems, n, d_nodes);
 }
-int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
 int smi_dev_merkle_build_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes) {
     if (!ctx || !d_cols || !d_nodes) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
@@ -929,7 +915,6 @@ int smi_dev_hash_bytes(smi_ctx *ctx, const uint8_t *d_msg, size_t len, uint8_t *
     return launch_hash_bytes(ctx, d_msg, len, (uint32_t *)d_out32);
 }
 
-int launch_hash_bytes_batch(smi_ctx *ctx, const uint8_t *d_msgs, size_t n, size_t len, uint32_t *d_out);
 int smi_hash_bytes_batch(smi_ctx *ctx, const uint8_t *msgs, size_t n, size_t msg_len, uint8_t *out) {
     if (!ctx || (n && msg_len && !msgs) || (n && !out)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);

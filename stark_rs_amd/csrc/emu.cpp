@@ -575,3 +575,44 @@ extern "C" size_t emu_proof_parse(const uint8_t *b, size_t n, size_t max_objs, i
     if (end) *end = e;
     return objs.size();
 }
+
+// ------------------------------------------------------------------------- launch plans
+// merkle_plan / fri_layout / fri_round_plan (merkle_plan.h, fri_plan.h: what hash.hip and fri.hip execute) as flat arrays.
+// The knobs arrive as arguments -- K, TOP_BLOCKS, ELEMS_LOG, SINGLE, MINCHUNK, FUSE, GENERIC -- so one process sweeps them.
+#include "fri_plan.h"
+static MerkleKnobs emu_knobs(const int64_t *k) { return merkle_knobs_make(k[0], k[1], k[2], k[3], k[4], k[5], k[6]); }
+// per step: family, inst, from_leaves, level, count, arg (chunk | K), grid.x, LDS bytes, ends_root, src_cap; returns the step count
+extern "C" int emu_merkle_plan(uint64_t n, uint32_t n_trees, int leaves, uint32_t row_cols, const int64_t *knobs, uint64_t *out) {
+    const MerklePlan pl = merkle_plan(MerkleShape{(size_t)n, n_trees, leaves, row_cols}, emu_knobs(knobs));
+    for (uint32_t i = 0; i < pl.n_steps; i++) {
+        const MerkleStep &s = pl.s[i];
+        const uint64_t row[10] = {s.family, s.inst, s.from_leaves, s.level, s.count, s.arg, s.grid, s.lds,
+                                  s.ends_root, s.src_cap};
+        memcpy(out + 10 * i, row, sizeof row);
+    }
+    return (int)pl.n_steps;
+}
+// head: R, last_n, off_last, off_layers, proof_len; offs: off_triples then off_paths of layer i at 2 i
+extern "C" void emu_fri_layout(uint64_t domain_length, uint64_t expansion_factor, uint64_t t, int do_query, uint64_t *head, uint64_t *offs) {
+    smi_fri_cfg cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.domain_length = domain_length;
+    cfg.expansion_factor = expansion_factor;
+    cfg.num_colinearity_tests = t;
+    const FriLayout l = fri_layout(cfg, do_query != 0);
+    const uint64_t h[5] = {l.R, l.last_n, l.off_last, l.off_layers, l.proof_len};
+    memcpy(head, h, sizeof h);
+    for (uint64_t i = 0; i + 1 < l.R; i++) {
+        offs[2 * i] = l.off_triples[i];
+        offs[2 * i + 1] = l.off_paths[i];
+    }
+}
+// producer / tree: R entries each (the FRI_BY_* / FRI_TREE_* values); returns plan.ok, *tail_at = the tail's first round (R: none)
+extern "C" int emu_fri_round_plan(uint64_t len, uint64_t R, uint32_t phase, uint64_t tail_len, int round0, const int64_t *knobs,
+                                  uint8_t *producer, uint8_t *tree, uint32_t *tail_at) {
+    const FriRoundPlan pl = fri_round_plan(len, R, phase, tail_len, round0, emu_knobs(knobs));
+    memcpy(producer, pl.producer, pl.R);
+    memcpy(tree, pl.tree, pl.R);
+    *tail_at = pl.tail_at;
+    return pl.ok ? 1 : 0;
+}

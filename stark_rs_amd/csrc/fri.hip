@@ -6,15 +6,12 @@
 // each root and draws alpha into device memory, the fold kernel reads alpha from there, so
 // a whole prove is enqueued without one host round trip; the host synchronises once to
 // copy the serialized proof back.
+#include <assert.h>
+
 #include "fri_core.h"
 #include "hash_core.h"
 #include "hash_hex.h"
 #include "internal.h"
-
-int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes);
-// the same, with the Fiat-Shamir round of the root run by the launch that produces it (*done says whether it was)
-int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
-                     uint64_t *alpha_out, bool *done);
 
 // ------------------------------------------------------------------------- fold
 // out[i] = 2^-1 * ((1 + a/x_i) c[i] + (1 - a/x_i) c[i+h])            (src/fri.rs:70-88)
@@ -37,15 +34,11 @@ __global__ __launch_bounds__(256) void fri_fold_kernel(const uint32_t *__restric
 // fs_state (16 words) and `challenge` = 8 more mixes on a copy: the same function of the
 // whole transcript as re-hashing it, evaluated incrementally.
 // A caller's transcript that is not whole 32-byte chunks leaves `phase` bytes pending (hash_core.h fs_seed); the phase
-// rides in the state so that the phase-aware kernels below read it with the words.
-struct FsState {
-    uint32_t s[16];
-    uint32_t phase;
-};
+// rides in the state (FsSeed, internal.h) so that the phase-aware kernels below read it with the words.
 
 // the seed (the initial constants for a fresh transcript) arrives by value: it is computed on the host
 // (ride_*: a few bytes of the caller's -- the column roots of a prove -- placed behind the proof, to come back with its copy)
-__global__ void fs_init_kernel(FsState *fs, FsSeed seed, const uint8_t *ride_src = nullptr, uint8_t *ride_dst = nullptr, size_t ride_n = 0) {
+__global__ void fs_init_kernel(FsSeed *fs, FsSeed seed, const uint8_t *ride_src = nullptr, uint8_t *ride_dst = nullptr, size_t ride_n = 0) {
     if (blockIdx.x) return;
     for (size_t i = threadIdx.x; i < ride_n; i += blockDim.x) ride_dst[i] = ride_src[i];
     if (threadIdx.x) return;
@@ -61,7 +54,7 @@ static FsSeed fresh_seed() {
 // absorb the root at `root`, append it (tag 0 + 32 bytes, src/stream.rs:39-42) to the proof
 // buffer, and if alpha_out != nullptr draw the challenge.
 // (both over the first sixteen lanes, one state word each: hash_hex.h)
-__global__ void fs_round_kernel(FsState *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
+__global__ void fs_round_kernel(FsSeed *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
     if (threadIdx.x >= 16 || blockIdx.x) return;
     const hashx::Lane row = hashx::make_lane(threadIdx.x);
     const uint32_t j = threadIdx.x >> 2;
@@ -69,7 +62,7 @@ __global__ void fs_round_kernel(FsState *fs, const uint32_t *root, uint8_t *proo
 }
 
 // challenge without absorbing (src/fri.rs:272: the index-sampling seed)
-__global__ void fs_challenge_kernel(const FsState *fs, uint64_t *alpha_out) {
+__global__ void fs_challenge_kernel(const FsSeed *fs, uint64_t *alpha_out) {
     if (threadIdx.x >= 16 || blockIdx.x) return;
     const hashx::Lane row = hashx::make_lane(threadIdx.x);
     const uint64_t a = hashx::low_bytes_u64(hashx::fs_challenge(fs->s[threadIdx.x], row));
@@ -78,13 +71,13 @@ __global__ void fs_challenge_kernel(const FsState *fs, uint64_t *alpha_out) {
 
 // The same two at a phase != 0 (hash_core.h fs_absorb_root_phase / fs_challenge_phase), one lane: the root straddles
 // two chunks there, which the sixteen-lane form does not cover.  Run once per round on a few hundred bytes of state.
-__global__ void fs_round_phase_kernel(FsState *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
+__global__ void fs_round_phase_kernel(FsSeed *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
     if (threadIdx.x || blockIdx.x) return;
     uint32_t m[8];
     for (int j = 0; j < 8; j++) m[j] = root[j];
     hashc::fs_absorb_root_phase(fs->s, m, fs->phase, proof_slot, alpha_out);
 }
-__global__ void fs_challenge_phase_kernel(const FsState *fs, uint64_t *alpha_out) {
+__global__ void fs_challenge_phase_kernel(const FsSeed *fs, uint64_t *alpha_out) {
     if (threadIdx.x || blockIdx.x) return;
     *alpha_out = hashc::fs_challenge_phase(fs->s, fs->phase);
 }
@@ -253,22 +246,21 @@ __global__ void emit_codeword_kernel(const uint32_t *cw, uint64_t len, uint8_t *
 }
 
 // launchers for the multi-GPU round loop (mgpu.hip), which sequences the same kernels
-size_t fri_fs_bytes() { return sizeof(FsState); }
 // (seed == nullptr: a fresh transcript; phase: the seed's, which the caller keeps on the host to pick the kernels)
 int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed) {
-    fs_init_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, seed ? *seed : fresh_seed());
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>((FsSeed *)fs, seed ? *seed : fresh_seed());
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
 int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase) {
-    if (phase) fs_round_phase_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, (const uint32_t *)root, proof_slot, alpha_out);
-    else fs_round_kernel<<<1, 64, 0, ctx->stream>>>((FsState *)fs, (const uint32_t *)root, proof_slot, alpha_out);
+    if (phase) fs_round_phase_kernel<<<1, 64, 0, ctx->stream>>>((FsSeed *)fs, (const uint32_t *)root, proof_slot, alpha_out);
+    else fs_round_kernel<<<1, 64, 0, ctx->stream>>>((FsSeed *)fs, (const uint32_t *)root, proof_slot, alpha_out);
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
 int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out, uint32_t phase) {
-    if (phase) fs_challenge_phase_kernel<<<1, 64, 0, ctx->stream>>>((const FsState *)fs, out);
-    else fs_challenge_kernel<<<1, 64, 0, ctx->stream>>>((const FsState *)fs, out);
+    if (phase) fs_challenge_phase_kernel<<<1, 64, 0, ctx->stream>>>((const FsSeed *)fs, out);
+    else fs_challenge_kernel<<<1, 64, 0, ctx->stream>>>((const FsSeed *)fs, out);
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
@@ -287,20 +279,8 @@ int launch_emit_codeword(smi_ctx *ctx, const uint32_t *cw, uint64_t len, uint8_t
 // ------------------------------------------------------------------------- host side
 int smi_fri_num_rounds(const smi_fri_cfg *cfg, uint64_t *rounds) {
     if (!cfg || !rounds) return SMI_ERR_BAD_ARG;
-    uint64_t len = cfg->domain_length, r = 0;  // src/fri.rs:93-103
-    while (len > cfg->expansion_factor && 4 * cfg->num_colinearity_tests < len) {
-        len /= 2;
-        r++;
-    }
-    *rounds = r;
+    *rounds = fri_layout(*cfg, false).R;   // src/fri.rs:93-103
     return SMI_OK;
-}
-
-static bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
-static uint32_t ilog2(uint64_t n) {
-    uint32_t l = 0;
-    while ((n >> l) > 1) l++;
-    return l;
 }
 
 int smi_fri_check(const smi_ctx *ctx, const smi_fri_cfg *cfg) {
@@ -311,6 +291,7 @@ int smi_fri_check(const smi_ctx *ctx, const smi_fri_cfg *cfg) {
     return SMI_OK;
 }
 
+// Every device buffer of a run is handed to it at the moment it is allocated: smi_fri_run_free is the only place that frees.
 struct smi_fri_run {
     smi_ctx *ctx;
     std::vector<uint32_t *> codewords;  // device, lengths N, N/2, ...
@@ -329,6 +310,19 @@ static void *run_alloc(smi_fri_run *run, size_t bytes) {
         return nullptr;
     }
     return q;
+}
+static uint32_t *run_codeword(smi_fri_run *run, uint64_t len) {
+    uint32_t *cw = (uint32_t *)run_alloc(run, len * 4);
+    if (cw) {
+        run->codewords.push_back(cw);
+        run->lens.push_back(len);
+    }
+    return cw;
+}
+static uint8_t *run_tree(smi_fri_run *run, uint64_t len) {
+    uint8_t *nodes = (uint8_t *)run_alloc(run, (2 * len - 1) * 32);
+    if (nodes) run->trees.push_back(nodes);
+    return nodes;
 }
 
 void smi_fri_run_free(smi_fri_run *run) {
@@ -351,20 +345,13 @@ void smi_fri_run_free(smi_fri_run *run) {
     delete run;
 }
 
-// Folds `count` outputs starting at global index i0 of a codeword of length full_len:
-// out[k] = fold(lo[k], hi[k]) where lo[k] = c[i0+k], hi[k] = c[i0+k+full_len/2].
-int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, size_t full_len,
-                             const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out) {
-    const uint32_t p = ctx->fs.F.p;
-    if (full_len < 2 || !is_pow2(full_len)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2");
-    if (i0 + count > full_len / 2) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: shard outside the folded codeword");
-    if (offset >= p || omega >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "fold: offset/omega must be < p");
+int fri_fold_tables(smi_ctx *ctx, uint32_t offset, uint32_t omega, uint64_t len, ScaleTables *S) {
+    if (len < 2 || !is_pow2(len)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2");
     if (offset == 0 || omega == 0) return smi_fail(ctx, SMI_ERR_DIV_BY_ZERO, "no division by zero");  // src/ff.rs:182
-    if (!count) return SMI_OK;
-    ScaleScope pin__(ctx);
-    ScaleTables S;
-    SMI_TRY(ctx_scale_tables(ctx, h_inv(ctx, (uint32_t)offset), h_inv(ctx, (uint32_t)omega), ilog2(full_len / 2), &S));
-    const uint32_t inv2_m = (uint32_t)(((uint64_t)h_inv(ctx, 2) << 32) % p);
+    return ctx_scale_tables(ctx, h_inv(ctx, offset), h_inv(ctx, omega), ilog2(len / 2), S);
+}
+static int launch_fold_tables(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, const uint64_t *d_alpha,
+                              const ScaleTables &S, uint32_t inv2_m, uint32_t *d_out) {
     uint32_t grid = (uint32_t)((count + 255) / 256);
     if (grid > 2048) grid = 2048;
     ProfScope ps(ctx, "fri_fold_kernel", 12.0 * (double)count);  // read 2 x 4 B, write 4 B per output
@@ -372,10 +359,20 @@ int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, 
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
-int launch_fold(smi_ctx *ctx, const uint32_t *d_in, size_t len, const uint64_t *d_alpha, uint64_t offset, uint64_t omega,
-                uint32_t *d_out) {
-    if (len < 2 || !is_pow2(len)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2");
-    return launch_fold_shard(ctx, d_in, d_in + len / 2, len / 2, 0, len, d_alpha, offset, omega, d_out);
+// Folds `count` outputs starting at global index i0 of a codeword of length full_len:
+// out[k] = fold(lo[k], hi[k]) where lo[k] = c[i0+k], hi[k] = c[i0+k+full_len/2].
+int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, size_t full_len,
+                      const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out) {
+    const uint32_t p = ctx->fs.F.p;
+    if (full_len < 2 || !is_pow2(full_len)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2");
+    if (i0 + count > full_len / 2) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: shard outside the folded codeword");
+    if (offset >= p || omega >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "fold: offset/omega must be < p");
+    if (offset == 0 || omega == 0) return smi_fail(ctx, SMI_ERR_DIV_BY_ZERO, "no division by zero");  // (also for an empty shard)
+    if (!count) return SMI_OK;
+    ScaleScope pin__(ctx);
+    ScaleTables S;
+    SMI_TRY(fri_fold_tables(ctx, (uint32_t)offset, (uint32_t)omega, full_len, &S));
+    return launch_fold_tables(ctx, d_lo, d_hi, count, i0, d_alpha, S, fri_inv2_m(ctx), d_out);
 }
 int smi_dev_fri_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t index0, size_t full_len,
                            const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out) {
@@ -384,25 +381,13 @@ int smi_dev_fri_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d
     return launch_fold_shard(ctx, d_lo, d_hi, count, index0, full_len, d_alpha, offset, omega, d_out);
 }
 
-// misc device block layout (the challenges and the sampled indices are not here: they sit behind the proof, fri_run)
-struct MiscLayout {
-    size_t fs, seed_ch, reduced, layers, total;
-};
-static MiscLayout misc_layout(uint64_t R, uint64_t t) {
-    MiscLayout m;
-    size_t o = 0;
-    m.fs = o; o += sizeof(FsState);
-    o = (o + 63) & ~(size_t)63;
-    m.seed_ch = o; o += 8;
-    m.reduced = o; o += 8 * (t + 1);
-    o = (o + 63) & ~(size_t)63;
-    m.layers = o; o += sizeof(LayerInfo) * (R + 1);
-    m.total = o;
-    return m;
-}
-
-// Fri::commit (+ optionally the query phase of Fri::prove) over a device codeword.
-// With do_query == false only roots/alphas/last codeword are produced.
+// Codewords of at most this many elements finish in the fused tail launch (hash.hip, fri_tail_kernel).
+// Measured on MI355X (2^25-point prove): the FRI stage is 4.44..4.69 ms with the tail
+// off, from 512, from 1024 or from 2048 elements alike -- the differences are inside the run-to-run
+// spread of +-0.1 ms, because the tail's cost is the serial chain tree -> alpha -> fold, not launch
+// overhead.  Default: 512, the size the per-round path hands to a single workgroup anyway (above it
+// the per-round path spreads a tree's 64-leaf chunks over several CUs).  SMI_FRI_TAIL=<len> overrides
+// (0: never).
 uint64_t fri_tail_len() {
     static const uint64_t tail_len = [] {
         const char *e = getenv("SMI_FRI_TAIL");
@@ -411,263 +396,225 @@ uint64_t fri_tail_len() {
     }();
     return tail_len;
 }
-int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
-                   smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
-                   uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src, const FsSeed *seed) {
-    SMI_TRY(smi_fri_check(ctx, cfg));
-    if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
+
+// What the three parts of fri_run share.  Device block `misc`: fs state | seed challenge | reduced indices | layer table;
+// the challenges, the sampled indices and the caller's ride-along bytes live behind the proof in ONE device buffer, so
+// that everything the host needs comes back in a single device-to-host copy: four copies cost 17 + 5 + 4 + 4 us of blit
+// kernels and 86 us of runtime gaps between them at the end of every prove (profiles/r03_b_prove_timeline.txt).
+struct FriExec {
+    smi_ctx *ctx;
+    const FriRequest *rq;
+    smi_fri_run *run;
+    FriLayout lay;
+    FriRoundPlan plan;
+    uint32_t phase;
+    size_t off_al, off_top, off_ride, back_len;   // in run->d_proof
+    FsSeed *d_fs;
+    uint64_t *d_alphas, *d_seed_ch, *d_top, *d_reduced;
+    LayerInfo *d_layers;
+};
+
+// part 1: validate, lay out, allocate, start the transcript
+static int fri_setup(FriExec &x) {
+    smi_ctx *ctx = x.ctx;
+    const FriRequest &rq = *x.rq;
+    SMI_TRY(smi_fri_check(ctx, rq.cfg));
+    if (rq.cfg->domain_length != rq.len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     const uint32_t p = ctx->fs.F.p;
-    if (cfg->omega >= p || cfg->offset >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
-    uint64_t R;
-    smi_fri_num_rounds(cfg, &R);
+    if (rq.cfg->omega >= p || rq.cfg->offset >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
+    x.lay = fri_layout(*rq.cfg, rq.do_query);
+    const uint64_t R = x.lay.R, t = rq.cfg->num_colinearity_tests;
     if (R == 0) return smi_fail(ctx, SMI_ERR_NO_ROUNDS, "num_rounds() == 0: the reference's verify rejects such a proof");
-    const uint64_t t = cfg->num_colinearity_tests;
-    const uint64_t last_n = len >> (R - 1);
-    if (do_query) {  // asserts of src/fri.rs:183-192
-        if (t > 2 * last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, "not enough entropy in indices wrt last codeword");
-        if (t > last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, "cannot sample more indices than available in last codeword");
+    if (rq.do_query) {  // asserts of src/fri.rs:183-192
+        if (t > 2 * x.lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, "not enough entropy in indices wrt last codeword");
+        if (t > x.lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, "cannot sample more indices than available in last codeword");
     }
+    const FsSeed fs0 = rq.seed ? *rq.seed : fresh_seed();
+    x.phase = fs0.phase;
+    const int round0 = rq.round0_src ? FRI_R0_COMBINE : (((uintptr_t)rq.d_codeword & 15u) ? FRI_R0_UNALIGNED : FRI_R0_ALIGNED16);
+    x.plan = fri_round_plan(rq.len, R, x.phase, fri_tail_len(), round0, merkle_knobs_env());
+    if (!x.plan.ok) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri: the initial codeword is too short for a computed leaf source");
 
-    ScaleScope pin__(ctx);   // the fused tail collects one x^-1 table per fold before its single launch
-    smi_fri_run *run = new smi_fri_run();
-    run->ctx = ctx;
-    run->owns_first = false;
-    run->arena = run_out == nullptr;   // nothing outlives the call: use the recycled arena
-    if (run->arena && reset_arena) (void)arena_reset(ctx);
-    run->d_misc = nullptr;
-    run->d_proof = nullptr;
-    int rc = SMI_OK;
-    auto bail = [&](int code) {
-        smi_fri_run_free(run);
-        return code;
-    };
+    smi_fri_run *run = x.run = new smi_fri_run{ctx, {}, {}, {}, nullptr, nullptr, false, !rq.retain};   // not retained: the arena
+    if (run->arena && rq.reset_arena) (void)arena_reset(ctx);
+    run->codewords.push_back(const_cast<uint32_t *>(rq.d_codeword));
+    run->lens.push_back(rq.len);
 
-    // proof layout (src/fri.rs:129,151,229-243; tags src/stream.rs:39-60)
-    const size_t off_roots = 0, off_last = 33 * R, off_layers = off_last + 9 + 8 * last_n;
-    std::vector<LayerInfo> layers(R ? R - 1 : 0);
-    size_t off = off_layers;
-    for (uint64_t i = 0; i + 1 < R; i++) {
-        const uint64_t li = len >> i;
-        const uint32_t d = ilog2(li);
-        layers[i].len = li;
-        layers[i].depth = d;
-        layers[i].depth_next = d - 1;
-        layers[i].off_triples = off;
-        off += 33 * t;
-        layers[i].off_paths = off;
-        off += t * (2 * (9 + 32ull * d) + (9 + 32ull * (d - 1)));
-    }
-    const size_t proof_len = do_query ? off : off_layers;
-
-    const MiscLayout ml = misc_layout(R, t);
-    if (!(run->d_misc = run_alloc(run, ml.total))) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc misc"));
-    // The challenges, the sampled indices and the caller's ride-along bytes live behind the proof in ONE device buffer, so
-    // that everything the host needs comes back in a single device-to-host copy: four copies cost 17 + 5 + 4 + 4 us of blit
-    // kernels and 86 us of runtime gaps between them at the end of every prove (profiles/r03_b_prove_timeline.txt).
-    const size_t off_al = (proof_len + 7) & ~(size_t)7, off_top = off_al + 8 * R, off_ride = off_top + 8 * (t + 1);
-    const void *ride_src = ctx->ride_src;
-    const size_t ride_bytes = ride_src ? ctx->ride_bytes : 0;
-    void *ride_dst = ctx->ride_dst;
-    ctx->ride_src = nullptr;
-    ctx->ride_bytes = 0;
-    ctx->ride_dst = nullptr;
-    const size_t back_len = off_ride + ride_bytes;
-    if (!(run->d_proof = (uint8_t *)run_alloc(run, back_len))) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc proof"));
+    const size_t m_seed_ch = (sizeof(FsSeed) + 63) & ~(size_t)63, m_reduced = m_seed_ch + 8;
+    const size_t m_layers = (m_reduced + 8 * (t + 1) + 63) & ~(size_t)63;
+    if (!(run->d_misc = run_alloc(run, m_layers + sizeof(LayerInfo) * (R + 1)))) return smi_fail(ctx, SMI_ERR_OOM, "alloc misc");
+    x.off_al = (x.lay.proof_len + 7) & ~(size_t)7;
+    x.off_top = x.off_al + 8 * R;
+    x.off_ride = x.off_top + 8 * (t + 1);
+    x.back_len = x.off_ride + (rq.ride_src ? rq.ride_bytes : 0);
+    if (!(run->d_proof = (uint8_t *)run_alloc(run, x.back_len))) return smi_fail(ctx, SMI_ERR_OOM, "alloc proof");
     uint8_t *misc = (uint8_t *)run->d_misc;
-    FsState *d_fs = (FsState *)(misc + ml.fs);
-    uint64_t *d_alphas = (uint64_t *)(run->d_proof + off_al);
-    uint64_t *d_seed_ch = (uint64_t *)(misc + ml.seed_ch);
-    uint64_t *d_top = (uint64_t *)(run->d_proof + off_top);
-    uint64_t *d_reduced = (uint64_t *)(misc + ml.reduced);
-    LayerInfo *d_layers = (LayerInfo *)(misc + ml.layers);
+    x.d_fs = (FsSeed *)misc;
+    x.d_seed_ch = (uint64_t *)(misc + m_seed_ch);
+    x.d_reduced = (uint64_t *)(misc + m_reduced);
+    x.d_layers = (LayerInfo *)(misc + m_layers);
+    x.d_alphas = (uint64_t *)(run->d_proof + x.off_al);
+    x.d_top = (uint64_t *)(run->d_proof + x.off_top);
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(x.d_fs, fs0, (const uint8_t *)rq.ride_src, run->d_proof + x.off_ride,
+                                              x.back_len - x.off_ride);
+    return SMI_OK;
+}
 
-    const FsSeed fs0 = seed ? *seed : fresh_seed();
-    const uint32_t phase = fs0.phase;
-    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, fs0, (const uint8_t *)ride_src, run->d_proof + off_ride, ride_bytes);
-
-    uint32_t omega = (uint32_t)cfg->omega, offset = (uint32_t)cfg->offset;
-    const uint32_t *cur = d_codeword;
-    uint64_t cur_len = len;
-    // Codewords of at most this many elements finish in the fused tail launch (hash.hip, fri_tail_kernel).
-    // Measured on MI355X (2^25-point prove): the FRI stage is 4.44..4.69 ms with the tail
-    // off, from 512, from 1024 or from 2048 elements alike -- the differences are inside the run-to-run
-    // spread of +-0.1 ms, because the tail's cost is the serial chain tree -> alpha -> fold, not launch
-    // overhead.  Default: 512, the size the per-round path hands to a single workgroup anyway (above it
-    // the per-round path spreads a tree's 64-leaf chunks over several CUs).  SMI_FRI_TAIL=<len> overrides
-    // (0: never).
-    const uint64_t tail_len = fri_tail_len();
-    // The fused tail runs the sixteen-lane Fiat-Shamir round, which knows phase 0 only.  Decided here once, for the loop
-    // head and for the fold-elision lookahead alike: a fold elided into a tail that then does not run would be lost.
-    auto tail_from = [&](uint64_t n, uint64_t round) { return phase == 0 && n <= tail_len && R - round <= SMI_FRI_TAIL_MAX_ROUNDS; };
+// part 2: the rounds of Fri::commit (src/fri.rs:116-148), as the round plan says (fri_plan.h).  A round's codeword is read
+// from memory, or computed by the launch that hashes it (LeafSrc, internal.h; the codeword buffer is written by that launch
+// and everything downstream reads it as before), or folded inside the tail launch.
+static int fri_rounds(FriExec &x) {
+    smi_ctx *ctx = x.ctx;
+    smi_fri_run *run = x.run;
+    const FriRoundPlan &plan = x.plan;
+    const uint32_t R = plan.R, inv2_m = fri_inv2_m(ctx);
+    uint32_t omega = (uint32_t)x.rq->cfg->omega, offset = (uint32_t)x.rq->cfg->offset;
     // phase != 0: the merkle launches get no Fiat-Shamir hook (fs_words == nullptr), a phase-aware kernel follows each tree
-    uint32_t *const hook_fs = phase == 0 ? d_fs->s : nullptr;
-    static const bool fold_in_tail = !(getenv("SMI_MERKLE_FUSE") && atoi(getenv("SMI_MERKLE_FUSE")) == 0);
-    // The leaves of a round's tree can be computed by the launch that hashes them (LeafSrc, internal.h): the initial
-    // codeword as the caller's weighted column sum (round0_src), every later one as the fold of the round before --
-    // wherever the tree starts with the four-leaves-per-lane kernel (merkle_fuses_leaf_source).  The codeword buffer is
-    // written by that launch; everything downstream reads it as before.
-    LeafSrc pending;
-    memset(&pending, 0, sizeof pending);
-    bool have_pending = false;
-    if (round0_src) {
-        if (!merkle_fuses_leaf_source(len) || !(cur_len > tail_len)) return bail(smi_fail(ctx, SMI_ERR_BAD_ARG, "fri: the initial codeword is too short for a computed leaf source"));
-        pending = *round0_src;
-        have_pending = true;
+    uint32_t *const hook_fs = x.phase == 0 ? x.d_fs->s : nullptr;
+    FriTailArgs ta;   // every round from plan.tail_at on, in one workgroup launch (hash.hip, fri_tail_kernel)
+    if (plan.tail_at < R) {
+        memset(&ta, 0, sizeof ta);
+        ta.n_rounds = R - plan.tail_at;
+        ta.fs_words = x.d_fs->s;
+        ta.F = ctx->fs.F;
+        ta.inv2_m = inv2_m;
     }
-    for (uint64_t r = 0; r < R; r++) {
-        if (tail_from(cur_len, r)) {
-            // every remaining round in one workgroup launch (hash.hip, fri_tail_kernel)
-            // the tail holds one x^-1 table per fold until its launch: none of them may be evicted in between
-            if ((rc = ctx_scale_reserve(ctx, (size_t)(R - r))) != SMI_OK) return bail(rc);
-            FriTailArgs ta;
-            memset(&ta, 0, sizeof ta);
-            ta.n_rounds = (uint32_t)(R - r);
-            ta.fs_words = d_fs->s;
-            ta.F = ctx->fs.F;
-            ta.inv2_m = (uint32_t)(((uint64_t)h_inv(ctx, 2) << 32) % p);
-            if (have_pending) {   // the fold into this codeword runs at the head of the tail launch
-                ta.pre_lo = pending.lo;
-                ta.pre_hi = pending.hi;
-                ta.pre_alpha = pending.alpha;
-                ta.pre_S = pending.S;
-                have_pending = false;
-            }
-            for (uint64_t k = r; k < R; k++) {
-                FriTailRound &tr = ta.r[k - r];
-                const bool last = k == R - 1;
-                tr.cw = cur;
-                tr.len = (uint32_t)cur_len;
-                run->codewords.push_back(const_cast<uint32_t *>(cur));
-                run->lens.push_back(cur_len);
-                tr.nodes = (uint8_t *)run_alloc(run, (2 * cur_len - 1) * 32);
-                if (!tr.nodes) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc tree"));
-                run->trees.push_back(tr.nodes);
-                tr.proof_slot = run->d_proof + off_roots + 33 * k;
-                tr.alpha_out = last ? nullptr : d_alphas + k;
-                if (last) break;
-                if (cur_len < 2) return bail(smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2"));
-                if (offset == 0 || omega == 0) return bail(smi_fail(ctx, SMI_ERR_DIV_BY_ZERO, "no division by zero"));   // src/ff.rs:182
-                if ((rc = ctx_scale_tables(ctx, h_inv(ctx, offset), h_inv(ctx, omega), ilog2(cur_len / 2), &tr.S)) != SMI_OK) return bail(rc);
-                tr.next = (uint32_t *)run_alloc(run, (cur_len / 2) * 4);
-                if (!tr.next) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc codeword"));
-                cur = tr.next;
-                cur_len /= 2;
-                omega = h_mul(ctx, omega, omega);    // src/fri.rs:146-147
-                offset = h_mul(ctx, offset, offset);
-            }
-            if ((rc = launch_fri_tail(ctx, ta)) != SMI_OK) return bail(rc);
-            break;
-        }
-        // leaf hashes + tree (src/fri.rs:118-127); power-of-two lengths never need padding
-        run->codewords.push_back(const_cast<uint32_t *>(cur));   // owned by the run from here on: nothing below can leak it
-        run->lens.push_back(cur_len);
-        uint8_t *nodes = (uint8_t *)run_alloc(run, (2 * cur_len - 1) * 32);
-        if (!nodes) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc tree"));
-        run->trees.push_back(nodes);
-        const uint32_t *root = (const uint32_t *)(nodes + (2 * cur_len - 2) * 32);
+    LeafSrc pending;   // how the launch that hashes this round's leaves computes them
+    bool have_pending = x.rq->round0_src != nullptr;
+    if (have_pending) pending = *x.rq->round0_src;
+    for (uint32_t r = 0; r < R; r++) {
+        const uint32_t *cur = run->codewords[r];
+        const uint64_t len = run->lens[r];
         const bool last = r == R - 1;
-        // push root, absorb, challenge (src/fri.rs:129-138): done by the workgroup that finishes the tree
-        // when that is the chunk kernel (one launch fewer per round), by a kernel of its own otherwise
-        bool fs_done = false;
-        if (have_pending) {
-            rc = launch_merkle_src_fs(ctx, pending, cur_len, nodes, hook_fs, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
-            have_pending = false;
+        // leaf hashes + tree (src/fri.rs:118-127); power-of-two lengths never need padding
+        uint8_t *nodes = run_tree(run, len);
+        if (!nodes) return smi_fail(ctx, SMI_ERR_OOM, "alloc tree");
+        uint8_t *slot = run->d_proof + 33 * r;
+        uint64_t *alpha_out = last ? nullptr : x.d_alphas + r;   // no challenge after the last root (src/fri.rs:133-135)
+        FriTailRound *tr = plan.tree[r] == FRI_TREE_TAIL ? &ta.r[r - plan.tail_at] : nullptr;
+        if (tr) {
+            // the tail holds one x^-1 table per fold until its launch: none of them may be evicted in between
+            if (r == plan.tail_at) SMI_TRY(ctx_scale_reserve(ctx, (size_t)(R - r)));
+            tr->cw = cur;
+            tr->len = (uint32_t)len;
+            tr->nodes = nodes;
+            tr->proof_slot = slot;
+            tr->alpha_out = alpha_out;
         } else {
-            rc = launch_merkle_fs(ctx, cur, cur_len, nodes, hook_fs, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r, &fs_done);
+            // push root, absorb, challenge (src/fri.rs:129-138): done by the workgroup that finishes the tree
+            // when that is the chunk kernel (one launch fewer per round), by a kernel of its own otherwise
+            bool fs_done = false;
+            if (have_pending) SMI_TRY(launch_merkle_src_fs(ctx, pending, len, nodes, hook_fs, slot, alpha_out, &fs_done));
+            else SMI_TRY(launch_merkle_fs(ctx, cur, len, nodes, hook_fs, slot, alpha_out, &fs_done));
+            have_pending = false;
+            if (!fs_done) SMI_TRY(launch_fs_round(ctx, x.d_fs, nodes + (2 * len - 2) * 32, slot, alpha_out, x.phase));
         }
-        if (rc != SMI_OK) return bail(rc);
-        if (!fs_done && (rc = launch_fs_round(ctx, d_fs, (const uint8_t *)root, run->d_proof + off_roots + 33 * r, last ? nullptr : d_alphas + r,
-                                              phase)) != SMI_OK)
-            return bail(rc);
         if (last) break;
-        uint32_t *next = (uint32_t *)run_alloc(run, (cur_len / 2) * 4);
-        if (!next) return bail(smi_fail(ctx, SMI_ERR_OOM, "alloc codeword"));
-        const uint64_t next_len = cur_len / 2;
-        const bool next_is_tail = tail_from(next_len, r + 1);
-        // (the computed-leaf kernel reads and writes four elements at a time: 16-byte aligned buffers only -- the library's own
-        // are, a caller's initial codeword need not be)
-        const bool aligned16 = (((uintptr_t)cur | (uintptr_t)next) & 15u) == 0;
-        if ((merkle_fuses_leaf_source(next_len) && !next_is_tail && aligned16) || (merkle_chunks_fold(next_len) && !next_is_tail) ||
-            (next_is_tail && fold_in_tail)) {
-            // no fold launch: the next round's leaf kernel (the four-leaves-per-lane kernel, the chunk kernel or the fused
-            // tail, whichever that round starts with) folds (same checks and tables as launch_fold_shard)
-            if (offset == 0 || omega == 0) {
-                if (!run->arena) (void)hipFree(next);
-                return bail(smi_fail(ctx, SMI_ERR_DIV_BY_ZERO, "no division by zero"));   // src/ff.rs:182
-            }
+        const uint64_t half = len / 2;
+        uint32_t *next = run_codeword(run, half);
+        if (!next) return smi_fail(ctx, SMI_ERR_OOM, "alloc codeword");
+        ScaleTables S;
+        SMI_TRY(fri_fold_tables(ctx, offset, omega, len, &S));
+        switch (plan.producer[r + 1]) {
+        case FRI_BY_FOLD:
+            SMI_TRY(launch_fold_tables(ctx, cur, cur + half, half, 0, x.d_alphas + r, S, inv2_m, next));
+            break;
+        case FRI_BY_LEAF_QUAD:   // four elements per access.  Round 1 was planned from the caller's pointer and every later buffer
+            assert((((uintptr_t)cur | (uintptr_t)next) & 15u) == 0);   // is the arena's or hipMalloc's: this can only be a library bug
+            [[fallthrough]];
+        case FRI_BY_LEAF_CHUNK:
             memset(&pending, 0, sizeof pending);
             pending.kind = LEAF_FOLD;
             pending.cw_out = next;
             pending.F = ctx->fs.F;
             pending.lo = cur;
-            pending.hi = cur + next_len;
-            pending.alpha = d_alphas + r;
-            pending.inv2_m = (uint32_t)(((uint64_t)h_inv(ctx, 2) << 32) % p);
-            if ((rc = ctx_scale_tables(ctx, h_inv(ctx, offset), h_inv(ctx, omega), ilog2(next_len), &pending.S)) != SMI_OK) {
-                if (!run->arena) (void)hipFree(next);
-                return bail(rc);
-            }
+            pending.hi = cur + half;
+            pending.alpha = x.d_alphas + r;
+            pending.inv2_m = inv2_m;
+            pending.S = S;
             have_pending = true;
-        } else if ((rc = launch_fold(ctx, cur, cur_len, d_alphas + r, offset, omega, next)) != SMI_OK) {
-            if (!run->arena) (void)hipFree(next);
-            return bail(rc);
+            break;
+        case FRI_BY_TAIL_HEAD:
+            ta.pre_lo = cur;
+            ta.pre_hi = cur + half;
+            ta.pre_alpha = x.d_alphas + r;
+            ta.pre_S = S;
+            break;
+        default:   // FRI_IN_TAIL
+            tr->next = next;
+            tr->S = S;
         }
-        cur = next;
-        cur_len /= 2;
         omega = h_mul(ctx, omega, omega);    // src/fri.rs:146-147
         offset = h_mul(ctx, offset, offset);
     }
-    // last codeword in the clear (src/fri.rs:151)
-    emit_codeword_kernel<<<(uint32_t)((cur_len + 255) / 256), 256, 0, ctx->stream>>>(cur, cur_len, run->d_proof + off_last);
+    if (plan.tail_at < R) SMI_TRY(launch_fri_tail(ctx, ta));
+    return SMI_OK;
+}
 
-    if (do_query) {
-        if ((rc = launch_fs_challenge(ctx, d_fs, d_seed_ch, phase)) != SMI_OK) return bail(rc);
+// part 3: the last codeword in the clear, the query phase of Fri::prove, and the one synchronising copy-back
+static int fri_finish(FriExec &x, FriResult *res) {
+    smi_ctx *ctx = x.ctx;
+    smi_fri_run *run = x.run;
+    const FriLayout &lay = x.lay;
+    const uint64_t R = lay.R, t = x.rq->cfg->num_colinearity_tests, len = x.rq->len;
+    std::vector<LayerInfo> layers(R - 1);   // lives past the synchronisation below: the source of an asynchronous copy
+    SMI_TRY(launch_emit_codeword(ctx, run->codewords[R - 1], lay.last_n, run->d_proof + lay.off_last));   // src/fri.rs:151
+    if (x.rq->do_query) {
+        SMI_TRY(launch_fs_challenge(ctx, x.d_fs, x.d_seed_ch, x.phase));
         const uint64_t sample_size = R > 1 ? len / 2 : len;  // src/fri.rs:266-270
-        sample_indices_kernel<<<1, 64, 0, ctx->stream>>>(d_seed_ch, sample_size, last_n, (uint32_t)t, d_top, d_reduced);
+        SMI_TRY(launch_sample_indices(ctx, x.d_seed_ch, sample_size, lay.last_n, (uint32_t)t, x.d_top, x.d_reduced));
         if (R > 1 && t > 0) {
             for (uint64_t i = 0; i + 1 < R; i++) {
-                layers[i].cw = run->codewords[i];
-                layers[i].cw_next = run->codewords[i + 1];
-                layers[i].nodes = run->trees[i];
-                layers[i].nodes_next = run->trees[i + 1];
+                LayerInfo &L = layers[i];
+                L.cw = run->codewords[i];
+                L.cw_next = run->codewords[i + 1];
+                L.nodes = run->trees[i];
+                L.nodes_next = run->trees[i + 1];
+                L.len = len >> i;
+                L.off_triples = lay.off_triples[i];
+                L.off_paths = lay.off_paths[i];
+                L.depth = ilog2(L.len);
+                L.depth_next = L.depth - 1;
             }
-            if (R - 1 <= SMI_QUERY_TAB_MAX) {
+            const dim3 grid((uint32_t)t, (uint32_t)(R - 1));
+            if (R - 1 <= SMI_QUERY_TAB_MAX) {   // the layer table travels as a kernel argument while it fits
                 LayerTable tab;
                 memset(&tab, 0, sizeof tab);
                 memcpy(tab.l, layers.data(), sizeof(LayerInfo) * (R - 1));
-                query_tab_kernel<<<dim3((uint32_t)t, (uint32_t)(R - 1)), 64, 0, ctx->stream>>>(tab, d_top, (uint32_t)t, run->d_proof);
+                query_tab_kernel<<<grid, 64, 0, ctx->stream>>>(tab, x.d_top, (uint32_t)t, run->d_proof);
             } else {
-                if (hipMemcpyAsync(d_layers, layers.data(), sizeof(LayerInfo) * (R - 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-                    return bail(smi_fail(ctx, SMI_ERR_HIP, "hipMemcpyAsync layers"));
-                query_kernel<<<dim3((uint32_t)t, (uint32_t)(R - 1)), 64, 0, ctx->stream>>>(d_layers, d_top, (uint32_t)t, run->d_proof);
+                HIP_TRY(ctx, hipMemcpyAsync(x.d_layers, layers.data(), sizeof(LayerInfo) * (R - 1), hipMemcpyHostToDevice, ctx->stream));
+                query_kernel<<<grid, 64, 0, ctx->stream>>>(x.d_layers, x.d_top, (uint32_t)t, run->d_proof);
             }
         }
     }
-    if (hipGetLastError() != hipSuccess) return bail(smi_fail(ctx, SMI_ERR_HIP, "fri kernel launch"));
+    if (hipGetLastError() != hipSuccess) return smi_fail(ctx, SMI_ERR_HIP, "fri kernel launch");
 
-    // one synchronising copy-back, through the context's pinned landing buffer: proof | challenges | indices | ride-along
+    // through the context's pinned landing buffer: proof | challenges | indices | ride-along
     uint8_t *land = nullptr;
-    if ((rc = ctx_pin_out(ctx, back_len, &land)) != SMI_OK) return bail(rc);
-    if (hipMemcpyAsync(land, run->d_proof, back_len, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        return bail(smi_fail(ctx, SMI_ERR_HIP, "copy proof"));
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(smi_hip_fail(ctx, e, "fri sync"));
-    std::vector<uint8_t> proof(land, land + proof_len);
-    std::vector<uint64_t> alphas(R), top(t + 1);
-    if (R > 1) memcpy(alphas.data(), land + off_al, 8 * (R - 1));
-    if (do_query && t) memcpy(top.data(), land + off_top, 8 * t);
-    if (ride_bytes && ride_dst) memcpy(ride_dst, land + off_ride, ride_bytes);
-
-    if (roots_host)
-        for (uint64_t r = 0; r < R; r++) memcpy(roots_host + 32 * r, proof.data() + 33 * r + 1, 32);
-    if (alphas_host) memcpy(alphas_host, alphas.data(), 8 * (R - 1));
-    if (last_host) memcpy(last_host, proof.data() + off_last + 9, 8 * last_n);
-    if (last_len) *last_len = last_n;
-    if (top_host && do_query) memcpy(top_host, top.data(), 8 * t);
-    if (proof_host) proof_host->swap(proof);
-    if (run_out) *run_out = run;
-    else smi_fri_run_free(run);
+    SMI_TRY(ctx_pin_out(ctx, x.back_len, &land));
+    HIP_TRY(ctx, hipMemcpyAsync(land, run->d_proof, x.back_len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    res->lay = lay;
+    res->proof.assign(land, land + lay.proof_len);
+    res->alphas.assign(R, 0);
+    res->top.assign(t + 1, 0);
+    if (R > 1) memcpy(res->alphas.data(), land + x.off_al, 8 * (R - 1));
+    if (x.rq->do_query && t) memcpy(res->top.data(), land + x.off_top, 8 * t);
+    if (x.back_len > x.off_ride && x.rq->ride_dst) memcpy(x.rq->ride_dst, land + x.off_ride, x.back_len - x.off_ride);
     return SMI_OK;
+}
+
+int fri_run(smi_ctx *ctx, const FriRequest &rq, FriResult *res) {
+    ScaleScope pin__(ctx);   // the fused tail collects one x^-1 table per fold before its single launch
+    FriExec x;
+    x.ctx = ctx, x.rq = &rq, x.run = nullptr;
+    int rc = fri_setup(x);
+    if (rc == SMI_OK) rc = fri_rounds(x);
+    if (rc == SMI_OK) rc = fri_finish(x, res);
+    if (rc == SMI_OK && rq.retain) res->run = x.run;
+    else smi_fri_run_free(x.run);
+    return rc;
 }
 
 // ------------------------------------------------------------------------- C ABI
@@ -696,7 +643,7 @@ int smi_dev_fri_fold(smi_ctx *ctx, const uint32_t *d_in, size_t len, const uint6
                      uint64_t omega, uint32_t *d_out) {
     if (!ctx || !d_in || !d_alpha || !d_out) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
-    return launch_fold(ctx, d_in, len, d_alpha, offset, omega, d_out);
+    return launch_fold_shard(ctx, d_in, d_in + len / 2, len / 2, 0, len, d_alpha, offset, omega, d_out);   // (it checks len)
 }
 
 // the caller's transcript (host bytes) as the device starts from it; (NULL, 0) is a fresh FiatShamir
@@ -712,13 +659,14 @@ int smi_dev_fri_prove_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *tr
     FsSeed seed;
     SMI_TRY(transcript_seed(transcript, transcript_len, &seed));
     DeviceGuard dg__(ctx);
-    std::vector<uint8_t> bytes;
-    SMI_TRY(fri_run(ctx, cfg, d_codeword, len, true, true, run, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr, nullptr, &seed));
-    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
-    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
-    memcpy(*proof, bytes.data(), bytes.size());
-    *proof_len = bytes.size();
-    return SMI_OK;
+    FriRequest rq(cfg, d_codeword, len, true);
+    rq.retain = run != nullptr;
+    rq.seed = &seed;
+    FriResult res;
+    SMI_TRY(fri_run(ctx, rq, &res));
+    if (run) *run = res.run;
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    return smi_proof_out(ctx, res.proof, proof, proof_len);
 }
 
 int smi_dev_fri_prove(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, uint8_t **proof,
@@ -759,13 +707,23 @@ int smi_fri_commit_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *trans
     if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     uint32_t *d_cw = nullptr;
     int rc = upload_codeword(ctx, codeword, len, &d_cw);
-    smi_fri_run *r = nullptr;
-    if (rc == SMI_OK) rc = fri_run(ctx, cfg, d_cw, len, false, true, run ? &r : nullptr, nullptr, nullptr, roots, alphas, last_codeword, last_len, nullptr,
-                                   &seed);
+    FriRequest rq(cfg, d_cw, len, false);
+    rq.retain = run != nullptr;
+    rq.seed = &seed;
+    FriResult res;
+    if (rc == SMI_OK) rc = fri_run(ctx, rq, &res);
     (void)hipStreamSynchronize(ctx->stream);
+    if (rc == SMI_OK) {
+        const uint64_t R = res.lay.R;
+        if (roots)
+            for (uint64_t r = 0; r < R; r++) memcpy(roots + 32 * r, res.proof.data() + 33 * r + 1, 32);
+        if (alphas) memcpy(alphas, res.alphas.data(), 8 * (R - 1));
+        if (last_codeword) memcpy(last_codeword, res.proof.data() + res.lay.off_last + 9, 8 * res.lay.last_n);
+        if (last_len) *last_len = res.lay.last_n;
+    }
     if (rc == SMI_OK && run) {
-        r->owns_first = true;  // the run keeps the uploaded codeword
-        *run = r;
+        res.run->owns_first = true;  // the run keeps the uploaded codeword
+        *run = res.run;
     } else {
         (void)hipFree(d_cw);
     }
@@ -787,6 +745,7 @@ int smi_fri_fold(smi_ctx *ctx, const uint64_t *codeword, size_t len, uint64_t al
     SMI_TRY(ctx_tmp(ctx, 3, 8, &d_alpha));
     SMI_TRY(host_to_dev_u32(ctx, codeword, len, (uint32_t *)d_in, 0));
     HIP_TRY(ctx, hipMemcpyAsync(d_alpha, &alpha, 8, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(launch_fold(ctx, (const uint32_t *)d_in, len, (const uint64_t *)d_alpha, offset, omega, (uint32_t *)d_out));
+    const uint32_t *cw = (const uint32_t *)d_in;
+    SMI_TRY(launch_fold_shard(ctx, cw, cw + len / 2, len / 2, 0, len, (const uint64_t *)d_alpha, offset, omega, (uint32_t *)d_out));
     return dev_u32_to_host(ctx, (const uint32_t *)d_out, len / 2, out);
 }

@@ -18,9 +18,6 @@
 #include "hash_hex.h"
 #include "internal.h"
 
-#ifndef SMI_HASH_THREADS
-#define SMI_HASH_THREADS 256   // tuning builds: -DSMI_HASH_THREADS=128 | 512
-#endif
 #define SMI_ROW_MAX 64   // columns per row leaf
 
 __device__ __forceinline__ size_t level_offset(size_t n, uint32_t lvl) { return 2 * n - ((2 * n) >> lvl); }
@@ -204,7 +201,6 @@ __global__ __launch_bounds__(SMI_HASH_THREADS) void merkle_sub_kernel(const uint
 #endif                     // 16 nodes = 256 lanes = one wave per SIMD: a level of a 1024-lane workgroup takes 1.0 us that way and
                            // 1.45 over quads; with 32 nodes (two waves per SIMD) both take 1.5, with 64 the rows lose, 2.5 to 1.5
                            // (tools/quad_hash_test.hip, profiles/r03_y_tophash_ubench.log)
-#define SMI_TOP_MAX 2048
 #define SMI_TOP_THREADS (SMI_TOP_MAX / 2)
 // Optional epilogue of the launch that produces a tree's root: the Fiat-Shamir round of Fri::commit
 // (hashc::fs_absorb_root) by lane 0 of the workgroup holding the root -- one launch fewer per FRI round.
@@ -547,19 +543,65 @@ int launch_hash_bytes_batch(smi_ctx *ctx, const uint8_t *d_msgs, size_t n, size_
     return SMI_OK;
 }
 
-static uint32_t log2_floor(size_t n) {
-    uint32_t l = 0;
-    while ((n >> l) > 1) l++;
-    return l;
-}
-
-// Builds levels (lvl_from, log2 n] of the tree in d_nodes; if d_elems != nullptr level 0 is
-// hashed from the codeword first (fused with the bottom levels).  n must be a power of two.
-int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
-                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
+// Builds every level of n_trees equally sized trees in d_nodes: tree y reads d_elems + y*elem_stride (nullptr: level 0
+// is in place already) and writes d_nodes + y*node_stride_bytes.  n must be a power of two.  The launches are
+// merkle_plan's steps (merkle_plan.h); this function only executes them.
 static int launch_merkle_impl(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
                               size_t node_stride_bytes, uint32_t row_cols, size_t row_stride, const TopHook *hook, bool *hook_done,
-                              const LeafSrc *src = nullptr);
+                              const LeafSrc *src = nullptr) {
+    const MerkleShape shape{n, n_trees, !d_elems ? MK_DIGESTS : (row_cols ? MK_ROWS : MK_ELEMENTS), row_cols};
+    const MerklePlan plan = merkle_plan(shape, merkle_knobs_env());
+    // a computed leaf source goes where the plan's first step takes it: the chunk kernel folds, the four-leaves-per-lane kernel
+    // folds or combines.  Checked before anything is launched.
+    if (src && !(plan.n_steps && (plan.s[0].src_cap == MK_SRC_QUAD || (plan.s[0].src_cap == MK_SRC_CHUNK && src->kind == LEAF_FOLD))))
+        return smi_fail(ctx, SMI_ERR_BAD_ARG, "merkle: this tree cannot take a computed leaf source");
+    LeafSrc none;
+    memset(&none, 0, sizeof none);
+    const size_t node_stride = node_stride_bytes / 16;
+    uint4 *nodes = (uint4 *)d_nodes;
+    for (uint32_t i = 0; i < plan.n_steps; i++) {
+        const MerkleStep &st = plan.s[i];
+        if (st.family == MK_LEAF_HASH) {
+            for (uint32_t y = 0; y < n_trees; y++) SMI_TRY(launch_leaf_hash(ctx, d_elems + y * elem_stride, 1, d_nodes + y * node_stride_bytes));
+            continue;
+        }
+        const bool leaves = st.from_leaves;
+        const int kind = leaves && src ? src->kind : LEAF_LOAD;
+        const MerkleCost cost = merkle_step_cost(st, shape);
+        ProfScope ps(ctx, st.family == MK_CHUNK ? "merkle_top_kernel" : (leaves ? "merkle_sub_kernel<leaves>" : "merkle_sub_kernel<digests>"),
+                     cost.bytes, cost.mixes);
+        const dim3 grid(st.grid, n_trees);
+        const size_t lds = st.lds;
+        if (st.family == MK_CHUNK) {
+            TopHook h{nullptr, nullptr, nullptr};
+            if (hook && st.ends_root) {
+                h = *hook;
+                *hook_done = true;
+            }
+            if (kind == LEAF_FOLD)
+                merkle_top_fold_kernel<<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(nodes, n, st.arg, h, *src);
+            else if (leaves)
+                merkle_top_kernel<true><<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(d_elems, nodes, n, 0, st.arg, elem_stride, node_stride, row_cols, row_stride, h);
+            else
+                merkle_top_kernel<false><<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(nullptr, nodes, n, st.level, st.arg, 0, node_stride, 0, 0, h);
+        } else if (st.inst == MK_INST_ROWS)
+            merkle_sub_kernel<true, 0, true><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, st.count, st.arg, elem_stride, node_stride, row_cols, row_stride, none);
+        else if (kind == LEAF_FOLD)      // leaves computed on the fly (LeafSrc): MK_SRC_QUAD, so MK_INST_K2
+            merkle_sub_kernel<true, 2, false, LEAF_FOLD><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, st.count, st.arg, elem_stride, node_stride, 0, 0, *src);
+        else if (kind == LEAF_COMBINE)
+            merkle_sub_kernel<true, 2, false, LEAF_COMBINE><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, st.count, st.arg, elem_stride, node_stride, 0, 0, *src);
+        else if (leaves && st.inst == MK_INST_K2)   // its stash holds two digests per lane
+            merkle_sub_kernel<true, 2, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, st.count, st.arg, elem_stride, node_stride, 0, 0, none);
+        else if (leaves)
+            merkle_sub_kernel<true, 0, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, st.count, st.arg, elem_stride, node_stride, 0, 0, none);
+        else if (st.inst == MK_INST_K2)             // no stash at all
+            merkle_sub_kernel<false, 2, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(nullptr, nodes, n, st.level, st.count, st.arg, 0, node_stride, 0, 0, none);
+        else
+            merkle_sub_kernel<false, 0, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(nullptr, nodes, n, st.level, st.count, st.arg, 0, node_stride, 0, 0, none);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return SMI_OK;
+}
 int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes) {
     return launch_merkle_batch(ctx, d_elems, n, d_nodes, 1, 0, 0);
 }
@@ -571,36 +613,11 @@ int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d
     *done = false;   // fs_words == nullptr: no epilogue, the caller runs the round itself
     return launch_merkle_impl(ctx, d_elems, n, d_nodes, 1, 0, 0, 0, 0, fs_words ? &hook : nullptr, done);
 }
-// The planner's rule, restated: with more than 2048 * TOP_BLOCKS leaves the first launch of a single tree is the
-// four-leaves-per-lane kernel (the chunk kernel takes over below that), and that kernel can compute its leaves (LeafSrc).
-static size_t merkle_top_blocks() {
-    static const size_t v = [] { const char *e = getenv("SMI_MERKLE_TOP_BLOCKS"); return (size_t)(e ? atoi(e) : 256); }();
-    return v;
-}
-// A tree that starts from codeword elements goes to the chunk kernel only once it has at most this many leaves: a chunk's
-// first level is then leaf hashing, nine mixes per leaf by single lanes, which the four-leaves-per-lane kernel does at twice
-// the rate even when it fills a quarter of the chip (tuning knob SMI_MERKLE_ELEMS_LOG, log2)
-static size_t merkle_elems_max() {
-    static const size_t v = [] { const char *e = getenv("SMI_MERKLE_ELEMS_LOG"); return (size_t)1 << (e ? atoi(e) : 19); }();
-    const size_t by_blocks = (size_t)SMI_TOP_MAX * merkle_top_blocks();
-    return v < by_blocks ? v : by_blocks;
-}
-bool merkle_fuses_leaf_source(size_t n) {
-    static const bool off = (getenv("SMI_MERKLE_FUSE") && atoi(getenv("SMI_MERKLE_FUSE")) == 0) ||
-                            (getenv("SMI_MERKLE_GENERIC") && atoi(getenv("SMI_MERKLE_GENERIC"))) ||
-                            (getenv("SMI_MERKLE_K") && atoi(getenv("SMI_MERKLE_K")) != 2);
-    return !off && n >= 8 && (n & (n - 1)) == 0 && n > merkle_elems_max();
-}
-// ... and with at most that many (and at least two) the first launch is the chunk kernel, which can fold as it reads
-bool merkle_chunks_fold(size_t n) {
-    static const bool off = getenv("SMI_MERKLE_FUSE") && atoi(getenv("SMI_MERKLE_FUSE")) == 0;
-    return !off && n >= 2 && (n & (n - 1)) == 0 && n <= merkle_elems_max();
-}
 // one tree whose leaves are computed by the launch that hashes them (src.cw_out receives the codeword)
 int launch_merkle_src_fs(smi_ctx *ctx, const LeafSrc &src, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
                          uint64_t *alpha_out, bool *done) {
-    const bool ok = merkle_fuses_leaf_source(n) || (src.kind == LEAF_FOLD && merkle_chunks_fold(n));
-    if (!ok || !src.cw_out || (src.kind == LEAF_COMBINE && (!src.n_cols || src.n_cols > SMI_LEAF_COMBINE_MAX)))
+    if (!is_pow2(n) || !src.cw_out || (src.kind != LEAF_FOLD && src.kind != LEAF_COMBINE) ||
+        (src.kind == LEAF_COMBINE && (!src.n_cols || src.n_cols > SMI_LEAF_COMBINE_MAX)))
         return smi_fail(ctx, SMI_ERR_BAD_ARG, "merkle: this tree cannot take a computed leaf source");
     const TopHook hook{fs_words, proof_slot, alpha_out};
     *done = false;
@@ -614,110 +631,8 @@ int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, si
     HIP_TRY(ctx, hipGetLastError());
     return launch_merkle_batch(ctx, nullptr, n, d_nodes, 1, 0, 0);
 }
-// n_trees equally sized trees in one set of launches: tree y reads d_elems + y*elem_stride and writes
-// d_nodes + y*node_stride_bytes.  The small upper levels of all trees share their launch latency.
+// n_trees equally sized trees in one set of launches.  The small upper levels of all trees share their launch latency.
 int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
                         size_t node_stride_bytes, uint32_t row_cols, size_t row_stride) {
     return launch_merkle_impl(ctx, d_elems, n, d_nodes, n_trees, elem_stride, node_stride_bytes, row_cols, row_stride, nullptr, nullptr);
-}
-static int launch_merkle_impl(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
-                              size_t node_stride_bytes, uint32_t row_cols, size_t row_stride, const TopHook *hook, bool *hook_done,
-                              const LeafSrc *src) {
-    if (!n_trees) return SMI_OK;
-    LeafSrc none;
-    memset(&none, 0, sizeof none);
-    const size_t node_stride = node_stride_bytes / 16;
-    const uint32_t depth = log2_floor(n);
-    uint4 *nodes = (uint4 *)d_nodes;
-    uint32_t lvl = 0;
-    size_t count = n;
-    bool from_elems = d_elems != nullptr;
-    static const uint32_t KMAX = [] {  // levels fused per launch (tuning knob; LDS stash = 8 KB << K)
-        const char *e = getenv("SMI_MERKLE_K");
-        const int k = e ? atoi(e) : 2;
-        return (uint32_t)(k < 1 ? 1 : (k > 3 ? 3 : k));
-    }();
-    // chunk workgroups per launch below which the chunk kernel takes over (one per CU; tuning knob)
-    const size_t TOP_BLOCKS = merkle_top_blocks();
-    if (from_elems && depth == 0 && !row_cols) {
-        for (uint32_t y = 0; y < n_trees; y++) SMI_TRY(launch_leaf_hash(ctx, d_elems + y * elem_stride, 1, d_nodes + y * node_stride_bytes));
-        return SMI_OK;
-    }
-    while (lvl < depth || from_elems) {
-        // Once what is left fits the chip as one wave of chunk workgroups, the per-level latency of
-        // the chunk kernel beats two-level launches: up to SMI_TOP_MAX digests (11 levels) per launch.
-        // Chunks are as small as one workgroup per CU allows (not below 64): the widest levels of a chunk
-        // are throughput on a single CU, so 256 chunks of 256 digests and then their 256 roots finish a
-        // 2^16-leaf tree in 42 us where 32 chunks of 2048 took 65.  Up to 512 digests stay one chunk.
-        // (Both bounds are tuning knobs; tools/sweep_merkle_chunks.sh: flat within 3 % from 8 to 64.)
-        static const size_t SINGLE_MAX = [] { const char *e = getenv("SMI_MERKLE_SINGLE"); return (size_t)(e ? atoi(e) : 512); }();
-        static const size_t MIN_CHUNK = [] { const char *e = getenv("SMI_MERKLE_MINCHUNK"); return (size_t)(e ? atoi(e) : 64); }();
-        size_t chunk = count;
-        if (count > SINGLE_MAX) {
-            chunk = MIN_CHUNK;
-            while (chunk < SMI_TOP_MAX && (count / chunk) * n_trees > TOP_BLOCKS) chunk <<= 1;
-        }
-        const size_t n_chunks = count / chunk;
-        if (chunk <= SMI_TOP_MAX && n_chunks * n_trees <= TOP_BLOCKS && (!from_elems || row_cols || count <= merkle_elems_max())) {
-            const double hashed = (from_elems ? 2.0 * (double)count : (double)count) - (double)n_chunks;
-            // mix_state evaluations: 9 per single-element leaf (one more per extra 32-byte chunk of a row), 10 per node
-            const double leaf_mixes = 8.0 + (row_cols ? (double)((row_cols + 3) / 4) : 1.0);
-            const double mixes = (from_elems ? leaf_mixes * (double)count : 0.0) + 10.0 * ((double)count - (double)n_chunks);
-            ProfScope ps(ctx, "merkle_top_kernel", ((from_elems ? 4.0 * (row_cols ? row_cols : 1) : 32.0) * (double)count + 32.0 * hashed) * n_trees,
-                         mixes * n_trees);
-            const dim3 grid((uint32_t)n_chunks, n_trees);
-            TopHook h{nullptr, nullptr, nullptr};
-            if (hook && n_chunks == 1 && n_trees == 1) {   // this launch ends with the root
-                h = *hook;
-                *hook_done = true;
-            }
-            if (from_elems && src) {
-                if (src->kind != LEAF_FOLD || n_trees != 1 || row_cols) return smi_fail(ctx, SMI_ERR_BAD_ARG, "merkle: the chunk kernel computes folded leaves only");
-                merkle_top_fold_kernel<<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(nodes, n, (uint32_t)chunk, h, *src);
-            } else if (from_elems)
-                merkle_top_kernel<true><<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(d_elems, nodes, n, 0, (uint32_t)chunk, elem_stride, node_stride, row_cols, row_stride, h);
-            else
-                merkle_top_kernel<false><<<grid, SMI_TOP_THREADS, 0, ctx->stream>>>(nullptr, nodes, n, lvl, (uint32_t)chunk, 0, node_stride, 0, 0, h);
-            HIP_TRY(ctx, hipGetLastError());
-            from_elems = false;
-            uint32_t up = 0;
-            while (((size_t)1 << up) < chunk) up++;
-            lvl += up;
-            count = n_chunks;
-            continue;
-        }
-        uint32_t K = depth - lvl < KMAX ? depth - lvl : KMAX;
-        const size_t threads = count >> K;
-        const size_t lds = (size_t)(8u << K) * SMI_HASH_THREADS * sizeof(uint32_t);
-        // algorithmic bytes: inputs read once (4 B elements or 32 B digests), every produced digest written once
-        const double produced = from_elems ? (double)count * 2.0 - (double)(count >> K) : (double)count - (double)(count >> K);
-        const double sub_mixes = (from_elems ? (8.0 + (row_cols ? (double)((row_cols + 3) / 4) : 1.0)) * (double)count : 0.0) +
-                                 10.0 * ((double)count - (double)(count >> K));
-        ProfScope ps(ctx, from_elems ? "merkle_sub_kernel<leaves>" : "merkle_sub_kernel<digests>",
-                     ((from_elems ? 4.0 * (row_cols ? row_cols : 1) : 32.0) * (double)count + 32.0 * produced) * n_trees, sub_mixes * n_trees);
-        const dim3 grid(blocks_for(threads), n_trees);
-        // the hot shapes (element leaves or digests, two levels per lane) have instantiations of their own
-        static const bool generic_only = getenv("SMI_MERKLE_GENERIC") && atoi(getenv("SMI_MERKLE_GENERIC"));
-        if (from_elems && row_cols)
-            merkle_sub_kernel<true, 0, true><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, count, K, elem_stride, node_stride, row_cols, row_stride, none);
-        else if (from_elems && K == 2 && !generic_only && src && src->kind == LEAF_FOLD)   // leaves computed on the fly (LeafSrc)
-            merkle_sub_kernel<true, 2, false, LEAF_FOLD><<<grid, SMI_HASH_THREADS, (size_t)16 * SMI_HASH_THREADS * sizeof(uint32_t), ctx->stream>>>(d_elems, nodes, n, 0, count, K, elem_stride, node_stride, 0, 0, *src);
-        else if (from_elems && K == 2 && !generic_only && src && src->kind == LEAF_COMBINE)
-            merkle_sub_kernel<true, 2, false, LEAF_COMBINE><<<grid, SMI_HASH_THREADS, (size_t)16 * SMI_HASH_THREADS * sizeof(uint32_t), ctx->stream>>>(d_elems, nodes, n, 0, count, K, elem_stride, node_stride, 0, 0, *src);
-        else if (src && from_elems)
-            return smi_fail(ctx, SMI_ERR_BAD_ARG, "merkle: computed leaves need the four-leaves-per-lane kernel");
-        else if (from_elems && K == 2 && !generic_only)   // its stash holds two digests per lane
-            merkle_sub_kernel<true, 2, false><<<grid, SMI_HASH_THREADS, (size_t)16 * SMI_HASH_THREADS * sizeof(uint32_t), ctx->stream>>>(d_elems, nodes, n, 0, count, K, elem_stride, node_stride, 0, 0, none);
-        else if (from_elems)
-            merkle_sub_kernel<true, 0, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(d_elems, nodes, n, 0, count, K, elem_stride, node_stride, 0, 0, none);
-        else if (K == 2 && !generic_only)                 // no stash at all
-            merkle_sub_kernel<false, 2, false><<<grid, SMI_HASH_THREADS, 0, ctx->stream>>>(nullptr, nodes, n, lvl, count, K, 0, node_stride, 0, 0, none);
-        else
-            merkle_sub_kernel<false, 0, false><<<grid, SMI_HASH_THREADS, lds, ctx->stream>>>(nullptr, nodes, n, lvl, count, K, 0, node_stride, 0, 0, none);
-        HIP_TRY(ctx, hipGetLastError());
-        from_elems = false;
-        lvl += K;
-        count >>= K;
-    }
-    return SMI_OK;
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/stark_mi.h"
+#include "fri_plan.h"
 #include "tables.h"
 
 struct ScaleEntry {
@@ -44,11 +45,6 @@ struct smi_ctx {
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     void *pin_out = nullptr;       // pinned landing buffer of a prove's results (proof bytes, challenges, indices, roots)
     size_t pin_out_bytes = 0;
-    // a small device buffer that rides back with the next fri_run's single copy-back (the column roots of
-    // smi_dev_stark_prove): set by the caller, consumed and cleared by fri_run
-    const void *ride_src = nullptr;
-    size_t ride_bytes = 0;
-    void *ride_dst = nullptr;
     std::string err;
     bool prof_on = false;
     char prof_only[56] = {0};   // smi_ctx_profile_only: bracket only launches whose name contains this (empty: all)
@@ -126,6 +122,14 @@ int smi_hip_fail(smi_ctx *ctx, hipError_t e, const char *what);
     } while (0)
 
 int smi_fail(smi_ctx *ctx, int code, const char *msg);
+// a prove's serialized bytes as the C ABI hands them out: malloc'ed, the caller frees
+inline int smi_proof_out(smi_ctx *ctx, const std::vector<uint8_t> &bytes, uint8_t **proof, size_t *proof_len) {
+    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
+    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
+    memcpy(*proof, bytes.data(), bytes.size());
+    *proof_len = bytes.size();
+    return SMI_OK;
+}
 
 // grows (never shrinks) a context-owned staging buffer
 int ctx_tmp(smi_ctx *ctx, int slot, size_t bytes, void **out);
@@ -166,8 +170,7 @@ inline uint32_t h_root(const smi_ctx *c, uint32_t log_n) {  // primitive 2^log_n
 // One launch for the last rounds of Fri::commit (hash.hip, fri_tail_kernel): round k hashes and commits
 // cw (len elements), runs the Fiat-Shamir round of its root and, unless next == nullptr (the last
 // round), folds into next with the round's x^-1 table S.
-#define SMI_FRI_TAIL_MAX_ROUNDS 12
-#define SMI_FRI_TAIL_MAX_LEN 2048   // = SMI_TOP_MAX of hash.hip
+// (SMI_FRI_TAIL_MAX_ROUNDS, SMI_FRI_TAIL_MAX_LEN: fri_plan.h)
 struct FriTailRound {
     const uint32_t *cw;
     uint32_t *next;
@@ -193,8 +196,9 @@ int launch_fri_tail(smi_ctx *ctx, const FriTailArgs &a);
 uint64_t fri_tail_len();   // codewords of at most this many elements finish in the fused tail (SMI_FRI_TAIL, default 512; fri.hip)
 // A caller's Fiat-Shamir transcript as the prover continues it (hash_core.h fs_seed): the sponge state after its whole
 // 32-byte chunks and its trailing bytes, and the count of those trailing bytes.  Computed on the host: the reference's
-// transcript is a host Vec<u8>.  phase == 0 (every transcript of whole roots, the empty one included) runs the fused
-// Fiat-Shamir sites; phase != 0 takes the single-lane phase-aware kernels after each tree and no fused tail.
+// transcript is a host Vec<u8>.  The same 17 words are the transcript's state on the device.  phase == 0 (every transcript
+// of whole roots, the empty one included) runs the fused Fiat-Shamir sites; phase != 0 takes the single-lane phase-aware
+// kernels after each tree and no fused tail.
 struct FsSeed {
     uint32_t s[16];
     uint32_t phase;
@@ -224,15 +228,63 @@ struct LeafSrc {
     uint32_t n_cols;
     const uint32_t *weights_m;   // (weight mod p) in Montgomery form, on the device (fs_weights_kernel)
 };
-// true when a tree of n single-element leaves starts with the thread-per-four-leaves kernel that can take a LeafSrc
-bool merkle_fuses_leaf_source(size_t n);
-// true when a tree of n single-element leaves starts with the chunk kernel, which can take a LEAF_FOLD source (no other
-// kind; no alignment demands: it reads and writes single elements)
-bool merkle_chunks_fold(size_t n);
+// Fri::commit (+ the query phase of Fri::prove with do_query) over a device codeword (fri.hip).
+struct FriRequest {
+    const smi_fri_cfg *cfg;
+    const uint32_t *d_codeword;   // cfg->domain_length elements; with round0_src: the buffer the first tree's launch fills
+    size_t len;
+    bool do_query;
+    bool reset_arena = true;    // false: the caller's own buffers of this prove live in the arena
+    bool retain = false;        // true: the codewords and trees outlive the call (FriResult::run, hipMalloc); false: arena
+    const LeafSrc *round0_src = nullptr;   // LEAF_COMBINE: the initial codeword is computed by the launch that hashes it
+    const FsSeed *seed = nullptr;          // nullptr: a fresh FiatShamir
+    // a few device bytes of the caller's (the column roots of a prove) that ride back with the single copy-back
+    const void *ride_src = nullptr;
+    size_t ride_bytes = 0;
+    void *ride_dst = nullptr;              // host
+    FriRequest(const smi_fri_cfg *c, const uint32_t *cw, size_t n, bool query) : cfg(c), d_codeword(cw), len(n), do_query(query) {}
+};
+struct FriResult {
+    FriLayout lay;                  // rounds, last_n and where things are in `proof`
+    std::vector<uint8_t> proof;     // serialized ProofStream: root r at 33 r + 1, the last codeword's u64s at off_last + 9
+    std::vector<uint64_t> alphas;   // R - 1 unreduced challenges (R entries)
+    std::vector<uint64_t> top;      // top-level indices (do_query)
+    smi_fri_run *run = nullptr;     // retain
+};
+int fri_run(smi_ctx *ctx, const FriRequest &rq, FriResult *res);
+
+// launches (defined in the .hip files; every function one .hip file defines and another calls is declared here, once --
+// the MgSide ones in mgpu_core.h)
+// hash.hip
+int launch_leaf_hash(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_digests);
+int launch_combine(smi_ctx *ctx, const uint8_t *d_in, size_t n_pairs, uint8_t *d_out);
+int launch_hash_bytes(smi_ctx *ctx, const uint8_t *d_msg, size_t len, uint32_t *d_out);
+int launch_hash_bytes_batch(smi_ctx *ctx, const uint8_t *d_msgs, size_t n, size_t len, uint32_t *d_out);
+int launch_verify_paths(smi_ctx *ctx, const uint8_t *d_leaves, const uint64_t *d_idx, const uint8_t *d_paths, size_t k, uint32_t depth,
+                        const uint8_t *d_root, uint8_t *d_ok);
+int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes);
+int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
+                     uint64_t *alpha_out, bool *done);
 int launch_merkle_src_fs(smi_ctx *ctx, const LeafSrc &src, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
                          uint64_t *alpha_out, bool *done);
-
-// launches (defined in the .hip files)
+int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
+int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
+                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
+// fri.hip
+int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, size_t full_len,
+                      const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out);
+// the x^-1 table of the fold out of a codeword of len elements on offset * <omega> (src/ff.rs:182: no division by zero)
+int fri_fold_tables(smi_ctx *ctx, uint32_t offset, uint32_t omega, uint64_t len, ScaleTables *S);
+inline uint32_t fri_inv2_m(const smi_ctx *c) { return (uint32_t)(((uint64_t)h_inv(c, 2) << 32) % c->fs.F.p); }   // 2^-1, Montgomery form
+int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed);   // seed == nullptr: a fresh transcript
+int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase);
+int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out, uint32_t phase);
+int launch_sample_indices(smi_ctx *ctx, const uint64_t *challenge, uint64_t size, uint64_t reduced_size, uint32_t number,
+                          uint64_t *indices, uint64_t *reduced);
+int launch_emit_codeword(smi_ctx *ctx, const uint32_t *cw, uint64_t len, uint8_t *dst);
+// stark.hip
+int launch_fs_weights(smi_ctx *ctx, const uint8_t *const *d_root_ptrs, uint32_t n, uint64_t *weights, uint8_t *roots_out);
+// ntt.hip
 int launch_geom_table(smi_ctx *ctx, const GeomSpec &s, uint32_t *d_out);
 int launch_narrow(smi_ctx *ctx, const uint64_t *d_in, uint32_t *d_out, size_t n, int reduce);
 int launch_widen(smi_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, size_t n);

@@ -20,24 +20,6 @@
 #include "internal.h"
 #include "mgpu_loop.h"
 
-// launchers of the single-GPU engine (hash.hip, fri.hip, stark.hip)
-int launch_merkle(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes);
-int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
-                     uint64_t *alpha_out, bool *done);
-int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
-                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
-int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, size_t count, size_t i0, size_t full_len,
-                      const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out);
-size_t fri_fs_bytes();
-int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed);
-int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase);
-int launch_fs_challenge(smi_ctx *ctx, const void *fs, uint64_t *out, uint32_t phase);
-int launch_sample_indices(smi_ctx *ctx, const uint64_t *challenge, uint64_t size, uint64_t reduced_size, uint32_t number,
-                          uint64_t *indices, uint64_t *reduced);
-int launch_emit_codeword(smi_ctx *ctx, const uint32_t *cw, uint64_t len, uint8_t *dst);
-int launch_fs_weights(smi_ctx *ctx, const uint8_t *const *d_root_ptrs, uint32_t n, uint64_t *weights, uint8_t *roots_out);
-int launch_column_open(smi_ctx *ctx, const MgSide *d_cols, uint32_t W, const uint64_t *d_top, uint32_t t, int rank, uint8_t *d_out);
-
 // ------------------------------------------------------------------------- kernels
 // Fri::query for every (test, layer): each rank writes what it owns (mgpu_core.h)
 __global__ __launch_bounds__(64) void mg_query_kernel(const MgLayer *layers, const uint64_t *top, int rank, uint8_t *proof) {
@@ -112,7 +94,7 @@ struct HipDev : MgDev {
         return launch_merkle_batch(ctx, elems, n, nodes, n_trees, elem_stride, node_stride_bytes);
     }
     int merkle_from_digests(size_t n, uint8_t *nodes) override { return launch_merkle(ctx, nullptr, n, nodes); }
-    size_t fs_bytes() const override { return fri_fs_bytes(); }
+    size_t fs_bytes() const override { return sizeof(FsSeed); }
     int fs_init(void *fs, const uint32_t seed[16], uint32_t phase) override {
         FsSeed s;
         memcpy(s.s, seed, sizeof s.s);
@@ -142,18 +124,14 @@ struct HipDev : MgDev {
         ta.n_rounds = n_rounds;
         ta.fs_words = (uint32_t *)fs;
         ta.F = ctx->fs.F;
-        ta.inv2_m = (uint32_t)(((uint64_t)h_inv(ctx, 2) << 32) % ctx->fs.F.p);
+        ta.inv2_m = fri_inv2_m(ctx);
         for (uint32_t k = 0; k < n_rounds; k++) {
             const MgTailRound &t = rounds[k];
             FriTailRound &tr = ta.r[k];
             tr.cw = t.cw; tr.next = t.next; tr.nodes = t.nodes; tr.proof_slot = t.proof_slot; tr.alpha_out = t.alpha_out;
             tr.len = (uint32_t)t.len;
             if (!t.next) break;
-            if (t.len < 2) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold: codeword length must be a power of two >= 2");
-            if (t.offset == 0 || t.omega == 0) return smi_fail(ctx, SMI_ERR_DIV_BY_ZERO, "no division by zero");   // src/ff.rs:182
-            uint32_t lg = 0;
-            while ((2ull << lg) < t.len) lg++;
-            SMI_TRY(ctx_scale_tables(ctx, h_inv(ctx, (uint32_t)t.offset), h_inv(ctx, (uint32_t)t.omega), lg, &tr.S));
+            SMI_TRY(fri_fold_tables(ctx, (uint32_t)t.offset, (uint32_t)t.omega, t.len, &tr.S));
         }
         return launch_fri_tail(ctx, ta);
     }
@@ -366,14 +344,6 @@ int smi_mgpu_set_min_block(smi_mgpu *m, size_t min_block) {
     return SMI_OK;
 }
 
-static int give_proof(smi_ctx *ctx, const std::vector<uint8_t> &bytes, uint8_t **proof, size_t *proof_len) {
-    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
-    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
-    memcpy(*proof, bytes.data(), bytes.size());
-    *proof_len = bytes.size();
-    return SMI_OK;
-}
-
 int smi_mgpu_fri_commit_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_block,
                            size_t block_len, uint8_t *roots, uint64_t *alphas, uint64_t *last_codeword, size_t *last_len) {
     if (!m || !cfg || !d_block || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
@@ -402,7 +372,7 @@ int smi_mgpu_fri_prove_fs(smi_mgpu *m, const smi_fri_cfg *cfg, const uint8_t *tr
     MgFriOut o;
     SMI_TRY(mg_fri_run(m->dev, *m->coll, m->rank, m->world, *cfg, d_block, block_len, m->min_block, true, o, transcript, transcript_len));
     if (top_indices && !o.top.empty()) memcpy(top_indices, o.top.data(), 8 * o.top.size());
-    return give_proof(m->ctx, o.proof, proof, proof_len);
+    return smi_proof_out(m->ctx, o.proof, proof, proof_len);
 }
 int smi_mgpu_fri_prove(smi_mgpu *m, const smi_fri_cfg *cfg, const uint32_t *d_block, size_t block_len, uint8_t **proof, size_t *proof_len,
                        uint64_t *top_indices) {
@@ -455,5 +425,5 @@ int smi_mgpu_stark_prove(smi_mgpu *m, const smi_stark_cfg *cfg, const uint32_t *
     SMI_TRY(mg_stark_prove(m->dev, *m->coll, m->rank, m->world, *cfg, d_trace_cols, m->min_block, o));
     if (column_roots) memcpy(column_roots, o.column_roots.data(), o.column_roots.size());
     if (top_indices && !o.fri.top.empty()) memcpy(top_indices, o.fri.top.data(), 8 * o.fri.top.size());
-    return give_proof(m->ctx, o.fri.proof, proof, proof_len);
+    return smi_proof_out(m->ctx, o.fri.proof, proof, proof_len);
 }

@@ -114,3 +114,7 @@ SMI_HD void mg_column_open_write(const MgSide *cols, uint32_t W, uint32_t c, uin
                                  uint8_t *out, uint32_t lane, uint32_t n_lanes) {
     mg_column_open_write_n(cols, W, c, top_index, s, t, rank, out, lane, n_lanes, 2, 0);
 }
+
+// column_open_kernel on the context's stream (stark.hip; mgpu.hip and air.hip call it too)
+struct smi_ctx;
+int launch_column_open(smi_ctx *ctx, const MgSide *d_cols, uint32_t W, const uint64_t *d_top, uint32_t t, int rank, uint8_t *d_out);

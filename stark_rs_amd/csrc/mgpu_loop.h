@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/stark_mi.h"
+#include "fri_plan.h"
 #include "hash_core.h"
 #include "mgpu_core.h"
 #include "ntt_host.h"
@@ -136,12 +137,6 @@ struct MgFriOut {
 };
 
 namespace mg {
-inline uint32_t ilog2(uint64_t n) {
-    uint32_t l = 0;
-    while ((n >> l) > 1) l++;
-    return l;
-}
-inline bool pow2(uint64_t n) { return n && !(n & (n - 1)); }
 #define MG_TRY(call)                 \
     do {                             \
         int rc__ = (call);           \
@@ -157,36 +152,30 @@ inline int mg_fri_run(MgDev &d, MgColl &coll, int rank, int G, const smi_fri_cfg
     using namespace mg;
     if (!transcript && transcript_len) return d.fail(SMI_ERR_BAD_ARG, "transcript == NULL with a length");
     // asserts of Fri::new / Fri::prove (src/fri.rs:37-45, 256-260)
-    if (!pow2(cfg.domain_length)) return d.fail(SMI_ERR_DOMAIN_NOT_POW2, nullptr);
-    if (!pow2(cfg.expansion_factor)) return d.fail(SMI_ERR_EXPANSION_NOT_POW2, nullptr);
+    if (!is_pow2(cfg.domain_length)) return d.fail(SMI_ERR_DOMAIN_NOT_POW2, nullptr);
+    if (!is_pow2(cfg.expansion_factor)) return d.fail(SMI_ERR_EXPANSION_NOT_POW2, nullptr);
     if (cfg.expansion_factor < 4) return d.fail(SMI_ERR_EXPANSION_TOO_SMALL, nullptr);
-    if (G < 1 || !pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
+    if (G < 1 || !is_pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
     const uint64_t N = cfg.domain_length;
     if ((uint64_t)block_len * (uint64_t)G != N) return d.fail(SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     const uint32_t p = d.prime();
     if (cfg.omega >= p || cfg.offset >= p) return d.fail(SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
-    uint64_t R = 0;
-    for (uint64_t len = N; len > cfg.expansion_factor && 4 * cfg.num_colinearity_tests < len; len /= 2) R++;   // src/fri.rs:93-103
+    const FriLayout lay = fri_layout(cfg, do_query);   // the single-GPU proof layout
+    const uint64_t R = lay.R;
     if (R == 0) return d.fail(SMI_ERR_NO_ROUNDS, "num_rounds() == 0: the reference's verify rejects such a proof");
-    const uint64_t t = cfg.num_colinearity_tests, last_n = N >> (R - 1);
+    const uint64_t t = cfg.num_colinearity_tests, last_n = lay.last_n;
     if (do_query) {   // asserts of src/fri.rs:183-192
         if (t > 2 * last_n) return d.fail(SMI_ERR_SAMPLE_ENTROPY, nullptr);
         if (t > last_n) return d.fail(SMI_ERR_SAMPLE_TOO_MANY, nullptr);
     }
     if (min_block < 2) min_block = 2;
 
-    // proof layout (src/fri.rs:129,151,229-243; tags src/stream.rs:39-60) -- the single-GPU one
-    const size_t off_last = 33 * R, off_layers = off_last + 9 + 8 * last_n;
+    const size_t off_last = lay.off_last, proof_len = lay.proof_len;
     std::vector<MgLayer> layers(R - 1);
-    size_t off = off_layers;
     for (uint64_t i = 0; i + 1 < R; i++) {
-        const uint32_t dep = ilog2(N >> i);
-        layers[i].off_triples = off;
-        off += 33 * t;
-        layers[i].off_paths = off;
-        off += t * (2 * (9 + 32ull * dep) + (9 + 32ull * (dep - 1)));
+        layers[i].off_triples = lay.off_triples[i];
+        layers[i].off_paths = lay.off_paths[i];
     }
-    const size_t proof_len = do_query ? off : off_layers;
 
     uint8_t *fs = (uint8_t *)d.alloc(d.fs_bytes());
     uint64_t *d_alphas = (uint64_t *)d.alloc(8 * (R + 1));
@@ -217,7 +206,7 @@ inline int mg_fri_run(MgDev &d, MgColl &coll, int rank, int G, const smi_fri_cfg
             cur_local = length;
             sharded = false;
         }
-        if (!sharded && phase == 0 && length <= d.tail_max_len() && R - r <= d.tail_max_rounds()) {   // (the tail's rounds run at phase 0)
+        if (!sharded && fri_tail_starts(phase, length, d.tail_max_len(), R - r, d.tail_max_rounds())) {   // (the tail's rounds run at phase 0)
             // replicated and small: every remaining round in one call (SURVEY 8e "gather to one GPU and run the fused
             // tail"; here every rank runs it, so nothing has to be broadcast afterwards)
             std::vector<MgTailRound> tr((size_t)(R - r));
@@ -408,7 +397,7 @@ inline int mg_lde_blocks(MgDev &d, MgColl &coll, int rank, int G, const uint32_t
 inline int mg_ntt(MgDev &d, MgColl &coll, int rank, int G, uint32_t *strip, uint32_t *out, uint32_t log_n, int inverse, uint64_t offset,
                   bool natural = false) {
     using namespace mg;
-    if (G < 1 || !pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
+    if (G < 1 || !is_pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
     const uint32_t log_g = ilog2((uint64_t)G);
     if (!ntt_shard_ok(log_n, log_g)) return d.fail(SMI_ERR_BAD_ARG, "mgpu: transform too small to shard over this many ranks");
     const NttPlan pl = ntt_make_plan(log_n, 1);
@@ -463,7 +452,7 @@ inline int mg_stark_prove(MgDev &d, MgColl &coll, int rank, int G, const smi_sta
     if (!W || W > 64) return d.fail(SMI_ERR_BAD_ARG, "stark_prove: 1..64 columns");
     if (cfg.row_leaves) return d.fail(SMI_ERR_BAD_ARG, "mgpu: the row-leaf variant is single-GPU only");
     if (cfg.log_blowup < 2) return d.fail(SMI_ERR_EXPANSION_TOO_SMALL, nullptr);    // Fri::new, src/fri.rs:45
-    if (G < 1 || !pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
+    if (G < 1 || !is_pow2((uint64_t)G) || rank < 0 || rank >= G) return d.fail(SMI_ERR_BAD_ARG, "mgpu: world size must be a power of two");
     const uint64_t N = 1ull << logN, blk = N / G;
     if (!blk) return d.fail(SMI_ERR_BAD_ARG, "mgpu: more ranks than leaves");
     MG_TRY(d.reset());

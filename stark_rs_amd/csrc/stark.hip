@@ -19,14 +19,6 @@
 #include "internal.h"
 #include "mgpu_core.h"
 
-int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
-                        size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);
-int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
-int fri_run(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint32_t *d_codeword, size_t len, bool do_query, bool reset_arena,
-            smi_fri_run **run_out, std::vector<uint8_t> *proof_host, uint64_t *top_host, uint8_t *roots_host,
-            uint64_t *alphas_host, uint64_t *last_host, size_t *last_len, const LeafSrc *round0_src,
-            const FsSeed *seed = nullptr);
-
 // weights[c] = FiatShamir::challenge after absorbing roots[0..c] (unreduced u64)
 // weights_m (optional): the same weights reduced mod p in Montgomery form, what the fused combination multiplies by
 // the roots are named by a pointer table, or (root_ptrs == nullptr) sit root_stride bytes apart from root0 on
@@ -166,12 +158,19 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
         fs_weights_kernel<<<1, 64, 0, ctx->stream>>>(nullptr, W, d_weights, (uint32_t *)d_roots, d_weights_m, ctx->fs.F, rootp[0], tree_stride);
     }
     HIP_TRY(ctx, hipGetLastError());
-    // Sum_c weight_c * col_c: by a kernel of its own, or -- when the first FRI tree starts with the four-leaves-per-lane
-    // kernel -- by that kernel as it hashes (LeafSrc, internal.h): one launch and one pass over the codeword less
+    smi_fri_cfg fc;
+    fc.omega = h_root(ctx, log_N);
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = N;
+    fc.expansion_factor = 1ull << cfg->log_blowup;
+    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    // Sum_c weight_c * col_c: by a kernel of its own, or -- where the FRI round plan lets the first tree's launch compute
+    // its leaves (fri_plan.h, FRI_R0_COMBINE) -- by that launch as it hashes (LeafSrc, internal.h): one launch and one pass
+    // over the codeword less.  Four elements per access: the arena's buffers are 16-byte aligned, N is a multiple of 4.
     LeafSrc csrc;
     memset(&csrc, 0, sizeof csrc);
-    const bool fuse_combine = merkle_fuses_leaf_source(N) && W <= SMI_LEAF_COMBINE_MAX && N > fri_tail_len() &&
-                              (((uintptr_t)d_lde | (uintptr_t)d_cw) & 15u) == 0;   // four elements per access, N is a multiple of 4
+    const bool fuse_combine = W <= SMI_LEAF_COMBINE_MAX && (((uintptr_t)d_lde | (uintptr_t)d_cw) & 15u) == 0 &&
+                              fri_round_plan(N, fri_layout(fc, true).R, 0, fri_tail_len(), FRI_R0_COMBINE, merkle_knobs_env()).ok;
     if (fuse_combine) {
         csrc.kind = LEAF_COMBINE;
         csrc.cw_out = d_cw;
@@ -184,27 +183,19 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
         SMI_TRY(smi_dev_combine_columns(ctx, d_lde, W, N, N, d_weights, d_cw));
     }
     mark(3);
-    smi_fri_cfg fc;
-    fc.omega = h_root(ctx, log_N);
-    fc.offset = cfg->lde_offset;
-    fc.domain_length = N;
-    fc.expansion_factor = 1ull << cfg->log_blowup;
-    fc.num_colinearity_tests = cfg->num_colinearity_tests;
-    std::vector<uint8_t> bytes;
-    // the column openings need the top-level indices whether or not the caller wants them back
-    std::vector<uint64_t> top_tmp(top_indices ? 0 : (size_t)cfg->num_colinearity_tests);
-    if (!top_indices && !top_tmp.empty()) top_indices = top_tmp.data();
+    FriRequest rq(&fc, d_cw, N, true);
+    rq.reset_arena = false;
+    rq.round0_src = fuse_combine ? &csrc : nullptr;
     if (column_roots) {   // the roots come back with fri_run's one copy-back instead of a copy and a sync of their own
-        ctx->ride_src = d_roots;
-        ctx->ride_bytes = 32 * (size_t)T;
-        ctx->ride_dst = column_roots;
+        rq.ride_src = d_roots;
+        rq.ride_bytes = 32 * (size_t)T;
+        rq.ride_dst = column_roots;
     }
-    const int fri_rc = fri_run(ctx, &fc, d_cw, N, true, false, nullptr, &bytes, top_indices, nullptr, nullptr, nullptr, nullptr,
-                               fuse_combine ? &csrc : nullptr);
-    ctx->ride_src = nullptr;   // not consumed if fri_run failed early
-    ctx->ride_bytes = 0;
-    ctx->ride_dst = nullptr;
-    SMI_TRY(fri_rc);
+    FriResult res;
+    SMI_TRY(fri_run(ctx, rq, &res));
+    std::vector<uint8_t> &bytes = res.proof;
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    else top_indices = res.top.data();   // the column openings need the top-level indices either way
     mark(4);
     if (cfg->open_columns && !cfg->row_leaves && cfg->num_colinearity_tests) {
         // the top-level indices are on the host now (fri_run synchronised): one more small launch
@@ -236,9 +227,5 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
             stage_ms[i] = ms;
         }
     }
-    *proof = (uint8_t *)malloc(bytes.size() ? bytes.size() : 1);
-    if (!*proof) return smi_fail(ctx, SMI_ERR_OOM, "malloc proof");
-    memcpy(*proof, bytes.data(), bytes.size());
-    *proof_len = bytes.size();
-    return SMI_OK;
+    return smi_proof_out(ctx, bytes, proof, proof_len);
 }

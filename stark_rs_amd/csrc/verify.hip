@@ -23,12 +23,6 @@ namespace {
 using proofp::Obj;
 using proofp::get_u64;
 using proofp::parse;
-bool pow2(uint64_t n) { return n && !(n & (n - 1)); }
-uint32_t ilog2(uint64_t n) {
-    uint32_t l = 0;
-    while ((n >> l) > 1) l++;
-    return l;
-}
 uint64_t mulm(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((unsigned __int128)a * b % p); }
 // FiniteField::sub (src/ff.rs:154-160): `p + l - r` in u128, then `% p`; for an unreduced r > p + l a release build wraps
 // mod 2^128 before the reduction (a debug build panics) -- the oracle restates the release behaviour and so does this
@@ -95,7 +89,7 @@ int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, con
     std::vector<uint64_t> last(n_last);
     for (size_t i = 0; i < n_last; i++) last[i] = get_u64(lo->p + 8 * i);
     if (n_last == 0) return smi_fail(ctx, SMI_ERR_EMPTY_LEAVES, nullptr);          // MerkleTree::new panics, :353
-    if (!pow2(n_last)) return smi_fail(ctx, SMI_ERR_LEAVES_NOT_POW2, nullptr);
+    if (!is_pow2(n_last)) return smi_fail(ctx, SMI_ERR_LEAVES_NOT_POW2, nullptr);
     std::vector<uint8_t> digests;
     SMI_TRY(leaf_digests(ctx, last.data(), n_last, digests));
     uint8_t last_root[32];

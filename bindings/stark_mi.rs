@@ -113,12 +113,17 @@ pub struct smi_air {
     pub boundary_col: *const u32,
     pub boundary_row: *const u64,
     pub boundary_value: *const u64,
+    pub n_periodic: u32,
+    pub reserved0: u32,
+    pub periodic_log_period: *const u32,
+    pub periodic_value: *const u64,
 }
 pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
 pub const SMI_AIR_MAX_TERMS: u32 = 1024;
 pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
 pub const SMI_AIR_MAX_EXP: u32 = 255;
 pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
+pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -617,14 +622,27 @@ pub struct Air {
     boundary_col: Vec<u32>,
     boundary_row: Vec<u64>,
     boundary_value: Vec<u64>,
+    periodic_log_period: Vec<u32>,
+    periodic_value: Vec<u64>,
 }
 
-/// One factor of a monomial: column, row shift (0 = this row, 1 = next row), exponent.
+/// One factor of a monomial: column, row shift (0 = this row, 1 = next row), exponent.  `AirFactor::periodic` names a
+/// periodic column in place of a trace column.
 #[derive(Clone, Copy, Debug)]
 pub struct AirFactor {
     pub col: u32,
     pub next: bool,
     pub exp: u32,
+}
+
+/// Set in `AirFactor::col` when the factor is a periodic column (the rest is the index `Air::periodic` returned).
+pub const AIR_PERIODIC: u32 = 1 << 31;
+
+impl AirFactor {
+    /// Periodic column `j` (as returned by `Air::periodic`) at this row or the next.
+    pub fn periodic(j: u32, next: bool, exp: u32) -> AirFactor {
+        AirFactor { col: AIR_PERIODIC | j, next, exp }
+    }
 }
 
 impl Air {
@@ -638,12 +656,23 @@ impl Air {
         self.boundary_value.push(value);
         self
     }
+    /// A periodic column: row r holds `values[r mod values.len()]` (canonical; the length a power of two that divides
+    /// the trace length).  Part of the statement: not committed, not in the proof.  Returns its index for
+    /// `AirFactor::periodic`.
+    pub fn periodic(&mut self, values: &[u64]) -> u32 {
+        assert!(values.len().is_power_of_two(), "the period must be a power of two");
+        self.periodic_log_period.push(values.len().trailing_zeros());
+        self.periodic_value.extend_from_slice(values);
+        (self.periodic_log_period.len() - 1) as u32
+    }
     /// One transition constraint: a sum of `(coefficient, factors)` terms that vanishes on every pair of consecutive rows.
     pub fn transition(&mut self, terms: &[(u64, Vec<AirFactor>)]) -> &mut Air {
         for (coeff, factors) in terms {
             self.term_coeff.push(*coeff);
             for f in factors {
-                self.factor_var.push(f.col + if f.next { self.n_cols } else { 0 });
+                // a periodic factor keeps its tag until with_raw, where the number of periodic columns is final
+                self.factor_var.push(if f.col & AIR_PERIODIC != 0 { f.col | if f.next { AIR_PERIODIC >> 1 } else { 0 } }
+                                     else { f.col + if f.next { self.n_cols } else { 0 } });
                 self.factor_exp.push(f.exp);
             }
             self.term_first_factor.push(self.factor_var.len() as u32);
@@ -652,6 +681,12 @@ impl Air {
         self
     }
     fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        // var = 2W + j (this row) or 2W + Q + j (next row) for periodic column j
+        let q = self.periodic_log_period.len() as u32;
+        let factor_var: Vec<u32> = self.factor_var.iter().map(|&v| {
+            if v & AIR_PERIODIC == 0 { v }
+            else { 2 * self.n_cols + (v & !(AIR_PERIODIC | AIR_PERIODIC >> 1)) + if v & (AIR_PERIODIC >> 1) != 0 { q } else { 0 } }
+        }).collect();
         let raw = smi_air {
             n_constraints: (self.constraint_first_term.len() - 1) as u32,
             n_terms: self.term_coeff.len() as u32,
@@ -660,11 +695,15 @@ impl Air {
             constraint_first_term: self.constraint_first_term.as_ptr(),
             term_coeff: self.term_coeff.as_ptr(),
             term_first_factor: self.term_first_factor.as_ptr(),
-            factor_var: self.factor_var.as_ptr(),
+            factor_var: factor_var.as_ptr(),
             factor_exp: self.factor_exp.as_ptr(),
             boundary_col: self.boundary_col.as_ptr(),
             boundary_row: self.boundary_row.as_ptr(),
             boundary_value: self.boundary_value.as_ptr(),
+            n_periodic: q,
+            reserved0: 0,
+            periodic_log_period: self.periodic_log_period.as_ptr(),
+            periodic_value: self.periodic_value.as_ptr(),
         };
         f(&raw as *const smi_air as *const c_void)
     }

@@ -381,32 +381,48 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
  * two consecutive rows that vanish on every row pair (r, r+1), r = 0 .. n-2, no wrap-around).
  *
  * Flat, pointer-plus-count, host memory.  Transition constraint k is
- *   C_k(X_0 .. X_{2W-1}) = sum_{terms of k} coeff * prod_{factors} X_var^exp,   var = col + n_cols * shift,
- * shift 0 = this row, 1 = next row.  Its degree d_k is the largest sum of exponents over its terms,
+ *   C_k(X_0 .. X_{2W+2Q-1}) = sum_{terms of k} coeff * prod_{factors} X_var^exp,
+ * with four kinds of variable (W = n_cols, Q = n_periodic):
+ *   var = c           (c < W)   trace column c at this row;        var = W + c        trace column c at the next row;
+ *   var = 2W + j      (j < Q)   periodic column j at this row;     var = 2W + Q + j   periodic column j at the next row.
+ * Its degree d_k is the largest sum of exponents over its terms, periodic factors counted like trace factors,
  * d = max(1, max_k d_k), D = the smallest power of two >= max(1, d-1), E = 2^log_blowup / D: the expansion factor
  * FRI runs at (the quotients have degree < D * n).
+ *
+ * Periodic columns (round constants, selectors, public columns).  Column j has a period P_j = 2^l_j, 0 <= l_j <= log_n,
+ * and P_j canonical values v_j[0 .. P_j); row r holds v_j[r mod P_j].  P_j = 1 is a constant, P_j = n a fully public
+ * column.  They are part of the statement, like the coefficients and the boundary values: prover and verifier both
+ * hold them, and they are not committed, not opened, carry no weight and do not enter the transcript -- the proof
+ * bytes of an AIR with periodic columns have the layout of one without.  As a polynomial, column j is pi_j, the
+ * unique one of degree < n with pi_j(tau w^r) = v_j[r mod P_j]; X_{2W+j} = pi_j(x) and X_{2W+Q+j} = pi_j(w x).
+ * pi_j(x) = q_j((x / tau)^(n / P_j)) with q_j the interpolant of v_j on the P_j-th roots of unity, so on the evaluation
+ * coset pi_j(x_i) depends on i mod (P_j * B) only: the library extends v_j to P_j * B values with smi_dev_lde
+ * (log_n = l_j, trace_offset 1, lde_offset (h / tau)^(n / P_j)) and the kernels read that table modulo its length.
+ * On the trace itself (smi_dev_air_check) the operands of row pair (r, r+1) are v_j[r mod P_j] and v_j[(r+1) mod P_j].
  *
  * The composition codeword.  p the modulus, n = 2^log_n, B = 2^log_blowup, N = nB, w = omega_n, tau = trace_offset,
  * h = lde_offset, x_i = h * omega_N^i, lde[c][i] = f_c(x_i) (smi_dev_lde, natural order; the next row is the index
  * shift f_c(w x_i) = lde[c][(i + B) mod N]).
  *   column c with boundary points {(r_j, v_j)}: I_c the interpolant through (tau w^r_j, v_j), Z_c(x) = prod_j (x - tau w^r_j),
  *       term_c(x_i) = (lde[c][i] - I_c(x_i)) / Z_c(x_i);   without boundary points term_c(x_i) = lde[c][i];
- *   tq_k(x_i) = C_k(lde[.][i], lde[.][(i+B) mod N]) * (x_i - tau w^(n-1)) / (x_i^n - tau^n);
+ *   tq_k(x_i) = C_k(lde[.][i], lde[.][(i+B) mod N], pi_.(x_i), pi_.(w x_i)) * (x_i - tau w^(n-1)) / (x_i^n - tau^n);
  *   cw[i] = sum_{c<W} (weight_c mod p) * term_c(x_i) + sum_{k<K} (weight_{W+k} mod p) * tq_k(x_i)   (mod p).
  * With K = 0 and no boundary point this is smi_dev_combine_columns.
  *
  * Limits (SMI_ERR_BAD_ARG, the text of smi_air_last_error / smi_last_error names the one that was broken):
  *   n_cols <= 64; n_constraints <= SMI_AIR_MAX_CONSTRAINTS; n_terms <= SMI_AIR_MAX_TERMS; at most
- *   SMI_AIR_MAX_TERM_FACTORS factors in a term; 1 <= factor_exp <= SMI_AIR_MAX_EXP; factor_var < 2 * n_cols; at most
- *   SMI_AIR_MAX_BOUNDARY_PER_COL boundary points in a column, a (col, row) pair at most once, row < n;
+ *   SMI_AIR_MAX_TERM_FACTORS factors in a term; 1 <= factor_exp <= SMI_AIR_MAX_EXP; factor_var < 2 * n_cols +
+ *   2 * n_periodic; at most SMI_AIR_MAX_BOUNDARY_PER_COL boundary points in a column, a (col, row) pair at most once,
+ *   row < n; n_periodic <= SMI_AIR_MAX_PERIODIC; periodic_log_period[j] <= log_n;
  *   offsets in 1 .. p-1.  Refused as well (SMI_ERR_BAD_ARG): lde_offset^N == 1, and (lde_offset / trace_offset)^N == 1 --
  *   the evaluation coset then meets the trace domain and a zerofier vanishes on it (the second is the exact condition
- *   when trace_offset != 1; the first is kept for every trace_offset).  A coefficient or boundary value >= p gives
+ *   when trace_offset != 1; the first is kept for every trace_offset).  A coefficient, boundary or periodic value >= p gives
  *   SMI_ERR_NON_CANONICAL; E < 4 gives SMI_ERR_EXPANSION_TOO_SMALL (Fri::new's assert, src/fri.rs:45: the quotients
  *   would not fit under the degree bound).
  *
- * Out of scope: row shifts other than 0 and 1; periodic or public-input columns; zero-knowledge randomisers;
- * degree-adjusted terms (alpha + beta * x^shift); binding a digest of the AIR into the transcript; an extension
+ * Out of scope: row shifts other than 0 and 1; zero-knowledge randomisers; degree-adjusted terms
+ * (alpha + beta * x^shift); binding a digest of the AIR (coefficients, boundary values, periodic values) into the
+ * transcript; keeping the periodic tables on the device between calls; an extension
  * field (with a 30-bit modulus the soundness of any proof from this library is bounded by the field, the reference's
  * choice); a multi-GPU twin.
  *
@@ -417,16 +433,21 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
 #define SMI_AIR_MAX_TERM_FACTORS 8
 #define SMI_AIR_MAX_EXP 255
 #define SMI_AIR_MAX_BOUNDARY_PER_COL 16
+#define SMI_AIR_MAX_PERIODIC 16
 typedef struct smi_air {
     uint32_t n_constraints, n_terms, n_factors, n_boundary;
     const uint32_t *constraint_first_term;  /* n_constraints + 1, ascending, [0] = 0, last = n_terms          */
     const uint64_t *term_coeff;             /* n_terms, canonical (< p)                                        */
     const uint32_t *term_first_factor;      /* n_terms + 1; a term with no factor is a constant                */
-    const uint32_t *factor_var;             /* n_factors; var = col + n_cols * shift, shift 0 = this row, 1 = next row */
+    const uint32_t *factor_var;             /* n_factors; < 2 * n_cols + 2 * n_periodic, the four kinds above  */
     const uint32_t *factor_exp;             /* n_factors; >= 1                                                 */
     const uint32_t *boundary_col;           /* n_boundary                                                      */
     const uint64_t *boundary_row;           /* n_boundary; < n, a (col, row) pair at most once                 */
     const uint64_t *boundary_value;         /* n_boundary; canonical                                           */
+    uint32_t n_periodic;                    /* Q <= SMI_AIR_MAX_PERIODIC                                       */
+    uint32_t reserved0;                     /* explicit padding, ignored                                       */
+    const uint32_t *periodic_log_period;    /* n_periodic; l_j <= log_n                                        */
+    const uint64_t *periodic_value;         /* the columns' values back to back, 2^l_j each, canonical         */
 } smi_air;
 /* Host only, no context (callable without a GPU, like smi_fri_num_rounds): validates air against cfg (log_n,
  * log_blowup, n_cols and the two offsets are read) for the modulus p and returns d and E.  Every AIR entry point

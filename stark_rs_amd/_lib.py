@@ -50,7 +50,8 @@ class Air(C.Structure):
     """smi_air (include/stark_mi.h): flat host tables; mirror.Air.flatten fills one and keeps the arrays alive"""
     _fields_ = [("n_constraints", C.c_uint32), ("n_terms", C.c_uint32), ("n_factors", C.c_uint32), ("n_boundary", C.c_uint32),
                 ("constraint_first_term", u32p), ("term_coeff", u64p), ("term_first_factor", u32p), ("factor_var", u32p),
-                ("factor_exp", u32p), ("boundary_col", u32p), ("boundary_row", u64p), ("boundary_value", u64p)]
+                ("factor_exp", u32p), ("boundary_col", u32p), ("boundary_row", u64p), ("boundary_value", u64p),
+                ("n_periodic", C.c_uint32), ("reserved0", C.c_uint32), ("periodic_log_period", u32p), ("periodic_value", u64p)]
 
 
 def build(force=False):

@@ -12,6 +12,10 @@
 // conflict).  The AIR tables are indexed with wave-uniform values only, so they are scalar loads; x_i is one table
 // entry times one per-tile power, then a multiplication per further point; 1 / (x^n - tau^n) is a B-entry table and
 // the 1 / Z_c(x_i) share one Fermat inversion per AIR_INV_BATCH values.
+//
+// Periodic columns are Q more tile rows, staged from tables of L_j = P_j * B values that are read modulo their length
+// (air_core.h).  A table is at most a column and usually a few KB, so it comes from L2 and the floor above stands.
+// air_periodic_tables builds the tables on the stream with one batched smi_dev_lde per distinct period.
 #include <string>
 #include <vector>
 
@@ -39,6 +43,12 @@ __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, 
         for (uint32_t c = 0; c < A.W; c++)
             for (uint32_t e = tid * 4; e < pitch; e += threads * 4)   // pitch, base and N are multiples of 4: no access straddles the wrap
                 *(uint4 *)(tile + c * pitch + e) = *(const uint4 *)(cols + c * stride + ((base + e) & (A.N - 1)));
+        for (uint32_t j = 0; j < A.Q; j++) {   // L_j is a multiple of 4 as well: a short table wraps any number of times inside a tile
+            const uint32_t *__restrict__ tb = A.ptab + A.pofs[j];
+            const uint32_t mask = (1u << A.plog[j]) - 1u;
+            for (uint32_t e = tid * 4; e < pitch; e += threads * 4)
+                *(uint4 *)(tile + (A.W + j) * pitch + e) = *(const uint4 *)(tb + ((uint32_t)(base + e) & mask));
+        }
         __syncthreads();   // tile (and, the first time, the weights) visible
         air_tile_thread<P>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out);
         xbase_m = mont_mul(xbase_m, xstride_m, F);   // wave-uniform
@@ -65,7 +75,9 @@ __global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const ui
     }
     if (i + 1 < n)
         for (uint32_t k = 0; k < A.K; k++) {
-            const uint32_t v = air_constraint(A, F, k, [&](uint32_t var) { return var < A.W ? trace[var * n + i] : trace[(var - A.W) * n + i + 1]; });
+            const uint32_t v = air_constraint(A, F, k, [&](uint32_t var) {   // log_B = 0: periodic operands v_j[i mod P_j], v_j[(i + 1) mod P_j]
+                return air_mem_operand(A, var, i, [&](uint32_t c) { return trace[c * n + i]; }, [&](uint32_t c) { return trace[c * n + i + 1]; });
+            });
             if (v) {
                 atomicMin(first, (1ull << 63) | ((unsigned long long)k << 32) | i);
                 break;   // a higher k of the same row cannot come first
@@ -78,6 +90,50 @@ __global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const ui
 __global__ __launch_bounds__(64) void air_open_kernel(const MgSide *cols, uint32_t W, const uint64_t *top, uint32_t t, uint32_t R, uint64_t B,
                                                        uint8_t *out) {
     mg_column_open_write_n(cols, W, blockIdx.y, top[blockIdx.x], blockIdx.x, t, 0, out, threadIdx.x, 64, R, B);
+}
+
+// out[q * 2Q + j] = pi_j(x_i), out[q * 2Q + Q + j] = pi_j(w x_i) for i = idx[q]: what the verifier needs of the tables
+__global__ __launch_bounds__(64) void air_periodic_gather_kernel(AirDev A, const uint64_t *__restrict__ idx, uint32_t count, uint32_t *__restrict__ out) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count) return;
+    for (uint32_t v = 0; v < 2 * A.Q; v++) out[q * 2 * A.Q + v] = air_periodic_operand(A, v < A.Q ? v : v - A.Q, v >= A.Q, idx[q]);
+}
+
+// The periodic tables of H on the stream: the grouped values go to d_vals (H.per.vals.size() words), every group is one
+// batched extension into d_tab (H.per.table_words words, 16-byte aligned).  H.per must outlive the copy.
+int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint32_t *d_vals, uint32_t *d_tab) {
+    const AirPeriodic &P = H.per;
+    H.dev.ptab = d_tab;
+    if (P.groups.empty()) return SMI_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(d_vals, P.vals.data(), P.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    for (const AirPeriodGroup &g : P.groups)
+        SMI_TRY(smi_dev_lde(ctx, d_vals + g.in_off, g.count, g.log_period, cfg->log_blowup, 1, g.lde_offset, d_tab + g.out_off));
+    return SMI_OK;
+}
+
+int air_periodic_at(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, const std::vector<uint64_t> &idx, std::vector<uint32_t> *out) {
+    const uint32_t Q = H.dev.Q;
+    out->assign(idx.size() * 2 * Q, 0);
+    if (!Q || idx.empty()) return SMI_OK;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4), b_blob = up16(H.blob.size() * 4), b_idx = up16(idx.size() * 8);
+    void *base = nullptr;
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + b_blob + b_idx + out->size() * 4, &base));
+    uint8_t *d = (uint8_t *)base;
+    uint32_t *d_tab = (uint32_t *)d, *d_vals = (uint32_t *)(d + b_tab), *d_blob = (uint32_t *)(d + b_tab + b_vals);
+    uint64_t *d_idx = (uint64_t *)(d + b_tab + b_vals + b_blob);
+    uint32_t *d_out = (uint32_t *)(d + b_tab + b_vals + b_blob + b_idx);
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_vals, d_tab));
+    HIP_TRY(ctx, hipMemcpyAsync(d_blob, H.blob.data(), H.blob.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    air_bind(H, d_blob);
+    air_periodic_gather_kernel<<<(uint32_t)((idx.size() + 63) / 64), 64, 0, ctx->stream>>>(H.dev, d_idx, (uint32_t)idx.size(), d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out->data(), d_out, out->size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    air_bind(H, H.blob.data());
+    H.dev.ptab = nullptr;
+    return SMI_OK;
 }
 
 namespace {
@@ -95,7 +151,8 @@ int air_host(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost
     return SMI_OK;
 }
 
-// the blob to d_blob (room for H.blob.size() words), the launch of the codeword kernel
+// the blob to d_blob (room for H.blob.size() words), the launch of the codeword kernel; the periodic tables are in place
+// (air_periodic_tables)
 int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights,
                        uint32_t *d_out) {
     HIP_TRY(ctx, hipMemcpyAsync(d_blob, H.blob.data(), H.blob.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -103,7 +160,7 @@ int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_
     const AirDev &A = H.dev;
     const Fp F = ctx->fs.F;
     const uint64_t B = 1ull << A.log_B;
-    AirTile tl = air_tile(A.W, B, A.N);
+    AirTile tl = air_tile(A.W + A.Q, B, A.N);
     if (B < 4 || (stride & 3) || (((uintptr_t)d_lde) & 15u)) tl.T = 0;   // 16-byte loads need aligned columns
     ProfScope ps(ctx, "air_compose_kernel", 4.0 * (A.W + 1.0) * (double)A.N);
     if (!tl.T) {
@@ -112,7 +169,7 @@ int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_
         air_direct_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out);
     } else {
         const uint64_t tiles = A.N / tl.T;
-        const size_t lds = (size_t)AIR_MAX_WEIGHTS * 4 + (size_t)A.W * (tl.T + B) * 4;
+        const size_t lds = (size_t)AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + B) * 4;
         const uint64_t cap = (uint64_t)ctx->num_cus * 8;
         const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
         if (tl.P == 4) air_compose_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
@@ -137,9 +194,12 @@ int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     AirHost H;
     SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr));
     if (stride < H.dev.N) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose: stride < N");
-    void *d_blob = nullptr;
-    SMI_TRY(ctx_tmp(ctx, 3, H.blob.size() * 4, &d_blob));
-    return air_launch_compose(ctx, H, (uint32_t *)d_blob, d_lde, stride, d_weights, d_out);
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
+    void *base = nullptr;   // tables | grouped values | blob
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
+    return air_launch_compose(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out);
 }
 
 int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t log_n, const uint32_t *d_trace_cols, int *ok,
@@ -158,19 +218,22 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
     AirHost H;
     air_build(ctx->fs.F, 1, &cfg, air, &H, true);
     const uint32_t nb = air->n_boundary;
-    const size_t words = H.blob.size(), total = words + 3 * (size_t)nb + 2;
-    std::vector<uint32_t> up(H.blob);
+    const size_t words = H.blob.size(), n_per = H.per.vals.size(), total = words + 3 * (size_t)nb + n_per + 2;
+    std::vector<uint32_t> up(H.blob);   // blob | boundary triples | periodic values (the tables of the trace itself)
+    up.reserve(total);
     for (uint32_t j = 0; j < nb; j++) {
         up.push_back(air->boundary_col[j]);
         up.push_back((uint32_t)air->boundary_row[j]);
         up.push_back((uint32_t)air->boundary_value[j]);
     }
+    up.insert(up.end(), H.per.vals.begin(), H.per.vals.end());
     void *d_blob = nullptr;
     SMI_TRY(ctx_tmp(ctx, 3, total * 4 + 16, &d_blob));
     unsigned long long *d_first = (unsigned long long *)((uint8_t *)d_blob + ((total * 4 + 7) & ~(size_t)7));
     HIP_TRY(ctx, hipMemcpyAsync(d_blob, up.data(), up.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_first, 0xff, 8, ctx->stream));
     air_bind(H, (const uint32_t *)d_blob);
+    H.dev.ptab = (const uint32_t *)d_blob + words + 3 * (size_t)nb;
     const uint64_t n = 1ull << log_n, work = n > nb ? n : nb;
     air_check_kernel<<<(uint32_t)((work + 255) / 256), 256, 0, ctx->stream>>>(H.dev, ctx->fs.F, d_trace_cols, n, nb, (const uint32_t *)d_blob + words,
                                                                              d_first);
@@ -223,7 +286,13 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * (size_t)(W + K));
     uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
     uint8_t *tree_base = (uint8_t *)arena_alloc(ctx, tree_stride * W);
-    if (!d_lde || !d_cw || !d_weights || !d_blob || !tree_base) return smi_fail(ctx, SMI_ERR_OOM, "air_prove: device memory");
+    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
+    if (H.dev.Q) {
+        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
+        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
+    }
+    if (!d_lde || !d_cw || !d_weights || !d_blob || !tree_base || (H.dev.Q && (!d_ptab || !d_pvals)))
+        return smi_fail(ctx, SMI_ERR_OOM, "air_prove: device memory");
     mark(0);
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, cfg->log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
     mark(1);
@@ -233,6 +302,7 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     // are computed on the host, where fri_run's seed is computed anyway (FsSeed, internal.h).
     std::vector<uint8_t> roots(32 * (size_t)W), tr;
     HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, W, hipMemcpyDeviceToHost, ctx->stream));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // part of the compose stage, queued before the host waits for the roots
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> weights(W + K);
     auto challenge = [&]() {

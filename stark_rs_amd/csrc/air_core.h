@@ -4,6 +4,12 @@
 //   cw[i] = sum_c w_c * term_c(x_i) + sum_k w_{W+k} * C_k(row i, row i+B) * (x_i - tau*w^(n-1)) / (x_i^n - tau^n)
 // (include/stark_mi.h, "AIR").  The reference has no counterpart (its Trace has no consumer).
 //
+// Periodic columns.  Column j (period P_j) is a table of L_j = P_j * B values tbl_j[i] = pi_j(x_i), i < L_j, that is read
+// modulo its length: pi_j(x_i) = tbl_j[i mod L_j], pi_j(w x_i) = tbl_j[(i + B) mod L_j] (stark_mi.h has the identity).
+// The tables lie back to back in one buffer (AirDev::ptab), longest period first, so that every table starts at a
+// multiple of its own length; air_periodic_plan lays them out and names the transforms that fill them.  On the trace
+// itself (the checker) B = 1 and the tables are the values themselves.
+//
 // Number forms.  Column values are plain residues, as smi_dev_lde leaves them.  x_i, the boundary roots, the inverse
 // tables and the weights are in Montgomery form (suffix _m), so mont_mul(plain, mont) stays plain.  A term's
 // coefficient is stored as coeff * R^e (e = the term's total exponent): after its e products with plain operands the
@@ -30,7 +36,8 @@ struct AirDev {   // pointers into one blob of u32 (device memory for the kernel
     const uint32_t *cft;       // K + 1: first term of constraint k
     const uint32_t *tcoef;     // n_terms: coeff * R^(total exponent) mod p
     const uint32_t *tff;       // n_terms + 1: first factor of term t
-    const uint32_t *fac;       // n_factors: var | exp << 16
+    const uint32_t *fac;       // n_factors: operand | exp << 16; the operands are numbered by tile row, R = W + Q rows:
+                               // row (trace column c: c, periodic column j: W + j) at this row, R + row at the next row
     const uint32_t *free_col;  // W - n_bcols: the columns without a boundary point, ascending
     const uint32_t *bcol;      // n_bcols: the columns with boundary points, ascending
     const uint32_t *bfirst;    // n_bcols + 1: first point of boundary column j
@@ -40,10 +47,29 @@ struct AirDev {   // pointers into one blob of u32 (device memory for the kernel
     const uint32_t *lane_pow_m;  // AIR_BLOCK entries: omega_N^t, Montgomery form
     uint32_t last_m;           // tau * w^(n-1), Montgomery form
     uint32_t h_m, omega_m;     // lde_offset and omega_N, Montgomery form
+    uint32_t Q;                // periodic columns
+    const uint32_t *plog;      // Q: log2 of the length L_j of table j
+    const uint32_t *pofs;      // Q: first element of table j in ptab, a multiple of L_j
+    const uint32_t *ptab;      // the tables, plain residues; not part of the blob
 };
 
+// periodic column j at the point with index i (next: one row further), from memory: table j read modulo its length
+SMI_HD uint32_t air_periodic_operand(const AirDev &A, uint32_t j, bool next, uint64_t i) {
+    const uint64_t at = next ? i + (1ull << A.log_B) : i;
+    return A.ptab[A.pofs[j] + (uint32_t)(at & ((1ull << A.plog[j]) - 1))];
+}
+// operand `var` of a point without a tile: cur(c) / nxt(c) the trace column c at this row / the next, i the point's index
+template <class Cur, class Nxt>
+SMI_HD uint32_t air_mem_operand(const AirDev &A, uint32_t var, uint64_t i, Cur cur, Nxt nxt) {
+    const uint32_t R = A.W + A.Q;
+    const bool next = var >= R;
+    const uint32_t c = next ? var - R : var;
+    if (c >= A.W) return air_periodic_operand(A, c - A.W, next, i);
+    return next ? nxt(c) : cur(c);
+}
+
 // ------------------------------------------------------------------------------------------------ evaluator
-// C_k at one point; fetch(var) returns the plain operand X_var (var < W: this row, else the next row)
+// C_k at one point; fetch(var) returns the plain operand of AirDev::fac's numbering
 template <class Fetch>
 SMI_HD uint32_t air_constraint(const AirDev &A, const Fp &F, uint32_t k, Fetch fetch) {
     uint32_t ck = 0;
@@ -141,11 +167,12 @@ SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m
 }
 
 // The tile of T points a workgroup stages per column: T points and a halo of B, wrapping at N.  Tile element e of
-// column c sits at tile[c * (T + B) + e] and comes from column index (base + e) mod N.
+// column c sits at tile[c * (T + B) + e] and comes from column index (base + e) mod N.  Periodic column j is tile row
+// W + j, staged the same way from table index (base + e) mod L_j: air_tile is asked for W + Q rows.
 struct AirTile {
     uint32_t T, threads, P;   // points per tile, threads per workgroup, points per thread (T = threads * P)
 };
-inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N) {
+inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N) {   // W: tile rows
     AirTile t{0, 0, 0};
     for (uint32_t T = 1024; T >= 64; T >>= 1) {
         if (T > N || (uint64_t)W * (T + B) * 4 + AIR_MAX_WEIGHTS * 4 > AIR_LDS_BYTES) continue;
@@ -183,10 +210,18 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
         return fail(SMI_ERR_BAD_ARG, "air: more than SMI_AIR_MAX_BOUNDARY_PER_COL (" + std::to_string(SMI_AIR_MAX_BOUNDARY_PER_COL) + ") boundary points per column");
     if ((uint64_t)air->n_factors > (uint64_t)SMI_AIR_MAX_TERM_FACTORS * air->n_terms)
         return fail(SMI_ERR_BAD_ARG, "air: more than SMI_AIR_MAX_TERM_FACTORS (" + std::to_string(SMI_AIR_MAX_TERM_FACTORS) + ") factors in a term");
-    const uint32_t K = air->n_constraints, nt = air->n_terms, nf = air->n_factors, nb = air->n_boundary;
+    if (air->n_periodic > SMI_AIR_MAX_PERIODIC)
+        return fail(SMI_ERR_BAD_ARG, "air: more than SMI_AIR_MAX_PERIODIC (" + std::to_string(SMI_AIR_MAX_PERIODIC) + ") periodic columns");
+    const uint32_t K = air->n_constraints, nt = air->n_terms, nf = air->n_factors, nb = air->n_boundary, Q = air->n_periodic;
     if ((!air->constraint_first_term) || (!air->term_first_factor) || (nt && !air->term_coeff) || (nf && (!air->factor_var || !air->factor_exp)) ||
-        (nb && (!air->boundary_col || !air->boundary_row || !air->boundary_value)))
+        (nb && (!air->boundary_col || !air->boundary_row || !air->boundary_value)) || (Q && (!air->periodic_log_period || !air->periodic_value)))
         return fail(SMI_ERR_BAD_ARG, "air: null table");
+    for (uint64_t j = 0, at = 0; j < Q; j++) {
+        if (air->periodic_log_period[j] > cfg->log_n) return fail(SMI_ERR_BAD_ARG, "air: periodic_log_period must be <= log_n (a period divides the trace length)");
+        for (uint64_t i = 0, P = 1ull << air->periodic_log_period[j]; i < P; i++)
+            if (air->periodic_value[at + i] >= p) return fail(SMI_ERR_NON_CANONICAL, "air: periodic value >= p");
+        at += 1ull << air->periodic_log_period[j];
+    }
     if (air->constraint_first_term[0] != 0 || air->constraint_first_term[K] != nt) return fail(SMI_ERR_BAD_ARG, "air: constraint_first_term must run from 0 to n_terms");
     for (uint32_t k = 0; k < K; k++)
         if (air->constraint_first_term[k] > air->constraint_first_term[k + 1]) return fail(SMI_ERR_BAD_ARG, "air: constraint_first_term must ascend");
@@ -200,7 +235,8 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
         if (air->term_coeff[t] >= p) return fail(SMI_ERR_NON_CANONICAL, "air: term coefficient >= p");
         uint64_t deg = 0;
         for (uint32_t f = f0; f < f1; f++) {
-            if (air->factor_var[f] >= 2 * W) return fail(SMI_ERR_BAD_ARG, "air: factor_var must be < 2 * n_cols (row shifts 0 and 1 only)");
+            if (air->factor_var[f] >= 2 * W + 2 * Q)
+                return fail(SMI_ERR_BAD_ARG, "air: factor_var must be < 2 * n_cols + 2 * n_periodic (row shifts 0 and 1 only)");
             if (air->factor_exp[f] < 1 || air->factor_exp[f] > SMI_AIR_MAX_EXP)
                 return fail(SMI_ERR_BAD_ARG, "air: factor_exp must be in 1 .. SMI_AIR_MAX_EXP (" + std::to_string(SMI_AIR_MAX_EXP) + ")");
             deg += air->factor_exp[f];
@@ -239,15 +275,59 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
 }
 
 // The tables of a validated AIR as one blob of u32.  omega_N: the primitive N-th root the LDE uses.
+// The periodic tables of one AIR: the columns grouped by period, longest first (a group is one batched extension of
+// `count` columns from 2^log_period values to 2^log_len), the values in that order as u32, and every column's place.
+struct AirPeriodGroup {
+    uint32_t log_period, log_len, count;
+    size_t in_off, out_off;   // first value / first table element of the group
+    uint32_t lde_offset;      // (h / tau)^(n / P): the coset the group's extension evaluates on
+};
+struct AirPeriodic {
+    std::vector<AirPeriodGroup> groups;
+    std::vector<uint32_t> vals;             // the values, grouped; the tables themselves when log_B = 0 (the checker)
+    std::vector<uint32_t> log_len, ofs;     // per column j as the AIR numbers them
+    size_t table_words = 0;
+};
+// tables_only: no extension (B = 1, the offsets unused)
+inline void air_periodic_plan(uint32_t p, const smi_stark_cfg *cfg, const smi_air *air, bool tables_only, AirPeriodic *out) {
+    const uint32_t Q = air->n_periodic, lb = tables_only ? 0 : cfg->log_blowup;
+    out->groups.clear();
+    out->vals.clear();
+    out->log_len.assign(Q, 0);
+    out->ofs.assign(Q, 0);
+    out->table_words = 0;
+    if (!Q) return;
+    std::vector<size_t> first(Q);
+    size_t at = 0;
+    for (uint32_t j = 0; j < Q; j++) first[j] = at, at += (size_t)1 << air->periodic_log_period[j];
+    out->vals.reserve(at);
+    const uint32_t ratio = tables_only ? 1 : host_mulmod((uint32_t)cfg->lde_offset, host_powmod((uint32_t)cfg->trace_offset, p - 2, p), p);
+    for (int l = (int)cfg->log_n; l >= 0; l--) {
+        AirPeriodGroup g{(uint32_t)l, (uint32_t)l + lb, 0, out->vals.size(), out->table_words, 0};
+        for (uint32_t j = 0; j < Q; j++) {
+            if (air->periodic_log_period[j] != (uint32_t)l) continue;
+            out->log_len[j] = g.log_len;
+            out->ofs[j] = (uint32_t)(g.out_off + ((size_t)g.count << g.log_len));
+            for (size_t i = 0; i < (size_t)1 << l; i++) out->vals.push_back((uint32_t)air->periodic_value[first[j] + i]);
+            g.count++;
+        }
+        if (!g.count) continue;
+        g.lde_offset = host_powmod(ratio, 1ull << (cfg->log_n - l), p);
+        out->table_words += (size_t)g.count << g.log_len;
+        out->groups.push_back(g);
+    }
+}
+
 struct AirHost {
     std::vector<uint32_t> blob;
-    size_t off[11];
-    AirDev dev;   // pointers unset until air_bind
+    size_t off[13];
+    AirDev dev;   // pointers unset until air_bind; ptab is the caller's to set
+    AirPeriodic per;
 };
 inline void air_bind(AirHost &H, const uint32_t *base) {
-    const uint32_t **slot[11] = {&H.dev.cft,    &H.dev.tcoef,   &H.dev.tff,    &H.dev.fac,   &H.dev.free_col,  &H.dev.bcol,
-                                 &H.dev.bfirst, &H.dev.broot_m, &H.dev.bicoef, &H.dev.izt_m, &H.dev.lane_pow_m};
-    for (int i = 0; i < 11; i++) *slot[i] = base + H.off[i];
+    const uint32_t **slot[13] = {&H.dev.cft,    &H.dev.tcoef,   &H.dev.tff,    &H.dev.fac,   &H.dev.free_col,   &H.dev.bcol, &H.dev.bfirst,
+                                 &H.dev.broot_m, &H.dev.bicoef, &H.dev.izt_m,  &H.dev.lane_pow_m, &H.dev.plog, &H.dev.pofs};
+    for (int i = 0; i < 13; i++) *slot[i] = base + H.off[i];
 }
 // tables_only: the constraint tables alone (smi_dev_air_check); every other pointer then names the blob's end.
 inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, bool tables_only = false) {
@@ -258,6 +338,15 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
     std::vector<uint32_t> &b = H->blob;
     b.clear();
     auto mark = [&](int i) { H->off[i] = b.size(); };
+    auto periodic = [&]() {   // sections 11 and 12
+        air_periodic_plan(p, cfg, air, tables_only, &H->per);
+        mark(11);
+        for (uint32_t v : H->per.log_len) b.push_back(v);
+        mark(12);
+        for (uint32_t v : H->per.ofs) b.push_back(v);
+        H->dev.Q = air->n_periodic;
+        H->dev.ptab = nullptr;
+    };
     mark(0);
     for (uint32_t k = 0; k <= K; k++) b.push_back(air->constraint_first_term[k]);
     mark(1);
@@ -269,7 +358,11 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
     mark(2);
     for (uint32_t t = 0; t <= nt; t++) b.push_back(air->term_first_factor[t]);
     mark(3);
-    for (uint32_t f = 0; f < nf; f++) b.push_back(air->factor_var[f] | (air->factor_exp[f] << 16));   // exponent <= SMI_AIR_MAX_EXP < 2^16
+    for (uint32_t f = 0; f < nf; f++) {   // smi_air's variables to tile rows; with Q = 0 the two numberings are one
+        const uint32_t Q = air->n_periodic, v = air->factor_var[f];
+        const uint32_t row = v < 2 * W ? (v < W ? v : v + Q) : (v < 2 * W + Q ? v - W : v);   // < 2 (W + Q) <= 160
+        b.push_back(row | (air->factor_exp[f] << 16));   // exponent <= SMI_AIR_MAX_EXP < 2^16
+    }
     if (tables_only) {
         for (int i = 4; i < 11; i++) mark(i);
         H->dev.W = W;
@@ -278,6 +371,7 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
         H->dev.log_B = 0;
         H->dev.N = n;
         H->dev.last_m = H->dev.h_m = H->dev.omega_m = 0;
+        periodic();
         b.push_back(0);
         air_bind(*H, b.data());
         return;
@@ -333,6 +427,7 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
         b.push_back(air_to_m(lp, p));
         lp = host_mulmod(lp, omega_N, p);
     }
+    periodic();
     while (b.size() & 3) b.push_back(0);
     AirDev &d = H->dev;
     d.W = W;
@@ -347,11 +442,11 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
 }
 
 // One workgroup's tile, one "thread" at a time: what air_compose_kernel runs between its barriers, over `tile`
-// (W x (T + B) staged elements).  Shared so that the emulator executes the kernel's own indexing.
+// ((W + Q) x (T + B) staged elements).  Shared so that the emulator executes the kernel's own indexing.
 template <int P>
 SMI_HD void air_tile_thread(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *tile, uint32_t T, uint32_t threads,
                             uint64_t base, uint32_t xbase_m, uint32_t step_m, uint32_t tid, uint32_t *out) {
-    const uint32_t B = 1u << A.log_B, pitch = T + B;
+    const uint32_t B = 1u << A.log_B, pitch = T + B, R = A.W + A.Q;
     uint32_t x_m[P], ib[P], res[P];
     uint32_t x = mont_mul(xbase_m, A.lane_pow_m[tid], F);
     for (int q = 0; q < P; q++) {
@@ -361,9 +456,9 @@ SMI_HD void air_tile_thread(const AirDev &A, const Fp &F, const uint32_t *w_m, c
     }
     air_compose_points<P>(
         A, F, w_m, x_m, ib,
-        [&](int q, uint32_t var) {
-            const uint32_t c = var < A.W ? var : var - A.W;
-            return tile[c * pitch + tid + q * threads + (var < A.W ? 0 : B)];
+        [&](int q, uint32_t var) {   // rows 0 .. W-1 the trace columns, W .. R-1 the periodic ones; the next row is B further
+            const uint32_t c = var < R ? var : var - R;
+            return tile[c * pitch + tid + q * threads + (var < R ? 0 : B)];
         },
         res);
     for (int q = 0; q < P; q++) out[base + tid + (uint64_t)q * threads] = res[q];
@@ -377,6 +472,10 @@ SMI_HD void air_direct_point(const AirDev &A, const Fp &F, const uint32_t *w_m, 
     const uint32_t x_m = mont_mul(A.h_m, mont_pow(A.omega_m, i, F), F), ib = (uint32_t)(i & (B - 1));
     uint32_t res;
     air_compose_points<1>(
-        A, F, w_m, &x_m, &ib, [&](int, uint32_t var) { return var < A.W ? cols[var * stride + i] : cols[(var - A.W) * stride + nx]; }, &res);
+        A, F, w_m, &x_m, &ib,
+        [&](int, uint32_t var) {
+            return air_mem_operand(A, var, i, [&](uint32_t c) { return cols[c * stride + i]; }, [&](uint32_t c) { return cols[c * stride + nx]; });
+        },
+        &res);
     out[i] = res;
 }

@@ -5,6 +5,8 @@
 // time; where the kernel takes air_direct_kernel the emulator runs air_direct_point.  emu_air_check evaluates the
 // boundary points and the constraints with the kernels' air_constraint and keeps the first violation in the order the
 // device's atomic minimum does.  Same arguments and statuses as the C ABI, with (p, g) in place of a context.
+// The periodic tables are laid out by air_periodic_plan (air_core.h) and filled with the emulator's own transforms
+// (emu_ntt: an inverse transform per group, then a forward one on the group's coset), not with anything of the GPU path.
 // There is no emu_air_prove / emu_air_verify: the emulator has no single-device Fri::prove loop to continue a
 // transcript with (emu_mgpu.cpp emulates the multi-GPU round loop only), and the verifier is host code already.
 #include <string.h>
@@ -15,15 +17,32 @@
 #include "air_core.h"
 #include "tables.h"
 
+extern "C" int emu_ntt(uint64_t p, uint64_t g, const uint32_t *in, uint32_t *out, uint32_t L, uint32_t n_in, uint32_t batch, uint64_t in_stride,
+                       uint64_t out_stride, int inverse, uint64_t offset, uint64_t post_scale);
+
 namespace {
+// tbl_j[i] = pi_j(x_i), i < L_j, for every periodic column, at the places AirHost::per names
+bool emu_periodic_tables(uint64_t p, uint64_t g, const AirPeriodic &P, std::vector<uint32_t> *tab) {
+    tab->assign(P.table_words, 0);
+    for (const AirPeriodGroup &gr : P.groups) {
+        const uint64_t per = 1ull << gr.log_period, len = 1ull << gr.log_len;
+        std::vector<uint32_t> coef(gr.count * per);
+        if (emu_ntt(p, g, P.vals.data() + gr.in_off, coef.data(), gr.log_period, (uint32_t)per, gr.count, per, per, 1, 1, gr.lde_offset)) return false;
+        if (emu_ntt(p, g, coef.data(), tab->data() + gr.out_off, gr.log_len, (uint32_t)per, gr.count, per, len, 0, 1, 1)) return false;
+    }
+    return true;
+}
+
 template <int P>
 void emu_tiles(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, const AirTile &tl, uint32_t *out) {
     const uint32_t B = 1u << A.log_B, pitch = tl.T + B;
-    std::vector<uint32_t> tile((size_t)A.W * pitch);
+    std::vector<uint32_t> tile((size_t)(A.W + A.Q) * pitch);
     const uint32_t step_m = mont_pow(A.omega_m, tl.threads, F);
     for (uint64_t base = 0; base < A.N; base += tl.T) {
         for (uint32_t c = 0; c < A.W; c++)
             for (uint32_t e = 0; e < pitch; e++) tile[(size_t)c * pitch + e] = cols[c * stride + ((base + e) & (A.N - 1))];
+        for (uint32_t j = 0; j < A.Q; j++)
+            for (uint32_t e = 0; e < pitch; e++) tile[(size_t)(A.W + j) * pitch + e] = A.ptab[A.pofs[j] + ((uint32_t)(base + e) & ((1u << A.plog[j]) - 1u))];
         const uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, base, F), F);
         for (uint32_t tid = 0; tid < tl.threads; tid++) air_tile_thread<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out);
     }
@@ -41,11 +60,14 @@ extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg,
     if (log_N > fs.K) return SMI_ERR_UNSUPPORTED_PRIME;
     AirHost H;
     air_build(fs.F, host_powmod(fs.wmax[0], 1ull << (fs.K - log_N), fs.F.p), cfg, air, &H);
+    std::vector<uint32_t> tab;
+    if (!emu_periodic_tables(p, g, H.per, &tab)) return SMI_ERR_BAD_ARG;
+    H.dev.ptab = tab.data();
     const AirDev &A = H.dev;
     if (stride < A.N) return SMI_ERR_BAD_ARG;
     std::vector<uint32_t> w_m(A.W + A.K);
     for (uint32_t i = 0; i < A.W + A.K; i++) w_m[i] = to_mont_u64(weights[i], fs.F);
-    AirTile tl = air_tile(A.W, 1ull << A.log_B, A.N);
+    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N);
     if (force_direct || (stride & 3)) tl.T = 0;
     if (!tl.T)
         for (uint64_t i = 0; i < A.N; i++) air_direct_point(A, fs.F, w_m.data(), lde, stride, i, out);
@@ -67,6 +89,7 @@ extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, ui
     const Fp F = fp_make((uint32_t)p);
     AirHost H;
     air_build(F, 1, &cfg, air, &H, true);
+    H.dev.ptab = H.per.vals.data();   // on the trace itself the tables are the values
     const uint64_t n = 1ull << log_n;
     uint64_t first = ~0ull;
     auto take = [&](uint64_t key) { if (key < first) first = key; };
@@ -75,7 +98,9 @@ extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, ui
             take((i << 32) | air->boundary_row[i]);
         if (i + 1 < n)
             for (uint32_t k = 0; k < H.dev.K; k++)
-                if (air_constraint(H.dev, F, k, [&](uint32_t var) { return var < n_cols ? trace[var * n + i] : trace[(var - n_cols) * n + i + 1]; })) {
+                if (air_constraint(H.dev, F, k, [&](uint32_t var) {
+                        return air_mem_operand(H.dev, var, i, [&](uint32_t c) { return trace[c * n + i]; }, [&](uint32_t c) { return trace[c * n + i + 1]; });
+                    })) {
                     take((1ull << 63) | ((uint64_t)k << 32) | i);
                     break;
                 }

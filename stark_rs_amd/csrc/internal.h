@@ -300,3 +300,7 @@ int check_flag(smi_ctx *ctx);  // syncs; SMI_ERR_NON_CANONICAL if a narrow kerne
 // caller's (pageable) u64 buffers <-> device u32 residues; synchronous on return
 int host_to_dev_u32(smi_ctx *ctx, const uint64_t *host, size_t n, uint32_t *d_out, int reduce);
 int dev_u32_to_host(smi_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *host);
+// air.hip: the periodic operands of an AIR (air_core.h) at the points idx -- out[q * 2Q + j] = pi_j(x_idx[q]),
+// out[q * 2Q + Q + j] = pi_j(w x_idx[q]) -- from tables built on the device as the prover builds them; synchronises
+struct AirHost;
+int air_periodic_at(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, const std::vector<uint64_t> &idx, std::vector<uint32_t> *out);

@@ -413,6 +413,16 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
     AirHost H;
     air_build(ctx->fs.F, (uint32_t)fc.omega, cfg, air, &H);
     const Fp F = ctx->fs.F;
+    // the periodic operands at the 2 t positions and B further, from the statement alone: the tables the prover's
+    // builder makes of it, gathered on the device (per[(2 s + k) * 2Q + ..]: Q at this row, Q at the next)
+    const uint32_t Q = air->n_periodic;
+    std::vector<uint32_t> per;
+    if (Q) {
+        std::vector<uint64_t> at(2 * t);
+        for (uint64_t s = 0; s < t; s++)
+            for (size_t k = 0; k < 2; k++) at[2 * s + k] = pos[R * s + k];
+        SMI_TRY(air_periodic_at(ctx, cfg, H, at, &per));
+    }
     std::vector<uint32_t> w_m(W + K);
     for (uint32_t i = 0; i < W + K; i++) w_m[i] = to_mont_u64(weights[i], F);
     for (uint64_t s = 0; s < t; s++)
@@ -425,7 +435,14 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
             const uint32_t x_m = air_to_m((uint32_t)mulm(cfg->lde_offset, powm(fc.omega, i, p), p), (uint32_t)p), ib = (uint32_t)(i & (B - 1));
             uint32_t got = 0;
             air_compose_points<1>(
-                H.dev, F, w_m.data(), &x_m, &ib, [&](int, uint32_t var) { return (uint32_t)(var < W ? cur[var] : nxt[var - W]); }, &got);
+                H.dev, F, w_m.data(), &x_m, &ib,
+                [&](int, uint32_t var) {   // AirDev::fac's numbering: W + Q operands at this row, then at the next
+                    const bool next = var >= W + Q;
+                    const uint32_t c = next ? var - (W + Q) : var;
+                    if (c >= W) return per[(2 * s + k) * 2 * Q + (next ? Q : 0) + (c - W)];
+                    return (uint32_t)(next ? nxt[c] : cur[c]);
+                },
+                &got);
             if (got != ab[2 * s + k] % p) return reject(ctx, accept, "air openings: the composition of the opened rows is not the codeword value");
         }
     *accept = 1;

@@ -711,16 +711,52 @@ class Air:
         air.transition({("next", 1): 1, ("cur", 0): -1, ("cur", 1): -1})
 
     A monomial is () (a constant), one factor, or a tuple of factors; a factor is ("cur" | "next", column) or
-    ("cur" | "next", column, exponent).  Coefficients are integers, reduced mod p when flattened."""
+    ("cur" | "next", column, exponent).  Coefficients are integers, reduced mod p when flattened.
+
+    Periodic columns (round constants, selectors, public columns) are part of the statement, not of the trace:
+
+        k = air.periodic([3, 1, 4, 1])                          # row r holds values[r mod 4]; the period is a power of two
+        air.transition({("next", 0): 1, ("cur", 0): -1, ("per", k): -1})          # a' = a + k
+        air.transition({("next", 1): 1, (("per_next", k), ("cur", 1, 2)): -1})    # b' = k' b^2
+
+    ("per", j[, exponent]) is periodic column j at this row, ("per_next", j[, exponent]) at the next row.  Factors are
+    kept symbolic until they are used, so periodic columns may be declared before or after the constraints."""
 
     def __init__(self, n_cols):
         self.n_cols = n_cols
-        self.constraints = []   # [[(coeff, [(var, exp), ...]), ...], ...]
+        self._symbolic = []     # [[(coeff, [(kind, index, exp), ...]), ...], ...]
         self.boundaries = []    # [(col, row, value), ...]
+        self.periodics = []     # [[value, ...], ...]: a power-of-two number of integers each
+
+    @property
+    def constraints(self):
+        """[[(coeff, [(var, exp), ...]), ...], ...] with the variable numbering of smi_air: col, W + col, 2W + j, 2W + Q + j"""
+        W, Q = self.n_cols, len(self.periodics)
+        base = {"cur": 0, "next": W, "per": 2 * W, "per_next": 2 * W + Q}
+        return [[(cf, [(base[kind] + idx, e) for kind, idx, e in factors]) for cf, factors in con] for con in self._symbolic]
 
     def _factor(self, f):
-        shift = {"cur": 0, "next": 1}[f[0]]
-        return f[1] + self.n_cols * shift, (f[2] if len(f) > 2 else 1)
+        if f[0] not in ("cur", "next", "per", "per_next"):
+            raise ValueError(f"unknown factor kind {f[0]!r}")
+        return f[0], int(f[1]), (f[2] if len(f) > 2 else 1)
+
+    def periodic(self, values):
+        """a periodic column: row r holds values[r mod len(values)]; -> its index j for ("per", j) / ("per_next", j)"""
+        values = [int(v) for v in values]
+        if not values or len(values) & (len(values) - 1):
+            raise ValueError("the period must be a power of two")
+        self.periodics.append(values)
+        return len(self.periodics) - 1
+
+    def with_periodic_as_trace(self):
+        """-> the AIR over n_cols + Q trace columns that states the same transitions with the periodic columns read as
+        trace columns n_cols .. n_cols + Q - 1 (what one had to write before periodic columns, and what they are as
+        polynomials).  The boundary points carry over; the extra columns get none."""
+        out = Air(self.n_cols + len(self.periodics))
+        kind = {"cur": ("cur", 0), "next": ("next", 0), "per": ("cur", self.n_cols), "per_next": ("next", self.n_cols)}
+        out._symbolic = [[(cf, [(kind[k][0], kind[k][1] + i, e) for k, i, e in factors]) for cf, factors in con] for con in self._symbolic]
+        out.boundaries = list(self.boundaries)
+        return out
 
     def transition(self, poly):
         terms = []
@@ -732,7 +768,7 @@ class Air:
             else:
                 factors = [self._factor(f) for f in mono]
             terms.append((int(coeff), factors))
-        self.constraints.append(terms)
+        self._symbolic.append(terms)
         return self
 
     def boundary(self, col, row, value):
@@ -758,17 +794,45 @@ class Air:
         arrs = [np.array(cft, dtype=np.uint32), np.array(coeff, dtype=np.uint64), np.array(tff, dtype=np.uint32),
                 np.array(var, dtype=np.uint32), np.array(exp, dtype=np.uint32),
                 np.array([b[0] for b in self.boundaries], dtype=np.uint32), np.array([b[1] for b in self.boundaries], dtype=np.uint64),
-                np.array([b[2] for b in self.boundaries], dtype=np.uint64)]
+                np.array([b[2] for b in self.boundaries], dtype=np.uint64),
+                np.array([len(v).bit_length() - 1 for v in self.periodics], dtype=np.uint32),
+                np.array([x % p for v in self.periodics for x in v], dtype=np.uint64)]
         ptr = lambda a, t: a.ctypes.data_as(t)
         out = _lib.Air(len(self.constraints), len(coeff), len(var), len(self.boundaries), ptr(arrs[0], _lib.u32p), ptr(arrs[1], _lib.u64p),
                        ptr(arrs[2], _lib.u32p), ptr(arrs[3], _lib.u32p), ptr(arrs[4], _lib.u32p), ptr(arrs[5], _lib.u32p),
-                       ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p))
+                       ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p), len(self.periodics), 0, ptr(arrs[8], _lib.u32p), ptr(arrs[9], _lib.u64p))
         out._keep = arrs
         return out
 
-    def constraint_value(self, k, p, cur, nxt):
-        """C_k on one row pair"""
-        vals = [int(v) for v in cur] + [int(v) for v in nxt]
+    def periodic_row(self, p, r):
+        """the periodic columns' values in trace row r"""
+        return [v[r % len(v)] % p for v in self.periodics]
+
+    def periodic_at(self, p, log_n, trace_offset, omega_n, x):
+        """pi_j(x) for every periodic column, from the definition: pi_j(x) = q_j((x / tau)^(n / P_j)) with q_j the Lagrange
+        interpolant of the P_j values on the powers of omega_n^(n / P_j) (P_j inversions per column and point: for
+        small periods or small n)"""
+        inv = lambda v: pow(v, p - 2, p)
+        n, out = 1 << log_n, []
+        for v in self.periodics:
+            P = len(v)
+            y = pow(x * inv(trace_offset) % p, n // P, p)
+            w = pow(omega_n, n // P, p)
+            # q(y) = (y^P - 1) / P * sum_r v_r w^r / (y - w^r); y is never a P-th root of unity off the trace domain
+            zp, acc, wr = (pow(y, P, p) - 1) % p, 0, 1
+            if zp == 0:
+                r = next(r for r in range(P) if pow(w, r, p) == y)
+                out.append(v[r] % p)
+                continue
+            for r in range(P):
+                acc += v[r] % p * wr % p * inv((y - wr) % p)
+                wr = wr * w % p
+            out.append(acc % p * zp % p * inv(P % p) % p)
+        return out
+
+    def constraint_value(self, k, p, cur, nxt, per_cur=(), per_nxt=()):
+        """C_k on one row pair; per_cur / per_nxt: the periodic columns' values at this row and the next"""
+        vals = [int(v) for v in cur] + [int(v) for v in nxt] + [int(v) for v in per_cur] + [int(v) for v in per_nxt]
         acc = 0
         for cf, factors in self.constraints[k]:
             m = cf % p
@@ -785,13 +849,16 @@ class Air:
                 return j, r
         for k in range(len(self.constraints)):
             for r in range(n - 1):
-                if self.constraint_value(k, p, [col[r] for col in cols], [col[r + 1] for col in cols]):
+                if self.constraint_value(k, p, [col[r] for col in cols], [col[r + 1] for col in cols], self.periodic_row(p, r),
+                                         self.periodic_row(p, r + 1)):
                     return len(self.boundaries) + k, r
         return None
 
-    def compose_at(self, p, log_n, log_blowup, trace_offset, lde_offset, omega_N, i, cur, nxt, weights):
+    def compose_at(self, p, log_n, log_blowup, trace_offset, lde_offset, omega_N, i, cur, nxt, weights, per_cur=None, per_nxt=None):
         """cw[i] from the extended columns' values at index i (cur) and (i + B) mod N (nxt; unused when there is no
-        transition constraint) under the W + K unreduced weights -- the definition of include/stark_mi.h, term by term"""
+        transition constraint) under the W + K unreduced weights -- the definition of include/stark_mi.h, term by term.
+        per_cur / per_nxt: pi_j(x_i) and pi_j(w x_i) of the periodic columns; left out, they are evaluated here from the
+        definition (periodic_at), which is for small periods or small n"""
         n, B = 1 << log_n, 1 << log_blowup
         inv = lambda v: pow(v, p - 2, p)
         w = pow(omega_N, B, p)
@@ -814,6 +881,10 @@ class Air:
         if self.constraints:
             last = trace_offset * pow(w, n - 1, p) % p
             zt_inv = (x - last) * inv(pow(x, n, p) - pow(trace_offset, n, p)) % p
+            if self.periodics and per_cur is None:
+                per_cur = self.periodic_at(p, log_n, trace_offset, w, x)
+            if self.periodics and per_nxt is None:
+                per_nxt = self.periodic_at(p, log_n, trace_offset, w, x * w % p)
             for k in range(len(self.constraints)):
-                acc += weights[self.n_cols + k] % p * (self.constraint_value(k, p, cur, nxt) * zt_inv % p)
+                acc += weights[self.n_cols + k] % p * (self.constraint_value(k, p, cur, nxt, per_cur or (), per_nxt or ()) * zt_inv % p)
         return acc % p

@@ -10,7 +10,10 @@
 compose: HIP-event time of air_compose_kernel (smi_ctx_profile) at (W = 4, n = 2^22, B = 8) for the empty, fib-like,
 mixer AIRs and at (W = 64, n = 2^18) for a 32-constraint AIR; median of REPS launches after 3 warm-up launches;
 achieved bytes/s of 4 (W + 1) N against an in-run device-to-device copy moving the same bytes.
-prove: median wall time of nine smi_dev_air_prove(empty) / smi_dev_stark_prove(open_columns = 1) calls on one trace."""
+prove: median wall time of nine smi_dev_air_prove(empty) / smi_dev_stark_prove(open_columns = 1) calls on one trace.
+periodic: four lanes x' = (x + k)^3 at (n = 2^22, B = 8), (a) the constants as periodic columns (W = 4, Q = 4, period 64 and
+period n) and (b) as four more trace columns (W = 8, Q = 0): compose kernel time, prove wall time and stages.  --no-periodic
+leaves (a) out: what a library without periodic columns (SMI_LIB) can run."""
 import argparse
 import os
 import statistics
@@ -25,6 +28,8 @@ ap.add_argument("--stark-only", action="store_true")
 ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--single", action="store_true", help="one launch per AIR at (W = 4, n = 2^22) and nothing else: the run to put under "
                 "`rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES` (the k-th air_compose_kernel dispatch is the k-th AIR printed)")
+ap.add_argument("--no-periodic", action="store_true", help="skip the legs that need periodic columns")
+ap.add_argument("--no-stark", action="store_true", help="skip smi_dev_stark_prove")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 import torch  # noqa: E402
@@ -75,13 +80,13 @@ def airs(W, n):
     fib = Air(W)
     fib.transition({("next", 0): 1, ("cur", 1): -1}).transition({("next", 1): 1, ("cur", 0): -1, ("cur", 1): -1})
     fib.boundary(0, 0, 1).boundary(1, 0, 1).boundary(0, n - 1, 5)
-    mixer = Air(W)
-    mixer.transition({("next", 0): 1, (("cur", 0), ("cur", 1)): -1, ("cur", 2): -1})
-    mixer.transition({("next", 1): 1, (("cur", 0, 2), ("cur", 2)): -1, ("cur", 1): -3})
-    mixer.transition({("next", 2): 1, ("cur", 2): -1, (): -1})
+    def transitions(air):
+        air.transition({("next", 0): 1, (("cur", 0), ("cur", 1)): -1, ("cur", 2): -1})
+        air.transition({("next", 1): 1, (("cur", 0, 2), ("cur", 2)): -1, ("cur", 1): -3})
+        return air.transition({("next", 2): 1, ("cur", 2): -1, (): -1})
+    mixer = transitions(Air(W))
     mixer.boundary(0, 0, 5).boundary(1, 0, 11).boundary(2, 0, 0).boundary(2, n - 1, n - 1).boundary(0, n - 1, 9)
-    only_t = Air(W)
-    only_t.constraints = list(mixer.constraints)
+    only_t = transitions(Air(W))
     only_b = Air(W)
     only_b.boundaries = list(mixer.boundaries)
     return [("empty", empty), ("fib", fib), ("mixer", mixer), ("mixer, transitions only", only_t), ("mixer, boundaries only", only_b)]
@@ -94,6 +99,16 @@ def wide(W, K, n):
         air.transition({("next", k % W): 1, (("cur", (k + 1) % W), ("cur", (3 * k + 2) % W)): -(k + 1), ("cur", (5 * k) % W, 2): 7, (): k})
     for c in range(0, W, 4):
         air.boundary(c, 0, 1).boundary(c, n - 1 - c, 2)
+    return air
+
+
+def lanes(periods):
+    """len(periods) lanes x' = (x + k)^3 with lane c's constants in periodic column c"""
+    from stark_rs_amd.mirror import Air
+    air = Air(len(periods))
+    for c, P in enumerate(periods):
+        air.periodic([int(v) for v in rng.integers(0, p, P)])
+        air.transition({("next", c): 1, ("cur", c, 3): -1, (("cur", c, 2), ("per", c)): -3, (("cur", c), ("per", c, 2)): -3, ("per", c, 3): -1})
     return air
 
 
@@ -146,8 +161,9 @@ def wall(fn):
     return runs
 
 
-runs = wall(lambda: eng.dev_stark_prove(trace.data_ptr(), W, log_n, lb, t, timed=True, open_columns=True))
-print(f"stark_prove(open_columns=1) W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+if not args.no_stark:
+    runs = wall(lambda: eng.dev_stark_prove(trace.data_ptr(), W, log_n, lb, t, timed=True, open_columns=True))
+    print(f"stark_prove(open_columns=1) W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
 if not args.stark_only:
     from stark_rs_amd.mirror import Air
     flat = Air(W).flatten(p)
@@ -157,4 +173,27 @@ if not args.stark_only:
     flat = mixer.flatten(p)
     runs = wall(lambda: eng.dev_air_prove(flat, trace.data_ptr(), W, log_n, lb, t, timed=True, check=False))
     print(f"air_prove(mixer, any trace) W=4 n=2^22: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+
+if not args.stark_only:
+    # periodic columns against the same constants committed as trace columns
+    n, N = 1 << log_n, 1 << (log_n + lb)
+    legs = [] if args.no_periodic else [("(a) W=4 Q=4 period 64", lanes([64] * 4), None), ("(a') W=4 Q=4 period n", lanes([n] * 4), None)]
+    a64 = lanes([64] * 4)
+    legs.append(("(b) W=8 Q=0, constants committed", a64.with_periodic_as_trace(),
+                 torch.from_numpy(np.stack([np.resize(np.array(v, dtype=np.int64), n) for v in a64.periodics]).astype(np.int32)).to(dev)))
+    for name, air, extra in legs:
+        Wl, K = air.n_cols, len(air.constraints)
+        flat = air.flatten(p)
+        tr = trace if extra is None else torch.cat([trace, extra]).contiguous()
+        lde, out = torch.empty((Wl, N), dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+        wts = torch.from_numpy(rng.integers(0, 1 << 62, Wl + K, dtype=np.int64)).to(dev)
+        torch.cuda.synchronize()
+        eng.dev_lde(tr.data_ptr(), Wl, log_n, lb, lde.data_ptr())
+        med, lo, hi = median_kernel_ms(lambda: eng.dev_air_compose(flat, lde.data_ptr(), Wl, log_n, lb, wts.data_ptr(), out.data_ptr()),
+                                       "air_compose_kernel")
+        nbytes = 4 * (Wl + 1) * N
+        print(f"  compose {name:34s}: median {med:7.3f} ms (min {lo:.3f}, max {hi:.3f})  4(W+1)N = {nbytes / 1e9:.3f} GB  {nbytes / med / 1e9:5.2f} TB/s", flush=True)
+        del lde, out
+        runs = wall(lambda: eng.dev_air_prove(flat, tr.data_ptr(), Wl, log_n, lb, t, timed=True, check=False))
+        print(f"air_prove {name:34s}: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
 eng.close()

@@ -85,6 +85,8 @@ def lib():
         L.so_hash_from_bytes.argtypes = [C.c_char_p, C.c_size_t, u8p]
         L.so_hash_from_field_elements.argtypes = [u64p, C.c_size_t, u8p]
         L.so_hash_from_u64.argtypes = [u64, u8p]
+        L.so_leaf_hashes.argtypes = [u64p, C.c_size_t, C.c_void_p]
+        L.so_row_hashes.argtypes = [u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
         L.so_hash_combine.argtypes = [C.c_char_p, C.c_char_p, u8p]
         L.so_merkle_new.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.so_merkle_commit.argtypes = [C.c_void_p, C.c_size_t, u8p]
@@ -277,6 +279,23 @@ def leaf_hashes(codeword) -> np.ndarray:
     for i in range(len(a)):
         L.so_hash_from_field_elements(_p(a[i:i + 1]), 1, tmp)
         out[i] = np.frombuffer(bytes(tmp), dtype=np.uint8)
+    return out
+
+
+def leaf_hashes_batched(codeword) -> np.ndarray:
+    """leaf_hashes in one C call (so_leaf_hashes: the same per-element hash in a loop) -- for trees of 2^16 leaves and up."""
+    a = _arr(codeword).reshape(-1)
+    out = np.zeros((len(a), 32), dtype=np.uint8)
+    lib().so_leaf_hashes(_p(a), len(a), out.ctypes.data)
+    return out
+
+
+def row_hashes(cols) -> np.ndarray:
+    """cols (W, n) -> (n, 32): leaf i = Hash::from_field_elements(row i) (so_row_hashes; the build-defined row-leaf rule)."""
+    a = _arr(cols)
+    assert a.ndim == 2
+    out = np.zeros((a.shape[1], 32), dtype=np.uint8)
+    lib().so_row_hashes(_p(a), a.shape[0], a.shape[1], a.shape[1], out.ctypes.data)
     return out
 
 

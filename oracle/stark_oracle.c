@@ -364,6 +364,20 @@ void so_hash_from_field_elements(const uint64_t *e, size_t n, uint8_t out[32]) {
     so_hash_from_bytes(buf, n * 8, out);
     free(buf);
 }
+/* Batched leaf rules: plain loops over so_hash_from_field_elements, the one statement of the hash.
+ * so_leaf_hashes: leaf i = from_field_elements([e[i]]) (fri.rs:118-121).
+ * so_row_hashes : leaf i = from_field_elements(row i) of n_cols columns, column c at cols + c*col_stride (build-defined). */
+void so_leaf_hashes(const uint64_t *e, size_t n, uint8_t *out) {
+    for (size_t i = 0; i < n; i++) so_hash_from_field_elements(e + i, 1, out + i * 32);
+}
+void so_row_hashes(const uint64_t *cols, size_t n_cols, size_t col_stride, size_t n, uint8_t *out) {
+    uint64_t *row = xmalloc((n_cols ? n_cols : 1) * 8);
+    for (size_t i = 0; i < n; i++) {
+        for (size_t c = 0; c < n_cols; c++) row[c] = cols[c * col_stride + i];
+        so_hash_from_field_elements(row, n_cols, out + i * 32);
+    }
+    free(row);
+}
 /* hash.rs:37-39 */
 void so_hash_from_u64(uint64_t v, uint8_t out[32]) {
     uint8_t b[8];

@@ -77,6 +77,8 @@ int so_poly_test_colinearity(uint64_t p, const uint64_t *xs, const uint64_t *ys,
 /* ---- hash (src/hash.rs) ---- */
 void so_hash_from_bytes(const uint8_t *bytes, size_t len, uint8_t out[32]);          /* hash.rs:7-30 */
 void so_hash_from_field_elements(const uint64_t *e, size_t n, uint8_t out[32]);      /* hash.rs:32-35 */
+void so_leaf_hashes(const uint64_t *e, size_t n, uint8_t *out);                       /* n x from_field_elements([e[i]]) */
+void so_row_hashes(const uint64_t *cols, size_t n_cols, size_t col_stride, size_t n, uint8_t *out); /* n x from_field_elements(row i) */
 void so_hash_from_u64(uint64_t v, uint8_t out[32]);                                  /* hash.rs:37-39 */
 void so_hash_combine(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]);     /* hash.rs:41-46 */
 

@@ -424,6 +424,119 @@ def test_fold_equals_reference_fold(eng, oracle, logn):
         assert np.array_equal(eng.fri_fold(cw, alpha, 3, omega), want)
 
 
+def _dev_u64(values):
+    """raw 64-bit words in device memory (dev_upload stores 32-bit residues): a torch tensor, kept alive by the caller"""
+    import torch
+    return torch.from_numpy(np.array(values, dtype=np.uint64).view(np.int64)).cuda()
+
+
+UNREDUCED_ALPHAS = (0, 1, P - 1, P, 0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF)
+
+
+@pytest.mark.parametrize("logn", [1, 10, 20])
+def test_dev_fold_with_the_challenge_in_device_memory(eng, oracle, logn):
+    """smi_dev_fri_fold: codeword, challenge (an unreduced u64, as the Fiat-Shamir kernels leave it) and result all on the
+    device -- Fri::fold_codeword (src/fri.rs:158-181) op for op up to 2^10, its fast restatement at 2^20."""
+    o = oracle
+    n = 1 << logn
+    omega, offset = o.ff_prim_nth_root(n), 3
+    cfg = o.fri_cfg(omega, offset, n, 4, 1)
+    cw = _vals(o, 0xF01D + logn, n)
+    cw[0] = cw[n // 2] = cw[n - 1] = P - 1
+    d_in, d_out = eng.dev_alloc(n * 4), eng.dev_alloc(max(n // 2, 1) * 4)
+    eng.dev_upload(cw, d_in)
+    alphas = _dev_u64(UNREDUCED_ALPHAS)
+    for k, alpha in enumerate(UNREDUCED_ALPHAS):
+        eng.dev_fri_fold(d_in, n, alphas.data_ptr() + 8 * k, offset, omega, d_out)
+        got = eng.dev_download(d_out, n // 2)
+        want = o.fast_fold(cw, alpha, offset, omega)
+        if logn <= 10:
+            assert np.array_equal(want, o.fri_fold_codeword(cfg, cw, alpha, offset, omega))
+        assert np.array_equal(got, want), (logn, hex(alpha))
+    assert np.array_equal(eng.dev_download(d_in, n), cw)   # the input is left alone
+    eng.dev_free(d_in)
+    eng.dev_free(d_out)
+
+
+@pytest.mark.parametrize("cuts", [(), (1,), (7, 20000), (1, 2, 255, 256, 257, 4096, 32767)])
+def test_dev_fold_in_uneven_shards_concatenates_to_the_fold(eng, oracle, cuts):
+    """smi_dev_fri_fold_shard, the multi-GPU loop's piece: the 2^15 outputs of a 2^16 codeword cut into 1, 2, 3 and 8
+    uneven ranges, each folded from its own copies of the two halves it needs (nothing else of the codeword is on the
+    device, so an index taken from the wrong base reads poison); concatenated they are the oracle's fold."""
+    o = oracle
+    n = 1 << 16
+    half, omega, offset = n // 2, o.ff_prim_nth_root(n), 5
+    cw = _vals(o, 0x5A4D, n)
+    cw[0] = cw[half - 1] = cw[half] = cw[n - 1] = P - 1
+    alpha = 0xFFFFFFFFFFFFFFFF
+    want = o.fast_fold(cw, alpha, offset, omega)
+    assert np.array_equal(want[:64], o.fri_fold_codeword(o.fri_cfg(omega, offset, n, 4, 1), cw, alpha, offset, omega)[:64])
+    d_alpha = _dev_u64([alpha])
+    bounds = [0] + list(cuts) + [half]
+    assert len(bounds) - 1 in (1, 2, 3, 8) and bounds == sorted(set(bounds))
+    poison = np.full(8, P - 2, dtype=np.uint64)
+    got = []
+    for i0, i1 in zip(bounds, bounds[1:]):
+        count = i1 - i0
+        d_lo, d_hi, d_out = (eng.dev_alloc((count + 16) * 4) for _ in range(3))
+        for d, part in ((d_lo, cw[i0:i1]), (d_hi, cw[half + i0:half + i1])):
+            eng.dev_upload(np.concatenate([poison, part, poison]), d)
+        eng.dev_upload(np.full(count + 16, 12345, dtype=np.uint64), d_out)
+        eng.dev_fri_fold_shard(d_lo + 32, d_hi + 32, count, i0, n, d_alpha.data_ptr(), offset, omega, d_out + 32)
+        out = eng.dev_download(d_out, count + 16)
+        assert (out[:8] == 12345).all() and (out[-8:] == 12345).all()   # nothing written outside the shard
+        got.append(out[8:-8])
+        for d in (d_lo, d_hi, d_out):
+            eng.dev_free(d)
+    assert np.array_equal(np.concatenate(got), want)
+
+
+def test_set_stream_runs_the_pipeline_on_the_callers_stream(oracle):
+    """smi_ctx_set_stream: upload, dev_lde, dev_merkle_build, dev_fri_prove and download on a fresh engine's own stream, then
+    on a caller's stream, then on a second one -- every result the oracle's each time, and the engine closes cleanly."""
+    import torch
+    import stark_rs_amd as s
+    o = oracle
+    logn, lb, t = 12, 3, 8
+    n, N = 1 << logn, 1 << (logn + lb)
+    col = _vals(o, 0x57E4, n)
+    col[0] = col[-1] = P - 1
+    w, Wn = o.ff_prim_nth_root(n), o.ff_prim_nth_root(N)
+    want_lde = o.fast_coset_ntt(o.fast_intt(col, w, 1), N, Wn, G)
+    want_nodes = o.merkle_new(o.leaf_hashes_batched(want_lde))
+    want_proof, want_top = o.fri_prove(o.fri_cfg(Wn, G, N, 1 << lb, t), want_lde)
+    e = s.Engine(P, G, 0)
+    cfg = e.fri_cfg(Wn, G, N, 1 << lb, t)
+
+    def pipeline():
+        d_in, d_out, d_nodes = e.dev_alloc(n * 4), e.dev_alloc(N * 4), e.dev_alloc((2 * N - 1) * 32)
+        e.dev_upload(col, d_in)
+        e.dev_lde(d_in, 1, logn, lb, d_out, 1, G)
+        e.dev_merkle_build(d_out, N, d_nodes)
+        proof, top = e.dev_fri_prove(cfg, d_out, N)
+        lde = e.dev_download(d_out, N)
+        nodes = e.dev_download(d_nodes, (2 * N - 1) * 8).astype(np.uint32).view(np.uint8).reshape(-1, 32)
+        for d in (d_in, d_out, d_nodes):
+            e.dev_free(d)
+        return lde, nodes, bytes(proof), list(top)
+
+    runs = [pipeline()]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]   # alive until the engine is closed
+    for st in streams:
+        e.set_stream(st.cuda_stream)
+        runs.append(pipeline())
+        e.sync()
+        assert st.query()   # the work went to this stream and is finished
+    for lde, nodes, proof, top in runs:
+        assert np.array_equal(lde, want_lde)
+        assert np.array_equal(nodes, want_nodes)
+        assert proof == want_proof and top == want_top
+    e.close()
+    assert e.h is None
+    torch.cuda.synchronize()
+    del streams
+
+
 def _domain(o, omega, offset, n):
     return [o.ff_mul(offset, o.ff_exp(omega, i)) for i in range(n)]
 

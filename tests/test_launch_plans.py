@@ -252,3 +252,49 @@ def test_fri_layout_against_the_oracle(emu, oracle):
             assert proof[offs[2 * i]] == 2 and proof[offs[2 * i + 1]] == 3
         emu.emu_fri_layout(N, expansion, t, 0, head, offs)
         assert head[4] == off_layers
+
+
+# ------------------------------------------------------- what the GPU battery (tests/gpu_battery.py) must reach
+def step_signature(st, kind):
+    """what tells one launch of launch_merkle_impl from another: the kernel family and instantiation, where level 0 comes
+    from (the leaf kind, when this step hashes leaves), K or the chunk size, whether it ends with the root, and what it
+    can do with computed leaves"""
+    return (st["family"], st["inst"], kind if st["from_leaves"] else "-", st["arg"], st["ends_root"], st["src_cap"])
+
+
+def test_battery_trees_take_every_step_a_single_tree_takes(emu):
+    """A coverage condition, not a measurement: under each of the thirteen knob settings, every step signature that a
+    single tree of up to 2^23 leaves takes -- element, digest or row leaves -- is taken by some tree of the battery that
+    tests/test_gpu_plans.py runs on the GPU under that setting.  The battery's trees stop at 2^21 leaves; only under
+    TOP_BLOCKS=1024 do steps first appear above that, and for that setting alone its two extra trees count."""
+    import gpu_battery as gb
+    shape = {"E": (ELEMENTS, 0), "D": (DIGESTS, 0), "R": (ROWS, 4)}
+
+    def battery_plan(kind, logn, w, kn):
+        if kind == "R" and w > 4:      # launch_merkle_rows: rows wider than four columns are hashed first, then a tree of digests
+            return "D", merkle_plan(emu, 1 << logn, 1, DIGESTS, 0, kn)
+        leaves, cols = shape[kind]
+        return kind, merkle_plan(emu, 1 << logn, 1, leaves, w if kind == "R" else cols, kn)
+
+    assert set(gb.EXTRA_TREES) == {"Dx22", "Rx22"}
+    for over in KNOB_SETTINGS:
+        kn = knobs(**over)
+        have = set()
+        for name, (kind, logn, w, _full) in gb.tree_items(extras=over == dict(TOP_BLOCKS=1024)).items():
+            k, plan = battery_plan(kind, logn, w, kn)
+            have |= {step_signature(st, k) for st in plan}
+        for kind, (leaves, cols) in shape.items():
+            for logn in range(24):
+                for st in merkle_plan(emu, 1 << logn, 1, leaves, cols, kn):
+                    assert step_signature(st, kind) in have, (over, kind, logn, st)
+    # the extras are the smallest trees that take the two late steps of TOP_BLOCKS=1024, and they are needed
+    kn = knobs(TOP_BLOCKS=1024)
+    late = {"D": (SUB, INST_K2, "-", 2, 0, 0), "R": (SUB, INST_ROWS, "R", 2, 0, 0)}
+    for kind, sig in late.items():
+        leaves, cols = shape[kind]
+        first = min(l for l in range(24) if sig in {step_signature(st, kind) for st in merkle_plan(emu, 1 << l, 1, leaves, cols, kn)})
+        assert first == 22 and gb.EXTRA_TREES[kind + "x22"][1] == 22
+        for other in ("E", "D", "R"):
+            lv, cc = shape[other]
+            for l in range(22):
+                assert sig not in {step_signature(st, other) for st in merkle_plan(emu, 1 << l, 1, lv, cc, kn)}

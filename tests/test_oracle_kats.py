@@ -266,6 +266,28 @@ def test_hash_two_restatements_agree(oracle):
         assert oracle.hash_from_bytes(data) == _pyhash(data), n
 
 
+def test_batched_leaf_and_row_hashes_equal_the_per_item_calls(oracle):
+    """so_leaf_hashes / so_row_hashes are loops over so_hash_from_field_elements: digest for digest the per-item calls,
+    for values up to 2^64 - 1 (eight bytes each on the wire), every row width the row kernels take, and n = 0."""
+    o = oracle
+    vals = o.splitmix64(0x4B4154, 300)
+    vals[0], vals[1], vals[-1] = o.P_REF - 1, 2**64 - 1, 0
+    got = o.leaf_hashes_batched(vals)
+    assert got.shape == (300, 32) and got.dtype == np.uint8
+    for i in range(300):
+        assert bytes(got[i]) == o.hash_from_field_elements([int(vals[i])]), i
+    assert np.array_equal(got, o.leaf_hashes(vals))
+    assert o.leaf_hashes_batched(vals[:0]).shape == (0, 32)
+    for W in (1, 2, 3, 4, 5, 9):
+        cols = np.stack([o.splitmix64(0x524F57 + 16 * W + c, 70) % np.uint64(o.P_REF) for c in range(W)])
+        cols[0, 0] = cols[W - 1, -1] = o.P_REF - 1
+        got = o.row_hashes(cols)
+        assert got.shape == (70, 32)
+        for i in range(70):
+            assert bytes(got[i]) == o.hash_from_field_elements([int(cols[c, i]) for c in range(W)]), (W, i)
+    assert np.array_equal(o.row_hashes(vals[None, :]), o.leaf_hashes_batched(vals))   # one column: the single-element leaf
+
+
 def test_merkle(oracle):
     o = oracle
     leaves = np.stack([np.frombuffer(o.hash_from_bytes(bytes([i])), dtype=np.uint8) for i in range(4)])

@@ -208,6 +208,8 @@ extern "C" {
     pub fn smi_dev_air_check(ctx: *mut smi_ctx, air: *const c_void, n_cols: u32, log_n: u32, d_trace_cols: *const u32, ok: *mut c_int, constraint: *mut u32, row: *mut u64) -> c_int;
     pub fn smi_dev_air_prove(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, column_roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
     pub fn smi_air_verify(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, column_roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
+    pub fn smi_dev_air_prove_rows(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
+    pub fn smi_air_verify_rows(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -751,6 +753,36 @@ impl Air {
         let mut accept = 0 as c_int;
         ctx.check(self.with_raw(|a| unsafe {
             smi_air_verify(ctx.raw, cfg, a, column_roots.as_ptr() as *const u8, proof.as_ptr(), proof.len(), &mut accept)
+        }));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+    /// `smi_dev_air_prove_rows` -> (root of the one tree over the rows, proof bytes): the same statement with every
+    /// queried position opened once.  `check_trace` as in `prove`.
+    pub fn prove_rows(&self, ctx: &Context, cfg: &smi_stark_cfg, d_trace_cols: *const u32, check_trace: bool) -> ([u8; 32], Vec<u8>) {
+        if check_trace {
+            if let Some((con, row)) = self.check_trace(ctx, cfg.log_n, d_trace_cols) {
+                let why = unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned();
+                panic!("the trace violates constraint {} at row {}: {}", con, row, why);
+            }
+        }
+        let mut root = [0u8; 32];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_dev_air_prove_rows(ctx.raw, cfg, a, d_trace_cols, root.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut())
+        }));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (root, bytes)
+    }
+    /// `smi_air_verify_rows` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify_rows(&self, ctx: &Context, cfg: &smi_stark_cfg, row_root: &[u8; 32], proof: &[u8]) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_air_verify_rows(ctx.raw, cfg, a, row_root.as_ptr(), proof.as_ptr(), proof.len(), &mut accept)
         }));
         if accept != 0 {
             Ok(())

@@ -470,7 +470,8 @@ int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
 int smi_dev_air_check(smi_ctx *ctx, const void *air, uint32_t n_cols, uint32_t log_n, const uint32_t *d_trace_cols, int *ok,
                       uint32_t *constraint, uint64_t *row);
 /* trace -> LDE -> one tree per column -> weights -> composition codeword -> Fri::prove at expansion factor E ->
- * openings.  cfg->row_leaves must be 0 (SMI_ERR_BAD_ARG); open_columns is taken as set.
+ * openings.  cfg->row_leaves must be 0 (SMI_ERR_BAD_ARG; smi_dev_air_prove_rows below commits to one tree over the
+ * rows); open_columns is taken as set.
  * Transcript: empty; for c < W absorb column root c, weight_c = challenge(); for k < K absorb k as 8 little-endian
  * bytes, weight_{W+k} = challenge(); FRI continues this transcript of 32W + 8K bytes (as smi_dev_fri_prove_fs would).
  * Proof bytes: the FRI objects, then per colinearity test s, with a = top[s] mod N/2 and b = a + N/2, the rows
@@ -486,6 +487,36 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, c
  * smi_stark_verify. */
 int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *column_roots, const uint8_t *proof,
                    size_t proof_len, int *accept);
+
+/* ---- AIR over one row-committed tree ----------------------------------------------------------
+ * The same statement, composition codeword, limits, status codes and smi_air_plan as above, with the extended trace
+ * committed as ONE tree over its rows instead of W trees over its columns: a leaf costs ceil(W/4) + 8 mixes where the W
+ * column leaves cost 9 W, there is one set of node levels instead of W, and a queried position is opened once instead of
+ * W times.  The two calls below take cfg->row_leaves and cfg->open_columns as set, whatever they hold (smi_dev_air_prove
+ * and smi_air_verify keep refusing row_leaves = 1).  n_cols <= 64 is also the widest row the leaf hash takes.
+ *
+ * Commitment.  One tree over N = n B leaves, leaf i = Hash::from_field_elements([lde[0][i] .. lde[W-1][i]]) (src/hash.rs:
+ *   32-35 on the row's W u64s): the tree smi_dev_merkle_build_rows builds over the extended columns.  row_root (host,
+ *   optional in the prover) is its root.
+ * Transcript.  Empty; absorb the root (32 bytes); for j = 0 .. W+K-1 absorb j as 8 little-endian bytes, weight_j =
+ *   challenge().  Column c has j = c, constraint k has j = W + k.  FRI continues this transcript of 32 + 8 (W + K) bytes
+ *   (as smi_dev_fri_prove_fs would).  Periodic columns stay outside it.
+ * Proof bytes.  The FRI objects at expansion factor E; then per colinearity test s, with a = top[s] mod N/2 and b = a +
+ *   N/2, the rows FieldElements(col_0 .. col_{W-1}) at a, b and -- only when K > 0 -- at (a+B) mod N, (b+B) mod N (the
+ *   column-tree proof's rows); then for every s ONE MerklePath per opened position, in the same position order, each
+ *   log2 N digests deep.  With R = K ? 4 : 2 the opening section is t R (9 + 8 W) + t R (9 + 32 log2 N) bytes:
+ *   t R (W - 1) (9 + 32 log2 N) fewer than the column-tree proof of the same statement.
+ * stage_ms (optional) gets five values {lde, commit, compose, fri, open}, as in smi_dev_air_prove.
+ * Verifier.  Transcript, weights and seed as above; Fri::verify at E; the exact length of the opening section, the tag
+ *   and width of every record; every opened row hashed to its leaf from its 8-byte little-endian values as they stand in
+ *   the proof; all t R paths against row_root; then the canonical check and the composition recomputed at x_a and x_b
+ *   exactly as smi_air_verify does, periodic operands included (the same code).  *accept and smi_last_error as in
+ *   smi_air_verify; a proof of the column-tree variant is rejected here and the other way round, since the transcripts
+ *   differ even where the roots coincide (W = 1). */
+int smi_dev_air_prove_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms);
+int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                        size_t proof_len, int *accept);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

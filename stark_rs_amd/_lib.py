@@ -175,6 +175,8 @@ def lib():
         "smi_dev_air_check": (i32, [vp, C.POINTER(Air), C.c_uint32, C.c_uint32, vp, C.POINTER(i32), u32p, u64p]),
         "smi_dev_air_prove": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
         "smi_air_verify": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
+        "smi_dev_air_prove_rows": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
+        "smi_air_verify_rows": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

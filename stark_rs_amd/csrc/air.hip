@@ -92,6 +92,13 @@ __global__ __launch_bounds__(64) void air_open_kernel(const MgSide *cols, uint32
     mg_column_open_write_n(cols, W, blockIdx.y, top[blockIdx.x], blockIdx.x, t, 0, out, threadIdx.x, 64, R, B);
 }
 
+// openings of the one tree over the rows at the same positions (mgpu_core.h mg_row_open_write): one workgroup per (test,
+// position); lanes gather the row's W values from the extended columns and copy the log2 N sibling digests
+__global__ __launch_bounds__(64) void air_row_open_kernel(const uint32_t *__restrict__ cols, size_t stride, uint32_t W, const uint8_t *__restrict__ nodes,
+                                                           uint32_t depth, const uint64_t *__restrict__ top, uint32_t t, uint32_t R, uint64_t B, uint8_t *out) {
+    mg_row_open_write(cols, stride, W, nodes, depth, top[blockIdx.x], blockIdx.x, blockIdx.y, t, out, threadIdx.x, 64, R, B);
+}
+
 // out[q * 2Q + j] = pi_j(x_i), out[q * 2Q + Q + j] = pi_j(w x_i) for i = idx[q]: what the verifier needs of the tables
 __global__ __launch_bounds__(64) void air_periodic_gather_kernel(AirDev A, const uint64_t *__restrict__ idx, uint32_t count, uint32_t *__restrict__ out) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -256,12 +263,12 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
     return SMI_OK;
 }
 
-int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const uint32_t *d_trace_cols, uint8_t *column_roots,
-                      uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms) {
-    const smi_air *air = (const smi_air *)air_;
-    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
-    DeviceGuard dg__(ctx);
-    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_prove: column trees only (row_leaves must be 0)");
+// The prover of both commitments.  rows == false: one tree per column, the transcript of the W roots and the K constraint
+// indices, W paths per opened position (smi_dev_air_prove).  rows == true: one tree over the rows, the transcript of its
+// root and the W + K indices, one path per opened position (smi_dev_air_prove_rows).  Everything else -- the extension, the
+// periodic tables, the composition, FRI, the copy-back -- is the same code.
+static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
+                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows) {
     AirHost H;
     uint64_t E = 0;
     SMI_TRY(air_host(ctx, cfg, air, &H, &E));
@@ -281,11 +288,12 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
 
     const size_t tree_stride = 2 * N * 32;
+    const uint32_t n_trees = rows ? 1u : W;
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
     uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, N * 4);
     uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * (size_t)(W + K));
     uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree_base = (uint8_t *)arena_alloc(ctx, tree_stride * W);
+    uint8_t *tree_base = (uint8_t *)arena_alloc(ctx, tree_stride * n_trees);
     uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
     if (H.dev.Q) {
         d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
@@ -296,12 +304,13 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     mark(0);
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, cfg->log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
     mark(1);
-    SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
+    if (rows) SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree_base));
+    else SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
     mark(2);
-    // The W roots make one small round trip: the transcript (roots, then the constraint indices) and its weights
+    // The roots make one small round trip: the transcript (roots, then the indices) and its weights
     // are computed on the host, where fri_run's seed is computed anyway (FsSeed, internal.h).
-    std::vector<uint8_t> roots(32 * (size_t)W), tr;
-    HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, W, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<uint8_t> roots(32 * (size_t)n_trees), tr;
+    HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, n_trees, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // part of the compose stage, queued before the host waits for the roots
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> weights(W + K);
@@ -310,13 +319,24 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
         hashc::hash_bytes(tr.data(), tr.size(), d);
         return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
     };
-    for (uint32_t c = 0; c < W; c++) {
-        tr.insert(tr.end(), roots.begin() + 32 * c, roots.begin() + 32 * c + 32);
-        weights[c] = challenge();
-    }
-    for (uint32_t k = 0; k < K; k++) {
-        for (int i = 0; i < 8; i++) tr.push_back((uint8_t)((uint64_t)k >> (8 * i)));
-        weights[W + k] = challenge();
+    auto absorb_index = [&](uint64_t j) {
+        for (int i = 0; i < 8; i++) tr.push_back((uint8_t)(j >> (8 * i)));
+    };
+    if (rows) {   // the root, then j = 0 .. W + K - 1 with a challenge after each
+        tr = roots;
+        for (uint32_t j = 0; j < W + K; j++) {
+            absorb_index(j);
+            weights[j] = challenge();
+        }
+    } else {
+        for (uint32_t c = 0; c < W; c++) {
+            tr.insert(tr.end(), roots.begin() + 32 * c, roots.begin() + 32 * c + 32);
+            weights[c] = challenge();
+        }
+        for (uint32_t k = 0; k < K; k++) {
+            absorb_index(k);
+            weights[W + k] = challenge();
+        }
     }
     FsSeed seed;
     hashc::fs_seed(tr.data(), tr.size(), seed.s, &seed.phase);
@@ -339,7 +359,19 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
     if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
     else top_indices = res.top.data();   // the column openings need the top-level indices either way
     mark(4);
-    if (cfg->num_colinearity_tests) {
+    if (cfg->num_colinearity_tests && rows) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
+        const size_t ob = (size_t)mg_row_open_bytes(W, t, log_N, R);
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob);
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove: row openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, top_indices, 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        air_row_open_kernel<<<dim3(t, R), 64, 0, ctx->stream>>>(d_lde, N, W, tree_base, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open);
+        HIP_TRY(ctx, hipGetLastError());
+        const size_t at = bytes.size();
+        bytes.resize(at + ob);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob, hipMemcpyDeviceToHost, ctx->stream));
+    } else if (cfg->num_colinearity_tests) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
         std::vector<MgSide> sides(W);
         for (uint32_t c = 0; c < W; c++) {
@@ -369,4 +401,19 @@ int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, 
             stage_ms[i] = ms;
         }
     return smi_proof_out(ctx, bytes, proof, proof_len);
+}
+
+int smi_dev_air_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
+                      uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_prove: column trees only (row_leaves must be 0; smi_dev_air_prove_rows commits to one tree over the rows)");
+    return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, column_roots, proof, proof_len, top_indices, stage_ms, false);
+}
+
+int smi_dev_air_prove_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true);
 }

@@ -318,6 +318,7 @@ extern "C" int emu_lde2(uint64_t p, uint64_t g, const uint32_t *coef, uint32_t *
 
 // ---- hash phases (hash_core.h) --------------------------------------------------------
 #include "hash_core.h"
+#include "merkle_plan.h"   // SMI_HASH_THREADS
 // pairs go through the two-hashes-per-state path the Merkle kernels use, the odd tail through the
 // single-hash path
 extern "C" void emu_leaf_hash(const uint32_t *v, size_t n, uint8_t *out) {
@@ -534,6 +535,22 @@ extern "C" void emu_row_hash(const uint32_t *v, size_t n_rows, int W, uint8_t *o
         hashc::row_hash(v + i * W, W, d);
         memcpy(out + 32 * i, d, 32);
     }
+}
+// row_hash_wide_kernel (hash.hip) one workgroup and one lane at a time: the kernel's grid, its choice of a lane's two
+// rows (row_wide_pair) and its per-lane body (row_hash_wide2) over columns `stride` apart
+extern "C" void emu_row_hash_wide(const uint32_t *cols, size_t stride, size_t n, int W, uint8_t *out) {
+    const uint32_t T = SMI_HASH_THREADS;
+    const size_t blocks = ((n + 1) / 2 + T - 1) / T;
+    for (size_t blk = 0; blk < blocks; blk++)
+        for (uint32_t tid = 0; tid < T; tid++) {
+            size_t i0, i1;
+            bool two;
+            if (!hashc::row_wide_pair(blk, tid, T, n, &i0, &i1, &two)) continue;
+            uint32_t d0[8], d1[8];
+            hashc::row_hash_wide2(cols, stride, i0, i1, W, d0, d1);
+            memcpy(out + 32 * i0, d0, 32);
+            if (two) memcpy(out + 32 * i1, d1, 32);
+        }
 }
 extern "C" void emu_hash_bytes(const uint8_t *msg, size_t len, uint8_t *out) {
     uint32_t d[8];

@@ -7,6 +7,8 @@
 // device's atomic minimum does.  Same arguments and statuses as the C ABI, with (p, g) in place of a context.
 // The periodic tables are laid out by air_periodic_plan (air_core.h) and filled with the emulator's own transforms
 // (emu_ntt: an inverse transform per group, then a forward one on the group's coset), not with anything of the GPU path.
+// emu_air_row_open runs air_row_open_kernel's grid -- one workgroup of 64 lanes per (test, position) -- over the record
+// writer both share (mgpu_core.h mg_row_open_write).
 // There is no emu_air_prove / emu_air_verify: the emulator has no single-device Fri::prove loop to continue a
 // transcript with (emu_mgpu.cpp emulates the multi-GPU round loop only), and the verifier is host code already.
 #include <string.h>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "air_core.h"
+#include "mgpu_core.h"
 #include "tables.h"
 
 extern "C" int emu_ntt(uint64_t p, uint64_t g, const uint32_t *in, uint32_t *out, uint32_t L, uint32_t n_in, uint32_t batch, uint64_t in_stride,
@@ -112,4 +115,15 @@ extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, ui
         if (row) *row = first & 0xffffffffull;
     }
     return SMI_OK;
+}
+
+// air_row_open_kernel (air.hip): grid (t, R), 64 lanes; -> the bytes of the opening section
+extern "C" uint64_t emu_air_row_open(const uint32_t *cols, uint64_t stride, uint32_t W, const uint8_t *nodes, uint64_t N, const uint64_t *top,
+                                     uint32_t t, uint32_t R, uint64_t B, uint8_t *out) {
+    uint32_t depth = 0;
+    while ((1ull << depth) < N) depth++;
+    for (uint32_t s = 0; s < t; s++)
+        for (uint32_t k = 0; k < R; k++)
+            for (uint32_t lane = 0; lane < 64; lane++) mg_row_open_write(cols, stride, W, nodes, depth, top[s], s, k, t, out, lane, 64, R, B);
+    return mg_row_open_bytes(W, t, depth, R);
 }

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(SMI_HASH_THREADS) void merkle_sub_kernel(const uint
     }
     if (FROM_ELEMS && ROWS && row_cols) {
         // row leaves: leaf i = Hash::from_field_elements(row i) over row_cols <= 4 columns row_stride
-        // apart (wider rows are hashed by row_hash_kernel and enter as digests)
+        // apart (wider rows are hashed by row_hash_wide_kernel and enter as digests)
         for (uint32_t i = 0; i < per; i += 2) {
             uint32_t d0[8], d1[8];
             if (i + 1 < per) {
@@ -391,16 +391,26 @@ int launch_fri_tail(smi_ctx *ctx, const FriTailArgs &a) {
     return SMI_OK;
 }
 
-// digests of rows of any width (the fused kernels above take rows of up to 4 columns)
-__global__ __launch_bounds__(SMI_HASH_THREADS) void row_hash_kernel(const uint32_t *__restrict__ cols, uint32_t n_cols, size_t stride,
-                                                                      uint4 *out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * SMI_HASH_THREADS + threadIdx.x;
-    if (i >= n) return;
-    uint32_t row[SMI_ROW_MAX], d[8];
-    for (uint32_t c = 0; c < n_cols; c++) row[c] = cols[c * stride + i];
-    hashc::row_hash(row, (int)n_cols, d);
-    out[2 * i] = make_uint4(d[0], d[1], d[2], d[3]);
-    out[2 * i + 1] = make_uint4(d[4], d[5], d[6], d[7]);
+// Digests of rows of 5 .. SMI_ROW_MAX columns (the fused kernels above take rows of up to 4): hashc::row_hash_wide2,
+// two rows per lane in the paired-lane state, the columns streamed four at a time with the next chunk's eight loads
+// issued before the current chunk's mix (~88 VALU instructions per hash to wait under).  No per-thread array is indexed
+// by a run-time value, so nothing goes to scratch and the register count does not depend on the width.  A workgroup owns
+// 2 * SMI_HASH_THREADS consecutive rows (row_wide_pair): every load of a wave reads 64 consecutive words of one column.
+// Floors: 4 W n + 32 n bytes; (ceil(W / 4) + 8) n mixes.  The second launch bound asks for the eight waves per SIMD the
+// other Merkle kernels run at: 59 VGPRs instead of 65 (one over the step to seven waves), no scratch either way.
+__global__ __launch_bounds__(SMI_HASH_THREADS, 8) void row_hash_wide_kernel(const uint32_t *__restrict__ cols, uint32_t n_cols, size_t stride,
+                                                                           uint4 *out, size_t n) {
+    size_t i0, i1;
+    bool two;
+    if (!hashc::row_wide_pair(blockIdx.x, threadIdx.x, SMI_HASH_THREADS, n, &i0, &i1, &two)) return;
+    uint32_t d0[8], d1[8];
+    hashc::row_hash_wide2(cols, stride, i0, i1, (int)n_cols, d0, d1);
+    out[2 * i0] = make_uint4(d0[0], d0[1], d0[2], d0[3]);
+    out[2 * i0 + 1] = make_uint4(d0[4], d0[5], d0[6], d0[7]);
+    if (two) {
+        out[2 * i1] = make_uint4(d1[0], d1[1], d1[2], d1[3]);
+        out[2 * i1 + 1] = make_uint4(d1[4], d1[5], d1[6], d1[7]);
+    }
 }
 
 // digests only (Hash::from_field_elements per element)
@@ -627,8 +637,11 @@ int launch_merkle_src_fs(smi_ctx *ctx, const LeafSrc &src, size_t n, uint8_t *d_
 int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes) {
     if (!n_cols || n_cols > SMI_ROW_MAX) return smi_fail(ctx, SMI_ERR_BAD_ARG, "row leaves: 1..64 columns");
     if (n_cols <= 4) return launch_merkle_batch(ctx, d_cols, n, d_nodes, 1, 0, 0, n_cols, col_stride);
-    row_hash_kernel<<<blocks_for(n), SMI_HASH_THREADS, 0, ctx->stream>>>(d_cols, n_cols, col_stride, (uint4 *)d_nodes, n);
-    HIP_TRY(ctx, hipGetLastError());
+    {
+        ProfScope ps(ctx, "row_hash_wide_kernel", 4.0 * n_cols * (double)n + 32.0 * (double)n, ((n_cols + 3) / 4 + 8.0) * (double)n);
+        row_hash_wide_kernel<<<blocks_for((n + 1) / 2), SMI_HASH_THREADS, 0, ctx->stream>>>(d_cols, n_cols, col_stride, (uint4 *)d_nodes, n);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     return launch_merkle_batch(ctx, nullptr, n, d_nodes, 1, 0, 0);
 }
 // n_trees equally sized trees in one set of launches.  The small upper levels of all trees share their launch latency.

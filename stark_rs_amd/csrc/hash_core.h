@@ -668,6 +668,89 @@ SMI_HD void row_hash2(const uint32_t *v0, const uint32_t *v1, int W, uint32_t d0
     to_words2(st, d0, d1);
 }
 
+// ---- rows of any width, two per lane, the columns streamed four at a time (hash.hip row_hash_wide_kernel and the
+// emulator's emu_row_hash_wide run exactly this).  Nothing here is indexed by a run-time value: a chunk lives in four
+// named registers per row, the width of the short last chunk is dispatched to compile-time counts, and the loop over
+// the full chunks is not unrolled, so the register count does not depend on W.
+//
+// Which two rows lane `tid` of workgroup `block` hashes.  A workgroup of T lanes owns 2T consecutive rows and a lane
+// takes rows base + tid and base + h + tid, h = T (or half the tree when it has fewer than 2T rows): the 64 lanes of a
+// wave read 64 consecutive words of a column with every load, for either row.  n is a power of two; with n == 1 the
+// one active lane hashes row 0 in both halves of its state and stores it once (*two = false).
+SMI_HD bool row_wide_pair(size_t block, uint32_t tid, uint32_t T, size_t n, size_t *i0, size_t *i1, bool *two) {
+    const size_t base = block * 2 * (size_t)T;
+    if (base >= n) return false;
+    const size_t span = n - base < 2 * (size_t)T ? n - base : 2 * (size_t)T;   // a power of two
+    const size_t h = span > 1 ? span / 2 : 1;
+    if (tid >= h) return false;
+    *two = span > 1;
+    *i0 = base + tid;
+    *i1 = *two ? base + h + tid : base + tid;
+    return true;
+}
+// columns c0 .. c0 + 3 of rows i0 and i1.  Every chunk issues its eight loads unconditionally -- a column at or beyond W
+// reads column W - 1 once more (the line is in cache: this lane has just read it) and its word is zeroed afterwards --
+// so the number of loads in flight is a compile-time constant and the wait before a chunk's first use leaves the next
+// chunk's loads outstanding; loads under a per-column branch would make the compiler drain them all.
+SMI_HD void row_wide_load(const uint32_t *__restrict__ cols, size_t stride, size_t i0, size_t i1, int c0, int W, uint32_t (&a)[4],
+                          uint32_t (&b)[4]) {
+    uint32_t va[4], vb[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int c = c0 + j < W ? c0 + j : W - 1;
+        const uint32_t *col = cols + (size_t)c * stride;
+        va[j] = col[i0];
+        vb[j] = col[i1];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        a[j] = c0 + j < W ? va[j] : 0u;
+        b[j] = c0 + j < W ? vb[j] : 0u;
+    }
+}
+template <int COUNT> SMI_HD void row_wide_absorb(const uint32_t (&a)[4], const uint32_t (&b)[4], uint32_t X[8], uint32_t Y[8]) {
+    row_chunk_words(a, COUNT, X);
+    row_chunk_words(b, COUNT, Y);
+}
+// digests of rows i0 and i1 of W >= 1 columns `stride` apart: hashc::row_hash of each, bit for bit
+SMI_HD void row_hash_wide2(const uint32_t *__restrict__ cols, size_t stride, size_t i0, size_t i1, int W, uint32_t d0[8], uint32_t d1[8]) {
+    constexpr InitWords I = make_init_words();
+    uint32_t X[8], Y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) X[j] = Y[j] = I.p[j];
+    const MixK K = mix_consts();
+    State2 st;
+    const int chunks = (W + 3) >> 2;
+    uint32_t a[4], b[4];
+    row_wide_load(cols, stride, i0, i1, 0, W, a, b);
+#pragma unroll 1
+    for (int ch = 0; ch + 1 < chunks; ch++) {   // the full chunks that another chunk follows
+        uint32_t na[4], nb[4];
+        row_wide_load(cols, stride, i0, i1, 4 * ch + 4, W, na, nb);   // in flight under this chunk's absorb and mix
+        row_wide_absorb<4>(a, b, X, Y);
+        from_words2(X, Y, st);
+        mix2(st, K);
+        to_words2(st, X, Y);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            a[j] = na[j];
+            b[j] = nb[j];
+        }
+    }
+    switch (W - 4 * (chunks - 1)) {   // the last chunk, 1 .. 4 elements: wave-uniform
+        case 1: row_wide_absorb<1>(a, b, X, Y); break;
+        case 2: row_wide_absorb<2>(a, b, X, Y); break;
+        case 3: row_wide_absorb<3>(a, b, X, Y); break;
+        default: row_wide_absorb<4>(a, b, X, Y); break;
+    }
+    from_words2(X, Y, st);
+    mix2_t<false>(st, K);
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) mix2_t<true>(st, K);
+    flush2(st);
+    to_words2(st, d0, d1);
+}
+
 // Hash::from_bytes for an arbitrary message (src/hash.rs:7-30); single lane, used by the
 // Fiat-Shamir and index-sampling kernels (transcripts of a few hundred bytes).
 SMI_HD void hash_bytes(const uint8_t *msg, size_t len, uint32_t d[8]) {

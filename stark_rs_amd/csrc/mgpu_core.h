@@ -115,6 +115,35 @@ SMI_HD void mg_column_open_write(const MgSide *cols, uint32_t W, uint32_t c, uin
     mg_column_open_write_n(cols, W, c, top_index, s, t, rank, out, lane, n_lanes, 2, 0);
 }
 
+// Row openings of ONE tree over the rows of W columns (smi_dev_air_prove_rows): the rows as above, then one path per
+// opened position instead of one per (position, column):
+//   rows : t x R records  tag 2 | u64 W | W x u64
+//   paths: t x R records  tag 3 | u64 depth | depth x 32       (test s, inside it the positions in the rows' order)
+// Single device: the tree (`nodes`, every level back to back, N = 2^depth leaves) and the columns (`stride` apart) are whole.
+SMI_HD uint64_t mg_row_open_bytes(uint32_t W, uint32_t t, uint32_t depth, uint32_t R) {
+    return (uint64_t)t * R * (9 + 8ull * W) + (uint64_t)t * R * (9 + 32ull * depth);
+}
+// record k (position k of a, b, (a + shift) mod N, (b + shift) mod N) of test s, by n_lanes cooperating lanes
+SMI_HD void mg_row_open_write(const uint32_t *cols, uint64_t stride, uint32_t W, const uint8_t *nodes, uint32_t depth, uint64_t top_index,
+                              uint32_t s, uint32_t k, uint32_t t, uint8_t *out, uint32_t lane, uint32_t n_lanes, uint32_t R, uint64_t shift) {
+    const uint64_t N = 1ull << depth, half = N / 2, a = top_index % half, rec = 9 + 8ull * W, prec = 9 + 32ull * depth;
+    const uint64_t pos = ((k & 1 ? a + half : a) + (k & 2 ? shift : 0)) & (N - 1);
+    uint8_t *row = out + ((uint64_t)s * R + k) * rec;
+    uint8_t *path = out + (uint64_t)t * R * rec + ((uint64_t)s * R + k) * prec;
+    if (lane == 0) {
+        row[0] = 2;
+        mg_put_u64(row + 1, W);
+        path[0] = 3;
+        mg_put_u64(path + 1, depth);
+    }
+    for (uint32_t c = lane; c < W; c += n_lanes) mg_put_u64(row + 9 + 8ull * c, cols[c * stride + pos]);
+    for (uint32_t q = lane; q < 32 * depth; q += n_lanes) {   // byte q & 31 of the sibling on level q >> 5 (level l starts at 2N - (2N >> l))
+        const uint32_t l = q >> 5;
+        const uint64_t sib = (pos >> l) ^ 1;
+        path[9 + q] = nodes[(2 * N - ((2 * N) >> l) + sib) * 32 + (q & 31)];
+    }
+}
+
 // column_open_kernel on the context's stream (stark.hip; mgpu.hip and air.hip call it too)
 struct smi_ctx;
 int launch_column_open(smi_ctx *ctx, const MgSide *d_cols, uint32_t W, const uint64_t *d_top, uint32_t t, int rank, uint8_t *d_out);

@@ -335,17 +335,13 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
     return SMI_OK;
 }
 
-// Verifier of smi_dev_air_prove (include/stark_mi.h, "AIR"): the weights and FRI's seed from the transcript of the
-// column roots and the constraint indices, Fri::verify at expansion factor E, then the openings -- length, rows,
-// every path against its column root, and the composition codeword recomputed at x_a and x_b with the evaluator
-// the prover's kernel runs (air_core.h) over the opened rows.
-int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const uint8_t *column_roots, const uint8_t *proof,
-                   size_t proof_len, int *accept) {
-    const smi_air *air = (const smi_air *)air_;
-    if (!ctx || !cfg || !air || !column_roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
-    DeviceGuard dg__(ctx);
-    *accept = 0;
-    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_verify: column trees only (row_leaves must be 0)");
+// Verifier of smi_dev_air_prove and smi_dev_air_prove_rows (include/stark_mi.h, "AIR"): the weights and FRI's seed from
+// the variant's transcript, Fri::verify at expansion factor E, then the openings -- length, rows, every path against its
+// root (W column roots, or the one root of the tree over the rows), and the composition codeword recomputed at x_a and
+// x_b with the evaluator the prover's kernel runs (air_core.h) over the opened rows.  Only the transcript and the
+// authentication of the opened rows differ between the two commitments; everything else is this one function.
+static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint8_t *column_roots, const uint8_t *proof,
+                           size_t proof_len, int *accept, bool by_rows) {
     std::string why;
     uint64_t E = 0;
     const int vrc = air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
@@ -359,16 +355,28 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
     fc.domain_length = N;
     fc.expansion_factor = E;
     fc.num_colinearity_tests = t;
-    // transcript: root c, weight c; then k as 8 LE bytes, weight W + k
+    // transcript.  Column trees: root c, weight c; then k as 8 LE bytes, weight W + k.  Row tree: the root; then j = 0 ..
+    // W + K - 1 as 8 LE bytes, weight j.
     std::vector<uint64_t> weights(W + K);
     std::vector<uint8_t> transcript;
-    for (uint32_t c = 0; c < W; c++) {
-        transcript.insert(transcript.end(), column_roots + 32 * c, column_roots + 32 * c + 32);
-        SMI_TRY(challenge_of(ctx, transcript, &weights[c]));
-    }
-    for (uint32_t k = 0; k < K; k++) {
-        for (int i = 0; i < 8; i++) transcript.push_back((uint8_t)((uint64_t)k >> (8 * i)));
-        SMI_TRY(challenge_of(ctx, transcript, &weights[W + k]));
+    auto absorb_index = [&](uint64_t j) {
+        for (int i = 0; i < 8; i++) transcript.push_back((uint8_t)(j >> (8 * i)));
+    };
+    if (by_rows) {
+        transcript.assign(column_roots, column_roots + 32);
+        for (uint32_t j = 0; j < W + K; j++) {
+            absorb_index(j);
+            SMI_TRY(challenge_of(ctx, transcript, &weights[j]));
+        }
+    } else {
+        for (uint32_t c = 0; c < W; c++) {
+            transcript.insert(transcript.end(), column_roots + 32 * c, column_roots + 32 * c + 32);
+            SMI_TRY(challenge_of(ctx, transcript, &weights[c]));
+        }
+        for (uint32_t k = 0; k < K; k++) {
+            absorb_index(k);
+            SMI_TRY(challenge_of(ctx, transcript, &weights[W + k]));
+        }
     }
     FsSeed seed;
     hashc::fs_seed(transcript.data(), transcript.size(), seed.s, &seed.phase);
@@ -379,7 +387,7 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
     SMI_TRY(fri_verify_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
     if (!*accept) return SMI_OK;
     *accept = 0;
-    const size_t R = K ? 4 : 2, rec = 9 + 8 * (size_t)W, prec = 9 + 32 * (size_t)logN, need = t * R * rec + t * W * R * prec;
+    const size_t R = K ? 4 : 2, rec = 9 + 8 * (size_t)W, prec = 9 + 32 * (size_t)logN, need = t * R * rec + t * (by_rows ? 1 : W) * R * prec;
     if (proof_len - end != need) return reject(ctx, accept, "air openings: wrong length");
     const uint8_t *ext = proof + end, *pathsb = ext + t * R * rec;
     const uint64_t half = N / 2;
@@ -394,7 +402,23 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
             for (uint32_t c = 0; c < W; c++) rows[(R * s + k) * W + c] = get_u64(r + 9 + 8 * c);
         }
     }
-    for (uint32_t c = 0; c < W; c++) {
+    if (by_rows) {
+        // one path per opened row; its leaf is the hash of the row's 8 W bytes as they stand in the proof
+        const size_t m = R * t;
+        std::vector<uint8_t> paths(m * 32 * (size_t)logN), leaf(32 * (m ? m : 1)), ok(m ? m : 1);
+        for (size_t q = 0; q < m; q++) {
+            const uint8_t *pr = pathsb + q * prec;
+            if (pr[0] != 3 || get_u64(pr + 1) != logN) return reject(ctx, accept, "air openings: malformed path");
+            memcpy(&paths[q * 32 * (size_t)logN], pr + 9, 32 * (size_t)logN);
+            uint32_t d[8];
+            hashc::hash_bytes(ext + q * rec + 9, 8 * (size_t)W, d);
+            memcpy(&leaf[32 * q], d, 32);
+        }
+        if (m) SMI_TRY(smi_merkle_verify_batch(ctx, leaf.data(), pos.data(), paths.data(), m, logN, column_roots, ok.data()));
+        for (size_t q = 0; q < m; q++)
+            if (!ok[q]) return reject(ctx, accept, "air openings: authentication path does not verify");
+    }
+    for (uint32_t c = 0; c < W && !by_rows; c++) {
         const size_t m = R * t;
         std::vector<uint64_t> vals(m);
         std::vector<uint8_t> paths(m * 32 * (size_t)logN), leaf, ok(m ? m : 1);
@@ -447,4 +471,21 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, con
         }
     *accept = 1;
     return SMI_OK;
+}
+
+int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *column_roots, const uint8_t *proof,
+                   size_t proof_len, int *accept) {
+    if (!ctx || !cfg || !air || !column_roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_verify: column trees only (row_leaves must be 0; smi_air_verify_rows checks a proof over one row tree)");
+    return air_verify_impl(ctx, cfg, (const smi_air *)air, column_roots, proof, proof_len, accept, false);
+}
+
+int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                        size_t proof_len, int *accept) {
+    if (!ctx || !cfg || !air || !row_root || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true);
 }

@@ -437,8 +437,8 @@ class Engine:
     def _air(self, air):
         return air if isinstance(air, _lib.Air) else air.flatten(self.p)
 
-    def _stark_cfg(self, n_cols, log_n, log_blowup, num_colinearity_tests=0, trace_offset=1, lde_offset=None):
-        return _lib.StarkCfg(log_n, log_blowup, n_cols, 0, trace_offset, self.g if lde_offset is None else lde_offset,
+    def _stark_cfg(self, n_cols, log_n, log_blowup, num_colinearity_tests=0, trace_offset=1, lde_offset=None, row_leaves=False):
+        return _lib.StarkCfg(log_n, log_blowup, n_cols, 1 if row_leaves else 0, trace_offset, self.g if lde_offset is None else lde_offset,
                              num_colinearity_tests, 1)
 
     def air_plan(self, air, n_cols, log_n, log_blowup, trace_offset=1, lde_offset=None):
@@ -463,20 +463,23 @@ class Engine:
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True):
+                      timed=False, check=True, row_leaves=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
-        dev_air_check first and raises StarkMiError naming the first violated constraint and row."""
+        dev_air_check first and raises StarkMiError naming the first violated constraint and row.
+        row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
+        one root, shape (1, 32), and the proof opens every queried position once (verify with row_leaves=True)."""
         a = self._air(air)
         if check:
             ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
             if not ok:
                 raise StarkMiError(-50, why)   # SMI_ERR_BAD_ARG: the trace handed in does not satisfy the AIR
-        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset)
-        roots = np.zeros((n_cols, 32), dtype=np.uint8)
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, row_leaves)
+        roots = np.zeros((1 if row_leaves else n_cols, 32), dtype=np.uint8)
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
         stage = (C.c_double * 5)()
-        self._ck(self.L.smi_dev_air_prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof),
+        prove = self.L.smi_dev_air_prove_rows if row_leaves else self.L.smi_dev_air_prove
+        self._ck(prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof),
                                           C.byref(plen), top.ctypes.data, stage if timed else None))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
@@ -486,13 +489,17 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None):
-        """verifier of dev_air_prove -> (accept, reason)"""
-        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset)
+                   lde_offset=None, row_leaves=False):
+        """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
+        the tree over the rows"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, row_leaves)
         a = self._air(air)
         roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
         acc = C.c_int()
-        self._ck(self.L.smi_air_verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc)))
+        verify = self.L.smi_air_verify_rows if row_leaves else self.L.smi_air_verify
+        if row_leaves and roots.size != 32:
+            raise StarkMiError(-50, "air_verify(row_leaves=True) takes the one 32-byte root of the row tree")
+        self._ck(verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc)))
         return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
 
 

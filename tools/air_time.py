@@ -13,7 +13,10 @@ achieved bytes/s of 4 (W + 1) N against an in-run device-to-device copy moving t
 prove: median wall time of nine smi_dev_air_prove(empty) / smi_dev_stark_prove(open_columns = 1) calls on one trace.
 periodic: four lanes x' = (x + k)^3 at (n = 2^22, B = 8), (a) the constants as periodic columns (W = 4, Q = 4, period 64 and
 period n) and (b) as four more trace columns (W = 8, Q = 0): compose kernel time, prove wall time and stages.  --no-periodic
-leaves (a) out: what a library without periodic columns (SMI_LIB) can run."""
+leaves (a) out: what a library without periodic columns (SMI_LIB) can run.
+rows: smi_dev_air_prove_rows beside smi_dev_air_prove on the same trace -- empty and mixer at (W = 4, n = 2^22) and the
+32-constraint AIR at (W = 64, n = 2^18): median of nine calls, the five stages and the proof length of both.  --no-rows leaves
+them out: what a library without the row-committed entry points can run."""
 import argparse
 import os
 import statistics
@@ -30,6 +33,8 @@ ap.add_argument("--single", action="store_true", help="one launch per AIR at (W 
                 "`rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES` (the k-th air_compose_kernel dispatch is the k-th AIR printed)")
 ap.add_argument("--no-periodic", action="store_true", help="skip the legs that need periodic columns")
 ap.add_argument("--no-stark", action="store_true", help="skip smi_dev_stark_prove")
+ap.add_argument("--no-rows", action="store_true", help="skip the smi_dev_air_prove_rows legs")
+ap.add_argument("--rows-only", action="store_true", help="only the column-tree / row-tree prove pairs")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 import torch  # noqa: E402
@@ -125,7 +130,7 @@ if args.single:
     eng.close()
     sys.exit(0)
 
-if not args.stark_only:
+if not args.stark_only and not args.rows_only:
     for W, log_n, lb, cases in [(4, 22, 3, None), (64, 18, 3, "wide")]:
         n, N = 1 << log_n, 1 << (log_n + lb)
         lde, out = rand_cols(W, N), torch.empty(N, dtype=torch.int32, device=dev)
@@ -160,6 +165,29 @@ def wall(fn):
     runs.sort(key=lambda x: x[0])
     return runs
 
+
+def prove_pair(label, flat, tr, Wl, ln):
+    """column trees and, unless --no-rows, the row tree: the same statement on the same trace, one after the other"""
+    for variant in ("columns",) + (() if args.no_rows else ("rows",)):
+        runs = wall(lambda: eng.dev_air_prove(flat, tr.data_ptr(), Wl, ln, lb, t, timed=True, check=False, **({"row_leaves": True} if variant == "rows" else {})))
+        med = runs[4]
+        print(f"air_prove[{variant:7s}] {label:26s} W={Wl} n=2^{ln}: median {med[0]:.3f} ms (min {runs[0][0]:.3f}, max {runs[-1][0]:.3f})  "
+              f"stages {({k: round(v, 3) for k, v in med[1]['stage_ms'].items()})}  proof {len(med[1]['proof'])} bytes", flush=True)
+
+
+def pair_legs():
+    from stark_rs_amd.mirror import Air
+    prove_pair("empty", Air(W).flatten(p), trace, W, log_n)
+    prove_pair("mixer, any trace", airs(W, 1 << log_n)[2][1].flatten(p), trace, W, log_n)
+    wide_trace = rand_cols(64, 1 << 18)
+    torch.cuda.synchronize()
+    prove_pair("32 constraints", wide(64, 32, 1 << 18).flatten(p), wide_trace, 64, 18)
+
+
+if args.rows_only:
+    pair_legs()
+    eng.close()
+    sys.exit(0)
 
 if not args.no_stark:
     runs = wall(lambda: eng.dev_stark_prove(trace.data_ptr(), W, log_n, lb, t, timed=True, open_columns=True))
@@ -196,4 +224,6 @@ if not args.stark_only:
         del lde, out
         runs = wall(lambda: eng.dev_air_prove(flat, tr.data_ptr(), Wl, log_n, lb, t, timed=True, check=False))
         print(f"air_prove {name:34s}: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
+if not args.stark_only and not args.no_rows:
+    pair_legs()
 eng.close()

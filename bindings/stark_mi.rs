@@ -210,6 +210,14 @@ extern "C" {
     pub fn smi_air_verify(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, column_roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
     pub fn smi_dev_air_prove_rows(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
     pub fn smi_air_verify_rows(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
+    pub fn smi_ext_mul(p: u64, g: u64, a: *const u64, b: *const u64, out: *mut u64) -> c_int;
+    pub fn smi_ext_inv(p: u64, g: u64, a: *const u64, out: *mut u64) -> c_int;
+    pub fn smi_dev_fri_fold_ext(ctx: *mut smi_ctx, d_in: *const u32, len: usize, stride: usize, d_alpha: *const u64, offset: u64, omega: u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_compose_ext(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_lde: *const u32, stride: usize, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_fri_prove_ext(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_codeword: *const u32, len: usize, stride: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64) -> c_int;
+    pub fn smi_fri_verify_ext(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize) -> c_int;
+    pub fn smi_dev_air_prove_ext(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
+    pub fn smi_air_verify_ext(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -783,6 +791,36 @@ impl Air {
         let mut accept = 0 as c_int;
         ctx.check(self.with_raw(|a| unsafe {
             smi_air_verify_rows(ctx.raw, cfg, a, row_root.as_ptr(), proof.as_ptr(), proof.len(), &mut accept)
+        }));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+    /// `smi_dev_air_prove_ext` -> (root of the one tree over the rows, proof bytes): the row-committed proof with the
+    /// composition weights and FRI's challenges drawn from the quartic extension.  `check_trace` as in `prove`.
+    pub fn prove_ext(&self, ctx: &Context, cfg: &smi_stark_cfg, d_trace_cols: *const u32, check_trace: bool) -> ([u8; 32], Vec<u8>) {
+        if check_trace {
+            if let Some((con, row)) = self.check_trace(ctx, cfg.log_n, d_trace_cols) {
+                let why = unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned();
+                panic!("the trace violates constraint {} at row {}: {}", con, row, why);
+            }
+        }
+        let mut root = [0u8; 32];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_dev_air_prove_ext(ctx.raw, cfg, a, d_trace_cols, root.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut())
+        }));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (root, bytes)
+    }
+    /// `smi_air_verify_ext` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify_ext(&self, ctx: &Context, cfg: &smi_stark_cfg, row_root: &[u8; 32], proof: &[u8]) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_air_verify_ext(ctx.raw, cfg, a, row_root.as_ptr(), proof.as_ptr(), proof.len(), &mut accept)
         }));
         if accept != 0 {
             Ok(())

@@ -422,9 +422,10 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
  *
  * Out of scope: row shifts other than 0 and 1; zero-knowledge randomisers; degree-adjusted terms
  * (alpha + beta * x^shift); binding a digest of the AIR (coefficients, boundary values, periodic values) into the
- * transcript; keeping the periodic tables on the device between calls; an extension
- * field (with a 30-bit modulus the soundness of any proof from this library is bounded by the field, the reference's
- * choice); a multi-GPU twin.
+ * transcript; keeping the periodic tables on the device between calls; a multi-GPU twin.  The proofs of the entry
+ * points of this section and the next draw every challenge from F_p: with a 30-bit modulus (the reference's choice) their
+ * soundness is bounded by the field.  "Quartic extension" below has the field, the fold and the composition that lift the
+ * challenges to 116 bits (smi_dev_air_prove_ext / smi_air_verify_ext), and lists what it leaves out.
  *
  * The entry points take the description as `const void *air` (a pointer to an smi_air): every parameter type of this
  * header is a scalar, a pointer to one, or one of the handle / configuration types the bindings already know. */
@@ -517,6 +518,102 @@ int smi_dev_air_prove_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms);
 int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
                         size_t proof_len, int *accept);
+
+/* ---- Quartic extension: 116-bit challenges -----------------------------------------------------
+ * The reference draws every challenge from F_p.  The standard remedy over a small NTT-friendly prime keeps the trace and
+ * its commitment in the base field and takes the verifier's challenges -- the composition weights, the FRI folding
+ * challenges -- from an extension; the composition codeword and FRI then live there.  This section has the field, FRI over
+ * it and the AIR proof with weights from it; the entry points above are unchanged, byte for byte.
+ *
+ * The field.  F_q = F_p[X] / (X^4 - g) with p and g the context's; an element is four canonical residues c0 .. c3, low
+ *   degree first: c0 + c1 X + c2 X^2 + c3 X^3.  X^4 - g is irreducible when p = 1 (mod 4) and g^((p-1)/2) = -1, which
+ *   holds for both project primes with g = 3; q is 2^119.6 for 998244353 and 2^115.2 for 469762049.  Every entry point of
+ *   this section refuses a p that is 3 (mod 4) or a g that is a square: SMI_ERR_BAD_ARG, the reason in smi_last_error
+ *   (smi_ctx_create accepts neither today -- it wants 2^12 | p - 1 and a g of full 2-power order --, so through a context
+ *   the check is a guard; smi_ext_mul and smi_ext_inv take any p and g and meet it).
+ * Layout.  An extension codeword of L elements on the device is four coordinate columns of L u32 residues, `stride`
+ *   elements apart: coordinate e of element i at d[e * stride + i].  That is the shape smi_dev_merkle_build_rows(n_cols = 4,
+ *   col_stride = stride) hashes, so leaf i of its tree is Hash::from_field_elements([c0, c1, c2, c3]) of element i and costs
+ *   the 9 mixes a base-field leaf costs.  The coordinates of a codeword are base-field codewords on the same domain:
+ *   smi_dev_lde, smi_dev_ntt and a degree check apply coordinate by coordinate.  On the host an element is four
+ *   consecutive u64.
+ * Left out: the column-tree variant of the AIR proof; any smi_mgpu_* twin; committed extension-field columns (an
+ *   auxiliary trace); out-of-domain sampling; zero-knowledge randomisers; binding an AIR digest into the transcript; the
+ *   fold fused into the launch that hashes the row leaves (the base-field path's LEAF_FOLD) and a fused tail. */
+#define SMI_EXT_DEGREE 4
+/* Host only, no context (like smi_air_plan): out = a * b and out = a^-1 in F_q, coordinates canonical.  SMI_ERR_BAD_ARG
+ * for a (p, g) the section refuses (p not a prime < 2^31 that is 1 mod 4, g a square or outside 1 .. p-1),
+ * SMI_ERR_NON_CANONICAL for a coordinate >= p, SMI_ERR_NO_INVERSE ("no inverse", src/ff.rs:171) for smi_ext_inv of zero.
+ * out may alias an input. */
+int smi_ext_mul(uint64_t p, uint64_t g, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]);
+int smi_ext_inv(uint64_t p, uint64_t g, const uint64_t a[4], uint64_t out[4]);
+/* Fri::fold_codeword (src/fri.rs:57-91) over F_q.  d_in: an extension codeword of len elements (a power of two, 2 ..
+ * 2^27) on offset * <omega>, coordinate columns stride >= len apart; d_alpha: the challenge's four coordinates as
+ * unreduced u64 on the device, used mod p; d_out: len / 2 elements, columns out_stride >= len / 2 apart, not
+ * overlapping d_in.  With lo = element i, hi = element i + len / 2 and x_i = offset * omega^i in F_p,
+ *   out[i] = 2^-1 (lo + hi) + alpha * ((lo - hi) * 2^-1 * x_i^-1),
+ * the product by alpha a full F_q product (16 multiplies and 4 reductions).  With alpha = (a, 0, 0, 0) every coordinate
+ * is smi_dev_fri_fold of that coordinate.  16-byte accesses when d_in and d_out are 16-byte aligned and stride,
+ * out_stride and len / 2 are multiples of 4; 4-byte accesses otherwise, same values.  Statuses as smi_dev_fri_fold. */
+int smi_dev_fri_fold_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset,
+                         uint64_t omega, uint32_t *d_out, size_t out_stride);
+/* The composition codeword of "AIR" above under weights from F_q.  d_weights: 4 (n_cols + n_constraints) unreduced u64
+ * on the device, coordinate e of weight j at 4 j + e (column c has j = c, constraint k has j = n_cols + k); d_out: four
+ * coordinate columns of N elements, out_stride >= N apart.  term_c and tq_k are base-field values, so
+ *   cw_e[i] = sum_c (w_{c,e} mod p) * term_c(x_i) + sum_k (w_{W+k,e} mod p) * tq_k(x_i)      for e = 0 .. 3:
+ * coordinate e is what smi_dev_air_compose returns for the weight vector (w_{.,e}), bit for bit.  One launch evaluates
+ * every quotient once per point and adds it into four accumulators, where four launches of smi_dev_air_compose read the
+ * columns and walk the constraints four times.  Limits, statuses, periodic columns and the conditions of the tiled
+ * kernel as for smi_dev_air_compose. */
+int smi_dev_air_compose_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_lde, size_t stride,
+                            const uint64_t *d_weights, uint32_t *d_out, size_t out_stride);
+
+/* Extension FRI.  Fri::commit / Fri::prove / Fri::verify (src/fri.rs:105-156, 250-311, 313-504) with codewords over
+ * F_q.  The domain, the number of rounds (smi_fri_num_rounds), index sampling (src/fri.rs:168-213) and the authentication
+ * paths are the reference's.  The differences:
+ * Commitment.  Round r's tree is the row-leaf tree of its codeword (Layout above): one tree, 9 mixes a leaf.
+ * Transcript.  The caller's prefix (any length, as in the *_fs calls); every round absorbs its root (32 bytes); on every
+ *   round but the last, for e = 0 .. 3, the round then absorbs e as 8 little-endian bytes and takes challenge(): coordinate
+ *   e of that round's alpha as an unreduced u64, used mod p.  The last round absorbs nothing after its root (the prover
+ *   breaks before alpha, src/fri.rs:133-135).  The index seed is challenge() of the transcript as it then stands,
+ *   through Hash::from_u64 as in src/fri.rs:272.  A round adds 64 bytes: the transcript's length mod 32 never changes.
+ * Fold.  smi_dev_fri_fold_ext, the domain squared from round to round as in src/fri.rs:146-147.
+ * Proof bytes (tags and widths of src/stream.rs:35-64).  R records of tag 0, the roots; one tag-2 record of 4 L_last
+ *   values, the last codeword, element i at positions 4 i .. 4 i + 3; then per layer: per test one tag-2 record of 12
+ *   values -- a, b, c, four coordinates each -- and after the layer's t records the three paths (a, b, c) per test.
+ * Verifier.  The transcript above; the last record holds exactly 4 L_last values, L_last = N >> (R - 1); the row-leaf root
+ *   of the last codeword equals the last root; EACH of its four coordinates, interpolated on the last domain, has degree
+ *   <= L_last / E - 1; for every triple (x_a, a), (-x_a, b), (alpha, c) are colinear over F_q, that is
+ *   (b - a)(alpha - x_a) = (c - a)(x_b - x_a) with x_a, x_b embedded from F_p; every path is checked against a leaf
+ *   hashed from the element's four u64s as they stand in the proof.  A coordinate >= p anywhere is a rejection
+ *   (*accept = 0 with a reason in smi_last_error), not a status.  A base-field proof is rejected here and an extension
+ *   proof by smi_fri_verify_fs: the record widths differ.
+ * smi_dev_fri_prove_ext: d_codeword = len = cfg->domain_length elements, coordinate columns stride >= len apart, len <=
+ *   2^27; transcript = host bytes (NULL, 0: a fresh FiatShamir); *proof is malloc'ed (smi_free); top_indices (optional)
+ *   gets the t top-level indices.  The round loop -- row tree, Fiat-Shamir round, fold -- the query and the emit are
+ *   enqueued without a host round trip; the call synchronises once, for the copy-back.  Statuses as smi_dev_fri_prove_fs.
+ * smi_fri_verify_ext: as smi_fri_verify_fs; pv_values gets FOUR values per entry of pv_indices (room for 8 t values). */
+int smi_dev_fri_prove_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                          size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices);
+int smi_fri_verify_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                       size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed);
+/* AIR with extension weights, over one row-committed tree ("AIR over one row-committed tree" above: the same statement,
+ * commitment, smi_air_plan, limits and status codes; cfg->row_leaves and cfg->open_columns are taken as set).
+ * Transcript.  Empty; absorb the row root; for m = 0 .. 4 (W + K) - 1 absorb m as 8 little-endian bytes and take
+ *   challenge().  Weight j is the element with coordinates challenge[4 j .. 4 j + 3] mod p; column c has j = c, constraint
+ *   k has j = W + k.  Extension FRI continues this transcript of 32 + 32 (W + K) bytes.  Periodic columns stay outside it.
+ * Composition.  smi_dev_air_compose_ext under those weights: four coordinate columns.
+ * Proof bytes.  The extension-FRI objects at expansion factor E; then the opening section of smi_dev_air_prove_rows,
+ *   unchanged: the same rows, the same single path per position, the same length formula.
+ * Verifier.  As smi_air_verify_rows, with the four coordinates of the composition recomputed at x_a and x_b from the
+ *   opened rows and the periodic operands and compared with the layer-0 triple's a and b.  A proof of
+ *   smi_dev_air_prove_rows is rejected here and the other way round: the transcripts differ from the first weight on.
+ * stage_ms as in smi_dev_air_prove_rows.  One host round trip remains, the one smi_dev_air_prove_rows has: the row root
+ * comes back so that the weights and FRI's seed are computed on the host. */
+int smi_dev_air_prove_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms);
+int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                       size_t proof_len, int *accept);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

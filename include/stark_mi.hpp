@@ -125,6 +125,37 @@ inline std::vector<FieldElement> elements_of(const std::vector<uint64_t> &v, con
     for (uint64_t x : v) out.push_back(f.new_element(x));
     return out;
 }
+// An element of F_p[X] / (X^4 - g) (stark_mi.h, "Quartic extension"): four canonical coordinates, low degree first.
+// The reference has no counterpart; products and inverses are the library's host helpers (no GPU involved).
+struct Ext4 {
+    uint64_t c[4];
+    uint64_t p, g;
+    static Ext4 embed(uint64_t v, uint64_t p, uint64_t g) { return Ext4{{v % p, 0, 0, 0}, p, g}; }
+    bool operator==(const Ext4 &o) const { return p == o.p && g == o.g && c[0] == o.c[0] && c[1] == o.c[1] && c[2] == o.c[2] && c[3] == o.c[3]; }
+    bool operator!=(const Ext4 &o) const { return !(*this == o); }
+    Ext4 operator+(const Ext4 &o) const {
+        Ext4 r = *this;
+        for (int e = 0; e < 4; e++) r.c[e] = (c[e] + o.c[e]) % p;
+        return r;
+    }
+    Ext4 operator-(const Ext4 &o) const {
+        Ext4 r = *this;
+        for (int e = 0; e < 4; e++) r.c[e] = (c[e] + p - o.c[e]) % p;
+        return r;
+    }
+    Ext4 operator*(const Ext4 &o) const {
+        Ext4 r = *this;
+        check(smi_ext_mul(p, g, c, o.c, r.c));
+        return r;
+    }
+    Ext4 inv() const {   // "no inverse" for zero, like ff.rs:171
+        Ext4 r = *this;
+        check(smi_ext_inv(p, g, c, r.c));
+        return r;
+    }
+    Ext4 operator/(const Ext4 &o) const { return *this * o.inv(); }
+};
+
 inline uint32_t log2_exact(size_t n) {
     uint32_t l = 0;
     while (((size_t)1 << l) < n) l++;

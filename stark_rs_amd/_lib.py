@@ -177,6 +177,15 @@ def lib():
         "smi_air_verify": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
         "smi_dev_air_prove_rows": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
         "smi_air_verify_rows": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
+        "smi_ext_mul": (i32, [C.c_uint64, C.c_uint64, u64p, u64p, u64p]),
+        "smi_ext_inv": (i32, [C.c_uint64, C.c_uint64, u64p, u64p]),
+        "smi_dev_fri_fold_ext": (i32, [vp, vp, sz, sz, vp, C.c_uint64, C.c_uint64, vp, sz]),
+        "smi_dev_air_compose_ext": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, sz, vp, vp, sz]),
+        "smi_dev_fri_prove_ext": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), vp]),
+        "smi_fri_verify_ext": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32), vp, vp, C.POINTER(sz),
+                                     C.POINTER(sz)]),
+        "smi_dev_air_prove_ext": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
+        "smi_air_verify_ext": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -64,6 +64,49 @@ __global__ __launch_bounds__(AIR_BLOCK) void air_direct_kernel(AirDev A, Fp F, c
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point(A, F, w_m, cols, stride, i, out);
 }
 
+// The composition under weights from the quartic extension: air_compose_kernel's tiling, halo and per-tile x, with
+// 4 (W + K) weights in LDS (coordinate e of weight j at w_m[e * AIR_MAX_WEIGHTS + j], from weights[4 j + e]) and four output
+// columns out_stride apart.  Every quotient is evaluated once per point and added into four accumulators
+// (air_core.h air_compose_points_ext); the floor is one read of the columns and four writes, 4 (W + 4) N bytes.
+template <int P>
+__global__ __launch_bounds__(AIR_BLOCK) void air_compose_ext_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
+                                                                     const uint64_t *__restrict__ weights, uint32_t T,
+                                                                     uint32_t *__restrict__ out, size_t out_stride) {
+    extern __shared__ __align__(16) uint32_t air_lds[];
+    uint32_t *w_m = air_lds, *tile = air_lds + 4 * AIR_MAX_WEIGHTS;
+    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (1u << A.log_B);
+    for (uint32_t i = tid; i < 4 * (A.W + A.K); i += threads) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
+    const uint32_t step_m = mont_pow(A.omega_m, threads, F);
+    const uint64_t tiles = A.N / T;
+    uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, (uint64_t)blockIdx.x * T, F), F);
+    const uint32_t xstride_m = mont_pow(A.omega_m, (uint64_t)gridDim.x * T, F);
+    for (uint64_t tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const uint64_t base = tl * T;
+        __syncthreads();   // the tile of the round before is consumed
+        for (uint32_t c = 0; c < A.W; c++)
+            for (uint32_t e = tid * 4; e < pitch; e += threads * 4)
+                *(uint4 *)(tile + c * pitch + e) = *(const uint4 *)(cols + c * stride + ((base + e) & (A.N - 1)));
+        for (uint32_t j = 0; j < A.Q; j++) {
+            const uint32_t *__restrict__ tb = A.ptab + A.pofs[j];
+            const uint32_t mask = (1u << A.plog[j]) - 1u;
+            for (uint32_t e = tid * 4; e < pitch; e += threads * 4)
+                *(uint4 *)(tile + (A.W + j) * pitch + e) = *(const uint4 *)(tb + ((uint32_t)(base + e) & mask));
+        }
+        __syncthreads();   // tile (and, the first time, the weights) visible
+        air_tile_thread_ext<P>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out, out_stride);
+        xbase_m = mont_mul(xbase_m, xstride_m, F);   // wave-uniform
+    }
+}
+
+__global__ __launch_bounds__(AIR_BLOCK) void air_direct_ext_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
+                                                                    const uint64_t *__restrict__ weights, uint32_t *__restrict__ out, size_t out_stride) {
+    __shared__ uint32_t w_m[4 * AIR_MAX_WEIGHTS];
+    for (uint32_t i = threadIdx.x; i < 4 * (A.W + A.K); i += blockDim.x) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point_ext(A, F, w_m, cols, stride, i, out, out_stride);
+}
+
 // the trace itself: thread i checks boundary point i (i < nb) and the row pair (i, i + 1) (i < n - 1); the first
 // violation in (kind, index, row) order wins an atomic minimum over the key kind << 63 | index << 32 | row
 __global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t nb,
@@ -186,6 +229,34 @@ int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
+
+// air_launch_compose for the extension kernel: four output columns out_stride apart
+int air_launch_compose_ext(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights,
+                           uint32_t *d_out, size_t out_stride) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_blob, H.blob.data(), H.blob.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    air_bind(H, d_blob);
+    const AirDev &A = H.dev;
+    const Fp F = ctx->fs.F;
+    const uint64_t B = 1ull << A.log_B;
+    AirTile tl = air_tile(A.W + A.Q, B, A.N, 4);
+    if (B < 4 || (stride & 3) || (((uintptr_t)d_lde) & 15u)) tl.T = 0;   // 16-byte loads need aligned columns
+    ProfScope ps(ctx, "air_compose_ext_kernel", 4.0 * (A.W + 4.0) * (double)A.N);
+    if (!tl.T) {
+        size_t grid = (size_t)((A.N + AIR_BLOCK - 1) / AIR_BLOCK);
+        if (grid > 4096) grid = 4096;
+        air_direct_ext_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out, out_stride);
+    } else {
+        const uint64_t tiles = A.N / tl.T;
+        const size_t lds = (size_t)4 * AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + B) * 4;
+        const uint64_t cap = (uint64_t)ctx->num_cus * 8;
+        const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
+        if (tl.P == 4) air_compose_ext_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+        else if (tl.P == 2) air_compose_ext_kernel<2><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+        else air_compose_ext_kernel<1><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
 }  // namespace
 
 int smi_air_plan(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint64_t *fri_expansion) {
@@ -207,6 +278,22 @@ int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
     SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
     return air_launch_compose(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out);
+}
+
+int smi_dev_air_compose_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_lde, size_t stride,
+                            const uint64_t *d_weights, uint32_t *d_out, size_t out_stride) {
+    if (!ctx || !cfg || !air || !d_lde || !d_weights || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(ext_field_check(ctx));
+    AirHost H;
+    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr));
+    if (stride < H.dev.N || out_stride < H.dev.N) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose_ext: stride < N or out_stride < N");
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
+    void *base = nullptr;   // tables | grouped values | blob
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
+    return air_launch_compose_ext(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride);
 }
 
 int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t log_n, const uint32_t *d_trace_cols, int *ok,
@@ -267,8 +354,10 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
 // indices, W paths per opened position (smi_dev_air_prove).  rows == true: one tree over the rows, the transcript of its
 // root and the W + K indices, one path per opened position (smi_dev_air_prove_rows).  Everything else -- the extension, the
 // periodic tables, the composition, FRI, the copy-back -- is the same code.
+// ext (with rows): the weights are elements of the quartic extension -- four counters and four challenges per weight --, the
+// composition codeword is four coordinate columns and FRI runs over F_q (smi_dev_air_prove_ext).
 static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
-                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows) {
+                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows, bool ext = false) {
     AirHost H;
     uint64_t E = 0;
     SMI_TRY(air_host(ctx, cfg, air, &H, &E));
@@ -290,8 +379,9 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     const size_t tree_stride = 2 * N * 32;
     const uint32_t n_trees = rows ? 1u : W;
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, N * 4);
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * (size_t)(W + K));
+    const uint32_t NE = ext ? 4 : 1;   // coordinates per weight and per codeword element
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, (size_t)NE * N * 4);
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * (size_t)NE * (W + K));
     uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
     uint8_t *tree_base = (uint8_t *)arena_alloc(ctx, tree_stride * n_trees);
     uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
@@ -313,7 +403,7 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, n_trees, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // part of the compose stage, queued before the host waits for the roots
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> weights(W + K);
+    std::vector<uint64_t> weights((size_t)NE * (W + K));
     auto challenge = [&]() {
         uint32_t d[8];
         hashc::hash_bytes(tr.data(), tr.size(), d);
@@ -322,9 +412,9 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     auto absorb_index = [&](uint64_t j) {
         for (int i = 0; i < 8; i++) tr.push_back((uint8_t)(j >> (8 * i)));
     };
-    if (rows) {   // the root, then j = 0 .. W + K - 1 with a challenge after each
+    if (rows) {   // the root, then j = 0 .. W + K - 1 (ext: m = 0 .. 4 (W + K) - 1, coordinate m mod 4 of weight m / 4) with a challenge after each
         tr = roots;
-        for (uint32_t j = 0; j < W + K; j++) {
+        for (uint32_t j = 0; j < NE * (W + K); j++) {
             absorb_index(j);
             weights[j] = challenge();
         }
@@ -342,7 +432,8 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     hashc::fs_seed(tr.data(), tr.size(), seed.s, &seed.phase);
     if (column_roots) memcpy(column_roots, roots.data(), roots.size());
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_launch_compose(ctx, H, d_blob, d_lde, N, d_weights, d_cw));
+    if (ext) SMI_TRY(air_launch_compose_ext(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
+    else SMI_TRY(air_launch_compose(ctx, H, d_blob, d_lde, N, d_weights, d_cw));
     mark(3);
     smi_fri_cfg fc;
     fc.omega = h_root(ctx, log_N);
@@ -350,14 +441,20 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     fc.domain_length = N;
     fc.expansion_factor = E;
     fc.num_colinearity_tests = cfg->num_colinearity_tests;
-    FriRequest rq(&fc, d_cw, N, true);
-    rq.reset_arena = false;
-    rq.seed = &seed;
     FriResult res;
-    SMI_TRY(fri_run(ctx, rq, &res));
-    std::vector<uint8_t> &bytes = res.proof;
-    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    else top_indices = res.top.data();   // the column openings need the top-level indices either way
+    FriExtResult xres;
+    if (ext) {
+        SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres));
+    } else {
+        FriRequest rq(&fc, d_cw, N, true);
+        rq.reset_arena = false;
+        rq.seed = &seed;
+        SMI_TRY(fri_run(ctx, rq, &res));
+    }
+    std::vector<uint8_t> &bytes = ext ? xres.proof : res.proof;
+    std::vector<uint64_t> &top = ext ? xres.top : res.top;
+    if (top_indices) memcpy(top_indices, top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    else top_indices = top.data();   // the column openings need the top-level indices either way
     mark(4);
     if (cfg->num_colinearity_tests && rows) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
@@ -416,4 +513,12 @@ int smi_dev_air_prove_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true);
+}
+
+int smi_dev_air_prove_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(ext_field_check(ctx));
+    return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true, true);
 }

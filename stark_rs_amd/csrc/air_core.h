@@ -166,16 +166,104 @@ SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m
     for (int q = 0; q < P; q++) out[q] = acc[q];
 }
 
+// The same P points under weights from the quartic extension (stark_mi.h, "AIR with extension weights"): weight j has
+// four coordinates, w_m[e * AIR_MAX_WEIGHTS + j] the e-th (reduced, Montgomery form), and out[e * P + q] is coordinate e of
+// point q.  The quotients do not depend on the weights: every term_c and every C_k is evaluated once per point -- the
+// Horner chains, the batched inversion, the table walk are the ones above -- and enters four accumulators, so coordinate
+// e is exactly what air_compose_points returns for the weight vector (w_{.,e}).
+template <int P, class Fetch>
+SMI_HD void air_compose_points_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *x_m, const uint32_t *ib, Fetch fetch,
+                                   uint32_t *out) {
+    uint32_t acc[4][P];
+    for (int e = 0; e < 4; e++)
+        for (int q = 0; q < P; q++) acc[e][q] = 0;
+    const uint32_t n_free = A.W - A.n_bcols;
+    for (uint32_t j = 0; j < n_free; j++) {
+        const uint32_t c = A.free_col[j];
+        uint32_t v[P];
+        for (int q = 0; q < P; q++) v[q] = fetch(q, c);
+        for (int e = 0; e < 4; e++) {
+            const uint32_t w = w_m[e * AIR_MAX_WEIGHTS + c];
+            for (int q = 0; q < P; q++) acc[e][q] = fp_add(acc[e][q], mont_mul(v[q], w, F), F.p);
+        }
+    }
+    constexpr int G = AIR_INV_BATCH / P;   // columns per inversion
+    for (uint32_t j0 = 0; j0 < A.n_bcols; j0 += G) {
+        uint32_t z[AIR_INV_BATCH], pre[AIR_INV_BATCH];
+        for (int g = 0; g < G; g++) {
+            for (int q = 0; q < P; q++) z[g * P + q] = F.r1;
+            if (j0 + g < A.n_bcols)
+                for (uint32_t b = A.bfirst[j0 + g]; b < A.bfirst[j0 + g + 1]; b++) {
+                    const uint32_t r = A.broot_m[b];
+                    for (int q = 0; q < P; q++) z[g * P + q] = mont_mul(z[g * P + q], fp_sub(x_m[q], r, F.p), F);
+                }
+        }
+        pre[0] = z[0];
+        for (int i = 1; i < AIR_INV_BATCH; i++) pre[i] = mont_mul(pre[i - 1], z[i], F);
+        uint32_t inv = mont_pow(pre[AIR_INV_BATCH - 1], F.p - 2, F);   // never 0: the coset does not meet the trace domain
+        for (int g = G - 1; g >= 0; g--) {
+            uint32_t zi[P];   // 1 / z[g * P + q]
+            for (int q = P - 1; q >= 0; q--) {
+                const int i = g * P + q;
+                zi[q] = i ? mont_mul(inv, pre[i - 1], F) : inv;
+                inv = mont_mul(inv, z[i], F);
+            }
+            if (j0 + g >= A.n_bcols) continue;
+            const uint32_t c = A.bcol[j0 + g], b0 = A.bfirst[j0 + g], b1 = A.bfirst[j0 + g + 1];
+            uint32_t ix[P];   // I_c(x), Horner from the top coefficient
+            for (int q = 0; q < P; q++) ix[q] = 0;
+            for (uint32_t b = b1; b > b0; b--) {
+                const uint32_t coef = A.bicoef[b - 1];
+                for (int q = 0; q < P; q++) ix[q] = fp_add(mont_mul(ix[q], x_m[q], F), coef, F.p);
+            }
+            uint32_t bq[P];   // the boundary quotient (f_c - I_c) / Z_c, plain
+            for (int q = 0; q < P; q++) bq[q] = mont_mul(fp_sub(fetch(q, c), ix[q], F.p), zi[q], F);
+            for (int e = 0; e < 4; e++) {
+                const uint32_t w = w_m[e * AIR_MAX_WEIGHTS + c];
+                for (int q = 0; q < P; q++) acc[e][q] = fp_add(acc[e][q], mont_mul(bq[q], w, F), F.p);
+            }
+        }
+    }
+    if (A.K) {
+        uint32_t zt[P];   // (x - last) / (x^n - tau^n), Montgomery form
+        for (int q = 0; q < P; q++) zt[q] = mont_mul(fp_sub(x_m[q], A.last_m, F.p), A.izt_m[ib[q]], F);
+        for (uint32_t k = 0; k < A.K; k++) {
+            uint32_t ck[P];
+            for (int q = 0; q < P; q++) ck[q] = 0;
+            for (uint32_t t = A.cft[k]; t < A.cft[k + 1]; t++) {
+                uint32_t m[P];
+                const uint32_t coef = A.tcoef[t];
+                for (int q = 0; q < P; q++) m[q] = coef;
+                for (uint32_t f = A.tff[t]; f < A.tff[t + 1]; f++) {
+                    const uint32_t fe = A.fac[f], var = fe & 0xffffu;
+                    uint32_t v[P];
+                    for (int q = 0; q < P; q++) v[q] = fetch(q, var);
+                    for (uint32_t e = fe >> 16; e; e--)
+                        for (int q = 0; q < P; q++) m[q] = mont_mul(m[q], v[q], F);
+                }
+                for (int q = 0; q < P; q++) ck[q] = fp_add(ck[q], m[q], F.p);
+            }
+            for (int q = 0; q < P; q++) ck[q] = mont_mul(ck[q], zt[q], F);   // tq_k, plain
+            for (int e = 0; e < 4; e++) {
+                const uint32_t wk = w_m[e * AIR_MAX_WEIGHTS + A.W + k];
+                for (int q = 0; q < P; q++) acc[e][q] = fp_add(acc[e][q], mont_mul(ck[q], wk, F), F.p);
+            }
+        }
+    }
+    for (int e = 0; e < 4; e++)
+        for (int q = 0; q < P; q++) out[e * P + q] = acc[e][q];
+}
+
 // The tile of T points a workgroup stages per column: T points and a halo of B, wrapping at N.  Tile element e of
 // column c sits at tile[c * (T + B) + e] and comes from column index (base + e) mod N.  Periodic column j is tile row
 // W + j, staged the same way from table index (base + e) mod L_j: air_tile is asked for W + Q rows.
 struct AirTile {
     uint32_t T, threads, P;   // points per tile, threads per workgroup, points per thread (T = threads * P)
 };
-inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N) {   // W: tile rows
+inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N, uint32_t weight_vecs = 1) {   // W: tile rows; weight_vecs: 4 for the ext kernel
     AirTile t{0, 0, 0};
     for (uint32_t T = 1024; T >= 64; T >>= 1) {
-        if (T > N || (uint64_t)W * (T + B) * 4 + AIR_MAX_WEIGHTS * 4 > AIR_LDS_BYTES) continue;
+        if (T > N || (uint64_t)W * (T + B) * 4 + (uint64_t)weight_vecs * AIR_MAX_WEIGHTS * 4 > AIR_LDS_BYTES) continue;
         t.T = T;
         t.threads = T >= AIR_BLOCK ? AIR_BLOCK : T;
         t.P = T / t.threads;
@@ -478,4 +566,41 @@ SMI_HD void air_direct_point(const AirDev &A, const Fp &F, const uint32_t *w_m, 
         },
         &res);
     out[i] = res;
+}
+
+// air_tile_thread / air_direct_point under extension weights: the same tile, the same x, four output columns out_stride
+// apart (w_m: 4 * AIR_MAX_WEIGHTS words, air_compose_points_ext)
+template <int P>
+SMI_HD void air_tile_thread_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *tile, uint32_t T, uint32_t threads,
+                                uint64_t base, uint32_t xbase_m, uint32_t step_m, uint32_t tid, uint32_t *out, uint64_t out_stride) {
+    const uint32_t B = 1u << A.log_B, pitch = T + B, R = A.W + A.Q;
+    uint32_t x_m[P], ib[P], res[4 * P];
+    uint32_t x = mont_mul(xbase_m, A.lane_pow_m[tid], F);
+    for (int q = 0; q < P; q++) {
+        x_m[q] = x;
+        ib[q] = (uint32_t)((base + tid + (uint64_t)q * threads) & (B - 1));
+        x = mont_mul(x, step_m, F);
+    }
+    air_compose_points_ext<P>(
+        A, F, w_m, x_m, ib,
+        [&](int q, uint32_t var) {
+            const uint32_t c = var < R ? var : var - R;
+            return tile[c * pitch + tid + q * threads + (var < R ? 0 : B)];
+        },
+        res);
+    for (int e = 0; e < 4; e++)
+        for (int q = 0; q < P; q++) out[e * out_stride + base + tid + (uint64_t)q * threads] = res[e * P + q];
+}
+SMI_HD void air_direct_point_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, uint64_t i,
+                                 uint32_t *out, uint64_t out_stride) {
+    const uint64_t B = 1ull << A.log_B, nx = (i + B) & (A.N - 1);
+    const uint32_t x_m = mont_mul(A.h_m, mont_pow(A.omega_m, i, F), F), ib = (uint32_t)(i & (B - 1));
+    uint32_t res[4];
+    air_compose_points_ext<1>(
+        A, F, w_m, &x_m, &ib,
+        [&](int, uint32_t var) {
+            return air_mem_operand(A, var, i, [&](uint32_t c) { return cols[c * stride + i]; }, [&](uint32_t c) { return cols[c * stride + nx]; });
+        },
+        res);
+    for (int e = 0; e < 4; e++) out[e * out_stride + i] = res[e];
 }

@@ -578,6 +578,54 @@ extern "C" int emu_fold_shard(uint64_t p, uint64_t g, const uint32_t *lo, const 
     return 0;
 }
 
+// fri_fold_ext_kernel's per-element body (fri_core.h fold_element_ext) over four coordinate columns `stride` apart
+extern "C" int emu_fold_ext(uint64_t p, uint64_t g, const uint32_t *in, uint32_t len, uint64_t stride, const uint64_t *alpha, uint64_t offset,
+                            uint64_t omega, uint32_t *out, uint64_t out_stride) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs) || !ext_field_ok(p, g, nullptr)) return -1;
+    if (len < 2 || (len & (len - 1)) || stride < len || out_stride < len / 2 || !offset || !omega || offset >= p || omega >= p) return -1;
+    const Fp &F = fs.F;
+    const uint32_t pp = F.p, half = len / 2;
+    uint32_t L = 0;
+    while ((1u << L) < half) L++;
+    GeomSpec sp[2];
+    scale_table_specs(F, host_powmod((uint32_t)offset, pp - 2, pp), host_powmod((uint32_t)omega, pp - 2, pp), L, sp);
+    std::vector<uint32_t> slo = fill(sp[0], F), shi = fill(sp[1], F);
+    const ScaleTables S{slo.data(), shi.data(), scale_table_h(L)};
+    const uint32_t inv2_m = (uint32_t)(((uint64_t)host_powmod(2, pp - 2, pp) << 32) % pp), g_m = (uint32_t)(((uint64_t)fs.g << 32) % pp);
+    const ExtMul a = fold_ext_alpha(alpha, g_m, F);
+    for (uint32_t i = 0; i < half; i++) {
+        uint32_t l[4], h[4], o[4];
+        for (int e = 0; e < 4; e++) {
+            l[e] = in[e * stride + i];
+            h[e] = in[e * stride + half + i];
+        }
+        fold_element_ext(l, h, i, a, inv2_m, S, F, o);
+        for (int e = 0; e < 4; e++) out[e * out_stride + i] = o[e];
+    }
+    return 0;
+}
+
+// The transcript of FRI over the quartic extension as fs_round_ext_kernel runs it (hash_core.h fs_round_ext_lane, one call
+// per lane): prefix, then n_roots roots; alphas gets four unreduced coordinates per root but the last; returns the index-
+// seed challenge of the transcript as it stands after the last root.
+extern "C" uint64_t emu_fs_rounds_ext(const uint8_t *prefix, size_t prefix_len, const uint8_t *roots, uint32_t n_roots, uint64_t *alphas) {
+    uint32_t fs[16], phase = 0;
+    hashc::fs_seed(prefix, prefix_len, fs, &phase);
+    for (uint32_t r = 0; r < n_roots; r++) {
+        uint32_t m[8];
+        memcpy(m, roots + 32 * r, 32);
+        if (r + 1 == n_roots) {
+            hashc::fs_absorb_root_phase(fs, m, phase, nullptr, nullptr);
+            break;
+        }
+        uint32_t out[4][16];
+        for (int lane = 0; lane < 4; lane++) hashc::fs_round_ext_lane(fs, m, phase, lane, out[lane], &alphas[4 * r + lane]);
+        memcpy(fs, out[3], sizeof fs);
+    }
+    return hashc::fs_challenge_phase(fs, phase);
+}
+
 // ProofStream::deserialize as smi_fri_verify runs it (csrc/proof_parse.h), exposed for the CPU fuzz / sanitizer
 // tests: tags, element counts and payload offsets of up to `cap` objects; returns how many objects there are.
 extern "C" size_t emu_proof_parse(const uint8_t *b, size_t n, size_t max_objs, int32_t *tags, uint64_t *counts, uint64_t *offsets,

@@ -50,6 +50,23 @@ void emu_tiles(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t
         for (uint32_t tid = 0; tid < tl.threads; tid++) air_tile_thread<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out);
     }
 }
+
+template <int P>
+void emu_tiles_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, const AirTile &tl, uint32_t *out,
+                   uint64_t out_stride) {
+    const uint32_t B = 1u << A.log_B, pitch = tl.T + B;
+    std::vector<uint32_t> tile((size_t)(A.W + A.Q) * pitch);
+    const uint32_t step_m = mont_pow(A.omega_m, tl.threads, F);
+    for (uint64_t base = 0; base < A.N; base += tl.T) {
+        for (uint32_t c = 0; c < A.W; c++)
+            for (uint32_t e = 0; e < pitch; e++) tile[(size_t)c * pitch + e] = cols[c * stride + ((base + e) & (A.N - 1))];
+        for (uint32_t j = 0; j < A.Q; j++)
+            for (uint32_t e = 0; e < pitch; e++) tile[(size_t)(A.W + j) * pitch + e] = A.ptab[A.pofs[j] + ((uint32_t)(base + e) & ((1u << A.plog[j]) - 1u))];
+        const uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, base, F), F);
+        for (uint32_t tid = 0; tid < tl.threads; tid++)
+            air_tile_thread_ext<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out, out_stride);
+    }
+}
 }  // namespace
 
 extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *lde, uint64_t stride,
@@ -77,6 +94,36 @@ extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg,
     else if (tl.P == 4) emu_tiles<4>(A, fs.F, w_m.data(), lde, stride, tl, out);
     else if (tl.P == 2) emu_tiles<2>(A, fs.F, w_m.data(), lde, stride, tl, out);
     else emu_tiles<1>(A, fs.F, w_m.data(), lde, stride, tl, out);
+    return SMI_OK;
+}
+
+// air_compose_ext_kernel the same way: weights = 4 (W + K) unreduced u64 (coordinate e of weight j at 4 j + e), out =
+// four coordinate columns out_stride apart
+extern "C" int emu_air_compose_ext(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *lde, uint64_t stride,
+                                   const uint64_t *weights, uint32_t *out, uint64_t out_stride, int force_direct) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
+    std::string why;
+    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why);
+    if (rc != SMI_OK) return rc;
+    const uint32_t log_N = cfg->log_n + cfg->log_blowup;
+    if (log_N > fs.K) return SMI_ERR_UNSUPPORTED_PRIME;
+    AirHost H;
+    air_build(fs.F, host_powmod(fs.wmax[0], 1ull << (fs.K - log_N), fs.F.p), cfg, air, &H);
+    std::vector<uint32_t> tab;
+    if (!emu_periodic_tables(p, g, H.per, &tab)) return SMI_ERR_BAD_ARG;
+    H.dev.ptab = tab.data();
+    const AirDev &A = H.dev;
+    if (stride < A.N || out_stride < A.N) return SMI_ERR_BAD_ARG;
+    std::vector<uint32_t> w_m(4 * AIR_MAX_WEIGHTS, 0);
+    for (uint32_t i = 0; i < 4 * (A.W + A.K); i++) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], fs.F);
+    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N, 4);
+    if (force_direct || (stride & 3)) tl.T = 0;
+    if (!tl.T)
+        for (uint64_t i = 0; i < A.N; i++) air_direct_point_ext(A, fs.F, w_m.data(), lde, stride, i, out, out_stride);
+    else if (tl.P == 4) emu_tiles_ext<4>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
+    else if (tl.P == 2) emu_tiles_ext<2>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
+    else emu_tiles_ext<1>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
     return SMI_OK;
 }
 

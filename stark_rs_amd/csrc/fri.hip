@@ -381,6 +381,115 @@ int smi_dev_fri_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d
     return launch_fold_shard(ctx, d_lo, d_hi, count, index0, full_len, d_alpha, offset, omega, d_out);
 }
 
+// ------------------------------------------------------------------------- fold over the quartic extension
+// The codeword is four coordinate columns `stride` apart (include/stark_mi.h, "Quartic extension"); element i of the
+// next one is fold_element_ext (fri_core.h) of elements i and i + half.  8 words in, 4 out per output element: 48 B.
+// VEC: a lane takes four consecutive elements, every access 16 bytes (all bases 16-byte aligned, strides and half
+// multiples of 4); otherwise one element per lane, 4-byte accesses.  alpha: four unreduced u64 in device memory.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fri_fold_ext_kernel(const uint32_t *__restrict__ in, size_t stride, uint32_t half,
+                                                           const uint64_t *__restrict__ alpha_ptr, uint32_t g_m, Fp F, ScaleTables S,
+                                                           uint32_t inv2_m, uint32_t *__restrict__ out, size_t out_stride) {
+    const uint64_t a[4] = {alpha_ptr[0], alpha_ptr[1], alpha_ptr[2], alpha_ptr[3]};
+    const ExtMul alpha = fold_ext_alpha(a, g_m, F);
+    const uint32_t step = gridDim.x * blockDim.x;
+    if constexpr (VEC) {
+        for (uint32_t i = 4 * (blockIdx.x * blockDim.x + threadIdx.x); i < half; i += 4 * step) {
+            uint32_t lo[4][4], hi[4][4], res[4][4];   // [coordinate][element]
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const uint4 l = *(const uint4 *)(in + e * stride + i), h = *(const uint4 *)(in + e * stride + half + i);
+                lo[e][0] = l.x; lo[e][1] = l.y; lo[e][2] = l.z; lo[e][3] = l.w;
+                hi[e][0] = h.x; hi[e][1] = h.y; hi[e][2] = h.z; hi[e][3] = h.w;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t l[4] = {lo[0][j], lo[1][j], lo[2][j], lo[3][j]}, h[4] = {hi[0][j], hi[1][j], hi[2][j], hi[3][j]};
+                uint32_t o[4];
+                fold_element_ext(l, h, i + j, alpha, inv2_m, S, F, o);
+#pragma unroll
+                for (int e = 0; e < 4; e++) res[e][j] = o[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) *(uint4 *)(out + e * out_stride + i) = make_uint4(res[e][0], res[e][1], res[e][2], res[e][3]);
+        }
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < half; i += step) {
+            uint32_t l[4], h[4], o[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                l[e] = in[e * stride + i];
+                h[e] = in[e * stride + half + i];
+            }
+            fold_element_ext(l, h, i, alpha, inv2_m, S, F, o);
+#pragma unroll
+            for (int e = 0; e < 4; e++) out[e * out_stride + i] = o[e];
+        }
+    }
+}
+
+// the context's (p, g) must make X^4 - g irreducible (fri_core.h ext_field_ok)
+int ext_field_check(smi_ctx *ctx) {
+    const char *why = nullptr;
+    if (!ext_field_ok(ctx->fs.F.p, ctx->fs.g, &why)) return smi_fail(ctx, SMI_ERR_BAD_ARG, why);
+    return SMI_OK;
+}
+
+static int launch_fold_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset, uint64_t omega,
+                           uint32_t *d_out, size_t out_stride) {
+    const uint32_t p = ctx->fs.F.p;
+    if (len < 2 || !is_pow2(len) || len > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold_ext: codeword length must be a power of two in 2 .. 2^27");
+    const size_t half = len / 2;
+    if (stride < len || out_stride < half) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold_ext: stride < len or out_stride < len / 2");
+    if (offset >= p || omega >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "fold: offset/omega must be < p");
+    ScaleScope pin__(ctx);
+    ScaleTables S;
+    SMI_TRY(fri_fold_tables(ctx, (uint32_t)offset, (uint32_t)omega, len, &S));   // (refuses a zero offset / omega)
+    const uint32_t g_m = (uint32_t)(((uint64_t)ctx->fs.g << 32) % p);
+    const bool vec = !(half & 3) && !(stride & 3) && !(out_stride & 3) && !(((uintptr_t)d_in | (uintptr_t)d_out) & 15u);
+    const size_t lanes = vec ? half / 4 : half;
+    uint32_t grid = (uint32_t)((lanes + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    ProfScope ps(ctx, "fri_fold_ext_kernel", 48.0 * (double)half);   // read 2 x 16 B, write 16 B per output element
+    if (vec) fri_fold_ext_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_in, stride, (uint32_t)half, d_alpha, g_m, ctx->fs.F, S, fri_inv2_m(ctx), d_out, out_stride);
+    else fri_fold_ext_kernel<false><<<grid, 256, 0, ctx->stream>>>(d_in, stride, (uint32_t)half, d_alpha, g_m, ctx->fs.F, S, fri_inv2_m(ctx), d_out, out_stride);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+int smi_dev_fri_fold_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset, uint64_t omega,
+                         uint32_t *d_out, size_t out_stride) {
+    if (!ctx || !d_in || !d_alpha || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(ext_field_check(ctx));
+    return launch_fold_ext(ctx, d_in, len, stride, d_alpha, offset, omega, d_out, out_stride);
+}
+
+// F_q on the host, no context (smi_air_plan's kind): plain canonical coordinates in and out
+static int ext_args(uint64_t p, uint64_t g, const uint64_t *a, const uint64_t *b) {
+    if (!ext_field_ok(p, g, nullptr) || !is_prime_u32((uint32_t)p)) return SMI_ERR_BAD_ARG;
+    for (int e = 0; e < 4; e++)
+        if (a[e] >= p || (b && b[e] >= p)) return SMI_ERR_NON_CANONICAL;
+    return SMI_OK;
+}
+int smi_ext_mul(uint64_t p, uint64_t g, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) {
+    if (!a || !b || !out) return SMI_ERR_BAD_ARG;
+    SMI_TRY(ext_args(p, g, a, b));
+    const uint32_t x[4] = {(uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3]}, y[4] = {(uint32_t)b[0], (uint32_t)b[1], (uint32_t)b[2], (uint32_t)b[3]};
+    uint32_t r[4];
+    ext_mul_host((uint32_t)p, (uint32_t)g, x, y, r);
+    for (int e = 0; e < 4; e++) out[e] = r[e];
+    return SMI_OK;
+}
+int smi_ext_inv(uint64_t p, uint64_t g, const uint64_t a[4], uint64_t out[4]) {
+    if (!a || !out) return SMI_ERR_BAD_ARG;
+    SMI_TRY(ext_args(p, g, a, nullptr));
+    const uint32_t x[4] = {(uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3]};
+    uint32_t r[4];
+    if (!ext_inv_host((uint32_t)p, (uint32_t)g, x, r)) return SMI_ERR_NO_INVERSE;   // src/ff.rs:171
+    for (int e = 0; e < 4; e++) out[e] = r[e];
+    return SMI_OK;
+}
+
 // Codewords of at most this many elements finish in the fused tail launch (hash.hip, fri_tail_kernel).
 // Measured on MI355X (2^25-point prove): the FRI stage is 4.44..4.69 ms with the tail
 // off, from 512, from 1024 or from 2048 elements alike -- the differences are inside the run-to-run
@@ -615,6 +724,171 @@ int fri_run(smi_ctx *ctx, const FriRequest &rq, FriResult *res) {
     if (rc == SMI_OK && rq.retain) res->run = x.run;
     else smi_fri_run_free(x.run);
     return rc;
+}
+
+// ------------------------------------------------------------------------- FRI over the quartic extension
+// The round of hash_core.h fs_round_ext_lane on four lanes, one coordinate of alpha each; lane 3 keeps the state.  The
+// last round (alpha_out == nullptr) absorbs its root and draws nothing.  Any phase.
+__global__ __launch_bounds__(64) void fs_round_ext_kernel(FsSeed *fs, const uint32_t *root, uint8_t *proof_slot, uint64_t *alpha_out) {
+    if (blockIdx.x || threadIdx.x >= 4) return;
+    uint32_t m[8], in[16], out[16];
+    for (int j = 0; j < 8; j++) m[j] = root[j];
+    for (int j = 0; j < 16; j++) in[j] = fs->s[j];
+    const uint32_t phase = fs->phase;
+    if (threadIdx.x == 0) {
+        proof_slot[0] = 0;
+        for (int i = 0; i < 32; i++) proof_slot[1 + i] = (uint8_t)(m[i >> 2] >> (8 * (i & 3)));
+    }
+    if (!alpha_out) {
+        if (threadIdx.x == 0) hashc::fs_absorb_root_phase(fs->s, m, phase, nullptr, nullptr);
+        return;
+    }
+    uint64_t a;
+    hashc::fs_round_ext_lane(in, m, phase, (int)threadIdx.x, out, &a);
+    alpha_out[threadIdx.x] = a;
+    if (threadIdx.x == 3)
+        for (int j = 0; j < 16; j++) fs->s[j] = out[j];
+}
+
+// the last codeword in the clear: tag 2, count 4 len, element i at values 4 i .. 4 i + 3
+__global__ void emit_codeword_ext_kernel(const uint32_t *cw, size_t stride, uint64_t len, uint8_t *dst) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        dst[0] = 2;
+        put_u64(dst + 1, 4 * len);
+    }
+    if (i < 4 * len) put_u64(dst + 9 + 8 * i, cw[(i & 3) * stride + (i >> 2)]);
+}
+
+// query_one for four-column codewords: per (layer, test) one record of 12 values -- a, b, c, four coordinates each --
+// and the three paths of the reference's order
+struct LayerInfoExt {
+    const uint32_t *cw, *cw_next;
+    size_t stride, stride_next;
+    const uint8_t *nodes, *nodes_next;
+    uint64_t len, off_triples, off_paths;
+    uint32_t depth, depth_next;
+};
+struct LayerTableExt {
+    LayerInfoExt l[SMI_QUERY_TAB_MAX];
+};
+__global__ void query_ext_kernel(const LayerTableExt tab, const uint64_t *top, uint8_t *proof) {
+    const LayerInfoExt &L = tab.l[blockIdx.y];
+    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    const uint64_t half = L.len / 2;
+    const uint64_t c = top[s] % half;
+    uint8_t *tr = proof + L.off_triples + (uint64_t)s * (9 + 96);
+    if (lane == 0) {
+        tr[0] = 2;
+        put_u64(tr + 1, 12);
+    }
+    if (lane < 12) {
+        const uint32_t e = lane & 3, which = lane >> 2;
+        const uint32_t v = which == 0 ? L.cw[e * L.stride + c] : (which == 1 ? L.cw[e * L.stride + c + half] : L.cw_next[e * L.stride_next + c]);
+        put_u64(tr + 9 + 8 * lane, v);
+    }
+    const uint64_t pa = 9 + 32ull * L.depth, pc = 9 + 32ull * L.depth_next;
+    uint8_t *pp = proof + L.off_paths + (uint64_t)s * (2 * pa + pc);
+    write_path(pp, L.nodes, L.len, L.depth, c, lane);
+    write_path(pp + pa, L.nodes, L.len, L.depth, c + half, lane);
+    write_path(pp + 2 * pa, L.nodes_next, half, L.depth_next, c, lane);
+}
+
+int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
+                FriExtResult *res) {
+    SMI_TRY(ext_field_check(ctx));
+    SMI_TRY(smi_fri_check(ctx, cfg));
+    if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
+    if (stride < len || len > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext: stride < len, or len > 2^27");
+    const uint32_t p = ctx->fs.F.p;
+    if (cfg->omega >= p || cfg->offset >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
+    const FriLayout lay = fri_layout_ext(*cfg);
+    const uint64_t R = lay.R, t = cfg->num_colinearity_tests;
+    if (R == 0) return smi_fail(ctx, SMI_ERR_NO_ROUNDS, "num_rounds() == 0: the reference's verify rejects such a proof");
+    if (R - 1 > SMI_QUERY_TAB_MAX) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext: too many rounds");
+    if (t > 2 * lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, "not enough entropy in indices wrt last codeword");
+    if (t > lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, "cannot sample more indices than available in last codeword");
+    const FsSeed fs0 = seed ? *seed : fresh_seed();
+    if (reset_arena) SMI_TRY(arena_reset(ctx));
+    ScaleScope pin__(ctx);
+
+    // one device buffer comes back in one copy: proof | top-level indices; beside it: fs state | seed challenge | reduced
+    const size_t off_top = (lay.proof_len + 7) & ~(size_t)7, back_len = off_top + 8 * (t + 1);
+    const size_t m_alpha = (sizeof(FsSeed) + 63) & ~(size_t)63, m_seed_ch = m_alpha + 32 * R, m_reduced = m_seed_ch + 8;
+    uint8_t *misc = (uint8_t *)arena_alloc(ctx, m_reduced + 8 * (t + 1));
+    uint8_t *d_proof = (uint8_t *)arena_alloc(ctx, back_len);
+    if (!misc || !d_proof) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext: device memory");
+    FsSeed *d_fs = (FsSeed *)misc;
+    uint64_t *d_alphas = (uint64_t *)(misc + m_alpha), *d_seed_ch = (uint64_t *)(misc + m_seed_ch), *d_reduced = (uint64_t *)(misc + m_reduced);
+    uint64_t *d_top = (uint64_t *)(d_proof + off_top);
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, fs0);
+
+    LayerTableExt tab;
+    memset(&tab, 0, sizeof tab);
+    const uint32_t *cur = d_codeword;
+    size_t cur_stride = stride;
+    uint32_t omega = (uint32_t)cfg->omega, offset = (uint32_t)cfg->offset;
+    for (uint64_t r = 0; r < R; r++) {
+        const uint64_t n = len >> r;
+        const bool last = r == R - 1;
+        uint8_t *nodes = (uint8_t *)arena_alloc(ctx, (2 * n - 1) * 32);
+        if (!nodes) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext: tree");
+        SMI_TRY(launch_merkle_rows(ctx, cur, 4, cur_stride, n, nodes));   // leaf i = the hash of element i's four coordinates
+        fs_round_ext_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, (const uint32_t *)(nodes + (2 * n - 2) * 32), d_proof + 33 * r, last ? nullptr : d_alphas + 4 * r);
+        HIP_TRY(ctx, hipGetLastError());
+        if (r > 0) {
+            LayerInfoExt &L = tab.l[r - 1];
+            L.cw_next = cur;
+            L.stride_next = cur_stride;
+            L.nodes_next = nodes;
+        }
+        if (last) break;
+        LayerInfoExt &L = tab.l[r];
+        L.cw = cur;
+        L.stride = cur_stride;
+        L.nodes = nodes;
+        L.len = n;
+        L.off_triples = lay.off_triples[r];
+        L.off_paths = lay.off_paths[r];
+        L.depth = ilog2(n);
+        L.depth_next = L.depth - 1;
+        const uint64_t half = n / 2;
+        uint32_t *next = (uint32_t *)arena_alloc(ctx, 16 * half);
+        if (!next) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext: codeword");
+        SMI_TRY(launch_fold_ext(ctx, cur, n, cur_stride, d_alphas + 4 * r, offset, omega, next, half));
+        cur = next;
+        cur_stride = half;
+        omega = h_mul(ctx, omega, omega);
+        offset = h_mul(ctx, offset, offset);
+    }
+    emit_codeword_ext_kernel<<<(uint32_t)((4 * lay.last_n + 255) / 256), 256, 0, ctx->stream>>>(cur, cur_stride, lay.last_n, d_proof + lay.off_last);
+    HIP_TRY(ctx, hipGetLastError());
+    SMI_TRY(launch_fs_challenge(ctx, d_fs, d_seed_ch, fs0.phase));
+    SMI_TRY(launch_sample_indices(ctx, d_seed_ch, R > 1 ? len / 2 : len, lay.last_n, (uint32_t)t, d_top, d_reduced));
+    if (R > 1 && t > 0) {
+        query_ext_kernel<<<dim3((uint32_t)t, (uint32_t)(R - 1)), 64, 0, ctx->stream>>>(tab, d_top, d_proof);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    uint8_t *land = nullptr;
+    SMI_TRY(ctx_pin_out(ctx, back_len, &land));
+    HIP_TRY(ctx, hipMemcpyAsync(land, d_proof, back_len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    res->proof.assign(land, land + lay.proof_len);
+    res->top.assign(t + 1, 0);
+    if (t) memcpy(res->top.data(), land + off_top, 8 * t);
+    return SMI_OK;
+}
+
+int smi_dev_fri_prove_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                          size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices) {
+    if (!ctx || !cfg || !d_codeword || !proof || !proof_len || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
+    DeviceGuard dg__(ctx);
+    FriExtResult res;
+    SMI_TRY(fri_run_ext(ctx, cfg, &seed, d_codeword, len, stride, true, &res));
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    return smi_proof_out(ctx, res.proof, proof, proof_len);
 }
 
 // ------------------------------------------------------------------------- C ABI

@@ -15,3 +15,109 @@ SMI_HD uint32_t fold_element(uint32_t lo, uint32_t hi, uint32_t i, uint32_t ah_m
 SMI_HD uint32_t fold_alpha_half(uint64_t alpha, uint32_t inv2_m, const Fp &F) {
     return mont_mul(to_mont_u64(alpha, F), inv2_m, F);   // alpha may be an unreduced u64 (H6); no 64-bit division per thread
 }
+
+// ------------------------------------------------------------------------- quartic extension
+// F_q = F_p[X] / (X^4 - g): an element is four residues c0..c3, low degree first (include/stark_mi.h, "Quartic
+// extension").  (a b)_k = sum_{i+j=k} a_i b_j + g sum_{i+j=k+4} a_i b_j.
+//
+// One factor of every product on the hot path is fixed for the launch (the round's alpha), so it comes prepared: its
+// coordinates b_j and g b_j, both in Montgomery form.  Coordinate k of the product is then a sum of exactly four 32x32
+// products, and with 4 p < 2^32 that sum stays below p 2^32, the bound of ONE Montgomery reduction: 16 multiplies and
+// 4 reductions per product.  A larger modulus takes the branch that reduces every product (wave-uniform).
+struct ExtMul {
+    uint32_t b_m[4], gb_m[4];
+};
+SMI_HD ExtMul ext_mul_prepare(const uint32_t b_m[4], uint32_t g_m, const Fp &F) {
+    ExtMul M;
+    for (int j = 0; j < 4; j++) {
+        M.b_m[j] = b_m[j];
+        M.gb_m[j] = mont_mul(b_m[j], g_m, F);
+    }
+    return M;
+}
+// t * R^-1 mod p for t < p * 2^32 (mont_mul's reduction on a product that is already formed)
+SMI_HD uint32_t mont_reduce64(uint64_t t, const Fp &F) {
+    const uint32_t u = umulhi32((uint32_t)t * F.pinv, F.p);
+    const uint32_t r = (uint32_t)(t >> 32) - u;
+    return umin32(r, r + F.p);
+}
+// out = a * b with a plain and b prepared: plain.  out may not alias a.
+SMI_HD void ext_mul_prepared(const uint32_t a[4], const ExtMul &M, const Fp &F, uint32_t out[4]) {
+    if (F.p < (1u << 30)) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint64_t t = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) t += (uint64_t)a[i] * (i <= k ? M.b_m[k - i] : M.gb_m[k + 4 - i]);
+            out[k] = mont_reduce64(t, F);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t s = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) s = fp_add(s, mont_mul(a[i], i <= k ? M.b_m[k - i] : M.gb_m[k + 4 - i], F), F.p);
+            out[k] = s;
+        }
+    }
+}
+// the round's alpha as the fold uses it: four unreduced u64 coordinates -> prepared factor
+SMI_HD ExtMul fold_ext_alpha(const uint64_t alpha[4], uint32_t g_m, const Fp &F) {
+    uint32_t a_m[4];
+    for (int e = 0; e < 4; e++) a_m[e] = to_mont_u64(alpha[e], F);
+    return ext_mul_prepare(a_m, g_m, F);
+}
+// Element i of the next codeword: 2^-1 (lo + hi) + alpha * ((lo - hi) * 2^-1 * x_i^-1), lo and hi in F_q, x_i in F_p
+// from the same two-level table fold_element reads, the product by alpha a full F_q product.
+SMI_HD void fold_element_ext(const uint32_t lo[4], const uint32_t hi[4], uint32_t i, const ExtMul &alpha, uint32_t inv2_m, const ScaleTables &S,
+                             const Fp &F, uint32_t out[4]) {
+    const uint32_t t_m = mont_mul(two_level(S.lo, S.hi, S.h, i, F), inv2_m, F);   // 2^-1 x_i^-1, Montgomery form
+    uint32_t d[4], ad[4];
+    for (int e = 0; e < 4; e++) d[e] = mont_mul(fp_sub(lo[e], hi[e], F.p), t_m, F);
+    ext_mul_prepared(d, alpha, F, ad);
+    for (int e = 0; e < 4; e++) out[e] = fp_add(mont_mul(fp_add(lo[e], hi[e], F.p), inv2_m, F), ad[e], F.p);
+}
+
+// ---- host only: the field itself, on plain residues (smi_ext_mul / smi_ext_inv, the verifier, the tests)
+// X^4 - g is irreducible over F_p when p = 1 (mod 4) and g is a non-square (Lang, Algebra VI 9.1: g must be no square
+// and must not lie in -4 F_p^4; with p = 1 (mod 4), -4 = (1 + i)^4 is a fourth power itself, so -4 F_p^4 holds squares only)
+inline bool ext_field_ok(uint64_t p, uint64_t g, const char **why) {
+    const char *w = nullptr;
+    if (p < 5 || p >= (1ull << 31) || !(p & 1)) w = "ext: modulus must be an odd prime < 2^31";
+    else if ((p & 3) != 1) w = "ext: p = 3 (mod 4): X^4 - g is reducible for every g";
+    else if (!g || g >= p) w = "ext: g must be in 1 .. p-1";
+    else if (host_powmod((uint32_t)g, (p - 1) / 2, (uint32_t)p) != p - 1) w = "ext: g^((p-1)/2) != -1: g is a square and X^4 - g is reducible";
+    if (why) *why = w ? w : "";
+    return w == nullptr;
+}
+inline void ext_mul_host(uint32_t p, uint32_t g, const uint32_t a[4], const uint32_t b[4], uint32_t out[4]) {
+    uint32_t r[4];
+    for (int k = 0; k < 4; k++) {
+        uint32_t lo = 0, hi = 0;
+        for (int i = 0; i < 4; i++) {
+            if (i <= k) lo = fp_add(lo, host_mulmod(a[i], b[k - i], p), p);
+            else hi = fp_add(hi, host_mulmod(a[i], b[k + 4 - i], p), p);
+        }
+        r[k] = fp_add(lo, host_mulmod(hi, g, p), p);
+    }
+    for (int k = 0; k < 4; k++) out[k] = r[k];
+}
+// Through the tower F_p < F_p[Y]/(Y^2 - g) < F_q, Y = X^2: a = A + B X with A = a0 + a2 Y, B = a1 + a3 Y, and
+// a^-1 = (A - B X) / (A^2 - Y B^2); the denominator D = d0 + d1 Y has D^-1 = (d0 - d1 Y) / (d0^2 - g d1^2).
+// false for a == 0 (the only element without an inverse).
+inline bool ext_inv_host(uint32_t p, uint32_t g, const uint32_t a[4], uint32_t out[4]) {
+    if (!(a[0] | a[1] | a[2] | a[3])) return false;
+    auto mul = [&](uint32_t x, uint32_t y) { return host_mulmod(x, y, p); };
+    struct Q { uint32_t u, v; };   // u + v Y
+    auto qmul = [&](Q x, Q y) { return Q{fp_add(mul(x.u, y.u), mul(g, mul(x.v, y.v)), p), fp_add(mul(x.u, y.v), mul(x.v, y.u), p)}; };
+    const Q A{a[0], a[2]}, B{a[1], a[3]};
+    const Q A2 = qmul(A, A), B2 = qmul(B, B);
+    const Q D{fp_sub(A2.u, mul(g, B2.v), p), fp_sub(A2.v, B2.u, p)};   // A^2 - Y B^2, Y (u + v Y) = g v + u Y
+    const uint32_t norm = fp_sub(mul(D.u, D.u), mul(g, mul(D.v, D.v)), p);
+    const uint32_t ni = host_powmod(norm, p - 2, p);
+    const Q Di{mul(D.u, ni), mul(fp_neg(D.v, p), ni)};
+    const Q rA = qmul(A, Di), rB = qmul(B, Di);
+    out[0] = rA.u; out[2] = rA.v;
+    out[1] = fp_neg(rB.u, p); out[3] = fp_neg(rB.v, p);
+    return true;
+}

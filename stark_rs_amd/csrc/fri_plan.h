@@ -37,6 +37,24 @@ inline FriLayout fri_layout(const smi_fri_cfg &cfg, bool do_query) {
     return l;
 }
 
+// The same layout for FRI over the quartic extension (include/stark_mi.h, "Extension FRI"): an element is four u64, so the
+// last codeword is one record of 4 last_n values and a triple one record of 12; rounds, paths and their order are unchanged.
+inline FriLayout fri_layout_ext(const smi_fri_cfg &cfg) {
+    FriLayout l = fri_layout(cfg, true);
+    const uint64_t N = cfg.domain_length, t = cfg.num_colinearity_tests;
+    l.off_layers = l.off_last + 9 + 32 * l.last_n;
+    size_t off = l.off_layers;
+    for (uint64_t i = 0; i + 1 < l.R; i++) {
+        const uint32_t d = ilog2(N >> i);
+        l.off_triples[i] = off;
+        off += (9 + 96) * t;
+        l.off_paths[i] = off;
+        off += t * (2 * (9 + 32ull * d) + (9 + 32ull * (d - 1)));
+    }
+    l.proof_len = off;
+    return l;
+}
+
 // The fused tail (hash.hip, fri_tail_kernel) finishes every remaining round in one workgroup launch.  It runs the
 // sixteen-lane Fiat-Shamir round, which knows phase 0 only, and holds at most max_rounds rounds.
 inline bool fri_tail_starts(uint32_t phase, uint64_t len, uint64_t tail_len, uint64_t rounds_left, uint64_t max_rounds) {

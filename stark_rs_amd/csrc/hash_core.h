@@ -436,6 +436,39 @@ SMI_HD void fs_absorb_root_phase(uint32_t *fs_words, const uint32_t m[8], uint32
     if (alpha_out) *alpha_out = fs_challenge_phase(fs_words, phase);
 }
 
+// n <= 32 further bytes on a transcript at phase k (the general step fs_absorb_root_phase takes for n = 32) -> the new
+// phase: the bytes that complete the pending chunk, its mix when it is complete, the rest at the head of the next one
+SMI_HD uint32_t fs_absorb_bytes_phase(State &st, uint32_t phase, const uint8_t *msg, int n) {
+    int k = (int)phase;
+    const int first = n < 32 - k ? n : 32 - k;
+    absorb_bytes_at(st, k, msg, first);
+    k += first;
+    if (k == 32) {
+        mix(st);
+        absorb_bytes_at(st, 0, msg + first, n - first);
+        k = n - first;
+    }
+    return (uint32_t)k;
+}
+// One Fiat-Shamir round of FRI over the quartic extension (include/stark_mi.h, "Extension FRI"): the root, then for e' =
+// 0 .. 3 the counter e' as 8 little-endian bytes with a challenge after each -- coordinate e' of the round's alpha.  The
+// four challenges hash four prefixes of one transcript, so they are independent once the cheap absorbs are done: this is
+// the work of ONE of four lanes.  Lane e absorbs the root and the counters 0 .. e into a copy of the state (fs_out) and
+// closes it: *alpha = coordinate e.  fs_out of lane 3 is the state after the round; 64 bytes went in, the phase stands.
+SMI_HD void fs_round_ext_lane(const uint32_t *fs_in, const uint32_t m[8], uint32_t phase, int e, uint32_t fs_out[16], uint64_t *alpha) {
+    for (int i = 0; i < 16; i++) fs_out[i] = fs_in[i];
+    fs_absorb_root_phase(fs_out, m, phase, nullptr, nullptr);
+    State st;
+    for (int i = 0; i < 16; i++) st.s[i] = fs_out[i];
+    uint32_t k = phase;
+    for (int j = 0; j <= e; j++) {
+        const uint8_t ctr[8] = {(uint8_t)j, 0, 0, 0, 0, 0, 0, 0};
+        k = fs_absorb_bytes_phase(st, k, ctr, 8);
+    }
+    for (int i = 0; i < 16; i++) fs_out[i] = st.s[i];
+    *alpha = fs_challenge_phase(fs_out, k);
+}
+
 // Hash::from_field_elements(&[v as u64]) (src/hash.rs:32-35 as used by src/fri.rs:118-121):
 // 8 message bytes (LE u64 of a u32 residue: the upper four are zero), 1 + 8 mixes.
 // the 8-byte chunk of a leaf in natural layout: it touches bytes 0..14 -- v_0..v_7 as in

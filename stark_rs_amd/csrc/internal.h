@@ -253,6 +253,15 @@ struct FriResult {
 };
 int fri_run(smi_ctx *ctx, const FriRequest &rq, FriResult *res);
 
+// Fri::prove over the quartic extension (fri.hip): the plain loop row tree -> Fiat-Shamir round -> fold -> ... -> query ->
+// emit over a codeword of four coordinate columns `stride` apart; everything stays on the device until one copy-back.
+struct FriExtResult {
+    std::vector<uint8_t> proof;
+    std::vector<uint64_t> top;      // top-level indices
+};
+int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
+                FriExtResult *res);
+
 // launches (defined in the .hip files; every function one .hip file defines and another calls is declared here, once --
 // the MgSide ones in mgpu_core.h)
 // hash.hip
@@ -275,6 +284,7 @@ int launch_fold_shard(smi_ctx *ctx, const uint32_t *d_lo, const uint32_t *d_hi, 
                       const uint64_t *d_alpha, uint64_t offset, uint64_t omega, uint32_t *d_out);
 // the x^-1 table of the fold out of a codeword of len elements on offset * <omega> (src/ff.rs:182: no division by zero)
 int fri_fold_tables(smi_ctx *ctx, uint32_t offset, uint32_t omega, uint64_t len, ScaleTables *S);
+int ext_field_check(smi_ctx *ctx);   // SMI_ERR_BAD_ARG unless X^4 - g is irreducible over the context's field (fri_core.h)
 inline uint32_t fri_inv2_m(const smi_ctx *c) { return (uint32_t)(((uint64_t)h_inv(c, 2) << 32) % c->fs.F.p); }   // 2^-1, Montgomery form
 int launch_fs_init(smi_ctx *ctx, void *fs, const FsSeed *seed);   // seed == nullptr: a fresh transcript
 int launch_fs_round(smi_ctx *ctx, void *fs, const uint8_t *root, uint8_t *proof_slot, uint64_t *alpha_out, uint32_t phase);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "air_core.h"
+#include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
 #include "proof_parse.h"
@@ -55,6 +56,38 @@ int challenge_of(smi_ctx *ctx, const std::vector<uint8_t> &transcript, uint64_t 
     uint8_t d[32];
     SMI_TRY(smi_hash_bytes(ctx, transcript.data(), transcript.size(), d));
     *out = get_u64(d);
+    return SMI_OK;
+}
+
+// Fri::sample_indices (src/fri.rs:168-213) from the index-seed challenge, counters hashed a batch at a time
+int sample_top(smi_ctx *ctx, uint64_t seed_ch, uint64_t size, uint64_t reduced_size, uint64_t t, std::vector<uint64_t> *top_out) {
+    if (t > 2 * reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, nullptr);
+    if (t > reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, nullptr);
+    uint8_t seed[32], seed_msg[8];
+    for (int k = 0; k < 8; k++) seed_msg[k] = (uint8_t)(seed_ch >> (8 * k));
+    SMI_TRY(smi_hash_bytes(ctx, seed_msg, 8, seed));                                // Hash::from_u64
+    std::vector<uint64_t> &top = *top_out, reduced;
+    top.clear();
+    for (uint32_t counter = 0; top.size() < t;) {
+        const size_t run = 2 * (size_t)(t - top.size()) + 8;
+        std::vector<uint8_t> msgs(36 * run), dig(32 * run);
+        for (size_t k = 0; k < run; k++) {
+            memcpy(&msgs[36 * k], seed, 32);
+            for (int b = 0; b < 4; b++) msgs[36 * k + 32 + b] = (uint8_t)((counter + k) >> (8 * b));
+        }
+        SMI_TRY(smi_hash_bytes_batch(ctx, msgs.data(), run, 36, dig.data()));
+        for (size_t k = 0; k < run && top.size() < t; k++, counter++) {
+            uint64_t acc = 0;                                                       // sample_index: the last eight digest bytes, big-endian
+            for (int b = 24; b < 32; b++) acc = (acc << 8) | dig[32 * k + b];
+            const uint64_t index = acc % size, ri = index % reduced_size;
+            bool seen = false;
+            for (uint64_t q : reduced) seen |= q == ri;
+            if (!seen) {
+                top.push_back(index);
+                reduced.push_back(ri);
+            }
+        }
+    }
     return SMI_OK;
 }
 
@@ -119,35 +152,9 @@ int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, con
     for (size_t i = degree_bound; i < n_last; i++)                                  // :392-397: degree <= degree_bound - 1
         if (coeffs[i] != 0) return reject(ctx, accept, "last codeword does not correspond to polynomial of low enough degree");
 
-    // index sampling (:400-405, :168-213), counters hashed a batch at a time
-    const uint64_t size = N >> 1, reduced_size = N >> (R - 1);
-    if (t > 2 * reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, nullptr);
-    if (t > reduced_size) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, nullptr);
-    const uint64_t seed_ch = hashc::fs_challenge_phase(fs, fs0.phase);
-    uint8_t seed[32], seed_msg[8];
-    for (int k = 0; k < 8; k++) seed_msg[k] = (uint8_t)(seed_ch >> (8 * k));
-    SMI_TRY(smi_hash_bytes(ctx, seed_msg, 8, seed));                                // Hash::from_u64
-    std::vector<uint64_t> top, reduced;
-    for (uint32_t counter = 0; top.size() < t;) {
-        const size_t run = 2 * (size_t)(t - top.size()) + 8;
-        std::vector<uint8_t> msgs(36 * run), dig(32 * run);
-        for (size_t k = 0; k < run; k++) {
-            memcpy(&msgs[36 * k], seed, 32);
-            for (int b = 0; b < 4; b++) msgs[36 * k + 32 + b] = (uint8_t)((counter + k) >> (8 * b));
-        }
-        SMI_TRY(smi_hash_bytes_batch(ctx, msgs.data(), run, 36, dig.data()));
-        for (size_t k = 0; k < run && top.size() < t; k++, counter++) {
-            uint64_t acc = 0;                                                       // sample_index: the last eight digest bytes, big-endian
-            for (int b = 24; b < 32; b++) acc = (acc << 8) | dig[32 * k + b];
-            const uint64_t index = acc % size, ri = index % reduced_size;
-            bool seen = false;
-            for (uint64_t q : reduced) seen |= q == ri;
-            if (!seen) {
-                top.push_back(index);
-                reduced.push_back(ri);
-            }
-        }
-    }
+    // index sampling (:400-405, :168-213)
+    std::vector<uint64_t> top;
+    SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, fs0.phase), N >> 1, N >> (R - 1), t, &top));
     if (top_out) *top_out = top;
 
     uint64_t om = cfg.omega % p, off = cfg.offset % p;
@@ -225,6 +232,157 @@ int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, con
     if (used) *used = at;
     return SMI_OK;
 }
+// The verifier of FRI over the quartic extension (include/stark_mi.h, "Extension FRI") on objs[0..]; the structure of
+// fri_verify_objs with four-coordinate elements.  pv_val gets four values per entry, layer0_ab eight per test (a, then b).
+int fri_verify_ext_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, const std::vector<Obj> &objs, int *accept,
+                        std::vector<uint64_t> *top_out, std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val,
+                        std::vector<uint64_t> *layer0_ab, size_t *used) {
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g;
+    const uint64_t t = cfg.num_colinearity_tests, N = cfg.domain_length;
+    uint64_t R = 0;
+    smi_fri_num_rounds(&cfg, &R);
+    if (R == 0) return reject(ctx, accept, "No FRI roots extracted");
+    size_t at = 0;
+    auto pop = [&]() -> const Obj * { return at < objs.size() ? &objs[at++] : nullptr; };
+    uint32_t fs[16];
+    memcpy(fs, fs0.s, sizeof fs);
+    std::vector<const uint8_t *> roots;
+    std::vector<uint64_t> alphas;   // four unreduced coordinates per round but the last
+    for (uint64_t r = 0; r < R; r++) {
+        const Obj *o = pop();
+        if (!o || o->tag != 0) return reject(ctx, accept, "Failed to extract Merkle root");
+        roots.push_back(o->p);
+        uint32_t m[8];
+        memcpy(m, o->p, 32);
+        if (r + 1 == R) {
+            hashc::fs_absorb_root_phase(fs, m, fs0.phase, nullptr, nullptr);
+            break;
+        }
+        uint32_t out[16];
+        for (int e = 0; e < 4; e++) {
+            uint64_t a = 0;
+            hashc::fs_round_ext_lane(fs, m, fs0.phase, e, out, &a);
+            alphas.push_back(a);
+        }
+        memcpy(fs, out, sizeof fs);
+    }
+    const size_t n_last = (size_t)(N >> (R - 1));
+    const Obj *lo = pop();
+    if (!lo || lo->tag != 2) return reject(ctx, accept, "Failed to extract last codeword");
+    if (lo->count != 4 * n_last) return reject(ctx, accept, "last codeword: expected four values per element of the last domain");
+    std::vector<uint64_t> last(4 * n_last);
+    for (size_t i = 0; i < 4 * n_last; i++)
+        if ((last[i] = get_u64(lo->p + 8 * i)) >= p) return reject(ctx, accept, "last codeword: a coordinate is not canonical");
+    // row-leaf root: leaf i = Hash::from_field_elements of element i's four u64s as they stand in the proof
+    std::vector<uint8_t> digests(32 * n_last);
+    for (size_t i = 0; i < n_last; i++) {
+        uint32_t d[8];
+        hashc::hash_bytes(lo->p + 32 * i, 32, d);
+        memcpy(&digests[32 * i], d, 32);
+    }
+    uint8_t last_root[32];
+    SMI_TRY(smi_merkle_commit(ctx, digests.data(), n_last, last_root));
+    if (memcmp(last_root, roots.back(), 32) != 0) return reject(ctx, accept, "last codeword is not well formed");
+    const size_t degree_bound = n_last / cfg.expansion_factor;
+    if (degree_bound == 0) return reject(ctx, accept, "last codeword too small");
+    uint64_t last_omega = cfg.omega % p, last_offset = cfg.offset % p;
+    for (uint64_t i = 0; i + 1 < R; i++) {
+        last_omega = mulm(last_omega, last_omega, p);
+        last_offset = mulm(last_offset, last_offset, p);
+    }
+    if (n_last > ((uint64_t)1 << ctx->fs.K) || last_omega != h_root(ctx, ilog2(n_last)) || last_offset == 0)
+        return smi_fail(ctx, SMI_ERR_NOT_GEOMETRIC, "Fri::verify: the last layer's domain is not offset * <primitive root>");
+    // EVERY coordinate is a base-field codeword on the last domain and must be of low degree
+    for (int e = 0; e < 4; e++) {
+        std::vector<uint64_t> col(n_last), coeffs(n_last);
+        for (size_t i = 0; i < n_last; i++) col[i] = last[4 * i + e];
+        if (n_last > 1) SMI_TRY(smi_intt(ctx, col.data(), coeffs.data(), ilog2(n_last), last_offset));
+        else coeffs = col;
+        for (size_t i = degree_bound; i < n_last; i++)
+            if (coeffs[i] != 0) return reject(ctx, accept, "last codeword does not correspond to polynomial of low enough degree");
+    }
+    std::vector<uint64_t> top;
+    SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, fs0.phase), N >> 1, n_last, t, &top));
+    if (top_out) *top_out = top;
+
+    uint64_t om = cfg.omega % p, off = cfg.offset % p;
+    for (uint64_t r = 0; r + 1 < R; r++) {
+        const uint64_t half = N >> (r + 1);
+        std::vector<uint64_t> ci(t), bi(t);
+        std::vector<const uint8_t *> rec(t);
+        const uint32_t al[4] = {(uint32_t)(alphas[4 * r] % p), (uint32_t)(alphas[4 * r + 1] % p), (uint32_t)(alphas[4 * r + 2] % p), (uint32_t)(alphas[4 * r + 3] % p)};
+        for (uint64_t s = 0; s < t; s++) {
+            ci[s] = top[s] % half;
+            bi[s] = ci[s] + half;
+            const Obj *o = pop();
+            if (!o || o->tag != 2) return reject(ctx, accept, "Failed to extract triple values");
+            if (o->count != 12) return reject(ctx, accept, "Expected triple of values");
+            rec[s] = o->p;
+            uint32_t v[12];
+            for (int k = 0; k < 12; k++) {
+                const uint64_t x = get_u64(o->p + 8 * k);
+                if (x >= p) return reject(ctx, accept, "triple: a coordinate is not canonical");
+                v[k] = (uint32_t)x;
+            }
+            if (r == 0) {
+                if (pv_idx && pv_val) {
+                    pv_idx->push_back(ci[s]); pv_val->insert(pv_val->end(), v, v + 4);
+                    pv_idx->push_back(bi[s]); pv_val->insert(pv_val->end(), v + 4, v + 8);
+                }
+                if (layer0_ab) layer0_ab->insert(layer0_ab->end(), v, v + 8);
+            }
+            // (x_a, a), (-x_a, b), (alpha, c) colinear over F_q: (b - a)(alpha - x_a) == (c - a)(x_b - x_a), x_a and x_b in F_p
+            const uint32_t ax = (uint32_t)mulm(off, powm(om, ci[s], p), p), bx = (uint32_t)mulm(off, powm(om, bi[s], p), p);
+            uint32_t ba[4], ca[4], lhs[4];
+            for (int e = 0; e < 4; e++) {
+                ba[e] = fp_sub(v[4 + e], v[e], p);
+                ca[e] = fp_sub(v[8 + e], v[e], p);
+            }
+            const uint32_t ax4[4] = {fp_sub(al[0], ax, p), al[1], al[2], al[3]};
+            ext_mul_host(p, g, ba, ax4, lhs);
+            const uint32_t dx = fp_sub(bx, ax, p);
+            for (int e = 0; e < 4; e++)
+                if (lhs[e] != host_mulmod(ca[e], dx, p)) return reject(ctx, accept, "colinearity check failure");
+        }
+        static const char *const miss[3] = {"Failed to extract path for aa", "Failed to extract path for bb", "Failed to extract path for cc"};
+        static const char *const bad[3] = {"merkle authentication path verification fails for aa", "merkle authentication path verification fails for bb",
+                                           "merkle authentication path verification fails for cc"};
+        const uint32_t want_depth[3] = {ilog2(2 * half), ilog2(2 * half), ilog2(half)};
+        std::vector<std::vector<uint8_t>> paths(3), leaves(3);
+        for (uint64_t s = 0; s < t; s++)
+            for (int w = 0; w < 3; w++) {
+                const Obj *o = pop();
+                if (!o || o->tag != 3) return reject(ctx, accept, miss[w]);
+                if (o->count != want_depth[w]) return reject(ctx, accept, bad[w]);
+                paths[w].insert(paths[w].end(), o->p, o->p + 32 * o->count);
+                uint32_t d[8];   // the leaf: the four u64s of a / b / c as they stand in the proof
+                hashc::hash_bytes(rec[s] + 32 * w, 32, d);
+                leaves[w].insert(leaves[w].end(), (const uint8_t *)d, (const uint8_t *)d + 32);
+            }
+        const std::vector<uint64_t> *idxs[3] = {&ci, &bi, &ci};
+        const uint8_t *rt[3] = {roots[r], roots[r], roots[r + 1]};
+        uint64_t first_bad = 3 * t;
+        const char *why = nullptr;
+        for (int w = 0; w < 3 && t; w++) {
+            std::vector<uint8_t> ok(t);
+            if (want_depth[w])
+                SMI_TRY(smi_merkle_verify_batch(ctx, leaves[w].data(), idxs[w]->data(), paths[w].data(), t, want_depth[w], rt[w], ok.data()));
+            else
+                for (uint64_t s = 0; s < t; s++) ok[s] = memcmp(&leaves[w][32 * s], rt[w], 32) == 0;
+            for (uint64_t s = 0; s < t; s++)
+                if (!ok[s] && 3 * s + w < first_bad) {
+                    first_bad = 3 * s + w;
+                    why = bad[w];
+                }
+        }
+        if (why) return reject(ctx, accept, why);
+        om = mulm(om, om, p);
+        off = mulm(off, off, p);
+    }
+    *accept = 1;
+    if (used) *used = at;
+    return SMI_OK;
+}
 size_t fri_object_count(const smi_fri_cfg &cfg) {
     uint64_t R = 0;
     smi_fri_num_rounds(&cfg, &R);
@@ -261,6 +419,29 @@ int smi_fri_verify_fs(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *trans
 int smi_fri_verify(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *proof, size_t proof_len, int *accept, uint64_t *pv_indices,
                    uint64_t *pv_values, size_t *n_pv) {
     return smi_fri_verify_fs(ctx, cfg, nullptr, 0, proof, proof_len, accept, pv_indices, pv_values, n_pv, nullptr);
+}
+
+int smi_fri_verify_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                       size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed) {
+    if (!ctx || !cfg || (!proof && proof_len) || !accept || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    if (n_pv) *n_pv = 0;
+    if (consumed) *consumed = 0;
+    SMI_TRY(ext_field_check(ctx));
+    SMI_TRY(smi_fri_check(ctx, cfg));
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
+    size_t end = 0;
+    const std::vector<Obj> objs = parse(proof, proof_len, (size_t)-1, &end);
+    std::vector<uint64_t> pi, pv;
+    size_t used = 0;
+    const int rc = fri_verify_ext_objs(ctx, *cfg, seed, objs, accept, nullptr, &pi, &pv, nullptr, &used);
+    if (n_pv) *n_pv = pi.size();
+    if (pv_indices && !pi.empty()) memcpy(pv_indices, pi.data(), 8 * pi.size());
+    if (pv_values && !pv.empty()) memcpy(pv_values, pv.data(), 8 * pv.size());
+    if (rc == SMI_OK && *accept && consumed) (void)parse(proof, proof_len, used, consumed);
+    return rc;
 }
 
 int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *column_roots, const uint8_t *proof, size_t proof_len,
@@ -340,8 +521,10 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
 // root (W column roots, or the one root of the tree over the rows), and the composition codeword recomputed at x_a and
 // x_b with the evaluator the prover's kernel runs (air_core.h) over the opened rows.  Only the transcript and the
 // authentication of the opened rows differ between the two commitments; everything else is this one function.
+// over_ext (with by_rows): weights from the quartic extension -- four counters and four challenges per weight, FRI over F_q, the
+// four coordinates of the composition against the layer-0 triple's a and b (smi_air_verify_ext).
 static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint8_t *column_roots, const uint8_t *proof,
-                           size_t proof_len, int *accept, bool by_rows) {
+                           size_t proof_len, int *accept, bool by_rows, bool over_ext = false) {
     std::string why;
     uint64_t E = 0;
     const int vrc = air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
@@ -357,12 +540,19 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     fc.num_colinearity_tests = t;
     // transcript.  Column trees: root c, weight c; then k as 8 LE bytes, weight W + k.  Row tree: the root; then j = 0 ..
     // W + K - 1 as 8 LE bytes, weight j.
-    std::vector<uint64_t> weights(W + K);
+    const uint32_t NE = over_ext ? 4 : 1;   // coordinates per weight and per codeword value
+    std::vector<uint64_t> weights((size_t)NE * (W + K));
     std::vector<uint8_t> transcript;
     auto absorb_index = [&](uint64_t j) {
         for (int i = 0; i < 8; i++) transcript.push_back((uint8_t)(j >> (8 * i)));
     };
-    if (by_rows) {
+    if (over_ext) {   // the root; then m = 0 .. 4 (W + K) - 1 as 8 LE bytes, challenge m = coordinate m mod 4 of weight m / 4
+        transcript.assign(column_roots, column_roots + 32);
+        for (uint32_t m = 0; m < 4 * (W + K); m++) {
+            absorb_index(m);
+            SMI_TRY(challenge_of(ctx, transcript, &weights[m]));
+        }
+    } else if (by_rows) {
         transcript.assign(column_roots, column_roots + 32);
         for (uint32_t j = 0; j < W + K; j++) {
             absorb_index(j);
@@ -384,7 +574,8 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc), &end);
     std::vector<uint64_t> top, ab;
     size_t used = 0;
-    SMI_TRY(fri_verify_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
+    if (over_ext) SMI_TRY(fri_verify_ext_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
+    else SMI_TRY(fri_verify_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
     if (!*accept) return SMI_OK;
     *accept = 0;
     const size_t R = K ? 4 : 2, rec = 9 + 8 * (size_t)W, prec = 9 + 32 * (size_t)logN, need = t * R * rec + t * (by_rows ? 1 : W) * R * prec;
@@ -447,8 +638,8 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
             for (size_t k = 0; k < 2; k++) at[2 * s + k] = pos[R * s + k];
         SMI_TRY(air_periodic_at(ctx, cfg, H, at, &per));
     }
-    std::vector<uint32_t> w_m(W + K);
-    for (uint32_t i = 0; i < W + K; i++) w_m[i] = to_mont_u64(weights[i], F);
+    std::vector<uint32_t> w_m(over_ext ? 4 * AIR_MAX_WEIGHTS : W + K, 0);   // over_ext: coordinate e of weight j at e * AIR_MAX_WEIGHTS + j
+    for (uint32_t i = 0; i < NE * (W + K); i++) w_m[over_ext ? (i & 3) * AIR_MAX_WEIGHTS + (i >> 2) : i] = to_mont_u64(weights[i], F);
     for (uint64_t s = 0; s < t; s++)
         for (size_t k = 0; k < 2; k++) {
             const uint64_t i = pos[R * s + k];
@@ -457,17 +648,17 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                     if (rows[(R * s + r) * W + c] >= p) return reject(ctx, accept, "air openings: an opened value is not canonical");
             const uint64_t *cur = &rows[(R * s + k) * W], *nxt = K ? &rows[(R * s + k + 2) * W] : nullptr;
             const uint32_t x_m = air_to_m((uint32_t)mulm(cfg->lde_offset, powm(fc.omega, i, p), p), (uint32_t)p), ib = (uint32_t)(i & (B - 1));
-            uint32_t got = 0;
-            air_compose_points<1>(
-                H.dev, F, w_m.data(), &x_m, &ib,
-                [&](int, uint32_t var) {   // AirDev::fac's numbering: W + Q operands at this row, then at the next
-                    const bool next = var >= W + Q;
-                    const uint32_t c = next ? var - (W + Q) : var;
-                    if (c >= W) return per[(2 * s + k) * 2 * Q + (next ? Q : 0) + (c - W)];
-                    return (uint32_t)(next ? nxt[c] : cur[c]);
-                },
-                &got);
-            if (got != ab[2 * s + k] % p) return reject(ctx, accept, "air openings: the composition of the opened rows is not the codeword value");
+            auto operand = [&](int, uint32_t var) {   // AirDev::fac's numbering: W + Q operands at this row, then at the next
+                const bool next = var >= W + Q;
+                const uint32_t c = next ? var - (W + Q) : var;
+                if (c >= W) return per[(2 * s + k) * 2 * Q + (next ? Q : 0) + (c - W)];
+                return (uint32_t)(next ? nxt[c] : cur[c]);
+            };
+            uint32_t got[4] = {0, 0, 0, 0};
+            if (over_ext) air_compose_points_ext<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
+            else air_compose_points<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
+            for (uint32_t e = 0; e < NE; e++)
+                if (got[e] != ab[(2 * s + k) * NE + e] % p) return reject(ctx, accept, "air openings: the composition of the opened rows is not the codeword value");
         }
     *accept = 1;
     return SMI_OK;
@@ -488,4 +679,13 @@ int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     DeviceGuard dg__(ctx);
     *accept = 0;
     return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true);
+}
+
+int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                       size_t proof_len, int *accept) {
+    if (!ctx || !cfg || !air || !row_root || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(ext_field_check(ctx));
+    return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true, true);
 }

@@ -393,6 +393,12 @@ class Engine:
     def dev_fri_fold(self, d_in, length, d_alpha, offset, omega, d_out):
         self._ck(self.L.smi_dev_fri_fold(self.h, vp(d_in), length, vp(d_alpha), offset, omega, vp(d_out)))
 
+    def dev_fri_fold_ext(self, d_in, length, stride, d_alpha, offset, omega, d_out, out_stride=None):
+        """smi_dev_fri_fold_ext: the fold of a codeword over the quartic extension -- four coordinate columns `stride`
+        apart in, four columns out_stride (default length / 2) apart out; d_alpha = four unreduced u64 on the device"""
+        out_stride = length // 2 if out_stride is None else out_stride
+        self._ck(self.L.smi_dev_fri_fold_ext(self.h, vp(d_in), length, stride, vp(d_alpha), offset, omega, vp(d_out), out_stride))
+
     def dev_fri_fold_shard(self, d_lo, d_hi, count, index0, full_len, d_alpha, offset, omega, d_out):
         self._ck(self.L.smi_dev_fri_fold_shard(self.h, vp(d_lo), vp(d_hi), count, index0, full_len, vp(d_alpha), offset, omega,
                                                vp(d_out)))
@@ -410,6 +416,29 @@ class Engine:
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         return b, [int(v) for v in top[:cfg.num_colinearity_tests]]
+
+    def dev_fri_prove_ext(self, cfg, d_codeword, length, stride=None, transcript=b""):
+        """smi_dev_fri_prove_ext: Fri::prove over the quartic extension on four device coordinate columns `stride`
+        (default length) apart, continuing the caller's transcript (host bytes) -> (proof bytes, top-level indices)"""
+        proof, plen = vp(), C.c_size_t()
+        top = np.zeros(max(cfg.num_colinearity_tests, 1), dtype=np.uint64)
+        t = bytes(transcript)
+        self._ck(self.L.smi_dev_fri_prove_ext(self.h, C.byref(cfg), t if t else None, len(t), vp(d_codeword), length,
+                                              length if stride is None else stride, C.byref(proof), C.byref(plen), top.ctypes.data))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        return b, [int(v) for v in top[:cfg.num_colinearity_tests]]
+
+    def fri_verify_ext(self, cfg, proof: bytes, transcript=b""):
+        """smi_fri_verify_ext -> (accept, polynomial_values [(index, [c0, c1, c2, c3])], bytes consumed, reason)"""
+        t = bytes(transcript)
+        n = 2 * max(cfg.num_colinearity_tests, 1)
+        idx, val = np.zeros(n, dtype=np.uint64), np.zeros(4 * n, dtype=np.uint64)
+        acc, npv, used = C.c_int(), C.c_size_t(), C.c_size_t()
+        self._ck(self.L.smi_fri_verify_ext(self.h, C.byref(cfg), t if t else None, len(t), proof, len(proof), C.byref(acc), idx.ctypes.data,
+                                           val.ctypes.data, C.byref(npv), C.byref(used)))
+        pv = [(int(idx[i]), [int(v) for v in val[4 * i:4 * i + 4]]) for i in range(npv.value)]
+        return bool(acc.value), pv, used.value, ("" if acc.value else self.L.smi_last_error(self.h).decode())
 
     def dev_combine_columns(self, d_cols, n_cols, length, stride, d_weights, d_out):
         self._ck(self.L.smi_dev_combine_columns(self.h, vp(d_cols), n_cols, length, stride, vp(d_weights), vp(d_out)))
@@ -452,6 +481,16 @@ class Engine:
         stride = (1 << (log_n + log_blowup)) if stride is None else stride
         self._ck(self.L.smi_dev_air_compose(self.h, C.byref(cfg), C.byref(a), vp(d_lde), stride, vp(d_weights), vp(d_out)))
 
+    def dev_air_compose_ext(self, air, d_lde, n_cols, log_n, log_blowup, d_weights, d_out, stride=None, out_stride=None, trace_offset=1,
+                            lde_offset=None):
+        """smi_dev_air_compose_ext: the composition under 4 (n_cols + K) unreduced device weights (coordinate e of weight
+        j at 4 j + e) into four coordinate columns out_stride (default N) apart"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        a = self._air(air)
+        N = 1 << (log_n + log_blowup)
+        self._ck(self.L.smi_dev_air_compose_ext(self.h, C.byref(cfg), C.byref(a), vp(d_lde), N if stride is None else stride, vp(d_weights),
+                                                vp(d_out), N if out_stride is None else out_stride))
+
     def dev_air_check(self, air, d_trace_cols, n_cols, log_n):
         """-> (ok, constraint, row, sentence): the first violation of the AIR on the trace itself; constraint is the
         boundary point's position, or n_boundary + k for transition constraint k"""
@@ -463,11 +502,14 @@ class Engine:
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False):
+                      timed=False, check=True, row_leaves=False, ext=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
-        one root, shape (1, 32), and the proof opens every queried position once (verify with row_leaves=True)."""
+        one root, shape (1, 32), and the proof opens every queried position once (verify with row_leaves=True).
+        ext (needs row_leaves): smi_dev_air_prove_ext -- weights and FRI over the quartic extension."""
+        if ext and not row_leaves:
+            raise StarkMiError(-50, "dev_air_prove(ext=True) commits to one tree over the rows: pass row_leaves=True")
         a = self._air(air)
         if check:
             ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
@@ -478,7 +520,7 @@ class Engine:
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
         stage = (C.c_double * 5)()
-        prove = self.L.smi_dev_air_prove_rows if row_leaves else self.L.smi_dev_air_prove
+        prove = self.L.smi_dev_air_prove_ext if ext else (self.L.smi_dev_air_prove_rows if row_leaves else self.L.smi_dev_air_prove)
         self._ck(prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof),
                                           C.byref(plen), top.ctypes.data, stage if timed else None))
         b = C.string_at(proof, plen.value)
@@ -489,14 +531,16 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False):
+                   lde_offset=None, row_leaves=False, ext=False):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
-        the tree over the rows"""
+        the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext"""
+        if ext and not row_leaves:
+            raise StarkMiError(-50, "air_verify(ext=True) checks a proof over one row tree: pass row_leaves=True")
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, row_leaves)
         a = self._air(air)
         roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
         acc = C.c_int()
-        verify = self.L.smi_air_verify_rows if row_leaves else self.L.smi_air_verify
+        verify = self.L.smi_air_verify_ext if ext else (self.L.smi_air_verify_rows if row_leaves else self.L.smi_air_verify)
         if row_leaves and roots.size != 32:
             raise StarkMiError(-50, "air_verify(row_leaves=True) takes the one 32-byte root of the row tree")
         self._ck(verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc)))
@@ -583,6 +627,25 @@ def air_plan(p, air, cfg):
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value
+
+
+def _ext_call(fn, p, g, *elems):
+    arrs = [(C.c_uint64 * 4)(*[int(v) for v in e]) for e in elems]
+    out = (C.c_uint64 * 4)()
+    st = fn(p, g, *arrs, out)
+    if st:
+        raise StarkMiError(st, _lib.status_string(st))
+    return [int(v) for v in out]
+
+
+def ext_mul(p, g, a, b):
+    """smi_ext_mul (host only, no GPU): a * b in F_p[X] / (X^4 - g), four canonical coordinates each, low degree first"""
+    return _ext_call(_lib.lib().smi_ext_mul, p, g, a, b)
+
+
+def ext_inv(p, g, a):
+    """smi_ext_inv (host only, no GPU); StarkMiError "no inverse" for zero"""
+    return _ext_call(_lib.lib().smi_ext_inv, p, g, a)
 
 
 def default_engine(p=P_REF, g=G_REF, device=0):

@@ -151,6 +151,71 @@ class FieldElement:
         return f"FieldElement({self.value})"
 
 
+class Ext4:
+    """An element of F_p[X] / (X^4 - g) (include/stark_mi.h, "Quartic extension"): four canonical coordinates, low degree
+    first.  Products and inverses go through the library's host helpers (smi_ext_mul / smi_ext_inv: no GPU needed)."""
+    __slots__ = ("c", "p", "g")
+
+    def __init__(self, coords, p, g):
+        coords = [int(v) % p for v in coords]
+        if len(coords) != 4:
+            raise ValueError("Ext4 takes four coordinates")
+        self.c, self.p, self.g = tuple(coords), p, g
+
+    @classmethod
+    def embed(cls, value, p, g):
+        return cls((value, 0, 0, 0), p, g)
+
+    def _same(self, o):
+        if isinstance(o, FieldElement):
+            o = Ext4.embed(o.value, self.p, self.g)
+        elif isinstance(o, int):
+            o = Ext4.embed(o, self.p, self.g)
+        if (o.p, o.g) != (self.p, self.g):
+            raise ValueError("Ext4 operands of different fields")
+        return o
+
+    def __eq__(self, o):
+        return isinstance(o, Ext4) and (self.c, self.p, self.g) == (o.c, o.p, o.g)
+
+    def __hash__(self):
+        return hash((self.c, self.p, self.g))
+
+    def __add__(self, o):
+        o = self._same(o)
+        return Ext4([a + b for a, b in zip(self.c, o.c)], self.p, self.g)
+
+    def __sub__(self, o):
+        o = self._same(o)
+        return Ext4([a - b for a, b in zip(self.c, o.c)], self.p, self.g)
+
+    def __neg__(self):
+        return Ext4([-a for a in self.c], self.p, self.g)
+
+    def __mul__(self, o):
+        from .engine import ext_mul
+        return Ext4(ext_mul(self.p, self.g, self.c, self._same(o).c), self.p, self.g)
+
+    def inv(self):
+        from .engine import ext_inv
+        return Ext4(ext_inv(self.p, self.g, self.c), self.p, self.g)     # "no inverse" for zero, like src/ff.rs:171
+
+    def __truediv__(self, o):
+        return self * self._same(o).inv()
+
+    def pow(self, e):
+        r, b = Ext4.embed(1, self.p, self.g), self
+        while e:
+            if e & 1:
+                r = r * b
+            b = b * b
+            e >>= 1
+        return r
+
+    def __repr__(self):
+        return f"Ext4{self.c}"
+
+
 def _vals(elems):
     return np.fromiter((e.value for e in elems), dtype=np.uint64, count=len(elems))
 

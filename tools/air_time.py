@@ -16,7 +16,13 @@ period n) and (b) as four more trace columns (W = 8, Q = 0): compose kernel time
 leaves (a) out: what a library without periodic columns (SMI_LIB) can run.
 rows: smi_dev_air_prove_rows beside smi_dev_air_prove on the same trace -- empty and mixer at (W = 4, n = 2^22) and the
 32-constraint AIR at (W = 64, n = 2^18): median of nine calls, the five stages and the proof length of both.  --no-rows leaves
-them out: what a library without the row-committed entry points can run."""
+them out: what a library without the row-committed entry points can run.
+ext (--ext-only: nothing else): the quartic-extension legs.  air_compose_ext_kernel beside FOUR launches of
+air_compose_kernel (what a caller without it does for four weight vectors) on the same columns, against a device copy of
+4 (W + 4) N bytes; fri_fold_ext_kernel at 2^25 elements against a device copy of its 48 bytes per output element;
+smi_dev_air_prove_ext(mixer) beside smi_dev_air_prove_rows(mixer) on one trace, median of nine with the stages.
+--no-ext leaves them out (a build without the entry points skips them by itself).
+--single-ext: one air_compose_ext_kernel launch per AIR, the run to put under `rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES`."""
 import argparse
 import os
 import statistics
@@ -34,6 +40,9 @@ ap.add_argument("--single", action="store_true", help="one launch per AIR at (W 
 ap.add_argument("--no-periodic", action="store_true", help="skip the legs that need periodic columns")
 ap.add_argument("--no-stark", action="store_true", help="skip smi_dev_stark_prove")
 ap.add_argument("--no-rows", action="store_true", help="skip the smi_dev_air_prove_rows legs")
+ap.add_argument("--ext-only", action="store_true", help="only the quartic-extension legs")
+ap.add_argument("--no-ext", action="store_true", help="skip the quartic-extension legs: what a library without them can run")
+ap.add_argument("--single-ext", action="store_true", help="--single for air_compose_ext_kernel")
 ap.add_argument("--rows-only", action="store_true", help="only the column-tree / row-tree prove pairs")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
@@ -117,14 +126,78 @@ def lanes(periods):
     return air
 
 
-if args.single:
+def ext_legs():
+    for W, log_n, lb, cases in [(4, 22, 3, None), (64, 18, 3, "wide")]:
+        n, N = 1 << log_n, 1 << (log_n + lb)
+        lde, out4, out = rand_cols(W, N), torch.empty((4, N), dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+        nbytes = 4 * (W + 4) * N
+        cms = copy_ms(nbytes)
+        print(f"ext W={W} n=2^{log_n} B={1 << lb}: 4(W+4)N = {nbytes / 1e9:.3f} GB; device copy of the same bytes {cms:.3f} ms = {nbytes / cms / 1e9:.2f} TB/s", flush=True)
+        for name, air in (airs(W, n)[:3] if cases is None else [("empty", airs(W, n)[0][1]), ("32 constraints", wide(W, 32, n))]):
+            K = len(air.constraints)
+            ch = torch.from_numpy(rng.integers(0, 1 << 62, 4 * (W + K), dtype=np.int64)).to(dev)
+            vecs = [ch[e::4].contiguous() for e in range(4)]
+            flat = air.flatten(p)
+            torch.cuda.synchronize()
+            med, lo, hi = median_kernel_ms(lambda: eng.dev_air_compose_ext(flat, lde.data_ptr(), W, log_n, lb, ch.data_ptr(), out4.data_ptr()),
+                                           "air_compose_ext_kernel")
+
+            def four():
+                for e in range(4):
+                    eng.dev_air_compose(flat, lde.data_ptr(), W, log_n, lb, vecs[e].data_ptr(), out.data_ptr())
+            med4, lo4, hi4 = median_kernel_ms(four, "air_compose_kernel")
+            print(f"  compose_ext {name:16s}: median {med:7.3f} ms (min {lo:.3f}, max {hi:.3f})  {nbytes / med / 1e9:5.2f} TB/s = {100 * cms / med:5.1f} % of the copy;"
+                  f"  four air_compose_kernel launches {med4:7.3f} ms (min {lo4:.3f}, max {hi4:.3f}): x{med4 / med:.2f}", flush=True)
+        del lde, out4, out
+    L = 1 << 25
+    cw, nxt = rand_cols(4, L), torch.empty((4, L // 2), dtype=torch.int32, device=dev)
+    al = torch.from_numpy(rng.integers(0, 1 << 62, 4, dtype=np.int64)).to(dev)
+    omega = pow(g, (p - 1) // L, p)
+    torch.cuda.synchronize()
+    med, lo, hi = median_kernel_ms(lambda: eng.dev_fri_fold_ext(cw.data_ptr(), L, L, al.data_ptr(), g, omega, nxt.data_ptr()), "fri_fold_ext_kernel")
+    nbytes = 48 * (L // 2)
+    cms = copy_ms(nbytes)
+    print(f"fri_fold_ext_kernel 2^25 elements: median {med:.3f} ms (min {lo:.3f}, max {hi:.3f})  {nbytes / med / 1e9:.2f} TB/s; device copy of the same "
+          f"{nbytes / 1e9:.3f} GB {cms:.3f} ms = {nbytes / cms / 1e9:.2f} TB/s: {100 * cms / med:.1f} % of the copy", flush=True)
+    del cw, nxt
+    W, log_n, lb, t = 4, 22, 3, 32
+    trace = rand_cols(W, 1 << log_n)
+    flat = airs(W, 1 << log_n)[2][1].flatten(p)
+    torch.cuda.synchronize()
+    for variant, kw in (("rows", dict(row_leaves=True)), ("ext", dict(row_leaves=True, ext=True)), ("rows", dict(row_leaves=True)), ("ext", dict(row_leaves=True, ext=True))):
+        runs = wall(lambda: eng.dev_air_prove(flat, trace.data_ptr(), W, log_n, lb, t, timed=True, check=False, **kw))
+        med = runs[4]
+        print(f"air_prove[{variant:4s}] mixer, any trace W={W} n=2^{log_n}: median {med[0]:.3f} ms (min {runs[0][0]:.3f}, max {runs[-1][0]:.3f})  "
+              f"stages {({k: round(v, 3) for k, v in med[1]['stage_ms'].items()})}  proof {len(med[1]['proof'])} bytes", flush=True)
+
+
+def wall(fn):
+    for _ in range(2):
+        fn()
+    runs = []
+    for _ in range(9):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        runs.append((1e3 * (time.perf_counter() - t0), res))
+    runs.sort(key=lambda x: x[0])
+    return runs
+
+
+if args.ext_only:
+    ext_legs()
+    eng.close()
+    sys.exit(0)
+
+if args.single or args.single_ext:
     W, log_n, lb = 4, 22, 3
     N = 1 << (log_n + lb)
-    lde, out = rand_cols(W, N), torch.empty(N, dtype=torch.int32, device=dev)
+    lde, out = rand_cols(W, N), torch.empty((4 if args.single_ext else 1) * N, dtype=torch.int32, device=dev)
     for k, (name, air) in enumerate(airs(W, 1 << log_n)):
-        wts = torch.from_numpy(rng.integers(0, 1 << 62, W + len(air.constraints), dtype=np.int64)).to(dev)
+        wts = torch.from_numpy(rng.integers(0, 1 << 62, (4 if args.single_ext else 1) * (W + len(air.constraints)), dtype=np.int64)).to(dev)
         torch.cuda.synchronize()
-        eng.dev_air_compose(air.flatten(p), lde.data_ptr(), W, log_n, lb, wts.data_ptr(), out.data_ptr())
+        compose = eng.dev_air_compose_ext if args.single_ext else eng.dev_air_compose
+        compose(air.flatten(p), lde.data_ptr(), W, log_n, lb, wts.data_ptr(), out.data_ptr())
         eng.sync()
         print(f"dispatch {k}: {name}  ({N} points)", flush=True)
     eng.close()
@@ -151,19 +224,6 @@ if not args.stark_only and not args.rows_only:
 W, log_n, lb, t = 4, 22, 3, 32
 trace = rand_cols(W, 1 << log_n)
 torch.cuda.synchronize()
-
-
-def wall(fn):
-    for _ in range(2):
-        fn()
-    runs = []
-    for _ in range(9):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = fn()
-        runs.append((1e3 * (time.perf_counter() - t0), res))
-    runs.sort(key=lambda x: x[0])
-    return runs
 
 
 def prove_pair(label, flat, tr, Wl, ln):
@@ -226,4 +286,9 @@ if not args.stark_only:
         print(f"air_prove {name:34s}: median {runs[4][0]:.3f} ms  all {[round(r[0], 3) for r in runs]}  stages {runs[4][1]['stage_ms']}", flush=True)
 if not args.stark_only and not args.no_rows:
     pair_legs()
+if not args.stark_only and not args.no_ext:
+    if hasattr(eng, "dev_air_compose_ext"):
+        ext_legs()
+    else:
+        print("ext legs skipped: this build has no quartic-extension entry points (--no-ext says so up front)", flush=True)
 eng.close()

@@ -14,4 +14,4 @@ export SMI_ORACLE_LIB=$PWD/oracle/build/asan/libstark_oracle.so
 export ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:halt_on_error=1
 export UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
 LD_PRELOAD="$ASAN_SO $UBSAN_SO" python3 -m pytest -x -q -m "not gpu" -p no:cacheprovider \
-    tests/test_proof_parse.py tests/test_emu_kernels.py tests/test_launch_plans.py tests/test_air_emu.py tests/test_air_rows_emu.py tests/test_mgpu_gloo.py tests/test_oracle_kats.py tests/test_oracle_fast.py "$@"
+    tests/test_proof_parse.py tests/test_emu_kernels.py tests/test_launch_plans.py tests/test_air_emu.py tests/test_air_rows_emu.py tests/test_ext_emu.py tests/test_mgpu_gloo.py tests/test_oracle_kats.py tests/test_oracle_fast.py "$@"

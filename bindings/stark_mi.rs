@@ -49,6 +49,7 @@ pub const SMI_ERR_NON_CANONICAL: c_int = -51;
 pub const SMI_ERR_UNSUPPORTED_PRIME: c_int = -52;
 pub const SMI_ERR_NOT_GEOMETRIC: c_int = -53;
 pub const SMI_ERR_COLUMNS_NOT_BOUND: c_int = -54;
+pub const SMI_ERR_GRIND_EXHAUSTED: c_int = -55;
 pub const SMI_ERR_HIP: c_int = -100;
 pub const SMI_ERR_NO_DEVICE: c_int = -101;
 pub const SMI_ERR_OOM: c_int = -102;
@@ -124,6 +125,7 @@ pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
 pub const SMI_AIR_MAX_EXP: u32 = 255;
 pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
 pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
+pub const SMI_GRIND_MAX_BITS: u32 = 32;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -218,6 +220,12 @@ extern "C" {
     pub fn smi_fri_verify_ext(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize) -> c_int;
     pub fn smi_dev_air_prove_ext(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64) -> c_int;
     pub fn smi_air_verify_ext(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int) -> c_int;
+    pub fn smi_grind_check(transcript: *const u8, transcript_len: usize, nonce: u64, bits: u32, ok: *mut c_int) -> c_int;
+    pub fn smi_dev_grind(ctx: *mut smi_ctx, transcript: *const u8, transcript_len: usize, bits: u32, max_tries: u64, nonce: *mut u64) -> c_int;
+    pub fn smi_dev_fri_prove_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_codeword: *const u32, len: usize, stride: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, grind_bits: u32, nonce: *mut u64) -> c_int;
+    pub fn smi_fri_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize, grind_bits: u32) -> c_int;
+    pub fn smi_dev_air_prove_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
+    pub fn smi_air_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -828,4 +836,57 @@ impl Air {
             Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
         }
     }
+    /// `smi_dev_air_prove_ext_pow` -> (root of the one tree over the rows, proof bytes): `prove_ext` with `grind_bits`
+    /// proof-of-work bits ground before the query indices are drawn (17 bytes more).  `check_trace` as in `prove`.
+    pub fn prove_ext_pow(&self, ctx: &Context, cfg: &smi_stark_cfg, d_trace_cols: *const u32, check_trace: bool, grind_bits: u32) -> ([u8; 32], Vec<u8>) {
+        if check_trace {
+            if let Some((con, row)) = self.check_trace(ctx, cfg.log_n, d_trace_cols) {
+                let why = unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned();
+                panic!("the trace violates constraint {} at row {}: {}", con, row, why);
+            }
+        }
+        let mut root = [0u8; 32];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_dev_air_prove_ext_pow(ctx.raw, cfg, a, d_trace_cols, root.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut(), grind_bits)
+        }));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (root, bytes)
+    }
+    /// `smi_air_verify_ext_pow` -> `Ok(())` or the reason the proof is rejected; `grind_bits` is the least difficulty
+    /// demanded (a proof ground at more bits is accepted).
+    pub fn verify_ext_pow(&self, ctx: &Context, cfg: &smi_stark_cfg, row_root: &[u8; 32], proof: &[u8], grind_bits: u32) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| unsafe {
+            smi_air_verify_ext_pow(ctx.raw, cfg, a, row_root.as_ptr(), proof.as_ptr(), proof.len(), &mut accept, grind_bits)
+        }));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+}
+
+/// `smi_grind_check` (host only): does `nonce` meet `bits` proof-of-work bits on `transcript`?
+pub fn grind_check(transcript: &[u8], nonce: u64, bits: u32) -> bool {
+    let mut ok = 0 as c_int;
+    let st = unsafe { smi_grind_check(transcript.as_ptr(), transcript.len(), nonce, bits, &mut ok) };
+    if st != SMI_OK {
+        panic!("{}", status_text(st));
+    }
+    ok != 0
+}
+
+/// `smi_dev_grind`: the smallest nonce that meets `bits` proof-of-work bits on `transcript`, searched on the GPU below
+/// `max_tries` (0: the default cap 2^(bits+6)); `None` when the cap is exhausted.
+pub fn grind(ctx: &Context, transcript: &[u8], bits: u32, max_tries: u64) -> Option<u64> {
+    let mut nonce = 0u64;
+    let st = unsafe { smi_dev_grind(ctx.raw, transcript.as_ptr(), transcript.len(), bits, max_tries, &mut nonce) };
+    if st == SMI_ERR_GRIND_EXHAUSTED {
+        return None;
+    }
+    ctx.check(st);
+    Some(nonce)
 }

@@ -59,6 +59,7 @@ enum {
     SMI_ERR_NOT_GEOMETRIC = -53,      /* domain is not offset*omega^k: caller must fall back to the CPU code */
     SMI_ERR_COLUMNS_NOT_BOUND = -54,  /* smi_stark_verify on a proof made without open_columns: nothing in it refers to the
                                          column roots, so it can only be checked as a FRI proof (smi_fri_verify) */
+    SMI_ERR_GRIND_EXHAUSTED = -55,    /* no nonce below the search cap meets the proof-of-work difficulty ("Grinding") */
     /* runtime */
     SMI_ERR_HIP = -100,
     SMI_ERR_NO_DEVICE = -101,
@@ -539,7 +540,9 @@ int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   consecutive u64.
  * Left out: the column-tree variant of the AIR proof; any smi_mgpu_* twin; committed extension-field columns (an
  *   auxiliary trace); out-of-domain sampling; zero-knowledge randomisers; binding an AIR digest into the transcript; the
- *   fold fused into the launch that hashes the row leaves (the base-field path's LEAF_FOLD) and a fused tail. */
+ *   fold fused into the launch that hashes the row leaves (the base-field path's LEAF_FOLD) and a fused tail.  The query
+ *   phase of the entry points of this section rests on t colinearity tests alone; "Grinding" below adds proof-of-work
+ *   bits to it (smi_dev_fri_prove_ext_pow / smi_dev_air_prove_ext_pow). */
 #define SMI_EXT_DEGREE 4
 /* Host only, no context (like smi_air_plan): out = a * b and out = a^-1 in F_q, coordinates canonical.  SMI_ERR_BAD_ARG
  * for a (p, g) the section refuses (p not a prime < 2^31 that is 1 mod 4, g a square or outside 1 .. p-1),
@@ -614,6 +617,55 @@ int smi_dev_air_prove_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms);
 int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
                        size_t proof_len, int *accept);
+
+/* ---- Grinding: proof-of-work bits for the query phase of the extension proofs ----------------
+ * The extension lifts every challenge to 116 bits and more; the query phase still rests on t colinearity tests at
+ * expansion factor E, about t log2(E) bits.  Grinding adds b bits to it: before the query indices are drawn the prover
+ * finds a nonce whose hash with the transcript has b low zero bits and absorbs it; the verifier checks it with one hash.
+ * The entry points above are unchanged, byte for byte; the ones below are the extension ones with a difficulty.
+ *
+ * Definition.  T = the transcript bytes (any length), b = the difficulty, 0 .. SMI_GRIND_MAX_BITS, nu = a u64 nonce.
+ *   pow_ok(T, nu, b): with d = Hash::from_bytes(T || nu as 8 little-endian bytes) (src/hash.rs:7-30), the u64 read
+ *     little-endian from d[24..32] has its b low bits zero.  b = 0 accepts every nonce.
+ *   grind(T, b) = the SMALLEST nu with pow_ok(T, nu, b): proofs are deterministic, byte for byte.
+ *   The check word is taken from bytes 24..31 because the index seed, challenge() of T || nu, is bytes 0..7 of the same
+ *     digest: the seed's bits stay unconstrained.
+ *   Search cap: 2^(b+6) tries unless the caller names one; beyond it the status is SMI_ERR_GRIND_EXHAUSTED (for a uniform
+ *     hash the default cap is missed with probability e^-64).
+ * Extension FRI with grinding.  The transcript of "Extension FRI" up to and including the last root; then nu =
+ *   grind(transcript, b) is absorbed as 8 little-endian bytes; the index seed is challenge() of the transcript as it then
+ *   stands, drawn and used exactly as before.  Proof bytes: the roots, the last-codeword record, then ONE record of tag 2
+ *   with count 1 holding nu (17 bytes), then the layers as before.
+ * Verifier.  After the last-codeword record the next record must be of tag 2 and hold exactly one value; nu is a u64, not
+ *   a field element, so there is no canonical check; pow_ok must hold on the transcript after the last root, otherwise
+ *   *accept = 0 with the reason "proof of work"; then the nonce is absorbed and the indices are sampled.  A proof ground
+ *   at b verifies at every b' <= b (the b low zero bits include the b' low ones): the verifier's grind_bits is the least
+ *   difficulty it demands.  A proof of the entry points without grinding is rejected here and the other way round.
+ * AIR.  The transcript of smi_dev_air_prove_ext, the FRI above, the opening section unchanged: 17 bytes more than the
+ *   proof of smi_dev_air_prove_ext.  stage_ms keeps five values; the search is part of `fri`.
+ * grind_bits > SMI_GRIND_MAX_BITS is SMI_ERR_BAD_ARG (the reason in smi_last_error).
+ * Left out: grinding on the base-field FRI / AIR entry points (their soundness is bounded by the 30-bit field anyway);
+ *   smi_mgpu_* twins; grinding before the composition weights are drawn. */
+#define SMI_GRIND_MAX_BITS 32
+/* Host only, no context (like smi_air_plan): *ok = pow_ok(transcript, nonce, bits).  (NULL, 0) is the empty transcript. */
+int smi_grind_check(const uint8_t *transcript, size_t transcript_len, uint64_t nonce, uint32_t bits, int *ok);
+/* The search alone: *nonce = grind(transcript, bits).  The transcript is host memory; its state goes to the device, one
+ * kernel searches, and the call synchronises once for the answer.  max_tries: the nonces 0 .. max_tries - 1 are tried, 0 =
+ * the default cap 2^(bits+6); SMI_ERR_GRIND_EXHAUSTED when none of them is valid (the context stays usable). */
+int smi_dev_grind(smi_ctx *ctx, const uint8_t *transcript, size_t transcript_len, uint32_t bits, uint64_t max_tries, uint64_t *nonce);
+/* smi_dev_fri_prove_ext / smi_fri_verify_ext with grinding.  *nonce (optional) gets nu.  The search and the absorb run on
+ * the device between the last codeword's emit and the index sampling: the prove gains no host round trip. */
+int smi_dev_fri_prove_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                              size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, uint32_t grind_bits,
+                              uint64_t *nonce);
+int smi_fri_verify_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                           size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed,
+                           uint32_t grind_bits);
+/* smi_dev_air_prove_ext / smi_air_verify_ext with grinding. */
+int smi_dev_air_prove_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                              uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
+int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                           size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

@@ -186,6 +186,14 @@ def lib():
                                      C.POINTER(sz)]),
         "smi_dev_air_prove_ext": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp]),
         "smi_air_verify_ext": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32)]),
+        "smi_grind_check": (i32, [C.c_char_p, sz, C.c_uint64, C.c_uint32, C.POINTER(i32)]),
+        "smi_dev_grind": (i32, [vp, C.c_char_p, sz, C.c_uint32, C.c_uint64, u64p]),
+        "smi_dev_fri_prove_ext_pow": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), vp, C.c_uint32,
+                                            u64p]),
+        "smi_fri_verify_ext_pow": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32), vp, vp, C.POINTER(sz),
+                                         C.POINTER(sz), C.c_uint32]),
+        "smi_dev_air_prove_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
+        "smi_air_verify_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

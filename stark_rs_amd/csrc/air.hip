@@ -356,8 +356,10 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
 // periodic tables, the composition, FRI, the copy-back -- is the same code.
 // ext (with rows): the weights are elements of the quartic extension -- four counters and four challenges per weight --, the
 // composition codeword is four coordinate columns and FRI runs over F_q (smi_dev_air_prove_ext).
+// grind (with ext): the proof-of-work difficulty of the FRI part, or SMI_GRIND_NONE (smi_dev_air_prove_ext_pow).
 static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
-                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows, bool ext = false) {
+                          uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows, bool ext = false,
+                          int grind = SMI_GRIND_NONE) {
     AirHost H;
     uint64_t E = 0;
     SMI_TRY(air_host(ctx, cfg, air, &H, &E));
@@ -444,7 +446,7 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     FriResult res;
     FriExtResult xres;
     if (ext) {
-        SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres));
+        SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, grind));
     } else {
         FriRequest rq(&fc, d_cw, N, true);
         rq.reset_arena = false;
@@ -521,4 +523,13 @@ int smi_dev_air_prove_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
     DeviceGuard dg__(ctx);
     SMI_TRY(ext_field_check(ctx));
     return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true, true);
+}
+
+int smi_dev_air_prove_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                              uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true, true, (int)grind_bits);
 }

@@ -626,6 +626,41 @@ extern "C" uint64_t emu_fs_rounds_ext(const uint8_t *prefix, size_t prefix_len, 
     return hashc::fs_challenge_phase(fs, phase);
 }
 
+// grind_kernel (fri.hip) on the CPU: the kernel's rounds and lanes over the shared per-lane round (hash_core.h grind_round).
+// A grid of `lanes` lanes; round r of lane l tests r S + 2 l and r S + 2 l + 1, S = 2 lanes.  Within a round the lanes are
+// visited in DESCENDING order, so a larger valid nonce is published before a smaller one and the minimum, not the first
+// writer, has to win; a lane reads `best` as it stands when its turn comes.  -> 0 and *nonce, or 1: exhausted.
+extern "C" int emu_grind(const uint32_t *seed_words, uint32_t phase, uint32_t bits, uint64_t max_tries, uint64_t lanes, uint64_t *nonce) {
+    if (bits > 32 || !lanes || phase >= 32) return -1;
+    if (!max_tries) max_tries = 1ull << (bits + 6);
+    const uint64_t S = 2 * lanes;
+    uint64_t best = ~0ull, live = lanes;
+    std::vector<uint8_t> done(lanes, 0);
+    for (uint64_t r = 0; live; r++)
+        for (uint64_t l = lanes; l-- > 0;) {
+            if (done[l]) continue;
+            const uint64_t n = r * S + 2 * l;
+            uint64_t hit;
+            bool stop = hashc::grind_round(seed_words, phase, bits, max_tries, n, best, &hit);
+            if (hit < best) best = hit;   // atomicMin
+            if (stop || max_tries - n <= S) {
+                done[l] = 1;
+                live--;
+            }
+        }
+    if (best == ~0ull) return 1;
+    *nonce = best;
+    return 0;
+}
+// the check words of one pair of nonces (hashc::grind_pair) and of one nonce on the single-hash state (hashc::grind_word,
+// the verifier's), with the transcript after the absorb
+extern "C" void emu_grind_pair(const uint32_t *seed_words, uint32_t phase, uint64_t n0, uint64_t n1, uint64_t *w) {
+    hashc::grind_pair(seed_words, phase, n0, n1, &w[0], &w[1]);
+}
+extern "C" uint64_t emu_grind_word(const uint32_t *seed_words, uint32_t phase, uint64_t nonce, uint32_t *words_out, uint32_t *phase_out) {
+    return hashc::grind_word(seed_words, phase, nonce, words_out, phase_out);
+}
+
 // ProofStream::deserialize as smi_fri_verify runs it (csrc/proof_parse.h), exposed for the CPU fuzz / sanitizer
 // tests: tags, element counts and payload offsets of up to `cap` objects; returns how many objects there are.
 extern "C" size_t emu_proof_parse(const uint8_t *b, size_t n, size_t max_objs, int32_t *tags, uint64_t *counts, uint64_t *offsets,

@@ -794,15 +794,83 @@ __global__ void query_ext_kernel(const LayerTableExt tab, const uint64_t *top, u
     write_path(pp + 2 * pa, L.nodes_next, half, L.depth_next, c, lane);
 }
 
+// ------------------------------------------------------------------------- proof-of-work search ("Grinding")
+// The smallest nonce nu whose hash with the transcript has `bits` low zero bits in its check word (hash_core.h grind_pair:
+// two nonces per lane in the paired-lane state, 9 or 10 mixes each, no memory traffic and no LDS).  Round r of a lane tests
+// r S + 2 gid and r S + 2 gid + 1, S = twice the lanes of the grid; a hit is published with an atomic minimum on *best
+// (preset to all-ones), and before each round the lane reads *best with a relaxed agent-scope load.
+//   - No workgroup ever waits for another: every lane only runs its own bounded loop, so nothing can hang.
+//   - Only the value itself is communicated, so no fence is needed: a stale read costs one more round, never a wrong answer.
+//   - The minimum is exact: a lane stops only below a value that is itself a valid nonce, or after its own hit, below
+//     which it has tested every nonce it owns.
+//   - The loop is bounded by max_tries.
+__global__ __launch_bounds__(256, 8) void grind_kernel(const FsSeed *__restrict__ fs, uint32_t bits, uint64_t max_tries, unsigned long long *best) {
+    uint32_t mid[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) mid[i] = fs->s[i];
+    const uint32_t phase = fs->phase;   // uniform over the launch
+    const uint64_t S = 2ull * gridDim.x * blockDim.x;
+    uint64_t n = 2ull * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    for (;;) {
+        const uint64_t seen = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint64_t hit;
+        const bool done = hashc::grind_round(mid, phase, bits, max_tries, n, seen, &hit);
+        if (hit != ~0ull) atomicMin(best, (unsigned long long)hit);
+        if (done || max_tries - n <= S) break;   // (not done: n < max_tries)
+        n += S;
+    }
+}
+// One lane after the search: the nonce record (tag 2, count 1, the u64) into the proof, the nonce absorbed into the device
+// transcript (its phase moves by 8), and the nonce and an "exhausted" flag (*best still all-ones) into the block that the
+// prove copies back anyway.
+__global__ void grind_finish_kernel(FsSeed *fs, const unsigned long long *best, uint8_t *record, uint64_t *back) {
+    if (threadIdx.x || blockIdx.x) return;
+    const uint64_t nu = *best;
+    record[0] = 2;
+    put_u64(record + 1, 1);
+    put_u64(record + 9, nu);
+    back[0] = nu;
+    back[1] = nu == ~0ull ? 1u : 0u;
+    hashc::State st;
+    for (int i = 0; i < 16; i++) st.s[i] = fs->s[i];
+    uint8_t nb[8];
+    for (int i = 0; i < 8; i++) nb[i] = (uint8_t)(nu >> (8 * i));
+    const uint32_t k = hashc::fs_absorb_bytes_phase(st, fs->phase, nb, 8);
+    for (int i = 0; i < 16; i++) fs->s[i] = st.s[i];
+    fs->phase = k;
+}
+int grind_bits_check(smi_ctx *ctx, uint32_t bits) {
+    if (bits > SMI_GRIND_MAX_BITS) return smi_fail(ctx, SMI_ERR_BAD_ARG, "grind_bits must be at most SMI_GRIND_MAX_BITS (32)");
+    return SMI_OK;
+}
+// *d_best = all-ones, then the search over the nonces 0 .. max_tries - 1 (0: the default cap 2^(bits+6)).  The grid covers
+// about 2^bits nonces per round -- the expected place of the first hit -- between one workgroup and a chip's worth (8
+// workgroups of 256 per CU, the shape of the other hash kernels), and never more lanes than there are nonces to try.
+static int launch_grind(smi_ctx *ctx, const FsSeed *d_fs, uint32_t bits, uint64_t max_tries, unsigned long long *d_best) {
+    if (!max_tries) max_tries = 1ull << (bits + 6);
+    HIP_TRY(ctx, hipMemsetAsync(d_best, 0xFF, 8, ctx->stream));
+    uint64_t lanes = ((1ull << bits) + 1) / 2;
+    if (lanes > max_tries / 2 + 1) lanes = max_tries / 2 + 1;
+    uint64_t blocks = (lanes + 255) / 256;
+    const uint64_t chip = 8ull * (uint64_t)ctx->num_cus;
+    if (blocks > chip) blocks = chip;
+    ProfScope ps(ctx, "grind_kernel", 0.0);
+    grind_kernel<<<(uint32_t)blocks, 256, 0, ctx->stream>>>(d_fs, bits, max_tries, d_best);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+
 int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
-                FriExtResult *res) {
+                FriExtResult *res, int grind) {
     SMI_TRY(ext_field_check(ctx));
     SMI_TRY(smi_fri_check(ctx, cfg));
     if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
     if (stride < len || len > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext: stride < len, or len > 2^27");
     const uint32_t p = ctx->fs.F.p;
     if (cfg->omega >= p || cfg->offset >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
-    const FriLayout lay = fri_layout_ext(*cfg);
+    const bool pow = grind != SMI_GRIND_NONE;
+    if (pow) SMI_TRY(grind_bits_check(ctx, (uint32_t)grind));
+    const FriLayout lay = fri_layout_ext(*cfg, pow);
     const uint64_t R = lay.R, t = cfg->num_colinearity_tests;
     if (R == 0) return smi_fail(ctx, SMI_ERR_NO_ROUNDS, "num_rounds() == 0: the reference's verify rejects such a proof");
     if (R - 1 > SMI_QUERY_TAB_MAX) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext: too many rounds");
@@ -812,10 +880,12 @@ int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const 
     if (reset_arena) SMI_TRY(arena_reset(ctx));
     ScaleScope pin__(ctx);
 
-    // one device buffer comes back in one copy: proof | top-level indices; beside it: fs state | seed challenge | reduced
-    const size_t off_top = (lay.proof_len + 7) & ~(size_t)7, back_len = off_top + 8 * (t + 1);
+    // one device buffer comes back in one copy: proof | top-level indices (| nonce, exhausted flag); beside it: fs state |
+    // seed challenge | reduced | the search's best nonce
+    const size_t off_top = (lay.proof_len + 7) & ~(size_t)7, off_pow = off_top + 8 * (t + 1), back_len = off_pow + (pow ? 16 : 0);
     const size_t m_alpha = (sizeof(FsSeed) + 63) & ~(size_t)63, m_seed_ch = m_alpha + 32 * R, m_reduced = m_seed_ch + 8;
-    uint8_t *misc = (uint8_t *)arena_alloc(ctx, m_reduced + 8 * (t + 1));
+    const size_t m_best = m_reduced + 8 * (t + 1);
+    uint8_t *misc = (uint8_t *)arena_alloc(ctx, m_best + (pow ? 8 : 0));
     uint8_t *d_proof = (uint8_t *)arena_alloc(ctx, back_len);
     if (!misc || !d_proof) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext: device memory");
     FsSeed *d_fs = (FsSeed *)misc;
@@ -863,7 +933,15 @@ int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const 
     }
     emit_codeword_ext_kernel<<<(uint32_t)((4 * lay.last_n + 255) / 256), 256, 0, ctx->stream>>>(cur, cur_stride, lay.last_n, d_proof + lay.off_last);
     HIP_TRY(ctx, hipGetLastError());
-    SMI_TRY(launch_fs_challenge(ctx, d_fs, d_seed_ch, fs0.phase));
+    uint32_t seed_phase = fs0.phase;
+    if (pow) {   // the search, then one lane writes the record and absorbs the nonce: the transcript stays on the device
+        unsigned long long *d_best = (unsigned long long *)(misc + m_best);
+        SMI_TRY(launch_grind(ctx, d_fs, (uint32_t)grind, 0, d_best));
+        grind_finish_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, d_best, d_proof + lay.off_layers - SMI_GRIND_RECORD_BYTES, (uint64_t *)(d_proof + off_pow));
+        HIP_TRY(ctx, hipGetLastError());
+        seed_phase = (fs0.phase + 8) & 31u;
+    }
+    SMI_TRY(launch_fs_challenge(ctx, d_fs, d_seed_ch, seed_phase));
     SMI_TRY(launch_sample_indices(ctx, d_seed_ch, R > 1 ? len / 2 : len, lay.last_n, (uint32_t)t, d_top, d_reduced));
     if (R > 1 && t > 0) {
         query_ext_kernel<<<dim3((uint32_t)t, (uint32_t)(R - 1)), 64, 0, ctx->stream>>>(tab, d_top, d_proof);
@@ -873,6 +951,12 @@ int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const 
     SMI_TRY(ctx_pin_out(ctx, back_len, &land));
     HIP_TRY(ctx, hipMemcpyAsync(land, d_proof, back_len, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (pow) {
+        uint64_t back[2];
+        memcpy(back, land + off_pow, 16);
+        if (back[1]) return smi_fail(ctx, SMI_ERR_GRIND_EXHAUSTED, "proof of work: no nonce below 2^(grind_bits + 6) meets the difficulty");
+        res->nonce = back[0];
+    }
     res->proof.assign(land, land + lay.proof_len);
     res->top.assign(t + 1, 0);
     if (t) memcpy(res->top.data(), land + off_top, 8 * t);
@@ -889,6 +973,59 @@ int smi_dev_fri_prove_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *t
     SMI_TRY(fri_run_ext(ctx, cfg, &seed, d_codeword, len, stride, true, &res));
     if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
     return smi_proof_out(ctx, res.proof, proof, proof_len);
+}
+
+int smi_dev_fri_prove_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                              size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, uint32_t grind_bits,
+                              uint64_t *nonce) {
+    if (!ctx || !cfg || !d_codeword || !proof || !proof_len || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
+    DeviceGuard dg__(ctx);
+    FriExtResult res;
+    SMI_TRY(fri_run_ext(ctx, cfg, &seed, d_codeword, len, stride, true, &res, (int)grind_bits));
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    if (nonce) *nonce = res.nonce;
+    return smi_proof_out(ctx, res.proof, proof, proof_len);
+}
+
+// pow_ok on the host: the definition as it stands, one Hash::from_bytes of transcript || nonce
+int smi_grind_check(const uint8_t *transcript, size_t transcript_len, uint64_t nonce, uint32_t bits, int *ok) {
+    if (!ok || (!transcript && transcript_len) || bits > SMI_GRIND_MAX_BITS) return SMI_ERR_BAD_ARG;
+    std::vector<uint8_t> msg(transcript_len + 8);
+    if (transcript_len) memcpy(msg.data(), transcript, transcript_len);
+    for (int i = 0; i < 8; i++) msg[transcript_len + i] = (uint8_t)(nonce >> (8 * i));
+    uint32_t d[8];
+    hashc::hash_bytes(msg.data(), msg.size(), d);
+    const uint64_t word = (uint64_t)d[6] | ((uint64_t)d[7] << 32);
+    *ok = (word & ((1ull << bits) - 1)) == 0;
+    return SMI_OK;
+}
+
+// the search alone: host transcript -> FsSeed on the device -> grind_kernel -> one synchronising copy of *best
+int smi_dev_grind(smi_ctx *ctx, const uint8_t *transcript, size_t transcript_len, uint32_t bits, uint64_t max_tries, uint64_t *nonce) {
+    if (!ctx || !nonce || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    SMI_TRY(grind_bits_check(ctx, bits));
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
+    DeviceGuard dg__(ctx);
+    void *d = nullptr;
+    SMI_TRY(ctx_tmp(ctx, 3, 256, &d));
+    FsSeed *d_fs = (FsSeed *)d;
+    unsigned long long *d_best = (unsigned long long *)((uint8_t *)d + 128);
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, seed);
+    HIP_TRY(ctx, hipGetLastError());
+    SMI_TRY(launch_grind(ctx, d_fs, bits, max_tries, d_best));
+    uint8_t *land = nullptr;
+    SMI_TRY(ctx_pin_out(ctx, 8, &land));
+    HIP_TRY(ctx, hipMemcpyAsync(land, d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t best;
+    memcpy(&best, land, 8);
+    if (best == ~0ull) return smi_fail(ctx, SMI_ERR_GRIND_EXHAUSTED, "proof of work: no nonce below max_tries meets the difficulty");
+    *nonce = best;
+    return SMI_OK;
 }
 
 // ------------------------------------------------------------------------- C ABI

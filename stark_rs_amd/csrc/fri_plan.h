@@ -39,10 +39,13 @@ inline FriLayout fri_layout(const smi_fri_cfg &cfg, bool do_query) {
 
 // The same layout for FRI over the quartic extension (include/stark_mi.h, "Extension FRI"): an element is four u64, so the
 // last codeword is one record of 4 last_n values and a triple one record of 12; rounds, paths and their order are unchanged.
-inline FriLayout fri_layout_ext(const smi_fri_cfg &cfg) {
+// pow: the proof-of-work nonce record (include/stark_mi.h, "Grinding": tag 2, count 1, one u64) sits between the last
+// codeword and the layers, at off_layers - SMI_GRIND_RECORD_BYTES.
+#define SMI_GRIND_RECORD_BYTES 17
+inline FriLayout fri_layout_ext(const smi_fri_cfg &cfg, bool pow = false) {
     FriLayout l = fri_layout(cfg, true);
     const uint64_t N = cfg.domain_length, t = cfg.num_colinearity_tests;
-    l.off_layers = l.off_last + 9 + 32 * l.last_n;
+    l.off_layers = l.off_last + 9 + 32 * l.last_n + (pow ? SMI_GRIND_RECORD_BYTES : 0);
     size_t off = l.off_layers;
     for (uint64_t i = 0; i + 1 < l.R; i++) {
         const uint32_t d = ilog2(N >> i);

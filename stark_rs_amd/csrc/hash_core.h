@@ -804,4 +804,96 @@ SMI_HD void hash_bytes(const uint8_t *msg, size_t len, uint32_t d[8]) {
     to_words(st, d);
 }
 
+// ---- proof-of-work grinding (include/stark_mi.h, "Grinding"): the check word of T || nu for TWO nonces per lane, from
+// the transcript T kept as its midstate (fs_seed: 16 paired-lane words, nothing pending) and its phase.  The search kernel
+// (fri.hip grind_kernel) and the emulator (emu.cpp emu_grind) run exactly this.  The phase is uniform over a launch: every
+// state index below is a compile-time constant and the phase only selects, by a uniform branch, which of the unrolled
+// positions take a nonce byte -- nothing is indexed by a run-time value, so nothing goes to scratch.
+
+// byte i of both nonces as one State2 word (X in lane 0, Y in lane 1)
+SMI_HD uint32_t grind_byte2(uint64_t n0, uint64_t n1, uint32_t i) {
+    return ((uint32_t)(n0 >> (8 * i)) & 0xFFu) | (((uint32_t)(n1 >> (8 * i)) & 0xFFu) << 16);
+}
+// src/hash.rs:15-20 for one byte of each hash at chunk position pos (compile-time), the state fully applied; carry dirt
+// above bit 7 of a lane is masked off the byte that is replaced and left alone in the byte that is XORed into
+SMI_HD void grind_absorb_at(State2 &st, int pos, uint32_t m) {
+    uint32_t v = (st.s[pos] + m) & 0x00FF00FFu;
+    v = ((v << 3) | (v >> 5)) & 0x00FF00FFu;
+    st.s[pos] = v;
+    st.s[(pos + 7) & 31] ^= v;
+}
+// *w0 / *w1: bytes 24..31 of Hash::from_bytes(T || n0) / (T || n1), read as little-endian u64.  The eight nonce bytes go
+// to positions phase .. phase + 7; at phase >= 24 they complete the pending chunk, which is mixed, and at phase > 24 the
+// rest starts the next one.  Then the short chunk's mix (none at phase 24) and the 8 closing ones: 9 mixes for phase <=
+// 24, 10 above.  Only the last mix's round constants of words 24..31 are applied: the other bytes are not read.
+SMI_HD void grind_pair(const uint32_t mid[16], uint32_t phase, uint64_t n0, uint64_t n1, uint64_t *w0, uint64_t *w1) {
+    constexpr Consts2 C = make_consts2();
+    State2 st;
+#pragma unroll
+    for (int w = 0; w < 32; w++) st.s[w] = ((mid[w & 15] >> ((w & 16) ? 16 : 0)) & 0xFFu) * 0x00010001u;
+    const MixK K = mix_consts();
+#pragma unroll
+    for (int pos = 0; pos < 32; pos++) {
+        const uint32_t i = (uint32_t)pos - phase;   // pos < phase: wraps to a value >= 8
+        if (i < 8u) grind_absorb_at(st, pos, grind_byte2(n0, n1, i));
+    }
+    if (phase > 24) {
+        mix2(st, K);
+#pragma unroll
+        for (int pos = 0; pos < 7; pos++) {
+            const uint32_t i = (uint32_t)pos + 32u - phase;
+            if (i < 8u) grind_absorb_at(st, pos, grind_byte2(n0, n1, i));
+        }
+    }
+    mix2_t<false>(st, K);
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) mix2_t<true>(st, K);
+    uint64_t x = 0, y = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t s = st.s[24 + i] + C.rc[24 + i];
+        x |= (uint64_t)(s & 0xFFu) << (8 * i);
+        y |= (uint64_t)((s >> 16) & 0xFFu) << (8 * i);
+    }
+    *w0 = x;
+    *w1 = y;
+}
+// One round of one lane of the search: the nonces n (even) and n + 1 against `best`, the smallest valid nonce any lane has
+// published so far as this lane read it (all-ones: none).  -> true when the lane is done: its nonces have reached
+// max_tries, a smaller valid nonce is known, or it has found one (*hit; all-ones otherwise) -- its later nonces are all
+// larger.  A stale `best` only costs the round; the caller publishes *hit with an atomic minimum.  bits <= 32.
+SMI_HD bool grind_round(const uint32_t mid[16], uint32_t phase, uint32_t bits, uint64_t max_tries, uint64_t n, uint64_t best, uint64_t *hit) {
+    *hit = ~0ull;
+    if (n >= max_tries || best < n) return true;
+    uint64_t w0, w1;
+    grind_pair(mid, phase, n, n + 1, &w0, &w1);
+    const uint64_t mask = (1ull << bits) - 1;
+    if (!(w0 & mask)) {
+        *hit = n;
+        return true;
+    }
+    if (!(w1 & mask) && n + 1 < max_tries) {
+        *hit = n + 1;
+        return true;
+    }
+    return false;
+}
+// The same check word for one nonce on the single-hash state, and the transcript with the nonce absorbed (fs_out, may be
+// fs_in; *phase_out = (phase + 8) mod 32): the verifier's one hash, and the absorb of the prover's finishing step.
+SMI_HD uint64_t grind_word(const uint32_t *fs_in, uint32_t phase, uint64_t nonce, uint32_t *fs_out, uint32_t *phase_out) {
+    State st;
+    for (int i = 0; i < 16; i++) st.s[i] = fs_in[i];
+    uint8_t nb[8];
+    for (int i = 0; i < 8; i++) nb[i] = (uint8_t)(nonce >> (8 * i));
+    const uint32_t k = fs_absorb_bytes_phase(st, phase, nb, 8);
+    if (fs_out)
+        for (int i = 0; i < 16; i++) fs_out[i] = st.s[i];
+    if (phase_out) *phase_out = k;
+    const int mixes = k ? 9 : 8;
+    for (int j = 0; j < mixes; j++) mix(st);
+    uint32_t d[8];
+    to_words(st, d);
+    return (uint64_t)d[6] | ((uint64_t)d[7] << 32);
+}
+
 }  // namespace hashc

@@ -258,9 +258,14 @@ int fri_run(smi_ctx *ctx, const FriRequest &rq, FriResult *res);
 struct FriExtResult {
     std::vector<uint8_t> proof;
     std::vector<uint64_t> top;      // top-level indices
+    uint64_t nonce = 0;             // the proof-of-work nonce (grind != SMI_GRIND_NONE)
 };
+// grind: the proof-of-work difficulty (include/stark_mi.h, "Grinding"), 0 .. SMI_GRIND_MAX_BITS, or SMI_GRIND_NONE: no
+// nonce record and no absorb -- the stream of smi_dev_fri_prove_ext.  The verifier (verify.hip) takes the same argument.
+#define SMI_GRIND_NONE (-1)
 int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
-                FriExtResult *res);
+                FriExtResult *res, int grind = SMI_GRIND_NONE);
+int grind_bits_check(smi_ctx *ctx, uint32_t bits);   // SMI_ERR_BAD_ARG above SMI_GRIND_MAX_BITS (fri.hip)
 
 // launches (defined in the .hip files; every function one .hip file defines and another calls is declared here, once --
 // the MgSide ones in mgpu_core.h)

@@ -234,9 +234,10 @@ int fri_verify_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, con
 }
 // The verifier of FRI over the quartic extension (include/stark_mi.h, "Extension FRI") on objs[0..]; the structure of
 // fri_verify_objs with four-coordinate elements.  pv_val gets four values per entry, layer0_ab eight per test (a, then b).
+// grind: the least proof-of-work difficulty demanded (include/stark_mi.h, "Grinding"), or SMI_GRIND_NONE: no nonce record.
 int fri_verify_ext_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, const std::vector<Obj> &objs, int *accept,
                         std::vector<uint64_t> *top_out, std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val,
-                        std::vector<uint64_t> *layer0_ab, size_t *used) {
+                        std::vector<uint64_t> *layer0_ab, size_t *used, int grind = SMI_GRIND_NONE) {
     const uint32_t p = ctx->fs.F.p, g = ctx->fs.g;
     const uint64_t t = cfg.num_colinearity_tests, N = cfg.domain_length;
     uint64_t R = 0;
@@ -301,8 +302,16 @@ int fri_verify_ext_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0,
         for (size_t i = degree_bound; i < n_last; i++)
             if (coeffs[i] != 0) return reject(ctx, accept, "last codeword does not correspond to polynomial of low enough degree");
     }
+    uint32_t seed_phase = fs0.phase;
+    if (grind != SMI_GRIND_NONE) {   // the nonce record: one u64 (not a field element), checked with one hash, then absorbed
+        const Obj *no = pop();
+        if (!no || no->tag != 2) return reject(ctx, accept, "proof of work: failed to extract the nonce");
+        if (no->count != 1) return reject(ctx, accept, "proof of work: the nonce record must hold exactly one value");
+        const uint64_t word = hashc::grind_word(fs, fs0.phase, get_u64(no->p), fs, &seed_phase);
+        if (word & ((1ull << grind) - 1)) return reject(ctx, accept, "proof of work");
+    }
     std::vector<uint64_t> top;
-    SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, fs0.phase), N >> 1, n_last, t, &top));
+    SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, seed_phase), N >> 1, n_last, t, &top));
     if (top_out) *top_out = top;
 
     uint64_t om = cfg.omega % p, off = cfg.offset % p;
@@ -421,8 +430,8 @@ int smi_fri_verify(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *proof, s
     return smi_fri_verify_fs(ctx, cfg, nullptr, 0, proof, proof_len, accept, pv_indices, pv_values, n_pv, nullptr);
 }
 
-int smi_fri_verify_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
-                       size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed) {
+static int fri_verify_ext_impl(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                               size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed, int grind) {
     if (!ctx || !cfg || (!proof && proof_len) || !accept || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     *accept = 0;
@@ -436,12 +445,25 @@ int smi_fri_verify_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *tran
     const std::vector<Obj> objs = parse(proof, proof_len, (size_t)-1, &end);
     std::vector<uint64_t> pi, pv;
     size_t used = 0;
-    const int rc = fri_verify_ext_objs(ctx, *cfg, seed, objs, accept, nullptr, &pi, &pv, nullptr, &used);
+    const int rc = fri_verify_ext_objs(ctx, *cfg, seed, objs, accept, nullptr, &pi, &pv, nullptr, &used, grind);
     if (n_pv) *n_pv = pi.size();
     if (pv_indices && !pi.empty()) memcpy(pv_indices, pi.data(), 8 * pi.size());
     if (pv_values && !pv.empty()) memcpy(pv_values, pv.data(), 8 * pv.size());
     if (rc == SMI_OK && *accept && consumed) (void)parse(proof, proof_len, used, consumed);
     return rc;
+}
+
+int smi_fri_verify_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                       size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed) {
+    return fri_verify_ext_impl(ctx, cfg, transcript, transcript_len, proof, proof_len, accept, pv_indices, pv_values, n_pv, consumed, SMI_GRIND_NONE);
+}
+int smi_fri_verify_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                           size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed,
+                           uint32_t grind_bits) {
+    if (!ctx) return SMI_ERR_BAD_ARG;
+    if (accept) *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    return fri_verify_ext_impl(ctx, cfg, transcript, transcript_len, proof, proof_len, accept, pv_indices, pv_values, n_pv, consumed, (int)grind_bits);
 }
 
 int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *column_roots, const uint8_t *proof, size_t proof_len,
@@ -523,8 +545,9 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
 // authentication of the opened rows differ between the two commitments; everything else is this one function.
 // over_ext (with by_rows): weights from the quartic extension -- four counters and four challenges per weight, FRI over F_q, the
 // four coordinates of the composition against the layer-0 triple's a and b (smi_air_verify_ext).
+// grind (with over_ext): the proof-of-work difficulty demanded of the FRI part, or SMI_GRIND_NONE (smi_air_verify_ext_pow).
 static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint8_t *column_roots, const uint8_t *proof,
-                           size_t proof_len, int *accept, bool by_rows, bool over_ext = false) {
+                           size_t proof_len, int *accept, bool by_rows, bool over_ext = false, int grind = SMI_GRIND_NONE) {
     std::string why;
     uint64_t E = 0;
     const int vrc = air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
@@ -571,10 +594,10 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     FsSeed seed;
     hashc::fs_seed(transcript.data(), transcript.size(), seed.s, &seed.phase);
     size_t end = 0;
-    const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc), &end);
+    const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc) + (grind != SMI_GRIND_NONE ? 1 : 0), &end);
     std::vector<uint64_t> top, ab;
     size_t used = 0;
-    if (over_ext) SMI_TRY(fri_verify_ext_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
+    if (over_ext) SMI_TRY(fri_verify_ext_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used, grind));
     else SMI_TRY(fri_verify_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used));
     if (!*accept) return SMI_OK;
     *accept = 0;
@@ -688,4 +711,14 @@ int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, 
     *accept = 0;
     SMI_TRY(ext_field_check(ctx));
     return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true, true);
+}
+
+int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                           size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !row_root || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true, true, (int)grind_bits);
 }

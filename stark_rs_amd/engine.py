@@ -417,26 +417,52 @@ class Engine:
         self.L.smi_free(proof)
         return b, [int(v) for v in top[:cfg.num_colinearity_tests]]
 
-    def dev_fri_prove_ext(self, cfg, d_codeword, length, stride=None, transcript=b""):
+    # ---- proof-of-work grinding (include/stark_mi.h, "Grinding")
+    def grind(self, transcript, bits, max_tries=0):
+        """smi_dev_grind -> the smallest nonce whose hash with the transcript (host bytes) has `bits` low zero bits in its
+        check word; max_tries = 0: the default cap 2^(bits+6).  StarkMiError -55 when no nonce below the cap is valid."""
+        t = bytes(transcript)
+        out = C.c_uint64()
+        self._ck(self.L.smi_dev_grind(self.h, t if t else None, len(t), bits, max_tries, C.byref(out)))
+        return int(out.value)
+
+    @staticmethod
+    def grind_check(transcript, nonce, bits):
+        """smi_grind_check (host only) -> pow_ok(transcript, nonce, bits)"""
+        return grind_check(transcript, nonce, bits)
+
+    def dev_fri_prove_ext(self, cfg, d_codeword, length, stride=None, transcript=b"", grind_bits=None):
         """smi_dev_fri_prove_ext: Fri::prove over the quartic extension on four device coordinate columns `stride`
-        (default length) apart, continuing the caller's transcript (host bytes) -> (proof bytes, top-level indices)"""
+        (default length) apart, continuing the caller's transcript (host bytes) -> (proof bytes, top-level indices).
+        grind_bits (None: no grinding, today's stream): smi_dev_fri_prove_ext_pow -> (proof bytes, top-level indices, nonce)"""
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(cfg.num_colinearity_tests, 1), dtype=np.uint64)
         t = bytes(transcript)
-        self._ck(self.L.smi_dev_fri_prove_ext(self.h, C.byref(cfg), t if t else None, len(t), vp(d_codeword), length,
-                                              length if stride is None else stride, C.byref(proof), C.byref(plen), top.ctypes.data))
+        args = (self.h, C.byref(cfg), t if t else None, len(t), vp(d_codeword), length, length if stride is None else stride, C.byref(proof),
+                C.byref(plen), top.ctypes.data)
+        nonce = C.c_uint64()
+        if grind_bits is None:
+            self._ck(self.L.smi_dev_fri_prove_ext(*args))
+        else:
+            self._ck(self.L.smi_dev_fri_prove_ext_pow(*args, grind_bits, C.byref(nonce)))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
-        return b, [int(v) for v in top[:cfg.num_colinearity_tests]]
+        top = [int(v) for v in top[:cfg.num_colinearity_tests]]
+        return (b, top) if grind_bits is None else (b, top, int(nonce.value))
 
-    def fri_verify_ext(self, cfg, proof: bytes, transcript=b""):
-        """smi_fri_verify_ext -> (accept, polynomial_values [(index, [c0, c1, c2, c3])], bytes consumed, reason)"""
+    def fri_verify_ext(self, cfg, proof: bytes, transcript=b"", grind_bits=None):
+        """smi_fri_verify_ext -> (accept, polynomial_values [(index, [c0, c1, c2, c3])], bytes consumed, reason).
+        grind_bits (None: a proof without grinding): smi_fri_verify_ext_pow, the least difficulty demanded"""
         t = bytes(transcript)
         n = 2 * max(cfg.num_colinearity_tests, 1)
         idx, val = np.zeros(n, dtype=np.uint64), np.zeros(4 * n, dtype=np.uint64)
         acc, npv, used = C.c_int(), C.c_size_t(), C.c_size_t()
-        self._ck(self.L.smi_fri_verify_ext(self.h, C.byref(cfg), t if t else None, len(t), proof, len(proof), C.byref(acc), idx.ctypes.data,
-                                           val.ctypes.data, C.byref(npv), C.byref(used)))
+        args = (self.h, C.byref(cfg), t if t else None, len(t), proof, len(proof), C.byref(acc), idx.ctypes.data, val.ctypes.data, C.byref(npv),
+                C.byref(used))
+        if grind_bits is None:
+            self._ck(self.L.smi_fri_verify_ext(*args))
+        else:
+            self._ck(self.L.smi_fri_verify_ext_pow(*args, grind_bits))
         pv = [(int(idx[i]), [int(v) for v in val[4 * i:4 * i + 4]]) for i in range(npv.value)]
         return bool(acc.value), pv, used.value, ("" if acc.value else self.L.smi_last_error(self.h).decode())
 
@@ -502,14 +528,17 @@ class Engine:
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False, ext=False):
+                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
         one root, shape (1, 32), and the proof opens every queried position once (verify with row_leaves=True).
-        ext (needs row_leaves): smi_dev_air_prove_ext -- weights and FRI over the quartic extension."""
+        ext (needs row_leaves): smi_dev_air_prove_ext -- weights and FRI over the quartic extension.
+        grind_bits (needs ext; None: no grinding): smi_dev_air_prove_ext_pow -- proof-of-work bits before the query indices."""
         if ext and not row_leaves:
             raise StarkMiError(-50, "dev_air_prove(ext=True) commits to one tree over the rows: pass row_leaves=True")
+        if grind_bits is not None and not ext:
+            raise StarkMiError(-50, "dev_air_prove(grind_bits=...) grinds the extension proof: pass ext=True")
         a = self._air(air)
         if check:
             ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
@@ -521,8 +550,12 @@ class Engine:
         top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
         stage = (C.c_double * 5)()
         prove = self.L.smi_dev_air_prove_ext if ext else (self.L.smi_dev_air_prove_rows if row_leaves else self.L.smi_dev_air_prove)
-        self._ck(prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof),
-                                          C.byref(plen), top.ctypes.data, stage if timed else None))
+        args = (self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data,
+                stage if timed else None)
+        if grind_bits is None:
+            self._ck(prove(*args))
+        else:
+            self._ck(self.L.smi_dev_air_prove_ext_pow(*args, grind_bits))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]]}
@@ -531,11 +564,14 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False, ext=False):
+                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
-        the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext"""
+        the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
+        grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded"""
         if ext and not row_leaves:
             raise StarkMiError(-50, "air_verify(ext=True) checks a proof over one row tree: pass row_leaves=True")
+        if grind_bits is not None and not ext:
+            raise StarkMiError(-50, "air_verify(grind_bits=...) checks a ground extension proof: pass ext=True")
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, row_leaves)
         a = self._air(air)
         roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
@@ -543,7 +579,11 @@ class Engine:
         verify = self.L.smi_air_verify_ext if ext else (self.L.smi_air_verify_rows if row_leaves else self.L.smi_air_verify)
         if row_leaves and roots.size != 32:
             raise StarkMiError(-50, "air_verify(row_leaves=True) takes the one 32-byte root of the row tree")
-        self._ck(verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc)))
+        args = (self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc))
+        if grind_bits is None:
+            self._ck(verify(*args))
+        else:
+            self._ck(self.L.smi_air_verify_ext_pow(*args, grind_bits))
         return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
 
 
@@ -646,6 +686,17 @@ def ext_mul(p, g, a, b):
 def ext_inv(p, g, a):
     """smi_ext_inv (host only, no GPU); StarkMiError "no inverse" for zero"""
     return _ext_call(_lib.lib().smi_ext_inv, p, g, a)
+
+
+def grind_check(transcript, nonce, bits):
+    """smi_grind_check (host only, no GPU): pow_ok(transcript, nonce, bits) -- the hash of transcript || nonce (8 little-endian
+    bytes) has `bits` low zero bits in the u64 read from its bytes 24..31"""
+    t = bytes(transcript)
+    ok = C.c_int()
+    st = _lib.lib().smi_grind_check(t if t else None, len(t), nonce, bits, C.byref(ok))
+    if st:
+        raise StarkMiError(st, _lib.status_string(st))
+    return bool(ok.value)
 
 
 def default_engine(p=P_REF, g=G_REF, device=0):

@@ -435,6 +435,19 @@ class FiatShamir:
         h = default_engine().hash_bytes(bytes(self.transcript))
         return field.new_element(int.from_bytes(h[:8], "little"))      # unreduced (H6)
 
+    # proof-of-work grinding (include/stark_mi.h, "Grinding"; no reference counterpart)
+    def grind(self, bits, max_tries=0):
+        """the smallest nonce whose hash with the transcript has `bits` low zero bits in its check word: found on the GPU
+        (smi_dev_grind), absorbed as 8 little-endian bytes, returned"""
+        nonce = default_engine().grind(bytes(self.transcript), bits, max_tries)
+        self.absorb(nonce.to_bytes(8, "little"))
+        return nonce
+
+    def check_grind(self, nonce, bits):
+        """pow_ok of `nonce` on the transcript as it stands (smi_grind_check, host only); absorbs nothing"""
+        from .engine import grind_check
+        return grind_check(bytes(self.transcript), nonce, bits)
+
 
 class ProofObject:
     """src/stream.rs:8-14"""

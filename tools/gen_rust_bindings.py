@@ -146,7 +146,7 @@ def generate():
         for nm in names.split(","):
             lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
     lines.append("}")
-    for m in re.finditer(r"#define (SMI_AIR_MAX_\w+) (\d+)", text):
+    for m in re.finditer(r"#define (SMI_\w+_MAX_\w+) (\d+)", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     lines.append("")
     lines.append('#[link(name = "starkmi")]')

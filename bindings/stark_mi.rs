@@ -119,6 +119,14 @@ pub struct smi_air {
     pub periodic_log_period: *const u32,
     pub periodic_value: *const u64,
 }
+/// smi_air_perm: one permutation argument (host pointers; the entry points take it as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_perm {
+    pub width: u32,
+    pub reserved0: u32,
+    pub left_col: *const u32,
+    pub right_col: *const u32,
+}
 pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
 pub const SMI_AIR_MAX_TERMS: u32 = 1024;
 pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
@@ -126,6 +134,7 @@ pub const SMI_AIR_MAX_EXP: u32 = 255;
 pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
 pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
 pub const SMI_GRIND_MAX_BITS: u32 = 32;
+pub const SMI_PERM_MAX_WIDTH: u32 = 8;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -226,6 +235,11 @@ extern "C" {
     pub fn smi_fri_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize, grind_bits: u32) -> c_int;
     pub fn smi_dev_air_prove_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
     pub fn smi_air_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_perm(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
+    pub fn smi_dev_perm_column(ctx: *mut smi_ctx, perm: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: *const u64, d_z: *mut u32, z_stride: usize, closes: *mut c_int) -> c_int;
+    pub fn smi_dev_air_compose_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, d_lde: *const u32, stride: usize, d_z_lde: *const u32, z_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_prove_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut c_int) -> c_int;
+    pub fn smi_air_verify_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -866,6 +880,68 @@ impl Air {
         } else {
             Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
         }
+    }
+    /// `smi_air_plan_perm` (host only): `(max(degree, 2), FRI expansion factor)` of this AIR with the permutation `perm`.
+    pub fn plan_perm(&self, p: u64, cfg: &smi_stark_cfg, perm: &Permutation) -> (u32, u64) {
+        let (mut d, mut e) = (0u32, 0u64);
+        let st = self.with_raw(|a| perm.with_raw(|pm| unsafe { smi_air_plan_perm(p, cfg, a, pm, &mut d, &mut e) }));
+        if st != SMI_OK {
+            panic!("{}: {}", status_text(st), unsafe { CStr::from_ptr(smi_air_last_error()) }.to_string_lossy());
+        }
+        (d, e)
+    }
+    /// `smi_dev_air_prove_perm` -> (root_1 then root_2, proof bytes, closes): the AIR proof with the permutation argument
+    /// `perm` over a committed extension column.  A trace whose product does not close is proved all the same (`closes`
+    /// is false and the verifier rejects); a zero denominator panics with "no inverse" and the row.
+    pub fn prove_perm(&self, ctx: &Context, cfg: &smi_stark_cfg, perm: &Permutation, d_trace_cols: *const u32, grind_bits: u32) -> ([u8; 64], Vec<u8>, bool) {
+        let mut roots = [0u8; 64];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        let mut closes = 0 as c_int;
+        ctx.check(self.with_raw(|a| perm.with_raw(|pm| unsafe {
+            smi_dev_air_prove_perm(ctx.raw, cfg, a, pm, d_trace_cols, roots.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut(), grind_bits, &mut closes)
+        })));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (roots, bytes, closes != 0)
+    }
+    /// `smi_air_verify_perm` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify_perm(&self, ctx: &Context, cfg: &smi_stark_cfg, perm: &Permutation, roots: &[u8; 64], proof: &[u8], grind_bits: u32) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| perm.with_raw(|pm| unsafe {
+            smi_air_verify_perm(ctx.raw, cfg, a, pm, roots.as_ptr(), proof.as_ptr(), proof.len(), &mut accept, grind_bits)
+        })));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+}
+
+/// One permutation argument (include/stark_mi.h, "Permutation argument"): the multiset of the row tuples over the
+/// `left` columns equals that over the `right` columns; 1 ..= `SMI_PERM_MAX_WIDTH` columns a side, the lists may overlap.
+pub struct Permutation {
+    left: Vec<u32>,
+    right: Vec<u32>,
+}
+
+impl Permutation {
+    pub fn new(left: &[u32], right: &[u32]) -> Permutation {
+        assert!(left.len() == right.len() && !left.is_empty() && left.len() <= SMI_PERM_MAX_WIDTH as usize, "1 ..= SMI_PERM_MAX_WIDTH columns a side");
+        Permutation { left: left.to_vec(), right: right.to_vec() }
+    }
+    fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        let raw = smi_air_perm { width: self.left.len() as u32, reserved0: 0, left_col: self.left.as_ptr(), right_col: self.right.as_ptr() };
+        f(&raw as *const smi_air_perm as *const c_void)
+    }
+    /// `smi_dev_perm_column`: the column z of the device trace under the 8 unreduced challenges into four coordinate
+    /// columns `z_stride` apart -> closes.  Panics with "no inverse" and the row when a denominator is zero.
+    pub fn column(&self, ctx: &Context, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: &[u64; 8], d_z: *mut u32, z_stride: usize) -> bool {
+        let mut closes = 0 as c_int;
+        ctx.check(self.with_raw(|pm| unsafe {
+            smi_dev_perm_column(ctx.raw, pm, d_trace_cols, n_cols, log_n, challenges.as_ptr(), d_z, z_stride, &mut closes)
+        }));
+        closes != 0
     }
 }
 

@@ -538,11 +538,12 @@ int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   the 9 mixes a base-field leaf costs.  The coordinates of a codeword are base-field codewords on the same domain:
  *   smi_dev_lde, smi_dev_ntt and a degree check apply coordinate by coordinate.  On the host an element is four
  *   consecutive u64.
- * Left out: the column-tree variant of the AIR proof; any smi_mgpu_* twin; committed extension-field columns (an
- *   auxiliary trace); out-of-domain sampling; zero-knowledge randomisers; binding an AIR digest into the transcript; the
+ * Left out: the column-tree variant of the AIR proof; any smi_mgpu_* twin; out-of-domain sampling; zero-knowledge randomisers; binding an AIR digest into the transcript; the
  *   fold fused into the launch that hashes the row leaves (the base-field path's LEAF_FOLD) and a fused tail.  The query
  *   phase of the entry points of this section rests on t colinearity tests alone; "Grinding" below adds proof-of-work
- *   bits to it (smi_dev_fri_prove_ext_pow / smi_dev_air_prove_ext_pow). */
+ *   bits to it (smi_dev_fri_prove_ext_pow / smi_dev_air_prove_ext_pow).  A committed extension-field column (an auxiliary
+ *   trace) exists in one form, "Permutation argument" below: one permutation per proof, no periodic or next-row tuple
+ *   members, no LogUp / lookup argument, no column-tree or smi_mgpu_* twin. */
 #define SMI_EXT_DEGREE 4
 /* Host only, no context (like smi_air_plan): out = a * b and out = a^-1 in F_q, coordinates canonical.  SMI_ERR_BAD_ARG
  * for a (p, g) the section refuses (p not a prime < 2^31 that is 1 mod 4, g a square or outside 1 .. p-1),
@@ -666,6 +667,90 @@ int smi_dev_air_prove_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
                               uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
 int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
                            size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Permutation argument: a committed extension column ----------------------------------------
+ * The AIR sections relate two consecutive rows.  This one relates rows far apart: it proves that two lists of row tuples
+ * are equal as multisets -- "this column is a sorted copy of that one", memory consistency, copy constraints -- the way
+ * every production STARK does: after the trace is committed the verifier draws challenges, the prover commits a second,
+ * challenge-dependent column over F_q and the composition constrains it.  The entry points above are unchanged, byte for
+ * byte.  Extension weights, extension FRI, row-committed trees and a nonce record always (grind_bits = 0 accepts nonce 0).
+ *
+ * Statement.  With m = width, l_j = left_col[j], r_j = right_col[j] and T the trace (n = 2^log_n rows): as multisets over
+ *   all n rows, { (T[l_0][r], .., T[l_{m-1}][r]) } = { (T[r_0][r], .., T[r_{m-1}][r]) }.  One permutation per proof.
+ * The column.  With alpha, gamma in F_q:  f_L(r) = gamma + sum_j alpha^j T[l_j][r], f_R likewise with r_j;
+ *   rho[r] = f_L(r) / f_R(r);  z[0] = 1, z[r+1] = z[r] rho[r] for r = 0 .. n-2.  The multisets are equal iff (up to about
+ *   n m / q) the product closes: z[n-1] rho[n-1] = 1.  z is four coordinate columns of n residues ("Layout" above).
+ * Auxiliary constraints.  The column's own transition WRAPS AROUND: z(w x) f_R(x) - z(x) f_L(x) vanishes on all n rows and
+ *   is divided by x^n - tau^n (the main AIR's transitions keep their no-wrap rule); the boundary quotient is
+ *   (z(x) - 1) / (x - tau).  Both have degree 2: d = max(d_air, 2), D and E follow as in smi_air_plan.
+ * Protocol.
+ *   1. smi_dev_lde of the trace, the tree over its rows: root_1.
+ *   2. The transcript starts empty and absorbs root_1.
+ *   3. For m = 0 .. 7 absorb m as 8 little-endian bytes and take challenge() -> c[m];  alpha = (c0 .. c3) mod p, gamma =
+ *      (c4 .. c7) mod p.
+ *   4. z on the device from the unextended trace (smi_dev_perm_column).
+ *   5. smi_dev_lde of its four coordinate columns, smi_dev_merkle_build_rows(n_cols = 4) over them: root_2.
+ *   6. Absorb root_2.
+ *   7. For m = 0 .. 4 (W + K + 2) - 1 absorb 8 + m as 8 little-endian bytes and take challenge().  Weight j has the
+ *      coordinates 4 j .. 4 j + 3; column c has j = c, constraint k has j = W + k, the auxiliary boundary quotient j = W + K,
+ *      the auxiliary transition quotient j = W + K + 1.  The transcript is then 32 + 64 + 32 + 32 (W + K + 2) bytes.
+ *   8. The codeword is smi_dev_air_compose_ext under the weights 0 .. W + K - 1, plus
+ *        w_{W+K} (z(x_i) - 1) / (x_i - tau)  +  w_{W+K+1} (z(w x_i) f_R(x_i) - z(x_i) f_L(x_i)) / (x_i^n - tau^n),
+ *      f_L(x_i) = gamma + sum_j alpha^j lde[l_j][i], z(w x_i) = the extended column at index (i + B) mod N, every product
+ *      in F_q.
+ *   9. Extension FRI with grinding at E, continuing that transcript ("Grinding" above).
+ *  10. Openings: two sections, each in the layout of smi_dev_air_prove_rows with R = 4 positions per test (a, b, (a + B) mod
+ *      N, (b + B) mod N; always 4, whatever K): tree 1 with rows of W values, then tree 2 with rows of 4 values.
+ *   Proof bytes: the extension-FRI objects with their nonce record, then t 4 (9 + 8 W) + t 4 (9 + 32 log2 N) bytes, then
+ *   t 4 (9 + 32) + t 4 (9 + 32 log2 N) bytes.  Two host round trips remain, one per root: each root comes back so that the
+ *   challenges that depend on it are computed on the host.
+ * Verifier (host).  In this order: the same transcript; smi_fri_verify_ext_pow's checks at E; the exact lengths of both
+ *   sections, every record's tag and width; the leaves hashed from the bytes as they stand; all paths against root_1 and
+ *   root_2; every opened value canonical, the z coordinates included (a violation is a rejection with a reason, not a
+ *   status); the composition recomputed at x_a and x_b from the opened rows -- the main part by the code smi_air_verify_ext
+ *   runs, the two auxiliary quotients in host F_q arithmetic -- against the layer-0 triple.  A proof of
+ *   smi_dev_air_prove_ext_pow is rejected here and the other way round, and so is a proof checked under another
+ *   smi_air_perm: the challenges are the same, the recomputed composition is not.
+ * The prover does not refuse a trace whose product does not close (*closes = 0); the verifier rejects that proof, as with
+ *   smi_dev_air_check and a violated AIR.
+ * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_PERM_MAX_WIDTH; every
+ *   column index < n_cols; log_n >= 1; everything smi_air_plan refuses.
+ * Left out: more than one permutation per proof; periodic or next-row tuple members; LogUp / lookup arguments; a
+ *   column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
+ *   as a second streaming kernel over the four coordinate columns). */
+#define SMI_PERM_MAX_WIDTH 8
+typedef struct smi_air_perm {
+    uint32_t width, reserved0;      /* m, 1 .. SMI_PERM_MAX_WIDTH; explicit padding, ignored */
+    const uint32_t *left_col;       /* m column indices < n_cols                              */
+    const uint32_t *right_col;      /* m column indices < n_cols; may overlap left_col        */
+} smi_air_perm;
+/* Host only (like smi_air_plan, which it runs first): validates perm against cfg and returns d = max(d_air, 2) and E.
+ * `perm` is a pointer to an smi_air_perm, passed as the AIR is. */
+int smi_air_plan_perm(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *perm, uint32_t *degree, uint64_t *fri_expansion);
+/* The column z of the trace d_trace_cols (n_cols columns of n = 2^log_n residues, n apart) under challenges[0 .. 7] (host,
+ * unreduced): d_z gets four coordinate columns of n residues, z_stride >= n apart.  Each lane takes four consecutive rows
+ * and inverts its four denominators with one F_q inversion; the prefix product is a multi-launch scan (workgroup products,
+ * one workgroup scanning them, propagation) with no wait of one workgroup on another.  16-byte accesses when d_trace_cols
+ * and d_z are 16-byte aligned, n >= 4 and z_stride is a multiple of 4; 4-byte accesses otherwise, same values.
+ * *closes (optional) = 1 iff z[n-1] rho[n-1] = 1.  If some f_R(r) is zero the status is SMI_ERR_NO_INVERSE, smi_last_error
+ * names the smallest such r, and the context stays usable.  Synchronises (both verdicts come back to the host). */
+int smi_dev_perm_column(smi_ctx *ctx, const void *perm, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n, const uint64_t *challenges,
+                        uint32_t *d_z, size_t z_stride, int *closes);
+/* The codeword of step 8: smi_dev_air_compose_ext under the first 4 (W + K) of d_weights (4 (W + K + 2) unreduced u64 on the
+ * device), then one streaming launch that adds the two auxiliary quotients into the four coordinate columns.  d_z_lde: the
+ * extended column z, four coordinate columns of N residues z_stride >= N apart; challenges as for smi_dev_perm_column.
+ * The streaming launch makes 16-byte accesses, four points per lane, when d_lde, d_z_lde and d_out are 16-byte aligned and
+ * the three strides are multiples of 4; 4-byte accesses otherwise, same values. */
+int smi_dev_air_compose_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *perm, const uint32_t *d_lde, size_t stride,
+                             const uint32_t *d_z_lde, size_t z_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                             size_t out_stride);
+/* The prover of the protocol above.  roots (host, optional) gets root_1 then root_2; stage_ms (optional) gets six values
+ * {lde, commit, perm, compose, fri, open} -- perm is the column, its extension and its tree; *closes (optional) as above.
+ * cfg->row_leaves and cfg->open_columns are taken as set.  A zero denominator is SMI_ERR_NO_INVERSE as above. */
+int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *perm, const uint32_t *d_trace_cols, uint8_t *roots,
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, int *closes);
+int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *perm, const uint8_t *roots, const uint8_t *proof,
+                        size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

@@ -54,6 +54,11 @@ class Air(C.Structure):
                 ("n_periodic", C.c_uint32), ("reserved0", C.c_uint32), ("periodic_log_period", u32p), ("periodic_value", u64p)]
 
 
+class AirPerm(C.Structure):
+    """smi_air_perm (include/stark_mi.h, "Permutation argument"); mirror.Air.flatten fills one when Air.permutation was called"""
+    _fields_ = [("width", C.c_uint32), ("reserved0", C.c_uint32), ("left_col", u32p), ("right_col", u32p)]
+
+
 def build(force=False):
     """Compile libstarkmi.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
@@ -194,6 +199,12 @@ def lib():
                                          C.POINTER(sz), C.c_uint32]),
         "smi_dev_air_prove_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
         "smi_air_verify_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_perm": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), u32p, u64p]),
+        "smi_dev_perm_column": (i32, [vp, C.POINTER(AirPerm), vp, C.c_uint32, C.c_uint32, u64p, vp, sz, C.POINTER(i32)]),
+        "smi_dev_air_compose_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, sz, vp, sz, u64p, vp, vp, sz]),
+        "smi_dev_air_prove_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
+                                         C.c_uint32, C.POINTER(i32)]),
+        "smi_air_verify_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -23,6 +23,7 @@
 #include "hash_core.h"
 #include "internal.h"
 #include "mgpu_core.h"
+#include "perm_core.h"
 
 template <int P>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
@@ -264,6 +265,22 @@ int smi_air_plan(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t
     return air_validate(p, cfg, (const smi_air *)air, degree, fri_expansion, &g_air_err);
 }
 const char *smi_air_last_error(void) { return g_air_err.c_str(); }
+int smi_air_plan_perm(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *perm, uint32_t *degree, uint64_t *fri_expansion) {
+    g_air_err.clear();
+    return perm_plan(p, cfg, (const smi_air *)air, (const smi_air_perm *)perm, degree, fri_expansion, &g_air_err);
+}
+// what perm.hip shares with the provers of this file (internal.h)
+int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }
+int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights, uint32_t *d_out,
+                           size_t out_stride) {
+    return air_launch_compose_ext(ctx, H, d_blob, d_lde, stride, d_weights, d_out, out_stride);
+}
+int launch_air_row_open(smi_ctx *ctx, const uint32_t *d_cols, size_t stride, uint32_t W, const uint8_t *d_nodes, uint32_t depth, const uint64_t *d_top,
+                        uint32_t t, uint32_t R, uint64_t B, uint8_t *d_out) {
+    air_row_open_kernel<<<dim3(t, R), 64, 0, ctx->stream>>>(d_cols, stride, W, d_nodes, depth, d_top, t, R, B, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
 
 int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_lde, size_t stride,
                         const uint64_t *d_weights, uint32_t *d_out) {

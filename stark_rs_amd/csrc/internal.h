@@ -319,3 +319,12 @@ int dev_u32_to_host(smi_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *host
 // out[q * 2Q + Q + j] = pi_j(w x_idx[q]) -- from tables built on the device as the prover builds them; synchronises
 struct AirHost;
 int air_periodic_at(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, const std::vector<uint64_t> &idx, std::vector<uint32_t> *out);
+// air.hip, for perm.hip: the validated tables of (cfg, air) bound to host memory; the blob to d_blob and the launch of the
+// extension composition (binds H to d_blob); air_row_open_kernel on the context's stream; the periodic tables on the stream
+struct smi_air;
+int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E);
+int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights, uint32_t *d_out,
+                           size_t out_stride);
+int launch_air_row_open(smi_ctx *ctx, const uint32_t *d_cols, size_t stride, uint32_t W, const uint8_t *d_nodes, uint32_t depth, const uint64_t *d_top,
+                        uint32_t t, uint32_t R, uint64_t B, uint8_t *d_out);
+int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint32_t *d_vals, uint32_t *d_tab);

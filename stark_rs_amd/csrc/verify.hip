@@ -18,6 +18,7 @@
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
+#include "perm_core.h"
 #include "proof_parse.h"
 
 namespace {
@@ -721,4 +722,169 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(ext_field_check(ctx));
     return air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, true, true, (int)grind_bits);
+}
+
+// Verifier of smi_dev_air_prove_perm (include/stark_mi.h, "Permutation argument"), in the order the header gives: the
+// transcript of both roots; extension FRI with proof of work at E; the exact lengths, tags and widths of the two opening
+// sections; the leaves from the bytes as they stand and every path against root_1 / root_2; the canonical check, z
+// coordinates included; the composition at x_a and x_b -- the main part by air_compose_points_ext as smi_air_verify_ext runs
+// it, the two auxiliary quotients in host F_q arithmetic (ext_mul_host) -- against the layer-0 triple.
+int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *perm_, const uint8_t *roots, const uint8_t *proof,
+                        size_t proof_len, int *accept, uint32_t grind_bits) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_perm *perm = (const smi_air_perm *)perm_;
+    if (!ctx || !cfg || !air || !perm || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    std::string why;
+    uint64_t E = 0;
+    const int vrc = perm_plan(ctx->fs.F.p, cfg, air, perm, nullptr, &E, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup, NW = W + K + 2;
+    if (logN > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    const uint64_t p = ctx->fs.F.p, N = 1ull << logN, B = 1ull << cfg->log_blowup, n = 1ull << cfg->log_n, t = cfg->num_colinearity_tests;
+    const uint32_t p32 = (uint32_t)p, g = ctx->fs.g;
+    smi_fri_cfg fc;
+    fc.omega = h_root(ctx, logN);
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = N;
+    fc.expansion_factor = E;
+    fc.num_colinearity_tests = t;
+    // transcript: root_1; m = 0 .. 7; root_2; 8 + m for m = 0 .. 4 (W + K + 2) - 1
+    std::vector<uint8_t> transcript(roots, roots + 32);
+    auto absorb_index = [&](uint64_t j) {
+        for (int i = 0; i < 8; i++) transcript.push_back((uint8_t)(j >> (8 * i)));
+    };
+    uint64_t ch[8];
+    for (uint32_t m = 0; m < 8; m++) {
+        absorb_index(m);
+        SMI_TRY(challenge_of(ctx, transcript, &ch[m]));
+    }
+    transcript.insert(transcript.end(), roots + 32, roots + 64);
+    std::vector<uint64_t> weights(4 * (size_t)NW);
+    for (uint32_t m = 0; m < 4 * NW; m++) {
+        absorb_index(8 + m);
+        SMI_TRY(challenge_of(ctx, transcript, &weights[m]));
+    }
+    FsSeed seed;
+    hashc::fs_seed(transcript.data(), transcript.size(), seed.s, &seed.phase);
+    size_t end = 0;
+    const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count(fc) + 1, &end);
+    std::vector<uint64_t> top, ab;
+    size_t used = 0;
+    SMI_TRY(fri_verify_ext_objs(ctx, fc, seed, objs, accept, &top, nullptr, nullptr, &ab, &used, (int)grind_bits));
+    if (!*accept) return SMI_OK;
+    *accept = 0;
+    // ---- the two opening sections: rows of W values under root_1, rows of 4 values under root_2; R = 4 positions per test
+    const size_t R = 4, prec = 9 + 32 * (size_t)logN, m_pos = R * t;
+    const uint32_t widths[2] = {W, 4};
+    const size_t sec_len[2] = {m_pos * (9 + 8 * (size_t)W) + m_pos * prec, m_pos * (9 + 8 * (size_t)4) + m_pos * prec};
+    if (proof_len - end != sec_len[0] + sec_len[1]) return reject(ctx, accept, "perm openings: wrong length");
+    const uint64_t half = N / 2;
+    std::vector<uint64_t> pos(m_pos);
+    for (uint64_t s = 0; s < t; s++) {
+        const uint64_t a = top[s] % half;
+        const uint64_t ps[4] = {a, a + half, (a + B) & (N - 1), (a + half + B) & (N - 1)};
+        for (size_t k = 0; k < R; k++) pos[R * s + k] = ps[k];
+    }
+    std::vector<uint64_t> rows[2];
+    const uint8_t *sec = proof + end;
+    for (int v = 0; v < 2; v++) {   // tags and widths of every record of both sections first
+        const size_t rec = 9 + 8 * (size_t)widths[v];
+        const uint8_t *pathsb = sec + m_pos * rec;
+        rows[v].resize(m_pos * widths[v]);
+        for (size_t q = 0; q < m_pos; q++) {
+            const uint8_t *r = sec + q * rec, *pr = pathsb + q * prec;
+            if (r[0] != 2 || get_u64(r + 1) != widths[v]) return reject(ctx, accept, "perm openings: malformed row");
+            if (pr[0] != 3 || get_u64(pr + 1) != logN) return reject(ctx, accept, "perm openings: malformed path");
+            for (uint32_t c = 0; c < widths[v]; c++) rows[v][q * widths[v] + c] = get_u64(r + 9 + 8 * c);
+        }
+        sec += sec_len[v];
+    }
+    sec = proof + end;
+    for (int v = 0; v < 2; v++) {   // leaves from the bytes as they stand, every path against its root
+        const size_t rec = 9 + 8 * (size_t)widths[v];
+        const uint8_t *pathsb = sec + m_pos * rec;
+        std::vector<uint8_t> paths(m_pos * 32 * (size_t)logN), leaf(32 * (m_pos ? m_pos : 1)), ok(m_pos ? m_pos : 1);
+        for (size_t q = 0; q < m_pos; q++) {
+            memcpy(&paths[q * 32 * (size_t)logN], pathsb + q * prec + 9, 32 * (size_t)logN);
+            uint32_t d[8];
+            hashc::hash_bytes(sec + q * rec + 9, 8 * (size_t)widths[v], d);
+            memcpy(&leaf[32 * q], d, 32);
+        }
+        if (m_pos) SMI_TRY(smi_merkle_verify_batch(ctx, leaf.data(), pos.data(), paths.data(), m_pos, logN, roots + 32 * v, ok.data()));
+        for (size_t q = 0; q < m_pos; q++)
+            if (!ok[q]) return reject(ctx, accept, "perm openings: authentication path does not verify");
+        sec += sec_len[v];
+    }
+    for (int v = 0; v < 2; v++)
+        for (uint64_t x : rows[v])
+            if (x >= p) return reject(ctx, accept, "perm openings: an opened value is not canonical");
+    // ---- the composition at x_a and x_b
+    AirHost H;
+    air_build(ctx->fs.F, (uint32_t)fc.omega, cfg, air, &H);
+    const Fp F = ctx->fs.F;
+    const uint32_t Q = air->n_periodic;
+    std::vector<uint32_t> per;
+    if (Q) {
+        std::vector<uint64_t> at(2 * t);
+        for (uint64_t s = 0; s < t; s++)
+            for (size_t k = 0; k < 2; k++) at[2 * s + k] = pos[R * s + k];
+        SMI_TRY(air_periodic_at(ctx, cfg, H, at, &per));
+    }
+    std::vector<uint32_t> w_m(4 * AIR_MAX_WEIGHTS, 0);
+    for (uint32_t i = 0; i < 4 * (W + K); i++) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
+    uint32_t alpha[4], gamma[4], wb[4], wt[4];
+    perm_challenges(p32, ch, alpha, gamma);
+    for (int e = 0; e < 4; e++) wb[e] = (uint32_t)(weights[4 * (W + K) + e] % p), wt[e] = (uint32_t)(weights[4 * (W + K + 1) + e] % p);
+    std::vector<std::vector<uint32_t>> apow(perm->width, std::vector<uint32_t>(4, 0));
+    {
+        uint32_t pw[4] = {1, 0, 0, 0};
+        for (uint32_t j = 0; j < perm->width; j++) {
+            apow[j].assign(pw, pw + 4);
+            ext_mul_host(p32, g, pw, alpha, pw);
+        }
+    }
+    const uint64_t tau = cfg->trace_offset, tau_n = powm(tau, n, p);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < 2; k++) {
+            const uint64_t i = pos[R * s + k];
+            const uint64_t *cur = &rows[0][(R * s + k) * W], *nxt = &rows[0][(R * s + k + 2) * W];
+            const uint64_t *zc = &rows[1][(R * s + k) * 4], *zn = &rows[1][(R * s + k + 2) * 4];
+            const uint64_t x = mulm(cfg->lde_offset, powm(fc.omega, i, p), p);
+            const uint32_t x_m = air_to_m((uint32_t)x, p32), ib = (uint32_t)(i & (B - 1));
+            auto operand = [&](int, uint32_t var) {
+                const bool next = var >= W + Q;
+                const uint32_t c = next ? var - (W + Q) : var;
+                if (c >= W) return per[(2 * s + k) * 2 * Q + (next ? Q : 0) + (c - W)];
+                return (uint32_t)(next ? nxt[c] : cur[c]);
+            };
+            uint32_t got[4] = {0, 0, 0, 0};
+            air_compose_points_ext<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
+            // the auxiliary quotients
+            uint32_t fl[4], fr[4], z0[4], z1[4], a[4], b[4], bq[4], tq[4], u[4], v[4];
+            for (int e = 0; e < 4; e++) fl[e] = fr[e] = gamma[e], z0[e] = (uint32_t)zc[e], z1[e] = (uint32_t)zn[e];
+            for (uint32_t j = 0; j < perm->width; j++)
+                for (int e = 0; e < 4; e++) {
+                    fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], cur[perm->left_col[j]], p)) % p);
+                    fr[e] = (uint32_t)((fr[e] + mulm(apow[j][e], cur[perm->right_col[j]], p)) % p);
+                }
+            ext_mul_host(p32, g, z1, fr, a);
+            ext_mul_host(p32, g, z0, fl, b);
+            const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
+            for (int e = 0; e < 4; e++) {
+                tq[e] = (uint32_t)mulm((a[e] + p - b[e]) % p, izt, p);
+                bq[e] = (uint32_t)mulm(e ? z0[e] : (z0[0] + p - 1) % p, ixt, p);
+            }
+            ext_mul_host(p32, g, bq, wb, u);
+            ext_mul_host(p32, g, tq, wt, v);
+            for (uint32_t e = 0; e < 4; e++) {
+                const uint64_t want = ((uint64_t)got[e] + u[e] + v[e]) % p;
+                if (want != ab[(2 * s + k) * 4 + e] % p) return reject(ctx, accept, "perm openings: the composition of the opened rows is not the codeword value");
+            }
+        }
+    *accept = 1;
+    return SMI_OK;
 }

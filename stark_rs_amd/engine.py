@@ -498,7 +498,48 @@ class Engine:
 
     def air_plan(self, air, n_cols, log_n, log_blowup, trace_offset=1, lde_offset=None):
         """smi_air_plan -> (degree d, FRI expansion factor E); raises with the limit that was broken"""
-        return air_plan(self.p, self._air(air), self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset))
+        a = self._air(air)
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        if self._perm(a) is not None:   # smi_air_plan_perm: d = max(d_air, 2)
+            return air_plan_perm(self.p, a, a.perm, cfg)
+        return air_plan(self.p, a, cfg)
+
+    @staticmethod
+    def _perm(air):
+        """the _lib.AirPerm a flattened AIR carries (mirror.Air.permutation), or None"""
+        return getattr(air, "perm", None)
+
+    def _ck_perm(self, st):
+        if st == -1:   # SMI_ERR_NO_INVERSE: the sentence names the row
+            raise StarkMiError(st, f"{_lib.status_string(st)}: {self.L.smi_last_error(self.h).decode()}")
+        self._ck(st)
+
+    def dev_perm_column(self, air, d_trace_cols, n_cols, log_n, challenges, d_z, z_stride=None):
+        """smi_dev_perm_column: the column z of air's permutation under the 8 unreduced challenges (alpha, gamma) into four
+        coordinate columns z_stride (default n) apart -> closes (bool).  StarkMiError "no inverse: ... row r" when some
+        f_R(r) is zero."""
+        a = self._air(air)
+        if self._perm(a) is None:
+            raise ValueError("dev_perm_column: the AIR has no permutation (mirror.Air.permutation)")
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        closes = C.c_int()
+        self._ck_perm(self.L.smi_dev_perm_column(self.h, C.byref(a.perm), vp(d_trace_cols), n_cols, log_n, ch, vp(d_z),
+                                                 (1 << log_n) if z_stride is None else z_stride, C.byref(closes)))
+        return bool(closes.value)
+
+    def dev_air_compose_perm(self, air, d_lde, d_z_lde, n_cols, log_n, log_blowup, challenges, d_weights, d_out, stride=None, z_stride=None,
+                             out_stride=None, trace_offset=1, lde_offset=None):
+        """smi_dev_air_compose_perm: smi_dev_air_compose_ext under the first 4 (W + K) of the 4 (W + K + 2) device weights plus
+        the two auxiliary quotients of the extended column d_z_lde"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        a = self._air(air)
+        if self._perm(a) is None:
+            raise ValueError("dev_air_compose_perm: the AIR has no permutation (mirror.Air.permutation)")
+        N = 1 << (log_n + log_blowup)
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        self._ck(self.L.smi_dev_air_compose_perm(self.h, C.byref(cfg), C.byref(a), C.byref(a.perm), vp(d_lde), N if stride is None else stride,
+                                                 vp(d_z_lde), N if z_stride is None else z_stride, ch, vp(d_weights), vp(d_out),
+                                                 N if out_stride is None else out_stride))
 
     def dev_air_compose(self, air, d_lde, n_cols, log_n, log_blowup, d_weights, d_out, stride=None, trace_offset=1, lde_offset=None):
         """the composition codeword of n_cols extended device columns under n_cols + K unreduced device weights"""
@@ -534,12 +575,38 @@ class Engine:
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
         one root, shape (1, 32), and the proof opens every queried position once (verify with row_leaves=True).
         ext (needs row_leaves): smi_dev_air_prove_ext -- weights and FRI over the quartic extension.
-        grind_bits (needs ext; None: no grinding): smi_dev_air_prove_ext_pow -- proof-of-work bits before the query indices."""
+        grind_bits (needs ext; None: no grinding): smi_dev_air_prove_ext_pow -- proof-of-work bits before the query indices.
+        An AIR with a permutation (mirror.Air.permutation) takes smi_dev_air_prove_perm: row_leaves=True and ext=True are
+        required (ValueError otherwise), grind_bits None counts as 0, column_roots is (2, 32) -- root_1, root_2 --, stage_ms has
+        a sixth stage "perm", the result has "closes", and check=True raises when the product does not close."""
+        a = self._air(air)
+        if self._perm(a) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("dev_air_prove: an AIR with a permutation needs row_leaves=True, ext=True")
+            if check:
+                ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+                if not ok:
+                    raise StarkMiError(-50, why)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.zeros((2, 32), dtype=np.uint8)
+            proof, plen, closes = vp(), C.c_size_t(), C.c_int()
+            top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
+            stage = (C.c_double * 6)()
+            self._ck_perm(self.L.smi_dev_air_prove_perm(self.h, C.byref(cfg), C.byref(a), C.byref(a.perm), vp(d_trace_cols), roots.ctypes.data,
+                                                        C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                        0 if grind_bits is None else grind_bits, C.byref(closes)))
+            b = C.string_at(proof, plen.value)
+            self.L.smi_free(proof)
+            if check and not closes.value:
+                raise StarkMiError(-50, "air_prove_perm: the permutation product does not close (the two multisets differ)")
+            out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]], "closes": bool(closes.value)}
+            if timed:
+                out["stage_ms"] = dict(zip(("lde", "commit", "perm", "compose", "fri", "open"), [float(x) for x in stage]))
+            return out
         if ext and not row_leaves:
             raise StarkMiError(-50, "dev_air_prove(ext=True) commits to one tree over the rows: pass row_leaves=True")
         if grind_bits is not None and not ext:
             raise StarkMiError(-50, "dev_air_prove(grind_bits=...) grinds the extension proof: pass ext=True")
-        a = self._air(air)
         if check:
             ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
             if not ok:
@@ -567,7 +634,21 @@ class Engine:
                    lde_offset=None, row_leaves=False, ext=False, grind_bits=None):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
-        grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded"""
+        grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
+        An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
+        column_roots is root_1 then root_2, grind_bits None counts as 0."""
+        if self._perm(self._air(air)) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("air_verify: an AIR with a permutation needs row_leaves=True, ext=True")
+            a = self._air(air)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 64:
+                raise StarkMiError(-50, "air_verify: an AIR with a permutation takes two 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_perm(self.h, C.byref(cfg), C.byref(a), C.byref(a.perm), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if ext and not row_leaves:
             raise StarkMiError(-50, "air_verify(ext=True) checks a proof over one row tree: pass row_leaves=True")
         if grind_bits is not None and not ext:
@@ -664,6 +745,16 @@ def air_plan(p, air, cfg):
     d, e = C.c_uint32(), C.c_uint64()
     L = _lib.lib()
     st = L.smi_air_plan(p, C.byref(cfg), C.byref(air), C.byref(d), C.byref(e))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, e.value
+
+
+def air_plan_perm(p, air, perm, cfg):
+    """smi_air_plan_perm (host only) -> (d = max(d_air, 2), E).  air: a flattened _lib.Air; perm: a _lib.AirPerm"""
+    d, e = C.c_uint32(), C.c_uint64()
+    L = _lib.lib()
+    st = L.smi_air_plan_perm(p, C.byref(cfg), C.byref(air), C.byref(perm), C.byref(d), C.byref(e))
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value

@@ -798,13 +798,21 @@ class Air:
         air.transition({("next", 1): 1, (("per_next", k), ("cur", 1, 2)): -1})    # b' = k' b^2
 
     ("per", j[, exponent]) is periodic column j at this row, ("per_next", j[, exponent]) at the next row.  Factors are
-    kept symbolic until they are used, so periodic columns may be declared before or after the constraints."""
+    kept symbolic until they are used, so periodic columns may be declared before or after the constraints.
+
+    A permutation argument (include/stark_mi.h, "Permutation argument"; one per AIR) claims that two lists of row tuples
+    are equal as multisets over all rows:
+
+        air.permutation([0, 1], [2, 3])                         # {(c0[r], c1[r])} = {(c2[r], c3[r])}
+
+    With it set, Engine.air_plan / dev_air_prove / air_verify take the smi_*_perm entry points."""
 
     def __init__(self, n_cols):
         self.n_cols = n_cols
         self._symbolic = []     # [[(coeff, [(kind, index, exp), ...]), ...], ...]
         self.boundaries = []    # [(col, row, value), ...]
         self.periodics = []     # [[value, ...], ...]: a power-of-two number of integers each
+        self.perm = None        # ([left columns], [right columns]) once permutation() was called
 
     @property
     def constraints(self):
@@ -825,6 +833,31 @@ class Air:
             raise ValueError("the period must be a power of two")
         self.periodics.append(values)
         return len(self.periodics) - 1
+
+    def permutation(self, left, right):
+        """the multiset of the tuples (T[left[0]][r], ..) over all rows equals that of (T[right[0]][r], ..); 1 .. 8 columns a
+        side, the two lists may overlap"""
+        left, right = [int(c) for c in left], [int(c) for c in right]
+        if len(left) != len(right):
+            raise ValueError("a permutation relates tuples of one width")
+        if self.perm is not None:
+            raise ValueError("one permutation per AIR")
+        self.perm = (left, right)
+        return self
+
+    def closes(self, p, g, cols, alpha, gamma):
+        """z[n-1] * rho[n-1] == 1 for the trace cols under alpha, gamma (four canonical coordinates each); plain Python"""
+        left, right = self.perm
+        num = den = Ext4([1, 0, 0, 0], p, g)
+        a, c = Ext4(alpha, p, g), Ext4(gamma, p, g)
+        for r in range(len(cols[0])):
+            fl = fr = c
+            pw = Ext4([1, 0, 0, 0], p, g)
+            for lj, rj in zip(left, right):
+                fl, fr = fl + pw * Ext4.embed(int(cols[lj][r]), p, g), fr + pw * Ext4.embed(int(cols[rj][r]), p, g)
+                pw = pw * a
+            num, den = num * fl, den * fr
+        return num == den
 
     def with_periodic_as_trace(self):
         """-> the AIR over n_cols + Q trace columns that states the same transitions with the periodic columns read as
@@ -880,6 +913,11 @@ class Air:
                        ptr(arrs[2], _lib.u32p), ptr(arrs[3], _lib.u32p), ptr(arrs[4], _lib.u32p), ptr(arrs[5], _lib.u32p),
                        ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p), len(self.periodics), 0, ptr(arrs[8], _lib.u32p), ptr(arrs[9], _lib.u64p))
         out._keep = arrs
+        out.perm = None
+        if self.perm is not None:
+            la, ra = np.array(self.perm[0], dtype=np.uint32), np.array(self.perm[1], dtype=np.uint32)
+            out.perm = _lib.AirPerm(len(la), 0, ptr(la, _lib.u32p), ptr(ra, _lib.u32p))
+            out.perm._keep = (la, ra)
         return out
 
     def periodic_row(self, p, r):

@@ -417,49 +417,23 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     else SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
     mark(2);
     // The roots make one small round trip: the transcript (roots, then the indices) and its weights
-    // are computed on the host, where fri_run's seed is computed anyway (FsSeed, internal.h).
-    std::vector<uint8_t> roots(32 * (size_t)n_trees), tr;
+    // are computed on the host, where fri_run's seed is computed anyway (transcript_core.h).
+    std::vector<uint8_t> roots(32 * (size_t)n_trees);
     HIP_TRY(ctx, hipMemcpy2DAsync(roots.data(), 32, tree_base + (2 * N - 2) * 32, tree_stride, 32, n_trees, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // part of the compose stage, queued before the host waits for the roots
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> weights((size_t)NE * (W + K));
-    auto challenge = [&]() {
-        uint32_t d[8];
-        hashc::hash_bytes(tr.data(), tr.size(), d);
-        return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-    };
-    auto absorb_index = [&](uint64_t j) {
-        for (int i = 0; i < 8; i++) tr.push_back((uint8_t)(j >> (8 * i)));
-    };
-    if (rows) {   // the root, then j = 0 .. W + K - 1 (ext: m = 0 .. 4 (W + K) - 1, coordinate m mod 4 of weight m / 4) with a challenge after each
-        tr = roots;
-        for (uint32_t j = 0; j < NE * (W + K); j++) {
-            absorb_index(j);
-            weights[j] = challenge();
-        }
-    } else {
-        for (uint32_t c = 0; c < W; c++) {
-            tr.insert(tr.end(), roots.begin() + 32 * c, roots.begin() + 32 * c + 32);
-            weights[c] = challenge();
-        }
-        for (uint32_t k = 0; k < K; k++) {
-            absorb_index(k);
-            weights[W + k] = challenge();
-        }
-    }
-    FsSeed seed;
-    hashc::fs_seed(tr.data(), tr.size(), seed.s, &seed.phase);
+    Transcript tr;
+    std::vector<uint64_t> weights;   // NE (W + K) of them
+    if (ext) transcript_ext(tr, roots.data(), W, K, &weights);
+    else if (rows) transcript_rows(tr, roots.data(), W, K, &weights);
+    else transcript_columns(tr, roots.data(), W, K, &weights);
+    const FsSeed seed = tr.seed();
     if (column_roots) memcpy(column_roots, roots.data(), roots.size());
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     if (ext) SMI_TRY(air_launch_compose_ext(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
     else SMI_TRY(air_launch_compose(ctx, H, d_blob, d_lde, N, d_weights, d_cw));
     mark(3);
-    smi_fri_cfg fc;
-    fc.omega = h_root(ctx, log_N);
-    fc.offset = cfg->lde_offset;
-    fc.domain_length = N;
-    fc.expansion_factor = E;
-    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriResult res;
     FriExtResult xres;
     if (ext) {

@@ -9,6 +9,8 @@
 // (emu_ntt: an inverse transform per group, then a forward one on the group's coset), not with anything of the GPU path.
 // emu_air_row_open runs air_row_open_kernel's grid -- one workgroup of 64 lanes per (test, position) -- over the record
 // writer both share (mgpu_core.h mg_row_open_write).
+// emu_air_transcript runs the transcript layouts of transcript_core.h, the code provers and verifiers derive the weights and
+// FRI's seed with.
 // There is no emu_air_prove / emu_air_verify: the emulator has no single-device Fri::prove loop to continue a
 // transcript with (emu_mgpu.cpp emulates the multi-GPU round loop only), and the verifier is host code already.
 #include <string.h>
@@ -19,6 +21,7 @@
 #include "air_core.h"
 #include "mgpu_core.h"
 #include "tables.h"
+#include "transcript_core.h"
 
 extern "C" int emu_ntt(uint64_t p, uint64_t g, const uint32_t *in, uint32_t *out, uint32_t L, uint32_t n_in, uint32_t batch, uint64_t in_stride,
                        uint64_t out_stride, int inverse, uint64_t offset, uint64_t post_scale);
@@ -173,4 +176,24 @@ extern "C" uint64_t emu_air_row_open(const uint32_t *cols, uint64_t stride, uint
         for (uint32_t k = 0; k < R; k++)
             for (uint32_t lane = 0; lane < 64; lane++) mg_row_open_write(cols, stride, W, nodes, depth, top[s], s, k, t, out, lane, 64, R, B);
     return mg_row_open_bytes(W, t, depth, R);
+}
+
+// transcript_core.h: layout 0 column trees (roots = W roots), 1 one row tree, 2 the extension, 3 the permutation proof (roots =
+// root_1, root_2; the 8 challenges, then the 4 (W + K + 2) weights) -> the number of challenges written; seed = the 16 words
+// and the phase FRI continues
+extern "C" uint64_t emu_air_transcript(int layout, const uint8_t *roots, uint32_t W, uint32_t K, uint64_t *challenges, uint32_t *seed) {
+    Transcript T;
+    std::vector<uint64_t> out;
+    if (layout == 0) transcript_columns(T, roots, W, K, &out);
+    else if (layout == 1) transcript_rows(T, roots, W, K, &out);
+    else if (layout == 2) transcript_ext(T, roots, W, K, &out);
+    else {
+        transcript_perm_challenges(T, roots, &out);
+        transcript_perm_weights(T, roots + 32, W, K, &out);
+    }
+    memcpy(challenges, out.data(), 8 * out.size());
+    const FsSeed z = T.seed();
+    memcpy(seed, z.s, sizeof z.s);
+    seed[16] = z.phase;
+    return out.size();
 }

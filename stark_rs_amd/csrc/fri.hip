@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void fri_fold_kernel(const uint32_t *__restric
 // fs_state (16 words) and `challenge` = 8 more mixes on a copy: the same function of the
 // whole transcript as re-hashing it, evaluated incrementally.
 // A caller's transcript that is not whole 32-byte chunks leaves `phase` bytes pending (hash_core.h fs_seed); the phase
-// rides in the state (FsSeed, internal.h) so that the phase-aware kernels below read it with the words.
+// rides in the state (FsSeed, transcript_core.h) so that the phase-aware kernels below read it with the words.
 
 // the seed (the initial constants for a fresh transcript) arrives by value: it is computed on the host
 // (ride_*: a few bytes of the caller's -- the column roots of a prove -- placed behind the proof, to come back with its copy)
@@ -44,11 +44,6 @@ __global__ void fs_init_kernel(FsSeed *fs, FsSeed seed, const uint8_t *ride_src 
     if (threadIdx.x) return;
     for (int i = 0; i < 16; i++) fs->s[i] = seed.s[i];
     fs->phase = seed.phase;
-}
-static FsSeed fresh_seed() {
-    FsSeed z;
-    hashc::fs_seed(nullptr, 0, z.s, &z.phase);
-    return z;
 }
 
 // absorb the root at `root`, append it (tag 0 + 32 bytes, src/stream.rs:39-42) to the proof

@@ -11,6 +11,7 @@
 #include "../../include/stark_mi.h"
 #include "fri_plan.h"
 #include "tables.h"
+#include "transcript_core.h"
 
 struct ScaleEntry {
     uint32_t c, q, L;
@@ -167,6 +168,18 @@ inline uint32_t h_root(const smi_ctx *c, uint32_t log_n) {  // primitive 2^log_n
     return host_powmod(c->fs.wmax[0], 1ull << (c->fs.K - log_n), c->fs.F.p);
 }
 
+// the FRI instance of a proof over the extended trace domain (stark.hip's build-defined composition at E = the blowup,
+// the AIR proofs at the E of their plan): provers and verifiers take it from here
+inline smi_fri_cfg trace_fri_cfg(const smi_ctx *c, const smi_stark_cfg *cfg, uint64_t E) {
+    smi_fri_cfg fc;
+    fc.omega = h_root(c, cfg->log_n + cfg->log_blowup);
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = 1ull << (cfg->log_n + cfg->log_blowup);
+    fc.expansion_factor = E;
+    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    return fc;
+}
+
 // One launch for the last rounds of Fri::commit (hash.hip, fri_tail_kernel): round k hashes and commits
 // cw (len elements), runs the Fiat-Shamir round of its root and, unless next == nullptr (the last
 // round), folds into next with the round's x^-1 table S.
@@ -194,15 +207,7 @@ struct FriTailArgs {
 };
 int launch_fri_tail(smi_ctx *ctx, const FriTailArgs &a);
 uint64_t fri_tail_len();   // codewords of at most this many elements finish in the fused tail (SMI_FRI_TAIL, default 512; fri.hip)
-// A caller's Fiat-Shamir transcript as the prover continues it (hash_core.h fs_seed): the sponge state after its whole
-// 32-byte chunks and its trailing bytes, and the count of those trailing bytes.  Computed on the host: the reference's
-// transcript is a host Vec<u8>.  The same 17 words are the transcript's state on the device.  phase == 0 (every transcript
-// of whole roots, the empty one included) runs the fused Fiat-Shamir sites; phase != 0 takes the single-lane phase-aware
-// kernels after each tree and no fused tail.
-struct FsSeed {
-    uint32_t s[16];
-    uint32_t phase;
-};
+inline FsSeed fresh_seed() { return fs_seed_of(nullptr, 0); }   // FsSeed: transcript_core.h
 
 // Where the leaves of a tree come from when they are not simply read (hash.hip, merkle_sub_kernel's LEAF_* kinds): the
 // kernel computes the codeword element, stores it to cw_out (the query phase and the next fold read it) and hashes it.

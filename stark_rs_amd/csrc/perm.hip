@@ -358,26 +358,14 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     mark(2);
     // first round trip: root_1 -> alpha, gamma
     uint8_t roots[64];
-    std::vector<uint8_t> tr;
     HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    auto challenge = [&]() {
-        uint32_t d[8];
-        hashc::hash_bytes(tr.data(), tr.size(), d);
-        return (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-    };
-    auto absorb_index = [&](uint64_t j) {
-        for (int i = 0; i < 8; i++) tr.push_back((uint8_t)(j >> (8 * i)));
-    };
-    tr.assign(roots, roots + 32);
-    uint64_t ch[8];
-    for (uint32_t m = 0; m < 8; m++) {
-        absorb_index(m);
-        ch[m] = challenge();
-    }
+    Transcript tr;
+    std::vector<uint64_t> ch, weights;   // 8 challenges; 4 NW weights
+    transcript_perm_challenges(tr, roots, &ch);
     PermDev PD;
-    perm_build(ctx->fs.F, ctx->fs.g, perm, ch, &PD);
+    perm_build(ctx->fs.F, ctx->fs.g, perm, ch.data(), &PD);
     SMI_TRY(perm_column_enqueue(ctx, PD, d_trace_cols, log_n, d_z, n, d_ptmp));
     SMI_TRY(smi_dev_lde(ctx, d_z, 4, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_zl));
     SMI_TRY(launch_merkle_rows(ctx, d_zl, 4, N, N, tree2));
@@ -388,25 +376,14 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     HIP_TRY(ctx, hipMemcpyAsync(&fl, perm_column_flags(d_ptmp, log_n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     SMI_TRY(perm_column_verdict(ctx, fl, closes));
-    tr.insert(tr.end(), roots + 32, roots + 64);
-    std::vector<uint64_t> weights(4 * (size_t)NW);
-    for (uint32_t m = 0; m < 4 * NW; m++) {
-        absorb_index(8 + m);
-        weights[m] = challenge();
-    }
-    FsSeed seed;
-    hashc::fs_seed(tr.data(), tr.size(), seed.s, &seed.phase);
+    transcript_perm_weights(tr, roots + 32, W, K, &weights);
+    const FsSeed seed = tr.seed();
     if (roots_out) memcpy(roots_out, roots, 64);
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
     SMI_TRY(perm_compose_enqueue(ctx, PD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_zl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
     mark(4);
-    smi_fri_cfg fc;
-    fc.omega = h_root(ctx, log_N);
-    fc.offset = cfg->lde_offset;
-    fc.domain_length = N;
-    fc.expansion_factor = E;
-    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriExtResult xres;
     SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
     std::vector<uint8_t> &bytes = xres.proof;

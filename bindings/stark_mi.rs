@@ -50,6 +50,7 @@ pub const SMI_ERR_UNSUPPORTED_PRIME: c_int = -52;
 pub const SMI_ERR_NOT_GEOMETRIC: c_int = -53;
 pub const SMI_ERR_COLUMNS_NOT_BOUND: c_int = -54;
 pub const SMI_ERR_GRIND_EXHAUSTED: c_int = -55;
+pub const SMI_ERR_LOOKUP_MISSING: c_int = -56;
 pub const SMI_ERR_HIP: c_int = -100;
 pub const SMI_ERR_NO_DEVICE: c_int = -101;
 pub const SMI_ERR_OOM: c_int = -102;
@@ -127,6 +128,14 @@ pub struct smi_air_perm {
     pub left_col: *const u32,
     pub right_col: *const u32,
 }
+/// smi_air_lookup: one lookup argument (host pointers; the entry points take it as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_lookup {
+    pub width: u32,
+    pub mult_col: u32,
+    pub lookup_col: *const u32,
+    pub table_col: *const u32,
+}
 pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
 pub const SMI_AIR_MAX_TERMS: u32 = 1024;
 pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
@@ -135,6 +144,7 @@ pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
 pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
 pub const SMI_GRIND_MAX_BITS: u32 = 32;
 pub const SMI_PERM_MAX_WIDTH: u32 = 8;
+pub const SMI_LOOKUP_MAX_WIDTH: u32 = 8;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -240,6 +250,12 @@ extern "C" {
     pub fn smi_dev_air_compose_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, d_lde: *const u32, stride: usize, d_z_lde: *const u32, z_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
     pub fn smi_dev_air_prove_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut c_int) -> c_int;
     pub fn smi_air_verify_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_lookup(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
+    pub fn smi_dev_lookup_multiplicities(ctx: *mut smi_ctx, lookup: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, d_mult: *mut u32) -> c_int;
+    pub fn smi_dev_lookup_column(ctx: *mut smi_ctx, lookup: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: *const u64, d_s: *mut u32, s_stride: usize, closes: *mut c_int) -> c_int;
+    pub fn smi_dev_air_compose_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, d_lde: *const u32, stride: usize, d_s_lde: *const u32, s_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_prove_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut c_int) -> c_int;
+    pub fn smi_air_verify_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -915,6 +931,89 @@ impl Air {
         } else {
             Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
         }
+    }
+    /// `smi_air_plan_lookup` (host only): `(max(degree, 3), FRI expansion factor)` of this AIR with the lookup `lookup`.
+    pub fn plan_lookup(&self, p: u64, cfg: &smi_stark_cfg, lookup: &Lookup) -> (u32, u64) {
+        let (mut d, mut e) = (0u32, 0u64);
+        let st = self.with_raw(|a| lookup.with_raw(|lk| unsafe { smi_air_plan_lookup(p, cfg, a, lk, &mut d, &mut e) }));
+        if st != SMI_OK {
+            panic!("{}: {}", status_text(st), unsafe { CStr::from_ptr(smi_air_last_error()) }.to_string_lossy());
+        }
+        (d, e)
+    }
+    /// `smi_dev_air_prove_lookup` -> (root_1 then root_2, proof bytes, closes): the AIR proof with the lookup argument
+    /// `lookup` over a committed extension column; the trace's multiplicity column is taken as filled
+    /// (`Lookup::multiplicities`).  A trace whose sum does not close is proved all the same (`closes` is false and the
+    /// verifier rejects); a zero denominator panics with "no inverse" and the row.
+    pub fn prove_lookup(&self, ctx: &Context, cfg: &smi_stark_cfg, lookup: &Lookup, d_trace_cols: *const u32, grind_bits: u32) -> ([u8; 64], Vec<u8>, bool) {
+        let mut roots = [0u8; 64];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        let mut closes = 0 as c_int;
+        ctx.check(self.with_raw(|a| lookup.with_raw(|lk| unsafe {
+            smi_dev_air_prove_lookup(ctx.raw, cfg, a, lk, d_trace_cols, roots.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut(), grind_bits, &mut closes)
+        })));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (roots, bytes, closes != 0)
+    }
+    /// `smi_air_verify_lookup` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify_lookup(&self, ctx: &Context, cfg: &smi_stark_cfg, lookup: &Lookup, roots: &[u8; 64], proof: &[u8], grind_bits: u32) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| lookup.with_raw(|lk| unsafe {
+            smi_air_verify_lookup(ctx.raw, cfg, a, lk, roots.as_ptr(), proof.as_ptr(), proof.len(), &mut accept, grind_bits)
+        })));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+    /// `smi_dev_air_compose_lookup`: the composition under the first 4 (W + K) of the 4 (W + K + 2) device weights plus the
+    /// two auxiliary quotients of the extended column `d_s_lde`, into four coordinate columns `out_stride` apart.
+    pub fn compose_lookup(&self, ctx: &Context, cfg: &smi_stark_cfg, lookup: &Lookup, d_lde: *const u32, stride: usize, d_s_lde: *const u32, s_stride: usize,
+                          challenges: &[u64; 8], d_weights: *const u64, d_out: *mut u32, out_stride: usize) {
+        ctx.check(self.with_raw(|a| lookup.with_raw(|lk| unsafe {
+            smi_dev_air_compose_lookup(ctx.raw, cfg, a, lk, d_lde, stride, d_s_lde, s_stride, challenges.as_ptr(), d_weights, d_out, out_stride)
+        })));
+    }
+}
+
+/// One lookup argument (include/stark_mi.h, "Lookup argument"): every row tuple over the `lookup` columns occurs among
+/// the row tuples over the `table` columns, column `mult_col` holding the multiplicities; 1 ..= `SMI_LOOKUP_MAX_WIDTH`
+/// columns a side, the lists may overlap, `mult_col` is none of them.
+pub struct Lookup {
+    lookup: Vec<u32>,
+    table: Vec<u32>,
+    mult_col: u32,
+}
+
+impl Lookup {
+    pub fn new(lookup: &[u32], table: &[u32], mult_col: u32) -> Lookup {
+        assert!(lookup.len() == table.len() && !lookup.is_empty() && lookup.len() <= SMI_LOOKUP_MAX_WIDTH as usize, "1 ..= SMI_LOOKUP_MAX_WIDTH columns a side");
+        Lookup { lookup: lookup.to_vec(), table: table.to_vec(), mult_col }
+    }
+    fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        let raw = smi_air_lookup { width: self.lookup.len() as u32, mult_col: self.mult_col, lookup_col: self.lookup.as_ptr(), table_col: self.table.as_ptr() };
+        f(&raw as *const smi_air_lookup as *const c_void)
+    }
+    /// `smi_dev_lookup_multiplicities`: the multiplicities of the device trace into `d_mult` (n residues, zeroed by the
+    /// call) -> `Ok(())`, or the smallest row whose tuple is in no table row.
+    pub fn multiplicities(&self, ctx: &Context, d_trace_cols: *const u32, n_cols: u32, log_n: u32, d_mult: *mut u32) -> Result<(), String> {
+        let st = self.with_raw(|lk| unsafe { smi_dev_lookup_multiplicities(ctx.raw, lk, d_trace_cols, n_cols, log_n, d_mult) });
+        if st == SMI_ERR_LOOKUP_MISSING {
+            return Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned());
+        }
+        ctx.check(st);
+        Ok(())
+    }
+    /// `smi_dev_lookup_column`: the column s of the device trace under the 8 unreduced challenges into four coordinate
+    /// columns `s_stride` apart -> closes.  Panics with "no inverse" and the row when a denominator is zero.
+    pub fn column(&self, ctx: &Context, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: &[u64; 8], d_s: *mut u32, s_stride: usize) -> bool {
+        let mut closes = 0 as c_int;
+        ctx.check(self.with_raw(|lk| unsafe {
+            smi_dev_lookup_column(ctx.raw, lk, d_trace_cols, n_cols, log_n, challenges.as_ptr(), d_s, s_stride, &mut closes)
+        }));
+        closes != 0
     }
 }
 

@@ -60,6 +60,7 @@ enum {
     SMI_ERR_COLUMNS_NOT_BOUND = -54,  /* smi_stark_verify on a proof made without open_columns: nothing in it refers to the
                                          column roots, so it can only be checked as a FRI proof (smi_fri_verify) */
     SMI_ERR_GRIND_EXHAUSTED = -55,    /* no nonce below the search cap meets the proof-of-work difficulty ("Grinding") */
+    SMI_ERR_LOOKUP_MISSING = -56,     /* smi_dev_lookup_multiplicities: a looked-up tuple is in no table row ("Lookup argument") */
     /* runtime */
     SMI_ERR_HIP = -100,
     SMI_ERR_NO_DEVICE = -101,
@@ -542,8 +543,8 @@ int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   fold fused into the launch that hashes the row leaves (the base-field path's LEAF_FOLD) and a fused tail.  The query
  *   phase of the entry points of this section rests on t colinearity tests alone; "Grinding" below adds proof-of-work
  *   bits to it (smi_dev_fri_prove_ext_pow / smi_dev_air_prove_ext_pow).  A committed extension-field column (an auxiliary
- *   trace) exists in one form, "Permutation argument" below: one permutation per proof, no periodic or next-row tuple
- *   members, no LogUp / lookup argument, no column-tree or smi_mgpu_* twin. */
+ *   trace) exists in two forms, "Permutation argument" and "Lookup argument" below: one permutation per proof or one
+ *   lookup per proof and not both, no periodic or next-row tuple members, no selectors, no column-tree or smi_mgpu_* twin. */
 #define SMI_EXT_DEGREE 4
 /* Host only, no context (like smi_air_plan): out = a * b and out = a^-1 in F_q, coordinates canonical.  SMI_ERR_BAD_ARG
  * for a (p, g) the section refuses (p not a prime < 2^31 that is 1 mod 4, g a square or outside 1 .. p-1),
@@ -715,8 +716,8 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
  *   smi_dev_air_check and a violated AIR.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_PERM_MAX_WIDTH; every
  *   column index < n_cols; log_n >= 1; everything smi_air_plan refuses.
- * Left out: more than one permutation per proof; periodic or next-row tuple members; LogUp / lookup arguments; a
- *   column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
+ * Left out: more than one permutation per proof; periodic or next-row tuple members; a permutation together with a
+ *   lookup ("Lookup argument" below); a column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
  *   as a second streaming kernel over the four coordinate columns). */
 #define SMI_PERM_MAX_WIDTH 8
 typedef struct smi_air_perm {
@@ -751,6 +752,91 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, int *closes);
 int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *perm, const uint8_t *roots, const uint8_t *proof,
                         size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Lookup argument: LogUp over a committed extension column ----------------------------------
+ * The permutation argument states that two lists of row tuples are equal as multisets.  This one states that every tuple of
+ * one list OCCURS in the other -- range checks, opcode and instruction tables, byte decompositions, S-box tables, memory-
+ * address membership -- by the logarithmic-derivative argument (LogUp): sum_r 1 / (X + l_r) = sum_t M_t / (X + t_t) as
+ * rational functions iff every l_r is some t_t and M counts them.  The construction follows "Permutation argument" step
+ * by step with a running SUM s in place of the running product z; the entry points above are unchanged, byte for byte.
+ *
+ * Statement.  With m = width in 1 .. SMI_LOOKUP_MAX_WIDTH, l_j = lookup_col[j], t_j = table_col[j], mult_col a trace column
+ *   that is none of those 2 m, and T the trace (n = 2^log_n rows): for every row r the tuple (T[l_0][r], .., T[l_{m-1}][r])
+ *   occurs among the n table tuples (T[t_0][t], .., T[t_{m-1}][t]).  Column mult_col holds the multiplicities: M[t] = the
+ *   number of rows r whose lookup tuple equals table tuple t; when several table rows hold the same tuple it is credited
+ *   to the lowest such t and the others hold 0.  M[t] <= n <= 2^27 < p: the characteristic does not interfere.  A short table
+ *   is padded by repeating an entry; lookups that are not wanted are padded by repeating a table entry.  One lookup per
+ *   proof, and not together with a permutation.
+ * The column.  With alpha, gamma in F_q:  f_L(r) = gamma + sum_j alpha^j T[l_j][r], f_T likewise with t_j;
+ *   s[0] = 0, s[r+1] = s[r] + 1 / f_L(r) - M[r] / f_T(r).  The statement holds iff (up to about n m / q) the sum closes:
+ *   s[n-1] + 1 / f_L(n-1) - M[n-1] / f_T(n-1) = 0.  s is four coordinate columns of n residues.
+ * Auxiliary constraints.  The boundary quotient is s(x) / (x - tau); the transition WRAPS AROUND:
+ *   ((s(w x) - s(x)) f_L(x) f_T(x) - f_T(x) + M(x) f_L(x)) / (x^n - tau^n).  The transition has degree 3: d = max(d_air, 3),
+ *   D >= 2, E = B / D, so log_blowup >= 3 is needed for E >= 4 (SMI_ERR_EXPANSION_TOO_SMALL otherwise).
+ * Protocol.  The ten steps of the permutation argument with s in place of z:
+ *   1. smi_dev_lde of the trace -- mult_col included, so the multiplicities are committed before alpha and gamma are
+ *      drawn --, the tree over its rows: root_1.
+ *   2-3. The transcript absorbs root_1; eight challenges under the counters 0 .. 7: alpha = (c0 .. c3) mod p, gamma =
+ *      (c4 .. c7) mod p.
+ *   4-6. s on the device from the unextended trace (smi_dev_lookup_column), smi_dev_lde of its four coordinate columns, the
+ *      tree over their rows: root_2, absorbed.
+ *   7. 4 (W + K + 2) weight challenges under the counters 8 + i; weight W + K is the auxiliary boundary quotient's, W + K + 1
+ *      the auxiliary transition quotient's.  The transcript is 32 + 64 + 32 + 32 (W + K + 2) bytes, as for a permutation.
+ *   8. The codeword is smi_dev_air_compose_ext under the weights 0 .. W + K - 1 plus
+ *        w_{W+K} s(x_i) / (x_i - tau)
+ *        + w_{W+K+1} ((s(w x_i) - s(x_i)) f_L(x_i) f_T(x_i) - f_T(x_i) + M(x_i) f_L(x_i)) / (x_i^n - tau^n),
+ *      f_L(x_i) = gamma + sum_j alpha^j lde[l_j][i], M(x_i) = lde[mult_col][i], s(w x_i) = the extended column at index
+ *      (i + B) mod N, every product in F_q.
+ *   9. Extension FRI with grinding at E, continuing that transcript.
+ *  10. Openings: two sections with R = 4, tree 1 with rows of W values, tree 2 with rows of 4 values.  Proof bytes and
+ *      lengths as for a permutation proof.
+ * Verifier (host).  The order of checks of smi_air_verify_perm, its sentences starting "lookup openings:".  A permutation
+ *   proof checked here is rejected on the composition, and the other way round: transcript and layout are the same, the
+ *   recomputed composition is not.  So is a proof checked under another smi_air_lookup.
+ * The prover takes the trace as const with mult_col filled (smi_dev_lookup_multiplicities fills it for a caller who has
+ *   not).  It does not refuse a wrong M or a missing lookup: *closes = 0 and the verifier rejects that proof.
+ * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_LOOKUP_MAX_WIDTH; every
+ *   column index < n_cols; mult_col none of the tuple columns; log_n >= 1; everything smi_air_plan refuses.
+ * Left out: several lookups, or several looked-up tuples sharing one table; selectors; periodic or next-row tuple
+ *   members; a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
+ *   column-tree or smi_mgpu_* twin. */
+#define SMI_LOOKUP_MAX_WIDTH 8
+typedef struct smi_air_lookup {
+    uint32_t width, mult_col;       /* m, 1 .. SMI_LOOKUP_MAX_WIDTH; the multiplicity column, < n_cols */
+    const uint32_t *lookup_col;     /* m column indices < n_cols                                        */
+    const uint32_t *table_col;      /* m column indices < n_cols; may overlap lookup_col                */
+} smi_air_lookup;
+/* Host only (like smi_air_plan, which it runs first): validates lookup against cfg and returns d = max(d_air, 3) and E.
+ * `lookup` is a pointer to an smi_air_lookup, passed as the AIR is. */
+int smi_air_plan_lookup(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *lookup, uint32_t *degree, uint64_t *fri_expansion);
+/* A helper for callers, never called by the prover: d_mult (n residues, zeroed by the call) gets the multiplicities M of the
+ * statement above for the trace d_trace_cols (n_cols columns of n = 2^log_n residues, n apart; column mult_col is not
+ * read).  Two launches over an open-addressing table of 2 n row indices: the table tuples are inserted with the lowest row
+ * winning, then every lookup tuple is probed for and counted with an atomic add.  Every probe loop is bounded by the
+ * table's size and no lane waits on another.  The result does not depend on the hash function or on scheduling.  If some
+ * lookup tuple is in no table row the status is SMI_ERR_LOOKUP_MISSING, smi_last_error names the smallest such row, d_mult
+ * holds the counts of the others, and the context stays usable.  Synchronises. */
+int smi_dev_lookup_multiplicities(smi_ctx *ctx, const void *lookup, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n, uint32_t *d_mult);
+/* The column s of the trace under challenges[0 .. 7] (host, unreduced): d_s gets four coordinate columns of n residues,
+ * s_stride >= n apart.  The three launches of smi_dev_perm_column -- workgroup sums, one workgroup scanning them,
+ * propagation; no wait of one workgroup on another -- with an additive scan; each lane takes four consecutive rows and
+ * inverts its four products f_L f_T with one F_q inversion.  16-byte accesses when d_trace_cols and d_s are 16-byte aligned,
+ * n >= 4 and s_stride is a multiple of 4; 4-byte accesses otherwise, same values.  *closes (optional) = 1 iff the sum
+ * closes.  If some f_L(r) or f_T(r) is zero the status is SMI_ERR_NO_INVERSE, smi_last_error names the smallest such r and
+ * which of the two it was, and the context stays usable.  Synchronises. */
+int smi_dev_lookup_column(smi_ctx *ctx, const void *lookup, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n, const uint64_t *challenges,
+                          uint32_t *d_s, size_t s_stride, int *closes);
+/* The codeword of step 8; arguments and access rules as for smi_dev_air_compose_perm, d_s_lde the extended column s. */
+int smi_dev_air_compose_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *lookup, const uint32_t *d_lde, size_t stride,
+                               const uint32_t *d_s_lde, size_t s_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                               size_t out_stride);
+/* The prover of the protocol above.  roots (host, optional) gets root_1 then root_2; stage_ms (optional) gets six values
+ * {lde, commit, lookup, compose, fri, open} -- lookup is the column, its extension and its tree; *closes (optional) as
+ * above.  cfg->row_leaves and cfg->open_columns are taken as set.  A zero denominator is SMI_ERR_NO_INVERSE as above. */
+int smi_dev_air_prove_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *lookup, const uint32_t *d_trace_cols, uint8_t *roots,
+                             uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, int *closes);
+int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *lookup, const uint8_t *roots, const uint8_t *proof,
+                          size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

@@ -59,6 +59,11 @@ class AirPerm(C.Structure):
     _fields_ = [("width", C.c_uint32), ("reserved0", C.c_uint32), ("left_col", u32p), ("right_col", u32p)]
 
 
+class AirLookup(C.Structure):
+    """smi_air_lookup (include/stark_mi.h, "Lookup argument"); mirror.Air.flatten fills one when Air.lookup was called"""
+    _fields_ = [("width", C.c_uint32), ("mult_col", C.c_uint32), ("lookup_col", u32p), ("table_col", u32p)]
+
+
 def build(force=False):
     """Compile libstarkmi.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
@@ -205,6 +210,13 @@ def lib():
         "smi_dev_air_prove_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
                                          C.c_uint32, C.POINTER(i32)]),
         "smi_air_verify_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_lookup": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), u32p, u64p]),
+        "smi_dev_lookup_multiplicities": (i32, [vp, C.POINTER(AirLookup), vp, C.c_uint32, C.c_uint32, vp]),
+        "smi_dev_lookup_column": (i32, [vp, C.POINTER(AirLookup), vp, C.c_uint32, C.c_uint32, u64p, vp, sz, C.POINTER(i32)]),
+        "smi_dev_air_compose_lookup": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), vp, sz, vp, sz, u64p, vp, vp, sz]),
+        "smi_dev_air_prove_lookup": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
+                                           C.c_uint32, C.POINTER(i32)]),
+        "smi_air_verify_lookup": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

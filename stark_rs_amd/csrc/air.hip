@@ -23,6 +23,7 @@
 #include "hash_core.h"
 #include "internal.h"
 #include "mgpu_core.h"
+#include "lookup_core.h"
 #include "perm_core.h"
 
 template <int P>
@@ -269,7 +270,11 @@ int smi_air_plan_perm(uint64_t p, const smi_stark_cfg *cfg, const void *air, con
     g_air_err.clear();
     return perm_plan(p, cfg, (const smi_air *)air, (const smi_air_perm *)perm, degree, fri_expansion, &g_air_err);
 }
-// what perm.hip shares with the provers of this file (internal.h)
+int smi_air_plan_lookup(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *lookup, uint32_t *degree, uint64_t *fri_expansion) {
+    g_air_err.clear();
+    return lookup_plan(p, cfg, (const smi_air *)air, (const smi_air_lookup *)lookup, degree, fri_expansion, &g_air_err);
+}
+// what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }
 int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights, uint32_t *d_out,
                            size_t out_stride) {

@@ -36,6 +36,7 @@ const char *smi_status_string(int status) {
     case SMI_ERR_NOT_GEOMETRIC: return "domain is not offset*omega^k";
     case SMI_ERR_COLUMNS_NOT_BOUND: return "proof has no column openings: it does not bind the column roots";
     case SMI_ERR_GRIND_EXHAUSTED: return "proof of work: no nonce below the search cap meets the difficulty";
+    case SMI_ERR_LOOKUP_MISSING: return "lookup: a looked-up tuple is in no table row";
     case SMI_ERR_HIP: return "HIP runtime error";
     case SMI_ERR_NO_DEVICE: return "no usable HIP device";
     case SMI_ERR_OOM: return "out of memory";

@@ -14,6 +14,8 @@
 // 3.25 F_q products and a quarter of an inversion, the reload 32 bytes of traffic and one product (DESIGN.md has the figures).
 // One tile of perm_scan_kernel covers PERM_BLOCK * PERM_TILE = 2^18 rows; above that it loops.
 //
+// (perm_load4 / perm_store4, the 16-byte accesses of these kernels, are row4_dev.h's, shared with lookup.hip.)
+//
 // air_perm_compose_kernel streams: per lane four consecutive points, one 16-byte load per tuple column, two per
 // coordinate of z (this row, and B further: a second coalesced read, no halo), a 16-byte read-modify-write per coordinate of
 // the codeword.  x_i advances by a per-lane step over a grid-stride loop, so the two powers a lane computes are set-up.
@@ -25,6 +27,7 @@
 #include "internal.h"
 #include "mgpu_core.h"
 #include "perm_core.h"
+#include "row4_dev.h"
 
 namespace {
 // the workgroup scan of perm_core.h (perm_scan_step) between barriers; returns the lane's EXCLUSIVE prefix and the
@@ -42,27 +45,6 @@ __device__ __forceinline__ Fq perm_wg_scan(Fq v, uint32_t (*sc)[4][PERM_BLOCK], 
     }
     *total = perm_scan_at(sc[cur], PERM_BLOCK - 1);
     return tid ? perm_scan_at(sc[cur], tid - 1) : fq_one(F);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void perm_load4(const uint32_t *__restrict__ src, uint64_t at, uint64_t len, uint32_t v[4]) {
-    if (VEC) {
-        const uint4 t = *(const uint4 *)(src + at);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = at + q < len ? src[at + q] : 0u;
-    }
-}
-template <bool VEC>
-__device__ __forceinline__ void perm_store4(uint32_t *__restrict__ dst, uint64_t at, uint64_t len, const uint32_t v[4]) {
-    if (VEC) {
-        *(uint4 *)(dst + at) = make_uint4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            if (at + q < len) dst[at + q] = v[q];
-    }
 }
 }  // namespace
 
@@ -179,9 +161,6 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_perm_compose_kernel(PermDev PD
 }
 
 namespace {
-inline bool al16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // bytes of device scratch the column build wants: the workgroup products | the total (16) | the first zero row (8, padded)
 size_t perm_column_tmp_bytes(uint64_t n) { return ((n + PERM_TILE - 1) / PERM_TILE) * 16 + 32; }
 

@@ -33,6 +33,7 @@
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
+#include "lookup_core.h"
 #include "perm_core.h"
 #include "proof_parse.h"
 
@@ -419,6 +420,7 @@ const OpeningWords COLUMN_WORDS = {"column openings: wrong length", "column open
 const OpeningWords AIR_WORDS = {"air openings: wrong length", "air openings: malformed row", "air openings: malformed path",
                                 "air openings: authentication path does not verify", "air openings: an opened value is not canonical",
                                 "air openings: the composition of the opened rows is not the codeword value"};
+const OpeningWords LOOKUP_WORDS = {LOOKUP_SENTENCES[0], LOOKUP_SENTENCES[1], LOOKUP_SENTENCES[2], LOOKUP_SENTENCES[3], LOOKUP_SENTENCES[4], LOOKUP_SENTENCES[5]};   // lookup_core.h
 const OpeningWords PERM_WORDS = {"perm openings: wrong length", "perm openings: malformed row", "perm openings: malformed path",
                                  "perm openings: authentication path does not verify", "perm openings: an opened value is not canonical",
                                  "perm openings: the composition of the opened rows is not the codeword value"};
@@ -607,6 +609,47 @@ struct PermAux {
     }
 };
 
+// the two auxiliary quotients of the lookup argument (include/stark_mi.h, "Lookup argument") at one point, in host F_q
+// arithmetic: what smi_dev_air_compose_lookup adds to the main part of the composition
+struct LookupAux {
+    uint32_t p, g, width;
+    const smi_air_lookup *lk;
+    uint32_t gamma[4], wb[4], wt[4];
+    std::vector<std::vector<uint32_t>> apow;   // alpha^j, j < width
+    uint64_t n, tau, tau_n;
+    LookupAux(const smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air_lookup *lk_, const uint64_t ch[8], const uint64_t *w_bound, const uint64_t *w_trans)
+        : p(ctx->fs.F.p), g(ctx->fs.g), width(lk_->width), lk(lk_), apow(lk_->width, std::vector<uint32_t>(4, 0)), n(1ull << cfg->log_n),
+          tau(cfg->trace_offset), tau_n(powm(cfg->trace_offset, 1ull << cfg->log_n, ctx->fs.F.p)) {
+        uint32_t alpha[4], pw[4] = {1, 0, 0, 0};
+        perm_challenges(p, ch, alpha, gamma);
+        for (int e = 0; e < 4; e++) wb[e] = (uint32_t)(w_bound[e] % p), wt[e] = (uint32_t)(w_trans[e] % p);
+        for (uint32_t j = 0; j < width; j++) {
+            apow[j].assign(pw, pw + 4);
+            ext_mul_host(p, g, pw, alpha, pw);
+        }
+    }
+    // got += w_b s / (x - tau) + w_t ((s' - s) f_L f_T - f_T + M f_L) / (x^n - tau^n) over the row cur and the s coordinates sc, sn
+    void add(uint64_t x, const uint64_t *cur, const uint64_t *sc, const uint64_t *sn, uint32_t got[4]) const {
+        uint32_t fl[4], ft[4], ds[4], lt[4], a[4], bq[4], tq[4], u[4], v[4];
+        for (int e = 0; e < 4; e++) fl[e] = ft[e] = gamma[e], ds[e] = (uint32_t)((sn[e] + p - sc[e]) % p);
+        for (uint32_t j = 0; j < width; j++)
+            for (int e = 0; e < 4; e++) {
+                fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], cur[lk->lookup_col[j]], p)) % p);
+                ft[e] = (uint32_t)((ft[e] + mulm(apow[j][e], cur[lk->table_col[j]], p)) % p);
+            }
+        ext_mul_host(p, g, fl, ft, lt);
+        ext_mul_host(p, g, ds, lt, a);
+        const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p), M = cur[lk->mult_col];
+        for (int e = 0; e < 4; e++) {
+            tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - ft[e] + mulm(M, fl[e], p)) % p, izt, p);
+            bq[e] = (uint32_t)mulm(sc[e], ixt, p);
+        }
+        ext_mul_host(p, g, bq, wb, u);
+        ext_mul_host(p, g, tq, wt, v);
+        for (int e = 0; e < 4; e++) got[e] = (uint32_t)(((uint64_t)got[e] + u[e] + v[e]) % p);
+    }
+};
+
 // What the AIR verifiers differ in (include/stark_mi.h: "AIR", "AIR over one row-committed tree", "Extension FRI",
 // "Grinding", "Permutation argument").
 //   by_rows : one tree over the rows (one path per position, leaves from the bytes) instead of W column trees
@@ -616,10 +659,13 @@ struct PermAux {
 //   perm    : the permutation argument: a second root and a second section (the rows of z, four values wide), the two
 //             auxiliary quotients added to the composition; the tags of both sections are checked record by record before
 //             either is authenticated, and every opened value is checked canonical before the composition
+//   lookup  : the lookup argument: the same second root and second section (the rows of s) with its own two quotients and
+//             its own sentences; at most one of perm and lookup is set
 struct AirVariant {
     bool by_rows, over_ext;
     int grind;
     const smi_air_perm *perm;
+    const smi_air_lookup *lookup;
 };
 // One verifier for them all: the weights and FRI's seed from the variant's transcript, Fri::verify at expansion factor E,
 // then the openings -- length, records, every path against its root, and the composition codeword recomputed at x_a and
@@ -628,15 +674,18 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                            int *accept, const AirVariant &var) {
     std::string why;
     uint64_t E = 0;
-    const int vrc = var.perm ? perm_plan(ctx->fs.F.p, cfg, air, var.perm, nullptr, &E, &why) : air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
+    const bool has_aux = var.perm || var.lookup;   // an auxiliary column: a second root, a second section, two more quotients
+    const int vrc = var.perm     ? perm_plan(ctx->fs.F.p, cfg, air, var.perm, nullptr, &E, &why)
+                    : var.lookup ? lookup_plan(ctx->fs.F.p, cfg, air, var.lookup, nullptr, &E, &why)
+                                 : air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
     if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
     const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
     SMI_TRY(domain_check(ctx, logN));
     const uint64_t p = ctx->fs.F.p, N = 1ull << logN, B = 1ull << cfg->log_blowup, t = cfg->num_colinearity_tests;
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     Transcript tr;
-    std::vector<uint64_t> ch, weights;   // ch: alpha and gamma of the permutation argument
-    if (var.perm) {
+    std::vector<uint64_t> ch, weights;   // ch: alpha and gamma of the auxiliary column
+    if (has_aux) {
         transcript_perm_challenges(tr, roots, &ch);
         transcript_perm_weights(tr, roots + 32, W, K, &weights);
     } else if (var.over_ext) {
@@ -653,22 +702,23 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     if (var.over_ext) SMI_TRY(fri_verify_ext_objs(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &ab, &used, var.grind));
     else SMI_TRY(fri_verify_objs(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &ab, &used));
     *accept = 0;
-    // ---- the opening sections: rows of W values under root_1 (or the column roots); with perm, rows of 4 values under root_2
-    const OpeningWords &say = var.perm ? PERM_WORDS : AIR_WORDS;
-    const size_t R = (K || var.perm) ? 4 : 2, m = R * t, prec = 9 + 32 * (size_t)logN, n_sec = var.perm ? 2 : 1;
+    // ---- the opening sections: rows of W values under root_1 (or the column roots); with an auxiliary column, rows of 4
+    // values under root_2
+    const OpeningWords &say = var.perm ? PERM_WORDS : var.lookup ? LOOKUP_WORDS : AIR_WORDS;
+    const size_t R = (K || has_aux) ? 4 : 2, m = R * t, prec = 9 + 32 * (size_t)logN, n_sec = has_aux ? 2 : 1;
     const uint32_t widths[2] = {W, 4}, NE = var.over_ext ? 4 : 1;
-    const size_t sec_len[2] = {m * (9 + 8 * (size_t)W) + (var.by_rows ? 1 : W) * m * prec, var.perm ? m * (9 + 8 * (size_t)4) + m * prec : 0};
+    const size_t sec_len[2] = {m * (9 + 8 * (size_t)W) + (var.by_rows ? 1 : W) * m * prec, has_aux ? m * (9 + 8 * (size_t)4) + m * prec : 0};
     if (proof_len - end != sec_len[0] + sec_len[1]) return reject(ctx, accept, say.length);
     const uint8_t *sec[2] = {proof + end, proof + end + sec_len[0]};
     const std::vector<uint64_t> pos = opened_positions(top, N, B, R);
     std::vector<uint64_t> rows[2];
-    const RecordOrder order = var.perm ? RECORD_BY_RECORD : var.by_rows ? ROWS_THEN_PATHS : ROWS_ONLY;
+    const RecordOrder order = has_aux ? RECORD_BY_RECORD : var.by_rows ? ROWS_THEN_PATHS : ROWS_ONLY;
     for (size_t v = 0; v < n_sec; v++) SMI_TRY(parse_section(ctx, accept, say, sec[v], m, widths[v], logN, order, &rows[v]));
     for (size_t v = 0; v < n_sec; v++) {
         if (var.by_rows) SMI_TRY(auth_section(ctx, accept, say, sec[v], m, widths[v], logN, pos, roots + 32 * v));
         else SMI_TRY(auth_column_trees(ctx, accept, say, sec[v] + m * (9 + 8 * (size_t)W), rows[v], m, R, W, logN, pos, roots));
     }
-    if (var.perm)
+    if (has_aux)
         for (size_t v = 0; v < n_sec; v++)
             for (uint64_t x : rows[v])
                 if (x >= p) return reject(ctx, accept, say.canonical);
@@ -690,11 +740,13 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     std::vector<uint32_t> w_m(var.over_ext ? 4 * AIR_MAX_WEIGHTS : W + K, 0);
     for (uint32_t i = 0; i < NE * (W + K); i++) w_m[var.over_ext ? (i & 3) * AIR_MAX_WEIGHTS + (i >> 2) : i] = to_mont_u64(weights[i], F);
     std::optional<PermAux> aux;
+    std::optional<LookupAux> laux;
     if (var.perm) aux.emplace(ctx, cfg, var.perm, ch.data(), &weights[4 * (W + K)], &weights[4 * (W + K + 1)]);
+    if (var.lookup) laux.emplace(ctx, cfg, var.lookup, ch.data(), &weights[4 * (W + K)], &weights[4 * (W + K + 1)]);
     for (uint64_t s = 0; s < t; s++)
         for (size_t k = 0; k < 2; k++) {
             const uint64_t i = pos[R * s + k];
-            for (size_t r = k; r < R && !var.perm; r += 2)   // this side's rows, in front of this side's composition
+            for (size_t r = k; r < R && !has_aux; r += 2)   // this side's rows, in front of this side's composition
                 for (uint32_t c = 0; c < W; c++)
                     if (rows[0][(R * s + r) * W + c] >= p) return reject(ctx, accept, say.canonical);
             const uint64_t *cur = &rows[0][(R * s + k) * W], *nxt = R == 4 ? &rows[0][(R * s + k + 2) * W] : nullptr;
@@ -710,6 +762,7 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
             if (var.over_ext) air_compose_points_ext<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
             else air_compose_points<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
             if (var.perm) aux->add(x, cur, &rows[1][(R * s + k) * 4], &rows[1][(R * s + k + 2) * 4], got);
+            if (var.lookup) laux->add(x, cur, &rows[1][(R * s + k) * 4], &rows[1][(R * s + k + 2) * 4], got);
             for (uint32_t e = 0; e < NE; e++)
                 if (got[e] != ab[(2 * s + k) * NE + e] % p) return reject(ctx, accept, say.composition);
         }
@@ -723,7 +776,7 @@ int smi_air_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, cons
     DeviceGuard dg__(ctx);
     *accept = 0;
     if (cfg->row_leaves) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_verify: column trees only (row_leaves must be 0; smi_air_verify_rows checks a proof over one row tree)");
-    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, column_roots, proof, proof_len, accept, AirVariant{false, false, SMI_GRIND_NONE, nullptr}));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, column_roots, proof, proof_len, accept, AirVariant{false, false, SMI_GRIND_NONE, nullptr, nullptr}));
 }
 
 int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
@@ -731,7 +784,7 @@ int smi_air_verify_rows(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     if (!ctx || !cfg || !air || !row_root || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     *accept = 0;
-    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, false, SMI_GRIND_NONE, nullptr}));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, false, SMI_GRIND_NONE, nullptr, nullptr}));
 }
 
 int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
@@ -740,7 +793,7 @@ int smi_air_verify_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, 
     DeviceGuard dg__(ctx);
     *accept = 0;
     SMI_TRY(ext_field_check(ctx));
-    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, true, SMI_GRIND_NONE, nullptr}));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, true, SMI_GRIND_NONE, nullptr, nullptr}));
 }
 
 int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
@@ -750,7 +803,7 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     *accept = 0;
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(ext_field_check(ctx));
-    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, true, (int)grind_bits, nullptr}));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, true, (int)grind_bits, nullptr, nullptr}));
 }
 
 // Verifier of smi_dev_air_prove_perm (include/stark_mi.h, "Permutation argument"): the extension verifier with proof of
@@ -763,5 +816,18 @@ int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(ext_field_check(ctx));
     return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
-                                  AirVariant{true, true, (int)grind_bits, (const smi_air_perm *)perm}));
+                                  AirVariant{true, true, (int)grind_bits, (const smi_air_perm *)perm, nullptr}));
+}
+
+// Verifier of smi_dev_air_prove_lookup (include/stark_mi.h, "Lookup argument"): smi_air_verify_perm's checks with the lookup
+// argument's two auxiliary quotients (AirVariant::lookup).
+int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *lookup, const uint8_t *roots, const uint8_t *proof,
+                          size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !lookup || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
+                                  AirVariant{true, true, (int)grind_bits, nullptr, (const smi_air_lookup *)lookup}));
 }

@@ -502,6 +502,8 @@ class Engine:
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
         if self._perm(a) is not None:   # smi_air_plan_perm: d = max(d_air, 2)
             return air_plan_perm(self.p, a, a.perm, cfg)
+        if self._lookup(a) is not None:   # smi_air_plan_lookup: d = max(d_air, 3)
+            return air_plan_lookup(self.p, a, a.lookup, cfg)
         return air_plan(self.p, a, cfg)
 
     @staticmethod
@@ -509,8 +511,13 @@ class Engine:
         """the _lib.AirPerm a flattened AIR carries (mirror.Air.permutation), or None"""
         return getattr(air, "perm", None)
 
+    @staticmethod
+    def _lookup(air):
+        """the _lib.AirLookup a flattened AIR carries (mirror.Air.lookup), or None"""
+        return getattr(air, "lookup", None)
+
     def _ck_perm(self, st):
-        if st == -1:   # SMI_ERR_NO_INVERSE: the sentence names the row
+        if st in (-1, -56):   # SMI_ERR_NO_INVERSE, SMI_ERR_LOOKUP_MISSING: the sentence names the row
             raise StarkMiError(st, f"{_lib.status_string(st)}: {self.L.smi_last_error(self.h).decode()}")
         self._ck(st)
 
@@ -541,6 +548,42 @@ class Engine:
                                                  vp(d_z_lde), N if z_stride is None else z_stride, ch, vp(d_weights), vp(d_out),
                                                  N if out_stride is None else out_stride))
 
+    def _lookup_of(self, air, who):
+        a = self._air(air)
+        if self._lookup(a) is None:
+            raise ValueError(f"{who}: the AIR has no lookup (mirror.Air.lookup)")
+        return a
+
+    def dev_lookup_multiplicities(self, air, d_trace_cols, n_cols, log_n, d_mult):
+        """smi_dev_lookup_multiplicities: the multiplicities of air's lookup over the device trace into d_mult (n u32, zeroed by
+        the call; pass the address of the trace's mult_col to fill the trace in place).  StarkMiError -56 naming the smallest
+        row whose tuple is in no table row."""
+        a = self._lookup_of(air, "dev_lookup_multiplicities")
+        self._ck_perm(self.L.smi_dev_lookup_multiplicities(self.h, C.byref(a.lookup), vp(d_trace_cols), n_cols, log_n, vp(d_mult)))
+
+    def dev_lookup_column(self, air, d_trace_cols, n_cols, log_n, challenges, d_s, s_stride=None):
+        """smi_dev_lookup_column: the column s of air's lookup under the 8 unreduced challenges (alpha, gamma) into four
+        coordinate columns s_stride (default n) apart -> closes (bool).  StarkMiError "no inverse: ... row r" when some f_L(r)
+        or f_T(r) is zero."""
+        a = self._lookup_of(air, "dev_lookup_column")
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        closes = C.c_int()
+        self._ck_perm(self.L.smi_dev_lookup_column(self.h, C.byref(a.lookup), vp(d_trace_cols), n_cols, log_n, ch, vp(d_s),
+                                                   (1 << log_n) if s_stride is None else s_stride, C.byref(closes)))
+        return bool(closes.value)
+
+    def dev_air_compose_lookup(self, air, d_lde, d_s_lde, n_cols, log_n, log_blowup, challenges, d_weights, d_out, stride=None, s_stride=None,
+                               out_stride=None, trace_offset=1, lde_offset=None):
+        """smi_dev_air_compose_lookup: smi_dev_air_compose_ext under the first 4 (W + K) of the 4 (W + K + 2) device weights plus
+        the two auxiliary quotients of the extended column d_s_lde"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        a = self._lookup_of(air, "dev_air_compose_lookup")
+        N = 1 << (log_n + log_blowup)
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        self._ck(self.L.smi_dev_air_compose_lookup(self.h, C.byref(cfg), C.byref(a), C.byref(a.lookup), vp(d_lde), N if stride is None else stride,
+                                                   vp(d_s_lde), N if s_stride is None else s_stride, ch, vp(d_weights), vp(d_out),
+                                                   N if out_stride is None else out_stride))
+
     def dev_air_compose(self, air, d_lde, n_cols, log_n, log_blowup, d_weights, d_out, stride=None, trace_offset=1, lde_offset=None):
         """the composition codeword of n_cols extended device columns under n_cols + K unreduced device weights"""
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
@@ -569,7 +612,7 @@ class Engine:
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None):
+                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -578,8 +621,38 @@ class Engine:
         grind_bits (needs ext; None: no grinding): smi_dev_air_prove_ext_pow -- proof-of-work bits before the query indices.
         An AIR with a permutation (mirror.Air.permutation) takes smi_dev_air_prove_perm: row_leaves=True and ext=True are
         required (ValueError otherwise), grind_bits None counts as 0, column_roots is (2, 32) -- root_1, root_2 --, stage_ms has
-        a sixth stage "perm", the result has "closes", and check=True raises when the product does not close."""
+        a sixth stage "perm", the result has "closes", and check=True raises when the product does not close.
+        An AIR with a lookup (mirror.Air.lookup) takes smi_dev_air_prove_lookup in the same way (the sixth stage is "lookup",
+        check=True raises when the sum does not close); fill_multiplicities=True first runs dev_lookup_multiplicities into the
+        trace's mult_col, which is otherwise taken as filled."""
         a = self._air(air)
+        if fill_multiplicities and self._lookup(a) is None:
+            raise ValueError("dev_air_prove(fill_multiplicities=True): the AIR has no lookup (mirror.Air.lookup)")
+        if self._lookup(a) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("dev_air_prove: an AIR with a lookup needs row_leaves=True, ext=True")
+            if fill_multiplicities:
+                self.dev_lookup_multiplicities(a, d_trace_cols, n_cols, log_n, vp(d_trace_cols).value + 4 * (a.lookup.mult_col << log_n))
+            if check:
+                ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+                if not ok:
+                    raise StarkMiError(-50, why)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.zeros((2, 32), dtype=np.uint8)
+            proof, plen, closes = vp(), C.c_size_t(), C.c_int()
+            top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
+            stage = (C.c_double * 6)()
+            self._ck_perm(self.L.smi_dev_air_prove_lookup(self.h, C.byref(cfg), C.byref(a), C.byref(a.lookup), vp(d_trace_cols), roots.ctypes.data,
+                                                          C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                          0 if grind_bits is None else grind_bits, C.byref(closes)))
+            b = C.string_at(proof, plen.value)
+            self.L.smi_free(proof)
+            if check and not closes.value:
+                raise StarkMiError(-50, "air_prove_lookup: the lookup sum does not close (a missing lookup or a wrong multiplicity)")
+            out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]], "closes": bool(closes.value)}
+            if timed:
+                out["stage_ms"] = dict(zip(("lde", "commit", "lookup", "compose", "fri", "open"), [float(x) for x in stage]))
+            return out
         if self._perm(a) is not None:
             if not (row_leaves and ext):
                 raise ValueError("dev_air_prove: an AIR with a permutation needs row_leaves=True, ext=True")
@@ -636,7 +709,20 @@ class Engine:
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
-        column_roots is root_1 then root_2, grind_bits None counts as 0."""
+        column_roots is root_1 then root_2, grind_bits None counts as 0.  An AIR with a lookup takes smi_air_verify_lookup in
+        the same way."""
+        if self._lookup(self._air(air)) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("air_verify: an AIR with a lookup needs row_leaves=True, ext=True")
+            a = self._air(air)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 64:
+                raise StarkMiError(-50, "air_verify: an AIR with a lookup takes two 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_lookup(self.h, C.byref(cfg), C.byref(a), C.byref(a.lookup), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                  0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if self._perm(self._air(air)) is not None:
             if not (row_leaves and ext):
                 raise ValueError("air_verify: an AIR with a permutation needs row_leaves=True, ext=True")
@@ -755,6 +841,16 @@ def air_plan_perm(p, air, perm, cfg):
     d, e = C.c_uint32(), C.c_uint64()
     L = _lib.lib()
     st = L.smi_air_plan_perm(p, C.byref(cfg), C.byref(air), C.byref(perm), C.byref(d), C.byref(e))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, e.value
+
+
+def air_plan_lookup(p, air, lookup, cfg):
+    """smi_air_plan_lookup (host only) -> (d = max(d_air, 3), E).  air: a flattened _lib.Air; lookup: a _lib.AirLookup"""
+    d, e = C.c_uint32(), C.c_uint64()
+    L = _lib.lib()
+    st = L.smi_air_plan_lookup(p, C.byref(cfg), C.byref(air), C.byref(lookup), C.byref(d), C.byref(e))
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value

@@ -805,7 +805,14 @@ class Air:
 
         air.permutation([0, 1], [2, 3])                         # {(c0[r], c1[r])} = {(c2[r], c3[r])}
 
-    With it set, Engine.air_plan / dev_air_prove / air_verify take the smi_*_perm entry points."""
+    With it set, Engine.air_plan / dev_air_prove / air_verify take the smi_*_perm entry points.
+
+    A lookup argument (include/stark_mi.h, "Lookup argument"; one per AIR, and not together with a permutation) claims that
+    every row's tuple of some columns occurs among the rows' tuples of other columns, with a trace column of multiplicities:
+
+        air.lookup([0], [1], 2)                                 # every c0[r] is some c1[t]; c2[t] counts them
+
+    With it set the same three take the smi_*_lookup entry points."""
 
     def __init__(self, n_cols):
         self.n_cols = n_cols
@@ -813,6 +820,7 @@ class Air:
         self.boundaries = []    # [(col, row, value), ...]
         self.periodics = []     # [[value, ...], ...]: a power-of-two number of integers each
         self.perm = None        # ([left columns], [right columns]) once permutation() was called
+        self.lookup_arg = None  # ([lookup columns], [table columns], multiplicity column) once lookup() was called
 
     @property
     def constraints(self):
@@ -842,7 +850,23 @@ class Air:
             raise ValueError("a permutation relates tuples of one width")
         if self.perm is not None:
             raise ValueError("one permutation per AIR")
+        if self.lookup_arg is not None:
+            raise ValueError("an AIR takes a permutation or a lookup, not both")
         self.perm = (left, right)
+        return self
+
+    def lookup(self, cols, table_cols, mult_col):
+        """every tuple (T[cols[0]][r], ..) occurs among the tuples (T[table_cols[0]][t], ..); column mult_col holds the
+        multiplicities (a duplicated table tuple is credited to its lowest row); 1 .. 8 columns a side, the two lists may
+        overlap, mult_col is none of them"""
+        cols, table_cols = [int(c) for c in cols], [int(c) for c in table_cols]
+        if len(cols) != len(table_cols):
+            raise ValueError("a lookup relates tuples of one width")
+        if self.lookup_arg is not None:
+            raise ValueError("one lookup per AIR")
+        if self.perm is not None:
+            raise ValueError("an AIR takes a permutation or a lookup, not both")
+        self.lookup_arg = (cols, table_cols, int(mult_col))
         return self
 
     def closes(self, p, g, cols, alpha, gamma):
@@ -913,6 +937,13 @@ class Air:
                        ptr(arrs[2], _lib.u32p), ptr(arrs[3], _lib.u32p), ptr(arrs[4], _lib.u32p), ptr(arrs[5], _lib.u32p),
                        ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p), len(self.periodics), 0, ptr(arrs[8], _lib.u32p), ptr(arrs[9], _lib.u64p))
         out._keep = arrs
+        if self.perm is not None and self.lookup_arg is not None:
+            raise ValueError("an AIR takes a permutation or a lookup, not both")
+        out.lookup = None
+        if self.lookup_arg is not None:
+            la, ta = np.array(self.lookup_arg[0], dtype=np.uint32), np.array(self.lookup_arg[1], dtype=np.uint32)
+            out.lookup = _lib.AirLookup(len(la), self.lookup_arg[2] % (1 << 32), ptr(la, _lib.u32p), ptr(ta, _lib.u32p))
+            out.lookup._keep = (la, ta)
         out.perm = None
         if self.perm is not None:
             la, ra = np.array(self.perm[0], dtype=np.uint32), np.array(self.perm[1], dtype=np.uint32)

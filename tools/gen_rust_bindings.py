@@ -159,6 +159,19 @@ def generate():
         for nm in names.split(","):
             lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
     lines.append("}")
+    lines.append("/// smi_air_lookup: one lookup argument (host pointers; the entry points take it as `*const c_void`)")
+    lines.append("#[repr(C)] #[derive(Clone, Copy)]")
+    lines.append("pub struct smi_air_lookup {")
+    lookup = re.search(r"typedef struct smi_air_lookup\s*\{(.*?)\}\s*smi_air_lookup\s*;", text, flags=re.S).group(1)
+    for decl in [" ".join(d.split()) for d in lookup.split(";") if d.strip()]:
+        pm = re.fullmatch(r"const (\w+) \*(\w+)", decl)
+        if pm:
+            lines.append(f"    pub {pm.group(2)}: *const {SCALAR[pm.group(1)]},")
+            continue
+        ty, names = decl.split(" ", 1)
+        for nm in names.split(","):
+            lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
+    lines.append("}")
     for m in re.finditer(r"#define (SMI_\w+_MAX_\w+) (\d+)", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     lines.append("")

@@ -136,6 +136,23 @@ pub struct smi_air_lookup {
     pub lookup_col: *const u32,
     pub table_col: *const u32,
 }
+/// smi_air_arg: one argument of an argument list (host pointers; the entry points take the list as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_arg {
+    pub kind: u32,
+    pub width: u32,
+    pub mult_col: u32,
+    pub reserved0: u32,
+    pub a_col: *const u32,
+    pub b_col: *const u32,
+}
+/// smi_air_args: an argument list (host pointers; the entry points take the list as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_args {
+    pub count: u32,
+    pub reserved0: u32,
+    pub arg: *const smi_air_arg,
+}
 pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
 pub const SMI_AIR_MAX_TERMS: u32 = 1024;
 pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
@@ -145,6 +162,9 @@ pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
 pub const SMI_GRIND_MAX_BITS: u32 = 32;
 pub const SMI_PERM_MAX_WIDTH: u32 = 8;
 pub const SMI_LOOKUP_MAX_WIDTH: u32 = 8;
+pub const SMI_ARGS_MAX: u32 = 8;
+pub const SMI_ARG_PERM: u32 = 0;
+pub const SMI_ARG_LOOKUP: u32 = 1;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -256,6 +276,11 @@ extern "C" {
     pub fn smi_dev_air_compose_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, d_lde: *const u32, stride: usize, d_s_lde: *const u32, s_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
     pub fn smi_dev_air_prove_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut c_int) -> c_int;
     pub fn smi_air_verify_lookup(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, lookup: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_args(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
+    pub fn smi_dev_args_columns(ctx: *mut smi_ctx, args: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: *const u64, d_c: *mut u32, c_stride: usize, closes: *mut u32) -> c_int;
+    pub fn smi_dev_air_compose_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_prove_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
+    pub fn smi_air_verify_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -975,6 +1000,87 @@ impl Air {
         ctx.check(self.with_raw(|a| lookup.with_raw(|lk| unsafe {
             smi_dev_air_compose_lookup(ctx.raw, cfg, a, lk, d_lde, stride, d_s_lde, s_stride, challenges.as_ptr(), d_weights, d_out, out_stride)
         })));
+    }
+    /// `smi_air_plan_args` (host only): `(degree, FRI expansion factor)` of this AIR with the argument list `args`.
+    pub fn plan_args(&self, p: u64, cfg: &smi_stark_cfg, args: &Arguments) -> (u32, u64) {
+        let (mut d, mut e) = (0u32, 0u64);
+        let st = self.with_raw(|a| args.with_raw(|al| unsafe { smi_air_plan_args(p, cfg, a, al, &mut d, &mut e) }));
+        if st != SMI_OK {
+            panic!("{}: {}", status_text(st), unsafe { CStr::from_ptr(smi_air_last_error()) }.to_string_lossy());
+        }
+        (d, e)
+    }
+    /// `smi_dev_air_prove_args` -> (root_1 then root_2, proof bytes, closes): one AIR proof with every argument of `args`
+    /// over one second tree; bit a of `closes` is set iff argument a closes.  A column that does not close is proved all the
+    /// same and the verifier rejects; a zero denominator panics with "no inverse", the argument and the row.
+    pub fn prove_args(&self, ctx: &Context, cfg: &smi_stark_cfg, args: &Arguments, d_trace_cols: *const u32, grind_bits: u32) -> ([u8; 64], Vec<u8>, u32) {
+        let mut roots = [0u8; 64];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        let mut closes = 0u32;
+        ctx.check(self.with_raw(|a| args.with_raw(|al| unsafe {
+            smi_dev_air_prove_args(ctx.raw, cfg, a, al, d_trace_cols, roots.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut(), grind_bits, &mut closes)
+        })));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (roots, bytes, closes)
+    }
+    /// `smi_air_verify_args` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify_args(&self, ctx: &Context, cfg: &smi_stark_cfg, args: &Arguments, roots: &[u8; 64], proof: &[u8], grind_bits: u32) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(self.with_raw(|a| args.with_raw(|al| unsafe {
+            smi_air_verify_args(ctx.raw, cfg, a, al, roots.as_ptr(), proof.as_ptr(), proof.len(), &mut accept, grind_bits)
+        })));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
+    }
+    /// `smi_dev_air_compose_args`: the composition under the first 4 (W + K) of the 4 (W + K + 2 A) device weights plus the
+    /// 2 A auxiliary quotients of the 4 A extended coordinate columns `d_c_lde`, into four coordinate columns.
+    pub fn compose_args(&self, ctx: &Context, cfg: &smi_stark_cfg, args: &Arguments, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize,
+                        challenges: &[u64; 8], d_weights: *const u64, d_out: *mut u32, out_stride: usize) {
+        ctx.check(self.with_raw(|a| args.with_raw(|al| unsafe {
+            smi_dev_air_compose_args(ctx.raw, cfg, a, al, d_lde, stride, d_c_lde, c_stride, challenges.as_ptr(), d_weights, d_out, out_stride)
+        })));
+    }
+}
+
+/// An argument list (include/stark_mi.h, "Argument list"): 1 ..= `SMI_ARGS_MAX` permutations and lookups, in any mix and
+/// order, proved over one committed trace with one second tree.
+pub struct Arguments {
+    items: Vec<(u32, Vec<u32>, Vec<u32>, u32)>,   // kind, a_col, b_col, mult_col
+}
+
+impl Arguments {
+    pub fn new() -> Arguments {
+        Arguments { items: Vec::new() }
+    }
+    pub fn permutation(mut self, left: &[u32], right: &[u32]) -> Arguments {
+        assert!(left.len() == right.len() && !left.is_empty() && left.len() <= SMI_PERM_MAX_WIDTH as usize, "1 ..= SMI_PERM_MAX_WIDTH columns a side");
+        assert!(self.items.len() < SMI_ARGS_MAX as usize, "at most SMI_ARGS_MAX arguments");
+        self.items.push((SMI_ARG_PERM, left.to_vec(), right.to_vec(), 0));
+        self
+    }
+    pub fn lookup(mut self, lookup: &[u32], table: &[u32], mult_col: u32) -> Arguments {
+        assert!(lookup.len() == table.len() && !lookup.is_empty() && lookup.len() <= SMI_LOOKUP_MAX_WIDTH as usize, "1 ..= SMI_LOOKUP_MAX_WIDTH columns a side");
+        assert!(self.items.len() < SMI_ARGS_MAX as usize, "at most SMI_ARGS_MAX arguments");
+        self.items.push((SMI_ARG_LOOKUP, lookup.to_vec(), table.to_vec(), mult_col));
+        self
+    }
+    fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        let raw: Vec<smi_air_arg> = self.items.iter().map(|(kind, a, b, m)| smi_air_arg { kind: *kind, width: a.len() as u32, mult_col: *m, reserved0: 0, a_col: a.as_ptr(), b_col: b.as_ptr() }).collect();
+        let list = smi_air_args { count: raw.len() as u32, reserved0: 0, arg: raw.as_ptr() };
+        f(&list as *const smi_air_args as *const c_void)
+    }
+    /// `smi_dev_args_columns`: the A columns of the device trace under the 8 unreduced challenges into 4 A coordinate
+    /// columns `c_stride` apart -> the mask of the arguments that close.  Panics with "no inverse" when a denominator is zero.
+    pub fn columns(&self, ctx: &Context, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: &[u64; 8], d_c: *mut u32, c_stride: usize) -> u32 {
+        let mut closes = 0u32;
+        ctx.check(self.with_raw(|al| unsafe {
+            smi_dev_args_columns(ctx.raw, al, d_trace_cols, n_cols, log_n, challenges.as_ptr(), d_c, c_stride, &mut closes)
+        }));
+        closes
     }
 }
 

@@ -718,7 +718,8 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
  *   column index < n_cols; log_n >= 1; everything smi_air_plan refuses.
  * Left out: more than one permutation per proof; periodic or next-row tuple members; a permutation together with a
  *   lookup ("Lookup argument" below); a column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
- *   as a second streaming kernel over the four coordinate columns). */
+ *   as a second streaming kernel over the four coordinate columns).  Several arguments, and permutations together with
+ *   lookups, are what "Argument list" below adds; these entry points stay at one. */
 #define SMI_PERM_MAX_WIDTH 8
 typedef struct smi_air_perm {
     uint32_t width, reserved0;      /* m, 1 .. SMI_PERM_MAX_WIDTH; explicit padding, ignored */
@@ -799,7 +800,8 @@ int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   column index < n_cols; mult_col none of the tuple columns; log_n >= 1; everything smi_air_plan refuses.
  * Left out: several lookups, or several looked-up tuples sharing one table; selectors; periodic or next-row tuple
  *   members; a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
- *   column-tree or smi_mgpu_* twin. */
+ *   column-tree or smi_mgpu_* twin.  Several lookups, each with a multiplicity column of its own, and lookups together
+ *   with permutations are what "Argument list" below adds; these entry points stay at one. */
 #define SMI_LOOKUP_MAX_WIDTH 8
 typedef struct smi_air_lookup {
     uint32_t width, mult_col;       /* m, 1 .. SMI_LOOKUP_MAX_WIDTH; the multiplicity column, < n_cols */
@@ -837,6 +839,84 @@ int smi_dev_air_prove_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void 
                              uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, int *closes);
 int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *lookup, const uint8_t *roots, const uint8_t *proof,
                           size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Argument list: several permutation and lookup arguments in one proof ----------------------
+ * The two sections above put ONE challenge-dependent F_q column in the second row tree.  A real statement needs several --
+ * a memory-consistency permutation, an opcode-table lookup and a range check or two over the same trace -- and separate
+ * proofs would repeat the trace's extension, its tree and FRI, and would not bind the arguments to one committed trace.
+ * This variant takes a list of A arguments, 1 <= A <= SMI_ARGS_MAX, each a permutation or a lookup, in any mix and any
+ * order.  The entry points above are unchanged, byte for byte.
+ *
+ * Statement.  Argument a is the statement of "Permutation argument" (kind SMI_ARG_PERM: a_col = left_col, b_col =
+ *   right_col) or of "Lookup argument" (kind SMI_ARG_LOOKUP: a_col = lookup_col, b_col = table_col, and its own mult_col) as
+ *   written there, with its own column lists.  Several lookups that share one multiplicity column are left out.
+ * Challenges.  All arguments share one alpha and one gamma.  No further separation is needed: every argument owns a column
+ *   that closes on its own, and each column's two quotients enter the composition under weights of their own.
+ * The columns.  Argument a has the F_q column c_a -- z for a permutation, s for a lookup --, with its section's recurrence
+ *   unchanged.  The A columns are stored as 4 A coordinate columns; argument a occupies the columns 4 a .. 4 a + 3.
+ * Degree.  d = max(d_air, 2 if any argument is a permutation, 3 if any is a lookup); D and E follow as in smi_air_plan, so a
+ *   list with a lookup needs log_blowup >= 3.
+ * Protocol.  The ten steps of the permutation argument with these differences:
+ *   4-6. All A columns on the device from the unextended trace (smi_dev_args_columns), ONE smi_dev_lde over the 4 A
+ *      coordinate columns, ONE tree over their rows (n_cols = 4 A): root_2, absorbed.
+ *   7. 4 (W + K + 2 A) weight challenges under the counters 8 + i; weight W + K + 2 a is the boundary quotient of argument
+ *      a, weight W + K + 2 a + 1 its wrapping transition quotient.  The transcript is 32 + 64 + 32 + 32 (W + K + 2 A) bytes.
+ *   8. The codeword is smi_dev_air_compose_ext under the weights 0 .. W + K - 1 plus the 2 A auxiliary quotients, each
+ *      exactly as its own section defines it.
+ *  10. Openings: two sections with R = 4, tree 1 with rows of W values, tree 2 with rows of 4 A values: the second section is
+ *      t 4 (9 + 32 A) + t 4 (9 + 32 log2 N) bytes.
+ *   With A = 1 every byte coincides with the proof of smi_dev_air_prove_perm or smi_dev_air_prove_lookup.
+ * Verifier (host).  The order of checks of smi_air_verify_perm, its sentences starting "argument openings:".  A proof
+ *   checked under the list in another order, under a changed argument or under fewer arguments is rejected.
+ * The prover does not refuse a column that does not close: bit a of *closes is set iff argument a closes, and the verifier
+ *   rejects a proof with a column that does not.
+ * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): count in 1 .. SMI_ARGS_MAX; kind 0 or 1;
+ *   every argument by its own section's limits, the reason naming the argument's index; everything smi_air_plan refuses.
+ * Left out: selectors; periodic or next-row tuple members; several lookups sharing one multiplicity column; the auxiliary
+ *   quotients fused into the main composition launch; a column-tree or smi_mgpu_* twin; a wave-level scan. */
+#define SMI_ARGS_MAX 8
+#define SMI_ARG_PERM 0
+#define SMI_ARG_LOOKUP 1
+typedef struct smi_air_arg {
+    uint32_t kind;            /* SMI_ARG_PERM = 0, SMI_ARG_LOOKUP = 1 */
+    uint32_t width;           /* m, 1 .. 8                             */
+    uint32_t mult_col;        /* ignored for a permutation             */
+    uint32_t reserved0;       /* explicit padding, ignored             */
+    const uint32_t *a_col;    /* left / lookup columns                 */
+    const uint32_t *b_col;    /* right / table columns                 */
+} smi_air_arg;
+typedef struct smi_air_args {
+    uint32_t count;           /* A, 1 .. SMI_ARGS_MAX                  */
+    uint32_t reserved0;
+    const smi_air_arg *arg;
+} smi_air_args;
+/* Host only (like smi_air_plan, which it runs first): validates the list against cfg and returns d and E.  `args` is a
+ * pointer to an smi_air_args, passed as the AIR is. */
+int smi_air_plan_args(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *args, uint32_t *degree, uint64_t *fri_expansion);
+/* The A columns of the trace under challenges[0 .. 7] (host, unreduced): d_c gets 4 A coordinate columns of n residues,
+ * c_stride >= n apart.  Exactly three launches whatever A is: the block launch with the argument as the second grid
+ * dimension, the scan launch with one workgroup per argument, the propagation; no wait of one workgroup on another.
+ * 16-byte accesses when d_trace_cols and d_c are 16-byte aligned, n >= 4 and c_stride is a multiple of 4; 4-byte accesses
+ * otherwise, same values.  *closes (optional): bit a is set iff argument a closes.  A zero denominator is
+ * SMI_ERR_NO_INVERSE; smi_last_error names the smallest key 16 row + 2 a + side (side 0: f_L, side 1: f_R or f_T) by its
+ * row, argument and side, and the context stays usable.  Synchronises.  smi_dev_lookup_multiplicities stays the helper for
+ * the multiplicities: a caller runs it once per lookup argument. */
+int smi_dev_args_columns(smi_ctx *ctx, const void *args, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n, const uint64_t *challenges,
+                         uint32_t *d_c, size_t c_stride, uint32_t *closes);
+/* The codeword of step 8: smi_dev_air_compose_ext under the first 4 (W + K) of d_weights (4 (W + K + 2 A) unreduced u64 on
+ * the device), then ONE streaming launch that adds the 2 A auxiliary quotients with one 16-byte read-modify-write per
+ * codeword coordinate.  d_c_lde: the 4 A extended coordinate columns, c_stride >= N apart.  Access rules as for
+ * smi_dev_air_compose_perm. */
+int smi_dev_air_compose_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *args, const uint32_t *d_lde, size_t stride,
+                             const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                             size_t out_stride);
+/* The prover of the protocol above.  roots (host, optional) gets root_1 then root_2; stage_ms (optional) gets six values
+ * {lde, commit, args, compose, fri, open} -- args is the columns, their extension and their tree; *closes (optional) is the
+ * mask above.  cfg->row_leaves and cfg->open_columns are taken as set.  Two host round trips, as for one argument. */
+int smi_dev_air_prove_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *args, const uint32_t *d_trace_cols, uint8_t *roots,
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes);
+int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *args, const uint8_t *roots, const uint8_t *proof,
+                        size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

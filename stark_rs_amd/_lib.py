@@ -64,6 +64,16 @@ class AirLookup(C.Structure):
     _fields_ = [("width", C.c_uint32), ("mult_col", C.c_uint32), ("lookup_col", u32p), ("table_col", u32p)]
 
 
+class AirArg(C.Structure):
+    """smi_air_arg (include/stark_mi.h, "Argument list"): one permutation (kind 0) or lookup (kind 1) of a list"""
+    _fields_ = [("kind", C.c_uint32), ("width", C.c_uint32), ("mult_col", C.c_uint32), ("reserved0", C.c_uint32), ("a_col", u32p), ("b_col", u32p)]
+
+
+class AirArgs(C.Structure):
+    """smi_air_args; mirror.Air.flatten fills one when Air.add_permutation / Air.add_lookup were called"""
+    _fields_ = [("count", C.c_uint32), ("reserved0", C.c_uint32), ("arg", C.POINTER(AirArg))]
+
+
 def build(force=False):
     """Compile libstarkmi.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
@@ -217,6 +227,12 @@ def lib():
         "smi_dev_air_prove_lookup": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
                                            C.c_uint32, C.POINTER(i32)]),
         "smi_air_verify_lookup": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirLookup), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_args": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), u32p, u64p]),
+        "smi_dev_args_columns": (i32, [vp, C.POINTER(AirArgs), vp, C.c_uint32, C.c_uint32, u64p, vp, sz, u32p]),
+        "smi_dev_air_compose_args": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), vp, sz, vp, sz, u64p, vp, vp, sz]),
+        "smi_dev_air_prove_args": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
+                                         C.c_uint32, u32p]),
+        "smi_air_verify_args": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

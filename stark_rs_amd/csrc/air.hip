@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "air_core.h"
+#include "args_core.h"
 #include "hash_core.h"
 #include "internal.h"
 #include "mgpu_core.h"
@@ -273,6 +274,10 @@ int smi_air_plan_perm(uint64_t p, const smi_stark_cfg *cfg, const void *air, con
 int smi_air_plan_lookup(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *lookup, uint32_t *degree, uint64_t *fri_expansion) {
     g_air_err.clear();
     return lookup_plan(p, cfg, (const smi_air *)air, (const smi_air_lookup *)lookup, degree, fri_expansion, &g_air_err);
+}
+int smi_air_plan_args(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *args, uint32_t *degree, uint64_t *fri_expansion) {
+    g_air_err.clear();
+    return args_plan(p, cfg, (const smi_air *)air, (const smi_air_args *)args, degree, fri_expansion, &g_air_err);
 }
 // what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }

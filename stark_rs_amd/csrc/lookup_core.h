@@ -77,17 +77,14 @@ SMI_HD Fq fq_add(const Fq &a, const Fq &b, uint32_t p) {
 // return anything for them).  sl[q]: the sum of the lane's delta before row q (sl[0] = 0), *sum the sum of all of them, plain.
 // delta[r] = 1 / f_L(r) - M[r] / f_T(r) = (f_T - M f_L) / (f_L f_T): one F_q inversion serves the lane's four products.  A
 // zero f_L or f_T is replaced by one and reported: *zero_at is the smallest 2 * row + (0: f_L, 1: f_T), or ~0.
-template <class Load4>
-SMI_HD void lookup_lane_column(const LookupDev &LD, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq sl[PERM_ROWS], Fq *sum, uint64_t *zero_at) {
-    const PermDev &PD = LD.P;
+// lookup_lane_deltas is the part behind the tuples: fl = f_L, ft = f_T and mult = M of the lane's rows on entry (fl and ft
+// are overwritten).
+SMI_HD void lookup_lane_deltas(uint32_t g_m, const Fp &F, uint64_t row0, uint64_t n, Fq fl[PERM_ROWS], Fq ft[PERM_ROWS], const uint32_t mult[PERM_ROWS],
+                               Fq sl[PERM_ROWS], Fq *sum, uint64_t *zero_at) {
     const uint32_t p = F.p;
-    Fq fl[PERM_ROWS], ft[PERM_ROWS], den[PERM_ROWS], pre[PERM_ROWS];
-    uint32_t mult[PERM_ROWS];
+    Fq den[PERM_ROWS], pre[PERM_ROWS];
     const Fq one = fq_one(F);
     uint64_t za = ~0ull;
-    perm_tuples(PD, F, PD.lcol, load4, fl);
-    perm_tuples(PD, F, PD.rcol, load4, ft);
-    load4(LD.mcol, mult);
 #pragma unroll
     for (int q = PERM_ROWS - 1; q >= 0; q--) {
         if (row0 + q >= n) {
@@ -103,21 +100,21 @@ SMI_HD void lookup_lane_column(const LookupDev &LD, const Fp &F, uint64_t row0, 
                 za = 2 * (row0 + q);
             }
         }
-        den[q] = fq_mul(fl[q], ft[q], PD.g_m, F);
+        den[q] = fq_mul(fl[q], ft[q], g_m, F);
     }
     pre[0] = den[0];
 #pragma unroll
-    for (int q = 1; q < PERM_ROWS; q++) pre[q] = fq_mul(pre[q - 1], den[q], PD.g_m, F);
-    Fq inv = fq_inv(pre[PERM_ROWS - 1], PD.g_m, F);
+    for (int q = 1; q < PERM_ROWS; q++) pre[q] = fq_mul(pre[q - 1], den[q], g_m, F);
+    Fq inv = fq_inv(pre[PERM_ROWS - 1], g_m, F);
     Fq delta[PERM_ROWS];
 #pragma unroll
     for (int q = PERM_ROWS - 1; q >= 0; q--) {
-        const Fq di = q ? fq_mul(inv, pre[q - 1], PD.g_m, F) : inv;   // 1 / den[q], Montgomery
-        if (q) inv = fq_mul(inv, den[q], PD.g_m, F);
+        const Fq di = q ? fq_mul(inv, pre[q - 1], g_m, F) : inv;   // 1 / den[q], Montgomery
+        if (q) inv = fq_mul(inv, den[q], g_m, F);
         Fq num;                                                        // f_T - M f_L, plain
 #pragma unroll
         for (int e = 0; e < 4; e++) num.c[e] = fp_sub(from_mont(ft[q].c[e], F), mont_mul(mult[q], fl[q].c[e], F), p);
-        delta[q] = fq_mul(num, di, PD.g_m, F);                         // plain
+        delta[q] = fq_mul(num, di, g_m, F);                         // plain
         if (row0 + q >= n) delta[q] = Fq{{0, 0, 0, 0}};
     }
     sl[0] = Fq{{0, 0, 0, 0}};
@@ -125,6 +122,16 @@ SMI_HD void lookup_lane_column(const LookupDev &LD, const Fp &F, uint64_t row0, 
     for (int q = 1; q < PERM_ROWS; q++) sl[q] = fq_add(sl[q - 1], delta[q - 1], p);
     *sum = fq_add(sl[PERM_ROWS - 1], delta[PERM_ROWS - 1], p);
     *zero_at = za;
+}
+template <class Load4>
+SMI_HD void lookup_lane_column(const LookupDev &LD, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq sl[PERM_ROWS], Fq *sum, uint64_t *zero_at) {
+    const PermDev &PD = LD.P;
+    Fq fl[PERM_ROWS], ft[PERM_ROWS];
+    uint32_t mult[PERM_ROWS];
+    perm_tuples(PD, F, PD.lcol, load4, fl);
+    perm_tuples(PD, F, PD.rcol, load4, ft);
+    load4(LD.mcol, mult);
+    lookup_lane_deltas(PD.g_m, F, row0, n, fl, ft, mult, sl, sum, zero_at);
 }
 
 // The workgroup's additive scan of one F_q element per lane, Hillis-Steele over two buffers of 4 x PERM_BLOCK words, with the
@@ -138,11 +145,11 @@ SMI_HD void lookup_scan_step(const uint32_t (*in)[PERM_BLOCK], uint32_t (*out)[P
 // tau) and izt = 1 / (x^n - tau^n), Montgomery).  Q is a template argument and the four points are instantiated one after
 // the other: every index into the lane's arrays is a constant, whatever the unroller makes of a body of this size.
 template <int Q>
-SMI_HD void lookup_compose_point(const PermDev &PD, const Fp &F, const ExtMul &wb, const ExtMul &wt, uint32_t di_m, uint32_t izt, const Fq &fl, const Fq &ft,
+SMI_HD void lookup_compose_point(uint32_t g_m, const Fp &F, const ExtMul &wb, const ExtMul &wt, uint32_t di_m, uint32_t izt, const Fq &fl, const Fq &ft,
                                  uint32_t mult, uint32_t sc[4][PERM_ROWS], uint32_t sx[4][PERM_ROWS], uint32_t acc[4][PERM_ROWS]) {
     const uint32_t p = F.p;
-    const Fq lt = fq_mul(fl, ft, PD.g_m, F);                // f_L f_T, Montgomery
-    const ExtMul MP = ext_mul_prepare(lt.c, PD.g_m, F);
+    const Fq lt = fq_mul(fl, ft, g_m, F);                   // f_L f_T, Montgomery
+    const ExtMul MP = ext_mul_prepare(lt.c, g_m, F);
     uint32_t ds[4], a[4], tq[4], bq[4], u[4], v[4];
 #pragma unroll
     for (int e = 0; e < 4; e++) ds[e] = fp_sub(sx[e][Q], sc[e][Q], p);
@@ -191,10 +198,10 @@ SMI_HD void lookup_compose_points(const LookupDev &LD, const Fp &F, const ExtMul
     perm_tuples(PD, F, PD.rcol, load4, ft);
     load4(LD.mcol, mult);
     const uint32_t ib = (uint32_t)(i0 & (B - 1));   // i0 and B are multiples of 4: the four table entries are consecutive
-    lookup_compose_point<0>(PD, F, wb, wt, di[0], izt_m[ib], fl[0], ft[0], mult[0], sc, sx, acc);
-    lookup_compose_point<1>(PD, F, wb, wt, di[1], izt_m[ib + 1], fl[1], ft[1], mult[1], sc, sx, acc);
-    lookup_compose_point<2>(PD, F, wb, wt, di[2], izt_m[ib + 2], fl[2], ft[2], mult[2], sc, sx, acc);
-    lookup_compose_point<3>(PD, F, wb, wt, di[3], izt_m[ib + 3], fl[3], ft[3], mult[3], sc, sx, acc);
+    lookup_compose_point<0>(PD.g_m, F, wb, wt, di[0], izt_m[ib], fl[0], ft[0], mult[0], sc, sx, acc);
+    lookup_compose_point<1>(PD.g_m, F, wb, wt, di[1], izt_m[ib + 1], fl[1], ft[1], mult[1], sc, sx, acc);
+    lookup_compose_point<2>(PD.g_m, F, wb, wt, di[2], izt_m[ib + 2], fl[2], ft[2], mult[2], sc, sx, acc);
+    lookup_compose_point<3>(PD.g_m, F, wb, wt, di[3], izt_m[ib + 3], fl[3], ft[3], mult[3], sc, sx, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ host side

@@ -64,14 +64,15 @@ SMI_HD Fq fq_inv(const Fq &a, uint32_t g_m, const Fp &F) {
 // four plain cells of column col (one 16-byte access where the layout allows); the members are the outer loop, so a column is
 // fetched once for the four rows and nothing is indexed by a runtime value but the kernel's own argument.  A product of an
 // F_q element by a base-field cell is four multiplies.
+// tuples_of takes the tables by pointer (the argument list of args_core.h keeps alpha's powers once for all its arguments).
 template <class Load4>
-SMI_HD void perm_tuples(const PermDev &PD, const Fp &F, const uint32_t *cols, Load4 load4, Fq f[PERM_ROWS]) {
+SMI_HD void tuples_of(const uint32_t (*apow_mm)[4], const uint32_t *gamma_m, uint32_t m, const Fp &F, const uint32_t *cols, Load4 load4, Fq f[PERM_ROWS]) {
 #pragma unroll
-    for (int q = 0; q < PERM_ROWS; q++) f[q] = Fq{{PD.gamma_m[0], PD.gamma_m[1], PD.gamma_m[2], PD.gamma_m[3]}};
-    for (uint32_t j = 0; j < PD.m; j++) {
+    for (int q = 0; q < PERM_ROWS; q++) f[q] = Fq{{gamma_m[0], gamma_m[1], gamma_m[2], gamma_m[3]}};
+    for (uint32_t j = 0; j < m; j++) {
         uint32_t v[PERM_ROWS];
         load4(cols[j], v);
-        const uint32_t a0 = PD.apow_mm[j][0], a1 = PD.apow_mm[j][1], a2 = PD.apow_mm[j][2], a3 = PD.apow_mm[j][3];
+        const uint32_t a0 = apow_mm[j][0], a1 = apow_mm[j][1], a2 = apow_mm[j][2], a3 = apow_mm[j][3];
 #pragma unroll
         for (int q = 0; q < PERM_ROWS; q++) {
             f[q].c[0] = fp_add(f[q].c[0], mont_mul(v[q], a0, F), F.p);
@@ -81,18 +82,21 @@ SMI_HD void perm_tuples(const PermDev &PD, const Fp &F, const uint32_t *cols, Lo
         }
     }
 }
+template <class Load4>
+SMI_HD void perm_tuples(const PermDev &PD, const Fp &F, const uint32_t *cols, Load4 load4, Fq f[PERM_ROWS]) {
+    tuples_of(PD.apow_mm, PD.gamma_m, PD.m, F, cols, load4, f);
+}
 
 // One lane of the column build: rows row0 .. row0 + PERM_ROWS - 1 (those below n; the others count as rho = 1 and load4 may
 // return anything for them).  zl[q]: the product of the lane's rho before row q (zl[0] = 1), *prod the product of all of
 // them, both Montgomery.  One F_q inversion serves the lane's denominators (Montgomery's trick); a zero denominator would
 // spoil the whole batch, so it is replaced by one first and its row is reported: *zero_row is the smallest such row, or ~0.
-template <class Load4>
-SMI_HD void perm_lane_column(const PermDev &PD, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq zl[PERM_ROWS], Fq *prod, uint64_t *zero_row) {
-    Fq num[PERM_ROWS], den[PERM_ROWS], pre[PERM_ROWS];
+// perm_lane_ratios is the part behind the tuples: num = f_L and den = f_R of the lane's rows on entry (both are overwritten).
+SMI_HD void perm_lane_ratios(uint32_t g_m, const Fp &F, uint64_t row0, uint64_t n, Fq num[PERM_ROWS], Fq den[PERM_ROWS], Fq zl[PERM_ROWS], Fq *prod,
+                             uint64_t *zero_row) {
+    Fq pre[PERM_ROWS];
     const Fq one = fq_one(F);
     uint64_t zr = ~0ull;
-    perm_tuples(PD, F, PD.lcol, load4, num);
-    perm_tuples(PD, F, PD.rcol, load4, den);
 #pragma unroll
     for (int q = PERM_ROWS - 1; q >= 0; q--) {
         if (row0 + q >= n) {
@@ -105,19 +109,26 @@ SMI_HD void perm_lane_column(const PermDev &PD, const Fp &F, uint64_t row0, uint
     }
     pre[0] = den[0];
 #pragma unroll
-    for (int q = 1; q < PERM_ROWS; q++) pre[q] = fq_mul(pre[q - 1], den[q], PD.g_m, F);
-    Fq inv = fq_inv(pre[PERM_ROWS - 1], PD.g_m, F);
+    for (int q = 1; q < PERM_ROWS; q++) pre[q] = fq_mul(pre[q - 1], den[q], g_m, F);
+    Fq inv = fq_inv(pre[PERM_ROWS - 1], g_m, F);
 #pragma unroll
     for (int q = PERM_ROWS - 1; q >= 0; q--) {
-        const Fq di = q ? fq_mul(inv, pre[q - 1], PD.g_m, F) : inv;   // 1 / den[q]
-        if (q) inv = fq_mul(inv, den[q], PD.g_m, F);
-        num[q] = fq_mul(num[q], di, PD.g_m, F);                        // rho
+        const Fq di = q ? fq_mul(inv, pre[q - 1], g_m, F) : inv;   // 1 / den[q]
+        if (q) inv = fq_mul(inv, den[q], g_m, F);
+        num[q] = fq_mul(num[q], di, g_m, F);                        // rho
     }
     zl[0] = one;
 #pragma unroll
-    for (int q = 1; q < PERM_ROWS; q++) zl[q] = fq_mul(zl[q - 1], num[q - 1], PD.g_m, F);
-    *prod = fq_mul(zl[PERM_ROWS - 1], num[PERM_ROWS - 1], PD.g_m, F);
+    for (int q = 1; q < PERM_ROWS; q++) zl[q] = fq_mul(zl[q - 1], num[q - 1], g_m, F);
+    *prod = fq_mul(zl[PERM_ROWS - 1], num[PERM_ROWS - 1], g_m, F);
     *zero_row = zr;
+}
+template <class Load4>
+SMI_HD void perm_lane_column(const PermDev &PD, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq zl[PERM_ROWS], Fq *prod, uint64_t *zero_row) {
+    Fq num[PERM_ROWS], den[PERM_ROWS];
+    perm_tuples(PD, F, PD.lcol, load4, num);
+    perm_tuples(PD, F, PD.rcol, load4, den);
+    perm_lane_ratios(PD.g_m, F, row0, n, num, den, zl, prod, zero_row);
 }
 
 // One lane of the auxiliary quotients: PERM_ROWS consecutive points i0 .. i0 + PERM_ROWS - 1.

@@ -75,3 +75,8 @@ inline void transcript_perm_challenges(Transcript &T, const uint8_t root1[32], s
 inline void transcript_perm_weights(Transcript &T, const uint8_t root2[32], uint32_t W, uint32_t K, std::vector<uint64_t> *out) {
     transcript_indexed(T, root2, 8, 4 * ((uint64_t)W + K + 2), out);
 }
+// the argument list (include/stark_mi.h, "Argument list"): transcript_perm_challenges, then root_2 and 8 + m for m < 4 (W + K +
+// 2 A); with A = 1 these are transcript_perm_weights' bytes
+inline void transcript_args_weights(Transcript &T, const uint8_t root2[32], uint32_t W, uint32_t K, uint32_t A, std::vector<uint64_t> *out) {
+    transcript_indexed(T, root2, 8, 4 * ((uint64_t)W + K + 2 * (uint64_t)A), out);
+}

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "air_core.h"
+#include "args_core.h"
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
@@ -421,6 +422,7 @@ const OpeningWords AIR_WORDS = {"air openings: wrong length", "air openings: mal
                                 "air openings: authentication path does not verify", "air openings: an opened value is not canonical",
                                 "air openings: the composition of the opened rows is not the codeword value"};
 const OpeningWords LOOKUP_WORDS = {LOOKUP_SENTENCES[0], LOOKUP_SENTENCES[1], LOOKUP_SENTENCES[2], LOOKUP_SENTENCES[3], LOOKUP_SENTENCES[4], LOOKUP_SENTENCES[5]};   // lookup_core.h
+const OpeningWords ARGS_WORDS = {ARGS_SENTENCES[0], ARGS_SENTENCES[1], ARGS_SENTENCES[2], ARGS_SENTENCES[3], ARGS_SENTENCES[4], ARGS_SENTENCES[5]};   // args_core.h
 const OpeningWords PERM_WORDS = {"perm openings: wrong length", "perm openings: malformed row", "perm openings: malformed path",
                                  "perm openings: authentication path does not verify", "perm openings: an opened value is not canonical",
                                  "perm openings: the composition of the opened rows is not the codeword value"};
@@ -660,12 +662,16 @@ struct LookupAux {
 //             auxiliary quotients added to the composition; the tags of both sections are checked record by record before
 //             either is authenticated, and every opened value is checked canonical before the composition
 //   lookup  : the lookup argument: the same second root and second section (the rows of s) with its own two quotients and
-//             its own sentences; at most one of perm and lookup is set
+//             its own sentences
+//   args    : the argument list ("Argument list"): the second section's rows are 4 A values wide, argument a at the
+//             coordinates 4 a .. 4 a + 3 with the weights W + K + 2 a and W + K + 2 a + 1, PermAux or LookupAux once per
+//             argument, its own sentences; at most one of perm, lookup and args is set
 struct AirVariant {
     bool by_rows, over_ext;
     int grind;
     const smi_air_perm *perm;
     const smi_air_lookup *lookup;
+    const smi_air_args *args = nullptr;
 };
 // One verifier for them all: the weights and FRI's seed from the variant's transcript, Fri::verify at expansion factor E,
 // then the openings -- length, records, every path against its root, and the composition codeword recomputed at x_a and
@@ -674,9 +680,10 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                            int *accept, const AirVariant &var) {
     std::string why;
     uint64_t E = 0;
-    const bool has_aux = var.perm || var.lookup;   // an auxiliary column: a second root, a second section, two more quotients
+    const bool has_aux = var.perm || var.lookup || var.args;   // auxiliary columns: a second root, a second section, two more quotients each
     const int vrc = var.perm     ? perm_plan(ctx->fs.F.p, cfg, air, var.perm, nullptr, &E, &why)
                     : var.lookup ? lookup_plan(ctx->fs.F.p, cfg, air, var.lookup, nullptr, &E, &why)
+                    : var.args   ? args_plan(ctx->fs.F.p, cfg, air, var.args, nullptr, &E, &why)
                                  : air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
     if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
     const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
@@ -687,7 +694,8 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     std::vector<uint64_t> ch, weights;   // ch: alpha and gamma of the auxiliary column
     if (has_aux) {
         transcript_perm_challenges(tr, roots, &ch);
-        transcript_perm_weights(tr, roots + 32, W, K, &weights);
+        if (var.args) transcript_args_weights(tr, roots + 32, W, K, var.args->count, &weights);
+        else transcript_perm_weights(tr, roots + 32, W, K, &weights);
     } else if (var.over_ext) {
         transcript_ext(tr, roots, W, K, &weights);
     } else if (var.by_rows) {
@@ -704,10 +712,11 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     *accept = 0;
     // ---- the opening sections: rows of W values under root_1 (or the column roots); with an auxiliary column, rows of 4
     // values under root_2
-    const OpeningWords &say = var.perm ? PERM_WORDS : var.lookup ? LOOKUP_WORDS : AIR_WORDS;
+    const OpeningWords &say = var.perm ? PERM_WORDS : var.lookup ? LOOKUP_WORDS : var.args ? ARGS_WORDS : AIR_WORDS;
     const size_t R = (K || has_aux) ? 4 : 2, m = R * t, prec = 9 + 32 * (size_t)logN, n_sec = has_aux ? 2 : 1;
-    const uint32_t widths[2] = {W, 4}, NE = var.over_ext ? 4 : 1;
-    const size_t sec_len[2] = {m * (9 + 8 * (size_t)W) + (var.by_rows ? 1 : W) * m * prec, has_aux ? m * (9 + 8 * (size_t)4) + m * prec : 0};
+    const uint32_t AW = var.args ? 4 * var.args->count : 4;   // values in a row of the second section
+    const uint32_t widths[2] = {W, AW}, NE = var.over_ext ? 4 : 1;
+    const size_t sec_len[2] = {m * (9 + 8 * (size_t)W) + (var.by_rows ? 1 : W) * m * prec, has_aux ? m * (9 + 8 * (size_t)AW) + m * prec : 0};
     if (proof_len - end != sec_len[0] + sec_len[1]) return reject(ctx, accept, say.length);
     const uint8_t *sec[2] = {proof + end, proof + end + sec_len[0]};
     const std::vector<uint64_t> pos = opened_positions(top, N, B, R);
@@ -743,6 +752,22 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     std::optional<LookupAux> laux;
     if (var.perm) aux.emplace(ctx, cfg, var.perm, ch.data(), &weights[4 * (W + K)], &weights[4 * (W + K + 1)]);
     if (var.lookup) laux.emplace(ctx, cfg, var.lookup, ch.data(), &weights[4 * (W + K)], &weights[4 * (W + K + 1)]);
+    // the argument list: argument a as a PermAux or a LookupAux over its own statement (kept here: the Aux hold pointers)
+    const uint32_t NA = var.args ? var.args->count : 0;
+    std::vector<smi_air_perm> a_perm(NA);
+    std::vector<smi_air_lookup> a_lookup(NA);
+    std::vector<std::optional<PermAux>> a_paux(NA);
+    std::vector<std::optional<LookupAux>> a_laux(NA);
+    for (uint32_t a = 0; a < NA; a++) {
+        const uint64_t *wb = &weights[4 * (W + K + 2 * a)], *wt = &weights[4 * (W + K + 2 * a + 1)];
+        if (var.args->arg[a].kind == SMI_ARG_PERM) {
+            a_perm[a] = args_as_perm(var.args->arg[a]);
+            a_paux[a].emplace(ctx, cfg, &a_perm[a], ch.data(), wb, wt);
+        } else {
+            a_lookup[a] = args_as_lookup(var.args->arg[a]);
+            a_laux[a].emplace(ctx, cfg, &a_lookup[a], ch.data(), wb, wt);
+        }
+    }
     for (uint64_t s = 0; s < t; s++)
         for (size_t k = 0; k < 2; k++) {
             const uint64_t i = pos[R * s + k];
@@ -763,6 +788,11 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
             else air_compose_points<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
             if (var.perm) aux->add(x, cur, &rows[1][(R * s + k) * 4], &rows[1][(R * s + k + 2) * 4], got);
             if (var.lookup) laux->add(x, cur, &rows[1][(R * s + k) * 4], &rows[1][(R * s + k + 2) * 4], got);
+            for (uint32_t a = 0; a < NA; a++) {
+                const uint64_t *cc = &rows[1][(R * s + k) * AW + 4 * a], *cn = &rows[1][(R * s + k + 2) * AW + 4 * a];
+                if (a_paux[a]) a_paux[a]->add(x, cur, cc, cn, got);
+                else a_laux[a]->add(x, cur, cc, cn, got);
+            }
             for (uint32_t e = 0; e < NE; e++)
                 if (got[e] != ab[(2 * s + k) * NE + e] % p) return reject(ctx, accept, say.composition);
         }
@@ -830,4 +860,17 @@ int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
     SMI_TRY(ext_field_check(ctx));
     return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
                                   AirVariant{true, true, (int)grind_bits, nullptr, (const smi_air_lookup *)lookup}));
+}
+
+// Verifier of smi_dev_air_prove_args (include/stark_mi.h, "Argument list"): smi_air_verify_perm's checks over a second section
+// of 4 A values a row, with every argument's two auxiliary quotients (AirVariant::args).
+int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *args, const uint8_t *roots, const uint8_t *proof,
+                        size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !args || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
+                                  AirVariant{true, true, (int)grind_bits, nullptr, nullptr, (const smi_air_args *)args}));
 }

@@ -500,6 +500,8 @@ class Engine:
         """smi_air_plan -> (degree d, FRI expansion factor E); raises with the limit that was broken"""
         a = self._air(air)
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        if self._args(a) is not None:   # smi_air_plan_args: d = max(d_air, 2 with a permutation, 3 with a lookup)
+            return air_plan_args(self.p, a, a.args, cfg)
         if self._perm(a) is not None:   # smi_air_plan_perm: d = max(d_air, 2)
             return air_plan_perm(self.p, a, a.perm, cfg)
         if self._lookup(a) is not None:   # smi_air_plan_lookup: d = max(d_air, 3)
@@ -515,6 +517,40 @@ class Engine:
     def _lookup(air):
         """the _lib.AirLookup a flattened AIR carries (mirror.Air.lookup), or None"""
         return getattr(air, "lookup", None)
+
+    @staticmethod
+    def _args(air):
+        """the _lib.AirArgs a flattened AIR carries (mirror.Air.add_permutation / add_lookup), or None"""
+        return getattr(air, "args", None)
+
+    def _args_of(self, air, who):
+        a = self._air(air)
+        if self._args(a) is None:
+            raise ValueError(f"{who}: the AIR has no argument list (mirror.Air.add_permutation / add_lookup)")
+        return a
+
+    def dev_args_columns(self, air, d_trace_cols, n_cols, log_n, challenges, d_c, c_stride=None):
+        """smi_dev_args_columns: the A columns of air's argument list under the 8 unreduced challenges (alpha, gamma) into 4 A
+        coordinate columns c_stride (default n) apart -> closes, a list of A bools.  StarkMiError "no inverse: ... argument a:
+        ... row r" when a denominator is zero."""
+        a = self._args_of(air, "dev_args_columns")
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        closes = C.c_uint32()
+        self._ck_perm(self.L.smi_dev_args_columns(self.h, C.byref(a.args), vp(d_trace_cols), n_cols, log_n, ch, vp(d_c),
+                                                  (1 << log_n) if c_stride is None else c_stride, C.byref(closes)))
+        return [bool(closes.value >> i & 1) for i in range(a.args.count)]
+
+    def dev_air_compose_args(self, air, d_lde, d_c_lde, n_cols, log_n, log_blowup, challenges, d_weights, d_out, stride=None, c_stride=None,
+                             out_stride=None, trace_offset=1, lde_offset=None):
+        """smi_dev_air_compose_args: smi_dev_air_compose_ext under the first 4 (W + K) of the 4 (W + K + 2 A) device weights plus
+        the 2 A auxiliary quotients of the 4 A extended coordinate columns d_c_lde, in one streaming launch"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        a = self._args_of(air, "dev_air_compose_args")
+        N = 1 << (log_n + log_blowup)
+        ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        self._ck(self.L.smi_dev_air_compose_args(self.h, C.byref(cfg), C.byref(a), C.byref(a.args), vp(d_lde), N if stride is None else stride,
+                                                 vp(d_c_lde), N if c_stride is None else c_stride, ch, vp(d_weights), vp(d_out),
+                                                 N if out_stride is None else out_stride))
 
     def _ck_perm(self, st):
         if st in (-1, -56):   # SMI_ERR_NO_INVERSE, SMI_ERR_LOOKUP_MISSING: the sentence names the row
@@ -624,8 +660,43 @@ class Engine:
         a sixth stage "perm", the result has "closes", and check=True raises when the product does not close.
         An AIR with a lookup (mirror.Air.lookup) takes smi_dev_air_prove_lookup in the same way (the sixth stage is "lookup",
         check=True raises when the sum does not close); fill_multiplicities=True first runs dev_lookup_multiplicities into the
-        trace's mult_col, which is otherwise taken as filled."""
+        trace's mult_col, which is otherwise taken as filled.
+        An AIR with an argument list (mirror.Air.add_permutation / add_lookup) takes smi_dev_air_prove_args in the same way: the
+        sixth stage is "args", "closes" is a list of A bools, check=True raises naming the arguments that do not close, and
+        fill_multiplicities=True runs dev_lookup_multiplicities once per lookup argument."""
         a = self._air(air)
+        if self._args(a) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("dev_air_prove: an AIR with an argument list needs row_leaves=True, ext=True")
+            lookups = [a.args.arg[i] for i in range(a.args.count) if a.args.arg[i].kind == 1]
+            if fill_multiplicities and not lookups:
+                raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
+            if fill_multiplicities:
+                for g in lookups:
+                    one = _lib.AirLookup(g.width, g.mult_col, g.a_col, g.b_col)
+                    self._ck_perm(self.L.smi_dev_lookup_multiplicities(self.h, C.byref(one), vp(d_trace_cols), n_cols, log_n,
+                                                                       vp(vp(d_trace_cols).value + 4 * (g.mult_col << log_n))))
+            if check:
+                ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+                if not ok:
+                    raise StarkMiError(-50, why)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.zeros((2, 32), dtype=np.uint8)
+            proof, plen, mask = vp(), C.c_size_t(), C.c_uint32()
+            top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
+            stage = (C.c_double * 6)()
+            self._ck_perm(self.L.smi_dev_air_prove_args(self.h, C.byref(cfg), C.byref(a), C.byref(a.args), vp(d_trace_cols), roots.ctypes.data,
+                                                        C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                        0 if grind_bits is None else grind_bits, C.byref(mask)))
+            b = C.string_at(proof, plen.value)
+            self.L.smi_free(proof)
+            closes = [bool(mask.value >> i & 1) for i in range(a.args.count)]
+            if check and not all(closes):
+                raise StarkMiError(-50, f"air_prove_args: the arguments {[i for i, c in enumerate(closes) if not c]} do not close")
+            out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]], "closes": closes}
+            if timed:
+                out["stage_ms"] = dict(zip(("lde", "commit", "args", "compose", "fri", "open"), [float(x) for x in stage]))
+            return out
         if fill_multiplicities and self._lookup(a) is None:
             raise ValueError("dev_air_prove(fill_multiplicities=True): the AIR has no lookup (mirror.Air.lookup)")
         if self._lookup(a) is not None:
@@ -710,7 +781,19 @@ class Engine:
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
         column_roots is root_1 then root_2, grind_bits None counts as 0.  An AIR with a lookup takes smi_air_verify_lookup in
-        the same way."""
+        the same way, and an AIR with an argument list smi_air_verify_args."""
+        if self._args(self._air(air)) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("air_verify: an AIR with an argument list needs row_leaves=True, ext=True")
+            a = self._air(air)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 64:
+                raise StarkMiError(-50, "air_verify: an AIR with an argument list takes two 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_args(self.h, C.byref(cfg), C.byref(a), C.byref(a.args), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if self._lookup(self._air(air)) is not None:
             if not (row_leaves and ext):
                 raise ValueError("air_verify: an AIR with a lookup needs row_leaves=True, ext=True")
@@ -842,6 +925,16 @@ def air_plan_perm(p, air, perm, cfg):
     L = _lib.lib()
     st = L.smi_air_plan_perm(p, C.byref(cfg), C.byref(air), C.byref(perm), C.byref(d), C.byref(e))
     if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, e.value
+
+
+def air_plan_args(p, air, args, cfg):
+    """smi_air_plan_args (host only) -> (d, E).  air: a flattened _lib.Air; args: a _lib.AirArgs"""
+    L = _lib.lib()
+    d, e = C.c_uint32(), C.c_uint64()
+    st = L.smi_air_plan_args(p, C.byref(cfg), C.byref(air), C.byref(args), C.byref(d), C.byref(e))
+    if st != 0:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value
 

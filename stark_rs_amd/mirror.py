@@ -812,7 +812,15 @@ class Air:
 
         air.lookup([0], [1], 2)                                 # every c0[r] is some c1[t]; c2[t] counts them
 
-    With it set the same three take the smi_*_lookup entry points."""
+    With it set the same three take the smi_*_lookup entry points.
+
+    An argument list (include/stark_mi.h, "Argument list") holds up to 8 permutations and lookups, in any mix and order, that
+    one proof shows over one committed trace:
+
+        air.add_permutation([0, 1], [2, 3]).add_lookup([4], [5], 6).add_lookup([7], [5], 8)
+
+    With a non-empty air.args the same three take the smi_*_args entry points.  A list does not mix with permutation() /
+    lookup(): a single argument is either the one of its own section or a list of one, which give the same proof."""
 
     def __init__(self, n_cols):
         self.n_cols = n_cols
@@ -821,6 +829,7 @@ class Air:
         self.periodics = []     # [[value, ...], ...]: a power-of-two number of integers each
         self.perm = None        # ([left columns], [right columns]) once permutation() was called
         self.lookup_arg = None  # ([lookup columns], [table columns], multiplicity column) once lookup() was called
+        self.args = []          # [("perm", left, right) | ("lookup", columns, table columns, multiplicity column), ...]
 
     @property
     def constraints(self):
@@ -850,6 +859,8 @@ class Air:
             raise ValueError("a permutation relates tuples of one width")
         if self.perm is not None:
             raise ValueError("one permutation per AIR")
+        if self.args:
+            raise ValueError("permutation() does not mix with an argument list (add_permutation / add_lookup)")
         if self.lookup_arg is not None:
             raise ValueError("an AIR takes a permutation or a lookup, not both")
         self.perm = (left, right)
@@ -864,10 +875,35 @@ class Air:
             raise ValueError("a lookup relates tuples of one width")
         if self.lookup_arg is not None:
             raise ValueError("one lookup per AIR")
+        if self.args:
+            raise ValueError("lookup() does not mix with an argument list (add_permutation / add_lookup)")
         if self.perm is not None:
             raise ValueError("an AIR takes a permutation or a lookup, not both")
         self.lookup_arg = (cols, table_cols, int(mult_col))
         return self
+
+    ARGS_MAX = 8            # SMI_ARGS_MAX
+
+    def _add_arg(self, arg):
+        a = len(self.args)
+        if self.perm is not None or self.lookup_arg is not None:
+            raise ValueError(f"argument {a}: an argument list does not mix with permutation() / lookup()")
+        if a >= self.ARGS_MAX:
+            raise ValueError(f"argument {a}: an argument list holds at most {self.ARGS_MAX} arguments")
+        if len(arg[1]) != len(arg[2]):
+            raise ValueError(f"argument {a}: a {'permutation' if arg[0] == 'perm' else 'lookup'} relates tuples of one width")
+        if not 1 <= len(arg[1]) <= 8:
+            raise ValueError(f"argument {a}: 1 .. 8 columns a side")
+        self.args.append(arg)
+        return self
+
+    def add_permutation(self, left, right):
+        """appends a permutation argument (see permutation()) to the argument list"""
+        return self._add_arg(("perm", [int(c) for c in left], [int(c) for c in right]))
+
+    def add_lookup(self, cols, table_cols, mult_col):
+        """appends a lookup argument (see lookup()) to the argument list"""
+        return self._add_arg(("lookup", [int(c) for c in cols], [int(c) for c in table_cols], int(mult_col)))
 
     def closes(self, p, g, cols, alpha, gamma):
         """z[n-1] * rho[n-1] == 1 for the trace cols under alpha, gamma (four canonical coordinates each); plain Python"""
@@ -944,6 +980,16 @@ class Air:
             la, ta = np.array(self.lookup_arg[0], dtype=np.uint32), np.array(self.lookup_arg[1], dtype=np.uint32)
             out.lookup = _lib.AirLookup(len(la), self.lookup_arg[2] % (1 << 32), ptr(la, _lib.u32p), ptr(ta, _lib.u32p))
             out.lookup._keep = (la, ta)
+        out.args = None
+        if self.args:
+            keep, raw = [], (_lib.AirArg * len(self.args))()
+            for a, arg in enumerate(self.args):
+                la, ra = np.array(arg[1], dtype=np.uint32), np.array(arg[2], dtype=np.uint32)
+                keep += [la, ra]
+                raw[a] = _lib.AirArg(0 if arg[0] == "perm" else 1, len(la), (arg[3] % (1 << 32)) if arg[0] == "lookup" else 0, 0, ptr(la, _lib.u32p),
+                                     ptr(ra, _lib.u32p))
+            out.args = _lib.AirArgs(len(self.args), 0, raw)
+            out.args._keep = (keep, raw)
         out.perm = None
         if self.perm is not None:
             la, ra = np.array(self.perm[0], dtype=np.uint32), np.array(self.perm[1], dtype=np.uint32)

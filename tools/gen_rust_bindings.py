@@ -172,7 +172,23 @@ def generate():
         for nm in names.split(","):
             lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
     lines.append("}")
+    for sname, what in (("smi_air_arg", "one argument of an argument list"), ("smi_air_args", "an argument list")):
+        lines.append(f"/// {sname}: {what} (host pointers; the entry points take the list as `*const c_void`)")
+        lines.append("#[repr(C)] #[derive(Clone, Copy)]")
+        lines.append(f"pub struct {sname} {{")
+        body = re.search(r"typedef struct " + sname + r"\s*\{(.*?)\}\s*" + sname + r"\s*;", text, flags=re.S).group(1)
+        for decl in [" ".join(d.split()) for d in body.split(";") if d.strip()]:
+            pm = re.fullmatch(r"const (\w+) \*(\w+)", decl)
+            if pm:
+                lines.append(f"    pub {pm.group(2)}: *const {SCALAR.get(pm.group(1), pm.group(1))},")
+                continue
+            ty, names = decl.split(" ", 1)
+            for nm in names.split(","):
+                lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
+        lines.append("}")
     for m in re.finditer(r"#define (SMI_\w+_MAX_\w+) (\d+)", text):
+        lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
+    for m in re.finditer(r"#define (SMI_ARGS_MAX|SMI_ARG_[A-Z]+) (\d+)", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     lines.append("")
     lines.append('#[link(name = "starkmi")]')

@@ -61,18 +61,29 @@ def recurrences_hold(c, cols, args, ch, p, g):
 
 
 # ---------------------------------------------------------------------------------------------- the auxiliary quotients
-def aux_terms(o, lde, cl, args, ch, wch_aux, p, g, log_n, lb, tau, h):
-    """the 2 A auxiliary quotients for every i, as (4, N); cl: (4 A, N) extended columns; wch_aux: the 8 A unreduced challenges
-    behind the main weights (argument a: boundary at 8 a, transition at 8 a + 4)"""
-    total = np.zeros((4, 1 << (log_n + lb)), dtype=np.uint64)
+def aux_terms_at(idx, lde_at, c_at, c_next, args, ch, wch_aux, p, g, wN, log_n, tau, h):
+    """the 2 A auxiliary quotients at the points i of idx alone, as (4, len(idx)): pm.aux_terms_at / lc.aux_terms_at once per
+    argument.  lde_at: (W, len(idx)) the extended trace columns at idx; c_at, c_next: (4 A, len(idx)) the extended columns at
+    idx and at (idx + B) mod N; wch_aux: the 8 A unreduced challenges behind the main weights (argument a: boundary at 8 a,
+    transition at 8 a + 4)"""
+    total = np.zeros((4, len(idx)), dtype=np.uint64)
     for a, arg in enumerate(args):
-        wb, wt, ca = wch_aux[8 * a:8 * a + 4], wch_aux[8 * a + 4:8 * a + 8], cl[4 * a:4 * a + 4]
+        wb, wt = wch_aux[8 * a:8 * a + 4], wch_aux[8 * a + 4:8 * a + 8]
+        ca, cn = c_at[4 * a:4 * a + 4], c_next[4 * a:4 * a + 4]
         if is_perm(arg):
-            t = pm.aux_terms(o, lde, ca, arg[1], arg[2], ch, wb, wt, p, g, log_n, lb, tau, h)
+            t = pm.aux_terms_at(idx, lde_at, ca, cn, arg[1], arg[2], ch, wb, wt, p, g, wN, log_n, tau, h)
         else:
-            t = lc.aux_terms(o, lde, ca, arg[1], arg[2], arg[3], ch, wb, wt, p, g, log_n, lb, tau, h)
+            t = lc.aux_terms_at(idx, lde_at, ca, cn, arg[1], arg[2], arg[3], ch, wb, wt, p, g, wN, log_n, tau, h)
         total = (total + t) % np.uint64(p)
     return total
+
+
+def aux_terms(o, lde, cl, args, ch, wch_aux, p, g, log_n, lb, tau, h):
+    """aux_terms_at for every i, as (4, N); cl: (4 A, N) extended columns"""
+    B, N = 1 << lb, 1 << (log_n + lb)
+    _w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    cl = np.asarray(cl, dtype=np.uint64)
+    return aux_terms_at(np.arange(N), lde, cl, np.roll(cl, -B, axis=1), args, ch, wch_aux, p, g, wN, log_n, tau, h)
 
 
 # ---------------------------------------------------------------------------------------------- transcript, prover, verifier

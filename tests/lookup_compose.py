@@ -86,25 +86,28 @@ def gamma_for_zero(cols, idx, ch, row, p, g):
 
 
 # ---------------------------------------------------------------------------------------------- the auxiliary quotients
-def aux_terms(o, lde, sl, lookup, table, mult_col, ch, wb, wt, p, g, log_n, lb, tau, h):
-    """w_b s(x_i) / (x_i - tau) + w_t ((s(w x_i) - s(x_i)) f_L f_T - f_T + M f_L)(x_i) / (x_i^n - tau^n) for every i, as (4, N);
-    lde: (W, N), sl: (4, N) extended columns; wb, wt: four unreduced ints each"""
-    n, B = 1 << log_n, 1 << lb
-    N = n * B
-    _w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+def aux_terms_at(idx, lde_at, s_at, s_next, lookup, table, mult_col, ch, wb, wt, p, g, wN, log_n, tau, h):
+    """w_b s(x_i) / (x_i - tau) + w_t ((s(w x_i) - s(x_i)) f_L f_T - f_T + M f_L)(x_i) / (x_i^n - tau^n) at the points i of idx
+    alone, as (4, len(idx)).  lde_at: (W, len(idx)) the extended trace columns at idx; s_at, s_next: (4, len(idx)) the extended
+    column s at idx and at (idx + B) mod N; wN: the N-th root of unity of the evaluation domain; wb, wt: four unreduced ints
+    each.  Nothing here is as long as N: the cost is per sampled point (pm.point_inverses)"""
     P = np.uint64(p)
-    lde, sl = np.asarray(lde, dtype=np.uint64), np.asarray(sl, dtype=np.uint64)
-    x = [h * pow(wN, i, p) % p for i in range(N)]
-    ixt = np.array([pow((xi - tau) % p, p - 2, p) for xi in x], dtype=np.uint64)
-    tn = pow(tau, n, p)
-    izt_b = [pow((pow(x[b], n, p) - tn) % p, p - 2, p) for b in range(B)]          # x_i^n depends on i mod B only
-    izt = np.array([izt_b[i % B] for i in range(N)], dtype=np.uint64)
-    fl, ft = pm.tuples_vec(lde, lookup, ch, p, g), pm.tuples_vec(lde, table, ch, p, g)
-    ds = (np.roll(sl, -B, axis=1) + P - sl) % P                                    # index (i + B) mod N
-    num = (pm.mul_vec(ds, pm.mul_vec(fl, ft, p, g), p, g) + P - ft + fl * lde[mult_col] % P) % P
+    lde_at, s_at, s_next = (np.asarray(a, dtype=np.uint64) for a in (lde_at, s_at, s_next))
+    ixt, izt = pm.point_inverses(idx, p, wN, log_n, tau, h)
+    fl, ft = pm.tuples_vec(lde_at, lookup, ch, p, g), pm.tuples_vec(lde_at, table, ch, p, g)
+    ds = (s_next + P - s_at) % P
+    num = (pm.mul_vec(ds, pm.mul_vec(fl, ft, p, g), p, g) + P - ft + fl * (lde_at[mult_col] % P) % P) % P
     tq = num * izt % P
-    bq = sl * ixt % P
+    bq = s_at * ixt % P
     return (xc.mul_arr(bq, [int(v) % p for v in wb], p, g) + xc.mul_arr(tq, [int(v) % p for v in wt], p, g)) % P
+
+
+def aux_terms(o, lde, sl, lookup, table, mult_col, ch, wb, wt, p, g, log_n, lb, tau, h):
+    """aux_terms_at for every i, as (4, N); lde: (W, N), sl: (4, N) extended columns"""
+    B, N = 1 << lb, 1 << (log_n + lb)
+    _w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    sl = np.asarray(sl, dtype=np.uint64)
+    return aux_terms_at(np.arange(N), lde, sl, np.roll(sl, -B, axis=1), lookup, table, mult_col, ch, wb, wt, p, g, wN, log_n, tau, h)
 
 
 # ---------------------------------------------------------------------------------------------- prover, verifier

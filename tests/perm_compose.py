@@ -109,26 +109,37 @@ def gamma_for_zero(cols, right, ch, row, p, g):
 
 
 # ---------------------------------------------------------------------------------------------- the auxiliary quotients
-def aux_terms(o, lde, zl, left, right, ch, wb, wt, p, g, log_n, lb, tau, h):
-    """w_b (z(x_i) - 1) / (x_i - tau) + w_t (z(w x_i) f_R(x_i) - z(x_i) f_L(x_i)) / (x_i^n - tau^n) for every i, as (4, N);
-    lde: (W, N), zl: (4, N) extended columns; wb, wt: four unreduced ints each"""
-    n, B = 1 << log_n, 1 << lb
-    N = n * B
-    _w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
-    P = np.uint64(p)
-    lde, zl = np.asarray(lde, dtype=np.uint64), np.asarray(zl, dtype=np.uint64)
-    x = [h * pow(wN, i, p) % p for i in range(N)]
+def point_inverses(idx, p, wN, log_n, tau, h):
+    """-> (1 / (x_i - tau), 1 / (x_i^n - tau^n)) for the points i of idx as uint64 arrays, x_i = h wN^i by one pow per point"""
+    n, tn = 1 << log_n, pow(tau, 1 << log_n, p)
+    x = [h * pow(wN, int(i), p) % p for i in idx]
     ixt = np.array([pow((xi - tau) % p, p - 2, p) for xi in x], dtype=np.uint64)
-    tn = pow(tau, n, p)
-    izt_b = [pow((pow(x[b], n, p) - tn) % p, p - 2, p) for b in range(B)]          # x_i^n depends on i mod B only
-    izt = np.array([izt_b[i % B] for i in range(N)], dtype=np.uint64)
-    fl, fr = tuples_vec(lde, left, ch, p, g), tuples_vec(lde, right, ch, p, g)
-    zn = np.roll(zl, -B, axis=1)                                                   # index (i + B) mod N
-    tq = (mul_vec(zn, fr, p, g) + P - mul_vec(zl, fl, p, g)) % P * izt % P
-    zm = zl.copy()
+    izt = np.array([pow((pow(xi, n, p) - tn) % p, p - 2, p) for xi in x], dtype=np.uint64)
+    return ixt, izt
+
+
+def aux_terms_at(idx, lde_at, z_at, z_next, left, right, ch, wb, wt, p, g, wN, log_n, tau, h):
+    """w_b (z(x_i) - 1) / (x_i - tau) + w_t (z(w x_i) f_R(x_i) - z(x_i) f_L(x_i)) / (x_i^n - tau^n) at the points i of idx
+    alone, as (4, len(idx)).  lde_at: (W, len(idx)) the extended trace columns at idx; z_at, z_next: (4, len(idx)) the extended
+    column z at idx and at (idx + B) mod N; wN: the N-th root of unity of the evaluation domain; wb, wt: four unreduced ints
+    each.  Nothing here is as long as N: the cost is per sampled point"""
+    P = np.uint64(p)
+    lde_at, z_at, z_next = (np.asarray(a, dtype=np.uint64) for a in (lde_at, z_at, z_next))
+    ixt, izt = point_inverses(idx, p, wN, log_n, tau, h)
+    fl, fr = tuples_vec(lde_at, left, ch, p, g), tuples_vec(lde_at, right, ch, p, g)
+    tq = (mul_vec(z_next, fr, p, g) + P - mul_vec(z_at, fl, p, g)) % P * izt % P
+    zm = z_at.copy()
     zm[0] = (zm[0] + P - np.uint64(1)) % P
     bq = zm * ixt % P
     return (xc.mul_arr(bq, [int(v) % p for v in wb], p, g) + xc.mul_arr(tq, [int(v) % p for v in wt], p, g)) % P
+
+
+def aux_terms(o, lde, zl, left, right, ch, wb, wt, p, g, log_n, lb, tau, h):
+    """aux_terms_at for every i, as (4, N); lde: (W, N), zl: (4, N) extended columns"""
+    B, N = 1 << lb, 1 << (log_n + lb)
+    _w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    zl = np.asarray(zl, dtype=np.uint64)
+    return aux_terms_at(np.arange(N), lde, zl, np.roll(zl, -B, axis=1), left, right, ch, wb, wt, p, g, wN, log_n, tau, h)
 
 
 def main_codeword(o, air, cols, ch_w, p, g, log_n, lb, tau, h, honest=True):

@@ -99,6 +99,34 @@ def test_dev_columns_large_by_the_recurrences(engines):
         assert agc.recurrences_hold(c, bad, args, ch, p, g) == [(True, a != 0), (True, a != 1)]
 
 
+def test_dev_columns_of_eight_arguments_large_by_the_recurrences(engines):
+    """the list of eight (widths 1, 2 and 8, grid.y = 8) at 2^19 rows: eight scan workgroups, each twice round its loop"""
+    log_n = 19
+    p, g = xc.PRIMES[log_n % 2]
+    n = 1 << log_n
+    rng = np.random.default_rng(log_n + 1)
+    src = rng.integers(0, p, (8, n), dtype=np.uint64)
+    tab = rng.integers(0, p, (8, n), dtype=np.uint64)
+    tab[0] = rng.permutation(n).astype(np.uint64)                        # distinct tuples at every width: a plain count
+    pick = rng.integers(0, n, n)
+    M = np.bincount(pick, minlength=n).astype(np.uint64)
+    cols, args = [src, tab[:, pick], tab], []
+    for kind, m in agc.EIGHT:                                            # agc.pool's layout, in numpy
+        W = sum(len(c) for c in cols)
+        if kind == "perm":
+            cols.append(src[:m, rng.permutation(n)])
+            args.append(("perm", list(range(m)), list(range(W, W + m))))
+        else:
+            cols.append(M[None, :])
+            args.append(("lookup", list(range(8, 8 + m)), list(range(16, 16 + m)), W))
+    cols = np.concatenate(cols)
+    assert len(cols) <= 64
+    ch = chall(log_n)
+    c, closes = gpu_columns(engines[p], cols, args, ch)
+    assert closes == [True] * 8
+    assert agc.recurrences_hold(c, cols, args, ch, p, g) == [(True, True)] * 8
+
+
 @pytest.mark.parametrize("p,g", xc.PRIMES)
 def test_zero_denominators_name_the_smallest_key_and_the_next_call_succeeds(engines, p, g):
     """a zero denominator in argument 0 and in argument 2 at once, the lower row in either"""
@@ -185,6 +213,19 @@ def test_dev_air_compose_args_equals_the_restatement(engines, oracle, p, g, name
         assert np.array_equal(got, want), (stride, lead)
         for e in range(4):
             assert np.all(host[e * out_stride + N:(e + 1) * out_stride] == 0x7fffffff)
+
+
+def test_compose_args_on_every_trip_of_the_grid_equals_the_restatement_at_sampled_points(engines):
+    """air_args_compose_kernel on four trips of its grid (tests/test_gpu_perm.py, looping_check) with the list [lookup 1, perm 2,
+    lookup 2], against agc.aux_terms_at"""
+    from test_gpu_perm import looping_check
+    p, g = xc.PRIMES[1]
+    eng = engines[p]
+    args = [("lookup", [4], [5], 6), ("perm", [0, 1], [2, 3]), ("lookup", [0, 1], [2, 3], 7)]
+    assert [(a[0], len(a[1])) for a in args] == SPECS["LPL"]
+    looping_check(eng, p, 8, 4 * len(args), 22, lambda air: agc.mirror_air(air, args),
+                  lambda air, d_lde, d_c, W, log_n, ch, d_w, d_out: eng.dev_air_compose_args(air, d_lde, d_c, W, log_n, LB, ch, d_w, d_out),
+                  lambda idx, lde_at, c_at, c_next, ch, w, wN, log_n: agc.aux_terms_at(idx, lde_at, c_at, c_next, args, ch, w, p, g, wN, log_n, TAU, g))
 
 
 # ---------------------------------------------------------------------------------------------- whole proofs

@@ -223,6 +223,18 @@ def test_dev_air_compose_lookup_equals_the_restatement(engines, oracle, p, g, lo
             assert np.all(host[e * out_stride + N:(e + 1) * out_stride] == 0x7fffffff)
 
 
+def test_compose_lookup_on_every_trip_of_the_grid_equals_the_restatement_at_sampled_points(engines):
+    """air_lookup_compose_kernel on four trips of its grid (tests/test_gpu_perm.py, looping_check): width 2, against
+    lc.aux_terms_at"""
+    from test_gpu_perm import looping_check
+    p, g = xc.PRIMES[1]
+    eng = engines[p]
+    looping_check(eng, p, 5, 4, 21, lambda air: air.lookup([0, 1], [2, 3], 4),
+                  lambda air, d_lde, d_s, W, log_n, ch, d_w, d_out: eng.dev_air_compose_lookup(air, d_lde, d_s, W, log_n, LB, ch, d_w, d_out),
+                  lambda idx, lde_at, s_at, s_next, ch, w, wN, log_n: lc.aux_terms_at(idx, lde_at, s_at, s_next, [0, 1], [2, 3], 4, ch, w[:4], w[4:8], p, g,
+                                                                                      wN, log_n, TAU, g))
+
+
 # ---------------------------------------------------------------------------------------------- whole proofs
 def gpu_prove(eng, air, cols, log_n, t, bits, **kw):
     with Dev(eng) as dev:

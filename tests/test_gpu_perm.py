@@ -159,6 +159,95 @@ def test_dev_air_compose_perm_is_compose_ext_plus_the_restated_auxiliary_terms(e
             assert np.all(host[e * out_stride + N:(e + 1) * out_stride] == 0x7fffffff)
 
 
+def looping_shape(p):
+    """-> (log_n, trip): the smallest trace at blowup 2^LB whose N / 1024 workgroups' worth of points are at least four trips of
+    a grid of 8 workgroups per CU -- the cap of the three streaming compose launches -- and the points of one trip"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    log_n = 1
+    while (1 << (log_n + LB)) // 1024 < 4 * 8 * cus:
+        log_n += 1
+    N = 1 << (log_n + LB)
+    assert N // 1024 >= 4 * 8 * cus                                      # a one-trip launch is not what the callers test
+    assert (p - 1) % N == 0 and log_n <= 27
+    return log_n, 8 * cus * 1024
+
+
+def looping_sample(rng, N, B, trip):
+    """-> at least 4096 distinct points of 0 .. N - 1, among them the first and the last point of every trip and the points
+    round the row step B and the wrap"""
+    edges = [i for k in range(-(-N // trip)) for i in (k * trip, min((k + 1) * trip, N) - 1)]
+    assert len(edges) >= 8 and all(k * trip in edges and k * trip - 1 in edges for k in range(1, 4))
+    must = edges + [0, B - 1, B, N - B - 1, N - B, N - 1]
+    idx = np.unique(np.concatenate([rng.integers(0, N, 4200), np.array(must)]))
+    assert len(idx) >= 4096 and set(must) <= set(int(i) for i in idx)
+    return idx
+
+
+def looping_inputs(p, n_cols, n_aux, log_n, seed):
+    """-> (air, lde, aux, main, full, wch of 4 (W + K) + 8 n_aux / 4 challenges): the mixer AIR with its last-row boundaries moved
+    to row n - 1, over seeded random residues generated on the device.  The compose kernels work point by point: their
+    inputs need not be extensions of anything"""
+    import torch
+    n, N = 1 << log_n, 1 << (log_n + LB)
+    air, _ = ac.make("mixer", 64, p)
+    air.boundaries = [(c, (n - 1 if r == 63 else r), v) for (c, r, v) in air.boundaries]
+    air.n_cols = n_cols
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    lde = torch.randint(0, p, (n_cols, N), generator=gen, device="cuda", dtype=torch.int32)
+    aux = torch.randint(0, p, (n_aux, N), generator=gen, device="cuda", dtype=torch.int32)
+    main, full = torch.empty((4, N), dtype=torch.int32, device="cuda"), torch.empty((4, N), dtype=torch.int32, device="cuda")
+    count = 4 * (n_cols + len(air.constraints)) + 2 * n_aux
+    wch = [int(x) for x in np.random.default_rng(seed).integers(1 << 62, U64_MAX, count, dtype=np.uint64)]
+    torch.cuda.synchronize()
+    return air, lde, aux, main, full, wch
+
+
+def gathered(t, at):
+    """the columns `at` (a device index tensor) of a device int32 matrix, as uint64 on the host"""
+    return t[:, at].cpu().numpy().view(np.uint32).astype(np.uint64)
+
+
+def looping_check(eng, p, n_cols, n_aux, seed, state, compose, restated):
+    """One streaming compose launch on at least four trips of its grid (looping_shape), over looping_inputs:
+    state(air) adds the argument(s) to the AIR; compose(air, d_lde, d_aux, W, log_n, ch, d_w, d_out) is the launch under test;
+    restated(idx, lde_at, aux_at, aux_next, ch, wch_aux, wN, log_n) its auxiliary part at the points idx.
+    (compose - compose_ext) mod p equals it in all four coordinates at >= 4096 sampled points, the edges of every trip
+    among them (looping_sample); a failure names the coordinate, the first wrong point and its trip"""
+    import torch
+    from test_gpu_ext import _dev_u64
+    g = dict(xc.PRIMES)[p]
+    B = 1 << LB
+    log_n, trip = looping_shape(p)
+    N = 1 << (log_n + LB)
+    air, lde, aux, main, full, wch = looping_inputs(p, n_cols, n_aux, log_n, seed)
+    state(air)
+    K, ch = len(air.constraints), chall(seed)
+    t_w, d_w = _dev_u64(wch)
+    torch.cuda.synchronize()
+    eng.dev_air_compose_ext(air, lde.data_ptr(), n_cols, log_n, LB, d_w, main.data_ptr())
+    compose(air, lde.data_ptr(), aux.data_ptr(), n_cols, log_n, ch, d_w, full.data_ptr())
+    eng.sync()
+    idx = looping_sample(np.random.default_rng(seed), N, B, trip)
+    ti = torch.from_numpy(idx).cuda()
+    got = (gathered(full, ti) + np.uint64(p) - gathered(main, ti)) % np.uint64(p)
+    want = restated(idx, gathered(lde, ti), gathered(aux, ti), gathered(aux, (ti + B) % N), ch, wch[4 * (n_cols + K):], pow(g, (p - 1) // N, p), log_n)
+    for e in range(4):
+        bad = np.flatnonzero(got[e] != want[e])
+        assert not len(bad), (e, int(idx[bad[0]]), int(idx[bad[0]]) // trip)
+
+
+def test_compose_perm_on_every_trip_of_the_grid_equals_the_restatement_at_sampled_points(engines):
+    """air_perm_compose_kernel launches at most 8 workgroups per CU and strides over the rest: from 2^23 points on (256 CUs)
+    every lane makes four trips, advancing x by omega^(4 x 256 x gridDim.x) per trip.  Width 2, against pm.aux_terms_at"""
+    p, g = xc.PRIMES[1]
+    eng = engines[p]
+    looping_check(eng, p, 4, 4, 20, lambda air: air.permutation([0, 1], [2, 3]),
+                  lambda air, d_lde, d_z, W, log_n, ch, d_w, d_out: eng.dev_air_compose_perm(air, d_lde, d_z, W, log_n, LB, ch, d_w, d_out),
+                  lambda idx, lde_at, z_at, z_next, ch, w, wN, log_n: pm.aux_terms_at(idx, lde_at, z_at, z_next, [0, 1], [2, 3], ch, w[:4], w[4:8], p, g, wN,
+                                                                                      log_n, TAU, g))
+
+
 # ---------------------------------------------------------------------------------------------- whole proofs
 def case(name, n, p, spoil=False):
     """-> (air with its permutation, cols)"""

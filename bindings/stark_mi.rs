@@ -153,6 +153,25 @@ pub struct smi_air_args {
     pub reserved0: u32,
     pub arg: *const smi_air_arg,
 }
+/// smi_air_xarg: one argument of a list with selectors and periodic members (host pointers; the entry points take the list as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_xarg {
+    pub kind: u32,
+    pub width: u32,
+    pub mult_col: u32,
+    pub reserved0: u32,
+    pub a_var: *const u32,
+    pub b_var: *const u32,
+    pub a_sel: u32,
+    pub b_sel: u32,
+}
+/// smi_air_xargs: an argument list with selectors and periodic members (host pointers; the entry points take the list as `*const c_void`)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct smi_air_xargs {
+    pub count: u32,
+    pub reserved0: u32,
+    pub arg: *const smi_air_xarg,
+}
 pub const SMI_AIR_MAX_CONSTRAINTS: u32 = 64;
 pub const SMI_AIR_MAX_TERMS: u32 = 1024;
 pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
@@ -165,6 +184,7 @@ pub const SMI_LOOKUP_MAX_WIDTH: u32 = 8;
 pub const SMI_ARGS_MAX: u32 = 8;
 pub const SMI_ARG_PERM: u32 = 0;
 pub const SMI_ARG_LOOKUP: u32 = 1;
+pub const SMI_ARG_NO_SELECTOR: u32 = 0xffffffff;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -281,6 +301,12 @@ extern "C" {
     pub fn smi_dev_air_compose_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
     pub fn smi_dev_air_prove_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
     pub fn smi_air_verify_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, args: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_xargs(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
+    pub fn smi_dev_xargs_multiplicities(ctx: *mut smi_ctx, air: *const c_void, xargs: *const c_void, a: u32, d_trace_cols: *const u32, n_cols: u32, log_n: u32, d_mult: *mut u32) -> c_int;
+    pub fn smi_dev_xargs_columns(ctx: *mut smi_ctx, air: *const c_void, xargs: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: *const u64, d_c: *mut u32, c_stride: usize, closes: *mut u32) -> c_int;
+    pub fn smi_dev_air_compose_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_prove_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_trace_cols: *const u32, roots: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
+    pub fn smi_air_verify_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
@@ -1081,6 +1107,109 @@ impl Arguments {
             smi_dev_args_columns(ctx.raw, al, d_trace_cols, n_cols, log_n, challenges.as_ptr(), d_c, c_stride, &mut closes)
         }));
         closes
+    }
+}
+
+/// A member or selector of an argument with selectors and periodic members: a trace column or a periodic column of the AIR.
+#[derive(Clone, Copy)]
+pub enum Operand {
+    Col(u32),
+    Periodic(u32),
+}
+
+/// An argument list with selectors and periodic members (include/stark_mi.h, "Argument list with selectors and periodic
+/// members"): `Arguments` whose tuple members may be periodic columns of the AIR and whose sides may each have a selector.
+/// `n_cols` is the trace width the operands are numbered against.
+pub struct SelectedArguments {
+    n_cols: u32,
+    items: Vec<(u32, Vec<u32>, Vec<u32>, u32, u32, u32)>,   // kind, a_var, b_var, mult_col, a_sel, b_sel
+}
+
+impl SelectedArguments {
+    pub fn new(n_cols: u32) -> SelectedArguments {
+        SelectedArguments { n_cols, items: Vec::new() }
+    }
+    fn var(&self, o: Operand) -> u32 {
+        match o {
+            Operand::Col(c) => c,
+            Operand::Periodic(j) => 2 * self.n_cols + j,
+        }
+    }
+    fn sel(&self, o: Option<Operand>) -> u32 {
+        o.map_or(SMI_ARG_NO_SELECTOR, |x| self.var(x))
+    }
+    pub fn permutation(mut self, left: &[Operand], right: &[Operand], left_sel: Option<Operand>, right_sel: Option<Operand>) -> SelectedArguments {
+        assert!(left.len() == right.len() && !left.is_empty() && left.len() <= SMI_PERM_MAX_WIDTH as usize, "1 ..= SMI_PERM_MAX_WIDTH members a side");
+        assert!(self.items.len() < SMI_ARGS_MAX as usize, "at most SMI_ARGS_MAX arguments");
+        let item = (SMI_ARG_PERM, left.iter().map(|o| self.var(*o)).collect(), right.iter().map(|o| self.var(*o)).collect(), 0, self.sel(left_sel), self.sel(right_sel));
+        self.items.push(item);
+        self
+    }
+    pub fn lookup(mut self, lookup: &[Operand], table: &[Operand], mult_col: u32, sel: Option<Operand>, table_sel: Option<Operand>) -> SelectedArguments {
+        assert!(lookup.len() == table.len() && !lookup.is_empty() && lookup.len() <= SMI_LOOKUP_MAX_WIDTH as usize, "1 ..= SMI_LOOKUP_MAX_WIDTH members a side");
+        assert!(self.items.len() < SMI_ARGS_MAX as usize, "at most SMI_ARGS_MAX arguments");
+        let item = (SMI_ARG_LOOKUP, lookup.iter().map(|o| self.var(*o)).collect(), table.iter().map(|o| self.var(*o)).collect(), mult_col, self.sel(sel), self.sel(table_sel));
+        self.items.push(item);
+        self
+    }
+    fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
+        let raw: Vec<smi_air_xarg> = self.items.iter().map(|(kind, a, b, m, sa, sb)| smi_air_xarg { kind: *kind, width: a.len() as u32, mult_col: *m, reserved0: 0, a_var: a.as_ptr(), b_var: b.as_ptr(), a_sel: *sa, b_sel: *sb }).collect();
+        let list = smi_air_xargs { count: raw.len() as u32, reserved0: 0, arg: raw.as_ptr() };
+        f(&list as *const smi_air_xargs as *const c_void)
+    }
+    /// `smi_air_plan_xargs` (host only): `(degree, FRI expansion factor)` of `air` with this list.
+    pub fn plan(&self, air: &Air, p: u64, cfg: &smi_stark_cfg) -> (u32, u64) {
+        let (mut d, mut e) = (0u32, 0u64);
+        let st = air.with_raw(|a| self.with_raw(|al| unsafe { smi_air_plan_xargs(p, cfg, a, al, &mut d, &mut e) }));
+        if st != SMI_OK {
+            panic!("{}: {}", status_text(st), unsafe { CStr::from_ptr(smi_air_last_error()) }.to_string_lossy());
+        }
+        (d, e)
+    }
+    /// `smi_dev_xargs_multiplicities`: the multiplicities of lookup argument `a` over the selected rows into `d_mult`.
+    pub fn multiplicities(&self, ctx: &Context, air: &Air, a: u32, d_trace_cols: *const u32, log_n: u32, d_mult: *mut u32) {
+        ctx.check(air.with_raw(|ar| self.with_raw(|al| unsafe {
+            smi_dev_xargs_multiplicities(ctx.raw, ar, al, a, d_trace_cols, self.n_cols, log_n, d_mult)
+        })));
+    }
+    /// `smi_dev_xargs_columns` -> the mask of the arguments that close.
+    pub fn columns(&self, ctx: &Context, air: &Air, d_trace_cols: *const u32, log_n: u32, challenges: &[u64; 8], d_c: *mut u32, c_stride: usize) -> u32 {
+        let mut closes = 0u32;
+        ctx.check(air.with_raw(|ar| self.with_raw(|al| unsafe {
+            smi_dev_xargs_columns(ctx.raw, ar, al, d_trace_cols, self.n_cols, log_n, challenges.as_ptr(), d_c, c_stride, &mut closes)
+        })));
+        closes
+    }
+    /// `smi_dev_air_compose_xargs`: the composition plus the 2 A auxiliary quotients of this list.
+    pub fn compose(&self, ctx: &Context, air: &Air, cfg: &smi_stark_cfg, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize,
+                   challenges: &[u64; 8], d_weights: *const u64, d_out: *mut u32, out_stride: usize) {
+        ctx.check(air.with_raw(|ar| self.with_raw(|al| unsafe {
+            smi_dev_air_compose_xargs(ctx.raw, cfg, ar, al, d_lde, stride, d_c_lde, c_stride, challenges.as_ptr(), d_weights, d_out, out_stride)
+        })));
+    }
+    /// `smi_dev_air_prove_xargs` -> (root_1 then root_2, proof bytes, closes).
+    pub fn prove(&self, ctx: &Context, air: &Air, cfg: &smi_stark_cfg, d_trace_cols: *const u32, grind_bits: u32) -> ([u8; 64], Vec<u8>, u32) {
+        let mut roots = [0u8; 64];
+        let (mut proof, mut len) = (std::ptr::null_mut::<u8>(), 0usize);
+        let mut closes = 0u32;
+        ctx.check(air.with_raw(|ar| self.with_raw(|al| unsafe {
+            smi_dev_air_prove_xargs(ctx.raw, cfg, ar, al, d_trace_cols, roots.as_mut_ptr(), &mut proof, &mut len, std::ptr::null_mut(), std::ptr::null_mut(), grind_bits, &mut closes)
+        })));
+        let bytes = unsafe { std::slice::from_raw_parts(proof, len) }.to_vec();
+        unsafe { smi_free(proof as *mut c_void) };
+        (roots, bytes, closes)
+    }
+    /// `smi_air_verify_xargs` -> `Ok(())` or the reason the proof is rejected.
+    pub fn verify(&self, ctx: &Context, air: &Air, cfg: &smi_stark_cfg, roots: &[u8; 64], proof: &[u8], grind_bits: u32) -> Result<(), String> {
+        let mut accept = 0 as c_int;
+        ctx.check(air.with_raw(|ar| self.with_raw(|al| unsafe {
+            smi_air_verify_xargs(ctx.raw, cfg, ar, al, roots.as_ptr(), proof.as_ptr(), proof.len(), &mut accept, grind_bits)
+        })));
+        if accept != 0 {
+            Ok(())
+        } else {
+            Err(unsafe { CStr::from_ptr(smi_last_error(ctx.raw)) }.to_string_lossy().into_owned())
+        }
     }
 }
 

@@ -716,7 +716,8 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
  *   smi_dev_air_check and a violated AIR.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_PERM_MAX_WIDTH; every
  *   column index < n_cols; log_n >= 1; everything smi_air_plan refuses.
- * Left out: more than one permutation per proof; periodic or next-row tuple members; a permutation together with a
+ * Left out: more than one permutation per proof; next-row tuple members (selectors and periodic members: "Argument list
+ *   with selectors and periodic members" below); a permutation together with a
  *   lookup ("Lookup argument" below); a column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
  *   as a second streaming kernel over the four coordinate columns).  Several arguments, and permutations together with
  *   lookups, are what "Argument list" below adds; these entry points stay at one. */
@@ -798,8 +799,8 @@ int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   not).  It does not refuse a wrong M or a missing lookup: *closes = 0 and the verifier rejects that proof.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_LOOKUP_MAX_WIDTH; every
  *   column index < n_cols; mult_col none of the tuple columns; log_n >= 1; everything smi_air_plan refuses.
- * Left out: several lookups, or several looked-up tuples sharing one table; selectors; periodic or next-row tuple
- *   members; a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
+ * Left out: several lookups, or several looked-up tuples sharing one table; next-row tuple members (selectors and
+ *   periodic members: "Argument list with selectors and periodic members" below); a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
  *   column-tree or smi_mgpu_* twin.  Several lookups, each with a multiplicity column of its own, and lookups together
  *   with permutations are what "Argument list" below adds; these entry points stay at one. */
 #define SMI_LOOKUP_MAX_WIDTH 8
@@ -872,7 +873,8 @@ int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
  *   rejects a proof with a column that does not.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): count in 1 .. SMI_ARGS_MAX; kind 0 or 1;
  *   every argument by its own section's limits, the reason naming the argument's index; everything smi_air_plan refuses.
- * Left out: selectors; periodic or next-row tuple members; several lookups sharing one multiplicity column; the auxiliary
+ * Left out: next-row tuple members; several lookups sharing one multiplicity column (selectors and periodic members are
+ *   what "Argument list with selectors and periodic members" below adds; these entry points stay as they are); the auxiliary
  *   quotients fused into the main composition launch; a column-tree or smi_mgpu_* twin; a wave-level scan. */
 #define SMI_ARGS_MAX 8
 #define SMI_ARG_PERM 0
@@ -917,6 +919,86 @@ int smi_dev_air_prove_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes);
 int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *args, const uint8_t *roots, const uint8_t *proof,
                         size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Argument list with selectors and periodic members ------------------------------------------
+ * The arguments of the three sections above fire on every row and read committed trace columns only.  A real trace looks an
+ * operand up only on the rows where an opcode flag is set, looks it up in a PUBLIC table (a range 0 .. 255, an opcode
+ * table) and relates "the selected rows of these columns" to "the selected rows of those".  This variant of "Argument list"
+ * gives every argument two optional selectors and lets tuple members and selectors be periodic columns of the AIR.  The
+ * entry points above are unchanged, byte for byte, and keep launching the kernels they launch.
+ *
+ * Operands.  An operand is a variable in the AIR's own numbering (W = n_cols, Q = n_periodic): var = c with c < W is trace
+ *   column c at this row, var = 2 W + j with j < Q periodic column j at this row.  The two next-row kinds (W <= var < 2 W,
+ *   var >= 2 W + Q) are refused.  On the trace the value V(r) is T[c][r] or v_j[r mod P_j]; on the evaluation coset V(x_i)
+ *   is lde[c][i] or pi_j(x_i), the extended periodic table read modulo its length P_j B exactly as the main composition
+ *   reads it ("AIR" above).
+ * Argument a.  kind, width m in 1 .. 8, the operand lists a_var[m] and b_var[m], the selectors a_sel and b_sel -- an operand
+ *   each, or SMI_ARG_NO_SELECTOR for the constant 1 -- and for a lookup mult_col, a trace column that is none of the
+ *   argument's trace operands and none of its selectors.  S_a, S_b are the selector values, M = T[mult_col];
+ *   f_L = gamma + sum_j alpha^j V_{a_var[j]}, f_R / f_T likewise with b_var.  All arguments share alpha and gamma.
+ * Permutation.  g_L = 1 + S_a (f_L - 1), g_R = 1 + S_b (f_R - 1);  z[0] = 1, z[r+1] = z[r] g_L(r) / g_R(r); the argument
+ *   closes iff z[n-1] g_L(n-1) / g_R(n-1) = 1.  Boundary quotient (z(x) - 1) / (x - tau); wrapping transition quotient
+ *   (z(w x) g_R(x) - z(x) g_L(x)) / (x^n - tau^n).  Degree contributed: 2 with no selector, 3 with one or two.
+ * Lookup.  s[0] = 0, s[r+1] = s[r] + S_a(r) / f_L(r) - M(r) S_b(r) / f_T(r); the argument closes iff the next step returns
+ *   to 0.  Boundary quotient s(x) / (x - tau); wrapping transition quotient
+ *   ((s(w x) - s(x)) f_L f_T - S_a f_T + M S_b f_L) / (x^n - tau^n), of degree 3 with or without selectors.
+ * What is proved.  The two identities above, rational or multiplicative.  With selectors that hold only 0 and 1 that is the
+ *   multiset statement (permutation) or the inclusion statement (lookup) over the SELECTED rows of either side.  Forcing a
+ *   trace selector to be 0 / 1 is the AIR's business (a transition or boundary constraint s^2 - s = 0 of the caller's); a
+ *   periodic selector is public, part of the statement, and needs no constraint.
+ * Degree.  d = max(d_air, the arguments' contributions); D and E follow as in smi_air_plan_args.
+ * Zero denominators.  A zero f_L or f_T of a lookup is SMI_ERR_NO_INVERSE on every row, selected or not; so is a zero g_R
+ *   of a permutation.  The key stays 16 row + 2 a + side, the smallest key is reported, the context stays usable.
+ * Transcript, second tree, weights, FRI, grinding, openings, proof layout, byte counts: exactly those of "Argument list".
+ *   Periodic columns stay outside the transcript, as everywhere.
+ * Verifier (host).  The order of checks of smi_air_verify_args and its sentences.  The 2 A auxiliary quotients are recomputed
+ *   at x_a and x_b from the opened rows in host F_q arithmetic; the periodic operands at those points come from the code
+ *   smi_air_verify_ext uses.  A proof checked under a list that differs in one selector, or in one member being periodic
+ *   instead of a trace column, is rejected on the composition.
+ * Anchor.  A list in which no argument has a selector or a periodic operand yields every byte of smi_dev_air_prove_args for
+ *   the same list; the roots, the columns and the codeword are equal too.
+ * Limits (SMI_ERR_BAD_ARG, the reason names the argument): those of "Argument list"; every operand a this-row variable;
+ *   mult_col < n_cols, none of the argument's trace operands, none of its selectors; everything smi_air_plan refuses.
+ * Left out: next-row tuple members; several lookups sharing one multiplicity column; a column-tree or smi_mgpu_* twin. */
+#define SMI_ARG_NO_SELECTOR 0xffffffffu
+typedef struct smi_air_xarg {
+    uint32_t kind;            /* SMI_ARG_PERM = 0, SMI_ARG_LOOKUP = 1              */
+    uint32_t width;           /* m, 1 .. 8                                          */
+    uint32_t mult_col;        /* a trace column; ignored for a permutation          */
+    uint32_t reserved0;       /* explicit padding, ignored                          */
+    const uint32_t *a_var;    /* left / lookup operands, m variables of this row    */
+    const uint32_t *b_var;    /* right / table operands                             */
+    uint32_t a_sel, b_sel;    /* an operand, or SMI_ARG_NO_SELECTOR                 */
+} smi_air_xarg;
+typedef struct smi_air_xargs {
+    uint32_t count;           /* A, 1 .. SMI_ARGS_MAX                               */
+    uint32_t reserved0;
+    const smi_air_xarg *arg;
+} smi_air_xargs;
+/* Host only (like smi_air_plan, which it runs first): validates the list against cfg and air and returns d and E.  `xargs`
+ * is a pointer to an smi_air_xargs, passed as the AIR is. */
+int smi_air_plan_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint64_t *fri_expansion);
+/* smi_dev_lookup_multiplicities for argument a of the list, which must be a lookup: d_mult (n residues, zeroed by the call)
+ * gets M.  Only table rows with S_b != 0 are inserted, only lookup rows with S_a != 0 are counted, M at an unselected table
+ * row is 0; SMI_ERR_LOOKUP_MISSING names the smallest SELECTED row whose tuple is in no selected table row.  Of air the
+ * periodic columns are read (periods <= n).  Two launches, every probe loop bounded by the table's size.  Synchronises. */
+int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air, const void *xargs, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                 uint32_t log_n, uint32_t *d_mult);
+/* smi_dev_args_columns under the recurrences above: three launches whatever A is -- a block launch of its own with the
+ * argument as the second grid dimension, then the scan and propagation launches of smi_dev_args_columns.  The raw periodic
+ * values go to the device first.  Access rules, *closes, the zero-denominator report as there. */
+int smi_dev_xargs_columns(smi_ctx *ctx, const void *air, const void *xargs, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n,
+                          const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes);
+/* smi_dev_air_compose_args with the quotients above: smi_dev_air_compose_ext, then ONE streaming launch that reads the
+ * periodic operands from the tables the main composition of the same call has built. */
+int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_lde, size_t stride,
+                              const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                              size_t out_stride);
+/* The prover: smi_dev_air_prove_args step by step (two host round trips, stage_ms {lde, commit, args, compose, fri, open}). */
+int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols, uint8_t *roots,
+                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes);
+int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                         size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

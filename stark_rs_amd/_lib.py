@@ -74,6 +74,21 @@ class AirArgs(C.Structure):
     _fields_ = [("count", C.c_uint32), ("reserved0", C.c_uint32), ("arg", C.POINTER(AirArg))]
 
 
+class AirXArg(C.Structure):
+    """smi_air_xarg (include/stark_mi.h, "Argument list with selectors and periodic members"): operands are variables of the
+    AIR (trace column c, or 2 W + j for periodic column j); a selector is an operand or NO_SELECTOR"""
+    _fields_ = [("kind", C.c_uint32), ("width", C.c_uint32), ("mult_col", C.c_uint32), ("reserved0", C.c_uint32), ("a_var", u32p), ("b_var", u32p),
+                ("a_sel", C.c_uint32), ("b_sel", C.c_uint32)]
+
+
+class AirXArgs(C.Structure):
+    """smi_air_xargs; mirror.Air.flatten fills one when some argument of the list has a selector or a periodic member"""
+    _fields_ = [("count", C.c_uint32), ("reserved0", C.c_uint32), ("arg", C.POINTER(AirXArg))]
+
+
+NO_SELECTOR = 0xffffffff   # SMI_ARG_NO_SELECTOR
+
+
 def build(force=False):
     """Compile libstarkmi.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
@@ -233,6 +248,13 @@ def lib():
         "smi_dev_air_prove_args": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
                                          C.c_uint32, u32p]),
         "smi_air_verify_args": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirArgs), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_xargs": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u32p, u64p]),
+        "smi_dev_xargs_multiplicities": (i32, [vp, C.POINTER(Air), C.POINTER(AirXArgs), C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]),
+        "smi_dev_xargs_columns": (i32, [vp, C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_uint32, C.c_uint32, u64p, vp, sz, u32p]),
+        "smi_dev_air_compose_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, sz, vp, sz, u64p, vp, vp, sz]),
+        "smi_dev_air_prove_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
+                                          C.c_uint32, u32p]),
+        "smi_air_verify_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -26,6 +26,7 @@
 #include "mgpu_core.h"
 #include "lookup_core.h"
 #include "perm_core.h"
+#include "xargs_core.h"
 
 template <int P>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
@@ -278,6 +279,10 @@ int smi_air_plan_lookup(uint64_t p, const smi_stark_cfg *cfg, const void *air, c
 int smi_air_plan_args(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *args, uint32_t *degree, uint64_t *fri_expansion) {
     g_air_err.clear();
     return args_plan(p, cfg, (const smi_air *)air, (const smi_air_args *)args, degree, fri_expansion, &g_air_err);
+}
+int smi_air_plan_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint64_t *fri_expansion) {
+    g_air_err.clear();
+    return xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, degree, fri_expansion, &g_air_err);
 }
 // what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }

@@ -151,12 +151,28 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_args_compose_kernel(ArgsDev AD
     }
 }
 
+static_assert(SMI_ARGS_MAX == 8, "ArgsFlags (internal.h) holds SMI_ARGS_MAX totals");
+// the scan launch and the propagation launch of a column build whose block launch has filled d_c and d_agg
+int args_scan_propagate_enqueue(smi_ctx *ctx, const ArgsDev &AD, uint32_t A, uint64_t n, bool vec, uint32_t *d_c, size_t c_stride, uint32_t *d_agg,
+                                ArgsFlags *d_fl) {
+    const uint64_t nb = (n + PERM_TILE - 1) / PERM_TILE;
+    const Fp F = ctx->fs.F;
+    const dim3 grid((uint32_t)nb, A);
+    {
+        ProfScope ps(ctx, "args_scan_kernel", 32.0 * A * (double)nb);
+        args_scan_kernel<<<A, PERM_BLOCK, 0, ctx->stream>>>(AD, F, (uint32_t)nb, d_agg, &d_fl->total[0][0]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, "args_propagate_kernel", 32.0 * A * (double)n);
+        if (vec) args_propagate_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(AD, F, n, d_c, c_stride, d_agg);
+        else args_propagate_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(AD, F, n, d_c, c_stride, d_agg);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return SMI_OK;
+}
+
 namespace {
-struct ArgsFlags {   // as the column build leaves them on the device: the totals (plain), the smallest key 16 row + 2 a + side
-    uint32_t total[SMI_ARGS_MAX][4];
-    unsigned long long first;
-    unsigned long long pad;
-};
 // bytes of device scratch the column build wants: A runs of workgroup aggregates | the flags
 size_t args_columns_tmp_bytes(uint32_t A, uint64_t n) { return (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16 + sizeof(ArgsFlags); }
 const ArgsFlags *args_columns_flags(const uint8_t *d_tmp, uint32_t A, uint32_t log_n) {
@@ -180,18 +196,7 @@ int args_columns_enqueue(smi_ctx *ctx, const ArgsDev &AD, const uint32_t *d_trac
         else args_block_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(AD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
         HIP_TRY(ctx, hipGetLastError());
     }
-    {
-        ProfScope ps(ctx, "args_scan_kernel", 32.0 * AD.A * (double)nb);
-        args_scan_kernel<<<AD.A, PERM_BLOCK, 0, ctx->stream>>>(AD, F, (uint32_t)nb, d_agg, &d_fl->total[0][0]);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    {
-        ProfScope ps(ctx, "args_propagate_kernel", 32.0 * AD.A * (double)n);
-        if (vec) args_propagate_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(AD, F, n, d_c, c_stride, d_agg);
-        else args_propagate_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(AD, F, n, d_c, c_stride, d_agg);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return SMI_OK;
+    return args_scan_propagate_enqueue(ctx, AD, AD.A, n, vec, d_c, c_stride, d_agg, d_fl);
 }
 
 // the verdicts of a finished column build (fl: the flags copied to the host)

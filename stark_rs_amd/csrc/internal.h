@@ -332,4 +332,14 @@ int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uin
                            size_t out_stride);
 int launch_air_row_open(smi_ctx *ctx, const uint32_t *d_cols, size_t stride, uint32_t W, const uint8_t *d_nodes, uint32_t depth, const uint64_t *d_top,
                         uint32_t t, uint32_t R, uint64_t B, uint8_t *d_out);
+// args.hip, for xargs.hip: the scan and propagation launches of the column build (they read kind and g_m of AD only), and
+// the flags the build leaves on the device
+struct ArgsDev;
+struct ArgsFlags {   // the totals (plain), the smallest key 16 row + 2 a + side
+    uint32_t total[8][4];
+    unsigned long long first;
+    unsigned long long pad;
+};
+int args_scan_propagate_enqueue(smi_ctx *ctx, const ArgsDev &AD, uint32_t A, uint64_t n, bool vec, uint32_t *d_c, size_t c_stride, uint32_t *d_agg,
+                                ArgsFlags *d_fl);
 int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint32_t *d_vals, uint32_t *d_tab);

@@ -31,6 +31,7 @@
 
 #include "air_core.h"
 #include "args_core.h"
+#include "xargs_core.h"
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
@@ -652,6 +653,66 @@ struct LookupAux {
     }
 };
 
+// the two auxiliary quotients of one argument of a list with selectors and periodic members (include/stark_mi.h, "Argument
+// list with selectors and periodic members") at one point, in host F_q arithmetic: what smi_dev_air_compose_xargs adds for it
+struct XArgAux {
+    uint32_t p, g, W;
+    const smi_air_xarg *arg;
+    uint32_t gamma[4], wb[4], wt[4];
+    std::vector<std::vector<uint32_t>> apow;   // alpha^j, j < width
+    uint64_t n, tau, tau_n;
+    XArgAux(const smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air_xarg *arg_, const uint64_t ch[8], const uint64_t *w_bound, const uint64_t *w_trans)
+        : p(ctx->fs.F.p), g(ctx->fs.g), W(cfg->n_cols), arg(arg_), apow(arg_->width, std::vector<uint32_t>(4, 0)), n(1ull << cfg->log_n),
+          tau(cfg->trace_offset), tau_n(powm(cfg->trace_offset, 1ull << cfg->log_n, ctx->fs.F.p)) {
+        uint32_t alpha[4], pw[4] = {1, 0, 0, 0};
+        perm_challenges(p, ch, alpha, gamma);
+        for (int e = 0; e < 4; e++) wb[e] = (uint32_t)(w_bound[e] % p), wt[e] = (uint32_t)(w_trans[e] % p);
+        for (uint32_t j = 0; j < arg->width; j++) {
+            apow[j].assign(pw, pw + 4);
+            ext_mul_host(p, g, pw, alpha, pw);
+        }
+    }
+    // operand v at the point: the opened row cur, or the periodic values per[0 .. Q) of this row
+    uint64_t val(uint32_t v, const uint64_t *cur, const uint32_t *per) const { return v == SMI_ARG_NO_SELECTOR ? 1 : v < W ? cur[v] : per[v - 2 * W]; }
+    // got += w_b bq + w_t tq over the row cur, the periodic values per and the column's coordinates cc (this row), cn (next)
+    void add(uint64_t x, const uint64_t *cur, const uint32_t *per, const uint64_t *cc, const uint64_t *cn, uint32_t got[4]) const {
+        uint32_t fl[4], fr[4], c0[4], c1[4], a[4], b[4], bq[4], tq[4], u[4], v[4];
+        for (int e = 0; e < 4; e++) fl[e] = fr[e] = gamma[e], c0[e] = (uint32_t)cc[e], c1[e] = (uint32_t)cn[e];
+        for (uint32_t j = 0; j < arg->width; j++)
+            for (int e = 0; e < 4; e++) {
+                fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], val(arg->a_var[j], cur, per), p)) % p);
+                fr[e] = (uint32_t)((fr[e] + mulm(apow[j][e], val(arg->b_var[j], cur, per), p)) % p);
+            }
+        const uint64_t sa = val(arg->a_sel, cur, per), sb = val(arg->b_sel, cur, per);
+        const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
+        if (arg->kind == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
+            for (int e = 0; e < 4; e++) {
+                fl[e] = (uint32_t)(((e ? 0 : 1) + mulm(sa, (fl[e] + (uint64_t)p - (e ? 0 : 1)) % p, p)) % p);
+                fr[e] = (uint32_t)(((e ? 0 : 1) + mulm(sb, (fr[e] + (uint64_t)p - (e ? 0 : 1)) % p, p)) % p);
+            }
+            ext_mul_host(p, g, c1, fr, a);
+            ext_mul_host(p, g, c0, fl, b);
+            for (int e = 0; e < 4; e++) {
+                tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - b[e]) % p, izt, p);
+                bq[e] = (uint32_t)mulm(e ? c0[e] : (c0[0] + (uint64_t)p - 1) % p, ixt, p);
+            }
+        } else {   // (s' - s) f_L f_T - S_a f_T + M S_b f_L
+            uint32_t ds[4], lt[4];
+            for (int e = 0; e < 4; e++) ds[e] = (uint32_t)((c1[e] + (uint64_t)p - c0[e]) % p);
+            ext_mul_host(p, g, fl, fr, lt);
+            ext_mul_host(p, g, ds, lt, a);
+            const uint64_t M = mulm(cur[arg->mult_col], sb, p);
+            for (int e = 0; e < 4; e++) {
+                tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - mulm(sa, fr[e], p) + mulm(M, fl[e], p)) % p, izt, p);
+                bq[e] = (uint32_t)mulm(c0[e], ixt, p);
+            }
+        }
+        ext_mul_host(p, g, bq, wb, u);
+        ext_mul_host(p, g, tq, wt, v);
+        for (int e = 0; e < 4; e++) got[e] = (uint32_t)(((uint64_t)got[e] + u[e] + v[e]) % p);
+    }
+};
+
 // What the AIR verifiers differ in (include/stark_mi.h: "AIR", "AIR over one row-committed tree", "Extension FRI",
 // "Grinding", "Permutation argument").
 //   by_rows : one tree over the rows (one path per position, leaves from the bytes) instead of W column trees
@@ -665,13 +726,16 @@ struct LookupAux {
 //             its own sentences
 //   args    : the argument list ("Argument list"): the second section's rows are 4 A values wide, argument a at the
 //             coordinates 4 a .. 4 a + 3 with the weights W + K + 2 a and W + K + 2 a + 1, PermAux or LookupAux once per
-//             argument, its own sentences; at most one of perm, lookup and args is set
+//             argument, its own sentences
+//   xargs   : the argument list with selectors and periodic members: the layout, transcript and sentences of args, XArgAux once
+//             per argument over the opened row and the periodic operands at the point; at most one of the four is set
 struct AirVariant {
     bool by_rows, over_ext;
     int grind;
     const smi_air_perm *perm;
     const smi_air_lookup *lookup;
     const smi_air_args *args = nullptr;
+    const smi_air_xargs *xargs = nullptr;
 };
 // One verifier for them all: the weights and FRI's seed from the variant's transcript, Fri::verify at expansion factor E,
 // then the openings -- length, records, every path against its root, and the composition codeword recomputed at x_a and
@@ -680,10 +744,11 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                            int *accept, const AirVariant &var) {
     std::string why;
     uint64_t E = 0;
-    const bool has_aux = var.perm || var.lookup || var.args;   // auxiliary columns: a second root, a second section, two more quotients each
+    const bool has_aux = var.perm || var.lookup || var.args || var.xargs;   // auxiliary columns: a second root, a second section, two more quotients each
     const int vrc = var.perm     ? perm_plan(ctx->fs.F.p, cfg, air, var.perm, nullptr, &E, &why)
                     : var.lookup ? lookup_plan(ctx->fs.F.p, cfg, air, var.lookup, nullptr, &E, &why)
                     : var.args   ? args_plan(ctx->fs.F.p, cfg, air, var.args, nullptr, &E, &why)
+                    : var.xargs  ? xargs_plan(ctx->fs.F.p, cfg, air, var.xargs, nullptr, &E, &why)
                                  : air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
     if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
     const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
@@ -694,7 +759,7 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     std::vector<uint64_t> ch, weights;   // ch: alpha and gamma of the auxiliary column
     if (has_aux) {
         transcript_perm_challenges(tr, roots, &ch);
-        if (var.args) transcript_args_weights(tr, roots + 32, W, K, var.args->count, &weights);
+        if (var.args || var.xargs) transcript_args_weights(tr, roots + 32, W, K, var.args ? var.args->count : var.xargs->count, &weights);
         else transcript_perm_weights(tr, roots + 32, W, K, &weights);
     } else if (var.over_ext) {
         transcript_ext(tr, roots, W, K, &weights);
@@ -712,9 +777,9 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
     *accept = 0;
     // ---- the opening sections: rows of W values under root_1 (or the column roots); with an auxiliary column, rows of 4
     // values under root_2
-    const OpeningWords &say = var.perm ? PERM_WORDS : var.lookup ? LOOKUP_WORDS : var.args ? ARGS_WORDS : AIR_WORDS;
+    const OpeningWords &say = var.perm ? PERM_WORDS : var.lookup ? LOOKUP_WORDS : (var.args || var.xargs) ? ARGS_WORDS : AIR_WORDS;
     const size_t R = (K || has_aux) ? 4 : 2, m = R * t, prec = 9 + 32 * (size_t)logN, n_sec = has_aux ? 2 : 1;
-    const uint32_t AW = var.args ? 4 * var.args->count : 4;   // values in a row of the second section
+    const uint32_t AW = var.args ? 4 * var.args->count : var.xargs ? 4 * var.xargs->count : 4;   // values in a row of the second section
     const uint32_t widths[2] = {W, AW}, NE = var.over_ext ? 4 : 1;
     const size_t sec_len[2] = {m * (9 + 8 * (size_t)W) + (var.by_rows ? 1 : W) * m * prec, has_aux ? m * (9 + 8 * (size_t)AW) + m * prec : 0};
     if (proof_len - end != sec_len[0] + sec_len[1]) return reject(ctx, accept, say.length);
@@ -768,6 +833,9 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
             a_laux[a].emplace(ctx, cfg, &a_lookup[a], ch.data(), wb, wt);
         }
     }
+    std::vector<XArgAux> x_aux;
+    for (uint32_t a = 0; var.xargs && a < var.xargs->count; a++)
+        x_aux.emplace_back(ctx, cfg, &var.xargs->arg[a], ch.data(), &weights[4 * (W + K + 2 * a)], &weights[4 * (W + K + 2 * a + 1)]);
     for (uint64_t s = 0; s < t; s++)
         for (size_t k = 0; k < 2; k++) {
             const uint64_t i = pos[R * s + k];
@@ -793,6 +861,8 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                 if (a_paux[a]) a_paux[a]->add(x, cur, cc, cn, got);
                 else a_laux[a]->add(x, cur, cc, cn, got);
             }
+            for (size_t a = 0; a < x_aux.size(); a++)
+                x_aux[a].add(x, cur, Q ? &per[(2 * s + k) * 2 * Q] : nullptr, &rows[1][(R * s + k) * AW + 4 * a], &rows[1][(R * s + k + 2) * AW + 4 * a], got);
             for (uint32_t e = 0; e < NE; e++)
                 if (got[e] != ab[(2 * s + k) * NE + e] % p) return reject(ctx, accept, say.composition);
         }
@@ -873,4 +943,17 @@ int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     SMI_TRY(ext_field_check(ctx));
     return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
                                   AirVariant{true, true, (int)grind_bits, nullptr, nullptr, (const smi_air_args *)args}));
+}
+
+// Verifier of smi_dev_air_prove_xargs (include/stark_mi.h, "Argument list with selectors and periodic members"):
+// smi_air_verify_args's checks with the quotients of that section (AirVariant::xargs).
+int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                         size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !xargs || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
+                                  AirVariant{true, true, (int)grind_bits, nullptr, nullptr, nullptr, (const smi_air_xargs *)xargs}));
 }

@@ -1,0 +1,470 @@
+// xargs.hip -- the argument list with selectors and periodic members (include/stark_mi.h, "Argument list with selectors and
+// periodic members"): the multiplicity helper over operands, the A auxiliary columns, the 2 A auxiliary quotients and the
+// prover.  The lane bodies are xargs_core.h over args_core.h, shared with the CPU emulator (emu_xargs.cpp); the verifier is
+// in verify.hip.  The entry points of args.hip are untouched and keep their kernels.
+//
+// The column build is args.hip's trio of launches with a block launch of its own:
+//   xargs_block_kernel     grid (workgroups of rows, A), args_block_kernel with an operand loader: a trace operand is one
+//                          16-byte load, a periodic operand four values v_j[(row0 + q) mod P_j] of the raw periodic values
+//                          (one 16-byte load when P_j >= 4: row0 is a multiple of 4, so it cannot straddle the wrap; word by
+//                          word when P_j is 1 or 2); the selectors are applied around perm_lane_ratios, a lookup goes
+//                          through xlookup_lane_deltas.  One F_q inversion per lane, as there.
+//   args_scan_kernel, args_propagate_kernel   unchanged: they read kind[a] and nothing of the tuples.
+// air_xargs_compose_kernel has the shape of air_args_compose_kernel; a periodic operand is read at the lane's four points
+// from the extended tables the main composition of the same call has built (AirDev::ptab), modulo L_j = P_j B.
+// The helper is lookup.hip's two launches with rows that are not selected left out.
+#include <string>
+#include <vector>
+
+#include "air_core.h"
+#include "hash_core.h"
+#include "internal.h"
+#include "mgpu_core.h"
+#include "row4_dev.h"
+#include "xargs_core.h"
+
+namespace {
+// args_wg_scan of args.hip: the workgroup scan of args_core.h between barriers
+__device__ __forceinline__ Fq xargs_wg_scan(bool perm, Fq v, uint32_t (*sc)[4][PERM_BLOCK], uint32_t tid, uint32_t g_m, const Fp &F, Fq *total) {
+    __syncthreads();   // the buffers of the scan before are consumed
+#pragma unroll
+    for (int e = 0; e < 4; e++) sc[0][e][tid] = v.c[e];
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t off = 1; off < PERM_BLOCK; off <<= 1) {
+        args_scan_step(perm, sc[cur], sc[cur ^ 1], tid, off, g_m, F);
+        __syncthreads();
+        cur ^= 1;
+    }
+    *total = perm_scan_at(sc[cur], PERM_BLOCK - 1);
+    return tid ? perm_scan_at(sc[cur], tid - 1) : args_identity(perm, F);
+}
+
+struct XDevAtomics {   // DevAtomics of lookup.hip
+    __device__ __forceinline__ uint32_t cas(uint32_t *a, uint32_t expect, uint32_t v) const { return atomicCAS(a, expect, v); }
+    __device__ __forceinline__ void min(uint32_t *a, uint32_t v) const { atomicMin(a, v); }
+    // Lanes of a wave that arrive here together and count into the same word send ONE atomic with their sum.  Each trip
+    // retires the first lane still here and every lane with its address: at most 64 trips, and no lane waits for a lane that
+    // is not in the trip.
+    __device__ __forceinline__ void add(uint32_t *a, uint32_t v) const {
+        const uint64_t mine = (uint64_t)(uintptr_t)a;
+        for (int trip = 0; trip < 64; trip++) {
+            const uint32_t lead_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(mine >> 32)), lead_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)mine);
+            const uint64_t lead = ((uint64_t)lead_hi << 32) | lead_lo;
+            const uint64_t peers = __ballot(mine == lead);
+            if (mine == lead) {
+                if ((uint32_t)__lane_id() == (uint32_t)__ffsll((long long)peers) - 1) atomicAdd(a, v * (uint32_t)__popcll(peers));
+                return;
+            }
+        }
+    }
+};
+struct XHelperFlags {   // the first missing selected row, a probe that ran out
+    unsigned long long first;
+    uint32_t exhausted, pad;
+};
+}  // namespace
+
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_insert_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *tab,
+                                                                   uint32_t cap, XHelperFlags *fl) {
+    const uint64_t t = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    if (!xlookup_insert_lane(XD, a, trace, n, tab, cap, (uint32_t)t, XDevAtomics{})) atomicOr(&fl->exhausted, 1u);
+}
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_count_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n,
+                                                                  const uint32_t *__restrict__ tab, uint32_t cap, uint32_t *mult, XHelperFlags *fl) {
+    const uint64_t r = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
+    if (r >= n) return;
+    const int got = xlookup_count_lane(XD, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{});
+    if (got == 1) atomicMin(&fl->first, (unsigned long long)r);
+    if (got == 2) atomicOr(&fl->exhausted, 1u);
+}
+
+// c: 4 A coordinate columns c_stride apart; block_agg: A runs of nb aggregates (four words each); first: the smallest key
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_block_kernel(XArgsDev XD, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *__restrict__ c,
+                                                                  size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first) {
+    __shared__ uint32_t sc[2][4][PERM_BLOCK];
+    const uint32_t tid = threadIdx.x, a = blockIdx.y;
+    const bool perm = XD.kind[a] == SMI_ARG_PERM;
+    const uint64_t row0 = ((uint64_t)blockIdx.x * PERM_BLOCK + tid) * PERM_ROWS;
+    Fq pl[PERM_ROWS], agg;
+    uint64_t key;
+    xargs_lane_column(
+        XD, a, F, row0, n,
+        [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
+            if (row0 >= n) {
+                v[0] = v[1] = v[2] = v[3] = 0u;
+            } else if (xop_periodic(op)) {
+                const uint32_t j = op & 0xffu, lp = XD.plog[j];
+                // P_j >= 4 and row0 a multiple of 4: the four values are consecutive and 16-byte aligned (pfirst[j] is a multiple of P_j)
+                if (VEC && lp >= 2) perm_load4<true>(XD.pvals + XD.pfirst[j], row0 & ((1ull << lp) - 1), 1ull << lp, v);
+                else xargs_periodic_rows(XD, j, row0, v);
+            } else {
+                perm_load4<VEC>(trace + (uint64_t)op * n, row0, n, v);
+            }
+        },
+        pl, &agg, &key);
+    if (key != ~0ull) atomicMin(first, (unsigned long long)key);
+    Fq total;
+    const Fq excl = xargs_wg_scan(perm, agg, sc, tid, XD.g_m, F, &total);
+    if (!tid) *(uint4 *)(block_agg + 4 * ((uint64_t)a * gridDim.x + blockIdx.x)) = make_uint4(total.c[0], total.c[1], total.c[2], total.c[3]);
+    if (row0 >= n) return;
+    uint32_t o[4][PERM_ROWS];
+#pragma unroll
+    for (int q = 0; q < PERM_ROWS; q++) {
+        const Fq w = args_combine(perm, pl[q], excl, XD.g_m, F);
+#pragma unroll
+        for (int e = 0; e < 4; e++) o[e][q] = w.c[e];
+    }
+    uint32_t *ca = c + 4 * (uint64_t)a * c_stride;
+#pragma unroll
+    for (int e = 0; e < 4; e++) perm_store4<VEC>(ca + e * c_stride, row0, n, o[e]);
+}
+
+// out (four coordinate columns, the composition of the main AIR) += the 2 A auxiliary quotients under w (8 A coordinates).
+// plog / pofs / ptab: AirDev's periodic tables on the device.
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
+                                                                        uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
+                                                                        const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
+                                                                        const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl,
+                                                                        size_t c_stride, const uint64_t *__restrict__ w, uint32_t *__restrict__ out,
+                                                                        size_t out_stride) {
+    const uint64_t groups = N / PERM_ROWS, gid = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x, gstep = (uint64_t)gridDim.x * PERM_BLOCK;
+    const uint32_t B = 1u << log_B;
+    uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * PERM_ROWS, F), F);
+    const uint32_t xstep_m = mont_pow(omega_m, gstep * PERM_ROWS, F);
+    for (uint64_t g = gid; g < groups; g += gstep) {
+        const uint64_t i0 = g * PERM_ROWS, i1 = (i0 + B) & (N - 1);   // B and N are multiples of 4: no access straddles the wrap
+        uint32_t acc[4][PERM_ROWS];
+#pragma unroll
+        for (int e = 0; e < 4; e++) perm_load4<VEC>(out + e * out_stride, i0, N, acc[e]);
+        xargs_compose_points(
+            XD, F, w, tau_m, izt_m, B, i0, x_m, omega_m,
+            [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
+                if (xop_periodic(op)) {
+                    // the table's length L_j = P_j B is a multiple of 4, as i0 is: four consecutive entries, none past the end
+                    uint64_t L, at;
+                    const uint32_t *table = xargs_table_at(plog, pofs, ptab, op & 0xffu, i0, &L, &at);
+                    perm_load4<VEC>(table, at, L, v);
+                } else {
+                    perm_load4<VEC>(lde + (uint64_t)op * stride, i0, N, v);
+                }
+            },
+            [&](uint32_t col, bool next, uint32_t v[4]) { perm_load4<VEC>(cl + (uint64_t)col * c_stride, next ? i1 : i0, N, v); }, acc);
+#pragma unroll
+        for (int e = 0; e < 4; e++) perm_store4<VEC>(out + e * out_stride, i0, N, acc[e]);
+        x_m = mont_mul(x_m, xstep_m, F);
+    }
+}
+
+namespace {
+static_assert(sizeof(XArgsDev) + 160 <= 4096, "the kernel arguments of every launch here stay inside 4 KB");
+
+size_t xargs_columns_tmp_bytes(uint32_t A, uint64_t n) { return (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16 + sizeof(ArgsFlags); }
+const ArgsFlags *xargs_columns_flags(const uint8_t *d_tmp, uint32_t A, uint64_t n) {
+    return (const ArgsFlags *)(d_tmp + (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16);
+}
+double xargs_cols_read(const XArgsDev &XD) {   // operands read per row, over the arguments
+    double cols = 0;
+    for (uint32_t a = 0; a < XD.A; a++)
+        cols += 2 * XD.m[a] + (XD.kind[a] == SMI_ARG_LOOKUP ? 1 : 0) + (XD.asel[a] != SMI_ARG_NO_SELECTOR) + (XD.bsel[a] != SMI_ARG_NO_SELECTOR);
+    return cols;
+}
+// what the scan and propagation launches read of a list
+ArgsDev xargs_scan_tables(const XArgsDev &XD) {
+    ArgsDev AD{};
+    AD.A = XD.A;
+    AD.g_m = XD.g_m;
+    for (uint32_t a = 0; a < XD.A; a++) AD.kind[a] = XD.kind[a], AD.m[a] = XD.m[a];
+    return AD;
+}
+
+// the three launches; d_tmp: xargs_columns_tmp_bytes(A, n) bytes, 16-byte aligned; XD.pvals on the device
+int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp) {
+    const uint64_t n = 1ull << log_n, nb = (n + PERM_TILE - 1) / PERM_TILE;
+    uint32_t *d_agg = (uint32_t *)d_tmp;
+    ArgsFlags *d_fl = (ArgsFlags *)(d_tmp + (size_t)XD.A * nb * 16);
+    const Fp F = ctx->fs.F;
+    const bool vec = n >= 4 && al16(d_trace) && al16(d_c) && !(c_stride & 3) && al16(XD.pvals);
+    const dim3 grid((uint32_t)nb, XD.A);
+    HIP_TRY(ctx, hipMemsetAsync(&d_fl->first, 0xff, 8, ctx->stream));
+    {
+        ProfScope ps(ctx, "xargs_block_kernel", (4.0 * xargs_cols_read(XD) + 16.0 * XD.A) * (double)n);
+        if (vec) xargs_block_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        else xargs_block_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return args_scan_propagate_enqueue(ctx, xargs_scan_tables(XD), XD.A, n, vec, d_c, c_stride, d_agg, d_fl);
+}
+
+// the verdicts of a finished column build (fl: the flags copied to the host)
+int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes) {
+    if (fl.first != ~0ull) {
+        const uint32_t a = (uint32_t)(fl.first & 15) >> 1;
+        const char *side = !(fl.first & 1) ? "f_L" : XD.kind[a] == SMI_ARG_PERM ? "g_R" : "f_T";
+        const std::string why = "xargs_columns: argument " + std::to_string(a) + ": " + side + " is zero in row " + std::to_string(fl.first >> 4) + ": no inverse";
+        return smi_fail(ctx, SMI_ERR_NO_INVERSE, why.c_str());
+    }
+    uint32_t mask = 0;
+    for (uint32_t a = 0; a < XD.A; a++) {
+        const uint32_t *t = fl.total[a];
+        if (t[0] == (XD.kind[a] == SMI_ARG_PERM ? 1u : 0u) && !(t[1] | t[2] | t[3])) mask |= 1u << a;
+    }
+    if (closes) *closes = mask;
+    return SMI_OK;
+}
+
+// H bound to the device blob and its periodic tables in place (air_periodic_tables, air_compose_ext_launch); d_w: the 8 A
+// coordinates behind the main weights
+int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+                          size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
+    const AirDev &A = H.dev;
+    const Fp F = ctx->fs.F;
+    // the periodic loader rests on this: every table's length P_j B is a multiple of 4 and every table starts at a multiple of
+    // its length (air_periodic_plan), so four entries from a multiple of 4 are consecutive, aligned and inside the table
+    if (A.log_B < 2) return smi_fail(ctx, SMI_ERR_EXPANSION_TOO_SMALL, "air_compose_xargs: log_blowup < 2");
+    for (uint32_t j = 0; j < A.Q; j++)
+        if (H.per.ofs[j] & ((1u << H.per.log_len[j]) - 1u)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose_xargs: a periodic table does not start at a multiple of its length");
+    const bool vec = al16(d_lde) && al16(d_cl) && al16(d_out) && !(stride & 3) && !(c_stride & 3) && !(out_stride & 3) && (!A.Q || al16(A.ptab));
+    const uint64_t groups = A.N / PERM_ROWS, want = (groups + PERM_BLOCK - 1) / PERM_BLOCK, cap = (uint64_t)ctx->num_cus * 8;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t tau_m = air_to_m(tau, F.p);
+    ProfScope ps(ctx, "air_xargs_compose_kernel", (4.0 * xargs_cols_read(XD) + 32.0 * XD.A + 32.0) * (double)A.N);
+    if (vec)
+        air_xargs_compose_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde,
+                                                                             stride, d_cl, c_stride, d_w, d_out, out_stride);
+    else
+        air_xargs_compose_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde,
+                                                                              stride, d_cl, c_stride, d_w, d_out, out_stride);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+
+// the checks every entry point without a cfg starts with
+int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uint32_t n_cols, uint32_t log_n) {
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "xargs: modulus must be < 2^30");
+    std::string why;
+    if (!n_cols || n_cols > 64) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs: 1..64 columns");
+    if (log_n < 1 || log_n > 27) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs: log_n must be in 1 .. 27");
+    const int prc = xargs_periodic_check(ctx->fs.F.p, air, log_n, &why);
+    if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
+    if (xargs_validate(xargs, n_cols, air->n_periodic, &why) != SMI_OK) return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
+    return SMI_OK;
+}
+}  // namespace
+
+int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                 uint32_t log_n, uint32_t *d_mult) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !air || !xargs || !d_trace_cols || !d_mult) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
+    if (a >= xargs->count) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities: no such argument");
+    if (xargs->arg[a].kind != SMI_ARG_LOOKUP) {
+        const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + " is a permutation: it has no multiplicities";
+        return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
+    }
+    const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
+    AirPeriodic per;
+    xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
+    XArgsDev XD;
+    const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the helper reads the operand lists alone
+    xargs_build(ctx->fs.F, ctx->fs.g, xargs, n_cols, air, per, no_challenges, &XD);
+    void *tmp = nullptr;   // the table | the flags | the periodic values
+    SMI_TRY(ctx_tmp(ctx, 3, cap * 4 + sizeof(XHelperFlags) + per.vals.size() * 4, &tmp));
+    uint32_t *d_tab = (uint32_t *)tmp;
+    XHelperFlags *d_fl = (XHelperFlags *)((uint8_t *)tmp + cap * 4);
+    uint32_t *d_pvals = (uint32_t *)((uint8_t *)tmp + cap * 4 + sizeof(XHelperFlags));
+    XD.pvals = d_pvals;
+    HIP_TRY(ctx, hipMemsetAsync(d_tab, 0xff, cap * 4 + 8, ctx->stream));   // every slot free; no row missing yet
+    HIP_TRY(ctx, hipMemsetAsync(&d_fl->exhausted, 0, 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_mult, 0, n * 4, ctx->stream));
+    if (!per.vals.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pvals, per.vals.data(), per.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t grid = (uint32_t)((n + PERM_BLOCK - 1) / PERM_BLOCK), m = XD.m[a];
+    {
+        ProfScope ps(ctx, "xargs_insert_kernel", (4.0 * m + 4.0) * (double)n);
+        xargs_insert_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, d_tab, (uint32_t)cap, d_fl);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, "xargs_count_kernel", (4.0 * 2 * m + 8.0) * (double)n);
+        xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, d_tab, (uint32_t)cap, d_mult, d_fl);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    XHelperFlags fl;
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, d_fl, sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // per.vals has been read by now
+    if (fl.exhausted) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities: a probe ran through the whole table");
+    if (fl.first != ~0ull) {
+        const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + ": the tuple of selected row " + std::to_string(fl.first) +
+                                " is in no selected table row";
+        return smi_fail(ctx, SMI_ERR_LOOKUP_MISSING, why.c_str());
+    }
+    return SMI_OK;
+}
+
+int smi_dev_xargs_columns(smi_ctx *ctx, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n,
+                          const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !air || !xargs || !d_trace_cols || !challenges || !d_c) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (closes) *closes = 0;
+    SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
+    const uint64_t n = 1ull << log_n;
+    if (c_stride < n) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_columns: c_stride < n");
+    AirPeriodic per;
+    xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
+    XArgsDev XD;
+    xargs_build(ctx->fs.F, ctx->fs.g, xargs, n_cols, air, per, challenges, &XD);
+    const size_t b_tmp = up16(xargs_columns_tmp_bytes(XD.A, n));
+    void *tmp = nullptr;   // the aggregates and flags | the periodic values
+    SMI_TRY(ctx_tmp(ctx, 3, b_tmp + per.vals.size() * 4, &tmp));
+    uint32_t *d_pvals = (uint32_t *)((uint8_t *)tmp + b_tmp);
+    XD.pvals = d_pvals;
+    if (!per.vals.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pvals, per.vals.data(), per.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(xargs_columns_enqueue(ctx, XD, d_trace_cols, log_n, d_c, c_stride, (uint8_t *)tmp));
+    ArgsFlags fl;
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags((const uint8_t *)tmp, XD.A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return xargs_columns_verdict(ctx, XD, fl, closes);
+}
+
+int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_lde, size_t stride,
+                              const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                              size_t out_stride) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !cfg || !air || !xargs || !d_lde || !d_c_lde || !challenges || !d_weights || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    AirHost H;
+    SMI_TRY(air_host_tables(ctx, cfg, air, &H, nullptr));
+    SMI_TRY(xargs_args(ctx, air, xargs, cfg->n_cols, cfg->log_n));
+    if (stride < H.dev.N || out_stride < H.dev.N || c_stride < H.dev.N)
+        return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose_xargs: stride < N, c_stride < N or out_stride < N");
+    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
+    void *base = nullptr;   // tables | grouped values | blob
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
+    SMI_TRY(air_compose_ext_launch(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride));
+    XArgsDev XD;
+    xargs_build(ctx->fs.F, ctx->fs.g, xargs, cfg->n_cols, air, H.per, challenges, &XD);
+    const uint32_t W = cfg->n_cols, K = air->n_constraints;
+    return xargs_compose_enqueue(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride);
+}
+
+int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint8_t *roots_out,
+                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (closes) *closes = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    AirHost H;
+    uint64_t E = 0;
+    SMI_TRY(air_host_tables(ctx, cfg, air, &H, &E));   // E of the AIR alone; the plan below counts the auxiliary transitions in
+    SMI_TRY(xargs_args(ctx, air, xargs, cfg->n_cols, cfg->log_n));
+    {
+        std::string why;
+        const int rc = xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &E, &why);
+        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    }
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup, A = xargs->count;
+    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
+    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the second tree
+    SMI_TRY(arena_reset(ctx));
+    struct Events {   // destroyed on every return path
+        hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs;
+    const bool timed = stage_ms != nullptr;
+    if (timed)
+        for (int i = 0; i < 7; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+
+    const size_t tree_bytes = 2 * N * 32;
+    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
+    uint32_t *d_c = (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4);
+    uint32_t *d_cl = (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4);
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
+    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
+    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes);
+    uint8_t *d_atmp = (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_bytes(A, n));
+    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
+    if (H.dev.Q) {
+        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
+        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
+    }
+    if (!d_lde || !d_c || !d_cl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_atmp || (H.dev.Q && (!d_ptab || !d_pvals)))
+        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_xargs: device memory");
+    mark(0);
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
+    mark(1);
+    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
+    mark(2);
+    // first round trip: root_1 -> alpha, gamma
+    uint8_t roots[64];
+    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root; d_pvals: the raw values the column build reads
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    Transcript tr;
+    std::vector<uint64_t> ch, weights;   // 8 challenges; 4 NW weights
+    transcript_perm_challenges(tr, roots, &ch);
+    XArgsDev XD;
+    xargs_build(ctx->fs.F, ctx->fs.g, xargs, W, air, H.per, ch.data(), &XD);
+    XD.pvals = d_pvals;
+    SMI_TRY(xargs_columns_enqueue(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
+    SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
+    SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
+    mark(3);
+    // second round trip: root_2 (and the columns' verdicts) -> the weights and FRI's seed
+    ArgsFlags fl;
+    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SMI_TRY(xargs_columns_verdict(ctx, XD, fl, closes));
+    transcript_args_weights(tr, roots + 32, W, K, A, &weights);
+    const FsSeed seed = tr.seed();
+    if (roots_out) memcpy(roots_out, roots, 64);
+    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
+    SMI_TRY(xargs_compose_enqueue(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
+    mark(4);
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
+    FriExtResult xres;
+    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
+    std::vector<uint8_t> &bytes = xres.proof;
+    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    mark(5);
+    if (cfg->num_colinearity_tests) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
+        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R);
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2);
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_xargs: row openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
+        SMI_TRY(launch_air_row_open(ctx, d_cl, N, CW, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
+        const size_t at = bytes.size();
+        bytes.resize(at + ob1 + ob2);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    mark(6);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed)
+        for (int i = 0; i < 6; i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    return smi_proof_out(ctx, bytes, proof, proof_len);
+}

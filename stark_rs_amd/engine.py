@@ -500,6 +500,8 @@ class Engine:
         """smi_air_plan -> (degree d, FRI expansion factor E); raises with the limit that was broken"""
         a = self._air(air)
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, trace_offset, lde_offset)
+        if self._xargs(a) is not None:   # smi_air_plan_xargs: a permutation with a selector counts 3
+            return air_plan_xargs(self.p, a, a.xargs, cfg)
         if self._args(a) is not None:   # smi_air_plan_args: d = max(d_air, 2 with a permutation, 3 with a lookup)
             return air_plan_args(self.p, a, a.args, cfg)
         if self._perm(a) is not None:   # smi_air_plan_perm: d = max(d_air, 2)
@@ -523,9 +525,30 @@ class Engine:
         """the _lib.AirArgs a flattened AIR carries (mirror.Air.add_permutation / add_lookup), or None"""
         return getattr(air, "args", None)
 
+    @staticmethod
+    def _xargs(air):
+        """the _lib.AirXArgs a flattened AIR carries (a list with a selector or a periodic member), or None"""
+        return getattr(air, "xargs", None)
+
+    def dev_args_multiplicities(self, air, a, d_trace_cols, n_cols, log_n, d_mult):
+        """the multiplicities of lookup argument a of air's list into d_mult (n device words): smi_dev_xargs_multiplicities for
+        a list with selectors or periodic members -- only selected rows are inserted and counted --, smi_dev_lookup_multiplicities
+        otherwise.  StarkMiError naming the smallest (selected) row whose tuple is in no (selected) table row."""
+        f = self._air(air)
+        if self._xargs(f) is not None:
+            self._ck_perm(self.L.smi_dev_xargs_multiplicities(self.h, C.byref(f), C.byref(f.xargs), a, vp(d_trace_cols), n_cols, log_n, vp(d_mult)))
+            return
+        if self._args(f) is None:
+            raise ValueError("dev_args_multiplicities: the AIR has no argument list (mirror.Air.add_permutation / add_lookup)")
+        if not 0 <= a < f.args.count or f.args.arg[a].kind != 1:
+            raise ValueError(f"dev_args_multiplicities: argument {a} is not a lookup of the list")
+        g = f.args.arg[a]
+        one = _lib.AirLookup(g.width, g.mult_col, g.a_col, g.b_col)
+        self._ck_perm(self.L.smi_dev_lookup_multiplicities(self.h, C.byref(one), vp(d_trace_cols), n_cols, log_n, vp(d_mult)))
+
     def _args_of(self, air, who):
         a = self._air(air)
-        if self._args(a) is None:
+        if self._args(a) is None and self._xargs(a) is None:
             raise ValueError(f"{who}: the AIR has no argument list (mirror.Air.add_permutation / add_lookup)")
         return a
 
@@ -536,6 +559,10 @@ class Engine:
         a = self._args_of(air, "dev_args_columns")
         ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
         closes = C.c_uint32()
+        if self._xargs(a) is not None:   # selectors or periodic members: smi_dev_xargs_columns
+            self._ck_perm(self.L.smi_dev_xargs_columns(self.h, C.byref(a), C.byref(a.xargs), vp(d_trace_cols), n_cols, log_n, ch, vp(d_c),
+                                                       (1 << log_n) if c_stride is None else c_stride, C.byref(closes)))
+            return [bool(closes.value >> i & 1) for i in range(a.xargs.count)]
         self._ck_perm(self.L.smi_dev_args_columns(self.h, C.byref(a.args), vp(d_trace_cols), n_cols, log_n, ch, vp(d_c),
                                                   (1 << log_n) if c_stride is None else c_stride, C.byref(closes)))
         return [bool(closes.value >> i & 1) for i in range(a.args.count)]
@@ -548,6 +575,11 @@ class Engine:
         a = self._args_of(air, "dev_air_compose_args")
         N = 1 << (log_n + log_blowup)
         ch = (C.c_uint64 * 8)(*[int(c) for c in challenges])
+        if self._xargs(a) is not None:   # selectors or periodic members: smi_dev_air_compose_xargs
+            self._ck(self.L.smi_dev_air_compose_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(a.xargs), vp(d_lde), N if stride is None else stride,
+                                                      vp(d_c_lde), N if c_stride is None else c_stride, ch, vp(d_weights), vp(d_out),
+                                                      N if out_stride is None else out_stride))
+            return
         self._ck(self.L.smi_dev_air_compose_args(self.h, C.byref(cfg), C.byref(a), C.byref(a.args), vp(d_lde), N if stride is None else stride,
                                                  vp(d_c_lde), N if c_stride is None else c_stride, ch, vp(d_weights), vp(d_out),
                                                  N if out_stride is None else out_stride))
@@ -663,8 +695,40 @@ class Engine:
         trace's mult_col, which is otherwise taken as filled.
         An AIR with an argument list (mirror.Air.add_permutation / add_lookup) takes smi_dev_air_prove_args in the same way: the
         sixth stage is "args", "closes" is a list of A bools, check=True raises naming the arguments that do not close, and
-        fill_multiplicities=True runs dev_lookup_multiplicities once per lookup argument."""
+        fill_multiplicities=True runs dev_lookup_multiplicities once per lookup argument.  A list with selectors or periodic
+        members (mirror.Air.extended_args) takes smi_dev_air_prove_xargs and smi_dev_xargs_multiplicities instead."""
         a = self._air(air)
+        if self._xargs(a) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("dev_air_prove: an AIR with an argument list needs row_leaves=True, ext=True")
+            A = a.xargs.count
+            lookups = [i for i in range(A) if a.xargs.arg[i].kind == 1]
+            if fill_multiplicities and not lookups:
+                raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
+            if fill_multiplicities:
+                for i in lookups:
+                    self.dev_args_multiplicities(a, i, d_trace_cols, n_cols, log_n, vp(d_trace_cols).value + 4 * (a.xargs.arg[i].mult_col << log_n))
+            if check:
+                ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+                if not ok:
+                    raise StarkMiError(-50, why)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.zeros((2, 32), dtype=np.uint8)
+            proof, plen, mask = vp(), C.c_size_t(), C.c_uint32()
+            top = np.zeros(max(num_colinearity_tests, 1), dtype=np.uint64)
+            stage = (C.c_double * 6)()
+            self._ck_perm(self.L.smi_dev_air_prove_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(a.xargs), vp(d_trace_cols), roots.ctypes.data,
+                                                         C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                         0 if grind_bits is None else grind_bits, C.byref(mask)))
+            b = C.string_at(proof, plen.value)
+            self.L.smi_free(proof)
+            closes = [bool(mask.value >> i & 1) for i in range(A)]
+            if check and not all(closes):
+                raise StarkMiError(-50, f"air_prove_xargs: the arguments {[i for i, c in enumerate(closes) if not c]} do not close")
+            out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:num_colinearity_tests]], "closes": closes}
+            if timed:
+                out["stage_ms"] = dict(zip(("lde", "commit", "args", "compose", "fri", "open"), [float(x) for x in stage]))
+            return out
         if self._args(a) is not None:
             if not (row_leaves and ext):
                 raise ValueError("dev_air_prove: an AIR with an argument list needs row_leaves=True, ext=True")
@@ -781,7 +845,20 @@ class Engine:
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
         column_roots is root_1 then root_2, grind_bits None counts as 0.  An AIR with a lookup takes smi_air_verify_lookup in
-        the same way, and an AIR with an argument list smi_air_verify_args."""
+        the same way, and an AIR with an argument list smi_air_verify_args (smi_air_verify_xargs when the list has selectors
+        or periodic members)."""
+        if self._xargs(self._air(air)) is not None:
+            if not (row_leaves and ext):
+                raise ValueError("air_verify: an AIR with an argument list needs row_leaves=True, ext=True")
+            a = self._air(air)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 64:
+                raise StarkMiError(-50, "air_verify: an AIR with an argument list takes two 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(a.xargs), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                 0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if self._args(self._air(air)) is not None:
             if not (row_leaves and ext):
                 raise ValueError("air_verify: an AIR with an argument list needs row_leaves=True, ext=True")
@@ -934,6 +1011,16 @@ def air_plan_args(p, air, args, cfg):
     L = _lib.lib()
     d, e = C.c_uint32(), C.c_uint64()
     st = L.smi_air_plan_args(p, C.byref(cfg), C.byref(air), C.byref(args), C.byref(d), C.byref(e))
+    if st != 0:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, e.value
+
+
+def air_plan_xargs(p, air, xargs, cfg):
+    """smi_air_plan_xargs (host only) -> (d, E).  air: a flattened _lib.Air; xargs: a _lib.AirXArgs"""
+    L = _lib.lib()
+    d, e = C.c_uint32(), C.c_uint64()
+    st = L.smi_air_plan_xargs(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(d), C.byref(e))
     if st != 0:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value

@@ -820,7 +820,13 @@ class Air:
         air.add_permutation([0, 1], [2, 3]).add_lookup([4], [5], 6).add_lookup([7], [5], 8)
 
     With a non-empty air.args the same three take the smi_*_args entry points.  A list does not mix with permutation() /
-    lookup(): a single argument is either the one of its own section or a list of one, which give the same proof."""
+    lookup(): a single argument is either the one of its own section or a list of one, which give the same proof.
+
+    In a list a tuple member may be a periodic column, ("per", j), and each side may have a selector (include/stark_mi.h,
+    "Argument list with selectors and periodic members"):
+        flag, rng = 3, air.periodic(range(256))
+        air.add_lookup([0], [("per", rng)], 2, sel=flag)         # on the rows with c3 = 1, c0[r] is in 0 .. 255; c2 counts
+    A list with such an argument takes the smi_*_xargs entry points; any other list the smi_*_args ones, as before."""
 
     def __init__(self, n_cols):
         self.n_cols = n_cols
@@ -829,7 +835,10 @@ class Air:
         self.periodics = []     # [[value, ...], ...]: a power-of-two number of integers each
         self.perm = None        # ([left columns], [right columns]) once permutation() was called
         self.lookup_arg = None  # ([lookup columns], [table columns], multiplicity column) once lookup() was called
-        self.args = []          # [("perm", left, right) | ("lookup", columns, table columns, multiplicity column), ...]
+        self.xargs_always = False   # flatten a list without selectors or periodic members to smi_air_xargs all the same (the
+                                    # two paths give the same bytes; for comparisons)
+        self.args = []          # [("perm", left, right) | ("lookup", columns, table columns, multiplicity column), ...]; with
+                                # selectors two more entries (a_sel, b_sel); a member is an int or ("per", j)
 
     @property
     def constraints(self):
@@ -897,13 +906,44 @@ class Air:
         self.args.append(arg)
         return self
 
-    def add_permutation(self, left, right):
-        """appends a permutation argument (see permutation()) to the argument list"""
-        return self._add_arg(("perm", [int(c) for c in left], [int(c) for c in right]))
+    @staticmethod
+    def _operand(x, what, none_ok=False):
+        """a member or selector of an argument: an int (trace column) or ("per", j) (periodic column j)"""
+        if x is None and none_ok:
+            return None
+        if isinstance(x, tuple):
+            if len(x) != 2 or x[0] != "per":
+                raise ValueError(f"{what}: an operand is a trace column or (\"per\", j), not {x!r} (next-row members are not supported)")
+            return ("per", int(x[1]))
+        return int(x)
 
-    def add_lookup(self, cols, table_cols, mult_col):
-        """appends a lookup argument (see lookup()) to the argument list"""
-        return self._add_arg(("lookup", [int(c) for c in cols], [int(c) for c in table_cols], int(mult_col)))
+    def add_permutation(self, left, right, left_sel=None, right_sel=None):
+        """appends a permutation argument (see permutation()) to the argument list.  A member is a trace column or ("per", j),
+        periodic column j; left_sel / right_sel (a member each, or None) select the rows of a side: with 0 / 1 selectors the
+        selected left tuples are a permutation of the selected right tuples (include/stark_mi.h, "Argument list with selectors
+        and periodic members")"""
+        arg = ("perm", [self._operand(c, "add_permutation") for c in left], [self._operand(c, "add_permutation") for c in right])
+        ls, rs = self._operand(left_sel, "left_sel", True), self._operand(right_sel, "right_sel", True)
+        return self._add_arg(arg if ls is None and rs is None else arg + (ls, rs))
+
+    def add_lookup(self, cols, table_cols, mult_col, sel=None, table_sel=None):
+        """appends a lookup argument (see lookup()) to the argument list.  A member is a trace column or ("per", j); sel selects
+        the rows that look up, table_sel the rows of the table; mult_col is a trace column"""
+        arg = ("lookup", [self._operand(c, "add_lookup") for c in cols], [self._operand(c, "add_lookup") for c in table_cols], int(mult_col))
+        s, ts = self._operand(sel, "sel", True), self._operand(table_sel, "table_sel", True)
+        return self._add_arg(arg if s is None and ts is None else arg + (s, ts))
+
+    @staticmethod
+    def arg_selectors(arg):
+        """(a_sel, b_sel) of an entry of Air.args; None: the constant 1"""
+        k = 3 if arg[0] == "perm" else 4
+        return (arg[k], arg[k + 1]) if len(arg) > k else (None, None)
+
+    @property
+    def extended_args(self):
+        """does some argument of the list use a selector or a periodic member?  Then the list flattens to smi_air_xargs;
+        otherwise to smi_air_args, and callers take the entry points of "Argument list" as before"""
+        return any(self.arg_selectors(g) != (None, None) or any(isinstance(c, tuple) for c in g[1] + g[2]) for g in self.args)
 
     def closes(self, p, g, cols, alpha, gamma):
         """z[n-1] * rho[n-1] == 1 for the trace cols under alpha, gamma (four canonical coordinates each); plain Python"""
@@ -980,8 +1020,20 @@ class Air:
             la, ta = np.array(self.lookup_arg[0], dtype=np.uint32), np.array(self.lookup_arg[1], dtype=np.uint32)
             out.lookup = _lib.AirLookup(len(la), self.lookup_arg[2] % (1 << 32), ptr(la, _lib.u32p), ptr(ta, _lib.u32p))
             out.lookup._keep = (la, ta)
-        out.args = None
-        if self.args:
+        out.args = out.xargs = None
+        if self.extended_args or (self.args and self.xargs_always):
+            W = self.n_cols
+            var = lambda c: _lib.NO_SELECTOR if c is None else (2 * W + c[1]) % (1 << 32) if isinstance(c, tuple) else c % (1 << 32)
+            keep, raw = [], (_lib.AirXArg * len(self.args))()
+            for a, arg in enumerate(self.args):
+                la, ra = np.array([var(c) for c in arg[1]], dtype=np.uint32), np.array([var(c) for c in arg[2]], dtype=np.uint32)
+                keep += [la, ra]
+                sa, sb = self.arg_selectors(arg)
+                raw[a] = _lib.AirXArg(0 if arg[0] == "perm" else 1, len(la), (arg[3] % (1 << 32)) if arg[0] == "lookup" else 0, 0, ptr(la, _lib.u32p),
+                                      ptr(ra, _lib.u32p), var(sa), var(sb))
+            out.xargs = _lib.AirXArgs(len(self.args), 0, raw)
+            out.xargs._keep = (keep, raw)
+        elif self.args:
             keep, raw = [], (_lib.AirArg * len(self.args))()
             for a, arg in enumerate(self.args):
                 la, ra = np.array(arg[1], dtype=np.uint32), np.array(arg[2], dtype=np.uint32)

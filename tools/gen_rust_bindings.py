@@ -172,7 +172,9 @@ def generate():
         for nm in names.split(","):
             lines.append(f"    pub {nm.strip()}: {SCALAR[ty]},")
     lines.append("}")
-    for sname, what in (("smi_air_arg", "one argument of an argument list"), ("smi_air_args", "an argument list")):
+    for sname, what in (("smi_air_arg", "one argument of an argument list"), ("smi_air_args", "an argument list"),
+                        ("smi_air_xarg", "one argument of a list with selectors and periodic members"),
+                        ("smi_air_xargs", "an argument list with selectors and periodic members")):
         lines.append(f"/// {sname}: {what} (host pointers; the entry points take the list as `*const c_void`)")
         lines.append("#[repr(C)] #[derive(Clone, Copy)]")
         lines.append(f"pub struct {sname} {{")
@@ -189,6 +191,8 @@ def generate():
     for m in re.finditer(r"#define (SMI_\w+_MAX_\w+) (\d+)", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     for m in re.finditer(r"#define (SMI_ARGS_MAX|SMI_ARG_[A-Z]+) (\d+)", text):
+        lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
+    for m in re.finditer(r"#define (SMI_ARG_NO_SELECTOR) (0x[0-9a-f]+)u", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     lines.append("")
     lines.append('#[link(name = "starkmi")]')

@@ -153,6 +153,12 @@ extern "C" void emu_set_last_direct(int on) { g_emu_last_direct = on != 0; }
 static int g_emu_defer_tw = 2;   // NttRequest::defer_tw: 0 never, 1 always, 2 the driver's rule
 extern "C" void emu_set_defer_tw(int mode) { g_emu_defer_tw = mode; }
 extern "C" void emu_set_share_cols(int mode) { g_share_cols = mode; }
+// the planner's answer under the process's SMI_NTT_PLAN_<L> override, if any: -> np (0 = the small kernel)
+extern "C" int emu_ntt_plan(uint32_t L, uint32_t batch, int *logr, int *logw) {
+    const NttPlan pl = ntt_make_plan(L, batch);
+    for (int i = 0; i < 4; i++) { logr[i] = pl.logr[i]; logw[i] = pl.logw[i]; }
+    return pl.np;
+}
 extern "C" int emu_ntt(uint64_t p, uint64_t g, const uint32_t *in, uint32_t *out, uint32_t L, uint32_t n_in,
                        uint32_t batch, uint64_t in_stride, uint64_t out_stride, int inverse, uint64_t offset,
                        uint64_t post_scale) {

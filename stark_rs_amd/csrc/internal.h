@@ -51,7 +51,9 @@ struct smi_ctx {
     char prof_only[56] = {0};   // smi_ctx_profile_only: bracket only launches whose name contains this (empty: all)
     bool copy_probe = false;       // smi_ctx_copy_probe: NTT passes launch their copy-only twins
     // three-pass transforms: the second pass applies the first pass's inter-pass twiddle as it loads (ntt_core.h)
-    bool ntt_share_cols = !(getenv("SMI_NTT_SHARE_COLS") && atoi(getenv("SMI_NTT_SHARE_COLS")) == 0);   // tuning knob, default on
+    // tuning knob, default 1: 0 never, 1 the launchers' rule (NttPass::share_cols), 2 whenever the pass has multipliers (no
+    // launch-size threshold: how the tests reach the column-sharing kernels at small sizes); any other value is 1
+    int ntt_share_cols = !getenv("SMI_NTT_SHARE_COLS") ? 1 : atoi(getenv("SMI_NTT_SHARE_COLS")) == 0 ? 0 : atoi(getenv("SMI_NTT_SHARE_COLS")) == 2 ? 2 : 1;
     bool ntt_twin_regs = !(getenv("SMI_NTT_TWIN_REGS") && atoi(getenv("SMI_NTT_TWIN_REGS")) == 0);   // tuning knob, default on: deferred twiddles held as per-thread input multipliers
     bool ntt_last_direct = !(getenv("SMI_NTT_LAST_DIRECT") && atoi(getenv("SMI_NTT_LAST_DIRECT")) == 0);   // NttRequest::last_direct; tuning knob, default on
     int ntt_defer_tw = getenv("SMI_NTT_DEFER_TW") ? (atoi(getenv("SMI_NTT_DEFER_TW")) != 0) : 2;   // NttRequest::defer_tw; tuning knob, default 2 (auto)

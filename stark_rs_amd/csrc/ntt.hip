@@ -337,9 +337,15 @@ struct HipLauncher {
         ntt_small_kernel<<<batch, SMI_NTT_THREADS, 0, ctx->stream>>>(a);
         note();
     }
+    // The one rule both launch() and the name pass() records go by: SMI_NTT_SHARE_COLS 0 never, 1 NttPass::share_cols with
+    // its launch-size threshold, 2 without it (the lazy range CAP has no part in the rule)
+    template <int LR, int LW, int KIND> bool takes_cols(const PassArgs &a) const {
+        if (KIND == PASS_FIRST || !ctx->ntt_share_cols) return false;
+        return NttPass<LR, LW, KIND, 4>::share_cols(a, ctx->ntt_share_cols == 2 ? 0u : (uint32_t)SMI_COLS_MIN_WGS);
+    }
     template <int LR, int LW, int KIND, int CAP> void launch(const PassArgs &a) {
         if constexpr (KIND != PASS_FIRST) {
-            if (ctx->ntt_share_cols && NttPass<LR, LW, KIND, CAP>::share_cols(a)) {
+            if (takes_cols<LR, LW, KIND>(a)) {
                 const dim3 grid(a.n_tiles, NttPass<LR, LW, KIND, CAP>::col_groups(a));
                 if (KIND == PASS_MID && (a.flags & NTT_TW_IN) && ctx->ntt_twin_regs)
                     ntt_pass_cols_kernel<LR, LW, KIND, CAP, KIND == PASS_MID><<<grid, 1 << (LR + LW - 4), 0, ctx->stream>>>(a);
@@ -379,8 +385,7 @@ struct HipLauncher {
             note();                                                                                            \
             return;                                                                                            \
         }                                                                                                      \
-        const bool cols = ctx->ntt_share_cols && (kind == PASS_LAST ? NttPass<LR, LW, PASS_LAST, 4>::share_cols(a)                     \
-                                                  : kind == PASS_MID ? NttPass<LR, LW, PASS_MID, 4>::share_cols(a) : false);            \
+        const bool cols = kind == PASS_LAST ? takes_cols<LR, LW, PASS_LAST>(a) : kind == PASS_MID ? takes_cols<LR, LW, PASS_MID>(a) : false; \
         ProfScope ps(ctx, cols ? (kind == PASS_LAST ? "ntt_pass_cols_kernel<" #LR "," #LW ",last>" : "ntt_pass_cols_kernel<" #LR "," #LW ",mid>") \
                           : kind == PASS_LAST ? "ntt_pass_kernel<" #LR "," #LW ",last>" : kind == PASS_MID ? "ntt_pass_kernel<" #LR "," #LW ",mid>" : "ntt_pass_kernel<" #LR "," #LW ",first>", bytes); \
         if (wide) launch_kind<LR, LW, 8>(kind, a);                                                             \

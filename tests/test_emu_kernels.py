@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import ntt_matrix as nm
+
 P, G = 998244353, 3
 P2, G2 = 469762049, 3
 u32p = C.POINTER(C.c_uint32)
@@ -145,22 +147,70 @@ def test_emulated_hex_fiat_shamir_round(emu, oracle):
         assert [x & 0x00FF00FF for x in st_a] == [x & 0x00FF00FF for x in st_b], k
 
 
-@pytest.mark.parametrize("L,plan", [
+# the plans this test ran before the table of tests/ntt_matrix.py existed: kept, with what they assert
+_EXPLICIT_PLANS = [
     (18, "9.3,9.3"), (18, "9.5,9.4"), (18, "10.4,8.4"), (18, "6.6,6.6,6.6"), (19, "7.6,6.6,6.6"), (20, "10.2,10.2"),
     (20, "10.4,10.3"), (20, "7.5,7.5,6.6"), (20, "8.6,6.6,6.6"), (21, "8.5,7.6,6.6"), (21, "9.4,6.6,6.6"),
-])
+]
+_TABLE = {}
+for _r in nm.plan_table():
+    _TABLE.setdefault((_r["L"], _r["plan"]), []).append(_r)
+
+
+def _emu_leg(emu, o, prime, L, leg, cols):
+    """one leg of the matrix on the emulator, the columns `cols` of the six as its batch, every one against the oracle"""
+    p, g, _ = nm.PRIMES[prime]
+    n = 1 << L
+    flat = np.concatenate([nm.column(p, L, c) for c in cols])
+    got = _ntt(emu, p, g, flat, L, nm.n_in_of(leg, n), 1 if leg["inverse"] else 0, leg["offset"], post=leg["post"], batch=len(cols),
+               in_stride=n).reshape(len(cols), n)
+    for i, c in enumerate(cols):
+        assert np.array_equal(got[i], nm.oracle_column(o, prime, L, leg, c)), (prime, L, leg, c)
+
+
+@pytest.mark.parametrize("L,plan", _EXPLICIT_PLANS + [k for k in _TABLE if k not in _EXPLICIT_PLANS])
 def test_emulated_ntt_explicit_tile_shapes(emu, oracle, L, plan):
-    """Every instantiated (logr, logw) tile shape, selected through the tuning override."""
+    """Every instantiated (logr, logw) tile shape in every role, selected through the tuning override: the plan table of
+    tests/ntt_matrix.py (what tests/test_gpu_ntt_matrix.py runs on the GPU) on the emulator.  One column under the
+    launcher's rule; the columns of a tile in one workgroup (share mode 2) with the first pass's twiddles kept and deferred;
+    both primes; the zero-padding sweep of the first role; the last column all p - 1.  Six columns up to 2^18 points, two
+    (a pseudo-random one and the one of p - 1) above; from 2^21 points one prime per plan, column sharing only."""
     o = oracle
+    rows = _TABLE.get((L, plan), [])
     os.environ[f"SMI_NTT_PLAN_{L}"] = plan
     try:
         n = 1 << L
-        w = o.ff_prim_nth_root(n)
-        vals = o.splitmix64(L, n) % np.uint64(P)
-        assert np.array_equal(_ntt(emu, P, G, vals, L, n, 1, 3), o.fast_intt(vals, w, 3))
-        assert np.array_equal(_ntt(emu, P, G, vals[: n // 8], L, n // 8, 0, 3), o.fast_coset_ntt(vals[: n // 8], n, w, 3))
+        if (L, plan) in _EXPLICIT_PLANS or L <= 20:
+            w = o.ff_prim_nth_root(n)
+            vals = o.splitmix64(L, n) % np.uint64(P)
+            assert np.array_equal(_ntt(emu, P, G, vals, L, n, 1, 3), o.fast_intt(vals, w, 3))
+            assert np.array_equal(_ntt(emu, P, G, vals[: n // 8], L, n // 8, 0, 3), o.fast_coset_ntt(vals[: n // 8], n, w, 3))
+        if not rows:
+            return
+        family = "first" if any(r["family"] == "first" for r in rows) else rows[0]["family"]
+        legs = nm.legs(family, {"SMI_NTT_SHARE_COLS": "2"})
+        cols = list(range(nm.BATCH)) if L <= 18 else [0, nm.BATCH - 1]
+        three_pass = len(nm.parse_plan(plan)) >= 3
+        if L <= 20:
+            primes = ("ref", "p2")
+        else:   # one prime per plan, both over the plans of a size
+            primes = ("p2",) if L > 23 or sum(lr + lw for lr, lw in nm.parse_plan(plan)) % 2 else ("ref",)
+        for prime in primes:
+            if L <= 20:
+                emu.emu_set_share_cols(1)
+                emu.emu_set_defer_tw(2)
+                for name, leg in legs.items():
+                    if leg["batch"] == 1:
+                        _emu_leg(emu, o, prime, L, leg, [0])
+            emu.emu_set_share_cols(2)
+            for defer in ((0, 1) if three_pass and L <= 20 else (1,)):
+                emu.emu_set_defer_tw(defer)
+                _emu_leg(emu, o, prime, L, legs["inv6"], cols)
+                _emu_leg(emu, o, prime, L, legs["fwd6"], cols)
     finally:
         del os.environ[f"SMI_NTT_PLAN_{L}"]
+        emu.emu_set_share_cols(1)
+        emu.emu_set_defer_tw(2)
 
 
 @pytest.mark.parametrize("p,g", [(P, G), (P2, G2)])

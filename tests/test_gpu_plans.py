@@ -41,7 +41,9 @@ SETTINGS += [("FRI_TAIL=0", {"SMI_FRI_TAIL": "0"}, {}, 0),
              ("FRI_TAIL=2048", {"SMI_FRI_TAIL": "2048"}, {}, 2048),
              ("FUSE=0-FRI_TAIL=2048", {"SMI_MERKLE_FUSE": "0", "SMI_FRI_TAIL": "2048"}, dict(FUSE=0), 2048)]
 # the NTT knobs change no Merkle or FRI plan: the battery's LDE items (and the extension inside the build-defined prove)
-# are what they reach, and the environment the child echoes is the only evidence that they were set
+# are what they reach -- one 2^20 two-pass plan and one 2^23 plan (8.6, 6.6, 9.5) at batch 3, not the other pass kernels:
+# tests/test_gpu_ntt_matrix.py runs every instantiation -- and the environment the child echoes is the only evidence here
+# that they were set
 NTT_SETTINGS = [{"SMI_NTT_SHARE_COLS": "0"}, {"SMI_NTT_TWIN_REGS": "0"}, {"SMI_NTT_LAST_DIRECT": "0"}, {"SMI_NTT_DEFER_TW": "0"},
                 {"SMI_NTT_DEFER_TW": "1"}, {"SMI_LDE_GEO": "2", "SMI_LDE_LAYOUT": "4"}, {"SMI_LDE_GEO": "1", "SMI_LDE_LAYOUT": "3"}]
 SETTINGS += [("-".join("%s=%s" % (k[4:], v) for k, v in env.items()), env, {}, TAIL_LEN) for env in NTT_SETTINGS]

@@ -285,6 +285,12 @@ extern "C" {
     pub fn smi_fri_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize, grind_bits: u32) -> c_int;
     pub fn smi_dev_air_prove_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
     pub fn smi_air_verify_ext_pow(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_fri_fold4_layout(cfg: *const smi_fri_cfg, folds: *mut u64, last_len: *mut u64, proof_len: *mut usize) -> c_int;
+    pub fn smi_dev_fri_fold4_ext(ctx: *mut smi_ctx, d_in: *const u32, len: usize, stride: usize, d_alpha: *const u64, offset: u64, omega: u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_fri_prove_ext_fold4(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, d_codeword: *const u32, len: usize, stride: usize, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, grind_bits: u32, nonce: *mut u64) -> c_int;
+    pub fn smi_fri_verify_ext_fold4(ctx: *mut smi_ctx, cfg: *const smi_fri_cfg, transcript: *const u8, transcript_len: usize, proof: *const u8, proof_len: usize, accept: *mut c_int, pv_indices: *mut u64, pv_values: *mut u64, n_pv: *mut usize, consumed: *mut usize, grind_bits: u32) -> c_int;
+    pub fn smi_dev_air_prove_ext_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, row_root: *mut u8, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
+    pub fn smi_air_verify_ext_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, row_root: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_air_plan_perm(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, degree: *mut u32, fri_expansion: *mut u64) -> c_int;
     pub fn smi_dev_perm_column(ctx: *mut smi_ctx, perm: *const c_void, d_trace_cols: *const u32, n_cols: u32, log_n: u32, challenges: *const u64, d_z: *mut u32, z_stride: usize, closes: *mut c_int) -> c_int;
     pub fn smi_dev_air_compose_perm(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, perm: *const c_void, d_lde: *const u32, stride: usize, d_z_lde: *const u32, z_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;

@@ -669,6 +669,78 @@ int smi_dev_air_prove_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
 int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
                            size_t proof_len, int *accept, uint32_t grind_bits);
 
+/* ---- Extension FRI, folding factor 4: one coset leaf per query and layer ------------------------
+ * "Extension FRI" folds by 2: about 2 N leaves hashed over the rounds, and per query and layer three authentication paths.
+ * Folding by 4 halves the round loop, hashes about N / 3 leaves of 16 values, and a query opens ONE path per layer: the
+ * four points of a coset sit in one leaf, and the folded value needs no path of its own because it is an entry of the next
+ * layer's opened coset.  The entry points above are unchanged, byte for byte; these are new ones beside them.
+ * Field, codeword layout and transcript are those of "Extension FRI".  Grinding is always part of the stream: the nonce
+ * record is always present, grind_bits is 0 .. SMI_GRIND_MAX_BITS, and at 0 the nonce is 0.
+ *
+ * Rounds.  R2 = smi_fri_num_rounds(cfg); R2 = 0 is refused as today (SMI_ERR_NO_ROUNDS).  F = (R2 - 1) / 2 (integer
+ *   division) folds, F + 1 committed codewords.  Layer r has length n_r = N / 4^r, offset^(4^r) and omega^(4^r).  The last
+ *   length L_last = n_F is at least the reference's last length and above E, so the degree bound L_last / E - 1 stays
+ *   meaningful; the entropy statuses of smi_dev_fri_prove_ext apply to L_last.  A fold takes lengths 4 .. 2^27.  F = 0 is a
+ *   proof without layers: one root, the codeword in the clear, the nonce.
+ * Fold.  With q = n / 4, x = offset omega^i and iota = omega^q (a primitive fourth root of unity), output element i < q is
+ *   P(alpha) for the unique P of degree < 4 over F_q with P(x iota^j) = cw[i + j q], j = 0 .. 3.  Equivalently -- the
+ *   identity the tests check -- smi_dev_fri_fold_ext under alpha over (offset, omega, n), then under alpha^2 (the F_q square,
+ *   reduced) over (offset^2, omega^2, n / 2), word for word: the outputs are canonical residues.
+ * Commitment.  Layer r's tree has q_r = n_r / 4 leaves; leaf i is Hash::from_field_elements of 16 values: for e = 0 .. 3
+ *   (outer) and j = 0 .. 3 (inner), coordinate e of element i + j q_r.  For a codeword whose columns are exactly n_r apart
+ *   that is smi_dev_merkle_build_rows(n_cols = 16, col_stride = q_r, n = q_r): 12 mixes a leaf.  The last codeword is
+ *   committed the same way.  A caller's first codeword with stride > len is compacted once (one copy of 16 N bytes).
+ * Transcript.  Per codeword: absorb the root; on every one but the last draw four challenges exactly as "Extension FRI"
+ *   does.  After the last root nu = grind(transcript, grind_bits) is absorbed; the index seed is challenge() of the
+ *   transcript as it then stands, and the indices are sample_indices(seed, size = F ? N / 4 : N, reduced = L_last, t).
+ * Indices.  i_0 = top mod q_0, i_{r+1} = i_r mod q_{r+1}.  The folded value of layer r's coset i_r is element i_r of
+ *   codeword r + 1: slot j = i_r div q_{r+1} of layer r + 1's opened coset, and for r = F - 1 entry i_r of the last
+ *   codeword.
+ * Proof bytes.  F + 1 records of tag 0; one tag-2 record of 4 L_last values (element i at 4 i .. 4 i + 3); one tag-2
+ *   record holding nu; then per layer r < F: t tag-2 records of 16 values in leaf order (the verifier hashes a record as
+ *   it stands), then t paths of log2 q_r digests.  Length:
+ *     33 (F + 1) + (9 + 32 L_last) + 17 + sum_{r < F} t (9 + 128) + t (9 + 32 log2 q_r)       (smi_fri_fold4_layout).
+ * Verifier.  The checks that are "Extension FRI"'s keep its sentences: the roots, the last codeword's shape, canonical
+ *   coordinates, its root (over coset leaves) and the degree of each coordinate, the proof of work; a coset record plays the
+ *   triple's part ("Failed to extract triple values", "Expected triple of values", "triple: a coordinate is not
+ *   canonical") and its path the part of path a.  Per layer: the t records, then -- from layer 1 on -- the previous layer's
+ *   folds against this layer's slots, then the t paths; after the last layer its folds against the last codeword.  The one
+ *   new sentence: "folded coset does not match the next layer".  A factor-2 proof is rejected here and a factor-4 proof by
+ *   smi_fri_verify_ext_pow: the numbers of roots differ, or (R2 = 1) the leaves do.
+ * AIR (row leaves, extension weights).  Transcript, weights, commitment and composition of smi_dev_air_prove_ext_pow; the
+ *   FRI above.  Opening section, per test: a = top mod N / 4; the rows at a, a + N/4, a + N/2, a + 3N/4; when K > 0 the
+ *   four rows at (. + B) mod N in the same order; then one path per opened position.  With R = K ? 8 : 4 the section is
+ *   t R (9 + 8 W) + t R (9 + 32 log2 N) bytes.  The verifier recomputes the composition's four coordinates at all four
+ *   points, periodic operands included, and compares them with the layer-0 coset record.  With F = 0 there is no such
+ *   record: prover and verifier refuse the shape with SMI_ERR_BAD_ARG and a sentence in smi_last_error.
+ * Left out: the permutation, lookup, args and xargs provers (they fold by 2); column trees; smi_mgpu_* twins; folding
+ *   factors above 4; the fold fused into the launch that hashes the leaves. */
+/* Host only, no context: the number of folds, the last codeword's length and the proof's length in bytes for cfg.
+ * SMI_ERR_NO_ROUNDS when smi_fri_num_rounds is 0; the statuses of smi_fri_check for a malformed cfg. */
+int smi_fri_fold4_layout(const smi_fri_cfg *cfg, uint64_t *folds, uint64_t *last_len, size_t *proof_len);
+/* The fold above in one launch.  d_in: len elements (a power of two, 4 .. 2^27), columns stride >= len apart; d_out:
+ * len / 4 elements, columns out_stride >= len / 4 apart, not overlapping d_in; d_alpha as for smi_dev_fri_fold_ext.  It
+ * moves 80 bytes per output element where the two launches of smi_dev_fri_fold_ext move 144.  16-byte accesses when d_in
+ * and d_out are 16-byte aligned and stride, out_stride and len / 4 are multiples of 4; 4-byte accesses otherwise, same
+ * values.  omega must have order len for the Lagrange reading; the two-fold identity holds whenever omega^(len/2) = -1.
+ * Statuses as smi_dev_fri_fold_ext. */
+int smi_dev_fri_fold4_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset,
+                          uint64_t omega, uint32_t *d_out, size_t out_stride);
+/* smi_dev_fri_prove_ext_pow / smi_fri_verify_ext_pow at folding factor 4: the same parameters.  The round loop, the
+ * search, the query and the emit are enqueued without a host round trip.  pv_indices needs room for 4 t entries and
+ * pv_values for 16 t: the layer-0 cosets, element i_0 + j q_0 for j = 0 .. 3 per test. */
+int smi_dev_fri_prove_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                                size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, uint32_t grind_bits,
+                                uint64_t *nonce);
+int smi_fri_verify_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                             size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed,
+                             uint32_t grind_bits);
+/* smi_dev_air_prove_ext_pow / smi_air_verify_ext_pow over the FRI above (AIR, above): the same parameters and stage_ms. */
+int smi_dev_air_prove_ext_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                                uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
+int smi_air_verify_ext_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                             size_t proof_len, int *accept, uint32_t grind_bits);
+
 /* ---- Permutation argument: a committed extension column ----------------------------------------
  * The AIR sections relate two consecutive rows.  This one relates rows far apart: it proves that two lists of row tuples
  * are equal as multisets -- "this column is a sorted copy of that one", memory consistency, copy constraints -- the way

@@ -229,6 +229,14 @@ def lib():
                                          C.POINTER(sz), C.c_uint32]),
         "smi_dev_air_prove_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
         "smi_air_verify_ext_pow": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_fri_fold4_layout": (i32, [C.POINTER(FriCfg), u64p, u64p, C.POINTER(sz)]),
+        "smi_dev_fri_fold4_ext": (i32, [vp, vp, sz, sz, vp, C.c_uint64, C.c_uint64, vp, sz]),
+        "smi_dev_fri_prove_ext_fold4": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), vp, C.c_uint32,
+                                              u64p]),
+        "smi_fri_verify_ext_fold4": (i32, [vp, C.POINTER(FriCfg), C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32), vp, vp, C.POINTER(sz),
+                                           C.POINTER(sz), C.c_uint32]),
+        "smi_dev_air_prove_ext_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
+        "smi_air_verify_ext_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
         "smi_air_plan_perm": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), u32p, u64p]),
         "smi_dev_perm_column": (i32, [vp, C.POINTER(AirPerm), vp, C.c_uint32, C.c_uint32, u64p, vp, sz, C.POINTER(i32)]),
         "smi_dev_air_compose_perm": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirPerm), vp, sz, vp, sz, u64p, vp, vp, sz]),

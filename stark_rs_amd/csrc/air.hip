@@ -146,6 +146,12 @@ __global__ __launch_bounds__(64) void air_row_open_kernel(const uint32_t *__rest
     mg_row_open_write(cols, stride, W, nodes, depth, top[blockIdx.x], blockIdx.x, blockIdx.y, t, out, threadIdx.x, 64, R, B);
 }
 
+// the same at the four points of a layer-0 coset of FRI at folding factor 4 (mgpu_core.h mg_row_open4_write), R = 4 or 8
+__global__ __launch_bounds__(64) void air_row_open4_kernel(const uint32_t *__restrict__ cols, size_t stride, uint32_t W, const uint8_t *__restrict__ nodes,
+                                                            uint32_t depth, const uint64_t *__restrict__ top, uint32_t t, uint32_t R, uint64_t B, uint8_t *out) {
+    mg_row_open4_write(cols, stride, W, nodes, depth, top[blockIdx.x], blockIdx.x, blockIdx.y, t, out, threadIdx.x, 64, R, B);
+}
+
 // out[q * 2Q + j] = pi_j(x_i), out[q * 2Q + Q + j] = pi_j(w x_i) for i = idx[q]: what the verifier needs of the tables
 __global__ __launch_bounds__(64) void air_periodic_gather_kernel(AirDev A, const uint64_t *__restrict__ idx, uint32_t count, uint32_t *__restrict__ out) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -389,12 +395,19 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
 // ext (with rows): the weights are elements of the quartic extension -- four counters and four challenges per weight --, the
 // composition codeword is four coordinate columns and FRI runs over F_q (smi_dev_air_prove_ext).
 // grind (with ext): the proof-of-work difficulty of the FRI part, or SMI_GRIND_NONE (smi_dev_air_prove_ext_pow).
+// fold4 (with ext and a difficulty): FRI at folding factor 4 and the rows at the four points of every layer-0 coset
+// (smi_dev_air_prove_ext_fold4); every other caller passes false and runs what it ran before.
 static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint32_t *d_trace_cols, uint8_t *column_roots,
                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, bool rows, bool ext = false,
-                          int grind = SMI_GRIND_NONE) {
+                          int grind = SMI_GRIND_NONE, bool fold4 = false) {
     AirHost H;
     uint64_t E = 0;
     SMI_TRY(air_host(ctx, cfg, air, &H, &E));
+    if (fold4) {   // without a fold there is no layer-0 coset record to compare the composition with
+        const smi_fri_cfg fc0 = trace_fri_cfg(ctx, cfg, E);
+        const FriFold4Layout lay = fri_layout_fold4(fc0);
+        if (lay.R2 && lay.F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, AIR_FOLD4_NO_LAYER);
+    }
     const uint32_t W = cfg->n_cols, K = air->n_constraints, log_N = cfg->log_n + cfg->log_blowup;
     const size_t N = (size_t)1 << log_N;
     SMI_TRY(arena_reset(ctx));
@@ -452,7 +465,8 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     FriResult res;
     FriExtResult xres;
     if (ext) {
-        SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, grind));
+        if (fold4) SMI_TRY(fri_run_ext_fold4(ctx, &fc, &seed, d_cw, N, N, false, &xres, (uint32_t)grind));
+        else SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, grind));
     } else {
         FriRequest rq(&fc, d_cw, N, true);
         rq.reset_arena = false;
@@ -465,13 +479,14 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     else top_indices = top.data();   // the column openings need the top-level indices either way
     mark(4);
     if (cfg->num_colinearity_tests && rows) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = K ? 4u : 2u;
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = (K ? 4u : 2u) * (fold4 ? 2u : 1u);
         const size_t ob = (size_t)mg_row_open_bytes(W, t, log_N, R);
         uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
         uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob);
         if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove: row openings");
         HIP_TRY(ctx, hipMemcpyAsync(d_top, top_indices, 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        air_row_open_kernel<<<dim3(t, R), 64, 0, ctx->stream>>>(d_lde, N, W, tree_base, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open);
+        if (fold4) air_row_open4_kernel<<<dim3(t, R), 64, 0, ctx->stream>>>(d_lde, N, W, tree_base, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open);
+        else air_row_open_kernel<<<dim3(t, R), 64, 0, ctx->stream>>>(d_lde, N, W, tree_base, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open);
         HIP_TRY(ctx, hipGetLastError());
         const size_t at = bytes.size();
         bytes.resize(at + ob);
@@ -538,4 +553,14 @@ int smi_dev_air_prove_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(ext_field_check(ctx));
     return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true, true, (int)grind_bits);
+}
+
+// smi_dev_air_prove_ext_pow over FRI at folding factor 4 (include/stark_mi.h, "Extension FRI, folding factor 4")
+int smi_dev_air_prove_ext_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t row_root[32],
+                                uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return air_prove_impl(ctx, cfg, (const smi_air *)air, d_trace_cols, row_root, proof, proof_len, top_indices, stage_ms, true, true, (int)grind_bits, true);
 }

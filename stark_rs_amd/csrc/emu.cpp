@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ntt_driver.h"
+#include "fri_plan.h"
 #include "lde_core.h"
 #include "tables.h"
 #include "proof_parse.h"
@@ -610,6 +611,60 @@ extern "C" int emu_fold_ext(uint64_t p, uint64_t g, const uint32_t *in, uint32_t
         for (int e = 0; e < 4; e++) out[e * out_stride + i] = o[e];
     }
     return 0;
+}
+
+// fri_fold4_ext_kernel's lane body (fri_core.h fold4_element_ext) with the kernel's two batchings: vec != 0 takes four
+// consecutive outputs a lane through the [slot][coordinate][element] registers of the 16-byte variant (refused unless q and
+// both strides are multiples of 4, the launcher's condition), vec == 0 one output a lane.
+extern "C" int emu_fold4_ext(uint64_t p, uint64_t g, const uint32_t *in, uint32_t len, uint64_t stride, const uint64_t *alpha, uint64_t offset,
+                             uint64_t omega, uint32_t *out, uint64_t out_stride, int vec) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs) || !ext_field_ok(p, g, nullptr)) return -1;
+    if (len < 4 || (len & (len - 1)) || stride < len || out_stride < len / 4 || !offset || !omega || offset >= p || omega >= p) return -1;
+    const Fp &F = fs.F;
+    const uint32_t pp = F.p, q = len / 4;
+    if (vec && ((q & 3) || (stride & 3) || (out_stride & 3))) return -2;
+    uint32_t L = 0;
+    while ((1u << L) < q) L++;
+    GeomSpec sp[2];
+    const uint32_t omega_inv = host_powmod((uint32_t)omega, pp - 2, pp);
+    scale_table_specs(F, host_powmod((uint32_t)offset, pp - 2, pp), omega_inv, L, sp);
+    std::vector<uint32_t> slo = fill(sp[0], F), shi = fill(sp[1], F);
+    const ScaleTables S{slo.data(), shi.data(), scale_table_h(L)};
+    const uint32_t inv2_m = (uint32_t)(((uint64_t)host_powmod(2, pp - 2, pp) << 32) % pp), g_m = (uint32_t)(((uint64_t)fs.g << 32) % pp);
+    const uint32_t iota_inv_m = (uint32_t)(((uint64_t)host_powmod(omega_inv, q, pp) << 32) % pp);
+    const Fold4Alpha A = fold4_ext_alpha(alpha, g_m, F);
+    if (vec) {
+        for (uint32_t i = 0; i < q; i += 4) {
+            uint32_t v[4][4][4], res[4][4];
+            for (int j = 0; j < 4; j++)
+                for (int e = 0; e < 4; e++)
+                    for (int k = 0; k < 4; k++) v[j][e][k] = in[e * stride + (uint64_t)j * q + i + k];
+            for (int k = 0; k < 4; k++) {
+                uint32_t c[4][4], o[4];
+                for (int j = 0; j < 4; j++)
+                    for (int e = 0; e < 4; e++) c[j][e] = v[j][e][k];
+                fold4_element_ext(c, i + k, A, inv2_m, iota_inv_m, S, F, o);
+                for (int e = 0; e < 4; e++) res[e][k] = o[e];
+            }
+            for (int e = 0; e < 4; e++)
+                for (int k = 0; k < 4; k++) out[e * out_stride + i + k] = res[e][k];
+        }
+    } else {
+        for (uint32_t i = 0; i < q; i++) {
+            uint32_t c[4][4], o[4];
+            for (int j = 0; j < 4; j++)
+                for (int e = 0; e < 4; e++) c[j][e] = in[e * stride + (uint64_t)j * q + i];
+            fold4_element_ext(c, i, A, inv2_m, iota_inv_m, S, F, o);
+            for (int e = 0; e < 4; e++) out[e * out_stride + i] = o[e];
+        }
+    }
+    return 0;
+}
+// fri_layout_fold4 (fri_plan.h): out = {R2, F, last_n, proof_len}
+extern "C" void emu_fold4_layout(const smi_fri_cfg *cfg, uint64_t out[4]) {
+    const FriFold4Layout l = fri_layout_fold4(*cfg);
+    out[0] = l.R2; out[1] = l.F; out[2] = l.last_n; out[3] = l.proof_len;
 }
 
 // The transcript of FRI over the quartic extension as fs_round_ext_kernel runs it (hash_core.h fs_round_ext_lane, one call

@@ -286,6 +286,19 @@ int smi_fri_check(const smi_ctx *ctx, const smi_fri_cfg *cfg) {
     return SMI_OK;
 }
 
+int smi_fri_fold4_layout(const smi_fri_cfg *cfg, uint64_t *folds, uint64_t *last_len, size_t *proof_len) {
+    if (!cfg || !folds || !last_len || !proof_len) return SMI_ERR_BAD_ARG;
+    if (!is_pow2(cfg->domain_length)) return SMI_ERR_DOMAIN_NOT_POW2;
+    if (!is_pow2(cfg->expansion_factor)) return SMI_ERR_EXPANSION_NOT_POW2;
+    if (cfg->expansion_factor < 4) return SMI_ERR_EXPANSION_TOO_SMALL;
+    const FriFold4Layout l = fri_layout_fold4(*cfg);
+    if (l.R2 == 0) return SMI_ERR_NO_ROUNDS;
+    *folds = l.F;
+    *last_len = l.last_n;
+    *proof_len = l.proof_len;
+    return SMI_OK;
+}
+
 // Every device buffer of a run is handed to it at the moment it is allocated: smi_fri_run_free is the only place that frees.
 struct smi_fri_run {
     smi_ctx *ctx;
@@ -457,6 +470,89 @@ int smi_dev_fri_fold_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t 
     DeviceGuard dg__(ctx);
     SMI_TRY(ext_field_check(ctx));
     return launch_fold_ext(ctx, d_in, len, stride, d_alpha, offset, omega, d_out, out_stride);
+}
+
+// ------------------------------------------------------------------------- fold by 4 over the quartic extension
+// Element i of the output (i < q = len / 4) is fold4_element_ext (fri_core.h) of elements i, i + q, i + 2 q, i + 3 q: the
+// two folds fri_fold_ext_kernel makes in two launches, in registers.  16 words in, 4 out per output element: 80 B, against
+// 96 + 48 for the pair.  VEC: a lane takes four consecutive outputs, every access 16 bytes (all bases 16-byte aligned;
+// strides and q multiples of 4); otherwise one output per lane, 4-byte accesses.  The largest index read is
+// 3 stride + 3 q + i < 4 stride, the largest written 3 out_stride + i < 4 out_stride.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fri_fold4_ext_kernel(const uint32_t *__restrict__ in, size_t stride, uint32_t q,
+                                                            const uint64_t *__restrict__ alpha_ptr, uint32_t g_m, Fp F, ScaleTables S,
+                                                            uint32_t inv2_m, uint32_t iota_inv_m, uint32_t *__restrict__ out, size_t out_stride) {
+    const uint64_t a[4] = {alpha_ptr[0], alpha_ptr[1], alpha_ptr[2], alpha_ptr[3]};
+    const Fold4Alpha A = fold4_ext_alpha(a, g_m, F);
+    const uint32_t step = gridDim.x * blockDim.x;
+    if constexpr (VEC) {
+        for (uint32_t i = 4 * (blockIdx.x * blockDim.x + threadIdx.x); i < q; i += 4 * step) {
+            uint32_t v[4][4][4], res[4][4];   // v[coset slot][coordinate][element], res[coordinate][element]
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const uint4 w = *(const uint4 *)(in + e * stride + (size_t)j * q + i);
+                    v[j][e][0] = w.x; v[j][e][1] = w.y; v[j][e][2] = w.z; v[j][e][3] = w.w;
+                }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint32_t c[4][4], o[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) c[j][e] = v[j][e][k];
+                fold4_element_ext(c, i + k, A, inv2_m, iota_inv_m, S, F, o);
+#pragma unroll
+                for (int e = 0; e < 4; e++) res[e][k] = o[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) *(uint4 *)(out + e * out_stride + i) = make_uint4(res[e][0], res[e][1], res[e][2], res[e][3]);
+        }
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < q; i += step) {
+            uint32_t c[4][4], o[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) c[j][e] = in[e * stride + (size_t)j * q + i];
+            fold4_element_ext(c, i, A, inv2_m, iota_inv_m, S, F, o);
+#pragma unroll
+            for (int e = 0; e < 4; e++) out[e * out_stride + i] = o[e];
+        }
+    }
+}
+
+// The grid is capped at 2048 workgroups of 256 lanes as launch_fold_ext's is: with four outputs a lane the grid-stride loop
+// makes a second trip from q = 2^22 on, that is from len = 2^24.
+static int launch_fold4_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset, uint64_t omega,
+                            uint32_t *d_out, size_t out_stride) {
+    const uint32_t p = ctx->fs.F.p;
+    if (len < 4 || !is_pow2(len) || len > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold4_ext: codeword length must be a power of two in 4 .. 2^27");
+    const size_t q = len / 4;
+    if (stride < len || out_stride < q) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fold4_ext: stride < len or out_stride < len / 4");
+    if (offset >= p || omega >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "fold: offset/omega must be < p");
+    ScaleScope pin__(ctx);
+    ScaleTables S;
+    SMI_TRY(fri_fold_tables(ctx, (uint32_t)offset, (uint32_t)omega, len / 2, &S));   // q entries; refuses a zero offset / omega
+    const uint32_t g_m = (uint32_t)(((uint64_t)ctx->fs.g << 32) % p);
+    const uint32_t iota_inv = host_powmod(h_inv(ctx, (uint32_t)omega), q, p), iota_inv_m = (uint32_t)(((uint64_t)iota_inv << 32) % p);
+    const bool vec = !(q & 3) && !(stride & 3) && !(out_stride & 3) && !(((uintptr_t)d_in | (uintptr_t)d_out) & 15u);
+    const size_t lanes = vec ? q / 4 : q;
+    uint32_t grid = (uint32_t)((lanes + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    ProfScope ps(ctx, "fri_fold4_ext_kernel", 80.0 * (double)q);   // read 4 x 16 B, write 16 B per output element
+    if (vec) fri_fold4_ext_kernel<true><<<grid, 256, 0, ctx->stream>>>(d_in, stride, (uint32_t)q, d_alpha, g_m, ctx->fs.F, S, fri_inv2_m(ctx), iota_inv_m, d_out, out_stride);
+    else fri_fold4_ext_kernel<false><<<grid, 256, 0, ctx->stream>>>(d_in, stride, (uint32_t)q, d_alpha, g_m, ctx->fs.F, S, fri_inv2_m(ctx), iota_inv_m, d_out, out_stride);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+int smi_dev_fri_fold4_ext(smi_ctx *ctx, const uint32_t *d_in, size_t len, size_t stride, const uint64_t *d_alpha, uint64_t offset, uint64_t omega,
+                          uint32_t *d_out, size_t out_stride) {
+    if (!ctx || !d_in || !d_alpha || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(ext_field_check(ctx));
+    return launch_fold4_ext(ctx, d_in, len, stride, d_alpha, offset, omega, d_out, out_stride);
 }
 
 // F_q on the host, no context (smi_air_plan's kind): plain canonical coordinates in and out
@@ -980,6 +1076,142 @@ int smi_dev_fri_prove_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_
     DeviceGuard dg__(ctx);
     FriExtResult res;
     SMI_TRY(fri_run_ext(ctx, cfg, &seed, d_codeword, len, stride, true, &res, (int)grind_bits));
+    if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    if (nonce) *nonce = res.nonce;
+    return smi_proof_out(ctx, res.proof, proof, proof_len);
+}
+
+// ------------------------------------------------------------------------- extension FRI at folding factor 4
+// (include/stark_mi.h, "Extension FRI, folding factor 4").  A sibling of fri_run_ext, which stays as it is: F + 1 codewords
+// of lengths N / 4^r, each committed by a tree of coset leaves (leaf i = the 16 coordinates of elements i, i + q, i + 2 q,
+// i + 3 q: launch_merkle_rows over the codeword read as 16 columns q apart), one fold4 launch between two of them, the
+// nonce always searched.  Per (test, layer) the query kernel writes one coset record and one path.
+struct LayerInfoFold4 {
+    const uint32_t *cw;      // columns 4 q apart
+    const uint8_t *nodes;    // the tree of q leaves
+    uint64_t q, off_cosets, off_paths;
+    uint32_t depth;          // log2 q
+};
+struct LayerTableFold4 {
+    LayerInfoFold4 l[SMI_FRI_MAX_ROUNDS / 2];
+};
+__global__ void query_fold4_kernel(const LayerTableFold4 tab, const uint64_t *top, uint8_t *proof) {
+    const LayerInfoFold4 &L = tab.l[blockIdx.y];
+    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    const uint64_t i = top[s] % L.q;
+    uint8_t *rec = proof + L.off_cosets + (uint64_t)s * (9 + 128);
+    if (lane == 0) {
+        rec[0] = 2;
+        put_u64(rec + 1, 16);
+    }
+    if (lane < 16) put_u64(rec + 9 + 8 * lane, L.cw[(uint64_t)lane * L.q + i]);   // lane = 4 e + j: coordinate e of element i + j q
+    write_path(proof + L.off_paths + (uint64_t)s * (9 + 32ull * L.depth), L.nodes, L.q, L.depth, i, lane);
+}
+
+int fri_run_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
+                      FriExtResult *res, uint32_t grind_bits) {
+    SMI_TRY(ext_field_check(ctx));
+    SMI_TRY(smi_fri_check(ctx, cfg));
+    if (cfg->domain_length != len) return smi_fail(ctx, SMI_ERR_CODEWORD_LEN, "initial codeword length does not match domain length");
+    if (stride < len || len > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext_fold4: stride < len, or len > 2^27");
+    const uint32_t p = ctx->fs.F.p;
+    if (cfg->omega >= p || cfg->offset >= p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "omega/offset must be < p");
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    const FriFold4Layout lay = fri_layout_fold4(*cfg);
+    const uint64_t F = lay.F, t = cfg->num_colinearity_tests;
+    if (lay.R2 == 0) return smi_fail(ctx, SMI_ERR_NO_ROUNDS, "num_rounds() == 0: the reference's verify rejects such a proof");
+    if (t > 2 * lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_ENTROPY, "not enough entropy in indices wrt last codeword");
+    if (t > lay.last_n) return smi_fail(ctx, SMI_ERR_SAMPLE_TOO_MANY, "cannot sample more indices than available in last codeword");
+    if (len < 4) return smi_fail(ctx, SMI_ERR_BAD_ARG, "fri_prove_ext_fold4: a coset leaf needs four elements");
+    const FsSeed fs0 = seed ? *seed : fresh_seed();
+    if (reset_arena) SMI_TRY(arena_reset(ctx));
+    ScaleScope pin__(ctx);
+
+    // what comes back in one copy: proof | top-level indices | nonce, exhausted flag; beside it: fs state | alphas | seed
+    // challenge | reduced | the search's best nonce
+    const size_t off_top = (lay.proof_len + 7) & ~(size_t)7, off_pow = off_top + 8 * (t + 1), back_len = off_pow + 16;
+    const size_t m_alpha = (sizeof(FsSeed) + 63) & ~(size_t)63, m_seed_ch = m_alpha + 32 * (F + 1), m_reduced = m_seed_ch + 8;
+    const size_t m_best = m_reduced + 8 * (t + 1);
+    uint8_t *misc = (uint8_t *)arena_alloc(ctx, m_best + 8);
+    uint8_t *d_proof = (uint8_t *)arena_alloc(ctx, back_len);
+    if (!misc || !d_proof) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext_fold4: device memory");
+    FsSeed *d_fs = (FsSeed *)misc;
+    uint64_t *d_alphas = (uint64_t *)(misc + m_alpha), *d_seed_ch = (uint64_t *)(misc + m_seed_ch), *d_reduced = (uint64_t *)(misc + m_reduced);
+    uint64_t *d_top = (uint64_t *)(d_proof + off_top);
+    fs_init_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, fs0);
+
+    // A coset leaf reads its codeword as 16 columns q apart, which needs the four coordinate columns exactly len apart.  A
+    // caller's strided first codeword is compacted once (16 N bytes moved, against the 16 N the first tree reads anyway);
+    // every later codeword is allocated here with stride == length.
+    const uint32_t *cur = d_codeword;
+    if (stride != len) {
+        uint32_t *packed = (uint32_t *)arena_alloc(ctx, 16 * len);
+        if (!packed) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext_fold4: codeword");
+        HIP_TRY(ctx, hipMemcpy2DAsync(packed, 4 * len, d_codeword, 4 * stride, 4 * len, 4, hipMemcpyDeviceToDevice, ctx->stream));
+        cur = packed;
+    }
+    LayerTableFold4 tab;
+    memset(&tab, 0, sizeof tab);
+    uint32_t omega = (uint32_t)cfg->omega, offset = (uint32_t)cfg->offset;
+    for (uint64_t r = 0; r <= F; r++) {
+        const uint64_t n = len >> (2 * r), q = n / 4;
+        const bool last = r == F;
+        uint8_t *nodes = (uint8_t *)arena_alloc(ctx, (2 * q - 1) * 32);
+        if (!nodes) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext_fold4: tree");
+        SMI_TRY(launch_merkle_rows(ctx, cur, 16, q, q, nodes));
+        fs_round_ext_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, (const uint32_t *)(nodes + (2 * q - 2) * 32), d_proof + 33 * r, last ? nullptr : d_alphas + 4 * r);
+        HIP_TRY(ctx, hipGetLastError());
+        if (last) break;
+        LayerInfoFold4 &L = tab.l[r];
+        L.cw = cur;
+        L.nodes = nodes;
+        L.q = q;
+        L.off_cosets = lay.off_cosets[r];
+        L.off_paths = lay.off_paths[r];
+        L.depth = ilog2(q);
+        uint32_t *next = (uint32_t *)arena_alloc(ctx, 16 * q);
+        if (!next) return smi_fail(ctx, SMI_ERR_OOM, "fri_prove_ext_fold4: codeword");
+        SMI_TRY(launch_fold4_ext(ctx, cur, n, n, d_alphas + 4 * r, offset, omega, next, q));
+        cur = next;
+        omega = h_pow(ctx, omega, 4);
+        offset = h_pow(ctx, offset, 4);
+    }
+    emit_codeword_ext_kernel<<<(uint32_t)((4 * lay.last_n + 255) / 256), 256, 0, ctx->stream>>>(cur, lay.last_n, lay.last_n, d_proof + lay.off_last);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long *d_best = (unsigned long long *)(misc + m_best);
+    SMI_TRY(launch_grind(ctx, d_fs, grind_bits, 0, d_best));
+    grind_finish_kernel<<<1, 64, 0, ctx->stream>>>(d_fs, d_best, d_proof + lay.off_nonce, (uint64_t *)(d_proof + off_pow));
+    HIP_TRY(ctx, hipGetLastError());
+    SMI_TRY(launch_fs_challenge(ctx, d_fs, d_seed_ch, (fs0.phase + 8) & 31u));
+    SMI_TRY(launch_sample_indices(ctx, d_seed_ch, F ? len / 4 : len, lay.last_n, (uint32_t)t, d_top, d_reduced));
+    if (F && t > 0) {
+        query_fold4_kernel<<<dim3((uint32_t)t, (uint32_t)F), 64, 0, ctx->stream>>>(tab, d_top, d_proof);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    uint8_t *land = nullptr;
+    SMI_TRY(ctx_pin_out(ctx, back_len, &land));
+    HIP_TRY(ctx, hipMemcpyAsync(land, d_proof, back_len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t back[2];
+    memcpy(back, land + off_pow, 16);
+    if (back[1]) return smi_fail(ctx, SMI_ERR_GRIND_EXHAUSTED, "proof of work: no nonce below 2^(grind_bits + 6) meets the difficulty");
+    res->nonce = back[0];
+    res->proof.assign(land, land + lay.proof_len);
+    res->top.assign(t + 1, 0);
+    if (t) memcpy(res->top.data(), land + off_top, 8 * t);
+    return SMI_OK;
+}
+
+int smi_dev_fri_prove_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint32_t *d_codeword,
+                                size_t len, size_t stride, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, uint32_t grind_bits,
+                                uint64_t *nonce) {
+    if (!ctx || !cfg || !d_codeword || !proof || !proof_len || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    FsSeed seed;
+    hashc::fs_seed(transcript, transcript_len, seed.s, &seed.phase);
+    DeviceGuard dg__(ctx);
+    FriExtResult res;
+    SMI_TRY(fri_run_ext_fold4(ctx, cfg, &seed, d_codeword, len, stride, true, &res, grind_bits));
     if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
     if (nonce) *nonce = res.nonce;
     return smi_proof_out(ctx, res.proof, proof, proof_len);

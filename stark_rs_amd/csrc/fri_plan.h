@@ -58,6 +58,36 @@ inline FriLayout fri_layout_ext(const smi_fri_cfg &cfg, bool pow = false) {
     return l;
 }
 
+// Extension FRI at folding factor 4 (include/stark_mi.h, "Extension FRI, folding factor 4"): with R2 the reference's round
+// count, F = (R2 - 1) / 2 folds and F + 1 committed codewords, layer r of length N / 4^r; the last one, of length
+// N / 4^F, in the clear; the nonce record always present; per layer t coset records of 16 values and t paths of
+// log2(n_r / 4) digests.
+struct FriFold4Layout {
+    uint64_t R2, F, last_n;
+    size_t off_last, off_nonce, off_layers, proof_len;
+    size_t off_cosets[SMI_FRI_MAX_ROUNDS / 2], off_paths[SMI_FRI_MAX_ROUNDS / 2];   // layers 0 .. F - 1
+};
+inline FriFold4Layout fri_layout_fold4(const smi_fri_cfg &cfg) {
+    FriFold4Layout l = {};
+    const uint64_t N = cfg.domain_length, t = cfg.num_colinearity_tests;
+    l.R2 = fri_layout(cfg, false).R;
+    l.F = l.R2 ? (l.R2 - 1) / 2 : 0;
+    l.last_n = N >> (2 * l.F);
+    l.off_last = 33 * (l.F + 1);
+    l.off_nonce = l.off_last + 9 + 32 * l.last_n;
+    l.off_layers = l.off_nonce + SMI_GRIND_RECORD_BYTES;
+    size_t off = l.off_layers;
+    for (uint64_t r = 0; r < l.F; r++) {
+        const uint32_t d = ilog2(N >> (2 * r)) - 2;   // log2 q_r
+        l.off_cosets[r] = off;
+        off += (9 + 128) * t;
+        l.off_paths[r] = off;
+        off += t * (9 + 32ull * d);
+    }
+    l.proof_len = off;
+    return l;
+}
+
 // The fused tail (hash.hip, fri_tail_kernel) finishes every remaining round in one workgroup launch.  It runs the
 // sixteen-lane Fiat-Shamir round, which knows phase 0 only, and holds at most max_rounds rounds.
 inline bool fri_tail_starts(uint32_t phase, uint64_t len, uint64_t tail_len, uint64_t rounds_left, uint64_t max_rounds) {

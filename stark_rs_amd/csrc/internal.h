@@ -273,6 +273,12 @@ struct FriExtResult {
 int fri_run_ext(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
                 FriExtResult *res, int grind = SMI_GRIND_NONE);
 int grind_bits_check(smi_ctx *ctx, uint32_t bits);   // SMI_ERR_BAD_ARG above SMI_GRIND_MAX_BITS (fri.hip)
+// the AIR proof over FRI at folding factor 4 compares the composition with the layer-0 coset record: refused (SMI_ERR_BAD_ARG)
+// by prover and verifier when the FRI part has no fold
+#define AIR_FOLD4_NO_LAYER "air fold4: FRI has no fold at this shape (F = 0), so there is no layer-0 coset to compare the composition with"
+// extension FRI at folding factor 4 (fri.hip): the nonce is always searched, res->nonce always set
+int fri_run_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const FsSeed *seed, const uint32_t *d_codeword, size_t len, size_t stride, bool reset_arena,
+                      FriExtResult *res, uint32_t grind_bits);
 
 // launches (defined in the .hip files; every function one .hip file defines and another calls is declared here, once --
 // the MgSide ones in mgpu_core.h)

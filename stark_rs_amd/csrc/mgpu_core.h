@@ -144,6 +144,29 @@ SMI_HD void mg_row_open_write(const uint32_t *cols, uint64_t stride, uint32_t W,
     }
 }
 
+// The same section for the AIR proof over FRI at folding factor 4 (include/stark_mi.h, "Extension FRI, folding factor 4"):
+// record k of test s is the row at a + (k & 3) N / 4, a = top mod N / 4 -- the four points of the layer-0 coset --, and for
+// k >= 4 (R == 8) the row `shift` further, mod N.  Layout and lengths as above (mg_row_open_bytes with R = 4 or 8).
+SMI_HD void mg_row_open4_write(const uint32_t *cols, uint64_t stride, uint32_t W, const uint8_t *nodes, uint32_t depth, uint64_t top_index,
+                               uint32_t s, uint32_t k, uint32_t t, uint8_t *out, uint32_t lane, uint32_t n_lanes, uint32_t R, uint64_t shift) {
+    const uint64_t N = 1ull << depth, q = N / 4, a = top_index % q, rec = 9 + 8ull * W, prec = 9 + 32ull * depth;
+    const uint64_t pos = (a + (k & 3) * q + (k & 4 ? shift : 0)) & (N - 1);
+    uint8_t *row = out + ((uint64_t)s * R + k) * rec;
+    uint8_t *path = out + (uint64_t)t * R * rec + ((uint64_t)s * R + k) * prec;
+    if (lane == 0) {
+        row[0] = 2;
+        mg_put_u64(row + 1, W);
+        path[0] = 3;
+        mg_put_u64(path + 1, depth);
+    }
+    for (uint32_t c = lane; c < W; c += n_lanes) mg_put_u64(row + 9 + 8ull * c, cols[c * stride + pos]);
+    for (uint32_t b = lane; b < 32 * depth; b += n_lanes) {
+        const uint32_t l = b >> 5;
+        const uint64_t sib = (pos >> l) ^ 1;
+        path[9 + b] = nodes[(2 * N - ((2 * N) >> l) + sib) * 32 + (b & 31)];
+    }
+}
+
 // column_open_kernel on the context's stream (stark.hip; mgpu.hip and air.hip call it too)
 struct smi_ctx;
 int launch_column_open(smi_ctx *ctx, const MgSide *d_cols, uint32_t W, const uint64_t *d_top, uint32_t t, int rank, uint8_t *d_out);

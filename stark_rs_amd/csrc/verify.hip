@@ -239,6 +239,32 @@ struct ExtFri {
     }
 };
 
+// Two steps every walk below takes the same way (fri_walk, fri_walk_fold4).
+// The last layer's domain after `squarings` squarings of (omega, offset) -> *last_offset.  The reference interpolates over
+// the point list offset_L * omega_L^i; the transform needs that list to be the coset of the 2^k-th roots (any prover that
+// folded a codeword over a proper domain has it).
+int last_domain(smi_ctx *ctx, const smi_fri_cfg &cfg, uint64_t squarings, size_t n_last, uint64_t *last_offset) {
+    const uint64_t p = ctx->fs.F.p;
+    uint64_t last_omega = cfg.omega % p;
+    *last_offset = cfg.offset % p;
+    for (uint64_t i = 0; i < squarings; i++) {
+        last_omega = mulm(last_omega, last_omega, p);
+        *last_offset = mulm(*last_offset, *last_offset, p);
+    }
+    if (n_last > ((uint64_t)1 << ctx->fs.K) || last_omega != h_root(ctx, ilog2(n_last)) || *last_offset == 0)
+        return smi_fail(ctx, SMI_ERR_NOT_GEOMETRIC, "Fri::verify: the last layer's domain is not offset * <primitive root>");
+    return SMI_OK;
+}
+// The nonce record (`no`: the popped object, or nullptr): one u64 (not a field element), checked with one hash at the
+// difficulty `grind`, then absorbed into fs; *seed_phase: the transcript's phase behind it.
+int nonce_record(smi_ctx *ctx, int *accept, const Obj *no, uint32_t fs[16], uint32_t phase, int grind, uint32_t *seed_phase) {
+    if (!no || no->tag != 2) return reject(ctx, accept, "proof of work: failed to extract the nonce");
+    if (no->count != 1) return reject(ctx, accept, "proof of work: the nonce record must hold exactly one value");
+    const uint64_t word = hashc::grind_word(fs, phase, get_u64(no->p), fs, seed_phase);
+    if (word & ((1ull << (grind & 63)) - 1)) return reject(ctx, accept, "proof of work");
+    return SMI_OK;
+}
+
 // Fri::verify on objs[0..] with the transcript the caller's FiatShamir holds (fs0, hash_core.h fs_seed); *used = objects
 // consumed on acceptance.  The challenges continue the seed one root at a time instead of re-hashing the transcript.
 // pv_val gets Kind::NE values per entry, layer0_ab 2 Kind::NE per test (a, then b).
@@ -278,24 +304,11 @@ int fri_walk(smi_ctx *ctx, const Kind &K, const smi_fri_cfg &cfg, const FsSeed &
     if (memcmp(last_root, roots.back(), 32) != 0) return reject(ctx, accept, "last codeword is not well formed");
     const size_t degree_bound = n_last / cfg.expansion_factor;                      // :360-365
     if (degree_bound == 0) return reject(ctx, accept, "last codeword too small");
-    uint64_t last_omega = cfg.omega % p, last_offset = cfg.offset % p;
-    for (uint64_t i = 0; i + 1 < R; i++) {
-        last_omega = mulm(last_omega, last_omega, p);
-        last_offset = mulm(last_offset, last_offset, p);
-    }
-    // The reference interpolates over the point list offset_L * omega_L^i; the transform needs that list
-    // to be the coset of the 2^k-th roots (any prover that folded a codeword over a proper domain has it).
-    if (n_last > ((uint64_t)1 << ctx->fs.K) || last_omega != h_root(ctx, ilog2(n_last)) || last_offset == 0)
-        return smi_fail(ctx, SMI_ERR_NOT_GEOMETRIC, "Fri::verify: the last layer's domain is not offset * <primitive root>");
+    uint64_t last_offset = 0;
+    SMI_TRY(last_domain(ctx, cfg, R - 1, n_last, &last_offset));
     SMI_TRY(K.low_degree(ctx, accept, lo->p, n_last, last_offset, degree_bound));
     uint32_t seed_phase = fs0.phase;
-    if (K.grind != SMI_GRIND_NONE) {   // the nonce record: one u64 (not a field element), checked with one hash, then absorbed
-        const Obj *no = pop();
-        if (!no || no->tag != 2) return reject(ctx, accept, "proof of work: failed to extract the nonce");
-        if (no->count != 1) return reject(ctx, accept, "proof of work: the nonce record must hold exactly one value");
-        const uint64_t word = hashc::grind_word(fs, fs0.phase, get_u64(no->p), fs, &seed_phase);
-        if (word & ((1ull << (K.grind & 63)) - 1)) return reject(ctx, accept, "proof of work");
-    }
+    if (K.grind != SMI_GRIND_NONE) SMI_TRY(nonce_record(ctx, accept, pop(), fs, fs0.phase, K.grind, &seed_phase));
     // index sampling (:400-405, :168-213)
     std::vector<uint64_t> top;
     SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, seed_phase), N >> 1, N >> (R - 1), t, &top));
@@ -381,6 +394,157 @@ int fri_verify_ext_objs(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0,
                         std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val, std::vector<uint64_t> *layer0_ab, size_t *used, int grind) {
     return fri_walk(ctx, ExtFri{grind}, cfg, fs0, objs, accept, top_out, pv_idx, pv_val, layer0_ab, used);
 }
+// ---- extension FRI at folding factor 4 (include/stark_mi.h, "Extension FRI, folding factor 4")
+// The walk differs from fri_walk in its shape -- F + 1 roots, one coset record and one path per (test, layer), no c -- so it
+// is a walk of its own over ExtFri's rules: the draw, the last codeword's shape and degree, the nonce.  Where a check is
+// fri_walk's, the sentence is fri_walk's (a coset record plays the triple's part); the one new sentence is FOLD4_MISMATCH.
+const char *const FOLD4_MISMATCH = FRI_FOLD4_MISMATCH_SENTENCE;   // fri_core.h
+
+// 2^-1 (lo + hi) + alpha ((lo - hi) 2^-1 x^-1) on plain residues; alpha reduced
+void fold_pair_host(uint32_t p, uint32_t g, const uint32_t lo[4], const uint32_t hi[4], uint32_t x_inv, const uint32_t alpha[4], uint32_t out[4]) {
+    const uint32_t inv2 = (p + 1) / 2, t = host_mulmod(inv2, x_inv, p);
+    uint32_t d[4], ad[4];
+    for (int e = 0; e < 4; e++) d[e] = host_mulmod(fp_sub(lo[e], hi[e], p), t, p);
+    ext_mul_host(p, g, d, alpha, ad);
+    for (int e = 0; e < 4; e++) out[e] = fp_add(host_mulmod(fp_add(lo[e], hi[e], p), inv2, p), ad[e], p);
+}
+// the fold by 4 of one coset record (16 values, 4 e + j = coordinate e of slot j) at x = the point of slot 0, iota = omega^q
+void fold4_host(uint32_t p, uint32_t g, const uint64_t rec[16], uint32_t x, uint32_t iota, const uint64_t *alpha_raw, uint32_t out[4]) {
+    uint32_t c[4][4], a1[4], a2[4], y0[4], y1[4];
+    for (int j = 0; j < 4; j++)
+        for (int e = 0; e < 4; e++) c[j][e] = (uint32_t)rec[4 * e + j];
+    for (int e = 0; e < 4; e++) a1[e] = (uint32_t)(alpha_raw[e] % p);
+    ext_mul_host(p, g, a1, a1, a2);
+    const uint32_t x_inv = host_powmod(x, p - 2, p), iota_inv = host_powmod(iota, p - 2, p);
+    fold_pair_host(p, g, c[0], c[2], x_inv, a1, y0);
+    fold_pair_host(p, g, c[1], c[3], host_mulmod(x_inv, iota_inv, p), a1, y1);
+    fold_pair_host(p, g, y0, y1, host_mulmod(x_inv, x_inv, p), a2, out);
+}
+
+// pv_idx / pv_val: the layer-0 cosets, four entries per test (element i + j q_0, j = 0 .. 3) of four values each;
+// layer0: the 16 values of each layer-0 record as they stand
+int fri_walk_fold4(smi_ctx *ctx, const smi_fri_cfg &cfg, const FsSeed &fs0, const std::vector<Obj> &objs, int *accept, std::vector<uint64_t> *top_out,
+                   std::vector<uint64_t> *pv_idx, std::vector<uint64_t> *pv_val, std::vector<uint64_t> *layer0, size_t *used, uint32_t grind) {
+    const ExtFri K{(int)grind};
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g;
+    const uint64_t t = cfg.num_colinearity_tests, N = cfg.domain_length;
+    const FriFold4Layout lay = fri_layout_fold4(cfg);
+    const uint64_t F = lay.F;
+    if (lay.R2 == 0) return reject(ctx, accept, "No FRI roots extracted");
+    if (N < 4) return reject(ctx, accept, "last codeword too small");
+    size_t at = 0;
+    auto pop = [&]() -> const Obj * { return at < objs.size() ? &objs[at++] : nullptr; };
+    uint32_t fs[16];
+    memcpy(fs, fs0.s, sizeof fs);
+    std::vector<const uint8_t *> roots;
+    std::vector<uint64_t> alphas;   // four unreduced values per fold
+    for (uint64_t r = 0; r <= F; r++) {
+        const Obj *o = pop();
+        if (!o || o->tag != 0) return reject(ctx, accept, "Failed to extract Merkle root");
+        roots.push_back(o->p);
+        uint32_t m[8];
+        memcpy(m, o->p, 32);
+        K.draw(fs, m, fs0.phase, r == F, &alphas);
+    }
+    const Obj *lo = pop();
+    if (!lo || lo->tag != 2) return reject(ctx, accept, "Failed to extract last codeword");
+    size_t n_last = (size_t)lay.last_n;
+    SMI_TRY(K.last_shape(ctx, *lo, accept, &n_last));
+    // the last tree: n_last / 4 coset leaves, leaf i = the 16 values (coordinate outer, slot inner) of elements i + j q
+    const size_t q_last = n_last / 4;
+    std::vector<uint8_t> leaf_msgs(128 * q_last), digests(32 * q_last);
+    for (size_t i = 0; i < q_last; i++)
+        for (int e = 0; e < 4; e++)
+            for (int j = 0; j < 4; j++) memcpy(&leaf_msgs[128 * i + 8 * (4 * e + j)], lo->p + 8 * (4 * (i + j * q_last) + e), 8);
+    for (size_t i = 0; i < q_last; i++) {
+        uint32_t d[8];
+        hashc::hash_bytes(&leaf_msgs[128 * i], 128, d);
+        memcpy(&digests[32 * i], d, 32);
+    }
+    uint8_t last_root[32];
+    SMI_TRY(smi_merkle_commit(ctx, digests.data(), q_last, last_root));
+    if (memcmp(last_root, roots.back(), 32) != 0) return reject(ctx, accept, "last codeword is not well formed");
+    const size_t degree_bound = n_last / cfg.expansion_factor;
+    if (degree_bound == 0) return reject(ctx, accept, "last codeword too small");
+    uint64_t last_offset = 0;
+    SMI_TRY(last_domain(ctx, cfg, 2 * F, n_last, &last_offset));   // a fold by 4 squares the domain twice
+    SMI_TRY(K.low_degree(ctx, accept, lo->p, n_last, last_offset, degree_bound));
+    uint32_t seed_phase = fs0.phase;
+    SMI_TRY(nonce_record(ctx, accept, pop(), fs, fs0.phase, (int)grind, &seed_phase));   // always present
+    std::vector<uint64_t> top;
+    SMI_TRY(sample_top(ctx, hashc::fs_challenge_phase(fs, seed_phase), F ? N >> 2 : N, n_last, t, &top));
+    if (top_out) *top_out = top;
+
+    uint64_t om = cfg.omega % p, off = cfg.offset % p;
+    std::vector<uint32_t> folded(4 * t);   // the fold of the previous layer's coset, per test
+    for (uint64_t r = 0; r < F; r++) {
+        const uint64_t q = N >> (2 * r + 2);
+        std::vector<uint64_t> idx(t);
+        std::vector<const uint8_t *> rec(t);
+        std::vector<uint64_t> vals(16 * t);
+        for (uint64_t s = 0; s < t; s++) {
+            idx[s] = top[s] % q;
+            const Obj *o = pop();
+            if (!o || o->tag != 2) return reject(ctx, accept, "Failed to extract triple values");
+            if (o->count != 16) return reject(ctx, accept, "Expected triple of values");
+            rec[s] = o->p;
+            uint64_t *v = &vals[16 * s];
+            for (int k = 0; k < 16; k++)
+                if ((v[k] = get_u64(o->p + 8 * k)) >= p) return reject(ctx, accept, "triple: a coordinate is not canonical");
+            if (r == 0) {
+                if (pv_idx && pv_val)
+                    for (int j = 0; j < 4; j++) {
+                        pv_idx->push_back(idx[s] + j * q);
+                        for (int e = 0; e < 4; e++) pv_val->push_back(v[4 * e + j]);
+                    }
+                if (layer0) layer0->insert(layer0->end(), v, v + 16);
+            }
+        }
+        if (r > 0)   // the previous layer's fold is slot j = i_{r-1} div q of this layer's coset
+            for (uint64_t s = 0; s < t; s++) {
+                const uint64_t j = (top[s] % (4 * q)) / q;
+                for (int e = 0; e < 4; e++)
+                    if (vals[16 * s + 4 * e + j] != folded[4 * s + e]) return reject(ctx, accept, FOLD4_MISMATCH);
+            }
+        const uint32_t depth = ilog2(q);
+        std::vector<uint8_t> paths, leaf, ok(t);
+        for (uint64_t s = 0; s < t; s++) {
+            const Obj *o = pop();
+            if (!o || o->tag != 3) return reject(ctx, accept, "Failed to extract path for aa");
+            if (o->count != depth) return reject(ctx, accept, "merkle authentication path verification fails for aa");
+            paths.insert(paths.end(), o->p, o->p + 32 * o->count);
+        }
+        leaf_digests_host(rec, 128, leaf);   // the record as it stands is the leaf
+        if (t) {
+            if (depth) SMI_TRY(smi_merkle_verify_batch(ctx, leaf.data(), idx.data(), paths.data(), t, depth, roots[r], ok.data()));
+            else
+                for (uint64_t s = 0; s < t; s++) ok[s] = memcmp(&leaf[32 * s], roots[r], 32) == 0;
+        }
+        for (uint64_t s = 0; s < t; s++)
+            if (!ok[s]) return reject(ctx, accept, "merkle authentication path verification fails for aa");
+        const uint32_t iota = (uint32_t)powm(om, q, p);
+        for (uint64_t s = 0; s < t; s++)
+            fold4_host(p, g, &vals[16 * s], (uint32_t)mulm(off, powm(om, idx[s], p), p), iota, &alphas[4 * r], &folded[4 * s]);
+        for (int k = 0; k < 2; k++) {
+            om = mulm(om, om, p);
+            off = mulm(off, off, p);
+        }
+    }
+    if (F)   // the last fold is entry i_{F-1} of the last codeword
+        for (uint64_t s = 0; s < t; s++) {
+            const uint64_t i = top[s] % n_last;
+            for (int e = 0; e < 4; e++)
+                if (get_u64(lo->p + 8 * (4 * i + e)) != folded[4 * s + e]) return reject(ctx, accept, FOLD4_MISMATCH);
+        }
+    *accept = 1;
+    if (used) *used = at;
+    return SMI_OK;
+}
+size_t fri_object_count_fold4(const smi_fri_cfg &cfg) {
+    const FriFold4Layout lay = fri_layout_fold4(cfg);
+    return (size_t)(lay.F + 1 + 2 + lay.F * 2 * cfg.num_colinearity_tests);
+}
+
 size_t fri_object_count(const smi_fri_cfg &cfg) {
     uint64_t R = 0;
     smi_fri_num_rounds(&cfg, &R);
@@ -520,6 +684,30 @@ int smi_fri_verify_ext_pow(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *
     if (accept) *accept = 0;
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     return fri_verify_abi(ctx, cfg, transcript, transcript_len, proof, proof_len, accept, pv_indices, pv_values, n_pv, consumed, true, (int)grind_bits);
+}
+int smi_fri_verify_ext_fold4(smi_ctx *ctx, const smi_fri_cfg *cfg, const uint8_t *transcript, size_t transcript_len, const uint8_t *proof,
+                             size_t proof_len, int *accept, uint64_t *pv_indices, uint64_t *pv_values, size_t *n_pv, size_t *consumed,
+                             uint32_t grind_bits) {
+    if (!ctx) return SMI_ERR_BAD_ARG;
+    if (accept) *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    if (!cfg || (!proof && proof_len) || !accept || (!transcript && transcript_len)) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (n_pv) *n_pv = 0;
+    if (consumed) *consumed = 0;
+    SMI_TRY(ext_field_check(ctx));
+    SMI_TRY(smi_fri_check(ctx, cfg));
+    const FsSeed seed = fs_seed_of(transcript, transcript_len);
+    size_t end = 0;
+    const std::vector<Obj> objs = parse(proof, proof_len, (size_t)-1, &end);
+    std::vector<uint64_t> pi, pv;
+    size_t used = 0;
+    const int rc = fri_walk_fold4(ctx, *cfg, seed, objs, accept, nullptr, &pi, &pv, nullptr, &used, grind_bits);
+    if (n_pv) *n_pv = pi.size();
+    if (pv_indices && !pi.empty()) memcpy(pv_indices, pi.data(), 8 * pi.size());
+    if (pv_values && !pv.empty()) memcpy(pv_values, pv.data(), 8 * pv.size());
+    if (rc == SMI_OK && *accept && consumed) (void)parse(proof, proof_len, used, consumed);
+    return settle(rc);
 }
 
 static int stark_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *column_roots, const uint8_t *proof, size_t proof_len, int *accept) {
@@ -904,6 +1092,89 @@ int smi_air_verify_ext_pow(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(ext_field_check(ctx));
     return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, AirVariant{true, true, (int)grind_bits, nullptr, nullptr}));
+}
+
+// Verifier of smi_dev_air_prove_ext_fold4 (include/stark_mi.h, "Extension FRI, folding factor 4"): air_verify_impl's row /
+// extension / proof-of-work variant with four points per test instead of two.  The transcript, the section checks
+// (parse_section, auth_section, AIR_WORDS), the periodic operands and the evaluator are the ones air_verify_impl uses; what
+// differs is the FRI walk, the opened positions (the layer-0 coset) and the record the composition is compared with.
+static int air_verify_fold4_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint8_t *root, const uint8_t *proof, size_t proof_len,
+                                 int *accept, uint32_t grind) {
+    std::string why;
+    uint64_t E = 0;
+    const int vrc = air_validate(ctx->fs.F.p, cfg, air, nullptr, &E, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint64_t p = ctx->fs.F.p, N = 1ull << logN, B = 1ull << cfg->log_blowup, t = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
+    {
+        const FriFold4Layout lay = fri_layout_fold4(fc);
+        if (lay.R2 && lay.F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, AIR_FOLD4_NO_LAYER);
+    }
+    Transcript tr;
+    std::vector<uint64_t> weights;
+    transcript_ext(tr, root, W, K, &weights);
+    size_t end = 0;
+    const std::vector<Obj> objs = parse(proof, proof_len, fri_object_count_fold4(fc), &end);
+    std::vector<uint64_t> top, coset;   // coset: the 16 values of every layer-0 record
+    size_t used = 0;
+    SMI_TRY(fri_walk_fold4(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &coset, &used, grind));
+    *accept = 0;
+    const OpeningWords &say = AIR_WORDS;
+    const size_t R = K ? 8 : 4, m = R * t, prec = 9 + 32 * (size_t)logN;
+    if (proof_len - end != m * (9 + 8 * (size_t)W) + m * prec) return reject(ctx, accept, say.length);
+    const uint8_t *sec = proof + end;
+    std::vector<uint64_t> pos(m);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < R; k++) pos[R * s + k] = (top[s] % (N / 4) + (k & 3) * (N / 4) + (k & 4 ? B : 0)) & (N - 1);
+    std::vector<uint64_t> rows;
+    SMI_TRY(parse_section(ctx, accept, say, sec, m, W, logN, ROWS_THEN_PATHS, &rows));
+    SMI_TRY(auth_section(ctx, accept, say, sec, m, W, logN, pos, root));
+    AirHost H;
+    air_build(ctx->fs.F, (uint32_t)fc.omega, cfg, air, &H);
+    const Fp F = ctx->fs.F;
+    const uint32_t Q = air->n_periodic;
+    std::vector<uint32_t> per;   // per[(4 s + k) * 2Q + ..]: Q at this row, Q at the next
+    if (Q) {
+        std::vector<uint64_t> at(4 * t);
+        for (uint64_t s = 0; s < t; s++)
+            for (size_t k = 0; k < 4; k++) at[4 * s + k] = pos[R * s + k];
+        SMI_TRY(air_periodic_at(ctx, cfg, H, at, &per));
+    }
+    std::vector<uint32_t> w_m(4 * AIR_MAX_WEIGHTS, 0);
+    for (uint32_t i = 0; i < 4 * (W + K); i++) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < 4; k++) {
+            const uint64_t i = pos[R * s + k];
+            for (size_t r = k; r < R; r += 4)   // this point's rows, in front of this point's composition
+                for (uint32_t c = 0; c < W; c++)
+                    if (rows[(R * s + r) * W + c] >= p) return reject(ctx, accept, say.canonical);
+            const uint64_t *cur = &rows[(R * s + k) * W], *nxt = R == 8 ? &rows[(R * s + k + 4) * W] : nullptr;
+            const uint64_t x = mulm(cfg->lde_offset, powm(fc.omega, i, p), p);
+            const uint32_t x_m = air_to_m((uint32_t)x, (uint32_t)p), ib = (uint32_t)(i & (B - 1));
+            auto operand = [&](int, uint32_t v) {
+                const bool next = v >= W + Q;
+                const uint32_t c = next ? v - (W + Q) : v;
+                if (c >= W) return per[(4 * s + k) * 2 * Q + (next ? Q : 0) + (c - W)];
+                return (uint32_t)(next ? nxt[c] : cur[c]);
+            };
+            uint32_t got[4] = {0, 0, 0, 0};
+            air_compose_points_ext<1>(H.dev, F, w_m.data(), &x_m, &ib, operand, got);
+            for (uint32_t e = 0; e < 4; e++)
+                if (got[e] != coset[16 * s + 4 * e + k]) return reject(ctx, accept, say.composition);
+        }
+    *accept = 1;
+    return SMI_OK;
+}
+int smi_air_verify_ext_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t row_root[32], const uint8_t *proof,
+                             size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !row_root || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    return settle(air_verify_fold4_impl(ctx, cfg, (const smi_air *)air, row_root, proof, proof_len, accept, grind_bits));
 }
 
 // Verifier of smi_dev_air_prove_perm (include/stark_mi.h, "Permutation argument"): the extension verifier with proof of

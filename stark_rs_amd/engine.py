@@ -399,6 +399,18 @@ class Engine:
         out_stride = length // 2 if out_stride is None else out_stride
         self._ck(self.L.smi_dev_fri_fold_ext(self.h, vp(d_in), length, stride, vp(d_alpha), offset, omega, vp(d_out), out_stride))
 
+    def dev_fri_fold4_ext(self, d_in, length, stride, d_alpha, offset, omega, d_out, out_stride=None):
+        """smi_dev_fri_fold4_ext: the fold by 4 of a codeword over the quartic extension in one launch -- what
+        dev_fri_fold_ext gives under alpha over (offset, omega, length) and then under alpha^2 over (offset^2, omega^2,
+        length / 2); four columns out_stride (default length / 4) apart out"""
+        out_stride = length // 4 if out_stride is None else out_stride
+        self._ck(self.L.smi_dev_fri_fold4_ext(self.h, vp(d_in), length, stride, vp(d_alpha), offset, omega, vp(d_out), out_stride))
+
+    @staticmethod
+    def fri_fold4_layout(cfg):
+        """smi_fri_fold4_layout (host only) -> (folds, last codeword length, proof bytes) of extension FRI at folding factor 4"""
+        return fri_fold4_layout(cfg)
+
     def dev_fri_fold_shard(self, d_lo, d_hi, count, index0, full_len, d_alpha, offset, omega, d_out):
         self._ck(self.L.smi_dev_fri_fold_shard(self.h, vp(d_lo), vp(d_hi), count, index0, full_len, vp(d_alpha), offset, omega,
                                                vp(d_out)))
@@ -431,35 +443,44 @@ class Engine:
         """smi_grind_check (host only) -> pow_ok(transcript, nonce, bits)"""
         return grind_check(transcript, nonce, bits)
 
-    def dev_fri_prove_ext(self, cfg, d_codeword, length, stride=None, transcript=b"", grind_bits=None):
+    def dev_fri_prove_ext(self, cfg, d_codeword, length, stride=None, transcript=b"", grind_bits=None, folding=2):
         """smi_dev_fri_prove_ext: Fri::prove over the quartic extension on four device coordinate columns `stride`
         (default length) apart, continuing the caller's transcript (host bytes) -> (proof bytes, top-level indices).
-        grind_bits (None: no grinding, today's stream): smi_dev_fri_prove_ext_pow -> (proof bytes, top-level indices, nonce)"""
+        grind_bits (None: no grinding, today's stream): smi_dev_fri_prove_ext_pow -> (proof bytes, top-level indices, nonce).
+        folding=4: smi_dev_fri_prove_ext_fold4 -> (proof bytes, top-level indices, nonce); grind_bits None means 0 there"""
+        _check_folding(folding)
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(cfg.num_colinearity_tests, 1), dtype=np.uint64)
         t = bytes(transcript)
         args = (self.h, C.byref(cfg), t if t else None, len(t), vp(d_codeword), length, length if stride is None else stride, C.byref(proof),
                 C.byref(plen), top.ctypes.data)
         nonce = C.c_uint64()
-        if grind_bits is None:
+        if folding == 4:
+            self._ck(self.L.smi_dev_fri_prove_ext_fold4(*args, grind_bits or 0, C.byref(nonce)))
+        elif grind_bits is None:
             self._ck(self.L.smi_dev_fri_prove_ext(*args))
         else:
             self._ck(self.L.smi_dev_fri_prove_ext_pow(*args, grind_bits, C.byref(nonce)))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         top = [int(v) for v in top[:cfg.num_colinearity_tests]]
-        return (b, top) if grind_bits is None else (b, top, int(nonce.value))
+        return (b, top) if grind_bits is None and folding == 2 else (b, top, int(nonce.value))
 
-    def fri_verify_ext(self, cfg, proof: bytes, transcript=b"", grind_bits=None):
+    def fri_verify_ext(self, cfg, proof: bytes, transcript=b"", grind_bits=None, folding=2):
         """smi_fri_verify_ext -> (accept, polynomial_values [(index, [c0, c1, c2, c3])], bytes consumed, reason).
-        grind_bits (None: a proof without grinding): smi_fri_verify_ext_pow, the least difficulty demanded"""
+        grind_bits (None: a proof without grinding): smi_fri_verify_ext_pow, the least difficulty demanded.
+        folding=4: smi_fri_verify_ext_fold4 (grind_bits None means 0); polynomial_values holds the layer-0 cosets, four
+        entries per test"""
+        _check_folding(folding)
         t = bytes(transcript)
-        n = 2 * max(cfg.num_colinearity_tests, 1)
+        n = (4 if folding == 4 else 2) * max(cfg.num_colinearity_tests, 1)
         idx, val = np.zeros(n, dtype=np.uint64), np.zeros(4 * n, dtype=np.uint64)
         acc, npv, used = C.c_int(), C.c_size_t(), C.c_size_t()
         args = (self.h, C.byref(cfg), t if t else None, len(t), proof, len(proof), C.byref(acc), idx.ctypes.data, val.ctypes.data, C.byref(npv),
                 C.byref(used))
-        if grind_bits is None:
+        if folding == 4:
+            self._ck(self.L.smi_fri_verify_ext_fold4(*args, grind_bits or 0))
+        elif grind_bits is None:
             self._ck(self.L.smi_fri_verify_ext(*args))
         else:
             self._ck(self.L.smi_fri_verify_ext_pow(*args, grind_bits))
@@ -679,8 +700,15 @@ class Engine:
             return True, None, None, ""
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
+    def _check_air_folding(self, a, folding, row_leaves, ext):
+        _check_folding(folding)
+        if folding == 4 and not (row_leaves and ext):
+            raise StarkMiError(-50, "folding=4 runs over the row-committed extension proof: pass row_leaves=True, ext=True")
+        if folding == 4 and any(f(a) is not None for f in (self._xargs, self._args, self._lookup, self._perm)):
+            raise StarkMiError(-50, "folding=4: the permutation, lookup and argument-list provers fold by 2 only")
+
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False):
+                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -696,8 +724,12 @@ class Engine:
         An AIR with an argument list (mirror.Air.add_permutation / add_lookup) takes smi_dev_air_prove_args in the same way: the
         sixth stage is "args", "closes" is a list of A bools, check=True raises naming the arguments that do not close, and
         fill_multiplicities=True runs dev_lookup_multiplicities once per lookup argument.  A list with selectors or periodic
-        members (mirror.Air.extended_args) takes smi_dev_air_prove_xargs and smi_dev_xargs_multiplicities instead."""
+        members (mirror.Air.extended_args) takes smi_dev_air_prove_xargs and smi_dev_xargs_multiplicities instead.
+        folding=4 (needs row_leaves=True, ext=True and an AIR without permutation, lookup or argument list; StarkMiError
+        otherwise, and for any value but 2 and 4): smi_dev_air_prove_ext_fold4 -- FRI at folding factor 4, the rows opened at
+        the four points of every layer-0 coset; grind_bits None counts as 0."""
         a = self._air(air)
+        self._check_air_folding(a, folding, row_leaves, ext)
         if self._xargs(a) is not None:
             if not (row_leaves and ext):
                 raise ValueError("dev_air_prove: an AIR with an argument list needs row_leaves=True, ext=True")
@@ -827,7 +859,9 @@ class Engine:
         prove = self.L.smi_dev_air_prove_ext if ext else (self.L.smi_dev_air_prove_rows if row_leaves else self.L.smi_dev_air_prove)
         args = (self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data,
                 stage if timed else None)
-        if grind_bits is None:
+        if folding == 4:
+            self._ck(self.L.smi_dev_air_prove_ext_fold4(*args, grind_bits or 0))
+        elif grind_bits is None:
             self._ck(prove(*args))
         else:
             self._ck(self.L.smi_dev_air_prove_ext_pow(*args, grind_bits))
@@ -839,14 +873,16 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None):
+                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
         column_roots is root_1 then root_2, grind_bits None counts as 0.  An AIR with a lookup takes smi_air_verify_lookup in
         the same way, and an AIR with an argument list smi_air_verify_args (smi_air_verify_xargs when the list has selectors
-        or periodic members)."""
+        or periodic members).
+        folding=4: smi_air_verify_ext_fold4, under the conditions of dev_air_prove(folding=4)."""
+        self._check_air_folding(self._air(air), folding, row_leaves, ext)
         if self._xargs(self._air(air)) is not None:
             if not (row_leaves and ext):
                 raise ValueError("air_verify: an AIR with an argument list needs row_leaves=True, ext=True")
@@ -907,7 +943,9 @@ class Engine:
         if row_leaves and roots.size != 32:
             raise StarkMiError(-50, "air_verify(row_leaves=True) takes the one 32-byte root of the row tree")
         args = (self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc))
-        if grind_bits is None:
+        if folding == 4:
+            self._ck(self.L.smi_air_verify_ext_fold4(*args, grind_bits or 0))
+        elif grind_bits is None:
             self._ck(verify(*args))
         else:
             self._ck(self.L.smi_air_verify_ext_pow(*args, grind_bits))
@@ -1064,6 +1102,21 @@ def grind_check(transcript, nonce, bits):
     if st:
         raise StarkMiError(st, _lib.status_string(st))
     return bool(ok.value)
+
+
+def _check_folding(folding):
+    if folding not in (2, 4):
+        raise StarkMiError(-50, f"folding must be 2 or 4, not {folding!r}")
+
+
+def fri_fold4_layout(cfg):
+    """smi_fri_fold4_layout (host only, no GPU) -> (folds, last codeword length, proof bytes) of extension FRI at folding
+    factor 4 for this FriCfg"""
+    folds, last, plen = C.c_uint64(), C.c_uint64(), C.c_size_t()
+    st = _lib.lib().smi_fri_fold4_layout(C.byref(cfg), C.byref(folds), C.byref(last), C.byref(plen))
+    if st:
+        raise StarkMiError(st, _lib.status_string(st))
+    return int(folds.value), int(last.value), int(plen.value)
 
 
 def default_engine(p=P_REF, g=G_REF, device=0):

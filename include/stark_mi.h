@@ -1072,6 +1072,93 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
 int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
                          size_t proof_len, int *accept, uint32_t grind_bits);
 
+/* ---- Out-of-domain sampling (DEEP): FRI at the full blowup -------------------------------------
+ * The AIR proofs above recompute the composition at the t queried positions only, so their FRI runs at E = B / D, an AIR
+ * with E < 4 is refused, and every test opens the next rows (a + B, b + B) as well.  Here the constraint check moves to one
+ * random point z of F_q ("out-of-domain sampling", listed as left out by "AIR" and "Quartic extension" above: this section
+ * is that step).  The composition is committed in D segments of degree < n, everything FRI sees has degree < n, FRI runs at
+ * E = B whatever the AIR's degree is, the + B rows disappear and every AIR with D <= B is provable -- mimc at
+ * log_blowup = 2, for one.  The variant stands next to smi_dev_air_prove_ext_pow: row leaves, extension weights, extension
+ * FRI folding by 2, the nonce record always present (grind_bits = 0 accepts nonce 0).  It takes a plain AIR -- boundary
+ * points, transition constraints, periodic columns -- and has no permutation, lookup or argument-list form and no
+ * folding factor 4.  Every entry point above is unchanged, byte for byte.
+ *
+ * Notation of "AIR": W, K, Q, n, B, N = n B, tau, h, w = omega_n, x_i = h omega_N^i, f_c the trace polynomials, term_c,
+ *   tq_k, pi_j; d and D as smi_air_plan computes them.
+ * Plan (smi_air_plan_deep).  smi_air_plan's checks, except its bound on E, which plays no part.  Refused: D > B
+ *   (SMI_ERR_BAD_ARG: the composition has degree < D n and must fit the N points); B < 4 (SMI_ERR_EXPANSION_TOO_SMALL);
+ *   4 D > 64 (SMI_ERR_BAD_ARG: the widest row the leaf hash takes).
+ * Prover.
+ *   1. smi_dev_lde of the trace, the row tree over it: root_1.  The transcript starts empty and absorbs root_1.
+ *   2. For m = 0 .. 4 (W + K) - 1 absorb m as 8 little-endian bytes and take challenge(): the composition weights of
+ *      smi_dev_air_prove_ext.  H = the codeword of smi_dev_air_compose_ext under them, four coordinate columns.
+ *   3. Segments.  The coefficients of every coordinate of H on the coset h <omega_N> (an inverse coset transform of size N);
+ *      H(x) = sum_{j<D} x^(j n) H_j(x) with H_j the coefficients j n .. (j + 1) n - 1 (those at and above D n are dropped: an
+ *      honest H has none); every coordinate of every H_j extended back to the N points, 4 D columns; the second tree is
+ *      smi_dev_merkle_build_rows(n_cols = 4 D) over them, row value 4 j + e = coordinate e of H_j.  Its root is root_2,
+ *      which is absorbed.
+ *   4. For m = 4 (W + K) .. 4 (W + K) + 3 absorb m and take challenge(): the coordinates of z mod p.  If coordinates 1 .. 3
+ *      are all zero z lies in F_p: the prover returns SMI_ERR_BAD_ARG with a sentence and the verifier rejects with the same
+ *      sentence (probability about p^-3).  For every other z each denominator below is non-zero, since the n-th roots of
+ *      unity of F_q all lie in F_p.
+ *   5. u_c = f_c(z) and v_c = f_c(z w) for c < W from the trace polynomials' coefficients (smi_dev_ntt, inverse, offset tau),
+ *      s_j = H_j(z) for j < D.  One tag-2 record of 4 (2 W + D) values u_0 .. u_{W-1}, v_0 .. v_{W-1}, s_0 .. s_{D-1}, four
+ *      canonical coordinates each (the v_c are sent when K = 0 as well).  Its payload, 32 (2 W + D) bytes without tag and
+ *      count, is absorbed.
+ *   6. For m = 4 (W + K) + 4 .. 4 (W + K) + 4 + 4 (2 W + D) - 1 absorb m and take challenge(): gamma_c, gamma'_c, gamma''_j in
+ *      record order, four coordinates each, used mod p.  The transcript is then 32 (3 + W + K + 2 (2 W + D)) bytes.
+ *   7. The DEEP codeword over F_q, i < N:
+ *        Q(x_i) = sum_c gamma_c (f_c(x_i) - u_c) / (x_i - z) + sum_c gamma'_c (f_c(x_i) - v_c) / (x_i - z w)
+ *               + sum_j gamma''_j (H_j(x_i) - s_j) / (x_i - z),   of degree < n.
+ *   8. Extension FRI with grinding continues that transcript on h <omega_N> at expansion factor B.
+ *   9. Openings.  Per test a = top mod N/2 and b = a + N/2; two sections in the layout of smi_dev_air_prove_rows with R = 2:
+ *      tree 1 with rows of W values, then tree 2 with rows of 4 D values.  No + B rows.
+ * Proof bytes.  The out-of-domain record, the FRI objects with their nonce record, the two sections:
+ *   9 + 32 (2W + D) + len_FRI(N, B, t) + 2t (9 + 8W) + 2t (9 + 32 log2 N) + 2t (9 + 32D) + 2t (9 + 32 log2 N)
+ *   (smi_air_deep_layout).  The two roots go to the caller, 64 bytes, as in the permutation variant.
+ * Host round trips of the prover: three -- root_1, root_2, and the out-of-domain values.
+ * Verifier (smi_air_verify_deep), all arithmetic in F_q, in this order, each rejection with a sentence of its own in
+ *   smi_last_error: the out-of-domain record has the exact count and canonical coordinates; the same transcript (z in F_p is
+ *   rejected); out-of-domain consistency,
+ *        sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z) = sum_j z^(j n) s_j,
+ *   with term_c(z) = (u_c - I_c(z)) / Z_c(z) (u_c without boundary points), tq_k(z) = C_k(u, v, pi(z), pi(z w))
+ *   (z - tau w^(n-1)) / (z^n - tau^n) and pi_j(z) = q_j((z / tau)^(n / P_j)), the constraints evaluated over F_q operands on
+ *   the host; Fri::verify over F_q at E = B with the proof of work; the lengths, tags and widths of both sections; every path
+ *   against its root, leaves hashed from the bytes as they stand; canonical values in the opened rows; Q(x_a) and Q(x_b)
+ *   recomputed from the opened rows against the layer-0 triple's a and b.  A proof of smi_dev_air_prove_ext_pow is rejected
+ *   here, and a proof of this variant by smi_air_verify_ext_pow.
+ * Soundness accounting and measured times: DESIGN.md section 11, "Out-of-domain sampling".
+ * Left out: folding factor 4; permutation, lookup and argument lists; column trees; smi_mgpu_* twins; zero-knowledge
+ *   randomisers; binding an AIR digest into the transcript; the segment extension fused into the leaf hash. */
+/* Host only (like smi_air_plan): the plan above -> d and D. */
+int smi_air_plan_deep(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments);
+/* Host only: the plan, and the length in bytes of the proof of that shape (num_colinearity_tests is read as well). */
+int smi_air_deep_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, size_t *proof_len);
+/* n_cols columns of n_coeffs base-field coefficients (low degree first, `stride` elements apart, any n_coeffs >= 1) at
+ * n_points = 1 or 2 points of F_q (points: four canonical coordinates each, host): out[4 (c n_points + k) + e] = coordinate
+ * e of column c at point k (host).  Both points come from one pass over the coefficients.  Two launches whatever n_cols is:
+ * workgroups reduce chunks of 1024 coefficients against a table of the points' powers (four base-field multiplies per
+ * coefficient and point), a second small launch combines the partial sums; no atomics.  16-byte loads when d_coeffs is
+ * 16-byte aligned and stride a multiple of 4, 4-byte loads otherwise.  Synchronises (the values come back to the host). */
+int smi_dev_poly_eval_ext(smi_ctx *ctx, const uint32_t *d_coeffs, uint32_t n_cols, size_t n_coeffs, size_t stride, const uint64_t *points,
+                          uint32_t n_points, uint64_t *out);
+/* The DEEP codeword of step 7 on its own.  cfg: n_cols = W, log_n, log_blowup (>= 2) and lde_offset are read.  d_lde: W
+ * extended columns `stride` apart; d_seg: 4 n_segments segment columns seg_stride apart (column 4 j + e = coordinate e of
+ * H_j); z: four canonical coordinates, not all of 1 .. 3 zero; ood: the record's 4 (2 W + D) canonical values; challenges:
+ * as many unreduced u64 (gamma, gamma', gamma''), all three on the host; d_out: four coordinate columns out_stride apart.
+ * One streaming launch, 4 (W + 4 D) + 16 bytes a point; the F_q inversions are batched eight to a lane.  16-byte accesses
+ * when the three bases are 16-byte aligned and the three strides multiples of 4, 4-byte accesses with the same values
+ * otherwise.  The table of the gammas is copied to the device from pageable memory before the launch. */
+int smi_dev_deep_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_segments, const uint32_t *d_lde, size_t stride, const uint32_t *d_seg,
+                         size_t seg_stride, const uint64_t z[4], const uint64_t *ood, const uint64_t *challenges, uint32_t *d_out, size_t out_stride);
+/* The prover above.  roots (optional): root_1 then root_2, 64 bytes; ood (optional): the record's 4 (2 W + D) values;
+ * stage_ms (optional) gets seven values {lde, commit, compose, segments, ood, fri, open} -- "ood" holds the evaluations,
+ * their round trip and the DEEP codeword. */
+int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots, uint64_t *ood,
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
+int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
+                        uint32_t grind_bits);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous
  * blocks (rank g holds [g*N/G, (g+1)*N/G)), and the build-defined trace -> proof composition of

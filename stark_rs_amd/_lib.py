@@ -263,6 +263,12 @@ def lib():
         "smi_dev_air_prove_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp,
                                           C.c_uint32, u32p]),
         "smi_air_verify_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_deep": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), u32p, u32p]),
+        "smi_air_deep_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(sz)]),
+        "smi_dev_poly_eval_ext": (i32, [vp, vp, C.c_uint32, sz, sz, u64p, C.c_uint32, u64p]),
+        "smi_dev_deep_compose": (i32, [vp, C.POINTER(StarkCfg), C.c_uint32, vp, sz, vp, sz, u64p, u64p, u64p, vp, sz]),
+        "smi_dev_air_prove_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
+        "smi_air_verify_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

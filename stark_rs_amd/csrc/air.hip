@@ -21,6 +21,7 @@
 
 #include "air_core.h"
 #include "args_core.h"
+#include "deep_core.h"
 #include "hash_core.h"
 #include "internal.h"
 #include "mgpu_core.h"
@@ -289,6 +290,18 @@ int smi_air_plan_args(uint64_t p, const smi_stark_cfg *cfg, const void *air, con
 int smi_air_plan_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint64_t *fri_expansion) {
     g_air_err.clear();
     return xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, degree, fri_expansion, &g_air_err);
+}
+// out-of-domain sampling (deep_core.h): the plan, and the proof length of a planned shape
+int smi_air_plan_deep(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments) {
+    g_air_err.clear();
+    return deep_plan(p, cfg, (const smi_air *)air, degree, segments, &g_air_err);
+}
+int smi_air_deep_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t D = 0;
+    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err);
+    if (rc == SMI_OK && proof_len) *proof_len = deep_proof_len(cfg, D);
+    return rc;
 }
 // what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }

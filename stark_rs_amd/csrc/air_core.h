@@ -278,8 +278,9 @@ inline uint32_t air_to_m(uint32_t a, uint32_t p) { return (uint32_t)(((uint64_t)
 
 // Everything smi_air_plan promises.  *why names the limit that was broken.
 // tables_only: the AIR's own tables against n_cols and log_n (smi_dev_air_check: no extension, no offsets).
+// any_expansion: E < 4 is not refused (out-of-domain sampling runs FRI at the blowup: deep_core.h deep_plan has its own bounds).
 inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *air, uint32_t *degree, uint64_t *fri_expansion,
-                        std::string *why, bool tables_only = false) {
+                        std::string *why, bool tables_only = false, bool any_expansion = false) {
     auto fail = [&](int code, const std::string &s) {
         if (why) *why = s;
         return code;
@@ -349,7 +350,7 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
     uint64_t D = 1;
     while (D < d - 1) D <<= 1;   // d >= 1; the smallest power of two >= max(1, d - 1)
     const uint64_t E = D > B ? 0 : B / D;
-    if (E < 4) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "air: 2^log_blowup / D < 4: the quotients of a degree-" + std::to_string(d) + " constraint do not fit under the FRI degree bound");
+    if (E < 4 && !any_expansion) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "air: 2^log_blowup / D < 4: the quotients of a degree-" + std::to_string(d) + " constraint do not fit under the FRI degree bound");
     const uint64_t tau = cfg->trace_offset, h = cfg->lde_offset;
     if (!tau || tau >= p || !h || h >= p) return fail(SMI_ERR_BAD_ARG, "air: offsets must be in 1 .. p-1");
     const uint64_t N = n * B;

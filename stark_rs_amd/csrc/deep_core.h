@@ -1,0 +1,417 @@
+// deep_core.h -- out-of-domain sampling (include/stark_mi.h, "Out-of-domain sampling"): the plan and the proof length, the
+// lane bodies of the two kernels of deep.hip -- coefficient columns evaluated at points of F_q (deep_eval_kernel,
+// deep_eval_combine_kernel) and the DEEP codeword (deep_compose_kernel) -- with the host tables they read, and the
+// verifier's side in plain host arithmetic: the transcript, the out-of-domain consistency check with the constraint
+// evaluator over F_q operands, and Q at one point from two opened rows.  Shared by the HIP kernels (deep.hip), the verifier
+// (verify.hip, host) and the CPU emulator (emu_deep.cpp), which runs the same lane bodies and block split.
+//
+// Number forms.  Coefficients and extended cells are plain residues.  The powers of a point come from the host in
+// Montgomery form coordinate by coordinate, so mont_mul(plain coefficient, .) is a plain coordinate of the product: a
+// coefficient times a power is four base-field multiplies.  In the compose lane x, z, z w and the inverted denominators are
+// Montgomery, the gammas Montgomery (the segment ones prepared, fri_core.h ExtMul), the accumulated numerators plain.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/stark_mi.h"
+#include "air_core.h"
+#include "fri_core.h"
+#include "fri_plan.h"
+#include "perm_core.h"
+#include "transcript_core.h"
+
+#define DEEP_ROWS 4                               // consecutive coefficients / points per lane: one 16-byte access per column
+#define DEEP_BLOCK 256                            // lanes per workgroup
+#define DEEP_TILE (DEEP_ROWS * DEEP_BLOCK)        // coefficients of one column a workgroup reduces
+#define DEEP_MAX_SEGMENTS 16                      // 4 D <= 64: the widest row the leaf hash takes
+#define DEEP_MAX_POINTS 2
+
+// the sentences of the prover's refusal and of the verifier's own rejections (verify.hip; tests match on them)
+#define DEEP_Z_IN_BASE_FIELD "deep: the out-of-domain point z lies in the base field"
+#define DEEP_BAD_RECORD "deep: the out-of-domain record is missing or has the wrong count"
+#define DEEP_RECORD_CANONICAL "deep: an out-of-domain coordinate is not canonical"
+#define DEEP_INCONSISTENT "deep: out-of-domain consistency check fails: the constraints at z do not give the segments' value"
+#define DEEP_NO_LAYER "deep: FRI has no fold at this shape, so there is no layer-0 triple to compare the DEEP quotient with"
+static const char *const DEEP_SENTENCES[6] = {"deep openings: wrong length",
+                                              "deep openings: malformed row",
+                                              "deep openings: malformed path",
+                                              "deep openings: authentication path does not verify",
+                                              "deep openings: an opened value is not canonical",
+                                              "deep openings: the DEEP quotient of the opened rows is not the codeword value"};
+
+// ------------------------------------------------------------------------------------------------ evaluation
+// Table of one launch, u32 words, P = n_points:
+//   pw[k][e][j], j < DEEP_TILE  : coordinate e of z_k^j                      at (k * 4 + e) * DEEP_TILE + j
+//   tp[k][j][e], j < DEEP_BLOCK : coordinate e of (z_k^DEEP_TILE)^j          at 4 P DEEP_TILE + (k * DEEP_BLOCK + j) * 4 + e
+//   st[k][e]                    : coordinate e of (z_k^DEEP_TILE)^DEEP_BLOCK at 4 P (DEEP_TILE + DEEP_BLOCK) + 4 k + e
+// all Montgomery.
+inline size_t deep_eval_tab_words(uint32_t P) { return (size_t)P * (4 * DEEP_TILE + 4 * DEEP_BLOCK + 4); }
+SMI_HD size_t deep_eval_tp_at(uint32_t P) { return (size_t)4 * P * DEEP_TILE; }
+SMI_HD size_t deep_eval_st_at(uint32_t P) { return (size_t)4 * P * (DEEP_TILE + DEEP_BLOCK); }
+inline uint64_t deep_eval_blocks(uint64_t n_coeffs) { return (n_coeffs + DEEP_TILE - 1) / DEEP_TILE; }
+
+// one lane of deep_eval_kernel: its DEEP_ROWS coefficients a[q] against coordinate e of the powers, tw[e][q] -> the lane's
+// share of the workgroup's partial sum, plain
+SMI_HD void deep_eval_lane(const uint32_t a[DEEP_ROWS], const uint32_t tw[4][DEEP_ROWS], const Fp &F, uint32_t acc[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) s = fp_add(s, mont_mul(a[q], tw[e][q], F), F.p);
+        acc[e] = s;
+    }
+}
+// one lane of deep_eval_combine_kernel: the partial sums tid, tid + DEEP_BLOCK, .. of one column and point (element b at
+// part[b * pitch .. + 3], plain) by Horner in (z^DEEP_TILE)^DEEP_BLOCK from the top, then times (z^DEEP_TILE)^tid
+SMI_HD void deep_eval_combine_lane(const uint32_t *part, uint32_t pitch, uint32_t nb, uint32_t tid, const uint32_t tp_m[4], const uint32_t st_m[4],
+                                   uint32_t g_m, const Fp &F, uint32_t acc[4]) {
+    acc[0] = acc[1] = acc[2] = acc[3] = 0;
+    if (tid >= nb) return;
+    const ExtMul S = ext_mul_prepare(st_m, g_m, F);
+    uint32_t t[4];
+    for (uint32_t m = (nb - 1 - tid) / DEEP_BLOCK;; m--) {
+        const uint32_t *v = part + (size_t)(tid + m * DEEP_BLOCK) * pitch;
+        ext_mul_prepared(acc, S, F, t);
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[e] = fp_add(t[e], v[e], F.p);
+        if (!m) break;
+    }
+    const ExtMul T = ext_mul_prepare(tp_m, g_m, F);
+    ext_mul_prepared(acc, T, F, t);
+#pragma unroll
+    for (int e = 0; e < 4; e++) acc[e] = t[e];
+}
+
+// ------------------------------------------------------------------------------------------------ the DEEP codeword
+// Table of one launch, u32 words:
+//   gamma_c    (Montgomery)            at 4 c + e
+//   gamma'_c   (Montgomery)            at 4 W + 4 c + e
+//   gamma''_j  (prepared: b_m | gb_m)  at 8 W + 8 j + e, 8 W + 8 j + 4 + e
+//   -C1 = -(sum_c gamma_c u_c + sum_j gamma''_j s_j), -C2 = -sum_c gamma'_c v_c (plain), z, z w (Montgomery): the last 16
+inline size_t deep_tab_words(uint32_t W, uint32_t D) { return (size_t)8 * W + 8 * D + 16; }
+
+// One lane: the DEEP_ROWS consecutive points x0, x0 omega, ..  load_t(c, v): extended trace column c at the four points;
+// load_s(col, v): segment column col (4 j + e: coordinate e of H_j); out[e][q]: coordinate e of Q at point q, plain.
+// The 2 DEEP_ROWS denominators x - z and x - z w share one F_q inversion; none is zero, since z and z w lie outside F_p.
+template <class LoadT, class LoadS>
+SMI_HD void deep_compose_points(const uint32_t *tab, uint32_t W, uint32_t D, uint32_t g_m, const Fp &F, uint32_t x0_m, uint32_t omega_m, LoadT load_t,
+                                LoadS load_s, uint32_t out[4][DEEP_ROWS]) {
+    const uint32_t p = F.p;
+    const uint32_t *cst = tab + 8 * (size_t)W + 8 * (size_t)D;
+    Fq dinv[2 * DEEP_ROWS];
+    {
+        Fq den[2 * DEEP_ROWS], pre[2 * DEEP_ROWS];
+        uint32_t x = x0_m;
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) {
+            den[q] = Fq{{fp_sub(x, cst[8], p), fp_neg(cst[9], p), fp_neg(cst[10], p), fp_neg(cst[11], p)}};
+            den[DEEP_ROWS + q] = Fq{{fp_sub(x, cst[12], p), fp_neg(cst[13], p), fp_neg(cst[14], p), fp_neg(cst[15], p)}};
+            x = mont_mul(x, omega_m, F);
+        }
+        pre[0] = den[0];
+#pragma unroll
+        for (int i = 1; i < 2 * DEEP_ROWS; i++) pre[i] = fq_mul(pre[i - 1], den[i], g_m, F);
+        Fq inv = fq_inv(pre[2 * DEEP_ROWS - 1], g_m, F);
+#pragma unroll
+        for (int i = 2 * DEEP_ROWS - 1; i >= 0; i--) {
+            dinv[i] = i ? fq_mul(inv, pre[i - 1], g_m, F) : inv;
+            if (i) inv = fq_mul(inv, den[i], g_m, F);
+        }
+    }
+    uint32_t a1[DEEP_ROWS][4], a2[DEEP_ROWS][4];
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) a1[q][e] = cst[e], a2[q][e] = cst[4 + e];
+    for (uint32_t c = 0; c < W; c++) {
+        uint32_t v[DEEP_ROWS];
+        load_t(c, v);
+        const uint32_t *g1 = tab + 4 * (size_t)c, *g2 = tab + 4 * (size_t)(W + c);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t b1 = g1[e], b2 = g2[e];
+#pragma unroll
+            for (int q = 0; q < DEEP_ROWS; q++) {
+                a1[q][e] = fp_add(a1[q][e], mont_mul(v[q], b1, F), p);
+                a2[q][e] = fp_add(a2[q][e], mont_mul(v[q], b2, F), p);
+            }
+        }
+    }
+    for (uint32_t j = 0; j < D; j++) {
+        uint32_t h[4][DEEP_ROWS];
+#pragma unroll
+        for (int e = 0; e < 4; e++) load_s(4 * j + e, h[e]);
+        ExtMul M;
+#pragma unroll
+        for (int e = 0; e < 4; e++) M.b_m[e] = tab[8 * (size_t)W + 8 * j + e], M.gb_m[e] = tab[8 * (size_t)W + 8 * j + 4 + e];
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) {
+            const uint32_t hv[4] = {h[0][q], h[1][q], h[2][q], h[3][q]};
+            uint32_t o[4];
+            ext_mul_prepared(hv, M, F, o);
+#pragma unroll
+            for (int e = 0; e < 4; e++) a1[q][e] = fp_add(a1[q][e], o[e], p);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++) {
+        const Fq n1{{a1[q][0], a1[q][1], a1[q][2], a1[q][3]}}, n2{{a2[q][0], a2[q][1], a2[q][2], a2[q][3]}};
+        const Fq r1 = fq_mul(n1, dinv[q], g_m, F), r2 = fq_mul(n2, dinv[DEEP_ROWS + q], g_m, F);
+#pragma unroll
+        for (int e = 0; e < 4; e++) out[e][q] = fp_add(r1.c[e], r2.c[e], p);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side: F_q, plain
+struct FqH {
+    uint32_t c[4];
+};
+inline FqH fqh(uint32_t v) { return FqH{{v, 0, 0, 0}}; }
+inline FqH fqh_of(const uint64_t *v, uint32_t p) { return FqH{{(uint32_t)(v[0] % p), (uint32_t)(v[1] % p), (uint32_t)(v[2] % p), (uint32_t)(v[3] % p)}}; }
+inline FqH fqh_add(const FqH &a, const FqH &b, uint32_t p) { return FqH{{fp_add(a.c[0], b.c[0], p), fp_add(a.c[1], b.c[1], p), fp_add(a.c[2], b.c[2], p), fp_add(a.c[3], b.c[3], p)}}; }
+inline FqH fqh_sub(const FqH &a, const FqH &b, uint32_t p) { return FqH{{fp_sub(a.c[0], b.c[0], p), fp_sub(a.c[1], b.c[1], p), fp_sub(a.c[2], b.c[2], p), fp_sub(a.c[3], b.c[3], p)}}; }
+inline FqH fqh_mul(const FqH &a, const FqH &b, uint32_t p, uint32_t g) {
+    FqH o;
+    ext_mul_host(p, g, a.c, b.c, o.c);
+    return o;
+}
+inline FqH fqh_scale(const FqH &a, uint32_t k, uint32_t p) { return FqH{{host_mulmod(a.c[0], k, p), host_mulmod(a.c[1], k, p), host_mulmod(a.c[2], k, p), host_mulmod(a.c[3], k, p)}}; }
+inline FqH fqh_inv(const FqH &a, uint32_t p, uint32_t g) {   // a != 0
+    FqH o{{0, 0, 0, 0}};
+    (void)ext_inv_host(p, g, a.c, o.c);
+    return o;
+}
+inline FqH fqh_pow(FqH b, uint64_t e, uint32_t p, uint32_t g) {
+    FqH r = fqh(1 % p);
+    while (e) {
+        if (e & 1) r = fqh_mul(r, b, p, g);
+        b = fqh_mul(b, b, p, g);
+        e >>= 1;
+    }
+    return r;
+}
+inline bool fqh_eq(const FqH &a, const FqH &b) { return a.c[0] == b.c[0] && a.c[1] == b.c[1] && a.c[2] == b.c[2] && a.c[3] == b.c[3]; }
+inline bool fqh_in_base(const FqH &a) { return !(a.c[1] | a.c[2] | a.c[3]); }
+
+// the table of deep_eval_kernel / deep_eval_combine_kernel for the P points z[k] (plain coordinates)
+inline void deep_eval_build(const Fp &F, uint32_t g, uint32_t P, const FqH *z, std::vector<uint32_t> *tab) {
+    const uint32_t p = F.p;
+    tab->assign(deep_eval_tab_words(P), 0);
+    uint32_t *t = tab->data();
+    for (uint32_t k = 0; k < P; k++) {
+        FqH pw = fqh(1 % p);
+        for (uint32_t j = 0; j < DEEP_TILE; j++) {
+            for (int e = 0; e < 4; e++) t[(size_t)(k * 4 + e) * DEEP_TILE + j] = air_to_m(pw.c[e], p);
+            pw = fqh_mul(pw, z[k], p, g);
+        }
+        const FqH zt = pw;   // z^DEEP_TILE
+        pw = fqh(1 % p);
+        for (uint32_t j = 0; j < DEEP_BLOCK; j++) {
+            for (int e = 0; e < 4; e++) t[deep_eval_tp_at(P) + (size_t)(k * DEEP_BLOCK + j) * 4 + e] = air_to_m(pw.c[e], p);
+            pw = fqh_mul(pw, zt, p, g);
+        }
+        for (int e = 0; e < 4; e++) t[deep_eval_st_at(P) + 4 * k + e] = air_to_m(pw.c[e], p);
+    }
+}
+
+// the table of deep_compose_kernel.  ood: the record's 4 (2 W + D) canonical values (u, v, s); ch: as many unreduced
+// challenges (gamma, gamma', gamma''); w_n = omega_n
+inline void deep_compose_build(const Fp &F, uint32_t g, uint32_t W, uint32_t D, uint32_t w_n, const FqH &z, const uint64_t *ood, const uint64_t *ch,
+                               std::vector<uint32_t> *tab) {
+    const uint32_t p = F.p;
+    tab->assign(deep_tab_words(W, D), 0);
+    uint32_t *t = tab->data();
+    FqH c1 = fqh(0), c2 = fqh(0);
+    for (uint32_t c = 0; c < W; c++) {
+        const FqH g1 = fqh_of(ch + 4 * (size_t)c, p), g2 = fqh_of(ch + 4 * (size_t)(W + c), p);
+        for (int e = 0; e < 4; e++) t[4 * c + e] = air_to_m(g1.c[e], p), t[4 * (W + c) + e] = air_to_m(g2.c[e], p);
+        c1 = fqh_add(c1, fqh_mul(g1, fqh_of(ood + 4 * (size_t)c, p), p, g), p);
+        c2 = fqh_add(c2, fqh_mul(g2, fqh_of(ood + 4 * (size_t)(W + c), p), p, g), p);
+    }
+    for (uint32_t j = 0; j < D; j++) {
+        const FqH g3 = fqh_of(ch + 4 * (size_t)(2 * W + j), p);
+        for (int e = 0; e < 4; e++) {
+            t[8 * W + 8 * j + e] = air_to_m(g3.c[e], p);
+            t[8 * W + 8 * j + 4 + e] = air_to_m(host_mulmod(g3.c[e], g, p), p);
+        }
+        c1 = fqh_add(c1, fqh_mul(g3, fqh_of(ood + 4 * (size_t)(2 * W + j), p), p, g), p);
+    }
+    uint32_t *cst = t + 8 * (size_t)W + 8 * (size_t)D;
+    const FqH zw = fqh_scale(z, w_n, p);
+    for (int e = 0; e < 4; e++) {
+        cst[e] = fp_neg(c1.c[e], p);
+        cst[4 + e] = fp_neg(c2.c[e], p);
+        cst[8 + e] = air_to_m(z.c[e], p);
+        cst[12 + e] = air_to_m(zw.c[e], p);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ plan, layout, transcript
+// smi_air_plan_deep: smi_air_plan's checks without its bound on E, then D <= B, B >= 4, 4 D <= 64
+inline int deep_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, uint32_t *degree, uint32_t *segments, std::string *why) {
+    auto fail = [&](int code, const std::string &s) {
+        if (why) *why = s;
+        return code;
+    };
+    uint32_t d = 0;
+    const int rc = air_validate(p, cfg, air, &d, nullptr, why, false, true);
+    if (rc != SMI_OK) return rc;
+    if ((p & 3) != 1) return fail(SMI_ERR_BAD_ARG, "deep: p = 3 (mod 4): the quartic extension does not exist");
+    const uint64_t B = 1ull << cfg->log_blowup;
+    uint64_t D = 1;
+    while (D < (uint64_t)d - 1 && D < (1ull << 32)) D <<= 1;
+    if (D > B)
+        return fail(SMI_ERR_BAD_ARG, "deep: D > 2^log_blowup: the composition of a degree-" + std::to_string(d) + " constraint has degree >= N and does not fit the evaluation domain");
+    if (B < 4) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "deep: 2^log_blowup < 4 (Fri::new's assert on the expansion factor)");
+    if (4 * D > 64) return fail(SMI_ERR_BAD_ARG, "deep: 4 D > 64: a row of the segment tree is wider than the leaf hash takes");
+    if (degree) *degree = d;
+    if (segments) *segments = (uint32_t)D;
+    return SMI_OK;
+}
+inline smi_fri_cfg deep_fri_cfg(const smi_stark_cfg *cfg, uint64_t omega_N) {
+    smi_fri_cfg fc;
+    fc.omega = omega_N;
+    fc.offset = cfg->lde_offset;
+    fc.domain_length = 1ull << (cfg->log_n + cfg->log_blowup);
+    fc.expansion_factor = 1ull << cfg->log_blowup;
+    fc.num_colinearity_tests = cfg->num_colinearity_tests;
+    return fc;
+}
+// 9 + 32 (2W + D) + len_FRI(N, B, t) + the two opening sections of two rows per test
+inline size_t deep_proof_len(const smi_stark_cfg *cfg, uint32_t D) {
+    const uint64_t W = cfg->n_cols, t = cfg->num_colinearity_tests, log_N = cfg->log_n + cfg->log_blowup;
+    const smi_fri_cfg fc = deep_fri_cfg(cfg, 1);
+    return (size_t)(9 + 32 * (2 * W + D) + fri_layout_ext(fc, true).proof_len + 2 * t * (9 + 8 * W) + 2 * t * (9 + 32 * log_N) + 2 * t * (9 + 32ull * D) +
+                    2 * t * (9 + 32 * log_N));
+}
+
+// The transcript in its three steps (prover and verifier): root_1 and the weights; root_2 and z; the record and the gammas.
+inline void deep_transcript_weights(Transcript &T, const uint8_t root1[32], uint32_t W, uint32_t K, std::vector<uint64_t> *weights) {
+    transcript_ext(T, root1, W, K, weights);
+}
+inline void deep_transcript_z(Transcript &T, const uint8_t root2[32], uint32_t W, uint32_t K, uint64_t z[4]) {
+    std::vector<uint64_t> ch;
+    transcript_indexed(T, root2, 4 * ((uint64_t)W + K), 4, &ch);
+    for (int e = 0; e < 4; e++) z[e] = ch[e];
+}
+inline void deep_transcript_gammas(Transcript &T, const uint64_t *ood, uint32_t W, uint32_t K, uint32_t D, std::vector<uint64_t> *gammas) {
+    const uint64_t cnt = 4 * (2 * (uint64_t)W + D);
+    for (uint64_t i = 0; i < cnt; i++) T.absorb_index(ood[i]);   // the payload: every value as 8 little-endian bytes
+    for (uint64_t m = 0; m < cnt; m++) {
+        T.absorb_index(4 * ((uint64_t)W + K) + 4 + m);
+        gammas->push_back(T.challenge());
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the verifier's side
+// C_k over F_q operands in smi_air's numbering: X[v], v < 2 W + 2 Q
+inline FqH deep_constraint(const smi_air *air, uint32_t k, const FqH *X, uint32_t p, uint32_t g) {
+    FqH ck = fqh(0);
+    for (uint32_t t = air->constraint_first_term[k]; t < air->constraint_first_term[k + 1]; t++) {
+        FqH m = fqh((uint32_t)(air->term_coeff[t] % p));
+        for (uint32_t f = air->term_first_factor[t]; f < air->term_first_factor[t + 1]; f++)
+            m = fqh_mul(m, fqh_pow(X[air->factor_var[f]], air->factor_exp[f], p, g), p, g);
+        ck = fqh_add(ck, m, p);
+    }
+    return ck;
+}
+// pi_j(x) = q_j(y), y = (x / tau)^(n / P_j), by the barycentric form over the P_j-th roots of unity:
+// q(y) = (y^P - 1) / P * sum_r v_r w_P^r / (y - w_P^r); for x outside F_p no y is such a root (an n-th root of unity of
+// F_q lies in F_p).  One F_q inversion per column and point (Montgomery's trick over the P denominators).
+inline FqH deep_periodic_at(const smi_air *air, uint32_t j, const uint64_t *vals, uint32_t log_n, uint32_t tau, uint32_t w_n, const FqH &x, uint32_t p,
+                            uint32_t g) {
+    const uint32_t l = air->periodic_log_period[j];
+    const uint64_t P = 1ull << l, n = 1ull << log_n;
+    const FqH y = fqh_pow(fqh_scale(x, host_powmod(tau, p - 2, p), p), n / P, p, g);
+    const uint32_t wP = host_powmod(w_n, n / P, p);
+    std::vector<FqH> den(P), pre(P);
+    uint32_t wr = 1 % p;
+    for (uint64_t r = 0; r < P; r++) {
+        den[r] = fqh_sub(y, fqh(wr), p);
+        pre[r] = r ? fqh_mul(pre[r - 1], den[r], p, g) : den[r];
+        wr = host_mulmod(wr, wP, p);
+    }
+    FqH inv = fqh_inv(pre[P - 1], p, g), acc = fqh(0);
+    const uint32_t wP_inv = host_powmod(wP, p - 2, p);
+    wr = host_powmod(wP, P - 1, p);
+    for (uint64_t r = P; r-- > 0;) {
+        const FqH di = r ? fqh_mul(inv, pre[r - 1], p, g) : inv;
+        if (r) inv = fqh_mul(inv, den[r], p, g);
+        acc = fqh_add(acc, fqh_scale(di, host_mulmod((uint32_t)(vals[r] % p), wr, p), p), p);
+        wr = host_mulmod(wr, wP_inv, p);
+    }
+    const FqH zp = fqh_sub(fqh_pow(y, P, p, g), fqh(1 % p), p);
+    return fqh_scale(fqh_mul(acc, zp, p, g), host_powmod((uint32_t)(P % p), p - 2, p), p);
+}
+// Both sides of the out-of-domain consistency check for a z outside F_p:
+//   lhs = sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z) from u = f(z), v = f(z w);   rhs = sum_j z^(j n) s_j.
+// weights: the 4 (W + K) unreduced challenges; ood: the record's 4 (2 W + D) canonical values; w_n = omega_n.
+inline void deep_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, const smi_air *air, uint32_t D, uint32_t w_n, const uint64_t *weights, const FqH &z,
+                           const uint64_t *ood, FqH *lhs, FqH *rhs) {
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, Q = air->n_periodic, tau = (uint32_t)cfg->trace_offset;
+    const uint64_t n = 1ull << cfg->log_n;
+    FqH acc = fqh(0);
+    for (uint32_t c = 0; c < W; c++) {
+        FqH term = fqh_of(ood + 4 * (size_t)c, p);
+        std::vector<uint32_t> r, val;
+        for (uint32_t b = 0; b < air->n_boundary; b++)
+            if (air->boundary_col[b] == c) {
+                r.push_back(host_mulmod(tau, host_powmod(w_n, air->boundary_row[b], p), p));
+                val.push_back((uint32_t)(air->boundary_value[b] % p));
+            }
+        if (!r.empty()) {   // I_c(z) in Lagrange form, Z_c(z) = prod (z - r_j)
+            FqH ix = fqh(0), zc = fqh(1 % p);
+            for (size_t j = 0; j < r.size(); j++) {
+                FqH num = fqh(1 % p);
+                uint32_t den = 1 % p;
+                for (size_t i = 0; i < r.size(); i++) {
+                    if (i == j) continue;
+                    num = fqh_mul(num, fqh_sub(z, fqh(r[i]), p), p, g);
+                    den = host_mulmod(den, fp_sub(r[j], r[i], p), p);
+                }
+                ix = fqh_add(ix, fqh_scale(num, host_mulmod(val[j], host_powmod(den, p - 2, p), p), p), p);
+                zc = fqh_mul(zc, fqh_sub(z, fqh(r[j]), p), p, g);
+            }
+            term = fqh_mul(fqh_sub(term, ix, p), fqh_inv(zc, p, g), p, g);
+        }
+        acc = fqh_add(acc, fqh_mul(fqh_of(weights + 4 * (size_t)c, p), term, p, g), p);
+    }
+    if (K) {
+        std::vector<FqH> X(2 * (size_t)W + 2 * (size_t)Q);
+        for (uint32_t c = 0; c < W; c++) X[c] = fqh_of(ood + 4 * (size_t)c, p), X[W + c] = fqh_of(ood + 4 * (size_t)(W + c), p);
+        const FqH zw = fqh_scale(z, w_n, p);
+        for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++) {
+            X[2 * W + j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, z, p, g);
+            X[2 * W + Q + j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, zw, p, g);
+        }
+        const uint32_t last = host_mulmod(tau, host_powmod(w_n, n - 1, p), p);
+        const FqH zt = fqh_mul(fqh_sub(z, fqh(last), p), fqh_inv(fqh_sub(fqh_pow(z, n, p, g), fqh(host_powmod(tau, n, p)), p), p, g), p, g);
+        for (uint32_t k = 0; k < K; k++)
+            acc = fqh_add(acc, fqh_mul(fqh_of(weights + 4 * (size_t)(W + k), p), fqh_mul(deep_constraint(air, k, X.data(), p, g), zt, p, g), p, g), p);
+    }
+    *lhs = acc;
+    const FqH zn = fqh_pow(z, n, p, g);
+    FqH r = fqh(0), pw = fqh(1 % p);
+    for (uint32_t j = 0; j < D; j++) {
+        r = fqh_add(r, fqh_mul(pw, fqh_of(ood + 4 * (size_t)(2 * W + j), p), p, g), p);
+        pw = fqh_mul(pw, zn, p, g);
+    }
+    *rhs = r;
+}
+// Q(x) from the opened rows at x: trow = the W trace values, srow = the 4 D segment values (canonical)
+inline FqH deep_q_at(uint32_t p, uint32_t g, uint32_t W, uint32_t D, uint32_t w_n, uint32_t x, const FqH &z, const uint64_t *ood, const uint64_t *gammas,
+                     const uint64_t *trow, const uint64_t *srow) {
+    FqH n1 = fqh(0), n2 = fqh(0);
+    for (uint32_t c = 0; c < W; c++) {
+        const FqH f = fqh((uint32_t)trow[c]);
+        n1 = fqh_add(n1, fqh_mul(fqh_of(gammas + 4 * (size_t)c, p), fqh_sub(f, fqh_of(ood + 4 * (size_t)c, p), p), p, g), p);
+        n2 = fqh_add(n2, fqh_mul(fqh_of(gammas + 4 * (size_t)(W + c), p), fqh_sub(f, fqh_of(ood + 4 * (size_t)(W + c), p), p), p, g), p);
+    }
+    for (uint32_t j = 0; j < D; j++)
+        n1 = fqh_add(n1, fqh_mul(fqh_of(gammas + 4 * (size_t)(2 * W + j), p), fqh_sub(fqh_of(srow + 4 * (size_t)j, p), fqh_of(ood + 4 * (size_t)(2 * W + j), p), p), p, g), p);
+    const FqH d1 = fqh_sub(fqh(x), z, p), d2 = fqh_sub(fqh(x), fqh_scale(z, w_n, p), p);
+    return fqh_add(fqh_mul(n1, fqh_inv(d1, p, g), p, g), fqh_mul(n2, fqh_inv(d2, p, g), p, g), p);
+}

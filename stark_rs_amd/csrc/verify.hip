@@ -31,6 +31,7 @@
 
 #include "air_core.h"
 #include "args_core.h"
+#include "deep_core.h"
 #include "xargs_core.h"
 #include "fri_core.h"
 #include "hash_core.h"
@@ -1227,4 +1228,80 @@ int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air
     SMI_TRY(ext_field_check(ctx));
     return settle(air_verify_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept,
                                   AirVariant{true, true, (int)grind_bits, nullptr, nullptr, nullptr, (const smi_air_xargs *)xargs}));
+}
+
+// Verifier of smi_dev_air_prove_deep (include/stark_mi.h, "Out-of-domain sampling").  In this order: the out-of-domain
+// record (count, canonical coordinates); the transcript -- root_1 and the weights, root_2 and z, the record and the gammas;
+// the consistency of the record with the constraints at z (deep_core.h deep_ood_sides, host F_q arithmetic); Fri::verify
+// over F_q at E = B with the proof of work; the two opening sections with air_verify_impl's parsing and authentication
+// (parse_section, auth_section), two rows per test and no next row; the canonical check; Q recomputed at x_a and x_b from
+// the opened rows (deep_q_at) against the layer-0 triple.
+const OpeningWords DEEP_WORDS = {DEEP_SENTENCES[0], DEEP_SENTENCES[1], DEEP_SENTENCES[2], DEEP_SENTENCES[3], DEEP_SENTENCES[4], DEEP_SENTENCES[5]};   // deep_core.h
+static int air_verify_deep_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
+                                int *accept, uint32_t grind) {
+    std::string why;
+    uint32_t D = 0;
+    const int vrc = deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    const size_t n_ood = 4 * (2 * (size_t)W + D);
+    size_t end = 0;
+    std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count(fc) + 1, &end);
+    if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, DEEP_BAD_RECORD);
+    std::vector<uint64_t> ood(n_ood);
+    for (size_t i = 0; i < n_ood; i++)
+        if ((ood[i] = get_u64(objs[0].p + 8 * i)) >= p) return reject(ctx, accept, DEEP_RECORD_CANONICAL);
+    Transcript tr;
+    std::vector<uint64_t> weights, gammas;
+    uint64_t zr[4];
+    deep_transcript_weights(tr, roots, W, K, &weights);
+    deep_transcript_z(tr, roots + 32, W, K, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return reject(ctx, accept, DEEP_Z_IN_BASE_FIELD);
+    deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
+    FqH lhs, rhs;
+    deep_ood_sides(p, g, cfg, air, D, w_n, weights.data(), z, ood.data(), &lhs, &rhs);
+    if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_INCONSISTENT);
+    objs.erase(objs.begin());
+    std::vector<uint64_t> top, ab;
+    size_t used = 0;
+    SMI_TRY(fri_verify_ext_objs(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &ab, &used, (int)grind));
+    *accept = 0;
+    if (ab.size() != 8 * t) return reject(ctx, accept, DEEP_NO_LAYER);
+    const OpeningWords &say = DEEP_WORDS;
+    const size_t R = 2, m = R * t, prec = 9 + 32 * (size_t)logN;
+    const uint32_t widths[2] = {W, 4 * D};
+    const size_t sec_len[2] = {m * (9 + 8 * (size_t)widths[0]) + m * prec, m * (9 + 8 * (size_t)widths[1]) + m * prec};
+    if (proof_len - end != sec_len[0] + sec_len[1]) return reject(ctx, accept, say.length);
+    const uint8_t *sec[2] = {proof + end, proof + end + sec_len[0]};
+    const std::vector<uint64_t> pos = opened_positions(top, N, 0, R);
+    std::vector<uint64_t> rows[2];
+    for (size_t v = 0; v < 2; v++) SMI_TRY(parse_section(ctx, accept, say, sec[v], m, widths[v], logN, ROWS_THEN_PATHS, &rows[v]));
+    for (size_t v = 0; v < 2; v++) SMI_TRY(auth_section(ctx, accept, say, sec[v], m, widths[v], logN, pos, roots + 32 * v));
+    for (size_t v = 0; v < 2; v++)
+        for (uint64_t x : rows[v])
+            if (x >= p) return reject(ctx, accept, say.canonical);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < 2; k++) {
+            const uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[R * s + k], p), p);
+            const FqH q = deep_q_at(p, g, W, D, w_n, x, z, ood.data(), gammas.data(), &rows[0][(R * s + k) * W], &rows[1][(R * s + k) * 4 * D]);
+            for (uint32_t e = 0; e < 4; e++)
+                if (q.c[e] != ab[(2 * s + k) * 4 + e]) return reject(ctx, accept, say.composition);
+        }
+    *accept = 1;
+    return SMI_OK;
+}
+int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
+                        uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept, grind_bits));
 }

@@ -700,6 +700,70 @@ class Engine:
             return True, None, None, ""
         return False, con.value, row.value, self.L.smi_last_error(self.h).decode()
 
+    # ---- out-of-domain sampling (include/stark_mi.h, "Out-of-domain sampling")
+    def _check_deep(self, a, row_leaves, ext, folding, fill_multiplicities):
+        if any(f(a) is not None for f in (self._xargs, self._args, self._lookup, self._perm)) or fill_multiplicities:
+            raise ValueError("deep=True takes a plain AIR: no permutation, lookup or argument list")
+        if folding != 2:
+            raise ValueError("deep=True folds by 2 only (folding=4 is not supported)")
+        if not (row_leaves and ext):
+            raise ValueError("deep=True runs over the row-committed extension proof: pass row_leaves=True, ext=True")
+
+    def air_plan_deep(self, air, n_cols, log_n, log_blowup, trace_offset=1, lde_offset=None, num_colinearity_tests=None):
+        """smi_air_plan_deep -> (degree d, segments D); with num_colinearity_tests also the proof length of
+        smi_air_deep_layout: (d, D, bytes).  Host only; raises with the limit that was broken."""
+        a = self._air(air)
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests or 0, trace_offset, lde_offset, True)
+        return air_plan_deep(self.p, a, cfg, num_colinearity_tests is not None)
+
+    def dev_poly_eval_ext(self, d_coeffs, n_cols, n_coeffs, points, stride=None):
+        """smi_dev_poly_eval_ext: n_cols device columns of n_coeffs base-field coefficients, stride (default n_coeffs) apart,
+        at one or two points of F_q (four canonical coordinates each) -> [[[c0..c3] per point] per column]"""
+        pts = [int(v) for pt in points for v in pt]
+        if len(pts) not in (4, 8):
+            raise ValueError("dev_poly_eval_ext: one or two points of four coordinates")
+        P = len(pts) // 4
+        arr = (C.c_uint64 * len(pts))(*pts)
+        out = (C.c_uint64 * (4 * n_cols * P))()
+        self._ck(self.L.smi_dev_poly_eval_ext(self.h, vp(d_coeffs), n_cols, n_coeffs, n_coeffs if stride is None else stride, arr, P, out))
+        return [[[int(out[4 * (c * P + k) + e]) for e in range(4)] for k in range(P)] for c in range(n_cols)]
+
+    def dev_deep_compose(self, d_lde, d_seg, n_cols, n_segments, log_n, log_blowup, z, ood, challenges, d_out, stride=None, seg_stride=None,
+                         out_stride=None, lde_offset=None):
+        """smi_dev_deep_compose: the DEEP codeword of n_cols extended columns and 4 n_segments segment columns under z (four
+        canonical coordinates), the record's 4 (2 W + D) values and as many unreduced challenges, into four coordinate columns"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, 1, lde_offset, True)
+        N, cnt = 1 << (log_n + log_blowup), 4 * (2 * n_cols + n_segments)
+        if len(z) != 4 or len(ood) != cnt or len(challenges) != cnt:
+            raise ValueError("dev_deep_compose: z has 4 coordinates, ood and challenges 4 (2 W + D) values")
+        za, oa, ca = (C.c_uint64 * 4)(*[int(v) for v in z]), (C.c_uint64 * cnt)(*[int(v) for v in ood]), (C.c_uint64 * cnt)(*[int(v) for v in challenges])
+        self._ck(self.L.smi_dev_deep_compose(self.h, C.byref(cfg), n_segments, vp(d_lde), N if stride is None else stride, vp(d_seg),
+                                             N if seg_stride is None else seg_stride, za, oa, ca, vp(d_out), N if out_stride is None else out_stride))
+
+    def _dev_air_prove_deep(self, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
+                            fill_multiplicities, folding):
+        self._check_deep(a, row_leaves, ext, folding, fill_multiplicities)
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
+        _d, D = air_plan_deep(self.p, a, cfg)
+        if check:
+            ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+            if not ok:
+                raise StarkMiError(-50, why)
+        roots = np.zeros((2, 32), dtype=np.uint8)
+        ood = np.zeros(4 * (2 * n_cols + D), dtype=np.uint64)
+        proof, plen = vp(), C.c_size_t()
+        top = np.zeros(max(t, 1), dtype=np.uint64)
+        stage = (C.c_double * 7)()
+        self._ck(self.L.smi_dev_air_prove_deep(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, ood.ctypes.data, C.byref(proof),
+                                               C.byref(plen), top.ctypes.data, stage if timed else None, 0 if grind_bits is None else grind_bits))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]],
+               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(2 * n_cols + D)]}
+        if timed:
+            out["stage_ms"] = dict(zip(("lde", "commit", "compose", "segments", "ood", "fri", "open"), [float(x) for x in stage]))
+        return out
+
     def _check_air_folding(self, a, folding, row_leaves, ext):
         _check_folding(folding)
         if folding == 4 and not (row_leaves and ext):
@@ -708,7 +772,7 @@ class Engine:
             raise StarkMiError(-50, "folding=4: the permutation, lookup and argument-list provers fold by 2 only")
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2):
+                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2, deep=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -727,8 +791,15 @@ class Engine:
         members (mirror.Air.extended_args) takes smi_dev_air_prove_xargs and smi_dev_xargs_multiplicities instead.
         folding=4 (needs row_leaves=True, ext=True and an AIR without permutation, lookup or argument list; StarkMiError
         otherwise, and for any value but 2 and 4): smi_dev_air_prove_ext_fold4 -- FRI at folding factor 4, the rows opened at
-        the four points of every layer-0 coset; grind_bits None counts as 0."""
+        the four points of every layer-0 coset; grind_bits None counts as 0.
+        deep=True (needs row_leaves=True, ext=True; ValueError together with a permutation, a lookup, an argument list or
+        folding=4): smi_dev_air_prove_deep -- out-of-domain sampling, FRI at the full blowup (include/stark_mi.h, "Out-of-domain
+        sampling").  column_roots is (2, 32) -- root_1, root_2 --, the result gains "ood" (the record's 2 W + D elements of
+        four coordinates each), stage_ms has seven stages, grind_bits None counts as 0."""
         a = self._air(air)
+        if deep:
+            return self._dev_air_prove_deep(a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed, check,
+                                            row_leaves, ext, grind_bits, fill_multiplicities, folding)
         self._check_air_folding(a, folding, row_leaves, ext)
         if self._xargs(a) is not None:
             if not (row_leaves and ext):
@@ -873,7 +944,7 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2):
+                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
@@ -881,7 +952,19 @@ class Engine:
         column_roots is root_1 then root_2, grind_bits None counts as 0.  An AIR with a lookup takes smi_air_verify_lookup in
         the same way, and an AIR with an argument list smi_air_verify_args (smi_air_verify_xargs when the list has selectors
         or periodic members).
-        folding=4: smi_air_verify_ext_fold4, under the conditions of dev_air_prove(folding=4)."""
+        folding=4: smi_air_verify_ext_fold4, under the conditions of dev_air_prove(folding=4).
+        deep=True: smi_air_verify_deep, under the conditions of dev_air_prove(deep=True); column_roots is root_1 then root_2."""
+        if deep:
+            a = self._air(air)
+            self._check_deep(a, row_leaves, ext, folding, False)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 64:
+                raise StarkMiError(-50, "air_verify(deep=True) takes two 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_deep(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         self._check_air_folding(self._air(air), folding, row_leaves, ext)
         if self._xargs(self._air(air)) is not None:
             if not (row_leaves and ext):
@@ -1032,6 +1115,19 @@ def air_plan(p, air, cfg):
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return d.value, e.value
+
+
+def air_plan_deep(p, air, cfg, with_length=False):
+    """smi_air_plan_deep (host only) -> (d, D), or with_length (d, D, proof bytes of smi_air_deep_layout for cfg's number of
+    colinearity tests).  air: a flattened _lib.Air"""
+    d, D, n = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_plan_deep(p, C.byref(cfg), C.byref(air), C.byref(d), C.byref(D))
+    if not st and with_length:
+        st = L.smi_air_deep_layout(p, C.byref(cfg), C.byref(air), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return (d.value, D.value, n.value) if with_length else (d.value, D.value)
 
 
 def air_plan_perm(p, air, perm, cfg):

@@ -29,6 +29,7 @@ std::vector<uint32_t> fill(const GeomSpec &s, const Fp &F) {
 // ntt_pass_cols_kernel: every column of a tile by one workgroup, output multipliers derived once per thread
 template <int LOGR, int LOGW, int KIND, int CAP> void emu_pass_cols(const PassArgs &a) {
     typedef NttPass<LOGR, LOGW, KIND, CAP> NP;
+    typedef NttPass<LOGR, LOGW, KIND, CAP, smi_cols_uniform_bases(LOGR, LOGW, KIND == PASS_MID, false)> NPN;   // the kernel's choice without TWIN
     constexpr bool LAST = KIND == PASS_LAST;
     const uint32_t NT = NP::NT;
     std::vector<uint32_t> tile(NP::R * NP::WP);
@@ -54,7 +55,7 @@ template <int LOGR, int LOGW, int KIND, int CAP> void emu_pass_cols(const PassAr
             } else if (!LAST) {
 #define ZCASE(Z)                                                                                                 \
     case Z:                                                                                                      \
-        for (uint32_t tid = 0; tid < NT; tid++) NP::template load_regs<Z>(a, t, b, r16(regs[tid]), tid);         \
+        for (uint32_t tid = 0; tid < NT; tid++) NPN::template load_regs<Z>(a, t, b, r16(regs[tid]), tid);        \
         for (uint32_t tid = 0; tid < NT; tid++) NP::template step0_regs<Z>(a, r16(regs[tid]), tile.data(), tw.data(), tid); \
         break;
                 switch (a.zlog) { ZCASE(2) ZCASE(3) ZCASE(4) default: ZCASE(0) }
@@ -68,7 +69,10 @@ template <int LOGR, int LOGW, int KIND, int CAP> void emu_pass_cols(const PassAr
                 for (uint32_t tid = 0; tid < NT; tid++) NP::step0_lds(a, tile.data(), tw.data(), tid);
             }
             for (uint32_t tid = 0; tid < NT; tid++) NP::step_mid(a, tile.data(), tw.data(), tid);
-            for (uint32_t tid = 0; tid < NT; tid++) NP::last_step_store_mul(a, t, b, tile.data(), tw.data(), tid, r16(mw[tid]), r16(mq[tid]));
+            for (uint32_t tid = 0; tid < NT; tid++) {
+                if (twin) NP::last_step_store_mul(a, t, b, tile.data(), tw.data(), tid, r16(mw[tid]), r16(mq[tid]));
+                else NPN::last_step_store_mul(a, t, b, tile.data(), tw.data(), tid, r16(mw[tid]), r16(mq[tid]));
+            }
         }
     }
 }

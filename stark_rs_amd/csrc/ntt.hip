@@ -70,12 +70,21 @@ __global__ __launch_bounds__(1 << (LOGR + LOGW - 4)) void ntt_pass_kernel(const 
 #ifndef SMI_COLS_TWIN_MQ
 #define SMI_COLS_TWIN_MQ 1
 #endif
+// The scalar twin of the column loops' opaque thread index: the row and run bases of a column's accesses are uniform (ntt_core.h,
+// ld32), and everything in them but the column is loop-invariant -- hoisted, sixteen 64-bit offsets per direction would be
+// held in scalar registers across the loop and spilled.  A per-iteration copy of the arguments whose sizes (L, Sp) the
+// compiler cannot see through keeps them where they are used: two strides, one scalar add per access.
+#define SMI_OPAQUE_SIZE(a, a0)        \
+    PassArgs a##_it = a0;             \
+    if constexpr (NP::UNIFORM_BASES) asm volatile("" : "+s"(a##_it.L), "+s"(a##_it.Sp)); \
+    const PassArgs &a = a##_it
 #ifndef SMI_COLS_PREFETCH   // the middle pass's column loop issues the next column's loads under the current column's last step and stores
 #define SMI_COLS_PREFETCH 1  // (r03, profiles/r03_r_prefetch_ab.log, r03_s_prefetch_ab.log: -1.2 ... -1.8 % per step)
 #endif
 template <int LOGR, int LOGW, int KIND, int CAP, bool TWIN = false>   // TWIN: the previous pass left its twiddles to this one (NTT_TW_IN)
-__global__ __launch_bounds__(1 << (LOGR + LOGW - 4), TWIN ? SMI_COLS_TWIN_WAVES : SMI_COLS_WAVES(LOGR + LOGW, LOGR)) void ntt_pass_cols_kernel(const PassArgs a) {
-    typedef NttPass<LOGR, LOGW, KIND, CAP> NP;
+__global__ __launch_bounds__(1 << (LOGR + LOGW - 4), TWIN ? SMI_COLS_TWIN_WAVES : SMI_COLS_WAVES(LOGR + LOGW, LOGR)) void ntt_pass_cols_kernel(const PassArgs a0) {
+    const PassArgs &a = a0;
+    typedef NttPass<LOGR, LOGW, KIND, CAP, smi_cols_uniform_bases(LOGR, LOGW, KIND == PASS_MID, TWIN)> NP;
     __shared__ uint32_t tile[NP::R * NP::WP];
     __shared__ Tw2 tw[NP::R];
     const uint32_t tid0 = threadIdx.x;
@@ -97,22 +106,23 @@ __global__ __launch_bounds__(1 << (LOGR + LOGW - 4), TWIN ? SMI_COLS_TWIN_WAVES 
     // changes nothing further (0.6964-0.6974) and is not built.
     if constexpr (SMI_COLS_PREFETCH && KIND == PASS_MID && LOGW == 5) {
         uint32_t v[NP::V];
-        auto load = [&](uint32_t col) {
+        auto load = [&](const PassArgs &a, uint32_t col) {
             uint32_t tid = tid0;
             asm volatile("" : "+v"(tid));   // see below: keeps the tile program's addresses from being hoisted
             NP::template load_regs<0, !TWIN>(a, t, col, v, tid);
         };
-        load(col0);
+        load(a0, col0);
         for (uint32_t batch = col0; batch < col1; batch++) {
             uint32_t tid = tid0;
             asm volatile("" : "+v"(tid));
+            SMI_OPAQUE_SIZE(a, a0);
             if constexpr (TWIN) {
 #pragma unroll
                 for (int i = 0; i < NP::V; i++) v[i] = mont_mul(v[i], iw[i], a.F);
             }
             __syncthreads();                // the previous column's LDS reads are over (first column: the twiddle table is staged)
             NP::template step0_regs<0>(a, v, tile, tw, tid);
-            if (batch + 1 < col1) load(batch + 1);
+            if (batch + 1 < col1) load(a, batch + 1);
             __syncthreads();
             if (NP::St::n == 3) {
                 NP::step_mid(a, tile, tw, tid);
@@ -127,6 +137,7 @@ __global__ __launch_bounds__(1 << (LOGR + LOGW - 4), TWIN ? SMI_COLS_TWIN_WAVES 
         // across the columns) is hoisted and held in registers -- 150 VGPRs, or spills under a bound
         uint32_t tid = tid0;
         asm volatile("" : "+v"(tid));
+        SMI_OPAQUE_SIZE(a, a0);
         uint32_t v[NP::V];
         // the barrier after the loads also separates the previous column's LDS reads from this column's writes
         static_assert(KIND != PASS_FIRST, "first passes keep one workgroup per (tile, column), NttPass::share_cols");
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(1 << (LOGR + LOGW - 4), TWIN ? SMI_COLS_TWIN_WAVES 
 template <int LOGR, int LOGW, int KIND>
 __global__ __launch_bounds__(1 << (LOGR + LOGW - 4)) void ntt_copy_probe_kernel(const PassArgs a) {
     typedef NttPass<LOGR, LOGW, KIND, 4> NP;
-    enum { NB = (NP::TILE / NP::RL) / NP::NT, KSTEP_LOG = LOGR - NP::SL };
+    enum { NB = (NP::TILE / NP::RL) / NP::NT };
     const uint32_t tid = threadIdx.x, batch = blockIdx.y;
     const typename NP::TileId t = NP::tile_id(a, blockIdx.x);
     uint32_t v[NP::V];
@@ -196,12 +207,14 @@ __global__ __launch_bounds__(1 << (LOGR + LOGW - 4)) void ntt_copy_probe_kernel(
     }
     uint32_t *out = a.out + (uint64_t)batch * a.out_stride + t.out_base;
     const uint32_t sh = KIND == PASS_LAST ? a.Sp : a.L - a.Sp - LOGR;   // stride of the frequency index in the output
+    const uint32_t o0 = NP::out_off(tid, sh);                            // the pass's own address formation (ntt_core.h)
+    typename NP::OutRuns runs(out, sh);
 #pragma unroll
     for (int bi = 0; bi < NB; bi++) {
         const uint32_t u = tid + bi * NP::NT;
-        const uint32_t o0 = (NP::blk_to_k(u >> LOGW) << sh) + (u & (NP::W - 1));
+        uint32_t *run = runs.next_bi();
 #pragma unroll
-        for (int kk = 0; kk < NP::RL; kk++) st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + sh)), v[bi * NP::RL + kk] + 1u);
+        for (int kk = 0; kk < NP::RL; kk++) NP::st_out(out, runs, run, o0, sh, u >> LOGW, u & (NP::W - 1), kk, v[bi * NP::RL + kk] + 1u);
     }
 }
 

@@ -36,8 +36,10 @@
 #if defined(SMI_EMU_CHECKS) && !defined(__HIP_DEVICE_COMPILE__)
 #include <assert.h>
 #define SMI_BOUND_CHECK(x, m, p) assert((m) <= 8 && (uint64_t)(x) < (uint64_t)((m) ? (m) : 1) * (p) && ((m) || (x) == 0))
+#define SMI_INDEX_CHECK(i, n) assert((uint64_t)(i) < (uint64_t)(n))   // an unmasked table index (step twiddles)
 #else
 #define SMI_BOUND_CHECK(x, m, p) ((void)0)
+#define SMI_INDEX_CHECK(i, n) ((void)0)
 #endif
 
 #define SMI_TILE_LOG 12          // smallest tile (and the size limit of the single-workgroup kernel)
@@ -99,6 +101,11 @@ struct PassArgs {
 // have for it; the driver's choice to defer the first pass's twiddles (ntt_driver.h) uses the same numbers
 enum { SMI_COLS_PER_WG = 4, SMI_COLS_MIN_WGS = 1024 };
 
+// ntt_pass_cols_kernel instantiations that keep a vector offset per access (NttPass's UB = false): the (7, 5) middle pass that
+// applies no deferred twiddles needs 72 / 80 vector registers with uniform bases against 64 / 65 without, one workgroup per
+// CU fewer (tools/isa_compare.py)
+constexpr bool smi_cols_uniform_bases(int logr, int logw, bool mid, bool twin) { return !(mid && logr == 7 && logw == 5 && !twin); }
+
 template <int LOGR> struct Steps;
 template <> struct Steps<6>  { enum { n = 2, s0 = 4, s1 = 2, s2 = 0 }; };
 template <> struct Steps<7>  { enum { n = 2, s0 = 4, s1 = 3, s2 = 0 }; };
@@ -125,9 +132,16 @@ SMI_HD uint32_t two_level(const uint32_t *lo, const uint32_t *hi, uint32_t h, ui
     return mont_mul(lo[e & ((1u << h) - 1u)], hi[e >> h], F);
 }
 
-// Global accesses as wave-uniform base + 32-bit byte offset (all tile-relative offsets stay below
-// 2^30 elements): lets the compiler use the SGPR-base addressing form instead of a 64-bit
-// vector add per access.
+// Global accesses as wave-uniform base + 32-bit byte offset: lets the compiler use the SGPR-base
+// addressing form instead of a 64-bit vector add per access.  An access of a middle or last pass is
+// ld32(base + uniform, thread) / st32(base + uniform, thread, v)  (NttPass::UNIFORM_BASES; the first pass and one
+// column-sharing instantiation keep a 32-bit vector offset per access beside the column's base):
+//   64-bit, in the pointer (scalar adds): the column (batch * stride), the tile (in_base / out_base) and the row or
+//       output run of the access -- i * T << ablog of a strided load, kk << (KSTEP_LOG + olog) and bi * RL << olog of
+//       a store -- everything that depends on kernel arguments and unrolled loop counters only;
+//   32-bit, in `idx` (one vector register per tile and direction): the thread's own place in the tile,
+//       (j0 << ablog) + w of a load, (blk_to_k(tid >> LOGW) << olog) + w of a store.  It stays below the tile's
+//       extent in memory, R rows of the column: below 2^30 elements for any transform the tables reach.
 #ifndef SMI_NTT_NT
 #define SMI_NTT_NT 0   // 1: tuning builds (non-temporal data loads and stores)
 #endif
@@ -151,6 +165,20 @@ SMI_HD void st32(uint32_t *base, uint32_t idx, uint32_t v) {
 #endif
 }
 SMI_HD Tw2 ld_tw(const Tw2 *base, uint32_t idx) { return *(const Tw2 *)((const char *)base + (size_t)(uint32_t)(idx << 3)); }
+
+// Step twiddles of a thread's butterfly, tw[stride * kk] for kk = 1, 2, ...: the index as a running sum of byte offsets
+// (one plain add per twiddle) instead of a product, a shift and a mask.  No mask is needed: the callers' largest index
+// stays below the table's n entries (bounds at the call sites; the emulator asserts every index).
+struct TwRun {
+    uint32_t off, stride;   // bytes
+    SMI_HD explicit TwRun(uint32_t stride_idx) : off(0), stride(stride_idx << 3) {}
+    SMI_HD Tw2 next(const Tw2 *tw, uint32_t n) {
+        off += stride;
+        SMI_INDEX_CHECK(off >> 3, n);
+        (void)n;
+        return *(const Tw2 *)((const char *)tw + off);
+    }
+};
 
 // ---- lazy arithmetic on [0, 2p), p < 2^30
 SMI_HD uint32_t shoup_mul(uint32_t a, const Tw2 &c, uint32_t p) {               // any a < 2^32 -> [0,2p)
@@ -223,16 +251,20 @@ SMI_HD void dft_regs(uint32_t (&x)[1 << S], int (&m)[1 << S], const Tw2 *cw, int
 //   last pass:    load_tw, load_rows, rows_to_lds | sync | step0_lds | sync | [step_mid | sync] | last_step_store
 enum { PASS_FIRST = 0, PASS_MID = 1, PASS_LAST = 2 };   // kernel kinds: first strided pass (zero padding, coset
                                                          // scale), later strided passes, last pass (transposing)
-template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
-    static constexpr bool FIRST = KIND == PASS_FIRST, MID = KIND == PASS_MID, LAST = KIND == PASS_LAST;
+struct NttTileId {  // wave-uniform description of the tile a workgroup owns
+    uint64_t in_base, out_base;  // element offsets of line 0 / output run 0 (within the column)
+    uint32_t b0;                 // first inner column (strided passes) / first k_0 (last pass)
+};
+// UB (uniform bases): the addresses of the global accesses as uniform row / run base + one thread offset (ld32 above).
+// false keeps a vector offset per access, for the one instantiation that needs more vector registers with the uniform
+// form than its occupancy step has (smi_cols_uniform_bases); same addresses either way.
+template <int LOGR, int LOGW, int KIND, int CAP, bool UB = true> struct NttPass {
+    static constexpr bool FIRST = KIND == PASS_FIRST, MID = KIND == PASS_MID, LAST = KIND == PASS_LAST, UNIFORM_BASES = UB && !FIRST;
     enum { TILE_LOG = LOGR + LOGW, TILE = 1 << TILE_LOG, NT = TILE / 16, R = 1 << LOGR, W = 1 << LOGW, WP = W + 1, V = 16 };
     typedef Steps<LOGR> St;
     enum { SL = St::n == 2 ? St::s1 : St::s2, RL = 1 << SL };   // radix of the last step
 
-    struct TileId {  // wave-uniform description of the tile this workgroup owns
-        uint64_t in_base, out_base;  // element offsets of line 0 / output run 0 (within the column)
-        uint32_t b0;                 // first inner column (strided passes) / first k_0 (last pass)
-    };
+    typedef NttTileId TileId;
 
     static SMI_HD TileId tile_id(const PassArgs &a, uint32_t block) {
         TileId t;
@@ -283,7 +315,9 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
         const uint32_t o0 = (j0 << ablog) + w;              // address within the tile's rows
         if constexpr (FIRST) {
             // zero padding: in_base == b0 in the first pass, so b_off + b0 + (j << blog) + w is the natural index.
-            // Branch-free (clamped address + select) so the loads issue back to back.
+            // Branch-free (clamped address + select) so the loads issue back to back.  These loads keep a vector offset
+            // each: with a uniform row base per load (selected against the padding, so that no row of padding is
+            // addressed) the first passes measured slower, 35 -> 38 and 115 -> 118 us (profiles/row_bases_kernel_means.txt).
             const uint32_t *col = a.in + (uint64_t)batch * a.in_stride;
             const uint32_t n0 = a.b_off + t.b0 + (j0 << blog) + w;
 #pragma unroll
@@ -307,7 +341,14 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
         } else {
             const uint32_t *in = a.in + (uint64_t)batch * a.in_stride + t.in_base;
 #pragma unroll
-            for (int i = 0; i < V; i++) v[i] = ld32(in, o0 + ((uint32_t)(i * (NT >> LOGW)) << ablog));
+            for (int i = 0; i < V; i++) {
+                if constexpr (UNIFORM_BASES) {   // row base uniform (a running pointer), one thread offset
+                    v[i] = ld32(in, o0);
+                    in += (size_t)(NT >> LOGW) << ablog;
+                } else {
+                    v[i] = ld32(in, o0 + ((uint32_t)(i * (NT >> LOGW)) << ablog));
+                }
+            }
             if (TWIN && (a.flags & NTT_TW_IN)) {
                 // the previous pass's w_m'^(k b'), m' = 2^(L - Sp + prev_logr): k = its output digit = the low
                 // prev_logr bits of this tile's sub-problem index, b' = (row << blog) + column; along a
@@ -334,11 +375,12 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
         for (int i = 0; i < 16; i++) m[i] = i < (V >> Z) ? 1 : 0;   // canonical loads / scaled products; padding
         dft_regs<4, CAP, Z>(x, m, tw, LOGR - 4, a.F);
+        TwRun run(pos);   // w_R^(pos * kk): pos < R/16 and kk < 16, so pos * kk <= 15 * (R/16 - 1) < R
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) {
             uint32_t v = x[brev<4>(kk)];
             int mv = m[brev<4>(kk)];
-            if (kk) v = shoup_mul(v, tw[(pos * kk) & (R - 1)], a.F.p);
+            if (kk) v = shoup_mul(v, run.next(tw, R), a.F.p);
             else lz_fold_to2(v, mv, a.F.p);
             tile[(pos + ((uint32_t)kk << SUB)) * WP + w] = v;       // LDS holds [0,2p)
         }
@@ -349,11 +391,13 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
     static SMI_HD void load_rows(const PassArgs &a, const TileId &t, uint32_t batch, uint32_t (&v)[V], uint32_t tid) {
         const uint32_t *in = a.in + (uint64_t)batch * a.in_stride + t.in_base;
         const uint32_t arest_log = a.Sp - a.d0_log;
+        // element idx = tid + i * NT of the tile is (line idx >> LOGR, point idx & (R - 1)); tid < NT, a power of two, so the
+        // bits of i * NT and of tid do not meet: the line and point of i * NT go to the base, those of tid are the offset
+        const uint32_t o0 = ((tid >> LOGR) << (arest_log + LOGR)) + (tid & (R - 1));
 #pragma unroll
         for (int i = 0; i < V; i++) {
-            const uint32_t idx = tid + i * NT;
-            const uint32_t j = idx & (R - 1), l = idx >> LOGR;
-            v[i] = ld32(in, (l << (arest_log + LOGR)) + j);
+            const uint32_t e = (uint32_t)i * NT;
+            v[i] = ld32(in + (((size_t)(e >> LOGR) << (arest_log + LOGR)) + (e & (R - 1))), o0);
         }
     }
     static SMI_HD void rows_to_lds(const uint32_t (&v)[V], uint32_t *tile, uint32_t tid) {
@@ -395,11 +439,12 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
         for (int i = 0; i < 16; i++) m[i] = 1;                      // canonical loads
         dft_regs<4, CAP>(x, m, tw, LOGR - 4, a.F);
+        TwRun run(pos);   // as in step0_regs: pos < R/16 (direct_map), pos * kk < R
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) {
             uint32_t v = x[brev<4>(kk)];
             int mv = m[brev<4>(kk)];
-            if (kk) v = shoup_mul(v, tw[(pos * kk) & (R - 1)], a.F.p);
+            if (kk) v = shoup_mul(v, run.next(tw, R), a.F.p);
             else lz_fold_to2(v, mv, a.F.p);
             tile[(pos + ((uint32_t)kk << SUB)) * WP + line] = v;    // what step0_lds leaves: LDS holds [0,2p)
         }
@@ -421,11 +466,14 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
             for (int q = 0; q < r; q++) m[q] = MIN;
             dft_regs<S, CAP>(x, m, tw, LOGR - S, a.F);
+            // w_2^MLOG^(pos * kk) = tw[(pos * kk) << (LOGR - MLOG)]: pos < 2^(MLOG - S) and kk < 2^S, so pos * kk < 2^MLOG
+            // and the index is below R
+            TwRun run(pos << (LOGR - MLOG));
 #pragma unroll
             for (int kk = 0; kk < r; kk++) {
                 uint32_t v = x[brev<S>(kk)];
                 int mv = m[brev<S>(kk)];
-                if (kk) v = shoup_mul(v, tw[((pos * kk) << (LOGR - MLOG)) & (R - 1)], a.F.p);
+                if (kk) v = shoup_mul(v, run.next(tw, R), a.F.p);
                 else lz_fold_to2(v, mv, a.F.p);
                 tile[(base + ((uint32_t)kk << SUB)) * WP + w] = v;
             }
@@ -444,6 +492,35 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
         return k0 | (k1 << St::s0);
     }
 
+    // Store addresses of the last step.  Output kk of a thread's butterfly bi is frequency blk_to_k(blk) + kk * (R/RL), blk =
+    // (tid >> LOGW) + bi * (R/16); a step of R/16 in blk is a step of RL in blk_to_k (two-step tiles: R/16 = RL; three-step
+    // tiles: it moves k_0 = blk >> s1 by 2^s2 = RL and leaves k_1).  With olog = log2 of the frequency index's stride in
+    // memory the element is  out + [(bi * RL + kk * (R/RL)) << olog]  +  [(blk_to_k(tid >> LOGW) << olog) + w]:
+    // a uniform run base per store and one offset per thread and tile.  The run bases are running pointers (two strides
+    // held, one 64-bit scalar add per store) rather than 16 separate offsets, which a column loop would hoist and hold.
+    static SMI_HD uint32_t out_off(uint32_t tid, uint32_t olog) { return (blk_to_k(tid >> LOGW) << olog) + (tid & (W - 1)); }
+    struct OutRuns {
+        uint32_t *bi_base;
+        size_t kstep, bstep;
+        SMI_HD OutRuns(uint32_t *out, uint32_t olog) : bi_base(out), kstep((size_t)1 << (LOGR - SL + olog)), bstep((size_t)RL << olog) {}
+        SMI_HD uint32_t *next_bi() {   // run 0 of the next butterfly
+            uint32_t *r = bi_base;
+            bi_base += bstep;
+            return r;
+        }
+        SMI_HD uint32_t *next(uint32_t *&run) const {   // the butterfly's next run
+            uint32_t *r = run;
+            run += kstep;
+            return r;
+        }
+    };
+    // store kk of butterfly bi (blk, w its block and line): by run base and the thread's one offset, or -- UNIFORM_BASES false
+    // -- by the column's base and a vector offset of its own
+    static SMI_HD void st_out(uint32_t *out, const OutRuns &runs, uint32_t *&run, uint32_t o0, uint32_t olog, uint32_t blk, uint32_t w, int kk, uint32_t y) {
+        if constexpr (UNIFORM_BASES) st32(runs.next(run), o0, y);
+        else st32(out, (blk_to_k(blk) << olog) + w + ((uint32_t)kk << (LOGR - SL + olog)), y);
+    }
+
     // Last in-tile step (radix RL, no step twiddles) fused with the store: outputs leave from
     // registers.  A butterfly's outputs are frequencies k = kbase + kk*(R/RL), kk < RL: an
     // arithmetic progression, so inter-pass twiddles / output scales are running products.
@@ -452,6 +529,9 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
         enum { NB = (TILE / RL) / NT, KSTEP_LOG = LOGR - SL };
         uint32_t *out = a.out + (uint64_t)batch * a.out_stride + t.out_base;
         const uint32_t mlog = a.L - a.Sp, p = a.F.p;
+        const uint32_t olog = LAST ? a.Sp : mlog - LOGR - a.shard_log;   // log2 of the frequency index's stride in memory (strided passes: the row length)
+        const uint32_t o0 = out_off(tid, olog);
+        OutRuns runs(out, olog);
         // Butterfly bi of a thread has kbase = kbase_0 + bi * RL (its block index advances by R/16,
         // i.e. k_0 by RL), so the per-butterfly bases are running products as well: three table
         // lookups per thread whatever NB is.
@@ -483,10 +563,8 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
             for (int q = 0; q < RL; q++) m[q] = 2;
             dft_regs<SL, CAP>(x, m, tw, LOGR - SL, a.F);   // outputs < CAP*p: fine for any multiply below
-            const uint32_t kbase = blk_to_k(blk);
+            uint32_t *run = runs.next_bi();
             if constexpr (!LAST) {
-                const uint32_t blog = mlog - LOGR - a.shard_log;   // row length in memory
-                const uint32_t o0 = (kbase << blog) + w;
                 {
                     // inter-pass twiddles w_m^(k*b) = g^k, g = w_m^b: running products over kk (and over
                     // the thread's butterflies, see above).  A per-pass table of (w, Shoup quotient)
@@ -500,7 +578,7 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
                         for (int kk = 0; kk < RL; kk++) {
                             SMI_BOUND_CHECK(x[brev<SL>(kk)], m[brev<SL>(kk)], p);
-                            st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + blog)), x[brev<SL>(kk)]);
+                            st_out(out, runs, run, o0, olog, blk, w, kk, x[brev<SL>(kk)]);
                         }
                         continue;
                     }
@@ -508,23 +586,22 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
                     if (bi + 1 < NB) base_run = mont_mul_c(base_run, gbi, gbq, a.F);
 #pragma unroll
                     for (int kk = 0; kk < RL; kk++) {
-                        st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + blog)), mont_mul(x[brev<SL>(kk)], cur, a.F));
+                        st_out(out, runs, run, o0, olog, blk, w, kk, mont_mul(x[brev<SL>(kk)], cur, a.F));
                         if (kk + 1 < RL) cur = mont_mul_c(cur, gs, gq, a.F);
                     }
                 }
             } else {
-                const uint32_t o0 = (kbase << a.Sp) + w;
                 if (a.flags & NTT_POST_SCALE) {
                     uint32_t sc = sc_run;
                     if (bi + 1 < NB) sc_run = mont_mul_c(sc_run, a.post_bi_ratio_m, rbq, a.F);
 #pragma unroll
                     for (int kk = 0; kk < RL; kk++) {
-                        st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + a.Sp)), mont_mul(x[brev<SL>(kk)], sc, a.F));
+                        st_out(out, runs, run, o0, olog, blk, w, kk, mont_mul(x[brev<SL>(kk)], sc, a.F));
                         if (kk + 1 < RL) sc = mont_mul_c(sc, a.post_ratio_m, rq, a.F);
                     }
                 } else {
 #pragma unroll
-                    for (int kk = 0; kk < RL; kk++) st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + a.Sp)), lz_canon_m(x[brev<SL>(kk)], m[brev<SL>(kk)], p));
+                    for (int kk = 0; kk < RL; kk++) st_out(out, runs, run, o0, olog, blk, w, kk, lz_canon_m(x[brev<SL>(kk)], m[brev<SL>(kk)], p));
                 }
             }
         }
@@ -594,9 +671,11 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
     template <bool MQ = true>
     static SMI_HD void last_step_store_mul(const PassArgs &a, const TileId &t, uint32_t batch, const uint32_t *tile, const Tw2 *tw,
                                            uint32_t tid, const uint32_t (&mw)[V], const uint32_t (&mq)[MQ ? V : 1]) {
-        enum { NB = (TILE / RL) / NT, KSTEP_LOG = LOGR - SL };
+        enum { NB = (TILE / RL) / NT };
         uint32_t *out = a.out + (uint64_t)batch * a.out_stride + t.out_base;
         const uint32_t olog = LAST ? a.Sp : a.L - a.Sp - LOGR - a.shard_log;   // log2 of the frequency index's stride in memory
+        const uint32_t o0 = out_off(tid, olog);
+        OutRuns runs(out, olog);
 #pragma unroll
         for (int bi = 0; bi < NB; bi++) {
             const uint32_t u = tid + bi * NT;
@@ -608,11 +687,12 @@ template <int LOGR, int LOGW, int KIND, int CAP> struct NttPass {
 #pragma unroll
             for (int q = 0; q < RL; q++) m[q] = 2;
             dft_regs<SL, CAP>(x, m, tw, LOGR - SL, a.F);
-            const uint32_t o0 = (blk_to_k(blk) << olog) + w;
+            uint32_t *run = runs.next_bi();
 #pragma unroll
-            for (int kk = 0; kk < RL; kk++)
-                if constexpr (MQ) st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + olog)), mont_mul_c(x[brev<SL>(kk)], mw[bi * RL + kk], mq[bi * RL + kk], a.F));
-                else st32(out, o0 + ((uint32_t)kk << (KSTEP_LOG + olog)), mont_mul(x[brev<SL>(kk)], mw[bi * RL + kk], a.F));
+            for (int kk = 0; kk < RL; kk++) {
+                const uint32_t y = MQ ? mont_mul_c(x[brev<SL>(kk)], mw[bi * RL + kk], mq[MQ ? bi * RL + kk : 0], a.F) : mont_mul(x[brev<SL>(kk)], mw[bi * RL + kk], a.F);
+                st_out(out, runs, run, o0, olog, blk, w, kk, y);
+            }
         }
     }
 };

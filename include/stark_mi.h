@@ -1031,7 +1031,9 @@ int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   the same list; the roots, the columns and the codeword are equal too.
  * Limits (SMI_ERR_BAD_ARG, the reason names the argument): those of "Argument list"; every operand a this-row variable;
  *   mult_col < n_cols, none of the argument's trace operands, none of its selectors; everything smi_air_plan refuses.
- * Left out: next-row tuple members; several lookups sharing one multiplicity column; a column-tree or smi_mgpu_* twin. */
+ * Left out: next-row tuple members; several lookups sharing one multiplicity column; a column-tree or smi_mgpu_* twin.
+ *   (FRI at the full blowup and a lookup list at log_blowup = 2 are what "Out-of-domain sampling with an argument list"
+ *   below adds.) */
 #define SMI_ARG_NO_SELECTOR 0xffffffffu
 typedef struct smi_air_xarg {
     uint32_t kind;            /* SMI_ARG_PERM = 0, SMI_ARG_LOOKUP = 1              */
@@ -1128,8 +1130,9 @@ int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air
  *   recomputed from the opened rows against the layer-0 triple's a and b.  A proof of smi_dev_air_prove_ext_pow is rejected
  *   here, and a proof of this variant by smi_air_verify_ext_pow.
  * Soundness accounting and measured times: DESIGN.md section 11, "Out-of-domain sampling".
- * Left out: folding factor 4; permutation, lookup and argument lists; column trees; smi_mgpu_* twins; zero-knowledge
- *   randomisers; binding an AIR digest into the transcript; the segment extension fused into the leaf hash. */
+ * Left out: folding factor 4; column trees; smi_mgpu_* twins; zero-knowledge randomisers; binding an AIR digest into the
+ *   transcript; the segment extension fused into the leaf hash.  (Permutation, lookup and argument lists are what
+ *   "Out-of-domain sampling with an argument list" below adds; these entry points stay as they are.) */
 /* Host only (like smi_air_plan): the plan above -> d and D. */
 int smi_air_plan_deep(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments);
 /* Host only: the plan, and the length in bytes of the proof of that shape (num_colinearity_tests is read as well). */
@@ -1158,6 +1161,86 @@ int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
 int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
                         uint32_t grind_bits);
+
+/* ---- Out-of-domain sampling with an argument list ----------------------------------------------
+ * The argument-list provers recompute the composition at the queried positions, so a list with a lookup (degree 3) needs
+ * log_blowup >= 3, runs FRI at E = B / 2 and opens four rows of two trees a test; "Out-of-domain sampling" above runs FRI at
+ * E = B and opens two rows a test, but takes a plain AIR.  This variant is out-of-domain sampling for an smi_air_xargs list
+ * (the superset form: a list without selectors is written as one with SMI_ARG_NO_SELECTOR everywhere): the A auxiliary F_q
+ * columns are opened at z and z w next to the trace, as production provers of this shape open main and auxiliary trace.
+ * A lookup list is provable at log_blowup = 2.  Every entry point above is unchanged, byte for byte, and keeps launching
+ * the kernels it launches.
+ *
+ * Notation of "Out-of-domain sampling" and "Argument list": W, K, A, D, n, B, N = n B, tau, h, w = omega_n, x_i = h omega_N^i,
+ *   c_a the polynomial of argument a's column, NW = W + K + 2 A weights.
+ * Plan (smi_air_plan_deep_xargs).  smi_air_plan_xargs's checks without its bound on E; d by that section's rule (a
+ *   permutation with a selector counts 3, any lookup 3); D the next power of two >= d - 1; refused as smi_air_plan_deep
+ *   refuses, with its sentences: D > B, B < 4, 4 D > 64.  4 A <= 32 always fits a leaf row.
+ * Prover.
+ *   1. smi_dev_lde of the trace, the row tree over it: root_1, absorbed by an empty transcript.
+ *   2. Counters 0 .. 7: alpha and gamma, as in step 3 of "Permutation argument".
+ *   3. The A columns (the launches of smi_dev_xargs_columns), ONE smi_dev_lde over their 4 A coordinate columns, ONE row tree
+ *      over those (n_cols = 4 A): root_2, absorbed.
+ *   4. Counters 8 + m, m < 4 NW: the composition weights of "Argument list" step 7.  H = the codeword of
+ *      smi_dev_air_compose_xargs on the N points; the columns' next-row values come from index (i + B) mod N.
+ *   5. The segments of H exactly as in step 3 of "Out-of-domain sampling"; the third tree is over their 4 D columns: root_3,
+ *      absorbed.
+ *   6. Counters 8 + 4 NW + e, e < 4: the coordinates of z.  A z in F_p is refused by prover and verifier with the sentence of
+ *      "Out-of-domain sampling".
+ *   7. One tag-2 record of 4 (2 W + 2 A + D) values, four canonical coordinates each, in this order: u_c = f_c(z) and
+ *      v_c = f_c(z w) for c < W; a_a = c_a(z) and b_a = c_a(z w) for a < A; s_j = H_j(z) for j < D.  c_a(z) is assembled on
+ *      the host as sum_e X^e coord_{a,e}(z) from the coefficients of the unextended coordinate columns (an inverse transform
+ *      of size n at offset tau), the way s_j is.  The payload is absorbed.
+ *   8. The following 4 (2 W + 2 A + D) counters: gamma_c, gamma'_c, delta_a, delta'_a, gamma''_j in record order.  The
+ *      transcript is then 32 (6 + NW + 2 (2 W + 2 A + D)) bytes.
+ *   9. The DEEP codeword over F_q, i < N:
+ *        Q(x_i) = sum_c gamma_c (f_c(x_i) - u_c) / (x_i - z) + sum_c gamma'_c (f_c(x_i) - v_c) / (x_i - z w)
+ *               + sum_a delta_a (c_a(x_i) - a_a) / (x_i - z) + sum_a delta'_a (c_a(x_i) - b_a) / (x_i - z w)
+ *               + sum_j gamma''_j (H_j(x_i) - s_j) / (x_i - z),   of degree < n.
+ *  10. Extension FRI with grinding continues that transcript at E = B, folding by 2.
+ *  11. Openings.  Per test a = top mod N/2 and b = a + N/2; three sections in the R = 2 row layout: rows of W values (tree 1),
+ *      rows of 4 A values (tree 2), rows of 4 D values (tree 3).  No + B rows.
+ * Proof bytes (smi_air_deep_xargs_layout):
+ *   9 + 32 (2W + 2A + D) + len_FRI(N, B, t) + 2t (9 + 8W) + 2t (9 + 32 log2 N) + 2t (9 + 32A) + 2t (9 + 32 log2 N)
+ *     + 2t (9 + 32D) + 2t (9 + 32 log2 N).
+ *   The three roots go to the caller, 96 bytes.  Host round trips of the prover: four -- the three roots and the record.
+ * Verifier (smi_air_verify_deep_xargs, host).  The checks of smi_air_verify_deep in their order, over three sections (their
+ *   sentences start "deep argument openings:"), with the consistency check extended to
+ *        sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z) + sum_a ( w_{W+K+2a} bq_a(z) + w_{W+K+2a+1} wq_a(z) ) = sum_j z^(j n) s_j;
+ *   permutation: bq_a = (a_a - 1) / (z - tau), wq_a = (b_a g_R(z) - a_a g_L(z)) / (z^n - tau^n); lookup: bq_a = a_a / (z - tau),
+ *   wq_a = ((b_a - a_a) f_L f_T - S_a f_T + M S_b f_L) / (z^n - tau^n); g_L, g_R, f_L, f_T, S, M as in "Argument list with
+ *   selectors and periodic members" with their operands at z: trace operand c is u_c, periodic operand j is pi_j(z), M is
+ *   u_{mult_col}.  No denominator vanishes for z outside F_p.  Q(x_a) and Q(x_b) are recomputed from the three opened rows
+ *   against the layer-0 triple.  A proof of smi_dev_air_prove_xargs or smi_dev_air_prove_deep is rejected here, and a
+ *   proof of this variant by their verifiers.
+ * The prover does not refuse a column that does not close: *closes is the mask of the list provers, and the verifier
+ *   rejects such a proof on the consistency check.  A zero denominator in a column is SMI_ERR_NO_INVERSE as
+ *   smi_dev_xargs_columns reports it.
+ * Soundness accounting: DESIGN.md section 11.
+ * Left out: folding factor 4; the single permutation / lookup forms (a one-element list covers them); next-row tuple
+ *   members; smi_mgpu_* twins; zero-knowledge randomisers; fusing the auxiliary quotients or the segment extension into
+ *   other launches. */
+/* Host only: the plan above -> d and D.  `xargs` is a pointer to an smi_air_xargs. */
+int smi_air_plan_deep_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments);
+/* Host only: the plan, and the length in bytes of the proof of that shape (num_colinearity_tests is read as well). */
+int smi_air_deep_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, size_t *proof_len);
+/* The DEEP codeword of step 9 on its own: smi_dev_deep_compose with n_args auxiliary F_q columns, 1 .. SMI_ARGS_MAX.
+ * d_c_lde: their 4 n_args extended coordinate columns c_stride apart (column 4 a + e = coordinate e of c_a); ood: the
+ * record's 4 (2 W + 2 A + D) canonical values; challenges: as many unreduced u64 in record order.  One streaming launch,
+ * 4 (W + 4 A + 4 D) + 16 bytes a point; an auxiliary column costs four loads and two prepared F_q multiplies a point.
+ * 16-byte accesses when the four bases are 16-byte aligned and the four strides multiples of 4, 4-byte accesses with the
+ * same values otherwise. */
+int smi_dev_deep_compose_args(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_args, uint32_t n_segments, const uint32_t *d_lde, size_t stride,
+                              const uint32_t *d_c_lde, size_t c_stride, const uint32_t *d_seg, size_t seg_stride, const uint64_t z[4], const uint64_t *ood,
+                              const uint64_t *challenges, uint32_t *d_out, size_t out_stride);
+/* The prover above.  roots (optional): root_1, root_2, root_3, 96 bytes; ood (optional): the record's 4 (2 W + 2 A + D)
+ * values; stage_ms (optional) gets eight values {lde, commit, args, compose, segments, ood, fri, open}; *closes (optional):
+ * bit a is set iff argument a closes. */
+int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols, uint8_t *roots,
+                                 uint64_t *ood, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits,
+                                 uint32_t *closes);
+int smi_air_verify_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                              size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

@@ -269,6 +269,13 @@ def lib():
         "smi_dev_deep_compose": (i32, [vp, C.POINTER(StarkCfg), C.c_uint32, vp, sz, vp, sz, u64p, u64p, u64p, vp, sz]),
         "smi_dev_air_prove_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
         "smi_air_verify_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_plan_deep_xargs": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u32p, u32p]),
+        "smi_air_deep_xargs_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), C.POINTER(sz)]),
+        "smi_dev_deep_compose_args": (i32, [vp, C.POINTER(StarkCfg), C.c_uint32, C.c_uint32, vp, sz, vp, sz, vp, sz, u64p, u64p, u64p, vp, sz]),
+        "smi_dev_air_prove_deep_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, vp, vp, C.POINTER(vp), C.POINTER(sz), vp,
+                                               vp, C.c_uint32, u32p]),
+        "smi_air_verify_deep_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32),
+                                            C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -303,6 +303,18 @@ int smi_air_deep_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, s
     if (rc == SMI_OK && proof_len) *proof_len = deep_proof_len(cfg, D);
     return rc;
 }
+// ... with an argument list (xargs_core.h)
+int smi_air_plan_deep_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments) {
+    g_air_err.clear();
+    return deep_xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, degree, segments, &g_air_err);
+}
+int smi_air_deep_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t D = 0;
+    const int rc = deep_xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, nullptr, &D, &g_air_err);
+    if (rc == SMI_OK && proof_len) *proof_len = deep_args_proof_len(cfg, ((const smi_air_xargs *)xargs)->count, D);
+    return rc;
+}
 // what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }
 int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights, uint32_t *d_out,

@@ -25,6 +25,7 @@
 #include "internal.h"
 #include "mgpu_core.h"
 #include "row4_dev.h"
+#include "xargs_core.h"
 
 // four consecutive words from `at` (a multiple of 4): one 16-byte access where the layout allows and all four lie below len
 template <bool VEC>
@@ -387,6 +388,271 @@ int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (timed)
         for (int i = 0; i < 7; i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    return smi_proof_out(ctx, bytes, proof, proof_len);
+}
+
+// ---- out-of-domain sampling with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
+// deep_compose_kernel with the 4 A extended coordinate columns of the auxiliary F_q columns as a third group of streams:
+// 4 (W + 4 A + 4 D) + 16 bytes a point, one 16-byte load per column and lane.  The lane body (deep_core.h) keeps one column
+// group live at a time, so the register count does not grow with A; the gammas are scalar loads of the table.
+template <bool VEC>
+__global__ __launch_bounds__(DEEP_BLOCK) void deep_compose_args_kernel(Fp F, uint32_t g_m, uint32_t W, uint32_t A, uint32_t D, uint64_t N, uint32_t h_m,
+                                                                        uint32_t omega_m, const uint32_t *__restrict__ tab, const uint32_t *__restrict__ lde,
+                                                                        size_t stride, const uint32_t *__restrict__ cl, size_t c_stride,
+                                                                        const uint32_t *__restrict__ seg, size_t seg_stride, uint32_t *__restrict__ out,
+                                                                        size_t out_stride) {
+    const uint64_t groups = N / DEEP_ROWS, gid = (uint64_t)blockIdx.x * DEEP_BLOCK + threadIdx.x, gstep = (uint64_t)gridDim.x * DEEP_BLOCK;
+    uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * DEEP_ROWS, F), F);
+    const uint32_t xstep_m = mont_pow(omega_m, gstep * DEEP_ROWS, F);
+    for (uint64_t g = gid; g < groups; g += gstep) {
+        const uint64_t i0 = g * DEEP_ROWS;   // N is a multiple of 4: i0 + 3 < N
+        uint32_t o[4][DEEP_ROWS];
+        deep_compose_args_points(
+            tab, W, A, D, g_m, F, x_m, omega_m, [&](uint32_t c, uint32_t v[4]) { perm_load4<VEC>(lde + (size_t)c * stride, i0, N, v); },
+            [&](uint32_t col, uint32_t v[4]) { perm_load4<VEC>(cl + (size_t)col * c_stride, i0, N, v); },
+            [&](uint32_t col, uint32_t v[4]) { perm_load4<VEC>(seg + (size_t)col * seg_stride, i0, N, v); }, o);
+#pragma unroll
+        for (int e = 0; e < 4; e++) perm_store4<VEC>(out + e * out_stride, i0, N, o[e]);
+        x_m = mont_mul(x_m, xstep_m, F);
+    }
+}
+
+namespace {
+// d_tab: the table of deep_compose_args_build on the device
+int deep_compose_args_enqueue(smi_ctx *ctx, uint32_t W, uint32_t A, uint32_t D, uint32_t log_N, uint32_t h, const uint32_t *d_tab, const uint32_t *d_lde,
+                              size_t stride, const uint32_t *d_cl, size_t c_stride, const uint32_t *d_seg, size_t seg_stride, uint32_t *d_out,
+                              size_t out_stride) {
+    const Fp F = ctx->fs.F;
+    const uint64_t N = 1ull << log_N;
+    const bool vec = al16(d_lde) && al16(d_cl) && al16(d_seg) && al16(d_out) && !(stride & 3) && !(c_stride & 3) && !(seg_stride & 3) && !(out_stride & 3);
+    const uint64_t groups = N / DEEP_ROWS, want = (groups + DEEP_BLOCK - 1) / DEEP_BLOCK, cap = (uint64_t)ctx->num_cus * 8;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t g_m = air_to_m(ctx->fs.g, F.p), h_m = air_to_m(h, F.p), omega_m = air_to_m(h_root(ctx, log_N), F.p);
+    ProfScope ps(ctx, "deep_compose_args_kernel", (4.0 * (W + 4.0 * A + 4.0 * D) + 16.0) * (double)N);
+    if (vec)
+        deep_compose_args_kernel<true><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, A, D, N, h_m, omega_m, d_tab, d_lde, stride, d_cl, c_stride, d_seg,
+                                                                             seg_stride, d_out, out_stride);
+    else
+        deep_compose_args_kernel<false><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, A, D, N, h_m, omega_m, d_tab, d_lde, stride, d_cl, c_stride, d_seg,
+                                                                              seg_stride, d_out, out_stride);
+    HIP_TRY(ctx, hipGetLastError());
+    return SMI_OK;
+}
+}  // namespace
+
+int smi_dev_deep_compose_args(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_args, uint32_t n_segments, const uint32_t *d_lde, size_t stride,
+                              const uint32_t *d_c_lde, size_t c_stride, const uint32_t *d_seg, size_t seg_stride, const uint64_t z[4], const uint64_t *ood,
+                              const uint64_t *challenges, uint32_t *d_out, size_t out_stride) {
+    if (!ctx || !cfg || !d_lde || !d_c_lde || !d_seg || !z || !ood || !challenges || !d_out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(deep_field_check(ctx));
+    const uint32_t W = cfg->n_cols, A = n_args, D = n_segments, log_N = cfg->log_n + cfg->log_blowup;
+    if (!W || W > 64) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: 1..64 columns");
+    if (!A || A > SMI_ARGS_MAX) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: 1 .. 8 auxiliary columns");
+    if (!D || D > DEEP_MAX_SEGMENTS) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: 1 .. 16 segments");
+    if (cfg->log_n < 1 || cfg->log_blowup < 2 || log_N > 27)
+        return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: log_n >= 1, log_blowup >= 2, log_n + log_blowup <= 27");
+    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    const uint64_t N = 1ull << log_N;
+    if (stride < N || c_stride < N || seg_stride < N || out_stride < N)
+        return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: stride < N, c_stride < N, seg_stride < N or out_stride < N");
+    if (!cfg->lde_offset || cfg->lde_offset >= ctx->fs.F.p) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_args: lde_offset must be in 1 .. p-1");
+    FqH zq;
+    SMI_TRY(deep_point(ctx, z, &zq));
+    if (fqh_in_base(zq)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
+    for (size_t i = 0; i < deep_args_record(W, A, D); i++)
+        if (ood[i] >= ctx->fs.F.p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "deep_compose_args: an out-of-domain coordinate is >= p");
+    std::vector<uint32_t> tab;
+    deep_compose_args_build(ctx->fs.F, ctx->fs.g, W, A, D, h_root(ctx, cfg->log_n), zq, ood, challenges, &tab);
+    void *d_tab = nullptr;
+    SMI_TRY(ctx_tmp(ctx, 3, tab.size() * 4, &d_tab));
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    return deep_compose_args_enqueue(ctx, W, A, D, log_N, (uint32_t)cfg->lde_offset, (const uint32_t *)d_tab, d_lde, stride, d_c_lde, c_stride, d_seg,
+                                     seg_stride, d_out, out_stride);
+}
+
+int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_trace_cols,
+                                 uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                                 uint32_t grind_bits, uint32_t *closes) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (closes) *closes = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(deep_field_check(ctx));
+    uint32_t D = 0;
+    {
+        std::string why;
+        const int rc = deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why);
+        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    }
+    SMI_TRY(xargs_entry_checks(ctx, air, xargs, cfg->n_cols, cfg->log_n));
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs->count, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
+    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the second tree
+    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
+    AirHost H;
+    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
+    SMI_TRY(arena_reset(ctx));
+    struct Events {   // destroyed on every return path
+        hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs;
+    const bool timed = stage_ms != nullptr;
+    if (timed)
+        for (int i = 0; i < 9; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+
+    const size_t n_ood = deep_args_record(W, A, D);
+    const size_t tree_bytes = 2 * N * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
+    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
+    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
+    uint32_t *d_c = (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4);
+    uint32_t *d_cl = (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4);
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // H, then Q
+    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // the coefficients of H's coordinates
+    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, 4 * (size_t)D * N * 4);
+    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)(W + CW) * n * 4);   // the trace polynomials, then the columns' coordinates
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
+    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
+    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree3 = (uint8_t *)arena_alloc(ctx, tree_bytes);
+    uint8_t *d_atmp = (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_size(A, n));
+    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
+    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
+    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | H_{j,e} at z, e-major
+    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_args_tab_words(W, A, D) * 4);
+    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
+    if (H.dev.Q) {
+        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
+        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
+    }
+    if (!d_lde || !d_c || !d_cl || !d_cw || !d_hc || !d_seg || !d_coef || !d_weights || !d_blob || !tree1 || !tree2 || !tree3 || !d_atmp || !d_tab2 ||
+        !d_tab1 || !d_part || !d_res || !d_ctab || (H.dev.Q && (!d_ptab || !d_pvals)))
+        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_xargs: device memory");
+    mark(0);
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
+    mark(1);
+    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
+    mark(2);
+    // first round trip: root_1 -> alpha, gamma
+    uint8_t roots[96];
+    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root; d_pvals: the raw values the column build reads
+    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for step 7
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    Transcript tr;
+    std::vector<uint64_t> ch, weights, gammas;   // 8 challenges; 4 NW weights; the record's gammas
+    transcript_perm_challenges(tr, roots, &ch);
+    XArgsDev XD;
+    xargs_build(ctx->fs.F, g, xargs, W, air, H.per, ch.data(), &XD);
+    XD.pvals = d_pvals;
+    SMI_TRY(xargs_columns_launch(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
+    SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
+    SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
+    mark(3);
+    // second round trip: root_2 (and the columns' verdicts) -> the weights
+    ArgsFlags fl;
+    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    SMI_TRY(dev_ntt(ctx, d_c, d_coef + (size_t)W * n, log_n, n, CW, n, n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SMI_TRY(xargs_columns_settle(ctx, XD, fl, closes));
+    transcript_args_weights(tr, roots + 32, W, K, A, &weights);
+    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
+    SMI_TRY(xargs_compose_launch(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
+    mark(4);
+    // the segments: coefficients of every coordinate of H on the coset, D slices of n, each extended back to the N points
+    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
+    for (uint32_t j = 0; j < D; j++)
+        SMI_TRY(dev_ntt(ctx, d_hc + (size_t)j * n, d_seg + 4 * (size_t)j * N, log_N, n, 4, N, N, 0, cfg->lde_offset, 1));
+    SMI_TRY(launch_merkle_rows(ctx, d_seg, 4 * D, N, N, tree3));
+    mark(5);
+    // third round trip: root_3 -> z
+    HIP_TRY(ctx, hipMemcpyAsync(roots + 64, tree3 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t zr[4];
+    deep_args_transcript_z(tr, roots + 64, NW, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
+    if (roots_out) memcpy(roots_out, roots, 96);
+    // fourth round trip: u, v = f(z), f(z w); a, b = c(z), c(z w); s = H_j(z)
+    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
+    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
+    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
+    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W + CW, n, n, 2, d_tab2, d_part, d_res));
+    uint32_t *d_sres = d_res + 8 * (size_t)(W + CW);
+    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D segments: D columns of n coefficients, n apart
+        SMI_TRY(deep_eval_enqueue(ctx, d_hc + (size_t)e * N, D, n, n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * D));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> ood(n_ood);
+    const FqH X{{0, 1 % p, 0, 0}};
+    auto assemble = [&](const uint32_t *at, size_t pitch, uint64_t *dst) {   // sum_e X^e v_e, v_e four words at at + e pitch
+        FqH s = fqh(0), xe = fqh(1 % p);
+        for (uint32_t e = 0; e < 4; e++) {
+            const uint32_t *v = at + e * pitch;
+            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
+            xe = fqh_mul(xe, X, p, g);
+        }
+        for (uint32_t e = 0; e < 4; e++) dst[e] = s.c[e];
+    };
+    for (uint32_t c = 0; c < W; c++)
+        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
+    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
+        assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
+        assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
+    }
+    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
+    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
+    deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
+    const FsSeed seed = tr.seed();
+    deep_compose_args_build(ctx->fs.F, g, W, A, D, w_n, z, ood.data(), gammas.data(), &ctab);
+    HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_compose_args_enqueue(ctx, W, A, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_cl, N, d_seg, N, d_cw, N));
+    mark(6);
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    FriExtResult xres;
+    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
+    std::vector<uint8_t> bytes(9 + 8 * n_ood);
+    bytes[0] = 2;
+    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
+    for (size_t v = 0; v < n_ood; v++)
+        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
+    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
+    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    mark(7);
+    if (cfg->num_colinearity_tests) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 2;
+        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R),
+                     ob3 = (size_t)mg_row_open_bytes(4 * D, t, log_N, R);
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2 + ob3);
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_xargs: row openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
+        SMI_TRY(launch_air_row_open(ctx, d_cl, N, CW, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
+        SMI_TRY(launch_air_row_open(ctx, d_seg, N, 4 * D, tree3, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1 + ob2));
+        const size_t at = bytes.size();
+        bytes.resize(at + ob1 + ob2 + ob3);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2 + ob3, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    mark(8);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed)
+        for (int i = 0; i < 8; i++) {
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
             stage_ms[i] = ms;

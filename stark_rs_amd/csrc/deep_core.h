@@ -165,6 +165,120 @@ SMI_HD void deep_compose_points(const uint32_t *tab, uint32_t W, uint32_t D, uin
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ... with auxiliary columns
+// include/stark_mi.h, "Out-of-domain sampling with an argument list": A committed F_q columns c_a, stored as 4 A extended
+// coordinate columns, are opened at z and z w like the trace.  Table of one launch, u32 words:
+//   gamma_c    (Montgomery)            at 4 c + e
+//   gamma'_c   (Montgomery)            at 4 W + 4 c + e
+//   delta_a    (prepared: b_m | gb_m)  at 8 W + 16 a + e,      8 W + 16 a + 4 + e
+//   delta'_a   (prepared)              at 8 W + 16 a + 8 + e,  8 W + 16 a + 12 + e
+//   gamma''_j  (prepared)              at 8 W + 16 A + 8 j + e, 8 W + 16 A + 8 j + 4 + e
+//   -C1 = -(sum_c gamma_c u_c + sum_a delta_a a_a + sum_j gamma''_j s_j), -C2 = -(sum_c gamma'_c v_c + sum_a delta'_a b_a)
+//   (plain), z, z w (Montgomery): the last 16
+inline size_t deep_args_tab_words(uint32_t W, uint32_t A, uint32_t D) { return (size_t)8 * W + 16 * (size_t)A + 8 * D + 16; }
+
+// the 2 DEEP_ROWS inverted denominators 1 / (x - z), 1 / (x - z w) of a lane under one F_q inversion (cst: the table's last
+// 16 words); none is zero, since z and z w lie outside F_p
+SMI_HD void deep_lane_inverses(const uint32_t *cst, uint32_t g_m, const Fp &F, uint32_t x0_m, uint32_t omega_m, Fq dinv[2 * DEEP_ROWS]) {
+    const uint32_t p = F.p;
+    Fq den[2 * DEEP_ROWS], pre[2 * DEEP_ROWS];
+    uint32_t x = x0_m;
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++) {
+        den[q] = Fq{{fp_sub(x, cst[8], p), fp_neg(cst[9], p), fp_neg(cst[10], p), fp_neg(cst[11], p)}};
+        den[DEEP_ROWS + q] = Fq{{fp_sub(x, cst[12], p), fp_neg(cst[13], p), fp_neg(cst[14], p), fp_neg(cst[15], p)}};
+        x = mont_mul(x, omega_m, F);
+    }
+    pre[0] = den[0];
+#pragma unroll
+    for (int i = 1; i < 2 * DEEP_ROWS; i++) pre[i] = fq_mul(pre[i - 1], den[i], g_m, F);
+    Fq inv = fq_inv(pre[2 * DEEP_ROWS - 1], g_m, F);
+#pragma unroll
+    for (int i = 2 * DEEP_ROWS - 1; i >= 0; i--) {
+        dinv[i] = i ? fq_mul(inv, pre[i - 1], g_m, F) : inv;
+        if (i) inv = fq_mul(inv, den[i], g_m, F);
+    }
+}
+
+// One lane of deep_compose_args_kernel: deep_compose_points with load_c(col, v): auxiliary coordinate column col (4 a + e:
+// coordinate e of c_a) at the four points.  One column stream is live at a time -- a trace column's four words, or the
+// sixteen of one F_q column -- next to the 2 x 4 x 4 accumulator words and the 8 inverses; the gammas are wave-uniform
+// table reads.
+template <class LoadT, class LoadC, class LoadS>
+SMI_HD void deep_compose_args_points(const uint32_t *tab, uint32_t W, uint32_t A, uint32_t D, uint32_t g_m, const Fp &F, uint32_t x0_m, uint32_t omega_m,
+                                     LoadT load_t, LoadC load_c, LoadS load_s, uint32_t out[4][DEEP_ROWS]) {
+    const uint32_t p = F.p;
+    const uint32_t *aux = tab + 8 * (size_t)W, *sg = aux + 16 * (size_t)A, *cst = sg + 8 * (size_t)D;
+    Fq dinv[2 * DEEP_ROWS];
+    deep_lane_inverses(cst, g_m, F, x0_m, omega_m, dinv);
+    uint32_t a1[DEEP_ROWS][4], a2[DEEP_ROWS][4];
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) a1[q][e] = cst[e], a2[q][e] = cst[4 + e];
+    for (uint32_t c = 0; c < W; c++) {
+        uint32_t v[DEEP_ROWS];
+        load_t(c, v);
+        const uint32_t *g1 = tab + 4 * (size_t)c, *g2 = tab + 4 * (size_t)(W + c);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t b1 = g1[e], b2 = g2[e];
+#pragma unroll
+            for (int q = 0; q < DEEP_ROWS; q++) {
+                a1[q][e] = fp_add(a1[q][e], mont_mul(v[q], b1, F), p);
+                a2[q][e] = fp_add(a2[q][e], mont_mul(v[q], b2, F), p);
+            }
+        }
+    }
+    // Range: ext_mul_prepared (fri_core.h) sums four 32 x 32 products of a plain coordinate with a Montgomery word, and wants
+    // every plain coordinate below p so that the sum stays below p 2^32.  The first factor here is always a loaded cell as it
+    // stands -- a canonical residue of the extended column, never a partial sum --, each product comes back reduced, and the
+    // accumulators a1, a2 only ever see fp_add of two residues: they stay below p for the fq_mul at the end, whatever A and D.
+    for (uint32_t a = 0; a < A; a++) {
+        uint32_t h[4][DEEP_ROWS];
+#pragma unroll
+        for (int e = 0; e < 4; e++) load_c(4 * a + e, h[e]);
+        ExtMul M1, M2;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            M1.b_m[e] = aux[16 * (size_t)a + e], M1.gb_m[e] = aux[16 * (size_t)a + 4 + e];
+            M2.b_m[e] = aux[16 * (size_t)a + 8 + e], M2.gb_m[e] = aux[16 * (size_t)a + 12 + e];
+        }
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) {
+            const uint32_t hv[4] = {h[0][q], h[1][q], h[2][q], h[3][q]};
+            uint32_t o1[4], o2[4];
+            ext_mul_prepared(hv, M1, F, o1);
+            ext_mul_prepared(hv, M2, F, o2);
+#pragma unroll
+            for (int e = 0; e < 4; e++) a1[q][e] = fp_add(a1[q][e], o1[e], p), a2[q][e] = fp_add(a2[q][e], o2[e], p);
+        }
+    }
+    for (uint32_t j = 0; j < D; j++) {
+        uint32_t h[4][DEEP_ROWS];
+#pragma unroll
+        for (int e = 0; e < 4; e++) load_s(4 * j + e, h[e]);
+        ExtMul M;
+#pragma unroll
+        for (int e = 0; e < 4; e++) M.b_m[e] = sg[8 * (size_t)j + e], M.gb_m[e] = sg[8 * (size_t)j + 4 + e];
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) {
+            const uint32_t hv[4] = {h[0][q], h[1][q], h[2][q], h[3][q]};
+            uint32_t o[4];
+            ext_mul_prepared(hv, M, F, o);
+#pragma unroll
+            for (int e = 0; e < 4; e++) a1[q][e] = fp_add(a1[q][e], o[e], p);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++) {
+        const Fq n1{{a1[q][0], a1[q][1], a1[q][2], a1[q][3]}}, n2{{a2[q][0], a2[q][1], a2[q][2], a2[q][3]}};
+        const Fq r1 = fq_mul(n1, dinv[q], g_m, F), r2 = fq_mul(n2, dinv[DEEP_ROWS + q], g_m, F);
+#pragma unroll
+        for (int e = 0; e < 4; e++) out[e][q] = fp_add(r1.c[e], r2.c[e], p);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side: F_q, plain
 struct FqH {
     uint32_t c[4];
@@ -412,6 +526,106 @@ inline FqH deep_q_at(uint32_t p, uint32_t g, uint32_t W, uint32_t D, uint32_t w_
     }
     for (uint32_t j = 0; j < D; j++)
         n1 = fqh_add(n1, fqh_mul(fqh_of(gammas + 4 * (size_t)(2 * W + j), p), fqh_sub(fqh_of(srow + 4 * (size_t)j, p), fqh_of(ood + 4 * (size_t)(2 * W + j), p), p), p, g), p);
+    const FqH d1 = fqh_sub(fqh(x), z, p), d2 = fqh_sub(fqh(x), fqh_scale(z, w_n, p), p);
+    return fqh_add(fqh_mul(n1, fqh_inv(d1, p, g), p, g), fqh_mul(n2, fqh_inv(d2, p, g), p, g), p);
+}
+
+// ------------------------------------------------------------------------------------------------ ... with an argument list
+// include/stark_mi.h, "Out-of-domain sampling with an argument list".  The record holds 4 (2 W + 2 A + D) values in the
+// order u, v, a, b, s; the challenges follow it: gamma, gamma', delta, delta', gamma''.  The plan, the auxiliary quotients at
+// z and the consistency check need the list and live in xargs_core.h.
+static const char *const DEEP_ARGS_SENTENCES[6] = {"deep argument openings: wrong length",
+                                                   "deep argument openings: malformed row",
+                                                   "deep argument openings: malformed path",
+                                                   "deep argument openings: authentication path does not verify",
+                                                   "deep argument openings: an opened value is not canonical",
+                                                   "deep argument openings: the DEEP quotient of the opened rows is not the codeword value"};
+#define DEEP_ARGS_INCONSISTENT \
+    "deep arguments: out-of-domain consistency check fails: the constraints and the auxiliary quotients at z do not give the segments' value"
+
+inline size_t deep_args_record(uint32_t W, uint32_t A, uint32_t D) { return 4 * (2 * (size_t)W + 2 * (size_t)A + D); }
+
+// the table of deep_compose_args_kernel.  ood: the record's canonical values; ch: as many unreduced challenges; w_n = omega_n
+inline void deep_compose_args_build(const Fp &F, uint32_t g, uint32_t W, uint32_t A, uint32_t D, uint32_t w_n, const FqH &z, const uint64_t *ood,
+                                    const uint64_t *ch, std::vector<uint32_t> *tab) {
+    const uint32_t p = F.p;
+    tab->assign(deep_args_tab_words(W, A, D), 0);
+    uint32_t *t = tab->data();
+    FqH c1 = fqh(0), c2 = fqh(0);
+    auto prepared = [&](const FqH &v, uint32_t *at) {
+        for (int e = 0; e < 4; e++) at[e] = air_to_m(v.c[e], p), at[4 + e] = air_to_m(host_mulmod(v.c[e], g, p), p);
+    };
+    for (uint32_t c = 0; c < W; c++) {
+        const FqH g1 = fqh_of(ch + 4 * (size_t)c, p), g2 = fqh_of(ch + 4 * (size_t)(W + c), p);
+        for (int e = 0; e < 4; e++) t[4 * c + e] = air_to_m(g1.c[e], p), t[4 * (W + c) + e] = air_to_m(g2.c[e], p);
+        c1 = fqh_add(c1, fqh_mul(g1, fqh_of(ood + 4 * (size_t)c, p), p, g), p);
+        c2 = fqh_add(c2, fqh_mul(g2, fqh_of(ood + 4 * (size_t)(W + c), p), p, g), p);
+    }
+    for (uint32_t a = 0; a < A; a++) {
+        const size_t ia = 2 * (size_t)W + a, ib = 2 * (size_t)W + A + a;
+        const FqH d1 = fqh_of(ch + 4 * ia, p), d2 = fqh_of(ch + 4 * ib, p);
+        prepared(d1, t + 8 * (size_t)W + 16 * (size_t)a);
+        prepared(d2, t + 8 * (size_t)W + 16 * (size_t)a + 8);
+        c1 = fqh_add(c1, fqh_mul(d1, fqh_of(ood + 4 * ia, p), p, g), p);
+        c2 = fqh_add(c2, fqh_mul(d2, fqh_of(ood + 4 * ib, p), p, g), p);
+    }
+    for (uint32_t j = 0; j < D; j++) {
+        const size_t is = 2 * (size_t)W + 2 * (size_t)A + j;
+        const FqH g3 = fqh_of(ch + 4 * is, p);
+        prepared(g3, t + 8 * (size_t)W + 16 * (size_t)A + 8 * (size_t)j);
+        c1 = fqh_add(c1, fqh_mul(g3, fqh_of(ood + 4 * is, p), p, g), p);
+    }
+    uint32_t *cst = t + 8 * (size_t)W + 16 * (size_t)A + 8 * (size_t)D;
+    const FqH zw = fqh_scale(z, w_n, p);
+    for (int e = 0; e < 4; e++) {
+        cst[e] = fp_neg(c1.c[e], p);
+        cst[4 + e] = fp_neg(c2.c[e], p);
+        cst[8 + e] = air_to_m(z.c[e], p);
+        cst[12 + e] = air_to_m(zw.c[e], p);
+    }
+}
+
+// 9 + 32 (2W + 2A + D) + len_FRI(N, B, t) + the three opening sections of two rows per test
+inline size_t deep_args_proof_len(const smi_stark_cfg *cfg, uint32_t A, uint32_t D) {
+    const uint64_t W = cfg->n_cols, t = cfg->num_colinearity_tests, log_N = cfg->log_n + cfg->log_blowup;
+    const smi_fri_cfg fc = deep_fri_cfg(cfg, 1);
+    const uint64_t path = 2 * t * (9 + 32 * log_N);
+    return (size_t)(9 + 32 * (2 * W + 2 * (uint64_t)A + D) + fri_layout_ext(fc, true).proof_len + 2 * t * (9 + 8 * W) + path + 2 * t * (9 + 32ull * A) + path +
+                    2 * t * (9 + 32ull * D) + path);
+}
+
+// The transcript's last two steps (the first two are transcript_perm_challenges and transcript_args_weights): root_3 and z
+// under the counters 8 + 4 NW + e, then the record and the gammas under the counters after those; NW = W + K + 2 A
+inline void deep_args_transcript_z(Transcript &T, const uint8_t root3[32], uint64_t NW, uint64_t z[4]) {
+    std::vector<uint64_t> ch;
+    transcript_indexed(T, root3, 8 + 4 * NW, 4, &ch);
+    for (int e = 0; e < 4; e++) z[e] = ch[e];
+}
+inline void deep_args_transcript_gammas(Transcript &T, const uint64_t *ood, uint64_t NW, size_t n_ood, std::vector<uint64_t> *gammas) {
+    for (size_t i = 0; i < n_ood; i++) T.absorb_index(ood[i]);   // the payload: every value as 8 little-endian bytes
+    for (size_t m = 0; m < n_ood; m++) {
+        T.absorb_index(8 + 4 * NW + 4 + m);
+        gammas->push_back(T.challenge());
+    }
+}
+
+// Q(x) from the three opened rows at x: trow = the W trace values, crow = the 4 A coordinates of the auxiliary columns, srow =
+// the 4 D segment values (canonical)
+inline FqH deep_args_q_at(uint32_t p, uint32_t g, uint32_t W, uint32_t A, uint32_t D, uint32_t w_n, uint32_t x, const FqH &z, const uint64_t *ood,
+                          const uint64_t *gammas, const uint64_t *trow, const uint64_t *crow, const uint64_t *srow) {
+    FqH n1 = fqh(0), n2 = fqh(0);
+    auto term = [&](const FqH &f, size_t i) { return fqh_mul(fqh_of(gammas + 4 * i, p), fqh_sub(f, fqh_of(ood + 4 * i, p), p), p, g); };
+    for (uint32_t c = 0; c < W; c++) {
+        const FqH f = fqh((uint32_t)trow[c]);
+        n1 = fqh_add(n1, term(f, c), p);
+        n2 = fqh_add(n2, term(f, (size_t)W + c), p);
+    }
+    for (uint32_t a = 0; a < A; a++) {
+        const FqH f = fqh_of(crow + 4 * (size_t)a, p);
+        n1 = fqh_add(n1, term(f, 2 * (size_t)W + a), p);
+        n2 = fqh_add(n2, term(f, 2 * (size_t)W + A + a), p);
+    }
+    for (uint32_t j = 0; j < D; j++) n1 = fqh_add(n1, term(fqh_of(srow + 4 * (size_t)j, p), 2 * (size_t)W + 2 * (size_t)A + j), p);
     const FqH d1 = fqh_sub(fqh(x), z, p), d2 = fqh_sub(fqh(x), fqh_scale(z, w_n, p), p);
     return fqh_add(fqh_mul(n1, fqh_inv(d1, p, g), p, g), fqh_mul(n2, fqh_inv(d2, p, g), p, g), p);
 }

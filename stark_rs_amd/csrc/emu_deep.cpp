@@ -166,3 +166,87 @@ extern "C" int emu_deep_q_at(uint64_t p, uint64_t g, uint32_t W, uint32_t D, uin
     for (int e = 0; e < 4; e++) out[e] = q.c[e];
     return SMI_OK;
 }
+
+// ---- out-of-domain sampling with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
+namespace {
+int args_shape(uint64_t p, const FieldSetup &fs, const smi_stark_cfg *cfg, uint32_t A, uint32_t D) {
+    const uint32_t W = cfg->n_cols, log_N = cfg->log_n + cfg->log_blowup;
+    if (!W || W > 64 || !A || A > SMI_ARGS_MAX || !D || D > DEEP_MAX_SEGMENTS || cfg->log_n < 1 || cfg->log_blowup < 2 || log_N > 27 || log_N > fs.K)
+        return SMI_ERR_BAD_ARG;
+    if (!cfg->lde_offset || cfg->lde_offset >= p) return SMI_ERR_BAD_ARG;
+    return SMI_OK;
+}
+}  // namespace
+
+// the table of deep_compose_args_kernel as the host builds it: tab gets deep_args_tab_words(W, A, D) words
+extern "C" int emu_deep_compose_args_table(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, uint32_t n_args, uint32_t n_segments, const uint64_t *z,
+                                           const uint64_t *ood, const uint64_t *challenges, uint32_t *tab_out, uint64_t tab_words) {
+    FieldSetup fs;
+    int rc = SMI_OK;
+    if (!setup(p, g, &fs, &rc)) return rc;
+    if ((rc = args_shape(p, fs, cfg, n_args, n_segments)) != SMI_OK) return rc;
+    const uint32_t W = cfg->n_cols, A = n_args, D = n_segments;
+    if (tab_words != deep_args_tab_words(W, A, D)) return SMI_ERR_BAD_ARG;
+    FqH zq;
+    if (!point(z, p, &zq)) return SMI_ERR_NON_CANONICAL;
+    for (size_t i = 0; i < deep_args_record(W, A, D); i++)
+        if (ood[i] >= p) return SMI_ERR_NON_CANONICAL;
+    const uint32_t w_n = host_powmod(fs.wmax[0], 1ull << (fs.K - cfg->log_n), fs.F.p);
+    std::vector<uint32_t> tab;
+    deep_compose_args_build(fs.F, (uint32_t)g, W, A, D, w_n, zq, ood, challenges, &tab);
+    memcpy(tab_out, tab.data(), tab.size() * 4);
+    return SMI_OK;
+}
+
+// deep_compose_args_kernel's grid-stride loop over deep_compose_args_points.  grid: workgroups of the streaming launch (0: as
+// the library sizes it for 256 compute units); with grid = 1 every lane loops once N > DEEP_TILE
+extern "C" int emu_deep_compose_args(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, uint32_t n_args, uint32_t n_segments, const uint32_t *lde,
+                                     uint64_t stride, const uint32_t *cl, uint64_t c_stride, const uint32_t *seg, uint64_t seg_stride, const uint64_t *z,
+                                     const uint64_t *ood, const uint64_t *challenges, uint32_t *out, uint64_t out_stride, uint32_t grid) {
+    FieldSetup fs;
+    int rc = SMI_OK;
+    if (!setup(p, g, &fs, &rc)) return rc;
+    if ((rc = args_shape(p, fs, cfg, n_args, n_segments)) != SMI_OK) return rc;
+    const Fp F = fs.F;
+    const uint32_t W = cfg->n_cols, A = n_args, D = n_segments, log_N = cfg->log_n + cfg->log_blowup;
+    const uint64_t N = 1ull << log_N;
+    if (stride < N || c_stride < N || seg_stride < N || out_stride < N) return SMI_ERR_BAD_ARG;
+    FqH zq;
+    if (!point(z, p, &zq)) return SMI_ERR_NON_CANONICAL;
+    if (fqh_in_base(zq)) return SMI_ERR_BAD_ARG;
+    for (size_t i = 0; i < deep_args_record(W, A, D); i++)
+        if (ood[i] >= p) return SMI_ERR_NON_CANONICAL;
+    const uint32_t w_n = host_powmod(fs.wmax[0], 1ull << (fs.K - cfg->log_n), F.p), omega = host_powmod(fs.wmax[0], 1ull << (fs.K - log_N), F.p);
+    std::vector<uint32_t> tab;
+    deep_compose_args_build(F, (uint32_t)g, W, A, D, w_n, zq, ood, challenges, &tab);
+    const uint32_t g_m = air_to_m((uint32_t)g, F.p), h_m = air_to_m((uint32_t)cfg->lde_offset, F.p), omega_m = air_to_m(omega, F.p);
+    const uint64_t groups = N / DEEP_ROWS, want = (groups + DEEP_BLOCK - 1) / DEEP_BLOCK;
+    if (!grid) grid = (uint32_t)(want < 2048 ? want : 2048);
+    const uint64_t gstep = (uint64_t)grid * DEEP_BLOCK;
+    const uint32_t xstep_m = mont_pow(omega_m, gstep * DEEP_ROWS, F);
+    for (uint64_t gid = 0; gid < gstep && gid < groups; gid++) {
+        uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * DEEP_ROWS, F), F);
+        for (uint64_t gq = gid; gq < groups; gq += gstep) {
+            const uint64_t i0 = gq * DEEP_ROWS;
+            uint32_t o[4][DEEP_ROWS];
+            deep_compose_args_points(
+                tab.data(), W, A, D, g_m, F, x_m, omega_m, [&](uint32_t c, uint32_t v[4]) { load4(lde + (uint64_t)c * stride, i0, N, v); },
+                [&](uint32_t col, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, i0, N, v); },
+                [&](uint32_t col, uint32_t v[4]) { load4(seg + (uint64_t)col * seg_stride, i0, N, v); }, o);
+            for (int e = 0; e < 4; e++) store4(out + e * out_stride, i0, N, o[e]);
+            x_m = mont_mul(x_m, xstep_m, F);
+        }
+    }
+    return SMI_OK;
+}
+
+// Q at the point x from the three opened rows, as the verifier recomputes it
+extern "C" int emu_deep_args_q_at(uint64_t p, uint64_t g, uint32_t W, uint32_t A, uint32_t D, uint64_t w_n, uint64_t x, const uint64_t *z, const uint64_t *ood,
+                                  const uint64_t *gammas, const uint64_t *trow, const uint64_t *crow, const uint64_t *srow, uint64_t *out) {
+    if (!ext_field_ok(p, g, nullptr) || p >= (1ull << 30)) return SMI_ERR_BAD_ARG;
+    FqH zq;
+    if (!point(z, p, &zq)) return SMI_ERR_NON_CANONICAL;
+    const FqH q = deep_args_q_at((uint32_t)p, (uint32_t)g, W, A, D, (uint32_t)w_n, (uint32_t)x, zq, ood, gammas, trow, crow, srow);
+    for (int e = 0; e < 4; e++) out[e] = q.c[e];
+    return SMI_OK;
+}

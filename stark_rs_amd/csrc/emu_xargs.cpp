@@ -245,3 +245,28 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
     }
     return SMI_OK;
 }
+
+// both sides of the verifier's extended out-of-domain consistency check (include/stark_mi.h, "Out-of-domain sampling with an
+// argument list"; four canonical coordinates each): challenges = alpha, gamma; weights = the 4 (W + K + 2 A) challenges
+extern "C" int emu_deep_xargs_ood_sides(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs,
+                                        const uint64_t *challenges, const uint64_t *weights, const uint64_t *z, const uint64_t *ood, uint64_t *lhs,
+                                        uint64_t *rhs) {
+    FieldSetup fs;
+    int rc = checks(p, g, air, xargs, cfg->n_cols, cfg->log_n, &fs);
+    if (rc != SMI_OK) return rc;
+    uint32_t D = 0;
+    rc = deep_xargs_plan(p, cfg, air, xargs, nullptr, &D, nullptr);
+    if (rc != SMI_OK) return rc;
+    FqH zq, l, r;
+    for (int e = 0; e < 4; e++) {
+        if (z[e] >= p) return SMI_ERR_NON_CANONICAL;
+        zq.c[e] = (uint32_t)z[e];
+    }
+    if (fqh_in_base(zq)) return SMI_ERR_BAD_ARG;
+    for (size_t i = 0; i < deep_args_record(cfg->n_cols, xargs->count, D); i++)
+        if (ood[i] >= p) return SMI_ERR_NON_CANONICAL;
+    const uint32_t w_n = host_powmod(fs.wmax[0], 1ull << (fs.K - cfg->log_n), fs.F.p);
+    deep_xargs_ood_sides((uint32_t)p, (uint32_t)g, cfg, air, xargs, D, w_n, challenges, weights, zq, ood, &l, &r);
+    for (int e = 0; e < 4; e++) lhs[e] = l.c[e], rhs[e] = r.c[e];
+    return SMI_OK;
+}

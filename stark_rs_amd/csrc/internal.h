@@ -351,3 +351,14 @@ struct ArgsFlags {   // the totals (plain), the smallest key 16 row + 2 a + side
 int args_scan_propagate_enqueue(smi_ctx *ctx, const ArgsDev &AD, uint32_t A, uint64_t n, bool vec, uint32_t *d_c, size_t c_stride, uint32_t *d_agg,
                                 ArgsFlags *d_fl);
 int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint32_t *d_vals, uint32_t *d_tab);
+// xargs.hip, for deep.hip (the prover of "Out-of-domain sampling with an argument list"): the column build's three launches
+// over caller-owned temporary memory (xargs_columns_tmp_size bytes, 16-byte aligned; XD.pvals on the device), where the
+// build leaves its flags in that memory, the verdicts of a finished build, and the launch of the 2 A auxiliary quotients
+struct XArgsDev;
+size_t xargs_columns_tmp_size(uint32_t A, uint64_t n);
+int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp);
+const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n);
+int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes);
+int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+                         size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride);
+int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n);

@@ -1305,3 +1305,88 @@ int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
     return settle(air_verify_deep_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept, grind_bits));
 }
+
+// Verifier of smi_dev_air_prove_deep_xargs (include/stark_mi.h, "Out-of-domain sampling with an argument list"):
+// air_verify_deep_impl's checks in its order with the record of 4 (2 W + 2 A + D) values, the transcript of that section
+// (alpha and gamma, the weights of the list, z, the gammas), the consistency check with the 2 A auxiliary quotients at z
+// (xargs_core.h deep_xargs_ood_sides), three opening sections, and Q from three rows (deep_args_q_at).
+const OpeningWords DEEP_ARGS_WORDS = {DEEP_ARGS_SENTENCES[0], DEEP_ARGS_SENTENCES[1], DEEP_ARGS_SENTENCES[2],
+                                      DEEP_ARGS_SENTENCES[3], DEEP_ARGS_SENTENCES[4], DEEP_ARGS_SENTENCES[5]};   // deep_core.h
+static int air_verify_deep_xargs_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint8_t *roots,
+                                      const uint8_t *proof, size_t proof_len, int *accept, uint32_t grind) {
+    std::string why;
+    uint32_t D = 0;
+    const int vrc = deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const int prc = xargs_periodic_check(ctx->fs.F.p, air, cfg->log_n, &why);
+    if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs->count, logN = cfg->log_n + cfg->log_blowup;
+    const uint64_t NW = (uint64_t)W + K + 2 * (uint64_t)A;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    const size_t n_ood = deep_args_record(W, A, D);
+    size_t end = 0;
+    std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count(fc) + 1, &end);
+    if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, DEEP_BAD_RECORD);
+    std::vector<uint64_t> ood(n_ood);
+    for (size_t i = 0; i < n_ood; i++)
+        if ((ood[i] = get_u64(objs[0].p + 8 * i)) >= p) return reject(ctx, accept, DEEP_RECORD_CANONICAL);
+    Transcript tr;
+    std::vector<uint64_t> ch, weights, gammas;
+    uint64_t zr[4];
+    transcript_perm_challenges(tr, roots, &ch);
+    transcript_args_weights(tr, roots + 32, W, K, A, &weights);
+    deep_args_transcript_z(tr, roots + 64, NW, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return reject(ctx, accept, DEEP_Z_IN_BASE_FIELD);
+    deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
+    FqH lhs, rhs;
+    deep_xargs_ood_sides(p, g, cfg, air, xargs, D, w_n, ch.data(), weights.data(), z, ood.data(), &lhs, &rhs);
+    if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_ARGS_INCONSISTENT);
+    objs.erase(objs.begin());
+    std::vector<uint64_t> top, ab;
+    size_t used = 0;
+    SMI_TRY(fri_verify_ext_objs(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &ab, &used, (int)grind));
+    *accept = 0;
+    if (ab.size() != 8 * t) return reject(ctx, accept, DEEP_NO_LAYER);
+    const OpeningWords &say = DEEP_ARGS_WORDS;
+    const size_t R = 2, m = R * t, prec = 9 + 32 * (size_t)logN;
+    const uint32_t widths[3] = {W, 4 * A, 4 * D};
+    size_t sec_len[3], total = 0;
+    const uint8_t *sec[3];
+    for (size_t v = 0; v < 3; v++) {
+        sec[v] = proof + end + total;
+        sec_len[v] = m * (9 + 8 * (size_t)widths[v]) + m * prec;
+        total += sec_len[v];
+    }
+    if (proof_len - end != total) return reject(ctx, accept, say.length);
+    const std::vector<uint64_t> pos = opened_positions(top, N, 0, R);
+    std::vector<uint64_t> rows[3];
+    for (size_t v = 0; v < 3; v++) SMI_TRY(parse_section(ctx, accept, say, sec[v], m, widths[v], logN, ROWS_THEN_PATHS, &rows[v]));
+    for (size_t v = 0; v < 3; v++) SMI_TRY(auth_section(ctx, accept, say, sec[v], m, widths[v], logN, pos, roots + 32 * v));
+    for (size_t v = 0; v < 3; v++)
+        for (uint64_t x : rows[v])
+            if (x >= p) return reject(ctx, accept, say.canonical);
+    for (uint64_t s = 0; s < t; s++)
+        for (size_t k = 0; k < 2; k++) {
+            const size_t r = R * s + k;
+            const uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[r], p), p);
+            const FqH q = deep_args_q_at(p, g, W, A, D, w_n, x, z, ood.data(), gammas.data(), &rows[0][r * W], &rows[1][r * 4 * A], &rows[2][r * 4 * D]);
+            for (uint32_t e = 0; e < 4; e++)
+                if (q.c[e] != ab[(2 * s + k) * 4 + e]) return reject(ctx, accept, say.composition);
+        }
+    *accept = 1;
+    return SMI_OK;
+}
+int smi_air_verify_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                              size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !xargs || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_xargs_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
+}

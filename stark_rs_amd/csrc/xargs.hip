@@ -468,3 +468,18 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
         }
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }
+
+// what deep.hip's prover shares with this file (internal.h)
+size_t xargs_columns_tmp_size(uint32_t A, uint64_t n) { return xargs_columns_tmp_bytes(A, n); }
+int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp) {
+    return xargs_columns_enqueue(ctx, XD, d_trace, log_n, d_c, c_stride, d_tmp);
+}
+const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n) { return xargs_columns_flags(d_tmp, A, n); }
+int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes) { return xargs_columns_verdict(ctx, XD, fl, closes); }
+int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+                         size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
+    return xargs_compose_enqueue(ctx, XD, H, tau, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+}
+int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n) {
+    return xargs_args(ctx, air, (const smi_air_xargs *)xargs, n_cols, log_n);
+}

@@ -9,6 +9,7 @@
 // table read stays a scalar load and every branch on it is taken by the whole wave.
 #pragma once
 #include "args_core.h"
+#include "deep_core.h"
 
 #define XOP_PER 0x100u   // operand code: trace column c is c (< 64), periodic column j is XOP_PER | j
 
@@ -441,4 +442,95 @@ inline void xargs_periodic_plan(uint32_t p, const smi_air *air, uint32_t log_n, 
     smi_stark_cfg cfg{};
     cfg.log_n = log_n;
     air_periodic_plan(p, &cfg, air, true, per);
+}
+
+// ------------------------------------------------------------------------------------------------ out-of-domain sampling
+// include/stark_mi.h, "Out-of-domain sampling with an argument list".
+// smi_air_plan_deep_xargs: xargs_plan's checks without its bound on E, d by its rule, then deep_plan's three refusals with
+// deep_plan's sentences
+inline int deep_xargs_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, uint32_t *degree, uint32_t *segments,
+                           std::string *why) {
+    auto fail = [&](int code, const std::string &s) {
+        if (why) *why = s;
+        return code;
+    };
+    uint32_t d = 0;
+    const int rc = air_validate(p, cfg, air, &d, nullptr, why, false, true);
+    if (rc != SMI_OK) return rc;
+    const int arc = xargs_validate(xargs, cfg->n_cols, air->n_periodic, why);
+    if (arc != SMI_OK) return arc;
+    if ((p & 3) != 1) return fail(SMI_ERR_BAD_ARG, "xargs: p = 3 (mod 4): the quartic extension does not exist");
+    for (uint32_t a = 0; a < xargs->count; a++) {
+        const smi_air_xarg &g = xargs->arg[a];
+        const bool sel = g.a_sel != SMI_ARG_NO_SELECTOR || g.b_sel != SMI_ARG_NO_SELECTOR;
+        const uint32_t da = (g.kind == SMI_ARG_LOOKUP || sel) ? 3 : 2;
+        if (d < da) d = da;
+    }
+    const uint64_t B = 1ull << cfg->log_blowup;
+    uint64_t D = 1;
+    while (D < (uint64_t)d - 1 && D < (1ull << 32)) D <<= 1;
+    if (D > B)
+        return fail(SMI_ERR_BAD_ARG, "deep: D > 2^log_blowup: the composition of a degree-" + std::to_string(d) + " constraint has degree >= N and does not fit the evaluation domain");
+    if (B < 4) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "deep: 2^log_blowup < 4 (Fri::new's assert on the expansion factor)");
+    if (4 * D > 64) return fail(SMI_ERR_BAD_ARG, "deep: 4 D > 64: a row of the segment tree is wider than the leaf hash takes");
+    if (degree) *degree = d;
+    if (segments) *segments = (uint32_t)D;
+    return SMI_OK;
+}
+
+// The two auxiliary quotients of argument g at a point z outside F_p, over F_q operands: what XArgAux (verify.hip) computes
+// from an opened row at a point of the coset, with u[c] = f_c(z) for a trace operand c, per[j] = pi_j(z) for a periodic
+// operand, ca = c_a(z), cb = c_a(z w).  alpha, gamma: the shared challenges; ixt = 1 / (z - tau), izt = 1 / (z^n - tau^n).
+inline void xargs_aux_at_z(uint32_t p, uint32_t g, uint32_t W, const smi_air_xarg &arg, const FqH &alpha, const FqH &gamma, const FqH *u, const FqH *per,
+                           const FqH &ca, const FqH &cb, const FqH &ixt, const FqH &izt, FqH *bq, FqH *wq) {
+    const FqH one = fqh(1 % p);
+    auto val = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? one : v < W ? u[v] : per[v - 2 * W]; };
+    FqH fl = gamma, fr = gamma, pw = one;
+    for (uint32_t j = 0; j < arg.width; j++) {
+        fl = fqh_add(fl, fqh_mul(pw, val(arg.a_var[j]), p, g), p);
+        fr = fqh_add(fr, fqh_mul(pw, val(arg.b_var[j]), p, g), p);
+        pw = fqh_mul(pw, alpha, p, g);
+    }
+    const FqH sa = val(arg.a_sel), sb = val(arg.b_sel);
+    if (arg.kind == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
+        const FqH gl = fqh_add(one, fqh_mul(sa, fqh_sub(fl, one, p), p, g), p), gr = fqh_add(one, fqh_mul(sb, fqh_sub(fr, one, p), p, g), p);
+        *bq = fqh_mul(fqh_sub(ca, one, p), ixt, p, g);
+        *wq = fqh_mul(fqh_sub(fqh_mul(cb, gr, p, g), fqh_mul(ca, gl, p, g), p), izt, p, g);
+    } else {   // (s' - s) f_L f_T - S_a f_T + M S_b f_L
+        const FqH m = fqh_mul(u[arg.mult_col], sb, p, g);
+        FqH num = fqh_mul(fqh_sub(cb, ca, p), fqh_mul(fl, fr, p, g), p, g);
+        num = fqh_add(fqh_sub(num, fqh_mul(sa, fr, p, g), p), fqh_mul(m, fl, p, g), p);
+        *bq = fqh_mul(ca, ixt, p, g);
+        *wq = fqh_mul(num, izt, p, g);
+    }
+}
+
+// Both sides of the extended consistency check: deep_ood_sides over u, v, s of the record, plus the 2 A auxiliary quotients at
+// z under the weights W + K + 2 a and W + K + 2 a + 1.  ch: alpha, gamma (8 unreduced); weights: the 4 (W + K + 2 A) unreduced
+// challenges; ood: the record's 4 (2 W + 2 A + D) canonical values.
+inline void deep_xargs_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, uint32_t D, uint32_t w_n,
+                                 const uint64_t ch[8], const uint64_t *weights, const FqH &z, const uint64_t *ood, FqH *lhs, FqH *rhs) {
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, Q = air->n_periodic, A = xargs->count, tau = (uint32_t)cfg->trace_offset;
+    const uint64_t n = 1ull << cfg->log_n;
+    std::vector<uint64_t> plain(ood, ood + 8 * (size_t)W);   // u, v, s: the record of the plain variant
+    plain.insert(plain.end(), ood + 4 * (2 * (size_t)W + 2 * (size_t)A), ood + deep_args_record(W, A, D));
+    deep_ood_sides(p, g, cfg, air, D, w_n, weights, z, plain.data(), lhs, rhs);
+    std::vector<FqH> u(W), per(Q);
+    for (uint32_t c = 0; c < W; c++) u[c] = fqh_of(ood + 4 * (size_t)c, p);
+    for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++)
+        per[j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, z, p, g);
+    uint32_t al[4], ga[4];
+    perm_challenges(p, ch, al, ga);
+    const FqH alpha{{al[0], al[1], al[2], al[3]}}, gamma{{ga[0], ga[1], ga[2], ga[3]}};
+    const FqH ixt = fqh_inv(fqh_sub(z, fqh(tau % p), p), p, g);
+    const FqH izt = fqh_inv(fqh_sub(fqh_pow(z, n, p, g), fqh(host_powmod(tau, n, p)), p), p, g);
+    FqH acc = *lhs;
+    for (uint32_t a = 0; a < A; a++) {
+        FqH bq, wq;
+        xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), fqh_of(ood + 4 * (2 * (size_t)W + a), p),
+                       fqh_of(ood + 4 * (2 * (size_t)W + A + a), p), ixt, izt, &bq, &wq);
+        const uint64_t *wa = weights + 4 * ((size_t)W + K + 2 * (size_t)a);
+        acc = fqh_add(acc, fqh_add(fqh_mul(fqh_of(wa, p), bq, p, g), fqh_mul(fqh_of(wa + 4, p), wq, p, g), p), p);
+    }
+    *lhs = acc;
 }

@@ -764,6 +764,76 @@ class Engine:
             out["stage_ms"] = dict(zip(("lde", "commit", "compose", "segments", "ood", "fri", "open"), [float(x) for x in stage]))
         return out
 
+    # ---- out-of-domain sampling with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
+    def _check_deep_args(self, a, row_leaves, ext, folding, deep):
+        if deep:
+            raise ValueError("deep_args=True and deep=True exclude each other: deep=True takes a plain AIR")
+        if self._xargs(a) is None and self._args(a) is None:
+            raise ValueError("deep_args=True takes an AIR with an argument list (mirror.Air.add_permutation / add_lookup)")
+        if folding != 2:
+            raise ValueError("deep_args=True folds by 2 only (folding=4 is not supported)")
+        if not (row_leaves and ext):
+            raise ValueError("deep_args=True runs over the row-committed extension proof: pass row_leaves=True, ext=True")
+        return xargs_of(a)
+
+    def air_plan_deep_args(self, air, n_cols, log_n, log_blowup, trace_offset=1, lde_offset=None, num_colinearity_tests=None):
+        """smi_air_plan_deep_xargs for air's argument list -> (degree d, segments D); with num_colinearity_tests also the proof
+        length of smi_air_deep_xargs_layout: (d, D, bytes).  Host only; raises with the limit that was broken."""
+        a = self._args_of(air, "air_plan_deep_args")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests or 0, trace_offset, lde_offset, True)
+        return air_plan_deep_args(self.p, a, xargs_of(a), cfg, num_colinearity_tests is not None)
+
+    def dev_deep_compose_args(self, d_lde, d_c_lde, d_seg, n_cols, n_args, n_segments, log_n, log_blowup, z, ood, challenges, d_out, stride=None,
+                              c_stride=None, seg_stride=None, out_stride=None, lde_offset=None):
+        """smi_dev_deep_compose_args: the DEEP codeword of n_cols extended columns, the 4 n_args extended coordinate columns of
+        the auxiliary columns and 4 n_segments segment columns under z, the record's 4 (2 W + 2 A + D) values and as many
+        unreduced challenges, into four coordinate columns"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, 1, lde_offset, True)
+        N, cnt = 1 << (log_n + log_blowup), 4 * (2 * n_cols + 2 * n_args + n_segments)
+        if len(z) != 4 or len(ood) != cnt or len(challenges) != cnt:
+            raise ValueError("dev_deep_compose_args: z has 4 coordinates, ood and challenges 4 (2 W + 2 A + D) values")
+        za, oa, ca = (C.c_uint64 * 4)(*[int(v) for v in z]), (C.c_uint64 * cnt)(*[int(v) for v in ood]), (C.c_uint64 * cnt)(*[int(v) for v in challenges])
+        self._ck(self.L.smi_dev_deep_compose_args(self.h, C.byref(cfg), n_args, n_segments, vp(d_lde), N if stride is None else stride, vp(d_c_lde),
+                                                  N if c_stride is None else c_stride, vp(d_seg), N if seg_stride is None else seg_stride, za, oa, ca,
+                                                  vp(d_out), N if out_stride is None else out_stride))
+
+    def _dev_air_prove_deep_args(self, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
+                                 fill_multiplicities, folding, deep):
+        xa = self._check_deep_args(a, row_leaves, ext, folding, deep)
+        A = xa.count
+        lookups = [i for i in range(A) if xa.arg[i].kind == 1]
+        if fill_multiplicities and not lookups:
+            raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
+        _d, D = air_plan_deep_args(self.p, a, xa, cfg)
+        if fill_multiplicities:
+            for i in lookups:
+                self._ck_perm(self.L.smi_dev_xargs_multiplicities(self.h, C.byref(a), C.byref(xa), i, vp(d_trace_cols), n_cols, log_n,
+                                                                  vp(vp(d_trace_cols).value + 4 * (xa.arg[i].mult_col << log_n))))
+        if check:
+            ok, _con, _row, why = self.dev_air_check(a, d_trace_cols, n_cols, log_n)
+            if not ok:
+                raise StarkMiError(-50, why)
+        roots = np.zeros((3, 32), dtype=np.uint8)
+        cnt = 2 * n_cols + 2 * A + D
+        ood = np.zeros(4 * cnt, dtype=np.uint64)
+        proof, plen, mask = vp(), C.c_size_t(), C.c_uint32()
+        top = np.zeros(max(t, 1), dtype=np.uint64)
+        stage = (C.c_double * 8)()
+        self._ck_perm(self.L.smi_dev_air_prove_deep_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xa), vp(d_trace_cols), roots.ctypes.data,
+                                                          ood.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                          0 if grind_bits is None else grind_bits, C.byref(mask)))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        closes = [bool(mask.value >> i & 1) for i in range(A)]
+        if check and not all(closes):
+            raise StarkMiError(-50, f"air_prove_deep_xargs: the arguments {[i for i, c in enumerate(closes) if not c]} do not close")
+        out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]], "closes": closes,
+               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(cnt)]}
+        if timed:
+            out["stage_ms"] = dict(zip(("lde", "commit", "args", "compose", "segments", "ood", "fri", "open"), [float(x) for x in stage]))
+        return out
+
     def _check_air_folding(self, a, folding, row_leaves, ext):
         _check_folding(folding)
         if folding == 4 and not (row_leaves and ext):
@@ -772,7 +842,8 @@ class Engine:
             raise StarkMiError(-50, "folding=4: the permutation, lookup and argument-list provers fold by 2 only")
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
-                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2, deep=False):
+                      timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2, deep=False,
+                      deep_args=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -795,8 +866,15 @@ class Engine:
         deep=True (needs row_leaves=True, ext=True; ValueError together with a permutation, a lookup, an argument list or
         folding=4): smi_dev_air_prove_deep -- out-of-domain sampling, FRI at the full blowup (include/stark_mi.h, "Out-of-domain
         sampling").  column_roots is (2, 32) -- root_1, root_2 --, the result gains "ood" (the record's 2 W + D elements of
-        four coordinates each), stage_ms has seven stages, grind_bits None counts as 0."""
+        four coordinates each), stage_ms has seven stages, grind_bits None counts as 0.
+        deep_args=True (needs row_leaves=True, ext=True, folding=2 and an add_permutation / add_lookup list; ValueError otherwise
+        and together with deep=True): smi_dev_air_prove_deep_xargs -- out-of-domain sampling for an argument list (include/
+        stark_mi.h, "Out-of-domain sampling with an argument list").  column_roots is (3, 32), the result has "ood" (2 W + 2 A + D
+        elements) and "closes", stage_ms has eight stages, fill_multiplicities works as for the list prover."""
         a = self._air(air)
+        if deep_args:
+            return self._dev_air_prove_deep_args(a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed,
+                                                 check, row_leaves, ext, grind_bits, fill_multiplicities, folding, deep)
         if deep:
             return self._dev_air_prove_deep(a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed, check,
                                             row_leaves, ext, grind_bits, fill_multiplicities, folding)
@@ -944,7 +1022,7 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False):
+                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False, deep_args=False):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
@@ -953,7 +1031,19 @@ class Engine:
         the same way, and an AIR with an argument list smi_air_verify_args (smi_air_verify_xargs when the list has selectors
         or periodic members).
         folding=4: smi_air_verify_ext_fold4, under the conditions of dev_air_prove(folding=4).
-        deep=True: smi_air_verify_deep, under the conditions of dev_air_prove(deep=True); column_roots is root_1 then root_2."""
+        deep=True: smi_air_verify_deep, under the conditions of dev_air_prove(deep=True); column_roots is root_1 then root_2.
+        deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots."""
+        if deep_args:
+            a = self._air(air)
+            xa = self._check_deep_args(a, row_leaves, ext, folding, deep)
+            cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+            roots = np.ascontiguousarray(np.frombuffer(b"".join(bytes(r) for r in column_roots), dtype=np.uint8))
+            if roots.size != 96:
+                raise StarkMiError(-50, "air_verify(deep_args=True) takes three 32-byte roots")
+            acc = C.c_int()
+            self._ck(self.L.smi_air_verify_deep_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xa), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                                                      0 if grind_bits is None else grind_bits))
+            return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if deep:
             a = self._air(air)
             self._check_deep(a, row_leaves, ext, folding, False)
@@ -1125,6 +1215,37 @@ def air_plan_deep(p, air, cfg, with_length=False):
     st = L.smi_air_plan_deep(p, C.byref(cfg), C.byref(air), C.byref(d), C.byref(D))
     if not st and with_length:
         st = L.smi_air_deep_layout(p, C.byref(cfg), C.byref(air), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return (d.value, D.value, n.value) if with_length else (d.value, D.value)
+
+
+def xargs_of(air):
+    """the _lib.AirXArgs of a flattened AIR's argument list: its own when the list has selectors or periodic members (or was
+    flattened with xargs_always), else its smi_air_args written in the superset form -- every column an operand of this row,
+    no selector.  None without a list."""
+    if getattr(air, "xargs", None) is not None:
+        return air.xargs
+    args = getattr(air, "args", None)
+    if args is None:
+        return None
+    raw = (_lib.AirXArg * args.count)()
+    for i in range(args.count):
+        g = args.arg[i]
+        raw[i] = _lib.AirXArg(g.kind, g.width, g.mult_col, 0, g.a_col, g.b_col, _lib.NO_SELECTOR, _lib.NO_SELECTOR)
+    out = _lib.AirXArgs(args.count, 0, raw)
+    out._keep = (raw, args)
+    return out
+
+
+def air_plan_deep_args(p, air, xargs, cfg, with_length=False):
+    """smi_air_plan_deep_xargs (host only) -> (d, D), or with_length (d, D, proof bytes of smi_air_deep_xargs_layout for cfg's
+    number of colinearity tests).  air: a flattened _lib.Air; xargs: a _lib.AirXArgs"""
+    d, D, n = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_plan_deep_xargs(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(d), C.byref(D))
+    if not st and with_length:
+        st = L.smi_air_deep_xargs_layout(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(n))
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return (d.value, D.value, n.value) if with_length else (d.value, D.value)

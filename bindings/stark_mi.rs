@@ -254,6 +254,7 @@ extern "C" {
     pub fn smi_dev_hash_leaves(ctx: *mut smi_ctx, d_elems: *const u32, n: usize, d_digests: *mut u8) -> c_int;
     pub fn smi_dev_merkle_build(ctx: *mut smi_ctx, d_elems: *const u32, n: usize, d_nodes: *mut u8) -> c_int;
     pub fn smi_dev_merkle_build_rows(ctx: *mut smi_ctx, d_cols: *const u32, n_cols: u32, col_stride: usize, n: usize, d_nodes: *mut u8) -> c_int;
+    pub fn smi_dev_merkle_build_cosets(ctx: *mut smi_ctx, d_cols: *const u32, n_cols: u32, col_stride: usize, n: usize, d_nodes: *mut u8) -> c_int;
     pub fn smi_dev_merkle_from_digests(ctx: *mut smi_ctx, n: usize, d_nodes: *mut u8) -> c_int;
     pub fn smi_dev_hash_bytes(ctx: *mut smi_ctx, d_msg: *const u8, len: usize, d_out32: *mut u8) -> c_int;
     pub fn smi_dev_fri_fold(ctx: *mut smi_ctx, d_in: *const u32, len: usize, d_alpha: *const u64, offset: u64, omega: u64, d_out: *mut u32) -> c_int;
@@ -324,6 +325,12 @@ extern "C" {
     pub fn smi_dev_deep_compose_args(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, n_args: u32, n_segments: u32, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize, d_seg: *const u32, seg_stride: usize, z: *const u64, ood: *const u64, challenges: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
     pub fn smi_dev_air_prove_deep_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_trace_cols: *const u32, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
     pub fn smi_air_verify_deep_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_deep_fold4_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
+    pub fn smi_dev_air_prove_deep_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
+    pub fn smi_air_verify_deep_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_deep_xargs_fold4_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
+    pub fn smi_dev_air_prove_deep_xargs_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_trace_cols: *const u32, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
+    pub fn smi_air_verify_deep_xargs_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;

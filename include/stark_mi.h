@@ -313,6 +313,15 @@ int smi_dev_merkle_build(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_
  * instead of to a single element; with 4 columns a leaf is one 32-byte chunk and costs what a
  * single-element leaf costs, so one tree replaces four. */
 int smi_dev_merkle_build_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
+/* Coset-leaf tree: a group of n_cols (1 .. 64) columns of n residues, n a power of two and at least 4, column c at
+ * d_cols + c*col_stride with col_stride >= n.  With q = n / 4, leaf i < q = Hash::from_field_elements of 4 n_cols values,
+ * value 4 c + j = column c at index i + j q, j = 0 .. 3: one leaf per coset {i, i + q, i + 2 q, i + 3 q} of a fold by 4,
+ * in the order of fold-by-4 FRI's leaf (coordinate outer, coset point inner), so a four-coordinate codeword's tree
+ * here is the tree of "Extension FRI, folding factor 4" and a trace tree follows the same rule.  One opening then
+ * serves all four points: one leaf and log2 q digests.  d_nodes: (2 q - 1) x 32 bytes, levels as above; q = 1 is a tree
+ * of one digest.  SMI_ERR_BAD_ARG (smi_last_error has the sentence) when n is not a power of two or n < 4, when
+ * col_stride < n, or when n_cols is outside 1 .. 64. */
+int smi_dev_merkle_build_cosets(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
 /* Tree over precomputed 32-byte leaves already at d_nodes[0 .. n*32). */
 int smi_dev_merkle_from_digests(smi_ctx *ctx, size_t n, uint8_t *d_nodes);
 /* Hash::from_bytes (src/hash.rs:7-30) of a message in device memory, digest to device memory: a
@@ -1130,7 +1139,7 @@ int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air
  *   recomputed from the opened rows against the layer-0 triple's a and b.  A proof of smi_dev_air_prove_ext_pow is rejected
  *   here, and a proof of this variant by smi_air_verify_ext_pow.
  * Soundness accounting and measured times: DESIGN.md section 11, "Out-of-domain sampling".
- * Left out: folding factor 4; column trees; smi_mgpu_* twins; zero-knowledge randomisers; binding an AIR digest into the
+ * Left out: folding factor 4 (it comes with coset leaves, below); column trees; smi_mgpu_* twins; zero-knowledge randomisers; binding an AIR digest into the
  *   transcript; the segment extension fused into the leaf hash.  (Permutation, lookup and argument lists are what
  *   "Out-of-domain sampling with an argument list" below adds; these entry points stay as they are.) */
 /* Host only (like smi_air_plan): the plan above -> d and D. */
@@ -1217,7 +1226,7 @@ int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   rejects such a proof on the consistency check.  A zero denominator in a column is SMI_ERR_NO_INVERSE as
  *   smi_dev_xargs_columns reports it.
  * Soundness accounting: DESIGN.md section 11.
- * Left out: folding factor 4; the single permutation / lookup forms (a one-element list covers them); next-row tuple
+ * Left out: folding factor 4 (it comes with coset leaves, below); the single permutation / lookup forms (a one-element list covers them); next-row tuple
  *   members; smi_mgpu_* twins; zero-knowledge randomisers; fusing the auxiliary quotients or the segment extension into
  *   other launches. */
 /* Host only: the plan above -> d and D.  `xargs` is a pointer to an smi_air_xargs. */
@@ -1241,6 +1250,58 @@ int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const v
                                  uint32_t *closes);
 int smi_air_verify_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
                               size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Out-of-domain sampling over coset leaves ---------------------------------------------------------------------------
+ * The two DEEP proofs above with FRI at folding factor 4 and every committed group of columns a tree of coset leaves.  FRI
+ * only sees the DEEP codeword Q, so folding it by 4 does not depend on the statement; and DEEP has no + B rows, so a test
+ * needs exactly the four points of one layer-0 coset from every group -- one leaf of smi_dev_merkle_build_cosets and one
+ * path of log2 N - 2 digests per tree, where a row tree would open four rows with four full paths.
+ * Plans: smi_air_plan_deep and smi_air_plan_deep_xargs as they are (4 D <= 64 is the bound 16 D <= 256 of a coset leaf).
+ * Prover.  Every step of "Out-of-domain sampling" (smi_dev_air_prove_deep_fold4) or of "Out-of-domain sampling with an
+ * argument list" (smi_dev_air_prove_deep_xargs_fold4) applies word for word, with three differences:
+ *   - every commitment is smi_dev_merkle_build_cosets over the same columns: the trace (V = W), the auxiliary coordinate
+ *     columns (V = 4 A, lists only), the segments (V = 4 D).  The transcript keeps its shape -- the same objects under the
+ *     same counters --; only the root values differ;
+ *   - FRI is "Extension FRI, folding factor 4", continuing that transcript at E = B over Q where it stands (stride == N, no
+ *     compaction copy); the nonce record is always present;
+ *   - openings, after the FRI objects, one section per group in the order trace, (auxiliary,) segments, each laid out like
+ *     a fold-by-4 FRI layer: t tag-2 records of 4 V values in leaf order (value 4 c + j = column c at a + j N / 4,
+ *     a = top mod N / 4), then t tag-3 paths of log2 N - 2 digests.  One launch (coset_open_kernel) writes them all.
+ * Proof bytes (smi_air_deep_fold4_layout, smi_air_deep_xargs_fold4_layout; len_FRI4 is smi_fri_fold4_layout's):
+ *   9 + 32 (2W + D) + len_FRI4(N, B, t) + sum over V in {W, 4D} of [ t (9 + 32 V) + t (9 + 32 (log2 N - 2)) ]
+ *   and with a list  9 + 32 (2W + 2A + D) + len_FRI4(N, B, t) + the same sum over V in {W, 4A, 4D}.
+ * A shape without a fold (F = 0 in smi_fri_fold4_layout's count) has no layer-0 coset to compare Q with: the prover refuses
+ *   it with SMI_ERR_BAD_ARG and a sentence that starts "deep fold4: FRI has no fold", and the verifier rejects every proof
+ *   with the same sentence after the consistency check.  The layout functions still report folds = 0 and the length.
+ * Verifier (host), in this order: the checks of smi_air_verify_deep (smi_air_verify_deep_xargs) in their order with their
+ *   sentences up to and including the consistency check at z; the fold-by-4 FRI walk with the proof of work, which hands
+ *   out the layer-0 coset records; the exact length of the opening sections; the tag and count of every record and path,
+ *   group by group; every record hashed as it stands to its leaf and its path checked against the group's root at index a;
+ *   canonical values; Q recomputed at the four points x_a iota^j, iota = omega_N^(N/4) -- group column c at point j is
+ *   record value 4 c + j -- and each coordinate e compared with value 4 e + j of the test's layer-0 coset record.  The
+ *   sentences of the opening checks start "deep coset openings:" ("deep argument coset openings:" with a list).  A proof of
+ *   smi_dev_air_prove_deep, smi_dev_air_prove_deep_xargs or smi_dev_air_prove_ext_fold4 is rejected here, and a proof of
+ *   this variant by their verifiers.
+ * Soundness is that of the two sections above: a query is still worth log2 B bits.
+ * Left out: the single permutation() / lookup() forms (a one-element list covers them); column trees; smi_mgpu_* twins;
+ *   folding factors above 4; fusing the DEEP codeword or the fold into a leaf launch; zero-knowledge randomisers; an AIR
+ *   digest in the transcript. */
+/* Host only: the plan of smi_air_plan_deep, then *folds = F and the proof length in bytes (num_colinearity_tests is read). */
+int smi_air_deep_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint64_t *folds, size_t *proof_len);
+/* smi_dev_air_prove_deep's parameters: roots (optional) root_1, root_2, 64 bytes; stage_ms (optional) seven values
+ * {lde, commit, compose, segments, ood, fri, open}. */
+int smi_dev_air_prove_deep_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots, uint64_t *ood,
+                                 uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
+int smi_air_verify_deep_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
+                              int *accept, uint32_t grind_bits);
+/* The same for an argument list: the plan of smi_air_plan_deep_xargs; three roots, 96 bytes; eight stages {lde, commit,
+ * args, compose, segments, ood, fri, open}; *closes as in smi_dev_air_prove_deep_xargs. */
+int smi_air_deep_xargs_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint64_t *folds, size_t *proof_len);
+int smi_dev_air_prove_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols,
+                                       uint8_t *roots, uint64_t *ood, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                                       uint32_t grind_bits, uint32_t *closes);
+int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                                    size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

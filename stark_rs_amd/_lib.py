@@ -197,6 +197,7 @@ def lib():
         "smi_dev_hash_leaves": (i32, [vp, vp, sz, vp]),
         "smi_dev_merkle_build": (i32, [vp, vp, sz, vp]),
         "smi_dev_merkle_build_rows": (i32, [vp, vp, C.c_uint32, sz, sz, vp]),
+        "smi_dev_merkle_build_cosets": (i32, [vp, vp, C.c_uint32, sz, sz, vp]),
         "smi_dev_merkle_from_digests": (i32, [vp, sz, vp]),
         "smi_dev_fri_fold": (i32, [vp, vp, sz, vp, C.c_uint64, C.c_uint64, vp]),
         "smi_dev_fri_fold_shard": (i32, [vp, vp, vp, sz, sz, sz, vp, C.c_uint64, C.c_uint64, vp]),
@@ -276,6 +277,14 @@ def lib():
                                                vp, C.c_uint32, u32p]),
         "smi_air_verify_deep_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32),
                                             C.c_uint32]),
+        "smi_air_deep_fold4_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), u64p, C.POINTER(sz)]),
+        "smi_dev_air_prove_deep_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
+        "smi_air_verify_deep_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_air_deep_xargs_fold4_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u64p, C.POINTER(sz)]),
+        "smi_dev_air_prove_deep_xargs_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, vp, vp, C.POINTER(vp), C.POINTER(sz),
+                                                     vp, vp, C.c_uint32, u32p]),
+        "smi_air_verify_deep_xargs_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32),
+                                                  C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -315,6 +315,25 @@ int smi_air_deep_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *
     if (rc == SMI_OK && proof_len) *proof_len = deep_args_proof_len(cfg, ((const smi_air_xargs *)xargs)->count, D);
     return rc;
 }
+// ... over coset leaves (deep_core.h): the plans above, the number of folds of FRI at folding factor 4 and the proof length
+int smi_air_deep_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint64_t *folds, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t D = 0;
+    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err);
+    if (rc != SMI_OK) return rc;
+    const size_t len = deep_fold4_proof_len(cfg, 0, D, folds);
+    if (proof_len) *proof_len = len;
+    return SMI_OK;
+}
+int smi_air_deep_xargs_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint64_t *folds, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t D = 0;
+    const int rc = deep_xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, nullptr, &D, &g_air_err);
+    if (rc != SMI_OK) return rc;
+    const size_t len = deep_fold4_proof_len(cfg, ((const smi_air_xargs *)xargs)->count, D, folds);
+    if (proof_len) *proof_len = len;
+    return SMI_OK;
+}
 // what perm.hip and lookup.hip share with the provers of this file (internal.h)
 int air_host_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) { return air_host(ctx, cfg, air, H, E); }
 int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_t *d_lde, size_t stride, const uint64_t *d_weights, uint32_t *d_out,

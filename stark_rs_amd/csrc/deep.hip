@@ -659,3 +659,240 @@ int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const v
         }
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }
+
+// ---- out-of-domain sampling over coset leaves (include/stark_mi.h, "Out-of-domain sampling over coset leaves")
+// The two provers above with every commitment a tree of coset leaves (launch_merkle_cosets), FRI at folding factor 4 over
+// the DEEP codeword where it stands (stride == N: no compaction copy), and one leaf and one path per test and group
+// (coset_open_kernel).  Everything else -- the transcripts, the segments, the evaluations at z, the two codeword kernels --
+// is what the provers above run, so the two variants are one function that differs by the list (xargs == nullptr: a plain
+// AIR) and by the group table.
+
+// one workgroup per (test, group): mgpu_core.h mg_coset_open_write
+__global__ __launch_bounds__(64) void coset_open_kernel(const MgCosetTable tab, uint32_t log_N, const uint64_t *__restrict__ top, uint32_t t, uint8_t *out) {
+    const MgCosetGroup &G = tab.g[blockIdx.y];
+    mg_coset_open_write(G, log_N, top[blockIdx.x], blockIdx.x, t, out + G.out_at, threadIdx.x, 64);
+}
+
+namespace {
+int deep_fold4_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *d_trace_cols, uint8_t *roots_out,
+                     uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes) {
+    if (closes) *closes = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(deep_field_check(ctx));
+    uint32_t D = 0;
+    {
+        std::string why;
+        const int rc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why) : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    }
+    if (xargs) SMI_TRY(xargs_entry_checks(ctx, air, xargs, cfg->n_cols, cfg->log_n));
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs ? xargs->count : 0, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
+    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the auxiliary tree
+    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    if (fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_FOLD4_NO_LAYER);
+    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N, q = N / 4;
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
+    const uint32_t G = A ? 3 : 2, n_stages = A ? 8 : 7;
+    AirHost H;
+    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
+    SMI_TRY(arena_reset(ctx));
+    struct Events {   // destroyed on every return path
+        hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs;
+    const bool timed = stage_ms != nullptr;
+    if (timed)
+        for (uint32_t i = 0; i <= n_stages; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
+    uint32_t marks = 0;
+    auto mark = [&]() {
+        if (timed) (void)hipEventRecord(evs.ev[marks], ctx->stream);
+        marks++;
+    };
+
+    const size_t n_ood = deep_args_record(W, A, D);
+    const size_t tree_bytes = 2 * q * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
+    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
+    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
+    uint32_t *d_c = A ? (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4) : nullptr;
+    uint32_t *d_cl = A ? (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4) : nullptr;
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // H, then Q
+    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // the coefficients of H's coordinates
+    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, 4 * (size_t)D * N * 4);
+    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)(W + CW) * n * 4);   // the trace polynomials, then the columns' coordinates
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
+    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
+    uint8_t *tree[3] = {nullptr, nullptr, nullptr};   // in group order: trace, (auxiliary,) segments
+    for (uint32_t k = 0; k < G; k++) tree[k] = (uint8_t *)arena_alloc(ctx, tree_bytes);
+    uint8_t *d_atmp = A ? (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_size(A, n)) : nullptr;
+    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
+    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
+    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | H_{j,e} at z, e-major
+    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_args_tab_words(W, A, D) * 4);
+    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
+    if (H.dev.Q) {
+        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
+        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
+    }
+    if (!d_lde || (A && (!d_c || !d_cl || !d_atmp)) || !d_cw || !d_hc || !d_seg || !d_coef || !d_weights || !d_blob || !tree[0] || !tree[1] || (A && !tree[2]) ||
+        !d_tab2 || !d_tab1 || !d_part || !d_res || !d_ctab || (H.dev.Q && (!d_ptab || !d_pvals)))
+        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_fold4: device memory");
+    auto root_of = [&](uint32_t k, uint8_t *dst) { return hipMemcpyAsync(dst, tree[k] + (2 * q - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream); };
+    mark();
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
+    mark();
+    SMI_TRY(launch_merkle_cosets(ctx, d_lde, W, N, N, tree[0]));
+    mark();
+    // root_1 -> the composition weights (plain AIR) or alpha, gamma (list)
+    uint8_t roots[96];
+    HIP_TRY(ctx, root_of(0, roots));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
+    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for the values at z
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    Transcript tr;
+    std::vector<uint64_t> ch, weights, gammas;
+    XArgsDev XD;
+    if (A) {
+        transcript_perm_challenges(tr, roots, &ch);
+        xargs_build(ctx->fs.F, g, xargs, W, air, H.per, ch.data(), &XD);
+        XD.pvals = d_pvals;
+        SMI_TRY(xargs_columns_launch(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
+        SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
+        SMI_TRY(launch_merkle_cosets(ctx, d_cl, CW, N, N, tree[1]));
+        mark();
+        // root_2 (and the columns' verdicts) -> the weights
+        ArgsFlags fl;
+        HIP_TRY(ctx, root_of(1, roots + 32));
+        HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+        SMI_TRY(dev_ntt(ctx, d_c, d_coef + (size_t)W * n, log_n, n, CW, n, n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        SMI_TRY(xargs_columns_settle(ctx, XD, fl, closes));
+        transcript_args_weights(tr, roots + 32, W, K, A, &weights);
+    } else {
+        deep_transcript_weights(tr, roots, W, K, &weights);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
+    if (A) SMI_TRY(xargs_compose_launch(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
+    mark();
+    // the segments: coefficients of every coordinate of H on the coset, D slices of n, each extended back to the N points
+    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
+    for (uint32_t j = 0; j < D; j++)
+        SMI_TRY(dev_ntt(ctx, d_hc + (size_t)j * n, d_seg + 4 * (size_t)j * N, log_N, n, 4, N, N, 0, cfg->lde_offset, 1));
+    SMI_TRY(launch_merkle_cosets(ctx, d_seg, 4 * D, N, N, tree[G - 1]));
+    mark();
+    // the segments' root -> z
+    HIP_TRY(ctx, root_of(G - 1, roots + 32 * (G - 1)));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t zr[4];
+    if (A) deep_args_transcript_z(tr, roots + 64, NW, zr);
+    else deep_transcript_z(tr, roots + 32, W, K, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
+    if (roots_out) memcpy(roots_out, roots, 32 * (size_t)G);
+    // u, v = f(z), f(z w); a, b = c(z), c(z w); s = H_j(z)
+    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
+    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
+    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
+    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W + CW, n, n, 2, d_tab2, d_part, d_res));
+    uint32_t *d_sres = d_res + 8 * (size_t)(W + CW);
+    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D segments: D columns of n coefficients, n apart
+        SMI_TRY(deep_eval_enqueue(ctx, d_hc + (size_t)e * N, D, n, n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * D));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> ood(n_ood);
+    const FqH X{{0, 1 % p, 0, 0}};
+    auto assemble = [&](const uint32_t *at, size_t pitch, uint64_t *dst) {   // sum_e X^e v_e, v_e four words at at + e pitch
+        FqH s = fqh(0), xe = fqh(1 % p);
+        for (uint32_t e = 0; e < 4; e++) {
+            const uint32_t *v = at + e * pitch;
+            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
+            xe = fqh_mul(xe, X, p, g);
+        }
+        for (uint32_t e = 0; e < 4; e++) dst[e] = s.c[e];
+    };
+    for (uint32_t c = 0; c < W; c++)
+        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
+    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
+        assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
+        assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
+    }
+    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
+    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
+    if (A) deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
+    else deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
+    const FsSeed seed = tr.seed();
+    if (A) {
+        deep_compose_args_build(ctx->fs.F, g, W, A, D, w_n, z, ood.data(), gammas.data(), &ctab);
+        HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        SMI_TRY(deep_compose_args_enqueue(ctx, W, A, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_cl, N, d_seg, N, d_cw, N));
+    } else {
+        deep_compose_build(ctx->fs.F, g, W, D, w_n, z, ood.data(), gammas.data(), &ctab);
+        HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        SMI_TRY(deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_seg, N, d_cw, N));
+    }
+    mark();
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    FriExtResult xres;
+    SMI_TRY(fri_run_ext_fold4(ctx, &fc, &seed, d_cw, N, N, false, &xres, grind_bits));
+    std::vector<uint8_t> bytes(9 + 8 * n_ood);
+    bytes[0] = 2;
+    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
+    for (size_t v = 0; v < n_ood; v++)
+        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
+    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
+    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    mark();
+    if (cfg->num_colinearity_tests) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests;
+        const DeepGroups gr = deep_groups(W, A, D);
+        const uint32_t *cols[3] = {d_lde, A ? d_cl : d_seg, d_seg};
+        MgCosetTable tab;
+        memset(&tab, 0, sizeof tab);
+        size_t total = 0;
+        for (uint32_t k = 0; k < G; k++) {
+            tab.g[k] = MgCosetGroup{cols[k], N, tree[k], total, gr.V[k], 0};
+            total += (size_t)mg_coset_open_bytes(gr.V[k], t, log_N);
+        }
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, total);
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_fold4: coset openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        coset_open_kernel<<<dim3(t, G), 64, 0, ctx->stream>>>(tab, log_N, d_top, t, d_open);
+        HIP_TRY(ctx, hipGetLastError());
+        const size_t at = bytes.size();
+        bytes.resize(at + total);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    mark();
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed)
+        for (uint32_t i = 0; i < n_stages; i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    return smi_proof_out(ctx, bytes, proof, proof_len);
+}
+}  // namespace
+
+int smi_dev_air_prove_deep_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots_out, uint64_t *ood_out,
+                                 uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return deep_fold4_prove(ctx, cfg, (const smi_air *)air, nullptr, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices, stage_ms, grind_bits,
+                            nullptr);
+}
+int smi_dev_air_prove_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols,
+                                       uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                                       uint32_t grind_bits, uint32_t *closes) {
+    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return deep_fold4_prove(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices,
+                            stage_ms, grind_bits, closes);
+}

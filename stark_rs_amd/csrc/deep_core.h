@@ -629,3 +629,102 @@ inline FqH deep_args_q_at(uint32_t p, uint32_t g, uint32_t W, uint32_t A, uint32
     const FqH d1 = fqh_sub(fqh(x), z, p), d2 = fqh_sub(fqh(x), fqh_scale(z, w_n, p), p);
     return fqh_add(fqh_mul(n1, fqh_inv(d1, p, g), p, g), fqh_mul(n2, fqh_inv(d2, p, g), p, g), p);
 }
+
+// ------------------------------------------------------------------------------------------------ ... over coset leaves
+// include/stark_mi.h, "Out-of-domain sampling over coset leaves": every committed group of columns -- the trace (V = W), the
+// auxiliary coordinates (V = 4 A, argument lists only) and the segments (V = 4 D) -- is a tree of N / 4 coset leaves
+// (smi_dev_merkle_build_cosets), FRI folds by 4, and a test opens one leaf and one path per group.  What the two variants
+// share is written once over a list of groups: the section lengths, the parsing, and Q at the four points of a coset.
+#define DEEP_FOLD4_NO_LAYER \
+    "deep fold4: FRI has no fold at this shape (F = 0), so there is no layer-0 coset to compare the DEEP quotient with"
+static const char *const DEEP_FOLD4_SENTENCES[6] = {"deep coset openings: wrong length",
+                                                    "deep coset openings: malformed record",
+                                                    "deep coset openings: malformed path",
+                                                    "deep coset openings: authentication path does not verify",
+                                                    "deep coset openings: an opened value is not canonical",
+                                                    "deep coset openings: the DEEP quotient of the opened cosets is not the codeword value"};
+static const char *const DEEP_ARGS_FOLD4_SENTENCES[6] = {"deep argument coset openings: wrong length",
+                                                         "deep argument coset openings: malformed record",
+                                                         "deep argument coset openings: malformed path",
+                                                         "deep argument coset openings: authentication path does not verify",
+                                                         "deep argument coset openings: an opened value is not canonical",
+                                                         "deep argument coset openings: the DEEP quotient of the opened cosets is not the codeword value"};
+
+// the groups of one proof in section order: W, 4 D (A == 0) or W, 4 A, 4 D
+struct DeepGroups {
+    uint32_t G, V[3];
+};
+inline DeepGroups deep_groups(uint32_t W, uint32_t A, uint32_t D) {
+    DeepGroups gr;
+    gr.G = A ? 3 : 2;
+    gr.V[0] = W;
+    gr.V[1] = A ? 4 * A : 4 * D;
+    gr.V[2] = A ? 4 * D : 0;
+    return gr;
+}
+// one group's section: t records of 4 V values, then t paths of log2 N - 2 digests
+inline size_t deep_coset_section_len(uint32_t V, uint64_t t, uint32_t log_N) { return (size_t)(t * (9 + 32ull * V) + t * (9 + 32ull * (log_N - 2))); }
+inline size_t deep_coset_sections_len(const DeepGroups &gr, uint64_t t, uint32_t log_N) {
+    size_t s = 0;
+    for (uint32_t k = 0; k < gr.G; k++) s += deep_coset_section_len(gr.V[k], t, log_N);
+    return s;
+}
+// 9 + 32 (2 W + 2 A + D) + len_FRI4(N, B, t) + the sections; A == 0: the plain-AIR variant
+inline size_t deep_fold4_proof_len(const smi_stark_cfg *cfg, uint32_t A, uint32_t D, uint64_t *folds) {
+    const uint32_t W = cfg->n_cols, log_N = cfg->log_n + cfg->log_blowup;
+    const FriFold4Layout lay = fri_layout_fold4(deep_fri_cfg(cfg, 1));
+    if (folds) *folds = lay.F;
+    return 9 + 32 * (2 * (size_t)W + 2 * (size_t)A + D) + lay.proof_len + deep_coset_sections_len(deep_groups(W, A, D), cfg->num_colinearity_tests, log_N);
+}
+
+enum { DEEP_COSET_OK = 0, DEEP_COSET_LENGTH = 1, DEEP_COSET_RECORD = 2, DEEP_COSET_PATH = 3 };
+// The opening sections as they stand in a proof (`len` bytes at `sec`): the exact length, then group by group the tag and
+// count of every record and of every path.  -> DEEP_COSET_OK with vals[k] = the t x 4 V_k values of group k and at[k] = the
+// offset of its section, or the first check that fails.
+inline int deep_coset_parse(const uint8_t *sec, size_t len, const DeepGroups &gr, uint64_t t, uint32_t log_N, std::vector<uint64_t> vals[3], size_t at[3]) {
+    if (len != deep_coset_sections_len(gr, t, log_N)) return DEEP_COSET_LENGTH;
+    auto u64_at = [](const uint8_t *b) {
+        uint64_t v = 0;
+        for (int i = 7; i >= 0; i--) v = (v << 8) | b[i];
+        return v;
+    };
+    const uint64_t depth = log_N - 2;
+    size_t off = 0;
+    for (uint32_t k = 0; k < gr.G; k++) {
+        const size_t cnt = 4 * (size_t)gr.V[k], rec = 9 + 8 * cnt, prec = 9 + 32 * (size_t)depth;
+        at[k] = off;
+        vals[k].resize((size_t)t * cnt);
+        for (uint64_t s = 0; s < t; s++) {
+            const uint8_t *r = sec + off + s * rec;
+            if (r[0] != 2 || u64_at(r + 1) != cnt) return DEEP_COSET_RECORD;
+            for (size_t i = 0; i < cnt; i++) vals[k][s * cnt + i] = u64_at(r + 9 + 8 * i);
+        }
+        for (uint64_t s = 0; s < t; s++) {
+            const uint8_t *r = sec + off + t * rec + s * prec;
+            if (r[0] != 3 || u64_at(r + 1) != depth) return DEEP_COSET_PATH;
+        }
+        off += (size_t)t * (rec + prec);
+    }
+    return DEEP_COSET_OK;
+}
+// Q at the four points x_a iota^j of one test's coset from its opened leaves (rec[k]: the 4 V_k canonical values of group k,
+// column c at point j = value 4 c + j) against the layer-0 coset record of FRI (coordinate e at point j = value 4 e + j).
+// Point by point through deep_q_at / deep_args_q_at.
+inline bool deep_coset_q_matches(uint32_t p, uint32_t g, uint32_t W, uint32_t A, uint32_t D, uint32_t w_n, uint32_t x_a, uint32_t iota, const FqH &z,
+                                 const uint64_t *ood, const uint64_t *gammas, const uint64_t *const rec[3], const uint64_t coset[16]) {
+    const DeepGroups gr = deep_groups(W, A, D);
+    std::vector<uint64_t> row[3];
+    uint32_t x = x_a;
+    for (uint32_t j = 0; j < 4; j++) {
+        for (uint32_t k = 0; k < gr.G; k++) {
+            row[k].resize(gr.V[k]);
+            for (uint32_t c = 0; c < gr.V[k]; c++) row[k][c] = rec[k][4 * (size_t)c + j];
+        }
+        const FqH q = A ? deep_args_q_at(p, g, W, A, D, w_n, x, z, ood, gammas, row[0].data(), row[1].data(), row[2].data())
+                        : deep_q_at(p, g, W, D, w_n, x, z, ood, gammas, row[0].data(), row[1].data());
+        for (uint32_t e = 0; e < 4; e++)
+            if (q.c[e] != coset[4 * e + j]) return false;
+        x = host_mulmod(x, iota, p);
+    }
+    return true;
+}

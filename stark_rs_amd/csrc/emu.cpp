@@ -563,6 +563,23 @@ extern "C" void emu_row_hash_wide(const uint32_t *cols, size_t stride, size_t n,
             if (two) memcpy(out + 32 * i1, d1, 32);
         }
 }
+// coset_leaf_hash_kernel (hash.hip) one workgroup and one lane at a time: the kernel's grid over q = n / 4 leaves, its
+// choice of a lane's two leaves (row_wide_pair) and its per-lane body (coset_leaf_hash2) over columns `stride` apart
+extern "C" void emu_coset_leaf_hash(const uint32_t *cols, size_t stride, size_t n, int V, uint8_t *out) {
+    const uint32_t T = SMI_HASH_THREADS;
+    const size_t q = n / 4;
+    const size_t blocks = ((q + 1) / 2 + T - 1) / T;
+    for (size_t blk = 0; blk < blocks; blk++)
+        for (uint32_t tid = 0; tid < T; tid++) {
+            size_t i0, i1;
+            bool two;
+            if (!hashc::row_wide_pair(blk, tid, T, q, &i0, &i1, &two)) continue;
+            uint32_t d0[8], d1[8];
+            hashc::coset_leaf_hash2(cols, stride, q, i0, i1, V, d0, d1);
+            memcpy(out + 32 * i0, d0, 32);
+            if (two) memcpy(out + 32 * i1, d1, 32);
+        }
+}
 extern "C" void emu_hash_bytes(const uint8_t *msg, size_t len, uint8_t *out) {
     uint32_t d[8];
     hashc::hash_bytes(msg, len, d);

@@ -178,6 +178,26 @@ extern "C" uint64_t emu_air_row_open(const uint32_t *cols, uint64_t stride, uint
     return mg_row_open_bytes(W, t, depth, R);
 }
 
+// coset_open_kernel (deep.hip): its grid -- one workgroup of 64 lanes per (test, group) -- over the writer both share
+// (mgpu_core.h mg_coset_open_write).  Group k: V[k] columns at cols[k], stride[k] apart, under the tree nodes[k] of N / 4
+// coset leaves; the sections follow each other in group order -> the bytes written
+extern "C" uint64_t emu_coset_open(uint32_t G, const uint32_t *const *cols, const uint64_t *stride, const uint32_t *V, const uint8_t *const *nodes, uint64_t N,
+                                   const uint64_t *top, uint32_t t, uint8_t *out) {
+    uint32_t log_N = 0;
+    while ((1ull << log_N) < N) log_N++;
+    MgCosetTable tab;
+    memset(&tab, 0, sizeof tab);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < G && k < 3; k++) {
+        tab.g[k] = MgCosetGroup{cols[k], stride[k], nodes[k], total, V[k], 0};
+        total += mg_coset_open_bytes(V[k], t, log_N);
+    }
+    for (uint32_t s = 0; s < t; s++)
+        for (uint32_t k = 0; k < G && k < 3; k++)
+            for (uint32_t lane = 0; lane < 64; lane++) mg_coset_open_write(tab.g[k], log_N, top[s], s, t, out + tab.g[k].out_at, lane, 64);
+    return total;
+}
+
 // transcript_core.h: layout 0 column trees (roots = W roots), 1 one row tree, 2 the extension, 3 the permutation proof (roots =
 // root_1, root_2; the 8 challenges, then the 4 (W + K + 2) weights) -> the number of challenges written; seed = the 16 words
 // and the phase FRI continues

@@ -19,6 +19,7 @@
 #include "internal.h"
 
 #define SMI_ROW_MAX 64   // columns per row leaf
+#define SMI_COSET_COLS_MAX 64   // columns per coset leaf: 256 values
 
 __device__ __forceinline__ size_t level_offset(size_t n, uint32_t lvl) { return 2 * n - ((2 * n) >> lvl); }
 
@@ -413,6 +414,26 @@ __global__ __launch_bounds__(SMI_HASH_THREADS, 8) void row_hash_wide_kernel(cons
     }
 }
 
+// Digests of the q = n / 4 coset leaves of a group of V columns (hashc::coset_leaf_hash2): row_hash_wide_kernel's shape
+// -- two leaves per lane in the paired-lane state, a workgroup owns 2 * SMI_HASH_THREADS consecutive leaves, every load
+// of a wave reads 64 consecutive words -- with a chunk that is one column at a leaf's four coset points, four loads q
+// apart, always complete; the next column's eight loads are issued before the current chunk's mix.  V mixes of chunks and
+// 8 closing ones a leaf.  Floors: 4 V n + 32 q bytes; (V + 8) q mixes.
+__global__ __launch_bounds__(SMI_HASH_THREADS, 8) void coset_leaf_hash_kernel(const uint32_t *__restrict__ cols, uint32_t n_cols, size_t stride,
+                                                                             uint4 *out, size_t q) {
+    size_t i0, i1;
+    bool two;
+    if (!hashc::row_wide_pair(blockIdx.x, threadIdx.x, SMI_HASH_THREADS, q, &i0, &i1, &two)) return;
+    uint32_t d0[8], d1[8];
+    hashc::coset_leaf_hash2(cols, stride, q, i0, i1, (int)n_cols, d0, d1);
+    out[2 * i0] = make_uint4(d0[0], d0[1], d0[2], d0[3]);
+    out[2 * i0 + 1] = make_uint4(d0[4], d0[5], d0[6], d0[7]);
+    if (two) {
+        out[2 * i1] = make_uint4(d1[0], d1[1], d1[2], d1[3]);
+        out[2 * i1 + 1] = make_uint4(d1[4], d1[5], d1[6], d1[7]);
+    }
+}
+
 // digests only (Hash::from_field_elements per element)
 __global__ __launch_bounds__(SMI_HASH_THREADS) void leaf_hash_kernel(const uint32_t *__restrict__ elems, uint4 *out, size_t n) {
     const size_t i = (size_t)blockIdx.x * SMI_HASH_THREADS + threadIdx.x;
@@ -643,6 +664,20 @@ int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, si
         HIP_TRY(ctx, hipGetLastError());
     }
     return launch_merkle_batch(ctx, nullptr, n, d_nodes, 1, 0, 0);
+}
+// one tree whose leaf i < q = n / 4 hashes the four coset points i, i + q, i + 2q, i + 3q of n_cols columns (value
+// 4 c + j = column c at i + j q); the levels above the leaves are launch_merkle_rows' digest path, q = 1 is one digest
+int launch_merkle_cosets(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes) {
+    if (!is_pow2(n) || n < 4) return smi_fail(ctx, SMI_ERR_BAD_ARG, "coset leaves: the length is a power of two, at least 4");
+    if (col_stride < n) return smi_fail(ctx, SMI_ERR_BAD_ARG, "coset leaves: the column stride is at least the length");
+    if (!n_cols || n_cols > SMI_COSET_COLS_MAX) return smi_fail(ctx, SMI_ERR_BAD_ARG, "coset leaves: 1..64 columns");
+    const size_t q = n / 4;
+    {
+        ProfScope ps(ctx, "coset_leaf_hash_kernel", 4.0 * n_cols * (double)n + 32.0 * (double)q, (n_cols + 8.0) * (double)q);
+        coset_leaf_hash_kernel<<<blocks_for((q + 1) / 2), SMI_HASH_THREADS, 0, ctx->stream>>>(d_cols, n_cols, col_stride, (uint4 *)d_nodes, q);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return launch_merkle_batch(ctx, nullptr, q, d_nodes, 1, 0, 0);
 }
 // n_trees equally sized trees in one set of launches.  The small upper levels of all trees share their launch latency.
 int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,

@@ -784,6 +784,54 @@ SMI_HD void row_hash_wide2(const uint32_t *__restrict__ cols, size_t stride, siz
     to_words2(st, d0, d1);
 }
 
+// ---- coset leaves: leaf i < q = n / 4 of a group of V columns of n residues hashes 4 V values, value 4 c + j = column
+// c at index i + j q (the order of fold-by-4 FRI's leaf: column outer, coset point inner).  hash.hip
+// coset_leaf_hash_kernel and the emulator's emu_coset_leaf_hash run exactly this under row_wide_pair.  A chunk of four
+// values is one column at the four coset points of each of the lane's two leaves -- always complete, so there is no
+// clamp, no zeroing and no short last chunk -- and, as above, nothing is indexed by a run-time value.
+SMI_HD void coset_leaf_load(const uint32_t *__restrict__ col, size_t q, size_t i0, size_t i1, uint32_t (&a)[4], uint32_t (&b)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        a[j] = col[i0 + (size_t)j * q];
+        b[j] = col[i1 + (size_t)j * q];
+    }
+}
+// digests of leaves i0 and i1 of V >= 1 columns `stride` apart: hashc::row_hash over each leaf's 4 V values, bit for bit
+SMI_HD void coset_leaf_hash2(const uint32_t *__restrict__ cols, size_t stride, size_t q, size_t i0, size_t i1, int V, uint32_t d0[8],
+                             uint32_t d1[8]) {
+    constexpr InitWords I = make_init_words();
+    uint32_t X[8], Y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) X[j] = Y[j] = I.p[j];
+    const MixK K = mix_consts();
+    State2 st;
+    uint32_t a[4], b[4];
+    const uint32_t *col = cols;
+    coset_leaf_load(col, q, i0, i1, a, b);
+#pragma unroll 1
+    for (int c = 0; c + 1 < V; c++) {   // the columns that another column follows
+        uint32_t na[4], nb[4];
+        col += stride;
+        coset_leaf_load(col, q, i0, i1, na, nb);   // in flight under this chunk's absorb and mix
+        row_wide_absorb<4>(a, b, X, Y);
+        from_words2(X, Y, st);
+        mix2(st, K);
+        to_words2(st, X, Y);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            a[j] = na[j];
+            b[j] = nb[j];
+        }
+    }
+    row_wide_absorb<4>(a, b, X, Y);
+    from_words2(X, Y, st);
+    mix2_t<false>(st, K);
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) mix2_t<true>(st, K);
+    flush2(st);
+    to_words2(st, d0, d1);
+}
+
 // Hash::from_bytes for an arbitrary message (src/hash.rs:7-30); single lane, used by the
 // Fiat-Shamir and index-sampling kernels (transcripts of a few hundred bytes).
 SMI_HD void hash_bytes(const uint8_t *msg, size_t len, uint32_t d[8]) {

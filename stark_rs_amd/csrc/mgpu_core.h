@@ -167,6 +167,46 @@ SMI_HD void mg_row_open4_write(const uint32_t *cols, uint64_t stride, uint32_t W
     }
 }
 
+// Openings of a tree of coset leaves (include/stark_mi.h, "Out-of-domain sampling over coset leaves"): the section of one
+// group of V columns follows a fold-by-4 FRI layer --
+//   records: t x  tag 2 | u64 4 V | 4 V x u64      (test s: leaf a = top_s mod N / 4, value 4 c + j = column c at a + j N / 4)
+//   paths  : t x  tag 3 | u64 depth | depth x 32   (depth = log2 N - 2, the siblings of leaf a from the leaves up)
+// The groups of one proof travel as a table (coset_open_kernel's argument, deep.hip): where the columns and the tree of
+// N / 4 leaves are, and where the group's section starts in the output.
+struct MgCosetGroup {
+    const uint32_t *cols;
+    uint64_t stride;
+    const uint8_t *nodes;
+    uint64_t out_at;
+    uint32_t V, reserved0;
+};
+struct MgCosetTable {
+    MgCosetGroup g[3];
+};
+SMI_HD uint64_t mg_coset_open_bytes(uint32_t V, uint32_t t, uint32_t log_N) {
+    return (uint64_t)t * (9 + 32ull * V) + (uint64_t)t * (9 + 32ull * (log_N - 2));
+}
+// the record and the path of test s of one group, by n_lanes cooperating lanes; out: the start of the group's section
+SMI_HD void mg_coset_open_write(const MgCosetGroup &G, uint32_t log_N, uint64_t top_index, uint32_t s, uint32_t t, uint8_t *out, uint32_t lane,
+                                uint32_t n_lanes) {
+    const uint32_t depth = log_N - 2, cnt = 4 * G.V;
+    const uint64_t q = 1ull << depth, a = top_index % q, rec = 9 + 8ull * cnt, prec = 9 + 32ull * depth;
+    uint8_t *row = out + (uint64_t)s * rec;
+    uint8_t *path = out + (uint64_t)t * rec + (uint64_t)s * prec;
+    if (lane == 0) {
+        row[0] = 2;
+        mg_put_u64(row + 1, cnt);
+        path[0] = 3;
+        mg_put_u64(path + 1, depth);
+    }
+    for (uint32_t i = lane; i < cnt; i += n_lanes) mg_put_u64(row + 9 + 8ull * i, G.cols[(uint64_t)(i >> 2) * G.stride + a + (uint64_t)(i & 3) * q]);
+    for (uint32_t b = lane; b < 32 * depth; b += n_lanes) {   // byte b & 31 of the sibling on level b >> 5 (level l starts at 2 q - (2 q >> l))
+        const uint32_t l = b >> 5;
+        const uint64_t sib = (a >> l) ^ 1;
+        path[9 + b] = G.nodes[(2 * q - ((2 * q) >> l) + sib) * 32 + (b & 31)];
+    }
+}
+
 // column_open_kernel on the context's stream (stark.hip; mgpu.hip and air.hip call it too)
 struct smi_ctx;
 int launch_column_open(smi_ctx *ctx, const MgSide *d_cols, uint32_t W, const uint64_t *d_top, uint32_t t, int rank, uint8_t *d_out);

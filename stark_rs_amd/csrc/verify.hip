@@ -1390,3 +1390,116 @@ int smi_air_verify_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
     if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
     return settle(air_verify_deep_xargs_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
 }
+
+// Verifiers of smi_dev_air_prove_deep_fold4 and smi_dev_air_prove_deep_xargs_fold4 (include/stark_mi.h, "Out-of-domain
+// sampling over coset leaves"), one function over the list (xargs == nullptr: a plain AIR).  The checks of
+// air_verify_deep_impl / air_verify_deep_xargs_impl in their order with their sentences up to and including the consistency
+// check at z; the refusal of a shape without a fold; the fold-by-4 FRI walk with the proof of work, which hands out the
+// layer-0 coset records; then the opening sections group by group (deep_core.h deep_coset_parse: the exact length, every
+// record's and every path's tag and count), every record hashed as it stands to its leaf and authenticated at a = top mod
+// N / 4 (auth_section over a tree of N / 4 leaves), the canonical check, and Q at the coset's four points against the
+// layer-0 record (deep_coset_q_matches).
+const OpeningWords DEEP_FOLD4_WORDS = {DEEP_FOLD4_SENTENCES[0], DEEP_FOLD4_SENTENCES[1], DEEP_FOLD4_SENTENCES[2],
+                                       DEEP_FOLD4_SENTENCES[3], DEEP_FOLD4_SENTENCES[4], DEEP_FOLD4_SENTENCES[5]};   // deep_core.h
+const OpeningWords DEEP_ARGS_FOLD4_WORDS = {DEEP_ARGS_FOLD4_SENTENCES[0], DEEP_ARGS_FOLD4_SENTENCES[1], DEEP_ARGS_FOLD4_SENTENCES[2],
+                                            DEEP_ARGS_FOLD4_SENTENCES[3], DEEP_ARGS_FOLD4_SENTENCES[4], DEEP_ARGS_FOLD4_SENTENCES[5]};
+static int air_verify_deep_fold4_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint8_t *roots,
+                                      const uint8_t *proof, size_t proof_len, int *accept, uint32_t grind) {
+    std::string why;
+    uint32_t D = 0;
+    const int vrc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why) : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    if (xargs) {
+        const int prc = xargs_periodic_check(ctx->fs.F.p, air, cfg->log_n, &why);
+        if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
+    }
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs ? xargs->count : 0, logN = cfg->log_n + cfg->log_blowup;
+    const uint64_t NW = (uint64_t)W + K + 2 * (uint64_t)A;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    const size_t n_ood = deep_args_record(W, A, D);
+    size_t end = 0;
+    std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count_fold4(fc), &end);
+    if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, DEEP_BAD_RECORD);
+    std::vector<uint64_t> ood(n_ood);
+    for (size_t i = 0; i < n_ood; i++)
+        if ((ood[i] = get_u64(objs[0].p + 8 * i)) >= p) return reject(ctx, accept, DEEP_RECORD_CANONICAL);
+    Transcript tr;
+    std::vector<uint64_t> ch, weights, gammas;
+    uint64_t zr[4];
+    if (xargs) {
+        transcript_perm_challenges(tr, roots, &ch);
+        transcript_args_weights(tr, roots + 32, W, K, A, &weights);
+        deep_args_transcript_z(tr, roots + 64, NW, zr);
+    } else {
+        deep_transcript_weights(tr, roots, W, K, &weights);
+        deep_transcript_z(tr, roots + 32, W, K, zr);
+    }
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return reject(ctx, accept, DEEP_Z_IN_BASE_FIELD);
+    FqH lhs, rhs;
+    if (xargs) {
+        deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
+        deep_xargs_ood_sides(p, g, cfg, air, xargs, D, w_n, ch.data(), weights.data(), z, ood.data(), &lhs, &rhs);
+        if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_ARGS_INCONSISTENT);
+    } else {
+        deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
+        deep_ood_sides(p, g, cfg, air, D, w_n, weights.data(), z, ood.data(), &lhs, &rhs);
+        if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_INCONSISTENT);
+    }
+    if (fri_layout_fold4(fc).F == 0) return reject(ctx, accept, DEEP_FOLD4_NO_LAYER);
+    objs.erase(objs.begin());
+    std::vector<uint64_t> top, coset;   // coset: the 16 values of every layer-0 record
+    size_t used = 0;
+    SMI_TRY(fri_walk_fold4(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &coset, &used, grind));
+    *accept = 0;
+    const OpeningWords &say = xargs ? DEEP_ARGS_FOLD4_WORDS : DEEP_FOLD4_WORDS;
+    const DeepGroups gr = deep_groups(W, A, D);
+    const uint8_t *sec = proof + end;
+    std::vector<uint64_t> vals[3];
+    size_t at[3] = {0, 0, 0};
+    switch (deep_coset_parse(sec, proof_len - end, gr, t, logN, vals, at)) {
+        case DEEP_COSET_LENGTH: return reject(ctx, accept, say.length);
+        case DEEP_COSET_RECORD: return reject(ctx, accept, say.row);
+        case DEEP_COSET_PATH: return reject(ctx, accept, say.path);
+        default: break;
+    }
+    const uint64_t q = N / 4;
+    std::vector<uint64_t> pos(t);
+    for (uint64_t s = 0; s < t; s++) pos[s] = top[s] % q;
+    for (uint32_t k = 0; k < gr.G; k++) SMI_TRY(auth_section(ctx, accept, say, sec + at[k], t, 4 * gr.V[k], logN - 2, pos, roots + 32 * k));
+    for (uint32_t k = 0; k < gr.G; k++)
+        for (uint64_t x : vals[k])
+            if (x >= p) return reject(ctx, accept, say.canonical);
+    const uint32_t iota = (uint32_t)powm(fc.omega, q, p);
+    for (uint64_t s = 0; s < t; s++) {
+        const uint64_t *rec[3] = {nullptr, nullptr, nullptr};
+        for (uint32_t k = 0; k < gr.G; k++) rec[k] = &vals[k][s * 4 * (size_t)gr.V[k]];
+        const uint32_t x_a = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[s], p), p);
+        if (!deep_coset_q_matches(p, g, W, A, D, w_n, x_a, iota, z, ood.data(), gammas.data(), rec, &coset[16 * s])) return reject(ctx, accept, say.composition);
+    }
+    *accept = 1;
+    return SMI_OK;
+}
+int smi_air_verify_deep_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
+                              int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_fold4_impl(ctx, cfg, (const smi_air *)air, nullptr, roots, proof, proof_len, accept, grind_bits));
+}
+int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                                    size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !xargs || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_fold4_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
+}

@@ -384,6 +384,11 @@ class Engine:
         """One tree whose leaf i is Hash::from_field_elements(row i) over n_cols columns."""
         self._ck(self.L.smi_dev_merkle_build_rows(self.h, vp(d_cols), n_cols, col_stride, n, vp(d_nodes)))
 
+    def dev_merkle_build_cosets(self, d_cols, n_cols, col_stride, n, d_nodes):
+        """One tree of n / 4 leaves: leaf i is Hash::from_field_elements of the 4 * n_cols values (column c at index
+        i + j * n / 4 is value 4 c + j) of the coset {i, i + n/4, i + n/2, i + 3n/4}; n_cols is 1 .. 64."""
+        self._ck(self.L.smi_dev_merkle_build_cosets(self.h, vp(d_cols), n_cols, col_stride, n, vp(d_nodes)))
+
     def dev_hash_bytes(self, d_msg, length, d_out32):
         self._ck(self.L.smi_dev_hash_bytes(self.h, vp(d_msg), length, vp(d_out32)))
 
@@ -741,7 +746,7 @@ class Engine:
                                              N if seg_stride is None else seg_stride, za, oa, ca, vp(d_out), N if out_stride is None else out_stride))
 
     def _dev_air_prove_deep(self, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
-                            fill_multiplicities, folding):
+                            fill_multiplicities, folding, coset_leaves=False):
         self._check_deep(a, row_leaves, ext, folding, fill_multiplicities)
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
         _d, D = air_plan_deep(self.p, a, cfg)
@@ -754,8 +759,9 @@ class Engine:
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(t, 1), dtype=np.uint64)
         stage = (C.c_double * 7)()
-        self._ck(self.L.smi_dev_air_prove_deep(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, ood.ctypes.data, C.byref(proof),
-                                               C.byref(plen), top.ctypes.data, stage if timed else None, 0 if grind_bits is None else grind_bits))
+        prove = self.L.smi_dev_air_prove_deep_fold4 if coset_leaves else self.L.smi_dev_air_prove_deep
+        self._ck(prove(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), roots.ctypes.data, ood.ctypes.data, C.byref(proof),
+                       C.byref(plen), top.ctypes.data, stage if timed else None, 0 if grind_bits is None else grind_bits))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]],
@@ -798,7 +804,7 @@ class Engine:
                                                   vp(d_out), N if out_stride is None else out_stride))
 
     def _dev_air_prove_deep_args(self, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
-                                 fill_multiplicities, folding, deep):
+                                 fill_multiplicities, folding, deep, coset_leaves=False):
         xa = self._check_deep_args(a, row_leaves, ext, folding, deep)
         A = xa.count
         lookups = [i for i in range(A) if xa.arg[i].kind == 1]
@@ -820,9 +826,9 @@ class Engine:
         proof, plen, mask = vp(), C.c_size_t(), C.c_uint32()
         top = np.zeros(max(t, 1), dtype=np.uint64)
         stage = (C.c_double * 8)()
-        self._ck_perm(self.L.smi_dev_air_prove_deep_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xa), vp(d_trace_cols), roots.ctypes.data,
-                                                          ood.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
-                                                          0 if grind_bits is None else grind_bits, C.byref(mask)))
+        prove = self.L.smi_dev_air_prove_deep_xargs_fold4 if coset_leaves else self.L.smi_dev_air_prove_deep_xargs
+        self._ck_perm(prove(self.h, C.byref(cfg), C.byref(a), C.byref(xa), vp(d_trace_cols), roots.ctypes.data, ood.ctypes.data, C.byref(proof),
+                            C.byref(plen), top.ctypes.data, stage if timed else None, 0 if grind_bits is None else grind_bits, C.byref(mask)))
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         closes = [bool(mask.value >> i & 1) for i in range(A)]
@@ -834,6 +840,28 @@ class Engine:
             out["stage_ms"] = dict(zip(("lde", "commit", "args", "compose", "segments", "ood", "fri", "open"), [float(x) for x in stage]))
         return out
 
+    # ---- out-of-domain sampling over coset leaves (include/stark_mi.h, "Out-of-domain sampling over coset leaves")
+    @staticmethod
+    def _check_coset_leaves(row_leaves, ext, deep, deep_args):
+        if not (row_leaves and ext):
+            raise ValueError("coset_leaves=True runs over the row-committed extension proof: pass row_leaves=True, ext=True")
+        if deep and deep_args:
+            raise ValueError("coset_leaves=True takes exactly one of deep=True and deep_args=True, not both")
+        if not (deep or deep_args):
+            raise ValueError("coset_leaves=True commits the groups of a DEEP proof: pass deep=True (a plain AIR) or deep_args=True (an argument list)")
+
+    def air_deep_fold4_layout(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_deep_fold4_layout -> (folds, proof bytes) of dev_air_prove(deep=True, coset_leaves=True).  Host only."""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_deep_fold4_layout(self.p, self._air(air), cfg)
+
+    def air_deep_args_fold4_layout(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_deep_xargs_fold4_layout for air's argument list -> (folds, proof bytes) of dev_air_prove(deep_args=True,
+        coset_leaves=True).  Host only."""
+        a = self._args_of(air, "air_deep_args_fold4_layout")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_deep_args_fold4_layout(self.p, a, xargs_of(a), cfg)
+
     def _check_air_folding(self, a, folding, row_leaves, ext):
         _check_folding(folding)
         if folding == 4 and not (row_leaves and ext):
@@ -843,7 +871,7 @@ class Engine:
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
                       timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2, deep=False,
-                      deep_args=False):
+                      deep_args=False, coset_leaves=False):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -870,14 +898,21 @@ class Engine:
         deep_args=True (needs row_leaves=True, ext=True, folding=2 and an add_permutation / add_lookup list; ValueError otherwise
         and together with deep=True): smi_dev_air_prove_deep_xargs -- out-of-domain sampling for an argument list (include/
         stark_mi.h, "Out-of-domain sampling with an argument list").  column_roots is (3, 32), the result has "ood" (2 W + 2 A + D
-        elements) and "closes", stage_ms has eight stages, fill_multiplicities works as for the list prover."""
+        elements) and "closes", stage_ms has eight stages, fill_multiplicities works as for the list prover.
+        coset_leaves=True (needs row_leaves=True, ext=True and exactly one of deep=True and deep_args=True; ValueError naming
+        what is missing otherwise): smi_dev_air_prove_deep_fold4 / smi_dev_air_prove_deep_xargs_fold4 -- the same DEEP proof
+        with every group of columns committed as a tree of coset leaves and FRI at folding factor 4 (include/stark_mi.h,
+        "Out-of-domain sampling over coset leaves").  The result has the keys of the variant it stands beside.  folding stays 2
+        on these calls: deep=True, folding=4 and deep_args=True, folding=4 keep raising ValueError."""
         a = self._air(air)
+        if coset_leaves:
+            self._check_coset_leaves(row_leaves, ext, deep, deep_args)
         if deep_args:
             return self._dev_air_prove_deep_args(a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed,
-                                                 check, row_leaves, ext, grind_bits, fill_multiplicities, folding, deep)
+                                                 check, row_leaves, ext, grind_bits, fill_multiplicities, folding, deep, coset_leaves)
         if deep:
             return self._dev_air_prove_deep(a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed, check,
-                                            row_leaves, ext, grind_bits, fill_multiplicities, folding)
+                                            row_leaves, ext, grind_bits, fill_multiplicities, folding, coset_leaves)
         self._check_air_folding(a, folding, row_leaves, ext)
         if self._xargs(a) is not None:
             if not (row_leaves and ext):
@@ -1022,7 +1057,8 @@ class Engine:
         return out
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
-                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False, deep_args=False):
+                   lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False, deep_args=False,
+                   coset_leaves=False):
         """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
@@ -1032,7 +1068,11 @@ class Engine:
         or periodic members).
         folding=4: smi_air_verify_ext_fold4, under the conditions of dev_air_prove(folding=4).
         deep=True: smi_air_verify_deep, under the conditions of dev_air_prove(deep=True); column_roots is root_1 then root_2.
-        deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots."""
+        deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots.
+        coset_leaves=True: smi_air_verify_deep_fold4 / smi_air_verify_deep_xargs_fold4, under the conditions of
+        dev_air_prove(coset_leaves=True); folding stays 2."""
+        if coset_leaves:
+            self._check_coset_leaves(row_leaves, ext, deep, deep_args)
         if deep_args:
             a = self._air(air)
             xa = self._check_deep_args(a, row_leaves, ext, folding, deep)
@@ -1041,8 +1081,9 @@ class Engine:
             if roots.size != 96:
                 raise StarkMiError(-50, "air_verify(deep_args=True) takes three 32-byte roots")
             acc = C.c_int()
-            self._ck(self.L.smi_air_verify_deep_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xa), roots.ctypes.data, proof, len(proof), C.byref(acc),
-                                                      0 if grind_bits is None else grind_bits))
+            verify = self.L.smi_air_verify_deep_xargs_fold4 if coset_leaves else self.L.smi_air_verify_deep_xargs
+            self._ck(verify(self.h, C.byref(cfg), C.byref(a), C.byref(xa), roots.ctypes.data, proof, len(proof), C.byref(acc),
+                            0 if grind_bits is None else grind_bits))
             return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         if deep:
             a = self._air(air)
@@ -1052,8 +1093,8 @@ class Engine:
             if roots.size != 64:
                 raise StarkMiError(-50, "air_verify(deep=True) takes two 32-byte roots")
             acc = C.c_int()
-            self._ck(self.L.smi_air_verify_deep(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc),
-                                                0 if grind_bits is None else grind_bits))
+            verify = self.L.smi_air_verify_deep_fold4 if coset_leaves else self.L.smi_air_verify_deep
+            self._ck(verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc), 0 if grind_bits is None else grind_bits))
             return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         self._check_air_folding(self._air(air), folding, row_leaves, ext)
         if self._xargs(self._air(air)) is not None:
@@ -1249,6 +1290,27 @@ def air_plan_deep_args(p, air, xargs, cfg, with_length=False):
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return (d.value, D.value, n.value) if with_length else (d.value, D.value)
+
+
+def air_deep_fold4_layout(p, air, cfg):
+    """smi_air_deep_fold4_layout (host only) -> (folds, proof bytes) for cfg's number of colinearity tests.  air: a flattened
+    _lib.Air"""
+    folds, n = C.c_uint64(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_deep_fold4_layout(p, C.byref(cfg), C.byref(air), C.byref(folds), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return int(folds.value), int(n.value)
+
+
+def air_deep_args_fold4_layout(p, air, xargs, cfg):
+    """smi_air_deep_xargs_fold4_layout (host only) -> (folds, proof bytes).  air: a flattened _lib.Air; xargs: a _lib.AirXArgs"""
+    folds, n = C.c_uint64(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_deep_xargs_fold4_layout(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(folds), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return int(folds.value), int(n.value)
 
 
 def air_plan_perm(p, air, perm, cfg):

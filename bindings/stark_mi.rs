@@ -331,6 +331,12 @@ extern "C" {
     pub fn smi_air_deep_xargs_fold4_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
     pub fn smi_dev_air_prove_deep_xargs_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_trace_cols: *const u32, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
     pub fn smi_air_verify_deep_xargs_fold4(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_deep_zk(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, degree: *mut u32, segments: *mut u32, k_t: *mut u32, k_s: *mut u32) -> c_int;
+    pub fn smi_dev_random_fill(ctx: *mut smi_ctx, seed: *const u8, stream_id: u64, d_out: *mut u32, count: usize) -> c_int;
+    pub fn smi_dev_zk_segments(ctx: *mut smi_ctx, d_h: *const u32, h_stride: usize, h_len: usize, log_n: u32, k_s: u32, n_segments: u32, d_rho: *const u32, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_air_deep_zk_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
+    pub fn smi_dev_air_prove_deep_zk(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *mut u32, seed: *const u8, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
+    pub fn smi_air_verify_deep_zk(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;

@@ -1303,6 +1303,91 @@ int smi_dev_air_prove_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, c
 int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
                                     size_t proof_len, int *accept, uint32_t grind_bits);
 
+/* ---- Zero-knowledge DEEP proofs ----------------------------------------------------------------------------------------
+ * None of the proofs above hides the trace: opened rows are raw values of the trace polynomials, digests are unsalted, and
+ * the segments and every FRI layer are functions of the witness.  A zero-knowledge variant of "Out-of-domain sampling over
+ * coset leaves" needs randomness inside the committed polynomials, a different split of the composition, one more polynomial
+ * in FRI and salted leaves.  This section adds that variant and the parts it is made of: the device random generator, the
+ * plan over the derived AIR, and the masked split.  Notation is that of "Out-of-domain sampling"; t = the number of
+ * colinearity tests, and a test opens one layer-0 coset of 4 points.
+ * Random residues (smi_dev_random_fill).  The project's 32-byte hash in counter mode.  Element i of a stream is
+ *     u64_le(digest[8 k .. 8 k + 7]) mod p,  k = i mod 4,  digest = Hash::from_bytes(message),  message (48 bytes) =
+ *     seed[0 .. 31] | stream_id as 8 little-endian bytes | floor(i / 4) as 8 little-endian bytes.
+ *   p < 2^30 and the word is uniform on 2^64 values, so an element's bias is below p / 2^64 < 2^-34.  Streams with different
+ *   stream_id, or different seeds, are independent under the random-oracle reading of the hash; the same (seed, stream_id,
+ *   count) gives the same words on every call, whatever the alignment of d_out.  One launch, no atomics: a lane hashes the
+ *   counters 2 l and 2 l + 1 the way the grinding search hashes transcript | nonce (the 40 leading bytes travel as a
+ *   midstate) and stores elements 8 l .. 8 l + 7 with two 16-byte stores when d_out is 16-byte aligned.
+ * Trace randomisers and the derived AIR (smi_air_plan_deep_zk).  k_t = 8 t + 8.  The statement covers the first n - k_t
+ *   rows; a prover overwrites the last k_t rows of every trace column with random residues, which makes k_t off-domain
+ *   functionals of f_c jointly uniform: f_c at the 4 t queried points, f_c at w times those points (through H), and f_c(z),
+ *   f_c(z w), four base-field functionals each.  Transitions are exempt on rows n - k_t - 1 .. n - 2 (row n - 1 already is)
+ *   without a new composition kernel: the library derives an AIR that differs from the caller's in one more periodic column
+ *   of period n, index Q, holding E(tau w^r) for E(x) = prod_{r = n - k_t - 1}^{n - 2} (x - tau w^r), and in every term of
+ *   every transition constraint carrying that column as one more factor (variables 2 W + Q + j move up by one).  The
+ *   interpolant of those n values is E itself, of degree k_t, so smi_dev_air_compose_ext, the periodic tables and a verifier's
+ *   pi_j(z) do the work unchanged, and the derived AIR holds on every row pair of an honest trace whatever the tail holds.
+ *   d and D are smi_air_plan_deep's for the derived AIR: a periodic factor is charged like a column, which is what the
+ *   true degree (d - 1) n + k_t needs once D is a power of two.
+ * Masked segments (smi_dev_zk_segments).  H_j(x_i) one by one is a global function of the witness, so the split changes:
+ *   k_s = 4 t + 1 (a segment is opened at 4 t points and at z), L = n - k_s, D' = ceil(D n / L), 4 D' + 5 <= 64 (the
+ *   segments, four mask columns and a salt column in one coset leaf).  From the 4 coefficient columns of H one streaming
+ *   launch writes 4 D' columns of exactly n coefficients, column 4 j + e = coordinate e of
+ *     H~_j[m]     = H[j L + m] - rho_{j-1}[m]   for m < L   (the rho term for m < k_s only; H reads 0 at and above h_len)
+ *     H~_j[L + m] = rho_j[m]                    for m < k_s
+ *   with rho_{-1} = rho_{D'-1} = 0 and rho_j (j < D' - 1) k_s coefficients of F_q, coordinate e of rho_j at
+ *   d_rho[(4 j + e) k_s ..].  Then sum_j x^{j L} H~_j = H identically, every H~_j has degree < n, and any D' - 1 of them at
+ *   k_s points are uniform.  16-byte accesses when d_h and d_out are 16-byte aligned and both strides are multiples of 4,
+ *   4-byte accesses with the same values otherwise.
+ * Refused by the plan with SMI_ERR_BAD_ARG and a sentence (smi_air_last_error) that starts "zk deep:": k_t >= n / 2; a
+ *   boundary point on a row >= n - k_t; 4 D' + 5 > 64; W + 1 > 64 (the trace tree's salt column); and whatever
+ *   smi_air_plan_deep refuses for the derived AIR, in its words.
+ * The proof (smi_dev_air_prove_deep_zk, smi_air_verify_deep_zk).  "Out-of-domain sampling over coset leaves" for a plain AIR
+ *   with D -> D' and:
+ *   - random values.  Everything comes from smi_dev_random_fill under the caller's seed, so a proof is a pure function of
+ *     (trace, seed); the seed is never part of a proof.  Streams: 1 = the randomiser rows (column c takes elements
+ *     c k_t .. (c + 1) k_t - 1 in its rows n - k_t .. n - 1; d_trace_cols is overwritten IN PLACE, as
+ *     smi_dev_lookup_multiplicities writes in place), 2 = the salt column of tree 1 (N residues), 3 = rho (4 (D' - 1) k_s),
+ *     4 = the mask R (coordinate e takes elements e n .. (e + 1) n - 1 as its n coefficients), 5 = the salt column of tree 2;
+ *   - tree 1 is smi_dev_merkle_build_cosets over the W extended trace columns and the salt column (W + 1 <= 64); tree 2 over
+ *     the 4 D' extended segment columns, the 4 extended columns of R and the salt column.  A salt column is N raw residues,
+ *     no codeword: 4 salt values, about 120 bits, in every leaf;
+ *   - the transcript keeps the DEEP shape: root_1, the composition weights, root_2, z, the record of 4 (2 W + D') values
+ *     (u, v, s_j = H~_j(z)), as many gammas, fold-by-4 FRI with the nonce record.  R has no DEEP quotient and is not opened
+ *     at z;
+ *   - FRI runs on Q' = Q + R, Q = smi_dev_deep_compose with D' segments; R is added by one small streaming launch
+ *     (zk_mask_add_kernel) after the DEEP compose launch, which stays as it is;
+ *   - the opening sections hold records of 4 (W + 1) and 4 (4 D' + 5) values.
+ * Proof bytes (smi_air_deep_zk_layout): 9 + 32 (2 W + D') + len_FRI4(N, B, t) + sum over V in {W + 1, 4 D' + 5} of
+ *   [ t (9 + 32 V) + t (9 + 32 (log2 N - 2)) ].
+ * Verifier (host), in this order, every sentence starting "zk deep": the record's tag and count; canonical coordinates; z
+ *   outside the base field; the consistency check -- the left side of smi_air_verify_deep's over the DERIVED AIR (the
+ *   exemption column evaluated at z and z w like any periodic column) against sum_j z^(j L) s_j; a shape without a fold; the
+ *   fold-by-4 FRI walk; the sections' exact length, tags and counts; every record hashed as it stands (salts included) and
+ *   its path; canonical values (the salts are not looked at); Q + R recomputed at the four coset points against the
+ *   layer-0 record.  A proof of smi_dev_air_prove_deep_fold4 is rejected here and a proof of this variant by
+ *   smi_air_verify_deep_fold4: their records differ in length (D' > D).
+ * Left out: argument lists; row leaves / fold 2; smi_mgpu_* twins; an AIR digest in the transcript. */
+/* Host only: *degree = d and *segments = D' for the derived AIR, *k_t and *k_s for cfg->num_colinearity_tests (outputs are
+ * optional). */
+int smi_air_plan_deep_zk(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments, uint32_t *k_t, uint32_t *k_s);
+/* d_out: count u32 residues (count <= 2^34).  Asynchronous on the context's stream. */
+int smi_dev_random_fill(smi_ctx *ctx, const uint8_t seed[32], uint64_t stream_id, uint32_t *d_out, size_t count);
+/* d_h: coordinate e of H's coefficients at d_h + e h_stride, h_len <= D' (n - k_s) of them; d_rho: 4 (D' - 1) k_s words (may
+ * be null when n_segments == 1); d_out: column c at d_out + c out_stride, out_stride >= n = 2^log_n.  log_n in 2 .. 27,
+ * 1 <= k_s < n / 2, 1 <= n_segments <= 14.  Asynchronous on the context's stream. */
+int smi_dev_zk_segments(smi_ctx *ctx, const uint32_t *d_h, size_t h_stride, size_t h_len, uint32_t log_n, uint32_t k_s, uint32_t n_segments,
+                        const uint32_t *d_rho, uint32_t *d_out, size_t out_stride);
+/* Host only: the plan above, then *folds = F and the proof length in bytes. */
+int smi_air_deep_zk_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint64_t *folds, size_t *proof_len);
+/* smi_dev_air_prove_deep_fold4's parameters with the seed; d_trace_cols is overwritten in its last k_t rows; roots (optional)
+ * root_1, root_2, 64 bytes; stage_ms (optional) nine values {random, lde, commit, compose, segments, ood, mask, fri, open}.
+ */
+int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots,
+                              uint64_t *ood, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
+int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
+                           int *accept, uint32_t grind_bits);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous
  * blocks (rank g holds [g*N/G, (g+1)*N/G)), and the build-defined trace -> proof composition of

@@ -285,6 +285,12 @@ def lib():
                                                      vp, vp, C.c_uint32, u32p]),
         "smi_air_verify_deep_xargs_fold4": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32),
                                                   C.c_uint32]),
+        "smi_air_plan_deep_zk": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), u32p, u32p, u32p, u32p]),
+        "smi_dev_random_fill": (i32, [vp, C.c_char_p, C.c_uint64, vp, sz]),
+        "smi_air_deep_zk_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), u64p, C.POINTER(sz)]),
+        "smi_dev_air_prove_deep_zk": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
+        "smi_air_verify_deep_zk": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
+        "smi_dev_zk_segments": (i32, [vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

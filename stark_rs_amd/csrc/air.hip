@@ -28,6 +28,7 @@
 #include "lookup_core.h"
 #include "perm_core.h"
 #include "xargs_core.h"
+#include "zk_core.h"
 
 template <int P>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
@@ -331,6 +332,20 @@ int smi_air_deep_xargs_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const 
     const int rc = deep_xargs_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, nullptr, &D, &g_air_err);
     if (rc != SMI_OK) return rc;
     const size_t len = deep_fold4_proof_len(cfg, ((const smi_air_xargs *)xargs)->count, D, folds);
+    if (proof_len) *proof_len = len;
+    return SMI_OK;
+}
+// zero-knowledge DEEP proofs (zk_core.h): the plan over the derived AIR
+int smi_air_plan_deep_zk(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments, uint32_t *k_t, uint32_t *k_s) {
+    g_air_err.clear();
+    return zk_plan(p, cfg, (const smi_air *)air, degree, segments, k_t, k_s, &g_air_err);
+}
+int smi_air_deep_zk_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint64_t *folds, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t Dp = 0;
+    const int rc = zk_plan(p, cfg, (const smi_air *)air, nullptr, &Dp, nullptr, nullptr, &g_air_err);
+    if (rc != SMI_OK) return rc;
+    const size_t len = zk_proof_len(cfg, Dp, folds);
     if (proof_len) *proof_len = len;
     return SMI_OK;
 }

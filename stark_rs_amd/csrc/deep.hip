@@ -26,6 +26,7 @@
 #include "mgpu_core.h"
 #include "row4_dev.h"
 #include "xargs_core.h"
+#include "zk_core.h"
 
 // four consecutive words from `at` (a multiple of 4): one 16-byte access where the layout allows and all four lie below len
 template <bool VEC>
@@ -895,4 +896,192 @@ int smi_dev_air_prove_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, c
     DeviceGuard dg__(ctx);
     return deep_fold4_prove(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices,
                             stage_ms, grind_bits, closes);
+}
+
+// ---- zero-knowledge DEEP proofs (include/stark_mi.h, "Zero-knowledge DEEP proofs")
+// deep_fold4_prove for a plain AIR with the four changes of the section: the last k_t rows of the trace overwritten in place
+// and the derived AIR composed in the caller's place; the masked split (zk_segments_kernel) for the slices of n; the mask
+// polynomial R extended with the segments and added to the DEEP codeword by zk_mask_add_kernel; one salt column in each tree.
+// Every random value comes from smi_dev_random_fill under the caller's seed and one of the ZK_STREAM_* identifiers.
+int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots_out,
+                              uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    const smi_air *air0 = (const smi_air *)air_;
+    if (!ctx || !cfg || !air0 || !d_trace_cols || !seed || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(deep_field_check(ctx));
+    uint32_t D = 0, Dp = 0, kt = 0, ks = 0;
+    {
+        std::string why;
+        const int rc = zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, &kt, &ks, &why, &D);
+        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    }
+    const uint32_t W = cfg->n_cols, K = air0->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
+    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    if (fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, ZK_NO_LAYER);
+    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N, q = N / 4;
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
+    const uint32_t V1 = W + 1, V2 = 4 * Dp + 5, n_stages = 9;
+    ZkAir Z;
+    {
+        std::string why;
+        const int rc = zk_derive_air(p, w_n, cfg, air0, &Z, &why);
+        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    }
+    const smi_air *air = &Z.air;
+    AirHost H;
+    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
+    SMI_TRY(arena_reset(ctx));
+    struct Events {   // destroyed on every return path
+        hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } evs;
+    const bool timed = stage_ms != nullptr;
+    if (timed)
+        for (uint32_t i = 0; i <= n_stages; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
+    uint32_t marks = 0;
+    auto mark = [&]() {
+        if (timed) (void)hipEventRecord(evs.ev[marks], ctx->stream);
+        marks++;
+    };
+
+    const size_t n_ood = 4 * (2 * (size_t)W + Dp);
+    const size_t tree_bytes = 2 * q * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
+    const size_t part_a = deep_eval_part_bytes(W, n, 2), part_b = deep_eval_part_bytes(Dp, n, 1);
+    uint32_t *d_rows = (uint32_t *)arena_alloc(ctx, (size_t)W * kt * 4);
+    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)V1 * N * 4);     // the trace, then the salt column
+    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);               // H, then Q, then Q + R
+    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);               // the coefficients of H's coordinates
+    uint32_t *d_rho = (uint32_t *)arena_alloc(ctx, (size_t)4 * Dp * ks * 4);
+    uint32_t *d_sc = (uint32_t *)arena_alloc(ctx, (size_t)(V2 - 1) * n * 4);   // n coefficients a column: 4 D' of the segments, 4 of R
+    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, (size_t)V2 * N * 4);     // their extensions, then the salt column
+    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)W * n * 4);
+    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)(W + K));
+    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
+    uint8_t *tree[2] = {(uint8_t *)arena_alloc(ctx, tree_bytes), (uint8_t *)arena_alloc(ctx, tree_bytes)};
+    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
+    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
+    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * W + 16 * Dp) * 4);   // columns at z and z w | H~_{j,e} at z, e-major
+    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_tab_words(W, Dp) * 4);
+    uint32_t *d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
+    uint32_t *d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
+    if (!d_rows || !d_lde || !d_cw || !d_hc || !d_rho || !d_sc || !d_seg || !d_coef || !d_weights || !d_blob || !tree[0] || !tree[1] || !d_tab2 || !d_tab1 ||
+        !d_part || !d_res || !d_ctab || !d_ptab || !d_pvals)
+        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: device memory");
+    auto root_of = [&](uint32_t k, uint8_t *dst) { return hipMemcpyAsync(dst, tree[k] + (2 * q - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream); };
+    mark();
+    // the randomisers: column c takes elements c k_t .. (c + 1) k_t - 1 of their stream in its last k_t rows; the two salts
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_ROWS, d_rows, (size_t)W * kt));
+    HIP_TRY(ctx, hipMemcpy2DAsync(d_trace_cols + (n - kt), n * 4, d_rows, (size_t)kt * 4, (size_t)kt * 4, W, hipMemcpyDeviceToDevice, ctx->stream));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT1, d_lde + (size_t)W * N, N));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT2, d_seg + (size_t)(V2 - 1) * N, N));
+    mark();
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
+    mark();
+    SMI_TRY(launch_merkle_cosets(ctx, d_lde, V1, N, N, tree[0]));
+    mark();
+    // root_1 -> the composition weights
+    uint8_t roots[64];
+    HIP_TRY(ctx, root_of(0, roots));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
+    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for the values at z
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    Transcript tr;
+    std::vector<uint64_t> weights, gammas;
+    deep_transcript_weights(tr, roots, W, K, &weights);
+    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
+    mark();
+    // the masked segments and R as coefficients, one batched extension, the second tree
+    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
+    if (Dp > 1) SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_RHO, d_rho, (size_t)4 * (Dp - 1) * ks));
+    SMI_TRY(smi_dev_zk_segments(ctx, d_hc, N, (size_t)D * n, log_n, ks, Dp, d_rho, d_sc, n));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_MASK, d_sc + (size_t)4 * Dp * n, 4 * n));
+    for (uint32_t c = 0; c < V2 - 1; c += 4)
+        SMI_TRY(dev_ntt(ctx, d_sc + (size_t)c * n, d_seg + (size_t)c * N, log_N, n, 4, n, N, 0, cfg->lde_offset, 1));
+    SMI_TRY(launch_merkle_cosets(ctx, d_seg, V2, N, N, tree[1]));
+    mark();
+    // root_2 -> z
+    HIP_TRY(ctx, root_of(1, roots + 32));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t zr[4];
+    deep_transcript_z(tr, roots + 32, W, K, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
+    if (roots_out) memcpy(roots_out, roots, 64);
+    // u, v = f(z), f(z w); s_j = H~_j(z)
+    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
+    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)W + 16 * (size_t)Dp);
+    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
+    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W, n, n, 2, d_tab2, d_part, d_res));
+    uint32_t *d_sres = d_res + 8 * (size_t)W;
+    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D' segments: D' columns of n coefficients, 4 n apart
+        SMI_TRY(deep_eval_enqueue(ctx, d_sc + (size_t)e * n, Dp, n, 4 * n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * Dp));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> ood(n_ood);
+    const FqH X{{0, 1 % p, 0, 0}};
+    for (uint32_t c = 0; c < W; c++)
+        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
+    for (uint32_t j = 0; j < Dp; j++) {   // s_j = sum_e X^e H~_{j,e}(z)
+        FqH s = fqh(0), xe = fqh(1 % p);
+        for (uint32_t e = 0; e < 4; e++) {
+            const uint32_t *v = &res[8 * (size_t)W + 4 * ((size_t)e * Dp + j)];
+            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
+            xe = fqh_mul(xe, X, p, g);
+        }
+        for (uint32_t e = 0; e < 4; e++) ood[4 * (2 * (size_t)W + j) + e] = s.c[e];
+    }
+    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
+    deep_transcript_gammas(tr, ood.data(), W, K, Dp, &gammas);
+    const FsSeed fseed = tr.seed();
+    deep_compose_build(ctx->fs.F, g, W, Dp, w_n, z, ood.data(), gammas.data(), &ctab);
+    HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_compose_enqueue(ctx, W, Dp, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_seg, N, d_cw, N));
+    mark();
+    SMI_TRY(zk_mask_add_launch(ctx, d_cw, N, d_seg + (size_t)4 * Dp * N, N, N));   // Q' = Q + R
+    mark();
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    FriExtResult xres;
+    SMI_TRY(fri_run_ext_fold4(ctx, &fc, &fseed, d_cw, N, N, false, &xres, grind_bits));
+    std::vector<uint8_t> bytes(9 + 8 * n_ood);
+    bytes[0] = 2;
+    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
+    for (size_t v = 0; v < n_ood; v++)
+        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
+    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
+    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
+    mark();
+    if (cfg->num_colinearity_tests) {
+        const uint32_t t = (uint32_t)cfg->num_colinearity_tests;
+        MgCosetTable tab;
+        memset(&tab, 0, sizeof tab);
+        const size_t ob1 = (size_t)mg_coset_open_bytes(V1, t, log_N), total = ob1 + (size_t)mg_coset_open_bytes(V2, t, log_N);
+        tab.g[0] = MgCosetGroup{d_lde, N, tree[0], 0, V1, 0};
+        tab.g[1] = MgCosetGroup{d_seg, N, tree[1], ob1, V2, 0};
+        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, total);
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: coset openings");
+        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+        coset_open_kernel<<<dim3(t, 2), 64, 0, ctx->stream>>>(tab, log_N, d_top, t, d_open);
+        HIP_TRY(ctx, hipGetLastError());
+        const size_t at = bytes.size();
+        bytes.resize(at + total);
+        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    mark();
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed)
+        for (uint32_t i = 0; i < n_stages; i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    return smi_proof_out(ctx, bytes, proof, proof_len);
 }

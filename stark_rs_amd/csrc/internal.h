@@ -295,6 +295,8 @@ int launch_merkle_fs(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d
 int launch_merkle_src_fs(smi_ctx *ctx, const LeafSrc &src, size_t n, uint8_t *d_nodes, uint32_t *fs_words, uint8_t *proof_slot,
                          uint64_t *alpha_out, bool *done);
 int launch_merkle_rows(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
+// zk.hip: q (four coordinate columns of N words) += r
+int zk_mask_add_launch(smi_ctx *ctx, uint32_t *d_q, size_t q_stride, const uint32_t *d_r, size_t r_stride, size_t N);
 int launch_merkle_cosets(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, size_t col_stride, size_t n, uint8_t *d_nodes);
 int launch_merkle_batch(smi_ctx *ctx, const uint32_t *d_elems, size_t n, uint8_t *d_nodes, uint32_t n_trees, size_t elem_stride,
                         size_t node_stride_bytes, uint32_t row_cols = 0, size_t row_stride = 0);

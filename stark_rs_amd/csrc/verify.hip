@@ -33,6 +33,7 @@
 #include "args_core.h"
 #include "deep_core.h"
 #include "xargs_core.h"
+#include "zk_core.h"
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
@@ -1503,3 +1504,98 @@ int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, cons
     if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
     return settle(air_verify_deep_fold4_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
 }
+
+// Verifier of smi_dev_air_prove_deep_zk (include/stark_mi.h, "Zero-knowledge DEEP proofs"): air_verify_deep_fold4_impl for a
+// plain AIR with the derived AIR on the left of the consistency check and sum_j z^(j L) s_j on its right, groups of W + 1 and
+// 4 D' + 5 columns, the salts hashed as they stand and otherwise ignored, and Q + R at the four coset points.
+const OpeningWords ZK_WORDS = {ZK_SENTENCES[0], ZK_SENTENCES[1], ZK_SENTENCES[2], ZK_SENTENCES[3], ZK_SENTENCES[4], ZK_SENTENCES[5]};   // zk_core.h
+static int air_verify_deep_zk_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
+                                   int *accept, uint32_t grind) {
+    std::string why;
+    uint32_t Dp = 0, ks = 0;
+    const int vrc = zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, nullptr, &ks, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air0->n_constraints, logN = cfg->log_n + cfg->log_blowup;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    ZkAir Z;
+    const int drc = zk_derive_air(p, w_n, cfg, air0, &Z, &why);
+    if (drc != SMI_OK) return smi_fail(ctx, drc, why.c_str());
+    const uint64_t N = 1ull << logN, n = 1ull << cfg->log_n, t = cfg->num_colinearity_tests;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    const size_t n_ood = 4 * (2 * (size_t)W + Dp);
+    size_t end = 0;
+    std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count_fold4(fc), &end);
+    if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, ZK_BAD_RECORD);
+    std::vector<uint64_t> ood(n_ood);
+    for (size_t i = 0; i < n_ood; i++)
+        if ((ood[i] = get_u64(objs[0].p + 8 * i)) >= p) return reject(ctx, accept, ZK_RECORD_CANONICAL);
+    Transcript tr;
+    std::vector<uint64_t> weights, gammas;
+    uint64_t zr[4];
+    deep_transcript_weights(tr, roots, W, K, &weights);
+    deep_transcript_z(tr, roots + 32, W, K, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return reject(ctx, accept, ZK_Z_IN_BASE_FIELD);
+    deep_transcript_gammas(tr, ood.data(), W, K, Dp, &gammas);
+    FqH lhs, unused, rhs = fqh(0), pw = fqh(1 % p);
+    deep_ood_sides(p, g, cfg, &Z.air, 0, w_n, weights.data(), z, ood.data(), &lhs, &unused);
+    const FqH zl = fqh_pow(z, n - ks, p, g);
+    for (uint32_t j = 0; j < Dp; j++) {
+        rhs = fqh_add(rhs, fqh_mul(pw, fqh_of(ood.data() + 4 * (2 * (size_t)W + j), p), p, g), p);
+        pw = fqh_mul(pw, zl, p, g);
+    }
+    if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, ZK_INCONSISTENT);
+    if (fri_layout_fold4(fc).F == 0) return reject(ctx, accept, ZK_NO_LAYER);
+    objs.erase(objs.begin());
+    std::vector<uint64_t> top, coset;   // coset: the 16 values of every layer-0 record
+    size_t used = 0;
+    SMI_TRY(fri_walk_fold4(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &coset, &used, grind));
+    *accept = 0;
+    const OpeningWords &say = ZK_WORDS;
+    const DeepGroups gr = zk_groups(W, Dp);
+    const uint8_t *sec = proof + end;
+    std::vector<uint64_t> vals[3];
+    size_t at[3] = {0, 0, 0};
+    switch (deep_coset_parse(sec, proof_len - end, gr, t, logN, vals, at)) {
+        case DEEP_COSET_LENGTH: return reject(ctx, accept, say.length);
+        case DEEP_COSET_RECORD: return reject(ctx, accept, say.row);
+        case DEEP_COSET_PATH: return reject(ctx, accept, say.path);
+        default: break;
+    }
+    const uint64_t q = N / 4;
+    std::vector<uint64_t> pos(t);
+    for (uint64_t s = 0; s < t; s++) pos[s] = top[s] % q;
+    for (uint32_t k = 0; k < gr.G; k++) SMI_TRY(auth_section(ctx, accept, say, sec + at[k], t, 4 * gr.V[k], logN - 2, pos, roots + 32 * k));
+    for (uint32_t k = 0; k < gr.G; k++)   // every value but the salts, which are the last four of a record
+        for (uint64_t s = 0; s < t; s++)
+            for (size_t i = 0; i + 4 < 4 * (size_t)gr.V[k]; i++)
+                if (vals[k][s * 4 * (size_t)gr.V[k] + i] >= p) return reject(ctx, accept, say.canonical);
+    const uint32_t iota = (uint32_t)powm(fc.omega, q, p);
+    std::vector<uint64_t> trow(W), srow(4 * (size_t)Dp);
+    for (uint64_t s = 0; s < t; s++) {
+        const uint64_t *r1 = &vals[0][s * 4 * (size_t)gr.V[0]], *r2 = &vals[1][s * 4 * (size_t)gr.V[1]];
+        uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[s], p), p);
+        for (uint32_t j = 0; j < 4; j++) {   // column c at point j = value 4 c + j
+            for (uint32_t c = 0; c < W; c++) trow[c] = r1[4 * (size_t)c + j];
+            for (uint32_t c = 0; c < 4 * Dp; c++) srow[c] = r2[4 * (size_t)c + j];
+            const FqH qv = deep_q_at(p, g, W, Dp, w_n, x, z, ood.data(), gammas.data(), trow.data(), srow.data());
+            for (uint32_t e = 0; e < 4; e++)
+                if (fp_add(qv.c[e], (uint32_t)r2[4 * (size_t)(4 * Dp + e) + j], p) != coset[16 * s + 4 * e + j]) return reject(ctx, accept, say.composition);
+            x = host_mulmod(x, iota, p);
+        }
+    }
+    *accept = 1;
+    return SMI_OK;
+}
+int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
+                           uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_zk_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept, grind_bits));
+}
+

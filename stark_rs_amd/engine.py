@@ -862,6 +862,64 @@ class Engine:
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
         return air_deep_args_fold4_layout(self.p, a, xargs_of(a), cfg)
 
+    # ---- zero-knowledge building blocks (include/stark_mi.h, "Zero-knowledge DEEP proofs")
+    def air_plan_deep_zk(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_plan_deep_zk -> (degree d of the derived AIR, segments D', k_t, k_s).  Host only; raises with the limit that
+        was broken."""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_plan_deep_zk(self.p, self._air(air), cfg)
+
+    def dev_random_fill(self, seed, stream_id, d_out, count):
+        """smi_dev_random_fill: count residues of stream stream_id under the 32-byte seed into device memory at d_out"""
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("dev_random_fill: the seed is 32 bytes")
+        self._ck(self.L.smi_dev_random_fill(self.h, seed, int(stream_id), vp(d_out), count))
+
+    def dev_zk_segments(self, d_h, h_len, log_n, k_s, n_segments, d_rho, d_out, h_stride=None, out_stride=None):
+        """smi_dev_zk_segments: the 4 n_segments masked segment columns (n = 2^log_n coefficients each, out_stride apart, default
+        n) of the four coefficient columns of H at d_h (h_len coefficients each, h_stride apart, default h_len) under the
+        4 (n_segments - 1) k_s random words at d_rho"""
+        self._ck(self.L.smi_dev_zk_segments(self.h, vp(d_h), h_len if h_stride is None else h_stride, h_len, log_n, k_s, n_segments, vp(d_rho),
+                                            vp(d_out), (1 << log_n) if out_stride is None else out_stride))
+
+    def air_deep_zk_layout(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_deep_zk_layout -> (folds, proof bytes) of dev_air_prove(deep=True, coset_leaves=True, zk=seed).  Host only."""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_deep_zk_layout(self.p, self._air(air), cfg)
+
+    def _dev_air_prove_deep_zk(self, air, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
+                               fill_multiplicities, folding, zk):
+        import os
+        self._check_deep(a, row_leaves, ext, folding, fill_multiplicities)
+        seed = os.urandom(32) if zk is True else bytes(zk)
+        if len(seed) != 32:
+            raise ValueError("zk: the seed is 32 bytes (or True for os.urandom(32))")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
+        _d, Dp, _kt, _ks = air_plan_deep_zk(self.p, a, cfg)
+        if check:
+            if isinstance(air, _lib.Air):
+                raise ValueError("zk with check=True derives the AIR to check from a mirror.Air; pass one, or check=False")
+            derived = air.zk_derived(self.p, log_n, t, trace_offset, self.prim_nth_root(1 << log_n))
+            ok, _con, _row, why = self.dev_air_check(derived.flatten(self.p), d_trace_cols, n_cols, log_n)
+            if not ok:
+                raise StarkMiError(-50, why)
+        roots = np.zeros((2, 32), dtype=np.uint8)
+        ood = np.zeros(4 * (2 * n_cols + Dp), dtype=np.uint64)
+        proof, plen = vp(), C.c_size_t()
+        top = np.zeros(max(t, 1), dtype=np.uint64)
+        stage = (C.c_double * 9)()
+        self._ck(self.L.smi_dev_air_prove_deep_zk(self.h, C.byref(cfg), C.byref(a), vp(d_trace_cols), seed, roots.ctypes.data, ood.ctypes.data,
+                                                  C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                  0 if grind_bits is None else grind_bits))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]], "seed": seed,
+               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(2 * n_cols + Dp)]}
+        if timed:
+            out["stage_ms"] = dict(zip(("random", "lde", "commit", "compose", "segments", "ood", "mask", "fri", "open"), [float(x) for x in stage]))
+        return out
+
     def _check_air_folding(self, a, folding, row_leaves, ext):
         _check_folding(folding)
         if folding == 4 and not (row_leaves and ext):
@@ -871,7 +929,7 @@ class Engine:
 
     def dev_air_prove(self, air, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None,
                       timed=False, check=True, row_leaves=False, ext=False, grind_bits=None, fill_multiplicities=False, folding=2, deep=False,
-                      deep_args=False, coset_leaves=False):
+                      deep_args=False, coset_leaves=False, zk=None):
         """smi_dev_air_prove -> dict(column_roots, proof, top_indices[, stage_ms]).  check (default on) runs
         dev_air_check first and raises StarkMiError naming the first violated constraint and row.
         row_leaves: smi_dev_air_prove_rows -- one tree over the rows of the extended trace; column_roots is then its
@@ -903,8 +961,19 @@ class Engine:
         what is missing otherwise): smi_dev_air_prove_deep_fold4 / smi_dev_air_prove_deep_xargs_fold4 -- the same DEEP proof
         with every group of columns committed as a tree of coset leaves and FRI at folding factor 4 (include/stark_mi.h,
         "Out-of-domain sampling over coset leaves").  The result has the keys of the variant it stands beside.  folding stays 2
-        on these calls: deep=True, folding=4 and deep_args=True, folding=4 keep raising ValueError."""
+        on these calls: deep=True, folding=4 and deep_args=True, folding=4 keep raising ValueError.
+        zk=seed (32 bytes) or zk=True (os.urandom(32)); needs deep=True, coset_leaves=True, ValueError otherwise:
+        smi_dev_air_prove_deep_zk -- the zero-knowledge variant (include/stark_mi.h, "Zero-knowledge DEEP proofs").  The last
+        k_t = 8 t + 8 rows of the device trace are OVERWRITTEN with random residues; the statement covers the rows before them.
+        check=True checks the derived AIR (air must then be a mirror.Air).  The result gains "seed", which is in no proof and
+        must stay with the prover; "ood" has 2 W + D' elements; stage_ms has nine stages."""
         a = self._air(air)
+        if zk is not None and zk is not False:
+            if not (deep and coset_leaves) or deep_args:
+                raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR: pass deep=True, coset_leaves=True")
+            self._check_coset_leaves(row_leaves, ext, deep, deep_args)
+            return self._dev_air_prove_deep_zk(air, a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed,
+                                               check, row_leaves, ext, grind_bits, fill_multiplicities, folding, zk)
         if coset_leaves:
             self._check_coset_leaves(row_leaves, ext, deep, deep_args)
         if deep_args:
@@ -1058,8 +1127,9 @@ class Engine:
 
     def air_verify(self, air, proof: bytes, column_roots, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1,
                    lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False, deep_args=False,
-                   coset_leaves=False):
-        """verifier of dev_air_prove -> (accept, reason).  row_leaves: smi_air_verify_rows, column_roots is the one root of
+                   coset_leaves=False, zk=False):
+        """verifier of dev_air_prove -> (accept, reason).  zk=True (needs deep=True, coset_leaves=True; ValueError otherwise):
+        smi_air_verify_deep_zk.  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
@@ -1071,6 +1141,8 @@ class Engine:
         deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots.
         coset_leaves=True: smi_air_verify_deep_fold4 / smi_air_verify_deep_xargs_fold4, under the conditions of
         dev_air_prove(coset_leaves=True); folding stays 2."""
+        if zk and (not (deep and coset_leaves) or deep_args):
+            raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR: pass deep=True, coset_leaves=True")
         if coset_leaves:
             self._check_coset_leaves(row_leaves, ext, deep, deep_args)
         if deep_args:
@@ -1093,7 +1165,7 @@ class Engine:
             if roots.size != 64:
                 raise StarkMiError(-50, "air_verify(deep=True) takes two 32-byte roots")
             acc = C.c_int()
-            verify = self.L.smi_air_verify_deep_fold4 if coset_leaves else self.L.smi_air_verify_deep
+            verify = self.L.smi_air_verify_deep_zk if zk else self.L.smi_air_verify_deep_fold4 if coset_leaves else self.L.smi_air_verify_deep
             self._ck(verify(self.h, C.byref(cfg), C.byref(a), roots.ctypes.data, proof, len(proof), C.byref(acc), 0 if grind_bits is None else grind_bits))
             return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
         self._check_air_folding(self._air(air), folding, row_leaves, ext)
@@ -1259,6 +1331,26 @@ def air_plan_deep(p, air, cfg, with_length=False):
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return (d.value, D.value, n.value) if with_length else (d.value, D.value)
+
+
+def air_plan_deep_zk(p, air, cfg):
+    """smi_air_plan_deep_zk (host only) -> (d, D', k_t, k_s) for cfg's number of colinearity tests.  air: a flattened _lib.Air"""
+    d, D, kt, ks = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    L = _lib.lib()
+    st = L.smi_air_plan_deep_zk(p, C.byref(cfg), C.byref(air), C.byref(d), C.byref(D), C.byref(kt), C.byref(ks))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, D.value, kt.value, ks.value
+
+
+def air_deep_zk_layout(p, air, cfg):
+    """smi_air_deep_zk_layout (host only) -> (folds, proof bytes).  air: a flattened _lib.Air"""
+    f, n = C.c_uint64(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_deep_zk_layout(p, C.byref(cfg), C.byref(air), C.byref(f), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return f.value, n.value
 
 
 def xargs_of(air):

@@ -969,6 +969,24 @@ class Air:
         out.boundaries = list(self.boundaries)
         return out
 
+    def zk_derived(self, p, log_n, t, trace_offset, omega_n):
+        """-> the AIR that a zero-knowledge DEEP proof of this one proves (include/stark_mi.h, "Zero-knowledge DEEP proofs"): one
+        more periodic column of period n = 2^log_n holding E(tau w^r), E(x) = prod over the exempt rows q = n - k_t - 1 .. n - 2
+        of (x - tau w^q), k_t = 8 t + 8, as one more factor of every transition term.  n k_t products in Python ints."""
+        import copy
+        n, kt = 1 << log_n, 8 * t + 8
+        pts = [trace_offset * pow(omega_n, r, p) % p for r in range(n)]
+        col = []
+        for r in range(n):
+            v = 1
+            for q in range(n - kt - 1, n - 1):
+                v = v * (pts[r] - pts[q]) % p
+            col.append(v)
+        out = copy.deepcopy(self)
+        j = out.periodic(col)
+        out._symbolic = [[(cf, list(factors) + [("per", j, 1)]) for cf, factors in con] for con in out._symbolic]
+        return out
+
     def transition(self, poly):
         terms = []
         for mono, coeff in poly.items():

@@ -23,11 +23,12 @@ SEED2 = bytes(range(1, 33))
 SHAPES = [("fib", 6, 2, 1), ("fib", 7, 3, 2), ("cubic", 7, 2, 1), ("cubic", 8, 3, 2), ("fib", 8, 2, 2)]
 
 
-def gpu_proof(eng, air, cols, log_n, lb, t, seed, bits=0, check=True):
+def gpu_proof(eng, air, cols, log_n, lb, t, seed, bits=0, check=True, trace_offset=1, lde_offset=None):
     """-> (result, the device trace after the call)"""
     with Dev(eng) as dev:
         d = dev.upload(np.array(cols, dtype=np.uint64))
-        res = eng.dev_air_prove(air, d, len(cols), log_n, lb, t, grind_bits=bits, check=check, zk=seed, **KW)
+        res = eng.dev_air_prove(air, d, len(cols), log_n, lb, t, trace_offset=trace_offset, lde_offset=lde_offset, grind_bits=bits, check=check, zk=seed,
+                                **KW)
         after = eng.dev_download(d, len(cols) << log_n).reshape(len(cols), -1)
     return res, [[int(v) for v in c] for c in after]
 

@@ -13,8 +13,13 @@ import zk_compose as zk
 P_REF, G_REF = 998244353, 3
 SEED = bytes(range(32))
 COUNTS = [1, 3, 4, 1023, 1024, 1025]
-# (log_n, t, D, h_len or None for D n): D' = 2, D' = 3, D n a multiple of L or not, the last coefficient of H in any residue
-SPLITS = [(6, 1, 1, None), (6, 1, 2, None), (7, 2, 2, None), (7, 1, 2, 2 * 123), (6, 2, 1, 57), (8, 2, 4, None)]
+# (log_n, t, D, h_len or None for D n): D' = 2, D' = 3, D n a multiple of L or not, the last coefficient of H in any residue;
+# then the limits: D' = 14 (the largest grid.y) with a full last segment and with one coefficient in it, and t = 32 (k_s = 129,
+# more masked coefficients at a column's end than a wavefront has lanes) at D' = 5 and with the last segment three short of full
+SPLITS = [(6, 1, 1, None), (6, 1, 2, None), (7, 2, 2, None), (7, 1, 2, 2 * 123), (6, 2, 1, 57), (8, 2, 4, None),
+          (6, 2, 14, 14 * (64 - 9)), (6, 2, 14, 13 * (64 - 9) + 1), (10, 32, 4, None), (10, 32, 2, 2 * 895 - 3)]
+# case -> (D', h_len mod L), written out
+SPLIT_DP = dict(zip(SPLITS, [(2, 5), (3, 10), (3, 18), (2, 0), (2, 2), (5, 36), (14, 0), (14, 1), (5, 516), (2, 892)]))
 
 
 @pytest.fixture(scope="module")
@@ -76,6 +81,62 @@ def cubic_statement(log_n, t, p):
 
 STATEMENTS = {"fib": fib_statement, "cubic": cubic_statement}
 SHAPES = [(6, 1), (7, 2), (8, 1), (8, 2)]          # (log_n, t): k_t = 16, 24 < n / 2
+
+
+def wide_statement(log_n, t, p, W=5):
+    """W >= 3 columns and two periodic columns, k4 of period 4 and k8 of period 8: a' = a^2 + k4, b' = b + k8' a with k8 read
+    at the next row, c_i' = c_i + c_(i-1) c_(i-2) for every further column.  Degree 2, so the derived AIR has degree 3: D = 2,
+    D' = 3.  A claim on every column in row 0 and on the last column in the last real row."""
+    from stark_rs_amd.mirror import Air
+    assert W >= 3
+    n = 1 << log_n
+    real = n - zk.k_t(t)
+    k4, k8 = [(5 * i + 1) % p for i in range(4)], [(3 * i * i + 2) % p for i in range(8)]
+    cols = [[c + 1] for c in range(W)]
+    for r in range(n - 1):
+        cur = [c[-1] for c in cols]
+        nxt = [(cur[0] * cur[0] + k4[r % 4]) % p, (cur[1] + k8[(r + 1) % 8] * cur[0]) % p]
+        nxt += [(cur[i] + cur[i - 1] * cur[i - 2]) % p for i in range(2, W)]
+        for c, v in zip(cols, nxt):
+            c.append(v)
+    air = Air(W)
+    j4, j8 = air.periodic(k4), air.periodic(k8)
+    air.transition({("next", 0): 1, ("cur", 0, 2): -1, ("per", j4): -1})
+    air.transition({("next", 1): 1, ("cur", 1): -1, (("per_next", j8), ("cur", 0)): -1})
+    for i in range(2, W):
+        air.transition({("next", i): 1, ("cur", i): -1, (("cur", i - 1), ("cur", i - 2)): -1})
+    for c in range(W):
+        air.boundary(c, 0, c + 1)
+    air.boundary(W - 1, real - 1, cols[W - 1][real - 1])
+    return air, cols
+
+
+def quintic_statement(log_n, t, p):
+    """one column, a' = a^5 + k with k a periodic column of period 1: the derived AIR has degree 6, D = 8 (log_blowup >= 3),
+    D' = 9 or, where n is small against k_s, 10"""
+    from stark_rs_amd.mirror import Air
+    n = 1 << log_n
+    real = n - zk.k_t(t)
+    a = [3]
+    for _ in range(n - 1):
+        a.append((pow(a[-1], 5, p) + 11) % p)
+    air = Air(1)
+    j = air.periodic([11])
+    air.transition({("next", 0): 1, ("cur", 0, 5): -1, ("per", j): -1})
+    air.boundary(0, 0, 3).boundary(0, real - 1, a[real - 1])
+    return air, [a]
+
+
+# the statements past two columns: name -> (log_n, t, p, W) -> (air, cols); the tests above STATEMENTS hard-code W = 2
+MORE_STATEMENTS = {"wide": wide_statement, "quintic": lambda log_n, t, p, W=1: quintic_statement(log_n, t, p)}
+# (statement, log_n, log_blowup, t, W, (d, D', k_t, k_s)): two periods with a next-row read, the widest leaf, D' = 9 and 10
+MORE_SHAPES = [("wide", 7, 2, 2, 5, (3, 3, 24, 9)), ("wide", 6, 2, 1, 63, (3, 3, 16, 5)), ("quintic", 6, 3, 1, 1, (6, 9, 16, 5)),
+               ("quintic", 6, 3, 2, 1, (6, 10, 24, 9))]
+
+
+def statement(name, log_n, t, p, W=2):
+    """any statement of this module by name"""
+    return STATEMENTS[name](log_n, t, p) if name in STATEMENTS else MORE_STATEMENTS[name](log_n, t, p, W)
 
 
 def w_of(oracle, log_n, p, g):
@@ -158,7 +219,7 @@ def test_zk_segments_recombine_to_the_composition(emu, log_n, t, D, h_len):
     import deep_compose as dc
     p, g = P_REF, G_REF
     n, ks, L, h_len, Dp, hc, rho = split_case(log_n, t, D, h_len, p)
-    assert Dp in (2, 3, 5) and (h_len % L != 0 or h_len == 2 * L)
+    assert (Dp, h_len % L) == SPLIT_DP[(log_n, t, D, None if h_len == D * n else h_len)] and Dp in (2, 3, 5, 14)
     got = emu_split(emu, p, hc, h_len, log_n, ks, Dp, rho)
     rng = np.random.default_rng(99)
     for _ in range(8):
@@ -185,10 +246,10 @@ def test_zk_segments_refusals(emu):
 
 
 # ---------------------------------------------------------------------------------------------- the derived AIR
-def emu_derived(emu, air, W, log_n, t, p, g, tau=1):
+def emu_derived(emu, air, W, log_n, t, p, g, tau=1, lb=2):
     from stark_rs_amd import _lib
     a = air.flatten(p)
-    cfg = _lib.StarkCfg(log_n, 2, W, 1, tau, g, t, 1)
+    cfg = _lib.StarkCfg(log_n, lb, W, 1, tau, g, t, 1)
     head = np.zeros(6, dtype=np.uint64)
     none = None
     assert emu.emu_zk_derived_air(p, g, C.byref(cfg), C.byref(a), head.ctypes.data, none, none, none, none, none, none, none) == 0
@@ -257,6 +318,57 @@ def test_the_derived_air_holds_on_garbage_tails_and_names_a_violation(oracle, em
     assert emu_check(emu, derived, bad, p, log_n) == (True, None, None)
 
 
+@pytest.mark.parametrize("name,log_n,lb,t,W,numbers", MORE_SHAPES)
+def test_the_library_derives_the_mirrors_air_past_two_columns(oracle, emu, name, log_n, lb, t, W, numbers):
+    """next-row periodic variables 2 W + Q + j move up by one when the exemption column takes index Q, and its n values stand
+    behind the caller's periods (4 + 8, or 1) in the value table"""
+    p, g, n = P_REF, G_REF, 1 << log_n
+    air, cols = statement(name, log_n, t, p, W)
+    assert len(cols) == W == air.n_cols and air.degree + 1 == numbers[0]
+    if name == "wide":
+        Q = len(air.periodics)
+        assert Q == 2 and any(v == 2 * W + Q + 1 for con in air.constraints for _cf, f in con for v, _e in f), "no next-row read of k8"
+    for tau in (1, 5):
+        want = zk.derived_air(air, log_n, t, p, tau, w_of(oracle, log_n, p, g)).flatten(p)
+        head, arrs = emu_derived(emu, air, W, log_n, t, p, g, tau, lb)
+        assert head == (want.n_constraints, want.n_terms, want.n_factors, want.n_boundary, want.n_periodic)
+        assert arrs == [[int(v) for v in k] for k in (want._keep[0], want._keep[1], want._keep[2], want._keep[3], want._keep[4], want._keep[8], want._keep[9])]
+        assert arrs[6][-n:] == zk.exemption_column(n, t, p, tau, w_of(oracle, log_n, p, g))
+        assert arrs[6][:-n] == [x % p for v in air.periodics for x in v]
+        if name == "wide":                                        # k8 at the next row: variable 2 W + (Q + 1) + 1 of the derived AIR
+            assert 2 * W + 3 + 1 in arrs[3] and 2 * W + 2 + 1 not in arrs[3]
+
+
+@pytest.mark.parametrize("name,log_n,lb,t,W,numbers", MORE_SHAPES)
+def test_the_derived_air_past_two_columns_holds_and_names_a_violation(oracle, emu, name, log_n, lb, t, W, numbers):
+    p, g, n = P_REF, G_REF, 1 << log_n
+    kt = zk.k_t(t)
+    air, cols = statement(name, log_n, t, p, W)
+    derived = zk.derived_air(air, log_n, t, p, 1, w_of(oracle, log_n, p, g))
+    tail = zk.rng(oracle, SEED, 1, W * kt, p)
+    masked = zk.randomised(cols, tail, t)
+    assert [c[-kt:] for c in masked] == [tail[c * kt:(c + 1) * kt] for c in range(W)] and [c[:n - kt] for c in masked] == [c[:n - kt] for c in cols]
+    assert emu_check(emu, derived, masked, p, log_n) == (True, None, None)
+    ok, con, row = emu_check(emu, air, masked, p, log_n)          # the caller's own AIR does not hold on the masked trace
+    assert not ok and row == n - kt - 1
+    nb = len(air.boundaries)
+    bad = [list(c) for c in masked]
+    bad[0][n - kt - 1] = (bad[0][n - kt - 1] + 1) % p             # the last real row: transition n - k_t - 2 -> n - k_t - 1 breaks
+    if name == "wide":                                            # column 0 has no boundary point there; constraint 0 sets it
+        assert emu_check(emu, derived, bad, p, log_n) == (False, nb + 0, n - kt - 2)
+    else:                                                         # the only column has one: it is named first, then the transition
+        assert emu_check(emu, derived, bad, p, log_n) == (False, nb - 1, n - kt - 1)
+        moved = zk.derived_air(air, log_n, t, p, 1, w_of(oracle, log_n, p, g))
+        moved.boundaries[-1] = (0, n - kt - 1, bad[0][n - kt - 1])
+        assert emu_check(emu, moved, bad, p, log_n) == (False, nb + 0, n - kt - 2)
+    bad = [list(c) for c in masked]
+    bad[W - 1][n - kt] = (bad[W - 1][n - kt] + 1) % p             # a randomiser row: exempt
+    assert emu_check(emu, derived, bad, p, log_n) == (True, None, None)
+    bad = [list(c) for c in masked]
+    bad[W - 1][n - 1] = (bad[W - 1][n - 1] + 1) % p               # the last row: only the wrap-around follows it, which no AIR checks
+    assert emu_check(emu, derived, bad, p, log_n) == (True, None, None)
+
+
 # ---------------------------------------------------------------------------------------------- the plan
 def lib_plan(air, W, log_n, lb, t, p=P_REF, g=G_REF):
     import stark_rs_amd as s
@@ -273,6 +385,15 @@ def test_plan_numbers(name, log_n, t, lb):
     want = zk.plan(air, log_n, t)
     assert lib_plan(air, 2, log_n, lb, t) == want
     assert want[2] in (16, 24) and want[3] in (5, 9) and want[1] == {"fib": 2, "cubic": 5}[name] and 4 * want[1] + 5 <= 64
+
+
+@pytest.mark.parametrize("name,log_n,lb,t,W,numbers", MORE_SHAPES + [("wide", 7, 2, 2, 4, (3, 3, 24, 9)), ("wide", 8, 3, 5, 3, (3, 3, 48, 21))])
+def test_plan_numbers_past_two_columns(name, log_n, lb, t, W, numbers):
+    """the numbers are written out in MORE_SHAPES, not computed: D' = 10 and a leaf of 64 values among them"""
+    air, _cols = statement(name, log_n, t, P_REF, W)
+    assert lib_plan(air, W, log_n, lb, t) == zk.plan(air, log_n, t) == numbers
+    assert lib_layout(air, W, log_n, lb, t) == zk.layout(W, numbers[1], log_n, lb, t)
+    assert W + 1 <= 64 and 4 * numbers[1] + 5 <= 64
 
 
 def test_plan_refusals():
@@ -353,6 +474,45 @@ def test_the_proof_length_equals_the_layout_and_the_restated_verifier_accepts(or
         assert zk.verify(oracle, air, bytes(m), res["roots"], p, g, 2, log_n, lb, t, 1, g) == (False, why), at
     other = zk.prove(oracle, air, cols, bytes(32), p, g, log_n, lb, t, 1, g)
     assert other["roots"][0] != res["roots"][0] and len(other["proof"]) == nbytes and other["trace"] != res["trace"]
+
+
+@pytest.mark.parametrize("name,log_n,lb,t,W,numbers", MORE_SHAPES)
+def test_the_restated_prover_and_verifier_agree_past_two_columns(oracle, name, log_n, lb, t, W, numbers):
+    p, g = P_REF, G_REF
+    air, cols = statement(name, log_n, t, p, W)
+    res = zk.prove(oracle, air, cols, SEED, p, g, log_n, lb, t, 1, g)
+    assert res["Dp"] == numbers[1] and d4_folds(log_n, lb, t) == 2
+    assert (2, len(res["proof"])) == zk.layout(W, res["Dp"], log_n, lb, t) == lib_layout(air, W, log_n, lb, t)
+    assert zk.verify(oracle, air, res["proof"], res["roots"], p, g, W, log_n, lb, t, 1, g) == (True, "")
+    off = zk.offsets(W, res["Dp"], log_n, lb, t)
+    assert off["end"] == len(res["proof"])
+    for at, why in ((off["s0"] + 32 * (res["Dp"] - 1), zk.FRONT["consistency"]), (off["rec 0"] + 9 + 32 * (W - 1), zk.WORDS["auth"]),
+                    (off["rec 1"] + 9 + 32 * (4 * res["Dp"] - 1), zk.WORDS["auth"])):
+        m = bytearray(res["proof"])
+        m[at] ^= 1
+        assert zk.verify(oracle, air, bytes(m), res["roots"], p, g, W, log_n, lb, t, 1, g) == (False, why), at
+
+
+def d4_folds(log_n, lb, t):
+    import deep_fold4_compose as d4
+    return d4.folds(log_n, lb, t)
+
+
+def test_the_restated_verifier_on_dishonest_commitments(oracle):
+    """commit_as of zk.prove: a column committed as value + p keeps every path and only the canonical check refuses it -- unless
+    it is a salt, which the verifier does not look at; a column committed with two coset points exchanged keeps every path
+    and every value canonical, and only the masked DEEP quotient refuses it"""
+    p, g, log_n, lb, t, W = P_REF, G_REF, 7, 2, 2, 5
+    air, cols = wide_statement(log_n, t, p, W)
+    Dp = zk.plan(air, log_n, t)[1]
+    said = lambda commit_as: zk.verify(oracle, air, *[zk.prove(oracle, air, cols, SEED, p, g, log_n, lb, t, 1, g, commit_as=commit_as)[k] for k in ("proof", "roots")],
+                                       p, g, W, log_n, lb, t, 1, g)
+    assert said(None) == (True, "")
+    assert said(zk.plus_p(0, W, p)) == (True, "") and said(zk.plus_p(1, 4 * Dp + 4, p)) == (True, "")        # the two salts
+    for group, col in ((0, 0), (0, W - 1), (1, 0), (1, 4 * Dp - 1), (1, 4 * Dp), (1, 4 * Dp + 3)):            # trace, segments, R
+        assert said(zk.plus_p(group, col, p)) == (False, zk.WORDS["canonical"]), (group, col)
+    for group, col in ((0, 1), (1, 0), (1, 4 * Dp + 1)):
+        assert said(zk.swapped(group, col)) == (False, zk.WORDS["quotient"]), (group, col)
 
 
 def test_layout_refusals():

@@ -124,6 +124,8 @@ WORDS = {"length": "zk deep coset openings: wrong length", "record": "zk deep co
          "canonical": "zk deep coset openings: an opened value is not canonical",
          "quotient": "zk deep coset openings: the masked DEEP quotient of the opened cosets is not the codeword value"}
 
+SENTENCES = set(FRONT.values()) | set(WORDS.values()) | f4.FRI_SENTENCES          # every sentence verify() can give
+
 
 def layout(W, Dp, log_n, lb, t):
     """-> (folds, proof bytes) from the formula of the header section"""
@@ -144,9 +146,14 @@ def offsets(W, Dp, log_n, lb, t):
     return out
 
 
-def prove(o, air, cols, seed, p, g, log_n, lb, t, tau, h, bits=0, compose_with=None):
+plus_p, swapped = d4.plus_p, d4.swapped          # commit_as of prove: group 0 is the trace and its salt, group 1 the segments, R and its salt
+
+
+def prove(o, air, cols, seed, p, g, log_n, lb, t, tau, h, bits=0, compose_with=None, commit_as=None):
     """-> dict(roots, proof, top, ood, trace, ...) of smi_dev_air_prove_deep_zk.  compose_with: a dishonest prover that skips the
-    derivation -- it composes this AIR over the trace as it stands, without randomiser rows; the plan stays the derived AIR's"""
+    derivation -- it composes this AIR over the trace as it stands, without randomiser rows; the plan stays the derived AIR's.
+    commit_as: a dishonest prover that commits and opens tampered columns (d4.plus_p, d4.swapped; the salt is the last column
+    of its group) -- the trees and the opened records hold the tampered columns, every other step the true ones"""
     n, N, B = 1 << log_n, 1 << (log_n + lb), 1 << lb
     W, K = len(cols), len(air.constraints)
     kt, ks = k_t(t), k_s(t)
@@ -157,8 +164,7 @@ def prove(o, air, cols, seed, p, g, log_n, lb, t, tau, h, bits=0, compose_with=N
     assert D <= B and 4 * Dp + 5 <= 64 and d4.folds(log_n, lb, t) >= 1
     trace = [list(c) for c in cols] if compose_with is not None else randomised(cols, rng(o, seed, STREAM_ROWS, W * kt, p), t)
     lde = [np.asarray(c, dtype=np.uint64) for c in ac.lde(o, trace, p, g, log_n, lb, tau, h)]
-    held1 = lde + [np.array(rng(o, seed, STREAM_SALT1, N, p), dtype=np.uint64)]
-    nodes1 = d4.coset_tree(o, held1, N)
+    held1, nodes1 = d4._commit(o, 0, lde + [np.array(rng(o, seed, STREAM_SALT1, N, p), dtype=np.uint64)], N, commit_as)
     root1 = bytes(nodes1[-1])
     tr, ch = xc.air_transcript(o, W, K, root1)
     tr = bytearray(tr)
@@ -169,8 +175,7 @@ def prove(o, air, cols, seed, p, g, log_n, lb, t, tau, h, bits=0, compose_with=N
     mask = rng(o, seed, STREAM_MASK, 4 * n, p)
     coefs = segc + [mask[e * n:(e + 1) * n] for e in range(4)]
     seg = [np.asarray(o.fast_coset_ntt(np.array(c, dtype=np.uint64), N, wN, h, p), dtype=np.uint64) for c in coefs]
-    held2 = seg + [np.array(rng(o, seed, STREAM_SALT2, N, p), dtype=np.uint64)]
-    nodes2 = d4.coset_tree(o, held2, N)
+    held2, nodes2 = d4._commit(o, 1, seg + [np.array(rng(o, seed, STREAM_SALT2, N, p), dtype=np.uint64)], N, commit_as)
     root2 = bytes(nodes2[-1])
     tr += root2
     z = [c % p for c in dc.draw(o, tr, 4 * (W + K), 4)]

@@ -470,17 +470,8 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     const uint32_t W = cfg->n_cols, K = air->n_constraints, log_N = cfg->log_n + cfg->log_blowup;
     const size_t N = (size_t)1 << log_N;
     SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 6; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+    StageTimer tm(ctx, 5, stage_ms != nullptr);
+    HIP_TRY(ctx, tm.create());
 
     const size_t tree_stride = 2 * N * 32;
     const uint32_t n_trees = rows ? 1u : W;
@@ -497,12 +488,12 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     }
     if (!d_lde || !d_cw || !d_weights || !d_blob || !tree_base || (H.dev.Q && (!d_ptab || !d_pvals)))
         return smi_fail(ctx, SMI_ERR_OOM, "air_prove: device memory");
-    mark(0);
+    tm.mark();
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, cfg->log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
+    tm.mark();
     if (rows) SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree_base));
     else SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
-    mark(2);
+    tm.mark();
     // The roots make one small round trip: the transcript (roots, then the indices) and its weights
     // are computed on the host, where fri_run's seed is computed anyway (transcript_core.h).
     std::vector<uint8_t> roots(32 * (size_t)n_trees);
@@ -519,7 +510,7 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     if (ext) SMI_TRY(air_launch_compose_ext(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
     else SMI_TRY(air_launch_compose(ctx, H, d_blob, d_lde, N, d_weights, d_cw));
-    mark(3);
+    tm.mark();
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriResult res;
     FriExtResult xres;
@@ -536,7 +527,7 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
     std::vector<uint64_t> &top = ext ? xres.top : res.top;
     if (top_indices) memcpy(top_indices, top.data(), 8 * (size_t)cfg->num_colinearity_tests);
     else top_indices = top.data();   // the column openings need the top-level indices either way
-    mark(4);
+    tm.mark();
     if (cfg->num_colinearity_tests && rows) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = (K ? 4u : 2u) * (fold4 ? 2u : 1u);
         const size_t ob = (size_t)mg_row_open_bytes(W, t, log_N, R);
@@ -571,14 +562,9 @@ static int air_prove_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air 
         bytes.resize(at + ob);
         HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob, hipMemcpyDeviceToHost, ctx->stream));
     }
-    mark(5);
+    tm.mark();
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (int i = 0; i < 5; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
+    tm.write(stage_ms);
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }
 

@@ -1,7 +1,10 @@
 // deep.hip -- out-of-domain sampling (include/stark_mi.h, "Out-of-domain sampling"): coefficient columns evaluated at one or
-// two points of F_q, the DEEP codeword, and the prover with its second commitment (the composition's segments) and its
-// three host round trips.  The lane bodies and the host tables are deep_core.h, shared with the CPU emulator (emu_deep.cpp);
-// the verifier is in verify.hip.
+// two points of F_q, the DEEP codeword (plain and with an argument list), and the provers.  The lane bodies and the host
+// tables are deep_core.h, shared with the CPU emulator (emu_deep.cpp); the verifier is in verify.hip.
+//
+// The provers -- row or coset leaves, plain or with a list, zero-knowledge -- are one set of step functions over a
+// DeepProver (shapes, buffers, transcript, record, proof bytes, stage timer) and two short drivers, deep_prove and zk_prove,
+// at the end of the file; the six public entry points check their pointers and call a driver.
 //
 // Evaluation is a two-level reduction with no atomics (the sums are exact residues: any order gives the same words):
 //   deep_eval_kernel          workgroup (b, .) takes coefficients [b T, (b + 1) T) (T = DEEP_TILE) of one column after the
@@ -243,160 +246,7 @@ int smi_dev_deep_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_segm
     return deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, (const uint32_t *)d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride);
 }
 
-int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const uint32_t *d_trace_cols, uint8_t *roots_out, uint64_t *ood_out,
-                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
-    const smi_air *air = (const smi_air *)air_;
-    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
-    DeviceGuard dg__(ctx);
-    SMI_TRY(grind_bits_check(ctx, grind_bits));
-    SMI_TRY(deep_field_check(ctx));
-    uint32_t D = 0;
-    {
-        std::string why;
-        const int rc = deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
-        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    }
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
-    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
-    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
-    AirHost H;
-    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
-    SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 8; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
-
-    const uint32_t n_ood = 4 * (2 * W + D);
-    const size_t tree_bytes = 2 * N * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
-    const size_t part_a = deep_eval_part_bytes(W, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // H, then Q
-    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // the coefficients of H's coordinates
-    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, 4 * (size_t)D * N * 4);
-    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)W * n * 4);
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)(W + K));
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
-    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
-    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * W + 16 * D) * 4);   // f_c at z and z w | H_{j,e} at z, e-major
-    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_tab_words(W, D) * 4);
-    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
-    if (H.dev.Q) {
-        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    }
-    if (!d_lde || !d_cw || !d_hc || !d_seg || !d_coef || !d_weights || !d_blob || !tree1 || !tree2 || !d_tab2 || !d_tab1 || !d_part || !d_res || !d_ctab ||
-        (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep: device memory");
-    mark(0);
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
-    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    mark(2);
-    // first round trip: root_1 -> the composition weights
-    uint8_t roots[64];
-    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
-    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for step 5
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> weights, gammas;
-    deep_transcript_weights(tr, roots, W, K, &weights);
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    mark(3);
-    // the segments: coefficients of every coordinate of H on the coset, D slices of n, each extended back to the N points
-    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
-    for (uint32_t j = 0; j < D; j++)
-        SMI_TRY(dev_ntt(ctx, d_hc + (size_t)j * n, d_seg + 4 * (size_t)j * N, log_N, n, 4, N, N, 0, cfg->lde_offset, 1));
-    SMI_TRY(launch_merkle_rows(ctx, d_seg, 4 * D, N, N, tree2));
-    mark(4);
-    // second round trip: root_2 -> z
-    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t zr[4];
-    deep_transcript_z(tr, roots + 32, W, K, zr);
-    const FqH z = fqh_of(zr, p);
-    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
-    if (roots_out) memcpy(roots_out, roots, 64);
-    // third round trip: u = f(z), v = f(z w), s = H_j(z)
-    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
-    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)W + 16 * (size_t)D);
-    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
-    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W, n, n, 2, d_tab2, d_part, d_res));
-    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D segments: D columns of n coefficients, n apart
-        SMI_TRY(deep_eval_enqueue(ctx, d_hc + (size_t)e * N, D, n, n, 1, d_tab1, d_part, d_res + 8 * (size_t)W + 4 * (size_t)e * D));
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> ood(n_ood);
-    for (uint32_t c = 0; c < W; c++)
-        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
-    for (uint32_t j = 0; j < D; j++) {   // s_j = sum_e X^e H_{j,e}(z)
-        FqH s = fqh(0), xe = fqh(1 % p);
-        const FqH X{{0, 1 % p, 0, 0}};
-        for (uint32_t e = 0; e < 4; e++) {
-            const uint32_t *v = &res[8 * (size_t)W + 4 * ((size_t)e * D + j)];
-            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
-            xe = fqh_mul(xe, X, p, g);
-        }
-        for (uint32_t e = 0; e < 4; e++) ood[4 * (2 * W + j) + e] = s.c[e];
-    }
-    if (ood_out) memcpy(ood_out, ood.data(), 8 * (size_t)n_ood);
-    deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
-    const FsSeed seed = tr.seed();
-    deep_compose_build(ctx->fs.F, g, W, D, w_n, z, ood.data(), gammas.data(), &ctab);
-    HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_seg, N, d_cw, N));
-    mark(5);
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
-    std::vector<uint8_t> bytes(9 + 8 * (size_t)n_ood);
-    bytes[0] = 2;
-    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
-    for (uint32_t v = 0; v < n_ood; v++)
-        for (int i = 0; i < 8; i++) bytes[9 + 8 * (size_t)v + i] = (uint8_t)(ood[v] >> (8 * i));
-    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark(6);
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 2;
-        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(4 * D, t, log_N, R);
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep: row openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
-        SMI_TRY(launch_air_row_open(ctx, d_seg, N, 4 * D, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
-        const size_t at = bytes.size();
-        bytes.resize(at + ob1 + ob2);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    mark(7);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (int i = 0; i < 7; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
-    return smi_proof_out(ctx, bytes, proof, proof_len);
-}
-
-// ---- out-of-domain sampling with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
+// ---- the codeword with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
 // deep_compose_kernel with the 4 A extended coordinate columns of the auxiliary F_q columns as a third group of streams:
 // 4 (W + 4 A + 4 D) + 16 bytes a point, one 16-byte load per column and lane.  The lane body (deep_core.h) keeps one column
 // group live at a time, so the register count does not grow with A; the gammas are scalar loads of the table.
@@ -476,197 +326,15 @@ int smi_dev_deep_compose_args(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n
                                      seg_stride, d_out, out_stride);
 }
 
-int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_trace_cols,
-                                 uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
-                                 uint32_t grind_bits, uint32_t *closes) {
-    const smi_air *air = (const smi_air *)air_;
-    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
-    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
-    DeviceGuard dg__(ctx);
-    if (closes) *closes = 0;
-    SMI_TRY(grind_bits_check(ctx, grind_bits));
-    SMI_TRY(deep_field_check(ctx));
-    uint32_t D = 0;
-    {
-        std::string why;
-        const int rc = deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why);
-        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    }
-    SMI_TRY(xargs_entry_checks(ctx, air, xargs, cfg->n_cols, cfg->log_n));
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs->count, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
-    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the second tree
-    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
-    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
-    AirHost H;
-    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
-    SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 9; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
-
-    const size_t n_ood = deep_args_record(W, A, D);
-    const size_t tree_bytes = 2 * N * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
-    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_c = (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4);
-    uint32_t *d_cl = (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4);
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // H, then Q
-    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // the coefficients of H's coordinates
-    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, 4 * (size_t)D * N * 4);
-    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)(W + CW) * n * 4);   // the trace polynomials, then the columns' coordinates
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree3 = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint8_t *d_atmp = (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_size(A, n));
-    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
-    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
-    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | H_{j,e} at z, e-major
-    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_args_tab_words(W, A, D) * 4);
-    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
-    if (H.dev.Q) {
-        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    }
-    if (!d_lde || !d_c || !d_cl || !d_cw || !d_hc || !d_seg || !d_coef || !d_weights || !d_blob || !tree1 || !tree2 || !tree3 || !d_atmp || !d_tab2 ||
-        !d_tab1 || !d_part || !d_res || !d_ctab || (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_xargs: device memory");
-    mark(0);
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
-    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    mark(2);
-    // first round trip: root_1 -> alpha, gamma
-    uint8_t roots[96];
-    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root; d_pvals: the raw values the column build reads
-    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for step 7
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> ch, weights, gammas;   // 8 challenges; 4 NW weights; the record's gammas
-    transcript_perm_challenges(tr, roots, &ch);
-    XArgsDev XD;
-    xargs_build(ctx->fs.F, g, xargs, W, air, H.per, ch.data(), &XD);
-    XD.pvals = d_pvals;
-    SMI_TRY(xargs_columns_launch(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
-    SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
-    SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
-    mark(3);
-    // second round trip: root_2 (and the columns' verdicts) -> the weights
-    ArgsFlags fl;
-    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(dev_ntt(ctx, d_c, d_coef + (size_t)W * n, log_n, n, CW, n, n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(xargs_columns_settle(ctx, XD, fl, closes));
-    transcript_args_weights(tr, roots + 32, W, K, A, &weights);
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    SMI_TRY(xargs_compose_launch(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    mark(4);
-    // the segments: coefficients of every coordinate of H on the coset, D slices of n, each extended back to the N points
-    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
-    for (uint32_t j = 0; j < D; j++)
-        SMI_TRY(dev_ntt(ctx, d_hc + (size_t)j * n, d_seg + 4 * (size_t)j * N, log_N, n, 4, N, N, 0, cfg->lde_offset, 1));
-    SMI_TRY(launch_merkle_rows(ctx, d_seg, 4 * D, N, N, tree3));
-    mark(5);
-    // third round trip: root_3 -> z
-    HIP_TRY(ctx, hipMemcpyAsync(roots + 64, tree3 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t zr[4];
-    deep_args_transcript_z(tr, roots + 64, NW, zr);
-    const FqH z = fqh_of(zr, p);
-    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
-    if (roots_out) memcpy(roots_out, roots, 96);
-    // fourth round trip: u, v = f(z), f(z w); a, b = c(z), c(z w); s = H_j(z)
-    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
-    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
-    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
-    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W + CW, n, n, 2, d_tab2, d_part, d_res));
-    uint32_t *d_sres = d_res + 8 * (size_t)(W + CW);
-    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D segments: D columns of n coefficients, n apart
-        SMI_TRY(deep_eval_enqueue(ctx, d_hc + (size_t)e * N, D, n, n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * D));
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> ood(n_ood);
-    const FqH X{{0, 1 % p, 0, 0}};
-    auto assemble = [&](const uint32_t *at, size_t pitch, uint64_t *dst) {   // sum_e X^e v_e, v_e four words at at + e pitch
-        FqH s = fqh(0), xe = fqh(1 % p);
-        for (uint32_t e = 0; e < 4; e++) {
-            const uint32_t *v = at + e * pitch;
-            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
-            xe = fqh_mul(xe, X, p, g);
-        }
-        for (uint32_t e = 0; e < 4; e++) dst[e] = s.c[e];
-    };
-    for (uint32_t c = 0; c < W; c++)
-        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
-    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
-        assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
-        assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
-    }
-    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
-    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
-    deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
-    const FsSeed seed = tr.seed();
-    deep_compose_args_build(ctx->fs.F, g, W, A, D, w_n, z, ood.data(), gammas.data(), &ctab);
-    HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_compose_args_enqueue(ctx, W, A, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_cl, N, d_seg, N, d_cw, N));
-    mark(6);
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
-    std::vector<uint8_t> bytes(9 + 8 * n_ood);
-    bytes[0] = 2;
-    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
-    for (size_t v = 0; v < n_ood; v++)
-        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
-    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark(7);
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 2;
-        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R),
-                     ob3 = (size_t)mg_row_open_bytes(4 * D, t, log_N, R);
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2 + ob3);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_xargs: row openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
-        SMI_TRY(launch_air_row_open(ctx, d_cl, N, CW, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
-        SMI_TRY(launch_air_row_open(ctx, d_seg, N, 4 * D, tree3, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1 + ob2));
-        const size_t at = bytes.size();
-        bytes.resize(at + ob1 + ob2 + ob3);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2 + ob3, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    mark(8);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (int i = 0; i < 8; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
-    return smi_proof_out(ctx, bytes, proof, proof_len);
-}
-
-// ---- out-of-domain sampling over coset leaves (include/stark_mi.h, "Out-of-domain sampling over coset leaves")
-// The two provers above with every commitment a tree of coset leaves (launch_merkle_cosets), FRI at folding factor 4 over
-// the DEEP codeword where it stands (stride == N: no compaction copy), and one leaf and one path per test and group
-// (coset_open_kernel).  Everything else -- the transcripts, the segments, the evaluations at z, the two codeword kernels --
-// is what the provers above run, so the two variants are one function that differs by the list (xargs == nullptr: a plain
-// AIR) and by the group table.
+// ---- the provers (include/stark_mi.h: "Out-of-domain sampling", "... with an argument list", "... over coset leaves",
+// "Zero-knowledge DEEP proofs")
+// Every variant is a sequence of the steps below over one DeepProver; each step exists once.  deep_prove is the driver of
+// {row leaves + FRI at folding factor 2, coset leaves + folding factor 4} x {plain AIR, argument list}: the leaf type
+// decides the commit, the FRI call and the openings (DeepProver::cosets), the list adds its columns between root_1 and the
+// composition and switches transcript and codeword kernel (DeepProver::A).  zk_prove is the coset-leaf plain driver with the
+// steps of its own in between: the randomiser rows and salts before the trace is extended, the masked split in place of the
+// slice loop, the mask added to the codeword; its widths V carry the salt columns and R.  The stage marks stand in the
+// drivers (and one in deep_list_columns), so a driver reads against the stage_ms list of its section in the header.
 
 // one workgroup per (test, group): mgpu_core.h mg_coset_open_write
 __global__ __launch_bounds__(64) void coset_open_kernel(const MgCosetTable tab, uint32_t log_N, const uint64_t *__restrict__ top, uint32_t t, uint8_t *out) {
@@ -675,8 +343,292 @@ __global__ __launch_bounds__(64) void coset_open_kernel(const MgCosetTable tab, 
 }
 
 namespace {
-int deep_fold4_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *d_trace_cols, uint8_t *roots_out,
-                     uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes) {
+struct DeepProver {
+    smi_ctx *ctx;
+    const smi_stark_cfg *cfg = nullptr;
+    const smi_air *air = nullptr;            // what is composed (zk: the derived AIR, once the entry checks are through)
+    const smi_air_xargs *xargs = nullptr;    // nullptr: a plain AIR
+    const char *name = nullptr;              // the entry point, for the out-of-memory sentences
+    bool cosets = false;                     // coset leaves, FRI at folding factor 4; else row leaves, folding factor 2
+    const uint32_t *d_trace = nullptr;
+    // shapes (deep_shapes)
+    uint32_t W = 0, K = 0, A = 0, CW = 0, NW = 0, D = 0, log_n = 0, log_N = 0, p = 0, g = 0, w_n = 0;   // CW = 4 A coordinate columns; NW weights; D committed segments
+    size_t n = 0, N = 0, leaves = 0, n_ood = 0;
+    uint32_t G = 0, V[3] = {0, 0, 0};   // the committed groups in order -- trace, (auxiliary,) segments -- and their widths in columns
+    // device buffers (deep_setup); cols[k] and tree[k] are group k's
+    uint32_t *d_lde = nullptr, *d_c = nullptr, *d_cl = nullptr, *d_cw = nullptr, *d_hc = nullptr, *d_seg = nullptr, *d_coef = nullptr, *d_blob = nullptr;
+    uint32_t *d_tab2 = nullptr, *d_tab1 = nullptr, *d_part = nullptr, *d_res = nullptr, *d_ctab = nullptr, *d_ptab = nullptr, *d_pvals = nullptr;
+    uint64_t *d_weights = nullptr;
+    uint8_t *d_atmp = nullptr, *tree[3] = {nullptr, nullptr, nullptr};
+    const uint32_t *cols[3] = {nullptr, nullptr, nullptr};
+    // host state; the vectors that a queued copy reads or fills live as long as the prover
+    AirHost H;
+    XArgsDev XD;
+    Transcript tr;
+    uint8_t roots[96];
+    FqH z;
+    FsSeed seed;
+    std::vector<uint64_t> weights, ood;
+    std::vector<uint32_t> ctab;
+    FriExtResult fri;
+    std::vector<uint8_t> bytes;
+    StageTimer timer;
+    DeepProver(smi_ctx *c, uint32_t stages, bool timed) : ctx(c), timer(c, stages, timed) {}
+};
+
+// the entry checks that follow the variant's plan, in their order, and the shapes; D: the plan's committed segments;
+// no_layer: the refusal sentence of a coset variant whose FRI part has no fold
+int deep_shapes(DeepProver &s, uint32_t D, const char *no_layer) {
+    smi_ctx *ctx = s.ctx;
+    const smi_stark_cfg *cfg = s.cfg;
+    if (s.xargs) SMI_TRY(xargs_entry_checks(ctx, s.air, s.xargs, cfg->n_cols, cfg->log_n));
+    s.W = cfg->n_cols, s.K = s.air->n_constraints, s.A = s.xargs ? s.xargs->count : 0, s.D = D, s.log_n = cfg->log_n, s.log_N = cfg->log_n + cfg->log_blowup;
+    s.NW = s.W + s.K + 2 * s.A, s.CW = 4 * s.A;
+    if (s.log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
+    if (s.cosets && fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, no_layer);
+    s.n = (size_t)1 << s.log_n, s.N = (size_t)1 << s.log_N, s.leaves = s.cosets ? s.N / 4 : s.N;
+    s.p = ctx->fs.F.p, s.g = ctx->fs.g, s.w_n = h_root(ctx, s.log_n);
+    s.n_ood = deep_args_record(s.W, s.A, D);
+    const DeepGroups gr = deep_groups(s.W, s.A, D);
+    s.G = gr.G;
+    for (uint32_t k = 0; k < 3; k++) s.V[k] = gr.V[k];
+    return SMI_OK;
+}
+
+// the AIR's tables, the arena, the timer's events and every buffer the shared steps use, by the variant's widths
+int deep_setup(DeepProver &s) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t W = s.W, A = s.A, CW = s.CW, D = s.D;
+    const size_t n = s.n, N = s.N;
+    air_build(ctx->fs.F, h_root(ctx, s.log_N), s.cfg, s.air, &s.H);
+    SMI_TRY(arena_reset(ctx));
+    HIP_TRY(ctx, s.timer.create());
+    bool ok = true;
+    auto take = [&](size_t bytes) {
+        void *q = arena_alloc(ctx, bytes);
+        ok = ok && q;
+        return q;
+    };
+    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
+    s.d_lde = (uint32_t *)take((size_t)s.V[0] * N * 4);
+    if (A) s.d_c = (uint32_t *)take((size_t)CW * n * 4), s.d_cl = (uint32_t *)take((size_t)CW * N * 4);
+    s.d_cw = (uint32_t *)take(4 * N * 4);   // H, then Q
+    s.d_hc = (uint32_t *)take(4 * N * 4);   // the coefficients of H's coordinates
+    s.d_seg = (uint32_t *)take((size_t)s.V[s.G - 1] * N * 4);
+    s.d_coef = (uint32_t *)take((size_t)(W + CW) * n * 4);   // the trace polynomials, then the columns' coordinates
+    s.d_weights = (uint64_t *)take(8 * 4 * (size_t)s.NW);
+    s.d_blob = (uint32_t *)take(s.H.blob.size() * 4);
+    for (uint32_t k = 0; k < s.G; k++) s.tree[k] = (uint8_t *)take(2 * s.leaves * 32);
+    if (A) s.d_atmp = (uint8_t *)take(xargs_columns_tmp_size(A, n));
+    s.d_tab2 = (uint32_t *)take(deep_eval_tab_words(2) * 4), s.d_tab1 = (uint32_t *)take(deep_eval_tab_words(1) * 4);
+    s.d_part = (uint32_t *)take(part_a > part_b ? part_a : part_b);
+    s.d_res = (uint32_t *)take((size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | the segments' coordinates at z, e-major
+    s.d_ctab = (uint32_t *)take(deep_args_tab_words(W, A, D) * 4);
+    if (s.H.dev.Q) s.d_ptab = (uint32_t *)take(s.H.per.table_words * 4), s.d_pvals = (uint32_t *)take(s.H.per.vals.size() * 4);
+    if (!ok) return smi_fail(ctx, SMI_ERR_OOM, (std::string(s.name) + ": device memory").c_str());
+    s.cols[0] = s.d_lde, s.cols[1] = A ? s.d_cl : s.d_seg, s.cols[2] = s.d_seg;
+    return SMI_OK;
+}
+
+// group k's V[k] columns -> tree[k]: 2 N digests over row leaves, 2 (N / 4) over coset leaves; deep_root_read queues the
+// copy of its root to roots + 32 k (a stage mark may stand between the two)
+int deep_commit(DeepProver &s, uint32_t k) {
+    return s.cosets ? launch_merkle_cosets(s.ctx, s.cols[k], s.V[k], s.N, s.N, s.tree[k]) : launch_merkle_rows(s.ctx, s.cols[k], s.V[k], s.N, s.N, s.tree[k]);
+}
+hipError_t deep_root_read(DeepProver &s, uint32_t k) {
+    return hipMemcpyAsync(s.roots + 32 * k, s.tree[k] + (2 * s.leaves - 2) * 32, 32, hipMemcpyDeviceToHost, s.ctx->stream);
+}
+
+// the round trip of root_1; the periodic tables and the trace polynomials (for the values at z) are queued before the host waits
+int deep_root1(DeepProver &s) {
+    smi_ctx *ctx = s.ctx;
+    HIP_TRY(ctx, deep_root_read(s, 0));
+    SMI_TRY(air_periodic_tables(ctx, s.cfg, s.H, s.d_pvals, s.d_ptab));
+    SMI_TRY(dev_ntt(ctx, s.d_trace, s.d_coef, s.log_n, s.n, s.W, s.n, s.n, 1, s.cfg->trace_offset, 1));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SMI_OK;
+}
+
+// a list: root_1 -> alpha, gamma -> the auxiliary columns, extended and committed (a stage of their own); root_2 and the
+// columns' verdicts -> the weights
+int deep_list_columns(DeepProver &s, uint32_t *closes) {
+    smi_ctx *ctx = s.ctx;
+    const smi_stark_cfg *cfg = s.cfg;
+    std::vector<uint64_t> ch;   // 8 challenges
+    transcript_perm_challenges(s.tr, s.roots, &ch);
+    xargs_build(ctx->fs.F, s.g, s.xargs, s.W, s.air, s.H.per, ch.data(), &s.XD);
+    s.XD.pvals = s.d_pvals;   // the raw periodic values the column build reads
+    SMI_TRY(xargs_columns_launch(ctx, s.XD, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
+    SMI_TRY(smi_dev_lde(ctx, s.d_c, s.CW, s.log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, s.d_cl));
+    SMI_TRY(deep_commit(s, 1));
+    s.timer.mark();
+    ArgsFlags fl;
+    HIP_TRY(ctx, deep_root_read(s, 1));
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(s.d_atmp, s.A, s.n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    SMI_TRY(dev_ntt(ctx, s.d_c, s.d_coef + (size_t)s.W * s.n, s.log_n, s.n, s.CW, s.n, s.n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SMI_TRY(xargs_columns_settle(ctx, s.XD, fl, closes));
+    transcript_args_weights(s.tr, s.roots + 32, s.W, s.K, s.A, &s.weights);
+    return SMI_OK;
+}
+
+// H on the N points into d_cw: the AIR's quotients under s.weights, plus the list's 2 A auxiliary quotients
+int deep_compose_h(DeepProver &s) {
+    smi_ctx *ctx = s.ctx;
+    const size_t N = s.N;
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_weights, s.weights.data(), 8 * s.weights.size(), hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(air_compose_ext_launch(ctx, s.H, s.d_blob, s.d_lde, N, s.d_weights, s.d_cw, N));
+    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, s.d_weights + 4 * (size_t)(s.W + s.K), s.d_cw, N));
+    return SMI_OK;
+}
+
+// the coefficients of every coordinate of H on the coset
+int deep_h_coefficients(DeepProver &s) { return dev_ntt(s.ctx, s.d_cw, s.d_hc, s.log_N, s.N, 4, s.N, s.N, 1, s.cfg->lde_offset, 1); }
+
+// the segments: D slices of n of those coefficients, each extended back to the N points
+int deep_segments(DeepProver &s) {
+    SMI_TRY(deep_h_coefficients(s));
+    for (uint32_t j = 0; j < s.D; j++)
+        SMI_TRY(dev_ntt(s.ctx, s.d_hc + (size_t)j * s.n, s.d_seg + 4 * (size_t)j * s.N, s.log_N, s.n, 4, s.N, s.N, 0, s.cfg->lde_offset, 1));
+    return SMI_OK;
+}
+
+// the round trip of the segments' root -> z
+int deep_draw_z(DeepProver &s, uint8_t *roots_out) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t k = s.G - 1;
+    HIP_TRY(ctx, deep_root_read(s, k));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t zr[4];
+    if (s.A) deep_args_transcript_z(s.tr, s.roots + 32 * k, s.NW, zr);
+    else deep_transcript_z(s.tr, s.roots + 32 * k, s.W, s.K, zr);
+    s.z = fqh_of(zr, s.p);
+    if (fqh_in_base(s.z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
+    if (roots_out) memcpy(roots_out, s.roots, 32 * (size_t)s.G);
+    return SMI_OK;
+}
+
+// the record: u, v = f(z), f(z w) of the trace; a, b = c(z), c(z w) of the auxiliary columns; s_j = the segments at z.
+// Coordinate e of the D segments is D columns of n coefficients at d_src + e src_pitch, src_stride apart.
+int deep_values_at_z(DeepProver &s, const uint32_t *d_src, size_t src_pitch, size_t src_stride, uint64_t *ood_out) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t W = s.W, A = s.A, CW = s.CW, D = s.D, p = s.p, g = s.g;
+    const size_t n = s.n;
+    const FqH pts[2] = {s.z, fqh_scale(s.z, s.w_n, p)};
+    std::vector<uint32_t> tab2, tab1, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
+    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
+    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_eval_enqueue(ctx, s.d_coef, W + CW, n, n, 2, s.d_tab2, s.d_part, s.d_res));
+    uint32_t *d_sres = s.d_res + 8 * (size_t)(W + CW);
+    for (uint32_t e = 0; e < 4; e++) SMI_TRY(deep_eval_enqueue(ctx, d_src + e * src_pitch, D, n, src_stride, 1, s.d_tab1, s.d_part, d_sres + 4 * (size_t)e * D));
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), s.d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    s.ood.assign(s.n_ood, 0);
+    uint64_t *ood = s.ood.data();
+    const FqH X{{0, 1 % p, 0, 0}};
+    auto assemble = [&](const uint32_t *at, size_t pitch, uint64_t *dst) {   // sum_e X^e v_e, v_e four words at at + e pitch
+        FqH sum = fqh(0), xe = fqh(1 % p);
+        for (uint32_t e = 0; e < 4; e++) {
+            const uint32_t *v = at + e * pitch;
+            sum = fqh_add(sum, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
+            xe = fqh_mul(xe, X, p, g);
+        }
+        for (uint32_t e = 0; e < 4; e++) dst[e] = sum.c[e];
+    };
+    for (uint32_t c = 0; c < W; c++)
+        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
+    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
+        assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
+        assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
+    }
+    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
+    if (ood_out) memcpy(ood_out, ood, 8 * s.n_ood);
+    return SMI_OK;
+}
+
+// the record -> the gammas and FRI's seed; the DEEP codeword Q into d_cw
+int deep_codeword(DeepProver &s) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t W = s.W, A = s.A, D = s.D, h = (uint32_t)s.cfg->lde_offset;
+    const size_t N = s.N;
+    std::vector<uint64_t> gammas;
+    if (A) deep_args_transcript_gammas(s.tr, s.ood.data(), s.NW, s.n_ood, &gammas);
+    else deep_transcript_gammas(s.tr, s.ood.data(), W, s.K, D, &gammas);
+    s.seed = s.tr.seed();
+    if (A) deep_compose_args_build(ctx->fs.F, s.g, W, A, D, s.w_n, s.z, s.ood.data(), gammas.data(), &s.ctab);
+    else deep_compose_build(ctx->fs.F, s.g, W, D, s.w_n, s.z, s.ood.data(), gammas.data(), &s.ctab);
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_ctab, s.ctab.data(), s.ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (A) return deep_compose_args_enqueue(ctx, W, A, D, s.log_N, h, s.d_ctab, s.d_lde, N, s.d_cl, N, s.d_seg, N, s.d_cw, N);
+    return deep_compose_enqueue(ctx, W, D, s.log_N, h, s.d_ctab, s.d_lde, N, s.d_seg, N, s.d_cw, N);
+}
+
+// the head of the proof: tag 2 | the record's length | its values
+void deep_record_header(DeepProver &s) {
+    std::vector<uint8_t> &bytes = s.bytes;
+    bytes.assign(9 + 8 * s.n_ood, 0);
+    bytes[0] = 2;
+    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)s.n_ood >> (8 * i));
+    for (size_t v = 0; v < s.n_ood; v++)
+        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(s.ood[v] >> (8 * i));
+}
+
+// FRI over the codeword where it stands (stride N: no compaction copy); the proof so far: header | FRI's stream
+int deep_fri(DeepProver &s, uint32_t grind_bits, uint64_t *top_indices) {
+    smi_ctx *ctx = s.ctx;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, s.cfg, 1ull << s.cfg->log_blowup);
+    if (s.cosets) SMI_TRY(fri_run_ext_fold4(ctx, &fc, &s.seed, s.d_cw, s.N, s.N, false, &s.fri, grind_bits));
+    else SMI_TRY(fri_run_ext(ctx, &fc, &s.seed, s.d_cw, s.N, s.N, false, &s.fri, (int)grind_bits));
+    deep_record_header(s);
+    s.bytes.insert(s.bytes.end(), s.fri.proof.begin(), s.fri.proof.end());
+    if (top_indices) memcpy(top_indices, s.fri.top.data(), 8 * (size_t)s.cfg->num_colinearity_tests);
+    return SMI_OK;
+}
+
+// every group at FRI's top-level indices, appended to the proof: row leaves by one launch a group (R = 2 rows a test), coset
+// leaves by one launch for all groups (one leaf and one path per test and group)
+int deep_open(DeepProver &s) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t t = (uint32_t)s.cfg->num_colinearity_tests, R = 2, log_N = s.log_N;
+    if (!t) return SMI_OK;
+    size_t at[3] = {0, 0, 0}, total = 0;   // group k's section in the openings
+    for (uint32_t k = 0; k < s.G; k++) {
+        at[k] = total;
+        total += s.cosets ? (size_t)mg_coset_open_bytes(s.V[k], t, log_N) : (size_t)mg_row_open_bytes(s.V[k], t, log_N, R);
+    }
+    uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
+    uint8_t *d_open = (uint8_t *)arena_alloc(ctx, total);
+    if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, (std::string(s.name) + (s.cosets ? ": coset openings" : ": row openings")).c_str());
+    HIP_TRY(ctx, hipMemcpyAsync(d_top, s.fri.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
+    if (s.cosets) {
+        MgCosetTable tab;
+        memset(&tab, 0, sizeof tab);
+        for (uint32_t k = 0; k < s.G; k++) tab.g[k] = MgCosetGroup{s.cols[k], s.N, s.tree[k], at[k], s.V[k], 0};
+        coset_open_kernel<<<dim3(t, s.G), 64, 0, ctx->stream>>>(tab, log_N, d_top, t, d_open);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        for (uint32_t k = 0; k < s.G; k++)
+            SMI_TRY(launch_air_row_open(ctx, s.cols[k], s.N, s.V[k], s.tree[k], log_N, d_top, t, R, 1ull << s.cfg->log_blowup, d_open + at[k]));
+    }
+    const size_t end = s.bytes.size();
+    s.bytes.resize(end + total);
+    HIP_TRY(ctx, hipMemcpyAsync(s.bytes.data() + end, d_open, total, hipMemcpyDeviceToHost, ctx->stream));
+    return SMI_OK;
+}
+
+// the last mark, the prover's final wait, the stage times and the proof
+int deep_finish(DeepProver &s, uint8_t **proof, size_t *proof_len, double *stage_ms) {
+    s.timer.mark();
+    HIP_TRY(s.ctx, hipStreamSynchronize(s.ctx->stream));
+    s.timer.write(stage_ms);
+    return smi_proof_out(s.ctx, s.bytes, proof, proof_len);
+}
+
+// {row leaves, coset leaves} x {plain AIR (xargs == nullptr), argument list}
+int deep_prove(smi_ctx *ctx, const char *name, bool cosets, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *d_trace_cols,
+               uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits,
+               uint32_t *closes) {
     if (closes) *closes = 0;
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(deep_field_check(ctx));
@@ -686,402 +638,151 @@ int deep_fold4_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air,
         const int rc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why) : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
         if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     }
-    if (xargs) SMI_TRY(xargs_entry_checks(ctx, air, xargs, cfg->n_cols, cfg->log_n));
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs ? xargs->count : 0, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
-    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the auxiliary tree
-    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
-    if (fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_FOLD4_NO_LAYER);
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N, q = N / 4;
-    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
-    const uint32_t G = A ? 3 : 2, n_stages = A ? 8 : 7;
-    AirHost H;
-    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
-    SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (uint32_t i = 0; i <= n_stages; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    uint32_t marks = 0;
-    auto mark = [&]() {
-        if (timed) (void)hipEventRecord(evs.ev[marks], ctx->stream);
-        marks++;
-    };
+    DeepProver s(ctx, xargs ? 8 : 7, stage_ms != nullptr);
+    s.cfg = cfg, s.air = air, s.xargs = xargs, s.name = name, s.cosets = cosets, s.d_trace = d_trace_cols;
+    SMI_TRY(deep_shapes(s, D, DEEP_FOLD4_NO_LAYER));
+    SMI_TRY(deep_setup(s));
+    s.timer.mark();
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, s.W, s.log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, s.d_lde));
+    s.timer.mark();
+    SMI_TRY(deep_commit(s, 0));
+    s.timer.mark();
+    SMI_TRY(deep_root1(s));
+    if (xargs) SMI_TRY(deep_list_columns(s, closes));   // marks the auxiliary stage
+    else deep_transcript_weights(s.tr, s.roots, s.W, s.K, &s.weights);
+    SMI_TRY(deep_compose_h(s));
+    s.timer.mark();
+    SMI_TRY(deep_segments(s));
+    SMI_TRY(deep_commit(s, s.G - 1));
+    s.timer.mark();
+    SMI_TRY(deep_draw_z(s, roots_out));
+    SMI_TRY(deep_values_at_z(s, s.d_hc, s.N, s.n, ood_out));
+    SMI_TRY(deep_codeword(s));
+    s.timer.mark();
+    SMI_TRY(deep_fri(s, grind_bits, top_indices));
+    s.timer.mark();
+    SMI_TRY(deep_open(s));
+    return deep_finish(s, proof, proof_len, stage_ms);
+}
 
-    const size_t n_ood = deep_args_record(W, A, D);
-    const size_t tree_bytes = 2 * q * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
-    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_c = A ? (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4) : nullptr;
-    uint32_t *d_cl = A ? (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4) : nullptr;
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // H, then Q
-    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);        // the coefficients of H's coordinates
-    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, 4 * (size_t)D * N * 4);
-    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)(W + CW) * n * 4);   // the trace polynomials, then the columns' coordinates
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree[3] = {nullptr, nullptr, nullptr};   // in group order: trace, (auxiliary,) segments
-    for (uint32_t k = 0; k < G; k++) tree[k] = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint8_t *d_atmp = A ? (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_size(A, n)) : nullptr;
-    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
-    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
-    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | H_{j,e} at z, e-major
-    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_args_tab_words(W, A, D) * 4);
-    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
-    if (H.dev.Q) {
-        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    }
-    if (!d_lde || (A && (!d_c || !d_cl || !d_atmp)) || !d_cw || !d_hc || !d_seg || !d_coef || !d_weights || !d_blob || !tree[0] || !tree[1] || (A && !tree[2]) ||
-        !d_tab2 || !d_tab1 || !d_part || !d_res || !d_ctab || (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_fold4: device memory");
-    auto root_of = [&](uint32_t k, uint8_t *dst) { return hipMemcpyAsync(dst, tree[k] + (2 * q - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream); };
-    mark();
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark();
-    SMI_TRY(launch_merkle_cosets(ctx, d_lde, W, N, N, tree[0]));
-    mark();
-    // root_1 -> the composition weights (plain AIR) or alpha, gamma (list)
-    uint8_t roots[96];
-    HIP_TRY(ctx, root_of(0, roots));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
-    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for the values at z
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> ch, weights, gammas;
-    XArgsDev XD;
-    if (A) {
-        transcript_perm_challenges(tr, roots, &ch);
-        xargs_build(ctx->fs.F, g, xargs, W, air, H.per, ch.data(), &XD);
-        XD.pvals = d_pvals;
-        SMI_TRY(xargs_columns_launch(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
-        SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
-        SMI_TRY(launch_merkle_cosets(ctx, d_cl, CW, N, N, tree[1]));
-        mark();
-        // root_2 (and the columns' verdicts) -> the weights
-        ArgsFlags fl;
-        HIP_TRY(ctx, root_of(1, roots + 32));
-        HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
-        SMI_TRY(dev_ntt(ctx, d_c, d_coef + (size_t)W * n, log_n, n, CW, n, n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        SMI_TRY(xargs_columns_settle(ctx, XD, fl, closes));
-        transcript_args_weights(tr, roots + 32, W, K, A, &weights);
-    } else {
-        deep_transcript_weights(tr, roots, W, K, &weights);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    if (A) SMI_TRY(xargs_compose_launch(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    mark();
-    // the segments: coefficients of every coordinate of H on the coset, D slices of n, each extended back to the N points
-    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
-    for (uint32_t j = 0; j < D; j++)
-        SMI_TRY(dev_ntt(ctx, d_hc + (size_t)j * n, d_seg + 4 * (size_t)j * N, log_N, n, 4, N, N, 0, cfg->lde_offset, 1));
-    SMI_TRY(launch_merkle_cosets(ctx, d_seg, 4 * D, N, N, tree[G - 1]));
-    mark();
-    // the segments' root -> z
-    HIP_TRY(ctx, root_of(G - 1, roots + 32 * (G - 1)));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t zr[4];
-    if (A) deep_args_transcript_z(tr, roots + 64, NW, zr);
-    else deep_transcript_z(tr, roots + 32, W, K, zr);
-    const FqH z = fqh_of(zr, p);
-    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
-    if (roots_out) memcpy(roots_out, roots, 32 * (size_t)G);
-    // u, v = f(z), f(z w); a, b = c(z), c(z w); s = H_j(z)
-    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
-    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
-    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
-    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W + CW, n, n, 2, d_tab2, d_part, d_res));
-    uint32_t *d_sres = d_res + 8 * (size_t)(W + CW);
-    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D segments: D columns of n coefficients, n apart
-        SMI_TRY(deep_eval_enqueue(ctx, d_hc + (size_t)e * N, D, n, n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * D));
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> ood(n_ood);
-    const FqH X{{0, 1 % p, 0, 0}};
-    auto assemble = [&](const uint32_t *at, size_t pitch, uint64_t *dst) {   // sum_e X^e v_e, v_e four words at at + e pitch
-        FqH s = fqh(0), xe = fqh(1 % p);
-        for (uint32_t e = 0; e < 4; e++) {
-            const uint32_t *v = at + e * pitch;
-            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
-            xe = fqh_mul(xe, X, p, g);
-        }
-        for (uint32_t e = 0; e < 4; e++) dst[e] = s.c[e];
-    };
-    for (uint32_t c = 0; c < W; c++)
-        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
-    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
-        assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
-        assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
-    }
-    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
-    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
-    if (A) deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
-    else deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
-    const FsSeed seed = tr.seed();
-    if (A) {
-        deep_compose_args_build(ctx->fs.F, g, W, A, D, w_n, z, ood.data(), gammas.data(), &ctab);
-        HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(deep_compose_args_enqueue(ctx, W, A, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_cl, N, d_seg, N, d_cw, N));
-    } else {
-        deep_compose_build(ctx->fs.F, g, W, D, w_n, z, ood.data(), gammas.data(), &ctab);
-        HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_seg, N, d_cw, N));
-    }
-    mark();
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext_fold4(ctx, &fc, &seed, d_cw, N, N, false, &xres, grind_bits));
-    std::vector<uint8_t> bytes(9 + 8 * n_ood);
-    bytes[0] = 2;
-    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
-    for (size_t v = 0; v < n_ood; v++)
-        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
-    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark();
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests;
-        const DeepGroups gr = deep_groups(W, A, D);
-        const uint32_t *cols[3] = {d_lde, A ? d_cl : d_seg, d_seg};
-        MgCosetTable tab;
-        memset(&tab, 0, sizeof tab);
-        size_t total = 0;
-        for (uint32_t k = 0; k < G; k++) {
-            tab.g[k] = MgCosetGroup{cols[k], N, tree[k], total, gr.V[k], 0};
-            total += (size_t)mg_coset_open_bytes(gr.V[k], t, log_N);
-        }
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, total);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_fold4: coset openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        coset_open_kernel<<<dim3(t, G), 64, 0, ctx->stream>>>(tab, log_N, d_top, t, d_open);
-        HIP_TRY(ctx, hipGetLastError());
-        const size_t at = bytes.size();
-        bytes.resize(at + total);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    mark();
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (uint32_t i = 0; i < n_stages; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
-    return smi_proof_out(ctx, bytes, proof, proof_len);
+// ---- zero-knowledge DEEP proofs (include/stark_mi.h, "Zero-knowledge DEEP proofs")
+// The coset-leaf plain prover with the four changes of the section, each a step of zk_prove: the last k_t rows of the trace
+// overwritten in place and the derived AIR composed in the caller's place; the masked split (zk_segments_kernel) for the
+// slices of n; the mask polynomial R extended with the segments and added to the DEEP codeword by zk_mask_add_kernel; one
+// salt column in each tree.  Every random value comes from smi_dev_random_fill under the caller's seed and one of the
+// ZK_STREAM_* identifiers.
+struct ZkBuffers {
+    uint32_t *d_rows, *d_rho, *d_sc;   // the randomiser rows; the split's masks; n coefficients a column: 4 D' of the segments, 4 of R
+};
+
+// the randomisers: column c takes elements c k_t .. (c + 1) k_t - 1 of their stream in its last k_t rows; the two salts
+int zk_randomise(DeepProver &s, const uint8_t seed[32], uint32_t kt, const ZkBuffers &zb, uint32_t *d_trace_cols) {
+    smi_ctx *ctx = s.ctx;
+    const size_t n = s.n, N = s.N;
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_ROWS, zb.d_rows, (size_t)s.W * kt));
+    HIP_TRY(ctx, hipMemcpy2DAsync(d_trace_cols + (n - kt), n * 4, zb.d_rows, (size_t)kt * 4, (size_t)kt * 4, s.W, hipMemcpyDeviceToDevice, ctx->stream));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT1, s.d_lde + (size_t)s.W * N, N));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT2, s.d_seg + (size_t)(s.V[1] - 1) * N, N));
+    return SMI_OK;
+}
+
+// the masked segments (D_h: the segments of H before masking) and R as coefficients, then one batched extension a polynomial
+int zk_segments(DeepProver &s, const uint8_t seed[32], uint32_t D_h, uint32_t ks, const ZkBuffers &zb) {
+    smi_ctx *ctx = s.ctx;
+    const uint32_t Dp = s.D;
+    const size_t n = s.n, N = s.N;
+    SMI_TRY(deep_h_coefficients(s));
+    if (Dp > 1) SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_RHO, zb.d_rho, (size_t)4 * (Dp - 1) * ks));
+    SMI_TRY(smi_dev_zk_segments(ctx, s.d_hc, N, (size_t)D_h * n, s.log_n, ks, Dp, zb.d_rho, zb.d_sc, n));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_MASK, zb.d_sc + (size_t)4 * Dp * n, 4 * n));
+    for (uint32_t c = 0; c < s.V[1] - 1; c += 4)
+        SMI_TRY(dev_ntt(ctx, zb.d_sc + (size_t)c * n, s.d_seg + (size_t)c * N, s.log_N, n, 4, n, N, 0, s.cfg->lde_offset, 1));
+    return SMI_OK;
+}
+
+int zk_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots_out, uint64_t *ood_out,
+             uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(deep_field_check(ctx));
+    uint32_t D_h = 0, Dp = 0, kt = 0, ks = 0;
+    std::string why;
+    int rc = zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, &kt, &ks, &why, &D_h);
+    if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    DeepProver s(ctx, 9, stage_ms != nullptr);
+    s.cfg = cfg, s.air = air0, s.name = "air_prove_deep_zk", s.cosets = true, s.d_trace = d_trace_cols;
+    SMI_TRY(deep_shapes(s, Dp, ZK_NO_LAYER));
+    s.V[0] = s.W + 1, s.V[1] = 4 * Dp + 5;   // the trace and its salt column; the segments, R and their salt column
+    ZkAir Z;
+    rc = zk_derive_air(s.p, s.w_n, cfg, air0, &Z, &why);
+    if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
+    s.air = &Z.air;   // K stays the caller's: the weights are drawn for the caller's constraints
+    SMI_TRY(deep_setup(s));
+    ZkBuffers zb;
+    zb.d_rows = (uint32_t *)arena_alloc(ctx, (size_t)s.W * kt * 4);
+    zb.d_rho = (uint32_t *)arena_alloc(ctx, (size_t)4 * Dp * ks * 4);
+    zb.d_sc = (uint32_t *)arena_alloc(ctx, (size_t)(s.V[1] - 1) * s.n * 4);
+    if (!zb.d_rows || !zb.d_rho || !zb.d_sc) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: device memory");
+    s.timer.mark();
+    SMI_TRY(zk_randomise(s, seed, kt, zb, d_trace_cols));
+    s.timer.mark();
+    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, s.W, s.log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, s.d_lde));
+    s.timer.mark();
+    SMI_TRY(deep_commit(s, 0));
+    s.timer.mark();
+    SMI_TRY(deep_root1(s));
+    deep_transcript_weights(s.tr, s.roots, s.W, s.K, &s.weights);
+    SMI_TRY(deep_compose_h(s));
+    s.timer.mark();
+    SMI_TRY(zk_segments(s, seed, D_h, ks, zb));
+    SMI_TRY(deep_commit(s, 1));
+    s.timer.mark();
+    SMI_TRY(deep_draw_z(s, roots_out));
+    SMI_TRY(deep_values_at_z(s, zb.d_sc, s.n, 4 * s.n, ood_out));   // the masked segments: coordinate e of segment j is column 4 j + e
+    SMI_TRY(deep_codeword(s));
+    s.timer.mark();
+    SMI_TRY(zk_mask_add_launch(ctx, s.d_cw, s.N, s.d_seg + (size_t)4 * Dp * s.N, s.N, s.N));   // Q' = Q + R
+    s.timer.mark();
+    SMI_TRY(deep_fri(s, grind_bits, top_indices));
+    s.timer.mark();
+    SMI_TRY(deep_open(s));
+    return deep_finish(s, proof, proof_len, stage_ms);
 }
 }  // namespace
 
+int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots_out, uint64_t *ood_out,
+                           uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return deep_prove(ctx, "air_prove_deep", false, cfg, (const smi_air *)air, nullptr, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices, stage_ms,
+                      grind_bits, nullptr);
+}
+int smi_dev_air_prove_deep_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols, uint8_t *roots_out,
+                                 uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits,
+                                 uint32_t *closes) {
+    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return deep_prove(ctx, "air_prove_deep_xargs", false, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, roots_out, ood_out, proof,
+                      proof_len, top_indices, stage_ms, grind_bits, closes);
+}
 int smi_dev_air_prove_deep_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots_out, uint64_t *ood_out,
                                  uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
     if (!ctx || !cfg || !air || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
-    return deep_fold4_prove(ctx, cfg, (const smi_air *)air, nullptr, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices, stage_ms, grind_bits,
-                            nullptr);
+    return deep_prove(ctx, "air_prove_deep_fold4", true, cfg, (const smi_air *)air, nullptr, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices,
+                      stage_ms, grind_bits, nullptr);
 }
 int smi_dev_air_prove_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_trace_cols,
                                        uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
                                        uint32_t grind_bits, uint32_t *closes) {
     if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !proof || !proof_len) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
-    return deep_fold4_prove(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, roots_out, ood_out, proof, proof_len, top_indices,
-                            stage_ms, grind_bits, closes);
+    return deep_prove(ctx, "air_prove_deep_fold4", true, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, roots_out, ood_out, proof,
+                      proof_len, top_indices, stage_ms, grind_bits, closes);
 }
-
-// ---- zero-knowledge DEEP proofs (include/stark_mi.h, "Zero-knowledge DEEP proofs")
-// deep_fold4_prove for a plain AIR with the four changes of the section: the last k_t rows of the trace overwritten in place
-// and the derived AIR composed in the caller's place; the masked split (zk_segments_kernel) for the slices of n; the mask
-// polynomial R extended with the segments and added to the DEEP codeword by zk_mask_add_kernel; one salt column in each tree.
-// Every random value comes from smi_dev_random_fill under the caller's seed and one of the ZK_STREAM_* identifiers.
-int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots_out,
+int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots_out,
                               uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
-    const smi_air *air0 = (const smi_air *)air_;
-    if (!ctx || !cfg || !air0 || !d_trace_cols || !seed || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    if (!ctx || !cfg || !air || !d_trace_cols || !seed || !proof || !proof_len) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
-    SMI_TRY(grind_bits_check(ctx, grind_bits));
-    SMI_TRY(deep_field_check(ctx));
-    uint32_t D = 0, Dp = 0, kt = 0, ks = 0;
-    {
-        std::string why;
-        const int rc = zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, &kt, &ks, &why, &D);
-        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    }
-    const uint32_t W = cfg->n_cols, K = air0->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
-    if (log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
-    if (fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, ZK_NO_LAYER);
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N, q = N / 4;
-    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, log_n);
-    const uint32_t V1 = W + 1, V2 = 4 * Dp + 5, n_stages = 9;
-    ZkAir Z;
-    {
-        std::string why;
-        const int rc = zk_derive_air(p, w_n, cfg, air0, &Z, &why);
-        if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    }
-    const smi_air *air = &Z.air;
-    AirHost H;
-    air_build(ctx->fs.F, h_root(ctx, log_N), cfg, air, &H);
-    SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (uint32_t i = 0; i <= n_stages; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    uint32_t marks = 0;
-    auto mark = [&]() {
-        if (timed) (void)hipEventRecord(evs.ev[marks], ctx->stream);
-        marks++;
-    };
-
-    const size_t n_ood = 4 * (2 * (size_t)W + Dp);
-    const size_t tree_bytes = 2 * q * 32, w_tab1 = deep_eval_tab_words(1), w_tab2 = deep_eval_tab_words(2);
-    const size_t part_a = deep_eval_part_bytes(W, n, 2), part_b = deep_eval_part_bytes(Dp, n, 1);
-    uint32_t *d_rows = (uint32_t *)arena_alloc(ctx, (size_t)W * kt * 4);
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)V1 * N * 4);     // the trace, then the salt column
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);               // H, then Q, then Q + R
-    uint32_t *d_hc = (uint32_t *)arena_alloc(ctx, 4 * N * 4);               // the coefficients of H's coordinates
-    uint32_t *d_rho = (uint32_t *)arena_alloc(ctx, (size_t)4 * Dp * ks * 4);
-    uint32_t *d_sc = (uint32_t *)arena_alloc(ctx, (size_t)(V2 - 1) * n * 4);   // n coefficients a column: 4 D' of the segments, 4 of R
-    uint32_t *d_seg = (uint32_t *)arena_alloc(ctx, (size_t)V2 * N * 4);     // their extensions, then the salt column
-    uint32_t *d_coef = (uint32_t *)arena_alloc(ctx, (size_t)W * n * 4);
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)(W + K));
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree[2] = {(uint8_t *)arena_alloc(ctx, tree_bytes), (uint8_t *)arena_alloc(ctx, tree_bytes)};
-    uint32_t *d_tab2 = (uint32_t *)arena_alloc(ctx, w_tab2 * 4), *d_tab1 = (uint32_t *)arena_alloc(ctx, w_tab1 * 4);
-    uint32_t *d_part = (uint32_t *)arena_alloc(ctx, part_a > part_b ? part_a : part_b);
-    uint32_t *d_res = (uint32_t *)arena_alloc(ctx, (size_t)(8 * W + 16 * Dp) * 4);   // columns at z and z w | H~_{j,e} at z, e-major
-    uint32_t *d_ctab = (uint32_t *)arena_alloc(ctx, deep_tab_words(W, Dp) * 4);
-    uint32_t *d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-    uint32_t *d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    if (!d_rows || !d_lde || !d_cw || !d_hc || !d_rho || !d_sc || !d_seg || !d_coef || !d_weights || !d_blob || !tree[0] || !tree[1] || !d_tab2 || !d_tab1 ||
-        !d_part || !d_res || !d_ctab || !d_ptab || !d_pvals)
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: device memory");
-    auto root_of = [&](uint32_t k, uint8_t *dst) { return hipMemcpyAsync(dst, tree[k] + (2 * q - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream); };
-    mark();
-    // the randomisers: column c takes elements c k_t .. (c + 1) k_t - 1 of their stream in its last k_t rows; the two salts
-    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_ROWS, d_rows, (size_t)W * kt));
-    HIP_TRY(ctx, hipMemcpy2DAsync(d_trace_cols + (n - kt), n * 4, d_rows, (size_t)kt * 4, (size_t)kt * 4, W, hipMemcpyDeviceToDevice, ctx->stream));
-    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT1, d_lde + (size_t)W * N, N));
-    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT2, d_seg + (size_t)(V2 - 1) * N, N));
-    mark();
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark();
-    SMI_TRY(launch_merkle_cosets(ctx, d_lde, V1, N, N, tree[0]));
-    mark();
-    // root_1 -> the composition weights
-    uint8_t roots[64];
-    HIP_TRY(ctx, root_of(0, roots));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
-    SMI_TRY(dev_ntt(ctx, d_trace_cols, d_coef, log_n, n, W, n, n, 1, cfg->trace_offset, 1));   // the trace polynomials, for the values at z
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> weights, gammas;
-    deep_transcript_weights(tr, roots, W, K, &weights);
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    mark();
-    // the masked segments and R as coefficients, one batched extension, the second tree
-    SMI_TRY(dev_ntt(ctx, d_cw, d_hc, log_N, N, 4, N, N, 1, cfg->lde_offset, 1));
-    if (Dp > 1) SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_RHO, d_rho, (size_t)4 * (Dp - 1) * ks));
-    SMI_TRY(smi_dev_zk_segments(ctx, d_hc, N, (size_t)D * n, log_n, ks, Dp, d_rho, d_sc, n));
-    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_MASK, d_sc + (size_t)4 * Dp * n, 4 * n));
-    for (uint32_t c = 0; c < V2 - 1; c += 4)
-        SMI_TRY(dev_ntt(ctx, d_sc + (size_t)c * n, d_seg + (size_t)c * N, log_N, n, 4, n, N, 0, cfg->lde_offset, 1));
-    SMI_TRY(launch_merkle_cosets(ctx, d_seg, V2, N, N, tree[1]));
-    mark();
-    // root_2 -> z
-    HIP_TRY(ctx, root_of(1, roots + 32));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t zr[4];
-    deep_transcript_z(tr, roots + 32, W, K, zr);
-    const FqH z = fqh_of(zr, p);
-    if (fqh_in_base(z)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
-    if (roots_out) memcpy(roots_out, roots, 64);
-    // u, v = f(z), f(z w); s_j = H~_j(z)
-    const FqH pts[2] = {z, fqh_scale(z, w_n, p)};
-    std::vector<uint32_t> tab2, tab1, ctab, res(8 * (size_t)W + 16 * (size_t)Dp);
-    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
-    deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_eval_enqueue(ctx, d_coef, W, n, n, 2, d_tab2, d_part, d_res));
-    uint32_t *d_sres = d_res + 8 * (size_t)W;
-    for (uint32_t e = 0; e < 4; e++)   // coordinate e of the D' segments: D' columns of n coefficients, 4 n apart
-        SMI_TRY(deep_eval_enqueue(ctx, d_sc + (size_t)e * n, Dp, n, 4 * n, 1, d_tab1, d_part, d_sres + 4 * (size_t)e * Dp));
-    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> ood(n_ood);
-    const FqH X{{0, 1 % p, 0, 0}};
-    for (uint32_t c = 0; c < W; c++)
-        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
-    for (uint32_t j = 0; j < Dp; j++) {   // s_j = sum_e X^e H~_{j,e}(z)
-        FqH s = fqh(0), xe = fqh(1 % p);
-        for (uint32_t e = 0; e < 4; e++) {
-            const uint32_t *v = &res[8 * (size_t)W + 4 * ((size_t)e * Dp + j)];
-            s = fqh_add(s, fqh_mul(xe, FqH{{v[0], v[1], v[2], v[3]}}, p, g), p);
-            xe = fqh_mul(xe, X, p, g);
-        }
-        for (uint32_t e = 0; e < 4; e++) ood[4 * (2 * (size_t)W + j) + e] = s.c[e];
-    }
-    if (ood_out) memcpy(ood_out, ood.data(), 8 * n_ood);
-    deep_transcript_gammas(tr, ood.data(), W, K, Dp, &gammas);
-    const FsSeed fseed = tr.seed();
-    deep_compose_build(ctx->fs.F, g, W, Dp, w_n, z, ood.data(), gammas.data(), &ctab);
-    HIP_TRY(ctx, hipMemcpyAsync(d_ctab, ctab.data(), ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_compose_enqueue(ctx, W, Dp, log_N, (uint32_t)cfg->lde_offset, d_ctab, d_lde, N, d_seg, N, d_cw, N));
-    mark();
-    SMI_TRY(zk_mask_add_launch(ctx, d_cw, N, d_seg + (size_t)4 * Dp * N, N, N));   // Q' = Q + R
-    mark();
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext_fold4(ctx, &fc, &fseed, d_cw, N, N, false, &xres, grind_bits));
-    std::vector<uint8_t> bytes(9 + 8 * n_ood);
-    bytes[0] = 2;
-    for (int i = 0; i < 8; i++) bytes[1 + i] = (uint8_t)((uint64_t)n_ood >> (8 * i));
-    for (size_t v = 0; v < n_ood; v++)
-        for (int i = 0; i < 8; i++) bytes[9 + 8 * v + i] = (uint8_t)(ood[v] >> (8 * i));
-    bytes.insert(bytes.end(), xres.proof.begin(), xres.proof.end());
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark();
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests;
-        MgCosetTable tab;
-        memset(&tab, 0, sizeof tab);
-        const size_t ob1 = (size_t)mg_coset_open_bytes(V1, t, log_N), total = ob1 + (size_t)mg_coset_open_bytes(V2, t, log_N);
-        tab.g[0] = MgCosetGroup{d_lde, N, tree[0], 0, V1, 0};
-        tab.g[1] = MgCosetGroup{d_seg, N, tree[1], ob1, V2, 0};
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, total);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: coset openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        coset_open_kernel<<<dim3(t, 2), 64, 0, ctx->stream>>>(tab, log_N, d_top, t, d_open);
-        HIP_TRY(ctx, hipGetLastError());
-        const size_t at = bytes.size();
-        bytes.resize(at + total);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    mark();
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (uint32_t i = 0; i < n_stages; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
-    return smi_proof_out(ctx, bytes, proof, proof_len);
+    return zk_prove(ctx, cfg, (const smi_air *)air, d_trace_cols, seed, roots_out, ood_out, proof, proof_len, top_indices, stage_ms, grind_bits);
 }
+

@@ -90,6 +90,39 @@ struct ProfScope {
     }
 };
 
+// A prover's stage_ms: `count` stages between count + 1 events on the context's stream.  The events exist only when the
+// caller passed stage_ms (timed) and are destroyed on every return path.  HIP_TRY(ctx, timer.create()) once, mark() at each
+// stage boundary in order, write(stage_ms) after the prover's final hipStreamSynchronize: exactly `count` values.
+struct StageTimer {
+    smi_ctx *ctx;
+    std::vector<hipEvent_t> ev;   // empty when not timed
+    size_t next = 0;
+    StageTimer(smi_ctx *c, uint32_t count, bool timed) : ctx(c), ev(timed ? count + 1 : 0, nullptr) {}
+    ~StageTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    StageTimer(const StageTimer &) = delete;
+    StageTimer &operator=(const StageTimer &) = delete;
+    hipError_t create() {
+        for (hipEvent_t &e : ev) {
+            const hipError_t rc = hipEventCreate(&e);
+            if (rc != hipSuccess) return rc;
+        }
+        return hipSuccess;
+    }
+    void mark() {
+        if (next < ev.size()) (void)hipEventRecord(ev[next++], ctx->stream);
+    }
+    void write(double *stage_ms) const {
+        for (size_t i = 0; i + 1 < ev.size(); i++) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+            stage_ms[i] = ms;
+        }
+    }
+};
+
 // Every public entry point runs on the context's device whatever the caller's current device is
 // (a process may hold contexts on several GPUs, or torch may have selected another one), and
 // leaves the caller's selection as it found it.

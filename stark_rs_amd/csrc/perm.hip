@@ -302,17 +302,8 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
     const uint32_t NW = W + K + 2;
     SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 7; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+    StageTimer tm(ctx, 6, stage_ms != nullptr);
+    HIP_TRY(ctx, tm.create());
 
     const size_t tree_bytes = 2 * N * 32;
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
@@ -330,11 +321,11 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     }
     if (!d_lde || !d_z || !d_zl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_ptmp || (H.dev.Q && (!d_ptab || !d_pvals)))
         return smi_fail(ctx, SMI_ERR_OOM, "air_prove_perm: device memory");
-    mark(0);
+    tm.mark();
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
+    tm.mark();
     SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    mark(2);
+    tm.mark();
     // first round trip: root_1 -> alpha, gamma
     uint8_t roots[64];
     HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -348,7 +339,7 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     SMI_TRY(perm_column_enqueue(ctx, PD, d_trace_cols, log_n, d_z, n, d_ptmp));
     SMI_TRY(smi_dev_lde(ctx, d_z, 4, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_zl));
     SMI_TRY(launch_merkle_rows(ctx, d_zl, 4, N, N, tree2));
-    mark(3);
+    tm.mark();
     // second round trip: root_2 (and the column's verdicts) -> the weights and FRI's seed
     PermFlags fl;
     HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -361,13 +352,13 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
     SMI_TRY(perm_compose_enqueue(ctx, PD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_zl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    mark(4);
+    tm.mark();
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriExtResult xres;
     SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
     std::vector<uint8_t> &bytes = xres.proof;
     if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark(5);
+    tm.mark();
     if (cfg->num_colinearity_tests) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
         const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(4, t, log_N, R);
@@ -381,13 +372,8 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
         bytes.resize(at + ob1 + ob2);
         HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
     }
-    mark(6);
+    tm.mark();
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (int i = 0; i < 6; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
+    tm.write(stage_ms);
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }

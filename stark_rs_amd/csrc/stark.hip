@@ -115,18 +115,8 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
     const size_t N = (size_t)1 << log_N;
     const uint32_t T = cfg->row_leaves ? 1u : W;   // trees (and roots entering the transcript)
     SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    hipEvent_t *ev = evs.ev;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 5; i++) HIP_TRY(ctx, hipEventCreate(&ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(ev[i], ctx->stream); };
+    StageTimer tm(ctx, 4, stage_ms != nullptr);
+    HIP_TRY(ctx, tm.create());
 
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
     uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, N * 4);
@@ -143,12 +133,12 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
         trees[c] = tree_base + c * tree_stride;
         rootp[c] = trees[c] + (2 * N - 2) * 32;
     }
-    mark(0);
+    tm.mark();
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, cfg->log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
+    tm.mark();
     if (cfg->row_leaves) SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree_base));
     else SMI_TRY(launch_merkle_batch(ctx, d_lde, N, tree_base, W, N, tree_stride));
-    mark(2);
+    tm.mark();
     uint8_t *d_roots = (uint8_t *)arena_alloc(ctx, 32 * (size_t)T);
     if (!d_roots) return smi_fail(ctx, SMI_ERR_OOM, "stark_prove: device memory");
     if (cfg->row_leaves) {
@@ -182,7 +172,7 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
     } else {
         SMI_TRY(smi_dev_combine_columns(ctx, d_lde, W, N, N, d_weights, d_cw));
     }
-    mark(3);
+    tm.mark();
     FriRequest rq(&fc, d_cw, N, true);
     rq.reset_arena = false;
     rq.round0_src = fuse_combine ? &csrc : nullptr;
@@ -196,7 +186,7 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
     std::vector<uint8_t> &bytes = res.proof;
     if (top_indices) memcpy(top_indices, res.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
     else top_indices = res.top.data();   // the column openings need the top-level indices either way
-    mark(4);
+    tm.mark();
     if (cfg->open_columns && !cfg->row_leaves && cfg->num_colinearity_tests) {
         // the top-level indices are on the host now (fri_run synchronised): one more small launch
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests;
@@ -219,13 +209,9 @@ int smi_dev_stark_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint32_t *
         HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if (timed) {
+    if (stage_ms) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < 4; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-            stage_ms[i] = ms;
-        }
+        tm.write(stage_ms);
     }
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }

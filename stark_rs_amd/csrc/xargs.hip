@@ -378,17 +378,8 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
     const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the second tree
     SMI_TRY(arena_reset(ctx));
-    struct Events {   // destroyed on every return path
-        hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-        }
-    } evs;
-    const bool timed = stage_ms != nullptr;
-    if (timed)
-        for (int i = 0; i < 7; i++) HIP_TRY(ctx, hipEventCreate(&evs.ev[i]));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(evs.ev[i], ctx->stream); };
+    StageTimer tm(ctx, 6, stage_ms != nullptr);
+    HIP_TRY(ctx, tm.create());
 
     const size_t tree_bytes = 2 * N * 32;
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
@@ -406,11 +397,11 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     }
     if (!d_lde || !d_c || !d_cl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_atmp || (H.dev.Q && (!d_ptab || !d_pvals)))
         return smi_fail(ctx, SMI_ERR_OOM, "air_prove_xargs: device memory");
-    mark(0);
+    tm.mark();
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    mark(1);
+    tm.mark();
     SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    mark(2);
+    tm.mark();
     // first round trip: root_1 -> alpha, gamma
     uint8_t roots[64];
     HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -425,7 +416,7 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     SMI_TRY(xargs_columns_enqueue(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
     SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
     SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
-    mark(3);
+    tm.mark();
     // second round trip: root_2 (and the columns' verdicts) -> the weights and FRI's seed
     ArgsFlags fl;
     HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -438,13 +429,13 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
     SMI_TRY(xargs_compose_enqueue(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    mark(4);
+    tm.mark();
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriExtResult xres;
     SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
     std::vector<uint8_t> &bytes = xres.proof;
     if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    mark(5);
+    tm.mark();
     if (cfg->num_colinearity_tests) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
         const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R);
@@ -458,14 +449,9 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
         bytes.resize(at + ob1 + ob2);
         HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
     }
-    mark(6);
+    tm.mark();
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (timed)
-        for (int i = 0; i < 6; i++) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1]);
-            stage_ms[i] = ms;
-        }
+    tm.write(stage_ms);
     return smi_proof_out(ctx, bytes, proof, proof_len);
 }
 

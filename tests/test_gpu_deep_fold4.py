@@ -327,3 +327,66 @@ def test_one_prove_at_2_16(engines):
     m = bytearray(res["proof"])
     m[-1] ^= 1
     assert eng.air_verify(air, bytes(m), res["column_roots"], W, log_n, lb, t, grind_bits=8, **KW) == (False, d4.WORDS["auth"])
+
+
+# ---------------------------------------------------------------------------------------------- stage_ms of every DEEP prover
+def mimc_on_the_real_rows(n, t, p):
+    """air_periodic's MiMC lane with its second claim on the last real row n - k_t - 1: the zk plan refuses a claim on a
+    randomiser row"""
+    import air_periodic as ap
+    import zk_compose as zk
+    from stark_rs_amd.mirror import Air
+    x = ap.make("mimc", n, p)[1][0]
+    air = Air(1)
+    k = air.periodic(ap.round_constants(64, p))
+    air.transition({("next", 0): 1, ("cur", 0, 3): -1, (("cur", 0, 2), ("per", k)): -3, (("cur", 0), ("per", k, 2)): -3, ("per", k, 3): -1})
+    real = n - zk.k_t(t)
+    air.boundary(0, 0, x[0]).boundary(0, real - 1, x[real - 1])
+    return air, [x]
+
+
+# (entry point, the stages its section of include/stark_mi.h documents, log_blowup, statement)
+STAGE_CASES = [("deep", 7, 3, "mimc"), ("deep_xargs", 8, 2, "perm"), ("deep_fold4", 7, 2, "mimc"), ("deep_xargs_fold4", 8, 3, "lookup"),
+               ("deep_zk", 9, 2, "mimc")]
+
+
+@pytest.mark.parametrize("entry,count,lb,name", STAGE_CASES)
+def test_stage_ms_gets_exactly_the_documented_count(engines, entry, count, lb, name):
+    """smi_dev_air_prove_<entry> through the library handle with a stage_ms array one double longer than documented, all NaN
+    beforehand: `count` finite values >= 0, the extra double untouched, and the bytes of the same call with stage_ms null (zk:
+    under the same seed).  n = 2^6, two colinearity tests."""
+    import ctypes as C
+    from stark_rs_amd import engine
+    p, g = xc.PRIMES[0]
+    eng, log_n, t, seed = engines[p], 6, 2, bytes(range(32))
+    xa = None
+    if name == "mimc":
+        air, cols = mimc_on_the_real_rows(1 << log_n, t, p) if entry == "deep_zk" else make_air("mimc", 1 << log_n, p)
+        a = eng._air(air)
+    else:
+        air, cols, lst = statement(name, log_n, p)
+        a = eng._air(mirror(air, lst))
+        xa = engine.xargs_of(a)
+    cfg = eng._stark_cfg(len(cols), log_n, lb, t, 1, None, True)
+    prove = getattr(eng.L, "smi_dev_air_prove_" + entry)
+
+    def call(stage):
+        roots, ood, top = np.zeros((3, 32), dtype=np.uint8), np.zeros(4096, dtype=np.uint64), np.zeros(t, dtype=np.uint64)
+        proof, plen, closes = C.c_void_p(), C.c_size_t(), C.c_uint32()
+        with Dev(eng) as dev:
+            d = dev.upload(np.array(cols, dtype=np.uint64))
+            args = [eng.h, C.byref(cfg), C.byref(a)] + ([C.byref(xa)] if xa is not None else []) + [C.c_void_p(d)] + ([seed] if entry == "deep_zk" else [])
+            args += [roots.ctypes.data, ood.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data, stage, 0] + ([C.byref(closes)] if xa is not None else [])
+            status = prove(*args)
+            assert status == 0, (status, eng.L.smi_last_error(eng.h))
+            out = C.string_at(proof, plen.value)
+            eng.L.smi_free(proof)
+        return out
+
+    stage = (C.c_double * (count + 1))(*[float("nan")] * (count + 1))
+    timed = call(stage)
+    got = [float(v) for v in stage]
+    print(entry, got)
+    assert all(np.isfinite(v) and v >= 0 for v in got[:count]), got
+    assert np.isnan(got[count]), got
+    assert len(timed) > 9 and timed == call(None)

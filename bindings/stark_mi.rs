@@ -337,6 +337,13 @@ extern "C" {
     pub fn smi_air_deep_zk_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
     pub fn smi_dev_air_prove_deep_zk(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *mut u32, seed: *const u8, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
     pub fn smi_air_verify_deep_zk(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
+    pub fn smi_air_plan_deep_zk_xargs(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, degree: *mut u32, segments: *mut u32, k_t: *mut u32, k_s: *mut u32) -> c_int;
+    pub fn smi_air_deep_zk_xargs_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, folds: *mut u64, proof_len: *mut usize) -> c_int;
+    pub fn smi_dev_xargs_multiplicities_rows(ctx: *mut smi_ctx, air: *const c_void, xargs: *const c_void, a: u32, d_trace_cols: *const u32, n_cols: u32, log_n: u32, rows: usize, d_mult: *mut u32) -> c_int;
+    pub fn smi_dev_zk_args_tail(ctx: *mut smi_ctx, d_c: *mut u32, c_stride: usize, log_n: u32, k_t: u32, n_args: u32, d_rnd: *const u32, closing: *mut u64) -> c_int;
+    pub fn smi_dev_air_compose_zk_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_lde: *const u32, stride: usize, d_c_lde: *const u32, c_stride: usize, challenges: *const u64, d_weights: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_air_prove_deep_zk_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, d_trace_cols: *mut u32, seed: *const u8, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32, closes: *mut u32) -> c_int;
+    pub fn smi_air_verify_deep_zk_xargs(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_mgpu_unique_id(id: *mut u8) -> c_int;
     pub fn smi_mgpu_create(ctx: *mut smi_ctx, id: *const u8, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;
     pub fn smi_mgpu_create_with(ctx: *mut smi_ctx, ops: *const smi_mgpu_coll, rank: c_int, world: c_int, out: *mut *mut smi_mgpu) -> c_int;

@@ -1367,7 +1367,7 @@ int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, cons
  *   its path; canonical values (the salts are not looked at); Q + R recomputed at the four coset points against the
  *   layer-0 record.  A proof of smi_dev_air_prove_deep_fold4 is rejected here and a proof of this variant by
  *   smi_air_verify_deep_fold4: their records differ in length (D' > D).
- * Left out: argument lists; row leaves / fold 2; smi_mgpu_* twins; an AIR digest in the transcript. */
+ * Left out: row leaves / fold 2; smi_mgpu_* twins; an AIR digest in the transcript.  Argument lists: the next section. */
 /* Host only: *degree = d and *segments = D' for the derived AIR, *k_t and *k_s for cfg->num_colinearity_tests (outputs are
  * optional). */
 int smi_air_plan_deep_zk(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments, uint32_t *k_t, uint32_t *k_s);
@@ -1387,6 +1387,92 @@ int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
                               uint64_t *ood, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
 int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len,
                            int *accept, uint32_t grind_bits);
+
+/* ---- Zero-knowledge DEEP proofs with an argument list -------------------------------------------------------------------
+ * The zero-knowledge variant of "Out-of-domain sampling over coset leaves" for an smi_air_xargs list (FRI folding factor 4).
+ * Notation is that of "Zero-knowledge DEEP proofs" and of "Out-of-domain sampling with an argument list"; the recurrences,
+ * T_a and init_a (1 for a permutation, 0 for a lookup) are those of "Argument list with selectors and periodic members".
+ * The plain variant cannot simply derive a list: an auxiliary column c_a wraps around over all n rows, is a deterministic
+ * function of the trace and two challenges, and is opened at the queried points, at z and at z w.  So c_a gets randomiser
+ * rows of its own, a transition that is exempt on them, and a closing condition that no longer rests on the wrap.
+ * Rows.  k_t = 8 t + 16 (the plain variant keeps 8 t + 8), k_s = 4 t + 1, n_a = n - k_t active rows.  The statement covers
+ *   the main transitions on the row pairs (r, r + 1), r <= n_a - 2, boundary points on rows < n_a, and every argument over
+ *   the rows < n_a only.  Why 16: a coordinate column of c_a has k_t - 1 free rows (below) and is revealed through 8 t + 8
+ *   base-field functionals -- 4 t queried points, 4 t points w x through H, and z and z w, four each.
+ * Trace randomisers.  Stream 1, the last k_t rows of every trace column, written in place BEFORE the auxiliary columns are
+ *   built (column c takes elements c k_t .. (c + 1) k_t - 1).
+ * Derived AIR (smi_air_plan_deep_zk_xargs).  The caller's AIR with two more periodic columns of period n.  Index Q holds
+ *   E(tau w^r), E(x) = prod_{r = n_a - 1}^{n - 2} (x - tau w^r), a factor of every term of every transition constraint, exactly
+ *   as in the plain variant with this k_t.  Index Q + 1 holds E_A(tau w^r), E_A(x) = prod_{r = n_a}^{n - 1} (x - tau w^r); no
+ *   main constraint reads it.  Variables 2 W + Q + j move up by two.  Refused when Q + 2 > SMI_AIR_MAX_PERIODIC.
+ * Auxiliary columns (smi_dev_zk_args_tail).  c_a[0] = init_a, and c_a[r + 1] follows from c_a[r] by the recurrence for r < n_a,
+ *   so c_a[n_a] is the closing value: argument a closes iff c_a[n_a] = init_a.  Rows n_a + 1 .. n - 1 of the four coordinate
+ *   columns of c_a are random: coordinate column 4 a + e takes elements (4 a + e)(k_t - 1) .. of stream 6.  The three-launch
+ *   column build runs over all n rows of the randomised trace -- its rows <= n_a are already right, and n_a is a multiple of
+ *   8, so no lane mixes active and tail rows; one more launch (zk_args_tail_kernel) then copies c_a[n_a] into the verdict
+ *   flags and overwrites the tail, with 16-byte stores where the alignment allows (n_a + 1 is odd: the head of every column's
+ *   tail is unaligned) and 4-byte stores of the same words otherwise.  *closes bit a is that verdict; the prover does not
+ *   refuse a column that does not close.  A zero denominator in any of the n rows is reported as smi_dev_xargs_columns
+ *   reports it.
+ * Auxiliary quotients (smi_dev_air_compose_zk_xargs).  Three per argument, under the weights w_{W+K+3a}, w_{W+K+3a+1},
+ *   w_{W+K+3a+2}, so NW = W + K + 3 A:
+ *     bq_a = (c_a(x) - init_a) / (x - tau)
+ *     wq_a = E_A(x) T_a(x) / (x^n - tau^n)        T_a: the wrapping transition numerator of the xargs section, unchanged
+ *     cq_a = (c_a(x) - init_a) / (x - tau w^n_a)
+ *   E_A(x_i) is read from the derived AIR's extended periodic table Q + 1 the way a periodic operand is read.  One streaming
+ *   launch after smi_dev_air_compose_ext; the eight denominators x - tau, x - tau w^n_a of a lane's four points share one
+ *   inversion whatever A is.
+ * Degree.  An argument contributes one more than in the xargs section: a permutation 3, with a selector 4, a lookup 4;
+ *   d = max(d of the derived AIR, contributions); D, D' = ceil(D n / (n - k_s)), D <= B, 4 D' + 5 <= 64, W + 1 <= 64 and
+ *   k_t < n / 2 as in the plain zk plan; no boundary point on a row >= n_a.  Refusals start "zk deep argument:".
+ * Multiplicities (smi_dev_xargs_multiplicities_rows).  smi_dev_xargs_multiplicities with a row bound: table rows >= rows are
+ *   not inserted, lookup rows >= rows are not counted, the column stride stays n; rows = n gives every word of that call.  A
+ *   caller fills the multiplicity columns with rows = n_a before the randomiser rows are written.
+ * Trees (coset leaves).  Tree 1: W + 1 columns (salt: stream 2).  Tree 2: 4 A + 1 (salt: stream 7).  Tree 3: 4 D' + 5, the
+ *   segments, the mask R and a salt (stream 5).  Streams 3 (rho) and 4 (R) as in the plain variant.
+ * Transcript and record.  The shape of "Out-of-domain sampling with an argument list" with NW above: root_1 -> alpha, gamma;
+ *   root_2 -> 4 NW weights; root_3 -> z; the record of 4 (2 W + 2 A + D') values u, v, a_a, b_a, s_j = H~_j(z); as many
+ *   gammas.  R has no DEEP quotient.
+ * Codeword.  Q' = Q + R: smi_dev_deep_compose_args with D' segments, then zk_mask_add_kernel.  Fold-by-4 FRI with the nonce
+ *   record.
+ * Proof bytes (smi_air_deep_zk_xargs_layout): 9 + 32 (2 W + 2 A + D') + len_FRI4(N, B, t) + sum over V in {W + 1, 4 A + 1,
+ *   4 D' + 5} of [ t (9 + 32 V) + t (9 + 32 (log2 N - 2)) ].
+ * Verifier (host), every sentence starting "zk deep argument", in the order of smi_air_verify_deep_zk over three sections.
+ *   The consistency check is
+ *     sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z) + sum_a (w bq_a(z) + w wq_a(z) + w cq_a(z)) = sum_j z^(j L) s_j
+ *   over the derived AIR; wq_a carries E_A(z), cq_a = (a_a - init_a) / (z - tau w^n_a), the operands at z are those of
+ *   smi_air_verify_deep_xargs.  Q + R is recomputed at the four coset points from the three opened records.  Proofs of
+ *   smi_dev_air_prove_deep_xargs_fold4 and of smi_dev_air_prove_deep_zk are rejected here, and this variant's proofs by their
+ *   verifiers: the records differ in length.
+ * Measured (profiles/zk_args_time.log): the 9-column list of README.md at n = 2^20, B = 8, t = 32, 16 grinding bits -- 1.36 times
+ *   the stage time of smi_dev_air_prove_deep_xargs_fold4 (wall time 1.93 times), proof 1.08 times its bytes.
+ * Left out: row leaves / fold 2; the single permutation and lookup forms (a one-element list covers them); smi_mgpu_* twins;
+ *   next-row tuple members; an AIR digest in the transcript. */
+/* Host only: *degree = d, *segments = D', *k_t = 8 t + 16, *k_s (outputs are optional). */
+int smi_air_plan_deep_zk_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments, uint32_t *k_t,
+                               uint32_t *k_s);
+/* Host only: the plan above, then *folds = F and the proof length in bytes. */
+int smi_air_deep_zk_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint64_t *folds, size_t *proof_len);
+/* smi_dev_xargs_multiplicities over the rows < rows (1 <= rows <= n); all n words of d_mult are written. */
+int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air, const void *xargs, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                      uint32_t log_n, size_t rows, uint32_t *d_mult);
+/* The tail step alone.  d_c: 4 n_args coordinate columns of n = 2^log_n words, c_stride >= n apart; k_t a multiple of 8 below
+ * n / 2; d_rnd: 4 n_args (k_t - 1) words.  closing (optional, host): 4 n_args values, coordinate e of c_a[n - k_t] at 4 a + e;
+ * the call synchronises when it is given. */
+int smi_dev_zk_args_tail(smi_ctx *ctx, uint32_t *d_c, size_t c_stride, uint32_t log_n, uint32_t k_t, uint32_t n_args, const uint32_t *d_rnd,
+                         uint64_t *closing);
+/* smi_dev_air_compose_xargs's parameters: the composition of the DERIVED AIR plus the 3 A auxiliary quotients; d_weights:
+ * 4 (W + K + 3 A) unreduced coordinates on the device. */
+int smi_dev_air_compose_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint32_t *d_lde, size_t stride,
+                                 const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out,
+                                 size_t out_stride);
+/* smi_dev_air_prove_deep_zk's parameters with the list; roots (optional) root_1, root_2, root_3, 96 bytes; stage_ms (optional)
+ * ten values {random, lde, commit, args, compose, segments, ood, mask, fri, open}; *closes as in smi_dev_air_prove_deep_xargs. */
+int smi_dev_air_prove_deep_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *d_trace_cols,
+                                    const uint8_t seed[32], uint8_t *roots, uint64_t *ood, uint8_t **proof, size_t *proof_len, uint64_t *top_indices,
+                                    double *stage_ms, uint32_t grind_bits, uint32_t *closes);
+int smi_air_verify_deep_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                                 size_t proof_len, int *accept, uint32_t grind_bits);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------
  * Fri::commit / Fri::prove (src/fri.rs:105-156, 250-311) over ONE codeword sharded in contiguous

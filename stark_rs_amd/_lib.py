@@ -291,8 +291,20 @@ def lib():
         "smi_dev_air_prove_deep_zk": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
         "smi_air_verify_deep_zk": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
         "smi_dev_zk_segments": (i32, [vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, sz]),
+        "smi_air_plan_deep_zk_xargs": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u32p, u32p, u32p, u32p]),
+        "smi_air_deep_zk_xargs_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u64p, C.POINTER(sz)]),
+        "smi_dev_xargs_multiplicities_rows": (i32, [vp, C.POINTER(Air), C.POINTER(AirXArgs), C.c_uint32, vp, C.c_uint32, C.c_uint32, sz, vp]),
+        "smi_dev_zk_args_tail": (i32, [vp, vp, sz, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64p]),
+        "smi_dev_air_compose_zk_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, sz, vp, sz, u64p, vp, vp, sz]),
+        "smi_dev_air_prove_deep_zk_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, vp, vp, C.POINTER(vp),
+                                                  C.POINTER(sz), vp, vp, C.c_uint32, u32p]),
+        "smi_air_verify_deep_zk_xargs": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), vp, C.c_char_p, sz, C.POINTER(i32),
+                                               C.c_uint32]),
     }
     for name, (res, args) in sig.items():
+        fn = getattr(L, name, None)
+        if fn is None and os.environ.get("SMI_LIB"):   # an older build loaded for an A/B run lacks the newer entry points; using one still raises
+            continue
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

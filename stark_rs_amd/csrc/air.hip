@@ -29,6 +29,7 @@
 #include "perm_core.h"
 #include "xargs_core.h"
 #include "zk_core.h"
+#include "zkargs_core.h"
 
 template <int P>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
@@ -346,6 +347,21 @@ int smi_air_deep_zk_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air
     const int rc = zk_plan(p, cfg, (const smi_air *)air, nullptr, &Dp, nullptr, nullptr, &g_air_err);
     if (rc != SMI_OK) return rc;
     const size_t len = zk_proof_len(cfg, Dp, folds);
+    if (proof_len) *proof_len = len;
+    return SMI_OK;
+}
+// ... with an argument list (zkargs_core.h)
+int smi_air_plan_deep_zk_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments, uint32_t *k_t,
+                               uint32_t *k_s) {
+    g_air_err.clear();
+    return zkx_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, degree, segments, k_t, k_s, &g_air_err);
+}
+int smi_air_deep_zk_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint64_t *folds, size_t *proof_len) {
+    g_air_err.clear();
+    uint32_t Dp = 0;
+    const int rc = zkx_plan(p, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, nullptr, &Dp, nullptr, nullptr, &g_air_err);
+    if (rc != SMI_OK) return rc;
+    const size_t len = zkx_proof_len(cfg, ((const smi_air_xargs *)xargs)->count, Dp, folds);
     if (proof_len) *proof_len = len;
     return SMI_OK;
 }

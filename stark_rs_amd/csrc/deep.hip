@@ -30,6 +30,7 @@
 #include "row4_dev.h"
 #include "xargs_core.h"
 #include "zk_core.h"
+#include "zkargs_core.h"
 
 // four consecutive words from `at` (a multiple of 4): one 16-byte access where the layout allows and all four lie below len
 template <bool VEC>
@@ -351,6 +352,10 @@ struct DeepProver {
     const char *name = nullptr;              // the entry point, for the out-of-memory sentences
     bool cosets = false;                     // coset leaves, FRI at folding factor 4; else row leaves, folding factor 2
     const uint32_t *d_trace = nullptr;
+    // a zero-knowledge proof with a list: k_t (else 0), the caller's seed, 4 A (k_t - 1) words for the tails of the auxiliary columns
+    uint32_t zk_kt = 0;
+    const uint8_t *zk_seed = nullptr;
+    uint32_t *d_tail = nullptr;
     // shapes (deep_shapes)
     uint32_t W = 0, K = 0, A = 0, CW = 0, NW = 0, D = 0, log_n = 0, log_N = 0, p = 0, g = 0, w_n = 0;   // CW = 4 A coordinate columns; NW weights; D committed segments
     size_t n = 0, N = 0, leaves = 0, n_ood = 0;
@@ -411,7 +416,7 @@ int deep_setup(DeepProver &s) {
     };
     const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
     s.d_lde = (uint32_t *)take((size_t)s.V[0] * N * 4);
-    if (A) s.d_c = (uint32_t *)take((size_t)CW * n * 4), s.d_cl = (uint32_t *)take((size_t)CW * N * 4);
+    if (A) s.d_c = (uint32_t *)take((size_t)CW * n * 4), s.d_cl = (uint32_t *)take((size_t)s.V[1] * N * 4);   // V[1]: CW, and a salt column under zk
     s.d_cw = (uint32_t *)take(4 * N * 4);   // H, then Q
     s.d_hc = (uint32_t *)take(4 * N * 4);   // the coefficients of H's coordinates
     s.d_seg = (uint32_t *)take((size_t)s.V[s.G - 1] * N * 4);
@@ -450,7 +455,8 @@ int deep_root1(DeepProver &s) {
 }
 
 // a list: root_1 -> alpha, gamma -> the auxiliary columns, extended and committed (a stage of their own); root_2 and the
-// columns' verdicts -> the weights
+// columns' verdicts -> the NW weights.  Under zk the tail step follows the column build -- the closing values c_a[n_a] take the
+// totals' place in the flags, the rows behind them become random -- and tree 2 gets its salt column.
 int deep_list_columns(DeepProver &s, uint32_t *closes) {
     smi_ctx *ctx = s.ctx;
     const smi_stark_cfg *cfg = s.cfg;
@@ -459,6 +465,12 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     xargs_build(ctx->fs.F, s.g, s.xargs, s.W, s.air, s.H.per, ch.data(), &s.XD);
     s.XD.pvals = s.d_pvals;   // the raw periodic values the column build reads
     SMI_TRY(xargs_columns_launch(ctx, s.XD, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
+    if (s.zk_kt) {
+        ArgsFlags *d_fl = const_cast<ArgsFlags *>(xargs_columns_flags_at(s.d_atmp, s.A, s.n));
+        SMI_TRY(smi_dev_random_fill(ctx, s.zk_seed, ZK_STREAM_ARGS_TAIL, s.d_tail, (size_t)s.CW * (s.zk_kt - 1)));
+        SMI_TRY(zk_args_tail_launch(ctx, s.d_c, s.n, s.log_n, s.zk_kt, s.A, s.d_tail, &d_fl->total[0][0]));
+        SMI_TRY(smi_dev_random_fill(ctx, s.zk_seed, ZK_STREAM_SALT_ARGS, s.d_cl + (size_t)s.CW * s.N, s.N));
+    }
     SMI_TRY(smi_dev_lde(ctx, s.d_c, s.CW, s.log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, s.d_cl));
     SMI_TRY(deep_commit(s, 1));
     s.timer.mark();
@@ -468,17 +480,19 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     SMI_TRY(dev_ntt(ctx, s.d_c, s.d_coef + (size_t)s.W * s.n, s.log_n, s.n, s.CW, s.n, s.n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     SMI_TRY(xargs_columns_settle(ctx, s.XD, fl, closes));
-    transcript_args_weights(s.tr, s.roots + 32, s.W, s.K, s.A, &s.weights);
+    transcript_indexed(s.tr, s.roots + 32, 8, 4 * (uint64_t)s.NW, &s.weights);   // root_2, then the indices 8 .. 8 + 4 NW - 1
     return SMI_OK;
 }
 
-// H on the N points into d_cw: the AIR's quotients under s.weights, plus the list's 2 A auxiliary quotients
+// H on the N points into d_cw: the AIR's quotients under s.weights, plus the list's 2 A auxiliary quotients (3 A under zk)
 int deep_compose_h(DeepProver &s) {
     smi_ctx *ctx = s.ctx;
     const size_t N = s.N;
     HIP_TRY(ctx, hipMemcpyAsync(s.d_weights, s.weights.data(), 8 * s.weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, s.H, s.d_blob, s.d_lde, N, s.d_weights, s.d_cw, N));
-    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, s.d_weights + 4 * (size_t)(s.W + s.K), s.d_cw, N));
+    const uint64_t *d_w = s.d_weights + 4 * (size_t)(s.W + s.K);
+    if (s.zk_kt) return zkx_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.log_n, s.zk_kt, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N);
+    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N));
     return SMI_OK;
 }
 
@@ -682,7 +696,7 @@ int zk_randomise(DeepProver &s, const uint8_t seed[32], uint32_t kt, const ZkBuf
     SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_ROWS, zb.d_rows, (size_t)s.W * kt));
     HIP_TRY(ctx, hipMemcpy2DAsync(d_trace_cols + (n - kt), n * 4, zb.d_rows, (size_t)kt * 4, (size_t)kt * 4, s.W, hipMemcpyDeviceToDevice, ctx->stream));
     SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT1, s.d_lde + (size_t)s.W * N, N));
-    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT2, s.d_seg + (size_t)(s.V[1] - 1) * N, N));
+    SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_SALT2, s.d_seg + (size_t)(s.V[s.G - 1] - 1) * N, N));
     return SMI_OK;
 }
 
@@ -695,33 +709,41 @@ int zk_segments(DeepProver &s, const uint8_t seed[32], uint32_t D_h, uint32_t ks
     if (Dp > 1) SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_RHO, zb.d_rho, (size_t)4 * (Dp - 1) * ks));
     SMI_TRY(smi_dev_zk_segments(ctx, s.d_hc, N, (size_t)D_h * n, s.log_n, ks, Dp, zb.d_rho, zb.d_sc, n));
     SMI_TRY(smi_dev_random_fill(ctx, seed, ZK_STREAM_MASK, zb.d_sc + (size_t)4 * Dp * n, 4 * n));
-    for (uint32_t c = 0; c < s.V[1] - 1; c += 4)
+    for (uint32_t c = 0; c < s.V[s.G - 1] - 1; c += 4)
         SMI_TRY(dev_ntt(ctx, zb.d_sc + (size_t)c * n, s.d_seg + (size_t)c * N, s.log_N, n, 4, n, N, 0, s.cfg->lde_offset, 1));
     return SMI_OK;
 }
 
-int zk_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, uint32_t *d_trace_cols, const uint8_t seed[32], uint8_t *roots_out, uint64_t *ood_out,
-             uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+// a plain AIR (xargs == nullptr: "Zero-knowledge DEEP proofs", nine stages) or an argument list ("... with an argument list",
+// ten stages: the auxiliary columns' between commit and compose)
+int zk_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, const smi_air_xargs *xargs, uint32_t *d_trace_cols, const uint8_t seed[32],
+             uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits,
+             uint32_t *closes) {
+    if (closes) *closes = 0;
     SMI_TRY(grind_bits_check(ctx, grind_bits));
     SMI_TRY(deep_field_check(ctx));
     uint32_t D_h = 0, Dp = 0, kt = 0, ks = 0;
     std::string why;
-    int rc = zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, &kt, &ks, &why, &D_h);
+    int rc = xargs ? zkx_plan(ctx->fs.F.p, cfg, air0, xargs, nullptr, &Dp, &kt, &ks, &why, &D_h) : zk_plan(ctx->fs.F.p, cfg, air0, nullptr, &Dp, &kt, &ks, &why, &D_h);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    DeepProver s(ctx, 9, stage_ms != nullptr);
-    s.cfg = cfg, s.air = air0, s.name = "air_prove_deep_zk", s.cosets = true, s.d_trace = d_trace_cols;
-    SMI_TRY(deep_shapes(s, Dp, ZK_NO_LAYER));
-    s.V[0] = s.W + 1, s.V[1] = 4 * Dp + 5;   // the trace and its salt column; the segments, R and their salt column
+    DeepProver s(ctx, xargs ? 10 : 9, stage_ms != nullptr);
+    s.cfg = cfg, s.air = air0, s.xargs = xargs, s.name = xargs ? "air_prove_deep_zk_xargs" : "air_prove_deep_zk", s.cosets = true, s.d_trace = d_trace_cols;
+    SMI_TRY(deep_shapes(s, Dp, xargs ? ZKX_NO_LAYER : ZK_NO_LAYER));   // a list is checked against the caller's AIR
+    const DeepGroups gr = xargs ? zkx_groups(s.W, s.A, Dp) : zk_groups(s.W, Dp);   // every tree with its salt column; the segments with R
+    for (uint32_t k = 0; k < 3; k++) s.V[k] = gr.V[k];
+    if (xargs) s.NW = s.W + s.K + 3 * s.A, s.zk_kt = kt, s.zk_seed = seed;
     ZkAir Z;
-    rc = zk_derive_air(s.p, s.w_n, cfg, air0, &Z, &why);
+    rc = zk_derive_air(s.p, s.w_n, cfg, air0, &Z, &why, xargs != nullptr);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     s.air = &Z.air;   // K stays the caller's: the weights are drawn for the caller's constraints
     SMI_TRY(deep_setup(s));
+    const uint32_t segw = s.V[s.G - 1] - 1;   // 4 D' + 4: the segments' and R's columns
     ZkBuffers zb;
     zb.d_rows = (uint32_t *)arena_alloc(ctx, (size_t)s.W * kt * 4);
     zb.d_rho = (uint32_t *)arena_alloc(ctx, (size_t)4 * Dp * ks * 4);
-    zb.d_sc = (uint32_t *)arena_alloc(ctx, (size_t)(s.V[1] - 1) * s.n * 4);
-    if (!zb.d_rows || !zb.d_rho || !zb.d_sc) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_deep_zk: device memory");
+    zb.d_sc = (uint32_t *)arena_alloc(ctx, (size_t)segw * s.n * 4);
+    if (xargs) s.d_tail = (uint32_t *)arena_alloc(ctx, (size_t)s.CW * (kt - 1) * 4);
+    if (!zb.d_rows || !zb.d_rho || !zb.d_sc || (xargs && !s.d_tail)) return smi_fail(ctx, SMI_ERR_OOM, (std::string(s.name) + ": device memory").c_str());
     s.timer.mark();
     SMI_TRY(zk_randomise(s, seed, kt, zb, d_trace_cols));
     s.timer.mark();
@@ -730,11 +752,12 @@ int zk_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, uint32
     SMI_TRY(deep_commit(s, 0));
     s.timer.mark();
     SMI_TRY(deep_root1(s));
-    deep_transcript_weights(s.tr, s.roots, s.W, s.K, &s.weights);
+    if (xargs) SMI_TRY(deep_list_columns(s, closes));   // marks the auxiliary stage
+    else deep_transcript_weights(s.tr, s.roots, s.W, s.K, &s.weights);
     SMI_TRY(deep_compose_h(s));
     s.timer.mark();
     SMI_TRY(zk_segments(s, seed, D_h, ks, zb));
-    SMI_TRY(deep_commit(s, 1));
+    SMI_TRY(deep_commit(s, s.G - 1));
     s.timer.mark();
     SMI_TRY(deep_draw_z(s, roots_out));
     SMI_TRY(deep_values_at_z(s, zb.d_sc, s.n, 4 * s.n, ood_out));   // the masked segments: coordinate e of segment j is column 4 j + e
@@ -783,6 +806,15 @@ int smi_dev_air_prove_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
                               uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
     if (!ctx || !cfg || !air || !d_trace_cols || !seed || !proof || !proof_len) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
-    return zk_prove(ctx, cfg, (const smi_air *)air, d_trace_cols, seed, roots_out, ood_out, proof, proof_len, top_indices, stage_ms, grind_bits);
+    return zk_prove(ctx, cfg, (const smi_air *)air, nullptr, d_trace_cols, seed, roots_out, ood_out, proof, proof_len, top_indices, stage_ms, grind_bits,
+                    nullptr);
+}
+int smi_dev_air_prove_deep_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *d_trace_cols, const uint8_t seed[32],
+                                    uint8_t *roots_out, uint64_t *ood_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                                    uint32_t grind_bits, uint32_t *closes) {
+    if (!ctx || !cfg || !air || !xargs || !d_trace_cols || !seed || !proof || !proof_len) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    return zk_prove(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, d_trace_cols, seed, roots_out, ood_out, proof, proof_len, top_indices,
+                    stage_ms, grind_bits, closes);
 }
 

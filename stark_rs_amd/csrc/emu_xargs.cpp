@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "emu_host.h"
 #include "tables.h"
 #include "xargs_core.h"
 
@@ -17,14 +18,12 @@ extern "C" int emu_air_compose_ext(uint64_t p, uint64_t g, const smi_stark_cfg *
 extern "C" int emu_ntt(uint64_t p, uint64_t g, const uint32_t *in, uint32_t *out, uint32_t L, uint32_t n_in, uint32_t batch, uint64_t in_stride,
                        uint64_t out_stride, int inverse, uint64_t offset, uint64_t post_scale);
 
+using emu_host::HostAtomics;
+using emu_host::load4;
+using emu_host::periodic_tables;
+using emu_host::store4;
+
 namespace {
-void load4(const uint32_t *src, uint64_t at, uint64_t len, uint32_t v[4]) {
-    for (int q = 0; q < 4; q++) v[q] = at + q < len ? src[at + q] : 0u;
-}
-void store4(uint32_t *dst, uint64_t at, uint64_t len, const uint32_t v[4]) {
-    for (int q = 0; q < 4; q++)
-        if (at + q < len) dst[at + q] = v[q];
-}
 // xargs_wg_scan of xargs.hip: v[tid] -> excl[tid] and the aggregate
 Fq wg_scan(bool perm, const Fq *v, Fq *excl, uint32_t g_m, const Fp &F) {
     static thread_local uint32_t sc[2][4][PERM_BLOCK];
@@ -38,28 +37,6 @@ Fq wg_scan(bool perm, const Fq *v, Fq *excl, uint32_t g_m, const Fp &F) {
     for (uint32_t tid = 0; tid < PERM_BLOCK; tid++) excl[tid] = tid ? perm_scan_at(sc[cur], tid - 1) : args_identity(perm, F);
     return perm_scan_at(sc[cur], PERM_BLOCK - 1);
 }
-// the extended periodic tables at the places AirPeriodic names (emu_air.cpp builds them the same way)
-bool periodic_tables(uint64_t p, uint64_t g, const AirPeriodic &P, std::vector<uint32_t> *tab) {
-    tab->assign(P.table_words, 0);
-    for (const AirPeriodGroup &gr : P.groups) {
-        const uint64_t per = 1ull << gr.log_period, len = 1ull << gr.log_len;
-        std::vector<uint32_t> coef(gr.count * per);
-        if (emu_ntt(p, g, P.vals.data() + gr.in_off, coef.data(), gr.log_period, (uint32_t)per, gr.count, per, per, 1, 1, gr.lde_offset)) return false;
-        if (emu_ntt(p, g, coef.data(), tab->data() + gr.out_off, gr.log_len, (uint32_t)per, gr.count, per, len, 0, 1, 1)) return false;
-    }
-    return true;
-}
-struct HostAtomics {
-    uint32_t cas(uint32_t *a, uint32_t expect, uint32_t v) const {
-        const uint32_t old = *a;
-        if (old == expect) *a = v;
-        return old;
-    }
-    void min(uint32_t *a, uint32_t v) const {
-        if (v < *a) *a = v;
-    }
-    void add(uint32_t *a, uint32_t v) const { *a += v; }
-};
 int checks(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, uint32_t n_cols, uint32_t log_n, FieldSetup *fs) {
     if (!field_setup(p, g, fs)) return SMI_ERR_UNSUPPORTED_PRIME;
     if (!ext_field_ok(p, g, nullptr) || p >= (1ull << 30)) return SMI_ERR_BAD_ARG;

@@ -34,6 +34,7 @@
 #include "deep_core.h"
 #include "xargs_core.h"
 #include "zk_core.h"
+#include "zkargs_core.h"
 #include "fri_core.h"
 #include "hash_core.h"
 #include "internal.h"
@@ -1505,6 +1506,60 @@ int smi_air_verify_deep_xargs_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, cons
     return settle(air_verify_deep_fold4_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
 }
 
+// What the two zero-knowledge verifiers share behind the consistency check: the refusal of a shape without a fold, the fold-by-4
+// FRI walk, the opening sections of the groups gr (every group's last column is its salt; the last group holds the 4 D'
+// segment columns, the 4 columns of R and the salt; A > 0: the middle group holds the 4 A auxiliary coordinates), every record
+// hashed as it stands, the canonical check that leaves the salts out, and Q + R at the four coset points.  objs: the record
+// first, then FRI's objects; end: where the sections start.
+static int zk_walk_and_open(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_fri_cfg &fc, const char *no_layer, const OpeningWords &say,
+                            const DeepGroups &gr, uint32_t A, uint32_t Dp, const uint8_t *roots, const uint8_t *proof, size_t proof_len, size_t end,
+                            std::vector<Obj> &objs, const Transcript &tr, const FqH &z, const std::vector<uint64_t> &ood, const std::vector<uint64_t> &gammas,
+                            int *accept, uint32_t grind) {
+    const uint32_t W = cfg->n_cols, logN = cfg->log_n + cfg->log_blowup, p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
+    if (fri_layout_fold4(fc).F == 0) return reject(ctx, accept, no_layer);
+    objs.erase(objs.begin());
+    std::vector<uint64_t> top, coset;   // coset: the 16 values of every layer-0 record
+    size_t used = 0;
+    SMI_TRY(fri_walk_fold4(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &coset, &used, grind));
+    *accept = 0;
+    const uint8_t *sec = proof + end;
+    std::vector<uint64_t> vals[3];
+    size_t at[3] = {0, 0, 0};
+    switch (deep_coset_parse(sec, proof_len - end, gr, t, logN, vals, at)) {
+        case DEEP_COSET_LENGTH: return reject(ctx, accept, say.length);
+        case DEEP_COSET_RECORD: return reject(ctx, accept, say.row);
+        case DEEP_COSET_PATH: return reject(ctx, accept, say.path);
+        default: break;
+    }
+    const uint64_t q = N / 4;
+    std::vector<uint64_t> pos(t);
+    for (uint64_t s = 0; s < t; s++) pos[s] = top[s] % q;
+    for (uint32_t k = 0; k < gr.G; k++) SMI_TRY(auth_section(ctx, accept, say, sec + at[k], t, 4 * gr.V[k], logN - 2, pos, roots + 32 * k));
+    for (uint32_t k = 0; k < gr.G; k++)   // every value but the salts, which are the last four of a record
+        for (uint64_t s = 0; s < t; s++)
+            for (size_t i = 0; i + 4 < 4 * (size_t)gr.V[k]; i++)
+                if (vals[k][s * 4 * (size_t)gr.V[k] + i] >= p) return reject(ctx, accept, say.canonical);
+    const uint32_t iota = (uint32_t)powm(fc.omega, q, p), last = gr.G - 1;
+    std::vector<uint64_t> trow(W), crow(4 * (size_t)A), srow(4 * (size_t)Dp);
+    for (uint64_t s = 0; s < t; s++) {
+        const uint64_t *r1 = &vals[0][s * 4 * (size_t)gr.V[0]], *r2 = &vals[1][s * 4 * (size_t)gr.V[1]], *r3 = &vals[last][s * 4 * (size_t)gr.V[last]];
+        uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[s], p), p);
+        for (uint32_t j = 0; j < 4; j++) {   // column c at point j = value 4 c + j
+            for (uint32_t c = 0; c < W; c++) trow[c] = r1[4 * (size_t)c + j];
+            for (uint32_t c = 0; c < 4 * A; c++) crow[c] = r2[4 * (size_t)c + j];
+            for (uint32_t c = 0; c < 4 * Dp; c++) srow[c] = r3[4 * (size_t)c + j];
+            const FqH qv = A ? deep_args_q_at(p, g, W, A, Dp, w_n, x, z, ood.data(), gammas.data(), trow.data(), crow.data(), srow.data())
+                             : deep_q_at(p, g, W, Dp, w_n, x, z, ood.data(), gammas.data(), trow.data(), srow.data());
+            for (uint32_t e = 0; e < 4; e++)
+                if (fp_add(qv.c[e], (uint32_t)r3[4 * (size_t)(4 * Dp + e) + j], p) != coset[16 * s + 4 * e + j]) return reject(ctx, accept, say.composition);
+            x = host_mulmod(x, iota, p);
+        }
+    }
+    *accept = 1;
+    return SMI_OK;
+}
+
 // Verifier of smi_dev_air_prove_deep_zk (include/stark_mi.h, "Zero-knowledge DEEP proofs"): air_verify_deep_fold4_impl for a
 // plain AIR with the derived AIR on the left of the consistency check and sum_j z^(j L) s_j on its right, groups of W + 1 and
 // 4 D' + 5 columns, the salts hashed as they stand and otherwise ignored, and Q + R at the four coset points.
@@ -1521,7 +1576,7 @@ static int air_verify_deep_zk_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const
     ZkAir Z;
     const int drc = zk_derive_air(p, w_n, cfg, air0, &Z, &why);
     if (drc != SMI_OK) return smi_fail(ctx, drc, why.c_str());
-    const uint64_t N = 1ull << logN, n = 1ull << cfg->log_n, t = cfg->num_colinearity_tests;
+    const uint64_t n = 1ull << cfg->log_n;
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
     const size_t n_ood = 4 * (2 * (size_t)W + Dp);
     size_t end = 0;
@@ -1546,47 +1601,7 @@ static int air_verify_deep_zk_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const
         pw = fqh_mul(pw, zl, p, g);
     }
     if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, ZK_INCONSISTENT);
-    if (fri_layout_fold4(fc).F == 0) return reject(ctx, accept, ZK_NO_LAYER);
-    objs.erase(objs.begin());
-    std::vector<uint64_t> top, coset;   // coset: the 16 values of every layer-0 record
-    size_t used = 0;
-    SMI_TRY(fri_walk_fold4(ctx, fc, tr.seed(), objs, accept, &top, nullptr, nullptr, &coset, &used, grind));
-    *accept = 0;
-    const OpeningWords &say = ZK_WORDS;
-    const DeepGroups gr = zk_groups(W, Dp);
-    const uint8_t *sec = proof + end;
-    std::vector<uint64_t> vals[3];
-    size_t at[3] = {0, 0, 0};
-    switch (deep_coset_parse(sec, proof_len - end, gr, t, logN, vals, at)) {
-        case DEEP_COSET_LENGTH: return reject(ctx, accept, say.length);
-        case DEEP_COSET_RECORD: return reject(ctx, accept, say.row);
-        case DEEP_COSET_PATH: return reject(ctx, accept, say.path);
-        default: break;
-    }
-    const uint64_t q = N / 4;
-    std::vector<uint64_t> pos(t);
-    for (uint64_t s = 0; s < t; s++) pos[s] = top[s] % q;
-    for (uint32_t k = 0; k < gr.G; k++) SMI_TRY(auth_section(ctx, accept, say, sec + at[k], t, 4 * gr.V[k], logN - 2, pos, roots + 32 * k));
-    for (uint32_t k = 0; k < gr.G; k++)   // every value but the salts, which are the last four of a record
-        for (uint64_t s = 0; s < t; s++)
-            for (size_t i = 0; i + 4 < 4 * (size_t)gr.V[k]; i++)
-                if (vals[k][s * 4 * (size_t)gr.V[k] + i] >= p) return reject(ctx, accept, say.canonical);
-    const uint32_t iota = (uint32_t)powm(fc.omega, q, p);
-    std::vector<uint64_t> trow(W), srow(4 * (size_t)Dp);
-    for (uint64_t s = 0; s < t; s++) {
-        const uint64_t *r1 = &vals[0][s * 4 * (size_t)gr.V[0]], *r2 = &vals[1][s * 4 * (size_t)gr.V[1]];
-        uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[s], p), p);
-        for (uint32_t j = 0; j < 4; j++) {   // column c at point j = value 4 c + j
-            for (uint32_t c = 0; c < W; c++) trow[c] = r1[4 * (size_t)c + j];
-            for (uint32_t c = 0; c < 4 * Dp; c++) srow[c] = r2[4 * (size_t)c + j];
-            const FqH qv = deep_q_at(p, g, W, Dp, w_n, x, z, ood.data(), gammas.data(), trow.data(), srow.data());
-            for (uint32_t e = 0; e < 4; e++)
-                if (fp_add(qv.c[e], (uint32_t)r2[4 * (size_t)(4 * Dp + e) + j], p) != coset[16 * s + 4 * e + j]) return reject(ctx, accept, say.composition);
-            x = host_mulmod(x, iota, p);
-        }
-    }
-    *accept = 1;
-    return SMI_OK;
+    return zk_walk_and_open(ctx, cfg, fc, ZK_NO_LAYER, ZK_WORDS, zk_groups(W, Dp), 0, Dp, roots, proof, proof_len, end, objs, tr, z, ood, gammas, accept, grind);
 }
 int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
                            uint32_t grind_bits) {
@@ -1599,3 +1614,63 @@ int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     return settle(air_verify_deep_zk_impl(ctx, cfg, (const smi_air *)air, roots, proof, proof_len, accept, grind_bits));
 }
 
+
+// Verifier of smi_dev_air_prove_deep_zk_xargs (include/stark_mi.h, "Zero-knowledge DEEP proofs with an argument list"):
+// air_verify_deep_zk_impl over three sections.  The transcript is the list variant's with NW = W + K + 3 A; the left side of the
+// consistency check is zkargs_core.h's zkx_ood_lhs over the derived AIR with both exemption columns; Q + R at the four coset
+// points goes through deep_args_q_at with D' segments.
+const OpeningWords ZKX_WORDS = {ZKX_SENTENCES[0], ZKX_SENTENCES[1], ZKX_SENTENCES[2], ZKX_SENTENCES[3], ZKX_SENTENCES[4], ZKX_SENTENCES[5]};   // zkargs_core.h
+static int air_verify_deep_zk_xargs_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air0, const smi_air_xargs *xargs, const uint8_t *roots,
+                                         const uint8_t *proof, size_t proof_len, int *accept, uint32_t grind) {
+    std::string why;
+    uint32_t Dp = 0, ks = 0;
+    const int vrc = zkx_plan(ctx->fs.F.p, cfg, air0, xargs, nullptr, &Dp, nullptr, &ks, &why);
+    if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
+    const int prc = xargs_periodic_check(ctx->fs.F.p, air0, cfg->log_n, &why);
+    if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
+    const uint32_t W = cfg->n_cols, K = air0->n_constraints, A = xargs->count, logN = cfg->log_n + cfg->log_blowup;
+    const uint64_t NW = (uint64_t)W + K + 3 * (uint64_t)A;
+    SMI_TRY(domain_check(ctx, logN));
+    const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
+    ZkAir Z;
+    const int drc = zk_derive_air(p, w_n, cfg, air0, &Z, &why, true);
+    if (drc != SMI_OK) return smi_fail(ctx, drc, why.c_str());
+    const uint64_t n = 1ull << cfg->log_n;
+    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
+    const size_t n_ood = deep_args_record(W, A, Dp);
+    size_t end = 0;
+    std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count_fold4(fc), &end);
+    if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, ZKX_BAD_RECORD);
+    std::vector<uint64_t> ood(n_ood);
+    for (size_t i = 0; i < n_ood; i++)
+        if ((ood[i] = get_u64(objs[0].p + 8 * i)) >= p) return reject(ctx, accept, ZKX_RECORD_CANONICAL);
+    Transcript tr;
+    std::vector<uint64_t> ch, weights, gammas;
+    uint64_t zr[4];
+    transcript_perm_challenges(tr, roots, &ch);
+    transcript_indexed(tr, roots + 32, 8, 4 * NW, &weights);
+    deep_args_transcript_z(tr, roots + 64, NW, zr);
+    const FqH z = fqh_of(zr, p);
+    if (fqh_in_base(z)) return reject(ctx, accept, ZKX_Z_IN_BASE_FIELD);
+    deep_args_transcript_gammas(tr, ood.data(), NW, n_ood, &gammas);
+    const FqH lhs = zkx_ood_lhs(p, g, cfg, &Z.air, xargs, w_n, ch.data(), weights.data(), z, ood.data());
+    FqH rhs = fqh(0), pw = fqh(1 % p);
+    const FqH zl = fqh_pow(z, n - ks, p, g);
+    for (uint32_t j = 0; j < Dp; j++) {
+        rhs = fqh_add(rhs, fqh_mul(pw, fqh_of(ood.data() + 4 * (2 * (size_t)W + 2 * (size_t)A + j), p), p, g), p);
+        pw = fqh_mul(pw, zl, p, g);
+    }
+    if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, ZKX_INCONSISTENT);
+    return zk_walk_and_open(ctx, cfg, fc, ZKX_NO_LAYER, ZKX_WORDS, zkx_groups(W, A, Dp), A, Dp, roots, proof, proof_len, end, objs, tr, z, ood, gammas, accept,
+                            grind);
+}
+int smi_air_verify_deep_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
+                                 size_t proof_len, int *accept, uint32_t grind_bits) {
+    if (!ctx || !cfg || !air || !xargs || !roots || (!proof && proof_len) || !accept) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    *accept = 0;
+    SMI_TRY(grind_bits_check(ctx, grind_bits));
+    SMI_TRY(ext_field_check(ctx));
+    if (ctx->fs.F.p >= (1u << 30)) return smi_fail(ctx, SMI_ERR_UNSUPPORTED_PRIME, "deep: modulus must be < 2^30");   // the prover's bound (deep.hip)
+    return settle(air_verify_deep_zk_xargs_impl(ctx, cfg, (const smi_air *)air, (const smi_air_xargs *)xargs, roots, proof, proof_len, accept, grind_bits));
+}

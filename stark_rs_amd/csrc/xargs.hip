@@ -65,16 +65,17 @@ struct XHelperFlags {   // the first missing selected row, a probe that ran out
 };
 }  // namespace
 
-__global__ __launch_bounds__(PERM_BLOCK) void xargs_insert_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *tab,
-                                                                   uint32_t cap, XHelperFlags *fl) {
+// rows <= n: the rows that take part (smi_dev_xargs_multiplicities_rows); the column stride stays n
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_insert_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint64_t rows,
+                                                                   uint32_t *tab, uint32_t cap, XHelperFlags *fl) {
     const uint64_t t = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
-    if (t >= n) return;
+    if (t >= rows) return;
     if (!xlookup_insert_lane(XD, a, trace, n, tab, cap, (uint32_t)t, XDevAtomics{})) atomicOr(&fl->exhausted, 1u);
 }
-__global__ __launch_bounds__(PERM_BLOCK) void xargs_count_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n,
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_count_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint64_t rows,
                                                                   const uint32_t *__restrict__ tab, uint32_t cap, uint32_t *mult, XHelperFlags *fl) {
     const uint64_t r = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
-    if (r >= n) return;
+    if (r >= rows) return;
     const int got = xlookup_count_lane(XD, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{});
     if (got == 1) atomicMin(&fl->first, (unsigned long long)r);
     if (got == 2) atomicOr(&fl->exhausted, 1u);
@@ -258,6 +259,13 @@ int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uin
 
 int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
                                  uint32_t log_n, uint32_t *d_mult) {
+    return smi_dev_xargs_multiplicities_rows(ctx, air_, xargs_, a, d_trace_cols, n_cols, log_n, (size_t)1 << (log_n < 63 ? log_n : 0), d_mult);
+}
+
+// the helper over the first `rows` rows: table rows at and above `rows` are not inserted, lookup rows there are not counted;
+// all n words of d_mult are written (zero where nothing is counted)
+int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                      uint32_t log_n, size_t rows, uint32_t *d_mult) {
     const smi_air *air = (const smi_air *)air_;
     const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
     if (!ctx || !air || !xargs || !d_trace_cols || !d_mult) return SMI_ERR_BAD_ARG;
@@ -269,6 +277,7 @@ int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xar
         return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
     }
     const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
+    if (!rows || rows > n) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities_rows: rows must be in 1 .. n");
     AirPeriodic per;
     xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
     XArgsDev XD;
@@ -284,15 +293,15 @@ int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xar
     HIP_TRY(ctx, hipMemsetAsync(&d_fl->exhausted, 0, 8, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_mult, 0, n * 4, ctx->stream));
     if (!per.vals.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pvals, per.vals.data(), per.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t grid = (uint32_t)((n + PERM_BLOCK - 1) / PERM_BLOCK), m = XD.m[a];
+    const uint32_t grid = (uint32_t)((rows + PERM_BLOCK - 1) / PERM_BLOCK), m = XD.m[a];
     {
         ProfScope ps(ctx, "xargs_insert_kernel", (4.0 * m + 4.0) * (double)n);
-        xargs_insert_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, d_tab, (uint32_t)cap, d_fl);
+        xargs_insert_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_fl);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
         ProfScope ps(ctx, "xargs_count_kernel", (4.0 * 2 * m + 8.0) * (double)n);
-        xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, d_tab, (uint32_t)cap, d_mult, d_fl);
+        xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
         HIP_TRY(ctx, hipGetLastError());
     }
     XHelperFlags fl;

@@ -179,7 +179,10 @@ inline void zk_exemption_column(uint32_t p, uint32_t tau, uint32_t w_n, uint32_t
         }
     }
 }
-inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, const smi_air *air, ZkAir *Z, std::string *why) {
+// list: the derived AIR of "Zero-knowledge DEEP proofs with an argument list" (zkargs_core.h) -- k_t = 8 t + 16, the sentences
+// start "zk deep argument:", and a second column of period n, index Q + 1, holds E_A(tau w^r), E_A(x) = prod_{r = n - k_t}^{n - 1}
+// (x - tau w^r) = w^k_t E(x / w): row r + 1 is w^k_t times row r of the first column.  No constraint reads it.
+inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, const smi_air *air, ZkAir *Z, std::string *why, bool list = false) {
     auto fail = [&](int code, const std::string &s) {
         if (why) *why = s;
         return code;
@@ -188,12 +191,18 @@ inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, c
     const int rc = air_validate(p64, cfg, air, nullptr, nullptr, why, true);
     if (rc != SMI_OK) return rc;
     const uint32_t W = cfg->n_cols, Q = air->n_periodic, K = air->n_constraints, nt = air->n_terms, nb = air->n_boundary;
-    const uint64_t n = 1ull << cfg->log_n, kt = zk_kt(cfg->num_colinearity_tests);
+    const uint64_t n = 1ull << cfg->log_n, kt = zk_kt(cfg->num_colinearity_tests) + (list ? 8 : 0);
+    const std::string who = list ? "zk deep argument: " : "zk deep: ";
+    const uint32_t extra = list ? 2 : 1;   // the periodic columns the derivation adds
     if (cfg->num_colinearity_tests > (1u << 20) || kt >= n / 2)
-        return fail(SMI_ERR_BAD_ARG, "zk deep: k_t = 8 t + 8 = " + std::to_string(kt) + " >= n / 2: the randomiser rows would outnumber the statement's");
+        return fail(SMI_ERR_BAD_ARG, who + "k_t = 8 t + " + (list ? "16" : "8") + " = " + std::to_string(kt) +
+                                         " >= n / 2: the randomiser rows would outnumber the statement's");
+    if (list && Q + 2 > SMI_AIR_MAX_PERIODIC)
+        return fail(SMI_ERR_BAD_ARG, who + "Q + 2 = " + std::to_string(Q + 2) + " > SMI_AIR_MAX_PERIODIC (" + std::to_string(SMI_AIR_MAX_PERIODIC) +
+                                         "): no room for the two exemption columns");
     for (uint32_t j = 0; j < nb; j++)
         if (air->boundary_row[j] >= n - kt)
-            return fail(SMI_ERR_BAD_ARG, "zk deep: boundary point " + std::to_string(j) + " lies on row " + std::to_string(air->boundary_row[j]) +
+            return fail(SMI_ERR_BAD_ARG, who + "boundary point " + std::to_string(j) + " lies on row " + std::to_string(air->boundary_row[j]) +
                                              " >= n - k_t = " + std::to_string(n - kt) + ", a randomiser row");
     Z->cft.assign(air->constraint_first_term, air->constraint_first_term + K + 1);
     Z->coeff.assign(air->term_coeff, air->term_coeff + nt);
@@ -203,7 +212,7 @@ inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, c
     for (uint32_t t = 0; t < nt; t++) {
         for (uint32_t f = air->term_first_factor[t]; f < air->term_first_factor[t + 1]; f++) {
             const uint32_t v = air->factor_var[f];
-            Z->var.push_back(v >= 2 * W + Q ? v + 1 : v);
+            Z->var.push_back(v >= 2 * W + Q ? v + extra : v);
             Z->exp.push_back(air->factor_exp[f]);
         }
         Z->var.push_back(2 * W + Q);
@@ -216,28 +225,33 @@ inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, c
     uint64_t at = 0;
     for (uint32_t j = 0; j < Q; j++) at += 1ull << air->periodic_log_period[j];
     Z->plog.assign(air->periodic_log_period, air->periodic_log_period + Q);
-    Z->plog.push_back(cfg->log_n);
+    for (uint32_t k = 0; k < extra; k++) Z->plog.push_back(cfg->log_n);
     Z->pval.assign(air->periodic_value, air->periodic_value + at);
-    Z->pval.resize(at + n, 0);
+    Z->pval.resize(at + extra * n, 0);
     if (w_n) {   // the column depends on (p, tau, w_n, n, k_t) alone: the last one made is kept for the next proof of that shape
         static std::mutex mu;
         static uint64_t key[5] = {0, 0, 0, 0, 0};
         static std::vector<uint64_t> kept;
         const uint64_t want[5] = {p64, cfg->trace_offset, w_n, cfg->log_n, kt};
         std::lock_guard<std::mutex> lock(mu);
-        if (memcmp(key, want, sizeof key) != 0 || kept.size() != n) {
-            kept.assign(n, 0);
+        if (memcmp(key, want, sizeof key) != 0 || kept.size() != extra * n) {   // k_t tells the two forms apart
+            kept.assign(extra * n, 0);
             zk_exemption_column((uint32_t)p64, (uint32_t)cfg->trace_offset, w_n, cfg->log_n, (uint32_t)kt, kept.data());
+            if (list) {
+                const uint32_t wk = host_powmod(w_n, kt, (uint32_t)p64);
+                uint64_t *ea = kept.data() + n;
+                for (uint64_t r = 0; r < n; r++) ea[(r + 1) & (n - 1)] = host_mulmod((uint32_t)kept[r], wk, (uint32_t)p64);
+            }
             memcpy(key, want, sizeof key);
         }
-        memcpy(Z->pval.data() + at, kept.data(), n * 8);
+        memcpy(Z->pval.data() + at, kept.data(), extra * n * 8);
     }
     smi_air &a = Z->air;
     a.n_constraints = K, a.n_terms = nt, a.n_factors = (uint32_t)Z->var.size(), a.n_boundary = nb;
     a.constraint_first_term = Z->cft.data(), a.term_coeff = Z->coeff.data(), a.term_first_factor = Z->tff.data();
     a.factor_var = Z->var.data(), a.factor_exp = Z->exp.data();
     a.boundary_col = Z->bcol.data(), a.boundary_row = Z->brow.data(), a.boundary_value = Z->bval.data();
-    a.n_periodic = Q + 1, a.reserved0 = 0;
+    a.n_periodic = Q + extra, a.reserved0 = 0;
     a.periodic_log_period = Z->plog.data(), a.periodic_value = Z->pval.data();
     return SMI_OK;
 }

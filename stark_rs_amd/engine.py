@@ -920,6 +920,93 @@ class Engine:
             out["stage_ms"] = dict(zip(("random", "lde", "commit", "compose", "segments", "ood", "mask", "fri", "open"), [float(x) for x in stage]))
         return out
 
+    # ---- zero-knowledge DEEP proofs with an argument list (include/stark_mi.h, "Zero-knowledge DEEP proofs with an argument list")
+    def air_plan_deep_zk_args(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_plan_deep_zk_xargs for air's argument list -> (d, D', k_t = 8 t + 16, k_s).  Host only."""
+        a = self._args_of(air, "air_plan_deep_zk_args")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_plan_deep_zk_args(self.p, a, xargs_of(a), cfg)
+
+    def air_deep_zk_args_layout(self, air, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset=1, lde_offset=None):
+        """smi_air_deep_zk_xargs_layout -> (folds, proof bytes) of dev_air_prove(deep_args=True, coset_leaves=True, zk=seed).  Host only."""
+        a = self._args_of(air, "air_deep_zk_args_layout")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        return air_deep_zk_args_layout(self.p, a, xargs_of(a), cfg)
+
+    def dev_xargs_multiplicities_rows(self, air, a, d_trace_cols, n_cols, log_n, rows, d_mult):
+        """smi_dev_xargs_multiplicities_rows: the multiplicities of lookup argument a over the rows < rows into d_mult (n words)"""
+        f = self._args_of(air, "dev_xargs_multiplicities_rows")
+        self._ck_perm(self.L.smi_dev_xargs_multiplicities_rows(self.h, C.byref(f), C.byref(xargs_of(f)), a, vp(d_trace_cols), n_cols, log_n, rows,
+                                                               vp(d_mult)))
+
+    def dev_zk_args_tail(self, d_c, log_n, k_t, n_args, d_rnd, c_stride=None):
+        """smi_dev_zk_args_tail: rows n - k_t + 1 .. n - 1 of the 4 n_args coordinate columns at d_c take the random words at
+        d_rnd -> the closing values c_a[n - k_t], n_args elements of four coordinates"""
+        closing = np.zeros(4 * n_args, dtype=np.uint64)
+        self._ck(self.L.smi_dev_zk_args_tail(self.h, vp(d_c), (1 << log_n) if c_stride is None else c_stride, log_n, k_t, n_args, vp(d_rnd),
+                                             closing.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [[int(v) for v in closing[4 * a:4 * a + 4]] for a in range(n_args)]
+
+    def dev_air_compose_zk_args(self, air, d_lde, d_c_lde, n_cols, log_n, log_blowup, num_colinearity_tests, challenges, d_weights, d_out, trace_offset=1,
+                                lde_offset=None, stride=None, c_stride=None, out_stride=None):
+        """smi_dev_air_compose_zk_xargs: the composition of the derived AIR plus the 3 A auxiliary quotients into four coordinate
+        columns; challenges: alpha, gamma (8 unreduced values); d_weights: 4 (W + K + 3 A) u64 on the device"""
+        a = self._args_of(air, "dev_air_compose_zk_args")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, True)
+        N = 1 << (log_n + log_blowup)
+        ch = (C.c_uint64 * 8)(*[int(v) for v in challenges])
+        self._ck(self.L.smi_dev_air_compose_zk_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xargs_of(a)), vp(d_lde), N if stride is None else stride,
+                                                     vp(d_c_lde), N if c_stride is None else c_stride, ch, vp(d_weights), vp(d_out),
+                                                     N if out_stride is None else out_stride))
+
+    def _dev_air_prove_deep_zk_args(self, air, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, grind_bits,
+                                    fill_multiplicities, zk):
+        import os
+        xa = xargs_of(a)
+        A = xa.count
+        seed = os.urandom(32) if zk is True else bytes(zk)
+        if len(seed) != 32:
+            raise ValueError("zk: the seed is 32 bytes (or True for os.urandom(32))")
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
+        _d, Dp, kt, _ks = air_plan_deep_zk_args(self.p, a, xa, cfg)
+        lookups = [i for i in range(A) if xa.arg[i].kind == 1]
+        if fill_multiplicities and not lookups:
+            raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
+        if fill_multiplicities:   # over the active rows, before the prover writes the randomiser rows
+            for i in lookups:
+                self._ck_perm(self.L.smi_dev_xargs_multiplicities_rows(self.h, C.byref(a), C.byref(xa), i, vp(d_trace_cols), n_cols, log_n, (1 << log_n) - kt,
+                                                                       vp(vp(d_trace_cols).value + 4 * (xa.arg[i].mult_col << log_n))))
+        if check:
+            if isinstance(air, _lib.Air):
+                raise ValueError("zk with check=True derives the AIR to check from a mirror.Air; pass one, or check=False")
+            derived = air.zk_derived(self.p, log_n, t, trace_offset, self.prim_nth_root(1 << log_n), with_args=True)
+            ok, _con, _row, why = self.dev_air_check(derived.flatten(self.p), d_trace_cols, n_cols, log_n)
+            if not ok:
+                raise StarkMiError(-50, why)
+        roots = np.zeros((3, 32), dtype=np.uint8)
+        cnt = 2 * n_cols + 2 * A + Dp
+        ood = np.zeros(4 * cnt, dtype=np.uint64)
+        proof, plen, mask = vp(), C.c_size_t(), C.c_uint32()
+        top = np.zeros(max(t, 1), dtype=np.uint64)
+        stage = (C.c_double * 10)()
+        self._ck_perm(self.L.smi_dev_air_prove_deep_zk_xargs(self.h, C.byref(cfg), C.byref(a), C.byref(xa), vp(d_trace_cols), seed, roots.ctypes.data,
+                                                             ood.ctypes.data, C.byref(proof), C.byref(plen), top.ctypes.data, stage if timed else None,
+                                                             0 if grind_bits is None else grind_bits, C.byref(mask)))
+        b = C.string_at(proof, plen.value)
+        self.L.smi_free(proof)
+        closes = [bool(mask.value >> i & 1) for i in range(A)]
+        if check and not all(closes):
+            raise StarkMiError(-50, f"air_prove_deep_zk_xargs: the arguments {[i for i, c in enumerate(closes) if not c]} do not close")
+        out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]], "closes": closes, "seed": seed,
+               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(cnt)]}
+        if timed:
+            out["stage_ms"] = dict(zip(("random", "lde", "commit", "args", "compose", "segments", "ood", "mask", "fri", "open"), [float(x) for x in stage]))
+        return out
+
+    def _zk_takes_a_list(self, a, deep, deep_args, coset_leaves):
+        """zk with deep_args=True, coset_leaves=True and an AIR that carries a list: the list variant"""
+        return bool(deep_args and coset_leaves and not deep and (self._xargs(a) is not None or self._args(a) is not None))
+
     def _check_air_folding(self, a, folding, row_leaves, ext):
         _check_folding(folding)
         if folding == 4 and not (row_leaves and ext):
@@ -966,11 +1053,22 @@ class Engine:
         smi_dev_air_prove_deep_zk -- the zero-knowledge variant (include/stark_mi.h, "Zero-knowledge DEEP proofs").  The last
         k_t = 8 t + 8 rows of the device trace are OVERWRITTEN with random residues; the statement covers the rows before them.
         check=True checks the derived AIR (air must then be a mirror.Air).  The result gains "seed", which is in no proof and
-        must stay with the prover; "ood" has 2 W + D' elements; stage_ms has nine stages."""
+        must stay with the prover; "ood" has 2 W + D' elements; stage_ms has nine stages.
+        zk with deep_args=True, coset_leaves=True and an AIR that carries a list: smi_dev_air_prove_deep_zk_xargs (include/
+        stark_mi.h, "Zero-knowledge DEEP proofs with an argument list").  k_t = 8 t + 16 rows are overwritten and every argument
+        is over the rows before them; column_roots is (3, 32); the result has "closes" and "seed"; "ood" has 2 W + 2 A + D'
+        elements; stage_ms has ten stages; fill_multiplicities=True counts over the active rows only
+        (smi_dev_xargs_multiplicities_rows)."""
         a = self._air(air)
         if zk is not None and zk is not False:
+            if self._zk_takes_a_list(a, deep, deep_args, coset_leaves):
+                self._check_coset_leaves(row_leaves, ext, deep, deep_args)
+                self._check_deep_args(a, row_leaves, ext, folding, deep)
+                return self._dev_air_prove_deep_zk_args(air, a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset,
+                                                        timed, check, grind_bits, fill_multiplicities, zk)
             if not (deep and coset_leaves) or deep_args:
-                raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR: pass deep=True, coset_leaves=True")
+                raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR (deep=True, coset_leaves=True) or of an AIR with an argument "
+                                 "list (deep_args=True, coset_leaves=True)")
             self._check_coset_leaves(row_leaves, ext, deep, deep_args)
             return self._dev_air_prove_deep_zk(air, a, d_trace_cols, n_cols, log_n, log_blowup, num_colinearity_tests, trace_offset, lde_offset, timed,
                                                check, row_leaves, ext, grind_bits, fill_multiplicities, folding, zk)
@@ -1129,7 +1227,7 @@ class Engine:
                    lde_offset=None, row_leaves=False, ext=False, grind_bits=None, folding=2, deep=False, deep_args=False,
                    coset_leaves=False, zk=False):
         """verifier of dev_air_prove -> (accept, reason).  zk=True (needs deep=True, coset_leaves=True; ValueError otherwise):
-        smi_air_verify_deep_zk.  row_leaves: smi_air_verify_rows, column_roots is the one root of
+        smi_air_verify_deep_zk; with deep_args=True, coset_leaves=True and an AIR that carries a list: smi_air_verify_deep_zk_xargs.  row_leaves: smi_air_verify_rows, column_roots is the one root of
         the tree over the rows.  ext (needs row_leaves): smi_air_verify_ext.  grind_bits (needs ext; None: a proof without
         grinding): smi_air_verify_ext_pow, the least proof-of-work difficulty demanded.
         An AIR with a permutation takes smi_air_verify_perm: row_leaves=True and ext=True are required (ValueError otherwise),
@@ -1141,8 +1239,10 @@ class Engine:
         deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots.
         coset_leaves=True: smi_air_verify_deep_fold4 / smi_air_verify_deep_xargs_fold4, under the conditions of
         dev_air_prove(coset_leaves=True); folding stays 2."""
-        if zk and (not (deep and coset_leaves) or deep_args):
-            raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR: pass deep=True, coset_leaves=True")
+        zk_list = bool(zk) and self._zk_takes_a_list(self._air(air), deep, deep_args, coset_leaves)
+        if zk and not zk_list and (not (deep and coset_leaves) or deep_args):
+            raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR (deep=True, coset_leaves=True) or of an AIR with an argument "
+                             "list (deep_args=True, coset_leaves=True)")
         if coset_leaves:
             self._check_coset_leaves(row_leaves, ext, deep, deep_args)
         if deep_args:
@@ -1153,7 +1253,7 @@ class Engine:
             if roots.size != 96:
                 raise StarkMiError(-50, "air_verify(deep_args=True) takes three 32-byte roots")
             acc = C.c_int()
-            verify = self.L.smi_air_verify_deep_xargs_fold4 if coset_leaves else self.L.smi_air_verify_deep_xargs
+            verify = self.L.smi_air_verify_deep_zk_xargs if zk_list else self.L.smi_air_verify_deep_xargs_fold4 if coset_leaves else self.L.smi_air_verify_deep_xargs
             self._ck(verify(self.h, C.byref(cfg), C.byref(a), C.byref(xa), roots.ctypes.data, proof, len(proof), C.byref(acc),
                             0 if grind_bits is None else grind_bits))
             return bool(acc.value), ("" if acc.value else self.L.smi_last_error(self.h).decode())
@@ -1348,6 +1448,26 @@ def air_deep_zk_layout(p, air, cfg):
     f, n = C.c_uint64(), C.c_size_t()
     L = _lib.lib()
     st = L.smi_air_deep_zk_layout(p, C.byref(cfg), C.byref(air), C.byref(f), C.byref(n))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return f.value, n.value
+
+
+def air_plan_deep_zk_args(p, air, xargs, cfg):
+    """smi_air_plan_deep_zk_xargs (host only) -> (d, D', k_t, k_s).  air: a flattened _lib.Air; xargs: xargs_of(air)"""
+    d, D, kt, ks = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    L = _lib.lib()
+    st = L.smi_air_plan_deep_zk_xargs(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(d), C.byref(D), C.byref(kt), C.byref(ks))
+    if st:
+        raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
+    return d.value, D.value, kt.value, ks.value
+
+
+def air_deep_zk_args_layout(p, air, xargs, cfg):
+    """smi_air_deep_zk_xargs_layout (host only) -> (folds, proof bytes)"""
+    f, n = C.c_uint64(), C.c_size_t()
+    L = _lib.lib()
+    st = L.smi_air_deep_zk_xargs_layout(p, C.byref(cfg), C.byref(air), C.byref(xargs), C.byref(f), C.byref(n))
     if st:
         raise StarkMiError(st, f"{_lib.status_string(st)}: {L.smi_air_last_error().decode()}")
     return f.value, n.value

@@ -969,12 +969,15 @@ class Air:
         out.boundaries = list(self.boundaries)
         return out
 
-    def zk_derived(self, p, log_n, t, trace_offset, omega_n):
+    def zk_derived(self, p, log_n, t, trace_offset, omega_n, with_args=False):
         """-> the AIR that a zero-knowledge DEEP proof of this one proves (include/stark_mi.h, "Zero-knowledge DEEP proofs"): one
         more periodic column of period n = 2^log_n holding E(tau w^r), E(x) = prod over the exempt rows q = n - k_t - 1 .. n - 2
-        of (x - tau w^q), k_t = 8 t + 8, as one more factor of every transition term.  n k_t products in Python ints."""
+        of (x - tau w^q), k_t = 8 t + 8, as one more factor of every transition term.  n k_t products in Python ints.
+        with_args: the list form ("... with an argument list") -- k_t = 8 t + 16 and a second column, E_A(tau w^r) with the roots
+        q = n - k_t .. n - 1, that no constraint reads; the result carries no argument list (the arguments cover the rows below
+        n - k_t and are the prover's to check: "closes")."""
         import copy
-        n, kt = 1 << log_n, 8 * t + 8
+        n, kt = 1 << log_n, 8 * t + (16 if with_args else 8)
         pts = [trace_offset * pow(omega_n, r, p) % p for r in range(n)]
         col = []
         for r in range(n):
@@ -985,6 +988,10 @@ class Air:
         out = copy.deepcopy(self)
         j = out.periodic(col)
         out._symbolic = [[(cf, list(factors) + [("per", j, 1)]) for cf, factors in con] for con in out._symbolic]
+        if with_args:
+            wk = pow(omega_n, kt, p)
+            out.periodic([col[(r - 1) % n] * wk % p for r in range(n)])   # E_A(x w) = w^k_t E(x)
+            out.args = []
         return out
 
     def transition(self, poly):

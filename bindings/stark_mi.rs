@@ -185,6 +185,8 @@ pub const SMI_ARGS_MAX: u32 = 8;
 pub const SMI_ARG_PERM: u32 = 0;
 pub const SMI_ARG_LOOKUP: u32 = 1;
 pub const SMI_ARG_NO_SELECTOR: u32 = 0xffffffff;
+pub const SMI_ARG_MAX_TUPLES: u32 = 4;
+pub const SMI_ARG_TUPLES_SHIFT: u32 = 8;
 
 #[link(name = "starkmi")]
 extern "C" {
@@ -1189,8 +1191,26 @@ impl SelectedArguments {
         self.items.push(item);
         self
     }
+    /// A shared-table lookup (include/stark_mi.h, "Shared-table lookups"): 1 ..= `SMI_ARG_MAX_TUPLES` looked-up tuples of one
+    /// width, each with its own optional selector, into one table with one multiplicity column and one running sum.  One
+    /// tuple is `lookup`.
+    pub fn shared_lookup(mut self, tuples: &[&[Operand]], sels: &[Option<Operand>], table: &[Operand], mult_col: u32, table_sel: Option<Operand>) -> SelectedArguments {
+        assert!(!tuples.is_empty() && tuples.len() <= SMI_ARG_MAX_TUPLES as usize && sels.len() == tuples.len(), "1 ..= SMI_ARG_MAX_TUPLES tuples, one selector or None each");
+        assert!(!table.is_empty() && table.len() <= SMI_LOOKUP_MAX_WIDTH as usize && tuples.iter().all(|t| t.len() == table.len()), "tuples of the table's width, 1 ..= SMI_LOOKUP_MAX_WIDTH");
+        if tuples.len() == 1 {
+            return self.lookup(tuples[0], table, mult_col, sels[0], table_sel);
+        }
+        assert!(self.items.len() < SMI_ARGS_MAX as usize, "at most SMI_ARGS_MAX arguments");
+        // a_var: the J m operands, tuple-major, then the J selector entries; J - 1 in the second byte of kind
+        let mut a: Vec<u32> = tuples.iter().flat_map(|t| t.iter().map(|o| self.var(*o))).collect();
+        a.extend(sels.iter().map(|x| self.sel(*x)));
+        let kind = SMI_ARG_LOOKUP | ((tuples.len() as u32 - 1) << SMI_ARG_TUPLES_SHIFT);
+        let item = (kind, a, table.iter().map(|o| self.var(*o)).collect(), mult_col, SMI_ARG_NO_SELECTOR, self.sel(table_sel));
+        self.items.push(item);
+        self
+    }
     fn with_raw<R>(&self, f: impl FnOnce(*const c_void) -> R) -> R {
-        let raw: Vec<smi_air_xarg> = self.items.iter().map(|(kind, a, b, m, sa, sb)| smi_air_xarg { kind: *kind, width: a.len() as u32, mult_col: *m, reserved0: 0, a_var: a.as_ptr(), b_var: b.as_ptr(), a_sel: *sa, b_sel: *sb }).collect();
+        let raw: Vec<smi_air_xarg> = self.items.iter().map(|(kind, a, b, m, sa, sb)| smi_air_xarg { kind: *kind, width: b.len() as u32, mult_col: *m, reserved0: 0, a_var: a.as_ptr(), b_var: b.as_ptr(), a_sel: *sa, b_sel: *sb }).collect();
         let list = smi_air_xargs { count: raw.len() as u32, reserved0: 0, arg: raw.as_ptr() };
         f(&list as *const smi_air_xargs as *const c_void)
     }

@@ -883,7 +883,8 @@ int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  * Left out: several lookups, or several looked-up tuples sharing one table; next-row tuple members (selectors and
  *   periodic members: "Argument list with selectors and periodic members" below); a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
  *   column-tree or smi_mgpu_* twin.  Several lookups, each with a multiplicity column of its own, and lookups together
- *   with permutations are what "Argument list" below adds; these entry points stay at one. */
+ *   with permutations are what "Argument list" below adds, several looked-up tuples sharing one table and one multiplicity
+ *   column what "Shared-table lookups" adds; these entry points stay at one. */
 #define SMI_LOOKUP_MAX_WIDTH 8
 typedef struct smi_air_lookup {
     uint32_t width, mult_col;       /* m, 1 .. SMI_LOOKUP_MAX_WIDTH; the multiplicity column, < n_cols */
@@ -954,8 +955,9 @@ int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
  *   rejects a proof with a column that does not.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): count in 1 .. SMI_ARGS_MAX; kind 0 or 1;
  *   every argument by its own section's limits, the reason naming the argument's index; everything smi_air_plan refuses.
- * Left out: next-row tuple members; several lookups sharing one multiplicity column (selectors and periodic members are
- *   what "Argument list with selectors and periodic members" below adds; these entry points stay as they are); the auxiliary
+ * Left out: next-row tuple members (selectors and periodic members are what "Argument list with selectors and periodic
+ *   members" below adds, several tuples under one multiplicity column what "Shared-table lookups" adds to that section's
+ *   entry points; these entry points stay as they are and refuse a kind with a tuple count); the auxiliary
  *   quotients fused into the main composition launch; a column-tree or smi_mgpu_* twin; a wave-level scan. */
 #define SMI_ARGS_MAX 8
 #define SMI_ARG_PERM 0
@@ -1040,12 +1042,15 @@ int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   the same list; the roots, the columns and the codeword are equal too.
  * Limits (SMI_ERR_BAD_ARG, the reason names the argument): those of "Argument list"; every operand a this-row variable;
  *   mult_col < n_cols, none of the argument's trace operands, none of its selectors; everything smi_air_plan refuses.
- * Left out: next-row tuple members; several lookups sharing one multiplicity column; a column-tree or smi_mgpu_* twin.
+ * Left out: next-row tuple members; a column-tree or smi_mgpu_* twin.  (Several looked-up tuples under one table, one
+ *   multiplicity column and one running sum: "Shared-table lookups" below, through these entry points.)
  *   (FRI at the full blowup and a lookup list at log_blowup = 2 are what "Out-of-domain sampling with an argument list"
  *   below adds.) */
 #define SMI_ARG_NO_SELECTOR 0xffffffffu
+#define SMI_ARG_MAX_TUPLES   4
+#define SMI_ARG_TUPLES_SHIFT 8      /* kind = SMI_ARG_LOOKUP | (J - 1) << SMI_ARG_TUPLES_SHIFT, J in 1 .. SMI_ARG_MAX_TUPLES ("Shared-table lookups") */
 typedef struct smi_air_xarg {
-    uint32_t kind;            /* SMI_ARG_PERM = 0, SMI_ARG_LOOKUP = 1              */
+    uint32_t kind;            /* SMI_ARG_PERM = 0, SMI_ARG_LOOKUP = 1; bits 8 .. 15: J - 1 */
     uint32_t width;           /* m, 1 .. 8                                          */
     uint32_t mult_col;        /* a trace column; ignored for a permutation          */
     uint32_t reserved0;       /* explicit padding, ignored                          */
@@ -1082,6 +1087,60 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
                             uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits, uint32_t *closes);
 int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const void *xargs, const uint8_t *roots, const uint8_t *proof,
                          size_t proof_len, int *accept, uint32_t grind_bits);
+
+/* ---- Shared-table lookups: several tuples, one multiplicity, one running sum --------------------
+ * In the sections above every looked-up tuple is an argument of its own: a multiplicity column in the trace, four committed
+ * coordinate columns, two auxiliary quotients (three under zero knowledge) and one of the SMI_ARGS_MAX slots.  A range check of
+ * four byte columns against one table 0 .. 255 takes half the list.  LogUp needs one multiplicity column and one running sum
+ * for all of them, and this section gives that to the smi_*_xargs entry points of every variant -- row leaves, DEEP, coset
+ * leaves, zero knowledge -- without a new entry point or struct.  smi_air_arg (the list without selectors) keeps refusing.
+ *
+ * Statement.  A shared lookup has J looked-up tuples of width m, one table tuple, one multiplicity column and one running
+ *   sum.  Tuple j has the operands a_j[0 .. m) and an optional selector S_j; the table side is b_var, b_sel, mult_col as in
+ *   "Argument list with selectors and periodic members".  With f_j = gamma + sum_i alpha^i V(a_j[i]) and f_T as there,
+ *       s[0] = 0,   s[r+1] = s[r] + sum_{j<J} S_j(r) / f_j(r)  -  M(r) S_b(r) / f_T(r);
+ *   it closes iff the step after the last row returns to 0 (under zero knowledge: iff c_a[n_a] = 0).  M[t] counts the
+ *   (row, tuple) pairs that hit table row t; two tuples of one row may hit the same table row.  The boundary quotient and
+ *   the closing quotient of the zero-knowledge variant are a lookup's.  With P = prod_j f_j and
+ *   Nn = sum_j S_j prod_{i != j} f_i the wrapping transition quotient is
+ *       ((s(w x) - s(x)) P f_T  -  Nn f_T  +  (M S_b) P) / (x^n - tau^n);
+ *   with J = 1 that is the lookup of that section, word for word.
+ * Encoding.  smi_air_xarg.kind = SMI_ARG_LOOKUP | (J - 1) << SMI_ARG_TUPLES_SHIFT: the low byte is the kind, bits 8 .. 15 hold
+ *   J - 1, bits 16 and above are 0.  J = 1 is the value SMI_ARG_LOOKUP itself: every list written before means what it meant.
+ *   For J >= 2: a_var holds the J m operands, tuple-major, followed by J selector entries (an operand each, or
+ *   SMI_ARG_NO_SELECTOR); a_sel is SMI_ARG_NO_SELECTOR; width is m; mult_col is none of the operands and none of the
+ *   selectors.  reserved0 stays ignored.
+ * Degree.  A shared lookup contributes J + 2 to d in smi_air_plan_xargs and smi_air_plan_deep_xargs and J + 3 in
+ *   smi_air_plan_deep_zk_xargs (3 and 4 for J = 1, as before); D, E, D' and every layout follow as they do there.  So the
+ *   saving in columns is conditional on the blowup at hand:
+ *     row leaves, fold 2   E = B / D >= 4 is needed: J = 2, 3 (D = 4) run from log_blowup 4, J = 4 (D = 8) from log_blowup 5,
+ *                          where a single lookup runs from 3;
+ *     DEEP, no zk          J = 2, 3 give D = 4, J = 4 gives D = 8, where a list of single lookups has D = 2: the composition
+ *                          gains segments while the trace and the second tree lose columns;
+ *     DEEP with zk         J = 2 keeps D = 4, exactly as a single lookup does -- sharing is free there; J = 3, 4 give D = 8;
+ *     an AIR whose own degree reaches J + 2 (J + 3 under zk) pays nothing anywhere.
+ * Kernels.  The tuples are folded one at a time into the pair (Nn, P) <- (Nn f_j + S_j P, P f_j) from (0, 1), so that a row
+ *   has ONE denominator P f_T and one numerator Nn f_T - (M S_b) P: the column build keeps its one F_q inversion per lane
+ *   of four rows, and registers grow by two F_q values a row, not by J.  A list in which some argument has J >= 2 takes
+ *   sibling launches (xargs_block_shared_kernel, air_xargs_compose_shared_kernel, air_zk_xargs_compose_shared_kernel,
+ *   xargs_count_shared_kernel) that get the tuples in a structure of their own; every other list launches the kernels it
+ *   launched, unchanged.  The scan, propagation, insert and tail launches are shared.
+ * Multiplicities.  smi_dev_xargs_multiplicities / _rows: the insert launch is unchanged; in the count launch a lane probes
+ *   once per selected tuple of its row.  SMI_ERR_LOOKUP_MISSING names the smallest row and, within it, the smallest tuple.
+ * Zero denominators.  A zero f_j or f_T is SMI_ERR_NO_INVERSE on every row, selected or not; the smallest (row, argument,
+ *   side) is reported, side = j for f_j and J for f_T, and for J >= 2 the sentence names the tuple.  A list without a
+ *   shared lookup keeps its key 16 row + 2 a + side and its sentence.
+ * Verifiers.  The order of checks and the sentences of each variant, unchanged; the transition numerator above is
+ *   recomputed from the opened rows (row leaves) or at z (DEEP, coset leaves, zero knowledge).  A proof checked under
+ *   J - 1 tuples, one changed operand, one dropped selector or the J single lookups is rejected.
+ * Limits (SMI_ERR_BAD_ARG, the reason names the argument): tuple bits on a permutation; J > SMI_ARG_MAX_TUPLES; a set a_sel
+ *   for J >= 2; a next-row operand in any tuple or selector; J n >= p, where the multiplicities could wrap (reachable for
+ *   J >= 2 alone, and only through the entry points that take log_n without a blowup: a plan keeps n <= (p - 1) / 4);
+ *   kind = 2, or bits above the second byte, with the sentence of "Argument list".
+ * Measured (profiles/shared_lookup_time.log, profiles/shared_lookup_kernel_resources.log): DESIGN.md section 11.
+ * Left out: next-row tuple members; several tables in one argument; sharing across arguments (a joint closing condition
+ *   over several columns); more than 4 tuples; smi_mgpu_* twins; the list without selectors (smi_air_args); an AIR digest
+ *   in the transcript. */
 
 /* ---- Out-of-domain sampling (DEEP): FRI at the full blowup -------------------------------------
  * The AIR proofs above recompute the composition at the t queried positions only, so their FRI runs at E = B / D, an AIR

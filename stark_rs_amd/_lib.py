@@ -87,6 +87,8 @@ class AirXArgs(C.Structure):
 
 
 NO_SELECTOR = 0xffffffff   # SMI_ARG_NO_SELECTOR
+ARG_MAX_TUPLES = 4          # SMI_ARG_MAX_TUPLES
+ARG_TUPLES_SHIFT = 8        # SMI_ARG_TUPLES_SHIFT: kind = 1 | (J - 1) << 8 for a shared lookup of J tuples
 
 
 def build(force=False):

@@ -369,6 +369,8 @@ struct DeepProver {
     // host state; the vectors that a queued copy reads or fills live as long as the prover
     AirHost H;
     XArgsDev XD;
+    XSharedDev SHs;
+    const XSharedDev *SH = nullptr;   // &SHs when the list has a shared lookup
     Transcript tr;
     uint8_t roots[96];
     FqH z;
@@ -464,7 +466,8 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     transcript_perm_challenges(s.tr, s.roots, &ch);
     xargs_build(ctx->fs.F, s.g, s.xargs, s.W, s.air, s.H.per, ch.data(), &s.XD);
     s.XD.pvals = s.d_pvals;   // the raw periodic values the column build reads
-    SMI_TRY(xargs_columns_launch(ctx, s.XD, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
+    s.SH = xshared_build(s.xargs, s.W, &s.SHs) ? &s.SHs : nullptr;
+    SMI_TRY(xargs_columns_launch(ctx, s.XD, s.SH, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
     if (s.zk_kt) {
         ArgsFlags *d_fl = const_cast<ArgsFlags *>(xargs_columns_flags_at(s.d_atmp, s.A, s.n));
         SMI_TRY(smi_dev_random_fill(ctx, s.zk_seed, ZK_STREAM_ARGS_TAIL, s.d_tail, (size_t)s.CW * (s.zk_kt - 1)));
@@ -479,7 +482,7 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(s.d_atmp, s.A, s.n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(dev_ntt(ctx, s.d_c, s.d_coef + (size_t)s.W * s.n, s.log_n, s.n, s.CW, s.n, s.n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(xargs_columns_settle(ctx, s.XD, fl, closes));
+    SMI_TRY(xargs_columns_settle(ctx, s.XD, s.SH, fl, closes));
     transcript_indexed(s.tr, s.roots + 32, 8, 4 * (uint64_t)s.NW, &s.weights);   // root_2, then the indices 8 .. 8 + 4 NW - 1
     return SMI_OK;
 }
@@ -491,8 +494,8 @@ int deep_compose_h(DeepProver &s) {
     HIP_TRY(ctx, hipMemcpyAsync(s.d_weights, s.weights.data(), 8 * s.weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, s.H, s.d_blob, s.d_lde, N, s.d_weights, s.d_cw, N));
     const uint64_t *d_w = s.d_weights + 4 * (size_t)(s.W + s.K);
-    if (s.zk_kt) return zkx_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.log_n, s.zk_kt, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N);
-    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N));
+    if (s.zk_kt) return zkx_compose_launch(ctx, s.XD, s.SH, s.H, (uint32_t)s.cfg->trace_offset, s.log_n, s.zk_kt, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N);
+    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.SH, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N));
     return SMI_OK;
 }
 

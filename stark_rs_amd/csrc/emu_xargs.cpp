@@ -43,7 +43,8 @@ int checks(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xarg
     if (!n_cols || n_cols > 64 || log_n < 1 || log_n > 27) return SMI_ERR_BAD_ARG;
     const int prc = xargs_periodic_check(p, air, log_n, nullptr);
     if (prc != SMI_OK) return prc;
-    return xargs_validate(xargs, n_cols, air->n_periodic, nullptr);
+    const int vrc = xargs_validate(xargs, n_cols, air->n_periodic, nullptr);
+    return vrc != SMI_OK ? vrc : xargs_shared_rows(p, xargs, log_n, nullptr);
 }
 }  // namespace
 
@@ -54,7 +55,7 @@ extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *a
     FieldSetup fs;
     const int rc = checks(p, g, air, xargs, n_cols, log_n, &fs);
     if (rc != SMI_OK) return rc;
-    if (a >= xargs->count || xargs->arg[a].kind != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
+    if (a >= xargs->count || (xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
     const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
     AirPeriodic per;
     xargs_periodic_plan((uint32_t)p, air, log_n, &per);
@@ -62,6 +63,8 @@ extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *a
     const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     xargs_build(fs.F, (uint32_t)g, xargs, n_cols, air, per, no_challenges, &XD);
     XD.pvals = per.vals.data();
+    XSharedDev SH;
+    xshared_build(xargs, n_cols, &SH);
     std::vector<uint32_t> tab(cap, LOOKUP_EMPTY);
     memset(mult, 0, n * 4);
     uint64_t first = ~0ull;
@@ -72,6 +75,13 @@ extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *a
     }
     for (uint64_t k = 0; k < n; k++) {
         const uint32_t r = (uint32_t)(order ? n - 1 - k : k);
+        if (SH.J[a] > 1) {   // xargs_count_shared_kernel: *missing is 4 row + tuple
+            uint32_t miss = 0;
+            const int got = xshared_count_lane(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
+            if ((got & 1) && 4 * (uint64_t)r + miss < first) first = 4 * (uint64_t)r + miss;
+            if (got & 2) exhausted = true;
+            continue;
+        }
         const int got = xlookup_count_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
         if (got == 1 && r < first) first = r;
         if (got == 2) exhausted = true;
@@ -82,7 +92,7 @@ extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *a
 }
 
 // c: 4 A coordinate columns c_stride apart.  *closes: the mask; *key: the smallest 16 row + 2 a + side with a zero
-// denominator, or ~0
+// denominator, or ~0 -- for a list with a shared lookup 64 row + 8 a + side, side = j for f_j and J for f_T
 extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *trace, uint32_t n_cols,
                                  uint32_t log_n, const uint64_t *challenges, uint32_t *c, uint64_t c_stride, uint32_t *closes, uint64_t *key) {
     FieldSetup fs;
@@ -97,6 +107,8 @@ extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, con
     xargs_build(F, (uint32_t)g, xargs, n_cols, air, per, challenges, &XD);
     XD.pvals = per.vals.data();
     const uint32_t A = XD.A;
+    XSharedDev SH;   // a list with a shared lookup runs xargs_block_shared_kernel: *key is 64 row + 8 a + side
+    const bool shared = xshared_build(xargs, n_cols, &SH);
     std::vector<Fq> agg_all((size_t)A * nb), total(A);
     uint64_t first = ~0ull;
     std::vector<Fq> agg(PERM_BLOCK), pre(PERM_BLOCK), pls((size_t)PERM_BLOCK * PERM_ROWS);
@@ -108,14 +120,13 @@ extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, con
             for (uint32_t tid = 0; tid < PERM_BLOCK; tid++) {
                 const uint64_t row0 = (b * PERM_BLOCK + tid) * PERM_ROWS;
                 uint64_t k;
-                xargs_lane_column(
-                    XD, a, F, row0, n,
-                    [&](uint32_t op, uint32_t v[4]) {
-                        if (row0 >= n) v[0] = v[1] = v[2] = v[3] = 0u;
-                        else if (xop_periodic(op)) xargs_periodic_rows(XD, op & 0xffu, row0, v);
-                        else load4(trace + (uint64_t)op * n, row0, n, v);
-                    },
-                    &pls[(size_t)tid * PERM_ROWS], &agg[tid], &k);
+                auto ld = [&](uint32_t op, uint32_t v[4]) {
+                    if (row0 >= n) v[0] = v[1] = v[2] = v[3] = 0u;
+                    else if (xop_periodic(op)) xargs_periodic_rows(XD, op & 0xffu, row0, v);
+                    else load4(trace + (uint64_t)op * n, row0, n, v);
+                };
+                if (shared) xargs_lane_column(XD, SH, a, F, row0, n, ld, &pls[(size_t)tid * PERM_ROWS], &agg[tid], &k);
+                else xargs_lane_column(XD, a, F, row0, n, ld, &pls[(size_t)tid * PERM_ROWS], &agg[tid], &k);
                 if (k < first) first = k;
             }
             agg_all[(size_t)a * nb + b] = wg_scan(perm, agg.data(), pre.data(), XD.g_m, F);
@@ -177,8 +188,9 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
     if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
     if (!ext_field_ok(p, g, nullptr)) return SMI_ERR_BAD_ARG;
     std::string why;
+    // the launch itself has no bound on E: the DEEP provers run it at every blowup a composition of D segments fits
     const int prc = xargs_plan(p, cfg, air, xargs, nullptr, nullptr, &why);
-    if (prc != SMI_OK) return prc;
+    if (prc != SMI_OK && prc != SMI_ERR_EXPANSION_TOO_SMALL) return prc;
     const int rc = emu_air_compose_ext(p, g, cfg, air, lde, stride, weights, out, out_stride, force_direct);
     if (rc != SMI_OK) return rc;
     const uint32_t log_N = cfg->log_n + cfg->log_blowup;
@@ -192,6 +204,8 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
     if (c_stride < A.N) return SMI_ERR_BAD_ARG;
     XArgsDev XD;
     xargs_build(F, (uint32_t)g, xargs, cfg->n_cols, air, H.per, challenges, &XD);
+    XSharedDev SH;
+    const bool shared = xshared_build(xargs, cfg->n_cols, &SH);
     const uint64_t *w = weights + 4 * (uint64_t)(A.W + A.K);
     const uint64_t groups = A.N / PERM_ROWS, want = (groups + PERM_BLOCK - 1) / PERM_BLOCK;
     if (!grid) grid = (uint32_t)(want < 2048 ? want : 2048);
@@ -204,18 +218,18 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
             const uint64_t i0 = gq * PERM_ROWS, i1 = (i0 + B) & (A.N - 1);
             uint32_t acc[4][PERM_ROWS];
             for (int e = 0; e < 4; e++) load4(out + e * out_stride, i0, A.N, acc[e]);
-            xargs_compose_points(
-                XD, F, w, tau_m, A.izt_m, B, i0, x_m, A.omega_m,
-                [&](uint32_t op, uint32_t v[4]) {
-                    if (xop_periodic(op)) {
-                        uint64_t L, at;
-                        const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, i0, &L, &at);
-                        load4(table, at, L, v);
-                    } else {
-                        load4(lde + (uint64_t)op * stride, i0, A.N, v);
-                    }
-                },
-                [&](uint32_t col, bool next, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, next ? i1 : i0, A.N, v); }, acc);
+            auto ld = [&](uint32_t op, uint32_t v[4]) {
+                if (xop_periodic(op)) {
+                    uint64_t L, at;
+                    const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, i0, &L, &at);
+                    load4(table, at, L, v);
+                } else {
+                    load4(lde + (uint64_t)op * stride, i0, A.N, v);
+                }
+            };
+            auto ldc = [&](uint32_t col, bool next, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, next ? i1 : i0, A.N, v); };
+            if (shared) xargs_compose_points(XD, SH, F, w, tau_m, A.izt_m, B, i0, x_m, A.omega_m, ld, ldc, acc);
+            else xargs_compose_points(XD, XNoShared{}, F, w, tau_m, A.izt_m, B, i0, x_m, A.omega_m, ld, ldc, acc);
             for (int e = 0; e < 4; e++) store4(out + e * out_stride, i0, A.N, acc[e]);
             x_m = mont_mul(x_m, xstep_m, F);
         }

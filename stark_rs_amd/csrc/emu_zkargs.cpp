@@ -80,6 +80,8 @@ extern "C" int emu_air_compose_zk_xargs(uint64_t p, uint64_t g, const smi_stark_
     if (c_stride < A.N) return SMI_ERR_BAD_ARG;
     XArgsDev XD;
     xargs_build(F, (uint32_t)g, xargs, cfg->n_cols, &Z.air, H.per, challenges, &XD);
+    XSharedDev SH;
+    const bool shared = xshared_build(xargs, cfg->n_cols, &SH);
     const uint64_t *w = weights + 4 * (uint64_t)(A.W + A.K);
     const uint64_t groups = A.N / PERM_ROWS, want = (groups + PERM_BLOCK - 1) / PERM_BLOCK, n = 1ull << cfg->log_n;
     if (!grid) grid = (uint32_t)(want < 2048 ? want : 2048);
@@ -93,18 +95,18 @@ extern "C" int emu_air_compose_zk_xargs(uint64_t p, uint64_t g, const smi_stark_
             const uint64_t i0 = gq * PERM_ROWS, i1 = (i0 + B) & (A.N - 1);
             uint32_t acc[4][PERM_ROWS];
             for (int e = 0; e < 4; e++) load4(out + e * out_stride, i0, A.N, acc[e]);
-            zkx_compose_points(
-                XD, F, w, tau_m, tna_m, ea_op, A.izt_m, B, i0, x_m, A.omega_m,
-                [&](uint32_t op, uint32_t v[4]) {
-                    if (xop_periodic(op)) {
-                        uint64_t L, at;
-                        const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, i0, &L, &at);
-                        load4(table, at, L, v);
-                    } else {
-                        load4(lde + (uint64_t)op * stride, i0, A.N, v);
-                    }
-                },
-                [&](uint32_t col, bool next, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, next ? i1 : i0, A.N, v); }, acc);
+            auto ld = [&](uint32_t op, uint32_t v[4]) {
+                if (xop_periodic(op)) {
+                    uint64_t L, at;
+                    const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, i0, &L, &at);
+                    load4(table, at, L, v);
+                } else {
+                    load4(lde + (uint64_t)op * stride, i0, A.N, v);
+                }
+            };
+            auto ldc = [&](uint32_t col, bool next, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, next ? i1 : i0, A.N, v); };
+            if (shared) zkx_compose_points(XD, SH, F, w, tau_m, tna_m, ea_op, A.izt_m, B, i0, x_m, A.omega_m, ld, ldc, acc);
+            else zkx_compose_points(XD, XNoShared{}, F, w, tau_m, tna_m, ea_op, A.izt_m, B, i0, x_m, A.omega_m, ld, ldc, acc);
             for (int e = 0; e < 4; e++) store4(out + e * out_stride, i0, A.N, acc[e]);
             x_m = mont_mul(x_m, xstep_m, F);
         }
@@ -147,7 +149,9 @@ extern "C" int emu_xargs_multiplicities_rows(uint64_t p, uint64_t g, const smi_a
     if (rc != SMI_OK) return rc;
     rc = xargs_validate(xargs, n_cols, air->n_periodic, nullptr);
     if (rc != SMI_OK) return rc;
-    if (a >= xargs->count || xargs->arg[a].kind != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
+    rc = xargs_shared_rows(p, xargs, log_n, nullptr);
+    if (rc != SMI_OK) return rc;
+    if (a >= xargs->count || (xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
     const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
     if (!rows || rows > n) return SMI_ERR_BAD_ARG;
     AirPeriodic per;
@@ -156,6 +160,8 @@ extern "C" int emu_xargs_multiplicities_rows(uint64_t p, uint64_t g, const smi_a
     const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     xargs_build(fs.F, (uint32_t)g, xargs, n_cols, air, per, no_challenges, &XD);
     XD.pvals = per.vals.data();
+    XSharedDev SH;
+    xshared_build(xargs, n_cols, &SH);
     std::vector<uint32_t> tab(cap, LOOKUP_EMPTY);
     memset(mult, 0, n * 4);
     uint64_t first = ~0ull;
@@ -166,6 +172,13 @@ extern "C" int emu_xargs_multiplicities_rows(uint64_t p, uint64_t g, const smi_a
     }
     for (uint64_t k = 0; k < rows; k++) {
         const uint32_t r = (uint32_t)(order ? rows - 1 - k : k);
+        if (SH.J[a] > 1) {   // xargs_count_shared_kernel: *missing is 4 row + tuple
+            uint32_t miss = 0;
+            const int got = xshared_count_lane(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
+            if ((got & 1) && 4 * (uint64_t)r + miss < first) first = 4 * (uint64_t)r + miss;
+            if (got & 2) exhausted = true;
+            continue;
+        }
         const int got = xlookup_count_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
         if (got == 1 && r < first) first = r;
         if (got == 2) exhausted = true;

@@ -391,16 +391,17 @@ int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint
 // over caller-owned temporary memory (xargs_columns_tmp_size bytes, 16-byte aligned; XD.pvals on the device), where the
 // build leaves its flags in that memory, the verdicts of a finished build, and the launch of the 2 A auxiliary quotients
 struct XArgsDev;
+struct XSharedDev;   // the tuples of a list with a shared lookup; nullptr below: the list has none
 size_t xargs_columns_tmp_size(uint32_t A, uint64_t n);
-int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp);
+int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp);
 const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n);
-int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes);
-int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes);
+int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
                          size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride);
 int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n);
 // zkargs.hip, for deep.hip (the prover of "Zero-knowledge DEEP proofs with an argument list"): the tail step of the auxiliary
 // columns (d_total: 4 A words for the closing values, d_rnd: 4 A (k_t - 1) random words) and the launch of the 3 A auxiliary
 // quotients over the derived AIR's tables
 int zk_args_tail_launch(smi_ctx *ctx, uint32_t *d_c, size_t c_stride, uint32_t log_n, uint32_t kt, uint32_t A, const uint32_t *d_rnd, uint32_t *d_total);
-int zkx_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, uint32_t log_n, uint32_t kt, const uint32_t *d_lde, size_t stride,
+int zkx_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, uint32_t log_n, uint32_t kt, const uint32_t *d_lde, size_t stride,
                        const uint32_t *d_cl, size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride);

@@ -869,6 +869,36 @@ struct XArgAux {
     void add(uint64_t x, const uint64_t *cur, const uint32_t *per, const uint64_t *cc, const uint64_t *cn, uint32_t got[4]) const {
         uint32_t fl[4], fr[4], c0[4], c1[4], a[4], b[4], bq[4], tq[4], u[4], v[4];
         for (int e = 0; e < 4; e++) fl[e] = fr[e] = gamma[e], c0[e] = (uint32_t)cc[e], c1[e] = (uint32_t)cn[e];
+        const uint32_t J = xarg_tuples(*arg), m = arg->width;
+        if (J > 1) {   // "Shared-table lookups": (s' - s) P f_T - Nn f_T + M S_b P with (Nn, P) folded over the tuples
+            uint32_t P[4] = {1 % p, 0, 0, 0}, Nn[4] = {0, 0, 0, 0}, ds[4], lt[4], nf[4], t[4];
+            for (uint32_t i = 0; i < m; i++)
+                for (int e = 0; e < 4; e++) fr[e] = (uint32_t)((fr[e] + mulm(apow[i][e], val(arg->b_var[i], cur, per), p)) % p);
+            for (uint32_t j = 0; j < J; j++) {
+                uint32_t f[4] = {gamma[0], gamma[1], gamma[2], gamma[3]};
+                for (uint32_t i = 0; i < m; i++)
+                    for (int e = 0; e < 4; e++) f[e] = (uint32_t)((f[e] + mulm(apow[i][e], val(arg->a_var[j * m + i], cur, per), p)) % p);
+                const uint64_t sj = val(arg->a_var[J * m + j], cur, per);
+                ext_mul_host(p, g, Nn, f, t);
+                for (int e = 0; e < 4; e++) Nn[e] = (uint32_t)((t[e] + mulm(sj, P[e], p)) % p);
+                ext_mul_host(p, g, P, f, t);
+                for (int e = 0; e < 4; e++) P[e] = t[e];
+            }
+            for (int e = 0; e < 4; e++) ds[e] = (uint32_t)((c1[e] + (uint64_t)p - c0[e]) % p);
+            ext_mul_host(p, g, P, fr, lt);
+            ext_mul_host(p, g, ds, lt, a);
+            ext_mul_host(p, g, Nn, fr, nf);
+            const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
+            const uint64_t M = mulm(cur[arg->mult_col], val(arg->b_sel, cur, per), p);
+            for (int e = 0; e < 4; e++) {
+                tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - nf[e] + mulm(M, P[e], p)) % p, izt, p);
+                bq[e] = (uint32_t)mulm(c0[e], ixt, p);
+            }
+            ext_mul_host(p, g, bq, wb, u);
+            ext_mul_host(p, g, tq, wt, v);
+            for (int e = 0; e < 4; e++) got[e] = (uint32_t)(((uint64_t)got[e] + u[e] + v[e]) % p);
+            return;
+        }
         for (uint32_t j = 0; j < arg->width; j++)
             for (int e = 0; e < 4; e++) {
                 fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], val(arg->a_var[j], cur, per), p)) % p);
@@ -876,7 +906,7 @@ struct XArgAux {
             }
         const uint64_t sa = val(arg->a_sel, cur, per), sb = val(arg->b_sel, cur, per);
         const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
-        if (arg->kind == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
+        if ((arg->kind & 0xffu) == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
             for (int e = 0; e < 4; e++) {
                 fl[e] = (uint32_t)(((e ? 0 : 1) + mulm(sa, (fl[e] + (uint64_t)p - (e ? 0 : 1)) % p, p)) % p);
                 fr[e] = (uint32_t)(((e ? 0 : 1) + mulm(sb, (fr[e] + (uint64_t)p - (e ? 0 : 1)) % p, p)) % p);

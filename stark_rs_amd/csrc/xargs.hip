@@ -80,19 +80,31 @@ __global__ __launch_bounds__(PERM_BLOCK) void xargs_count_kernel(XArgsDev XD, ui
     if (got == 1) atomicMin(&fl->first, (unsigned long long)r);
     if (got == 2) atomicOr(&fl->exhausted, 1u);
 }
+// the count launch of a shared lookup: one probe per selected tuple of the lane's row; first: the smallest 4 row + tuple missing
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_count_shared_kernel(XArgsDev XD, XSharedDev SH, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n,
+                                                                         uint64_t rows, const uint32_t *__restrict__ tab, uint32_t cap, uint32_t *mult,
+                                                                         XHelperFlags *fl) {
+    const uint64_t r = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
+    if (r >= rows) return;
+    uint32_t miss = 0;
+    const int got = xshared_count_lane(XD, SH, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{}, &miss);
+    if (got & 1) atomicMin(&fl->first, (unsigned long long)(4 * r + miss));
+    if (got & 2) atomicOr(&fl->exhausted, 1u);
+}
 
 // c: 4 A coordinate columns c_stride apart; block_agg: A runs of nb aggregates (four words each); first: the smallest key
-template <bool VEC>
-__global__ __launch_bounds__(PERM_BLOCK) void xargs_block_kernel(XArgsDev XD, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *__restrict__ c,
-                                                                  size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first) {
-    __shared__ uint32_t sc[2][4][PERM_BLOCK];
+// SHT: XNoShared (xargs_block_kernel) or XSharedDev (xargs_block_shared_kernel, a list with a shared lookup)
+template <bool VEC, class SHT>
+__device__ __forceinline__ void xargs_block_body(const XArgsDev &XD, const SHT &SH, const Fp &F, const uint32_t *__restrict__ trace, uint64_t n,
+                                                 uint32_t *__restrict__ c, size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first,
+                                                 uint32_t (*sc)[4][PERM_BLOCK]) {
     const uint32_t tid = threadIdx.x, a = blockIdx.y;
     const bool perm = XD.kind[a] == SMI_ARG_PERM;
     const uint64_t row0 = ((uint64_t)blockIdx.x * PERM_BLOCK + tid) * PERM_ROWS;
     Fq pl[PERM_ROWS], agg;
     uint64_t key;
     xargs_lane_column(
-        XD, a, F, row0, n,
+        XD, SH, a, F, row0, n,
         [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
             if (row0 >= n) {
                 v[0] = v[1] = v[2] = v[3] = 0u;
@@ -122,16 +134,28 @@ __global__ __launch_bounds__(PERM_BLOCK) void xargs_block_kernel(XArgsDev XD, Fp
 #pragma unroll
     for (int e = 0; e < 4; e++) perm_store4<VEC>(ca + e * c_stride, row0, n, o[e]);
 }
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_block_kernel(XArgsDev XD, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *__restrict__ c,
+                                                                  size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first) {
+    __shared__ uint32_t sc[2][4][PERM_BLOCK];
+    xargs_block_body<VEC>(XD, XNoShared{}, F, trace, n, c, c_stride, block_agg, first, sc);
+}
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void xargs_block_shared_kernel(XArgsDev XD, XSharedDev SH, Fp F, const uint32_t *__restrict__ trace, uint64_t n,
+                                                                         uint32_t *__restrict__ c, size_t c_stride, uint32_t *__restrict__ block_agg,
+                                                                         unsigned long long *first) {
+    __shared__ uint32_t sc[2][4][PERM_BLOCK];
+    xargs_block_body<VEC>(XD, SH, F, trace, n, c, c_stride, block_agg, first, sc);
+}
 
 // out (four coordinate columns, the composition of the main AIR) += the 2 A auxiliary quotients under w (8 A coordinates).
 // plog / pofs / ptab: AirDev's periodic tables on the device.
-template <bool VEC>
-__global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
-                                                                        uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
-                                                                        const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
-                                                                        const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl,
-                                                                        size_t c_stride, const uint64_t *__restrict__ w, uint32_t *__restrict__ out,
-                                                                        size_t out_stride) {
+template <bool VEC, class SHT>
+__device__ __forceinline__ void air_xargs_compose_body(const XArgsDev &XD, const SHT &SH, const Fp &F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
+                                                       uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
+                                                       const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde,
+                                                       size_t stride, const uint32_t *__restrict__ cl, size_t c_stride, const uint64_t *__restrict__ w,
+                                                       uint32_t *__restrict__ out, size_t out_stride) {
     const uint64_t groups = N / PERM_ROWS, gid = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x, gstep = (uint64_t)gridDim.x * PERM_BLOCK;
     const uint32_t B = 1u << log_B;
     uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * PERM_ROWS, F), F);
@@ -142,7 +166,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev 
 #pragma unroll
         for (int e = 0; e < 4; e++) perm_load4<VEC>(out + e * out_stride, i0, N, acc[e]);
         xargs_compose_points(
-            XD, F, w, tau_m, izt_m, B, i0, x_m, omega_m,
+            XD, SH, F, w, tau_m, izt_m, B, i0, x_m, omega_m,
             [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
                 if (xop_periodic(op)) {
                     // the table's length L_j = P_j B is a multiple of 4, as i0 is: four consecutive entries, none past the end
@@ -159,6 +183,25 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev 
         x_m = mont_mul(x_m, xstep_m, F);
     }
 }
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
+                                                                        uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
+                                                                        const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
+                                                                        const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl,
+                                                                        size_t c_stride, const uint64_t *__restrict__ w, uint32_t *__restrict__ out,
+                                                                        size_t out_stride) {
+    air_xargs_compose_body<VEC>(XD, XNoShared{}, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
+}
+// the sibling a list with a shared lookup takes ("Shared-table lookups"): the tuples travel in SH
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_shared_kernel(XArgsDev XD, XSharedDev SH, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m,
+                                                                               uint32_t omega_m, uint32_t tau_m, const uint32_t *__restrict__ izt_m,
+                                                                               const uint32_t *__restrict__ plog, const uint32_t *__restrict__ pofs,
+                                                                               const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde, size_t stride,
+                                                                               const uint32_t *__restrict__ cl, size_t c_stride, const uint64_t *__restrict__ w,
+                                                                               uint32_t *__restrict__ out, size_t out_stride) {
+    air_xargs_compose_body<VEC>(XD, SH, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
+}
 
 namespace {
 static_assert(sizeof(XArgsDev) + 160 <= 4096, "the kernel arguments of every launch here stay inside 4 KB");
@@ -167,8 +210,8 @@ size_t xargs_columns_tmp_bytes(uint32_t A, uint64_t n) { return (size_t)A * ((n 
 const ArgsFlags *xargs_columns_flags(const uint8_t *d_tmp, uint32_t A, uint64_t n) {
     return (const ArgsFlags *)(d_tmp + (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16);
 }
-double xargs_cols_read(const XArgsDev &XD) {   // operands read per row, over the arguments
-    double cols = 0;
+double xargs_cols_read(const XArgsDev &XD, const XSharedDev *SH) {   // operands read per row, over the arguments
+    double cols = SH ? xshared_cols_read(XD, *SH) : 0;
     for (uint32_t a = 0; a < XD.A; a++)
         cols += 2 * XD.m[a] + (XD.kind[a] == SMI_ARG_LOOKUP ? 1 : 0) + (XD.asel[a] != SMI_ARG_NO_SELECTOR) + (XD.bsel[a] != SMI_ARG_NO_SELECTOR);
     return cols;
@@ -183,7 +226,9 @@ ArgsDev xargs_scan_tables(const XArgsDev &XD) {
 }
 
 // the three launches; d_tmp: xargs_columns_tmp_bytes(A, n) bytes, 16-byte aligned; XD.pvals on the device
-int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp) {
+// SH: the tuples of a list with a shared lookup, which takes the shared instantiation; nullptr for every other list
+int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride,
+                          uint8_t *d_tmp) {
     const uint64_t n = 1ull << log_n, nb = (n + PERM_TILE - 1) / PERM_TILE;
     uint32_t *d_agg = (uint32_t *)d_tmp;
     ArgsFlags *d_fl = (ArgsFlags *)(d_tmp + (size_t)XD.A * nb * 16);
@@ -192,8 +237,10 @@ int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_tr
     const dim3 grid((uint32_t)nb, XD.A);
     HIP_TRY(ctx, hipMemsetAsync(&d_fl->first, 0xff, 8, ctx->stream));
     {
-        ProfScope ps(ctx, "xargs_block_kernel", (4.0 * xargs_cols_read(XD) + 16.0 * XD.A) * (double)n);
-        if (vec) xargs_block_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        ProfScope ps(ctx, SH ? "xargs_block_shared_kernel" : "xargs_block_kernel", (4.0 * xargs_cols_read(XD, SH) + 16.0 * XD.A) * (double)n);
+        if (SH && vec) xargs_block_shared_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        else if (SH) xargs_block_shared_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        else if (vec) xargs_block_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
         else xargs_block_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -201,7 +248,13 @@ int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_tr
 }
 
 // the verdicts of a finished column build (fl: the flags copied to the host)
-int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes) {
+int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes) {
+    if (SH && fl.first != ~0ull) {   // the key of a list with a shared lookup: 64 row + 8 a + side, side = j for f_j and J for f_T
+        const uint32_t a = (uint32_t)(fl.first >> 3) & 7, side = (uint32_t)fl.first & 7, J = SH->J[a];
+        const std::string what = XD.kind[a] == SMI_ARG_PERM ? "g_R" : side == J ? "f_T" : J > 1 ? "f_" + std::to_string(side) + " (tuple " + std::to_string(side) + ")" : "f_L";
+        const std::string why = "xargs_columns: argument " + std::to_string(a) + ": " + what + " is zero in row " + std::to_string(fl.first >> 6) + ": no inverse";
+        return smi_fail(ctx, SMI_ERR_NO_INVERSE, why.c_str());
+    }
     if (fl.first != ~0ull) {
         const uint32_t a = (uint32_t)(fl.first & 15) >> 1;
         const char *side = !(fl.first & 1) ? "f_L" : XD.kind[a] == SMI_ARG_PERM ? "g_R" : "f_T";
@@ -219,7 +272,7 @@ int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl,
 
 // H bound to the device blob and its periodic tables in place (air_periodic_tables, air_compose_ext_launch); d_w: the 8 A
 // coordinates behind the main weights
-int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
                           size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
     const AirDev &A = H.dev;
     const Fp F = ctx->fs.F;
@@ -232,8 +285,14 @@ int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, ui
     const uint64_t groups = A.N / PERM_ROWS, want = (groups + PERM_BLOCK - 1) / PERM_BLOCK, cap = (uint64_t)ctx->num_cus * 8;
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
     const uint32_t tau_m = air_to_m(tau, F.p);
-    ProfScope ps(ctx, "air_xargs_compose_kernel", (4.0 * xargs_cols_read(XD) + 32.0 * XD.A + 32.0) * (double)A.N);
-    if (vec)
+    ProfScope ps(ctx, SH ? "air_xargs_compose_shared_kernel" : "air_xargs_compose_kernel", (4.0 * xargs_cols_read(XD, SH) + 32.0 * XD.A + 32.0) * (double)A.N);
+    if (SH && vec)
+        air_xargs_compose_shared_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs,
+                                                                                    A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+    else if (SH)
+        air_xargs_compose_shared_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs,
+                                                                                     A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+    else if (vec)
         air_xargs_compose_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde,
                                                                              stride, d_cl, c_stride, d_w, d_out, out_stride);
     else
@@ -253,6 +312,7 @@ int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uin
     const int prc = xargs_periodic_check(ctx->fs.F.p, air, log_n, &why);
     if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
     if (xargs_validate(xargs, n_cols, air->n_periodic, &why) != SMI_OK) return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
+    if (xargs_shared_rows(ctx->fs.F.p, xargs, log_n, &why) != SMI_OK) return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
     return SMI_OK;
 }
 }  // namespace
@@ -272,7 +332,7 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
     DeviceGuard dg__(ctx);
     SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
     if (a >= xargs->count) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities: no such argument");
-    if (xargs->arg[a].kind != SMI_ARG_LOOKUP) {
+    if ((xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) {
         const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + " is a permutation: it has no multiplicities";
         return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
     }
@@ -283,6 +343,9 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
     XArgsDev XD;
     const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the helper reads the operand lists alone
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, n_cols, air, per, no_challenges, &XD);
+    XSharedDev SH;
+    xshared_build(xargs, n_cols, &SH);
+    const uint32_t J = SH.J[a];
     void *tmp = nullptr;   // the table | the flags | the periodic values
     SMI_TRY(ctx_tmp(ctx, 3, cap * 4 + sizeof(XHelperFlags) + per.vals.size() * 4, &tmp));
     uint32_t *d_tab = (uint32_t *)tmp;
@@ -300,14 +363,20 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
         HIP_TRY(ctx, hipGetLastError());
     }
     {
-        ProfScope ps(ctx, "xargs_count_kernel", (4.0 * 2 * m + 8.0) * (double)n);
-        xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
+        ProfScope ps(ctx, J > 1 ? "xargs_count_shared_kernel" : "xargs_count_kernel", (4.0 * 2 * m + 8.0) * J * (double)n);
+        if (J > 1) xargs_count_shared_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, SH, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
+        else xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
         HIP_TRY(ctx, hipGetLastError());
     }
     XHelperFlags fl;
     HIP_TRY(ctx, hipMemcpyAsync(&fl, d_fl, sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // per.vals has been read by now
     if (fl.exhausted) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities: a probe ran through the whole table");
+    if (fl.first != ~0ull && J > 1) {   // 4 row + tuple
+        const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + ": tuple " + std::to_string(fl.first & 3) + " of row " +
+                                std::to_string(fl.first >> 2) + ", which its selector selects, is in no selected table row";
+        return smi_fail(ctx, SMI_ERR_LOOKUP_MISSING, why.c_str());
+    }
     if (fl.first != ~0ull) {
         const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + ": the tuple of selected row " + std::to_string(fl.first) +
                                 " is in no selected table row";
@@ -330,17 +399,19 @@ int smi_dev_xargs_columns(smi_ctx *ctx, const void *air_, const void *xargs_, co
     xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
     XArgsDev XD;
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, n_cols, air, per, challenges, &XD);
+    XSharedDev SHs;
+    const XSharedDev *SH = xshared_build(xargs, n_cols, &SHs) ? &SHs : nullptr;
     const size_t b_tmp = up16(xargs_columns_tmp_bytes(XD.A, n));
     void *tmp = nullptr;   // the aggregates and flags | the periodic values
     SMI_TRY(ctx_tmp(ctx, 3, b_tmp + per.vals.size() * 4, &tmp));
     uint32_t *d_pvals = (uint32_t *)((uint8_t *)tmp + b_tmp);
     XD.pvals = d_pvals;
     if (!per.vals.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pvals, per.vals.data(), per.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(xargs_columns_enqueue(ctx, XD, d_trace_cols, log_n, d_c, c_stride, (uint8_t *)tmp));
+    SMI_TRY(xargs_columns_enqueue(ctx, XD, SH, d_trace_cols, log_n, d_c, c_stride, (uint8_t *)tmp));
     ArgsFlags fl;
     HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags((const uint8_t *)tmp, XD.A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return xargs_columns_verdict(ctx, XD, fl, closes);
+    return xargs_columns_verdict(ctx, XD, SH, fl, closes);
 }
 
 int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_lde, size_t stride,
@@ -362,8 +433,10 @@ int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
     SMI_TRY(air_compose_ext_launch(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride));
     XArgsDev XD;
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, cfg->n_cols, air, H.per, challenges, &XD);
+    XSharedDev SHs;
+    const XSharedDev *SH = xshared_build(xargs, cfg->n_cols, &SHs) ? &SHs : nullptr;
     const uint32_t W = cfg->n_cols, K = air->n_constraints;
-    return xargs_compose_enqueue(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride);
+    return xargs_compose_enqueue(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride);
 }
 
 int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint8_t *roots_out,
@@ -422,7 +495,9 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     XArgsDev XD;
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, W, air, H.per, ch.data(), &XD);
     XD.pvals = d_pvals;
-    SMI_TRY(xargs_columns_enqueue(ctx, XD, d_trace_cols, log_n, d_c, n, d_atmp));
+    XSharedDev SHs;
+    const XSharedDev *SH = xshared_build(xargs, W, &SHs) ? &SHs : nullptr;
+    SMI_TRY(xargs_columns_enqueue(ctx, XD, SH, d_trace_cols, log_n, d_c, n, d_atmp));
     SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
     SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
     tm.mark();
@@ -431,13 +506,13 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(xargs_columns_verdict(ctx, XD, fl, closes));
+    SMI_TRY(xargs_columns_verdict(ctx, XD, SH, fl, closes));
     transcript_args_weights(tr, roots + 32, W, K, A, &weights);
     const FsSeed seed = tr.seed();
     if (roots_out) memcpy(roots_out, roots, 64);
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    SMI_TRY(xargs_compose_enqueue(ctx, XD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
+    SMI_TRY(xargs_compose_enqueue(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
     tm.mark();
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriExtResult xres;
@@ -466,14 +541,17 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
 
 // what deep.hip's prover shares with this file (internal.h)
 size_t xargs_columns_tmp_size(uint32_t A, uint64_t n) { return xargs_columns_tmp_bytes(A, n); }
-int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp) {
-    return xargs_columns_enqueue(ctx, XD, d_trace, log_n, d_c, c_stride, d_tmp);
+int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride,
+                         uint8_t *d_tmp) {
+    return xargs_columns_enqueue(ctx, XD, SH, d_trace, log_n, d_c, c_stride, d_tmp);
 }
 const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n) { return xargs_columns_flags(d_tmp, A, n); }
-int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const ArgsFlags &fl, uint32_t *closes) { return xargs_columns_verdict(ctx, XD, fl, closes); }
-int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes) {
+    return xargs_columns_verdict(ctx, XD, SH, fl, closes);
+}
+int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
                          size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
-    return xargs_compose_enqueue(ctx, XD, H, tau, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+    return xargs_compose_enqueue(ctx, XD, SH, H, tau, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
 }
 int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n) {
     return xargs_args(ctx, air, (const smi_air_xargs *)xargs, n_cols, log_n);

@@ -8,6 +8,8 @@
 // indexed with the argument number and the tuple member only, both wave-uniform, and so is the kind of an operand: every
 // table read stays a scalar load and every branch on it is taken by the whole wave.
 #pragma once
+#include <algorithm>
+
 #include "args_core.h"
 #include "deep_core.h"
 
@@ -28,6 +30,21 @@ struct XArgsDev {   // passed to the kernels by value: 960 bytes
 };
 static_assert(sizeof(XArgsDev) <= 1024, "the kernel arguments stay well inside 4 KB");
 static_assert(SMI_AIR_MAX_PERIODIC <= XOP_PER && 64 <= XOP_PER, "an operand code holds a column of either kind");
+
+// Shared-table lookups (include/stark_mi.h, "Shared-table lookups"): the J looked-up tuples of every argument and their
+// selectors.  It travels by value NEXT TO XArgsDev and only to the kernels' shared instantiations, which a list with some
+// J >= 2 takes; XArgsDev and the instantiations of every other list stay what they were.  For a shared lookup XD.aop[a] is
+// tuple 0 and XD.asel[a] is SMI_ARG_NO_SELECTOR; XD.kind[a] is the kind alone (the low byte).  Indexed like XArgsDev with
+// wave-uniform numbers only.
+struct XSharedDev {   // 1184 bytes
+    uint32_t J[SMI_ARGS_MAX];                           // tuples of argument a; 1 for a permutation and for a single lookup
+    uint32_t sel[SMI_ARGS_MAX][SMI_ARG_MAX_TUPLES];     // operand codes, or SMI_ARG_NO_SELECTOR
+    uint32_t op[SMI_ARGS_MAX][SMI_ARG_MAX_TUPLES][SMI_PERM_MAX_WIDTH];
+};
+struct XNoShared {};   // in the place of XSharedDev for a list without a shared lookup: every use of it folds away
+static_assert(sizeof(XArgsDev) + sizeof(XSharedDev) + 192 <= 4096, "the kernel arguments of the shared instantiations stay inside 4 KB");
+SMI_HD uint32_t xshared_tuples(const XNoShared &, uint32_t) { return 1u; }
+SMI_HD uint32_t xshared_tuples(const XSharedDev &SH, uint32_t a) { return SH.J[a]; }
 
 SMI_HD bool xop_periodic(uint32_t op) { return (op & XOP_PER) != 0; }
 // the four values of periodic column j at the rows row0 .. row0 + 3 of the trace: v_j[(row0 + q) mod P_j], word by word --
@@ -154,6 +171,109 @@ SMI_HD void xargs_lane_column(const XArgsDev &XD, uint32_t a, const Fp &F, uint6
     }
 }
 
+// ---- shared-table lookups: the fold.  (Nn, P) <- (Nn f_j + S_j P, P f_j) over the tuples j < J from (0, 1), so that
+// sum_j S_j / f_j = Nn / P: after it a row has ONE denominator P f_T and one numerator Nn f_T - (M S_b) P, and the lane's
+// batched inversion is the single lookup's.  P is Montgomery, Nn plain (plain times Montgomery is plain; S_j is a plain cell);
+// the first tuple sets (S_0, f_0) without a product.  Two F_q values a row are live across the tuples, whatever J is.
+// DETECT (the column build): a zero f_j of a row below n is replaced by one and zj[q] keeps the smallest such j of row q
+// (zj comes in as ~0).
+template <bool DETECT, class Load4>
+SMI_HD void xshared_fold(const XArgsDev &XD, const XSharedDev &SH, uint32_t a, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq P[PERM_ROWS],
+                         Fq Nn[PERM_ROWS], uint32_t zj[PERM_ROWS]) {
+    const uint32_t p = F.p;
+    for (uint32_t j = 0; j < SH.J[a]; j++) {   // wave-uniform
+        Fq f[PERM_ROWS];
+        uint32_t s[PERM_ROWS];
+        tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, SH.op[a][j], load4, f);
+        if (SH.sel[a][j] != SMI_ARG_NO_SELECTOR) load4(SH.sel[a][j], s);
+        else s[0] = s[1] = s[2] = s[3] = 1u;
+#pragma unroll
+        for (int q = 0; q < PERM_ROWS; q++) {
+            if (DETECT && row0 + q < n && fq_is_zero(f[q])) {
+                f[q] = fq_one(F);
+                if (zj[q] == ~0u) zj[q] = j;
+            }
+            if (!j) {
+                P[q] = f[q];
+                Nn[q] = Fq{{s[q], 0, 0, 0}};
+            } else {
+                const Fq t = fq_mul(Nn[q], f[q], XD.g_m, F);   // plain
+#pragma unroll
+                for (int e = 0; e < 4; e++) Nn[q].c[e] = fp_add(t.c[e], mont_mul(s[q], P[q].c[e], F), p);
+                P[q] = fq_mul(P[q], f[q], XD.g_m, F);
+            }
+        }
+    }
+}
+// xlookup_lane_deltas behind the fold: delta = Nn / P - M S_b / f_T = (Nn f_T - (M S_b) P) / (P f_T).  *zero_at: the smallest
+// 8 row + side, side = j for f_j and J for f_T, or ~0.
+SMI_HD void xshared_lane_deltas(uint32_t g_m, const Fp &F, uint64_t row0, uint64_t n, uint32_t J, Fq P[PERM_ROWS], Fq Nn[PERM_ROWS], Fq ft[PERM_ROWS],
+                                const uint32_t zj[PERM_ROWS], const uint32_t mult[PERM_ROWS], Fq sl[PERM_ROWS], Fq *sum, uint64_t *zero_at) {
+    const uint32_t p = F.p;
+    Fq den[PERM_ROWS], pre[PERM_ROWS];
+    const Fq one = fq_one(F);
+    uint64_t za = ~0ull;
+#pragma unroll
+    for (int q = PERM_ROWS - 1; q >= 0; q--) {
+        if (row0 + q >= n) {
+            P[q] = one;
+            ft[q] = one;
+        } else {
+            if (fq_is_zero(ft[q])) {
+                ft[q] = one;
+                za = 8 * (row0 + q) + J;
+            }
+            if (zj[q] != ~0u) za = 8 * (row0 + q) + zj[q];
+        }
+        den[q] = fq_mul(P[q], ft[q], g_m, F);
+    }
+    pre[0] = den[0];
+#pragma unroll
+    for (int q = 1; q < PERM_ROWS; q++) pre[q] = fq_mul(pre[q - 1], den[q], g_m, F);
+    Fq inv = fq_inv(pre[PERM_ROWS - 1], g_m, F);
+    Fq delta[PERM_ROWS];
+#pragma unroll
+    for (int q = PERM_ROWS - 1; q >= 0; q--) {
+        const Fq di = q ? fq_mul(inv, pre[q - 1], g_m, F) : inv;   // 1 / den[q], Montgomery
+        if (q) inv = fq_mul(inv, den[q], g_m, F);
+        Fq num = fq_mul(Nn[q], ft[q], g_m, F);                         // Nn f_T - (M S_b) P, plain
+#pragma unroll
+        for (int e = 0; e < 4; e++) num.c[e] = fp_sub(num.c[e], mont_mul(mult[q], P[q].c[e], F), p);
+        delta[q] = fq_mul(num, di, g_m, F);                         // plain
+        if (row0 + q >= n) delta[q] = Fq{{0, 0, 0, 0}};
+    }
+    sl[0] = Fq{{0, 0, 0, 0}};
+#pragma unroll
+    for (int q = 1; q < PERM_ROWS; q++) sl[q] = fq_add(sl[q - 1], delta[q - 1], p);
+    *sum = fq_add(sl[PERM_ROWS - 1], delta[PERM_ROWS - 1], p);
+    *zero_at = za;
+}
+// xargs_lane_column of a list with a shared lookup.  *key: the smallest 64 row + 8 a + side with a zero denominator, or ~0:
+// side = j for f_j and J for f_T, so a single lookup keeps 0 for f_L and 1 for f_T and a permutation 1 for g_R, and the
+// order is (row, argument, side).  A list without a shared lookup keeps the key of the function above.
+template <class Load4>
+SMI_HD void xargs_lane_column(const XArgsDev &XD, const XSharedDev &SH, uint32_t a, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq pl[PERM_ROWS],
+                              Fq *agg, uint64_t *key) {
+    if (SH.J[a] < 2) {
+        xargs_lane_column(XD, a, F, row0, n, load4, pl, agg, key);
+        if (*key != ~0ull) *key = 64 * (*key >> 4) + 8 * a + (*key & 1);
+        return;
+    }
+    Fq P[PERM_ROWS], Nn[PERM_ROWS], ft[PERM_ROWS];
+    uint32_t zj[PERM_ROWS] = {~0u, ~0u, ~0u, ~0u}, sa[PERM_ROWS], mult[PERM_ROWS];
+    xshared_fold<true>(XD, SH, a, F, row0, n, load4, P, Nn, zj);
+    tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, ft);
+    xlookup_weights(XD, a, F, load4, sa, mult);   // XD.asel[a] is unset: sa is all ones and is not read
+    uint64_t z;
+    xshared_lane_deltas(XD.g_m, F, row0, n, SH.J[a], P, Nn, ft, zj, mult, pl, agg, &z);
+    *key = z == ~0ull ? z : 64 * (z >> 3) + 8 * a + (z & 7);
+}
+template <class Load4>
+SMI_HD void xargs_lane_column(const XArgsDev &XD, const XNoShared &, uint32_t a, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq pl[PERM_ROWS],
+                              Fq *agg, uint64_t *key) {
+    xargs_lane_column(XD, a, F, row0, n, load4, pl, agg, key);
+}
+
 // ------------------------------------------------------------------------------------------------ the multiplicity helper
 // lookup_core.h's helper over operands: the hash and the comparison read cells through xargs_cell, an unselected row takes
 // no part.  The hash is lookup_hash's function of the values.
@@ -192,13 +312,13 @@ SMI_HD bool xlookup_insert_lane(const XArgsDev &XD, uint32_t a, const uint32_t *
     }
     return false;
 }
-// Count launch, lane r (lookup_count_lane): 0 counted or not selected, 1 the tuple is in no selected table row, 2 the probe
-// ran through the whole table.
+// Count launch: the probe of one looked-up tuple (operands aops, selector sel) of row r.  0 counted or not selected, 1 the
+// tuple is in no selected table row, 2 the probe ran through the whole table.
 template <class Atomics>
-SMI_HD int xlookup_count_lane(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *tab, uint32_t cap, uint32_t r,
-                              uint32_t *mult, Atomics at) {
-    if (!xargs_selected(XD, trace, n, XD.asel[a], r)) return 0;
-    const uint32_t *aops = XD.aop[a], *bops = XD.bop[a], m = XD.m[a];
+SMI_HD int xlookup_count_tuple(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *aops, uint32_t sel, const uint32_t *tab,
+                               uint32_t cap, uint32_t r, uint32_t *mult, Atomics at) {
+    if (!xargs_selected(XD, trace, n, sel, r)) return 0;
+    const uint32_t *bops = XD.bop[a], m = XD.m[a];
     uint32_t slot = xlookup_hash(XD, trace, n, aops, m, r) & (cap - 1);
     for (uint32_t i = 0; i < cap; i++) {
         const uint32_t t = tab[slot];
@@ -210,6 +330,25 @@ SMI_HD int xlookup_count_lane(const XArgsDev &XD, uint32_t a, const uint32_t *tr
         slot = (slot + 1) & (cap - 1);
     }
     return 2;
+}
+// Count launch, lane r (lookup_count_lane): the statuses of xlookup_count_tuple for the argument's one tuple.
+template <class Atomics>
+SMI_HD int xlookup_count_lane(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *tab, uint32_t cap, uint32_t r,
+                              uint32_t *mult, Atomics at) {
+    return xlookup_count_tuple(XD, a, trace, n, XD.aop[a], XD.asel[a], tab, cap, r, mult, at);
+}
+// Count launch of a shared lookup, lane r: one probe per selected tuple of the row, so M[t] counts the (row, tuple) pairs
+// that hit table row t.  -> bit 0: some tuple is missing, *miss = the smallest such j; bit 1: a probe ran through the table.
+template <class Atomics>
+SMI_HD int xshared_count_lane(const XArgsDev &XD, const XSharedDev &SH, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *tab, uint32_t cap,
+                              uint32_t r, uint32_t *mult, Atomics at, uint32_t *miss) {
+    int out = 0;
+    for (uint32_t j = 0; j < SH.J[a]; j++) {
+        const int got = xlookup_count_tuple(XD, a, trace, n, SH.op[a][j], SH.sel[a][j], tab, cap, r, mult, at);
+        if (got == 1 && !(out & 1)) *miss = j, out |= 1;
+        if (got == 2) out |= 2;
+    }
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------ the auxiliary quotients
@@ -237,12 +376,57 @@ SMI_HD void xlookup_compose_point(uint32_t g_m, const Fp &F, const ExtMul &wb, c
     for (int e = 0; e < 4; e++) acc[e][Q] = fp_add(acc[e][Q], fp_add(u[e], v[e], p), p);
 }
 
+// xlookup_compose_point behind the fold: S_a f_T becomes Nn f_T and f_L becomes P, so the transition's numerator is
+// (s' - s) P f_T - Nn f_T + (M S_b) P; P, ft Montgomery, Nn and mult plain.
+template <int Q>
+SMI_HD void xshared_compose_point(uint32_t g_m, const Fp &F, const ExtMul &wb, const ExtMul &wt, uint32_t di_m, uint32_t izt, const Fq &P, const Fq &ft,
+                                  const Fq &Nn, uint32_t mult, uint32_t sc[4][PERM_ROWS], uint32_t sx[4][PERM_ROWS], uint32_t acc[4][PERM_ROWS]) {
+    const uint32_t p = F.p;
+    const ExtMul MT = ext_mul_prepare(ft.c, g_m, F);
+    uint32_t lt[4], nf[4], ds[4], a[4], tq[4], bq[4], u[4], v[4];
+    ext_mul_prepared(P.c, MT, F, lt);                       // P f_T, Montgomery
+    ext_mul_prepared(Nn.c, MT, F, nf);                      // Nn f_T, plain
+    const ExtMul MP = ext_mul_prepare(lt, g_m, F);
+#pragma unroll
+    for (int e = 0; e < 4; e++) ds[e] = fp_sub(sx[e][Q], sc[e][Q], p);
+    ext_mul_prepared(ds, MP, F, a);                         // (s(w x) - s(x)) P f_T, plain
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const uint32_t t = fp_add(fp_sub(a[e], nf[e], p), mont_mul(mult, P.c[e], F), p);
+        tq[e] = mont_mul(t, izt, F);
+        bq[e] = mont_mul(sc[e][Q], di_m, F);
+    }
+    ext_mul_prepared(bq, wb, F, u);
+    ext_mul_prepared(tq, wt, F, v);
+#pragma unroll
+    for (int e = 0; e < 4; e++) acc[e][Q] = fp_add(acc[e][Q], fp_add(u[e], v[e], p), p);
+}
+// the two quotients of shared lookup a at the lane's four points: the fold, then the point function above.  di: 1 / (x_q -
+// tau), zt: what multiplies the transition's numerator (Montgomery both).  The overload for XNoShared is never reached.
+template <class Load4>
+SMI_HD void xshared_compose(const XArgsDev &XD, const XSharedDev &SH, uint32_t a, const Fp &F, const ExtMul &wb, const ExtMul &wt, const uint32_t di[PERM_ROWS],
+                            const uint32_t zt[PERM_ROWS], Load4 load4, uint32_t cc[4][PERM_ROWS], uint32_t cx[4][PERM_ROWS], uint32_t acc[4][PERM_ROWS]) {
+    Fq P[PERM_ROWS], Nn[PERM_ROWS], ft[PERM_ROWS];
+    uint32_t sa[PERM_ROWS], mult[PERM_ROWS];
+    xshared_fold<false>(XD, SH, a, F, 0, 0, load4, P, Nn, sa);
+    tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, ft);
+    xlookup_weights(XD, a, F, load4, sa, mult);   // sa: all ones, not read
+    xshared_compose_point<0>(XD.g_m, F, wb, wt, di[0], zt[0], P[0], ft[0], Nn[0], mult[0], cc, cx, acc);
+    xshared_compose_point<1>(XD.g_m, F, wb, wt, di[1], zt[1], P[1], ft[1], Nn[1], mult[1], cc, cx, acc);
+    xshared_compose_point<2>(XD.g_m, F, wb, wt, di[2], zt[2], P[2], ft[2], Nn[2], mult[2], cc, cx, acc);
+    xshared_compose_point<3>(XD.g_m, F, wb, wt, di[3], zt[3], P[3], ft[3], Nn[3], mult[3], cc, cx, acc);
+}
+template <class Load4>
+SMI_HD void xshared_compose(const XArgsDev &, const XNoShared &, uint32_t, const Fp &, const ExtMul &, const ExtMul &, const uint32_t *, const uint32_t *, Load4,
+                            uint32_t (*)[PERM_ROWS], uint32_t (*)[PERM_ROWS], uint32_t (*)[PERM_ROWS]) {}
+
 // One lane and trip of the streaming launch: args_compose_points with operands and selectors.  load4(op, v): operand op at
 // the four points -- an extended trace column, or the extended periodic table read modulo its length.  Everything else as
 // there: 1 / (x_i - tau) and the four entries of 1 / (x^n - tau^n) once per trip, the accumulator in registers across the
 // arguments.
-template <class Load4, class LoadC>
-SMI_HD void xargs_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t *w, uint32_t tau_m, const uint32_t *izt_m, uint32_t B, uint64_t i0,
+// SH: XSharedDev for a list with a shared lookup (its arguments with J >= 2 go through xshared_compose), XNoShared otherwise.
+template <class SHT, class Load4, class LoadC>
+SMI_HD void xargs_compose_points(const XArgsDev &XD, const SHT &SH, const Fp &F, const uint64_t *w, uint32_t tau_m, const uint32_t *izt_m, uint32_t B, uint64_t i0,
                                  uint32_t x0_m, uint32_t omega_m, Load4 load4, LoadC loadc, uint32_t acc[4][PERM_ROWS]) {
     static_assert(PERM_ROWS == 4, "the four points are written out");
     const uint32_t p = F.p;
@@ -277,6 +461,11 @@ SMI_HD void xargs_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t
 #pragma unroll
         for (int e = 0; e < 4; e++) wm[e] = to_mont_u64(w[8 * a + 4 + e], F);
         const ExtMul wt = ext_mul_prepare(wm, XD.g_m, F);
+        if (xshared_tuples(SH, a) >= 2) {
+            const uint32_t zt[PERM_ROWS] = {z0, z1, z2, z3};
+            xshared_compose(XD, SH, a, F, wb, wt, di, zt, load4, cc, cx, acc);
+            continue;
+        }
         Fq fl[PERM_ROWS], fr[PERM_ROWS];
         tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.aop[a], load4, fl);
         tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, fr);
@@ -309,6 +498,8 @@ SMI_HD void xargs_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t
 // The reject sentences of the verifier are the argument list's (ARGS_SENTENCES, args_core.h): the checks and their order
 // are the same.
 
+// J of an argument: bits 8 .. 15 of kind hold J - 1
+inline uint32_t xarg_tuples(const smi_air_xarg &g) { return ((g.kind >> SMI_ARG_TUPLES_SHIFT) & 0xffu) + 1; }
 // every argument by the section's rules; W = n_cols, Q = the AIR's periodic columns; the reason names the argument
 inline int xargs_validate(const smi_air_xargs *xargs, uint32_t W, uint32_t Q, std::string *why) {
     auto fail = [&](const std::string &s) {
@@ -326,28 +517,61 @@ inline int xargs_validate(const smi_air_xargs *xargs, uint32_t W, uint32_t Q, st
             if (v < 2 * W || v < 2 * W + 2 * Q) return std::string(what) + " is a next-row variable: only this-row operands (c < n_cols, or 2 n_cols + j)";
             return std::string(what) + " must be a variable of the AIR (< 2 n_cols + 2 n_periodic)";
         };
-        if (g.kind != SMI_ARG_PERM && g.kind != SMI_ARG_LOOKUP) return fail(who + "kind must be SMI_ARG_PERM (0) or SMI_ARG_LOOKUP (1)");
+        const uint32_t kind = g.kind & 0xffu, J = xarg_tuples(g);   // bits 8 .. 15: J - 1 ("Shared-table lookups")
+        if ((g.kind >> 16) || (kind != SMI_ARG_PERM && kind != SMI_ARG_LOOKUP)) return fail(who + "kind must be SMI_ARG_PERM (0) or SMI_ARG_LOOKUP (1)");
+        if (kind == SMI_ARG_PERM && J > 1) return fail(who + "a permutation takes no tuple count (bits 8 .. 15 of kind must be 0)");
+        if (J > SMI_ARG_MAX_TUPLES) return fail(who + "a shared lookup has at most SMI_ARG_MAX_TUPLES (" + std::to_string(SMI_ARG_MAX_TUPLES) + ") tuples");
         if (g.width < 1 || g.width > SMI_PERM_MAX_WIDTH) return fail(who + "width must be in 1 .. 8");
         if (!g.a_var || !g.b_var) return fail(who + "null operand list");
+        if (J > 1 && g.a_sel != SMI_ARG_NO_SELECTOR) return fail(who + "a shared lookup keeps its selectors behind the tuples in a_var: a_sel must be SMI_ARG_NO_SELECTOR");
+        for (uint32_t j = 0; j < J * g.width; j++) {
+            const std::string e = operand(g.a_var[j], "a_var");
+            if (!e.empty()) return fail(who + (J > 1 ? "tuple " + std::to_string(j / g.width) + ": " : "") + e);
+        }
         for (uint32_t j = 0; j < g.width; j++) {
-            std::string e = operand(g.a_var[j], "a_var");
-            if (e.empty()) e = operand(g.b_var[j], "b_var");
+            const std::string e = operand(g.b_var[j], "b_var");
             if (!e.empty()) return fail(who + e);
         }
+        for (uint32_t j = 0; J > 1 && j < J; j++)
+            if (g.a_var[J * g.width + j] != SMI_ARG_NO_SELECTOR) {
+                const std::string e = operand(g.a_var[J * g.width + j], "selector");
+                if (!e.empty()) return fail(who + "tuple " + std::to_string(j) + ": " + e);
+            }
         const uint32_t sel[2] = {g.a_sel, g.b_sel};
         for (int k = 0; k < 2; k++)
             if (sel[k] != SMI_ARG_NO_SELECTOR) {
                 const std::string e = operand(sel[k], k ? "b_sel" : "a_sel");
                 if (!e.empty()) return fail(who + e);
             }
-        if (g.kind == SMI_ARG_LOOKUP) {
+        if (kind == SMI_ARG_LOOKUP) {
             if (g.mult_col >= W) return fail(who + "mult_col must be < n_cols");
+            for (uint32_t j = 0; j < J * g.width; j++)
+                if (g.a_var[j] == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
             for (uint32_t j = 0; j < g.width; j++)
-                if (g.a_var[j] == g.mult_col || g.b_var[j] == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
+                if (g.b_var[j] == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
             if (g.a_sel == g.mult_col || g.b_sel == g.mult_col) return fail(who + "mult_col must be none of the selectors");
+            for (uint32_t j = 0; J > 1 && j < J; j++)
+                if (g.a_var[J * g.width + j] == g.mult_col) return fail(who + "mult_col must be none of the selectors");
         }
     }
     return SMI_OK;
+}
+// the bound of a shared lookup that needs the trace length: M counts (row, tuple) pairs, up to J n of them in one cell, and
+// must stay below p.  (J = 1: n divides p - 1.)
+inline int xargs_shared_rows(uint64_t p, const smi_air_xargs *xargs, uint32_t log_n, std::string *why) {
+    for (uint32_t a = 0; a < xargs->count; a++) {
+        const uint64_t J = xarg_tuples(xargs->arg[a]);
+        if (J > 1 && (J << log_n) >= p) {
+            if (why) *why = "xargs: argument " + std::to_string(a) + ": J n >= p: the multiplicities of a shared lookup could wrap";
+            return SMI_ERR_BAD_ARG;
+        }
+    }
+    return SMI_OK;
+}
+// the degree argument g contributes: 2 for a permutation without a selector, 3 with one, J + 2 for a lookup; one more under zk
+inline uint32_t xarg_degree(const smi_air_xarg &g, bool zk) {
+    const bool sel = g.a_sel != SMI_ARG_NO_SELECTOR || g.b_sel != SMI_ARG_NO_SELECTOR;
+    return ((g.kind & 0xffu) == SMI_ARG_LOOKUP ? xarg_tuples(g) + 2 : sel ? 3 : 2) + (zk ? 1 : 0);
 }
 
 // the periodic columns of air as the column build and the helper read them (no cfg at hand): counts, periods <= n, values
@@ -383,12 +607,9 @@ inline int xargs_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, 
         if (why) *why = "xargs: p = 3 (mod 4): the quartic extension does not exist";
         return SMI_ERR_BAD_ARG;
     }
-    for (uint32_t a = 0; a < xargs->count; a++) {
-        const smi_air_xarg &g = xargs->arg[a];
-        const bool sel = g.a_sel != SMI_ARG_NO_SELECTOR || g.b_sel != SMI_ARG_NO_SELECTOR;
-        const uint32_t da = (g.kind == SMI_ARG_LOOKUP || sel) ? 3 : 2;
-        if (d < da) d = da;
-    }
+    const int src = xargs_shared_rows(p, xargs, cfg->log_n, why);
+    if (src != SMI_OK) return src;
+    for (uint32_t a = 0; a < xargs->count; a++) d = std::max(d, xarg_degree(xargs->arg[a], false));
     const uint64_t B = 1ull << cfg->log_blowup;
     uint64_t D = 1;
     while (D < d - 1) D <<= 1;
@@ -419,9 +640,9 @@ inline void xargs_build(const Fp &F, uint32_t g, const smi_air_xargs *xargs, uin
     auto code = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v < W ? v : (XOP_PER | (v - 2 * W)); };
     for (uint32_t a = 0; a < xargs->count; a++) {
         const smi_air_xarg &s = xargs->arg[a];
-        XD->kind[a] = s.kind;
+        XD->kind[a] = s.kind & 0xffu;
         XD->m[a] = s.width;
-        XD->mcol[a] = s.kind == SMI_ARG_LOOKUP ? s.mult_col : 0;
+        XD->mcol[a] = XD->kind[a] == SMI_ARG_LOOKUP ? s.mult_col : 0;
         XD->asel[a] = code(s.a_sel);
         XD->bsel[a] = code(s.b_sel);
         for (uint32_t j = 0; j < s.width; j++) XD->aop[a][j] = code(s.a_var[j]), XD->bop[a][j] = code(s.b_var[j]);
@@ -436,6 +657,30 @@ inline void xargs_build(const Fp &F, uint32_t g, const smi_air_xargs *xargs, uin
             }
     }
     XD->pvals = nullptr;
+}
+// the tuples of a validated list as the shared instantiations read them; -> does the list have a shared lookup at all?
+inline bool xshared_build(const smi_air_xargs *xargs, uint32_t W, XSharedDev *SH) {
+    auto code = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v < W ? v : (XOP_PER | (v - 2 * W)); };
+    *SH = XSharedDev{};
+    bool any = false;
+    for (uint32_t a = 0; a < xargs->count; a++) {
+        const smi_air_xarg &s = xargs->arg[a];
+        const uint32_t J = xarg_tuples(s), m = s.width;
+        SH->J[a] = J;
+        for (uint32_t j = 0; j < J; j++) {
+            SH->sel[a][j] = J > 1 ? code(s.a_var[J * m + j]) : code(s.a_sel);
+            for (uint32_t i = 0; i < m; i++) SH->op[a][j][i] = code(s.a_var[j * m + i]);
+        }
+        any = any || J > 1;
+    }
+    return any;
+}
+// operands a shared list reads per row on top of what XArgsDev shows (the byte counts of the profile)
+inline double xshared_cols_read(const XArgsDev &XD, const XSharedDev &SH) {
+    double cols = 0;
+    for (uint32_t a = 0; a < XD.A; a++)
+        for (uint32_t j = 0; SH.J[a] > 1 && j < SH.J[a]; j++) cols += (j ? XD.m[a] : 0) + (SH.sel[a][j] != SMI_ARG_NO_SELECTOR);
+    return cols;
 }
 // the periodic plan of air on the trace itself (no extension): what the column build and the helper upload
 inline void xargs_periodic_plan(uint32_t p, const smi_air *air, uint32_t log_n, AirPeriodic *per) {
@@ -460,12 +705,9 @@ inline int deep_xargs_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *
     const int arc = xargs_validate(xargs, cfg->n_cols, air->n_periodic, why);
     if (arc != SMI_OK) return arc;
     if ((p & 3) != 1) return fail(SMI_ERR_BAD_ARG, "xargs: p = 3 (mod 4): the quartic extension does not exist");
-    for (uint32_t a = 0; a < xargs->count; a++) {
-        const smi_air_xarg &g = xargs->arg[a];
-        const bool sel = g.a_sel != SMI_ARG_NO_SELECTOR || g.b_sel != SMI_ARG_NO_SELECTOR;
-        const uint32_t da = (g.kind == SMI_ARG_LOOKUP || sel) ? 3 : 2;
-        if (d < da) d = da;
-    }
+    const int src = xargs_shared_rows(p, xargs, cfg->log_n, why);
+    if (src != SMI_OK) return src;
+    for (uint32_t a = 0; a < xargs->count; a++) d = std::max(d, xarg_degree(xargs->arg[a], false));
     const uint64_t B = 1ull << cfg->log_blowup;
     uint64_t D = 1;
     while (D < (uint64_t)d - 1 && D < (1ull << 32)) D <<= 1;
@@ -485,6 +727,30 @@ inline void xargs_aux_at_z(uint32_t p, uint32_t g, uint32_t W, const smi_air_xar
                            const FqH &ca, const FqH &cb, const FqH &ixt, const FqH &izt, FqH *bq, FqH *wq) {
     const FqH one = fqh(1 % p);
     auto val = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? one : v < W ? u[v] : per[v - 2 * W]; };
+    const uint32_t J = xarg_tuples(arg), m = arg.width;
+    if (J > 1) {   // (s' - s) P f_T - Nn f_T + M S_b P over the fold of the tuples
+        FqH P = one, Nn = fqh(0), ft = gamma, pw = one;
+        for (uint32_t i = 0; i < m; i++) {
+            ft = fqh_add(ft, fqh_mul(pw, val(arg.b_var[i]), p, g), p);
+            pw = fqh_mul(pw, alpha, p, g);
+        }
+        for (uint32_t j = 0; j < J; j++) {
+            FqH f = gamma;
+            pw = one;
+            for (uint32_t i = 0; i < m; i++) {
+                f = fqh_add(f, fqh_mul(pw, val(arg.a_var[j * m + i]), p, g), p);
+                pw = fqh_mul(pw, alpha, p, g);
+            }
+            Nn = fqh_add(fqh_mul(Nn, f, p, g), fqh_mul(val(arg.a_var[J * m + j]), P, p, g), p);
+            P = fqh_mul(P, f, p, g);
+        }
+        const FqH ms = fqh_mul(u[arg.mult_col], val(arg.b_sel), p, g);
+        FqH num = fqh_mul(fqh_sub(cb, ca, p), fqh_mul(P, ft, p, g), p, g);
+        num = fqh_add(fqh_sub(num, fqh_mul(Nn, ft, p, g), p), fqh_mul(ms, P, p, g), p);
+        *bq = fqh_mul(ca, ixt, p, g);
+        *wq = fqh_mul(num, izt, p, g);
+        return;
+    }
     FqH fl = gamma, fr = gamma, pw = one;
     for (uint32_t j = 0; j < arg.width; j++) {
         fl = fqh_add(fl, fqh_mul(pw, val(arg.a_var[j]), p, g), p);
@@ -492,7 +758,7 @@ inline void xargs_aux_at_z(uint32_t p, uint32_t g, uint32_t W, const smi_air_xar
         pw = fqh_mul(pw, alpha, p, g);
     }
     const FqH sa = val(arg.a_sel), sb = val(arg.b_sel);
-    if (arg.kind == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
+    if ((arg.kind & 0xffu) == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
         const FqH gl = fqh_add(one, fqh_mul(sa, fqh_sub(fl, one, p), p, g), p), gr = fqh_add(one, fqh_mul(sb, fqh_sub(fr, one, p), p, g), p);
         *bq = fqh_mul(fqh_sub(ca, one, p), ixt, p, g);
         *wq = fqh_mul(fqh_sub(fqh_mul(cb, gr, p, g), fqh_mul(ca, gl, p, g), p), izt, p, g);

@@ -32,13 +32,13 @@ __global__ __launch_bounds__(ZK_BLOCK) void zk_args_tail_kernel(ZkTailShape S, c
 }
 
 // out (four coordinate columns, the composition of the derived AIR) += the 3 A auxiliary quotients under w (12 A coordinates)
-template <bool VEC>
-__global__ __launch_bounds__(PERM_BLOCK) void air_zk_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
-                                                                           uint32_t tau_m, uint32_t tna_m, uint32_t ea_op, const uint32_t *__restrict__ izt_m,
-                                                                           const uint32_t *__restrict__ plog, const uint32_t *__restrict__ pofs,
-                                                                           const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde, size_t stride,
-                                                                           const uint32_t *__restrict__ cl, size_t c_stride, const uint64_t *__restrict__ w,
-                                                                           uint32_t *__restrict__ out, size_t out_stride) {
+// SHT: XNoShared (air_zk_xargs_compose_kernel) or XSharedDev (air_zk_xargs_compose_shared_kernel, a list with a shared lookup)
+template <bool VEC, class SHT>
+__device__ __forceinline__ void air_zk_xargs_compose_body(const XArgsDev &XD, const SHT &SH, const Fp &F, uint64_t N, uint32_t log_B, uint32_t h_m,
+                                                          uint32_t omega_m, uint32_t tau_m, uint32_t tna_m, uint32_t ea_op, const uint32_t *__restrict__ izt_m,
+                                                          const uint32_t *__restrict__ plog, const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
+                                                          const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl, size_t c_stride,
+                                                          const uint64_t *__restrict__ w, uint32_t *__restrict__ out, size_t out_stride) {
     const uint64_t groups = N / PERM_ROWS, gid = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x, gstep = (uint64_t)gridDim.x * PERM_BLOCK;
     const uint32_t B = 1u << log_B;
     uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * PERM_ROWS, F), F);
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_zk_xargs_compose_kernel(XArgsD
 #pragma unroll
         for (int e = 0; e < 4; e++) perm_load4<VEC>(out + e * out_stride, i0, N, acc[e]);
         zkx_compose_points(
-            XD, F, w, tau_m, tna_m, ea_op, izt_m, B, i0, x_m, omega_m,
+            XD, SH, F, w, tau_m, tna_m, ea_op, izt_m, B, i0, x_m, omega_m,
             [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
                 if (xop_periodic(op)) {
                     uint64_t L, at;
@@ -64,6 +64,26 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_zk_xargs_compose_kernel(XArgsD
         for (int e = 0; e < 4; e++) perm_store4<VEC>(out + e * out_stride, i0, N, acc[e]);
         x_m = mont_mul(x_m, xstep_m, F);
     }
+}
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void air_zk_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
+                                                                           uint32_t tau_m, uint32_t tna_m, uint32_t ea_op, const uint32_t *__restrict__ izt_m,
+                                                                           const uint32_t *__restrict__ plog, const uint32_t *__restrict__ pofs,
+                                                                           const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde, size_t stride,
+                                                                           const uint32_t *__restrict__ cl, size_t c_stride, const uint64_t *__restrict__ w,
+                                                                           uint32_t *__restrict__ out, size_t out_stride) {
+    air_zk_xargs_compose_body<VEC>(XD, XNoShared{}, F, N, log_B, h_m, omega_m, tau_m, tna_m, ea_op, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out,
+                                   out_stride);
+}
+template <bool VEC>
+__global__ __launch_bounds__(PERM_BLOCK) void air_zk_xargs_compose_shared_kernel(XArgsDev XD, XSharedDev SH, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m,
+                                                                                  uint32_t omega_m, uint32_t tau_m, uint32_t tna_m, uint32_t ea_op,
+                                                                                  const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
+                                                                                  const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
+                                                                                  const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl,
+                                                                                  size_t c_stride, const uint64_t *__restrict__ w, uint32_t *__restrict__ out,
+                                                                                  size_t out_stride) {
+    air_zk_xargs_compose_body<VEC>(XD, SH, F, N, log_B, h_m, omega_m, tau_m, tna_m, ea_op, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
 }
 
 // d_total: 4 A words, word 4 a + e = coordinate e of c_a[n_a]; d_rnd: 4 A (k_t - 1) words
@@ -80,7 +100,7 @@ int zk_args_tail_launch(smi_ctx *ctx, uint32_t *d_c, size_t c_stride, uint32_t l
 
 // H: the DERIVED AIR's tables, bound to the device blob and its periodic tables (its last table is E_A's); d_w: the 12 A
 // coordinates behind the main weights
-int zkx_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint32_t tau, uint32_t log_n, uint32_t kt, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+int zkx_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, uint32_t log_n, uint32_t kt, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
                        size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
     const AirDev &A = H.dev;
     const Fp F = ctx->fs.F;
@@ -95,11 +115,17 @@ int zkx_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const AirHost &H, uint3
     const uint64_t n = 1ull << log_n;
     const uint32_t tau_m = air_to_m(tau, F.p), tna_m = air_to_m(host_mulmod(tau % F.p, host_powmod(h_root(ctx, log_n), n - kt, F.p), F.p), F.p);
     const uint32_t ea_op = XOP_PER | (A.Q - 1);
-    double cols = 1;   // operands read per point, over the arguments, and E_A
+    double cols = 1 + (SH ? xshared_cols_read(XD, *SH) : 0);   // operands read per point, over the arguments, and E_A
     for (uint32_t a = 0; a < XD.A; a++)
         cols += 2 * XD.m[a] + (XD.kind[a] == SMI_ARG_LOOKUP ? 1 : 0) + (XD.asel[a] != SMI_ARG_NO_SELECTOR) + (XD.bsel[a] != SMI_ARG_NO_SELECTOR);
-    ProfScope ps(ctx, "air_zk_xargs_compose_kernel", (4.0 * cols + 32.0 * XD.A + 32.0) * (double)A.N);
-    if (vec)
+    ProfScope ps(ctx, SH ? "air_zk_xargs_compose_shared_kernel" : "air_zk_xargs_compose_kernel", (4.0 * cols + 32.0 * XD.A + 32.0) * (double)A.N);
+    if (SH && vec)
+        air_zk_xargs_compose_shared_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, tna_m, ea_op, A.izt_m, A.plog,
+                                                                                       A.pofs, A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+    else if (SH)
+        air_zk_xargs_compose_shared_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, tna_m, ea_op, A.izt_m,
+                                                                                        A.plog, A.pofs, A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
+    else if (vec)
         air_zk_xargs_compose_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, tna_m, ea_op, A.izt_m, A.plog, A.pofs,
                                                                                 A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
     else
@@ -156,8 +182,10 @@ int smi_dev_air_compose_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const v
     SMI_TRY(air_compose_ext_launch(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride));
     XArgsDev XD;
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, cfg->n_cols, &Z.air, H.per, challenges, &XD);
+    XSharedDev SHs;
+    const XSharedDev *SH = xshared_build(xargs, cfg->n_cols, &SHs) ? &SHs : nullptr;
     const uint32_t W = cfg->n_cols, K = Z.air.n_constraints;
-    SMI_TRY(zkx_compose_launch(ctx, XD, H, (uint32_t)cfg->trace_offset, cfg->log_n, kt, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride));
+    SMI_TRY(zkx_compose_launch(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, cfg->log_n, kt, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // Z and H are read by queued copies
     return SMI_OK;
 }

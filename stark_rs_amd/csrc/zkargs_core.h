@@ -64,8 +64,9 @@ SMI_HD void zkx_close_point(bool perm, const Fp &F, const ExtMul &wc, uint32_t d
 // The eight denominators x_q - tau and x_q - tau w^n_a of the lane's four points share one inversion, whatever A is.  E_A(x_q)
 // goes into 1 / (x_q^n - tau^n) once per trip, so wq_a is the xargs section's transition quotient computed by that section's
 // point functions, and bq_a comes with it; cq_a is one more product per point and argument.
-template <class Load4, class LoadC>
-SMI_HD void zkx_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t *w, uint32_t tau_m, uint32_t tna_m, uint32_t ea_op, const uint32_t *izt_m,
+// SH as in xargs_compose_points: a shared lookup goes through xshared_compose and takes its closing quotient like any lookup.
+template <class SHT, class Load4, class LoadC>
+SMI_HD void zkx_compose_points(const XArgsDev &XD, const SHT &SH, const Fp &F, const uint64_t *w, uint32_t tau_m, uint32_t tna_m, uint32_t ea_op, const uint32_t *izt_m,
                                uint32_t B, uint64_t i0, uint32_t x0_m, uint32_t omega_m, Load4 load4, LoadC loadc, uint32_t acc[4][PERM_ROWS]) {
     static_assert(PERM_ROWS == 4, "the four points are written out");
     const uint32_t p = F.p;
@@ -107,11 +108,13 @@ SMI_HD void zkx_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t *
 #pragma unroll
         for (int e = 0; e < 4; e++) wm[e] = to_mont_u64(w[12 * a + 8 + e], F);
         const ExtMul wc = ext_mul_prepare(wm, XD.g_m, F);
-        Fq fl[PERM_ROWS], fr[PERM_ROWS];
-        tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.aop[a], load4, fl);
-        tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, fr);
         const bool perm = XD.kind[a] == SMI_ARG_PERM;
-        if (perm) {
+        if (xshared_tuples(SH, a) >= 2) {
+            xshared_compose(XD, SH, a, F, wb, wt, di, zt, load4, cc, cx, acc);
+        } else if (perm) {
+            Fq fl[PERM_ROWS], fr[PERM_ROWS];
+            tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.aop[a], load4, fl);
+            tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, fr);
             uint32_t s[PERM_ROWS];
             if (XD.asel[a] != SMI_ARG_NO_SELECTOR) {
                 load4(XD.asel[a], s);
@@ -126,6 +129,9 @@ SMI_HD void zkx_compose_points(const XArgsDev &XD, const Fp &F, const uint64_t *
             args_perm_point<2>(XD.g_m, F, wb, wt, di[2], zt[2], fl[2], fr[2], cc, cx, acc);
             args_perm_point<3>(XD.g_m, F, wb, wt, di[3], zt[3], fl[3], fr[3], cc, cx, acc);
         } else {
+            Fq fl[PERM_ROWS], fr[PERM_ROWS];
+            tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.aop[a], load4, fl);
+            tuples_of(XD.apow_mm, XD.gamma_m, XD.m[a], F, XD.bop[a], load4, fr);
             uint32_t sa[PERM_ROWS], mult[PERM_ROWS];
             xlookup_weights(XD, a, F, load4, sa, mult);
             xlookup_compose_point<0>(XD.g_m, F, wb, wt, di[0], zt[0], fl[0], fr[0], sa[0], mult[0], cc, cx, acc);
@@ -179,12 +185,9 @@ inline int zkx_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, co
     uint32_t d = 0;
     rc = air_validate(p, cfg, &Z.air, &d, nullptr, why, false, true);
     if (rc != SMI_OK) return rc;
-    for (uint32_t a = 0; a < xargs->count; a++) {
-        const smi_air_xarg &g = xargs->arg[a];
-        const bool sel = g.a_sel != SMI_ARG_NO_SELECTOR || g.b_sel != SMI_ARG_NO_SELECTOR;
-        const uint32_t da = (g.kind == SMI_ARG_LOOKUP || sel) ? 4 : 3;
-        if (d < da) d = da;
-    }
+    rc = xargs_shared_rows(p, xargs, cfg->log_n, why);
+    if (rc != SMI_OK) return rc;
+    for (uint32_t a = 0; a < xargs->count; a++) d = std::max(d, xarg_degree(xargs->arg[a], true));
     const uint64_t B = 1ull << cfg->log_blowup;
     uint64_t D = 1;
     while (D < (uint64_t)d - 1 && D < (1ull << 32)) D <<= 1;
@@ -253,7 +256,7 @@ inline FqH zkx_ood_lhs(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, const s
         FqH bq, wq;
         xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), ca, cb, ixt, izt, &bq, &wq);
         wq = fqh_mul(wq, ea, p, g);
-        const FqH init = fqh(xargs->arg[a].kind == SMI_ARG_PERM ? 1 % p : 0);
+        const FqH init = fqh((xargs->arg[a].kind & 0xffu) == SMI_ARG_PERM ? 1 % p : 0);
         const FqH cq = fqh_mul(fqh_sub(ca, init, p), ict, p, g);
         const uint64_t *wa = weights + 4 * ((size_t)W + K + 3 * (size_t)a);
         acc = fqh_add(acc, fqh_mul(fqh_of(wa, p), bq, p, g), p);

@@ -807,7 +807,7 @@ class Engine:
                                  fill_multiplicities, folding, deep, coset_leaves=False):
         xa = self._check_deep_args(a, row_leaves, ext, folding, deep)
         A = xa.count
-        lookups = [i for i in range(A) if xa.arg[i].kind == 1]
+        lookups = [i for i in range(A) if xa.arg[i].kind & 0xff == 1]
         if fill_multiplicities and not lookups:
             raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
@@ -969,7 +969,7 @@ class Engine:
             raise ValueError("zk: the seed is 32 bytes (or True for os.urandom(32))")
         cfg = self._stark_cfg(n_cols, log_n, log_blowup, t, trace_offset, lde_offset, True)
         _d, Dp, kt, _ks = air_plan_deep_zk_args(self.p, a, xa, cfg)
-        lookups = [i for i in range(A) if xa.arg[i].kind == 1]
+        lookups = [i for i in range(A) if xa.arg[i].kind & 0xff == 1]
         if fill_multiplicities and not lookups:
             raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
         if fill_multiplicities:   # over the active rows, before the prover writes the randomiser rows
@@ -1085,7 +1085,7 @@ class Engine:
             if not (row_leaves and ext):
                 raise ValueError("dev_air_prove: an AIR with an argument list needs row_leaves=True, ext=True")
             A = a.xargs.count
-            lookups = [i for i in range(A) if a.xargs.arg[i].kind == 1]
+            lookups = [i for i in range(A) if a.xargs.arg[i].kind & 0xff == 1]
             if fill_multiplicities and not lookups:
                 raise ValueError("dev_air_prove(fill_multiplicities=True): the argument list has no lookup")
             if fill_multiplicities:

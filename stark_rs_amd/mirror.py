@@ -838,7 +838,8 @@ class Air:
         self.xargs_always = False   # flatten a list without selectors or periodic members to smi_air_xargs all the same (the
                                     # two paths give the same bytes; for comparisons)
         self.args = []          # [("perm", left, right) | ("lookup", columns, table columns, multiplicity column), ...]; with
-                                # selectors two more entries (a_sel, b_sel); a member is an int or ("per", j)
+                                # selectors two more entries (a_sel, b_sel); a member is an int or ("per", j).  A shared
+                                # lookup is ("lookups", [columns_0, ..], table columns, multiplicity column, [sel_0, ..], table_sel)
 
     @property
     def constraints(self):
@@ -933,9 +934,40 @@ class Air:
         s, ts = self._operand(sel, "sel", True), self._operand(table_sel, "table_sel", True)
         return self._add_arg(arg if s is None and ts is None else arg + (s, ts))
 
+    ARG_MAX_TUPLES = 4      # SMI_ARG_MAX_TUPLES
+
+    def add_lookups(self, tuples, table_cols, mult_col, sels=None, table_sel=None):
+        """appends ONE lookup argument whose J = len(tuples) looked-up tuples share the table, the multiplicity column and the
+        running sum (include/stark_mi.h, "Shared-table lookups"): on every row each tuples[j] whose selector sels[j] holds
+        occurs among the selected table tuples, and mult_col counts the (row, tuple) pairs that hit a table row.  1 .. 4 tuples
+        of one width; sels: None, or one member or None per tuple.  One tuple is add_lookup."""
+        a = len(self.args)
+        tuples = [[self._operand(c, "add_lookups") for c in t] for t in tuples]
+        table = [self._operand(c, "add_lookups") for c in table_cols]
+        sels = [None] * len(tuples) if sels is None else [self._operand(x, "sels", True) for x in sels]
+        if not 1 <= len(tuples) <= self.ARG_MAX_TUPLES:
+            raise ValueError(f"argument {a}: a shared lookup has 1 .. {self.ARG_MAX_TUPLES} tuples")
+        if len(sels) != len(tuples):
+            raise ValueError(f"argument {a}: one selector (or None) per tuple")
+        if any(len(t) != len(table) for t in tuples):
+            raise ValueError(f"argument {a}: a lookup relates tuples of one width")
+        if len(tuples) == 1:
+            return self.add_lookup(tuples[0], table, mult_col, sels[0], table_sel)
+        if not 1 <= len(table) <= 8:
+            raise ValueError(f"argument {a}: 1 .. 8 columns a side")
+        if self.perm is not None or self.lookup_arg is not None:
+            raise ValueError(f"argument {a}: an argument list does not mix with permutation() / lookup()")
+        if a >= self.ARGS_MAX:
+            raise ValueError(f"argument {a}: an argument list holds at most {self.ARGS_MAX} arguments")
+        self.args.append(("lookups", tuples, table, int(mult_col), sels, self._operand(table_sel, "table_sel", True)))
+        return self
+
     @staticmethod
     def arg_selectors(arg):
-        """(a_sel, b_sel) of an entry of Air.args; None: the constant 1"""
+        """(a_sel, b_sel) of an entry of Air.args; None: the constant 1.  A shared lookup keeps its selectors per tuple
+        (arg[4]): its a_sel is None"""
+        if arg[0] == "lookups":
+            return (None, arg[5])
         k = 3 if arg[0] == "perm" else 4
         return (arg[k], arg[k + 1]) if len(arg) > k else (None, None)
 
@@ -943,7 +975,7 @@ class Air:
     def extended_args(self):
         """does some argument of the list use a selector or a periodic member?  Then the list flattens to smi_air_xargs;
         otherwise to smi_air_args, and callers take the entry points of "Argument list" as before"""
-        return any(self.arg_selectors(g) != (None, None) or any(isinstance(c, tuple) for c in g[1] + g[2]) for g in self.args)
+        return any(g[0] == "lookups" or self.arg_selectors(g) != (None, None) or any(isinstance(c, tuple) for c in g[1] + g[2]) for g in self.args)
 
     def closes(self, p, g, cols, alpha, gamma):
         """z[n-1] * rho[n-1] == 1 for the trace cols under alpha, gamma (four canonical coordinates each); plain Python"""
@@ -1051,6 +1083,14 @@ class Air:
             var = lambda c: _lib.NO_SELECTOR if c is None else (2 * W + c[1]) % (1 << 32) if isinstance(c, tuple) else c % (1 << 32)
             keep, raw = [], (_lib.AirXArg * len(self.args))()
             for a, arg in enumerate(self.args):
+                if arg[0] == "lookups":   # J m operands, tuple-major, then the J selectors; J - 1 in the second byte of kind
+                    J = len(arg[1])
+                    la = np.array([var(c) for t in arg[1] for c in t] + [var(x) for x in arg[4]], dtype=np.uint32)
+                    ra = np.array([var(c) for c in arg[2]], dtype=np.uint32)
+                    keep += [la, ra]
+                    raw[a] = _lib.AirXArg(1 | (J - 1) << _lib.ARG_TUPLES_SHIFT, len(ra), arg[3] % (1 << 32), 0, ptr(la, _lib.u32p), ptr(ra, _lib.u32p),
+                                          _lib.NO_SELECTOR, var(arg[5]))
+                    continue
                 la, ra = np.array([var(c) for c in arg[1]], dtype=np.uint32), np.array([var(c) for c in arg[2]], dtype=np.uint32)
                 keep += [la, ra]
                 sa, sb = self.arg_selectors(arg)

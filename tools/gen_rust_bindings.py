@@ -194,6 +194,8 @@ def generate():
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     for m in re.finditer(r"#define (SMI_ARG_NO_SELECTOR) (0x[0-9a-f]+)u", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
+    for m in re.finditer(r"#define (SMI_ARG_MAX_TUPLES|SMI_ARG_TUPLES_SHIFT) +(\d+)", text):   # "Shared-table lookups": aligned with spaces
+        lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     lines.append("")
     lines.append('#[link(name = "starkmi")]')
     lines.append('extern "C" {')

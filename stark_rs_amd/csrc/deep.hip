@@ -388,7 +388,7 @@ struct DeepProver {
 int deep_shapes(DeepProver &s, uint32_t D, const char *no_layer) {
     smi_ctx *ctx = s.ctx;
     const smi_stark_cfg *cfg = s.cfg;
-    if (s.xargs) SMI_TRY(xargs_entry_checks(ctx, s.air, s.xargs, cfg->n_cols, cfg->log_n));
+    if (s.xargs) SMI_TRY(xargs_args(ctx, s.air, s.xargs, cfg->n_cols, cfg->log_n));
     s.W = cfg->n_cols, s.K = s.air->n_constraints, s.A = s.xargs ? s.xargs->count : 0, s.D = D, s.log_n = cfg->log_n, s.log_N = cfg->log_n + cfg->log_blowup;
     s.NW = s.W + s.K + 2 * s.A, s.CW = 4 * s.A;
     if (s.log_N > ctx->fs.K) return smi_fail(ctx, ctx->fs.F.p == 998244353u ? SMI_ERR_ROOT_TOO_LARGE : SMI_ERR_UNSUPPORTED_PRIME, "LDE domain too large");
@@ -426,7 +426,7 @@ int deep_setup(DeepProver &s) {
     s.d_weights = (uint64_t *)take(8 * 4 * (size_t)s.NW);
     s.d_blob = (uint32_t *)take(s.H.blob.size() * 4);
     for (uint32_t k = 0; k < s.G; k++) s.tree[k] = (uint8_t *)take(2 * s.leaves * 32);
-    if (A) s.d_atmp = (uint8_t *)take(xargs_columns_tmp_size(A, n));
+    if (A) s.d_atmp = (uint8_t *)take(xargs_columns_tmp_bytes(A, n));
     s.d_tab2 = (uint32_t *)take(deep_eval_tab_words(2) * 4), s.d_tab1 = (uint32_t *)take(deep_eval_tab_words(1) * 4);
     s.d_part = (uint32_t *)take(part_a > part_b ? part_a : part_b);
     s.d_res = (uint32_t *)take((size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | the segments' coordinates at z, e-major
@@ -467,9 +467,9 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     xargs_build(ctx->fs.F, s.g, s.xargs, s.W, s.air, s.H.per, ch.data(), &s.XD);
     s.XD.pvals = s.d_pvals;   // the raw periodic values the column build reads
     s.SH = xshared_build(s.xargs, s.W, &s.SHs) ? &s.SHs : nullptr;
-    SMI_TRY(xargs_columns_launch(ctx, s.XD, s.SH, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
+    SMI_TRY(xargs_columns_enqueue(ctx, s.XD, s.SH, s.d_trace, s.log_n, s.d_c, s.n, s.d_atmp));
     if (s.zk_kt) {
-        ArgsFlags *d_fl = const_cast<ArgsFlags *>(xargs_columns_flags_at(s.d_atmp, s.A, s.n));
+        ArgsFlags *d_fl = const_cast<ArgsFlags *>(xargs_columns_flags(s.d_atmp, s.A, s.n));
         SMI_TRY(smi_dev_random_fill(ctx, s.zk_seed, ZK_STREAM_ARGS_TAIL, s.d_tail, (size_t)s.CW * (s.zk_kt - 1)));
         SMI_TRY(zk_args_tail_launch(ctx, s.d_c, s.n, s.log_n, s.zk_kt, s.A, s.d_tail, &d_fl->total[0][0]));
         SMI_TRY(smi_dev_random_fill(ctx, s.zk_seed, ZK_STREAM_SALT_ARGS, s.d_cl + (size_t)s.CW * s.N, s.N));
@@ -479,10 +479,10 @@ int deep_list_columns(DeepProver &s, uint32_t *closes) {
     s.timer.mark();
     ArgsFlags fl;
     HIP_TRY(ctx, deep_root_read(s, 1));
-    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags_at(s.d_atmp, s.A, s.n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags(s.d_atmp, s.A, s.n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     SMI_TRY(dev_ntt(ctx, s.d_c, s.d_coef + (size_t)s.W * s.n, s.log_n, s.n, s.CW, s.n, s.n, 1, cfg->trace_offset, 1));   // the columns' coordinates as polynomials
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(xargs_columns_settle(ctx, s.XD, s.SH, fl, closes));
+    SMI_TRY(xargs_columns_verdict(ctx, s.XD, s.SH, fl, closes));
     transcript_indexed(s.tr, s.roots + 32, 8, 4 * (uint64_t)s.NW, &s.weights);   // root_2, then the indices 8 .. 8 + 4 NW - 1
     return SMI_OK;
 }
@@ -495,7 +495,7 @@ int deep_compose_h(DeepProver &s) {
     SMI_TRY(air_compose_ext_launch(ctx, s.H, s.d_blob, s.d_lde, N, s.d_weights, s.d_cw, N));
     const uint64_t *d_w = s.d_weights + 4 * (size_t)(s.W + s.K);
     if (s.zk_kt) return zkx_compose_launch(ctx, s.XD, s.SH, s.H, (uint32_t)s.cfg->trace_offset, s.log_n, s.zk_kt, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N);
-    if (s.A) SMI_TRY(xargs_compose_launch(ctx, s.XD, s.SH, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N));
+    if (s.A) SMI_TRY(xargs_compose_enqueue(ctx, s.XD, s.SH, s.H, (uint32_t)s.cfg->trace_offset, s.d_lde, N, s.d_cl, N, d_w, s.d_cw, N));
     return SMI_OK;
 }
 

@@ -3,7 +3,8 @@
 // emu_xargs_columns runs the three launches of smi_dev_xargs_columns over xargs_core.h's lane code for every lane, workgroup
 // and argument, with the kernels' own lane batching and block split; emu_air_compose_xargs runs emu_air_compose_ext and then
 // air_xargs_compose_kernel's grid-stride loop over xargs_compose_points; emu_xargs_multiplicities runs the helper's two
-// launches lane by lane.  Same arguments and statuses as the C ABI, with (p, g) in place of a context.
+// launches lane by lane.  emu_args_columns and emu_air_compose_args, the plain list's, are their own checks in front of the
+// same code, as in the library.  Same arguments and statuses as the C ABI, with (p, g) in place of a context.
 #include <string.h>
 
 #include <string>
@@ -24,7 +25,7 @@ using emu_host::periodic_tables;
 using emu_host::store4;
 
 namespace {
-// xargs_wg_scan of xargs.hip: v[tid] -> excl[tid] and the aggregate
+// args_wg_scan of args_dev.h: v[tid] -> excl[tid] and the aggregate
 Fq wg_scan(bool perm, const Fq *v, Fq *excl, uint32_t g_m, const Fp &F) {
     static thread_local uint32_t sc[2][4][PERM_BLOCK];
     for (uint32_t tid = 0; tid < PERM_BLOCK; tid++)
@@ -46,63 +47,14 @@ int checks(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xarg
     const int vrc = xargs_validate(xargs, n_cols, air->n_periodic, nullptr);
     return vrc != SMI_OK ? vrc : xargs_shared_rows(p, xargs, log_n, nullptr);
 }
-}  // namespace
-
-// order: the order in which the lanes of each launch run (0: ascending, 1: descending) -- the result must not depend on it.
-// *missing: the smallest selected row whose tuple is in no selected table row, or ~0
-extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, uint32_t a, const uint32_t *trace,
-                                        uint32_t n_cols, uint32_t log_n, uint32_t *mult, int order, uint64_t *missing) {
-    FieldSetup fs;
-    const int rc = checks(p, g, air, xargs, n_cols, log_n, &fs);
-    if (rc != SMI_OK) return rc;
-    if (a >= xargs->count || (xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
-    const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
-    AirPeriodic per;
-    xargs_periodic_plan((uint32_t)p, air, log_n, &per);
-    XArgsDev XD;
-    const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    xargs_build(fs.F, (uint32_t)g, xargs, n_cols, air, per, no_challenges, &XD);
-    XD.pvals = per.vals.data();
-    XSharedDev SH;
-    xshared_build(xargs, n_cols, &SH);
-    std::vector<uint32_t> tab(cap, LOOKUP_EMPTY);
-    memset(mult, 0, n * 4);
-    uint64_t first = ~0ull;
-    bool exhausted = false;
-    for (uint64_t k = 0; k < n; k++) {
-        const uint32_t t = (uint32_t)(order ? n - 1 - k : k);
-        if (!xlookup_insert_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, t, HostAtomics{})) exhausted = true;
-    }
-    for (uint64_t k = 0; k < n; k++) {
-        const uint32_t r = (uint32_t)(order ? n - 1 - k : k);
-        if (SH.J[a] > 1) {   // xargs_count_shared_kernel: *missing is 4 row + tuple
-            uint32_t miss = 0;
-            const int got = xshared_count_lane(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
-            if ((got & 1) && 4 * (uint64_t)r + miss < first) first = 4 * (uint64_t)r + miss;
-            if (got & 2) exhausted = true;
-            continue;
-        }
-        const int got = xlookup_count_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
-        if (got == 1 && r < first) first = r;
-        if (got == 2) exhausted = true;
-    }
-    if (missing) *missing = first;
-    if (exhausted) return SMI_ERR_BAD_ARG;
-    return first != ~0ull ? SMI_ERR_LOOKUP_MISSING : SMI_OK;
-}
-
-// c: 4 A coordinate columns c_stride apart.  *closes: the mask; *key: the smallest 16 row + 2 a + side with a zero
-// denominator, or ~0 -- for a list with a shared lookup 64 row + 8 a + side, side = j for f_j and J for f_T
-extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *trace, uint32_t n_cols,
-                                 uint32_t log_n, const uint64_t *challenges, uint32_t *c, uint64_t c_stride, uint32_t *closes, uint64_t *key) {
-    FieldSetup fs;
-    const int rc = checks(p, g, air, xargs, n_cols, log_n, &fs);
-    if (rc != SMI_OK) return rc;
+// the three launches of a column build behind the entry points' checks.  air: nullptr for a plain list
+int columns_run(const FieldSetup &fs, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *trace, uint32_t n_cols, uint32_t log_n,
+                const uint64_t *challenges, uint32_t *c, uint64_t c_stride, uint32_t *closes, uint64_t *key) {
     const Fp F = fs.F;
     const uint64_t n = 1ull << log_n, nb = (n + PERM_TILE - 1) / PERM_TILE;
     if (c_stride < n) return SMI_ERR_BAD_ARG;
     AirPeriodic per;
-    xargs_periodic_plan((uint32_t)p, air, log_n, &per);
+    if (air) xargs_periodic_plan(F.p, air, log_n, &per);
     XArgsDev XD;
     xargs_build(F, (uint32_t)g, xargs, n_cols, air, per, challenges, &XD);
     XD.pvals = per.vals.data();
@@ -179,18 +131,78 @@ extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, con
     if (closes) *closes = mask;
     return SMI_OK;
 }
+}  // namespace
 
-// grid: workgroups of the streaming launch (0: as the library sizes it for 256 compute units)
-extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *lde,
-                                     uint64_t stride, const uint32_t *cl, uint64_t c_stride, const uint64_t *challenges, const uint64_t *weights,
-                                     uint32_t *out, uint64_t out_stride, int force_direct, uint32_t grid) {
+// order: the order in which the lanes of each launch run (0: ascending, 1: descending) -- the result must not depend on it.
+// *missing: the smallest selected row whose tuple is in no selected table row, or ~0
+extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, uint32_t a, const uint32_t *trace,
+                                        uint32_t n_cols, uint32_t log_n, uint32_t *mult, int order, uint64_t *missing) {
+    FieldSetup fs;
+    const int rc = checks(p, g, air, xargs, n_cols, log_n, &fs);
+    if (rc != SMI_OK) return rc;
+    if (a >= xargs->count || (xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;
+    const uint64_t n = 1ull << log_n, cap = lookup_table_slots(n);
+    AirPeriodic per;
+    xargs_periodic_plan((uint32_t)p, air, log_n, &per);
+    XArgsDev XD;
+    const uint64_t no_challenges[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    xargs_build(fs.F, (uint32_t)g, xargs, n_cols, air, per, no_challenges, &XD);
+    XD.pvals = per.vals.data();
+    XSharedDev SH;
+    xshared_build(xargs, n_cols, &SH);
+    std::vector<uint32_t> tab(cap, LOOKUP_EMPTY);
+    memset(mult, 0, n * 4);
+    uint64_t first = ~0ull;
+    bool exhausted = false;
+    for (uint64_t k = 0; k < n; k++) {
+        const uint32_t t = (uint32_t)(order ? n - 1 - k : k);
+        if (!xlookup_insert_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, t, HostAtomics{})) exhausted = true;
+    }
+    for (uint64_t k = 0; k < n; k++) {
+        const uint32_t r = (uint32_t)(order ? n - 1 - k : k);
+        if (SH.J[a] > 1) {   // xargs_count_shared_kernel: *missing is 4 row + tuple
+            uint32_t miss = 0;
+            const int got = xshared_count_lane(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
+            if ((got & 1) && 4 * (uint64_t)r + miss < first) first = 4 * (uint64_t)r + miss;
+            if (got & 2) exhausted = true;
+            continue;
+        }
+        const int got = xlookup_count_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
+        if (got == 1 && r < first) first = r;
+        if (got == 2) exhausted = true;
+    }
+    if (missing) *missing = first;
+    if (exhausted) return SMI_ERR_BAD_ARG;
+    return first != ~0ull ? SMI_ERR_LOOKUP_MISSING : SMI_OK;
+}
+
+// c: 4 A coordinate columns c_stride apart.  *closes: the mask; *key: the smallest 16 row + 2 a + side with a zero
+// denominator, or ~0 -- for a list with a shared lookup 64 row + 8 a + side, side = j for f_j and J for f_T
+extern "C" int emu_xargs_columns(uint64_t p, uint64_t g, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *trace, uint32_t n_cols,
+                                 uint32_t log_n, const uint64_t *challenges, uint32_t *c, uint64_t c_stride, uint32_t *closes, uint64_t *key) {
+    FieldSetup fs;
+    const int rc = checks(p, g, air, xargs, n_cols, log_n, &fs);
+    if (rc != SMI_OK) return rc;
+    return columns_run(fs, g, air, xargs, trace, n_cols, log_n, challenges, c, c_stride, closes, key);
+}
+// the plain list (emu_args_columns of old): its own checks, then the same list in the operand form -- no AIR, no periodic column
+extern "C" int emu_args_columns(uint64_t p, uint64_t g, const smi_air_args *args, const uint32_t *trace, uint32_t n_cols, uint32_t log_n,
+                                const uint64_t *challenges, uint32_t *c, uint64_t c_stride, uint32_t *closes, uint64_t *key) {
     FieldSetup fs;
     if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
-    if (!ext_field_ok(p, g, nullptr)) return SMI_ERR_BAD_ARG;
-    std::string why;
-    // the launch itself has no bound on E: the DEEP provers run it at every blowup a composition of D segments fits
-    const int prc = xargs_plan(p, cfg, air, xargs, nullptr, nullptr, &why);
-    if (prc != SMI_OK && prc != SMI_ERR_EXPANSION_TOO_SMALL) return prc;
+    if (!ext_field_ok(p, g, nullptr) || p >= (1ull << 30)) return SMI_ERR_BAD_ARG;
+    if (!n_cols || n_cols > 64 || log_n < 1 || log_n > 27) return SMI_ERR_BAD_ARG;
+    const int rc = args_validate(args, n_cols, nullptr);
+    if (rc != SMI_OK) return rc;
+    const XArgsOfPlain x(args);
+    return columns_run(fs, g, nullptr, &x.list, trace, n_cols, log_n, challenges, c, c_stride, closes, key);
+}
+
+// the main composition and the streaming launch behind the entry points' checks.  pair: the AIR whose periodic columns the
+// operands may name (air itself), nullptr for a plain list
+static int compose_run(const FieldSetup &fs, uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air *pair,
+                       const smi_air_xargs *xargs, const uint32_t *lde, uint64_t stride, const uint32_t *cl, uint64_t c_stride, const uint64_t *challenges,
+                       const uint64_t *weights, uint32_t *out, uint64_t out_stride, int force_direct, uint32_t grid) {
     const int rc = emu_air_compose_ext(p, g, cfg, air, lde, stride, weights, out, out_stride, force_direct);
     if (rc != SMI_OK) return rc;
     const uint32_t log_N = cfg->log_n + cfg->log_blowup;
@@ -198,12 +210,12 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
     AirHost H;
     air_build(F, host_powmod(fs.wmax[0], 1ull << (fs.K - log_N), F.p), cfg, air, &H);
     std::vector<uint32_t> tab;
-    if (!periodic_tables(p, g, H.per, &tab)) return SMI_ERR_BAD_ARG;
+    if (pair && !periodic_tables(p, g, H.per, &tab)) return SMI_ERR_BAD_ARG;
     H.dev.ptab = tab.data();
     const AirDev &A = H.dev;
     if (c_stride < A.N) return SMI_ERR_BAD_ARG;
     XArgsDev XD;
-    xargs_build(F, (uint32_t)g, xargs, cfg->n_cols, air, H.per, challenges, &XD);
+    xargs_build(F, (uint32_t)g, xargs, cfg->n_cols, pair, pair ? H.per : AirPeriodic{}, challenges, &XD);
     XSharedDev SH;
     const bool shared = xshared_build(xargs, cfg->n_cols, &SH);
     const uint64_t *w = weights + 4 * (uint64_t)(A.W + A.K);
@@ -235,6 +247,33 @@ extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg
         }
     }
     return SMI_OK;
+}
+
+// grid: workgroups of the streaming launch (0: as the library sizes it for 256 compute units)
+extern "C" int emu_air_compose_xargs(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *lde,
+                                     uint64_t stride, const uint32_t *cl, uint64_t c_stride, const uint64_t *challenges, const uint64_t *weights,
+                                     uint32_t *out, uint64_t out_stride, int force_direct, uint32_t grid) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
+    if (!ext_field_ok(p, g, nullptr)) return SMI_ERR_BAD_ARG;
+    std::string why;
+    // the launch itself has no bound on E: the DEEP provers run it at every blowup a composition of D segments fits
+    const int prc = xargs_plan(p, cfg, air, xargs, nullptr, nullptr, &why);
+    if (prc != SMI_OK && prc != SMI_ERR_EXPANSION_TOO_SMALL) return prc;
+    return compose_run(fs, p, g, cfg, air, air, xargs, lde, stride, cl, c_stride, challenges, weights, out, out_stride, force_direct, grid);
+}
+// the plain list: its own plan, then the same list in the operand form
+extern "C" int emu_air_compose_args(uint64_t p, uint64_t g, const smi_stark_cfg *cfg, const smi_air *air, const smi_air_args *args, const uint32_t *lde,
+                                    uint64_t stride, const uint32_t *cl, uint64_t c_stride, const uint64_t *challenges, const uint64_t *weights,
+                                    uint32_t *out, uint64_t out_stride, int force_direct, uint32_t grid) {
+    FieldSetup fs;
+    if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
+    if (!ext_field_ok(p, g, nullptr)) return SMI_ERR_BAD_ARG;
+    std::string why;
+    const int prc = args_plan(p, cfg, air, args, nullptr, nullptr, &why);
+    if (prc != SMI_OK) return prc;
+    const XArgsOfPlain x(args);
+    return compose_run(fs, p, g, cfg, air, nullptr, &x.list, lde, stride, cl, c_stride, challenges, weights, out, out_stride, force_direct, grid);
 }
 
 // both sides of the verifier's extended out-of-domain consistency check (include/stark_mi.h, "Out-of-domain sampling with an

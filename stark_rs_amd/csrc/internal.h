@@ -5,6 +5,7 @@
 
 #include <stdlib.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -376,29 +377,64 @@ int air_compose_ext_launch(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uin
                            size_t out_stride);
 int launch_air_row_open(smi_ctx *ctx, const uint32_t *d_cols, size_t stride, uint32_t W, const uint8_t *d_nodes, uint32_t depth, const uint64_t *d_top,
                         uint32_t t, uint32_t R, uint64_t B, uint8_t *d_out);
-// args.hip, for xargs.hip: the scan and propagation launches of the column build (they read kind and g_m of AD only), and
-// the flags the build leaves on the device
-struct ArgsDev;
+// args.hip, for xargs.hip: the scan and propagation launches of a column build whose block launch has filled d_c and d_agg
+// (SD: args_dev.h), and the flags the build leaves on the device
+struct ArgsScanDev;
 struct ArgsFlags {   // the totals (plain), the smallest key 16 row + 2 a + side
     uint32_t total[8][4];
     unsigned long long first;
     unsigned long long pad;
 };
-int args_scan_propagate_enqueue(smi_ctx *ctx, const ArgsDev &AD, uint32_t A, uint64_t n, bool vec, uint32_t *d_c, size_t c_stride, uint32_t *d_agg,
-                                ArgsFlags *d_fl);
+int args_scan_propagate_enqueue(smi_ctx *ctx, const ArgsScanDev &SD, uint64_t n, bool vec, uint32_t *d_c, size_t c_stride, uint32_t *d_agg, ArgsFlags *d_fl);
 int air_periodic_tables(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint32_t *d_vals, uint32_t *d_tab);
-// xargs.hip, for deep.hip (the prover of "Out-of-domain sampling with an argument list"): the column build's three launches
-// over caller-owned temporary memory (xargs_columns_tmp_size bytes, 16-byte aligned; XD.pvals on the device), where the
-// build leaves its flags in that memory, the verdicts of a finished build, and the launch of the 2 A auxiliary quotients
+// xargs.hip, for args.hip (a plain list runs these with its own checks in front), deep.hip and zkargs.hip: the entry checks;
+// the column build's three launches over caller-owned temporary memory (xargs_columns_tmp_bytes bytes, 16-byte aligned;
+// XD.pvals on the device), where the build leaves its flags in that memory, the verdicts of a finished build -- a zero
+// denominator's sentence starts with `who` and calls a permutation's right side `perm_right` --, and the launch of the 2 A
+// auxiliary quotients (H bound to the device blob, its periodic tables in place; d_w: the 8 A coordinates behind the main
+// weights)
 struct XArgsDev;
 struct XSharedDev;   // the tuples of a list with a shared lookup; nullptr below: the list has none
-size_t xargs_columns_tmp_size(uint32_t A, uint64_t n);
-int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp);
-const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n);
-int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes);
-int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
-                         size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride);
-int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n);
+int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uint32_t n_cols, uint32_t log_n);
+size_t xargs_columns_tmp_bytes(uint32_t A, uint64_t n);
+int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride, uint8_t *d_tmp);
+const ArgsFlags *xargs_columns_flags(const uint8_t *d_tmp, uint32_t A, uint64_t n);
+int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes, const char *who = "xargs_columns",
+                          const char *perm_right = "g_R");
+int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
+                          size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride);
+// xargs.hip, for args.hip: what the entry points of both lists run behind their checks -- the column build with its wait and
+// verdicts, the main composition plus the auxiliary quotients, the prover.  air: the AIR whose periodic columns the operands
+// may name, nullptr for a plain list; nm: the entry points' own words in the sentences these can fail with
+struct ListNames {
+    const char *columns, *perm_right;   // a zero denominator: "args_columns", "f_R" / "xargs_columns", "g_R"
+    const char *prove;                  // out of memory: "air_prove_args" / "air_prove_xargs"
+};
+int xargs_columns_run(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, const ListNames &nm, const uint32_t *d_trace_cols, uint32_t n_cols,
+                      uint32_t log_n, const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes);
+int xargs_compose_run(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *d_lde, size_t stride,
+                      const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out, size_t out_stride);
+int xargs_prove_run(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint64_t E, const smi_air *air, const smi_air_xargs *xargs, const ListNames &nm,
+                    const uint32_t *d_trace_cols, uint8_t *roots_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                    uint32_t grind_bits, uint32_t *closes);
+// perm.hip, for lookup.hip, args.hip and xargs.hip: the prover of every proof with two row trees, one over the extended trace
+// and one over A auxiliary columns built under the challenges of the first root (4 A coordinate columns; the composition takes
+// 2 A weights more).  The entry point has run its checks and its plan (H, E); the variant says how its columns are built,
+// judged and composed.  DESIGN.md, "Where a new two-tree variant plugs in".
+struct TwoTreeVariant {
+    const char *name;               // the entry point, for the two out-of-memory sentences
+    uint32_t A;                     // auxiliary columns
+    size_t tmp_bytes;               // temporary device memory of the column build
+    size_t flags_bytes;             // the build leaves its flags in the last flags_bytes of it (at most sizeof(ArgsFlags))
+    // the tables under alpha, gamma = ch[0 .. 7] and the launches of the column build: d_c gets 4 A columns n apart.
+    // d_pvals: the AIR's raw periodic values on the device (nullptr without periodic columns)
+    std::function<int(const uint64_t *ch, const uint32_t *d_pvals, uint32_t *d_c, uint8_t *d_tmp)> columns;
+    std::function<int(const void *flags)> settle;   // the flags on the host -> the caller's closes, or the failure
+    // d_cw (the main composition, four columns N apart) += the 2 A auxiliary quotients under d_w; every stride is N
+    std::function<int(const AirHost &H, const uint32_t *d_lde, const uint32_t *d_cl, const uint64_t *d_w, uint32_t *d_cw)> compose;
+};
+int two_tree_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint64_t E, const uint32_t *d_trace_cols, const TwoTreeVariant &v, uint8_t *roots_out,
+                   uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
 // zkargs.hip, for deep.hip (the prover of "Zero-knowledge DEEP proofs with an argument list"): the tail step of the auxiliary
 // columns (d_total: 4 A words for the closing values, d_rnd: 4 A (k_t - 1) random words) and the launch of the 3 A auxiliary
 // quotients over the derived AIR's tables

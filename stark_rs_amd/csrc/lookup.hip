@@ -373,82 +373,20 @@ int smi_dev_air_prove_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void 
         const int rc = lookup_plan(ctx->fs.F.p, cfg, air, lk, nullptr, &E, &why);
         if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     }
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
-    const uint32_t NW = W + K + 2;
-    SMI_TRY(arena_reset(ctx));
-    StageTimer tm(ctx, 6, stage_ms != nullptr);
-    HIP_TRY(ctx, tm.create());
-
-    const size_t tree_bytes = 2 * N * 32;
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_s = (uint32_t *)arena_alloc(ctx, 4 * n * 4);
-    uint32_t *d_sl = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint8_t *d_ltmp = (uint8_t *)arena_alloc(ctx, lookup_column_tmp_bytes(n));
-    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
-    if (H.dev.Q) {
-        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    }
-    if (!d_lde || !d_s || !d_sl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_ltmp || (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_lookup: device memory");
-    tm.mark();
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    tm.mark();
-    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    tm.mark();
-    // first round trip: root_1 -> alpha, gamma
-    uint8_t roots[64];
-    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> ch, weights;   // 8 challenges; 4 NW weights
-    transcript_perm_challenges(tr, roots, &ch);
+    const size_t n = (size_t)1 << cfg->log_n, N = n << cfg->log_blowup;
     LookupDev LD;
-    lookup_build(ctx->fs.F, ctx->fs.g, lk, ch.data(), &LD);
-    SMI_TRY(lookup_column_enqueue(ctx, LD, d_trace_cols, log_n, d_s, n, d_ltmp));
-    SMI_TRY(smi_dev_lde(ctx, d_s, 4, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_sl));
-    SMI_TRY(launch_merkle_rows(ctx, d_sl, 4, N, N, tree2));
-    tm.mark();
-    // second round trip: root_2 (and the column's verdicts) -> the weights and FRI's seed
-    LookupFlags fl;
-    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&fl, lookup_column_flags(d_ltmp, log_n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(lookup_column_verdict(ctx, fl, closes));
-    transcript_perm_weights(tr, roots + 32, W, K, &weights);
-    const FsSeed seed = tr.seed();
-    if (roots_out) memcpy(roots_out, roots, 64);
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    SMI_TRY(lookup_compose_enqueue(ctx, LD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_sl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    tm.mark();
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
-    std::vector<uint8_t> &bytes = xres.proof;
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    tm.mark();
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
-        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(4, t, log_N, R);
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_lookup: row openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
-        SMI_TRY(launch_air_row_open(ctx, d_sl, N, 4, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
-        const size_t at = bytes.size();
-        bytes.resize(at + ob1 + ob2);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    tm.mark();
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    tm.write(stage_ms);
-    return smi_proof_out(ctx, bytes, proof, proof_len);
+    TwoTreeVariant v;
+    v.name = "air_prove_lookup";
+    v.A = 1;
+    v.tmp_bytes = lookup_column_tmp_bytes(n);
+    v.flags_bytes = sizeof(LookupFlags);
+    v.columns = [&](const uint64_t *ch, const uint32_t *, uint32_t *d_s, uint8_t *d_tmp) {
+        lookup_build(ctx->fs.F, ctx->fs.g, lk, ch, &LD);
+        return lookup_column_enqueue(ctx, LD, d_trace_cols, cfg->log_n, d_s, n, d_tmp);
+    };
+    v.settle = [&](const void *fl) { return lookup_column_verdict(ctx, *(const LookupFlags *)fl, closes); };
+    v.compose = [&](const AirHost &Hd, const uint32_t *d_lde, const uint32_t *d_sl, const uint64_t *d_w, uint32_t *d_cw) {
+        return lookup_compose_enqueue(ctx, LD, Hd, (uint32_t)cfg->trace_offset, d_lde, N, d_sl, N, d_w, d_cw, N);
+    };
+    return two_tree_prove(ctx, cfg, H, E, d_trace_cols, v, roots_out, proof, proof_len, top_indices, stage_ms, grind_bits);
 }

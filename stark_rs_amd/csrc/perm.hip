@@ -298,29 +298,53 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
         const int rc = perm_plan(ctx->fs.F.p, cfg, air, perm, nullptr, &E, &why);
         if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     }
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
+    const size_t n = (size_t)1 << cfg->log_n, N = n << cfg->log_blowup;
+    PermDev PD;
+    TwoTreeVariant v;
+    v.name = "air_prove_perm";
+    v.A = 1;
+    v.tmp_bytes = perm_column_tmp_bytes(n);
+    v.flags_bytes = sizeof(PermFlags);
+    v.columns = [&](const uint64_t *ch, const uint32_t *, uint32_t *d_z, uint8_t *d_tmp) {
+        perm_build(ctx->fs.F, ctx->fs.g, perm, ch, &PD);
+        return perm_column_enqueue(ctx, PD, d_trace_cols, cfg->log_n, d_z, n, d_tmp);
+    };
+    v.settle = [&](const void *fl) { return perm_column_verdict(ctx, *(const PermFlags *)fl, closes); };
+    v.compose = [&](const AirHost &Hd, const uint32_t *d_lde, const uint32_t *d_zl, const uint64_t *d_w, uint32_t *d_cw) {
+        return perm_compose_enqueue(ctx, PD, Hd, (uint32_t)cfg->trace_offset, d_lde, N, d_zl, N, d_w, d_cw, N);
+    };
+    return two_tree_prove(ctx, cfg, H, E, d_trace_cols, v, roots_out, proof, proof_len, top_indices, stage_ms, grind_bits);
+}
+
+// The prover of every proof with two row trees (internal.h TwoTreeVariant): smi_dev_air_prove_perm, _lookup, _args and _xargs
+// behind their checks and plans.  Two waits of the host before FRI, one per root; the order of the arena's allocations fixes
+// the alignment of every buffer, and the six stage marks are those of the header's stage_ms lists.
+int two_tree_prove(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint64_t E, const uint32_t *d_trace_cols, const TwoTreeVariant &v, uint8_t *roots_out,
+                   uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits) {
+    const uint32_t W = cfg->n_cols, K = H.dev.K, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup;
     const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
-    const uint32_t NW = W + K + 2;
+    const uint32_t NW = W + K + 2 * v.A, CW = 4 * v.A;   // weights; coordinate columns of the second tree
+    const std::string name = v.name;
     SMI_TRY(arena_reset(ctx));
     StageTimer tm(ctx, 6, stage_ms != nullptr);
     HIP_TRY(ctx, tm.create());
 
     const size_t tree_bytes = 2 * N * 32;
     uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_z = (uint32_t *)arena_alloc(ctx, 4 * n * 4);
-    uint32_t *d_zl = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
+    uint32_t *d_c = (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4);
+    uint32_t *d_cl = (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4);
     uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
     uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
     uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
     uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint8_t *d_ptmp = (uint8_t *)arena_alloc(ctx, perm_column_tmp_bytes(n));
+    uint8_t *d_tmp = (uint8_t *)arena_alloc(ctx, v.tmp_bytes);
     uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
     if (H.dev.Q) {
         d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
         d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
     }
-    if (!d_lde || !d_z || !d_zl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_ptmp || (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_perm: device memory");
+    if (!d_lde || !d_c || !d_cl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_tmp || (H.dev.Q && (!d_ptab || !d_pvals)))
+        return smi_fail(ctx, SMI_ERR_OOM, (name + ": device memory").c_str());
     tm.mark();
     SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
     tm.mark();
@@ -329,29 +353,27 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     // first round trip: root_1 -> alpha, gamma
     uint8_t roots[64];
     HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root; d_pvals: the raw values a list's column build may read
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     Transcript tr;
     std::vector<uint64_t> ch, weights;   // 8 challenges; 4 NW weights
     transcript_perm_challenges(tr, roots, &ch);
-    PermDev PD;
-    perm_build(ctx->fs.F, ctx->fs.g, perm, ch.data(), &PD);
-    SMI_TRY(perm_column_enqueue(ctx, PD, d_trace_cols, log_n, d_z, n, d_ptmp));
-    SMI_TRY(smi_dev_lde(ctx, d_z, 4, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_zl));
-    SMI_TRY(launch_merkle_rows(ctx, d_zl, 4, N, N, tree2));
+    SMI_TRY(v.columns(ch.data(), d_pvals, d_c, d_tmp));
+    SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
+    SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
     tm.mark();
-    // second round trip: root_2 (and the column's verdicts) -> the weights and FRI's seed
-    PermFlags fl;
+    // second round trip: root_2 (and the columns' verdicts) -> the weights and FRI's seed
+    alignas(8) uint8_t flags[sizeof(ArgsFlags)];
     HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&fl, perm_column_flags(d_ptmp, log_n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(flags, d_tmp + v.tmp_bytes - v.flags_bytes, v.flags_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(perm_column_verdict(ctx, fl, closes));
-    transcript_perm_weights(tr, roots + 32, W, K, &weights);
+    SMI_TRY(v.settle(flags));
+    transcript_args_weights(tr, roots + 32, W, K, v.A, &weights);   // with one column transcript_perm_weights' bytes
     const FsSeed seed = tr.seed();
     if (roots_out) memcpy(roots_out, roots, 64);
     HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
     SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    SMI_TRY(perm_compose_enqueue(ctx, PD, H, (uint32_t)cfg->trace_offset, d_lde, N, d_zl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
+    SMI_TRY(v.compose(H, d_lde, d_cl, d_weights + 4 * (size_t)(W + K), d_cw));
     tm.mark();
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
     FriExtResult xres;
@@ -361,13 +383,13 @@ int smi_dev_air_prove_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
     tm.mark();
     if (cfg->num_colinearity_tests) {
         const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
-        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(4, t, log_N, R);
+        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R);
         uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
         uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_perm: row openings");
+        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, (name + ": row openings").c_str());
         HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
         SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
-        SMI_TRY(launch_air_row_open(ctx, d_zl, N, 4, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
+        SMI_TRY(launch_air_row_open(ctx, d_cl, N, CW, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
         const size_t at = bytes.size();
         bytes.resize(at + ob1 + ob2);
         HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,22 +1,33 @@
 // xargs.hip -- the argument list with selectors and periodic members (include/stark_mi.h, "Argument list with selectors and
 // periodic members"): the multiplicity helper over operands, the A auxiliary columns, the 2 A auxiliary quotients and the
 // prover.  The lane bodies are xargs_core.h over args_core.h, shared with the CPU emulator (emu_xargs.cpp); the verifier is
-// in verify.hip.  The entry points of args.hip are untouched and keep their kernels.
+// in verify.hip.  The plain list of args.hip ("Argument list") runs these kernels too: it is a list without selectors or
+// periodic members, converted on the host (xargs_core.h XArgsOfPlain) behind its own checks.
 //
-// The column build is args.hip's trio of launches with a block launch of its own:
-//   xargs_block_kernel     grid (workgroups of rows, A), args_block_kernel with an operand loader: a trace operand is one
-//                          16-byte load, a periodic operand four values v_j[(row0 + q) mod P_j] of the raw periodic values
-//                          (one 16-byte load when P_j >= 4: row0 is a multiple of 4, so it cannot straddle the wrap; word by
-//                          word when P_j is 1 or 2); the selectors are applied around perm_lane_ratios, a lookup goes
-//                          through xlookup_lane_deltas.  One F_q inversion per lane, as there.
-//   args_scan_kernel, args_propagate_kernel   unchanged: they read kind[a] and nothing of the tuples.
-// air_xargs_compose_kernel has the shape of air_args_compose_kernel; a periodic operand is read at the lane's four points
-// from the extended tables the main composition of the same call has built (AirDev::ptab), modulo L_j = P_j B.
+// The column build is the multi-launch scan of perm.hip and lookup.hip with the argument as a grid dimension, so A arguments
+// cost three launches and the latency of one scan workgroup:
+//   xargs_block_kernel     grid (workgroups of rows, A).  A lane takes PERM_ROWS consecutive rows of argument blockIdx.y and
+//                          forms its two tuples through the operand loader: a trace operand is one 16-byte load, a periodic
+//                          operand four values v_j[(row0 + q) mod P_j] of the raw periodic values (one 16-byte load when
+//                          P_j >= 4: row0 is a multiple of 4, so it cannot straddle the wrap; word by word when P_j is 1 or
+//                          2).  The selectors are applied around perm_lane_ratios, a lookup goes through
+//                          xlookup_lane_deltas: one F_q inversion per lane.  The workgroup scans the lane aggregates in LDS:
+//                          a product of Montgomery elements for a permutation, a sum of plain elements for a lookup.  The
+//                          kind is uniform over the workgroup, so every barrier is met by all of its lanes.
+//   args_scan_kernel, args_propagate_kernel   (args.hip) they read kind[a] and nothing of the tuples.
+// No look-back, no grid barrier, no spin; every loop is bounded by its data's size.
+//
+// air_xargs_compose_kernel streams as air_perm_compose_kernel does: per lane four consecutive points and ONE 16-byte
+// read-modify-write per coordinate of the codeword whatever A is; the F_q accumulator stays in registers while the lane
+// loops over the arguments, and 1 / (x - tau), the x_i walk and the 1 / (x^n - tau^n) entries are computed once per trip.
+// A periodic operand is read at the lane's four points from the extended tables the main composition of the same call has
+// built (AirDev::ptab), modulo L_j = P_j B.
 // The helper is lookup.hip's two launches with rows that are not selected left out.
 #include <string>
 #include <vector>
 
 #include "air_core.h"
+#include "args_dev.h"
 #include "hash_core.h"
 #include "internal.h"
 #include "mgpu_core.h"
@@ -24,22 +35,6 @@
 #include "xargs_core.h"
 
 namespace {
-// args_wg_scan of args.hip: the workgroup scan of args_core.h between barriers
-__device__ __forceinline__ Fq xargs_wg_scan(bool perm, Fq v, uint32_t (*sc)[4][PERM_BLOCK], uint32_t tid, uint32_t g_m, const Fp &F, Fq *total) {
-    __syncthreads();   // the buffers of the scan before are consumed
-#pragma unroll
-    for (int e = 0; e < 4; e++) sc[0][e][tid] = v.c[e];
-    __syncthreads();
-    int cur = 0;
-    for (uint32_t off = 1; off < PERM_BLOCK; off <<= 1) {
-        args_scan_step(perm, sc[cur], sc[cur ^ 1], tid, off, g_m, F);
-        __syncthreads();
-        cur ^= 1;
-    }
-    *total = perm_scan_at(sc[cur], PERM_BLOCK - 1);
-    return tid ? perm_scan_at(sc[cur], tid - 1) : args_identity(perm, F);
-}
-
 struct XDevAtomics {   // DevAtomics of lookup.hip
     __device__ __forceinline__ uint32_t cas(uint32_t *a, uint32_t expect, uint32_t v) const { return atomicCAS(a, expect, v); }
     __device__ __forceinline__ void min(uint32_t *a, uint32_t v) const { atomicMin(a, v); }
@@ -120,7 +115,7 @@ __device__ __forceinline__ void xargs_block_body(const XArgsDev &XD, const SHT &
         pl, &agg, &key);
     if (key != ~0ull) atomicMin(first, (unsigned long long)key);
     Fq total;
-    const Fq excl = xargs_wg_scan(perm, agg, sc, tid, XD.g_m, F, &total);
+    const Fq excl = args_wg_scan(perm, agg, sc, tid, XD.g_m, F, &total);
     if (!tid) *(uint4 *)(block_agg + 4 * ((uint64_t)a * gridDim.x + blockIdx.x)) = make_uint4(total.c[0], total.c[1], total.c[2], total.c[3]);
     if (row0 >= n) return;
     uint32_t o[4][PERM_ROWS];
@@ -206,23 +201,18 @@ __global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_shared_kernel(XA
 namespace {
 static_assert(sizeof(XArgsDev) + 160 <= 4096, "the kernel arguments of every launch here stay inside 4 KB");
 
-size_t xargs_columns_tmp_bytes(uint32_t A, uint64_t n) { return (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16 + sizeof(ArgsFlags); }
-const ArgsFlags *xargs_columns_flags(const uint8_t *d_tmp, uint32_t A, uint64_t n) {
-    return (const ArgsFlags *)(d_tmp + (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16);
-}
 double xargs_cols_read(const XArgsDev &XD, const XSharedDev *SH) {   // operands read per row, over the arguments
     double cols = SH ? xshared_cols_read(XD, *SH) : 0;
     for (uint32_t a = 0; a < XD.A; a++)
         cols += 2 * XD.m[a] + (XD.kind[a] == SMI_ARG_LOOKUP ? 1 : 0) + (XD.asel[a] != SMI_ARG_NO_SELECTOR) + (XD.bsel[a] != SMI_ARG_NO_SELECTOR);
     return cols;
 }
-// what the scan and propagation launches read of a list
-ArgsDev xargs_scan_tables(const XArgsDev &XD) {
-    ArgsDev AD{};
-    AD.A = XD.A;
-    AD.g_m = XD.g_m;
-    for (uint32_t a = 0; a < XD.A; a++) AD.kind[a] = XD.kind[a], AD.m[a] = XD.m[a];
-    return AD;
+}  // namespace
+
+// bytes of device memory the column build wants: A runs of workgroup aggregates | the flags
+size_t xargs_columns_tmp_bytes(uint32_t A, uint64_t n) { return (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16 + sizeof(ArgsFlags); }
+const ArgsFlags *xargs_columns_flags(const uint8_t *d_tmp, uint32_t A, uint64_t n) {
+    return (const ArgsFlags *)(d_tmp + (size_t)A * ((n + PERM_TILE - 1) / PERM_TILE) * 16);
 }
 
 // the three launches; d_tmp: xargs_columns_tmp_bytes(A, n) bytes, 16-byte aligned; XD.pvals on the device
@@ -244,21 +234,25 @@ int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH
         else xargs_block_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
         HIP_TRY(ctx, hipGetLastError());
     }
-    return args_scan_propagate_enqueue(ctx, xargs_scan_tables(XD), XD.A, n, vec, d_c, c_stride, d_agg, d_fl);
+    ArgsScanDev SD{XD.A, XD.g_m, {}};
+    for (uint32_t a = 0; a < XD.A; a++) SD.kind[a] = XD.kind[a];
+    return args_scan_propagate_enqueue(ctx, SD, n, vec, d_c, c_stride, d_agg, d_fl);
 }
 
-// the verdicts of a finished column build (fl: the flags copied to the host)
-int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes) {
+// the verdicts of a finished column build (fl: the flags copied to the host).  who, perm_right: how the entry point's
+// zero-denominator sentence starts and what it calls a permutation's right side ("xargs_columns", "g_R"; a plain list
+// "args_columns", "f_R")
+int xargs_columns_verdict(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes, const char *who, const char *perm_right) {
     if (SH && fl.first != ~0ull) {   // the key of a list with a shared lookup: 64 row + 8 a + side, side = j for f_j and J for f_T
         const uint32_t a = (uint32_t)(fl.first >> 3) & 7, side = (uint32_t)fl.first & 7, J = SH->J[a];
-        const std::string what = XD.kind[a] == SMI_ARG_PERM ? "g_R" : side == J ? "f_T" : J > 1 ? "f_" + std::to_string(side) + " (tuple " + std::to_string(side) + ")" : "f_L";
-        const std::string why = "xargs_columns: argument " + std::to_string(a) + ": " + what + " is zero in row " + std::to_string(fl.first >> 6) + ": no inverse";
+        const std::string what = XD.kind[a] == SMI_ARG_PERM ? perm_right : side == J ? "f_T" : J > 1 ? "f_" + std::to_string(side) + " (tuple " + std::to_string(side) + ")" : "f_L";
+        const std::string why = std::string(who) + ": argument " + std::to_string(a) + ": " + what + " is zero in row " + std::to_string(fl.first >> 6) + ": no inverse";
         return smi_fail(ctx, SMI_ERR_NO_INVERSE, why.c_str());
     }
     if (fl.first != ~0ull) {
         const uint32_t a = (uint32_t)(fl.first & 15) >> 1;
-        const char *side = !(fl.first & 1) ? "f_L" : XD.kind[a] == SMI_ARG_PERM ? "g_R" : "f_T";
-        const std::string why = "xargs_columns: argument " + std::to_string(a) + ": " + side + " is zero in row " + std::to_string(fl.first >> 4) + ": no inverse";
+        const char *side = !(fl.first & 1) ? "f_L" : XD.kind[a] == SMI_ARG_PERM ? perm_right : "f_T";
+        const std::string why = std::string(who) + ": argument " + std::to_string(a) + ": " + side + " is zero in row " + std::to_string(fl.first >> 4) + ": no inverse";
         return smi_fail(ctx, SMI_ERR_NO_INVERSE, why.c_str());
     }
     uint32_t mask = 0;
@@ -315,7 +309,6 @@ int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uin
     if (xargs_shared_rows(ctx->fs.F.p, xargs, log_n, &why) != SMI_OK) return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
     return SMI_OK;
 }
-}  // namespace
 
 int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
                                  uint32_t log_n, uint32_t *d_mult) {
@@ -385,18 +378,15 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
     return SMI_OK;
 }
 
-int smi_dev_xargs_columns(smi_ctx *ctx, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n,
-                          const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes) {
-    const smi_air *air = (const smi_air *)air_;
-    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
-    if (!ctx || !air || !xargs || !d_trace_cols || !challenges || !d_c) return SMI_ERR_BAD_ARG;
-    DeviceGuard dg__(ctx);
-    if (closes) *closes = 0;
-    SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
+
+// ---- what the entry points of both lists run behind their checks (the plain list's are in args.hip).  air: the AIR whose
+// periodic columns the operands may name; nullptr for a plain list, which has no periodic operand: its tables are built
+// without a look at them, and the periodic values the kernels are handed stay unread.  nm: the entry points' own words.
+int xargs_columns_run(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, const ListNames &nm, const uint32_t *d_trace_cols, uint32_t n_cols,
+                      uint32_t log_n, const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes) {
     const uint64_t n = 1ull << log_n;
-    if (c_stride < n) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_columns: c_stride < n");
     AirPeriodic per;
-    xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
+    if (air) xargs_periodic_plan(ctx->fs.F.p, air, log_n, &per);
     XArgsDev XD;
     xargs_build(ctx->fs.F, ctx->fs.g, xargs, n_cols, air, per, challenges, &XD);
     XSharedDev SHs;
@@ -411,7 +401,64 @@ int smi_dev_xargs_columns(smi_ctx *ctx, const void *air_, const void *xargs_, co
     ArgsFlags fl;
     HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags((const uint8_t *)tmp, XD.A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return xargs_columns_verdict(ctx, XD, SH, fl, closes);
+    return xargs_columns_verdict(ctx, XD, SH, fl, closes, nm.columns, nm.perm_right);
+}
+
+// H: air_host_tables of the proof's AIR -- its periodic tables are built for the main composition whatever the list reads
+int xargs_compose_run(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, const smi_air *air, const smi_air_xargs *xargs, const uint32_t *d_lde, size_t stride,
+                      const uint32_t *d_c_lde, size_t c_stride, const uint64_t *challenges, const uint64_t *d_weights, uint32_t *d_out, size_t out_stride) {
+    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
+    void *base = nullptr;   // tables | grouped values | blob
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
+    SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
+    SMI_TRY(air_compose_ext_launch(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride));
+    XArgsDev XD;
+    xargs_build(ctx->fs.F, ctx->fs.g, xargs, cfg->n_cols, air, air ? H.per : AirPeriodic{}, challenges, &XD);
+    XSharedDev SHs;
+    const XSharedDev *SH = xshared_build(xargs, cfg->n_cols, &SHs) ? &SHs : nullptr;
+    return xargs_compose_enqueue(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(cfg->n_cols + H.dev.K), d_out,
+                                 out_stride);
+}
+
+// the list as a variant of the two-tree prover (internal.h): one auxiliary column per argument
+int xargs_prove_run(smi_ctx *ctx, const smi_stark_cfg *cfg, AirHost &H, uint64_t E, const smi_air *air, const smi_air_xargs *xargs, const ListNames &nm,
+                    const uint32_t *d_trace_cols, uint8_t *roots_out, uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms,
+                    uint32_t grind_bits, uint32_t *closes) {
+    const uint32_t W = cfg->n_cols, A = xargs->count;
+    const size_t n = (size_t)1 << cfg->log_n, N = n << cfg->log_blowup;
+    XArgsDev XD;
+    XSharedDev SHs;
+    const XSharedDev *SH = nullptr;
+    TwoTreeVariant v;
+    v.name = nm.prove;
+    v.A = A;
+    v.tmp_bytes = xargs_columns_tmp_bytes(A, n);
+    v.flags_bytes = sizeof(ArgsFlags);
+    v.columns = [&](const uint64_t *ch, const uint32_t *d_pvals, uint32_t *d_c, uint8_t *d_tmp) {
+        xargs_build(ctx->fs.F, ctx->fs.g, xargs, W, air, air ? H.per : AirPeriodic{}, ch, &XD);
+        XD.pvals = air ? d_pvals : nullptr;   // the raw values the column build reads
+        SH = xshared_build(xargs, W, &SHs) ? &SHs : nullptr;
+        return xargs_columns_enqueue(ctx, XD, SH, d_trace_cols, cfg->log_n, d_c, n, d_tmp);
+    };
+    v.settle = [&](const void *fl) { return xargs_columns_verdict(ctx, XD, SH, *(const ArgsFlags *)fl, closes, nm.columns, nm.perm_right); };
+    v.compose = [&](const AirHost &Hd, const uint32_t *d_lde, const uint32_t *d_cl, const uint64_t *d_w, uint32_t *d_cw) {
+        return xargs_compose_enqueue(ctx, XD, SH, Hd, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_w, d_cw, N);
+    };
+    return two_tree_prove(ctx, cfg, H, E, d_trace_cols, v, roots_out, proof, proof_len, top_indices, stage_ms, grind_bits);
+}
+
+static const ListNames XARGS_NAMES = {"xargs_columns", "g_R", "air_prove_xargs"};
+
+int smi_dev_xargs_columns(smi_ctx *ctx, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint32_t n_cols, uint32_t log_n,
+                          const uint64_t *challenges, uint32_t *d_c, size_t c_stride, uint32_t *closes) {
+    const smi_air *air = (const smi_air *)air_;
+    const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
+    if (!ctx || !air || !xargs || !d_trace_cols || !challenges || !d_c) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    if (closes) *closes = 0;
+    SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
+    if (c_stride < (1ull << log_n)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_columns: c_stride < n");
+    return xargs_columns_run(ctx, air, xargs, XARGS_NAMES, d_trace_cols, n_cols, log_n, challenges, d_c, c_stride, closes);
 }
 
 int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_lde, size_t stride,
@@ -426,17 +473,7 @@ int smi_dev_air_compose_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void
     SMI_TRY(xargs_args(ctx, air, xargs, cfg->n_cols, cfg->log_n));
     if (stride < H.dev.N || out_stride < H.dev.N || c_stride < H.dev.N)
         return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose_xargs: stride < N, c_stride < N or out_stride < N");
-    const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
-    void *base = nullptr;   // tables | grouped values | blob
-    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_vals + H.blob.size() * 4, &base));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, (uint32_t *)((uint8_t *)base + b_tab), (uint32_t *)base));
-    SMI_TRY(air_compose_ext_launch(ctx, H, (uint32_t *)((uint8_t *)base + b_tab + b_vals), d_lde, stride, d_weights, d_out, out_stride));
-    XArgsDev XD;
-    xargs_build(ctx->fs.F, ctx->fs.g, xargs, cfg->n_cols, air, H.per, challenges, &XD);
-    XSharedDev SHs;
-    const XSharedDev *SH = xshared_build(xargs, cfg->n_cols, &SHs) ? &SHs : nullptr;
-    const uint32_t W = cfg->n_cols, K = air->n_constraints;
-    return xargs_compose_enqueue(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, d_lde, stride, d_c_lde, c_stride, d_weights + 4 * (size_t)(W + K), d_out, out_stride);
+    return xargs_compose_run(ctx, cfg, H, air, xargs, d_lde, stride, d_c_lde, c_stride, challenges, d_weights, d_out, out_stride);
 }
 
 int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air_, const void *xargs_, const uint32_t *d_trace_cols, uint8_t *roots_out,
@@ -456,103 +493,5 @@ int smi_dev_air_prove_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
         const int rc = xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &E, &why);
         if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     }
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, log_n = cfg->log_n, log_N = cfg->log_n + cfg->log_blowup, A = xargs->count;
-    const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_N;
-    const uint32_t NW = W + K + 2 * A, CW = 4 * A;   // weights; coordinate columns of the second tree
-    SMI_TRY(arena_reset(ctx));
-    StageTimer tm(ctx, 6, stage_ms != nullptr);
-    HIP_TRY(ctx, tm.create());
-
-    const size_t tree_bytes = 2 * N * 32;
-    uint32_t *d_lde = (uint32_t *)arena_alloc(ctx, (size_t)W * N * 4);
-    uint32_t *d_c = (uint32_t *)arena_alloc(ctx, (size_t)CW * n * 4);
-    uint32_t *d_cl = (uint32_t *)arena_alloc(ctx, (size_t)CW * N * 4);
-    uint32_t *d_cw = (uint32_t *)arena_alloc(ctx, 4 * N * 4);
-    uint64_t *d_weights = (uint64_t *)arena_alloc(ctx, 8 * 4 * (size_t)NW);
-    uint32_t *d_blob = (uint32_t *)arena_alloc(ctx, H.blob.size() * 4);
-    uint8_t *tree1 = (uint8_t *)arena_alloc(ctx, tree_bytes), *tree2 = (uint8_t *)arena_alloc(ctx, tree_bytes);
-    uint8_t *d_atmp = (uint8_t *)arena_alloc(ctx, xargs_columns_tmp_bytes(A, n));
-    uint32_t *d_ptab = nullptr, *d_pvals = nullptr;
-    if (H.dev.Q) {
-        d_ptab = (uint32_t *)arena_alloc(ctx, H.per.table_words * 4);
-        d_pvals = (uint32_t *)arena_alloc(ctx, H.per.vals.size() * 4);
-    }
-    if (!d_lde || !d_c || !d_cl || !d_cw || !d_weights || !d_blob || !tree1 || !tree2 || !d_atmp || (H.dev.Q && (!d_ptab || !d_pvals)))
-        return smi_fail(ctx, SMI_ERR_OOM, "air_prove_xargs: device memory");
-    tm.mark();
-    SMI_TRY(smi_dev_lde(ctx, d_trace_cols, W, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_lde));
-    tm.mark();
-    SMI_TRY(launch_merkle_rows(ctx, d_lde, W, N, N, tree1));
-    tm.mark();
-    // first round trip: root_1 -> alpha, gamma
-    uint8_t roots[64];
-    HIP_TRY(ctx, hipMemcpyAsync(roots, tree1 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    SMI_TRY(air_periodic_tables(ctx, cfg, H, d_pvals, d_ptab));   // queued before the host waits for the root; d_pvals: the raw values the column build reads
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    Transcript tr;
-    std::vector<uint64_t> ch, weights;   // 8 challenges; 4 NW weights
-    transcript_perm_challenges(tr, roots, &ch);
-    XArgsDev XD;
-    xargs_build(ctx->fs.F, ctx->fs.g, xargs, W, air, H.per, ch.data(), &XD);
-    XD.pvals = d_pvals;
-    XSharedDev SHs;
-    const XSharedDev *SH = xshared_build(xargs, W, &SHs) ? &SHs : nullptr;
-    SMI_TRY(xargs_columns_enqueue(ctx, XD, SH, d_trace_cols, log_n, d_c, n, d_atmp));
-    SMI_TRY(smi_dev_lde(ctx, d_c, CW, log_n, cfg->log_blowup, cfg->trace_offset, cfg->lde_offset, d_cl));
-    SMI_TRY(launch_merkle_rows(ctx, d_cl, CW, N, N, tree2));
-    tm.mark();
-    // second round trip: root_2 (and the columns' verdicts) -> the weights and FRI's seed
-    ArgsFlags fl;
-    HIP_TRY(ctx, hipMemcpyAsync(roots + 32, tree2 + (2 * N - 2) * 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&fl, xargs_columns_flags(d_atmp, A, n), sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SMI_TRY(xargs_columns_verdict(ctx, XD, SH, fl, closes));
-    transcript_args_weights(tr, roots + 32, W, K, A, &weights);
-    const FsSeed seed = tr.seed();
-    if (roots_out) memcpy(roots_out, roots, 64);
-    HIP_TRY(ctx, hipMemcpyAsync(d_weights, weights.data(), 8 * weights.size(), hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(air_compose_ext_launch(ctx, H, d_blob, d_lde, N, d_weights, d_cw, N));
-    SMI_TRY(xargs_compose_enqueue(ctx, XD, SH, H, (uint32_t)cfg->trace_offset, d_lde, N, d_cl, N, d_weights + 4 * (size_t)(W + K), d_cw, N));
-    tm.mark();
-    const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, E);
-    FriExtResult xres;
-    SMI_TRY(fri_run_ext(ctx, &fc, &seed, d_cw, N, N, false, &xres, (int)grind_bits));
-    std::vector<uint8_t> &bytes = xres.proof;
-    if (top_indices) memcpy(top_indices, xres.top.data(), 8 * (size_t)cfg->num_colinearity_tests);
-    tm.mark();
-    if (cfg->num_colinearity_tests) {
-        const uint32_t t = (uint32_t)cfg->num_colinearity_tests, R = 4;
-        const size_t ob1 = (size_t)mg_row_open_bytes(W, t, log_N, R), ob2 = (size_t)mg_row_open_bytes(CW, t, log_N, R);
-        uint64_t *d_top = (uint64_t *)arena_alloc(ctx, 8 * (size_t)t);
-        uint8_t *d_open = (uint8_t *)arena_alloc(ctx, ob1 + ob2);
-        if (!d_top || !d_open) return smi_fail(ctx, SMI_ERR_OOM, "air_prove_xargs: row openings");
-        HIP_TRY(ctx, hipMemcpyAsync(d_top, xres.top.data(), 8 * (size_t)t, hipMemcpyHostToDevice, ctx->stream));
-        SMI_TRY(launch_air_row_open(ctx, d_lde, N, W, tree1, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open));
-        SMI_TRY(launch_air_row_open(ctx, d_cl, N, CW, tree2, log_N, d_top, t, R, 1ull << cfg->log_blowup, d_open + ob1));
-        const size_t at = bytes.size();
-        bytes.resize(at + ob1 + ob2);
-        HIP_TRY(ctx, hipMemcpyAsync(bytes.data() + at, d_open, ob1 + ob2, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    tm.mark();
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    tm.write(stage_ms);
-    return smi_proof_out(ctx, bytes, proof, proof_len);
-}
-
-// what deep.hip's prover shares with this file (internal.h)
-size_t xargs_columns_tmp_size(uint32_t A, uint64_t n) { return xargs_columns_tmp_bytes(A, n); }
-int xargs_columns_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const uint32_t *d_trace, uint32_t log_n, uint32_t *d_c, size_t c_stride,
-                         uint8_t *d_tmp) {
-    return xargs_columns_enqueue(ctx, XD, SH, d_trace, log_n, d_c, c_stride, d_tmp);
-}
-const ArgsFlags *xargs_columns_flags_at(const uint8_t *d_tmp, uint32_t A, uint64_t n) { return xargs_columns_flags(d_tmp, A, n); }
-int xargs_columns_settle(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const ArgsFlags &fl, uint32_t *closes) {
-    return xargs_columns_verdict(ctx, XD, SH, fl, closes);
-}
-int xargs_compose_launch(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH, const AirHost &H, uint32_t tau, const uint32_t *d_lde, size_t stride, const uint32_t *d_cl,
-                         size_t c_stride, const uint64_t *d_w, uint32_t *d_out, size_t out_stride) {
-    return xargs_compose_enqueue(ctx, XD, SH, H, tau, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
-}
-int xargs_entry_checks(smi_ctx *ctx, const smi_air *air, const void *xargs, uint32_t n_cols, uint32_t log_n) {
-    return xargs_args(ctx, air, (const smi_air_xargs *)xargs, n_cols, log_n);
+    return xargs_prove_run(ctx, cfg, H, E, air, xargs, XARGS_NAMES, d_trace_cols, roots_out, proof, proof_len, top_indices, stage_ms, grind_bits, closes);
 }

@@ -142,9 +142,11 @@ SMI_HD void xlookup_weights(const XArgsDev &XD, uint32_t a, const Fp &F, Load4 l
         for (int q = 0; q < PERM_ROWS; q++) mult[q] = mont_mul(to_mont(mult[q], F), sb[q], F);
     }
 }
-// One lane of the block launch for argument a: args_lane_column with operands and selectors.  load4(op, v): the four cells
-// of operand op at the lane's rows (anything for rows at or above n).  A permutation goes through perm_lane_ratios with
-// g_L and g_R in place of f_L and f_R; a lookup through xlookup_lane_deltas.  *key as in args_lane_column.
+// One lane of the block launch for argument a: perm_lane_column or lookup_lane_column behind tuples of operands, with the
+// selectors.  load4(op, v): the four cells of operand op at the lane's rows (anything for rows at or above n).  A
+// permutation goes through perm_lane_ratios with g_L and g_R in place of f_L and f_R; a lookup through xlookup_lane_deltas.
+// pl[q]: the lane's prefix before row q, *agg: the lane's product or sum.  *key: ~0, or for the smallest row of the lane
+// with a zero denominator 16 row + 2 a + side (side 0: f_L, side 1: g_R or f_T).
 template <class Load4>
 SMI_HD void xargs_lane_column(const XArgsDev &XD, uint32_t a, const Fp &F, uint64_t row0, uint64_t n, Load4 load4, Fq pl[PERM_ROWS], Fq *agg, uint64_t *key) {
     Fq fl[PERM_ROWS], fr[PERM_ROWS];
@@ -420,10 +422,13 @@ template <class Load4>
 SMI_HD void xshared_compose(const XArgsDev &, const XNoShared &, uint32_t, const Fp &, const ExtMul &, const ExtMul &, const uint32_t *, const uint32_t *, Load4,
                             uint32_t (*)[PERM_ROWS], uint32_t (*)[PERM_ROWS], uint32_t (*)[PERM_ROWS]) {}
 
-// One lane and trip of the streaming launch: args_compose_points with operands and selectors.  load4(op, v): operand op at
-// the four points -- an extended trace column, or the extended periodic table read modulo its length.  Everything else as
-// there: 1 / (x_i - tau) and the four entries of 1 / (x^n - tau^n) once per trip, the accumulator in registers across the
-// arguments.
+// One lane and trip of the streaming launch: PERM_ROWS consecutive points i0 .. i0 + PERM_ROWS - 1 and all A arguments.
+//   w: 8 A unreduced weight coordinates (argument a's boundary weight at 8 a, its transition weight at 8 a + 4), read with
+//   uniform addresses; load4(op, v): operand op at the four points -- an extended trace column, or the extended periodic
+//   table read modulo its length; loadc(col, next, v): coordinate column col < 4 A of the extended auxiliary columns at the
+//   four points, or one row further; acc[e][q]: the composition so far, kept in registers across the arguments.
+//   1 / (x_i - tau) (one Fermat power per lane) and the four entries of the 1 / (x^n - tau^n) table are fetched once, not
+//   once per argument.
 // SH: XSharedDev for a list with a shared lookup (its arguments with J >= 2 go through xshared_compose), XNoShared otherwise.
 template <class SHT, class Load4, class LoadC>
 SMI_HD void xargs_compose_points(const XArgsDev &XD, const SHT &SH, const Fp &F, const uint64_t *w, uint32_t tau_m, const uint32_t *izt_m, uint32_t B, uint64_t i0,
@@ -658,6 +663,20 @@ inline void xargs_build(const Fp &F, uint32_t g, const smi_air_xargs *xargs, uin
     }
     XD->pvals = nullptr;
 }
+// A validated plain list (smi_air_args) in the operand form: the same kind, width and mult_col, its columns as operands, no
+// selector.  The plain entry points build their tables from this with xargs_build over an empty AirPeriodic (air = nullptr: a
+// plain list has no periodic operand and the AIR's periodic columns are not looked at) and run the kernels below.
+struct XArgsOfPlain {
+    smi_air_xarg arg[SMI_ARGS_MAX];
+    smi_air_xargs list;
+    explicit XArgsOfPlain(const smi_air_args *args) : list{args->count, 0, arg} {
+        for (uint32_t a = 0; a < args->count; a++) {
+            const smi_air_arg &s = args->arg[a];
+            arg[a] = smi_air_xarg{s.kind, s.width, s.mult_col, 0, s.a_col, s.b_col, SMI_ARG_NO_SELECTOR, SMI_ARG_NO_SELECTOR};
+        }
+    }
+    XArgsOfPlain(const XArgsOfPlain &) = delete;   // list.arg points into this object
+};
 // the tuples of a validated list as the shared instantiations read them; -> does the list have a shared lookup at all?
 inline bool xshared_build(const smi_air_xargs *xargs, uint32_t W, XSharedDev *SH) {
     auto code = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v < W ? v : (XOP_PER | (v - 2 * W)); };

@@ -167,7 +167,7 @@ int smi_dev_air_compose_zk_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const v
     uint32_t kt = 0;
     int rc = zkx_plan(ctx->fs.F.p, cfg, air0, xargs, nullptr, nullptr, &kt, nullptr, &why);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
-    SMI_TRY(xargs_entry_checks(ctx, air0, xargs, cfg->n_cols, cfg->log_n));
+    SMI_TRY(xargs_args(ctx, air0, xargs, cfg->n_cols, cfg->log_n));
     ZkAir Z;
     rc = zk_derive_air(ctx->fs.F.p, h_root(ctx, cfg->log_n), cfg, air0, &Z, &why, true);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());

@@ -216,8 +216,8 @@ def test_dev_air_compose_args_equals_the_restatement(engines, oracle, p, g, name
 
 
 def test_compose_args_on_every_trip_of_the_grid_equals_the_restatement_at_sampled_points(engines):
-    """air_args_compose_kernel on four trips of its grid (tests/test_gpu_perm.py, looping_check) with the list [lookup 1, perm 2,
-    lookup 2], against agc.aux_terms_at"""
+    """air_xargs_compose_kernel, which a plain list runs, on four trips of its grid (tests/test_gpu_perm.py, looping_check) with
+    the list [lookup 1, perm 2, lookup 2], against agc.aux_terms_at"""
     from test_gpu_perm import looping_check
     p, g = xc.PRIMES[1]
     eng = engines[p]

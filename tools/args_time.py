@@ -4,11 +4,12 @@
     python3 tools/args_time.py [--out profiles/args_time.log]
 
 At n = 2^22, W = 6, B = 8 on the second prime, the list [permutation m = 2, lookup m = 2] over one trace: columns 2, 3 hold
-the rows of columns 0, 1 in another order, so that both statements hold with every multiplicity one.  HIP-event medians of
+the rows of columns 0, 1 in another order, so that both statements hold with every multiplicity one.  The plain list runs the
+operand list's kernels (xargs_block_kernel, air_xargs_compose_kernel), so those are the labels read.  HIP-event medians of
 REPS runs after three warm-up runs, with min and max; each new path and its yardstick alternate in one process.  The
 yardsticks are the existing kernels, never the code under test.
 columns: the three launches of smi_dev_args_columns against smi_dev_perm_column then smi_dev_lookup_column (six launches).
-compose: air_args_compose_kernel against air_perm_compose_kernel and air_lookup_compose_kernel back to back, and against a
+compose: the list's air_xargs_compose_kernel against air_perm_compose_kernel and air_lookup_compose_kernel back to back, and against a
          device-to-device copy of its own bytes: 9 trace columns, two auxiliary columns twice, the codeword read and written.
 prove  : smi_dev_air_prove_args against smi_dev_air_prove_perm plus smi_dev_air_prove_lookup on the same trace, grind_bits =
          16, t = 32: wall time and the six stages."""
@@ -120,7 +121,7 @@ pair_columns()
 eng.sync()
 assert torch.equal(c2[:4 * n], z1) and torch.equal(c2[4 * n:], s1)
 res = alternate({"args": (lambda: eng.dev_args_columns(both, tp, W, log_n, ch, c2.data_ptr()),
-                          ("args_block_kernel", "args_scan_kernel", "args_propagate_kernel")),
+                          ("xargs_block_kernel", "args_scan_kernel", "args_propagate_kernel")),
                  "pair": (pair_columns, ("perm_block_kernel", "perm_scan_kernel", "perm_propagate_kernel", "lookup_block_kernel", "lookup_scan_kernel",
                                          "lookup_propagate_kernel"))})
 show(f"columns n=2^{log_n} [perm m=2, lookup m=2]", res)
@@ -144,7 +145,7 @@ def pair_compose():
 
 
 res = alternate({"args": (lambda: eng.dev_air_compose_args(both, lde.data_ptr(), cl.data_ptr(), W, log_n, lb, ch, wts.data_ptr(), cw.data_ptr()),
-                          ("air_args_compose_kernel",)),
+                          ("air_xargs_compose_kernel",)),
                  "pair": (pair_compose, ("air_perm_compose_kernel", "air_lookup_compose_kernel"))})
 show(f"compose N=2^{log_n + lb}", res)
 nbytes = (4 * 9 + 32 * 2 + 32) * N

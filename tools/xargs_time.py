@@ -5,10 +5,13 @@
 
 At n = 2^22, W = 9, B = 8 on the second prime.  HIP-event kernel times through smi_ctx_profile: medians of REPS launches after
 three warm-up launches, with min and max; nothing is pinned; the paths that are compared alternate in one process.
-(a) the plain list [permutation m = 2, lookup m = 2] through the kernels of "Argument list" and the same list through the new
-    kernels (mirror.Air.xargs_always): the yardstick is the old kernel in the same session.  The outputs are compared first.
+(a) the plain list [permutation m = 2, lookup m = 2] through its own entry points and the same list handed over as an operand
+    list (mirror.Air.xargs_always): both run xargs_block_kernel and air_xargs_compose_kernel, and the outputs are compared
+    first.  The plain list once had kernels of its own; they went when it was routed here, and the comparison of the two
+    pairs of kernels, against the parent commit's library, is on record in profiles/two_tree_prover_ab.log
+    (tools/two_tree_ab.py).
 (b) the list [permutation m = 2 with a selector on either side, lookup m = 1 into a periodic table of 256 entries with a
-    selector] through the new kernels, the compose launch beside a device-to-device copy of the bytes it moves."""
+    selector] through the same kernels, the compose launch beside a device-to-device copy of the bytes it moves."""
 import argparse
 import os
 import statistics
@@ -86,13 +89,6 @@ def show(title, res):
             say(f"  {label:9s} {k:26s} {mmm(v)}")
 
 
-def verdict(what, new, old):
-    spread = max(old) - min(old)
-    d = statistics.median(new) - statistics.median(old)
-    say(f"{what}: new - old = {d:+.4f} ms; the old kernel's own min-max spread is {spread:.4f} ms -> "
-        + ("within the spread" if d <= spread else "SLOWER than the old kernel by more than its spread"))
-
-
 table = rng.permutation(256).astype(np.int64)
 tab = np.stack([rng.permutation(n).astype(np.int64), rng.integers(0, p, n, dtype=np.int64)])
 order = rng.permutation(n)
@@ -103,7 +99,7 @@ cols = np.stack([tab[0], tab[1], tab[0][order], tab[1][order], np.ones(n, dtype=
                  rng.integers(0, p, n, dtype=np.int64)])
 trace = torch.from_numpy(cols.astype(np.int32).reshape(-1)).to(dev)
 tp = trace.data_ptr()
-old = Air(W).add_permutation([2, 3], [0, 1]).add_lookup([2, 3], [0, 1], 4)
+plain = Air(W).add_permutation([2, 3], [0, 1]).add_lookup([2, 3], [0, 1], 4)
 new = Air(W).add_permutation([2, 3], [0, 1]).add_lookup([2, 3], [0, 1], 4)
 new.xargs_always = True
 sel = Air(W)
@@ -112,20 +108,19 @@ sel.add_permutation([2, 3], [0, 1], left_sel=5, right_sel=6).add_lookup([7], [("
 ch = [int(x) for x in rng.integers(1 << 62, (1 << 64) - 1, 8, dtype=np.uint64)]
 
 # ---- the columns
-c_old = torch.empty(8 * n, dtype=torch.int32, device=dev)
+c_plain = torch.empty(8 * n, dtype=torch.int32, device=dev)
 c_new = torch.empty(8 * n, dtype=torch.int32, device=dev)
 c_sel = torch.empty(8 * n, dtype=torch.int32, device=dev)
 torch.cuda.synchronize()
-assert eng.dev_args_columns(old, tp, W, log_n, ch, c_old.data_ptr()) == [True, True]
+assert eng.dev_args_columns(plain, tp, W, log_n, ch, c_plain.data_ptr()) == [True, True]
 assert eng.dev_args_columns(new, tp, W, log_n, ch, c_new.data_ptr()) == [True, True]
 eng.dev_args_columns(sel, tp, W, log_n, ch, c_sel.data_ptr())
 eng.sync()
-assert torch.equal(c_old, c_new)
-res = alternate({"old": (lambda: eng.dev_args_columns(old, tp, W, log_n, ch, c_old.data_ptr()), ("args_block_kernel",)),
-                 "new": (lambda: eng.dev_args_columns(new, tp, W, log_n, ch, c_new.data_ptr()), ("xargs_block_kernel",)),
+assert torch.equal(c_plain, c_new)
+res = alternate({"plain": (lambda: eng.dev_args_columns(plain, tp, W, log_n, ch, c_plain.data_ptr()), ("xargs_block_kernel",)),
+                 "operand": (lambda: eng.dev_args_columns(new, tp, W, log_n, ch, c_new.data_ptr()), ("xargs_block_kernel",)),
                  "selected": (lambda: eng.dev_args_columns(sel, tp, W, log_n, ch, c_sel.data_ptr()), ("xargs_block_kernel",))})
 show(f"(a), (b) column build, block launch, n=2^{log_n}", res)
-verdict("block launch, plain list", res["new"]["xargs_block_kernel"], res["old"]["args_block_kernel"])
 
 # ---- the auxiliary quotients
 lde = torch.empty(W * N, dtype=torch.int32, device=dev)
@@ -133,20 +128,19 @@ cl = torch.empty(8 * N, dtype=torch.int32, device=dev)
 cls = torch.empty(8 * N, dtype=torch.int32, device=dev)
 cw = [torch.empty(4 * N, dtype=torch.int32, device=dev) for _ in range(3)]
 eng.dev_lde(tp, W, log_n, lb, lde.data_ptr())
-eng.dev_lde(c_old.data_ptr(), 8, log_n, lb, cl.data_ptr())
+eng.dev_lde(c_plain.data_ptr(), 8, log_n, lb, cl.data_ptr())
 eng.dev_lde(c_sel.data_ptr(), 8, log_n, lb, cls.data_ptr())
 wts = torch.from_numpy(rng.integers(1 << 62, (1 << 64) - 1, 4 * (W + 4), dtype=np.uint64).view(np.int64)).to(dev)
 torch.cuda.synchronize()
 run = lambda air, c, out: eng.dev_air_compose_args(air, lde.data_ptr(), c.data_ptr(), W, log_n, lb, ch, wts.data_ptr(), out.data_ptr())
-run(old, cl, cw[0])
+run(plain, cl, cw[0])
 run(new, cl, cw[1])
 eng.sync()
 assert torch.equal(cw[0], cw[1])
-res = alternate({"old": (lambda: run(old, cl, cw[0]), ("air_args_compose_kernel",)),
-                 "new": (lambda: run(new, cl, cw[1]), ("air_xargs_compose_kernel",)),
+res = alternate({"plain": (lambda: run(plain, cl, cw[0]), ("air_xargs_compose_kernel",)),
+                 "operand": (lambda: run(new, cl, cw[1]), ("air_xargs_compose_kernel",)),
                  "selected": (lambda: run(sel, cls, cw[2]), ("air_xargs_compose_kernel",))})
 show(f"(a), (b) compose launch, N=2^{log_n + lb}", res)
-verdict("compose launch, plain list", res["new"]["air_xargs_compose_kernel"], res["old"]["air_args_compose_kernel"])
 # (b) reads per point: the permutation's 4 members and 2 selectors, the lookup's 1 trace member, its multiplicity and its
 # selector (the periodic table stays in cache): 9 column words; two auxiliary columns twice; the codeword read and written
 nbytes = (4 * 9 + 32 * 2 + 32) * N

@@ -116,7 +116,7 @@ pub struct smi_air {
     pub boundary_row: *const u64,
     pub boundary_value: *const u64,
     pub n_periodic: u32,
-    pub reserved0: u32,
+    pub window: u32,
     pub periodic_log_period: *const u32,
     pub periodic_value: *const u64,
 }
@@ -178,6 +178,7 @@ pub const SMI_AIR_MAX_TERM_FACTORS: u32 = 8;
 pub const SMI_AIR_MAX_EXP: u32 = 255;
 pub const SMI_AIR_MAX_BOUNDARY_PER_COL: u32 = 16;
 pub const SMI_AIR_MAX_PERIODIC: u32 = 16;
+pub const SMI_AIR_MAX_WINDOW: u32 = 4;
 pub const SMI_GRIND_MAX_BITS: u32 = 32;
 pub const SMI_PERM_MAX_WIDTH: u32 = 8;
 pub const SMI_LOOKUP_MAX_WIDTH: u32 = 8;
@@ -320,6 +321,8 @@ extern "C" {
     pub fn smi_air_deep_layout(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, proof_len: *mut usize) -> c_int;
     pub fn smi_dev_poly_eval_ext(ctx: *mut smi_ctx, d_coeffs: *const u32, n_cols: u32, n_coeffs: usize, stride: usize, points: *const u64, n_points: u32, out: *mut u64) -> c_int;
     pub fn smi_dev_deep_compose(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, n_segments: u32, d_lde: *const u32, stride: usize, d_seg: *const u32, seg_stride: usize, z: *const u64, ood: *const u64, challenges: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
+    pub fn smi_dev_poly_eval_ext_shifts(ctx: *mut smi_ctx, d_coeffs: *const u32, n_cols: u32, n_coeffs: usize, stride: usize, z: *const u64, w: u64, n_shifts: u32, out: *mut u64) -> c_int;
+    pub fn smi_dev_deep_compose_window(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, window: u32, n_segments: u32, d_lde: *const u32, stride: usize, d_seg: *const u32, seg_stride: usize, z: *const u64, ood: *const u64, challenges: *const u64, d_out: *mut u32, out_stride: usize) -> c_int;
     pub fn smi_dev_air_prove_deep(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, d_trace_cols: *const u32, roots: *mut u8, ood: *mut u64, proof: *mut *mut u8, proof_len: *mut usize, top_indices: *mut u64, stage_ms: *mut f64, grind_bits: u32) -> c_int;
     pub fn smi_air_verify_deep(ctx: *mut smi_ctx, cfg: *const smi_stark_cfg, air: *const c_void, roots: *const u8, proof: *const u8, proof_len: usize, accept: *mut c_int, grind_bits: u32) -> c_int;
     pub fn smi_air_plan_deep_xargs(p: u64, cfg: *const smi_stark_cfg, air: *const c_void, xargs: *const c_void, degree: *mut u32, segments: *mut u32) -> c_int;
@@ -839,7 +842,7 @@ impl Air {
             boundary_row: self.boundary_row.as_ptr(),
             boundary_value: self.boundary_value.as_ptr(),
             n_periodic: q,
-            reserved0: 0,
+            window: 0,   // two rows; a wider window is built on the raw struct ("AIR: transition windows")
             periodic_log_period: self.periodic_log_period.as_ptr(),
             periodic_value: self.periodic_value.as_ptr(),
         };

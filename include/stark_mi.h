@@ -431,9 +431,10 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
  *   SMI_ERR_NON_CANONICAL; E < 4 gives SMI_ERR_EXPANSION_TOO_SMALL (Fri::new's assert, src/fri.rs:45: the quotients
  *   would not fit under the degree bound).
  *
- * Out of scope: row shifts other than 0 and 1; zero-knowledge randomisers; degree-adjusted terms
- * (alpha + beta * x^shift); binding a digest of the AIR (coefficients, boundary values, periodic values) into the
- * transcript; keeping the periodic tables on the device between calls; a multi-GPU twin.  The proofs of the entry
+ * Out of scope: binding a digest of the AIR (coefficients, boundary values, periodic values) into the transcript; keeping
+ * the periodic tables on the device between calls; a multi-GPU twin.  (Row shifts above 1 are "AIR: transition windows"
+ * below; zero-knowledge randomisers and the lift to extension challenges have sections of their own; degree-adjusted
+ * terms are moot under out-of-domain sampling.)  The proofs of the entry
  * points of this section and the next draw every challenge from F_p: with a 30-bit modulus (the reference's choice) their
  * soundness is bounded by the field.  "Quartic extension" below has the field, the fold and the composition that lift the
  * challenges to 116 bits (smi_dev_air_prove_ext / smi_air_verify_ext), and lists what it leaves out.
@@ -446,6 +447,7 @@ int smi_stark_verify(smi_ctx *ctx, const smi_stark_cfg *cfg, const uint8_t *colu
 #define SMI_AIR_MAX_EXP 255
 #define SMI_AIR_MAX_BOUNDARY_PER_COL 16
 #define SMI_AIR_MAX_PERIODIC 16
+#define SMI_AIR_MAX_WINDOW 4
 typedef struct smi_air {
     uint32_t n_constraints, n_terms, n_factors, n_boundary;
     const uint32_t *constraint_first_term;  /* n_constraints + 1, ascending, [0] = 0, last = n_terms          */
@@ -457,7 +459,7 @@ typedef struct smi_air {
     const uint64_t *boundary_row;           /* n_boundary; < n, a (col, row) pair at most once                 */
     const uint64_t *boundary_value;         /* n_boundary; canonical                                           */
     uint32_t n_periodic;                    /* Q <= SMI_AIR_MAX_PERIODIC                                       */
-    uint32_t reserved0;                     /* explicit padding, ignored                                       */
+    uint32_t window;                        /* S: 0 or 2 = two rows; 3 .. SMI_AIR_MAX_WINDOW: "AIR: transition windows" */
     const uint32_t *periodic_log_period;    /* n_periodic; l_j <= log_n                                        */
     const uint64_t *periodic_value;         /* the columns' values back to back, 2^l_j each, canonical         */
 } smi_air;
@@ -1222,13 +1224,67 @@ int smi_dev_poly_eval_ext(smi_ctx *ctx, const uint32_t *d_coeffs, uint32_t n_col
  * otherwise.  The table of the gammas is copied to the device from pageable memory before the launch. */
 int smi_dev_deep_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_segments, const uint32_t *d_lde, size_t stride, const uint32_t *d_seg,
                          size_t seg_stride, const uint64_t z[4], const uint64_t *ood, const uint64_t *challenges, uint32_t *d_out, size_t out_stride);
-/* The prover above.  roots (optional): root_1 then root_2, 64 bytes; ood (optional): the record's 4 (2 W + D) values;
+/* smi_dev_poly_eval_ext at the n_shifts = 1 .. SMI_AIR_MAX_WINDOW points z, z w, .. z w^(n_shifts - 1) ("AIR: transition
+ * windows"): z four canonical coordinates, w a canonical base-field element, out[4 (c n_shifts + s) + e] = coordinate e of
+ * column c at z w^s.  One pass over the coefficients serves all shifts: the first launch holds a table of powers per point
+ * (16 n_shifts words a lane), four base-field multiplies per coefficient and shift; the second combines the partial sums;
+ * no atomics; the same 16-byte / 4-byte load rule.  For n_shifts <= 2 the values are those of smi_dev_poly_eval_ext at z, z w.
+ * smi_dev_poly_eval_ext itself keeps its limit of two arbitrary points. */
+int smi_dev_poly_eval_ext_shifts(smi_ctx *ctx, const uint32_t *d_coeffs, uint32_t n_cols, size_t n_coeffs, size_t stride, const uint64_t z[4], uint64_t w,
+                                 uint32_t n_shifts, uint64_t *out);
+/* smi_dev_deep_compose under a window of S = window rows, 2 .. SMI_AIR_MAX_WINDOW ("AIR: transition windows"):
+ *   Q(x_i) = sum_{s<S} sum_c gamma_{s,c} (f_c(x_i) - u_{s,c}) / (x_i - z w^s) + sum_j gamma''_j (H_j(x_i) - s_j) / (x_i - z).
+ * ood: the record's 4 (S W + D) canonical values, u_{s,c} s-major, then s_j; challenges: as many unreduced u64 in that
+ * order.  One streaming launch; the 4 S denominators of a lane share one F_q inversion; the access rule of
+ * smi_dev_deep_compose.  With window = 2 every output word is smi_dev_deep_compose's (the same kernel over the same table). */
+int smi_dev_deep_compose_window(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t window, uint32_t n_segments, const uint32_t *d_lde, size_t stride,
+                                const uint32_t *d_seg, size_t seg_stride, const uint64_t z[4], const uint64_t *ood, const uint64_t *challenges, uint32_t *d_out,
+                                size_t out_stride);
+/* The prover above.  roots (optional): root_1 then root_2, 64 bytes; ood (optional): the record's 4 (2 W + D) values --
+ * 4 (S W + D) for an AIR with a window of S rows ("AIR: transition windows"), which is what the buffer must hold;
  * stage_ms (optional) gets seven values {lde, commit, compose, segments, ood, fri, open} -- "ood" holds the evaluations,
  * their round trip and the DEEP codeword. */
 int smi_dev_air_prove_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint32_t *d_trace_cols, uint8_t *roots, uint64_t *ood,
                            uint8_t **proof, size_t *proof_len, uint64_t *top_indices, double *stage_ms, uint32_t grind_bits);
 int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air, const uint8_t *roots, const uint8_t *proof, size_t proof_len, int *accept,
                         uint32_t grind_bits);
+
+/* ---- AIR: transition windows of up to four rows -------------------------------------------------
+ * A transition constraint of "AIR" reads a column at this row and the next.  With smi_air.window = S in {3, 4} it reads the
+ * rows r .. r + S - 1, so a[r+2] = a[r+1] + a[r] is one column and no copy column is committed, hashed and opened.  window 0
+ * and 2 both mean the two-row statement above, byte for byte; 1 and anything above SMI_AIR_MAX_WINDOW are SMI_ERR_BAD_ARG
+ * with a sentence that names the window.
+ * Variables (W = n_cols, Q = n_periodic): var = s W + c is trace column c at row r + s, var = S W + s Q + j periodic column
+ *   j at row r + s, s < S; for S = 2 that is the numbering of "AIR".  factor_var < S (W + Q).
+ * Where constraints hold: on the windows that start at rows 0 .. n - S, no wrap; n >= S is required.
+ *   tq_k(x) = C_k(...) * prod_{s=1..S-1} (x - tau w^(n-s)) / (x^n - tau^n);   boundary quotients do not change.
+ *   On the evaluation coset the operand of shift s is lde[c][(i + s B) mod N], and pi_j(w^s x_i) = table_j[(i + s B) mod L_j].
+ * Degree and segments: the quotient's degree is at most d (n - 1) + (S - 1) - n.  d is reported as before; D starts from the
+ *   smallest power of two >= max(1, d - 1) and is doubled while D n <= d (n - 1) + (S - 1) - n.  For S = 2 it never doubles;
+ *   it doubles once for (d, S) in {(2, 3), (2, 4), (3, 4)} (1 -> 2, 1 -> 2, 2 -> 4) and for no other pair.  E = B / D and the
+ *   DEEP refusals (D > B, 4 D > 64) follow from that D.
+ * Who takes such an AIR: smi_air_plan, smi_dev_air_compose, smi_dev_air_compose_ext, smi_dev_air_check (windows r .. r + S - 1
+ *   for r <= n - S, periodic operands v_j[(r + s) mod P_j], the same first-violation order), smi_air_plan_deep, the two DEEP
+ *   layouts, smi_dev_air_prove_deep / smi_air_verify_deep and smi_dev_air_prove_deep_fold4 / smi_air_verify_deep_fold4.
+ *   Every other prover, verifier and plan -- column trees, rows, ext, pow, fold4 without DEEP; perm, lookup, args, xargs and
+ *   their DEEP forms; both zero-knowledge variants -- returns SMI_ERR_BAD_ARG with a sentence naming the window, before any
+ *   device work.
+ * DEEP proofs under a window.  A window row is one more out-of-domain point: the queried rows do not change.
+ *   Record: u_{s,c} = f_c(z w^s), s-major (s = 0 .. S - 1, then c < W), then s_j: 4 (S W + D) values, 32 (S W + D) payload
+ *     bytes; for S = 2 that is u then v.  Step 6 draws 4 (S W + D) challenges in record order, the counter continuing.
+ *   Q(x_i) = sum_{s<S} sum_c gamma_{s,c} (f_c(x_i) - u_{s,c}) / (x_i - z w^s) + sum_j gamma''_j (H_j(x_i) - s_j) / (x_i - z).
+ *   Proof and transcript lengths: those of the two DEEP sections with 2 W replaced by S W in the record and in the challenge
+ *     count, and nothing else: 9 + 32 (S W + D) + ..., transcript 32 (3 + W + K + 2 (S W + D)).  Openings, FRI, grinding,
+ *     roots, host round trips and the stage_ms order are unchanged.
+ *   Verifiers: the record's count 4 (S W + D); C_k over the S opened rows and pi_j(z w^s); the exemption product at z;
+ *     Q(x_a), Q(x_b) with S denominators; the order of checks and the sentences of their sections.  A proof checked under
+ *     another window is rejected at the record count when S W differs, and at the consistency check otherwise.
+ * Kernels: the tiled composition stages a halo of (S - 1) B points (the direct kernel takes over where no tile fits);
+ *   smi_dev_poly_eval_ext_shifts and smi_dev_deep_compose_window are declared with "Out-of-domain sampling" above.
+ * Measured (profiles/air_window_kernel_resources.log, profiles/air_window_time.log): DESIGN.md section 11.
+ * Left out: windows above four rows; opening only the (column, shift) pairs that a constraint reads; argument lists and
+ *   zero knowledge over wider windows (the zk row counts k_t depend on the number of opened functionals); the non-DEEP
+ *   provers; smi_mgpu_* twins; next-row tuple members in lists. */
 
 /* ---- Out-of-domain sampling with an argument list ----------------------------------------------
  * The argument-list provers recompute the composition at the queried positions, so a list with a lookup (degree 3) needs

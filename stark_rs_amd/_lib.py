@@ -51,7 +51,7 @@ class Air(C.Structure):
     _fields_ = [("n_constraints", C.c_uint32), ("n_terms", C.c_uint32), ("n_factors", C.c_uint32), ("n_boundary", C.c_uint32),
                 ("constraint_first_term", u32p), ("term_coeff", u64p), ("term_first_factor", u32p), ("factor_var", u32p),
                 ("factor_exp", u32p), ("boundary_col", u32p), ("boundary_row", u64p), ("boundary_value", u64p),
-                ("n_periodic", C.c_uint32), ("reserved0", C.c_uint32), ("periodic_log_period", u32p), ("periodic_value", u64p)]
+                ("n_periodic", C.c_uint32), ("window", C.c_uint32), ("periodic_log_period", u32p), ("periodic_value", u64p)]
 
 
 class AirPerm(C.Structure):
@@ -270,6 +270,8 @@ def lib():
         "smi_air_deep_layout": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(sz)]),
         "smi_dev_poly_eval_ext": (i32, [vp, vp, C.c_uint32, sz, sz, u64p, C.c_uint32, u64p]),
         "smi_dev_deep_compose": (i32, [vp, C.POINTER(StarkCfg), C.c_uint32, vp, sz, vp, sz, u64p, u64p, u64p, vp, sz]),
+        "smi_dev_poly_eval_ext_shifts": (i32, [vp, vp, C.c_uint32, sz, sz, u64p, C.c_uint64, C.c_uint32, u64p]),
+        "smi_dev_deep_compose_window": (i32, [vp, C.POINTER(StarkCfg), C.c_uint32, C.c_uint32, vp, sz, vp, sz, u64p, u64p, u64p, vp, sz]),
         "smi_dev_air_prove_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, vp, vp, C.POINTER(vp), C.POINTER(sz), vp, vp, C.c_uint32]),
         "smi_air_verify_deep": (i32, [vp, C.POINTER(StarkCfg), C.POINTER(Air), vp, C.c_char_p, sz, C.POINTER(i32), C.c_uint32]),
         "smi_air_plan_deep_xargs": (i32, [C.c_uint64, C.POINTER(StarkCfg), C.POINTER(Air), C.POINTER(AirXArgs), u32p, u32p]),

@@ -16,6 +16,11 @@
 // Periodic columns are Q more tile rows, staged from tables of L_j = P_j * B values that are read modulo their length
 // (air_core.h).  A table is at most a column and usually a few KB, so it comes from L2 and the floor above stands.
 // air_periodic_tables builds the tables on the stream with one batched smi_dev_lde per distinct period.
+//
+// Transition windows (include/stark_mi.h, "AIR: transition windows").  WIN = true instantiates the same kernels for an AIR
+// that reads S = 3 or 4 rows: the halo is (S - 1) B points, which air_tile counts against the 64 KB, and an operand's LDS
+// address is its row's plus s B.  The two-row instantiations (WIN = false) are the code they were; the launchers pick by
+// AirDev::S.  Where no tile fits under the wider halo the direct kernel takes over as before.
 #include <string>
 #include <vector>
 
@@ -31,13 +36,13 @@
 #include "zk_core.h"
 #include "zkargs_core.h"
 
-template <int P>
+template <int P, bool WIN = false>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
                                                                  const uint64_t *__restrict__ weights, uint32_t T,
                                                                  uint32_t *__restrict__ out) {
     extern __shared__ __align__(16) uint32_t air_lds[];
     uint32_t *w_m = air_lds, *tile = air_lds + AIR_MAX_WEIGHTS;
-    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (1u << A.log_B);
+    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (WIN ? (A.S - 1) << A.log_B : 1u << A.log_B);
     for (uint32_t i = tid; i < A.W + A.K; i += threads) w_m[i] = to_mont_u64(weights[i], F);
     const uint32_t step_m = mont_pow(A.omega_m, threads, F);
     const uint64_t tiles = A.N / T;
@@ -57,31 +62,32 @@ __global__ __launch_bounds__(AIR_BLOCK) void air_compose_kernel(AirDev A, Fp F, 
                 *(uint4 *)(tile + (A.W + j) * pitch + e) = *(const uint4 *)(tb + ((uint32_t)(base + e) & mask));
         }
         __syncthreads();   // tile (and, the first time, the weights) visible
-        air_tile_thread<P>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out);
+        air_tile_thread<P, WIN>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out);
         xbase_m = mont_mul(xbase_m, xstride_m, F);   // wave-uniform
     }
 }
 
+template <bool WIN = false>
 __global__ __launch_bounds__(AIR_BLOCK) void air_direct_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
                                                                 const uint64_t *__restrict__ weights, uint32_t *__restrict__ out) {
     __shared__ uint32_t w_m[AIR_MAX_WEIGHTS];
     for (uint32_t i = threadIdx.x; i < A.W + A.K; i += blockDim.x) w_m[i] = to_mont_u64(weights[i], F);
     __syncthreads();
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point(A, F, w_m, cols, stride, i, out);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point<WIN>(A, F, w_m, cols, stride, i, out);
 }
 
 // The composition under weights from the quartic extension: air_compose_kernel's tiling, halo and per-tile x, with
 // 4 (W + K) weights in LDS (coordinate e of weight j at w_m[e * AIR_MAX_WEIGHTS + j], from weights[4 j + e]) and four output
 // columns out_stride apart.  Every quotient is evaluated once per point and added into four accumulators
 // (air_core.h air_compose_points_ext); the floor is one read of the columns and four writes, 4 (W + 4) N bytes.
-template <int P>
+template <int P, bool WIN = false>
 __global__ __launch_bounds__(AIR_BLOCK) void air_compose_ext_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
                                                                      const uint64_t *__restrict__ weights, uint32_t T,
                                                                      uint32_t *__restrict__ out, size_t out_stride) {
     extern __shared__ __align__(16) uint32_t air_lds[];
     uint32_t *w_m = air_lds, *tile = air_lds + 4 * AIR_MAX_WEIGHTS;
-    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (1u << A.log_B);
+    const uint32_t threads = blockDim.x, tid = threadIdx.x, pitch = T + (WIN ? (A.S - 1) << A.log_B : 1u << A.log_B);
     for (uint32_t i = tid; i < 4 * (A.W + A.K); i += threads) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
     const uint32_t step_m = mont_pow(A.omega_m, threads, F);
     const uint64_t tiles = A.N / T;
@@ -100,22 +106,23 @@ __global__ __launch_bounds__(AIR_BLOCK) void air_compose_ext_kernel(AirDev A, Fp
                 *(uint4 *)(tile + (A.W + j) * pitch + e) = *(const uint4 *)(tb + ((uint32_t)(base + e) & mask));
         }
         __syncthreads();   // tile (and, the first time, the weights) visible
-        air_tile_thread_ext<P>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out, out_stride);
+        air_tile_thread_ext<P, WIN>(A, F, w_m, tile, T, threads, base, xbase_m, step_m, tid, out, out_stride);
         xbase_m = mont_mul(xbase_m, xstride_m, F);   // wave-uniform
     }
 }
 
+template <bool WIN = false>
 __global__ __launch_bounds__(AIR_BLOCK) void air_direct_ext_kernel(AirDev A, Fp F, const uint32_t *__restrict__ cols, size_t stride,
                                                                     const uint64_t *__restrict__ weights, uint32_t *__restrict__ out, size_t out_stride) {
     __shared__ uint32_t w_m[4 * AIR_MAX_WEIGHTS];
     for (uint32_t i = threadIdx.x; i < 4 * (A.W + A.K); i += blockDim.x) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], F);
     __syncthreads();
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point_ext(A, F, w_m, cols, stride, i, out, out_stride);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.N; i += step) air_direct_point_ext<WIN>(A, F, w_m, cols, stride, i, out, out_stride);
 }
 
-// the trace itself: thread i checks boundary point i (i < nb) and the row pair (i, i + 1) (i < n - 1); the first
-// violation in (kind, index, row) order wins an atomic minimum over the key kind << 63 | index << 32 | row
+// the trace itself: thread i checks boundary point i (i < nb) and the window of rows i .. i + S - 1 (i <= n - S; S = 2: the
+// row pair); the first violation in (kind, index, row) order wins an atomic minimum over the key kind << 63 | index << 32 | row
 __global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t nb,
                                                          const uint32_t *__restrict__ bnd, unsigned long long *first) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -123,10 +130,10 @@ __global__ __launch_bounds__(256) void air_check_kernel(AirDev A, Fp F, const ui
         const uint32_t col = bnd[3 * i], row = bnd[3 * i + 1], val = bnd[3 * i + 2];
         if (trace[col * n + row] != val) atomicMin(first, ((unsigned long long)i << 32) | row);
     }
-    if (i + 1 < n)
+    if (i + A.S <= n)
         for (uint32_t k = 0; k < A.K; k++) {
-            const uint32_t v = air_constraint(A, F, k, [&](uint32_t var) {   // log_B = 0: periodic operands v_j[i mod P_j], v_j[(i + 1) mod P_j]
-                return air_mem_operand(A, var, i, [&](uint32_t c) { return trace[c * n + i]; }, [&](uint32_t c) { return trace[c * n + i + 1]; });
+            const uint32_t v = air_constraint(A, F, k, [&](uint32_t var) {   // log_B = 0: periodic operands v_j[(i + s) mod P_j]
+                return air_mem_operand_win(A, var, i, [&](uint32_t c, uint32_t s) { return trace[c * n + i + s]; });
             });
             if (v) {
                 atomicMin(first, (1ull << 63) | ((unsigned long long)k << 32) | i);
@@ -159,7 +166,7 @@ __global__ __launch_bounds__(64) void air_row_open4_kernel(const uint32_t *__res
 __global__ __launch_bounds__(64) void air_periodic_gather_kernel(AirDev A, const uint64_t *__restrict__ idx, uint32_t count, uint32_t *__restrict__ out) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= count) return;
-    for (uint32_t v = 0; v < 2 * A.Q; v++) out[q * 2 * A.Q + v] = air_periodic_operand(A, v < A.Q ? v : v - A.Q, v >= A.Q, idx[q]);
+    for (uint32_t v = 0; v < 2 * A.Q; v++) out[q * 2 * A.Q + v] = air_periodic_operand(A, v < A.Q ? v : v - A.Q, v >= A.Q ? 1u : 0u, idx[q]);
 }
 
 // The periodic tables of H on the stream: the grouped values go to d_vals (H.per.vals.size() words), every group is one
@@ -203,9 +210,9 @@ namespace {
 thread_local std::string g_air_err;
 
 // validated tables of (cfg, air) on the host, bound to host memory
-int air_host(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E) {
+int air_host(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air *air, AirHost *H, uint64_t *E, uint32_t max_window = 2) {
     std::string why;
-    const int rc = air_validate(ctx->fs.F.p, cfg, air, nullptr, E, &why);
+    const int rc = air_validate(ctx->fs.F.p, cfg, air, nullptr, E, &why, false, false, max_window);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     const uint32_t log_N = cfg->log_n + cfg->log_blowup;
     if (log_N > ctx->fs.K)
@@ -223,19 +230,25 @@ int air_launch_compose(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uint32_
     const AirDev &A = H.dev;
     const Fp F = ctx->fs.F;
     const uint64_t B = 1ull << A.log_B;
-    AirTile tl = air_tile(A.W + A.Q, B, A.N);
+    const bool win = A.S > 2;
+    AirTile tl = air_tile(A.W + A.Q, B, A.N, 1, A.S);
     if (B < 4 || (stride & 3) || (((uintptr_t)d_lde) & 15u)) tl.T = 0;   // 16-byte loads need aligned columns
     ProfScope ps(ctx, "air_compose_kernel", 4.0 * (A.W + 1.0) * (double)A.N);
     if (!tl.T) {
         size_t grid = (size_t)((A.N + AIR_BLOCK - 1) / AIR_BLOCK);
         if (grid > 4096) grid = 4096;
-        air_direct_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out);
+        if (win) air_direct_kernel<true><<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out);
+        else air_direct_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out);
     } else {
         const uint64_t tiles = A.N / tl.T;
-        const size_t lds = (size_t)AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + B) * 4;
+        const size_t lds = (size_t)AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + (A.S - 1) * B) * 4;
         const uint64_t cap = (uint64_t)ctx->num_cus * 8;
         const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
-        if (tl.P == 4) air_compose_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+        if (win) {
+            if (tl.P == 4) air_compose_kernel<4, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+            else if (tl.P == 2) air_compose_kernel<2, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+            else air_compose_kernel<1, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
+        } else if (tl.P == 4) air_compose_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
         else if (tl.P == 2) air_compose_kernel<2><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
         else air_compose_kernel<1><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out);
     }
@@ -251,19 +264,25 @@ int air_launch_compose_ext(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uin
     const AirDev &A = H.dev;
     const Fp F = ctx->fs.F;
     const uint64_t B = 1ull << A.log_B;
-    AirTile tl = air_tile(A.W + A.Q, B, A.N, 4);
+    const bool win = A.S > 2;
+    AirTile tl = air_tile(A.W + A.Q, B, A.N, 4, A.S);
     if (B < 4 || (stride & 3) || (((uintptr_t)d_lde) & 15u)) tl.T = 0;   // 16-byte loads need aligned columns
     ProfScope ps(ctx, "air_compose_ext_kernel", 4.0 * (A.W + 4.0) * (double)A.N);
     if (!tl.T) {
         size_t grid = (size_t)((A.N + AIR_BLOCK - 1) / AIR_BLOCK);
         if (grid > 4096) grid = 4096;
-        air_direct_ext_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out, out_stride);
+        if (win) air_direct_ext_kernel<true><<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out, out_stride);
+        else air_direct_ext_kernel<<<(uint32_t)grid, AIR_BLOCK, 0, ctx->stream>>>(A, F, d_lde, stride, d_weights, d_out, out_stride);
     } else {
         const uint64_t tiles = A.N / tl.T;
-        const size_t lds = (size_t)4 * AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + B) * 4;
+        const size_t lds = (size_t)4 * AIR_MAX_WEIGHTS * 4 + (size_t)(A.W + A.Q) * (tl.T + (A.S - 1) * B) * 4;
         const uint64_t cap = (uint64_t)ctx->num_cus * 8;
         const uint32_t grid = (uint32_t)(tiles < cap ? tiles : cap);
-        if (tl.P == 4) air_compose_ext_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+        if (win) {
+            if (tl.P == 4) air_compose_ext_kernel<4, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+            else if (tl.P == 2) air_compose_ext_kernel<2, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+            else air_compose_ext_kernel<1, true><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
+        } else if (tl.P == 4) air_compose_ext_kernel<4><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
         else if (tl.P == 2) air_compose_ext_kernel<2><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
         else air_compose_ext_kernel<1><<<grid, tl.threads, lds, ctx->stream>>>(A, F, d_lde, stride, d_weights, tl.T, d_out, out_stride);
     }
@@ -274,7 +293,7 @@ int air_launch_compose_ext(smi_ctx *ctx, AirHost &H, uint32_t *d_blob, const uin
 
 int smi_air_plan(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint64_t *fri_expansion) {
     g_air_err.clear();
-    return air_validate(p, cfg, (const smi_air *)air, degree, fri_expansion, &g_air_err);
+    return air_validate(p, cfg, (const smi_air *)air, degree, fri_expansion, &g_air_err, false, false, SMI_AIR_MAX_WINDOW);
 }
 const char *smi_air_last_error(void) { return g_air_err.c_str(); }
 int smi_air_plan_perm(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *perm, uint32_t *degree, uint64_t *fri_expansion) {
@@ -296,13 +315,13 @@ int smi_air_plan_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, co
 // out-of-domain sampling (deep_core.h): the plan, and the proof length of a planned shape
 int smi_air_plan_deep(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint32_t *degree, uint32_t *segments) {
     g_air_err.clear();
-    return deep_plan(p, cfg, (const smi_air *)air, degree, segments, &g_air_err);
+    return deep_plan(p, cfg, (const smi_air *)air, degree, segments, &g_air_err, SMI_AIR_MAX_WINDOW);
 }
 int smi_air_deep_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, size_t *proof_len) {
     g_air_err.clear();
     uint32_t D = 0;
-    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err);
-    if (rc == SMI_OK && proof_len) *proof_len = deep_proof_len(cfg, D);
+    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err, SMI_AIR_MAX_WINDOW);
+    if (rc == SMI_OK && proof_len) *proof_len = deep_proof_len(cfg, D, air_window((const smi_air *)air));
     return rc;
 }
 // ... with an argument list (xargs_core.h)
@@ -321,9 +340,9 @@ int smi_air_deep_xargs_layout(uint64_t p, const smi_stark_cfg *cfg, const void *
 int smi_air_deep_fold4_layout(uint64_t p, const smi_stark_cfg *cfg, const void *air, uint64_t *folds, size_t *proof_len) {
     g_air_err.clear();
     uint32_t D = 0;
-    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err);
+    const int rc = deep_plan(p, cfg, (const smi_air *)air, nullptr, &D, &g_air_err, SMI_AIR_MAX_WINDOW);
     if (rc != SMI_OK) return rc;
-    const size_t len = deep_fold4_proof_len(cfg, 0, D, folds);
+    const size_t len = deep_fold4_proof_len(cfg, 0, D, folds, air_window((const smi_air *)air));
     if (proof_len) *proof_len = len;
     return SMI_OK;
 }
@@ -383,7 +402,7 @@ int smi_dev_air_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
     if (!ctx || !cfg || !air || !d_lde || !d_weights || !d_out) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     AirHost H;
-    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr));
+    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr, SMI_AIR_MAX_WINDOW));
     if (stride < H.dev.N) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose: stride < N");
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
@@ -399,7 +418,7 @@ int smi_dev_air_compose_ext(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *
     DeviceGuard dg__(ctx);
     SMI_TRY(ext_field_check(ctx));
     AirHost H;
-    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr));
+    SMI_TRY(air_host(ctx, cfg, (const smi_air *)air, &H, nullptr, SMI_AIR_MAX_WINDOW));
     if (stride < H.dev.N || out_stride < H.dev.N) return smi_fail(ctx, SMI_ERR_BAD_ARG, "air_compose_ext: stride < N or out_stride < N");
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t b_tab = up16(H.per.table_words * 4), b_vals = up16(H.per.vals.size() * 4);
@@ -420,7 +439,7 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
     cfg.n_cols = n_cols;
     cfg.log_n = log_n;
     std::string why;
-    const int rc = air_validate(ctx->fs.F.p, &cfg, air, nullptr, nullptr, &why, true);
+    const int rc = air_validate(ctx->fs.F.p, &cfg, air, nullptr, nullptr, &why, true, false, SMI_AIR_MAX_WINDOW);
     if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     AirHost H;
     air_build(ctx->fs.F, 1, &cfg, air, &H, true);
@@ -457,7 +476,8 @@ int smi_dev_air_check(smi_ctx *ctx, const void *air_, uint32_t n_cols, uint32_t 
     const uint64_t r = first & 0xffffffffull;
     if (constraint) *constraint = transition ? nb + idx : idx;
     if (row) *row = r;
-    ctx->err = transition ? "air_check: transition constraint " + std::to_string(idx) + " is violated on rows " + std::to_string(r) + " and " + std::to_string(r + 1)
+    const uint32_t S = air_window(air);
+    ctx->err = transition ? "air_check: transition constraint " + std::to_string(idx) + " is violated on rows " + std::to_string(r) + (S > 2 ? " .. " : " and ") + std::to_string(r + S - 1)
                           : "air_check: boundary point " + std::to_string(idx) + " (column " + std::to_string(air->boundary_col[idx]) + ", row " + std::to_string(r) +
                                 ") does not hold value " + std::to_string(air->boundary_value[idx]);
     return SMI_OK;

@@ -4,6 +4,11 @@
 //   cw[i] = sum_c w_c * term_c(x_i) + sum_k w_{W+k} * C_k(row i, row i+B) * (x_i - tau*w^(n-1)) / (x_i^n - tau^n)
 // (include/stark_mi.h, "AIR").  The reference has no counterpart (its Trace has no consumer).
 //
+// Transition windows (include/stark_mi.h, "AIR: transition windows").  An AIR with a window of S = 3 or 4 rows reads row
+// i + s B for s < S: the tile's halo is (S - 1) B points, the operands are numbered s R + row, and the quotient's numerator
+// carries the S - 1 exemption roots tau w^(n-s).  That code is the WIN = true instantiation of the templates below; WIN =
+// false is the two-row code as it was, so the kernels of a two-row AIR do not change with the window's existence.
+//
 // Periodic columns.  Column j (period P_j) is a table of L_j = P_j * B values tbl_j[i] = pi_j(x_i), i < L_j, that is read
 // modulo its length: pi_j(x_i) = tbl_j[i mod L_j], pi_j(w x_i) = tbl_j[(i + B) mod L_j] (stark_mi.h has the identity).
 // The tables lie back to back in one buffer (AirDev::ptab), longest period first, so that every table starts at a
@@ -37,7 +42,7 @@ struct AirDev {   // pointers into one blob of u32 (device memory for the kernel
     const uint32_t *tcoef;     // n_terms: coeff * R^(total exponent) mod p
     const uint32_t *tff;       // n_terms + 1: first factor of term t
     const uint32_t *fac;       // n_factors: operand | exp << 16; the operands are numbered by tile row, R = W + Q rows:
-                               // row (trace column c: c, periodic column j: W + j) at this row, R + row at the next row
+                               // row (trace column c: c, periodic column j: W + j) at this row, s R + row at row + s
     const uint32_t *free_col;  // W - n_bcols: the columns without a boundary point, ascending
     const uint32_t *bcol;      // n_bcols: the columns with boundary points, ascending
     const uint32_t *bfirst;    // n_bcols + 1: first point of boundary column j
@@ -51,11 +56,13 @@ struct AirDev {   // pointers into one blob of u32 (device memory for the kernel
     const uint32_t *plog;      // Q: log2 of the length L_j of table j
     const uint32_t *pofs;      // Q: first element of table j in ptab, a multiple of L_j
     const uint32_t *ptab;      // the tables, plain residues; not part of the blob
+    uint32_t S;                // the window, 2 .. SMI_AIR_MAX_WINDOW; behind the two-row fields, whose offsets stay
+    uint32_t lastx_m[2];       // tau * w^(n-2), tau * w^(n-3), Montgomery form: the further exemption roots of S = 3, 4
 };
 
-// periodic column j at the point with index i (next: one row further), from memory: table j read modulo its length
-SMI_HD uint32_t air_periodic_operand(const AirDev &A, uint32_t j, bool next, uint64_t i) {
-    const uint64_t at = next ? i + (1ull << A.log_B) : i;
+// periodic column j at the point with index i, s rows further, from memory: table j read at i + s B modulo its length
+SMI_HD uint32_t air_periodic_operand(const AirDev &A, uint32_t j, uint32_t s, uint64_t i) {
+    const uint64_t at = i + ((uint64_t)s << A.log_B);
     return A.ptab[A.pofs[j] + (uint32_t)(at & ((1ull << A.plog[j]) - 1))];
 }
 // operand `var` of a point without a tile: cur(c) / nxt(c) the trace column c at this row / the next, i the point's index
@@ -64,8 +71,25 @@ SMI_HD uint32_t air_mem_operand(const AirDev &A, uint32_t var, uint64_t i, Cur c
     const uint32_t R = A.W + A.Q;
     const bool next = var >= R;
     const uint32_t c = next ? var - R : var;
-    if (c >= A.W) return air_periodic_operand(A, c - A.W, next, i);
+    if (c >= A.W) return air_periodic_operand(A, c - A.W, next ? 1u : 0u, i);
     return next ? nxt(c) : cur(c);
+}
+// the shift s < S <= 4 of operand `var` = s R + row: three compares of wave-uniform values, no division
+SMI_HD uint32_t air_var_shift(uint32_t var, uint32_t R) { return (uint32_t)(var >= R) + (uint32_t)(var >= 2 * R) + (uint32_t)(var >= 3 * R); }
+// air_mem_operand under a window: at(c, s) the trace column c at row + s
+template <class At>
+SMI_HD uint32_t air_mem_operand_win(const AirDev &A, uint32_t var, uint64_t i, At at) {
+    const uint32_t R = A.W + A.Q, s = air_var_shift(var, R), c = var - s * R;
+    if (c >= A.W) return air_periodic_operand(A, c - A.W, s, i);
+    return at(c, s);
+}
+// (x - last) and, WIN, the further exemption roots: the numerator of 1 / Z_T
+template <bool WIN>
+SMI_HD uint32_t air_exempt(const AirDev &A, const Fp &F, uint32_t x_m) {
+    uint32_t e = fp_sub(x_m, A.last_m, F.p);
+    if (WIN)
+        for (uint32_t s = 2; s < A.S; s++) e = mont_mul(e, fp_sub(x_m, A.lastx_m[s - 2], F.p), F);
+    return e;
 }
 
 // ------------------------------------------------------------------------------------------------ evaluator
@@ -87,7 +111,7 @@ SMI_HD uint32_t air_constraint(const AirDev &A, const Fp &F, uint32_t k, Fetch f
 // P points of one thread.  x_m[q]: the point, Montgomery form; ib[q] = (index of point q) mod B; w_m: the W + K weights
 // reduced mod p, Montgomery form; fetch(q, var) the operands of point q.  One field inversion per AIR_INV_BATCH
 // boundary quotients: the P points of up to AIR_INV_BATCH / P boundary columns share it.
-template <int P, class Fetch>
+template <int P, bool WIN = false, class Fetch>
 SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *x_m, const uint32_t *ib, Fetch fetch,
                                uint32_t *out) {
     uint32_t acc[P];
@@ -134,8 +158,9 @@ SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m
             }
         }
     }
-    // transition quotients: (sum_k w_k C_k) * (x - last) / (x^n - tau^n).  Terms outside, the P points inside: a table
-    // entry is fetched once for the P points, and their P product chains are independent
+    // transition quotients: (sum_k w_k C_k) * (x - last) / (x^n - tau^n) (WIN: the S - 1 exemption roots, air_exempt).
+    // Terms outside, the P points inside: a table entry is fetched once for the P points, and their P product chains are
+    // independent
     if (A.K) {
         uint32_t s[P];
         for (int q = 0; q < P; q++) s[q] = 0;
@@ -159,7 +184,7 @@ SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m
             for (int q = 0; q < P; q++) s[q] = fp_add(s[q], mont_mul(ck[q], wk, F), F.p);
         }
         for (int q = 0; q < P; q++) {
-            const uint32_t zt = mont_mul(fp_sub(x_m[q], A.last_m, F.p), A.izt_m[ib[q]], F);
+            const uint32_t zt = mont_mul(air_exempt<WIN>(A, F, x_m[q]), A.izt_m[ib[q]], F);
             acc[q] = fp_add(acc[q], mont_mul(s[q], zt, F), F.p);
         }
     }
@@ -171,7 +196,7 @@ SMI_HD void air_compose_points(const AirDev &A, const Fp &F, const uint32_t *w_m
 // point q.  The quotients do not depend on the weights: every term_c and every C_k is evaluated once per point -- the
 // Horner chains, the batched inversion, the table walk are the ones above -- and enters four accumulators, so coordinate
 // e is exactly what air_compose_points returns for the weight vector (w_{.,e}).
-template <int P, class Fetch>
+template <int P, bool WIN = false, class Fetch>
 SMI_HD void air_compose_points_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *x_m, const uint32_t *ib, Fetch fetch,
                                    uint32_t *out) {
     uint32_t acc[4][P];
@@ -226,7 +251,7 @@ SMI_HD void air_compose_points_ext(const AirDev &A, const Fp &F, const uint32_t 
     }
     if (A.K) {
         uint32_t zt[P];   // (x - last) / (x^n - tau^n), Montgomery form
-        for (int q = 0; q < P; q++) zt[q] = mont_mul(fp_sub(x_m[q], A.last_m, F.p), A.izt_m[ib[q]], F);
+        for (int q = 0; q < P; q++) zt[q] = mont_mul(air_exempt<WIN>(A, F, x_m[q]), A.izt_m[ib[q]], F);
         for (uint32_t k = 0; k < A.K; k++) {
             uint32_t ck[P];
             for (int q = 0; q < P; q++) ck[q] = 0;
@@ -254,16 +279,18 @@ SMI_HD void air_compose_points_ext(const AirDev &A, const Fp &F, const uint32_t 
         for (int q = 0; q < P; q++) out[e * P + q] = acc[e][q];
 }
 
-// The tile of T points a workgroup stages per column: T points and a halo of B, wrapping at N.  Tile element e of
-// column c sits at tile[c * (T + B) + e] and comes from column index (base + e) mod N.  Periodic column j is tile row
-// W + j, staged the same way from table index (base + e) mod L_j: air_tile is asked for W + Q rows.
+// The tile of T points a workgroup stages per column: T points and a halo of (S - 1) B (B for two rows), wrapping at N.
+// Tile element e of column c sits at tile[c * (T + halo) + e] and comes from column index (base + e) mod N.  Periodic
+// column j is tile row W + j, staged the same way from table index (base + e) mod L_j: air_tile is asked for W + Q rows.
 struct AirTile {
     uint32_t T, threads, P;   // points per tile, threads per workgroup, points per thread (T = threads * P)
 };
-inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N, uint32_t weight_vecs = 1) {   // W: tile rows; weight_vecs: 4 for the ext kernel
+// W: tile rows; weight_vecs: 4 for the ext kernel; window: the AIR's S
+inline AirTile air_tile(uint32_t W, uint64_t B, uint64_t N, uint32_t weight_vecs = 1, uint32_t window = 2) {
     AirTile t{0, 0, 0};
+    const uint64_t halo = (uint64_t)(window - 1) * B;
     for (uint32_t T = 1024; T >= 64; T >>= 1) {
-        if (T > N || (uint64_t)W * (T + B) * 4 + (uint64_t)weight_vecs * AIR_MAX_WEIGHTS * 4 > AIR_LDS_BYTES) continue;
+        if (T > N || (uint64_t)W * (T + halo) * 4 + (uint64_t)weight_vecs * AIR_MAX_WEIGHTS * 4 > AIR_LDS_BYTES) continue;
         t.T = T;
         t.threads = T >= AIR_BLOCK ? AIR_BLOCK : T;
         t.P = T / t.threads;
@@ -279,8 +306,19 @@ inline uint32_t air_to_m(uint32_t a, uint32_t p) { return (uint32_t)(((uint64_t)
 // Everything smi_air_plan promises.  *why names the limit that was broken.
 // tables_only: the AIR's own tables against n_cols and log_n (smi_dev_air_check: no extension, no offsets).
 // any_expansion: E < 4 is not refused (out-of-domain sampling runs FRI at the blowup: deep_core.h deep_plan has its own bounds).
+// max_window: the widest transition window the caller takes.  The plan, the composition, the checker and the plain DEEP
+// provers and verifiers pass SMI_AIR_MAX_WINDOW; everybody else keeps 2 and so refuses a wider AIR here, before any work.
+inline uint32_t air_window(const smi_air *air) { return air->window ? air->window : 2u; }
+// D: the smallest power of two >= max(1, d - 1), doubled while D n <= d (n - 1) + (S - 1) - n, the quotient's degree bound.
+// It doubles (once) for (d, S) in {(2, 3), (2, 4), (3, 4)} alone, and never for S = 2.
+inline uint64_t air_segments(uint64_t d, uint32_t S, uint64_t n) {
+    uint64_t D = 1;
+    while (D < d - 1 && D < (1ull << 32)) D <<= 1;
+    while (D * n + n <= d * (n - 1) + (S - 1) && D < (1ull << 32)) D <<= 1;
+    return D;
+}
 inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *air, uint32_t *degree, uint64_t *fri_expansion,
-                        std::string *why, bool tables_only = false, bool any_expansion = false) {
+                        std::string *why, bool tables_only = false, bool any_expansion = false, uint32_t max_window = 2) {
     auto fail = [&](int code, const std::string &s) {
         if (why) *why = s;
         return code;
@@ -302,6 +340,13 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
     if (air->n_periodic > SMI_AIR_MAX_PERIODIC)
         return fail(SMI_ERR_BAD_ARG, "air: more than SMI_AIR_MAX_PERIODIC (" + std::to_string(SMI_AIR_MAX_PERIODIC) + ") periodic columns");
     const uint32_t K = air->n_constraints, nt = air->n_terms, nf = air->n_factors, nb = air->n_boundary, Q = air->n_periodic;
+    if (air->window == 1 || air->window > SMI_AIR_MAX_WINDOW)
+        return fail(SMI_ERR_BAD_ARG, "air: window must be 0 or 2 (two rows) or 3 .. SMI_AIR_MAX_WINDOW (" + std::to_string(SMI_AIR_MAX_WINDOW) + ")");
+    const uint32_t S = air_window(air);
+    if (S > max_window)
+        return fail(SMI_ERR_BAD_ARG, "air: a transition window of " + std::to_string(S) +
+                                         " rows is taken by smi_air_plan, the composition, the checker and the plain DEEP provers and verifiers only");
+    if (S > 2 && (1ull << cfg->log_n) < S) return fail(SMI_ERR_BAD_ARG, "air: window " + std::to_string(S) + " needs a trace of at least as many rows");
     if ((!air->constraint_first_term) || (!air->term_first_factor) || (nt && !air->term_coeff) || (nf && (!air->factor_var || !air->factor_exp)) ||
         (nb && (!air->boundary_col || !air->boundary_row || !air->boundary_value)) || (Q && (!air->periodic_log_period || !air->periodic_value)))
         return fail(SMI_ERR_BAD_ARG, "air: null table");
@@ -324,8 +369,9 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
         if (air->term_coeff[t] >= p) return fail(SMI_ERR_NON_CANONICAL, "air: term coefficient >= p");
         uint64_t deg = 0;
         for (uint32_t f = f0; f < f1; f++) {
-            if (air->factor_var[f] >= 2 * W + 2 * Q)
-                return fail(SMI_ERR_BAD_ARG, "air: factor_var must be < 2 * n_cols + 2 * n_periodic (row shifts 0 and 1 only)");
+            if (air->factor_var[f] >= S * (W + Q))   // two rows: the sentence they always had
+                return fail(SMI_ERR_BAD_ARG, S == 2 ? "air: factor_var must be < 2 * n_cols + 2 * n_periodic (row shifts 0 and 1 only)"
+                                                    : "air: factor_var must be < window * (n_cols + n_periodic) (row shifts 0 .. window - 1)");
             if (air->factor_exp[f] < 1 || air->factor_exp[f] > SMI_AIR_MAX_EXP)
                 return fail(SMI_ERR_BAD_ARG, "air: factor_exp must be in 1 .. SMI_AIR_MAX_EXP (" + std::to_string(SMI_AIR_MAX_EXP) + ")");
             deg += air->factor_exp[f];
@@ -347,8 +393,7 @@ inline int air_validate(uint64_t p64, const smi_stark_cfg *cfg, const smi_air *a
     if (degree) *degree = (uint32_t)d;
     if (tables_only) return SMI_OK;
     const uint64_t B = 1ull << cfg->log_blowup;
-    uint64_t D = 1;
-    while (D < d - 1) D <<= 1;   // d >= 1; the smallest power of two >= max(1, d - 1)
+    const uint64_t D = air_segments(d, S, 1ull << cfg->log_n);   // d >= 1
     const uint64_t E = D > B ? 0 : B / D;
     if (E < 4 && !any_expansion) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "air: 2^log_blowup / D < 4: the quotients of a degree-" + std::to_string(d) + " constraint do not fit under the FRI degree bound");
     const uint64_t tau = cfg->trace_offset, h = cfg->lde_offset;
@@ -447,9 +492,11 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
     mark(2);
     for (uint32_t t = 0; t <= nt; t++) b.push_back(air->term_first_factor[t]);
     mark(3);
-    for (uint32_t f = 0; f < nf; f++) {   // smi_air's variables to tile rows; with Q = 0 the two numberings are one
-        const uint32_t Q = air->n_periodic, v = air->factor_var[f];
-        const uint32_t row = v < 2 * W ? (v < W ? v : v + Q) : (v < 2 * W + Q ? v - W : v);   // < 2 (W + Q) <= 160
+    const uint32_t S = air_window(air);
+    // smi_air's variables s W + c, S W + s Q + j to tile rows s R + c, s R + W + j; with Q = 0 the two numberings are one
+    for (uint32_t f = 0; f < nf; f++) {
+        const uint32_t Q = air->n_periodic, v = air->factor_var[f], R = W + Q;
+        const uint32_t row = v < S * W ? (v / W) * R + v % W : ((v - S * W) / Q) * R + W + (v - S * W) % Q;   // < S (W + Q) <= 320
         b.push_back(row | (air->factor_exp[f] << 16));   // exponent <= SMI_AIR_MAX_EXP < 2^16
     }
     if (tables_only) {
@@ -460,6 +507,8 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
         H->dev.log_B = 0;
         H->dev.N = n;
         H->dev.last_m = H->dev.h_m = H->dev.omega_m = 0;
+        H->dev.S = S;
+        H->dev.lastx_m[0] = H->dev.lastx_m[1] = 0;
         periodic();
         b.push_back(0);
         air_bind(*H, b.data());
@@ -525,6 +574,8 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
     d.log_B = cfg->log_blowup;
     d.N = N;
     d.last_m = air_to_m(host_mulmod(tau, host_powmod(w, n - 1, p), p), p);
+    d.S = S;
+    for (uint32_t s = 2; s < 4; s++) d.lastx_m[s - 2] = s < S ? air_to_m(host_mulmod(tau, host_powmod(w, n - s, p), p), p) : 0;
     d.h_m = air_to_m(h, p);
     d.omega_m = air_to_m(omega_N, p);
     air_bind(*H, b.data());
@@ -532,10 +583,10 @@ inline void air_build(const Fp &F, uint32_t omega_N, const smi_stark_cfg *cfg, c
 
 // One workgroup's tile, one "thread" at a time: what air_compose_kernel runs between its barriers, over `tile`
 // ((W + Q) x (T + B) staged elements).  Shared so that the emulator executes the kernel's own indexing.
-template <int P>
+template <int P, bool WIN = false>
 SMI_HD void air_tile_thread(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *tile, uint32_t T, uint32_t threads,
                             uint64_t base, uint32_t xbase_m, uint32_t step_m, uint32_t tid, uint32_t *out) {
-    const uint32_t B = 1u << A.log_B, pitch = T + B, R = A.W + A.Q;
+    const uint32_t B = 1u << A.log_B, pitch = T + (WIN ? (A.S - 1) << A.log_B : B), R = A.W + A.Q;
     uint32_t x_m[P], ib[P], res[P];
     uint32_t x = mont_mul(xbase_m, A.lane_pow_m[tid], F);
     for (int q = 0; q < P; q++) {
@@ -543,9 +594,13 @@ SMI_HD void air_tile_thread(const AirDev &A, const Fp &F, const uint32_t *w_m, c
         ib[q] = (uint32_t)((base + tid + (uint64_t)q * threads) & (B - 1));
         x = mont_mul(x, step_m, F);
     }
-    air_compose_points<P>(
+    air_compose_points<P, WIN>(
         A, F, w_m, x_m, ib,
         [&](int q, uint32_t var) {   // rows 0 .. W-1 the trace columns, W .. R-1 the periodic ones; the next row is B further
+            if (WIN) {               // row + s is s B further
+                const uint32_t s = air_var_shift(var, R);
+                return tile[(var - s * R) * pitch + tid + q * threads + (s << A.log_B)];
+            }
             const uint32_t c = var < R ? var : var - R;
             return tile[c * pitch + tid + q * threads + (var < R ? 0 : B)];
         },
@@ -555,14 +610,16 @@ SMI_HD void air_tile_thread(const AirDev &A, const Fp &F, const uint32_t *w_m, c
 
 // The same point without a tile (no tile fits, or the columns are not 16-byte aligned): operands straight from memory,
 // one power per point.  The rare path: many columns at a large blowup, or a domain of fewer than 64 points.
+template <bool WIN = false>
 SMI_HD void air_direct_point(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, uint64_t i,
                              uint32_t *out) {
     const uint64_t B = 1ull << A.log_B, nx = (i + B) & (A.N - 1);
     const uint32_t x_m = mont_mul(A.h_m, mont_pow(A.omega_m, i, F), F), ib = (uint32_t)(i & (B - 1));
     uint32_t res;
-    air_compose_points<1>(
+    air_compose_points<1, WIN>(
         A, F, w_m, &x_m, &ib,
         [&](int, uint32_t var) {
+            if (WIN) return air_mem_operand_win(A, var, i, [&](uint32_t c, uint32_t s) { return cols[c * stride + ((i + ((uint64_t)s << A.log_B)) & (A.N - 1))]; });
             return air_mem_operand(A, var, i, [&](uint32_t c) { return cols[c * stride + i]; }, [&](uint32_t c) { return cols[c * stride + nx]; });
         },
         &res);
@@ -571,10 +628,10 @@ SMI_HD void air_direct_point(const AirDev &A, const Fp &F, const uint32_t *w_m, 
 
 // air_tile_thread / air_direct_point under extension weights: the same tile, the same x, four output columns out_stride
 // apart (w_m: 4 * AIR_MAX_WEIGHTS words, air_compose_points_ext)
-template <int P>
+template <int P, bool WIN = false>
 SMI_HD void air_tile_thread_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *tile, uint32_t T, uint32_t threads,
                                 uint64_t base, uint32_t xbase_m, uint32_t step_m, uint32_t tid, uint32_t *out, uint64_t out_stride) {
-    const uint32_t B = 1u << A.log_B, pitch = T + B, R = A.W + A.Q;
+    const uint32_t B = 1u << A.log_B, pitch = T + (WIN ? (A.S - 1) << A.log_B : B), R = A.W + A.Q;
     uint32_t x_m[P], ib[P], res[4 * P];
     uint32_t x = mont_mul(xbase_m, A.lane_pow_m[tid], F);
     for (int q = 0; q < P; q++) {
@@ -582,9 +639,13 @@ SMI_HD void air_tile_thread_ext(const AirDev &A, const Fp &F, const uint32_t *w_
         ib[q] = (uint32_t)((base + tid + (uint64_t)q * threads) & (B - 1));
         x = mont_mul(x, step_m, F);
     }
-    air_compose_points_ext<P>(
+    air_compose_points_ext<P, WIN>(
         A, F, w_m, x_m, ib,
         [&](int q, uint32_t var) {
+            if (WIN) {
+                const uint32_t s = air_var_shift(var, R);
+                return tile[(var - s * R) * pitch + tid + q * threads + (s << A.log_B)];
+            }
             const uint32_t c = var < R ? var : var - R;
             return tile[c * pitch + tid + q * threads + (var < R ? 0 : B)];
         },
@@ -592,14 +653,16 @@ SMI_HD void air_tile_thread_ext(const AirDev &A, const Fp &F, const uint32_t *w_
     for (int e = 0; e < 4; e++)
         for (int q = 0; q < P; q++) out[e * out_stride + base + tid + (uint64_t)q * threads] = res[e * P + q];
 }
+template <bool WIN = false>
 SMI_HD void air_direct_point_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, uint64_t i,
                                  uint32_t *out, uint64_t out_stride) {
     const uint64_t B = 1ull << A.log_B, nx = (i + B) & (A.N - 1);
     const uint32_t x_m = mont_mul(A.h_m, mont_pow(A.omega_m, i, F), F), ib = (uint32_t)(i & (B - 1));
     uint32_t res[4];
-    air_compose_points_ext<1>(
+    air_compose_points_ext<1, WIN>(
         A, F, w_m, &x_m, &ib,
         [&](int, uint32_t var) {
+            if (WIN) return air_mem_operand_win(A, var, i, [&](uint32_t c, uint32_t s) { return cols[c * stride + ((i + ((uint64_t)s << A.log_B)) & (A.N - 1))]; });
             return air_mem_operand(A, var, i, [&](uint32_t c) { return cols[c * stride + i]; }, [&](uint32_t c) { return cols[c * stride + nx]; });
         },
         res);

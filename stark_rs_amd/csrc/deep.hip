@@ -19,6 +19,19 @@
 // coordinate, one 16-byte store per coordinate of Q: 4 (W + 4 D) + 16 bytes a point.  The eight denominators of a lane
 // (x - z and x - z w at four points) share one F_q inversion; the constants sum gamma u are folded into two subtrahends on
 // the host.  x advances by a per-lane step over a grid-stride loop.
+//
+// Transition windows (include/stark_mi.h, "AIR: transition windows").  A window of S = 3 or 4 rows opens the trace at
+// z w^s, s < S.  The evaluation takes a table per point: deep_eval_kernel<VEC, 3> and <VEC, 4> hold 16 S powers a lane and
+// keep the four multiplies per coefficient and point.  The price is registers: 100 .. 104 VGPRs at three points and
+// 132 .. 136 at four, 4 and 3 waves a SIMD against 7 at two points (profiles/air_window_kernel_resources.log).  The other
+// route -- one table of powers of z and a multiply by w^(s k) per coefficient and shift -- holds 16 + 4 (S - 1) words a
+// lane but does 4 S + S - 1 multiplies a coefficient, 19 against 16 at S = 4.  The kernel reads four bytes per 16 S
+// multiply-reduce chains, all independent of each other, so it is bound by the multiplier and not by latency that more
+// waves would hide; it runs over W n coefficients once a proof.  No timing of either route has been taken on a card.
+// deep_compose_window_kernel<VEC, S> is deep_compose_kernel with S accumulators a point and the 4 S denominators of a lane
+// under one F_q inversion (deep_core.h deep_compose_window_points): 16 S accumulator words and 16 S words of prefix products
+// are live together at the inversion, 163 .. 166 VGPRs (3 waves, as deep_compose_kernel) at S = 3 and 208 .. 243 (2 waves)
+// at S = 4, no scratch.
 #include <string>
 #include <vector>
 
@@ -128,6 +141,27 @@ __global__ __launch_bounds__(DEEP_BLOCK) void deep_compose_kernel(Fp F, uint32_t
     }
 }
 
+// deep_compose_kernel for a window of S = 3 or 4 rows: the same stream, S quotient groups
+template <bool VEC, int S>
+__global__ __launch_bounds__(DEEP_BLOCK) void deep_compose_window_kernel(Fp F, uint32_t g_m, uint32_t W, uint32_t D, uint64_t N, uint32_t h_m, uint32_t omega_m,
+                                                                          const uint32_t *__restrict__ tab, const uint32_t *__restrict__ lde, size_t stride,
+                                                                          const uint32_t *__restrict__ seg, size_t seg_stride, uint32_t *__restrict__ out,
+                                                                          size_t out_stride) {
+    const uint64_t groups = N / DEEP_ROWS, gid = (uint64_t)blockIdx.x * DEEP_BLOCK + threadIdx.x, gstep = (uint64_t)gridDim.x * DEEP_BLOCK;
+    uint32_t x_m = mont_mul(h_m, mont_pow(omega_m, gid * DEEP_ROWS, F), F);
+    const uint32_t xstep_m = mont_pow(omega_m, gstep * DEEP_ROWS, F);
+    for (uint64_t g = gid; g < groups; g += gstep) {
+        const uint64_t i0 = g * DEEP_ROWS;   // N is a multiple of 4: i0 + 3 < N
+        uint32_t o[4][DEEP_ROWS];
+        deep_compose_window_points<S>(
+            tab, W, D, g_m, F, x_m, omega_m, [&](uint32_t c, uint32_t v[4]) { perm_load4<VEC>(lde + (size_t)c * stride, i0, N, v); },
+            [&](uint32_t col, uint32_t v[4]) { perm_load4<VEC>(seg + (size_t)col * seg_stride, i0, N, v); }, o);
+#pragma unroll
+        for (int e = 0; e < 4; e++) perm_store4<VEC>(out + e * out_stride, i0, N, o[e]);
+        x_m = mont_mul(x_m, xstep_m, F);
+    }
+}
+
 namespace {
 // device bytes one evaluation wants behind its table: the partial sums
 size_t deep_eval_part_bytes(uint32_t n_cols, uint64_t n_coeffs, uint32_t P) { return (size_t)n_cols * deep_eval_blocks(n_coeffs) * P * 16; }
@@ -146,7 +180,13 @@ int deep_eval_enqueue(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, uin
     const dim3 grid((uint32_t)nb, (uint32_t)gy);
     {
         ProfScope ps(ctx, "deep_eval_kernel", 4.0 * (double)n_cols * (double)n_coeffs);
-        if (P == 2) {
+        if (P == 4) {
+            if (vec) deep_eval_kernel<true, 4><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
+            else deep_eval_kernel<false, 4><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
+        } else if (P == 3) {
+            if (vec) deep_eval_kernel<true, 3><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
+            else deep_eval_kernel<false, 3><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
+        } else if (P == 2) {
             if (vec) deep_eval_kernel<true, 2><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
             else deep_eval_kernel<false, 2><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, d_cols, stride, n_cols, n_coeffs, d_tab, d_part);
         } else {
@@ -157,25 +197,36 @@ int deep_eval_enqueue(smi_ctx *ctx, const uint32_t *d_cols, uint32_t n_cols, uin
     }
     {
         ProfScope ps(ctx, "deep_eval_combine_kernel", 16.0 * (double)n_cols * (double)nb * P);
-        if (P == 2) deep_eval_combine_kernel<2><<<dim3(n_cols, 2), DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, d_part, (uint32_t)nb, d_tab, d_out);
+        if (P == 4) deep_eval_combine_kernel<4><<<dim3(n_cols, 4), DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, d_part, (uint32_t)nb, d_tab, d_out);
+        else if (P == 3) deep_eval_combine_kernel<3><<<dim3(n_cols, 3), DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, d_part, (uint32_t)nb, d_tab, d_out);
+        else if (P == 2) deep_eval_combine_kernel<2><<<dim3(n_cols, 2), DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, d_part, (uint32_t)nb, d_tab, d_out);
         else deep_eval_combine_kernel<1><<<dim3(n_cols, 1), DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, d_part, (uint32_t)nb, d_tab, d_out);
         HIP_TRY(ctx, hipGetLastError());
     }
     return SMI_OK;
 }
 
-// d_tab: the table of deep_compose_build on the device
+// d_tab: the table of deep_compose_build on the device (built for the window S)
 int deep_compose_enqueue(smi_ctx *ctx, uint32_t W, uint32_t D, uint32_t log_N, uint32_t h, const uint32_t *d_tab, const uint32_t *d_lde, size_t stride,
-                         const uint32_t *d_seg, size_t seg_stride, uint32_t *d_out, size_t out_stride) {
+                         const uint32_t *d_seg, size_t seg_stride, uint32_t *d_out, size_t out_stride, uint32_t S = 2) {
     const Fp F = ctx->fs.F;
     const uint64_t N = 1ull << log_N;
     const bool vec = al16(d_lde) && al16(d_seg) && al16(d_out) && !(stride & 3) && !(seg_stride & 3) && !(out_stride & 3);
     const uint64_t groups = N / DEEP_ROWS, want = (groups + DEEP_BLOCK - 1) / DEEP_BLOCK, cap = (uint64_t)ctx->num_cus * 8;
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
     const uint32_t g_m = air_to_m(ctx->fs.g, F.p), h_m = air_to_m(h, F.p), omega_m = air_to_m(h_root(ctx, log_N), F.p);
-    ProfScope ps(ctx, "deep_compose_kernel", (4.0 * (W + 4.0 * D) + 16.0) * (double)N);
-    if (vec) deep_compose_kernel<true><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, D, N, h_m, omega_m, d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride);
+    ProfScope ps(ctx, S > 2 ? "deep_compose_window_kernel" : "deep_compose_kernel", (4.0 * (W + 4.0 * D) + 16.0) * (double)N);
+#define DEEP_WINDOW_LAUNCH(V, S_) \
+    deep_compose_window_kernel<V, S_><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, D, N, h_m, omega_m, d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride)
+    if (S == 4) {
+        if (vec) DEEP_WINDOW_LAUNCH(true, 4);
+        else DEEP_WINDOW_LAUNCH(false, 4);
+    } else if (S == 3) {
+        if (vec) DEEP_WINDOW_LAUNCH(true, 3);
+        else DEEP_WINDOW_LAUNCH(false, 3);
+    } else if (vec) deep_compose_kernel<true><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, D, N, h_m, omega_m, d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride);
     else deep_compose_kernel<false><<<grid, DEEP_BLOCK, 0, ctx->stream>>>(F, g_m, W, D, N, h_m, omega_m, d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride);
+#undef DEEP_WINDOW_LAUNCH
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
@@ -221,11 +272,49 @@ int smi_dev_poly_eval_ext(smi_ctx *ctx, const uint32_t *d_coeffs, uint32_t n_col
     return SMI_OK;
 }
 
+// the points z, z w, .. z w^(n_shifts - 1) through the launches above, a table per point
+int smi_dev_poly_eval_ext_shifts(smi_ctx *ctx, const uint32_t *d_coeffs, uint32_t n_cols, size_t n_coeffs, size_t stride, const uint64_t z[4], uint64_t w,
+                                 uint32_t n_shifts, uint64_t *out) {
+    if (!ctx || !d_coeffs || !z || !out) return SMI_ERR_BAD_ARG;
+    DeviceGuard dg__(ctx);
+    SMI_TRY(deep_field_check(ctx));
+    if (!n_cols || n_cols > 65535) return smi_fail(ctx, SMI_ERR_BAD_ARG, "poly_eval_ext_shifts: 1 .. 65535 columns");
+    if (!n_coeffs || n_coeffs > ((size_t)1 << 27)) return smi_fail(ctx, SMI_ERR_BAD_ARG, "poly_eval_ext_shifts: 1 .. 2^27 coefficients");
+    if (stride < n_coeffs) return smi_fail(ctx, SMI_ERR_BAD_ARG, "poly_eval_ext_shifts: stride < n_coeffs");
+    if (n_shifts < 1 || n_shifts > DEEP_MAX_SHIFTS) return smi_fail(ctx, SMI_ERR_BAD_ARG, "poly_eval_ext_shifts: 1 .. SMI_AIR_MAX_WINDOW shifts");
+    if (w >= ctx->fs.F.p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "poly_eval_ext_shifts: w is >= p");
+    FqH pts[DEEP_MAX_SHIFTS];
+    SMI_TRY(deep_point(ctx, z, &pts[0]));
+    for (uint32_t k = 1; k < n_shifts; k++) pts[k] = fqh_scale(pts[k - 1], (uint32_t)w, ctx->fs.F.p);
+    std::vector<uint32_t> tab;
+    deep_eval_build(ctx->fs.F, ctx->fs.g, n_shifts, pts, &tab);
+    const size_t b_tab = up16(tab.size() * 4), b_part = up16(deep_eval_part_bytes(n_cols, n_coeffs, n_shifts)), n_out = (size_t)n_cols * n_shifts * 4;
+    void *base = nullptr;   // table | partial sums | results
+    SMI_TRY(ctx_tmp(ctx, 3, b_tab + b_part + n_out * 4, &base));
+    uint32_t *d_tab = (uint32_t *)base, *d_part = (uint32_t *)((uint8_t *)base + b_tab), *d_out = (uint32_t *)((uint8_t *)base + b_tab + b_part);
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SMI_TRY(deep_eval_enqueue(ctx, d_coeffs, n_cols, n_coeffs, stride, n_shifts, d_tab, d_part, d_out));
+    std::vector<uint32_t> res(n_out);
+    HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_out, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n_out; i++) out[i] = res[i];
+    return SMI_OK;
+}
+
 int smi_dev_deep_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_segments, const uint32_t *d_lde, size_t stride, const uint32_t *d_seg,
                          size_t seg_stride, const uint64_t z[4], const uint64_t *ood, const uint64_t *challenges, uint32_t *d_out, size_t out_stride) {
+    return smi_dev_deep_compose_window(ctx, cfg, 2, n_segments, d_lde, stride, d_seg, seg_stride, z, ood, challenges, d_out, out_stride);
+}
+
+// window = 2: deep_compose_kernel over the same table, word for word what smi_dev_deep_compose launched before the window
+int smi_dev_deep_compose_window(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t window, uint32_t n_segments, const uint32_t *d_lde, size_t stride,
+                                const uint32_t *d_seg, size_t seg_stride, const uint64_t z[4], const uint64_t *ood, const uint64_t *challenges, uint32_t *d_out,
+                                size_t out_stride) {
     if (!ctx || !cfg || !d_lde || !d_seg || !z || !ood || !challenges || !d_out) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     SMI_TRY(deep_field_check(ctx));
+    const uint32_t S = window;
+    if (S < 2 || S > SMI_AIR_MAX_WINDOW) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose_window: window must be in 2 .. SMI_AIR_MAX_WINDOW");
     const uint32_t W = cfg->n_cols, D = n_segments, log_N = cfg->log_n + cfg->log_blowup;
     if (!W || W > 64) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose: 1..64 columns");
     if (!D || D > DEEP_MAX_SEGMENTS) return smi_fail(ctx, SMI_ERR_BAD_ARG, "deep_compose: 1 .. 16 segments");
@@ -237,14 +326,14 @@ int smi_dev_deep_compose(smi_ctx *ctx, const smi_stark_cfg *cfg, uint32_t n_segm
     FqH zq;
     SMI_TRY(deep_point(ctx, z, &zq));
     if (fqh_in_base(zq)) return smi_fail(ctx, SMI_ERR_BAD_ARG, DEEP_Z_IN_BASE_FIELD);
-    for (size_t i = 0; i < 4 * (2 * (size_t)W + D); i++)
+    for (size_t i = 0; i < 4 * ((size_t)S * W + D); i++)
         if (ood[i] >= ctx->fs.F.p) return smi_fail(ctx, SMI_ERR_NON_CANONICAL, "deep_compose: an out-of-domain coordinate is >= p");
     std::vector<uint32_t> tab;
-    deep_compose_build(ctx->fs.F, ctx->fs.g, W, D, h_root(ctx, cfg->log_n), zq, ood, challenges, &tab);
+    deep_compose_build(ctx->fs.F, ctx->fs.g, W, D, h_root(ctx, cfg->log_n), zq, ood, challenges, &tab, S);
     void *d_tab = nullptr;
     SMI_TRY(ctx_tmp(ctx, 3, tab.size() * 4, &d_tab));
     HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    return deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, (const uint32_t *)d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride);
+    return deep_compose_enqueue(ctx, W, D, log_N, (uint32_t)cfg->lde_offset, (const uint32_t *)d_tab, d_lde, stride, d_seg, seg_stride, d_out, out_stride, S);
 }
 
 // ---- the codeword with an argument list (include/stark_mi.h, "Out-of-domain sampling with an argument list")
@@ -358,6 +447,7 @@ struct DeepProver {
     uint32_t *d_tail = nullptr;
     // shapes (deep_shapes)
     uint32_t W = 0, K = 0, A = 0, CW = 0, NW = 0, D = 0, log_n = 0, log_N = 0, p = 0, g = 0, w_n = 0;   // CW = 4 A coordinate columns; NW weights; D committed segments
+    uint32_t S = 2;   // the transition window: the trace is opened at z w^s, s < S (a list or a derived AIR: always 2)
     size_t n = 0, N = 0, leaves = 0, n_ood = 0;
     uint32_t G = 0, V[3] = {0, 0, 0};   // the committed groups in order -- trace, (auxiliary,) segments -- and their widths in columns
     // device buffers (deep_setup); cols[k] and tree[k] are group k's
@@ -395,7 +485,8 @@ int deep_shapes(DeepProver &s, uint32_t D, const char *no_layer) {
     if (s.cosets && fri_layout_fold4(deep_fri_cfg(cfg, 1)).F == 0) return smi_fail(ctx, SMI_ERR_BAD_ARG, no_layer);
     s.n = (size_t)1 << s.log_n, s.N = (size_t)1 << s.log_N, s.leaves = s.cosets ? s.N / 4 : s.N;
     s.p = ctx->fs.F.p, s.g = ctx->fs.g, s.w_n = h_root(ctx, s.log_n);
-    s.n_ood = deep_args_record(s.W, s.A, D);
+    s.S = s.xargs ? 2 : air_window(s.air);
+    s.n_ood = deep_args_record(s.W, s.A, D) + 4 * (size_t)(s.S - 2) * s.W;   // 4 (S W + 2 A + D)
     const DeepGroups gr = deep_groups(s.W, s.A, D);
     s.G = gr.G;
     for (uint32_t k = 0; k < 3; k++) s.V[k] = gr.V[k];
@@ -416,7 +507,8 @@ int deep_setup(DeepProver &s) {
         ok = ok && q;
         return q;
     };
-    const size_t part_a = deep_eval_part_bytes(W + CW, n, 2), part_b = deep_eval_part_bytes(D, n, 1);
+    const size_t part_a = deep_eval_part_bytes(W + CW, n, s.S), part_b = deep_eval_part_bytes(D, n, 1);
+    const size_t ctab_a = deep_args_tab_words(W, A, D), ctab_w = deep_window_tab_words(W, D, s.S);
     s.d_lde = (uint32_t *)take((size_t)s.V[0] * N * 4);
     if (A) s.d_c = (uint32_t *)take((size_t)CW * n * 4), s.d_cl = (uint32_t *)take((size_t)s.V[1] * N * 4);   // V[1]: CW, and a salt column under zk
     s.d_cw = (uint32_t *)take(4 * N * 4);   // H, then Q
@@ -427,10 +519,10 @@ int deep_setup(DeepProver &s) {
     s.d_blob = (uint32_t *)take(s.H.blob.size() * 4);
     for (uint32_t k = 0; k < s.G; k++) s.tree[k] = (uint8_t *)take(2 * s.leaves * 32);
     if (A) s.d_atmp = (uint8_t *)take(xargs_columns_tmp_bytes(A, n));
-    s.d_tab2 = (uint32_t *)take(deep_eval_tab_words(2) * 4), s.d_tab1 = (uint32_t *)take(deep_eval_tab_words(1) * 4);
+    s.d_tab2 = (uint32_t *)take(deep_eval_tab_words(s.S) * 4), s.d_tab1 = (uint32_t *)take(deep_eval_tab_words(1) * 4);
     s.d_part = (uint32_t *)take(part_a > part_b ? part_a : part_b);
-    s.d_res = (uint32_t *)take((size_t)(8 * (W + CW) + 16 * D) * 4);   // columns at z and z w | the segments' coordinates at z, e-major
-    s.d_ctab = (uint32_t *)take(deep_args_tab_words(W, A, D) * 4);
+    s.d_res = (uint32_t *)take((size_t)(4 * s.S * (W + CW) + 16 * D) * 4);   // columns at the S points z w^s | the segments' coordinates at z, e-major
+    s.d_ctab = (uint32_t *)take((ctab_a > ctab_w ? ctab_a : ctab_w) * 4);
     if (s.H.dev.Q) s.d_ptab = (uint32_t *)take(s.H.per.table_words * 4), s.d_pvals = (uint32_t *)take(s.H.per.vals.size() * 4);
     if (!ok) return smi_fail(ctx, SMI_ERR_OOM, (std::string(s.name) + ": device memory").c_str());
     s.cols[0] = s.d_lde, s.cols[1] = A ? s.d_cl : s.d_seg, s.cols[2] = s.d_seg;
@@ -525,20 +617,23 @@ int deep_draw_z(DeepProver &s, uint8_t *roots_out) {
     return SMI_OK;
 }
 
-// the record: u, v = f(z), f(z w) of the trace; a, b = c(z), c(z w) of the auxiliary columns; s_j = the segments at z.
+// the record: u, v = f(z), f(z w) of the trace (under a window: u_s = f(z w^s), s < S); a, b = c(z), c(z w) of the auxiliary
+// columns; s_j = the segments at z.
 // Coordinate e of the D segments is D columns of n coefficients at d_src + e src_pitch, src_stride apart.
 int deep_values_at_z(DeepProver &s, const uint32_t *d_src, size_t src_pitch, size_t src_stride, uint64_t *ood_out) {
     smi_ctx *ctx = s.ctx;
-    const uint32_t W = s.W, A = s.A, CW = s.CW, D = s.D, p = s.p, g = s.g;
-    const size_t n = s.n;
-    const FqH pts[2] = {s.z, fqh_scale(s.z, s.w_n, p)};
-    std::vector<uint32_t> tab2, tab1, res(8 * (size_t)(W + CW) + 16 * (size_t)D);
-    deep_eval_build(ctx->fs.F, g, 2, pts, &tab2);
+    const uint32_t W = s.W, A = s.A, CW = s.CW, D = s.D, p = s.p, g = s.g, S = s.S;
+    const size_t n = s.n, PS = 4 * (size_t)S;   // words a column in the result
+    FqH pts[SMI_AIR_MAX_WINDOW];
+    pts[0] = s.z;
+    for (uint32_t k = 1; k < S; k++) pts[k] = fqh_scale(pts[k - 1], s.w_n, p);
+    std::vector<uint32_t> tab2, tab1, res(PS * (W + CW) + 16 * (size_t)D);
+    deep_eval_build(ctx->fs.F, g, S, pts, &tab2);
     deep_eval_build(ctx->fs.F, g, 1, pts, &tab1);
     HIP_TRY(ctx, hipMemcpyAsync(s.d_tab2, tab2.data(), tab2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s.d_tab1, tab1.data(), tab1.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SMI_TRY(deep_eval_enqueue(ctx, s.d_coef, W + CW, n, n, 2, s.d_tab2, s.d_part, s.d_res));
-    uint32_t *d_sres = s.d_res + 8 * (size_t)(W + CW);
+    SMI_TRY(deep_eval_enqueue(ctx, s.d_coef, W + CW, n, n, S, s.d_tab2, s.d_part, s.d_res));
+    uint32_t *d_sres = s.d_res + PS * (W + CW);
     for (uint32_t e = 0; e < 4; e++) SMI_TRY(deep_eval_enqueue(ctx, d_src + e * src_pitch, D, n, src_stride, 1, s.d_tab1, s.d_part, d_sres + 4 * (size_t)e * D));
     HIP_TRY(ctx, hipMemcpyAsync(res.data(), s.d_res, res.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -554,13 +649,14 @@ int deep_values_at_z(DeepProver &s, const uint32_t *d_src, size_t src_pitch, siz
         }
         for (uint32_t e = 0; e < 4; e++) dst[e] = sum.c[e];
     };
-    for (uint32_t c = 0; c < W; c++)
-        for (uint32_t e = 0; e < 4; e++) ood[4 * c + e] = res[8 * c + e], ood[4 * (W + c) + e] = res[8 * c + 4 + e];
-    for (uint32_t a = 0; a < A; a++) {   // coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
+    for (uint32_t k = 0; k < S; k++)   // s-major: u_{k,c} at 4 (k W + c)
+        for (uint32_t c = 0; c < W; c++)
+            for (uint32_t e = 0; e < 4; e++) ood[4 * ((size_t)k * W + c) + e] = res[PS * c + 4 * k + e];
+    for (uint32_t a = 0; a < A; a++) {   // S = 2.  Coordinate column 4 a + e at z: res[8 (W + 4 a + e) ..], at z w: four words on
         assemble(&res[8 * (size_t)(W + 4 * a)], 8, &ood[4 * (2 * (size_t)W + a)]);
         assemble(&res[8 * (size_t)(W + 4 * a) + 4], 8, &ood[4 * (2 * (size_t)W + A + a)]);
     }
-    for (uint32_t j = 0; j < D; j++) assemble(&res[8 * (size_t)(W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * (2 * (size_t)W + 2 * (size_t)A + j)]);
+    for (uint32_t j = 0; j < D; j++) assemble(&res[PS * (W + CW) + 4 * (size_t)j], 4 * (size_t)D, &ood[4 * ((size_t)S * W + 2 * (size_t)A + j)]);
     if (ood_out) memcpy(ood_out, ood, 8 * s.n_ood);
     return SMI_OK;
 }
@@ -572,13 +668,13 @@ int deep_codeword(DeepProver &s) {
     const size_t N = s.N;
     std::vector<uint64_t> gammas;
     if (A) deep_args_transcript_gammas(s.tr, s.ood.data(), s.NW, s.n_ood, &gammas);
-    else deep_transcript_gammas(s.tr, s.ood.data(), W, s.K, D, &gammas);
+    else deep_transcript_gammas(s.tr, s.ood.data(), W, s.K, D, &gammas, s.S);
     s.seed = s.tr.seed();
     if (A) deep_compose_args_build(ctx->fs.F, s.g, W, A, D, s.w_n, s.z, s.ood.data(), gammas.data(), &s.ctab);
-    else deep_compose_build(ctx->fs.F, s.g, W, D, s.w_n, s.z, s.ood.data(), gammas.data(), &s.ctab);
+    else deep_compose_build(ctx->fs.F, s.g, W, D, s.w_n, s.z, s.ood.data(), gammas.data(), &s.ctab, s.S);
     HIP_TRY(ctx, hipMemcpyAsync(s.d_ctab, s.ctab.data(), s.ctab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     if (A) return deep_compose_args_enqueue(ctx, W, A, D, s.log_N, h, s.d_ctab, s.d_lde, N, s.d_cl, N, s.d_seg, N, s.d_cw, N);
-    return deep_compose_enqueue(ctx, W, D, s.log_N, h, s.d_ctab, s.d_lde, N, s.d_seg, N, s.d_cw, N);
+    return deep_compose_enqueue(ctx, W, D, s.log_N, h, s.d_ctab, s.d_lde, N, s.d_seg, N, s.d_cw, N, s.S);
 }
 
 // the head of the proof: tag 2 | the record's length | its values
@@ -652,7 +748,8 @@ int deep_prove(smi_ctx *ctx, const char *name, bool cosets, const smi_stark_cfg 
     uint32_t D = 0;
     {
         std::string why;
-        const int rc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why) : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+        const int rc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why)
+                             : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why, SMI_AIR_MAX_WINDOW);
         if (rc != SMI_OK) return smi_fail(ctx, rc, why.c_str());
     }
     DeepProver s(ctx, xargs ? 8 : 7, stage_ms != nullptr);

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/stark_mi.h"
@@ -27,7 +28,8 @@
 #define DEEP_BLOCK 256                            // lanes per workgroup
 #define DEEP_TILE (DEEP_ROWS * DEEP_BLOCK)        // coefficients of one column a workgroup reduces
 #define DEEP_MAX_SEGMENTS 16                      // 4 D <= 64: the widest row the leaf hash takes
-#define DEEP_MAX_POINTS 2
+#define DEEP_MAX_POINTS 2                         // smi_dev_poly_eval_ext: any one or two points
+#define DEEP_MAX_SHIFTS SMI_AIR_MAX_WINDOW        // smi_dev_poly_eval_ext_shifts: z, z w, .. z w^(S-1), a table per point
 
 // the sentences of the prover's refusal and of the verifier's own rejections (verify.hip; tests match on them)
 #define DEEP_Z_IN_BASE_FIELD "deep: the out-of-domain point z lies in the base field"
@@ -163,6 +165,99 @@ SMI_HD void deep_compose_points(const uint32_t *tab, uint32_t W, uint32_t D, uin
 #pragma unroll
         for (int e = 0; e < 4; e++) out[e][q] = fp_add(r1.c[e], r2.c[e], p);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ ... under a transition window
+// include/stark_mi.h, "AIR: transition windows": the trace is opened at z w^s for s < S (S = 3 or 4), so Q has S quotient
+// groups.  Table of one launch, u32 words -- for S = 2 it is the table above:
+//   gamma_{s,c} (Montgomery)            at 4 (s W + c) + e
+//   gamma''_j   (prepared: b_m | gb_m)  at 4 S W + 8 j + e, 4 S W + 8 j + 4 + e
+//   -C_s (plain; C_0 with the segments' sum) at 4 S W + 8 D + 4 s + e, then z w^s (Montgomery) at 4 S W + 8 D + 4 S + 4 s + e
+inline size_t deep_window_tab_words(uint32_t W, uint32_t D, uint32_t S) { return (size_t)4 * S * W + 8 * D + 8 * S; }
+
+// One lane of deep_compose_window_kernel: deep_compose_points with S accumulators a point.  The S DEEP_ROWS denominators
+// x - z w^s share one F_q inversion, taken after the column loop; an inverse is used as soon as it is peeled off, so no
+// array of inverses is kept, but the accumulators (16 S words) and the prefix products (16 S words) are live together.
+template <int I, class Body>
+SMI_HD void deep_steps_down(Body &body) {   // body(I), body(I - 1), .. body(0) with the index a compile-time constant
+    body(std::integral_constant<int, I>{});
+    if constexpr (I > 0) deep_steps_down<I - 1>(body);
+}
+template <int S, class LoadT, class LoadS>
+SMI_HD void deep_compose_window_points(const uint32_t *tab, uint32_t W, uint32_t D, uint32_t g_m, const Fp &F, uint32_t x0_m, uint32_t omega_m, LoadT load_t,
+                                       LoadS load_s, uint32_t out[4][DEEP_ROWS]) {
+    const uint32_t p = F.p;
+    const uint32_t *sg = tab + 4 * (size_t)S * W, *cst = sg + 8 * (size_t)D, *zs = cst + 4 * S;
+    uint32_t a[S][DEEP_ROWS][4];
+#pragma unroll
+    for (int s = 0; s < S; s++)
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) a[s][q][e] = cst[4 * s + e];
+    for (uint32_t c = 0; c < W; c++) {
+        uint32_t v[DEEP_ROWS];
+        load_t(c, v);
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+            const uint32_t *gs = tab + 4 * ((size_t)s * W + c);
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const uint32_t b = gs[e];
+#pragma unroll
+                for (int q = 0; q < DEEP_ROWS; q++) a[s][q][e] = fp_add(a[s][q][e], mont_mul(v[q], b, F), p);
+            }
+        }
+    }
+    for (uint32_t j = 0; j < D; j++) {
+        uint32_t h[4][DEEP_ROWS];
+#pragma unroll
+        for (int e = 0; e < 4; e++) load_s(4 * j + e, h[e]);
+        ExtMul M;
+#pragma unroll
+        for (int e = 0; e < 4; e++) M.b_m[e] = sg[8 * (size_t)j + e], M.gb_m[e] = sg[8 * (size_t)j + 4 + e];
+#pragma unroll
+        for (int q = 0; q < DEEP_ROWS; q++) {
+            const uint32_t hv[4] = {h[0][q], h[1][q], h[2][q], h[3][q]};
+            uint32_t o[4];
+            ext_mul_prepared(hv, M, F, o);
+#pragma unroll
+            for (int e = 0; e < 4; e++) a[0][q][e] = fp_add(a[0][q][e], o[e], p);
+        }
+    }
+    // den[s * DEEP_ROWS + q] = x_q - z w^s, recomputed where it is needed: one subtraction in coordinate 0
+    uint32_t xq[DEEP_ROWS];
+    xq[0] = x0_m;
+#pragma unroll
+    for (int q = 1; q < DEEP_ROWS; q++) xq[q] = mont_mul(xq[q - 1], omega_m, F);
+    auto den = [&](int i) {
+        const uint32_t *zw = zs + 4 * (i / DEEP_ROWS);
+        return Fq{{fp_sub(xq[i % DEEP_ROWS], zw[0], p), fp_neg(zw[1], p), fp_neg(zw[2], p), fp_neg(zw[3], p)}};
+    };
+    Fq pre[S * DEEP_ROWS];
+    pre[0] = den(0);
+#pragma unroll
+    for (int i = 1; i < S * DEEP_ROWS; i++) pre[i] = fq_mul(pre[i - 1], den(i), g_m, F);
+    Fq inv = fq_inv(pre[S * DEEP_ROWS - 1], g_m, F);
+    uint32_t r[DEEP_ROWS][4];
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) r[q][e] = 0;
+    // 4 S steps of three F_q products each: more than an unroll pragma takes, so the steps are instantiated one by one
+    auto step = [&](auto I) {
+        constexpr int i = decltype(I)::value, s = i / DEEP_ROWS, q = i % DEEP_ROWS;
+        const Fq di = i ? fq_mul(inv, pre[i ? i - 1 : 0], g_m, F) : inv;
+        if (i) inv = fq_mul(inv, den(i), g_m, F);
+        const Fq t = fq_mul(Fq{{a[s][q][0], a[s][q][1], a[s][q][2], a[s][q][3]}}, di, g_m, F);
+#pragma unroll
+        for (int e = 0; e < 4; e++) r[q][e] = fp_add(r[q][e], t.c[e], p);
+    };
+    deep_steps_down<S * DEEP_ROWS - 1>(step);
+#pragma unroll
+    for (int q = 0; q < DEEP_ROWS; q++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) out[e][q] = r[q][e];
 }
 
 // ------------------------------------------------------------------------------------------------ ... with auxiliary columns
@@ -331,52 +426,56 @@ inline void deep_eval_build(const Fp &F, uint32_t g, uint32_t P, const FqH *z, s
     }
 }
 
-// the table of deep_compose_kernel.  ood: the record's 4 (2 W + D) canonical values (u, v, s); ch: as many unreduced
-// challenges (gamma, gamma', gamma''); w_n = omega_n
+// the table of deep_compose_kernel (S = 2) and deep_compose_window_kernel.  ood: the record's 4 (S W + D) canonical values
+// (u_{s,c} s-major, then s_j); ch: as many unreduced challenges in that order; w_n = omega_n
 inline void deep_compose_build(const Fp &F, uint32_t g, uint32_t W, uint32_t D, uint32_t w_n, const FqH &z, const uint64_t *ood, const uint64_t *ch,
-                               std::vector<uint32_t> *tab) {
+                               std::vector<uint32_t> *tab, uint32_t S = 2) {
     const uint32_t p = F.p;
-    tab->assign(deep_tab_words(W, D), 0);
+    tab->assign(deep_window_tab_words(W, D, S), 0);   // S = 2: deep_tab_words(W, D)
     uint32_t *t = tab->data();
-    FqH c1 = fqh(0), c2 = fqh(0);
-    for (uint32_t c = 0; c < W; c++) {
-        const FqH g1 = fqh_of(ch + 4 * (size_t)c, p), g2 = fqh_of(ch + 4 * (size_t)(W + c), p);
-        for (int e = 0; e < 4; e++) t[4 * c + e] = air_to_m(g1.c[e], p), t[4 * (W + c) + e] = air_to_m(g2.c[e], p);
-        c1 = fqh_add(c1, fqh_mul(g1, fqh_of(ood + 4 * (size_t)c, p), p, g), p);
-        c2 = fqh_add(c2, fqh_mul(g2, fqh_of(ood + 4 * (size_t)(W + c), p), p, g), p);
-    }
-    for (uint32_t j = 0; j < D; j++) {
-        const FqH g3 = fqh_of(ch + 4 * (size_t)(2 * W + j), p);
-        for (int e = 0; e < 4; e++) {
-            t[8 * W + 8 * j + e] = air_to_m(g3.c[e], p);
-            t[8 * W + 8 * j + 4 + e] = air_to_m(host_mulmod(g3.c[e], g, p), p);
+    FqH cs[SMI_AIR_MAX_WINDOW] = {fqh(0), fqh(0), fqh(0), fqh(0)};
+    for (uint32_t s = 0; s < S; s++)
+        for (uint32_t c = 0; c < W; c++) {
+            const size_t i = (size_t)s * W + c;
+            const FqH gs = fqh_of(ch + 4 * i, p);
+            for (int e = 0; e < 4; e++) t[4 * i + e] = air_to_m(gs.c[e], p);
+            cs[s] = fqh_add(cs[s], fqh_mul(gs, fqh_of(ood + 4 * i, p), p, g), p);
         }
-        c1 = fqh_add(c1, fqh_mul(g3, fqh_of(ood + 4 * (size_t)(2 * W + j), p), p, g), p);
+    uint32_t *sg = t + 4 * (size_t)S * W;
+    for (uint32_t j = 0; j < D; j++) {
+        const FqH g3 = fqh_of(ch + 4 * ((size_t)S * W + j), p);
+        for (int e = 0; e < 4; e++) {
+            sg[8 * j + e] = air_to_m(g3.c[e], p);
+            sg[8 * j + 4 + e] = air_to_m(host_mulmod(g3.c[e], g, p), p);
+        }
+        cs[0] = fqh_add(cs[0], fqh_mul(g3, fqh_of(ood + 4 * ((size_t)S * W + j), p), p, g), p);
     }
-    uint32_t *cst = t + 8 * (size_t)W + 8 * (size_t)D;
-    const FqH zw = fqh_scale(z, w_n, p);
-    for (int e = 0; e < 4; e++) {
-        cst[e] = fp_neg(c1.c[e], p);
-        cst[4 + e] = fp_neg(c2.c[e], p);
-        cst[8 + e] = air_to_m(z.c[e], p);
-        cst[12 + e] = air_to_m(zw.c[e], p);
+    uint32_t *cst = sg + 8 * (size_t)D;
+    FqH zw = z;
+    for (uint32_t s = 0; s < S; s++) {
+        for (int e = 0; e < 4; e++) {
+            cst[4 * s + e] = fp_neg(cs[s].c[e], p);
+            cst[4 * S + 4 * s + e] = air_to_m(zw.c[e], p);
+        }
+        zw = fqh_scale(zw, w_n, p);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ plan, layout, transcript
 // smi_air_plan_deep: smi_air_plan's checks without its bound on E, then D <= B, B >= 4, 4 D <= 64
-inline int deep_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, uint32_t *degree, uint32_t *segments, std::string *why) {
+// max_window: 2 for the callers that prove a list or a derived AIR; the plain entry points pass SMI_AIR_MAX_WINDOW
+inline int deep_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, uint32_t *degree, uint32_t *segments, std::string *why,
+                     uint32_t max_window = 2) {
     auto fail = [&](int code, const std::string &s) {
         if (why) *why = s;
         return code;
     };
     uint32_t d = 0;
-    const int rc = air_validate(p, cfg, air, &d, nullptr, why, false, true);
+    const int rc = air_validate(p, cfg, air, &d, nullptr, why, false, true, max_window);
     if (rc != SMI_OK) return rc;
     if ((p & 3) != 1) return fail(SMI_ERR_BAD_ARG, "deep: p = 3 (mod 4): the quartic extension does not exist");
     const uint64_t B = 1ull << cfg->log_blowup;
-    uint64_t D = 1;
-    while (D < (uint64_t)d - 1 && D < (1ull << 32)) D <<= 1;
+    const uint64_t D = air_segments(d, air_window(air), 1ull << cfg->log_n);
     if (D > B)
         return fail(SMI_ERR_BAD_ARG, "deep: D > 2^log_blowup: the composition of a degree-" + std::to_string(d) + " constraint has degree >= N and does not fit the evaluation domain");
     if (B < 4) return fail(SMI_ERR_EXPANSION_TOO_SMALL, "deep: 2^log_blowup < 4 (Fri::new's assert on the expansion factor)");
@@ -394,11 +493,11 @@ inline smi_fri_cfg deep_fri_cfg(const smi_stark_cfg *cfg, uint64_t omega_N) {
     fc.num_colinearity_tests = cfg->num_colinearity_tests;
     return fc;
 }
-// 9 + 32 (2W + D) + len_FRI(N, B, t) + the two opening sections of two rows per test
-inline size_t deep_proof_len(const smi_stark_cfg *cfg, uint32_t D) {
+// 9 + 32 (S W + D) + len_FRI(N, B, t) + the two opening sections of two rows per test
+inline size_t deep_proof_len(const smi_stark_cfg *cfg, uint32_t D, uint32_t S = 2) {
     const uint64_t W = cfg->n_cols, t = cfg->num_colinearity_tests, log_N = cfg->log_n + cfg->log_blowup;
     const smi_fri_cfg fc = deep_fri_cfg(cfg, 1);
-    return (size_t)(9 + 32 * (2 * W + D) + fri_layout_ext(fc, true).proof_len + 2 * t * (9 + 8 * W) + 2 * t * (9 + 32 * log_N) + 2 * t * (9 + 32ull * D) +
+    return (size_t)(9 + 32 * (S * W + D) + fri_layout_ext(fc, true).proof_len + 2 * t * (9 + 8 * W) + 2 * t * (9 + 32 * log_N) + 2 * t * (9 + 32ull * D) +
                     2 * t * (9 + 32 * log_N));
 }
 
@@ -411,8 +510,8 @@ inline void deep_transcript_z(Transcript &T, const uint8_t root2[32], uint32_t W
     transcript_indexed(T, root2, 4 * ((uint64_t)W + K), 4, &ch);
     for (int e = 0; e < 4; e++) z[e] = ch[e];
 }
-inline void deep_transcript_gammas(Transcript &T, const uint64_t *ood, uint32_t W, uint32_t K, uint32_t D, std::vector<uint64_t> *gammas) {
-    const uint64_t cnt = 4 * (2 * (uint64_t)W + D);
+inline void deep_transcript_gammas(Transcript &T, const uint64_t *ood, uint32_t W, uint32_t K, uint32_t D, std::vector<uint64_t> *gammas, uint32_t S = 2) {
+    const uint64_t cnt = 4 * (S * (uint64_t)W + D);
     for (uint64_t i = 0; i < cnt; i++) T.absorb_index(ood[i]);   // the payload: every value as 8 little-endian bytes
     for (uint64_t m = 0; m < cnt; m++) {
         T.absorb_index(4 * ((uint64_t)W + K) + 4 + m);
@@ -421,7 +520,7 @@ inline void deep_transcript_gammas(Transcript &T, const uint64_t *ood, uint32_t 
 }
 
 // ------------------------------------------------------------------------------------------------ the verifier's side
-// C_k over F_q operands in smi_air's numbering: X[v], v < 2 W + 2 Q
+// C_k over F_q operands in smi_air's numbering: X[v], v < S (W + Q)
 inline FqH deep_constraint(const smi_air *air, uint32_t k, const FqH *X, uint32_t p, uint32_t g) {
     FqH ck = fqh(0);
     for (uint32_t t = air->constraint_first_term[k]; t < air->constraint_first_term[k + 1]; t++) {
@@ -463,9 +562,11 @@ inline FqH deep_periodic_at(const smi_air *air, uint32_t j, const uint64_t *vals
 // Both sides of the out-of-domain consistency check for a z outside F_p:
 //   lhs = sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z) from u = f(z), v = f(z w);   rhs = sum_j z^(j n) s_j.
 // weights: the 4 (W + K) unreduced challenges; ood: the record's 4 (2 W + D) canonical values; w_n = omega_n.
+// Under a window of S = air_window(air) rows the record holds u_{s,c} = f_c(z w^s) s-major, 4 (S W + D) values, the
+// operands are X[s W + c] = u_{s,c} and X[S W + s Q + j] = pi_j(z w^s), and the numerator carries the S - 1 exemption roots.
 inline void deep_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, const smi_air *air, uint32_t D, uint32_t w_n, const uint64_t *weights, const FqH &z,
                            const uint64_t *ood, FqH *lhs, FqH *rhs) {
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, Q = air->n_periodic, tau = (uint32_t)cfg->trace_offset;
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, Q = air->n_periodic, tau = (uint32_t)cfg->trace_offset, S = air_window(air);
     const uint64_t n = 1ull << cfg->log_n;
     FqH acc = fqh(0);
     for (uint32_t c = 0; c < W; c++) {
@@ -494,15 +595,17 @@ inline void deep_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, con
         acc = fqh_add(acc, fqh_mul(fqh_of(weights + 4 * (size_t)c, p), term, p, g), p);
     }
     if (K) {
-        std::vector<FqH> X(2 * (size_t)W + 2 * (size_t)Q);
-        for (uint32_t c = 0; c < W; c++) X[c] = fqh_of(ood + 4 * (size_t)c, p), X[W + c] = fqh_of(ood + 4 * (size_t)(W + c), p);
-        const FqH zw = fqh_scale(z, w_n, p);
-        for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++) {
-            X[2 * W + j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, z, p, g);
-            X[2 * W + Q + j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, zw, p, g);
+        std::vector<FqH> X((size_t)S * (W + Q));
+        for (size_t i = 0; i < (size_t)S * W; i++) X[i] = fqh_of(ood + 4 * i, p);
+        FqH zw = z;
+        for (uint32_t s = 0; s < S; s++) {
+            for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++)
+                X[(size_t)S * W + (size_t)s * Q + j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, zw, p, g);
+            zw = fqh_scale(zw, w_n, p);
         }
-        const uint32_t last = host_mulmod(tau, host_powmod(w_n, n - 1, p), p);
-        const FqH zt = fqh_mul(fqh_sub(z, fqh(last), p), fqh_inv(fqh_sub(fqh_pow(z, n, p, g), fqh(host_powmod(tau, n, p)), p), p, g), p, g);
+        FqH ex = fqh(1 % p);   // prod_{s = 1 .. S-1} (z - tau w^(n-s))
+        for (uint32_t s = 1; s < S; s++) ex = fqh_mul(ex, fqh_sub(z, fqh(host_mulmod(tau, host_powmod(w_n, n - s, p), p)), p), p, g);
+        const FqH zt = fqh_mul(ex, fqh_inv(fqh_sub(fqh_pow(z, n, p, g), fqh(host_powmod(tau, n, p)), p), p, g), p, g);
         for (uint32_t k = 0; k < K; k++)
             acc = fqh_add(acc, fqh_mul(fqh_of(weights + 4 * (size_t)(W + k), p), fqh_mul(deep_constraint(air, k, X.data(), p, g), zt, p, g), p, g), p);
     }
@@ -510,24 +613,30 @@ inline void deep_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, con
     const FqH zn = fqh_pow(z, n, p, g);
     FqH r = fqh(0), pw = fqh(1 % p);
     for (uint32_t j = 0; j < D; j++) {
-        r = fqh_add(r, fqh_mul(pw, fqh_of(ood + 4 * (size_t)(2 * W + j), p), p, g), p);
+        r = fqh_add(r, fqh_mul(pw, fqh_of(ood + 4 * ((size_t)S * W + j), p), p, g), p);
         pw = fqh_mul(pw, zn, p, g);
     }
     *rhs = r;
 }
 // Q(x) from the opened rows at x: trow = the W trace values, srow = the 4 D segment values (canonical)
+// S: the window; the record and the gammas hold S W + D elements, group s over the denominator x - z w^s
 inline FqH deep_q_at(uint32_t p, uint32_t g, uint32_t W, uint32_t D, uint32_t w_n, uint32_t x, const FqH &z, const uint64_t *ood, const uint64_t *gammas,
-                     const uint64_t *trow, const uint64_t *srow) {
-    FqH n1 = fqh(0), n2 = fqh(0);
-    for (uint32_t c = 0; c < W; c++) {
-        const FqH f = fqh((uint32_t)trow[c]);
-        n1 = fqh_add(n1, fqh_mul(fqh_of(gammas + 4 * (size_t)c, p), fqh_sub(f, fqh_of(ood + 4 * (size_t)c, p), p), p, g), p);
-        n2 = fqh_add(n2, fqh_mul(fqh_of(gammas + 4 * (size_t)(W + c), p), fqh_sub(f, fqh_of(ood + 4 * (size_t)(W + c), p), p), p, g), p);
+                     const uint64_t *trow, const uint64_t *srow, uint32_t S = 2) {
+    FqH q = fqh(0), zw = z;
+    for (uint32_t s = 0; s < S; s++) {
+        FqH num = fqh(0);
+        for (uint32_t c = 0; c < W; c++) {
+            const size_t i = (size_t)s * W + c;
+            num = fqh_add(num, fqh_mul(fqh_of(gammas + 4 * i, p), fqh_sub(fqh((uint32_t)trow[c]), fqh_of(ood + 4 * i, p), p), p, g), p);
+        }
+        for (uint32_t j = 0; j < D && !s; j++) {
+            const size_t i = (size_t)S * W + j;
+            num = fqh_add(num, fqh_mul(fqh_of(gammas + 4 * i, p), fqh_sub(fqh_of(srow + 4 * (size_t)j, p), fqh_of(ood + 4 * i, p), p), p, g), p);
+        }
+        q = fqh_add(q, fqh_mul(num, fqh_inv(fqh_sub(fqh(x), zw, p), p, g), p, g), p);
+        zw = fqh_scale(zw, w_n, p);
     }
-    for (uint32_t j = 0; j < D; j++)
-        n1 = fqh_add(n1, fqh_mul(fqh_of(gammas + 4 * (size_t)(2 * W + j), p), fqh_sub(fqh_of(srow + 4 * (size_t)j, p), fqh_of(ood + 4 * (size_t)(2 * W + j), p), p), p, g), p);
-    const FqH d1 = fqh_sub(fqh(x), z, p), d2 = fqh_sub(fqh(x), fqh_scale(z, w_n, p), p);
-    return fqh_add(fqh_mul(n1, fqh_inv(d1, p, g), p, g), fqh_mul(n2, fqh_inv(d2, p, g), p, g), p);
+    return q;
 }
 
 // ------------------------------------------------------------------------------------------------ ... with an argument list
@@ -670,11 +779,11 @@ inline size_t deep_coset_sections_len(const DeepGroups &gr, uint64_t t, uint32_t
     return s;
 }
 // 9 + 32 (2 W + 2 A + D) + len_FRI4(N, B, t) + the sections; A == 0: the plain-AIR variant
-inline size_t deep_fold4_proof_len(const smi_stark_cfg *cfg, uint32_t A, uint32_t D, uint64_t *folds) {
+inline size_t deep_fold4_proof_len(const smi_stark_cfg *cfg, uint32_t A, uint32_t D, uint64_t *folds, uint32_t S = 2) {
     const uint32_t W = cfg->n_cols, log_N = cfg->log_n + cfg->log_blowup;
     const FriFold4Layout lay = fri_layout_fold4(deep_fri_cfg(cfg, 1));
     if (folds) *folds = lay.F;
-    return 9 + 32 * (2 * (size_t)W + 2 * (size_t)A + D) + lay.proof_len + deep_coset_sections_len(deep_groups(W, A, D), cfg->num_colinearity_tests, log_N);
+    return 9 + 32 * ((size_t)S * W + 2 * (size_t)A + D) + lay.proof_len + deep_coset_sections_len(deep_groups(W, A, D), cfg->num_colinearity_tests, log_N);
 }
 
 enum { DEEP_COSET_OK = 0, DEEP_COSET_LENGTH = 1, DEEP_COSET_RECORD = 2, DEEP_COSET_PATH = 3 };
@@ -711,7 +820,7 @@ inline int deep_coset_parse(const uint8_t *sec, size_t len, const DeepGroups &gr
 // column c at point j = value 4 c + j) against the layer-0 coset record of FRI (coordinate e at point j = value 4 e + j).
 // Point by point through deep_q_at / deep_args_q_at.
 inline bool deep_coset_q_matches(uint32_t p, uint32_t g, uint32_t W, uint32_t A, uint32_t D, uint32_t w_n, uint32_t x_a, uint32_t iota, const FqH &z,
-                                 const uint64_t *ood, const uint64_t *gammas, const uint64_t *const rec[3], const uint64_t coset[16]) {
+                                 const uint64_t *ood, const uint64_t *gammas, const uint64_t *const rec[3], const uint64_t coset[16], uint32_t S = 2) {
     const DeepGroups gr = deep_groups(W, A, D);
     std::vector<uint64_t> row[3];
     uint32_t x = x_a;
@@ -721,7 +830,7 @@ inline bool deep_coset_q_matches(uint32_t p, uint32_t g, uint32_t W, uint32_t A,
             for (uint32_t c = 0; c < gr.V[k]; c++) row[k][c] = rec[k][4 * (size_t)c + j];
         }
         const FqH q = A ? deep_args_q_at(p, g, W, A, D, w_n, x, z, ood, gammas, row[0].data(), row[1].data(), row[2].data())
-                        : deep_q_at(p, g, W, D, w_n, x, z, ood, gammas, row[0].data(), row[1].data());
+                        : deep_q_at(p, g, W, D, w_n, x, z, ood, gammas, row[0].data(), row[1].data(), S);
         for (uint32_t e = 0; e < 4; e++)
             if (q.c[e] != coset[4 * e + j]) return false;
         x = host_mulmod(x, iota, p);

@@ -39,9 +39,9 @@ bool emu_periodic_tables(uint64_t p, uint64_t g, const AirPeriodic &P, std::vect
     return true;
 }
 
-template <int P>
+template <int P, bool WIN = false>
 void emu_tiles(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, const AirTile &tl, uint32_t *out) {
-    const uint32_t B = 1u << A.log_B, pitch = tl.T + B;
+    const uint32_t B = 1u << A.log_B, pitch = tl.T + (A.S - 1) * B;
     std::vector<uint32_t> tile((size_t)(A.W + A.Q) * pitch);
     const uint32_t step_m = mont_pow(A.omega_m, tl.threads, F);
     for (uint64_t base = 0; base < A.N; base += tl.T) {
@@ -50,14 +50,14 @@ void emu_tiles(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t
         for (uint32_t j = 0; j < A.Q; j++)
             for (uint32_t e = 0; e < pitch; e++) tile[(size_t)(A.W + j) * pitch + e] = A.ptab[A.pofs[j] + ((uint32_t)(base + e) & ((1u << A.plog[j]) - 1u))];
         const uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, base, F), F);
-        for (uint32_t tid = 0; tid < tl.threads; tid++) air_tile_thread<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out);
+        for (uint32_t tid = 0; tid < tl.threads; tid++) air_tile_thread<P, WIN>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out);
     }
 }
 
-template <int P>
+template <int P, bool WIN = false>
 void emu_tiles_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint32_t *cols, uint64_t stride, const AirTile &tl, uint32_t *out,
                    uint64_t out_stride) {
-    const uint32_t B = 1u << A.log_B, pitch = tl.T + B;
+    const uint32_t B = 1u << A.log_B, pitch = tl.T + (A.S - 1) * B;
     std::vector<uint32_t> tile((size_t)(A.W + A.Q) * pitch);
     const uint32_t step_m = mont_pow(A.omega_m, tl.threads, F);
     for (uint64_t base = 0; base < A.N; base += tl.T) {
@@ -67,7 +67,7 @@ void emu_tiles_ext(const AirDev &A, const Fp &F, const uint32_t *w_m, const uint
             for (uint32_t e = 0; e < pitch; e++) tile[(size_t)(A.W + j) * pitch + e] = A.ptab[A.pofs[j] + ((uint32_t)(base + e) & ((1u << A.plog[j]) - 1u))];
         const uint32_t xbase_m = mont_mul(A.h_m, mont_pow(A.omega_m, base, F), F);
         for (uint32_t tid = 0; tid < tl.threads; tid++)
-            air_tile_thread_ext<P>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out, out_stride);
+            air_tile_thread_ext<P, WIN>(A, F, w_m, tile.data(), tl.T, tl.threads, base, xbase_m, step_m, tid, out, out_stride);
     }
 }
 }  // namespace
@@ -77,7 +77,7 @@ extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg,
     FieldSetup fs;
     if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
     std::string why;
-    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why);
+    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why, false, false, SMI_AIR_MAX_WINDOW);
     if (rc != SMI_OK) return rc;
     const uint32_t log_N = cfg->log_n + cfg->log_blowup;
     if (log_N > fs.K) return SMI_ERR_UNSUPPORTED_PRIME;
@@ -90,8 +90,16 @@ extern "C" int emu_air_compose(uint64_t p, uint64_t g, const smi_stark_cfg *cfg,
     if (stride < A.N) return SMI_ERR_BAD_ARG;
     std::vector<uint32_t> w_m(A.W + A.K);
     for (uint32_t i = 0; i < A.W + A.K; i++) w_m[i] = to_mont_u64(weights[i], fs.F);
-    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N);
+    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N, 1, A.S);
     if (force_direct || (stride & 3)) tl.T = 0;
+    if (A.S > 2) {   // the WIN = true instantiations the launcher picks for a window
+        if (!tl.T)
+            for (uint64_t i = 0; i < A.N; i++) air_direct_point<true>(A, fs.F, w_m.data(), lde, stride, i, out);
+        else if (tl.P == 4) emu_tiles<4, true>(A, fs.F, w_m.data(), lde, stride, tl, out);
+        else if (tl.P == 2) emu_tiles<2, true>(A, fs.F, w_m.data(), lde, stride, tl, out);
+        else emu_tiles<1, true>(A, fs.F, w_m.data(), lde, stride, tl, out);
+        return SMI_OK;
+    }
     if (!tl.T)
         for (uint64_t i = 0; i < A.N; i++) air_direct_point(A, fs.F, w_m.data(), lde, stride, i, out);
     else if (tl.P == 4) emu_tiles<4>(A, fs.F, w_m.data(), lde, stride, tl, out);
@@ -107,7 +115,7 @@ extern "C" int emu_air_compose_ext(uint64_t p, uint64_t g, const smi_stark_cfg *
     FieldSetup fs;
     if (!field_setup(p, g, &fs)) return SMI_ERR_UNSUPPORTED_PRIME;
     std::string why;
-    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why);
+    const int rc = air_validate(p, cfg, air, nullptr, nullptr, &why, false, false, SMI_AIR_MAX_WINDOW);
     if (rc != SMI_OK) return rc;
     const uint32_t log_N = cfg->log_n + cfg->log_blowup;
     if (log_N > fs.K) return SMI_ERR_UNSUPPORTED_PRIME;
@@ -120,8 +128,16 @@ extern "C" int emu_air_compose_ext(uint64_t p, uint64_t g, const smi_stark_cfg *
     if (stride < A.N || out_stride < A.N) return SMI_ERR_BAD_ARG;
     std::vector<uint32_t> w_m(4 * AIR_MAX_WEIGHTS, 0);
     for (uint32_t i = 0; i < 4 * (A.W + A.K); i++) w_m[(i & 3) * AIR_MAX_WEIGHTS + (i >> 2)] = to_mont_u64(weights[i], fs.F);
-    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N, 4);
+    AirTile tl = air_tile(A.W + A.Q, 1ull << A.log_B, A.N, 4, A.S);
     if (force_direct || (stride & 3)) tl.T = 0;
+    if (A.S > 2) {
+        if (!tl.T)
+            for (uint64_t i = 0; i < A.N; i++) air_direct_point_ext<true>(A, fs.F, w_m.data(), lde, stride, i, out, out_stride);
+        else if (tl.P == 4) emu_tiles_ext<4, true>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
+        else if (tl.P == 2) emu_tiles_ext<2, true>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
+        else emu_tiles_ext<1, true>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
+        return SMI_OK;
+    }
     if (!tl.T)
         for (uint64_t i = 0; i < A.N; i++) air_direct_point_ext(A, fs.F, w_m.data(), lde, stride, i, out, out_stride);
     else if (tl.P == 4) emu_tiles_ext<4>(A, fs.F, w_m.data(), lde, stride, tl, out, out_stride);
@@ -137,7 +153,7 @@ extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, ui
     cfg.n_cols = n_cols;
     cfg.log_n = log_n;
     std::string why;
-    const int rc = air_validate(p, &cfg, air, nullptr, nullptr, &why, true);
+    const int rc = air_validate(p, &cfg, air, nullptr, nullptr, &why, true, false, SMI_AIR_MAX_WINDOW);
     if (rc != SMI_OK) return rc;
     const Fp F = fp_make((uint32_t)p);
     AirHost H;
@@ -149,10 +165,10 @@ extern "C" int emu_air_check(uint64_t p, const smi_air *air, uint32_t n_cols, ui
     for (uint64_t i = 0; i < n || i < air->n_boundary; i++) {
         if (i < air->n_boundary && trace[air->boundary_col[i] * n + air->boundary_row[i]] != air->boundary_value[i])
             take((i << 32) | air->boundary_row[i]);
-        if (i + 1 < n)
+        if (i + H.dev.S <= n)
             for (uint32_t k = 0; k < H.dev.K; k++)
                 if (air_constraint(H.dev, F, k, [&](uint32_t var) {
-                        return air_mem_operand(H.dev, var, i, [&](uint32_t c) { return trace[c * n + i]; }, [&](uint32_t c) { return trace[c * n + i + 1]; });
+                        return air_mem_operand_win(H.dev, var, i, [&](uint32_t c, uint32_t s) { return trace[c * n + i + s]; });
                     })) {
                     take((1ull << 63) | ((uint64_t)k << 32) | i);
                     break;

@@ -1273,14 +1273,14 @@ static int air_verify_deep_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const sm
                                 int *accept, uint32_t grind) {
     std::string why;
     uint32_t D = 0;
-    const int vrc = deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+    const int vrc = deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why, SMI_AIR_MAX_WINDOW);
     if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
-    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup;
+    const uint32_t W = cfg->n_cols, K = air->n_constraints, logN = cfg->log_n + cfg->log_blowup, S = air_window(air);
     SMI_TRY(domain_check(ctx, logN));
     const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
     const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    const size_t n_ood = 4 * (2 * (size_t)W + D);
+    const size_t n_ood = 4 * ((size_t)S * W + D);
     size_t end = 0;
     std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count(fc) + 1, &end);
     if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, DEEP_BAD_RECORD);
@@ -1294,7 +1294,7 @@ static int air_verify_deep_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const sm
     deep_transcript_z(tr, roots + 32, W, K, zr);
     const FqH z = fqh_of(zr, p);
     if (fqh_in_base(z)) return reject(ctx, accept, DEEP_Z_IN_BASE_FIELD);
-    deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
+    deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas, S);
     FqH lhs, rhs;
     deep_ood_sides(p, g, cfg, air, D, w_n, weights.data(), z, ood.data(), &lhs, &rhs);
     if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_INCONSISTENT);
@@ -1320,7 +1320,7 @@ static int air_verify_deep_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const sm
     for (uint64_t s = 0; s < t; s++)
         for (size_t k = 0; k < 2; k++) {
             const uint32_t x = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[R * s + k], p), p);
-            const FqH q = deep_q_at(p, g, W, D, w_n, x, z, ood.data(), gammas.data(), &rows[0][(R * s + k) * W], &rows[1][(R * s + k) * 4 * D]);
+            const FqH q = deep_q_at(p, g, W, D, w_n, x, z, ood.data(), gammas.data(), &rows[0][(R * s + k) * W], &rows[1][(R * s + k) * 4 * D], S);
             for (uint32_t e = 0; e < 4; e++)
                 if (q.c[e] != ab[(2 * s + k) * 4 + e]) return reject(ctx, accept, say.composition);
         }
@@ -1439,19 +1439,21 @@ static int air_verify_deep_fold4_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, co
                                       const uint8_t *proof, size_t proof_len, int *accept, uint32_t grind) {
     std::string why;
     uint32_t D = 0;
-    const int vrc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why) : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why);
+    const int vrc = xargs ? deep_xargs_plan(ctx->fs.F.p, cfg, air, xargs, nullptr, &D, &why)
+                          : deep_plan(ctx->fs.F.p, cfg, air, nullptr, &D, &why, SMI_AIR_MAX_WINDOW);
     if (vrc != SMI_OK) return smi_fail(ctx, vrc, why.c_str());
     if (xargs) {
         const int prc = xargs_periodic_check(ctx->fs.F.p, air, cfg->log_n, &why);
         if (prc != SMI_OK) return smi_fail(ctx, prc, why.c_str());
     }
     const uint32_t W = cfg->n_cols, K = air->n_constraints, A = xargs ? xargs->count : 0, logN = cfg->log_n + cfg->log_blowup;
+    const uint32_t S = xargs ? 2 : air_window(air);   // a list is refused above when its AIR has a wider window
     const uint64_t NW = (uint64_t)W + K + 2 * (uint64_t)A;
     SMI_TRY(domain_check(ctx, logN));
     const uint32_t p = ctx->fs.F.p, g = ctx->fs.g, w_n = h_root(ctx, cfg->log_n);
     const uint64_t N = 1ull << logN, t = cfg->num_colinearity_tests;
     const smi_fri_cfg fc = trace_fri_cfg(ctx, cfg, 1ull << cfg->log_blowup);
-    const size_t n_ood = deep_args_record(W, A, D);
+    const size_t n_ood = deep_args_record(W, A, D) + 4 * (size_t)(S - 2) * W;
     size_t end = 0;
     std::vector<Obj> objs = parse(proof, proof_len, 1 + fri_object_count_fold4(fc), &end);
     if (objs.empty() || objs[0].tag != 2 || objs[0].count != n_ood) return reject(ctx, accept, DEEP_BAD_RECORD);
@@ -1477,7 +1479,7 @@ static int air_verify_deep_fold4_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, co
         deep_xargs_ood_sides(p, g, cfg, air, xargs, D, w_n, ch.data(), weights.data(), z, ood.data(), &lhs, &rhs);
         if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_ARGS_INCONSISTENT);
     } else {
-        deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas);
+        deep_transcript_gammas(tr, ood.data(), W, K, D, &gammas, S);
         deep_ood_sides(p, g, cfg, air, D, w_n, weights.data(), z, ood.data(), &lhs, &rhs);
         if (!fqh_eq(lhs, rhs)) return reject(ctx, accept, DEEP_INCONSISTENT);
     }
@@ -1510,7 +1512,7 @@ static int air_verify_deep_fold4_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, co
         const uint64_t *rec[3] = {nullptr, nullptr, nullptr};
         for (uint32_t k = 0; k < gr.G; k++) rec[k] = &vals[k][s * 4 * (size_t)gr.V[k]];
         const uint32_t x_a = (uint32_t)mulm(cfg->lde_offset, powm(fc.omega, pos[s], p), p);
-        if (!deep_coset_q_matches(p, g, W, A, D, w_n, x_a, iota, z, ood.data(), gammas.data(), rec, &coset[16 * s])) return reject(ctx, accept, say.composition);
+        if (!deep_coset_q_matches(p, g, W, A, D, w_n, x_a, iota, z, ood.data(), gammas.data(), rec, &coset[16 * s], S)) return reject(ctx, accept, say.composition);
     }
     *accept = 1;
     return SMI_OK;

@@ -251,7 +251,7 @@ inline int zk_derive_air(uint64_t p64, uint32_t w_n, const smi_stark_cfg *cfg, c
     a.constraint_first_term = Z->cft.data(), a.term_coeff = Z->coeff.data(), a.term_first_factor = Z->tff.data();
     a.factor_var = Z->var.data(), a.factor_exp = Z->exp.data();
     a.boundary_col = Z->bcol.data(), a.boundary_row = Z->brow.data(), a.boundary_value = Z->bval.data();
-    a.n_periodic = Q + extra, a.reserved0 = 0;
+    a.n_periodic = Q + extra, a.window = 0;
     a.periodic_log_period = Z->plog.data(), a.periodic_value = Z->pval.data();
     return SMI_OK;
 }

@@ -518,6 +518,17 @@ class Engine:
     def _air(self, air):
         return air if isinstance(air, _lib.Air) else air.flatten(self.p)
 
+    @staticmethod
+    def _window(a):
+        """the transition window S of a flattened AIR (include/stark_mi.h, "AIR: transition windows"); 0 reads as 2"""
+        return a.window or 2
+
+    def _check_window(self, a, who, deep, deep_args, zk):
+        """an AIR with a window above two rows is proven and verified by the plain DEEP variants only"""
+        if self._window(a) > 2 and (not deep or deep_args or (zk is not None and zk is not False)):
+            raise ValueError(f"{who}: an AIR with a transition window of {self._window(a)} rows takes deep=True (row or coset leaves) only: "
+                             "no argument list, no zero knowledge, none of the provers that open next rows")
+
     def _stark_cfg(self, n_cols, log_n, log_blowup, num_colinearity_tests=0, trace_offset=1, lde_offset=None, row_leaves=False):
         return _lib.StarkCfg(log_n, log_blowup, n_cols, 1 if row_leaves else 0, trace_offset, self.g if lde_offset is None else lde_offset,
                              num_colinearity_tests, 1)
@@ -733,6 +744,17 @@ class Engine:
         self._ck(self.L.smi_dev_poly_eval_ext(self.h, vp(d_coeffs), n_cols, n_coeffs, n_coeffs if stride is None else stride, arr, P, out))
         return [[[int(out[4 * (c * P + k) + e]) for e in range(4)] for k in range(P)] for c in range(n_cols)]
 
+    def dev_poly_eval_ext_shifts(self, d_coeffs, n_cols, n_coeffs, z, w, n_shifts, stride=None):
+        """smi_dev_poly_eval_ext_shifts: the columns of dev_poly_eval_ext at z, z w, .. z w^(n_shifts - 1) (z: four canonical
+        coordinates, w: a canonical base-field element, n_shifts in 1 .. 4) -> [[[c0..c3] per shift] per column]"""
+        if len(z) != 4:
+            raise ValueError("dev_poly_eval_ext_shifts: z has four coordinates")
+        za = (C.c_uint64 * 4)(*[int(v) for v in z])
+        out = (C.c_uint64 * (4 * n_cols * max(int(n_shifts), 1)))()
+        self._ck(self.L.smi_dev_poly_eval_ext_shifts(self.h, vp(d_coeffs), n_cols, n_coeffs, n_coeffs if stride is None else stride, za, int(w), n_shifts, out))
+        S = n_shifts
+        return [[[int(out[4 * (c * S + k) + e]) for e in range(4)] for k in range(S)] for c in range(n_cols)]
+
     def dev_deep_compose(self, d_lde, d_seg, n_cols, n_segments, log_n, log_blowup, z, ood, challenges, d_out, stride=None, seg_stride=None,
                          out_stride=None, lde_offset=None):
         """smi_dev_deep_compose: the DEEP codeword of n_cols extended columns and 4 n_segments segment columns under z (four
@@ -745,6 +767,18 @@ class Engine:
         self._ck(self.L.smi_dev_deep_compose(self.h, C.byref(cfg), n_segments, vp(d_lde), N if stride is None else stride, vp(d_seg),
                                              N if seg_stride is None else seg_stride, za, oa, ca, vp(d_out), N if out_stride is None else out_stride))
 
+    def dev_deep_compose_window(self, window, d_lde, d_seg, n_cols, n_segments, log_n, log_blowup, z, ood, challenges, d_out, stride=None,
+                                seg_stride=None, out_stride=None, lde_offset=None):
+        """smi_dev_deep_compose_window: dev_deep_compose under a window of S = window rows; ood and challenges hold 4 (S W + D)
+        values, u_{s,c} s-major, then s_j"""
+        cfg = self._stark_cfg(n_cols, log_n, log_blowup, 0, 1, lde_offset, True)
+        N, cnt = 1 << (log_n + log_blowup), 4 * (int(window) * n_cols + n_segments)
+        if len(z) != 4 or len(ood) != cnt or len(challenges) != cnt:
+            raise ValueError("dev_deep_compose_window: z has 4 coordinates, ood and challenges 4 (S W + D) values")
+        za, oa, ca = (C.c_uint64 * 4)(*[int(v) for v in z]), (C.c_uint64 * cnt)(*[int(v) for v in ood]), (C.c_uint64 * cnt)(*[int(v) for v in challenges])
+        self._ck(self.L.smi_dev_deep_compose_window(self.h, C.byref(cfg), window, n_segments, vp(d_lde), N if stride is None else stride, vp(d_seg),
+                                                    N if seg_stride is None else seg_stride, za, oa, ca, vp(d_out), N if out_stride is None else out_stride))
+
     def _dev_air_prove_deep(self, a, d_trace_cols, n_cols, log_n, log_blowup, t, trace_offset, lde_offset, timed, check, row_leaves, ext, grind_bits,
                             fill_multiplicities, folding, coset_leaves=False):
         self._check_deep(a, row_leaves, ext, folding, fill_multiplicities)
@@ -755,7 +789,8 @@ class Engine:
             if not ok:
                 raise StarkMiError(-50, why)
         roots = np.zeros((2, 32), dtype=np.uint8)
-        ood = np.zeros(4 * (2 * n_cols + D), dtype=np.uint64)
+        S = self._window(a)
+        ood = np.zeros(4 * (S * n_cols + D), dtype=np.uint64)
         proof, plen = vp(), C.c_size_t()
         top = np.zeros(max(t, 1), dtype=np.uint64)
         stage = (C.c_double * 7)()
@@ -765,7 +800,7 @@ class Engine:
         b = C.string_at(proof, plen.value)
         self.L.smi_free(proof)
         out = {"column_roots": roots, "proof": b, "top_indices": [int(v) for v in top[:t]],
-               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(2 * n_cols + D)]}
+               "ood": [[int(v) for v in ood[4 * i:4 * i + 4]] for i in range(S * n_cols + D)]}
         if timed:
             out["stage_ms"] = dict(zip(("lde", "commit", "compose", "segments", "ood", "fri", "open"), [float(x) for x in stage]))
         return out
@@ -1060,6 +1095,7 @@ class Engine:
         elements; stage_ms has ten stages; fill_multiplicities=True counts over the active rows only
         (smi_dev_xargs_multiplicities_rows)."""
         a = self._air(air)
+        self._check_window(a, "dev_air_prove", deep, deep_args, zk)
         if zk is not None and zk is not False:
             if self._zk_takes_a_list(a, deep, deep_args, coset_leaves):
                 self._check_coset_leaves(row_leaves, ext, deep, deep_args)
@@ -1239,6 +1275,7 @@ class Engine:
         deep_args=True: smi_air_verify_deep_xargs, under the conditions of dev_air_prove(deep_args=True); three roots.
         coset_leaves=True: smi_air_verify_deep_fold4 / smi_air_verify_deep_xargs_fold4, under the conditions of
         dev_air_prove(coset_leaves=True); folding stays 2."""
+        self._check_window(self._air(air), "air_verify", deep, deep_args, zk)
         zk_list = bool(zk) and self._zk_takes_a_list(self._air(air), deep, deep_args, coset_leaves)
         if zk and not zk_list and (not (deep and coset_leaves) or deep_args):
             raise ValueError("zk runs over the coset-leaf DEEP proof of a plain AIR (deep=True, coset_leaves=True) or of an AIR with an argument "

@@ -800,6 +800,15 @@ class Air:
     ("per", j[, exponent]) is periodic column j at this row, ("per_next", j[, exponent]) at the next row.  Factors are
     kept symbolic until they are used, so periodic columns may be declared before or after the constraints.
 
+    A constraint may read up to four consecutive rows (include/stark_mi.h, "AIR: transition windows"):
+
+        air = Air(1)
+        air.transition({("row", 2, 0): 1, ("row", 1, 0): -1, ("row", 0, 0): -1})  # a[r+2] = a[r+1] + a[r] in one column
+
+    ("row", s, column[, exponent]) is the column at row r + s and ("per_row", s, j[, exponent]) periodic column j there, s = 0 .. 3;
+    "cur" / "next" / "per" / "per_next" are s = 0 and 1.  Air.window is 2, or 1 + the largest s used; such an AIR holds on
+    the windows that start at rows 0 .. n - window and is proven by the plain DEEP provers (Engine.dev_air_prove(deep=True)).
+
     A permutation argument (include/stark_mi.h, "Permutation argument"; one per AIR) claims that two lists of row tuples
     are equal as multisets over all rows:
 
@@ -841,14 +850,35 @@ class Air:
                                 # selectors two more entries (a_sel, b_sel); a member is an int or ("per", j).  A shared
                                 # lookup is ("lookups", [columns_0, ..], table columns, multiplicity column, [sel_0, ..], table_sel)
 
+    MAX_WINDOW = 4          # SMI_AIR_MAX_WINDOW
+
+    @staticmethod
+    def _shift(kind):
+        """the row shift s of a stored factor kind: "cur" / "per" 0, "next" / "per_next" 1, ("row", s) / ("per_row", s) s"""
+        return kind[1] if isinstance(kind, tuple) else (1 if kind in ("next", "per_next") else 0)
+
+    @property
+    def window(self):
+        """S: the rows a constraint may read, max(2, 1 + the largest shift used)"""
+        return max([2] + [1 + self._shift(kind) for con in self._symbolic for _, factors in con for kind, _, _ in factors])
+
     @property
     def constraints(self):
-        """[[(coeff, [(var, exp), ...]), ...], ...] with the variable numbering of smi_air: col, W + col, 2W + j, 2W + Q + j"""
-        W, Q = self.n_cols, len(self.periodics)
-        base = {"cur": 0, "next": W, "per": 2 * W, "per_next": 2 * W + Q}
-        return [[(cf, [(base[kind] + idx, e) for kind, idx, e in factors]) for cf, factors in con] for con in self._symbolic]
+        """[[(coeff, [(var, exp), ...]), ...], ...] with the variable numbering of smi_air under the window S: s W + col, then
+        S W + s Q + j; for S = 2 that is col, W + col, 2W + j, 2W + Q + j"""
+        W, Q, S = self.n_cols, len(self.periodics), self.window
+
+        def var(kind, idx):
+            periodic = (kind[0] if isinstance(kind, tuple) else kind) in ("per", "per_next", "per_row")
+            return S * W + self._shift(kind) * Q + idx if periodic else self._shift(kind) * W + idx
+        return [[(cf, [(var(kind, idx), e) for kind, idx, e in factors]) for cf, factors in con] for con in self._symbolic]
 
     def _factor(self, f):
+        if f[0] in ("row", "per_row"):
+            s = int(f[1])
+            if not 0 <= s < self.MAX_WINDOW:
+                raise ValueError(f"row shift {s} is outside 0 .. {self.MAX_WINDOW - 1}")
+            return (f[0], s), int(f[2]), (f[3] if len(f) > 3 else 1)
         if f[0] not in ("cur", "next", "per", "per_next"):
             raise ValueError(f"unknown factor kind {f[0]!r}")
         return f[0], int(f[1]), (f[2] if len(f) > 2 else 1)
@@ -997,6 +1027,8 @@ class Air:
         polynomials).  The boundary points carry over; the extra columns get none."""
         out = Air(self.n_cols + len(self.periodics))
         kind = {"cur": ("cur", 0), "next": ("next", 0), "per": ("cur", self.n_cols), "per_next": ("next", self.n_cols)}
+        for s in range(self.MAX_WINDOW):
+            kind[("row", s)], kind[("per_row", s)] = (("row", s), 0), (("row", s), self.n_cols)
         out._symbolic = [[(cf, [(kind[k][0], kind[k][1] + i, e) for k, i, e in factors]) for cf, factors in con] for con in self._symbolic]
         out.boundaries = list(self.boundaries)
         return out
@@ -1068,7 +1100,8 @@ class Air:
         ptr = lambda a, t: a.ctypes.data_as(t)
         out = _lib.Air(len(self.constraints), len(coeff), len(var), len(self.boundaries), ptr(arrs[0], _lib.u32p), ptr(arrs[1], _lib.u64p),
                        ptr(arrs[2], _lib.u32p), ptr(arrs[3], _lib.u32p), ptr(arrs[4], _lib.u32p), ptr(arrs[5], _lib.u32p),
-                       ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p), len(self.periodics), 0, ptr(arrs[8], _lib.u32p), ptr(arrs[9], _lib.u64p))
+                       ptr(arrs[6], _lib.u64p), ptr(arrs[7], _lib.u64p), len(self.periodics), 0 if self.window == 2 else self.window,
+                       ptr(arrs[8], _lib.u32p), ptr(arrs[9], _lib.u64p))
         out._keep = arrs
         if self.perm is not None and self.lookup_arg is not None:
             raise ValueError("an AIR takes a permutation or a lookup, not both")
@@ -1151,16 +1184,29 @@ class Air:
             acc += m
         return acc % p
 
+    def constraint_value_window(self, k, p, rows, per_rows=()):
+        """C_k on one window: rows[s] the trace columns' values at row r + s, per_rows[s] the periodic columns' there, s < window"""
+        S = self.window
+        vals = [int(v) for s in range(S) for v in rows[s]] + [int(v) for s in range(S) for v in (per_rows[s] if per_rows else ())]
+        acc = 0
+        for cf, factors in self.constraints[k]:
+            m = cf % p
+            for v, e in factors:
+                m = m * pow(vals[v], e, p) % p
+            acc += m
+        return acc % p
+
     def first_violation(self, p, cols):
-        """(constraint, row) of the first violation on a trace in smi_dev_air_check's order, or None"""
-        n = len(cols[0])
+        """(constraint, row) of the first violation on a trace in smi_dev_air_check's order, or None; a constraint holds on
+        the windows that start at rows 0 .. n - window"""
+        n, S = len(cols[0]), self.window
         for j, (c, r, v) in enumerate(self.boundaries):
             if int(cols[c][r]) != v % p:
                 return j, r
         for k in range(len(self.constraints)):
-            for r in range(n - 1):
-                if self.constraint_value(k, p, [col[r] for col in cols], [col[r + 1] for col in cols], self.periodic_row(p, r),
-                                         self.periodic_row(p, r + 1)):
+            for r in range(n - S + 1):
+                if self.constraint_value_window(k, p, [[col[r + s] for col in cols] for s in range(S)],
+                                                [self.periodic_row(p, r + s) for s in range(S)]):
                     return len(self.boundaries) + k, r
         return None
 

@@ -1,0 +1,471 @@
+"""The checker of transition windows (include/stark_mi.h, "AIR: transition windows"), restated in Python ints and numpy over
+the CPU oracle's primitives and the helpers of tests/deep_compose.py: the window composition point by point on arrays (term_c,
+the S-row constraints with the periodic columns as extended tables, the S - 1 exemption roots), the plan rule, the record
+u_{s,c} = f_c(z w^s) and its transcript, the DEEP codeword with S denominators, both provers (row leaves with dc's FRI, coset
+leaves with fold-by-4 FRI) and both verifiers in the library's order of checks.
+Not a test module: imported by tests/test_air_window_host.py, tests/test_air_window_emu.py and tests/test_gpu_air_window.py."""
+import numpy as np
+
+import air_compose as ac
+import air_periodic as ap
+import air_rows as ar
+import deep_compose as dc
+import deep_fold4_compose as dfc
+import ext_compose as xc
+import fold4_compose as f4
+import perm_compose as pm
+import pow_compose as pc
+from stark_rs_amd.mirror import Air
+
+MAX_WINDOW = 4
+
+
+# ---------------------------------------------------------------------------------------------- the AIRs of the proof tests
+def make(name, n, p, seed=7):
+    """-> (Air, columns as lists of ints) that satisfy it on the windows starting at rows 0 .. n - S:
+    fib1  one column, a[r+2] = a[r+1] + a[r]                                        S = 3, d = 1
+    sq    one column, a[r+2] = a[r+1]^2 + a[r]                                      S = 3, d = 2 (two segments)
+    tap4  one column, a[r+3] = a[r+2] a[r+1] a[r] + k[r+3], k of period 8           S = 4, d = 3 (four segments)
+    wide  five columns, shifts mixed per column                                     S = 4, d = 2"""
+    rng = np.random.default_rng(seed)
+    if name == "fib1":
+        air, a = Air(1), [1, 1]
+        while len(a) < n:
+            a.append((a[-1] + a[-2]) % p)
+        air.boundary(0, 0, 1).boundary(0, 1, 1)
+        air.transition({("row", 2, 0): 1, ("row", 1, 0): -1, ("row", 0, 0): -1})
+        return air, [a]
+    if name == "sq":
+        air, a = Air(1), [3, 5]
+        while len(a) < n:
+            a.append((a[-1] * a[-1] + a[-2]) % p)
+        air.boundary(0, 0, 3).boundary(0, 1, 5)
+        air.transition({("row", 2, 0): 1, ("row", 1, 0, 2): -1, ("row", 0, 0): -1})
+        return air, [a]
+    if name == "tap4":
+        air = Air(1)
+        k = [int(v) for v in rng.integers(1, p, 8)]
+        j = air.periodic(k)
+        a = [2, 3, 5]
+        while len(a) < n:
+            a.append((a[-1] * a[-2] * a[-3] + k[len(a) % 8]) % p)
+        air.boundary(0, 0, 2).boundary(0, 2, 5)
+        air.transition({("row", 3, 0): 1, (("row", 2, 0), ("row", 1, 0), ("row", 0, 0)): -1, ("per_row", 3, j): -1})
+        return air, [a]
+    if name == "wide":
+        air = Air(5)
+        c0, c1 = [1, 2], [7]
+        while len(c0) < n:
+            c0.append((c0[-1] + c0[-2]) % p)
+        while len(c1) < n:
+            c1.append((c1[-1] * c0[len(c1) - 1] + 1) % p)
+        c2 = [4, 5, 6]
+        while len(c2) < n:
+            r = len(c2) - 3
+            c2.append((c2[r] + c1[r + 1]) % p)
+        c3 = [9]
+        while len(c3) < n:
+            r = len(c3) - 1
+            c3.append((c3[r] + c2[(r + 2) % n]) % p)   # rows past n - 3 lie outside every window
+        c4 = [3, 8]
+        while len(c4) < n:
+            r = len(c4) - 2
+            c4.append((c4[r] * c3[(r + 3) % n]) % p)
+        air.boundary(0, 0, 1).boundary(2, 1, 5).boundary(4, 0, 3)
+        air.transition({("row", 2, 0): 1, ("next", 0): -1, ("cur", 0): -1})
+        air.transition({("next", 1): 1, (("cur", 1), ("cur", 0)): -1, (): -1})
+        air.transition({("row", 3, 2): 1, ("row", 0, 2): -1, ("row", 1, 1): -1})
+        air.transition({("row", 1, 3): 1, ("row", 0, 3): -1, ("row", 2, 2): -1})
+        air.transition({("row", 2, 4): 1, (("row", 0, 4), ("row", 3, 3)): -1})
+        return air, [c0, c1, c2, c3, c4]
+    raise KeyError(name)
+
+
+def two_row_form(name, n, p, seed=7):
+    """sq and tap4 as a user states them without the window: copy columns b[r] = a[r+1] (and c[r] = a[r+2]) and two-row
+    constraints -> (Air, columns).  The statement over rows 0 .. n - 2 of the wider trace."""
+    air1, (a,) = make(name, n, p, seed)
+    if name == "sq":
+        air = Air(2)
+        b = a[1:] + [(a[-1] * a[-1] + a[-2]) % p]
+        air.boundary(0, 0, a[0]).boundary(1, 0, a[1])
+        air.transition({("next", 0): 1, ("cur", 1): -1})
+        air.transition({("next", 1): 1, ("cur", 1, 2): -1, ("cur", 0): -1})
+        return air, [a, b]
+    if name == "tap4":
+        k = air1.periodics[0]
+        ext = list(a)
+        while len(ext) < n + 2:
+            ext.append((ext[-1] * ext[-2] * ext[-3] + k[len(ext) % 8]) % p)
+        air = Air(3)
+        j = air.periodic(k[3:] + k[:3])   # row r holds k[r + 3]
+        air.boundary(0, 0, a[0]).boundary(2, 0, a[2])
+        air.transition({("next", 0): 1, ("cur", 1): -1})
+        air.transition({("next", 1): 1, ("cur", 2): -1})
+        air.transition({("next", 2): 1, (("cur", 2), ("cur", 1), ("cur", 0)): -1, ("per", j): -1})
+        return air, [ext[:n], ext[1:n + 1], ext[2:n + 2]]
+    raise KeyError(name)
+
+
+def synthetic(W, Q, S, d, p, n, seed=11):
+    """two constraints of degree d (1 or 2) over W random columns and Q periodic columns -- of period 2 and, with Q = 2, of
+    period n --, every shift s < S read from some column and the periodic columns read at shift S - 1.  The columns do not
+    satisfy them: the codeword is still defined point by point.  Column W - 1 holds p - 1 throughout.  -> (Air, columns)"""
+    rng = np.random.default_rng(seed + 131 * W + 17 * Q + S)
+    cols = [[int(v) for v in rng.integers(0, p, n)] for _ in range(W)]
+    cols[W - 1] = [p - 1] * n
+    air = Air(W)
+    pj = [air.periodic([int(v) for v in rng.integers(0, p, per)]) for per in ([2, n][:Q])]
+    air.boundary(0, 0, cols[0][0])
+    if W > 2:
+        air.boundary(2, n - 1, cols[2][n - 1]).boundary(2, 1, 5)
+    c0 = {("row", s, (3 * s) % W): int(rng.integers(1, p)) for s in range(S)}
+    c0[()] = 3
+    for j in pj:
+        c0[("per_row", S - 1, j)] = int(rng.integers(1, p))
+    c1 = {("row", S - 1, W - 1): 1, ("row", 0, W // 2): p - 2}
+    if d == 2:
+        c0[(("row", S - 1, W - 1), ("row", 1, 0))] = 7
+        c1[(("row", S - 2, W // 3), ("per_row", S - 1, pj[0]) if pj else ("row", 0, 0))] = 5
+    air.transition(c0).transition(c1)
+    return air, cols
+
+
+def wrapped_violations(air, p, cols):
+    """the rows r in n - S + 1 .. n - 1 at which some constraint fails on the window that wraps to row 0: the windows the
+    statement leaves out"""
+    n, S = len(cols[0]), air.window
+    out = []
+    for r in range(n - S + 1, n):
+        rows = [[col[(r + s) % n] for col in cols] for s in range(S)]
+        pers = [air.periodic_row(p, (r + s) % n) for s in range(S)]
+        if any(air.constraint_value_window(k, p, rows, pers) for k in range(len(air.constraints))):
+            out.append(r)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- plan, layout
+def segments_for(d, S, n):
+    """D: the smallest power of two >= max(1, d - 1), doubled while D n <= d (n - 1) + (S - 1) - n"""
+    D = 1
+    while D < d - 1:
+        D <<= 1
+    while D * n <= d * (n - 1) + (S - 1) - n:
+        D <<= 1
+    return D
+
+
+def plan(air, log_n):
+    """-> (d, D)"""
+    return air.degree, segments_for(air.degree, air.window, 1 << log_n)
+
+
+def air_tile(rows, B, N, weight_vecs, S):
+    """the tile air_core.h air_tile picks: T points and a halo of (S - 1) B within 64 KB next to the weights; 0: no tile"""
+    for T in (1024, 512, 256, 128, 64):
+        if T <= N and rows * (T + (S - 1) * B) * 4 + weight_vecs * 128 * 4 <= 65536:
+            return T
+    return 0
+
+
+def proof_len(o, W, D, S, log_n, lb, t, p, g, h):
+    """row leaves: dc.proof_len with S W in the record"""
+    return dc.proof_len(o, W, D, log_n, lb, t, p, g, h) + 32 * (S - 2) * W
+
+
+def fold4_layout(W, D, S, log_n, lb, t):
+    F, length = dfc.layout(W, 0, D, log_n, lb, t)
+    return F, length + 32 * (S - 2) * W
+
+
+def transcript_len(W, K, D, S):
+    return 32 * (3 + W + K + 2 * (S * W + D))
+
+
+# ---------------------------------------------------------------------------------------------- the composition
+def _horner_arr(coeffs, x, p):
+    acc = np.zeros_like(x)
+    for a in reversed(coeffs):
+        acc = (acc * x + np.uint64(int(a) % p)) % np.uint64(p)
+    return acc
+
+
+def compose(o, air, cols, weights, p, g, log_n, lb, tau, h):
+    """cw[i] for every i < N under the W + K unreduced base-field weights, from the definition: term_c(x_i), and
+    tq_k(x_i) = C_k(the S rows at i, i + B, ..) prod_{s=1..S-1} (x_i - tau w^(n-s)) / (x_i^n - tau^n); the operand of shift s
+    is the extended column (or the periodic column's extension) at index (i + s B) mod N"""
+    P = np.uint64(p)
+    n, B, N = 1 << log_n, 1 << lb, 1 << (log_n + lb)
+    W, Q, S = air.n_cols, len(air.periodics), air.window
+    w, _wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    lde = [np.asarray(c, dtype=np.uint64) for c in ac.lde(o, cols, p, g, log_n, lb, tau, h)]
+    per = [np.asarray(c, dtype=np.uint64) for c in ac.lde(o, [ap.tiled(v, n, p) for v in air.periodics], p, g, log_n, lb, tau, h)] if Q else []
+    x = dc.points(o, p, g, log_n, lb, h)
+    inv = lambda a: ap._pow_arr(a, p - 2, p)
+    acc = np.zeros(N, dtype=np.uint64)
+    for c in range(W):
+        pts = [(tau * pow(w, r, p) % p, v % p) for (cc, r, v) in air.boundaries if cc == c]
+        term = lde[c]
+        if pts:
+            interp = [int(v) for v in o.poly_interpolate_domain([r for r, _ in pts], [v for _, v in pts], p)]
+            zc = np.ones(N, dtype=np.uint64)
+            for r, _ in pts:
+                zc = zc * ((x + P - np.uint64(r)) % P) % P
+            term = (lde[c] + P - _horner_arr(interp, x, p)) % P * inv(zc) % P
+        acc = (acc + term * np.uint64(weights[c] % p)) % P
+    if air.constraints:
+        ops = [np.roll(lde[c], -s * B) for s in range(S) for c in range(W)] + [np.roll(per[j], -s * B) for s in range(S) for j in range(Q)]
+        zt = inv((ap._pow_arr(x, n, p) + P - np.uint64(pow(tau, n, p))) % P)
+        for s in range(1, S):
+            zt = zt * ((x + P - np.uint64(tau * pow(w, n - s, p) % p)) % P) % P
+        for k, con in enumerate(air.constraints):
+            ck = np.zeros(N, dtype=np.uint64)
+            for cf, factors in con:
+                m = np.full(N, cf % p, dtype=np.uint64)
+                for v, e in factors:
+                    m = m * ap._pow_arr(ops[v], e, p) % P
+                ck = (ck + m) % P
+            acc = (acc + ck * zt % P * np.uint64(weights[W + k] % p)) % P
+    return acc
+
+
+def compose_ext(o, air, cols, ch, p, g, log_n, lb, tau, h):
+    """H as four coordinate codewords under the 4 (W + K) challenges: coordinate e is compose under the weight vector e"""
+    return np.stack([compose(o, air, cols, xc.weight_vector(ch, e), p, g, log_n, lb, tau, h) for e in range(4)])
+
+
+# ---------------------------------------------------------------------------------------------- record, codeword
+def shifts_of(z, w, S, p):
+    out = [[int(c) % p for c in z]]
+    for _ in range(1, S):
+        out.append(dc.scale_q(out[-1], w, p))
+    return out
+
+
+def ood_values(o, cols, hc, D, S, z, p, g, log_n, tau):
+    """u_{s,c} s-major, then s_j: 4 (S W + D) canonical values"""
+    n = 1 << log_n
+    w = o.ff_prim_nth_root_g(n, p, g)
+    polys = np.stack([np.asarray(o.fast_intt(np.array(c, dtype=np.uint64), w, tau, p), dtype=np.uint64) for c in cols])
+    u = [el for zs in shifts_of(z, w, S, p) for el in dc.eval_cols(polys, zs, p, g)]
+    s = [dc.horner([[int(hc[e, j * n + i]) for e in range(4)] for i in range(n)], z, p, g) for j in range(D)]
+    return [c for el in u + s for c in el]
+
+
+def q_codeword(lde, seg, x, z, ood, ch, w_n, S, p, g):
+    """Q as a (4, N) array: sum_s sum_c gamma_{s,c} (f_c - u_{s,c}) / (x - z w^s) + sum_j gamma''_j (H_j - s_j) / (x - z)"""
+    lde, seg = np.asarray(lde, dtype=np.uint64), np.asarray(seg, dtype=np.uint64)
+    W, D, N, P = lde.shape[0], seg.shape[0] // 4, lde.shape[1], np.uint64(p)
+    el = lambda v, i: [int(c) % p for c in v[4 * i:4 * i + 4]]
+    zero = np.zeros(N, dtype=np.uint64)
+    minus = lambda vals, e4: np.stack([(vals[e] + P - np.uint64(e4[e])) % P for e in range(4)])
+    xs = [np.asarray(x, dtype=np.uint64), zero, zero, zero]
+    Q = np.zeros((4, N), dtype=np.uint64)
+    for s, zs in enumerate(shifts_of(z, w_n, S, p)):
+        num = np.zeros((4, N), dtype=np.uint64)
+        for c in range(W):
+            num = (num + dc._mul_const(minus([lde[c], zero, zero, zero], el(ood, s * W + c)), el(ch, s * W + c), p, g)) % P
+        if s == 0:
+            for j in range(D):
+                num = (num + dc._mul_const(minus(seg[4 * j:4 * j + 4], el(ood, S * W + j)), el(ch, S * W + j), p, g)) % P
+        Q = (Q + pm.mul_vec(num, dc.inv_vec(minus(xs, zs), p, g), p, g)) % P
+    return Q
+
+
+def q_at(trow, srow, x, z, ood, ch, w_n, S, p, g):
+    """Q(x) from one trace row and one segment row, Python ints"""
+    W, D = len(trow), len(srow) // 4
+    el = lambda v, i: [int(c) % p for c in v[4 * i:4 * i + 4]]
+    q = [0] * 4
+    for s, zs in enumerate(shifts_of(z, w_n, S, p)):
+        num = [0] * 4
+        for c in range(W):
+            num = xc.add(num, xc.mul(el(ch, s * W + c), xc.sub(xc.embed(int(trow[c]), p), el(ood, s * W + c), p), p, g), p)
+        if s == 0:
+            for j in range(D):
+                num = xc.add(num, xc.mul(el(ch, S * W + j), xc.sub(el(srow, j), el(ood, S * W + j), p), p, g), p)
+        q = xc.add(q, xc.mul(num, xc.inv(xc.sub(xc.embed(x, p), zs, p), p, g), p, g), p)
+    return q
+
+
+def ood_sides(o, air, W, D, weights, z, ood, p, g, log_n, tau):
+    """-> (sum_c w_c term_c(z) + sum_k w_{W+k} tq_k(z), sum_j z^(j n) s_j) under the AIR's window"""
+    n, K, S, Q = 1 << log_n, len(air.constraints), air.window, len(air.periodics)
+    w = o.ff_prim_nth_root_g(n, p, g)
+    el = lambda v, i: [int(c) % p for c in v[4 * i:4 * i + 4]]
+    u = [el(ood, i) for i in range(S * W)]
+    s = [el(ood, S * W + j) for j in range(D)]
+    acc = [0] * 4
+    for c in range(W):
+        pts = [(tau * pow(w, r, p) % p, val % p) for (cc, r, val) in air.boundaries if cc == c]
+        term = u[c]
+        if pts:
+            interp = [int(x) for x in o.poly_interpolate_domain([r for r, _ in pts], [val for _, val in pts], p)]
+            zc = xc.embed(1, p)
+            for r, _ in pts:
+                zc = xc.mul(zc, xc.sub(z, xc.embed(r, p), p), p, g)
+            term = xc.mul(xc.sub(u[c], dc.horner(interp, z, p, g), p), xc.inv(zc, p, g), p, g)
+        acc = xc.add(acc, xc.mul(el(weights, c), term, p, g), p)
+    if K:
+        X = list(u)
+        for zs in shifts_of(z, w, S, p):
+            X += dc.periodic_q(o, air, zs, p, g, log_n, tau, w) if Q else []
+        zt = xc.inv(xc.sub(xc.power(z, n, p, g), xc.embed(pow(tau, n, p), p), p), p, g)
+        for sh in range(1, S):
+            zt = xc.mul(zt, xc.sub(z, xc.embed(tau * pow(w, n - sh, p) % p, p), p), p, g)
+        for k in range(K):
+            acc = xc.add(acc, xc.mul(el(weights, W + k), xc.mul(dc.constraint_q(air, k, X, p, g), zt, p, g), p, g), p)
+    rhs, zn, pw = [0] * 4, xc.power(z, n, p, g), xc.embed(1, p)
+    for j in range(D):
+        rhs = xc.add(rhs, xc.mul(pw, s[j], p, g), p)
+        pw = xc.mul(pw, zn, p, g)
+    return acc, rhs
+
+
+# ---------------------------------------------------------------------------------------------- the provers
+def prove(o, air, cols, p, g, log_n, lb, t, tau, h, bits=0, cosets=False, honest=True, record_air=None):
+    """-> dict(roots, proof, top, ood, z, gammas, H, seg, Q, lde) of smi_dev_air_prove_deep (cosets: ..._deep_fold4) for an
+    AIR of any window.  honest=False skips the degree assertion (a trace that breaks a window).  record_air: the AIR whose
+    window and plan shape the record (a proof made under another statement)"""
+    N, B = 1 << (log_n + lb), 1 << lb
+    W, K, S = len(cols), len(air.constraints), air.window
+    _d, D = plan(air, log_n)
+    assert D <= B and B >= 4 and 4 * D <= 64
+    w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    lde = [np.asarray(c, dtype=np.uint64) for c in ac.lde(o, cols, p, g, log_n, lb, tau, h)]
+    nodes1 = dfc.coset_tree(o, lde, N) if cosets else o.merkle_new(ar.row_leaves(o, lde))
+    root1 = bytes(nodes1[-1])
+    tr, ch = xc.air_transcript(o, W, K, root1)
+    tr = bytearray(tr)
+    H = compose_ext(o, air, cols, ch, p, g, log_n, lb, tau, h)
+    hc, seg = dc.segments(o, H, D, p, g, log_n, lb, h)
+    assert not honest or not hc[:, D << log_n:].any(), "the composition has coefficients at or above D n"
+    nodes2 = dfc.coset_tree(o, list(seg), N) if cosets else o.merkle_new(ar.row_leaves(o, list(seg)))
+    root2 = bytes(nodes2[-1])
+    tr += root2
+    z = [c % p for c in dc.draw(o, tr, 4 * (W + K), 4)]
+    assert any(z[1:]), "z lies in the base field"
+    ood = ood_values(o, cols, hc, D, S, z, p, g, log_n, tau)
+    record = xc._elems(ood)
+    tr += record[9:]
+    gammas = dc.draw(o, tr, 4 * (W + K) + 4, 4 * (S * W + D))
+    assert len(tr) == transcript_len(W, K, D, S)
+    Q = q_codeword(lde, seg, dc.points(o, p, g, log_n, lb, h), z, ood, gammas, w, S, p, g)
+    cfg_o = o.fri_cfg(wN, h, N, B, t, p)
+    if cosets:
+        fri, top, _nonce = f4.prove(o, cfg_o, Q, g, bytes(tr), bits)
+        tail = dfc.section(o, lde, nodes1, top, N) + dfc.section(o, list(seg), nodes2, top, N)
+    else:
+        fri, top, _nonce = pc.prove(o, cfg_o, Q, g, bytes(tr), bits)
+        tail = ar.openings_bytes(o, lde, top, N, B, False, nodes1) + ar.openings_bytes(o, list(seg), top, N, B, False, nodes2)
+    return {"roots": [root1, root2], "proof": record + fri + tail, "top": top, "ood": ood, "z": z, "gammas": gammas, "H": H, "seg": seg, "Q": Q,
+            "lde": lde, "fri_at": len(record), "tail_at": len(record) + len(fri)}
+
+
+# ---------------------------------------------------------------------------------------------- the verifiers
+def verify(o, air, proof, roots, p, g, W, log_n, lb, t, tau, h, bits=0, cosets=False):
+    """-> (accept, sentence or keyword class) of smi_air_verify_deep / smi_air_verify_deep_fold4 in their order.  Row leaves:
+    the reason classes of dc.verify (dc.keyword maps them to the library's sentences); coset leaves: the sentences of dfc."""
+    N, B, log_N, K, S = 1 << (log_n + lb), 1 << lb, log_n + lb, len(air.constraints), air.window
+    _d, D = plan(air, log_n)
+    w, wN = ac.roots_of_unity(o, p, g, log_n, lb)
+    say = dfc.FRONT if cosets else {k: k for k in ("record", "record canonical", "base field", "consistency", "no layer")}
+    cnt = 4 * (S * W + D)
+    obj = xc._pop(proof, 0)
+    if obj is None or obj[0] != 2 or len(obj[1]) != cnt:
+        return False, say["record"]
+    ood, at = obj[1], obj[2]
+    if any(v >= p for v in ood):
+        return False, say["record canonical"]
+    tr, weights = xc.air_transcript(o, W, K, bytes(roots[0]))
+    tr = bytearray(tr) + bytes(roots[1])
+    z = [c % p for c in dc.draw(o, tr, 4 * (W + K), 4)]
+    if not any(z[1:]):
+        return False, say["base field"]
+    tr += proof[9:at]
+    gammas = dc.draw(o, tr, 4 * (W + K) + 4, cnt)
+    lhs, rhs = ood_sides(o, air, W, D, weights, z, ood, p, g, log_n, tau)
+    if lhs != rhs:
+        return False, say["consistency"]
+    cfg_o = o.fri_cfg(wN, h, N, B, t, p)
+    widths = [W, 4 * D]
+    if cosets:
+        if dfc.folds(log_n, lb, t) == 0:
+            return False, say["no layer"]
+        ok, pv, used, top, why = f4.verify(o, cfg_o, proof[at:], g, bytes(tr), bits)
+        if not ok:
+            return False, why
+        words = dfc.WORDS
+        rest = proof[at + used:]
+        if len(rest) != sum(dfc.section_len(V, t, log_N) for V in widths):
+            return False, words["length"]
+        q, depth = N // 4, log_N - 2
+        recs, paths, off = [], [], 0
+        for V in widths:
+            rec, prec = 9 + 32 * V, 9 + 32 * depth
+            rs, ps = [], []
+            for s in range(t):
+                r = rest[off + s * rec:off + (s + 1) * rec]
+                if r[0] != 2 or int.from_bytes(r[1:9], "little") != 4 * V:
+                    return False, words["record"]
+                rs.append([int.from_bytes(r[9 + 8 * i:17 + 8 * i], "little") for i in range(4 * V)])
+            for s in range(t):
+                r = rest[off + t * rec + s * prec:off + t * rec + (s + 1) * prec]
+                if r[0] != 3 or int.from_bytes(r[1:9], "little") != depth:
+                    return False, words["path"]
+                ps.append([bytes(r[9 + 32 * i:41 + 32 * i]) for i in range(depth)])
+            recs.append(rs)
+            paths.append(ps)
+            off += t * (rec + prec)
+        for k in range(2):
+            for s in range(t):
+                if not o.merkle_verify(o.hash_from_field_elements(recs[k][s]), top[s] % q, paths[k][s], bytes(roots[k])):
+                    return False, words["auth"]
+        if any(v >= p for rs in recs for r in rs for v in r):
+            return False, words["canonical"]
+        iota = pow(wN, q, p)
+        for s in range(t):
+            a = top[s] % q
+            for j in range(4):
+                x = h * pow(wN, a, p) % p * pow(iota, j, p) % p
+                rows = [[recs[k][s][4 * c + j] for c in range(V)] for k, V in enumerate(widths)]
+                idx, want = pv[4 * s + j]
+                assert idx == a + j * q
+                if q_at(rows[0], rows[1], x, z, ood, gammas, w, S, p, g) != [int(c) for c in want]:
+                    return False, words["quotient"]
+        return True, ""
+    ok, pv, used, top, why = pc.verify(o, cfg_o, proof[at:], g, bytes(tr), bits)
+    if not ok:
+        return False, "fri: " + why
+    if len(pv) != 2 * t:
+        return False, "no layer"
+    rest = proof[at + used:]
+    m = 2 * t
+    lens = [m * (9 + 8 * W) + m * (9 + 32 * log_N), m * (9 + 32 * D) + m * (9 + 32 * log_N)]
+    if len(rest) != sum(lens):
+        return False, "length"
+    secs = [rest[:lens[0]], rest[lens[0]:]]
+    pos = [i for s in top for i in ar.positions(s, N, B, False)]
+    rows = []
+    for v in range(2):
+        r, why = dc._section(o, secs[v], widths[v], log_N, pos, roots[v])
+        if r is None:
+            return False, why
+        rows.append(r)
+    for v in range(2):
+        if not dc._auth(o, secs[v], widths[v], log_N, pos, bytes(roots[v])):
+            return False, "auth"
+    if any(x >= p for r in rows for row in r for x in row):
+        return False, "canonical"
+    for q, i in enumerate(pos):
+        x = h * pow(wN, i, p) % p
+        if q_at(rows[0][q], rows[1][q], x, z, ood, gammas, w, S, p, g) != [int(c) for c in pv[q][1]] or pv[q][0] != i:
+            return False, "quotient"
+    return True, ""
+
+
+def sentence_matches(reason, sentence, cosets):
+    """does the library's sentence belong to the restated verifier's reason?"""
+    if cosets:
+        return reason == sentence
+    return dc.keyword(reason) in sentence

@@ -88,12 +88,30 @@ def test_composition_of_a_satisfying_trace_has_the_planned_degree(oracle):
             assert hc[:, (D // 2) << log_n:].any(), name
 
 
-@pytest.mark.parametrize("p,g", PRIMES)
+def test_synthetic_keeps_its_default_and_its_shape_when_extreme():
+    """extreme=False is the statement the tests have always composed (pinned by digest); extreme=True has the same operands,
+    exponents, boundary rows and periods, and every value p - 1"""
+    import hashlib
+    p = xc.PRIMES[0][0]
+    air, cols = wc.synthetic(5, 2, 4, 2, p, 16)
+    told = repr((cols, air.constraints, air.boundaries, air.periodics, air.window, air.degree)).encode()
+    assert hashlib.sha256(told).hexdigest() == "aeba049f6293ee5713c0ea7e5816a1eb5e94dd53cc740e405822f5afbb179292"
+    top, tcols = wc.synthetic(5, 2, 4, 2, p, 16, extreme=True)
+    assert (top.window, top.degree) == (air.window, air.degree) == (4, 2)
+    assert [[f for _cf, f in con] for con in top.constraints] == [[f for _cf, f in con] for con in air.constraints]
+    assert [(c, r) for c, r, _v in top.boundaries] == [(c, r) for c, r, _v in air.boundaries]
+    assert [len(v) for v in top.periodics] == [len(v) for v in air.periodics] == [2, 16]
+    values = [v for c in tcols for v in c] + [v for per in top.periodics for v in per] + [v for _c, _r, v in top.boundaries]
+    assert all(v % p == p - 1 for v in values + [cf for con in top.constraints for cf, _f in con])
+
+
+@pytest.mark.parametrize("p,g", FIELDS)
 @pytest.mark.parametrize("S", [3, 4])
 def test_emu_compose_window(emu, oracle, p, g, S):
-    """base and extension weights, tiled and direct, B in {4, 8, 16}, the halo longer than, equal to and shorter than a tile"""
+    """base and extension weights, tiled and direct, B in {4, 8, 16}, the halo longer than, equal to and shorter than a tile;
+    at log_N = 8, for every B, the statement with every value p - 1 as well"""
     o = oracle
-    seen = set()
+    seen, extremes = set(), set()
     for lb in (2, 3, 4):
         for log_N in range(((S << lb) - 1).bit_length(), 9):   # from N = S B on, where the halo is all of the domain but B points
             log_n = log_N - lb
@@ -102,17 +120,20 @@ def test_emu_compose_window(emu, oracle, p, g, S):
             W, Q = [(1, 0), (5, 2), (64, 0), (1, 2), (5, 0), (64, 2)][(log_N + lb + S) % 6]
             if Q == 2 and log_n < 1:
                 continue
-            air, cols = wc.synthetic(W, Q, S, 1 if lb == 2 else 2, p, 1 << log_n)
-            lde = ac.lde(o, cols, p, g, log_n, lb, 5, g)
-            wts, xw = ac.weights_for(air), xc.ext_weights_for(air)
-            want, want_x = wc.compose(o, air, cols, wts, p, g, log_n, lb, 5, g), wc.compose_ext(o, air, cols, xw, p, g, log_n, lb, 5, g)
-            seen.add(wc.air_tile(W + Q, 1 << lb, 1 << log_N, 1, S))
-            for direct, pad in ((False, 0), (True, 0), (False, 3)):
-                got = emu_compose(emu, air, lde, wts, p, g, log_n, lb, 5, g, direct, False, pad)
-                assert np.array_equal(got, want), (S, lb, log_N, W, Q, direct, pad, int(np.flatnonzero(got != want)[0]))
-                got = emu_compose(emu, air, lde, xw, p, g, log_n, lb, 5, g, direct, True, pad)
-                assert np.array_equal(got, want_x), (S, lb, log_N, W, Q, direct, pad)
+            for extreme in ((False, True) if log_N == 8 else (False,)):
+                air, cols = wc.synthetic(W, Q, S, 1 if lb == 2 else 2, p, 1 << log_n, extreme=extreme)
+                lde = ac.lde(o, cols, p, g, log_n, lb, 5, g)
+                wts, xw = ac.weights_for(air), xc.ext_weights_for(air)
+                want, want_x = wc.compose(o, air, cols, wts, p, g, log_n, lb, 5, g), wc.compose_ext(o, air, cols, xw, p, g, log_n, lb, 5, g)
+                seen.add(wc.air_tile(W + Q, 1 << lb, 1 << log_N, 1, S))
+                extremes |= {(S, lb)} if extreme else set()
+                for direct, pad in ((False, 0), (True, 0), (False, 3)):
+                    got = emu_compose(emu, air, lde, wts, p, g, log_n, lb, 5, g, direct, False, pad)
+                    assert np.array_equal(got, want), (S, lb, log_N, W, Q, extreme, direct, pad, int(np.flatnonzero(got != want)[0]))
+                    got = emu_compose(emu, air, lde, xw, p, g, log_n, lb, 5, g, direct, True, pad)
+                    assert np.array_equal(got, want_x), (S, lb, log_N, W, Q, extreme, direct, pad)
     assert {0, 64, 128, 256} <= seen, seen
+    assert extremes == {(S, 2), (S, 3), (S, 4)}
 
 
 def test_emu_check_window(emu):

@@ -200,6 +200,32 @@ def test_layout_lengths_are_the_formula(oracle, p, g):
         assert wc.transcript_len(W, len(air.constraints), D, 2) == 32 * (3 + W + len(air.constraints) + 2 * (2 * W + D))
 
 
+def test_plans_and_layouts_under_a_caller_s_offsets(oracle):
+    """smi_air_plan_deep with its length and smi_air_deep_fold4_layout under (trace_offset, lde_offset) other than (1, g) give
+    the length of the proof made under them -- the restated proofs, which tests/test_gpu_deep_offsets.py holds the device's
+    equal to -- for a two-row statement and a window statement, over row leaves and over coset leaves"""
+    import stark_rs_amd as s
+    from stark_rs_amd import _lib
+    s.build()
+    p, g = xc.PRIMES[0]
+    t = 4
+    for name, window, log_n, lb in (("mimc", False, 6, 3), ("tap4", True, 5, 3)):
+        air, cols = wc.make(name, 1 << log_n, p) if window else ap.make(name, 1 << log_n, p)
+        W, S, flat = len(cols), air.window, air.flatten(p)
+        d, D = wc.plan(air, log_n)
+        assert dfc.folds(log_n, lb, t) >= 1
+        for tau, h in ((5, 11), (1, 11), (5, g), (p - 1, p - 2)):
+            N = 1 << (log_n + lb)
+            assert pow(h, N, p) != 1 and pow(h * pow(tau, p - 2, p) % p, N, p) != 1
+            cfg = _lib.StarkCfg(log_n, lb, W, 1, tau, h, t, 1)
+            rows = wc.prove(oracle, air, cols, p, g, log_n, lb, t, tau, h) if window else dc.prove(oracle, air, cols, p, g, log_n, lb, t, tau, h)
+            cosets = wc.prove(oracle, air, cols, p, g, log_n, lb, t, tau, h, 0, True) if window else dfc.prove(oracle, air, cols, p, g, log_n, lb, t, tau, h)
+            assert s.engine.air_plan_deep(p, flat, cfg, True) == (d, D, len(rows["proof"])), (name, tau, h)
+            assert len(rows["proof"]) == wc.proof_len(oracle, W, D, S, log_n, lb, t, p, g, h)
+            assert s.engine.air_deep_fold4_layout(p, flat, cfg) == (dfc.folds(log_n, lb, t), len(cosets["proof"])), (name, tau, h)
+            assert len(cosets["proof"]) == wc.fold4_layout(W, D, S, log_n, lb, t)[1]
+
+
 def test_declarations():
     import stark_rs_amd as s
     from stark_rs_amd import _lib

@@ -184,24 +184,36 @@ def gpu_codeword(eng, S, lde, seg, log_n, lb, z, ood, ch, h, stride=None, lead=0
     return np.stack([host[lead + e * st:lead + e * st + N] for e in range(4)]).astype(np.uint64)
 
 
-@pytest.mark.parametrize("p,g", xc.PRIMES)
-@pytest.mark.parametrize("log_N", range(6, 13))
-def test_dev_deep_compose_window_equals_the_restatement(engines, oracle, p, g, log_N):
-    eng, N = engines[p], 1 << log_N
+def check_codeword(eng, oracle, p, g, log_N, h=None):
+    """smi_dev_deep_compose_window at S in {3, 4} (random and extreme inputs, both load paths) and at S = 2 (against
+    smi_dev_deep_compose and dc.q_codeword).  h: the offset of the evaluation domain (default g, what lde_offset=None means);
+    under another h the restatement over the default points must differ, so that a kernel which ignored h could not pass"""
+    N, h = 1 << log_N, g if h is None else h
     for lb, W, D in dc.compose_combos(log_N):
         log_n = log_N - lb
         w, _wN = ac.roots_of_unity(oracle, p, g, log_n, lb)
-        x = dc.points(oracle, p, g, log_n, lb, g)
+        x = dc.points(oracle, p, g, log_n, lb, h)
+        x_default = dc.points(oracle, p, g, log_n, lb, g)
         for S in (3, 4):
             for extreme in (False, True):
                 lde, seg, z, ood, ch = codeword_inputs(p, W, D, S, N, extreme)
                 want = wc.q_codeword(lde, seg, x, z, ood, ch, w, S, p, g)
-                assert np.array_equal(gpu_codeword(eng, S, lde, seg, log_n, lb, z, ood, ch, g), want), (lb, W, D, S, extreme)
-            assert np.array_equal(gpu_codeword(eng, S, lde, seg, log_n, lb, z, ood, ch, g, stride=N + 3, lead=1), want), (lb, W, D, S)   # 4-byte path
+                if h != g:
+                    assert not np.array_equal(want, wc.q_codeword(lde, seg, x_default, z, ood, ch, w, S, p, g)), (lb, W, D, S, extreme)
+                assert np.array_equal(gpu_codeword(eng, S, lde, seg, log_n, lb, z, ood, ch, h), want), (lb, W, D, S, extreme, h)
+            assert np.array_equal(gpu_codeword(eng, S, lde, seg, log_n, lb, z, ood, ch, h, stride=N + 3, lead=1), want), (lb, W, D, S, h)   # 4-byte path
         lde, seg, z, ood, ch = codeword_inputs(p, W, D, 2, N, False)
-        two = gpu_codeword(eng, 2, lde, seg, log_n, lb, z, ood, ch, g)
-        assert np.array_equal(two, gpu_codeword(eng, 2, lde, seg, log_n, lb, z, ood, ch, g, old=True))
+        two = gpu_codeword(eng, 2, lde, seg, log_n, lb, z, ood, ch, h)
+        assert np.array_equal(two, gpu_codeword(eng, 2, lde, seg, log_n, lb, z, ood, ch, h, old=True))
         assert np.array_equal(two, dc.q_codeword(lde, seg, x, z, ood, ch, w, p, g))
+        if h != g:
+            assert not np.array_equal(two, dc.q_codeword(lde, seg, x_default, z, ood, ch, w, p, g)), (lb, W, D)
+
+
+@pytest.mark.parametrize("p,g", xc.PRIMES)
+@pytest.mark.parametrize("log_N", range(6, 13))
+def test_dev_deep_compose_window_equals_the_restatement(engines, oracle, p, g, log_N):
+    check_codeword(engines[p], oracle, p, g, log_N)
 
 
 def test_dev_deep_compose_window_refusals(engines):

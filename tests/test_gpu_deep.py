@@ -100,19 +100,23 @@ def gpu_compose(eng, lde, seg, log_n, lb, z, ood, ch, h, stride=None, lead=0):
     return np.stack([host[lead + e * st:lead + e * st + N] for e in range(4)]).astype(np.uint64)
 
 
-def check_compose(eng, oracle, p, g, log_N, combos):
-    N = 1 << log_N
+def check_compose(eng, oracle, p, g, log_N, combos, h=None):
+    """h: the offset of the evaluation domain (default g, what lde_offset=None means); under another h the restatement over
+    the default points must differ, so that a kernel which ignored h could not pass"""
+    N, h = 1 << log_N, g if h is None else h
     for k, (lb, W, D) in enumerate(combos):
         log_n = log_N - lb
         w, _wN = ac.roots_of_unity(oracle, p, g, log_n, lb)
-        x = dc.points(oracle, p, g, log_n, lb, g)
+        x = dc.points(oracle, p, g, log_n, lb, h)
         for kind in ("random", "extreme"):
             lde, seg, z, ood, ch = compose_inputs(p, W, D, N, kind, seed=k)
             want = dc.q_codeword(lde, seg, x, z, ood, ch, w, p, g)
-            got = gpu_compose(eng, lde, seg, log_n, lb, z, ood, ch, g)
-            assert np.array_equal(got[:, :1 << lb], want[:, :1 << lb]), (lb, W, D, kind)      # the first B points: where an index i - B would wrap
-            assert np.array_equal(got, want), (lb, W, D, kind)
-        assert np.array_equal(gpu_compose(eng, lde, seg, log_n, lb, z, ood, ch, g, stride=N + 3, lead=1), want), (lb, W, D)   # the 4-byte path
+            if h != g:
+                assert not np.array_equal(want, dc.q_codeword(lde, seg, dc.points(oracle, p, g, log_n, lb, g), z, ood, ch, w, p, g)), (lb, W, D, kind)
+            got = gpu_compose(eng, lde, seg, log_n, lb, z, ood, ch, h)
+            assert np.array_equal(got[:, :1 << lb], want[:, :1 << lb]), (lb, W, D, kind, h)   # the first B points: where an index i - B would wrap
+            assert np.array_equal(got, want), (lb, W, D, kind, h)
+        assert np.array_equal(gpu_compose(eng, lde, seg, log_n, lb, z, ood, ch, h, stride=N + 3, lead=1), want), (lb, W, D, h)   # the 4-byte path
 
 
 @pytest.mark.parametrize("p,g", xc.PRIMES)

@@ -47,19 +47,23 @@ def gpu_compose_args(eng, lde, cl, seg, log_n, lb, z, ood, ch, h, odd=False):
     return np.stack([host[lead + e * st[3]:lead + e * st[3] + N] for e in range(4)]).astype(np.uint64)
 
 
-def check_compose(eng, oracle, p, g, log_N, shapes, challenge_sets=("random", "u64")):
-    N = 1 << log_N
+def check_compose(eng, oracle, p, g, log_N, shapes, challenge_sets=("random", "u64"), h=None):
+    """h: the offset of the evaluation domain (default g, what lde_offset=None means); under another h the restatement over
+    the default points must differ, so that a kernel which ignored h could not pass"""
+    N, h = 1 << log_N, g if h is None else h
     for k, (W, A, D) in enumerate(shapes):
         lb = 2 if log_N < 5 else 2 + k % 3
         log_n = log_N - lb
         w, _wN = ac.roots_of_unity(oracle, p, g, log_n, lb)
-        x = dc.points(oracle, p, g, log_n, lb, g)
+        x = dc.points(oracle, p, g, log_n, lb, h)
         for cs in challenge_sets:
             u = {"u64": u64_set(p), "max": [(1 << 64) - 1], "pm1": [p - 1]}.get(cs)
             lde, cl, seg, z, ood, ch = da.compose_inputs(p, W, A, D, N, "random" if cs == "random" else "extreme", seed=k + log_N, u=u)
             want = da.q_codeword(lde, cl, seg, x, z, ood, ch, w, p, g)
+            if h != g:
+                assert not np.array_equal(want, da.q_codeword(lde, cl, seg, dc.points(oracle, p, g, log_n, lb, g), z, ood, ch, w, p, g)), (W, A, D, cs)
             for odd in (False, True):
-                assert np.array_equal(gpu_compose_args(eng, lde, cl, seg, log_n, lb, z, ood, ch, g, odd=odd), want), (log_N, W, A, D, cs, odd)
+                assert np.array_equal(gpu_compose_args(eng, lde, cl, seg, log_n, lb, z, ood, ch, h, odd=odd), want), (log_N, W, A, D, cs, odd, h)
 
 
 @pytest.mark.parametrize("p,g", xc.PRIMES)

@@ -3,7 +3,8 @@ the CPU oracle's primitives and the helpers of tests/deep_compose.py: the window
 the S-row constraints with the periodic columns as extended tables, the S - 1 exemption roots), the plan rule, the record
 u_{s,c} = f_c(z w^s) and its transcript, the DEEP codeword with S denominators, both provers (row leaves with dc's FRI, coset
 leaves with fold-by-4 FRI) and both verifiers in the library's order of checks.
-Not a test module: imported by tests/test_air_window_host.py, tests/test_air_window_emu.py and tests/test_gpu_air_window.py."""
+Not a test module: imported by tests/test_air_window_host.py, tests/test_air_window_emu.py, tests/test_gpu_air_window.py,
+tests/test_gpu_boundary_primes_window.py and tests/test_gpu_deep_offsets.py."""
 import numpy as np
 
 import air_compose as ac
@@ -107,26 +108,29 @@ def two_row_form(name, n, p, seed=7):
     raise KeyError(name)
 
 
-def synthetic(W, Q, S, d, p, n, seed=11):
+def synthetic(W, Q, S, d, p, n, seed=11, extreme=False):
     """two constraints of degree d (1 or 2) over W random columns and Q periodic columns -- of period 2 and, with Q = 2, of
     period n --, every shift s < S read from some column and the periodic columns read at shift S - 1.  The columns do not
-    satisfy them: the codeword is still defined point by point.  Column W - 1 holds p - 1 throughout.  -> (Air, columns)"""
+    satisfy them: the codeword is still defined point by point.  Column W - 1 holds p - 1 throughout.  extreme: every trace
+    cell, periodic value, boundary value and constraint coefficient is p - 1, under the same shifts, columns and degree.
+    -> (Air, columns)"""
     rng = np.random.default_rng(seed + 131 * W + 17 * Q + S)
-    cols = [[int(v) for v in rng.integers(0, p, n)] for _ in range(W)]
+    v_ = (lambda v: p - 1) if extreme else (lambda v: int(v))
+    cols = [[v_(v) for v in rng.integers(0, p, n)] for _ in range(W)]
     cols[W - 1] = [p - 1] * n
     air = Air(W)
-    pj = [air.periodic([int(v) for v in rng.integers(0, p, per)]) for per in ([2, n][:Q])]
+    pj = [air.periodic([v_(v) for v in rng.integers(0, p, per)]) for per in ([2, n][:Q])]
     air.boundary(0, 0, cols[0][0])
     if W > 2:
-        air.boundary(2, n - 1, cols[2][n - 1]).boundary(2, 1, 5)
-    c0 = {("row", s, (3 * s) % W): int(rng.integers(1, p)) for s in range(S)}
-    c0[()] = 3
+        air.boundary(2, n - 1, cols[2][n - 1]).boundary(2, 1, v_(5))
+    c0 = {("row", s, (3 * s) % W): v_(rng.integers(1, p)) for s in range(S)}
+    c0[()] = v_(3)
     for j in pj:
-        c0[("per_row", S - 1, j)] = int(rng.integers(1, p))
-    c1 = {("row", S - 1, W - 1): 1, ("row", 0, W // 2): p - 2}
+        c0[("per_row", S - 1, j)] = v_(rng.integers(1, p))
+    c1 = {("row", S - 1, W - 1): v_(1), ("row", 0, W // 2): v_(p - 2)}
     if d == 2:
-        c0[(("row", S - 1, W - 1), ("row", 1, 0))] = 7
-        c1[(("row", S - 2, W // 3), ("per_row", S - 1, pj[0]) if pj else ("row", 0, 0))] = 5
+        c0[(("row", S - 1, W - 1), ("row", 1, 0))] = v_(7)
+        c1[(("row", S - 2, W // 3), ("per_row", S - 1, pj[0]) if pj else ("row", 0, 0))] = v_(5)
     air.transition(c0).transition(c1)
     return air, cols
 

@@ -186,6 +186,7 @@ pub const SMI_ARGS_MAX: u32 = 8;
 pub const SMI_ARG_PERM: u32 = 0;
 pub const SMI_ARG_LOOKUP: u32 = 1;
 pub const SMI_ARG_NO_SELECTOR: u32 = 0xffffffff;
+pub const SMI_ARG_NEXT_ROW: u32 = 0x40000000;
 pub const SMI_ARG_MAX_TUPLES: u32 = 4;
 pub const SMI_ARG_TUPLES_SHIFT: u32 = 8;
 

@@ -799,8 +799,9 @@ int smi_air_verify_ext_fold4(smi_ctx *ctx, const smi_stark_cfg *cfg, const void 
  *   smi_dev_air_check and a violated AIR.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_PERM_MAX_WIDTH; every
  *   column index < n_cols; log_n >= 1; everything smi_air_plan refuses.
- * Left out: more than one permutation per proof; next-row tuple members (selectors and periodic members: "Argument list
- *   with selectors and periodic members" below); a permutation together with a
+ * Left out: more than one permutation per proof; next-row tuple members in this single form (selectors and periodic
+ *   members: "Argument list with selectors and periodic members" below; a member read one row later: "Argument list:
+ *   next-row operands"); a permutation together with a
  *   lookup ("Lookup argument" below); a column-tree or smi_mgpu_* twin; the auxiliary quotients fused into the main composition launch (a follow-up: they run
  *   as a second streaming kernel over the four coordinate columns).  Several arguments, and permutations together with
  *   lookups, are what "Argument list" below adds; these entry points stay at one. */
@@ -882,8 +883,9 @@ int smi_air_verify_perm(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   not).  It does not refuse a wrong M or a missing lookup: *closes = 0 and the verifier rejects that proof.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): width in 1 .. SMI_LOOKUP_MAX_WIDTH; every
  *   column index < n_cols; mult_col none of the tuple columns; log_n >= 1; everything smi_air_plan refuses.
- * Left out: several lookups, or several looked-up tuples sharing one table; next-row tuple members (selectors and
- *   periodic members: "Argument list with selectors and periodic members" below); a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
+ * Left out: several lookups, or several looked-up tuples sharing one table; next-row tuple members in this single form
+ *   (selectors and periodic members: "Argument list with selectors and periodic members" below; a member read one row later:
+ *   "Argument list: next-row operands"); a lookup together with a permutation; the auxiliary quotients fused into the main composition launch; a
  *   column-tree or smi_mgpu_* twin.  Several lookups, each with a multiplicity column of its own, and lookups together
  *   with permutations are what "Argument list" below adds, several looked-up tuples sharing one table and one multiplicity
  *   column what "Shared-table lookups" adds; these entry points stay at one. */
@@ -957,8 +959,9 @@ int smi_air_verify_lookup(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *ai
  *   rejects a proof with a column that does not.
  * Limits (SMI_ERR_BAD_ARG, the reason in smi_air_last_error / smi_last_error): count in 1 .. SMI_ARGS_MAX; kind 0 or 1;
  *   every argument by its own section's limits, the reason naming the argument's index; everything smi_air_plan refuses.
- * Left out: next-row tuple members (selectors and periodic members are what "Argument list with selectors and periodic
- *   members" below adds, several tuples under one multiplicity column what "Shared-table lookups" adds to that section's
+ * Left out: next-row tuple members in this list without selectors (selectors and periodic members are what "Argument
+ *   list with selectors and periodic members" below adds, members read one row later what "Argument list: next-row
+ *   operands" adds to that section's entry points, several tuples under one multiplicity column what "Shared-table lookups" adds to that section's
  *   entry points; these entry points stay as they are and refuse a kind with a tuple count); the auxiliary
  *   quotients fused into the main composition launch; a column-tree or smi_mgpu_* twin; a wave-level scan. */
 #define SMI_ARGS_MAX 8
@@ -1014,7 +1017,8 @@ int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *
  * Operands.  An operand is a variable in the AIR's own numbering (W = n_cols, Q = n_periodic): var = c with c < W is trace
  *   column c at this row, var = 2 W + j with j < Q periodic column j at this row.  The two next-row kinds (W <= var < 2 W,
- *   var >= 2 W + Q) are refused.  On the trace the value V(r) is T[c][r] or v_j[r mod P_j]; on the evaluation coset V(x_i)
+ *   var >= 2 W + Q) are refused; a this-row variable read one row later is SMI_ARG_NEXT_ROW | var ("Argument list: next-row
+ *   operands" below).  On the trace the value V(r) is T[c][r] or v_j[r mod P_j]; on the evaluation coset V(x_i)
  *   is lde[c][i] or pi_j(x_i), the extended periodic table read modulo its length P_j B exactly as the main composition
  *   reads it ("AIR" above).
  * Argument a.  kind, width m in 1 .. 8, the operand lists a_var[m] and b_var[m], the selectors a_sel and b_sel -- an operand
@@ -1042,13 +1046,16 @@ int smi_air_verify_args(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   instead of a trace column, is rejected on the composition.
  * Anchor.  A list in which no argument has a selector or a periodic operand yields every byte of smi_dev_air_prove_args for
  *   the same list; the roots, the columns and the codeword are equal too.
- * Limits (SMI_ERR_BAD_ARG, the reason names the argument): those of "Argument list"; every operand a this-row variable;
+ * Limits (SMI_ERR_BAD_ARG, the reason names the argument): those of "Argument list"; every operand a this-row variable,
+ *   bare or under SMI_ARG_NEXT_ROW;
  *   mult_col < n_cols, none of the argument's trace operands, none of its selectors; everything smi_air_plan refuses.
- * Left out: next-row tuple members; a column-tree or smi_mgpu_* twin.  (Several looked-up tuples under one table, one
+ * Left out: a column-tree or smi_mgpu_* twin.  (Members and selectors read one row later: "Argument list: next-row
+ *   operands" below, through these entry points.  Several looked-up tuples under one table, one
  *   multiplicity column and one running sum: "Shared-table lookups" below, through these entry points.)
  *   (FRI at the full blowup and a lookup list at log_blowup = 2 are what "Out-of-domain sampling with an argument list"
  *   below adds.) */
 #define SMI_ARG_NO_SELECTOR 0xffffffffu
+#define SMI_ARG_NEXT_ROW 0x40000000u    /* operand = SMI_ARG_NEXT_ROW | v, v a this-row variable: v one row later ("Argument list: next-row operands") */
 #define SMI_ARG_MAX_TUPLES   4
 #define SMI_ARG_TUPLES_SHIFT 8      /* kind = SMI_ARG_LOOKUP | (J - 1) << SMI_ARG_TUPLES_SHIFT, J in 1 .. SMI_ARG_MAX_TUPLES ("Shared-table lookups") */
 typedef struct smi_air_xarg {
@@ -1136,13 +1143,58 @@ int smi_air_verify_xargs(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air
  *   recomputed from the opened rows (row leaves) or at z (DEEP, coset leaves, zero knowledge).  A proof checked under
  *   J - 1 tuples, one changed operand, one dropped selector or the J single lookups is rejected.
  * Limits (SMI_ERR_BAD_ARG, the reason names the argument): tuple bits on a permutation; J > SMI_ARG_MAX_TUPLES; a set a_sel
- *   for J >= 2; a next-row operand in any tuple or selector; J n >= p, where the multiplicities could wrap (reachable for
+ *   for J >= 2; one of the AIR's own next-row variables in any tuple or selector; J n >= p, where the multiplicities could wrap (reachable for
  *   J >= 2 alone, and only through the entry points that take log_n without a blowup: a plan keeps n <= (p - 1) / 4);
  *   kind = 2, or bits above the second byte, with the sentence of "Argument list".
  * Measured (profiles/shared_lookup_time.log, profiles/shared_lookup_kernel_resources.log): DESIGN.md section 11.
- * Left out: next-row tuple members; several tables in one argument; sharing across arguments (a joint closing condition
+ * Left out: next-row operands under zero knowledge; several tables in one argument; sharing across arguments (a joint closing condition
  *   over several columns); more than 4 tuples; smi_mgpu_* twins; the list without selectors (smi_air_args); an AIR digest
  *   in the transcript. */
+
+/* ---- Argument list: next-row operands -----------------------------------------------------------
+ * The lists above relate cells of ONE row.  What LogUp is most often asked for relates a row to its successor: (state[r],
+ * input[r], state[r+1]) is a row of a public transition table -- a DFA, an opcode decoder, a carry table -- or a sorted column
+ * is compared with its own shift.  Until here that took a copy column d[r] = c[r+1] and a transition constraint binding it: a
+ * column extended, hashed, opened at every query and at z and z w only because an operand could not say "next".  Every proof
+ * variant that takes a list already carries what such an operand needs -- the row-leaf provers open the rows a + B and b + B,
+ * the DEEP provers open every trace column at z w, every verifier evaluates pi_j(w x) -- so no proof layout, record count,
+ * transcript shape or degree changes.
+ *
+ * Statement.  An operand may be a this-row variable read one row later, cyclically: on the trace V(r) = T[c][(r + 1) mod n] or
+ *   v_j[(r + 1) mod P_j]; as a polynomial f_c(w x) or pi_j(w x); on the evaluation coset lde[c][(i + B) mod N], or the extended
+ *   periodic table read at (i + B) mod L_j.  The wrap is deliberate -- the arguments' own transition quotients wrap too; a
+ *   caller who does not want row n - 1 to see row 0 deselects it with a (periodic) selector.  Allowed in every operand
+ *   position: the members of either side, the J tuples of a shared lookup, a_sel, b_sel, the per-tuple selectors.  Not as
+ *   mult_col, which stays a plain trace column.
+ * Encoding.  operand = SMI_ARG_NEXT_ROW | v with v a this-row variable (c < W, or 2 W + j).  The AIR's own next-row variable
+ *   numbers stay refused with their sentence, flagged or not; SMI_ARG_NO_SELECTOR keeps its meaning; any other high bit leaves
+ *   v outside the AIR's variables and is refused as that.  mult_col is compared with the operands after the flag is stripped:
+ *   next(mult_col) as a member or a selector is refused with the sentences of mult_col.
+ * Degree.  Unchanged: d, D, E and every layout function return what they return for the same list with the flags removed.
+ * Kernels.  A NEXT template parameter on xargs_block_kernel, air_xargs_compose_kernel, xargs_insert_kernel /
+ *   xargs_count_kernel and their shared siblings; a list without a next-row operand launches the instantiations it always
+ *   launched (profiles/next_row_members_kernel_resources.log: their registers, LDS and scratch are the parent's, the new ones
+ *   have no scratch).  Column build: a lane owns four rows and needs the rows one further; three are in its own 16-byte load,
+ *   the fourth is one 4-byte load of the next word, row 0 for the last lane of the column.  Composition: the operand is read
+ *   at (i + B) mod N, where the launch reads the auxiliary columns' next row already; one aligned 16-byte load, as before.
+ *   Multiplicities: both launches hash and compare the cell at (row + 1) mod n; SMI_ERR_LOOKUP_MISSING and the
+ *   zero-denominator key name the row that READS, with their numbering.
+ * Who takes such a list.  smi_air_plan_xargs, smi_air_plan_deep_xargs and the three layouts; smi_dev_xargs_multiplicities,
+ *   smi_dev_xargs_columns, smi_dev_air_compose_xargs; smi_dev_air_prove_xargs / smi_air_verify_xargs (the operand at x_a from
+ *   the opened row a + B, and pi_j(w x_a)); smi_dev_air_prove_deep_xargs / smi_air_verify_deep_xargs and the _fold4 pair (the
+ *   operand at z from the record's v_c = f_c(z w), and pi_j(z w)).  Proof bytes, record counts and the order and text of every
+ *   rejection are unchanged; a proof checked under the list with one flag removed or moved is rejected on the composition
+ *   (row leaves) or the consistency check (DEEP).
+ * Who refuses (SMI_ERR_BAD_ARG, "<argument>: <operand> is a next-row operand", before any device work):
+ *   smi_air_plan_deep_zk_xargs and everything behind it (the layout, smi_dev_air_compose_zk_xargs, the prover, the verifier);
+ *   smi_dev_xargs_multiplicities_rows.  smi_air_args (no selectors) keeps refusing every operand that is no column; windows
+ *   above 2 keep being refused with lists.
+ * Measured (profiles/next_row_members_time.log; n = 2^20, B = 8, t = 32, coset leaves): the 9-column list of the README plus one
+ *   lookup with a next-row member proves in 6.618 ms and 260011 bytes, the same statement with a copy column and its constraint
+ *   in 6.822 ms and 261099 bytes.  The NEXT column build takes 0.107 ms where the plain one takes 0.097 (the extra 4-byte load,
+ *   131 VGPRs for 128), the NEXT composition 0.657 for 0.652.  DESIGN.md section 11.
+ * Left out: next-row operands under zero knowledge; shifts above one row in lists; the single permutation() / lookup() forms
+ *   and smi_air_args; smi_mgpu_* twins; opening at z w only the columns some operand or constraint reads there. */
 
 /* ---- Out-of-domain sampling (DEEP): FRI at the full blowup -------------------------------------
  * The AIR proofs above recompute the composition at the t queried positions only, so their FRI runs at E = B / D, an AIR
@@ -1284,7 +1336,7 @@ int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  * Measured (profiles/air_window_kernel_resources.log, profiles/air_window_time.log): DESIGN.md section 11.
  * Left out: windows above four rows; opening only the (column, shift) pairs that a constraint reads; argument lists and
  *   zero knowledge over wider windows (the zk row counts k_t depend on the number of opened functionals); the non-DEEP
- *   provers; smi_mgpu_* twins; next-row tuple members in lists. */
+ *   provers; smi_mgpu_* twins.  (A list reads one row further through its operands: "Argument list: next-row operands".) */
 
 /* ---- Out-of-domain sampling with an argument list ----------------------------------------------
  * The argument-list provers recompute the composition at the queried positions, so a list with a lookup (degree 3) needs
@@ -1341,8 +1393,8 @@ int smi_air_verify_deep(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *air,
  *   rejects such a proof on the consistency check.  A zero denominator in a column is SMI_ERR_NO_INVERSE as
  *   smi_dev_xargs_columns reports it.
  * Soundness accounting: DESIGN.md section 11.
- * Left out: folding factor 4 (it comes with coset leaves, below); the single permutation / lookup forms (a one-element list covers them); next-row tuple
- *   members; smi_mgpu_* twins; zero-knowledge randomisers; fusing the auxiliary quotients or the segment extension into
+ * Left out: folding factor 4 (it comes with coset leaves, below); the single permutation / lookup forms (a one-element list covers them);
+ *   smi_mgpu_* twins; zero-knowledge randomisers; fusing the auxiliary quotients or the segment extension into
  *   other launches. */
 /* Host only: the plan above -> d and D.  `xargs` is a pointer to an smi_air_xargs. */
 int smi_air_plan_deep_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments);
@@ -1562,7 +1614,8 @@ int smi_air_verify_deep_zk(smi_ctx *ctx, const smi_stark_cfg *cfg, const void *a
  * Measured (profiles/zk_args_time.log): the 9-column list of README.md at n = 2^20, B = 8, t = 32, 16 grinding bits -- 1.36 times
  *   the stage time of smi_dev_air_prove_deep_xargs_fold4 (wall time 1.93 times), proof 1.08 times its bytes.
  * Left out: row leaves / fold 2; the single permutation and lookup forms (a one-element list covers them); smi_mgpu_* twins;
- *   next-row tuple members; an AIR digest in the transcript. */
+ *   next-row operands (SMI_ARG_NEXT_ROW: the row after the last active row is random, and the statement over the active rows
+ *   needs a decision of its own -- the plan refuses such a list); an AIR digest in the transcript. */
 /* Host only: *degree = d, *segments = D', *k_t = 8 t + 16, *k_s (outputs are optional). */
 int smi_air_plan_deep_zk_xargs(uint64_t p, const smi_stark_cfg *cfg, const void *air, const void *xargs, uint32_t *degree, uint32_t *segments, uint32_t *k_t,
                                uint32_t *k_s);

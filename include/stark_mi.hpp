@@ -40,6 +40,9 @@ inline smi_ctx *context(uint64_t p) {
     return *slot;
 }
 
+// include/stark_mi.h, "Argument list: next-row operands": operand v of a list (a this-row variable) read one row later
+constexpr uint32_t next_row(uint32_t v) { return SMI_ARG_NEXT_ROW | v; }
+
 struct FieldElement;
 
 // src/ff.rs:9-12, 108-233

@@ -87,6 +87,7 @@ class AirXArgs(C.Structure):
 
 
 NO_SELECTOR = 0xffffffff   # SMI_ARG_NO_SELECTOR
+ARG_NEXT_ROW = 0x40000000  # SMI_ARG_NEXT_ROW: an operand of a list read one row later
 ARG_MAX_TUPLES = 4          # SMI_ARG_MAX_TUPLES
 ARG_TUPLES_SHIFT = 8        # SMI_ARG_TUPLES_SHIFT: kind = 1 | (J - 1) << 8 for a shared lookup of J tuples
 

@@ -73,8 +73,21 @@ int columns_run(const FieldSetup &fs, uint64_t g, const smi_air *air, const smi_
                 const uint64_t row0 = (b * PERM_BLOCK + tid) * PERM_ROWS;
                 uint64_t k;
                 auto ld = [&](uint32_t op, uint32_t v[4]) {
-                    if (row0 >= n) v[0] = v[1] = v[2] = v[3] = 0u;
-                    else if (xop_periodic(op)) xargs_periodic_rows(XD, op & 0xffu, row0, v);
+                    if (row0 >= n) {
+                        v[0] = v[1] = v[2] = v[3] = 0u;
+                    } else if (xop_next(op)) {   // xargs_block_body's NEXT branch, the 16-byte form where a column has four words
+                        const bool per = xop_periodic(op);
+                        const uint32_t j = op & 0xffu;
+                        const uint64_t len = per ? 1ull << XD.plog[j] : n, at = row0 & (len - 1);
+                        const uint32_t *col = per ? XD.pvals + XD.pfirst[j] : trace + (uint64_t)j * n;
+                        if (len >= 4) {
+                            uint32_t own[4];
+                            load4(col, at, len, own);
+                            xargs_next4(col, at, len, own, v);
+                        } else {
+                            xargs_next4_words(col, row0, len, n, v);
+                        }
+                    } else if (xop_periodic(op)) xargs_periodic_rows(XD, op & 0xffu, row0, v);
                     else load4(trace + (uint64_t)op * n, row0, n, v);
                 };
                 if (shared) xargs_lane_column(XD, SH, a, F, row0, n, ld, &pls[(size_t)tid * PERM_ROWS], &agg[tid], &k);
@@ -154,20 +167,25 @@ extern "C" int emu_xargs_multiplicities(uint64_t p, uint64_t g, const smi_air *a
     memset(mult, 0, n * 4);
     uint64_t first = ~0ull;
     bool exhausted = false;
+    const bool next = xargs_dev_any_next(XD, &SH);   // the NEXT instantiations of the two launches
     for (uint64_t k = 0; k < n; k++) {
         const uint32_t t = (uint32_t)(order ? n - 1 - k : k);
-        if (!xlookup_insert_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, t, HostAtomics{})) exhausted = true;
+        const bool ok = next ? xlookup_insert_lane<true>(XD, a, trace, n, tab.data(), (uint32_t)cap, t, HostAtomics{})
+                             : xlookup_insert_lane<false>(XD, a, trace, n, tab.data(), (uint32_t)cap, t, HostAtomics{});
+        if (!ok) exhausted = true;
     }
     for (uint64_t k = 0; k < n; k++) {
         const uint32_t r = (uint32_t)(order ? n - 1 - k : k);
         if (SH.J[a] > 1) {   // xargs_count_shared_kernel: *missing is 4 row + tuple
             uint32_t miss = 0;
-            const int got = xshared_count_lane(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
+            const int got = next ? xshared_count_lane<true>(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss)
+                                 : xshared_count_lane<false>(XD, SH, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{}, &miss);
             if ((got & 1) && 4 * (uint64_t)r + miss < first) first = 4 * (uint64_t)r + miss;
             if (got & 2) exhausted = true;
             continue;
         }
-        const int got = xlookup_count_lane(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
+        const int got = next ? xlookup_count_lane<true>(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{})
+                             : xlookup_count_lane<false>(XD, a, trace, n, tab.data(), (uint32_t)cap, r, mult, HostAtomics{});
         if (got == 1 && r < first) first = r;
         if (got == 2) exhausted = true;
     }
@@ -231,12 +249,13 @@ static int compose_run(const FieldSetup &fs, uint64_t p, uint64_t g, const smi_s
             uint32_t acc[4][PERM_ROWS];
             for (int e = 0; e < 4; e++) load4(out + e * out_stride, i0, A.N, acc[e]);
             auto ld = [&](uint32_t op, uint32_t v[4]) {
+                const uint64_t ia = xop_next(op) ? i1 : i0;   // air_xargs_compose_body's NEXT loader
                 if (xop_periodic(op)) {
                     uint64_t L, at;
-                    const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, i0, &L, &at);
+                    const uint32_t *table = xargs_table_at(A.plog, A.pofs, A.ptab, op & 0xffu, ia, &L, &at);
                     load4(table, at, L, v);
                 } else {
-                    load4(lde + (uint64_t)op * stride, i0, A.N, v);
+                    load4(lde + (uint64_t)(op & 0xffu) * stride, ia, A.N, v);
                 }
             };
             auto ldc = [&](uint32_t col, bool next, uint32_t v[4]) { load4(cl + (uint64_t)col * c_stride, next ? i1 : i0, A.N, v); };

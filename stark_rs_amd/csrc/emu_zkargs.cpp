@@ -149,6 +149,7 @@ extern "C" int emu_xargs_multiplicities_rows(uint64_t p, uint64_t g, const smi_a
     if (rc != SMI_OK) return rc;
     rc = xargs_validate(xargs, n_cols, air->n_periodic, nullptr);
     if (rc != SMI_OK) return rc;
+    if (xargs_any_next(xargs)) return SMI_ERR_BAD_ARG;   // smi_dev_xargs_multiplicities_rows: this-row operands only
     rc = xargs_shared_rows(p, xargs, log_n, nullptr);
     if (rc != SMI_OK) return rc;
     if (a >= xargs->count || (xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) return SMI_ERR_BAD_ARG;

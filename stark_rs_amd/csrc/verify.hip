@@ -863,22 +863,33 @@ struct XArgAux {
             ext_mul_host(p, g, pw, alpha, pw);
         }
     }
-    // operand v at the point: the opened row cur, or the periodic values per[0 .. Q) of this row
-    uint64_t val(uint32_t v, const uint64_t *cur, const uint32_t *per) const { return v == SMI_ARG_NO_SELECTOR ? 1 : v < W ? cur[v] : per[v - 2 * W]; }
-    // got += w_b bq + w_t tq over the row cur, the periodic values per and the column's coordinates cc (this row), cn (next)
-    void add(uint64_t x, const uint64_t *cur, const uint32_t *per, const uint64_t *cc, const uint64_t *cn, uint32_t got[4]) const {
+    // operand v at the point: the opened row cur, or the periodic values per[0 .. Q) of this row; a next-row operand
+    // ("Argument list: next-row operands") reads the opened row B further (nxt) or pi_j(w x), per[Q .. 2 Q)
+    struct Rows {
+        const uint64_t *cur, *nxt;
+        const uint32_t *per;
+        uint32_t Q;
+    };
+    uint64_t val(uint32_t v, const Rows &cur) const {
+        if (v == SMI_ARG_NO_SELECTOR) return 1;
+        const bool next = (v & SMI_ARG_NEXT_ROW) != 0;
+        v &= ~SMI_ARG_NEXT_ROW;
+        return v < W ? (next ? cur.nxt : cur.cur)[v] : cur.per[(next ? cur.Q : 0) + v - 2 * W];
+    }
+    // got += w_b bq + w_t tq over the rows, the periodic values and the column's coordinates cc (this row), cn (next)
+    void add(uint64_t x, const Rows &cur, const uint64_t *cc, const uint64_t *cn, uint32_t got[4]) const {
         uint32_t fl[4], fr[4], c0[4], c1[4], a[4], b[4], bq[4], tq[4], u[4], v[4];
         for (int e = 0; e < 4; e++) fl[e] = fr[e] = gamma[e], c0[e] = (uint32_t)cc[e], c1[e] = (uint32_t)cn[e];
         const uint32_t J = xarg_tuples(*arg), m = arg->width;
         if (J > 1) {   // "Shared-table lookups": (s' - s) P f_T - Nn f_T + M S_b P with (Nn, P) folded over the tuples
             uint32_t P[4] = {1 % p, 0, 0, 0}, Nn[4] = {0, 0, 0, 0}, ds[4], lt[4], nf[4], t[4];
             for (uint32_t i = 0; i < m; i++)
-                for (int e = 0; e < 4; e++) fr[e] = (uint32_t)((fr[e] + mulm(apow[i][e], val(arg->b_var[i], cur, per), p)) % p);
+                for (int e = 0; e < 4; e++) fr[e] = (uint32_t)((fr[e] + mulm(apow[i][e], val(arg->b_var[i], cur), p)) % p);
             for (uint32_t j = 0; j < J; j++) {
                 uint32_t f[4] = {gamma[0], gamma[1], gamma[2], gamma[3]};
                 for (uint32_t i = 0; i < m; i++)
-                    for (int e = 0; e < 4; e++) f[e] = (uint32_t)((f[e] + mulm(apow[i][e], val(arg->a_var[j * m + i], cur, per), p)) % p);
-                const uint64_t sj = val(arg->a_var[J * m + j], cur, per);
+                    for (int e = 0; e < 4; e++) f[e] = (uint32_t)((f[e] + mulm(apow[i][e], val(arg->a_var[j * m + i], cur), p)) % p);
+                const uint64_t sj = val(arg->a_var[J * m + j], cur);
                 ext_mul_host(p, g, Nn, f, t);
                 for (int e = 0; e < 4; e++) Nn[e] = (uint32_t)((t[e] + mulm(sj, P[e], p)) % p);
                 ext_mul_host(p, g, P, f, t);
@@ -889,7 +900,7 @@ struct XArgAux {
             ext_mul_host(p, g, ds, lt, a);
             ext_mul_host(p, g, Nn, fr, nf);
             const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
-            const uint64_t M = mulm(cur[arg->mult_col], val(arg->b_sel, cur, per), p);
+            const uint64_t M = mulm(cur.cur[arg->mult_col], val(arg->b_sel, cur), p);
             for (int e = 0; e < 4; e++) {
                 tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - nf[e] + mulm(M, P[e], p)) % p, izt, p);
                 bq[e] = (uint32_t)mulm(c0[e], ixt, p);
@@ -901,10 +912,10 @@ struct XArgAux {
         }
         for (uint32_t j = 0; j < arg->width; j++)
             for (int e = 0; e < 4; e++) {
-                fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], val(arg->a_var[j], cur, per), p)) % p);
-                fr[e] = (uint32_t)((fr[e] + mulm(apow[j][e], val(arg->b_var[j], cur, per), p)) % p);
+                fl[e] = (uint32_t)((fl[e] + mulm(apow[j][e], val(arg->a_var[j], cur), p)) % p);
+                fr[e] = (uint32_t)((fr[e] + mulm(apow[j][e], val(arg->b_var[j], cur), p)) % p);
             }
-        const uint64_t sa = val(arg->a_sel, cur, per), sb = val(arg->b_sel, cur, per);
+        const uint64_t sa = val(arg->a_sel, cur), sb = val(arg->b_sel, cur);
         const uint64_t izt = powm((powm(x, n, p) + p - tau_n) % p, p - 2, p), ixt = powm((x + p - tau) % p, p - 2, p);
         if ((arg->kind & 0xffu) == SMI_ARG_PERM) {   // g = 1 + S (f - 1)
             for (int e = 0; e < 4; e++) {
@@ -922,7 +933,7 @@ struct XArgAux {
             for (int e = 0; e < 4; e++) ds[e] = (uint32_t)((c1[e] + (uint64_t)p - c0[e]) % p);
             ext_mul_host(p, g, fl, fr, lt);
             ext_mul_host(p, g, ds, lt, a);
-            const uint64_t M = mulm(cur[arg->mult_col], sb, p);
+            const uint64_t M = mulm(cur.cur[arg->mult_col], sb, p);
             for (int e = 0; e < 4; e++) {
                 tq[e] = (uint32_t)mulm((a[e] + (uint64_t)p - mulm(sa, fr[e], p) + mulm(M, fl[e], p)) % p, izt, p);
                 bq[e] = (uint32_t)mulm(c0[e], ixt, p);
@@ -1083,7 +1094,7 @@ static int air_verify_impl(smi_ctx *ctx, const smi_stark_cfg *cfg, const smi_air
                 else a_laux[a]->add(x, cur, cc, cn, got);
             }
             for (size_t a = 0; a < x_aux.size(); a++)
-                x_aux[a].add(x, cur, Q ? &per[(2 * s + k) * 2 * Q] : nullptr, &rows[1][(R * s + k) * AW + 4 * a], &rows[1][(R * s + k + 2) * AW + 4 * a], got);
+                x_aux[a].add(x, XArgAux::Rows{cur, nxt, Q ? &per[(2 * s + k) * 2 * Q] : nullptr, Q}, &rows[1][(R * s + k) * AW + 4 * a], &rows[1][(R * s + k + 2) * AW + 4 * a], got);
             for (uint32_t e = 0; e < NE; e++)
                 if (got[e] != ab[(2 * s + k) * NE + e] % p) return reject(ctx, accept, say.composition);
         }

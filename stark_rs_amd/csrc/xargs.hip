@@ -61,35 +61,46 @@ struct XHelperFlags {   // the first missing selected row, a probe that ran out
 }  // namespace
 
 // rows <= n: the rows that take part (smi_dev_xargs_multiplicities_rows); the column stride stays n
+// NEXT: the list has a next-row operand ("Argument list: next-row operands") -- a cell of such an operand is read at
+// (row + 1) mod n by both launches, so both sides hash and compare the shifted values.  Every other list takes NEXT = false,
+// whose cells look at no flag.
+template <bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void xargs_insert_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint64_t rows,
                                                                    uint32_t *tab, uint32_t cap, XHelperFlags *fl) {
     const uint64_t t = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
     if (t >= rows) return;
-    if (!xlookup_insert_lane(XD, a, trace, n, tab, cap, (uint32_t)t, XDevAtomics{})) atomicOr(&fl->exhausted, 1u);
+    if (!xlookup_insert_lane<NEXT>(XD, a, trace, n, tab, cap, (uint32_t)t, XDevAtomics{})) atomicOr(&fl->exhausted, 1u);
 }
+template <bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void xargs_count_kernel(XArgsDev XD, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n, uint64_t rows,
                                                                   const uint32_t *__restrict__ tab, uint32_t cap, uint32_t *mult, XHelperFlags *fl) {
     const uint64_t r = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
     if (r >= rows) return;
-    const int got = xlookup_count_lane(XD, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{});
+    const int got = xlookup_count_lane<NEXT>(XD, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{});
     if (got == 1) atomicMin(&fl->first, (unsigned long long)r);
     if (got == 2) atomicOr(&fl->exhausted, 1u);
 }
 // the count launch of a shared lookup: one probe per selected tuple of the lane's row; first: the smallest 4 row + tuple missing
+template <bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void xargs_count_shared_kernel(XArgsDev XD, XSharedDev SH, uint32_t a, const uint32_t *__restrict__ trace, uint64_t n,
                                                                          uint64_t rows, const uint32_t *__restrict__ tab, uint32_t cap, uint32_t *mult,
                                                                          XHelperFlags *fl) {
     const uint64_t r = (uint64_t)blockIdx.x * PERM_BLOCK + threadIdx.x;
     if (r >= rows) return;
     uint32_t miss = 0;
-    const int got = xshared_count_lane(XD, SH, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{}, &miss);
+    const int got = xshared_count_lane<NEXT>(XD, SH, a, trace, n, tab, cap, (uint32_t)r, mult, XDevAtomics{}, &miss);
     if (got & 1) atomicMin(&fl->first, (unsigned long long)(4 * r + miss));
     if (got & 2) atomicOr(&fl->exhausted, 1u);
 }
 
 // c: 4 A coordinate columns c_stride apart; block_agg: A runs of nb aggregates (four words each); first: the smallest key
 // SHT: XNoShared (xargs_block_kernel) or XSharedDev (xargs_block_shared_kernel, a list with a shared lookup)
-template <bool VEC, class SHT>
+// NEXT: the list has a next-row operand.  Such an operand wants the rows row0 + 1 .. row0 + 4, cyclically: three of them are in
+// the lane's own 16-byte load, the fourth is one 4-byte load of the word behind it (the neighbour lane's line; word 0 for the
+// last lane of the column).  The operand code is wave-uniform, so the whole wave takes the branch.  Without VEC (n < 4, a base
+// that is not 16-byte aligned, a stride that is no multiple of 4) and for a periodic column of period 1 or 2 the four cells are
+// (row + 1) mod length word by word.  Lists without such an operand take NEXT = false, which is the launch they always took.
+template <bool VEC, bool NEXT, class SHT>
 __device__ __forceinline__ void xargs_block_body(const XArgsDev &XD, const SHT &SH, const Fp &F, const uint32_t *__restrict__ trace, uint64_t n,
                                                  uint32_t *__restrict__ c, size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first,
                                                  uint32_t (*sc)[4][PERM_BLOCK]) {
@@ -103,6 +114,18 @@ __device__ __forceinline__ void xargs_block_body(const XArgsDev &XD, const SHT &
         [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
             if (row0 >= n) {
                 v[0] = v[1] = v[2] = v[3] = 0u;
+            } else if (NEXT && xop_next(op)) {
+                const bool per = xop_periodic(op);
+                const uint32_t j = op & 0xffu;
+                const uint64_t len = per ? 1ull << XD.plog[j] : n, at = row0 & (len - 1);
+                const uint32_t *col = per ? XD.pvals + XD.pfirst[j] : trace + (uint64_t)j * n;
+                if (VEC && len >= 4) {   // at + 3 < len: the own four are one aligned access, as below
+                    uint32_t own[4];
+                    perm_load4<true>(col, at, len, own);
+                    xargs_next4(col, at, len, own, v);
+                } else {
+                    xargs_next4_words(col, row0, len, n, v);
+                }
             } else if (xop_periodic(op)) {
                 const uint32_t j = op & 0xffu, lp = XD.plog[j];
                 // P_j >= 4 and row0 a multiple of 4: the four values are consecutive and 16-byte aligned (pfirst[j] is a multiple of P_j)
@@ -129,23 +152,25 @@ __device__ __forceinline__ void xargs_block_body(const XArgsDev &XD, const SHT &
 #pragma unroll
     for (int e = 0; e < 4; e++) perm_store4<VEC>(ca + e * c_stride, row0, n, o[e]);
 }
-template <bool VEC>
+template <bool VEC, bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void xargs_block_kernel(XArgsDev XD, Fp F, const uint32_t *__restrict__ trace, uint64_t n, uint32_t *__restrict__ c,
                                                                   size_t c_stride, uint32_t *__restrict__ block_agg, unsigned long long *first) {
     __shared__ uint32_t sc[2][4][PERM_BLOCK];
-    xargs_block_body<VEC>(XD, XNoShared{}, F, trace, n, c, c_stride, block_agg, first, sc);
+    xargs_block_body<VEC, NEXT>(XD, XNoShared{}, F, trace, n, c, c_stride, block_agg, first, sc);
 }
-template <bool VEC>
+template <bool VEC, bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void xargs_block_shared_kernel(XArgsDev XD, XSharedDev SH, Fp F, const uint32_t *__restrict__ trace, uint64_t n,
                                                                          uint32_t *__restrict__ c, size_t c_stride, uint32_t *__restrict__ block_agg,
                                                                          unsigned long long *first) {
     __shared__ uint32_t sc[2][4][PERM_BLOCK];
-    xargs_block_body<VEC>(XD, SH, F, trace, n, c, c_stride, block_agg, first, sc);
+    xargs_block_body<VEC, NEXT>(XD, SH, F, trace, n, c, c_stride, block_agg, first, sc);
 }
 
 // out (four coordinate columns, the composition of the main AIR) += the 2 A auxiliary quotients under w (8 A coordinates).
 // plog / pofs / ptab: AirDev's periodic tables on the device.
-template <bool VEC, class SHT>
+// NEXT: the list has a next-row operand, f_c(w x) or pi_j(w x): it is read B points further, at i1 -- where the body reads
+// the auxiliary columns' next row already.  B, N and every table's length are multiples of 4, so it stays one aligned access.
+template <bool VEC, bool NEXT, class SHT>
 __device__ __forceinline__ void air_xargs_compose_body(const XArgsDev &XD, const SHT &SH, const Fp &F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
                                                        uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
                                                        const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde,
@@ -163,13 +188,14 @@ __device__ __forceinline__ void air_xargs_compose_body(const XArgsDev &XD, const
         xargs_compose_points(
             XD, SH, F, w, tau_m, izt_m, B, i0, x_m, omega_m,
             [&](uint32_t op, uint32_t v[4]) {   // op is wave-uniform
+                const uint64_t ia = NEXT && xop_next(op) ? i1 : i0;
                 if (xop_periodic(op)) {
                     // the table's length L_j = P_j B is a multiple of 4, as i0 is: four consecutive entries, none past the end
                     uint64_t L, at;
-                    const uint32_t *table = xargs_table_at(plog, pofs, ptab, op & 0xffu, i0, &L, &at);
+                    const uint32_t *table = xargs_table_at(plog, pofs, ptab, op & 0xffu, ia, &L, &at);
                     perm_load4<VEC>(table, at, L, v);
                 } else {
-                    perm_load4<VEC>(lde + (uint64_t)op * stride, i0, N, v);
+                    perm_load4<VEC>(lde + (uint64_t)(NEXT ? op & 0xffu : op) * stride, ia, N, v);
                 }
             },
             [&](uint32_t col, bool next, uint32_t v[4]) { perm_load4<VEC>(cl + (uint64_t)col * c_stride, next ? i1 : i0, N, v); }, acc);
@@ -178,24 +204,24 @@ __device__ __forceinline__ void air_xargs_compose_body(const XArgsDev &XD, const
         x_m = mont_mul(x_m, xstep_m, F);
     }
 }
-template <bool VEC>
+template <bool VEC, bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_kernel(XArgsDev XD, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m, uint32_t omega_m,
                                                                         uint32_t tau_m, const uint32_t *__restrict__ izt_m, const uint32_t *__restrict__ plog,
                                                                         const uint32_t *__restrict__ pofs, const uint32_t *__restrict__ ptab,
                                                                         const uint32_t *__restrict__ lde, size_t stride, const uint32_t *__restrict__ cl,
                                                                         size_t c_stride, const uint64_t *__restrict__ w, uint32_t *__restrict__ out,
                                                                         size_t out_stride) {
-    air_xargs_compose_body<VEC>(XD, XNoShared{}, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
+    air_xargs_compose_body<VEC, NEXT>(XD, XNoShared{}, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
 }
 // the sibling a list with a shared lookup takes ("Shared-table lookups"): the tuples travel in SH
-template <bool VEC>
+template <bool VEC, bool NEXT>
 __global__ __launch_bounds__(PERM_BLOCK) void air_xargs_compose_shared_kernel(XArgsDev XD, XSharedDev SH, Fp F, uint64_t N, uint32_t log_B, uint32_t h_m,
                                                                                uint32_t omega_m, uint32_t tau_m, const uint32_t *__restrict__ izt_m,
                                                                                const uint32_t *__restrict__ plog, const uint32_t *__restrict__ pofs,
                                                                                const uint32_t *__restrict__ ptab, const uint32_t *__restrict__ lde, size_t stride,
                                                                                const uint32_t *__restrict__ cl, size_t c_stride, const uint64_t *__restrict__ w,
                                                                                uint32_t *__restrict__ out, size_t out_stride) {
-    air_xargs_compose_body<VEC>(XD, SH, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
+    air_xargs_compose_body<VEC, NEXT>(XD, SH, F, N, log_B, h_m, omega_m, tau_m, izt_m, plog, pofs, ptab, lde, stride, cl, c_stride, w, out, out_stride);
 }
 
 namespace {
@@ -224,14 +250,17 @@ int xargs_columns_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH
     ArgsFlags *d_fl = (ArgsFlags *)(d_tmp + (size_t)XD.A * nb * 16);
     const Fp F = ctx->fs.F;
     const bool vec = n >= 4 && al16(d_trace) && al16(d_c) && !(c_stride & 3) && al16(XD.pvals);
+    const bool next = xargs_dev_any_next(XD, SH);   // a next-row operand somewhere: the NEXT instantiation
     const dim3 grid((uint32_t)nb, XD.A);
     HIP_TRY(ctx, hipMemsetAsync(&d_fl->first, 0xff, 8, ctx->stream));
     {
-        ProfScope ps(ctx, SH ? "xargs_block_shared_kernel" : "xargs_block_kernel", (4.0 * xargs_cols_read(XD, SH) + 16.0 * XD.A) * (double)n);
-        if (SH && vec) xargs_block_shared_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
-        else if (SH) xargs_block_shared_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
-        else if (vec) xargs_block_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
-        else xargs_block_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        ProfScope ps(ctx, SH ? (next ? "xargs_block_shared_kernel<next>" : "xargs_block_shared_kernel") : next ? "xargs_block_kernel<next>" : "xargs_block_kernel", (4.0 * xargs_cols_read(XD, SH) + 16.0 * XD.A) * (double)n);
+        auto shared = vec ? (next ? xargs_block_shared_kernel<true, true> : xargs_block_shared_kernel<true, false>)
+                          : (next ? xargs_block_shared_kernel<false, true> : xargs_block_shared_kernel<false, false>);
+        auto single = vec ? (next ? xargs_block_kernel<true, true> : xargs_block_kernel<true, false>)
+                          : (next ? xargs_block_kernel<false, true> : xargs_block_kernel<false, false>);
+        if (SH) shared<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
+        else single<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, d_trace, n, d_c, c_stride, d_agg, &d_fl->first);
         HIP_TRY(ctx, hipGetLastError());
     }
     ArgsScanDev SD{XD.A, XD.g_m, {}};
@@ -279,19 +308,19 @@ int xargs_compose_enqueue(smi_ctx *ctx, const XArgsDev &XD, const XSharedDev *SH
     const uint64_t groups = A.N / PERM_ROWS, want = (groups + PERM_BLOCK - 1) / PERM_BLOCK, cap = (uint64_t)ctx->num_cus * 8;
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
     const uint32_t tau_m = air_to_m(tau, F.p);
-    ProfScope ps(ctx, SH ? "air_xargs_compose_shared_kernel" : "air_xargs_compose_kernel", (4.0 * xargs_cols_read(XD, SH) + 32.0 * XD.A + 32.0) * (double)A.N);
-    if (SH && vec)
-        air_xargs_compose_shared_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs,
-                                                                                    A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
-    else if (SH)
-        air_xargs_compose_shared_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs,
-                                                                                     A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out, out_stride);
-    else if (vec)
-        air_xargs_compose_kernel<true><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde,
-                                                                             stride, d_cl, c_stride, d_w, d_out, out_stride);
+    const bool next = xargs_dev_any_next(XD, SH);   // a next-row operand somewhere: the NEXT instantiation
+    ProfScope ps(ctx, SH ? (next ? "air_xargs_compose_shared_kernel<next>" : "air_xargs_compose_shared_kernel") : next ? "air_xargs_compose_kernel<next>" : "air_xargs_compose_kernel",
+                 (4.0 * xargs_cols_read(XD, SH) + 32.0 * XD.A + 32.0) * (double)A.N);
+    auto shared = vec ? (next ? air_xargs_compose_shared_kernel<true, true> : air_xargs_compose_shared_kernel<true, false>)
+                      : (next ? air_xargs_compose_shared_kernel<false, true> : air_xargs_compose_shared_kernel<false, false>);
+    auto single = vec ? (next ? air_xargs_compose_kernel<true, true> : air_xargs_compose_kernel<true, false>)
+                      : (next ? air_xargs_compose_kernel<false, true> : air_xargs_compose_kernel<false, false>);
+    if (SH)
+        shared<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, *SH, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde, stride, d_cl, c_stride, d_w,
+                                                     d_out, out_stride);
     else
-        air_xargs_compose_kernel<false><<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde,
-                                                                              stride, d_cl, c_stride, d_w, d_out, out_stride);
+        single<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, F, A.N, A.log_B, A.h_m, A.omega_m, tau_m, A.izt_m, A.plog, A.pofs, A.ptab, d_lde, stride, d_cl, c_stride, d_w, d_out,
+                                                     out_stride);
     HIP_TRY(ctx, hipGetLastError());
     return SMI_OK;
 }
@@ -310,20 +339,21 @@ int xargs_args(smi_ctx *ctx, const smi_air *air, const smi_air_xargs *xargs, uin
     return SMI_OK;
 }
 
-int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
-                                 uint32_t log_n, uint32_t *d_mult) {
-    return smi_dev_xargs_multiplicities_rows(ctx, air_, xargs_, a, d_trace_cols, n_cols, log_n, (size_t)1 << (log_n < 63 ? log_n : 0), d_mult);
-}
-
 // the helper over the first `rows` rows: table rows at and above `rows` are not inserted, lookup rows there are not counted;
-// all n words of d_mult are written (zero where nothing is counted)
-int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
-                                      uint32_t log_n, size_t rows, uint32_t *d_mult) {
+// all n words of d_mult are written (zero where nothing is counted).  bounded: the caller is the entry point with a row bound,
+// which takes this-row operands only (what lies behind the bound is not the caller's successor row)
+static int xargs_multiplicities_run(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                    uint32_t log_n, size_t rows, uint32_t *d_mult, bool bounded) {
     const smi_air *air = (const smi_air *)air_;
     const smi_air_xargs *xargs = (const smi_air_xargs *)xargs_;
     if (!ctx || !air || !xargs || !d_trace_cols || !d_mult) return SMI_ERR_BAD_ARG;
     DeviceGuard dg__(ctx);
     SMI_TRY(xargs_args(ctx, air, xargs, n_cols, log_n));
+    if (bounded) {
+        std::string why;
+        if (xargs_refuse_next(xargs, "xargs_multiplicities_rows", "the helper over a row bound takes this-row operands only", &why) != SMI_OK)
+            return smi_fail(ctx, SMI_ERR_BAD_ARG, why.c_str());
+    }
     if (a >= xargs->count) return smi_fail(ctx, SMI_ERR_BAD_ARG, "xargs_multiplicities: no such argument");
     if ((xargs->arg[a].kind & 0xffu) != SMI_ARG_LOOKUP) {
         const std::string why = "xargs_multiplicities: argument " + std::to_string(a) + " is a permutation: it has no multiplicities";
@@ -350,15 +380,19 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
     HIP_TRY(ctx, hipMemsetAsync(d_mult, 0, n * 4, ctx->stream));
     if (!per.vals.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_pvals, per.vals.data(), per.vals.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     const uint32_t grid = (uint32_t)((rows + PERM_BLOCK - 1) / PERM_BLOCK), m = XD.m[a];
+    const bool next = xargs_dev_any_next(XD, &SH);   // a next-row operand somewhere in the list: the NEXT instantiations
     {
         ProfScope ps(ctx, "xargs_insert_kernel", (4.0 * m + 4.0) * (double)n);
-        xargs_insert_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_fl);
+        (next ? xargs_insert_kernel<true> : xargs_insert_kernel<false>)<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_fl);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
         ProfScope ps(ctx, J > 1 ? "xargs_count_shared_kernel" : "xargs_count_kernel", (4.0 * 2 * m + 8.0) * J * (double)n);
-        if (J > 1) xargs_count_shared_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, SH, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
-        else xargs_count_kernel<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
+        if (J > 1)
+            (next ? xargs_count_shared_kernel<true> : xargs_count_shared_kernel<false>)<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, SH, a, d_trace_cols, n, rows, d_tab,
+                                                                                                                              (uint32_t)cap, d_mult, d_fl);
+        else
+            (next ? xargs_count_kernel<true> : xargs_count_kernel<false>)<<<grid, PERM_BLOCK, 0, ctx->stream>>>(XD, a, d_trace_cols, n, rows, d_tab, (uint32_t)cap, d_mult, d_fl);
         HIP_TRY(ctx, hipGetLastError());
     }
     XHelperFlags fl;
@@ -377,7 +411,14 @@ int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void
     }
     return SMI_OK;
 }
-
+int smi_dev_xargs_multiplicities(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                 uint32_t log_n, uint32_t *d_mult) {
+    return xargs_multiplicities_run(ctx, air_, xargs_, a, d_trace_cols, n_cols, log_n, (size_t)1 << (log_n < 63 ? log_n : 0), d_mult, false);
+}
+int smi_dev_xargs_multiplicities_rows(smi_ctx *ctx, const void *air_, const void *xargs_, uint32_t a, const uint32_t *d_trace_cols, uint32_t n_cols,
+                                      uint32_t log_n, size_t rows, uint32_t *d_mult) {
+    return xargs_multiplicities_run(ctx, air_, xargs_, a, d_trace_cols, n_cols, log_n, rows, d_mult, true);
+}
 
 // ---- what the entry points of both lists run behind their checks (the plain list's are in args.hip).  air: the AIR whose
 // periodic columns the operands may name; nullptr for a plain list, which has no periodic operand: its tables are built

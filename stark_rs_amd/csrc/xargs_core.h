@@ -1,6 +1,7 @@
 // xargs_core.h -- the argument list with selectors and periodic members (include/stark_mi.h, "Argument list with selectors
 // and periodic members"): args_core.h's layer with operands in place of columns.  An operand is a trace column or a periodic
-// column of the AIR; every argument has two optional selectors.  Shared by the HIP kernels (xargs.hip), the verifier
+// column of the AIR, either of them at this row or one row later ("Argument list: next-row operands", XOP_NEXT); every
+// argument has two optional selectors.  Shared by the HIP kernels (xargs.hip), the verifier
 // (verify.hip, host) and the CPU emulator (emu_xargs.cpp), which runs the same lane batching and block split.
 //
 // Number forms are args_core.h's.  A selector cell is a plain residue S: g = 1 + S (f - 1) is formed in Montgomery form
@@ -14,6 +15,7 @@
 #include "deep_core.h"
 
 #define XOP_PER 0x100u   // operand code: trace column c is c (< 64), periodic column j is XOP_PER | j
+#define XOP_NEXT 0x200u  // ... read one row later, cyclically ("Argument list: next-row operands"): SMI_ARG_NEXT_ROW on the device
 
 struct XArgsDev {   // passed to the kernels by value: 960 bytes
     uint32_t A, g_m;
@@ -47,6 +49,25 @@ SMI_HD uint32_t xshared_tuples(const XNoShared &, uint32_t) { return 1u; }
 SMI_HD uint32_t xshared_tuples(const XSharedDev &SH, uint32_t a) { return SH.J[a]; }
 
 SMI_HD bool xop_periodic(uint32_t op) { return (op & XOP_PER) != 0; }
+SMI_HD bool xop_next(uint32_t op) { return (op & XOP_NEXT) != 0; }
+// the operand code of a validated operand v (W = n_cols): SMI_ARG_NO_SELECTOR stays what it is
+inline uint32_t xop_code(uint32_t v, uint32_t W) {
+    if (v == SMI_ARG_NO_SELECTOR) return v;
+    const uint32_t t = v & ~SMI_ARG_NEXT_ROW, c = t < W ? t : (XOP_PER | (t - 2 * W));
+    return (v & SMI_ARG_NEXT_ROW) ? (c | XOP_NEXT) : c;
+}
+// A next-row operand at the lane's four rows at .. at + 3 of a cyclic column of len words (a power of two): the words at + 1 ..
+// at + 4 modulo len.  xargs_next4: len >= 4 and `at` a multiple of 4 below len -- three of the lane's own four words (own)
+// serve, the fourth is one word further and wraps only to word 0.  xargs_next4_words: any len, word by word; a row at or above
+// `rows` gives zero.
+SMI_HD void xargs_next4(const uint32_t *col, uint64_t at, uint64_t len, const uint32_t own[PERM_ROWS], uint32_t v[PERM_ROWS]) {
+    v[0] = own[1], v[1] = own[2], v[2] = own[3];
+    v[3] = col[(at + 4) & (len - 1)];
+}
+SMI_HD void xargs_next4_words(const uint32_t *col, uint64_t at, uint64_t len, uint64_t rows, uint32_t v[PERM_ROWS]) {
+#pragma unroll
+    for (int q = 0; q < PERM_ROWS; q++) v[q] = at + q < rows ? col[(at + q + 1) & (len - 1)] : 0u;
+}
 // the four values of periodic column j at the rows row0 .. row0 + 3 of the trace: v_j[(row0 + q) mod P_j], word by word --
 // with P_j = 1 or 2 the wrap falls inside the lane
 SMI_HD void xargs_periodic_rows(const XArgsDev &XD, uint32_t j, uint64_t row0, uint32_t v[PERM_ROWS]) {
@@ -55,8 +76,14 @@ SMI_HD void xargs_periodic_rows(const XArgsDev &XD, uint32_t j, uint64_t row0, u
 #pragma unroll
     for (int q = 0; q < PERM_ROWS; q++) v[q] = src[(uint32_t)(row0 + q) & mask];
 }
-// one cell of an operand on the trace (the multiplicity helper)
+// one cell of an operand on the trace (the multiplicity helper).  NEXT: the list has a next-row operand, which reads row
+// (row + 1) mod n; without it the codes are bare and nothing here looks at the flag
+template <bool NEXT = false>
 SMI_HD uint32_t xargs_cell(const XArgsDev &XD, const uint32_t *trace, uint64_t n, uint32_t op, uint64_t row) {
+    if (NEXT) {
+        if (xop_next(op)) row = (row + 1) & (n - 1);
+        if (!xop_periodic(op)) op &= 0xffu;
+    }
     if (xop_periodic(op)) return XD.pvals[XD.pfirst[op & 0xffu] + ((uint32_t)row & ((1u << XD.plog[op & 0xffu]) - 1u))];
     return trace[(uint64_t)op * n + row];
 }
@@ -279,34 +306,37 @@ SMI_HD void xargs_lane_column(const XArgsDev &XD, const XNoShared &, uint32_t a,
 // ------------------------------------------------------------------------------------------------ the multiplicity helper
 // lookup_core.h's helper over operands: the hash and the comparison read cells through xargs_cell, an unselected row takes
 // no part.  The hash is lookup_hash's function of the values.
+template <bool NEXT = false>
 SMI_HD uint32_t xlookup_hash(const XArgsDev &XD, const uint32_t *trace, uint64_t n, const uint32_t *ops, uint32_t m, uint64_t row) {
     uint32_t h = 0x9e3779b9u;
     for (uint32_t j = 0; j < m; j++) {
-        h ^= xargs_cell(XD, trace, n, ops[j], row);
+        h ^= xargs_cell<NEXT>(XD, trace, n, ops[j], row);
         h *= 0x85ebca6bu;
         h ^= h >> 15;
     }
     return h;
 }
+template <bool NEXT = false>
 SMI_HD bool xlookup_same(const XArgsDev &XD, const uint32_t *trace, uint64_t n, const uint32_t *aops, uint64_t arow, const uint32_t *bops, uint64_t brow,
                          uint32_t m) {
     for (uint32_t j = 0; j < m; j++)
-        if (xargs_cell(XD, trace, n, aops[j], arow) != xargs_cell(XD, trace, n, bops[j], brow)) return false;
+        if (xargs_cell<NEXT>(XD, trace, n, aops[j], arow) != xargs_cell<NEXT>(XD, trace, n, bops[j], brow)) return false;
     return true;
 }
+template <bool NEXT = false>
 SMI_HD bool xargs_selected(const XArgsDev &XD, const uint32_t *trace, uint64_t n, uint32_t sel, uint64_t row) {
-    return sel == SMI_ARG_NO_SELECTOR || xargs_cell(XD, trace, n, sel, row) != 0;
+    return sel == SMI_ARG_NO_SELECTOR || xargs_cell<NEXT>(XD, trace, n, sel, row) != 0;
 }
 // Insert launch, lane t (lookup_insert_lane): a table row with S_b = 0 is not inserted.
-template <class Atomics>
+template <bool NEXT = false, class Atomics>
 SMI_HD bool xlookup_insert_lane(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, uint32_t *tab, uint32_t cap, uint32_t t, Atomics at) {
-    if (!xargs_selected(XD, trace, n, XD.bsel[a], t)) return true;
+    if (!xargs_selected<NEXT>(XD, trace, n, XD.bsel[a], t)) return true;
     const uint32_t *bops = XD.bop[a], m = XD.m[a];
-    uint32_t slot = xlookup_hash(XD, trace, n, bops, m, t) & (cap - 1);
+    uint32_t slot = xlookup_hash<NEXT>(XD, trace, n, bops, m, t) & (cap - 1);
     for (uint32_t i = 0; i < cap; i++) {
         const uint32_t old = at.cas(tab + slot, LOOKUP_EMPTY, t);
         if (old == LOOKUP_EMPTY) return true;
-        if (xlookup_same(XD, trace, n, bops, old, bops, t, m)) {   // a slot keeps its tuple: any occupant it ever had serves
+        if (xlookup_same<NEXT>(XD, trace, n, bops, old, bops, t, m)) {   // a slot keeps its tuple: any occupant it ever had serves
             at.min(tab + slot, t);
             return true;
         }
@@ -316,16 +346,16 @@ SMI_HD bool xlookup_insert_lane(const XArgsDev &XD, uint32_t a, const uint32_t *
 }
 // Count launch: the probe of one looked-up tuple (operands aops, selector sel) of row r.  0 counted or not selected, 1 the
 // tuple is in no selected table row, 2 the probe ran through the whole table.
-template <class Atomics>
+template <bool NEXT = false, class Atomics>
 SMI_HD int xlookup_count_tuple(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *aops, uint32_t sel, const uint32_t *tab,
                                uint32_t cap, uint32_t r, uint32_t *mult, Atomics at) {
-    if (!xargs_selected(XD, trace, n, sel, r)) return 0;
+    if (!xargs_selected<NEXT>(XD, trace, n, sel, r)) return 0;
     const uint32_t *bops = XD.bop[a], m = XD.m[a];
-    uint32_t slot = xlookup_hash(XD, trace, n, aops, m, r) & (cap - 1);
+    uint32_t slot = xlookup_hash<NEXT>(XD, trace, n, aops, m, r) & (cap - 1);
     for (uint32_t i = 0; i < cap; i++) {
         const uint32_t t = tab[slot];
         if (t == LOOKUP_EMPTY) return 1;
-        if (xlookup_same(XD, trace, n, bops, t, aops, r, m)) {
+        if (xlookup_same<NEXT>(XD, trace, n, bops, t, aops, r, m)) {
             at.add(mult + t, 1u);
             return 0;
         }
@@ -334,19 +364,19 @@ SMI_HD int xlookup_count_tuple(const XArgsDev &XD, uint32_t a, const uint32_t *t
     return 2;
 }
 // Count launch, lane r (lookup_count_lane): the statuses of xlookup_count_tuple for the argument's one tuple.
-template <class Atomics>
+template <bool NEXT = false, class Atomics>
 SMI_HD int xlookup_count_lane(const XArgsDev &XD, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *tab, uint32_t cap, uint32_t r,
                               uint32_t *mult, Atomics at) {
-    return xlookup_count_tuple(XD, a, trace, n, XD.aop[a], XD.asel[a], tab, cap, r, mult, at);
+    return xlookup_count_tuple<NEXT>(XD, a, trace, n, XD.aop[a], XD.asel[a], tab, cap, r, mult, at);
 }
 // Count launch of a shared lookup, lane r: one probe per selected tuple of the row, so M[t] counts the (row, tuple) pairs
 // that hit table row t.  -> bit 0: some tuple is missing, *miss = the smallest such j; bit 1: a probe ran through the table.
-template <class Atomics>
+template <bool NEXT = false, class Atomics>
 SMI_HD int xshared_count_lane(const XArgsDev &XD, const XSharedDev &SH, uint32_t a, const uint32_t *trace, uint64_t n, const uint32_t *tab, uint32_t cap,
                               uint32_t r, uint32_t *mult, Atomics at, uint32_t *miss) {
     int out = 0;
     for (uint32_t j = 0; j < SH.J[a]; j++) {
-        const int got = xlookup_count_tuple(XD, a, trace, n, SH.op[a][j], SH.sel[a][j], tab, cap, r, mult, at);
+        const int got = xlookup_count_tuple<NEXT>(XD, a, trace, n, SH.op[a][j], SH.sel[a][j], tab, cap, r, mult, at);
         if (got == 1 && !(out & 1)) *miss = j, out |= 1;
         if (got == 2) out |= 2;
     }
@@ -518,6 +548,7 @@ inline int xargs_validate(const smi_air_xargs *xargs, uint32_t W, uint32_t Q, st
         const smi_air_xarg &g = xargs->arg[a];
         const std::string who = "xargs: argument " + std::to_string(a) + ": ";
         auto operand = [&](uint32_t v, const char *what) -> std::string {
+            v &= ~SMI_ARG_NEXT_ROW;   // "Argument list: next-row operands": the flag on a this-row variable; nothing else gains from it
             if (v < W || (v >= 2 * W && v < 2 * W + Q)) return "";
             if (v < 2 * W || v < 2 * W + 2 * Q) return std::string(what) + " is a next-row variable: only this-row operands (c < n_cols, or 2 n_cols + j)";
             return std::string(what) + " must be a variable of the AIR (< 2 n_cols + 2 n_periodic)";
@@ -549,18 +580,62 @@ inline int xargs_validate(const smi_air_xargs *xargs, uint32_t W, uint32_t Q, st
                 if (!e.empty()) return fail(who + e);
             }
         if (kind == SMI_ARG_LOOKUP) {
+            auto bare = [](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v & ~SMI_ARG_NEXT_ROW; };   // next(mult_col) is mult_col here
             if (g.mult_col >= W) return fail(who + "mult_col must be < n_cols");
             for (uint32_t j = 0; j < J * g.width; j++)
-                if (g.a_var[j] == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
+                if (bare(g.a_var[j]) == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
             for (uint32_t j = 0; j < g.width; j++)
-                if (g.b_var[j] == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
-            if (g.a_sel == g.mult_col || g.b_sel == g.mult_col) return fail(who + "mult_col must be none of the selectors");
+                if (bare(g.b_var[j]) == g.mult_col) return fail(who + "mult_col must be none of the tuple operands");
+            if (bare(g.a_sel) == g.mult_col || bare(g.b_sel) == g.mult_col) return fail(who + "mult_col must be none of the selectors");
             for (uint32_t j = 0; J > 1 && j < J; j++)
-                if (g.a_var[J * g.width + j] == g.mult_col) return fail(who + "mult_col must be none of the selectors");
+                if (bare(g.a_var[J * g.width + j]) == g.mult_col) return fail(who + "mult_col must be none of the selectors");
         }
     }
     return SMI_OK;
 }
+// "Argument list: next-row operands".  The first next-row operand of the list as "argument a: what", or "" -- who takes no
+// such list (the zero-knowledge variants, the helper over a row bound) refuses with xargs_refuse_next's sentence.
+inline std::string xargs_first_next(const smi_air_xargs *xargs) {
+    for (uint32_t a = 0; a < xargs->count; a++) {
+        const smi_air_xarg &g = xargs->arg[a];
+        const uint32_t J = xarg_tuples(g);
+        auto next = [](uint32_t v) { return v != SMI_ARG_NO_SELECTOR && (v & SMI_ARG_NEXT_ROW); };
+        const char *what = nullptr;
+        for (uint32_t j = 0; j < J * g.width && !what; j++)
+            if (next(g.a_var[j])) what = "a_var";
+        for (uint32_t j = 0; j < g.width && !what; j++)
+            if (next(g.b_var[j])) what = "b_var";
+        for (uint32_t j = 0; J > 1 && j < J && !what; j++)
+            if (next(g.a_var[J * g.width + j])) what = "a tuple selector";
+        if (!what && next(g.a_sel)) what = "a_sel";
+        if (!what && next(g.b_sel)) what = "b_sel";
+        if (what) return "argument " + std::to_string(a) + ": " + what;
+    }
+    return "";
+}
+inline bool xargs_any_next(const smi_air_xargs *xargs) { return !xargs_first_next(xargs).empty(); }
+// a validated list: SMI_OK, or SMI_ERR_BAD_ARG with "<who>: argument a: <what> is a next-row operand: <reason>"
+inline int xargs_refuse_next(const smi_air_xargs *xargs, const char *who, const char *reason, std::string *why) {
+    const std::string at = xargs_first_next(xargs);
+    if (at.empty()) return SMI_OK;
+    if (why) *why = std::string(who) + ": " + at + " is a next-row operand: " + reason;
+    return SMI_ERR_BAD_ARG;
+}
+// the same question of the kernels' tables: which instantiation a launch takes
+inline bool xargs_dev_any_next(const XArgsDev &XD, const XSharedDev *SH) {
+    auto next = [](uint32_t op) { return op != SMI_ARG_NO_SELECTOR && xop_next(op); };
+    for (uint32_t a = 0; a < XD.A; a++) {
+        bool any = next(XD.asel[a]) || next(XD.bsel[a]);
+        for (uint32_t j = 0; j < XD.m[a]; j++) any = any || next(XD.aop[a][j]) || next(XD.bop[a][j]);
+        for (uint32_t t = 0; SH && t < SH->J[a]; t++) {
+            any = any || next(SH->sel[a][t]);
+            for (uint32_t j = 0; j < XD.m[a]; j++) any = any || next(SH->op[a][t][j]);
+        }
+        if (any) return true;
+    }
+    return false;
+}
+
 // the bound of a shared lookup that needs the trace length: M counts (row, tuple) pairs, up to J n of them in one cell, and
 // must stay below p.  (J = 1: n divides p - 1.)
 inline int xargs_shared_rows(uint64_t p, const smi_air_xargs *xargs, uint32_t log_n, std::string *why) {
@@ -642,7 +717,7 @@ inline void xargs_build(const Fp &F, uint32_t g, const smi_air_xargs *xargs, uin
     for (uint32_t j = 0; j < SMI_PERM_MAX_WIDTH; j++)
         for (int e = 0; e < 4; e++) XD->apow_mm[j][e] = PD.apow_mm[j][e];
     for (int e = 0; e < 4; e++) XD->gamma_m[e] = PD.gamma_m[e];
-    auto code = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v < W ? v : (XOP_PER | (v - 2 * W)); };
+    auto code = [&](uint32_t v) { return xop_code(v, W); };
     for (uint32_t a = 0; a < xargs->count; a++) {
         const smi_air_xarg &s = xargs->arg[a];
         XD->kind[a] = s.kind & 0xffu;
@@ -679,7 +754,7 @@ struct XArgsOfPlain {
 };
 // the tuples of a validated list as the shared instantiations read them; -> does the list have a shared lookup at all?
 inline bool xshared_build(const smi_air_xargs *xargs, uint32_t W, XSharedDev *SH) {
-    auto code = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? v : v < W ? v : (XOP_PER | (v - 2 * W)); };
+    auto code = [&](uint32_t v) { return xop_code(v, W); };
     *SH = XSharedDev{};
     bool any = false;
     for (uint32_t a = 0; a < xargs->count; a++) {
@@ -742,10 +817,17 @@ inline int deep_xargs_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *
 // The two auxiliary quotients of argument g at a point z outside F_p, over F_q operands: what XArgAux (verify.hip) computes
 // from an opened row at a point of the coset, with u[c] = f_c(z) for a trace operand c, per[j] = pi_j(z) for a periodic
 // operand, ca = c_a(z), cb = c_a(z w).  alpha, gamma: the shared challenges; ixt = 1 / (z - tau), izt = 1 / (z^n - tau^n).
+// un[c] = f_c(z w) and pern[j] = pi_j(z w): what a next-row operand reads ("Argument list: next-row operands"); a caller
+// whose lists have none (the zero-knowledge variant refuses them in its plan) passes nullptr.
 inline void xargs_aux_at_z(uint32_t p, uint32_t g, uint32_t W, const smi_air_xarg &arg, const FqH &alpha, const FqH &gamma, const FqH *u, const FqH *per,
-                           const FqH &ca, const FqH &cb, const FqH &ixt, const FqH &izt, FqH *bq, FqH *wq) {
+                           const FqH *un, const FqH *pern, const FqH &ca, const FqH &cb, const FqH &ixt, const FqH &izt, FqH *bq, FqH *wq) {
     const FqH one = fqh(1 % p);
-    auto val = [&](uint32_t v) { return v == SMI_ARG_NO_SELECTOR ? one : v < W ? u[v] : per[v - 2 * W]; };
+    auto val = [&](uint32_t v) {
+        if (v == SMI_ARG_NO_SELECTOR) return one;
+        const bool next = (v & SMI_ARG_NEXT_ROW) != 0;
+        v &= ~SMI_ARG_NEXT_ROW;
+        return v < W ? (next ? un : u)[v] : (next ? pern : per)[v - 2 * W];
+    };
     const uint32_t J = xarg_tuples(arg), m = arg.width;
     if (J > 1) {   // (s' - s) P f_T - Nn f_T + M S_b P over the fold of the tuples
         FqH P = one, Nn = fqh(0), ft = gamma, pw = one;
@@ -800,10 +882,13 @@ inline void deep_xargs_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cf
     std::vector<uint64_t> plain(ood, ood + 8 * (size_t)W);   // u, v, s: the record of the plain variant
     plain.insert(plain.end(), ood + 4 * (2 * (size_t)W + 2 * (size_t)A), ood + deep_args_record(W, A, D));
     deep_ood_sides(p, g, cfg, air, D, w_n, weights, z, plain.data(), lhs, rhs);
-    std::vector<FqH> u(W), per(Q);
-    for (uint32_t c = 0; c < W; c++) u[c] = fqh_of(ood + 4 * (size_t)c, p);
-    for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++)
+    std::vector<FqH> u(W), per(Q), un(W), pern(Q);   // at z, and at z w for the next-row operands
+    const FqH zw = fqh_scale(z, w_n, p);
+    for (uint32_t c = 0; c < W; c++) u[c] = fqh_of(ood + 4 * (size_t)c, p), un[c] = fqh_of(ood + 4 * ((size_t)W + c), p);
+    for (uint32_t j = 0, at = 0; j < Q; at += 1u << air->periodic_log_period[j], j++) {
         per[j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, z, p, g);
+        pern[j] = deep_periodic_at(air, j, air->periodic_value + at, cfg->log_n, tau, w_n, zw, p, g);
+    }
     uint32_t al[4], ga[4];
     perm_challenges(p, ch, al, ga);
     const FqH alpha{{al[0], al[1], al[2], al[3]}}, gamma{{ga[0], ga[1], ga[2], ga[3]}};
@@ -812,7 +897,7 @@ inline void deep_xargs_ood_sides(uint32_t p, uint32_t g, const smi_stark_cfg *cf
     FqH acc = *lhs;
     for (uint32_t a = 0; a < A; a++) {
         FqH bq, wq;
-        xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), fqh_of(ood + 4 * (2 * (size_t)W + a), p),
+        xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), un.data(), pern.data(), fqh_of(ood + 4 * (2 * (size_t)W + a), p),
                        fqh_of(ood + 4 * (2 * (size_t)W + A + a), p), ixt, izt, &bq, &wq);
         const uint64_t *wa = weights + 4 * ((size_t)W + K + 2 * (size_t)a);
         acc = fqh_add(acc, fqh_add(fqh_mul(fqh_of(wa, p), bq, p, g), fqh_mul(fqh_of(wa + 4, p), wq, p, g), p), p);

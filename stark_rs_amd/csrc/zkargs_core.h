@@ -181,6 +181,9 @@ inline int zkx_plan(uint64_t p, const smi_stark_cfg *cfg, const smi_air *air, co
     if (rc != SMI_OK) return rc;
     rc = xargs_validate(xargs, cfg->n_cols, air->n_periodic, why);
     if (rc != SMI_OK) return rc;
+    // "Argument list: next-row operands": the row after the last active row is random under zero knowledge
+    rc = xargs_refuse_next(xargs, "zk deep argument", "the zero-knowledge proofs take this-row operands only (the row after the last active row is random)", why);
+    if (rc != SMI_OK) return rc;
     if ((p & 3) != 1) return fail(SMI_ERR_BAD_ARG, "xargs: p = 3 (mod 4): the quartic extension does not exist");
     uint32_t d = 0;
     rc = air_validate(p, cfg, &Z.air, &d, nullptr, why, false, true);
@@ -254,7 +257,7 @@ inline FqH zkx_ood_lhs(uint32_t p, uint32_t g, const smi_stark_cfg *cfg, const s
     for (uint32_t a = 0; a < A; a++) {
         const FqH ca = fqh_of(ood + 4 * (2 * (size_t)W + a), p), cb = fqh_of(ood + 4 * (2 * (size_t)W + A + a), p);
         FqH bq, wq;
-        xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), ca, cb, ixt, izt, &bq, &wq);
+        xargs_aux_at_z(p, g, W, xargs->arg[a], alpha, gamma, u.data(), per.data(), nullptr, nullptr, ca, cb, ixt, izt, &bq, &wq);   // no next-row operand: zkx_plan
         wq = fqh_mul(wq, ea, p, g);
         const FqH init = fqh((xargs->arg[a].kind & 0xffu) == SMI_ARG_PERM ? 1 % p : 0);
         const FqH cq = fqh_mul(fqh_sub(ca, init, p), ict, p, g);

@@ -835,6 +835,9 @@ class Air:
     "Argument list with selectors and periodic members"):
         flag, rng = 3, air.periodic(range(256))
         air.add_lookup([0], [("per", rng)], 2, sel=flag)         # on the rows with c3 = 1, c0[r] is in 0 .. 255; c2 counts
+    A member or selector may also be read one row later, cyclically (include/stark_mi.h, "Argument list: next-row operands"):
+    ("next", c) for trace column c, ("next", ("per", j)) for periodic column j:
+        air.add_lookup([0, 1, ("next", 0)], [("per", s), ("per", i), ("per", nx)], 2, sel=("per", live))   # a table-driven transition
     A list with such an argument takes the smi_*_xargs entry points; any other list the smi_*_args ones, as before."""
 
     def __init__(self, n_cols):
@@ -939,12 +942,16 @@ class Air:
 
     @staticmethod
     def _operand(x, what, none_ok=False):
-        """a member or selector of an argument: an int (trace column) or ("per", j) (periodic column j)"""
+        """a member or selector of an argument: an int (trace column), ("per", j) (periodic column j), or either of them one
+        row later, cyclically: ("next", c) / ("next", ("per", j)) (include/stark_mi.h, "Argument list: next-row operands")"""
         if x is None and none_ok:
             return None
         if isinstance(x, tuple):
+            if len(x) == 2 and x[0] == "next" and not (isinstance(x[1], tuple) and x[1][:1] == ("next",)):
+                return ("next", Air._operand(x[1], what))
             if len(x) != 2 or x[0] != "per":
-                raise ValueError(f"{what}: an operand is a trace column or (\"per\", j), not {x!r} (next-row members are not supported)")
+                raise ValueError(f"{what}: an operand is a trace column, (\"per\", j), or (\"next\", either), not {x!r} "
+                                 "(a next-row operand is spelt (\"next\", c) or (\"next\", (\"per\", j)))")
             return ("per", int(x[1]))
         return int(x)
 
@@ -1113,7 +1120,14 @@ class Air:
         out.args = out.xargs = None
         if self.extended_args or (self.args and self.xargs_always):
             W = self.n_cols
-            var = lambda c: _lib.NO_SELECTOR if c is None else (2 * W + c[1]) % (1 << 32) if isinstance(c, tuple) else c % (1 << 32)
+
+            def var(c):
+                if c is None:
+                    return _lib.NO_SELECTOR
+                if isinstance(c, tuple) and c[0] == "next":   # SMI_ARG_NEXT_ROW on a this-row variable
+                    return _lib.ARG_NEXT_ROW | var(c[1])
+                return (2 * W + c[1]) % (1 << 32) if isinstance(c, tuple) else c % (1 << 32)
+
             keep, raw = [], (_lib.AirXArg * len(self.args))()
             for a, arg in enumerate(self.args):
                 if arg[0] == "lookups":   # J m operands, tuple-major, then the J selectors; J - 1 in the second byte of kind

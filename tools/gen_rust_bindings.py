@@ -192,7 +192,7 @@ def generate():
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     for m in re.finditer(r"#define (SMI_ARGS_MAX|SMI_ARG_[A-Z]+) (\d+)", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
-    for m in re.finditer(r"#define (SMI_ARG_NO_SELECTOR) (0x[0-9a-f]+)u", text):
+    for m in re.finditer(r"#define (SMI_ARG_NO_SELECTOR|SMI_ARG_NEXT_ROW) (0x[0-9a-f]+)u", text):
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
     for m in re.finditer(r"#define (SMI_ARG_MAX_TUPLES|SMI_ARG_TUPLES_SHIFT) +(\d+)", text):   # "Shared-table lookups": aligned with spaces
         lines.append(f"pub const {m.group(1)}: u32 = {m.group(2)};")
